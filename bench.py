@@ -13,6 +13,12 @@ reported in T=1000-equivalent evaluations per second: intervals processed by all
 
 Each step writes into the next of a ring of output buffers whose total exceeds 2 x 256 MiB, so a
 step's stores cannot be absorbed by the Infinity Cache across steps ("Measurement").
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds every side
+measurement (CPU baseline, per-launch event pairs, mu_d2F and the other device legs, host-visible
+calls, configs 4 and 5, the exponential integrator, the all-gather at N > 1).  `--dump-outputs DIR`
+writes the last timed step's F and Jacobian values to DIR/*.npy (inputs are seeded: two builds
+compare output for output).
 """
 from __future__ import annotations
 
@@ -67,6 +73,24 @@ def usable_cores() -> int:
     except Exception:
         pass
     return max(1, n)
+
+
+DUMP_BYTES = 60 * 10**6      # --dump-outputs: all arrays together (headers aside), under 64 MB
+DUMP_SEED = 20250218
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """Write each device vector of `arrays` ({name: 1-D float64 tensor}) to out_dir/<name>.npy as float64.  When they hold more than
+    `budget` bytes together, each is replaced by its entries at a fixed, seeded set of sorted indices, in proportion to its length."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(int(t.numel()) for t in arrays.values())
+    for k, (name, t) in enumerate(arrays.items()):
+        n = int(t.numel())
+        if 8 * total > budget:
+            want = max(1, n * (budget // 8) // total)
+            idx = np.unique(np.random.default_rng(DUMP_SEED + k).integers(0, n, size=want))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().cpu().numpy().astype(np.float64, copy=False))
 
 
 def cpu_baseline(qc, inp, seconds: float):
@@ -596,29 +620,41 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (CPU baseline, per-launch event pairs, one output buffer, mu_d2F / F alone / one call, "
+                         "host-visible calls, configs 4 and 5, the exponential integrator, the all-gather at N > 1); a plain run times the metric only. "
+                         "Each side measurement's own option below overrides this either way")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed (residual F, Jacobian values dF) as DIR/<name>.npy, "
+                         "float64; a fixed, seeded sample of each array where all of them would exceed 64 MB")
     ap.add_argument("--side-steps", type=int, default=SIDE_STEPS, help="launches per timed side leg (2000-launch windows read the same: profiles/NOTES.md)")
     ap.add_argument("--prewarm-seconds", type=float, default=0.25,
                     help="untimed launches before the W warm-up steps (output ring touched, clocks up); 0: one pass over the ring only")
     ap.add_argument("--config", type=int, default=3, help="BASELINE config id (3 = metric workload)")
     ap.add_argument("--T", type=int, default=0, help="knots per GPU (default: the config's own T)")
     ap.add_argument("--kernel", default="auto", choices=["auto", "lds", "mfma"])
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="0 disables the CPU baseline leg")
-    ap.add_argument("--hessian", action=argparse.BooleanOptionalAction, default=True,
-                    help="also time mu_d2F and F alone and report the ms/Ipopt-iter proxy of the metric (extra fields)")
-    ap.add_argument("--allgather", dest="allgather", action="store_true", default=True,
-                    help="at N > 1 also time the RCCL all-gather of the value blocks (default; reported beside the metric, never part of it)")
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="budget of the CPU baseline leg (default: 12 with --full, else 0); 0 disables it")
+    ap.add_argument("--hessian", action=argparse.BooleanOptionalAction, default=None,
+                    help="also time mu_d2F and F alone and report the ms/Ipopt-iter proxy of the metric (extra fields; default: --full)")
+    ap.add_argument("--allgather", dest="allgather", action="store_true", default=None,
+                    help="at N > 1 also time the RCCL all-gather of the value blocks (default: --full; reported beside the metric, never part of it)")
     ap.add_argument("--no-allgather", dest="allgather", action="store_false")
     ap.add_argument("--streams", type=int, default=0, help="also time the same steps issued round-robin on S streams "
                     "(independent evaluations overlapping their launch/drain phases; reported as an extra field, never `value`)")
-    ap.add_argument("--host-visible", action=argparse.BooleanOptionalAction, default=True,
-                    help="also time the host-buffer entry points (PCIe-inclusive; the `host_visible` object, never `value`)")
-    ap.add_argument("--config4", action=argparse.BooleanOptionalAction, default=True,
-                    help="at N = 1 also run BASELINE config 4's T = 8000 trajectory on the one device (`config4_one_gpu` object)")
-    ap.add_argument("--exponential", action=argparse.BooleanOptionalAction, default=True,
-                    help="at N = 1 also time the metric workload with the exponential integrator (`exponential_integrator` object)")
-    ap.add_argument("--config5", action=argparse.BooleanOptionalAction, default=True,
-                    help="at N = 1 also run BASELINE config 5 on the device and report its HBM / MFMA fractions (`config5` object)")
+    ap.add_argument("--host-visible", action=argparse.BooleanOptionalAction, default=None,
+                    help="also time the host-buffer entry points (PCIe-inclusive; the `host_visible` object, never `value`; default: --full)")
+    ap.add_argument("--config4", action=argparse.BooleanOptionalAction, default=None,
+                    help="at N = 1 also run BASELINE config 4's T = 8000 trajectory on the one device (`config4_one_gpu` object; default: --full)")
+    ap.add_argument("--exponential", action=argparse.BooleanOptionalAction, default=None,
+                    help="at N = 1 also time the metric workload with the exponential integrator (`exponential_integrator` object; default: --full)")
+    ap.add_argument("--config5", action=argparse.BooleanOptionalAction, default=None,
+                    help="at N = 1 also run BASELINE config 5 on the device and report its HBM / MFMA fractions (`config5` object; default: --full)")
     args = ap.parse_args()
+    if args.cpu_seconds is None:
+        args.cpu_seconds = 12.0 if args.full else 0.0
+    for name in ("hessian", "allgather", "host_visible", "config4", "exponential", "config5"):
+        if getattr(args, name) is None:
+            setattr(args, name, args.full)
     SIDE_STEPS = max(1, args.side_steps)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -735,34 +771,42 @@ def main():
         tt = torch.tensor([elapsed, stream_ms], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, stream_ms_max = float(tt[0].item()), float(tt[1].item())
+    dumped = None
+    if args.dump_outputs:
+        # the last timed step's slot of the ring, copied on the device before any later launch can overwrite it
+        last = (args.steps - 1) % nbuf
+        sfx = f"_rank{rank}" if world > 1 else ""
+        dumped = {"F" + sfx: Fb[last].clone(), "dF" + sfx: Jb[last].clone()}
 
-    # kernel duration: HIP event pair around each launch, on the launch stream, same steps
-    kn = min(args.steps, 400)
-    pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(kn)]
-    torch.cuda.synchronize()
-    for i, (a, b) in enumerate(pairs):
-        a.record(stream)
-        step(i)
-        b.record(stream)
-    torch.cuda.synchronize()
-    pair_us = np.array([a.elapsed_time(b) for a, b in pairs]) * 1e3
-    kernel_us_pairs = float(np.median(pair_us))
     kernel_us_stream = stream_ms * 1e3 / args.steps   # includes the inter-kernel boundary
-
+    kernel_us_pairs = None
     extra = {}
-    # What a device-resident consumer that reuses ONE output vector sees (the 43 MB stay in the Infinity Cache): informational,
-    # never `value` -- the timed region above cycles a ring of output buffers precisely so that no step is absorbed by the cache.
-    s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    one = dyn.bind_F_dF_device(Zs[0], Fb[0], Jb[0], stream)
-    for _ in range(50):
-        one()
-    torch.cuda.synchronize()
-    s0.record(stream)
-    for _ in range(SIDE_STEPS):
-        one()
-    s1.record(stream)
-    torch.cuda.synchronize()
-    extra["step_us_one_output_buffer"] = s0.elapsed_time(s1) * 1e3 / SIDE_STEPS
+    if args.full:
+        # kernel duration: HIP event pair around each launch, on the launch stream, same steps
+        kn = min(args.steps, 400)
+        pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(kn)]
+        torch.cuda.synchronize()
+        for i, (a, b) in enumerate(pairs):
+            a.record(stream)
+            step(i)
+            b.record(stream)
+        torch.cuda.synchronize()
+        pair_us = np.array([a.elapsed_time(b) for a, b in pairs]) * 1e3
+        kernel_us_pairs = float(np.median(pair_us))
+
+        # What a device-resident consumer that reuses ONE output vector sees (the 43 MB stay in the Infinity Cache): informational,
+        # never `value` -- the timed region above cycles a ring of output buffers precisely so that no step is absorbed by the cache.
+        s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        one = dyn.bind_F_dF_device(Zs[0], Fb[0], Jb[0], stream)
+        for _ in range(50):
+            one()
+        torch.cuda.synchronize()
+        s0.record(stream)
+        for _ in range(SIDE_STEPS):
+            one()
+        s1.record(stream)
+        torch.cuda.synchronize()
+        extra["step_us_one_output_buffer"] = s0.elapsed_time(s1) * 1e3 / SIDE_STEPS
     if args.hessian and dims.hess_nnz:
         mu = torch.from_numpy(rng.standard_normal(int(dims.n_rows))).to(dev)
         # a ring of value vectors beyond 2 x the Infinity Cache, like the F + dF outputs (one vector would stay cache-resident)
@@ -877,8 +921,8 @@ def main():
     total_intervals = (T_total - 1)
     t1000_equiv = total_intervals / (T_PER_GPU - 1) if args.config in (3, 4) else float(world)
     host_rec = None
-    Zhs = [Zh + (1e-3 * k) * rng.standard_normal(Zh.size) for k in range(3)]     # the host-buffer calls get a different vector each time
     if args.host_visible:
+        Zhs = [Zh + (1e-3 * k) * rng.standard_normal(Zh.size) for k in range(3)]     # the host-buffer calls get a different vector each time
         try:
             if world == 1:
                 # a handle of its own in the bindings' default layout: mu_d2F_structure is the reference's, entry for entry
@@ -931,6 +975,8 @@ def main():
         except Exception as exc:   # noqa: BLE001
             c4 = {"error": repr(exc)[:300]}
 
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped, DUMP_BYTES // world)
     value = args.steps * t1000_equiv / elapsed
     if rank == 0:
         traffic, traffic_note = recorded_traffic(dyn.kernel, args.config, t_per_gpu)
@@ -963,9 +1009,10 @@ def main():
                          # step and the closing synchronize included), so that the line can be checked against itself
                          "frac_wall": bytes_per_launch / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS,
                          "traffic": traffic, "traffic_source": traffic_note,
-                         "algorithmic_bytes_per_launch": bytes_per_launch,
-                         "kernel_us_event_pairs": kernel_us_pairs, "step_us_stream_events": kernel_us_stream},
+                         "algorithmic_bytes_per_launch": bytes_per_launch, "step_us_stream_events": kernel_us_stream},
         }
+        if kernel_us_pairs is not None:
+            line["roofline"]["kernel_us_event_pairs"] = kernel_us_pairs
         if world > 1:
             # whole job against N devices' HBM: every rank's launch moves the same algorithmic bytes (equal shards); the slowest
             # rank's stream-event step time is the job's

@@ -9,7 +9,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for cfg in 3 5; do
   rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_F64 SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $OUT/cfg$cfg -- \
-      python3 $R/bench.py --config $cfg --steps 100 --warmup 10 --cpu-seconds 0 > $OUT/bench_cfg$cfg.json 2> $OUT/cfg$cfg.log
+      python3 $R/bench.py --full --config $cfg --steps 100 --warmup 10 --cpu-seconds 0 > $OUT/bench_cfg$cfg.json 2> $OUT/cfg$cfg.log
 done
 python3 - <<PY
 import csv, glob, json, collections

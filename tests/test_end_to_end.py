@@ -68,7 +68,7 @@ def test_bench_line_keeps_the_driver_contract():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3", "--cpu-seconds", "0.6",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3", "--full", "--cpu-seconds", "0.6",
                         "--prewarm-seconds", "0", "--no-config5"], capture_output=True, text=True, timeout=600, check=True, cwd=root)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-500:]
@@ -102,7 +102,7 @@ def test_bench_line_at_two_ranks_is_complete():
     # started the way the driver starts its N = 1 run -- no launcher on the command line: bench.py starts its own ranks as a child
     # `python -m torch.distributed.run` (launch_ranks) and passes the line and the exit code through
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full",
                         "--cpu-seconds", "0.6", "--prewarm-seconds", "0"], capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-1500:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -117,6 +117,59 @@ def test_bench_line_at_two_ranks_is_complete():
     import torch
     assert hv["devices"] == [r % torch.cuda.device_count() for r in range(2)] and hv["speedup_vs_cpu_baseline"] > 0 and hv["host_expand_GBps"] > 0 and hv["evals_per_s_T1000_equivalent"] > 0
     assert set(hv["closure_ms"]) == {"F", "dF", "F_dF", "hess"} == set(hv["closure_fresh_ms"])
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_its_dumped_outputs(qc, tmp_path):
+    """A plain `python bench.py --gpus 1 --steps K --warmup W` times the metric and nothing else (the side measurements are behind
+    --full), and `--dump-outputs DIR` writes what the last timed step computed: at K = 5 that step evaluated the unperturbed
+    trajectory of the seeded workload, so the files hold F and the Jacobian values of config 3 at T = 1000."""
+    import json
+    import subprocess
+
+    import numpy as np
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, check=True, cwd=ROOT)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-500:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["higher_is_better"] is True and d["dtype"] == "f64" and d["unit"].startswith("evals/s")
+    assert d["value"] > 1e4 and abs(d["value"] * d["ms_per_step"] * 1e-3 - 1.0) < 1e-6
+    for side in ("cpu_baseline", "host_visible", "config4_one_gpu", "config5", "exponential_integrator", "hess_us", "step_us_one_output_buffer"):
+        assert side not in d, side
+    assert "kernel_us_event_pairs" not in d["roofline"] and d["roofline"]["step_us_stream_events"] > 0
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ["F.npy", "dF.npy"] and sum(p.stat().st_size for p in out.iterdir()) <= 64 * 10**6
+    F, J = np.load(out / "F.npy"), np.load(out / "dF.npy")
+    inp = qc.config_inputs(3, T=1000)
+    dyn = qc.QuantumDynamics(inp.integrators, inp.traj)
+    F_ref, J_ref = dyn.F_dF(inp.traj.datavec)
+    dyn.close()
+    assert F.dtype == np.float64 and J.dtype == np.float64 and F.shape == F_ref.shape and J.shape == J_ref.shape
+    np.testing.assert_allclose(F, F_ref, rtol=1e-12, atol=1e-14)
+    np.testing.assert_allclose(J, J_ref, rtol=1e-12, atol=1e-14)
+
+
+def test_bench_dump_samples_large_outputs_reproducibly(tmp_path):
+    """bench.dump_outputs: arrays within the budget are written whole; beyond it each one is a fixed, seeded sample of its entries
+    (sorted indices, in proportion to its length) that is the same from run to run and keeps the files within the budget."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    a = torch.arange(1000, dtype=torch.float64)
+    b = torch.linspace(-1.0, 1.0, 3000, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "whole"), {"a": a, "b": b}, budget=8 * 4000)
+    np.testing.assert_array_equal(np.load(tmp_path / "whole" / "a.npy"), a.numpy())
+    np.testing.assert_array_equal(np.load(tmp_path / "whole" / "b.npy"), b.numpy())
+    for run in ("one", "two"):
+        bench.dump_outputs(str(tmp_path / run), {"a": a, "b": b}, budget=8 * 400)
+    sa, sb = np.load(tmp_path / "one" / "a.npy"), np.load(tmp_path / "one" / "b.npy")
+    assert sa.dtype == np.float64 and 0 < sa.size <= 100 and 0 < sb.size <= 300 and sa.size + sb.size <= 400
+    assert np.all(np.diff(sa) > 0) and np.all(np.isin(sa, a.numpy())) and np.all(np.isin(sb, b.numpy()))
+    np.testing.assert_array_equal(sa, np.load(tmp_path / "two" / "a.npy"))
+    np.testing.assert_array_equal(sb, np.load(tmp_path / "two" / "b.npy"))
 
 
 def test_bench_without_a_launcher_starts_its_own_ranks(tmp_path):
