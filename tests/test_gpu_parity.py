@@ -399,7 +399,7 @@ def test_hessian_layouts_fixed_time_nonhermitian(qc, oracle, layout, free_time):
     h.close()
 
 
-def test_hessian_fixture_golden_and_exponential_unsupported(qc, oracle):
+def test_hessian_fixture_golden(qc, oracle):
     with open(os.path.join(GOLD, "named_trajectory_type_1.json")) as f:
         fx = json.load(f)
     gold = np.load(os.path.join(GOLD, "fixture_outputs.npz"))
@@ -2010,7 +2010,7 @@ def test_derivative_integrator_counts_and_sizes(qc, oracle, N, m, dims):
         h.close()
 
 
-@pytest.mark.parametrize("case", ["cfg3", "cfg3_long", "cfg2_fixed_dt", "cfg5", "exp3", "order6", "qutrit_lds"])
+@pytest.mark.parametrize("case", ["cfg3", "cfg3_long", "cfg2_fixed_dt", "cfg5", "exp3", "exp3_long", "exp4", "exp_lds", "order6", "qutrit_lds"])
 def test_shuffled_value_blocks_give_the_same_values_blockwise(qc, oracle, case):
     """qc_desc.jac_block_order / hess_block_order: every kernel family writes its blocks at the offsets the descriptor's order implies
     -- F, dF, mu_d2F and the one-call form of a handle with shuffled blocks equal the default handle's entry for entry (matched through
@@ -2028,6 +2028,13 @@ def test_shuffled_value_blocks_give_the_same_values_blockwise(qc, oracle, case):
         inp = qc.config_inputs(5, T=12)
     elif case == "exp3":
         inp = qc.unitary_smooth_pulse_inputs(qc.multi_qubit_system(3), qc.GATES["TOFFOLI"], 20, integrator="exponential")
+    elif case == "exp3_long":      # 999 intervals: two per workgroup (kIPW = 2, qc_mfma_exp*.hip)
+        inp = qc.unitary_smooth_pulse_inputs(qc.multi_qubit_system(3), qc.GATES["TOFFOLI"], 1000, integrator="exponential")
+    elif case == "exp4":
+        inp = qc.config_inputs(5, T=12, integrator="exponential")
+    elif case == "exp_lds":
+        inp = qc.unitary_smooth_pulse_inputs(qc.multi_qubit_system(2), qc.GATES["CNOT"], 20, integrator="exponential")
+        kw = dict(kernel="lds")
     elif case == "order6":
         inp = qc.unitary_smooth_pulse_inputs(qc.multi_qubit_system(2), qc.GATES["CNOT"], 20, pade_order=6)
     else:

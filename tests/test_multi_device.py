@@ -97,7 +97,8 @@ def test_multi_create_fails_loudly_without_a_device(qc):
 @pytest.mark.gpu
 @pytest.mark.parametrize("cfg,T,shards,full_from,integrator", [(3, 100, 3, None, "pade"), (3, 5, 8, None, "pade"), (1, 50, 2, None, "pade"),
                                                                (5, 21, 3, None, "pade"), (2, 37, 4, None, "pade"), (3, 150, 4, "1", "pade"),
-                                                               (3, 40, 3, None, "exponential"), (5, 9, 2, None, "exponential")])
+                                                               (3, 40, 3, None, "exponential"), (5, 9, 2, None, "exponential"),
+                                                               (3, 600, 2, None, "exponential")])
 def test_multi_handle_equals_single_handle(qc, oracle, cfg, T, shards, full_from, integrator, monkeypatch):
     """device_ids = [0] * shards: F, dF, mu_d2F, structures and dims bit-identical to the single-device handle (T = 5 with
     8 shards leaves empty trailing shards).  full_from: QC_HOST_MULTI_FULL -- the shards copy the Jacobian values in full (what a
