@@ -47,7 +47,7 @@ def solve(max_iter: int = 80, T: int = 50, verbose: bool = True, tol: float = 1e
     reg = qc.TrajectoryObjective(qc.QuadraticRegularizer("a", traj, R) + qc.QuadraticRegularizer("da", traj, R)
                                  + qc.QuadraticRegularizer("dda", traj, R), traj)
     ev = qc.QuantumControlEvaluator(dyn, objs + [reg])
-    nv, m = ev.n_variables, ev.n_constraints
+    nv = ev.n_variables
     zdim, comps = traj.dim, traj.components
 
     # pinned variables (initial state, initial / final controls) are eliminated; bounds as in the problem template
@@ -70,24 +70,11 @@ def solve(max_iter: int = 80, T: int = 50, verbose: bool = True, tol: float = 1e
     for nm in ("da", "dda"):
         for t in range(T):
             z_full[t * zdim + comps[nm].start:t * zdim + comps[nm].stop] *= 0.2
-    lo, hi = lb[free], ub[free]
-    has_lo, has_hi = np.isfinite(lo), np.isfinite(hi)
-    n = free.size
 
     def full(x):
         z = z_full.copy()
         z[free] = x
         return z
-
-    cbuf, gbuf = np.empty(m), np.empty(nv)
-
-    def f_c(x):                       # what a line-search trial asks for
-        z = full(x)
-        ev.eval_constraint(cbuf, z)
-        return ev.eval_objective(z), cbuf.copy()
-
-    def barrier(x, mu):
-        return -mu * (np.log(x[has_lo] - lo[has_lo]).sum() + np.log(hi[has_hi] - x[has_hi]).sum())
 
     def rollout_fidelity(z):          # of the pulse under every system's own generators: the smallest
         init, goal = qc.operator_to_iso_vec(np.eye(U_goal.shape[0], dtype=complex)), qc.operator_to_iso_vec(U_goal)
@@ -95,15 +82,65 @@ def solve(max_iter: int = 80, T: int = 50, verbose: bool = True, tol: float = 1e
             return qc.iso_vec_unitary_fidelity(dyn.rollout(z, init)[:, -1], goal)
         return min(qc.iso_vec_unitary_fidelity(dyn.rollout(z, init, part=k)[:, -1], goal) for k in range(len(state_names)))
 
+    f_before = rollout_fidelity(full(start_point(z_full, free, lb, ub)))
+    z, it = interior_point(ev, z_full, free, lb, ub, max_iter=max_iter, tol=tol, verbose=verbose)
+    f_after = rollout_fidelity(z)
+    viol = float(np.abs(dyn.F(z)).max())
+    if verbose:
+        print(f"iterations {it}  launches {ev.stats}  rollout fidelity {f_before:.6f} -> {f_after:.6f}  max |dynamics residual| {viol:.2e}")
+    stats = dict(ev.stats)
+    for o in [dyn, reg] + objs:
+        o.close()
+    return f_before, f_after, viol, stats
+
+
+def start_point(z_full, free, lb, ub):
+    """The free variables of z_full, moved 1 % of the bound width inside their bounds."""
+    lo, hi = lb[free], ub[free]
+    has_lo, has_hi = np.isfinite(lo), np.isfinite(hi)
     with np.errstate(invalid="ignore"):                 # (inf - inf on the unbounded variables, masked by the where)
         width = np.where(has_lo & has_hi, hi - lo, 1.0)
-    x = np.clip(z_full[free], np.where(has_lo, lo + 1e-2 * width, -np.inf), np.where(has_hi, hi - 1e-2 * width, np.inf))
+    return np.clip(z_full[free], np.where(has_lo, lo + 1e-2 * width, -np.inf), np.where(has_hi, hi - 1e-2 * width, np.inf))
+
+
+def interior_point(ev, z_full, free, lb, ub, max_iter: int = 80, tol: float = 1e-6, verbose: bool = True, n_ineq: int = 0):
+    """The iteration of the module docstring on the evaluator `ev` over the variables `free` of z_full (the others stay
+    fixed), bounds lb <= z <= ub.  The constraint rows are equalities c(z) = 0 except the last `n_ineq`, which are
+    c_i(z) >= 0, held as c_i(z) - s_i = 0 with slack variables s_i >= 0.  Returns (z, iterations)."""
+    nv, m = ev.n_variables, ev.n_constraints
+    lo, hi = lb[free], ub[free]
+    x = start_point(z_full, free, lb, ub)
+    nf, ns = free.size, int(n_ineq)
+    cbuf, gbuf = np.empty(m), np.empty(nv)
+
+    def full(x):
+        z = z_full.copy()
+        z[free] = x[:nf]
+        return z
+
+    if ns:                            # slacks s >= 0 of the inequality rows, started at max(c, 1e-4)
+        ev.eval_constraint(cbuf, full(x))
+        x = np.concatenate([x, np.maximum(cbuf[m - ns:], 1e-4)])
+        lo, hi = np.concatenate([lo, np.zeros(ns)]), np.concatenate([hi, np.full(ns, np.inf)])
+    has_lo, has_hi = np.isfinite(lo), np.isfinite(hi)
+    n = x.size
+
+    def f_c(x):                       # what a line-search trial asks for
+        z = full(x)
+        ev.eval_constraint(cbuf, z)
+        c = cbuf.copy()
+        if ns:
+            c[m - ns:] -= x[nf:]
+        return ev.eval_objective(z), c
+
+    def barrier(x, mu):
+        return -mu * (np.log(x[has_lo] - lo[has_lo]).sum() + np.log(hi[has_hi] - x[has_hi]).sum())
+
     lam = np.zeros(m)
     mu = 0.1
     zl = np.where(has_lo, mu / np.maximum(x - lo, 1e-12), 0.0)
     zu = np.where(has_hi, mu / np.maximum(hi - x, 1e-12), 0.0)
     nu = 10.0                                              # penalty of the l1 merit function
-    f_before = rollout_fidelity(full(x))
     fval, c = f_c(x)
     it = 0
     for it in range(1, max_iter + 1):
@@ -112,6 +149,10 @@ def solve(max_iter: int = 80, T: int = 50, verbose: bool = True, tol: float = 1e
         gx = gbuf[free]
         J = ev.jacobian_matrix(z).tocsc()[:, free]
         W = ev.hessian_lagrangian_matrix(z, 1.0, lam)[free][:, free]
+        if ns:
+            gx = np.concatenate([gx, np.zeros(ns)])
+            J = sp.hstack([J, sp.coo_matrix((-np.ones(ns), (np.arange(m - ns, m), np.arange(ns))), shape=(m, ns))]).tocsc()
+            W = sp.block_diag([W, sp.csr_matrix((ns, ns))]).tocsr()
         dl, du = np.where(has_lo, x - lo, 1.0), np.where(has_hi, hi - x, 1.0)
         r_dual = gx + J.T @ lam - zl + zu
         e0 = max(np.abs(r_dual).max(), np.abs(c).max(), np.abs(dl * zl)[has_lo].max(initial=0.0), np.abs(du * zu)[has_hi].max(initial=0.0))
@@ -166,15 +207,7 @@ def solve(max_iter: int = 80, T: int = 50, verbose: bool = True, tol: float = 1e
         dl, du = np.where(has_lo, x - lo, 1.0), np.where(has_hi, hi - x, 1.0)
         zl = np.where(has_lo, np.clip(zl, mu / (1e10 * dl), 1e10 * mu / dl), 0.0)
         zu = np.where(has_hi, np.clip(zu, mu / (1e10 * du), 1e10 * mu / du), 0.0)
-    z = full(x)
-    f_after = rollout_fidelity(z)
-    viol = float(np.abs(dyn.F(z)).max())
-    if verbose:
-        print(f"iterations {it}  launches {ev.stats}  rollout fidelity {f_before:.6f} -> {f_after:.6f}  max |dynamics residual| {viol:.2e}")
-    stats = dict(ev.stats)
-    for o in [dyn, reg] + objs:
-        o.close()
-    return f_before, f_after, viol, stats
+    return full(x), it
 
 
 if __name__ == "__main__":

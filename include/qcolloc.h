@@ -43,6 +43,8 @@
  *   DensityOperatorPureStateInfidelityObjective
  *   QuadraticRegularizer, MinimumTimeObjective           qc_terms_create / qc_terms_eval(_dev)
  *       (unitary_smooth_pulse_problem.jl:151-153, unitary_minimum_time_problem.jl:67-69)
+ *   UnitaryRobustnessObjective(H_error=...)              qc_robust_create / qc_robust_eval(_dev)
+ *       (unitary_robustness_problem.jl:46-49)
  *   unitary_rollout / rollout / open_rollout             qc_rollout / qc_rollout_dev
  *       (trajectory_initialization.jl:426,493,547)
  *
@@ -475,6 +477,53 @@ int qc_terms_hess_structure(const qc_terms* h, int64_t* rows, int64_t* cols, int
 int qc_terms_eval(qc_terms* h, const double* Z, double* J, double* grad, double* hvals);
 /* device buffers, asynchronous on `stream`; dgrad / dhvals may be NULL */
 int qc_terms_eval_dev(qc_terms* h, const double* dZ, double* dJ, double* dgrad, double* dhvals, void* stream);
+
+/* ---- robustness objective (UnitaryRobustnessObjective, reference unitary_robustness_problem.jl:46-49) ---------------- */
+/* A whole-trajectory term over the subspace block V_t = U_t[S, S] (n x n) of every knot t < K (n_knots):
+ *     A_t = V_t' H V_t,   tau = sum_{t<K} dt_t,   R = (1/tau) sum_{t<K} dt_t A_t,   L = Re tr(R'R) / n
+ * with H the n x n error operator (`unembed(H_error)`; complex, need not be Hermitian).  Its variables are the 2n^2 subspace
+ * entries of the unitary of every knot t < K, plus each such knot's timestep when off_dt >= 0: V = K (2n^2 [+1]), listed in
+ * increasing global index by qc_robust_vars.  Gradient: dense, Z_len entries (zeros included).  Hessian
+ * (QC_ROBUST_HESS_EXACT): dense over the V variables, the column-major upper triangle -- entry (i <= j) at j(j+1)/2 + i --
+ * refused with QC_ERR_UNSUPPORTED when V(V+1)/2 > 2^27.  2N <= 64.  The mathematics: the header comment of qc_robust.hip. */
+#define QC_ROBUST_HESS_NONE 0
+#define QC_ROBUST_HESS_EXACT 1
+typedef struct qc_robust_desc {
+    int64_t T;
+    int32_t zdim;
+    int32_t off_state;           /* offset of the unitary's iso-vec (2N^2 entries) inside a knot */
+    int32_t N;
+    int32_t n_sub;               /* subspace size n (0 with subspace = NULL: all N levels) */
+    const int32_t* subspace;     /* n distinct 0-based levels, or NULL */
+    const double* H_re;          /* n x n, column-major */
+    const double* H_im;          /* n x n, column-major, or NULL (real H) */
+    int32_t off_dt;              /* offset of the timestep inside a knot, -1: fixed */
+    int32_t reserved0;
+    double dt_fixed;
+    int64_t global_dim;
+    int64_t n_knots;             /* K, 1 .. T: knots 0 .. K-1 enter the sum */
+    int32_t hessian;             /* QC_ROBUST_HESS_NONE | QC_ROBUST_HESS_EXACT */
+    int32_t device;
+    int64_t reserved1[2];
+} qc_robust_desc;
+typedef struct qc_robust qc_robust;
+/* device-free: validate the descriptor (QC_ERR_INVALID with a message) and describe the term */
+int qc_robust_desc_n_vars(const qc_robust_desc* d, int64_t* n_vars);
+int qc_robust_desc_vars(const qc_robust_desc* d, int64_t* vars);
+int qc_robust_desc_hess_nnz(const qc_robust_desc* d, int64_t* nnz);
+int qc_robust_desc_hess_structure(const qc_robust_desc* d, int64_t* rows, int64_t* cols, int one_based);
+int64_t qc_sizeof_robust_desc(void);
+int qc_robust_create(const qc_robust_desc* d, qc_robust** out);
+void qc_robust_destroy(qc_robust* h);
+const char* qc_robust_last_error(const qc_robust* h);
+int qc_robust_n_vars(const qc_robust* h, int64_t* n_vars);
+int qc_robust_vars(const qc_robust* h, int64_t* vars);
+int qc_robust_hess_nnz(const qc_robust* h, int64_t* nnz);
+int qc_robust_hess_structure(const qc_robust* h, int64_t* rows, int64_t* cols, int one_based);
+/* host buffers; L / grad / hvals may be NULL */
+int qc_robust_eval(qc_robust* h, const double* Z, double* L, double* grad, double* hvals);
+/* device buffers, asynchronous on `stream` (no host synchronisation; scratch owned by the handle); dL / dgrad / dhvals may be NULL */
+int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad, double* dhvals, void* stream);
 
 /* Diagnostic only: when the environment variable QC_STAMPS=1 is set at qc_create, the MFMA kernel
  * records 16 s_memrealtime (100 MHz) checkpoints per interval; this copies them out (synchronises the

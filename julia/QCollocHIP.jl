@@ -54,12 +54,20 @@ struct QCFidelityDesc
     phase_dims::Ptr{Int32}; phase_ops::Ptr{Float64}
 end
 
+# mirror of `qc_robust_desc`
+struct QCRobustDesc
+    T::Int64; zdim::Int32; off_state::Int32; N::Int32; n_sub::Int32; subspace::Ptr{Int32}
+    H_re::Ptr{Float64}; H_im::Ptr{Float64}; off_dt::Int32; reserved0::Int32; dt_fixed::Float64
+    global_dim::Int64; n_knots::Int64; hessian::Int32; device::Int32; reserved1::NTuple{2,Int64}
+end
+
 function __init__()
     # constants were renumbered between ABI 0.1 / 0.2 / 0.3 and retired in 0.4 (QC_REG_*): the struct sizes do not show that, the version does
     abi = ccall(dlsym(dlopen(LIB[]), :qc_abi_version), Int32, ())
     abi == QC_ABI_VERSION || error("QCollocHIP: $(LIB[]) has ABI version $abi, this binding mirrors $QC_ABI_VERSION")
     # a stale mirror would corrupt memory silently: compare with the structs the library was compiled with
-    for (sym, T) in ((:qc_sizeof_desc, QCDesc), (:qc_sizeof_dims, QCDims), (:qc_sizeof_terms_desc, QCTermsDesc))
+    for (sym, T) in ((:qc_sizeof_desc, QCDesc), (:qc_sizeof_dims, QCDims), (:qc_sizeof_terms_desc, QCTermsDesc),
+                     (:qc_sizeof_robust_desc, QCRobustDesc))
         lib = ccall(dlsym(dlopen(LIB[]), sym), Int64, ())
         lib == sizeof(T) || error("QCollocHIP: $(T) has $(sizeof(T)) bytes, $(LIB[]) expects $lib (header / binding version mismatch)")
     end
@@ -555,6 +563,50 @@ function regularizers(traj, names_and_R; D::Float64=0.0, device::Int=0, dt_scale
     ev(Z⃗, J, g, H) = ccall((:qc_terms_eval, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), h[], Z⃗, J, g, H)
     L(Z⃗) = (J = Ref(0.0); GC.@preserve Z⃗ ev(Z⃗, J, C_NULL, C_NULL); J[])
     ∇L(Z⃗) = (g = Vector{Float64}(undef, Zlen); GC.@preserve Z⃗ g ev(Z⃗, C_NULL, g, C_NULL); g)          # fresh vectors: results never alias
+    ∂²L(Z⃗) = (H = Vector{Float64}(undef, nnz[]); GC.@preserve Z⃗ H ev(Z⃗, C_NULL, C_NULL, H); H)
+    return L, ∇L, ∂²L, collect(zip(Int.(hr), Int.(hc)))
+end
+
+"""
+    robustness_objective(traj, H_error; subspace=nothing, eval_hessian=true, device=0, unitary_name=:Ũ⃗, knots=traj.T)
+
+`UnitaryRobustnessObjective(H_error=H_error, eval_hessian=eval_hessian)` (unitary_robustness_problem.jl:46-49) on the device:
+L = Re tr(R'R)/n, R = (1/τ) Σ_{t≤knots} Δt_t V_t' H V_t over the subspace block V_t of every knot.  `H_error` is an N×N matrix
+(its subspace block is used), an n×n matrix with `subspace`, or anything with `operator` and `subspace` fields (an
+`EmbeddedOperator`); `subspace` is 1-based, as in Julia.  Returns `(L, ∇L, ∂²L, ∂²L_structure)` closures over one device handle:
+∇L is dense over Z⃗, ∂²L the dense upper triangle over the term's variables (empty with `eval_hessian=false`).
+"""
+function robustness_objective(traj, H_error; subspace=nothing, eval_hessian::Bool=true, device::Int=0, unitary_name::Symbol=:Ũ⃗,
+                              knots::Int=traj.T)
+    if hasproperty(H_error, :operator) && hasproperty(H_error, :subspace)
+        H, subspace = H_error.operator, H_error.subspace
+    else
+        H = H_error
+    end
+    N = isqrt(length(traj.components[unitary_name]) ÷ 2)
+    if !isnothing(subspace) && size(H, 1) == N && length(subspace) < N
+        H = H[collect(subspace), collect(subspace)]
+    end
+    sub = isnothing(subspace) ? Int32[] : Int32.(collect(subspace) .- 1)
+    Hre = Float64.(vec(real.(H))); Him = Float64.(vec(imag.(H)))
+    free_time = traj.timestep isa Symbol
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve sub Hre Him begin
+        desc = Ref(QCRobustDesc(traj.T, traj.dim, first(traj.components[unitary_name]) - 1, N, length(sub),
+                                isempty(sub) ? C_NULL : pointer(sub), pointer(Hre), pointer(Him),
+                                free_time ? first(traj.components[traj.timestep]) - 1 : -1, 0, free_time ? 0.0 : Float64(traj.timestep),
+                                traj.global_dim, knots, eval_hessian ? 1 : 0, device, (0, 0)))    # hessian: QC_ROBUST_HESS_EXACT = 1
+        rc = ccall((:qc_robust_create, LIB[]), Cint, (Ref{QCRobustDesc}, Ref{Ptr{Cvoid}}), desc, h)
+        rc == 0 || error("qc_robust_create: " * unsafe_string(ccall((:qc_robust_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
+    end
+    nnz = Ref{Int64}(0)
+    ccall((:qc_robust_hess_nnz, LIB[]), Cint, (Ptr{Cvoid}, Ref{Int64}), h[], nnz)
+    hr = Vector{Int64}(undef, nnz[]); hc = similar(hr)
+    ccall((:qc_robust_hess_structure, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Cint), h[], hr, hc, 1)
+    Zlen = traj.dim * traj.T + traj.global_dim
+    ev(Z⃗, L, g, H) = ccall((:qc_robust_eval, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), h[], Z⃗, L, g, H)
+    L(Z⃗) = (l = Ref(0.0); GC.@preserve Z⃗ ev(Z⃗, l, C_NULL, C_NULL); l[])
+    ∇L(Z⃗) = (g = Vector{Float64}(undef, Zlen); GC.@preserve Z⃗ g ev(Z⃗, C_NULL, g, C_NULL); g)
     ∂²L(Z⃗) = (H = Vector{Float64}(undef, nnz[]); GC.@preserve Z⃗ H ev(Z⃗, C_NULL, C_NULL, H); H)
     return L, ∇L, ∂²L, collect(zip(Int.(hr), Int.(hc)))
 end

@@ -214,6 +214,23 @@ r, _ = reference_record(sysD, probB.trajectory; integrators=probB.integrators, s
                         described=[upade(:Ũ⃗, :u, 1; order=12), deriv(:u, :du)])
 open(io -> write(io, json(r)), joinpath(out_dir, "ref_bangbang.json"), "w")
 
+# ---- UnitaryRobustnessObjective (unitary_robustness_problem.jl:46-49): which knots enter the sum, how it is normalised, and
+#      whether Core supplies a Hessian (this library: all T knots, / tau and / n, the exact dense Hessian) ---------------------------
+robObj = UnitaryRobustnessObjective(H_error=PAULIS[:Z])
+rob_core = robObj.L(traj.datavec, traj)
+function rob_restated(K; by_tau=true, by_n=true)
+    Us = [iso_vec_to_operator(traj[:Ũ⃗][:, t]) for t in 1:K]
+    dts = traj.timestep isa Symbol ? vec(traj[traj.timestep])[1:K] : fill(Float64(traj.timestep), K)
+    S = sum(dts[t] * Us[t]' * PAULIS[:Z] * Us[t] for t in 1:K)
+    R = by_tau ? S / sum(dts) : S
+    return real(tr(R' * R)) / (by_n ? 2 : 1)
+end
+rob_guess = [("all T knots, / tau, / n (this library)", rob_restated(traj.T)), ("K = T-1 (n_knots = T-1)", rob_restated(traj.T - 1)),
+             ("all T knots, no / tau", rob_restated(traj.T; by_tau=false)), ("all T knots, no / n", rob_restated(traj.T; by_n=false))]
+rob_hit = findfirst(((_, v),) -> isapprox(v, rob_core; rtol=1e-12), rob_guess)
+push!(verdicts, "robustness objective: knots and normalisation" => (isnothing(rob_hit) ? "NONE of the guesses: $rob_core" : rob_guess[rob_hit][1]))
+push!(verdicts, "robustness objective has a Hessian (this library: exact, dense)" => (robObj.∂²L !== nothing))
+
 println("\nreconcile.jl -- verdicts for INTEGRATION.md \"Choices this repository cannot verify\":")
 for (k, v) in verdicts
     println("  ", rpad(k, 72), " => ", v)

@@ -8,7 +8,7 @@ from . import _lib
 from ._lib import QCollocError
 from .evaluator import QuantumControlEvaluator
 from .dynamics import ComposedQuantumDynamics, QuantumDynamics, desc_dims, desc_structures, make_desc, pinned_zeros, split_groups, state_row_offset
-from .gates import GATES, PAULIS, operator_from_string
+from .gates import GATES, PAULIS, EmbeddedOperator, operator_from_string
 from .integrators import (DensityOperatorExponentialIntegrator, DerivativeIntegrator, QuantumStateExponentialIntegrator, QuantumStatePadeIntegrator,
                           UnitaryExponentialIntegrator, UnitaryPadeIntegrator)
 from .isomorphisms import (density_to_iso_vec, iso_generator, iso_operator, iso_vec_to_density, iso_vec_to_operator,
@@ -17,9 +17,10 @@ from .named_trajectory import NamedTrajectory
 from .objectives import (DensityOperatorPureStateInfidelityObjective, FinalQuantumStateFidelityConstraint, FinalUnitaryFidelityConstraint,
                          QuantumStateObjective, iso_fidelity, MinimumTimeObjective, QuadraticRegularizer, TimeStepsAllEqualConstraint,
                          TrajectoryObjective, UnitaryInfidelityObjective, iso_vec_unitary_fidelity, iso_vec_unitary_free_phase_fidelity,
-                         UnitaryFreePhaseInfidelityObjective, FinalUnitaryFreePhaseFidelityConstraint)
+                         UnitaryFreePhaseInfidelityObjective, FinalUnitaryFreePhaseFidelityConstraint, UnitaryRobustnessObjective)
 from .problems import (CONFIGS, config_inputs, density_operator_smooth_pulse_inputs, multi_qubit_system, quantum_state_sampling_inputs, quantum_state_smooth_pulse_inputs,
-                       unitary_bang_bang_inputs, unitary_direct_sum_inputs, unitary_sampling_inputs, unitary_smooth_pulse_inputs)
+                       unitary_bang_bang_inputs, unitary_direct_sum_inputs, unitary_robustness_problem, unitary_sampling_inputs, unitary_smooth_pulse_inputs,
+                       ControlProblemInputs)
 from .quantum_systems import OpenQuantumSystem, QuantumSystem
 from .rollouts import open_rollout, rollout, rollout_fidelity, unitary_rollout, unitary_rollout_fidelity
 from .trajectory_initialization import initialize_trajectory, unitary_geodesic
@@ -36,4 +37,5 @@ __all__ = [
     "QuadraticRegularizer", "MinimumTimeObjective", "TrajectoryObjective", "TimeStepsAllEqualConstraint",
     "OpenQuantumSystem", "DensityOperatorExponentialIntegrator", "density_operator_smooth_pulse_inputs",
     "density_to_iso_vec", "iso_vec_to_density", "iso_operator", "unitary_rollout", "rollout", "open_rollout", "unitary_rollout_fidelity", "rollout_fidelity", "make_desc", "desc_dims", "desc_structures", "state_row_offset", "QCollocError",
+    "EmbeddedOperator", "UnitaryRobustnessObjective", "unitary_robustness_problem", "ControlProblemInputs",
 ]

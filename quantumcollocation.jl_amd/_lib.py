@@ -45,6 +45,7 @@ QC_REG_DT_SCALED = 2       # (0 and 1 are retired values: the library refuses th
 QC_REG_PLAIN = 3
 QC_ABI_VERSION = 6          # QC_VERSION_MAJOR * 1000 + QC_VERSION_MINOR of the include/qcolloc.h this file mirrors
 QC_FID_FORM_ABS, QC_FID_FORM_ABS2 = 0, 1
+QC_ROBUST_HESS_NONE, QC_ROBUST_HESS_EXACT = 0, 1
 QC_ROWS_STACKED = 0
 QC_ROWS_BY_COMPONENT = 1
 
@@ -142,12 +143,34 @@ class qc_terms_desc(C.Structure):
     ]
 
 
+class qc_robust_desc(C.Structure):
+    _fields_ = [
+        ("T", C.c_int64),
+        ("zdim", C.c_int32),
+        ("off_state", C.c_int32),
+        ("N", C.c_int32),
+        ("n_sub", C.c_int32),
+        ("subspace", C.POINTER(C.c_int32)),
+        ("H_re", _c_double_p),
+        ("H_im", _c_double_p),
+        ("off_dt", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("dt_fixed", C.c_double),
+        ("global_dim", C.c_int64),
+        ("n_knots", C.c_int64),
+        ("hessian", C.c_int32),
+        ("device", C.c_int32),
+        ("reserved1", C.c_int64 * 2),
+    ]
+
+
 # Every symbol include/qcolloc.h declares: (name, restype, argtypes).  tests/test_abi.py checks this
 # table against the header and against the built library.
 _DESC_P = C.POINTER(qc_desc)
 _DIMS_P = C.POINTER(qc_dims_t)
 _H = C.c_void_p
 _TDESC_P = C.POINTER(qc_terms_desc)
+_RDESC_P = C.POINTER(qc_robust_desc)
 SYMBOLS = {
     "qc_operator_to_iso_vec": (C.c_int, [C.c_int32, _c_double_p, _c_double_p, _c_double_p]),
     "qc_iso_vec_to_operator": (C.c_int, [C.c_int32, _c_double_p, _c_double_p, _c_double_p]),
@@ -212,6 +235,20 @@ SYMBOLS = {
     "qc_terms_hess_structure": (C.c_int, [_H, _c_int64_p, _c_int64_p, C.c_int]),
     "qc_terms_eval": (C.c_int, [_H, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "qc_terms_eval_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qc_robust_desc_n_vars": (C.c_int, [_RDESC_P, _c_int64_p]),
+    "qc_robust_desc_vars": (C.c_int, [_RDESC_P, _c_int64_p]),
+    "qc_robust_desc_hess_nnz": (C.c_int, [_RDESC_P, _c_int64_p]),
+    "qc_robust_desc_hess_structure": (C.c_int, [_RDESC_P, _c_int64_p, _c_int64_p, C.c_int]),
+    "qc_sizeof_robust_desc": (C.c_int64, []),
+    "qc_robust_create": (C.c_int, [_RDESC_P, C.POINTER(_H)]),
+    "qc_robust_destroy": (None, [_H]),
+    "qc_robust_last_error": (C.c_char_p, [_H]),
+    "qc_robust_n_vars": (C.c_int, [_H, _c_int64_p]),
+    "qc_robust_vars": (C.c_int, [_H, _c_int64_p]),
+    "qc_robust_hess_nnz": (C.c_int, [_H, _c_int64_p]),
+    "qc_robust_hess_structure": (C.c_int, [_H, _c_int64_p, _c_int64_p, C.c_int]),
+    "qc_robust_eval": (C.c_int, [_H, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "qc_robust_eval_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qc_debug_read_stamps": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_int64]),
     "qc_debug_host_expand_rate": (C.c_int, [_H, C.c_int32, _c_double_p]),
     "qc_version": (C.c_char_p, []),
@@ -241,7 +278,8 @@ def _load() -> C.CDLL:
         raise ImportError(f"{LIB_PATH}: ABI version {lib.qc_abi_version()} but this binding mirrors {QC_ABI_VERSION} "
                           "(constants were renumbered between minor versions; stale build? run __graft_entry__.build())")
     # the struct mirrors above must be the structs this build of the library was compiled with
-    for name, mirror in (("qc_sizeof_desc", qc_desc), ("qc_sizeof_dims", qc_dims_t), ("qc_sizeof_terms_desc", qc_terms_desc)):
+    for name, mirror in (("qc_sizeof_desc", qc_desc), ("qc_sizeof_dims", qc_dims_t), ("qc_sizeof_terms_desc", qc_terms_desc),
+                         ("qc_sizeof_robust_desc", qc_robust_desc)):
         if getattr(lib, name)() != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: {name}() = {getattr(lib, name)()} but the Python mirror has {C.sizeof(mirror)} bytes "
                               "(stale build? run __graft_entry__.build())")

@@ -46,3 +46,31 @@ GATES = {
     "TOFFOLI": _controlled(_X, 2),
     "QFT16": qft(4),
 }
+
+
+class EmbeddedOperator:
+    """An operator on a subspace of an N-level system (PiccoloQuantumObjects' `EmbeddedOperator(op, subspace, levels)`):
+    `operator` is n x n, `subspace` the n 0-based levels it acts on (default: the first n), `N` the full dimension.
+    `unembed()` is the n x n operator; `embed(fill)` the N x N matrix with `fill` on the diagonal outside the subspace."""
+
+    def __init__(self, operator, subspace=None, N: int = None):
+        if isinstance(operator, str):
+            operator = GATES[operator]
+        self.operator = np.asarray(operator, dtype=complex)
+        n = self.operator.shape[0]
+        if self.operator.shape != (n, n):
+            raise ValueError("operator must be square")
+        self.subspace = list(range(n)) if subspace is None else [int(s) for s in subspace]
+        if len(self.subspace) != n or len(set(self.subspace)) != n:
+            raise ValueError("subspace must list one distinct level per row of the operator")
+        self.N = max(self.subspace) + 1 if N is None else int(N)
+        if min(self.subspace) < 0 or max(self.subspace) >= self.N:
+            raise ValueError("subspace levels must lie in 0 .. N-1")
+
+    def unembed(self) -> np.ndarray:
+        return self.operator.copy()
+
+    def embed(self, fill: complex = 0.0) -> np.ndarray:
+        out = np.diag(np.full(self.N, fill, dtype=complex))
+        out[np.ix_(self.subspace, self.subspace)] = self.operator
+        return out

@@ -10,7 +10,8 @@ Only the last knot's state enters; gradients/Hessians are returned on those `2N^
 their global indices.
 
 Whole-trajectory terms through `qc_terms_*`: `QuadraticRegularizer`, `MinimumTimeObjective`
-(summed into one `TrajectoryObjective`) and the constant `TimeStepsAllEqualConstraint`.
+(summed into one `TrajectoryObjective`) and the constant `TimeStepsAllEqualConstraint`; through `qc_robust_*`:
+`UnitaryRobustnessObjective` (unitary_robustness_problem.jl:46-49).
 """
 from __future__ import annotations
 
@@ -446,3 +447,145 @@ class TimeStepsAllEqualConstraint:
 
     def dg(self, Z=None) -> np.ndarray:
         return self.jac_values
+
+
+# ---------------------------------------------------------------------------------------------------------------
+#  UnitaryRobustnessObjective (reference unitary_robustness_problem.jl:46-49) through `qc_robust_*`
+# ---------------------------------------------------------------------------------------------------------------
+class UnitaryRobustnessObjective:
+    """L = Re tr(R'R) / n,  R = (1/tau) sum_{t<K} dt_t V_t' H V_t,  V_t = U_t[S, S],  tau = sum_{t<K} dt_t: how strongly the error
+    operator H (`unembed(H_error)`) survives, averaged over the trajectory in the toggling frame.  `L(Z)`, `grad_L(Z)` (dense,
+    length `len(Z)`), `hess_L(Z)` (values on `hess_structure`: the dense upper triangle over `variables`, column-major),
+    `L_grad_hess(Z)`, `eval_device(...)`; `"∇L"`, `"∂²L"`, `"∂²L_structure"` resolve to the same members.
+
+    H_error   N x N array (subspace = None: all levels; otherwise its [S, S] block is used) or an `EmbeddedOperator`
+              (its `unembed()` and `subspace`)
+    knots     K, the knots that enter the sum (default: all T)
+    """
+    _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
+
+    def __init__(self, traj: NamedTrajectory, H_error=None, eval_hessian: bool = True, symb: str = "Ũ⃗", subspace=None,
+                 knots: Optional[int] = None, device: int = 0):
+        from .gates import EmbeddedOperator
+        if H_error is None:
+            raise ValueError("H_error is required")
+        s = len(traj.components[symb])
+        N = int(round((s / 2) ** 0.5))
+        if 2 * N * N != s:
+            raise ValueError(f"component {symb} has length {s}, not 2 N^2")
+        if isinstance(H_error, EmbeddedOperator):
+            if H_error.N != N:
+                raise ValueError(f"H_error is embedded in {H_error.N} levels, the trajectory's unitary has {N}")
+            if subspace is not None and list(subspace) != H_error.subspace:
+                raise ValueError("subspace differs from H_error.subspace")
+            H, sub = H_error.unembed(), H_error.subspace
+        else:
+            H = np.asarray(H_error, dtype=complex)
+            sub = None if subspace is None else [int(x) for x in subspace]
+            if sub is not None and H.shape == (N, N):
+                H = H[np.ix_(sub, sub)]
+        n = N if sub is None else len(sub)
+        if H.shape != (n, n):
+            raise ValueError(f"H_error has shape {H.shape}, expected ({n}, {n}) or ({N}, {N})")
+        self.traj = traj
+        self.H = H
+        self.subspace = sub
+        self.eval_hessian = bool(eval_hessian)
+        free = isinstance(traj.timestep, str)
+        self._Hre = np.ascontiguousarray(H.real.reshape(-1, order="F"))
+        self._Him = np.ascontiguousarray(H.imag.reshape(-1, order="F"))
+        self._sub = None if sub is None else np.ascontiguousarray(sub, dtype=np.int32)
+        d = _lib.qc_robust_desc()
+        d.T = traj.T
+        d.zdim = traj.dim
+        d.off_state = traj.offset(symb)
+        d.N = N
+        d.n_sub = 0 if sub is None else len(sub)
+        d.subspace = None if sub is None else self._sub.ctypes.data_as(C.POINTER(C.c_int32))
+        d.H_re = _lib.dptr(self._Hre)
+        d.H_im = _lib.dptr(self._Him)
+        d.off_dt = traj.offset(traj.timestep) if free else -1
+        d.dt_fixed = 0.0 if free else float(traj.timestep)
+        d.global_dim = traj.global_dim
+        d.n_knots = traj.T if knots is None else int(knots)
+        d.hessian = _lib.QC_ROBUST_HESS_EXACT if eval_hessian else _lib.QC_ROBUST_HESS_NONE
+        d.device = device
+        self._desc = d
+        self.Z_len = traj.T * traj.dim + traj.global_dim
+        self._h = C.c_void_p()
+        rc = _lib.lib.qc_robust_create(C.byref(d), C.byref(self._h))
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_robust_last_error(None).decode())
+        v = C.c_int64()
+        _lib.lib.qc_robust_n_vars(self._h, C.byref(v))
+        self.n_vars = v.value
+        self.variables = np.empty(self.n_vars, dtype=np.int64)
+        _lib.lib.qc_robust_vars(self._h, _lib.iptr(self.variables))
+        _lib.lib.qc_robust_hess_nnz(self._h, C.byref(v))
+        self.hess_nnz = v.value
+        self._structure = None
+
+    @property
+    def hess_structure(self):
+        """(rows, cols) of the Hessian values: the upper triangle over `variables`, entry (i <= j) at j(j+1)/2 + i; empty
+        with eval_hessian=False.  Built on first use (V(V+1)/2 entries)."""
+        if self._structure is None:
+            r = np.empty(self.hess_nnz, dtype=np.int64)
+            c = np.empty(self.hess_nnz, dtype=np.int64)
+            rc = _lib.lib.qc_robust_hess_structure(self._h, _lib.iptr(r), _lib.iptr(c), 0)
+            if rc != _lib.QC_OK:
+                raise _lib.QCollocError(rc, _lib.lib.qc_robust_last_error(self._h).decode())
+            self._structure = (r, c)
+        return self._structure
+
+    def _eval(self, Z, grad: bool, hess: bool):
+        Z = np.ascontiguousarray(Z, dtype=np.float64)
+        if Z.size != self.Z_len:
+            raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
+        if hess and not self.eval_hessian:
+            raise RuntimeError("the objective was built with eval_hessian=False")
+        L = C.c_double()
+        g = np.empty(self.Z_len) if grad else None
+        H = np.empty(self.hess_nnz) if hess else None
+        rc = _lib.lib.qc_robust_eval(self._h, _lib.dptr(Z), C.byref(L), _lib.dptr(g) if grad else None,
+                                     _lib.dptr(H) if hess and self.hess_nnz else None)
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_robust_last_error(self._h).decode())
+        return L.value, g, H
+
+    def L(self, Z) -> float:
+        return self._eval(Z, False, False)[0]
+
+    def grad_L(self, Z) -> np.ndarray:
+        return self._eval(Z, True, False)[1]
+
+    def hess_L(self, Z) -> np.ndarray:
+        return self._eval(Z, False, True)[2]
+
+    def L_grad_hess(self, Z):
+        return self._eval(Z, True, self.eval_hessian)
+
+    def eval_device(self, dZ, dL, dgrad=None, dhess=None, stream=None):
+        """Device-resident evaluation on torch CUDA tensors (float64), asynchronous on `stream`; dL holds one double."""
+        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        rc = _lib.lib.qc_robust_eval_dev(self._h, dZ.data_ptr(), dL.data_ptr() if dL is not None else None,
+                                         dgrad.data_ptr() if dgrad is not None else None, dhess.data_ptr() if dhess is not None else None, s)
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_robust_last_error(self._h).decode())
+
+    def __getattr__(self, name):
+        al = type(self)._ALIASES
+        if name in al:
+            return getattr(self, al[name])
+        raise AttributeError(name)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib.qc_robust_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

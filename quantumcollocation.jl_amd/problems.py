@@ -307,3 +307,43 @@ def unitary_direct_sum_inputs(parts, labels=None) -> HotPathInputs:
             else:
                 raise NotImplementedError("direct sums of unitary smooth-pulse problems")
     return HotPathInputs(parts[0].system, traj, integrators)
+
+
+@dataclass
+class ControlProblemInputs:
+    """What `QuantumControlEvaluator(QuantumDynamics(integrators, traj), objectives, constraints)` needs."""
+    system: QuantumSystem
+    traj: NamedTrajectory
+    integrators: List
+    objectives: List
+    constraints: List
+
+
+def unitary_robustness_problem(H_error, inputs: HotPathInputs, *, objectives=(), constraints=(), final_fidelity: Optional[float] = None,
+                               subspace=None, phase_name: str = "ϕ", phase_operators=None, eval_hessian: bool = True,
+                               unitary_name: str = "Ũ⃗", device: int = 0) -> ControlProblemInputs:
+    """`UnitaryRobustnessProblem(H_error, trajectory, system, objective, integrators, constraints; ...)` (reference
+    unitary_robustness_problem.jl:28-99): the given objectives plus `UnitaryRobustnessObjective(H_error=H_error)` (:46-49), the
+    given constraints plus a final-fidelity constraint on `subspace` (:58-84) -- `FinalUnitaryFidelityConstraint`, or the
+    free-phase variant over `traj.global_data[phase_name]` when `phase_operators` is given.  `final_fidelity=None`: the
+    trajectory's current (free-phase) fidelity."""
+    from .objectives import (FinalUnitaryFidelityConstraint, FinalUnitaryFreePhaseFidelityConstraint, UnitaryRobustnessObjective,
+                             iso_vec_unitary_fidelity, iso_vec_unitary_free_phase_fidelity)
+    traj = inputs.traj
+    if unitary_name not in traj.names:
+        raise ValueError(f"trajectory has no component {unitary_name}")
+    rob = UnitaryRobustnessObjective(traj, H_error=H_error, eval_hessian=eval_hessian, symb=unitary_name, device=device)
+    U_T = np.array(traj[unitary_name][:, -1])
+    U_G = np.asarray(traj.goal[unitary_name], dtype=np.float64)
+    sub = None if subspace is None else [int(s) for s in subspace]
+    if phase_operators is None:
+        if final_fidelity is None:
+            final_fidelity = iso_vec_unitary_fidelity(U_T, U_G, subspace=sub, device=device)
+        con = FinalUnitaryFidelityConstraint(unitary_name, final_fidelity, traj, subspace=sub, device=device)
+    else:
+        if final_fidelity is None:
+            final_fidelity = iso_vec_unitary_free_phase_fidelity(U_T, U_G, traj.global_data[phase_name], phase_operators, subspace=sub,
+                                                                 device=device)
+        con = FinalUnitaryFreePhaseFidelityConstraint(unitary_name, phase_name, phase_operators, final_fidelity, traj, subspace=sub,
+                                                      device=device)
+    return ControlProblemInputs(inputs.system, traj, list(inputs.integrators), list(objectives) + [rob], list(constraints) + [con])
