@@ -69,9 +69,9 @@ def _pieces(Z, s: RobustSpec):
     V = iso(Zk[:, idx[0]], Zk[:, idx[1]])                             # (K, 2n, 2n)
     Hi = iso(np.asarray(s.H).real, np.asarray(s.H).imag)
     dt = Zk[:, s.off_dt] if s.off_dt >= 0 else np.full(s.nK, s.dt_fixed)
-    A = np.einsum("tji,jk,tkl->til", V, Hi, V)                        # iso(V' H V)
+    A = np.swapaxes(V, 1, 2) @ Hi @ V                                 # iso(V' H V)
     tau = dt.sum()
-    R = np.einsum("t,tij->ij", dt, A) / tau
+    R = np.tensordot(dt, A, axes=1) / tau
     return Zk, idx, V, Hi, dt, A, tau, R
 
 
@@ -84,7 +84,7 @@ def grad(Z, s: RobustSpec):
     """Analytic gradient, dense over Z (zeros outside the variables)."""
     Zk, idx, V, Hi, dt, A, tau, R = _pieces(Z, s)
     n = s.n
-    G = np.einsum("ij,tjk,lk->til", Hi, V, R) + np.einsum("ji,tjk,kl->til", Hi, V, R)   # iso(H V R' + H' V R)
+    G = Hi @ V @ R.T + Hi.T @ V @ R                                   # iso(H V R' + H' V R)
     G = G * (2.0 * dt / (n * tau))[:, None, None]
     out = np.zeros(Z.shape, dtype=Z.dtype)
     gk = out[:s.T * s.zdim].reshape(s.T, s.zdim)
@@ -122,3 +122,47 @@ def packed_upper(Hm):
     r, c = np.triu_indices(Hm.shape[0])
     order = np.lexsort((r, c))
     return Hm[r[order], c[order]]
+
+
+def hessian_columns(Z, s: RobustSpec, cols, h: float = 1e-30):
+    """Whole columns `cols` (positions in `variables(s)`) of the V x V Hessian, the method of `hessian`: (V, len(cols))."""
+    vs = variables(s)
+    Zc = np.asarray(Z, dtype=complex)
+    out = np.empty((vs.size, len(cols)))
+    for c, k in enumerate(cols):
+        Zc[vs[k]] += 1j * h
+        out[:, c] = grad(Zc, s)[vs].imag / h
+        Zc[vs[k]] -= 1j * h
+    return out
+
+
+def hessian_vector_product(Z, s: RobustSpec, v, h: float = 1e-30):
+    """H v over `variables(s)` by one complex step of the analytic gradient along v (no matrix is formed)."""
+    vs = variables(s)
+    Zc = np.asarray(Z, dtype=complex)
+    Zc[vs] += 1j * h * np.asarray(v, dtype=float)
+    return grad(Zc, s)[vs].imag / h
+
+
+def packed_column(Hp, k):
+    """Whole column k of the symmetric matrix whose column-major upper triangle is `Hp` (entry (i <= j) at j(j+1)/2 + i)."""
+    V = int((np.sqrt(8.0 * Hp.size + 1.0) - 1.0) / 2.0 + 0.5)
+    below = np.arange(k + 1, V, dtype=np.int64)
+    return np.concatenate([Hp[k * (k + 1) // 2:k * (k + 1) // 2 + k + 1], Hp[below * (below + 1) // 2 + k]])
+
+
+def packed_matvec(Hp, X):
+    """(H X, |H| |X|) for the symmetric H packed in `Hp` and X (V, m), one stored column at a time: every value takes part."""
+    X = np.asarray(X, dtype=float)
+    V = X.shape[0]
+    assert Hp.size == V * (V + 1) // 2
+    Y, A = np.zeros_like(X), np.zeros_like(X)
+    Xa = np.abs(X)
+    for j in range(V):
+        col = Hp[j * (j + 1) // 2:j * (j + 1) // 2 + j + 1]          # H[0..j, j]
+        Y[:j + 1] += np.outer(col, X[j])
+        A[:j + 1] += np.outer(np.abs(col), Xa[j])
+        if j:
+            Y[j] += col[:j] @ X[:j]                                   # H[j, 0..j-1] from the symmetric half
+            A[j] += np.abs(col[:j]) @ Xa[:j]
+    return Y, A

@@ -299,3 +299,134 @@ def test_free_phase_descriptor_errors(qc, oracle):
     assert L.lib.qc_fidelity_create_desc(C.byref(d), C.byref(h)) == L.QC_ERR_INVALID
     d.n_phases, d.form = 0, 7
     assert L.lib.qc_fidelity_create_desc(C.byref(d), C.byref(h)) == L.QC_ERR_INVALID
+
+
+# ------------------------------------------------------------------------------------------------
+#  Every form of qc_fidelity_kernel up to the documented 2N <= 128 ceiling
+# ------------------------------------------------------------------------------------------------
+# The kernel's branches (qc_fidelity.hip): free phases (K > 0) return before anything else (:44-148); the |t|^2 forms and the ket /
+# density kinds next (:173-189); the unitary |tr| / n Hessian stages g_r, g_i in LDS only when s = 2 N^2 <= 1024 (:190) and reads
+# them from global memory past that.
+def fidelity_form(kind, N, K=0, form="abs"):
+    s = 2 * N * N if kind == "unitary" else 2 * N
+    if K:
+        return "free-phase"
+    if kind != "unitary" or form == "abs2":
+        return "quadratic"
+    return "staged" if s <= 1024 else "unstaged"
+
+
+SUB_OF = {22: list(range(0, 22, 2)), 23: [22, 0, 5, 9, 13, 17, 20, 1], 32: list(range(3, 32, 3))}
+ABS_CASES = [(N, sub) for N in (22, 23, 32) for sub in (None, SUB_OF[N])]
+FREE_PHASE_32 = [ZP] * 5                                   # five single-qubit Z phases on 5 qubits: P = 2048 + 5
+
+
+def test_fidelity_form_coverage():
+    """The cases below reach the staged |tr| / n branch at its last size, the unstaged one, and free phases past n = 16."""
+    forms = [fidelity_form("unitary", N) for N, _ in ABS_CASES] + [fidelity_form("unitary", 64)]
+    assert 2 * 22 * 22 == 968 and 2 * 23 * 23 == 1058
+    assert forms.count("staged") == 2 and forms.count("unstaged") == 5
+    assert fidelity_form("unitary", 32, K=len(FREE_PHASE_32)) == "free-phase" and 2 ** len(FREE_PHASE_32) == 32 > 16
+    assert fidelity_form("unitary", 32, form="abs2") == "quadratic" and fidelity_form("ket", 64) == "quadratic"
+    # (today's cases stop at N = 16, s = 512: the staged branch only)
+    assert all(fidelity_form("unitary", N) == "staged" for N in (2, 3, 4, 8, 16))
+
+
+def _packed_to_upper(Hp, P):
+    Hd = np.zeros((P, P))
+    r, c = np.triu_indices(P)
+    order = np.lexsort((r, c))
+    Hd[r[order], c[order]] = Hp
+    return Hd
+
+
+def _near_goal(oracle, N, rng):
+    goal = oracle.operator_to_iso_vec(rand_unitary(N, rng))
+    u = oracle.operator_to_iso_vec(rand_unitary(N, rng)) + 0.05 * rng.standard_normal(2 * N * N)
+    return goal, u
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N,sub", ABS_CASES, ids=[f"N{N}-{'sub' if s else 'full'}" for N, s in ABS_CASES])
+def test_fidelity_kernel_staged_and_unstaged(qc, oracle, N, sub):
+    """|tr| / n at N = 22 (s = 968, the last staged size), 23 (s = 1058, the first unstaged one) and 32, against the oracle."""
+    from qcolloc_amd.objectives import _Fidelity
+    rng = np.random.default_rng(40 + N + (0 if sub is None else 1))
+    goal, u = _near_goal(oracle, N, rng)
+    f = _Fidelity(goal, sub)
+    try:
+        F, L, g, H = f.eval(u)
+    finally:
+        f.close()
+    Fr, gr, Hr = oracle.fidelity_value_grad_hess(u, goal, sub)
+    assert abs(F - Fr) < 1e-13 and abs(L - abs(1 - Fr)) < 1e-13
+    np.testing.assert_allclose(g, gr, rtol=1e-11, atol=1e-13)
+    np.testing.assert_allclose(_packed_to_upper(H, u.size), np.triu(Hr), rtol=1e-10, atol=1e-12)
+
+
+@pytest.mark.gpu
+def test_fidelity_kernel_at_32_levels_abs2_and_free_phases(qc, oracle):
+    """|tr|^2 / n^2 at N = 32, and both forms with five single-qubit Z phases (P = 2053)."""
+    from qcolloc_amd.objectives import _Fidelity
+    rng = np.random.default_rng(72)
+    goal, u = _near_goal(oracle, 32, rng)
+    for form, ops in (("abs2", []), ("abs", FREE_PHASE_32), ("abs2", FREE_PHASE_32)):
+        x = np.concatenate([u, rng.standard_normal(len(ops))])
+        f = _Fidelity(goal, None, form=form, phase_operators=ops or None)
+        try:
+            assert f.P == x.size
+            F, L, grad, H = f.eval(x)
+        finally:
+            f.close()
+        Fr, gr, Hr = oracle.free_phase_fidelity_value_grad_hess(x, goal, ops, None, form)
+        assert abs(F - Fr) < 1e-12 * max(1, abs(Fr)) and abs(L - abs(1 - Fr)) < 1e-12
+        np.testing.assert_allclose(grad, gr, rtol=1e-10, atol=1e-12)
+        np.testing.assert_allclose(_packed_to_upper(H, x.size), np.triu(Hr), rtol=1e-10, atol=1e-11 * max(1.0, np.abs(Hr).max()))
+
+
+@pytest.mark.gpu
+def test_ket_fidelity_kernel_at_64_levels(qc, oracle):
+    from qcolloc_amd.objectives import _Fidelity
+    rng = np.random.default_rng(64)
+    g = rng.standard_normal(64) + 1j * rng.standard_normal(64)
+    g /= np.linalg.norm(g)
+    giso = np.concatenate([g.real, g.imag])
+    p = giso + 0.3 * rng.standard_normal(128)
+    f = _Fidelity(giso, kind="ket")
+    try:
+        F, L, grad, H = f.eval(p)
+    finally:
+        f.close()
+    Fr, gr, Hr = oracle.ket_fidelity_value_grad_hess(p, giso)
+    assert abs(F - Fr) < 1e-13 * max(1, abs(Fr)) and abs(L - abs(1 - Fr)) < 1e-13 * max(1, abs(Fr))
+    np.testing.assert_allclose(grad, gr, rtol=1e-13, atol=1e-14)
+    np.testing.assert_allclose(_packed_to_upper(H, 128), np.triu(Hr), rtol=1e-13, atol=1e-14)
+
+
+@pytest.mark.gpu
+def test_fidelity_kernel_at_64_levels(qc, oracle):
+    """N = 64 (s = 8192, 33.5 M packed values): every stored value against the oracle's closed form, one block of columns at a time
+    (hess F = (g_r g_r' + g_i g_i') / (n^2 F) - grad F grad F' / F, oracle.fidelity_value_grad_hess), without the dense matrix."""
+    from qcolloc_amd.objectives import _Fidelity
+    N = 64
+    rng = np.random.default_rng(164)
+    goal, u = _near_goal(oracle, N, rng)
+    f = _Fidelity(goal)
+    try:
+        F, L, g, H = f.eval(u)
+    finally:
+        f.close()
+    gr, gi, n = oracle.fidelity_vectors(goal, N)
+    tr, ti = gr @ u, gi @ u
+    Fr = np.sqrt(tr * tr + ti * ti) / n
+    grad = (tr * gr + ti * gi) / (n * n * Fr)
+    assert abs(F - oracle.iso_vec_unitary_fidelity(u, goal)) < 1e-13 and abs(F - Fr) < 1e-13 and abs(L - abs(1 - Fr)) < 1e-13
+    np.testing.assert_allclose(g, grad, rtol=1e-11, atol=1e-13)
+    s = u.size
+    assert H.shape == (s * (s + 1) // 2,)
+    B = 512
+    for j0 in range(0, s, B):
+        j1 = j0 + B
+        blk = (np.outer(gr[:j1], gr[j0:j1]) + np.outer(gi[:j1], gi[j0:j1])) / (n * n * Fr) - np.outer(grad[:j1], grad[j0:j1]) / Fr
+        for j in range(j0, j1):
+            np.testing.assert_allclose(H[j * (j + 1) // 2:j * (j + 1) // 2 + j + 1], blk[:j + 1, j - j0], rtol=1e-10, atol=1e-12)

@@ -340,3 +340,208 @@ def test_evaluator_with_the_term_is_the_sum_of_its_parts(qc):
     finally:
         for o in (dyn, reg, rob):
             o.close()
+
+
+# ---------------------------------------------------------------------------------------------- launch forms ----
+# The host rule of qc_robust_create (qc_robust.hip:539-547, the opt-in at :581-586) restated: knots per group, passes of the
+# per-knot loops (load_v, mul_nn / mul_cn, the G loop: kp n^2 items strided by 256 threads), the two LDS sizes, V.
+HESS_CAP = 1 << 27          # V (V + 1) / 2 packed values (kRobHessCap, qc_robust.hip:47, checked at :455)
+
+
+def robust_launch(N, sub, free, K):
+    n = N if sub is None else len(sub)
+    nn, m2 = n * n, 2 * n * n
+    kp = max(1, min(64, 256 // nn))                                   # :540
+    V = K * (m2 + (1 if free else 0))                                 # robust_layout, :454
+    return dict(n=n, kp=kp, passes=-(-kp * nn // 256),
+                lds_partial=(m2 + kp * (2 * m2 + m2 + 1)) * 8,        # :546
+                lds_grad=(2 * m2 + kp * 5 * m2 + 2 * kp) * 8,         # :547
+                V=V)
+
+
+def hessian_check(V):
+    """How a case's Hessian is compared: 'full' (dense restatement), 'columns' (whole columns + HVPs), None (over the cap)."""
+    if V <= HESS_MAX_V:
+        return "full"
+    return "columns" if V * (V + 1) // 2 <= HESS_CAP else None
+
+
+SUB20 = [0, 2, 3, 5, 6, 7, 8, 9, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 23]
+# N, sub, T, K (None: every knot), free dt, state first (else a lead of 3 entries), global_dim
+FORM_CASES = [
+    (1, None, 2, None, False, True, 0),            # n = 1: kp = 64, m2 = 2 padded to 4
+    (3, [2], 257, 256, False, False, 2),
+    (3, [1], 1000, None, True, False, 2),          # n = 1, V = 3000
+    (17, None, 1, None, True, False, 2),           # n = 17: two passes, no opt-in
+    (17, None, 257, None, False, True, 0),
+    (24, SUB20, 2, None, True, False, 3),          # n = 20: two passes
+    (20, None, 1000, 999, True, True, 0),
+    (25, None, 1, None, True, False, 2),           # n = 25: opt-in on the gradient kernel
+    (25, None, 257, None, False, True, 0),
+    (32, None, 1, None, False, True, 2),           # n = 32: opt-in on both kernels (fixed dt: one knot's L does not depend on dt)
+    (32, None, 2, None, True, False, 0),
+    (32, None, 1000, 999, True, False, 2),
+]
+# the Hessian above V = 2000: N, sub, T, K, free, state first, global_dim
+HESS_BIG_CASES = [
+    (2, None, 700, 667, True, False, 2),           # V = 6003
+    (3, [0, 1], 1500, None, True, True, 0),        # V = 13 500, the size profiles/robust_summary.txt times
+    (32, None, 8, 7, True, False, 0),              # V = 14 343, near the cap
+]
+
+
+def _form_id(c):
+    N, sub, T, K, free, sf, gd = c
+    return f"N{N}-n{N if sub is None else len(sub)}-T{T}-K{K or T}-{'free' if free else 'fixed'}"
+
+
+def test_launch_form_coverage():
+    """The GPU cases below reach every launch form of qc_robust_create and every way the Hessian is compared."""
+    def forms(cases):
+        return [dict(robust_launch(N, sub, free, K or T), check=hessian_check(robust_launch(N, sub, free, K or T)["V"]))
+                for N, sub, T, K, free, _, _ in cases]
+    new = forms(FORM_CASES)
+    big = forms(HESS_BIG_CASES)
+    assert any(f["passes"] == 1 for f in new)
+    assert any(f["passes"] > 1 and f["lds_grad"] <= 65536 for f in new)
+    assert any(f["lds_grad"] > 65536 and f["lds_partial"] <= 65536 for f in new)
+    assert any(f["lds_partial"] > 65536 for f in new)
+    assert robust_launch(32, None, True, 1)["lds_partial"] == 65544 and robust_launch(24, None, True, 1)["lds_grad"] < 65536
+    assert any(f["n"] == 1 and f["kp"] == 64 for f in new)
+    assert any(f["check"] == "full" and f["passes"] > 1 for f in new) and any(f["check"] == "full" and f["lds_grad"] > 65536 for f in new)
+    assert any(f["check"] == "columns" for f in new) and any(f["check"] is None for f in new)
+    assert [f["check"] for f in big] == ["columns"] * 3 and 5000 < big[0]["V"] < 7000 and big[1]["V"] == 13500
+    assert big[2]["V"] == 14343 and big[2]["lds_partial"] > 65536
+
+
+def test_hessian_cap_at_32_levels(qc):
+    """n = 32 with a free timestep: V = 2049 K.  K = 7 is under the 2^27 cap, K = 8 over it; without the Hessian K = 8 is fine."""
+    L = qc._lib
+    nnz = C.c_int64()
+    s, _ = _spec_and_Z(np.random.default_rng(8), 8, 32, None, True, K=7)
+    d, keep = _desc(qc, s)
+    assert L.lib.qc_robust_desc_hess_nnz(C.byref(d), C.byref(nnz)) == 0 and nnz.value == 14343 * 14344 // 2
+    d.n_knots = 8
+    assert L.lib.qc_robust_desc_hess_nnz(C.byref(d), C.byref(nnz)) == L.QC_ERR_UNSUPPORTED
+    assert str(2049 * 8) in L.lib.qc_robust_last_error(None).decode()
+    d.hessian = 0
+    assert L.lib.qc_robust_desc_hess_nnz(C.byref(d), C.byref(nnz)) == 0 and nnz.value == 0
+    nv = C.c_int64()
+    assert L.lib.qc_robust_desc_n_vars(C.byref(d), C.byref(nv)) == 0 and nv.value == 2049 * 8
+    del keep
+
+
+def _column_picks(s: rr.RobustSpec, V, seed, count=48):
+    """Columns to compare whole: the first and last variable of knots 0, 1, K-2, K-1, some dt columns, columns 16J-1, 16J,
+    16J+15 of a low, a middle and the last tile row, the rest at random (fixed seed)."""
+    P, K = V // s.nK, s.nK
+    pick = set()
+    for t in (0, 1, K - 2, K - 1):
+        if 0 <= t < K:
+            pick.update((t * P, t * P + P - 1))
+    if s.off_dt >= 0:
+        dtpos = int(np.flatnonzero(rr.variables(s)[:P] == s.off_dt)[0])
+        pick.update(t * P + dtpos for t in {0, K // 2, K - 1})
+    last = (V - 1) // 16
+    for J in (1, last // 2, last):
+        pick.update(c for c in (16 * J - 1, 16 * J, 16 * J + 15) if 0 <= c < V)
+    rng = np.random.default_rng(seed)
+    while len(pick) < min(count, V):
+        pick.add(int(rng.integers(V)))
+    return sorted(pick)
+
+
+def _check_packed_hessian(Hp, Z, s: rr.RobustSpec, seed, n_hvp=2):
+    """(a) whole columns against the complex-stepped columns at 1e-10 of each column's max; (b) H v from every packed value
+    against the complex step of the gradient along v, entry by entry within 1e-10 of (|H| |v|)_i."""
+    V = rr.variables(s).size
+    assert Hp.shape == (V * (V + 1) // 2,) and np.isfinite(Hp).all()
+    cols = _column_picks(s, V, seed)
+    assert len(cols) >= min(48, V)
+    ref = rr.hessian_columns(Z, s, cols)
+    for c, k in enumerate(cols):
+        got = rr.packed_column(Hp, k)
+        assert np.abs(got - ref[:, c]).max() <= 1e-10 * np.abs(ref[:, c]).max(), k
+    X = np.random.default_rng(seed + 1).standard_normal((V, n_hvp))
+    HX, AX = rr.packed_matvec(Hp, X)
+    for q in range(n_hvp):
+        want = rr.hessian_vector_product(Z, s, X[:, q])
+        assert (np.abs(HX[:, q] - want) <= 1e-10 * AX[:, q]).all(), q
+
+
+def test_column_helpers_against_the_dense_hessian():
+    """hessian_columns / hessian_vector_product / packed_column / packed_matvec restate the dense Hessian, and the packed check
+    rejects one wrong stored value."""
+    rng = np.random.default_rng(9)
+    s, Z = _spec_and_Z(rng, 6, 3, [0, 2], True, K=5, global_dim=2, state_first=False)
+    Hm = rr.hessian(Z, s)
+    V = Hm.shape[0]
+    cols = [0, 7, V - 1]
+    assert np.abs(rr.hessian_columns(Z, s, cols) - Hm[:, cols]).max() <= 1e-14 * np.abs(Hm).max()
+    Hp = rr.packed_upper(Hm)
+    Hs = np.triu(Hm) + np.triu(Hm, 1).T                              # the matrix the packed triangle holds
+    for k in range(V):
+        assert np.array_equal(rr.packed_column(Hp, k), Hs[:, k])
+    X = rng.standard_normal((V, 2))
+    HX, AX = rr.packed_matvec(Hp, X)
+    assert np.abs(HX - Hs @ X).max() <= 1e-13 * np.abs(Hm).max() and np.allclose(AX, np.abs(Hs) @ np.abs(X), rtol=1e-14)
+    assert np.abs(rr.hessian_vector_product(Z, s, X[:, 0]) - Hm @ X[:, 0]).max() <= 1e-12 * AX[:, 0].max()
+    _check_packed_hessian(Hp, Z, s, seed=1)
+    bad = Hp.copy()
+    bad[bad.size // 2] *= 1 + 1e-7
+    with pytest.raises(AssertionError):
+        _check_packed_hessian(bad, Z, s, seed=1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N,sub,T,K,free,state_first,global_dim", FORM_CASES, ids=[_form_id(c) for c in FORM_CASES])
+def test_gpu_launch_forms_match_the_restatement(qc, N, sub, T, K, free, state_first, global_dim):
+    """More than one pass of the per-knot loops (n = 17, 20), the LDS opt-in of one kernel (n = 25) and of both (n = 32),
+    kp = 64 (n = 1): L and the gradient against the restatement, the Hessian wherever V allows."""
+    rng = np.random.default_rng(N * 1009 + T)
+    s, Z = _spec_and_Z(rng, T, N, sub, free, K=K, global_dim=global_dim, state_first=state_first)
+    form = robust_launch(N, sub, free, s.nK)
+    check = hessian_check(form["V"])
+    obj = qc.UnitaryRobustnessObjective(_traj(qc, s, Z), H_error=s.H, subspace=sub, knots=s.nK, eval_hessian=check is not None)
+    try:
+        assert np.array_equal(obj.variables, rr.variables(s))
+        if check is None:
+            L, g = obj.L(Z), obj.grad_L(Z)
+        else:
+            L, g, Hv = obj.L_grad_hess(Z)
+        L_ref, g_ref = rr.loss(Z, s), rr.grad(Z, s)
+        assert abs(L - L_ref) <= 1e-12 * abs(L_ref)
+        assert g.shape == Z.shape and np.abs(g - g_ref).max() <= 1e-12 * np.abs(g_ref).max()
+        if global_dim:
+            assert not g[T * s.zdim:].any()
+        if check == "full":
+            H_ref = rr.packed_upper(rr.hessian(Z, s))
+            assert Hv.shape == H_ref.shape and np.abs(Hv - H_ref).max() <= 1e-10 * np.abs(H_ref).max()
+        elif check == "columns":
+            _check_packed_hessian(Hv, Z, s, seed=N + T)
+    finally:
+        obj.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N,sub,T,K,free,state_first,global_dim", HESS_BIG_CASES, ids=[_form_id(c) for c in HESS_BIG_CASES])
+def test_gpu_hessian_above_the_dense_check(qc, N, sub, T, K, free, state_first, global_dim):
+    """2000 < V <= the cap: whole columns and Hessian-vector products over every packed value; the largest size twice, bit for bit."""
+    import gc
+    rng = np.random.default_rng(N * 31 + T)
+    s, Z = _spec_and_Z(rng, T, N, sub, free, K=K, global_dim=global_dim, state_first=state_first)
+    obj = qc.UnitaryRobustnessObjective(_traj(qc, s, Z), H_error=s.H, subspace=sub, knots=s.nK)
+    try:
+        L, g, Hv = obj.L_grad_hess(Z)
+        assert abs(L - rr.loss(Z, s)) <= 1e-12 * abs(rr.loss(Z, s))
+        g_ref = rr.grad(Z, s)
+        assert np.abs(g - g_ref).max() <= 1e-12 * np.abs(g_ref).max()
+        _check_packed_hessian(Hv, Z, s, seed=N + T, n_hvp=3 if N == 2 else 2)
+        if N == 32:
+            L2, g2, H2 = obj.L_grad_hess(Z)
+            assert L2 == L and np.array_equal(g2, g) and np.array_equal(H2, Hv)
+            del H2
+    finally:
+        obj.close()
+        Hv = None
+        gc.collect()

@@ -187,3 +187,148 @@ def test_ket_rollout_fidelity(qc, oracle):
         want = abs(np.vdot(goal[:4] + 1j * goal[4:], v)) ** 2
         got = qc.rollout_fidelity(inp.traj, system, state_name=name)
         assert abs(got - want) < 1e-12, (name, got, want)
+
+
+# ---------------------------------------------------------------------------------------------- launch forms ----
+# qc_launch_rollout's host rule (qc_rollout.hip:253-273, the switch at :297-303) restated: the compiled matrix size NT (0: the
+# generic instantiation), the dynamic LDS of the propagator / chunk-total / chain launches (opt-in past 64 KB) and the chunking.
+def rollout_launch(n, nc, T):
+    n_int = T - 1
+    chunk = 1
+    while chunk * chunk < n_int:
+        chunk += 1
+    return dict(NT=n if n in (4, 8, 16, 32) else 0, lds_prop=32 * n * n, lds_tot=24 * n * n, lds_st=(2 * n * nc + n * n) * 8,
+                chunk=chunk, n_chunks=-(-n_int // chunk), n_int=n_int)
+
+
+def _herm(rng, N, scale=1.0):
+    X = rng.standard_normal((N, N)) + 1j * rng.standard_normal((N, N))
+    return scale * (X + X.conj().T) / 2
+
+
+def _random_system(qc, N, seed, m=2, scale=1.0):
+    rng = np.random.default_rng(seed)
+    return qc.QuantumSystem(_herm(rng, N, scale), [_herm(rng, N, scale) for _ in range(m)])
+
+
+def _open_system(qc, N, seed, gamma=0.1):
+    rng = np.random.default_rng(seed)
+    lower = np.diag(np.sqrt(np.arange(1, N)), 1).astype(complex)
+    return qc.OpenQuantumSystem(_herm(rng, N), [_herm(rng, N, 0.5)], [np.sqrt(gamma) * lower, np.sqrt(gamma / 2) * _herm(rng, N, 0.3)])
+
+
+# name: (state kind, levels N, T); the launch form each reaches is restated by rollout_launch
+ROLLOUT_CASES = {
+    "qutrit-T2": ("unitary", 3, 2),
+    "qutrit-T102": ("unitary", 3, 102),            # n_int = 101: chunk 11, the last chunk is short
+    "qutrit-T10001": ("unitary", 3, 10001),        # 100 chunks: the start chain runs 99 steps
+    "levels12-T101": ("unitary", 12, 101),
+    "levels23-T40": ("unitary", 23, 40),           # n = 46: propagator opt-in
+    "qubits5-T2": ("unitary", 32, 2),              # n = 64: propagator and chunk-total opt-in
+    "qubits5-T300": ("unitary", 32, 300),
+    "qubits5-ket-T65": ("ket", 32, 65),            # n = 64, nc = 1
+    "open5-T30": ("density", 5, 30),               # n = 2 * 25 = 50: propagator opt-in
+    "qubits3-T10001": ("unitary", 8, 10001),       # compiled NT = 16, long chains
+}
+
+
+def _rollout_case_launch(name):
+    kind, N, T = ROLLOUT_CASES[name]
+    n = 2 * N * N if kind == "density" else 2 * N
+    return rollout_launch(n, N if kind == "unitary" else 1, T)
+
+
+def test_rollout_launch_coverage():
+    """The GPU cases below reach the generic NT = 0 instantiation with and without the LDS opt-ins, a short last chunk, long start
+    chains, one state column at n = 64 and a compiled NT over 100 chunks."""
+    f = {k: _rollout_case_launch(k) for k in ROLLOUT_CASES}
+    assert rollout_launch(64, 64, 300)["lds_st"] > 65536 and rollout_launch(46, 46, 2)["lds_prop"] > 65536
+    assert rollout_launch(45, 45, 2)["lds_prop"] <= 65536 and rollout_launch(52, 52, 2)["lds_tot"] <= 65536 < rollout_launch(53, 53, 2)["lds_tot"]
+    zero = [v for v in f.values() if v["NT"] == 0]
+    assert any(v["lds_prop"] <= 65536 for v in zero)
+    assert any(65536 < v["lds_prop"] and v["lds_tot"] <= 65536 for v in zero)
+    assert any(v["lds_tot"] > 65536 and v["n_chunks"] > 1 for v in zero)
+    assert any(v["n_chunks"] >= 100 for v in zero) and any(v["n_chunks"] >= 100 for v in f.values() if v["NT"])
+    assert any(v["n_int"] % v["chunk"] for v in zero) and any(v["n_int"] == 1 for v in zero)
+    assert f["qubits5-ket-T65"]["NT"] == 0 and f["qubits5-ket-T65"]["lds_st"] == (2 * 64 + 64 * 64) * 8
+    assert f["open5-T30"]["NT"] == 0 and f["qubits3-T10001"]["NT"] == 16
+
+
+def _expm_chain(system, init, a, dts):
+    """x_{t+1} = expm(dt_t G(a_t)) x_t with scipy, in the real iso form the kernels use: (n nc) x T."""
+    n = 2 * system.state_levels
+    X = np.asarray(init, dtype=float).reshape(n, -1, order="F")
+    out = np.empty((X.size, a.shape[1]))
+    out[:, 0] = X.ravel(order="F")
+    for t in range(a.shape[1] - 1):
+        G = system.G_drift + sum(x * Gk for x, Gk in zip(a[:, t], system.G_drives))
+        X = sla.expm(dts[t] * G) @ X
+        out[:, t + 1] = X.ravel(order="F")
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(ROLLOUT_CASES))
+def test_rollout_launch_forms(qc, name):
+    """Every launch form of qc_launch_rollout against a scipy expm chain, plus unitarity / trace of the GPU states."""
+    kind, N, T = ROLLOUT_CASES[name]
+    rng = np.random.default_rng(list(ROLLOUT_CASES).index(name) * 7919 + T)
+    if kind == "density":
+        system = _open_system(qc, N, seed=N)
+    elif N == 32:
+        base = qc.multi_qubit_system(5)                                # strong drive: ||dt G||_1 well past 1/4, several squarings
+        system = qc.QuantumSystem(8.0 * base.H_drift, [6.0 * H for H in base.H_drives])
+    elif N == 8:
+        system = qc.multi_qubit_system(3)
+    else:
+        system = _random_system(qc, N, seed=N)
+    a = rng.uniform(-1, 1, (system.n_drives, T))
+    dts = rng.uniform(0.1, 0.3, T)
+    if kind == "unitary":
+        U0 = sla.expm(1j * _herm(rng, N))
+        init = qc.operator_to_iso_vec(U0)
+        got = qc.unitary_rollout(init, a, dts, system)
+    elif kind == "ket":
+        psi = rng.standard_normal(N) + 1j * rng.standard_normal(N)
+        psi /= np.linalg.norm(psi)
+        init = np.concatenate([psi.real, psi.imag])
+        got = qc.rollout(init, a, dts, system)
+    else:
+        v = rng.standard_normal(N) + 1j * rng.standard_normal(N)
+        rho0 = 0.7 * np.outer(v, v.conj()) / np.vdot(v, v).real + 0.3 * np.eye(N) / N
+        init = qc.density_to_iso_vec(rho0)
+        got = qc.open_rollout(init, a, dts, system)
+    ref = _expm_chain(system, init, a, dts)
+    assert got.shape == ref.shape
+    np.testing.assert_allclose(got, ref, rtol=1e-10, atol=1e-11)
+    if kind == "unitary":
+        U = got.reshape(N, 2, N, T, order="F")                        # [row, part, column, knot]
+        U = np.moveaxis(U[:, 0] + 1j * U[:, 1], -1, 0)
+        assert np.abs(np.swapaxes(U.conj(), 1, 2) @ U - np.eye(N)).max() < 1e-10
+    elif kind == "ket":
+        assert np.abs(np.sum(got * got, axis=0) - 1.0).max() < 1e-10
+    else:
+        tr = np.array([np.trace(qc.iso_vec_to_density(got[:, t])) for t in range(T)])
+        assert np.abs(tr - 1.0).max() < 1e-10
+    if T == 10001 or N == 32:
+        again = {"unitary": qc.unitary_rollout, "ket": qc.rollout}[kind](init, a, dts, system)
+        np.testing.assert_array_equal(again, got)
+
+
+@pytest.mark.gpu
+def test_rollout_through_a_multi_device_handle(qc, oracle):
+    """qc_rollout on a [0, 0, 0] multi-device handle is served by shard 0: the single handle's states bit for bit."""
+    inp = qc.config_inputs(3, T=101)
+    Z = inp.traj.datavec
+    N = inp.system.levels
+    init = qc.operator_to_iso_vec(sla.expm(1j * _herm(np.random.default_rng(4), N)))
+    one = qc.QuantumDynamics(inp.integrators, inp.traj)
+    many = qc.QuantumDynamics(inp.integrators, inp.traj, devices=[0, 0, 0])
+    try:
+        assert many.n_shards == 3
+        got = many.rollout(Z, init)
+        np.testing.assert_array_equal(got, one.rollout(Z, init))
+        np.testing.assert_allclose(got, oracle.rollout(problem_from_inputs(inp), Z, init), rtol=1e-10, atol=1e-11)
+    finally:
+        one.close()
+        many.close()
