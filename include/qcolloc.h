@@ -43,6 +43,9 @@
  *   DensityOperatorPureStateInfidelityObjective
  *   QuadraticRegularizer, MinimumTimeObjective           qc_terms_create / qc_terms_eval(_dev)
  *       (unitary_smooth_pulse_problem.jl:151-153, unitary_minimum_time_problem.jl:67-69)
+ *   QuadraticSmoothnessRegularizer, Pairwise-            qc_terms_create_ext / qc_terms_eval(_dev)
+ *   QuadraticRegularizer, L1Regularizer! (its cost)
+ *       (unitary_smooth_pulse_problem.jl:311-340, unitary_direct_sum_problem.jl:130-169, _problem_templates.jl:41-54)
  *   UnitaryRobustnessObjective(H_error=...)              qc_robust_create / qc_robust_eval(_dev)
  *       (unitary_robustness_problem.jl:46-49)
  *   unitary_rollout / rollout / open_rollout             qc_rollout / qc_rollout_dev
@@ -477,6 +480,41 @@ int qc_terms_hess_structure(const qc_terms* h, int64_t* rows, int64_t* cols, int
 int qc_terms_eval(qc_terms* h, const double* Z, double* J, double* grad, double* hvals);
 /* device buffers, asynchronous on `stream`; dgrad / dhvals may be NULL */
 int qc_terms_eval_dev(qc_terms* h, const double* dZ, double* dJ, double* dgrad, double* dhvals, void* stream);
+/* Extension terms of the same pass (x_t[j] = entry j of knot t, sc_t as above):
+ *   smoothness  1/2 sum_{t<T-1} sum_k R_k (x_{t+1}[s_k] - x_t[s_k])^2       `QuadraticSmoothnessRegularizer(name, traj, R)`
+ *                (no timestep inside the square; unitary_smooth_pulse_problem.jl:311-340)
+ *   pairwise    sum_t sum_p 1/2 Q_p sc_t^2 (x_t[a_p] - x_t[b_p])^2          `PairwiseQuadraticRegularizer(traj, Q, graph)`
+ *                (unitary_direct_sum_problem.jl:130-169; the edges of the graph flattened into scalar pairs, one Q per pair)
+ *   linear      sum_t sum_k w_k x_t[l_k]                                     the cost of `L1Regularizer!` on its slack entries
+ *                (_problem_templates.jl:41-54); the slack rows and s >= 0 stay with the caller
+ * All three are how QuantumCollocationCore 0.3 is recalled to define them (not vendored; julia/reconcile.jl).
+ * Indices lie inside the knot and are not the timestep; s_k and l_k do not repeat; a_p != b_p; an entry may appear in the
+ * regulariser list, the smoothness list and any number of pairs at once (gradient and Hessian are the sums).
+ * Hessian: the layout above is an exact prefix; after it come
+ *   smoothness  per knot t: [ (s_k,s_k) k=0..n_smooth-1 | (x_t[s_k], x_{t+1}[s_k]) k=0..n_smooth-1 (t < T-1 only) ],
+ *               n_smooth (2T - 1) values
+ *   pairwise    per knot: [ (a_p,a_p) | (b_p,b_p) | (min(a_p,b_p), max(a_p,b_p)) | (a_p,dt) | (b_p,dt) | (dt,dt) ], p = 0..n_pair-1
+ *               in each group; the last three groups exist only for QC_REG_DT_SCALED with a free timestep
+ * all upper-triangular (row <= col).  Entries repeat across blocks; a consumer sums duplicates (as MOI specifies).
+ * A NULL extension, or one with all three counts zero, gives a handle identical to qc_terms_create. */
+typedef struct qc_terms_ext {
+    int32_t n_smooth;
+    int32_t n_pair;
+    int32_t n_lin;
+    int32_t reserved0;
+    const int32_t* smooth_index; /* n_smooth offsets inside a knot */
+    const double* smooth_R;      /* n_smooth weights */
+    const int32_t* pair_a;       /* n_pair offsets inside a knot */
+    const int32_t* pair_b;       /* n_pair offsets inside a knot, pair_b[p] != pair_a[p] */
+    const double* pair_Q;        /* n_pair weights */
+    const int32_t* lin_index;    /* n_lin offsets inside a knot */
+    const double* lin_w;         /* n_lin weights */
+    int64_t reserved1[2];
+} qc_terms_ext;
+int64_t qc_sizeof_terms_ext(void);
+int qc_terms_desc_ext_hess_nnz(const qc_terms_desc* d, const qc_terms_ext* ext, int64_t* nnz);
+int qc_terms_desc_ext_hess_structure(const qc_terms_desc* d, const qc_terms_ext* ext, int64_t* rows, int64_t* cols, int one_based);
+int qc_terms_create_ext(const qc_terms_desc* d, const qc_terms_ext* ext, qc_terms** out);
 
 /* ---- robustness objective (UnitaryRobustnessObjective, reference unitary_robustness_problem.jl:46-49) ---------------- */
 /* A whole-trajectory term over the subspace block V_t = U_t[S, S] (n x n) of every knot t < K (n_knots):

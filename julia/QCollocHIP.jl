@@ -48,6 +48,13 @@ struct QCTermsDesc
     min_time_D::Float64; min_time_knots::Int64; device::Int32; reserved0::Int32
 end
 
+# mirror of `qc_terms_ext`
+struct QCTermsExt
+    n_smooth::Int32; n_pair::Int32; n_lin::Int32; reserved0::Int32
+    smooth_index::Ptr{Int32}; smooth_R::Ptr{Float64}; pair_a::Ptr{Int32}; pair_b::Ptr{Int32}; pair_Q::Ptr{Float64}
+    lin_index::Ptr{Int32}; lin_w::Ptr{Float64}; reserved1::NTuple{2,Int64}
+end
+
 # mirror of `qc_fidelity_desc`
 struct QCFidelityDesc
     kind::Int32; N::Int32; goal_iso::Ptr{Float64}; subspace::Ptr{Int32}; n_sub::Int32; form::Int32; n_phases::Int32; device::Int32
@@ -67,7 +74,7 @@ function __init__()
     abi == QC_ABI_VERSION || error("QCollocHIP: $(LIB[]) has ABI version $abi, this binding mirrors $QC_ABI_VERSION")
     # a stale mirror would corrupt memory silently: compare with the structs the library was compiled with
     for (sym, T) in ((:qc_sizeof_desc, QCDesc), (:qc_sizeof_dims, QCDims), (:qc_sizeof_terms_desc, QCTermsDesc),
-                     (:qc_sizeof_robust_desc, QCRobustDesc))
+                     (:qc_sizeof_robust_desc, QCRobustDesc), (:qc_sizeof_terms_ext, QCTermsExt))
         lib = ccall(dlsym(dlopen(LIB[]), sym), Int64, ())
         lib == sizeof(T) || error("QCollocHIP: $(T) has $(sizeof(T)) bytes, $(LIB[]) expects $lib (header / binding version mismatch)")
     end
@@ -532,28 +539,49 @@ knot_generation(dyn::HIPDynamics) = ccall((:qc_knot_generation, LIB[]), Int64, (
 # ---------------------------------------------------------------------------------------------------------------
 
 
-"""
-    regularizers(traj, names_and_R; D=0.0, device=0, dt_scaled=true)
-
-`names_and_R = [(:a, R_a), (:da, R_da), (:dda, R_dda)]` (scalars or vectors, unitary_smooth_pulse_problem.jl:151-153);
-`D` adds `MinimumTimeObjective(traj; D)` (unitary_minimum_time_problem.jl:67-69).  Returns `(L, ∇L, ∂²L, ∂²L_structure)`
-closures over one device handle.
-"""
-function regularizers(traj, names_and_R; D::Float64=0.0, device::Int=0, dt_scaled::Bool=true)
-    idx = Int32[]; R = Float64[]
+# component entries (0-based) and one weight per entry of `[(name, R), ...]`, summed where components repeat
+function entries_and_weights(traj, names_and_R)
+    w = Dict{Int32, Float64}()
     for (name, r) in names_and_R
         comps = collect(traj.components[name]) .- 1
-        append!(idx, Int32.(comps)); append!(R, r isa Number ? fill(Float64(r), length(comps)) : Float64.(r))
+        for (k, j) in enumerate(comps)
+            w[Int32(j)] = get(w, Int32(j), 0.0) + (r isa Number ? Float64(r) : Float64(r[k]))
+        end
     end
-    p = sortperm(idx); idx = idx[p]; R = R[p]
+    idx = sort!(collect(keys(w)))
+    return idx, [w[j] for j in idx]
+end
+
+"""
+    regularizers(traj, names_and_R; D=0.0, smooth=[], pairwise=[], linear=[], device=0, dt_scaled=true)
+
+`names_and_R = [(:a, R_a), (:da, R_da), (:dda, R_dda)]` (scalars or vectors, unitary_smooth_pulse_problem.jl:151-153);
+`D` adds `MinimumTimeObjective(traj; D)` (unitary_minimum_time_problem.jl:67-69).  The extension terms of the same pass
+(qc_terms_ext): `smooth = [(:dda, R)]` is `QuadraticSmoothnessRegularizer` (unitary_smooth_pulse_problem.jl:311-340),
+`pairwise = [((:dda1, :dda2), Q), ...]` one edge of `PairwiseQuadraticRegularizer(traj, Q, graph)`
+(unitary_direct_sum_problem.jl:130-169), `linear = [(:s1_Ũ⃗, R), (:s2_Ũ⃗, R)]` the cost of `L1Regularizer!` on its slacks
+(_problem_templates.jl:41-54).  Returns `(L, ∇L, ∂²L, ∂²L_structure)` closures over one device handle.
+"""
+function regularizers(traj, names_and_R; D::Float64=0.0, smooth=[], pairwise=[], linear=[], device::Int=0, dt_scaled::Bool=true)
+    idx, R = entries_and_weights(traj, names_and_R)
+    sidx, sR = entries_and_weights(traj, smooth)
+    lidx, lw = entries_and_weights(traj, linear)
+    pa = Int32[]; pb = Int32[]; pQ = Float64[]
+    for ((A, B), q) in pairwise
+        a = collect(traj.components[A]) .- 1; b = collect(traj.components[B]) .- 1
+        length(a) == length(b) || error("pairwise edge ($A, $B): the components differ in length")
+        append!(pa, Int32.(a)); append!(pb, Int32.(b)); append!(pQ, fill(Float64(q), length(a)))
+    end
     free_time = traj.timestep isa Symbol
     h = Ref{Ptr{Cvoid}}(C_NULL)
-    GC.@preserve idx R begin
+    GC.@preserve idx R sidx sR lidx lw pa pb pQ begin
         desc = Ref(QCTermsDesc(traj.T, traj.dim, free_time ? first(traj.components[traj.timestep]) - 1 : -1, traj.global_dim,
                                free_time ? 0.0 : Float64(traj.timestep), length(idx), dt_scaled ? 2 : 3,   # QC_REG_DT_SCALED = 2 (templates pass timestep_name=), QC_REG_PLAIN = 3 (docstring form); 0 / 1 are retired
                                pointer(idx), pointer(R), C_NULL, D, D == 0.0 ? 0 : traj.T - 1, device, 0))
-        rc = ccall((:qc_terms_create, LIB[]), Cint, (Ref{QCTermsDesc}, Ref{Ptr{Cvoid}}), desc, h)
-        rc == 0 || error("qc_terms_create: " * unsafe_string(ccall((:qc_terms_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
+        ext = Ref(QCTermsExt(length(sidx), length(pa), length(lidx), 0, pointer(sidx), pointer(sR), pointer(pa), pointer(pb), pointer(pQ),
+                             pointer(lidx), pointer(lw), (0, 0)))
+        rc = ccall((:qc_terms_create_ext, LIB[]), Cint, (Ref{QCTermsDesc}, Ref{QCTermsExt}, Ref{Ptr{Cvoid}}), desc, ext, h)
+        rc == 0 || error("qc_terms_create_ext: " * unsafe_string(ccall((:qc_terms_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
     end
     nnz = Ref{Int64}(0)
     ccall((:qc_terms_hess_nnz, LIB[]), Cint, (Ptr{Cvoid}, Ref{Int64}), h[], nnz)

@@ -231,6 +231,42 @@ rob_hit = findfirst(((_, v),) -> isapprox(v, rob_core; rtol=1e-12), rob_guess)
 push!(verdicts, "robustness objective: knots and normalisation" => (isnothing(rob_hit) ? "NONE of the guesses: $rob_core" : rob_guess[rob_hit][1]))
 push!(verdicts, "robustness objective has a Hessian (this library: exact, dense)" => (robObj.∂²L !== nothing))
 
+# ---- extension terms of the terms pass (qc_terms_ext) and the leakage template: smoothness with or without Δt, the pairwise
+#      weighting, the L1 cost weighting, the slack names / order / row form, and the leakage index set -------------------------------
+Z⃗ = traj.datavec
+dts = traj.timestep isa Symbol ? vec(traj[traj.timestep]) : fill(Float64(traj.timestep), traj.T)
+sm_core = QuadraticSmoothnessRegularizer(:dda, traj, 10.0).L(Z⃗, traj)
+dd = diff(traj[:dda]; dims=2)
+sm_guess = [("1/2 sum R (x_t+1 - x_t)^2, no dt (this library)", 0.5 * 10.0 * sum(abs2, dd)),
+            ("1/2 sum R (dt_t (x_t+1 - x_t))^2", 0.5 * 10.0 * sum(abs2, dd .* dts[1:end-1]'))]
+sm_hit = findfirst(((_, v),) -> isapprox(v, sm_core; rtol=1e-12), sm_guess)
+push!(verdicts, "smoothness regulariser" => (isnothing(sm_hit) ? "NONE of the guesses: $sm_core" : sm_guess[sm_hit][1]))
+trD = probD.trajectory
+pw_core = PairwiseQuadraticRegularizer(trD, 100.0, [(:dda1, :dda2)]).L(trD.datavec, trD)
+dD = trD[:dda1] .- trD[:dda2]
+dtD = trD.timestep isa Symbol ? vec(trD[trD.timestep]) : fill(Float64(trD.timestep), trD.T)
+pw_guess = [("1/2 sum Q (dt_t d_t)^2 (QC_REG_DT_SCALED, this library's default)", 0.5 * 100.0 * sum(abs2, dD .* dtD')),
+            ("1/2 sum Q d_t^2 (QC_REG_PLAIN)", 0.5 * 100.0 * sum(abs2, dD))]
+pw_hit = findfirst(((_, v),) -> isapprox(v, pw_core; rtol=1e-12), pw_guess)
+push!(verdicts, "pairwise regulariser weighting" => (isnothing(pw_hit) ? "NONE of the guesses: $pw_core" : pw_guess[pw_hit][1]))
+a4 = annihilate(4)
+sys4 = QuantumSystem([(a4 + a4') / 2, (a4 - a4') / (2im)])
+U4 = EmbeddedOperator(GATES[:H], sys4)
+leak_core = get_leakage_indices(U4)
+push!(verdicts, "leakage indices (this library, 1-based: [3, 4, 7, 8, 11, 12, 15, 16])" => (sort(collect(leak_core)) == [3, 4, 7, 8, 11, 12, 15, 16] ? "same" : "DIFFER: $(collect(leak_core))"))
+probL = UnitarySmoothPulseProblem(sys4, U4, 8, 0.2; ipopt_options=IpoptOptions(print_level=1),
+                                  piccolo_options=PiccoloOptions(verbose=false, leakage_suppression=true, R_leakage=0.1))
+probN = UnitarySmoothPulseProblem(sys4, U4, 8, 0.2; ipopt_options=IpoptOptions(print_level=1), piccolo_options=PiccoloOptions(verbose=false))
+slacks = [n for n in probL.trajectory.names if !(n in probN.trajectory.names)]
+push!(verdicts, "L1 slack components, in trajectory order (this library: s1_Ũ⃗, s2_Ũ⃗ appended to the controls)" => slacks)
+trL = probL.trajectory
+ZL = trL.datavec
+l1_diff = Problems.get_objective(probL).L(ZL, trL) - Problems.get_objective(probN).L(probN.trajectory.datavec, probN.trajectory)
+l1_ours = 0.1 * sum(trL[slacks[1]]) + 0.1 * sum(trL[slacks[2]])
+push!(verdicts, "L1 cost weighting: R sum_t (s1 + s2), no dt (this library)" => (isapprox(l1_diff, l1_ours; rtol=1e-10) ? "same" : "DIFFER: $l1_diff vs $l1_ours"))
+push!(verdicts, "L1 slack rows: count T * n_leak, knot-major x - s1 + s2 = 0 (this library)" =>
+      [(typeof(c), hasproperty(c, :dim) ? c.dim : missing) for c in probL.constraints])
+
 println("\nreconcile.jl -- verdicts for INTEGRATION.md \"Choices this repository cannot verify\":")
 for (k, v) in verdicts
     println("  ", rpad(k, 72), " => ", v)

@@ -143,6 +143,23 @@ class qc_terms_desc(C.Structure):
     ]
 
 
+class qc_terms_ext(C.Structure):
+    _fields_ = [
+        ("n_smooth", C.c_int32),
+        ("n_pair", C.c_int32),
+        ("n_lin", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("smooth_index", C.POINTER(C.c_int32)),
+        ("smooth_R", _c_double_p),
+        ("pair_a", C.POINTER(C.c_int32)),
+        ("pair_b", C.POINTER(C.c_int32)),
+        ("pair_Q", _c_double_p),
+        ("lin_index", C.POINTER(C.c_int32)),
+        ("lin_w", _c_double_p),
+        ("reserved1", C.c_int64 * 2),
+    ]
+
+
 class qc_robust_desc(C.Structure):
     _fields_ = [
         ("T", C.c_int64),
@@ -171,6 +188,7 @@ _DIMS_P = C.POINTER(qc_dims_t)
 _H = C.c_void_p
 _TDESC_P = C.POINTER(qc_terms_desc)
 _RDESC_P = C.POINTER(qc_robust_desc)
+_TEXT_P = C.POINTER(qc_terms_ext)
 SYMBOLS = {
     "qc_operator_to_iso_vec": (C.c_int, [C.c_int32, _c_double_p, _c_double_p, _c_double_p]),
     "qc_iso_vec_to_operator": (C.c_int, [C.c_int32, _c_double_p, _c_double_p, _c_double_p]),
@@ -235,6 +253,10 @@ SYMBOLS = {
     "qc_terms_hess_structure": (C.c_int, [_H, _c_int64_p, _c_int64_p, C.c_int]),
     "qc_terms_eval": (C.c_int, [_H, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "qc_terms_eval_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qc_sizeof_terms_ext": (C.c_int64, []),
+    "qc_terms_desc_ext_hess_nnz": (C.c_int, [_TDESC_P, _TEXT_P, _c_int64_p]),
+    "qc_terms_desc_ext_hess_structure": (C.c_int, [_TDESC_P, _TEXT_P, _c_int64_p, _c_int64_p, C.c_int]),
+    "qc_terms_create_ext": (C.c_int, [_TDESC_P, _TEXT_P, C.POINTER(_H)]),
     "qc_robust_desc_n_vars": (C.c_int, [_RDESC_P, _c_int64_p]),
     "qc_robust_desc_vars": (C.c_int, [_RDESC_P, _c_int64_p]),
     "qc_robust_desc_hess_nnz": (C.c_int, [_RDESC_P, _c_int64_p]),
@@ -279,7 +301,7 @@ def _load() -> C.CDLL:
                           "(constants were renumbered between minor versions; stale build? run __graft_entry__.build())")
     # the struct mirrors above must be the structs this build of the library was compiled with
     for name, mirror in (("qc_sizeof_desc", qc_desc), ("qc_sizeof_dims", qc_dims_t), ("qc_sizeof_terms_desc", qc_terms_desc),
-                         ("qc_sizeof_robust_desc", qc_robust_desc)):
+                         ("qc_sizeof_robust_desc", qc_robust_desc), ("qc_sizeof_terms_ext", qc_terms_ext)):
         if getattr(lib, name)() != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: {name}() = {getattr(lib, name)()} but the Python mirror has {C.sizeof(mirror)} bytes "
                               "(stale build? run __graft_entry__.build())")

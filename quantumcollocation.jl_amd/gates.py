@@ -74,3 +74,11 @@ class EmbeddedOperator:
         out = np.diag(np.full(self.N, fill, dtype=complex))
         out[np.ix_(self.subspace, self.subspace)] = self.operator
         return out
+
+    def leakage_indices(self) -> np.ndarray:
+        """Entries of the iso-vec `Ũ⃗ = vec(vcat(real(U), imag(U)))` (column-major, N x N) that carry population leaving the
+        subspace: row outside it, column inside it, real and imaginary parts, ascending.  PiccoloQuantumObjects'
+        `get_leakage_indices(op)` is recalled to pick this set (not vendored; INTEGRATION.md, table of choices)."""
+        S = set(self.subspace)
+        out = [c * 2 * self.N + part * self.N + r for c in self.subspace for part in (0, 1) for r in range(self.N) if r not in S]
+        return np.array(sorted(out), dtype=np.int64)

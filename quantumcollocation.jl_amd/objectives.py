@@ -9,8 +9,9 @@ Loss per the reference docstring (unitary_smooth_pulse_problem.jl:23-28): l = |1
 Only the last knot's state enters; gradients/Hessians are returned on those `2N^2` variables together with
 their global indices.
 
-Whole-trajectory terms through `qc_terms_*`: `QuadraticRegularizer`, `MinimumTimeObjective`
-(summed into one `TrajectoryObjective`) and the constant `TimeStepsAllEqualConstraint`; through `qc_robust_*`:
+Whole-trajectory terms through `qc_terms_*`: `QuadraticRegularizer`, `MinimumTimeObjective`,
+`QuadraticSmoothnessRegularizer`, `PairwiseQuadraticRegularizer`, `L1Regularizer` (summed into one `TrajectoryObjective`) and
+the constant `TimeStepsAllEqualConstraint` / `L1SlackConstraint`; through `qc_robust_*`:
 `UnitaryRobustnessObjective` (unitary_robustness_problem.jl:46-49).
 """
 from __future__ import annotations
@@ -297,6 +298,110 @@ class MinimumTimeObjective:
         return TrajectoryObjectiveSpec([self]) + other
 
 
+class QuadraticSmoothnessRegularizer:
+    """`QuadraticSmoothnessRegularizer(name, traj, R)` (reference test "Additional Objective",
+    unitary_smooth_pulse_problem.jl:311-340): 1/2 sum_{t<T-1} sum_i R_i (x_{t+1,i} - x_{t,i})^2, no timestep inside the square.
+    A description only; add it to a `TrajectoryObjective` to evaluate it."""
+
+    def __init__(self, name: str, traj: NamedTrajectory, R):
+        self.name = name
+        self.dim = len(traj.components[name])
+        R = np.asarray(R, dtype=np.float64)
+        self.R = np.full(self.dim, float(R)) if R.ndim == 0 else R.copy()
+        if self.R.shape != (self.dim,):
+            raise ValueError(f"R has shape {self.R.shape}, expected ({self.dim},)")
+
+    def __add__(self, other):
+        return TrajectoryObjectiveSpec([self]) + other
+
+
+class PairwiseQuadraticRegularizer:
+    """`PairwiseQuadraticRegularizer(traj, Q, graph)` (reference unitary_direct_sum_problem.jl:130-169): for every edge
+    (A, B) of `graph`, two components of equal length, sum_t 1/2 Q_e sc_t^2 ||x_t[A] - x_t[B]||^2 with the weighting of the
+    quadratic regulariser.  `Q` is a scalar or one value per edge.  A description only."""
+
+    def __init__(self, traj: NamedTrajectory, Q, graph):
+        self.graph = [(str(a), str(b)) for a, b in graph]
+        Q = np.asarray(Q, dtype=np.float64)
+        self.Q = np.full(len(self.graph), float(Q)) if Q.ndim == 0 else Q.copy()
+        if self.Q.shape != (len(self.graph),):
+            raise ValueError(f"Q has shape {self.Q.shape}, expected one value per edge ({len(self.graph)},)")
+        for a, b in self.graph:
+            if len(traj.components[a]) != len(traj.components[b]):
+                raise ValueError(f"edge ({a}, {b}): the components differ in length")
+
+    def pairs(self, traj: NamedTrajectory):
+        """(a, b, Q): the edges flattened into scalar pairs of knot offsets, edge after edge."""
+        a = [np.asarray(traj.components[x]) for x, _ in self.graph]
+        b = [np.asarray(traj.components[y]) for _, y in self.graph]
+        Q = [np.full(len(ai), q) for ai, q in zip(a, self.Q)]
+        cat = lambda v, dt: np.concatenate(v).astype(dt) if v else np.zeros(0, dtype=dt)
+        return cat(a, np.int32), cat(b, np.int32), cat(Q, np.float64)
+
+    def __add__(self, other):
+        return TrajectoryObjectiveSpec([self]) + other
+
+
+def slack_names(name: str):
+    """Names of the two slack components of `L1Regularizer!` on component `name` (a choice of this build: QuantumCollocationCore,
+    which names them, is not vendored; INTEGRATION.md, table of choices)."""
+    return f"s1_{name}", f"s2_{name}"
+
+
+class L1Regularizer:
+    """The cost of `L1Regularizer!(constraints, name, traj; R_value, indices)` (reference _problem_templates.jl:41-54):
+    sum_t sum_i R_i (s1_{t,i} + s2_{t,i}) over the two slack components of `name` (`slack_names(name)`), which the problem
+    templates add to the trajectory.  Linear: constant gradient, no Hessian.  The slack rows are `L1SlackConstraint`; the bounds
+    s >= 0 stay with the solver.  A description only."""
+
+    def __init__(self, name: str, traj: NamedTrajectory, R):
+        self.name = name
+        self.slacks = slack_names(name)
+        self.dim = len(traj.components[self.slacks[0]])
+        if len(traj.components[self.slacks[1]]) != self.dim:
+            raise ValueError("the two slack components differ in length")
+        R = np.asarray(R, dtype=np.float64)
+        self.R = np.full(self.dim, float(R)) if R.ndim == 0 else R.copy()
+        if self.R.shape != (self.dim,):
+            raise ValueError(f"R has shape {self.R.shape}, expected ({self.dim},)")
+
+    def __add__(self, other):
+        return TrajectoryObjectiveSpec([self]) + other
+
+
+class L1SlackConstraint:
+    """The slack rows of `L1Regularizer!` (reference _problem_templates.jl:41-54): x_t[i_k] - s1_t[k] + s2_t[k] = 0 for every knot
+    t and every entry i_k of `indices` (offsets inside component `name`; default: all of it), knot-major.  Linear with a constant
+    Jacobian (+1, -1, +1), no Hessian: described on the host, like `TimeStepsAllEqualConstraint`."""
+
+    def __init__(self, name: str, traj: NamedTrajectory, indices=None):
+        comp = np.asarray(traj.components[name])
+        idx = np.arange(comp.size) if indices is None else np.asarray(indices, dtype=np.int64)
+        s1, s2 = (np.asarray(traj.components[n]) for n in slack_names(name))
+        if s1.size != idx.size or s2.size != idx.size:
+            raise ValueError(f"the slack components of {name} must have one entry per index ({idx.size})")
+        n = idx.size
+        self.dim = traj.T * n
+        t = np.repeat(np.arange(traj.T, dtype=np.int64) * traj.dim, n)
+        self.x_indices = t + np.tile(comp[idx], traj.T)
+        self.s1_indices = t + np.tile(s1, traj.T)
+        self.s2_indices = t + np.tile(s2, traj.T)
+        rows = np.repeat(np.arange(self.dim, dtype=np.int64), 3)
+        cols = np.stack([self.x_indices, self.s1_indices, self.s2_indices], axis=1).ravel()
+        self.jac_structure = (rows, cols)
+        self.jac_values = np.tile([1.0, -1.0, 1.0], self.dim)
+
+    def g(self, Z) -> np.ndarray:
+        Z = np.asarray(Z, dtype=np.float64)
+        return Z[self.x_indices] - Z[self.s1_indices] + Z[self.s2_indices]
+
+    def dg(self, Z=None) -> np.ndarray:
+        return self.jac_values
+
+
+_EXT_TERMS = (QuadraticSmoothnessRegularizer, PairwiseQuadraticRegularizer, L1Regularizer)
+
+
 class TrajectoryObjectiveSpec:
     def __init__(self, terms):
         self.terms = list(terms)
@@ -307,7 +412,8 @@ class TrajectoryObjectiveSpec:
 
 
 class TrajectoryObjective:
-    """Sum of `QuadraticRegularizer` / `MinimumTimeObjective` terms evaluated in one pass over the knots on the GPU.
+    """Sum of `QuadraticRegularizer` / `MinimumTimeObjective` / `QuadraticSmoothnessRegularizer` /
+    `PairwiseQuadraticRegularizer` / `L1Regularizer` terms evaluated in one pass over the knots on the GPU.
     `L(Z)`, `grad_L(Z)` (dense, length `len(Z)`), `hess_L(Z)` (values on `hess_structure`); `"∇L"`, `"∂²L"`,
     `"∂²L_structure"` resolve to the same members."""
     _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
@@ -317,7 +423,7 @@ class TrajectoryObjective:
         (unitary_smooth_pulse_problem.jl:151-153); False: the docstring's 1/2 sum_t R x_t^2 (QC_REG_PLAIN)."""
         if isinstance(terms, TrajectoryObjectiveSpec):
             terms = terms.terms
-        elif isinstance(terms, (QuadraticRegularizer, MinimumTimeObjective)):
+        elif isinstance(terms, (QuadraticRegularizer, MinimumTimeObjective) + _EXT_TERMS):
             terms = [terms]
         self.traj = traj
         w = np.zeros(traj.dim)
@@ -326,6 +432,9 @@ class TrajectoryObjective:
         any_base = False
         D = 0.0
         ts_names = set()
+        ws, used_s = np.zeros(traj.dim), np.zeros(traj.dim, dtype=bool)
+        wl, used_l = np.zeros(traj.dim), np.zeros(traj.dim, dtype=bool)
+        pairs = []
         for term in terms:
             if isinstance(term, QuadraticRegularizer):
                 idx = np.asarray(traj.components[term.name])
@@ -341,6 +450,17 @@ class TrajectoryObjective:
             elif isinstance(term, MinimumTimeObjective):
                 D += term.D
                 ts_names.add(term.timestep_name)
+            elif isinstance(term, QuadraticSmoothnessRegularizer):
+                idx = np.asarray(traj.components[term.name])
+                ws[idx] += term.R
+                used_s[idx] = True
+            elif isinstance(term, PairwiseQuadraticRegularizer):
+                pairs.append(term.pairs(traj))
+            elif isinstance(term, L1Regularizer):
+                for nm in term.slacks:
+                    idx = np.asarray(traj.components[nm])
+                    wl[idx] += term.R
+                    used_l[idx] = True
             else:
                 raise TypeError(f"unsupported term {type(term).__name__}")
         if len(ts_names) > 1:
@@ -364,9 +484,29 @@ class TrajectoryObjective:
         d.min_time_knots = traj.T - 1 if D != 0.0 else 0
         d.device = device
         self._desc = d
+        self._s_index = np.ascontiguousarray(np.nonzero(used_s)[0], dtype=np.int32)
+        self._s_R = np.ascontiguousarray(ws[self._s_index])
+        self._l_index = np.ascontiguousarray(np.nonzero(used_l)[0], dtype=np.int32)
+        self._l_w = np.ascontiguousarray(wl[self._l_index])
+        cat = lambda k, dt: np.ascontiguousarray(np.concatenate([p[k] for p in pairs]) if pairs else np.zeros(0), dtype=dt)
+        self._p_a, self._p_b, self._p_Q = cat(0, np.int32), cat(1, np.int32), cat(2, np.float64)
+        self.has_ext = bool(self._s_index.size or self._l_index.size or self._p_a.size)
+        self._ext = None
+        if self.has_ext:
+            x = _lib.qc_terms_ext()
+            x.n_smooth, x.n_pair, x.n_lin = self._s_index.size, self._p_a.size, self._l_index.size
+            ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32)) if a.size else None
+            dp = lambda a: _lib.dptr(a) if a.size else None
+            x.smooth_index, x.smooth_R = ip(self._s_index), dp(self._s_R)
+            x.pair_a, x.pair_b, x.pair_Q = ip(self._p_a), ip(self._p_b), dp(self._p_Q)
+            x.lin_index, x.lin_w = ip(self._l_index), dp(self._l_w)
+            self._ext = x
         self.Z_len = traj.T * traj.dim + traj.global_dim
         self._h = C.c_void_p()
-        rc = _lib.lib.qc_terms_create(C.byref(d), C.byref(self._h))
+        if self.has_ext:
+            rc = _lib.lib.qc_terms_create_ext(C.byref(d), C.byref(self._ext), C.byref(self._h))
+        else:
+            rc = _lib.lib.qc_terms_create(C.byref(d), C.byref(self._h))
         if rc != _lib.QC_OK:
             raise _lib.QCollocError(rc, _lib.lib.qc_terms_last_error(None).decode())
         nnz = C.c_int64()

@@ -347,3 +347,140 @@ def unitary_robustness_problem(H_error, inputs: HotPathInputs, *, objectives=(),
         con = FinalUnitaryFreePhaseFidelityConstraint(unitary_name, phase_name, phase_operators, final_fidelity, traj, subspace=sub,
                                                       device=device)
     return ControlProblemInputs(inputs.system, traj, list(inputs.integrators), list(objectives) + [rob], list(constraints) + [con])
+
+
+def add_l1_slacks(inp: HotPathInputs, name: str, indices, *, integrator: str = "pade", pade_order: int = 4) -> HotPathInputs:
+    """The trajectory side of `L1Regularizer!(constraints, name, traj; indices)` (reference _problem_templates.jl:41-54) on the
+    inputs of a unitary smooth-pulse problem: two slack components `slack_names(name)` with one entry per index, appended to the
+    controls and started at max(+-x, 0) so that their rows x - s1 + s2 = 0 hold (as `unitary_bang_bang_inputs` does), and the
+    integrators rebuilt on the wider knots.  The dynamics never read the slacks."""
+    from .objectives import slack_names
+    traj = inp.traj
+    x = np.array(traj[name])[np.asarray(indices, dtype=np.int64), :]
+    s1, s2 = slack_names(name)
+    comps = {nm: np.array(traj[nm]) for nm in traj.names}
+    comps[s1], comps[s2] = np.maximum(x, 0.0), np.maximum(-x, 0.0)
+    traj = NamedTrajectory(comps, controls=tuple(traj.controls) + (s1, s2), timestep=traj.timestep, initial=traj.initial, goal=traj.goal)
+    if integrator == "pade":
+        U_int = UnitaryPadeIntegrator("Ũ⃗", "a", inp.system, traj, order=pade_order)
+    elif integrator == "exponential":
+        U_int = UnitaryExponentialIntegrator("Ũ⃗", "a", inp.system, traj)
+    else:
+        raise ValueError("integrator must be one of ('pade', 'exponential')")
+    return HotPathInputs(inp.system, traj, [U_int, DerivativeIntegrator("a", "da", traj), DerivativeIntegrator("da", "dda", traj)])
+
+
+def unitary_smooth_pulse_problem(system: QuantumSystem, U_goal, T: int, dt: float = 0.2, *, Q: float = 100.0, R: float = 1e-2,
+                                 R_a=None, R_da=None, R_dda=None, leakage_suppression: bool = False, R_leakage: float = 1e-1,
+                                 additional_objective=None, timesteps_all_equal: bool = False, integrator: str = "pade",
+                                 pade_order: int = 4, free_time: bool = True, device: int = 0, seed: int = SEED) -> ControlProblemInputs:
+    """`UnitarySmoothPulseProblem(system, U_goal, T, dt; Q, R, R_a, R_da, R_dda, leakage_suppression, R_leakage,
+    additional_objective, ...)` (reference unitary_smooth_pulse_problem.jl:70-191 with `apply_piccolo_options!`,
+    _problem_templates.jl:31-75): the infidelity objective (on the subspace of an `EmbeddedOperator` goal) plus ONE
+    `TrajectoryObjective` holding the regularisers on a / da / dda, `additional_objective` and, with `leakage_suppression`, the
+    `L1Regularizer` on the leakage entries of `Ũ⃗` (`EmbeddedOperator.leakage_indices`).  Leakage suppression appends two slack
+    components `slack_names("Ũ⃗")` to the controls, started at max(+-x, 0) (as `unitary_bang_bang_inputs` does), and their rows
+    `L1SlackConstraint` to the constraints; the bounds s >= 0 are the solver's.  An `EmbeddedOperator` goal starts its geodesic
+    toward `embed(fill=1)`."""
+    from .gates import EmbeddedOperator
+    from .objectives import (L1Regularizer, L1SlackConstraint, QuadraticRegularizer, TimeStepsAllEqualConstraint, TrajectoryObjective,
+                             UnitaryInfidelityObjective)
+    emb = U_goal if isinstance(U_goal, EmbeddedOperator) else None
+    U = emb.embed(fill=1.0) if emb is not None else np.asarray(U_goal, dtype=complex)
+    sub = emb.subspace if emb is not None else None
+    inp = unitary_smooth_pulse_inputs(system, U, T, dt, free_time=free_time, integrator=integrator, pade_order=pade_order, seed=seed)
+    traj, integrators = inp.traj, inp.integrators
+    constraints = []
+    if leakage_suppression:
+        if emb is None:
+            raise ValueError("leakage suppression needs an EmbeddedOperator goal (its leakage indices)")
+        leak = emb.leakage_indices()
+        inp = add_l1_slacks(inp, "Ũ⃗", leak, integrator=integrator, pade_order=pade_order)
+        traj, integrators = inp.traj, inp.integrators
+        constraints.append(L1SlackConstraint("Ũ⃗", traj, leak))
+    if free_time and timesteps_all_equal:
+        constraints.append(TimeStepsAllEqualConstraint(traj.timestep, traj))
+    spec = (QuadraticRegularizer("a", traj, R if R_a is None else R_a) + QuadraticRegularizer("da", traj, R if R_da is None else R_da)
+            + QuadraticRegularizer("dda", traj, R if R_dda is None else R_dda))
+    if additional_objective is not None:
+        spec = spec + additional_objective
+    if leakage_suppression:
+        spec = spec + L1Regularizer("Ũ⃗", traj, R_leakage)
+    objectives = [UnitaryInfidelityObjective("Ũ⃗", traj, Q, subspace=sub, device=device),
+                  TrajectoryObjective(spec, traj, device=device)]
+    return ControlProblemInputs(system, traj, integrators, objectives, constraints)
+
+
+def direct_sum_graph(labels, graph, boundary_values, Q_symb: str, names):
+    """The edges of `UnitaryDirectSumProblem` (reference unitary_direct_sum_problem.jl:75-100) as component names: returns
+    (edges, boundary) with edges [(name_i, name_j)] and boundary [(name, baseline)].  graph=None: the chain over the labels.
+    Otherwise every edge is either two labels -- (Q_symb+l1, Q_symb+l2) -- a label and a key of `boundary_values` -- a boundary
+    edge, a baseline regulariser on Q_symb+label -- or two component names of the merged trajectory (the reference's Symbol
+    graph); anything else is a ValueError."""
+    labels = [str(l) for l in labels]
+    boundary_values = boundary_values or {}
+    if graph is None:
+        return [(Q_symb + a, Q_symb + b) for a, b in zip(labels[:-1], labels[1:])], []
+    edges, boundary = [], []
+    for e in graph:
+        a, b = (str(x) for x in e)
+        if a in labels and b in labels:
+            edges.append((Q_symb + a, Q_symb + b))
+        elif a in boundary_values and b in labels:
+            boundary.append((Q_symb + b, np.asarray(boundary_values[a], dtype=np.float64)))
+        elif a in labels and b in boundary_values:
+            boundary.append((Q_symb + a, np.asarray(boundary_values[b], dtype=np.float64)))
+        elif a in names and b in names:
+            edges.append((a, b))
+        else:
+            raise ValueError(f"edge ({a}, {b}): edge labels must be in the problem labels or the boundary values, or be component names")
+    return edges, boundary
+
+
+def unitary_direct_sum_problem(parts, final_fidelity: float, *, labels=None, graph=None, boundary_values=None, Q=100.0,
+                               Q_symb: str = "dda", R: float = 1e-2, R_a=None, R_da=None, R_dda=None, R_b=None,
+                               fidelity_cost: bool = False, subspace=None, drive_reset_ratio: float = 0.5,
+                               drive_derivative_sigma: float = 0.01, seed: int = SEED, device: int = 0) -> ControlProblemInputs:
+    """`UnitaryDirectSumProblem(probs, final_fidelity; prob_labels, graph, boundary_values, Q, Q_symb, R, R_a, R_da, R_dda, R_b,
+    drive_reset_ratio, fidelity_cost, subspace)` (reference unitary_direct_sum_problem.jl:48-186) on the hot-path inputs of its
+    members (`unitary_direct_sum_inputs`): the members' controls are mixed with a fresh draw (`drive_reset_ratio`, :106-123),
+    the graph becomes a `PairwiseQuadraticRegularizer` (`direct_sum_graph`), boundary edges baseline regularisers with weight
+    R_b, every member gets its a / da / dda regularisers and a `FinalUnitaryFidelityConstraint`, and with `fidelity_cost` an
+    infidelity objective (weight Q, or Q[0] for a per-edge Q).  A baseline regulariser and a plain one on the same component
+    cannot share a terms handle, so the baselines then go into a second `TrajectoryObjective`."""
+    from .objectives import (FinalUnitaryFidelityConstraint, PairwiseQuadraticRegularizer, QuadraticRegularizer, TrajectoryObjective,
+                             UnitaryInfidelityObjective)
+    from .trajectory_initialization import initialize_control_trajectory
+    labels = [str(i + 1) for i in range(len(parts))] if labels is None else [str(l) for l in labels]
+    boundary_values = {str(k): v for k, v in (boundary_values or {}).items()}
+    if set(boundary_values) & set(labels):
+        raise ValueError("boundary value keys cannot be problem labels")
+    if not 0.0 <= drive_reset_ratio <= 1.0:
+        raise ValueError("drive_reset_ratio must be in [0, 1]")
+    inp = unitary_direct_sum_inputs(parts, labels)
+    traj = inp.traj
+    edges, boundary = direct_sum_graph(labels, graph, boundary_values, Q_symb, traj.names)
+    if drive_reset_ratio > 0:
+        rng = np.random.default_rng(seed)
+        for l in labels:
+            m = len(traj.components["a" + l])
+            fresh = initialize_control_trajectory(m, 2, traj.T, [1.0] * m, drive_derivative_sigma, rng)
+            for nm, v in zip(("a", "da", "dda"), fresh):
+                traj[nm + l][:, :] = (1 - drive_reset_ratio) * traj[nm + l] + drive_reset_ratio * v
+    R_b = R if R_b is None else R_b
+    main = [PairwiseQuadraticRegularizer(traj, Q, edges)] if edges else []
+    for l in labels:
+        main += [QuadraticRegularizer("a" + l, traj, R if R_a is None else R_a), QuadraticRegularizer("da" + l, traj, R if R_da is None else R_da),
+                 QuadraticRegularizer("dda" + l, traj, R if R_dda is None else R_dda)]
+    base = [QuadraticRegularizer(nm, traj, R_b, baseline=val) for nm, val in boundary]
+    plain = {t.name for t in main if isinstance(t, QuadraticRegularizer)}
+    if any(b.name in plain for b in base):
+        objectives = [TrajectoryObjective(main, traj, device=device), TrajectoryObjective(base, traj, device=device)]
+    else:
+        objectives = [TrajectoryObjective(main + base, traj, device=device)]
+    sub = None if subspace is None else [int(s) for s in subspace]
+    constraints = [FinalUnitaryFidelityConstraint("Ũ⃗" + l, final_fidelity, traj, subspace=sub, device=device) for l in labels]
+    if fidelity_cost:
+        Q_fid = float(np.asarray(Q, dtype=np.float64).ravel()[0])
+        objectives += [UnitaryInfidelityObjective("Ũ⃗" + l, traj, Q_fid, subspace=sub, device=device) for l in labels]
+    return ControlProblemInputs(inp.system, traj, inp.integrators, objectives, constraints)
