@@ -159,6 +159,19 @@ int qc_build_params(const qc_desc* d, QcParams* P, qc_dims_t* dims, std::string*
         }
         P->ddim += dim;
     }
+    // One window per knot that holds every x and dx component of the derivative integrators: even width (16-byte pieces), inside the knot
+    P->dwin_lo = P->dwin_n = 0;
+    if (P->n_deriv > 0 && P->n_deriv <= QC_DWIN_MAX_DERIV) {
+        int lo = d->zdim, hi = 0;
+        bool small = true;
+        for (int i = 0; i < P->n_deriv; ++i) {
+            small = small && P->ddim_i[i] <= 64;
+            lo = std::min(lo, std::min(P->x_off[i], P->dx_off[i]));
+            hi = std::max(hi, std::max(P->x_off[i], P->dx_off[i]) + P->ddim_i[i]);
+        }
+        if ((hi - lo) & 1) { if (hi < d->zdim) ++hi; else --lo; }
+        if (small && lo >= 0 && hi - lo <= 128) { P->dwin_lo = lo; P->dwin_n = hi - lo; }
+    }
     long long tb = d->t_begin, te = d->t_end;
     if (tb == 0 && te == 0) te = d->T - 1;
     if (tb < 0 || te > d->T - 1 || tb > te) return fail(err, QC_ERR_INVALID, "interval range [t_begin, t_end) out of [0, T-1)");

@@ -11,6 +11,7 @@
 #include "qcolloc.h"
 
 #define QC_MAX_P 10  // Pade order up to 20
+#define QC_DWIN_MAX_DERIV 4  // derivative integrators the 2N = 16 F + dF kernel serves from one knot window (QcParams.dwin_n)
 
 // Per-interval value-block layout of the Jacobian (canonical order, DESIGN.md "COO order"):
 //   [ -F copies (N * n^2) | B copies (N * n^2)  or  identity (s) | d/da (s*m) | d/dh (s) | derivative integrators ]
@@ -29,6 +30,9 @@ struct QcParams {
     int dx_off[QC_MAX_DERIV], x_off[QC_MAX_DERIV], ddim_i[QC_MAX_DERIV];
     int drow[QC_MAX_DERIV];  // first row of derivative integrator i relative to this handle's row block (stacked: s + sum of the
                              // earlier dims; QC_ROWS_BY_COMPONENT: deriv_row_off[i] - row_offset, possibly negative)
+    int dwin_lo, dwin_n;     // knot window [dwin_lo, dwin_lo + dwin_n) holding every x and dx of the derivative integrators, dwin_n even
+                             // and <= 128 (one 16-byte-per-lane load per knot, 2N = 16 F + dF kernel); dwin_n = 0: no such window
+                             // (more than QC_DWIN_MAX_DERIV integrators, one of more than 64 rows, or components too far apart)
     long long t_begin;       // first interval of this handle
     int n_int;               // number of intervals of this handle
     int jac_nnz, hess_nnz;   // per interval (own values; hess_nnz excludes the padding)

@@ -1,9 +1,10 @@
 // Register-resident f64-MFMA kernels (v_mfma_f64_16x16x4_f64) for the order-4 Pade integrator.
 //
 // n = 2N = 16 (3 qubits, BASELINE configs 3 and 4): TWO WAVEFRONTS PER INTERVAL, one LDS hand-off, one barrier.
-//   wave 1 ("copy wave")    issues EVERY global load of the interval in one batch (generator images, both knots,
-//                           derivative-integrator data), assembles G, hands G / U_t / U_t+1 / the G_j images to the
-//                           compute wave through LDS, then G -> (G^2)^T -> B^T, F^T -> the 2N tile stores of the
+//   wave 1 ("copy wave")    issues EVERY global load of the interval: first what G needs (generator images, amplitudes,
+//                           timestep), then the data it only passes on (both knots' states and derivative-integrator
+//                           windows, four 16-byte-per-lane requests); assembles G, hands G / U_t / U_t+1 / the G_j images to
+//                           the compute wave through LDS, then G -> (G^2)^T -> B^T, F^T -> the 2N tile stores of the
 //                           I_N (x) B / -I_N (x) F blocks (80 % of the interval's bytes: this wave lives in the store queue)
 //   wave 0 ("compute wave") no global loads (one issued during the copy burst waits > 3 us); residual, d/dh and the m
 //                           drive columns as four batches of independent, interleaved MFMA products; its 16 stores are
@@ -54,7 +55,7 @@ constexpr int kMaxGrid = 1024;             // persistent beyond this many workgr
 // A-layout image of generator `mat` (0 = drift): [matrix][pair(2)][lane(64)][2] doubles
 __device__ inline v4d load_GA(const double* __restrict__ Gx, int mat, int lane) { return load_image_tile(Gx + mat * 256, lane); }
 
-constexpr int kDF = 4;   // derivative integrators handled from registers in the copy wave
+constexpr int kDF = QC_DWIN_MAX_DERIV;   // derivative integrators handled from registers in the copy wave (QcParams.dwin_n)
 
 
 // G = G_0 + sum_k a_k G_k (A-layout).  The first kMU drive images and the amplitudes are requested in one batch (no load
@@ -131,7 +132,11 @@ __device__ inline v4d load_state_tile(const double* __restrict__ zU, int col, in
     }
 }
 
-constexpr int kLdsGa = 0, kLdsU0 = 256, kLdsU1 = 512, kLdsGk = 768;   // + MU * 256 generator images
+// Hand-off block (doubles): G, the states of both knots, the drive images, then the derivative-integrator windows of both knots.  The
+// unmasked instantiation keeps each state as it lies in the knot (128 doubles, column-major), the masked one in the B layout (lds_put).
+// The windows lie beyond the compute wave's transpose scratch (lds_transpose16_multi over the block's first (MU/2 + 1) * 272
+// doubles): the copy wave reads them after the barrier.
+constexpr int kLdsGa = 0, kLdsU0 = 256, kLdsU1 = 512, kLdsGk = 768;   // + MU * 256 generator images, + 2 * 128 windows
 
 __device__ inline void lds_put(double* __restrict__ base, int lane, const v4d& x) {
     v2d* p = reinterpret_cast<v2d*>(base) + lane;
@@ -142,6 +147,16 @@ __device__ inline v4d lds_get(const double* __restrict__ base, int lane) {
     const v2d* p = reinterpret_cast<const v2d*>(base) + lane;
     const v2d lo = p[0], hi = p[64];
     return v4d{lo[0], lo[1], hi[0], hi[1]};
+}
+// 128 contiguous doubles of a knot (8-byte aligned only: zdim may be odd), doubles 2 lane, 2 lane + 1 in one 16-byte request
+__device__ inline v2d load_knot128(const double* __restrict__ p, int lane) {
+    typedef v2d __attribute__((aligned(8))) v2d_u;
+    return reinterpret_cast<const v2d_u*>(p)[lane];
+}
+// State tile [U | U] from a column-major 16 x 8 state in LDS: lane (g, j) reg r = U[4r+g][col]
+__device__ inline v4d lds_state_tile(const double* __restrict__ U, int col, int g) {
+    const double* p = U + col * 16 + g;
+    return v4d{p[0], p[4], p[8], p[12]};
 }
 
 // BATCH: blockIdx.y selects one of several handles' parameter blocks in device memory (the systems of a sampling
@@ -167,7 +182,9 @@ __global__ __launch_bounds__(JAC ? kThreads : 64, 2) void qc_mfma16_pade4_kernel
     const int h_n_int = BATCH ? P.n_int : hot_n_int, h_zdim = BATCH ? P.zdim : hot_zdim, h_off_a = BATCH ? P.off_a : hot_off_a;
     const int h_off_dt = BATCH ? P.off_dt : hot_off_dt;
     const long long h_t_begin = BATCH ? P.t_begin : hot_t_begin;
-    constexpr int kLdsBlock = kLdsGk + kMU * 256;
+    constexpr int kLdsD0 = kLdsGk + kMU * 256, kLdsD1 = kLdsD0 + 128;   // derivative-integrator windows of knots t, t+1
+    constexpr int kLdsBlock = kLdsD1 + 128;
+    static_assert((kMU / 2 + 1) * 272 <= kLdsD0, "the windows must lie beyond the compute wave's transpose scratch");
     __shared__ __attribute__((aligned(16))) double sm_all[JAC ? kIntervalsPerWG * kLdsBlock : 2];
     unsigned long long t_entry = 0, t_kernarg = 0;
     if constexpr (DIAG) {
@@ -249,28 +266,29 @@ __global__ __launch_bounds__(JAC ? kThreads : 64, 2) void qc_mfma16_pade4_kernel
             }
             QC_STAMP(P, b, lane, 0);
             // Every global load of the interval in one batch, in the order the wave needs them: first what G depends on (the
-            // timestep, the amplitudes, the generator images), then the state tiles and the derivative-integrator data that are only
-            // passed on.  G, its two products and B^T / F^T are formed as soon as the first group is back (the compiler's counted
-            // vmcnt leaves the second group in flight); the hand-off to the compute wave follows, then the stores.
+            // timestep, the amplitudes, the generator images), then the data that is only passed on: the states of both knots and
+            // the derivative-integrator window of both knots, 16 bytes per lane each -- four requests where per-element loads took
+            // twenty, which queued in the CU's one vector-memory pipeline in front of the early copies of this wave and of the other
+            // workgroups on the CU.  G, its two products and B^T / F^T are formed as soon as the first group is back (the compiler's
+            // counted vmcnt leaves the second group in flight); the early copies, the hand-off to the compute wave, then the stores.
             const double h = h_pre;
             double ak[kMU];
             const double av = av_pre;   // every amplitude in one vector load (qc_mfma_common.h)
             const v4d& g0 = g0_img;
             const v4d (&gk)[kMU] = gk_img;
-            // (Dropping these twenty loads altogether -- wrong results, timing only -- gains 0.23 us: the vector-memory pipeline of
-            // the CU is not what the first store waits for; it waits for the round trip of the amplitudes and the images.)
             // (The compute wave fetching the state tiles itself, so that the hand-off need not wait for them: 9.78 vs 9.17 us.)
-            const v4d u0 = load_state_tile<KET>(z0 + P.off_U, jc, nr, g);
-            const v4d u1 = load_state_tile<KET>(z1 + P.off_U, jc, nr, g);
-            double dxv[kDF], dfv[kDF];       // derivative integrators, register fast path (<= kDF of <= 64 rows)
-            const bool dfast = P.n_deriv <= kDF;
-#pragma unroll
-            for (int d = 0; d < kDF; ++d) {
-                // unused slots (d >= n_deriv) have zero offsets/dims in QcParams: the loads stay in bounds
-                const int i = lane < P.ddim_i[d] ? lane : 0;
-                dxv[d] = z0[P.dx_off[d] + i];
-                dfv[d] = z1[P.x_off[d] + i] - z0[P.x_off[d] + i];
+            v4d u0, u1;
+            v2d w_u0, w_u1;
+            if constexpr (KET) {
+                u0 = load_state_tile<true>(z0 + P.off_U, jc, nr, g);
+                u1 = load_state_tile<true>(z1 + P.off_U, jc, nr, g);
+            } else {
+                w_u0 = load_knot128(z0 + P.off_U, lane);
+                w_u1 = load_knot128(z1 + P.off_U, lane);
             }
+            // lanes beyond the window re-read its first piece (in bounds; never read back)
+            const int wo = P.dwin_lo + (2 * lane < P.dwin_n ? 2 * lane : 0);
+            const v2d w_d0 = load_knot128(z0 + wo, 0), w_d1 = load_knot128(z1 + wo, 0);
             if (DIAG && (P.dbg_skip & 4)) {   // QC_DEBUG_SKIP=4: when do the scalar loads (amplitudes, h) and when do the vector loads arrive?
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 QC_STAMP(P, b, lane, 10);
@@ -303,24 +321,43 @@ __global__ __launch_bounds__(JAC ? kThreads : 64, 2) void qc_mfma16_pade4_kernel
 #define QC_EARLY_COPIES 4
 #endif
             constexpr int kEarly = (!KET && ONCE) ? QC_EARLY_COPIES : 0;
-            if constexpr (kEarly > 0) {
-                if (!skip) {
-#pragma unroll
-                    for (int q = 0; q < kEarly; ++q) {
-                        if (q < P.copies) {
-                            store_tile_T<MODE>(Jb + P.jo_F + q * 256, Fm, g, j);
-                            store_tile_T<MODE>(Jb + P.jo_B + q * 256, Bm, g, j);
-                        }
-                    }
+            auto early_copy = [&](int q) {
+                store_tile_T<MODE>(Jb + P.jo_F + q * 256, Fm, g, j);
+                store_tile_T<MODE>(Jb + P.jo_B + q * 256, Bm, g, j);
+            };
+            // hand-off to the compute wave.  It waits for the passed-on loads, which are older than the early copies; loads and stores
+            // retire through one in-order counter (vmcnt), so the compiler's counted wait must count the copies issued behind them.
+            // Behind a join of paths with and without copies it would count those of the path with fewest and wait for the copies of
+            // the other to be written too: the hand-off is therefore issued at the end of each path.  (The derivative-integrator
+            // windows written behind the barrier instead, so that it does not wait for them: slower, 8.50 - 8.62 against 8.31 - 8.55 us.)
+            auto hand_off = [&]() {
+                lds_put(sm + kLdsGa, lane, Ga);
+                if constexpr (KET) {
+                    lds_put(sm + kLdsU0, lane, u0);
+                    lds_put(sm + kLdsU1, lane, u1);
+                } else {
+                    reinterpret_cast<v2d*>(sm + kLdsU0)[lane] = w_u0;
+                    reinterpret_cast<v2d*>(sm + kLdsU1)[lane] = w_u1;
                 }
-            }
-            // hand-off to the compute wave
-            lds_put(sm + kLdsGa, lane, Ga);
-            lds_put(sm + kLdsU0, lane, u0);
-            lds_put(sm + kLdsU1, lane, u1);
+                reinterpret_cast<v2d*>(sm + kLdsD0)[lane] = w_d0;
+                reinterpret_cast<v2d*>(sm + kLdsD1)[lane] = w_d1;
 #pragma unroll
-            for (int u = 0; u < kMU; ++u)
-                if (u < m) lds_put(sm + kLdsGk + u * 256, lane, gk[u]);
+                for (int u = 0; u < kMU; ++u)
+                    if (u < m) lds_put(sm + kLdsGk + u * 256, lane, gk[u]);
+            };
+            if constexpr (kEarly > 0) {
+                if (!skip && P.copies >= kEarly) {
+#pragma unroll
+                    for (int q = 0; q < kEarly; ++q) early_copy(q);
+                    hand_off();
+                } else {   // the compact form of the host path (one copy), and diagnostic runs without stores
+                    if (!skip)
+                        for (int q = 0; q < P.copies; ++q) early_copy(q);
+                    hand_off();
+                }
+            } else {
+                hand_off();
+            }
             __syncthreads();
             if (!skip) {
                 double* pF = Jb + P.jo_F;
@@ -340,27 +377,29 @@ __global__ __launch_bounds__(JAC ? kThreads : 64, 2) void qc_mfma16_pade4_kernel
                 __builtin_amdgcn_s_setprio(0);
                 QC_STAMP(P, b, lane, 2);
                 {   // derivative integrator rows: residual x_{t+1} - x_t - h dx_t and the 4 (3) diagonal blocks
-                    int jo = P.jo_d;
-                    bool all_fast = dfast;
+                    if (P.dwin_n > 0) {   // from the windows in the hand-off block (<= kDF integrators of <= 64 rows)
+                        const double* w0 = sm + kLdsD0 - P.dwin_lo;   // indexed by the offset in the knot
+                        const double* w1 = sm + kLdsD1 - P.dwin_lo;
+                        int jo = P.jo_d;
 #pragma unroll
-                    for (int d = 0; d < kDF; ++d) {
-                        if (d < P.n_deriv) {
-                            const int dim = P.ddim_i[d], r0 = P.drow[d];
-                            if (dfast && dim <= 64) {
+                        for (int d = 0; d < kDF; ++d) {
+                            if (d < P.n_deriv) {
+                                const int dim = P.ddim_i[d], r0 = P.drow[d];
                                 if (lane < dim) {
-                                    if (Fb) Fb[r0 + lane] = dfv[d] - h * dxv[d];
+                                    const double dxv = w0[P.dx_off[d] + lane];
+                                    const double dfv = w1[P.x_off[d] + lane] - w0[P.x_off[d] + lane];
+                                    if (Fb) Fb[r0 + lane] = dfv - h * dxv;
                                     Jb[jo + lane] = -1.0;
                                     Jb[jo + dim + lane] = 1.0;
                                     Jb[jo + 2 * dim + lane] = -h;
-                                    if (ft) Jb[jo + 3 * dim + lane] = -dxv[d];
+                                    if (ft) Jb[jo + 3 * dim + lane] = -dxv;
                                 }
-                            } else {
-                                all_fast = false;
+                                jo += (ft ? 4 : 3) * dim;
                             }
-                            jo += (ft ? 4 : 3) * dim;
                         }
+                    } else {
+                        deriv_rows_generic(P, z0, z1, h, Fb, Jb, lane, false);
                     }
-                    if (!all_fast) deriv_rows_generic(P, z0, z1, h, Fb, Jb, lane, dfast);
                 }
                 if constexpr (DIAG) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -384,8 +423,13 @@ __global__ __launch_bounds__(JAC ? kThreads : 64, 2) void qc_mfma16_pade4_kernel
         if constexpr (JAC) {
             __syncthreads();                      // wait for the copy wave's hand-off
             Ga = lds_get(sm + kLdsGa, lane);
-            u0 = lds_get(sm + kLdsU0, lane);
-            u1 = lds_get(sm + kLdsU1, lane);
+            if constexpr (KET) {
+                u0 = lds_get(sm + kLdsU0, lane);
+                u1 = lds_get(sm + kLdsU1, lane);
+            } else {
+                u0 = lds_state_tile(sm + kLdsU0, jc, g);
+                u1 = lds_state_tile(sm + kLdsU1, jc, g);
+            }
         } else {                                  // residual-only launch: a single wave, loads for itself
             u0 = load_state_tile<KET>(z0 + P.off_U, jc, nr, g);
             u1 = load_state_tile<KET>(z1 + P.off_U, jc, nr, g);
