@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "qc_internal.h"
+#include "qc_plan.h"
 
 
 static thread_local std::string g_err;
@@ -380,53 +381,30 @@ extern "C" int qc_desc_hess_structure(const qc_desc* d, int64_t* rows, int64_t* 
 // ------------------------------------------------------------------------------------------------
 //  Handle
 // ------------------------------------------------------------------------------------------------
-extern "C" int qc_create(const qc_desc* d, qc_handle** out) {
-    if (!out) return fail(nullptr, QC_ERR_INVALID, "qc_create: out is NULL");
-    *out = nullptr;
-    QcParams P; qc_dims_t dims; std::string err;
-    int rc = qc_build_params(d, &P, &dims, &err);
+// Everything qc_create decides from the descriptor alone.  Invalid descriptor: `params_ok` stays false.
+int qc_blueprint_build(const qc_desc* d, qc_blueprint* B, std::string* err) {
+    B->params_ok = false;
+    int rc = qc_build_params(d, &B->prm, &B->dims, err);
     if (rc) return rc;
-    if (!d->G_drift || (d->m > 0 && !d->G_drives)) return fail(nullptr, QC_ERR_INVALID, "qc_create: G_drift/G_drives is NULL");
-
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, QC_ERR_NO_DEVICE, "qc_create: no HIP device visible (this library has no CPU path)");
-    if (d->device < 0 || d->device >= ndev) return fail(nullptr, QC_ERR_NO_DEVICE, "qc_create: device ordinal out of range");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, d->device) != hipSuccess) return fail(nullptr, QC_ERR_HIP, "hipGetDeviceProperties failed");
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(nullptr, QC_ERR_NO_DEVICE, std::string("qc_create: device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
-
-    qc_handle* h = new qc_handle();
-    h->desc = *d;
-    h->desc.G_drift = nullptr;
-    h->desc.G_drives = nullptr;
-    h->device = d->device;
-    h->prm = P;
-    h->dims = dims;
+    if (!d->G_drift || (d->m > 0 && !d->G_drives)) return fail(err, QC_ERR_INVALID, "qc_create: G_drift/G_drives is NULL");
+    B->params_ok = true;
+    QcParams& P = B->prm;
+    const QcCreateSwitches sw = qc_create_switches();
 
     // kernel selection
     int kernel = d->kernel;
-    const bool mfma_ok = qc_mfma_supported(P);
+    const bool mfma_ok = qc_plan_mfma_serves(P);
     if (kernel == QC_KERNEL_AUTO) kernel = mfma_ok ? QC_KERNEL_MFMA : QC_KERNEL_LDS;
-    if (kernel == QC_KERNEL_MFMA && !mfma_ok) {
-        delete h;
-        return fail(nullptr, QC_ERR_UNSUPPORTED, "qc_create: no MFMA kernel serves this descriptor (order-4 Pade up to 32 levels, other Pade orders up to 8 levels, "
-                                                   "the exponential integrator up to 16 levels; see qc_desc.kernel)");
-    }
-    if (kernel != QC_KERNEL_MFMA && kernel != QC_KERNEL_LDS) { delete h; return fail(nullptr, QC_ERR_INVALID, "qc_create: unknown kernel id"); }
-    static std::atomic<unsigned long long> next_serial{1};
-    h->serial = next_serial.fetch_add(1);
-    h->kernel = kernel;
-    h->dims.kernel = kernel;
+    if (kernel == QC_KERNEL_MFMA && !mfma_ok)
+        return fail(err, QC_ERR_UNSUPPORTED, "qc_create: no MFMA kernel serves this descriptor (order-4 Pade up to 32 levels, other Pade orders up to 8 levels, "
+                                             "the exponential integrator up to 16 levels; see qc_desc.kernel)");
+    if (kernel != QC_KERNEL_MFMA && kernel != QC_KERNEL_LDS) return fail(err, QC_ERR_INVALID, "qc_create: unknown kernel id");
+    B->cls.kernel = kernel;
+    B->dims.kernel = kernel;
 
-    auto bail = [&](int code, const std::string& msg) { std::string m2 = msg; qc_destroy(h); return fail(nullptr, code, m2); };
-#define QC_HIP_C(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bail(QC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
-
-    qc_device_guard guard(h->device);
-    QC_HIP_C(guard.err);
     const size_t n2 = (size_t)P.n * P.n;
-    std::vector<double> G((size_t)(P.m + 1) * n2);
+    std::vector<double>& G = B->G;
+    G.resize((size_t)(P.m + 1) * n2);
     memcpy(G.data(), d->G_drift, n2 * sizeof(double));
     if (P.m) memcpy(G.data() + n2, d->G_drives, (size_t)P.m * n2 * sizeof(double));
     {   // exact antisymmetry of every generator (G = iso(-iH) of a Hermitian H): lets the Hessian kernels skip the transposed images
@@ -437,90 +415,126 @@ extern "C" int qc_create(const qc_desc* d, qc_handle** out) {
                 for (int r = 0; r <= c; ++r)
                     if (A[(size_t)c * P.n + r] != -A[(size_t)r * P.n + c]) { anti = false; break; }
         }
-        h->prm.antisym = anti ? 1 : 0;
-        if (const char* e = getenv("QC_NO_ANTISYM")) if (atoi(e)) h->prm.antisym = 0;   // diagnostic: force the general path
+        P.antisym = anti && !sw.no_antisym ? 1 : 0;      // (QC_NO_ANTISYM=1, diagnostic: force the general path)
     }
-    QC_HIP_C(hipMalloc((void**)&h->dG, G.size() * sizeof(double)));
-    QC_HIP_C(hipMemcpy(h->dG, G.data(), G.size() * sizeof(double), hipMemcpyHostToDevice));
-    h->prm.G = h->dG;
     // Outputs are written once and never re-read by the kernel: non-temporal stores measured fastest on
     // MI355X (profiles/README.md: plain 14.4, sc1 12.8, nt 11.9 us per config-3 evaluation).
-    h->prm.store_mode = 2;
-    if (const char* e = getenv("QC_STORE_MODE")) h->prm.store_mode = std::max(0, std::min(2, atoi(e)));   // diagnostic override
+    P.store_mode = 2;
+    if (const char* e = getenv("QC_STORE_MODE")) P.store_mode = std::max(0, std::min(2, atoi(e)));   // diagnostic override
     // Diagnostic ablation for the profiling scripts: it produces WRONG results, so it needs the explicit opt-in
     // QC_DIAGNOSTICS=1 next to it and says so on stderr every time a handle is created with it.
     if (const char* e = getenv("QC_DEBUG_SKIP")) {
         const char* opt = getenv("QC_DIAGNOSTICS");
         if (atoi(e) != 0 && opt && atoi(opt) == 1) {
-            h->prm.dbg_skip = atoi(e);
-            fprintf(stderr, "qcolloc: QC_DEBUG_SKIP=%d is active: outputs of this handle are NOT valid results\n", h->prm.dbg_skip);
+            P.dbg_skip = atoi(e);
+            fprintf(stderr, "qcolloc: QC_DEBUG_SKIP=%d is active: outputs of this handle are NOT valid results\n", P.dbg_skip);
         } else if (atoi(e) != 0) {
             fprintf(stderr, "qcolloc: QC_DEBUG_SKIP ignored (set QC_DIAGNOSTICS=1 to enable the ablation)\n");
         }
     }
     if (kernel == QC_KERNEL_MFMA) {
-        std::vector<double> Gx(qc_mfma_gx_doubles(P));
-        qc_mfma_pack_G(P, G.data(), Gx.data());
-        QC_HIP_C(hipMalloc((void**)&h->dGx, Gx.size() * sizeof(double)));
-        QC_HIP_C(hipMemcpy(h->dGx, Gx.data(), Gx.size() * sizeof(double), hipMemcpyHostToDevice));
-        h->prm.Gx = h->dGx;
+        B->Gx.resize(qc_mfma_gx_doubles(P));
+        qc_mfma_pack_G(P, G.data(), B->Gx.data());
         // drive generators with at most two entries per row (Pauli strings, ladder pairs): row-gather tables for the kernels that
         // never touch a dense drive image (QC_NO_ELL=1: the dense kernels, for A/B runs)
-        const bool no_ell = getenv("QC_NO_ELL") && atoi(getenv("QC_NO_ELL"));
-        std::vector<char> blob;
         int slots = 0;
-        const int R = no_ell ? 0 : qc_mfma32_ell_build(h->prm, G.data(), &blob, &slots);
+        const int R = sw.no_ell ? 0 : qc_mfma32_ell_build(P, G.data(), &B->ell, &slots);
         if (R > 0) {
-            QC_HIP_C(hipMalloc(&h->dEll, blob.size()));
-            QC_HIP_C(hipMemcpy(h->dEll, blob.data(), blob.size(), hipMemcpyHostToDevice));
-            h->prm.ell = h->dEll;
-            h->prm.ell_R = R;
-            h->prm.ell_slots = slots;
+            P.ell_R = R;
+            P.ell_slots = slots;
+        } else {
+            B->ell.clear();
         }
-        std::vector<char> blob16;
-        if (!no_ell && qc_mfma16_ell_build(h->prm, G.data(), &blob16)) {
-            qc_mfma16_ell_pair_table(h->prm, &blob16);
-            QC_HIP_C(hipMalloc(&h->dEll16, blob16.size()));
-            QC_HIP_C(hipMemcpy(h->dEll16, blob16.data(), blob16.size(), hipMemcpyHostToDevice));
-            h->prm.ell16 = h->dEll16;
-        } else if (!no_ell && qc_exp_ell_build(h->prm, G.data(), &blob16)) {      // the exponential integrator's MFMA kernels (2N <= 32)
-            QC_HIP_C(hipMalloc(&h->dEll16, blob16.size()));
-            QC_HIP_C(hipMemcpy(h->dEll16, blob16.data(), blob16.size(), hipMemcpyHostToDevice));
-            h->prm.ell16 = h->dEll16;
-        }
+        if (!sw.no_ell && qc_mfma16_ell_build(P, G.data(), &B->ell16)) qc_mfma16_ell_pair_table(P, &B->ell16);
+        else if (sw.no_ell || !qc_exp_ell_build(P, G.data(), &B->ell16)) B->ell16.clear();      // (the exponential integrator's MFMA kernels, 2N <= 32)
+        B->cls.ell16 = !B->ell16.empty();
     }
-    // LDS budget of the LDS kernels
-    {
-        // choose the j-chunk so the LDS kernel fits in 160 KiB (64 KiB keeps >= 2 blocks per CU when possible)
-        QcParams& Q = h->prm;
-        Q.jchunk = std::max(1, Q.m);
-        while (Q.jchunk > 1 && qc_lds_bytes_jac(Q) > 64 * 1024) Q.jchunk = (Q.jchunk + 1) / 2;
-        h->lds_bytes_jac = qc_lds_bytes_jac(Q);
-        h->lds_bytes_hess = qc_lds_bytes_hess(Q);
-        if (h->lds_bytes_jac > 160 * 1024 || h->lds_bytes_hess > 160 * 1024) {
-            // Too large for LDS: the same kernels run with their scratch in a global-memory workspace (slow, but the
-            // library does not refuse the problem: 5 qubits, N = 32, are 2 N = 64 rows).
-            Q.use_ws = 1;
-            Q.jchunk = std::min(std::max(1, Q.m), 2);
-            h->lds_bytes_jac = qc_lds_bytes_jac(Q);
-            h->lds_bytes_hess = qc_lds_bytes_hess(Q);
-            const size_t per = (std::max(h->lds_bytes_jac, h->lds_bytes_hess) / sizeof(double) + 1) & ~(size_t)1;
-            const size_t total = per * (size_t)std::max(1, Q.n_int);
-            if (total * sizeof(double) > ((size_t)16 << 30))
-                return bail(QC_ERR_UNSUPPORTED, "qc_create: the global workspace for this system would exceed 16 GiB");
-            QC_HIP_C(hipMalloc((void**)&h->dWs, total * sizeof(double)));
-            Q.ws = h->dWs;
-            Q.ws_stride = (long long)per;
-        }
+    // LDS budget of the LDS kernels: choose the j-chunk so the LDS kernel fits in 160 KiB (64 KiB keeps >= 2 blocks per CU when possible)
+    P.jchunk = std::max(1, P.m);
+    while (P.jchunk > 1 && qc_lds_bytes_jac(P) > 64 * 1024) P.jchunk = (P.jchunk + 1) / 2;
+    B->lds_bytes_jac = qc_lds_bytes_jac(P);
+    B->lds_bytes_hess = qc_lds_bytes_hess(P);
+    if (B->lds_bytes_jac > 160 * 1024 || B->lds_bytes_hess > 160 * 1024) {
+        // Too large for LDS: the same kernels run with their scratch in a global-memory workspace (slow, but the
+        // library does not refuse the problem: 5 qubits, N = 32, are 2 N = 64 rows).
+        P.use_ws = 1;
+        P.jchunk = std::min(std::max(1, P.m), 2);
+        B->lds_bytes_jac = qc_lds_bytes_jac(P);
+        B->lds_bytes_hess = qc_lds_bytes_hess(P);
+        P.ws_stride = (long long)((std::max(B->lds_bytes_jac, B->lds_bytes_hess) / sizeof(double) + 1) & ~(size_t)1);
+    }
+    if (const char* e = getenv("QC_STAMPS")) B->cls.stamped = atoi(e) && P.n_int > 0;
+    return QC_OK;
+}
+
+extern "C" int qc_create(const qc_desc* d, qc_handle** out) {
+    if (!out) return fail(nullptr, QC_ERR_INVALID, "qc_create: out is NULL");
+    *out = nullptr;
+    qc_blueprint B;
+    std::string err;
+    const int refused = qc_blueprint_build(d, &B, &err);
+    if (refused && !B.params_ok) return refused;      // an invalid descriptor is reported before the device is looked at ...
+
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(nullptr, QC_ERR_NO_DEVICE, "qc_create: no HIP device visible (this library has no CPU path)");
+    if (d->device < 0 || d->device >= ndev) return fail(nullptr, QC_ERR_NO_DEVICE, "qc_create: device ordinal out of range");
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, d->device) != hipSuccess) return fail(nullptr, QC_ERR_HIP, "hipGetDeviceProperties failed");
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(nullptr, QC_ERR_NO_DEVICE, std::string("qc_create: device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+    if (refused) return fail(nullptr, refused, err);   // ... a kernel class that cannot serve it after
+
+    qc_handle* h = new qc_handle();
+    h->desc = *d;
+    h->desc.G_drift = nullptr;
+    h->desc.G_drives = nullptr;
+    h->device = d->device;
+    h->prm = B.prm;
+    h->dims = B.dims;
+    h->cls = B.cls;
+    h->lds_bytes_jac = B.lds_bytes_jac;
+    h->lds_bytes_hess = B.lds_bytes_hess;
+    h->plan = qc_plan(B.prm, B.cls);
+    static std::atomic<unsigned long long> next_serial{1};
+    h->serial = next_serial.fetch_add(1);
+
+    auto bail = [&](int code, const std::string& msg) { std::string m2 = msg; qc_destroy(h); return fail(nullptr, code, m2); };
+#define QC_HIP_C(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bail(QC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
+    auto upload = [&](void** dst, const void* src, size_t bytes) {
+        hipError_t e = hipMalloc(dst, bytes);
+        return e != hipSuccess ? e : hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+    };
+
+    qc_device_guard guard(h->device);
+    QC_HIP_C(guard.err);
+    QC_HIP_C(upload((void**)&h->dG, B.G.data(), B.G.size() * sizeof(double)));
+    h->prm.G = h->dG;
+    if (!B.Gx.empty()) {
+        QC_HIP_C(upload((void**)&h->dGx, B.Gx.data(), B.Gx.size() * sizeof(double)));
+        h->prm.Gx = h->dGx;
+    }
+    if (!B.ell.empty()) {
+        QC_HIP_C(upload(&h->dEll, B.ell.data(), B.ell.size()));
+        h->prm.ell = h->dEll;
+    }
+    if (!B.ell16.empty()) {
+        QC_HIP_C(upload(&h->dEll16, B.ell16.data(), B.ell16.size()));
+        h->prm.ell16 = h->dEll16;
+    }
+    if (h->prm.use_ws) {      // global workspace of the LDS kernels
+        const size_t total = (size_t)h->prm.ws_stride * (size_t)std::max(1, h->prm.n_int);
+        if (total * sizeof(double) > ((size_t)16 << 30))
+            return bail(QC_ERR_UNSUPPORTED, "qc_create: the global workspace for this system would exceed 16 GiB");
+        QC_HIP_C(hipMalloc((void**)&h->dWs, total * sizeof(double)));
+        h->prm.ws = h->dWs;
     }
     if (const char* e = getenv("QC_HOST_COMPACT")) h->host_compact = std::max(0, std::min(2, atoi(e)));
     if (const char* e = getenv("QC_HOST_LANDING")) h->host_landing = atoi(e) ? 1 : 0;
-    if (const char* e = getenv("QC_STAMPS")) {
-        if (atoi(e) && P.n_int > 0) {
-            QC_HIP_C(hipMalloc((void**)&h->dStamps, (size_t)P.n_int * 16 * sizeof(unsigned long long)));
-            QC_HIP_C(hipMemset(h->dStamps, 0, (size_t)P.n_int * 16 * sizeof(unsigned long long)));
-            h->prm.stamps = h->dStamps;
-        }
+    if (h->cls.stamped) {
+        QC_HIP_C(hipMalloc((void**)&h->dStamps, (size_t)h->prm.n_int * 16 * sizeof(unsigned long long)));
+        QC_HIP_C(hipMemset(h->dStamps, 0, (size_t)h->prm.n_int * 16 * sizeof(unsigned long long)));
+        h->prm.stamps = h->dStamps;
     }
     QC_HIP_C(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     QC_HIP_C(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
@@ -581,30 +595,8 @@ extern "C" int qc_debug_read_stamps(qc_handle* h, uint64_t* out, int64_t count) 
 extern "C" const char* qc_kernel_name(const qc_handle* h, int32_t which) {
     if (!h) return "none";
     if (!h->shards.empty()) return qc_kernel_name(h->shards[0], which);
-    const QcParams& P = h->prm;
-    const bool mfma = h->kernel == QC_KERNEL_MFMA;
-    if (which == 0) {
-        if (!mfma) return P.use_ws ? "lds-gws" : "lds";
-        if (P.integrator == QC_EXPONENTIAL) return P.n > 16 ? (P.ell16 != nullptr ? "mfma32-exp-gather" : "mfma32-exp") : (P.ell16 != nullptr ? "mfma16-exp-gather" : "mfma16-exp");
-        if (qc_mfma16_padeP_supported(P)) return "mfma16-padeP";
-        if (P.n > 16 && P.n <= 32 && P.ell) return "mfma32-pade4-ell";
-        return P.n > 32 ? "mfma64-pade4" : (P.n > 16 ? "mfma32-pade4" : "mfma16-pade4");
-    }
-    if (P.integrator != QC_PADE) {      // exponential integrator: mu_d2F alone; F + dF + mu_d2F as two launches
-        if (which == 2) return "two-launches";
-        if (mfma && qc_mfma_exp_hess_supported(P)) return P.ell16 != nullptr ? "mfma16-exp-hess-gather" : "mfma16-exp-hess";
-        if (mfma && qc_mfma32_exp_hess_supported(P)) return P.ell16 != nullptr ? "mfma32-exp-hess-gather" : "mfma32-exp-hess";
-        return P.use_ws ? "lds-gws-exp-hess" : "lds-exp-hess";
-    }
-    if (which == 2) return mfma && qc_mfma16_fused_supported(P) ? (qc_mfma16_fused_gathers(P) ? "mfma16-pade4-fused-gather" : "mfma16-pade4-fused") : (mfma && P.ell && P.hess_nnz ? "mfma32-pade4-fused-ell" : "two-launches");
-    if (mfma && qc_mfma_hess_supported(P)) {
-        if (qc_mfma16_padeP_hess_supported(P)) return "mfma16-padeP-hess";
-        if (P.n == 16 && qc_mfma16_hess_gathers(P)) return "mfma16-pade4-hess-gather";      // one entry per drive-generator row: the one-wave kernel's row-gather form
-        if (qc_mfma16_hess2_supported(P)) return "mfma16-pade4-hess2";
-        if (P.n > 16 && P.n <= 32 && P.ell) return "mfma32-pade4-hess-ell";
-        return P.n > 32 ? "mfma64-pade4-hess" : (P.n > 16 ? "mfma32-pade4-hess" : "mfma16-pade4-hess");
-    }
-    return P.use_ws ? "lds-gws-hess" : "lds-hess";
+    const QcPlan& p = h->plan;
+    return which == 0 ? qc_jac_kernel_name(p.jac) : (which == 2 ? qc_fused_kernel_name(p.fused) : qc_hess_kernel_name(p.hess));
 }
 
 extern "C" int qc_dims(const qc_handle* h, qc_dims_t* out) {

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "qc_internal.h"
+#include "qc_plan.h"
 #include "qc_host_team.h"
 
 #define fail qc_fail
@@ -123,6 +124,51 @@ static int claim_plain(qc_handle* h, unsigned long long tag) {
     } while (0)
 
 // ------------------------------------------------------------------------------------------------
+//  The launches: one switch per question over what qc_plan answered for `P` -- the handle's own parameters (h->plan) or a copy
+//  of them (a chunk of intervals, the compact layout of the host path: qc_plan_jac / qc_plan_hess of the copy)
+// ------------------------------------------------------------------------------------------------
+static hipError_t launch_F_jac(const qc_handle* h, QcJacKernel k, const QcParams& P, const double* dZ, double* dF, double* dJ, hipStream_t st) {
+    switch (k) {
+        case QC_JAC_LDS:
+        case QC_JAC_LDS_GWS: return qc_launch_lds_F_jac(P, dZ, dF, dJ, h->lds_bytes_jac, st);
+        case QC_JAC_EXP16: return qc_launch_mfma_exp(P, false, dZ, dF, dJ, st);
+        case QC_JAC_EXP16_GATHER: return qc_launch_mfma_exp(P, true, dZ, dF, dJ, st);
+        case QC_JAC_EXP32: return qc_launch_mfma32_exp(P, false, dZ, dF, dJ, st);
+        case QC_JAC_EXP32_GATHER: return qc_launch_mfma32_exp(P, true, dZ, dF, dJ, st);
+        case QC_JAC_PADEP16: return qc_launch_mfma16_padeP(P, dZ, dF, dJ, st);
+        case QC_JAC_PADE4_64: return qc_launch_mfma64_F_jac(P, dZ, dF, dJ, st);
+        case QC_JAC_PADE4_32_ELL: return qc_launch_mfma32_ell_F_jac(P, dZ, dF, dJ, st);
+        case QC_JAC_PADE4_32: return qc_launch_mfma32_F_jac(P, dZ, dF, dJ, st);
+        case QC_JAC_PADE4_16: return qc_launch_mfma16_F_jac(P, dZ, dF, dJ, st);
+        case QC_JAC_KERNELS: break;
+    }
+    return hipErrorInvalidValue;
+}
+
+static hipError_t launch_hess(const qc_handle* h, QcHessKernel k, const QcParams& P, const double* dZ, const double* dMu, double* dH, hipStream_t st) {
+    switch (k) {
+        case QC_HESS_LDS:
+        case QC_HESS_LDS_GWS: return qc_launch_lds_hess(P, dZ, dMu, dH, h->lds_bytes_hess, st);
+        case QC_HESS_LDS_EXP:
+        case QC_HESS_LDS_GWS_EXP: return qc_launch_lds_exp_hess(P, dZ, dMu, dH, h->lds_bytes_hess, st);
+        case QC_HESS_EXP16: return qc_launch_mfma_exp_hess(P, false, dZ, dMu, dH, st);
+        case QC_HESS_EXP16_GATHER: return qc_launch_mfma_exp_hess(P, true, dZ, dMu, dH, st);
+        case QC_HESS_EXP32: return qc_launch_mfma32_exp_hess(P, false, dZ, dMu, dH, st);
+        case QC_HESS_EXP32_GATHER: return qc_launch_mfma32_exp_hess(P, true, dZ, dMu, dH, st);
+        case QC_HESS_PADEP16: return qc_launch_mfma16_padeP_hess(P, dZ, dMu, dH, st);
+        case QC_HESS_PADE4_64: return qc_launch_mfma64_hess(P, dZ, dMu, dH, st);
+        case QC_HESS_PADE4_32_ELL: return qc_launch_mfma32_ell_hess(P, dZ, dMu, dH, st);
+        case QC_HESS_PADE4_32: return qc_launch_mfma32_hess(P, dZ, dMu, dH, st);
+        case QC_HESS_PADE4_16_G2: return qc_launch_mfma16_hess_g2(P, dZ, dMu, dH, st);
+        case QC_HESS_PADE4_16_GATHER: return qc_launch_mfma16_hess(P, true, dZ, dMu, dH, st);
+        case QC_HESS_PADE4_16_TWO_WAVES: return qc_launch_mfma16_hess2(P, dZ, dMu, dH, st);
+        case QC_HESS_PADE4_16: return qc_launch_mfma16_hess(P, false, dZ, dMu, dH, st);
+        case QC_HESS_KERNELS: break;
+    }
+    return hipErrorInvalidValue;
+}
+
+// ------------------------------------------------------------------------------------------------
 //  Device-resident evaluation
 // ------------------------------------------------------------------------------------------------
 extern "C" int qc_eval_F_jac_dev(qc_handle* h, const double* dZ, double* dF, double* dvals, void* stream) {
@@ -136,11 +182,9 @@ extern "C" int qc_eval_F_jac_dev(qc_handle* h, const double* dZ, double* dF, dou
     if (h->prm.n_int == 0) return QC_OK;
     qc_device_guard guard(h->device);
     QC_HIP(h, guard.err);
-    hipError_t e;
     // (Keeping the parameter block in device memory instead of the kernarg segment -- the batched launch's mechanism with one
     // handle -- was measured: 10.9 instead of 10.55 us per config-3 launch.)
-    if (h->kernel == QC_KERNEL_MFMA) e = qc_launch_mfma_F_jac(h->prm, dZ, dF, dvals, (hipStream_t)stream);
-    else e = qc_launch_lds_F_jac(h->prm, dZ, dF, dvals, h->lds_bytes_jac, (hipStream_t)stream);
+    const hipError_t e = launch_F_jac(h, h->plan.jac, h->prm, dZ, dF, dvals, (hipStream_t)stream);
     if (e != hipSuccess) return fail(&h->err, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return QC_OK;
 }
@@ -158,8 +202,7 @@ static int prepare_batch(qc_handle* const* hs, int32_t count, bool hessian) {
     if (count < 2 || count > 65535) return 0;
     for (int i = 0; i < count; ++i) {
         const qc_handle* h = hs[i];
-        if (h->kernel != QC_KERNEL_MFMA || !qc_mfma16_batchable(h->prm)) return 0;
-        if (h->prm.m > 8 && hessian) return 0;
+        if (!(hessian ? h->plan.batch_hess : h->plan.batch_jac)) return 0;
         if (hessian && h->prm.antisym != h0->prm.antisym) return 0;   // (the antisymmetric generators' Hessian kernel is a different one)
         if (h->prm.n_int != h0->prm.n_int || h->prm.t_begin != h0->prm.t_begin || h->prm.zdim != h0->prm.zdim || h->prm.m != h0->prm.m ||
             h->prm.n != h0->prm.n || h->prm.nc != h0->prm.nc)
@@ -213,9 +256,7 @@ extern "C" int qc_eval_hess_dev_multi(qc_handle* const* hs, int32_t count, const
     if ((rc = check_align(h0, dhvals, 8, "dhvals"))) return rc;
     const int ok = prepare_batch(hs, count, true);
     if (ok < 0) return ok;
-    bool hess_ok = ok == 1 && h0->prm.n_int > 0;
-    for (int i = 0; hess_ok && i < count; ++i) hess_ok = hs[i]->prm.hess_nnz > 0 && qc_mfma_hess_supported(hs[i]->prm);
-    if (!hess_ok) {
+    if (ok == 0 || h0->prm.n_int == 0) {
         for (int i = 0; i < count; ++i) if ((rc = qc_eval_hess_dev(hs[i], dZ, dmu, dhvals, stream))) return rc;
         return QC_OK;
     }
@@ -238,19 +279,11 @@ extern "C" int qc_eval_hess_dev(qc_handle* h, const double* dZ, const double* dm
     if (h->prm.n_int == 0) return QC_OK;
     qc_device_guard guard(h->device);
     QC_HIP(h, guard.err);
-    hipError_t e;
-    if (h->kernel == QC_KERNEL_MFMA && qc_mfma64_hess_supported(h->prm) && !h->dHs) {   // 128 MiB of scratch, first Hessian call only
-        QC_HIP(h, hipMalloc((void**)&h->dHs, qc_mfma64_hess_scratch_doubles(h->prm) * sizeof(double)));
+    if (h->plan.hess_scratch_doubles && !h->dHs) {   // the 4 x 4-tile kernel's 128 MiB, first Hessian call only
+        QC_HIP(h, hipMalloc((void**)&h->dHs, h->plan.hess_scratch_doubles * sizeof(double)));
         h->prm.hs = h->dHs;
     }
-    if (h->kernel == QC_KERNEL_MFMA && qc_mfma_exp_hess_supported(h->prm))
-        e = qc_launch_mfma_exp_hess(h->prm, dZ, dmu, dhvals, (hipStream_t)stream);
-    else if (h->kernel == QC_KERNEL_MFMA && qc_mfma32_exp_hess_supported(h->prm))
-        e = qc_launch_mfma32_exp_hess(h->prm, dZ, dmu, dhvals, (hipStream_t)stream);
-    else if (h->kernel == QC_KERNEL_MFMA && qc_mfma_hess_supported(h->prm))
-        e = qc_launch_mfma_hess(h->prm, dZ, dmu, dhvals, (hipStream_t)stream);
-    else
-        e = qc_launch_lds_hess(h->prm, dZ, dmu, dhvals, h->lds_bytes_hess, (hipStream_t)stream);
+    const hipError_t e = launch_hess(h, h->plan.hess, h->prm, dZ, dmu, dhvals, (hipStream_t)stream);
     if (e != hipSuccess) return fail(&h->err, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return QC_OK;
 }
@@ -266,18 +299,16 @@ extern "C" int qc_eval_F_jac_hess_dev(qc_handle* h, const double* dZ, const doub
         (rc = check_align(h, dvals, 8, "dvals")) || (rc = check_align(h, dhvals, 8, "dhvals")))
         return rc;
     if (h->prm.n_int == 0) return QC_OK;
-    static const bool allow = !(getenv("QC_NO_FUSED") && atoi(getenv("QC_NO_FUSED")));
-    if (allow && h->kernel == QC_KERNEL_MFMA && qc_mfma16_fused_supported(h->prm)) {
+#ifdef QC_FUSED_ELL_DYNAMIC      /* experiment builds: QC_FUSED_ELL is read at every launch */
+    const QcFusedKernel fused = qc_plan_fused(h->prm, h->cls);
+#else
+    const QcFusedKernel fused = h->plan.fused;
+#endif
+    if (fused != QC_FUSED_TWO_LAUNCHES) {
         qc_device_guard guard(h->device);
         QC_HIP(h, guard.err);
-        const hipError_t e = qc_launch_mfma16_fused(h->prm, dZ, dmu, dF, dvals, dhvals, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(&h->err, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-        return QC_OK;
-    }
-    if (allow && h->kernel == QC_KERNEL_MFMA && h->prm.ell && h->prm.hess_nnz) {      // sparse drive generators at 2N = 32: qc_mfma32_ell.hip
-        qc_device_guard guard(h->device);
-        QC_HIP(h, guard.err);
-        const hipError_t e = qc_launch_mfma32_ell_fused(h->prm, dZ, dmu, dF, dvals, dhvals, (hipStream_t)stream);
+        const hipError_t e = fused == QC_FUSED_PADE4_32_ELL ? qc_launch_mfma32_ell_fused(h->prm, dZ, dmu, dF, dvals, dhvals, (hipStream_t)stream)
+                                                            : qc_launch_mfma16_fused(h->prm, fused == QC_FUSED_PADE4_16_GATHER, dZ, dmu, dF, dvals, dhvals, (hipStream_t)stream);
         if (e != hipSuccess) return fail(&h->err, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
         return QC_OK;
     }
@@ -855,7 +886,7 @@ static int eval_host(qc_handle* h, const double* Z, double* F, double* vals, int
     if (P.n_int == 0) return QC_OK;
     const CompactPlan cp = compact_plan(P);
     const bool compact = vals && h->host_compact && cp.useful;
-    const bool direct = (compact || !vals) && h->host_compact == 1 && h->kernel == QC_KERNEL_MFMA && qc_mfma_compact_supported(P);
+    const bool direct = (compact || !vals) && h->host_compact == 1 && h->plan.compact;
     if (vals && (!direct || h->host_landing != 1)) return eval_host_chunked(h, Z, F, vals, shards);
     const double t_begin = now_us();
     qc_device_guard guard(h->device);
@@ -910,7 +941,7 @@ static int eval_host(qc_handle* h, const double* Z, double* F, double* vals, int
     C.J_stride = (long long)J.blk;
     C.J_off = (long long)J.f_len;
     C.F_stride = (long long)J.blk;
-    const hipError_t e = qc_launch_mfma_F_jac(C, h->dZ, with_F ? h->dC : nullptr, h->dC, h->stream);
+    const hipError_t e = launch_F_jac(h, qc_plan_jac(C, h->cls), C, h->dZ, with_F ? h->dC : nullptr, h->dC, h->stream);
     if (e != hipSuccess) return fail(&h->err, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     const size_t used = (size_t)P.n_int * J.blk;
     hipError_t ec = hipMemcpyAsync(h->hC[ib], h->dC, used * sizeof(double), hipMemcpyDeviceToHost, h->stream);
@@ -955,7 +986,7 @@ static int eval_host_chunked(qc_handle* h, const double* Z, double* F, double* v
 
     const CompactPlan cp = compact_plan(P);
     const bool compact = vals && h->host_compact && cp.useful;
-    const bool direct = (compact || !vals) && h->host_compact == 1 && h->kernel == QC_KERNEL_MFMA && qc_mfma_compact_supported(P);
+    const bool direct = (compact || !vals) && h->host_compact == 1 && h->plan.compact;
     if (direct) {
         // Direct form: the kernel writes residuals and compact values straight into pinned host memory, one launch per chunk of
         // intervals; the first chunk's knots are staged and copied ahead of the rest, so that the first launch (and with it the
@@ -980,7 +1011,7 @@ static int eval_host_chunked(qc_handle* h, const double* Z, double* F, double* v
             QcParams Ck = C;
             Ck.t_begin = C.t_begin + b0;
             Ck.n_int = b1 - b0;
-            hipError_t e = qc_launch_mfma_F_jac(Ck, h->dZ, F ? h->hFc + (size_t)b0 * C.F_stride : nullptr,
+            hipError_t e = launch_F_jac(h, qc_plan_jac(Ck, h->cls), Ck, h->dZ, F ? h->hFc + (size_t)b0 * C.F_stride : nullptr,
                                                 vals ? h->hJc + (size_t)b0 * cp.comp_len : nullptr, (two && (k & 1)) ? h->stream2 : h->stream);
             if (e != hipSuccess) return fail(&h->err, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
             return QC_OK;
@@ -1036,8 +1067,7 @@ static int hess_host(qc_handle* h, const double* Z, const double* mu, double* hv
     // multipliers go up on the second stream -- bit-identical, 0.357 (one part) and 0.378 - 0.388 ms (two parts) against 0.346 for
     // this path: an upload running beside the download slows it (49 against 54.5 GB/s) and the team finishes 20 us after the link.
     static const int want = getenv("QC_HOST_HESS_CHUNKS") ? std::max(1, atoi(getenv("QC_HOST_HESS_CHUNKS"))) : 1;
-    const bool chunkable = h->kernel == QC_KERNEL_MFMA && qc_mfma_hess_supported(P) && !qc_mfma64_hess_supported(P) && !qc_mfma16_padeP_hess_supported(P) &&
-                           h->host_compact != 0;
+    const bool chunkable = h->plan.hess_chunks && h->host_compact != 0;
     const int n_chunks = chunkable ? std::max(1, std::min(want, P.n_int / 64)) : 1;
     if (n_chunks == 1) {
         QC_HIP(h, hipMemcpyAsync(h->dMu + m0, mu + m0, mn * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -1066,7 +1096,7 @@ static int hess_host(qc_handle* h, const double* Z, const double* mu, double* hv
             Ck.t_begin = P.t_begin + b0;
             Ck.n_int = b1 - b0;
             e = hipStreamWaitEvent(h->stream, h->chunk_events[k], 0);
-            if (e == hipSuccess) e = qc_launch_mfma_hess(Ck, h->dZ, h->dMu, h->dH + (size_t)b0 * P.H_stride, h->stream);
+            if (e == hipSuccess) e = launch_hess(h, qc_plan_hess(Ck, h->cls), Ck, h->dZ, h->dMu, h->dH + (size_t)b0 * P.H_stride, h->stream);
             if (e == hipSuccess)
                 e = hipMemcpyAsync(hvals + (size_t)b0 * P.H_stride, h->dH + (size_t)b0 * P.H_stride, (size_t)(b1 - b0) * P.H_stride * sizeof(double),
                                    hipMemcpyDeviceToHost, h->stream);
@@ -1198,8 +1228,8 @@ extern "C" int qc_create_multi(const qc_desc* d, int32_t n_shards, const int32_t
         h->shard_J_off.push_back(b0 * P.J_stride);
         h->shard_H_off.push_back(b0 * P.H_stride);
     }
-    h->kernel = h->shards[0]->kernel;
-    h->dims.kernel = h->kernel;
+    h->cls.kernel = h->shards[0]->cls.kernel;
+    h->dims.kernel = h->cls.kernel;
     {
         // Which way do the Jacobian values come home?  The compact form (one copy of the replicated blocks per link, 3.5x fewer
         // bytes at config 3) leaves the replication to ONE host: N x 41.5 MB per evaluation at the 170 - 235 GB/s its threads reach.
@@ -1441,7 +1471,7 @@ static int list_eval_landing(qc_handle* const* hs, int32_t count, double* F, dou
     qc_handle* h = hs[0];
     const QcParams& P0 = h->prm;
     if (!vals || h->host_landing != 1 || h->host_compact != 1) return 0;
-    struct Seg { CompactPlan cp; bool direct; size_t len, off; };
+    struct Seg { CompactPlan cp; bool direct, batchable; size_t len, off; };
     std::vector<Seg> seg((size_t)count);
     const size_t f_len = (size_t)P0.F_stride;       // always in the block: its layout must not depend on what a call asks for
     size_t blk = f_len;
@@ -1450,7 +1480,8 @@ static int list_eval_landing(qc_handle* const* hs, int32_t count, double* F, dou
         const QcParams& P = hs[i]->prm;
         Seg& S = seg[(size_t)i];
         S.cp = compact_plan(P);
-        S.direct = S.cp.useful && hs[i]->kernel == QC_KERNEL_MFMA && qc_mfma_compact_supported(P);
+        S.direct = S.cp.useful && hs[i]->plan.compact;
+        S.batchable = S.direct && hs[i]->plan.batch_jac;
         S.len = S.direct ? (size_t)S.cp.comp_len : (size_t)P.jac_nnz;
         S.off = blk;
         blk += S.len;
@@ -1475,7 +1506,7 @@ static int list_eval_landing(qc_handle* const* hs, int32_t count, double* F, dou
     // one launch for every member where the batched kernel serves them all (2N <= 16, order 4, equal shapes: the K systems of a
     // sampling problem, the members of a direct sum of equal systems), as the "_dev_multi" entry points do; else one launch each
     bool batch = count >= 2 && count <= 65535;
-    static const bool no_batch = getenv("QC_LIST_BATCH") && atoi(getenv("QC_LIST_BATCH")) == 0;     // A/B diagnostics
+    const bool no_batch = !qc_switches().list_batch;     // A/B diagnostics
     for (int i = 0; i < count; ++i) {
         const Seg& S = seg[(size_t)i];
         QcParams& C = Cs[(size_t)i];
@@ -1484,7 +1515,7 @@ static int list_eval_landing(qc_handle* const* hs, int32_t count, double* F, dou
         C.J_off = (long long)S.off;
         C.F_stride = (long long)blk;                          // (F_off = the handle's first row inside the problem's rows: unchanged)
         const QcParams& Pi = hs[i]->prm;
-        batch = batch && !no_batch && S.direct && hs[i]->kernel == QC_KERNEL_MFMA && qc_mfma16_batchable(Pi) && Pi.m == P0.m && Pi.n == P0.n && Pi.nc == P0.nc;
+        batch = batch && !no_batch && S.batchable && Pi.m == P0.m && Pi.n == P0.n && Pi.nc == P0.nc;
     }
     if (batch) {
         if ((rc = land_batch_params(hs, count, Cs, blk))) return rc;
@@ -1496,8 +1527,7 @@ static int list_eval_landing(qc_handle* const* hs, int32_t count, double* F, dou
     } else {
         for (int i = 0; i < count; ++i) {
             const QcParams& C = Cs[(size_t)i];
-            const hipError_t e = hs[i]->kernel == QC_KERNEL_MFMA ? qc_launch_mfma_F_jac(C, h->dZ, h->dC, h->dC, h->stream)
-                                                                  : qc_launch_lds_F_jac(C, h->dZ, h->dC, h->dC, hs[i]->lds_bytes_jac, h->stream);
+            const hipError_t e = launch_F_jac(hs[i], qc_plan_jac(C, hs[i]->cls), C, h->dZ, h->dC, h->dC, h->stream);
             if (e != hipSuccess) {
                 (void)hipStreamSynchronize(h->stream);
                 return fail(&h->err, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));

@@ -63,6 +63,42 @@ struct QcParams {
                              // [drive][16] weights (doubles), then [drive][16] columns x 17 (ints) -- qc_mfma_fused.hip; else nullptr
 };
 
+// The host-side facts of a handle that kernel selection needs beside QcParams (which holds its tables as device pointers only):
+// everything qc_plan (qc_plan.h) reads is known before anything is allocated.
+struct QcClass {
+    int kernel = QC_KERNEL_LDS;   // QC_KERNEL_MFMA: Gx exists / QC_KERNEL_LDS
+    bool ell16 = false;           // QcParams.ell16 exists (2N = 16 Pade order 4, or the exponential integrator: one entry per drive row)
+    bool stamped = false;         // QcParams.stamps exists (QC_STAMPS=1 diagnostics)
+};                                // (QcParams.ell exists  <=>  QcParams.ell_R > 0)
+
+// Which kernel serves a handle: the answer of qc_plan (qc_plan.h).  One enumerator per kernel family a launch can reach.  F + dF:
+enum QcJacKernel {
+    QC_JAC_LDS, QC_JAC_LDS_GWS,
+    QC_JAC_EXP16, QC_JAC_EXP16_GATHER, QC_JAC_EXP32, QC_JAC_EXP32_GATHER,
+    QC_JAC_PADEP16, QC_JAC_PADE4_64, QC_JAC_PADE4_32_ELL, QC_JAC_PADE4_32, QC_JAC_PADE4_16,
+    QC_JAC_KERNELS
+};
+// mu_d2F:
+enum QcHessKernel {
+    QC_HESS_LDS, QC_HESS_LDS_GWS, QC_HESS_LDS_EXP, QC_HESS_LDS_GWS_EXP,
+    QC_HESS_EXP16, QC_HESS_EXP16_GATHER, QC_HESS_EXP32, QC_HESS_EXP32_GATHER,
+    QC_HESS_PADEP16, QC_HESS_PADE4_64, QC_HESS_PADE4_32_ELL, QC_HESS_PADE4_32,
+    QC_HESS_PADE4_16_G2, QC_HESS_PADE4_16_GATHER, QC_HESS_PADE4_16_TWO_WAVES, QC_HESS_PADE4_16,
+    QC_HESS_KERNELS
+};
+// dF + mu_d2F at one point:
+enum QcFusedKernel { QC_FUSED_TWO_LAUNCHES, QC_FUSED_PADE4_16, QC_FUSED_PADE4_16_GATHER, QC_FUSED_PADE4_32_ELL, QC_FUSED_KERNELS };
+
+struct QcPlan {
+    QcJacKernel jac;
+    QcHessKernel hess;
+    QcFusedKernel fused;
+    bool compact;                  // the F + dF kernel honours QcParams.copies (the compact form of the host path)
+    bool batch_jac, batch_hess;    // may join a batched F + dF / mu_d2F launch (shapes equal to the others': the caller's check)
+    bool hess_chunks;              // the mu_d2F launch may be split into chunks of intervals
+    size_t hess_scratch_doubles;   // scratch the mu_d2F kernel needs in QcParams.hs (0: none), allocated at the first call
+};
+
 struct qc_fanout;
 void qc_fanout_destroy(qc_fanout* f);
 struct qc_rccl_state;
@@ -92,7 +128,8 @@ struct qc_handle {
     QcParams prm;
     qc_dims_t dims;
     int device = 0;
-    int kernel = QC_KERNEL_LDS;
+    QcClass cls;               // MFMA or LDS, and what else qc_plan needs beside prm
+    QcPlan plan;               // qc_plan(prm, cls), computed once by qc_create (copies of prm with other n_int / copies: computed per launch)
     size_t lds_bytes_jac = 0, lds_bytes_hess = 0;
     double* dG = nullptr;
     double* dGx = nullptr;
@@ -163,10 +200,23 @@ int qc_fail(std::string* err, int code, const std::string& msg);   // records th
 
 // Fills prm/dims from a descriptor (host only). Returns QC_OK or error with message in `err`.
 int qc_build_params(const qc_desc* d, QcParams* prm, qc_dims_t* dims, std::string* err);
+// The part of qc_create that needs no device: parameters, antisymmetry, MFMA-or-LDS, the row-gather tables, the LDS budget.
+// `params_ok` tells an invalid descriptor (reported before the device is looked at) from a refusal (reported after).
+struct qc_blueprint {
+    QcParams prm;              // every device pointer still null
+    qc_dims_t dims;
+    QcClass cls;
+    size_t lds_bytes_jac = 0, lds_bytes_hess = 0;
+    std::vector<double> G, Gx;         // generators as given; their kernel-specific images (MFMA)
+    std::vector<char> ell, ell16;      // row-gather tables (empty: none)
+    bool params_ok = false;
+};
+int qc_blueprint_build(const qc_desc* d, qc_blueprint* out, std::string* err);
 void qc_local_jac_structure(const QcParams& P, std::vector<int32_t>* rows, std::vector<int32_t>* cols);
 void qc_local_hess_structure(const QcParams& P, std::vector<int32_t>* rows, std::vector<int32_t>* cols);
 
-// Kernel launchers (defined in the .hip files). All asynchronous on `stream`.
+// Kernel launchers (defined in the .hip files), one per kernel family, and what each family can serve (`*_supported`: called by
+// qc_plan.cpp only, which decides between the families). All asynchronous on `stream`.
 size_t qc_lds_bytes_jac(const QcParams& P);
 size_t qc_lds_bytes_hess(const QcParams& P);
 hipError_t qc_launch_lds_F_jac(const QcParams& P, const double* dZ, double* dF, double* dJ, size_t lds, hipStream_t st);
@@ -174,12 +224,10 @@ hipError_t qc_launch_lds_hess(const QcParams& P, const double* dZ, const double*
                               hipStream_t st);
 size_t qc_lds_exp_hess_bytes(const QcParams& P);     // exponential integrator's mu_d2F, any size: qc_lds_exp_hess.hip
 hipError_t qc_launch_lds_exp_hess(const QcParams& P, const double* dZ, const double* dMu, double* dH, size_t lds, hipStream_t st);
-bool qc_mfma_supported(const QcParams& P);
-bool qc_mfma_hess_supported(const QcParams& P);
-bool qc_mfma_compact_supported(const QcParams& P);   // the F + dF kernel honours QcParams.copies (order-4 kernels, 2N <= 32)
+bool qc_mfma_pade4_supported(const QcParams& P);     // the order-4 F + dF kernels, 2N <= 32 (they honour QcParams.copies)
 size_t qc_mfma_gx_doubles(const QcParams& P);
 void qc_mfma_pack_G(const QcParams& P, const double* G_host, double* Gx_host);
-hipError_t qc_launch_mfma_F_jac(const QcParams& P, const double* dZ, double* dF, double* dJ, hipStream_t st);
+hipError_t qc_launch_mfma16_F_jac(const QcParams& P, const double* dZ, double* dF, double* dJ, hipStream_t st);
 size_t qc_mfma32_gx_doubles(const QcParams& P);
 void qc_mfma32_pack_G(const QcParams& P, const double* G_host, double* Gx_host);
 hipError_t qc_launch_mfma32_F_jac(const QcParams& P, const double* dZ, double* dF, double* dJ, hipStream_t st);
@@ -194,39 +242,39 @@ hipError_t qc_launch_mfma64_F_jac(const QcParams& P, const double* dZ, double* d
 bool qc_mfma64_hess_supported(const QcParams& P);
 size_t qc_mfma64_hess_scratch_doubles(const QcParams& P);
 hipError_t qc_launch_mfma64_hess(const QcParams& P, const double* dZ, const double* dMu, double* dH, hipStream_t st);
-bool qc_mfma16_batchable(const QcParams& P);
+bool qc_mfma16_batchable(const QcParams& P, const QcClass& cls);
 hipError_t qc_launch_mfma16_F_jac_batch(const QcParams& P0, const QcParams* dPb, int count, const double* dZ, double* dF, double* dJ,
                                         hipStream_t st);
 hipError_t qc_launch_mfma16_hess_batch(const QcParams& P0, const QcParams* dPb, int count, const double* dZ, const double* dMu, double* dH,
                                        hipStream_t st);
 bool qc_mfma_exp_supported(const QcParams& P);
-hipError_t qc_launch_mfma_exp(const QcParams& P, const double* dZ, double* dF, double* dJ, hipStream_t st);
+hipError_t qc_launch_mfma_exp(const QcParams& P, bool ell, const double* dZ, double* dF, double* dJ, hipStream_t st);
 bool qc_mfma_exp_hess_supported(const QcParams& P);   // mu_d2F of the exponential integrator, 2N <= 16: qc_mfma_exp_hess.hip
-hipError_t qc_launch_mfma_exp_hess(const QcParams& P, const double* dZ, const double* dMu, double* dH, hipStream_t st);
+hipError_t qc_launch_mfma_exp_hess(const QcParams& P, bool ell, const double* dZ, const double* dMu, double* dH, hipStream_t st);
 bool qc_mfma32_exp_hess_supported(const QcParams& P);  // ... 16 < 2N <= 32: qc_mfma32_exp_hess.hip
-hipError_t qc_launch_mfma32_exp_hess(const QcParams& P, const double* dZ, const double* dMu, double* dH, hipStream_t st);
+hipError_t qc_launch_mfma32_exp_hess(const QcParams& P, bool ell, const double* dZ, const double* dMu, double* dH, hipStream_t st);
 bool qc_mfma32_exp_supported(const QcParams& P);
-hipError_t qc_launch_mfma32_exp(const QcParams& P, const double* dZ, double* dF, double* dJ, hipStream_t st);
+hipError_t qc_launch_mfma32_exp(const QcParams& P, bool ell, const double* dZ, double* dF, double* dJ, hipStream_t st);
 bool qc_mfma32_hess_supported(const QcParams& P);
 // sparse drive generators (at most 2 entries per row), 2N = 32, Hermitian Hamiltonians: qc_mfma32_ell.hip
 int qc_mfma32_ell_build(const QcParams& P, const double* G_host, std::vector<char>* blob, int* slots_out);
 bool qc_mfma16_ell_build(const QcParams& P, const double* G_host, std::vector<char>* blob);   // 2N = 16, one entry per drive row: qc_mfma_fused.hip
 bool qc_exp_ell_build(const QcParams& P, const double* G_host, std::vector<char>* blob);   // exponential integrator, 2N <= 32, at most one entry per drive row: qc_mfma_exp_hess.hip
 void qc_mfma16_ell_pair_table(const QcParams& P, std::vector<char>* blob);                    // ... its pair table for the (a, a) block: qc_mfma_hess_g2.hip
-bool qc_mfma16_hess_g2(const QcParams& P);
+bool qc_mfma16_hess_g2_supported(const QcParams& P, const QcClass& cls);
 hipError_t qc_launch_mfma16_hess_g2(const QcParams& P, const double* dZ, const double* dMu, double* dH, hipStream_t st);
-bool qc_mfma16_hess_gathers(const QcParams& P);      // ... the mu_d2F launches (qc_mfma_hess.hip, qc_mfma_hess2.hip)
-bool qc_mfma16_fused_gathers(const QcParams& P);     // ... and whether the one-call launch of this handle takes the row-gather form
 hipError_t qc_launch_mfma32_ell_hess(const QcParams& P, const double* dZ, const double* dMu, double* dH, hipStream_t st);
 hipError_t qc_launch_mfma32_ell_F_jac(const QcParams& P, const double* dZ, double* dF, double* dJ, hipStream_t st);
 hipError_t qc_launch_mfma32_ell_fused(const QcParams& P, const double* dZ, const double* dMu, double* dF, double* dJ, double* dH, hipStream_t st);
 hipError_t qc_launch_mfma32_hess(const QcParams& P, const double* dZ, const double* dMu, double* dH, hipStream_t st);
 // F + dF + mu_d2F in one launch (qc_mfma_fused.hip): 2N = 16, a unitary on 8 levels, antisymmetric generators, 1 .. 6 drives
-bool qc_mfma16_fused_supported(const QcParams& P);
-bool qc_mfma16_hess2_supported(const QcParams& P);
+bool qc_mfma16_fused_supported(const QcParams& P, const QcClass& cls);
+bool qc_mfma16_hess2_supported(const QcParams& P, const QcClass& cls);
 hipError_t qc_launch_mfma16_hess2(const QcParams& P, const double* dZ, const double* dMu, double* dH, hipStream_t st);
-hipError_t qc_launch_mfma16_fused(const QcParams& P, const double* dZ, const double* dMu, double* dF, double* dJ, double* dH, hipStream_t st);
-hipError_t qc_launch_mfma_hess(const QcParams& P, const double* dZ, const double* dMu, double* dH, hipStream_t st);
+hipError_t qc_launch_mfma16_fused(const QcParams& P, bool gather, const double* dZ, const double* dMu, double* dF, double* dJ, double* dH, hipStream_t st);
+bool qc_mfma16_hess_supported(const QcParams& P);     // the order-4 mu_d2F kernels at 2N <= 16
+bool qc_mfma16_hess_gather_supported(const QcParams& P, const QcClass& cls);   // ... the one-wave kernel's row-gather form
+hipError_t qc_launch_mfma16_hess(const QcParams& P, bool gather, const double* dZ, const double* dMu, double* dH, hipStream_t st);   // the one-wave kernel
 
 hipError_t qc_launch_pack_jac(const double* dJ, double* dJc, int n_int, int jac_nnz, int comp_len, int n2, int jo_F, int jo_B, int head2,
                               int tail_src, hipStream_t st);

@@ -428,9 +428,8 @@ bool qc_mfma32_exp_supported(const QcParams& P) {
     return P.integrator == QC_EXPONENTIAL && P.n > 16 && P.n <= 32 && P.nc <= 16 && P.m <= kE32Mmax;
 }
 
-hipError_t qc_launch_mfma32_exp(const QcParams& P, const double* dZ, double* dF, double* dJ, hipStream_t st) {
-    static const bool ell_off = getenv("QC_EXP_ELL") && atoi(getenv("QC_EXP_ELL")) == 0;      // A/B diagnostics
-    if (dJ && P.ell16 != nullptr && !ell_off) hipLaunchKernelGGL((qc_mfma32_exp_kernel<true, true>), dim3(P.n_int), dim3(kE32Threads), 0, st, P, dZ, dF, dJ);
+hipError_t qc_launch_mfma32_exp(const QcParams& P, bool ell, const double* dZ, double* dF, double* dJ, hipStream_t st) {
+    if (dJ && ell) hipLaunchKernelGGL((qc_mfma32_exp_kernel<true, true>), dim3(P.n_int), dim3(kE32Threads), 0, st, P, dZ, dF, dJ);
     else if (dJ) hipLaunchKernelGGL(qc_mfma32_exp_kernel<true>, dim3(P.n_int), dim3(kE32Threads), 0, st, P, dZ, dF, dJ);
     else hipLaunchKernelGGL(qc_mfma32_exp_kernel<false>, dim3(P.n_int), dim3(kE32Threads), 0, st, P, dZ, dF, dJ);
     return hipGetLastError();

@@ -494,12 +494,11 @@ __global__ __launch_bounds__(kXThreads, 1) void qc_mfma32_exp_hess_kernel(const 
 }  // namespace
 
 bool qc_mfma32_exp_hess_supported(const QcParams& P) {
-    return P.integrator == QC_EXPONENTIAL && P.n > 16 && P.n <= 32 && P.nc <= 16 && P.m <= kXMmax && P.hess_nnz > 0 && P.Gx != nullptr;
+    return P.integrator == QC_EXPONENTIAL && P.n > 16 && P.n <= 32 && P.nc <= 16 && P.m <= kXMmax && P.hess_nnz > 0;
 }
 
-hipError_t qc_launch_mfma32_exp_hess(const QcParams& P, const double* dZ, const double* dMu, double* dH, hipStream_t st) {
-    static const bool ell_off = getenv("QC_EXP_ELL") && atoi(getenv("QC_EXP_ELL")) == 0;      // A/B diagnostics
-    if (P.ell16 != nullptr && !ell_off) hipLaunchKernelGGL(qc_mfma32_exp_hess_kernel<true>, dim3(P.n_int), dim3(kXThreads), 0, st, P, dZ, dMu, dH);
+hipError_t qc_launch_mfma32_exp_hess(const QcParams& P, bool ell, const double* dZ, const double* dMu, double* dH, hipStream_t st) {
+    if (ell) hipLaunchKernelGGL(qc_mfma32_exp_hess_kernel<true>, dim3(P.n_int), dim3(kXThreads), 0, st, P, dZ, dMu, dH);
     else hipLaunchKernelGGL(qc_mfma32_exp_hess_kernel<false>, dim3(P.n_int), dim3(kXThreads), 0, st, P, dZ, dMu, dH);
     return hipGetLastError();
 }

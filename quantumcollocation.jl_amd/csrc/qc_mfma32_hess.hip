@@ -439,7 +439,7 @@ __global__ __launch_bounds__(kHThreads32, 1) void qc_mfma32_pade4_hess_kernel(co
 }  // namespace
 
 bool qc_mfma32_hess_supported(const QcParams& P) {
-    return P.integrator == QC_PADE && P.p == 2 && P.n > 16 && P.n <= 32 && P.nc <= 16 && P.m <= kHMax32 && P.Gx != nullptr;
+    return P.integrator == QC_PADE && P.p == 2 && P.n > 16 && P.n <= 32 && P.nc <= 16 && P.m <= kHMax32;
 }
 
 hipError_t qc_launch_mfma32_hess(const QcParams& P, const double* dZ, const double* dMu, double* dH, hipStream_t st) {

@@ -283,7 +283,7 @@ __global__ __launch_bounds__(kHT64, 1) void qc_mfma64_pade4_hess_kernel(const Qc
 }  // namespace
 
 bool qc_mfma64_hess_supported(const QcParams& P) {
-    return P.integrator == QC_PADE && P.p == 2 && P.n > 32 && P.n <= 64 && P.nc <= 32 && P.m <= kHMax64 && P.Gx != nullptr;
+    return P.integrator == QC_PADE && P.p == 2 && P.n > 32 && P.n <= 64 && P.nc <= 32 && P.m <= kHMax64;
 }
 
 size_t qc_mfma64_hess_scratch_doubles(const QcParams& P) { return (size_t)kHGrid64 * 2 * kScratchSet; }

@@ -336,10 +336,9 @@ bool qc_mfma_exp_supported(const QcParams& P) {
     return P.integrator == QC_EXPONENTIAL && P.n <= 16 && P.nc <= 8 && P.m <= kXMmax;
 }
 
-hipError_t qc_launch_mfma_exp(const QcParams& P, const double* dZ, double* dF, double* dJ, hipStream_t st) {
+// `ell`: drive generators with one entry per row (QcParams.ell16), the row-gather form of the Horner steps
+hipError_t qc_launch_mfma_exp(const QcParams& P, bool ell, const double* dZ, double* dF, double* dJ, hipStream_t st) {
     const int grid = P.n_int;
-    static const bool ell_off = getenv("QC_EXP_ELL") && atoi(getenv("QC_EXP_ELL")) == 0;      // A/B diagnostics
-    const bool ell = P.ell16 != nullptr && !ell_off;      // drive generators with one entry per row: the row-gather form of the Horner steps
 #define QC_XJ1(MU_, W_, I_) do { const int wgs = (grid + I_ - 1) / I_; \
                             if (ell) hipLaunchKernelGGL((qc_mfma16_exp_kernel<true, MU_, W_, true, I_>), dim3(wgs), dim3(64 * W_ * I_), 0, st, P, dZ, dF, dJ); \
                             else hipLaunchKernelGGL((qc_mfma16_exp_kernel<true, MU_, W_, false, I_>), dim3(wgs), dim3(64 * W_ * I_), 0, st, P, dZ, dF, dJ); } while (0)

@@ -497,7 +497,7 @@ __global__ __launch_bounds__(64 * kW * kIPW) __attribute__((amdgpu_waves_per_eu(
 }  // namespace
 
 bool qc_mfma_exp_hess_supported(const QcParams& P) {
-    return P.integrator == QC_EXPONENTIAL && P.n <= 16 && P.nc <= 8 && P.m <= kXHMmax && P.hess_nnz > 0 && P.Gx != nullptr;
+    return P.integrator == QC_EXPONENTIAL && P.n <= 16 && P.nc <= 8 && P.m <= kXHMmax && P.hess_nnz > 0;
 }
 
 // Rows of the drive generators of an exponential-integrator handle at 2N <= 32 whose drives have at most ONE entry per row:
@@ -524,10 +524,8 @@ bool qc_exp_ell_build(const QcParams& P, const double* G, std::vector<char>* blo
     return true;
 }
 
-hipError_t qc_launch_mfma_exp_hess(const QcParams& P, const double* dZ, const double* dMu, double* dH, hipStream_t st) {
+hipError_t qc_launch_mfma_exp_hess(const QcParams& P, bool ell, const double* dZ, const double* dMu, double* dH, hipStream_t st) {
     const int grid = P.n_int;
-    static const bool ell_off = getenv("QC_EXP_ELL") && atoi(getenv("QC_EXP_ELL")) == 0;      // A/B diagnostics
-    const bool ell = P.ell16 != nullptr && !ell_off;
 #define QC_XH1(MU_, W_, I_) do { const int wgs = (grid + I_ - 1) / I_; \
                             if (ell) hipLaunchKernelGGL((qc_mfma16_exp_hess_kernel<MU_, W_, true, I_>), dim3(wgs), dim3(64 * W_ * I_), 0, st, P, dZ, dMu, dH); \
                             else hipLaunchKernelGGL((qc_mfma16_exp_hess_kernel<MU_, W_, false, I_>), dim3(wgs), dim3(64 * W_ * I_), 0, st, P, dZ, dMu, dH); } while (0)

@@ -35,7 +35,7 @@
 // (finite inputs), and the one call stays bit-identical to the two launches.  120 f64 MFMAs per interval (64 cycles each on the SIMD's
 // one matrix pipe: 3.6 us of pipe time per SIMD at T = 1000, in front of and between the stores of a store-bound kernel) become 48; the
 // copy wave's stage A no longer paces its tile copies; the compute wave holds no image in a register.  Used for trajectories of more
-// than one and up to four device rounds (qc_mfma16_fused_gathers below): within one round the launch follows its store stream and the images
+// than one and up to four device rounds (qc_plan.cpp): within one round the launch follows its store stream and the images
 // are faster; beyond four rounds the box decides.
 #include <stdlib.h>
 
@@ -733,28 +733,14 @@ __global__ __launch_bounds__(kFuThreads, 2) void qc_mfma16_pade4_fused_kernel(co
 
 }  // namespace
 
-// The row-gather form (ELL) serves trajectories of one to four device rounds (four workgroups per CU: 1024 intervals a round): there the
-// matrix pipes decide how fast workgroups retire and make room -- T = 1500 / 2000 / 3000 / 4000: 21.6 / 25.5 / 36.3 / 44.0 us against 22.7 /
-// 26.4 / 37.3 / 45.9 with the dense images, on every box measured -- while a single round follows its store stream and is 0.3 - 0.7 us
-// FASTER with the images (T = 1000: 12.8 against 13.5), and long streams are decided by the box: T = 6000 ... 32000 lose 2 - 4 % with the
-// gathers on two boxes and win 6 - 8 % (T = 16000: 143 - 148 against 155 - 156 us) on a third (profiles/r05_fused_ell16.txt: A/B inside one
-// process on the same buffers, profiles/fused_ab.py -- across processes long streams are bimodal).  QC_FUSED_ELL=0 / 1: never / always.
-constexpr int kFuEllMinIntervals = 1025, kFuEllMaxIntervals = 4096;
-bool qc_mfma16_fused_gathers(const QcParams& P) {
-#ifdef QC_FUSED_ELL_DYNAMIC      /* experiment builds: the switch is read at every launch (A/B inside one process, on the same buffers) */
-    const int mode = getenv("QC_FUSED_ELL") ? atoi(getenv("QC_FUSED_ELL")) : -1;
-#else
-    static const int mode = getenv("QC_FUSED_ELL") ? atoi(getenv("QC_FUSED_ELL")) : -1;
-#endif
-    return P.ell16 != nullptr && mode != 0 && (mode == 1 || (P.n_int >= kFuEllMinIntervals && P.n_int <= kFuEllMaxIntervals));
-}
-
-bool qc_mfma16_fused_supported(const QcParams& P) {
+// (when the plan prefers the row-gather form: qc_plan.cpp)
+bool qc_mfma16_fused_supported(const QcParams& P, const QcClass& cls) {
     return P.integrator == QC_PADE && P.p == 2 && P.n == 16 && P.nc == 8 && P.antisym && P.m >= 1 && P.m <= 6 && P.hess_nnz > 0 && P.store_mode == 2 &&
-           (P.stamps == nullptr || (P.m > 4 && P.n_int <= kFuMaxStamped)) && P.dbg_skip == 0 && P.Gx != nullptr && P.copies == P.nc;
+           (!cls.stamped || (P.m > 4 && P.n_int <= kFuMaxStamped)) && P.dbg_skip == 0 && P.copies == P.nc;
 }
 
-hipError_t qc_launch_mfma16_fused(const QcParams& P, const double* dZ, const double* dMu, double* dF, double* dJ, double* dH, hipStream_t st) {
+// `gather`: the plan chose the row-gather form (QcParams.ell16 exists)
+hipError_t qc_launch_mfma16_fused(const QcParams& P, bool gather, const double* dZ, const double* dMu, double* dF, double* dJ, double* dH, hipStream_t st) {
     for (int b0 = 0; b0 < P.n_int; b0 += kFuMaxGrid) {
         const int n = P.n_int - b0 < kFuMaxGrid ? P.n_int - b0 : kFuMaxGrid;
         const double* Zt = dZ + (P.t_begin + b0) * (long long)P.zdim;
@@ -771,7 +757,7 @@ hipError_t qc_launch_mfma16_fused(const QcParams& P, const double* dZ, const dou
         // 21: everything but bit 32 -- for comparison.
         static const bool plain = getenv("QC_FUSED_VARIANT") && atoi(getenv("QC_FUSED_VARIANT")) == 0;
         static const int var = getenv("QC_FUSED_VARIANT") ? atoi(getenv("QC_FUSED_VARIANT")) : -1;
-        const bool ell = qc_mfma16_fused_gathers(P) && var < 0;
+        const bool ell = gather && var < 0;
         if (P.stamps != nullptr && ell) hipLaunchKernelGGL((qc_mfma16_pade4_fused_kernel<6, 61, true>), dim3(n), dim3(kFuThreads), 0, st, P.Gx, Zt, mu0, n, P.zdim,
                                                            P.off_a, P.off_dt, P.m, P.off_U, (int)P.F_stride, P, Fp, Jp, Hp);
         else if (P.stamps != nullptr) QC_FU(6, 61);

@@ -661,10 +661,8 @@ __global__ __launch_bounds__(64) void qc_mfma16_pade4_hess_anti_kernel(const dou
 
 }  // namespace
 
-bool qc_mfma_hess_supported(const QcParams& P) {
-    if (qc_mfma32_hess_supported(P) || qc_mfma64_hess_supported(P) || qc_mfma16_padeP_hess_supported(P)) return true;
-    return P.integrator == QC_PADE && P.p == 2 && P.n <= 16 && P.nc <= 8 && P.m <= kHMmax;
-}
+// the order-4 mu_d2F kernels at 2N <= 16 (this file, qc_mfma_hess2.hip, qc_mfma_hess_g2.hip)
+bool qc_mfma16_hess_supported(const QcParams& P) { return P.integrator == QC_PADE && P.p == 2 && P.n <= 16 && P.nc <= 8 && P.m <= kHMmax; }
 
 hipError_t qc_launch_mfma16_hess_batch(const QcParams& P0, const QcParams* dPb, int count, const double* dZ, const double* dMu, double* dH,
                                        hipStream_t st) {
@@ -686,18 +684,13 @@ hipError_t qc_launch_mfma16_hess_batch(const QcParams& P0, const QcParams* dPb, 
     return hipGetLastError();
 }
 
-// mu_d2F alone takes the row-gather form of the one-wave kernel wherever the handle's drives allow it (P.ell16): the launch is a latency
-// chain per interval, mostly the 68 dependent f64 MFMAs -- 20 with the gathers -- and, holding no drive image through stage B, the form
-// keeps its stage-A tiles in registers instead of LDS: 14 KB of LDS and 217 registers, EIGHT workgroups per CU (the dense-image form:
-// six; round 4: four).  T = 1000 / 2000 / 4000 / 8000 / 32000: 8.1 / 11.5 / 20.4 / 38.1 / 120 us against 8.7 (two-wave kernel) / 15.7 / 23.9 /
-// 42.3 / 140 with the gathers but six per CU, and 8.7 / 15.4 / 25.9 / 47.2 / 173 in round 4 (profiles/r05_hess_long.txt).  QC_HESS_ELL=0: never.
-bool qc_mfma16_hess_gathers(const QcParams& P) {
-    static const bool off = getenv("QC_HESS_ELL") && atoi(getenv("QC_HESS_ELL")) == 0;
-    return !off && P.ell16 != nullptr && P.antisym && P.n == 16 && P.nc == 8 && P.m >= 1 && P.m <= 6 && P.stamps == nullptr;
+// the row-gather instantiation of the one-wave kernel (drive generators with one entry per row: QcClass.ell16)
+bool qc_mfma16_hess_gather_supported(const QcParams& P, const QcClass& cls) {
+    return cls.ell16 && P.antisym && P.n == 16 && P.nc == 8 && P.m >= 1 && P.m <= 6 && !cls.stamped;
 }
 
 template <int HM, bool KET>
-static void launch_hess16(const QcParams& P, const double* dZ, const double* dMu, double* dH, hipStream_t st, int grid) {
+static void launch_hess16(const QcParams& P, bool gather, const double* dZ, const double* dMu, double* dH, hipStream_t st, int grid) {
     const bool once = grid == P.n_int;      // one interval per workgroup: the loop-free instantiations
     if (P.antisym) {
         if constexpr (HM == 6 && !KET) {
@@ -707,7 +700,7 @@ static void launch_hess16(const QcParams& P, const double* dZ, const double* dMu
             }
         }
         if constexpr (!KET && HM <= 6) {
-            if (once && qc_mfma16_hess_gathers(P)) {      // drive generators with one entry per row: the row-gather instantiation (loop-free launches)
+            if (once && gather) {      // drive generators with one entry per row: the row-gather instantiation (loop-free launches)
                 hipLaunchKernelGGL((qc_mfma16_pade4_hess_anti_kernel<HM, KET, false, true, false, true>), dim3(grid), dim3(64), 0, st, QC_HESS_HOT_ARGS(P), P, dZ, dMu, dH, nullptr);
                 return;
             }
@@ -720,14 +713,8 @@ static void launch_hess16(const QcParams& P, const double* dZ, const double* dMu
     else hipLaunchKernelGGL((qc_mfma16_pade4_hess_kernel<HM, KET, false>), dim3(grid), dim3(64), 0, st, P, dZ, dMu, dH, nullptr);
 }
 
-hipError_t qc_launch_mfma_hess(const QcParams& P, const double* dZ, const double* dMu, double* dH, hipStream_t st) {
-    if (qc_mfma16_padeP_hess_supported(P)) return qc_launch_mfma16_padeP_hess(P, dZ, dMu, dH, st);
-    if (P.n > 32) return qc_launch_mfma64_hess(P, dZ, dMu, dH, st);
-    if (P.n > 16) return P.ell ? qc_launch_mfma32_ell_hess(P, dZ, dMu, dH, st) : qc_launch_mfma32_hess(P, dZ, dMu, dH, st);
-    if (qc_mfma16_hess_g2(P)) return qc_launch_mfma16_hess_g2(P, dZ, dMu, dH, st);       // one entry per drive-generator row: qc_mfma_hess_g2.hip (round 6)
-    // two waves per interval up to one round of the device (qc_mfma_hess2.hip) -- unless the drives allow the one-wave kernel's row-gather
-    // form, which keeps eight workgroups per CU resident and is faster at every length (T = 750 / 1000: 7.85 / 8.12 against 8.08 / 8.74 us)
-    if (qc_mfma16_hess2_supported(P) && !qc_mfma16_hess_gathers(P)) return qc_launch_mfma16_hess2(P, dZ, dMu, dH, st);
+// `gather`: the plan chose the row-gather form (qc_mfma16_hess_gather_supported)
+hipError_t qc_launch_mfma16_hess(const QcParams& P, bool gather, const double* dZ, const double* dMu, double* dH, hipStream_t st) {
     // One interval per workgroup at any length (round 5: the loop-free instantiation needs 228 registers and 25.3 KB of LDS at six
     // drives -- six workgroups per CU, the hardware refilling each CU as its workgroups retire; the persistent loop's instantiation
     // needs 308 registers, four per CU).  T = 3000 / 4000 / 8000 / 32000: 20.1 / 25.8 / 45.9 / 156.9 us against 20.8 / 25.9 / 47.0 / 172.8
@@ -736,18 +723,18 @@ hipError_t qc_launch_mfma_hess(const QcParams& P, const double* dZ, const double
     static const int once_max = getenv("QC_HESS_ONCE_MAX") ? atoi(getenv("QC_HESS_ONCE_MAX")) : (1 << 30);
     // Six workgroups per CU live 8.2 instead of 6.5 - 7.4 us each: between 1.5 and 2 rounds of the device that is a loss (two rounds either
     // way: T = 2000 17.7 against 15.4 us) -- there the persistent instantiation (four per CU) with one round of workgroups stays.
-    const bool window = P.antisym && P.m > 4 && P.m <= 6 && P.n_int > 1536 && P.n_int <= 2048 && !qc_mfma16_hess_gathers(P);   // (the row-gather form: eight per CU, one round)
+    const bool window = P.antisym && P.m > 4 && P.m <= 6 && P.n_int > 1536 && P.n_int <= 2048 && !gather;   // (the row-gather form: eight per CU, one round)
     const int grid = (P.n_int <= once_max && !window) ? P.n_int : (P.n_int < grid_cap ? P.n_int : grid_cap);
     if (P.nc != 8 || P.n != 16) {
-        if (P.m <= 2) launch_hess16<2, true>(P, dZ, dMu, dH, st, grid);
-        else if (P.m <= 4) launch_hess16<4, true>(P, dZ, dMu, dH, st, grid);
-        else if (P.m <= 6) launch_hess16<6, true>(P, dZ, dMu, dH, st, grid);
-        else launch_hess16<8, true>(P, dZ, dMu, dH, st, grid);
+        if (P.m <= 2) launch_hess16<2, true>(P, gather, dZ, dMu, dH, st, grid);
+        else if (P.m <= 4) launch_hess16<4, true>(P, gather, dZ, dMu, dH, st, grid);
+        else if (P.m <= 6) launch_hess16<6, true>(P, gather, dZ, dMu, dH, st, grid);
+        else launch_hess16<8, true>(P, gather, dZ, dMu, dH, st, grid);
         return hipGetLastError();
     }
-    if (P.m <= 2) launch_hess16<2, false>(P, dZ, dMu, dH, st, grid);
-    else if (P.m <= 4) launch_hess16<4, false>(P, dZ, dMu, dH, st, grid);
-    else if (P.m <= 6) launch_hess16<6, false>(P, dZ, dMu, dH, st, grid);
-    else launch_hess16<8, false>(P, dZ, dMu, dH, st, grid);
+    if (P.m <= 2) launch_hess16<2, false>(P, gather, dZ, dMu, dH, st, grid);
+    else if (P.m <= 4) launch_hess16<4, false>(P, gather, dZ, dMu, dH, st, grid);
+    else if (P.m <= 6) launch_hess16<6, false>(P, gather, dZ, dMu, dH, st, grid);
+    else launch_hess16<8, false>(P, gather, dZ, dMu, dH, st, grid);
     return hipGetLastError();
 }

@@ -399,15 +399,10 @@ __global__ __launch_bounds__(kH2Threads, 2) void qc_mfma16_pade4_hess2_kernel(co
 
 }  // namespace
 
-// Serves launches of up to kH2MaxInt intervals -- one round of the device (four workgroups per CU): measured against the one-wave kernel
-// (profiles/r03_hess2_ab.txt) 6.1 - 6.8 / 7.0 / 8.6 us against 7.1 / 7.5 / 8.7 at T = 250 / 500 / 1000; beyond one round the one-wave
-// kernel's persistent grid is faster (T = 2000: 15.1 against 17.3 us; T = 8000: 47.7 against 52.9).  QC_HESS_TWO_WAVES=0: never.
-constexpr int kH2MaxInt = 1024;
-
-bool qc_mfma16_hess2_supported(const QcParams& P) {
-    static const bool off = getenv("QC_HESS_TWO_WAVES") && atoi(getenv("QC_HESS_TWO_WAVES")) == 0;
-    return !off && P.n_int <= kH2MaxInt && P.integrator == QC_PADE && P.p == 2 && P.n == 16 && P.nc == 8 && P.antisym && P.m >= 1 && P.m <= 6 && P.hess_nnz > 0 &&
-           (P.stamps == nullptr || P.m > 4) && P.dbg_skip == 0 && P.Gx != nullptr;
+// (up to which length the plan prefers this kernel to the one-wave kernel: qc_plan.cpp)
+bool qc_mfma16_hess2_supported(const QcParams& P, const QcClass& cls) {
+    return P.integrator == QC_PADE && P.p == 2 && P.n == 16 && P.nc == 8 && P.antisym && P.m >= 1 && P.m <= 6 && P.hess_nnz > 0 &&
+           (!cls.stamped || P.m > 4) && P.dbg_skip == 0;
 }
 
 hipError_t qc_launch_mfma16_hess2(const QcParams& P, const double* dZ, const double* dMu, double* dH, hipStream_t st) {

@@ -353,10 +353,8 @@ void qc_mfma16_ell_pair_table(const QcParams& P, std::vector<char>* blob) {
         }
 }
 
-bool qc_mfma16_hess_g2(const QcParams& P) {
-    static const bool off = getenv("QC_HESS_G2") && atoi(getenv("QC_HESS_G2")) == 0;
-    static const bool ell_off = getenv("QC_HESS_ELL") && atoi(getenv("QC_HESS_ELL")) == 0;
-    return !off && !ell_off && P.ell16 != nullptr && P.antisym && P.n == 16 && P.nc == 8 && P.m >= 1 && P.m <= 6 && (P.stamps == nullptr || P.m > 4);
+bool qc_mfma16_hess_g2_supported(const QcParams& P, const QcClass& cls) {
+    return cls.ell16 && P.antisym && P.n == 16 && P.nc == 8 && P.m >= 1 && P.m <= 6 && (!cls.stamped || P.m > 4);
 }
 
 hipError_t qc_launch_mfma16_hess_g2(const QcParams& P, const double* dZ, const double* dMu, double* dH, hipStream_t st) {

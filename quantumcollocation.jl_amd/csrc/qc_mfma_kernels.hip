@@ -601,12 +601,8 @@ __global__ __launch_bounds__(JAC ? kThreads : 64, 2) void qc_mfma16_pade4_kernel
 
 }  // namespace
 
-bool qc_mfma_compact_supported(const QcParams& P) {
-    return P.integrator == QC_PADE && P.p == 2 && !qc_mfma16_padeP_supported(P) && ((P.n <= 16 && P.nc <= 8) || (P.n <= 32 && P.nc <= 16)) && P.m <= 32;
-}
-
-bool qc_mfma_supported(const QcParams& P) {
-    if (qc_mfma_exp_supported(P) || qc_mfma32_exp_supported(P) || qc_mfma64_supported(P) || qc_mfma16_padeP_supported(P)) return true;
+// the order-4 F + dF kernels up to 2N = 32 (this file and qc_mfma32_kernels.hip, qc_mfma32_ell.hip); they honour QcParams.copies
+bool qc_mfma_pade4_supported(const QcParams& P) {
     return P.integrator == QC_PADE && P.p == 2 && ((P.n <= 16 && P.nc <= 8) || (P.n <= 32 && P.nc <= 16)) && P.m <= 32;
 }
 
@@ -666,10 +662,9 @@ static void launch16(const QcParams& P, const double* dZ, double* dF, double* dJ
     else launch16m<JAC, DIAG, 8>(P, dZ, dF, dJ, st, grid, threads);
 }
 
-// One launch for `count` handles (gridDim.y = count).  The caller has checked qc_mfma16_batchable for every handle.
-bool qc_mfma16_batchable(const QcParams& P) {
-    return P.integrator == QC_PADE && P.p == 2 && P.n <= 16 && P.nc <= 8 && P.m <= 32 && P.store_mode == 2 && P.stamps == nullptr &&
-           P.dbg_skip == 0 && P.Gx != nullptr;
+// One launch for `count` handles (gridDim.y = count).  The caller has checked qc_mfma16_batchable for every handle (an MFMA handle's).
+bool qc_mfma16_batchable(const QcParams& P, const QcClass& cls) {
+    return P.integrator == QC_PADE && P.p == 2 && P.n <= 16 && P.nc <= 8 && P.m <= 32 && P.store_mode == 2 && !cls.stamped && P.dbg_skip == 0;
 }
 
 template <bool JAC, int MU>
@@ -693,16 +688,7 @@ hipError_t qc_launch_mfma16_F_jac_batch(const QcParams& P0, const QcParams* dPb,
     return hipGetLastError();
 }
 
-hipError_t qc_launch_mfma_F_jac(const QcParams& P, const double* dZ, double* dF, double* dJ, hipStream_t st) {
-    if (P.integrator == QC_EXPONENTIAL) return P.n > 16 ? qc_launch_mfma32_exp(P, dZ, dF, dJ, st) : qc_launch_mfma_exp(P, dZ, dF, dJ, st);
-    if (qc_mfma16_padeP_supported(P)) return qc_launch_mfma16_padeP(P, dZ, dF, dJ, st);
-    if (P.n > 32) return qc_launch_mfma64_F_jac(P, dZ, dF, dJ, st);
-    if (P.n > 16) {
-        // sparse drive generators: the row-gather kernel (qc_mfma32_ell.hip; QC_ELL_JAC=0: the dense-image kernel, for A/B runs);
-        static const bool ell_jac = !(getenv("QC_ELL_JAC") && atoi(getenv("QC_ELL_JAC")) == 0);
-        if (P.ell && ell_jac && P.n == 32 && P.nc == 16) return qc_launch_mfma32_ell_F_jac(P, dZ, dF, dJ, st);
-        return qc_launch_mfma32_F_jac(P, dZ, dF, dJ, st);
-    }
+hipError_t qc_launch_mfma16_F_jac(const QcParams& P, const double* dZ, double* dF, double* dJ, hipStream_t st) {
     const int n_wg = dJ ? (P.n_int + kIntervalsPerWG - 1) / kIntervalsPerWG : P.n_int;
     const int grid = n_wg < kMaxGrid ? n_wg : kMaxGrid;
     const bool diag = P.stamps != nullptr || P.dbg_skip != 0;

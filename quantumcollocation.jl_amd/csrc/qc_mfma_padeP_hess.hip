@@ -328,7 +328,7 @@ __global__ __launch_bounds__(kPHThreads, 4) void qc_mfma16_padeP_hess_kernel(con
 }  // namespace
 
 bool qc_mfma16_padeP_hess_supported(const QcParams& P) {
-    if (!(P.integrator == QC_PADE && P.p >= 1 && P.p <= QC_MAX_P && P.p != 2 && P.n <= 16 && P.nc <= 8 && P.m <= kPHMaxM && P.Gx != nullptr))
+    if (!(P.integrator == QC_PADE && P.p >= 1 && P.p <= QC_MAX_P && P.p != 2 && P.n <= 16 && P.nc <= 8 && P.m <= kPHMaxM))
         return false;
     return (size_t)ph_layout(P.p, P.m).total * sizeof(double) <= 160 * 1024;
 }

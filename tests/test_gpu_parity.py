@@ -526,7 +526,7 @@ def test_full_size_every_value_against_the_c_oracle(qc, cfg, align):
 @pytest.mark.parametrize("free_time", [True, False])
 def test_row_gather_forms_every_value_against_the_c_oracle(qc, m, free_time):
     """Pauli drives on three qubits (one entry per generator row), 1 .. 6 of them, more than one device round (T = 1100): mu_d2F alone and
-    the one-call launch take their row-gather forms (qc_mfma16_hess_gathers / qc_mfma16_fused_gathers: the 2-, 4- and 6-drive
+    the one-call launch take their row-gather forms (qc_plan.cpp: the 2-, 4- and 6-drive
     instantiations).  EVERY value against the C oracle, and the one call bit for bit against the two launches."""
     import torch
     import oracle.qc_oracle_c as oc
@@ -1156,7 +1156,7 @@ def test_fused_launch_is_bit_identical(qc, case):
         inp = qc.unitary_smooth_pulse_inputs(qc.QuantumSystem(herm(), [herm() for _ in range(m)]), qc.GATES["TOFFOLI"], 31)
     elif case.startswith("pauli"):
         # Pauli drives on three qubits (one entry per generator row), more than one device round: the one-call launch takes its
-        # row-gather form (qc_mfma16_fused_gathers) -- the 2-, 4- and 6-drive instantiations, free and fixed time steps
+        # row-gather form (QC_FUSED_PADE4_16_GATHER, qc_plan.cpp) -- the 2-, 4- and 6-drive instantiations, free and fixed time steps
         m = int(case[5])
         full = qc.multi_qubit_system(3)
         sysm = qc.QuantumSystem(full.H_drift, list(full.H_drives)[:m])
