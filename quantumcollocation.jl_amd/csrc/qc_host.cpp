@@ -417,6 +417,7 @@ int qc_blueprint_build(const qc_desc* d, qc_blueprint* B, std::string* err) {
         }
         P.antisym = anti && !sw.no_antisym ? 1 : 0;      // (QC_NO_ANTISYM=1, diagnostic: force the general path)
     }
+    P.head = sw.no_head ? 0 : 1;      // (QC_NO_HEAD=1, diagnostic: the run-time form of the 2N = 16 F + dF kernel)
     // Outputs are written once and never re-read by the kernel: non-temporal stores measured fastest on
     // MI355X (profiles/README.md: plain 14.4, sc1 12.8, nt 11.9 us per config-3 evaluation).
     P.store_mode = 2;

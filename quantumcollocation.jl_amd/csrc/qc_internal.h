@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <string>
@@ -33,6 +34,8 @@ struct QcParams {
     int dwin_lo, dwin_n;     // knot window [dwin_lo, dwin_lo + dwin_n) holding every x and dx of the derivative integrators, dwin_n even
                              // and <= 128 (one 16-byte-per-lane load per knot, 2N = 16 F + dF kernel); dwin_n = 0: no such window
                              // (more than QC_DWIN_MAX_DERIV integrators, one of more than 64 rows, or components too far apart)
+    int head;                // the 2N = 16 F + dF launch may take its HEAD instantiation (qc_mfma_kernels.hip); 0: QC_NO_HEAD=1 at create time
+                             // (this word was padding in front of t_begin: no other field moves)
     long long t_begin;       // first interval of this handle
     int n_int;               // number of intervals of this handle
     int jac_nnz, hess_nnz;   // per interval (own values; hess_nnz excludes the padding)
@@ -62,6 +65,8 @@ struct QcParams {
     const void* ell16;       // device: rows of the drive generators of a 2N = 16 handle whose drives have ONE entry per row (Pauli strings):
                              // [drive][16] weights (doubles), then [drive][16] columns x 17 (ints) -- qc_mfma_fused.hip; else nullptr
 };
+
+static_assert(offsetof(QcParams, head) + sizeof(int) == offsetof(QcParams, t_begin), "QcParams.head fills the padding in front of t_begin");
 
 // The host-side facts of a handle that kernel selection needs beside QcParams (which holds its tables as device pointers only):
 // everything qc_plan (qc_plan.h) reads is known before anything is allocated.

@@ -173,7 +173,11 @@ __device__ inline v4d lds_state_tile(const double* __restrict__ U, int col, int 
 // (Scalars and pointers only: a by-value struct is passed by reference and is not preloaded.)
 #define QC_HOT_ARGS(P) (P).Gx, dZ, (P).t_begin, (P).n_int, (P).zdim, (P).off_a, (P).off_dt, (P).m
 
-template <bool JAC, int MODE, bool DIAG, int kMU, bool KET, bool BATCH, bool ONCE = false>
+// HEAD: the loop-free unitary instantiation with everything its copy wave tests at run time known at compile time -- m = kMU drives,
+// all N copies, a free timestep, a derivative-integrator window, residuals wanted (launch16m decides; it asks for antisymmetric
+// generators as well, the case that was measured).  Between the arrival of the first load group and the first store stand then only
+// the assembly of G, the two products and the combines, without a branch.
+template <bool JAC, int MODE, bool DIAG, int kMU, bool KET, bool BATCH, bool ONCE = false, bool HEAD = false>
 __global__ __launch_bounds__(JAC ? kThreads : 64, 2) void qc_mfma16_pade4_kernel(const double* __restrict__ hot_Gx, const double* __restrict__ Z, long long hot_t_begin, int hot_n_int,
                                                                       int hot_zdim, int hot_off_a, int hot_off_dt, int hot_m, const QcParams Pk,
                                                                       double* __restrict__ F, double* __restrict__ J,
@@ -212,13 +216,14 @@ __global__ __launch_bounds__(JAC ? kThreads : 64, 2) void qc_mfma16_pade4_kernel
     double* __restrict__ sm = sm_all + (JAC ? slot * kLdsBlock : 0);
     const int ipw = JAC ? kIntervalsPerWG : 1;
     const int n_wg = (h_n_int + ipw - 1) / ipw;
-    const int m = BATCH ? P.m : hot_m;
+    static_assert(!HEAD || (JAC && ONCE && !KET && !BATCH), "HEAD is a form of the loop-free unitary F + dF instantiation");
+    const int m = HEAD ? kMU : BATCH ? P.m : hot_m;
     // KET = false: a unitary on N = 8 levels, every mask below folds away at compile time (as run-time tests they cost the
     // headline kernel 0.8 us per launch).  KET = true: the masked instantiation -- K <= 8 state columns (kets) and / or
     // N < 8 levels (2N = nr < 16 rows, zero-padded to the tile).
     const int nc = KET ? P.nc : 8;
     const int nr = KET ? P.n : 16;
-    const bool ft = h_off_dt >= 0;
+    const bool ft = HEAD || h_off_dt >= 0;
     const double c1 = P.c[1], c2 = P.c[2];
     const double* __restrict__ Gx = BATCH ? P.Gx : hot_Gx;
 
@@ -253,10 +258,11 @@ __global__ __launch_bounds__(JAC ? kThreads : 64, 2) void qc_mfma16_pade4_kernel
         const double av_pre = (JAC && role == 1) ? load_amp_lanes(z0, h_off_a, m, lane) : 0.0;
         const double h_pre = ft ? load_uniform(z0 + h_off_dt) : opaque_scalar(P.dt_fixed);
         double* __restrict__ Jb = JAC ? J + (size_t)b * P.J_stride + P.J_off : nullptr;
-        double* __restrict__ Fb = F ? F + (size_t)b * P.F_stride + P.F_off : nullptr;
+        double* __restrict__ Fb = (HEAD || F) ? F + (size_t)b * P.F_stride + P.F_off : nullptr;
         QC_STAMP_DECL;
 
-        if (JAC && role == 1) {
+        // (HEAD: the copy wave -- the only wave anything waits for -- is the fall-through behind the prologue)
+        if (HEAD ? __builtin_expect(role == 1, 1) : (JAC && role == 1)) {
             // ================= copy wave =====================================================================
             if (!active) { __syncthreads(); if constexpr (!ONCE) __syncthreads(); continue; }
             __builtin_amdgcn_s_setprio(3);   // critical path: nothing reaches HBM before this wave's first store
@@ -295,12 +301,28 @@ __global__ __launch_bounds__(JAC ? kThreads : 64, 2) void qc_mfma16_pade4_kernel
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 QC_STAMP(P, b, lane, 11);
             }
-            const v4d Ga = assemble_G_combine(P, Gx, lane, g0, gk, av, ak);
+            // HEAD, m = kMU: no test around a broadcast, no drive beyond the images in registers.  The run-time ladder also kept the four
+            // passed-on requests above in front of the wait for the first group.  Without it the scheduler issues them behind that wait,
+            // between the MFMAs of the second product, and the first group of every wave on the CU is back sooner: 8.14 - 8.22 us against
+            // 8.18 - 8.29 us with the four pinned right behind the wait and 8.37 - 8.40 us with them pinned in front of it as before
+            // (__builtin_amdgcn_sched_barrier; the parent 8.41 - 8.68 us on those boxes).  Store addresses formed ahead of the wait
+            // changed nothing (profiles/headline_path.txt).
+            v4d Ga;
+            if constexpr (HEAD) {
+                Ga = g0;
+#pragma unroll
+                for (int u = 0; u < kMU; ++u) Ga += bcast_lane(av, u) * gk[u];
+            } else {
+                Ga = assemble_G_combine(P, Gx, lane, g0, gk, av, ak);
+            }
             const double hc1 = h * c1, hc2 = h * h * c2;
             QC_STAMP(P, b, lane, 1);
             bool skip = false;
             if constexpr (DIAG) skip = (P.dbg_skip & 1) != 0;
             // A-layout(G^T) = B-layout(G) = Gb;  B-layout(G^T) = D-layout(G^T) = A-layout(G) = Ga.
+            // (For antisymmetric generators Gb = -Ga word for word as long as every amplitude is finite.  With an infinite one the identity
+            //  product turns whole rows into NaN where the sign flip keeps infinities, and the host-buffer path -- one copy of the blocks,
+            //  the run-time form -- must return the bits of the full copy: test_host_path_with_non_finite_inputs_and_the_sentinel_pattern.)
             const v4d Gb = mm16(Ga, IdB);
             const v4d G2T = mm16(Gb, Ga);
             v4d Fm, Bm;
@@ -346,7 +368,7 @@ __global__ __launch_bounds__(JAC ? kThreads : 64, 2) void qc_mfma16_pade4_kernel
                     if (u < m) lds_put(sm + kLdsGk + u * 256, lane, gk[u]);
             };
             if constexpr (kEarly > 0) {
-                if (!skip && P.copies >= kEarly) {
+                if (HEAD || (!skip && P.copies >= kEarly)) {
 #pragma unroll
                     for (int q = 0; q < kEarly; ++q) early_copy(q);
                     hand_off();
@@ -364,7 +386,7 @@ __global__ __launch_bounds__(JAC ? kThreads : 64, 2) void qc_mfma16_pade4_kernel
                 double* pB = Jb + P.jo_B;
                 // 8 bytes per lane, 512 contiguous bytes per instruction.  (Pairing lanes for 16-byte stores measured 8 % slower.)
                 // P.copies = N copies of each block (I_N (x) B); 1 when the host path asks for the compact form
-                const int ncop = P.copies;
+                const int ncop = HEAD ? 8 : P.copies;
                 for (int q = kEarly; q < ncop; ++q) {
                     if constexpr (!KET) {
                         store_tile_T<MODE>(pF + q * 256, Fm, g, j);
@@ -377,7 +399,7 @@ __global__ __launch_bounds__(JAC ? kThreads : 64, 2) void qc_mfma16_pade4_kernel
                 __builtin_amdgcn_s_setprio(0);
                 QC_STAMP(P, b, lane, 2);
                 {   // derivative integrator rows: residual x_{t+1} - x_t - h dx_t and the 4 (3) diagonal blocks
-                    if (P.dwin_n > 0) {   // from the windows in the hand-off block (<= kDF integrators of <= 64 rows)
+                    if (HEAD || P.dwin_n > 0) {   // from the windows in the hand-off block (<= kDF integrators of <= 64 rows)
                         const double* w0 = sm + kLdsD0 - P.dwin_lo;   // indexed by the offset in the knot
                         const double* w1 = sm + kLdsD1 - P.dwin_lo;
                         int jo = P.jo_d;
@@ -644,6 +666,14 @@ static void launch16m(const QcParams& P, const double* dZ, double* dF, double* d
         case 0: hipLaunchKernelGGL((qc_mfma16_pade4_kernel<JAC, 0, DIAG, MU, false, false>), dim3(grid), dim3(threads), 0, st, QC_HOT_ARGS(P), P, dF, dJ, nullptr); break;
         case 1: hipLaunchKernelGGL((qc_mfma16_pade4_kernel<JAC, 1, DIAG, MU, false, false>), dim3(grid), dim3(threads), 0, st, QC_HOT_ARGS(P), P, dF, dJ, nullptr); break;
         default:
+            if constexpr (JAC) {
+                // one interval per workgroup and nothing left to test at run time: the HEAD instantiation (QC_NO_HEAD=1 clears P.head;
+                // the stamped diagnostic build has one too, the ablations of QC_DEBUG_SKIP do not)
+                if (grid == n_wg && P.head && P.dbg_skip == 0 && P.m == MU && P.copies == 8 && P.copies >= QC_EARLY_COPIES && P.dwin_n > 0 && P.off_dt >= 0 && dF != nullptr && P.antisym) {
+                    hipLaunchKernelGGL((qc_mfma16_pade4_kernel<JAC, 2, DIAG, MU, false, false, true, true>), dim3(grid), dim3(threads), 0, st, QC_HOT_ARGS(P), P, dF, dJ, nullptr);
+                    break;
+                }
+            }
             if (grid == n_wg)   // one interval per workgroup: the loop-free instantiation (also for the stamped diagnostic build)
                 hipLaunchKernelGGL((qc_mfma16_pade4_kernel<JAC, 2, DIAG, MU, false, false, true>), dim3(grid), dim3(threads), 0, st, QC_HOT_ARGS(P), P, dF, dJ, nullptr);
             else

@@ -130,7 +130,7 @@ const QcSwitches& qc_switches() {
     return s;
 }
 
-QcCreateSwitches qc_create_switches() { return QcCreateSwitches{env_int("QC_NO_ELL", 0) != 0, env_int("QC_NO_ANTISYM", 0) != 0}; }
+QcCreateSwitches qc_create_switches() { return QcCreateSwitches{env_int("QC_NO_ELL", 0) != 0, env_int("QC_NO_ANTISYM", 0) != 0, env_int("QC_NO_HEAD", 0) != 0}; }
 
 bool qc_plan_mfma_serves(const QcParams& P) { return mfma_jac(P) >= 0; }
 

@@ -20,6 +20,7 @@ const QcSwitches& qc_switches();
 struct QcCreateSwitches {
     bool no_ell;           // QC_NO_ELL=1: no row-gather tables are built at all
     bool no_antisym;       // QC_NO_ANTISYM=1: the generators are treated as not antisymmetric
+    bool no_head;          // QC_NO_HEAD=1: the 2N = 16 F + dF launch never takes its HEAD instantiation (A/B runs, tests)
 };
 QcCreateSwitches qc_create_switches();
 
