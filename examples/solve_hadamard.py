@@ -30,7 +30,7 @@ def rollout_fidelity(qc, dyn, z, U_goal):
     return qc.iso_vec_unitary_fidelity(states[:, -1], qc.operator_to_iso_vec(U_goal))
 
 
-def solve(max_iter: int = 60, T: int = 50, verbose: bool = True, method: str = "SLSQP", _debug_hook=None):
+def solve(max_iter: int = 60, T: int = 50, verbose: bool = True, method: str = "SLSQP", _debug_hook=None, return_solution: bool = False):
     qc = g.load_package()
     inp = qc.config_inputs(1, T=T)   # geodesic + N(0, 1e-2) noise: exactly on the geodesic the loss |1 - F| sits on its kink
     traj, system = inp.traj, inp.system
@@ -118,6 +118,8 @@ def solve(max_iter: int = 60, T: int = 50, verbose: bool = True, method: str = "
     dyn.close()
     obj.close()
     reg.close()
+    if return_solution:      # the solved trajectory vector and its layout, for examples/robustness_landscape.py
+        return f_before, f_after, viol, res.x, traj, system
     return f_before, f_after, viol
 
 

@@ -50,6 +50,8 @@
  *       (unitary_robustness_problem.jl:46-49)
  *   unitary_rollout / rollout / open_rollout             qc_rollout / qc_rollout_dev
  *       (trajectory_initialization.jl:426,493,547)
+ *   unitary_rollout over systems(zeta)                   qc_sweep_create / qc_sweep_eval(_dev)
+ *       (unitary_sampling_problem.jl:233-243)
  *
  * Conventions
  *   - All matrices are column-major (Julia order).  All arrays are caller-owned; nothing is retained
@@ -562,6 +564,70 @@ int qc_robust_hess_structure(const qc_robust* h, int64_t* rows, int64_t* cols, i
 int qc_robust_eval(qc_robust* h, const double* Z, double* L, double* grad, double* hvals);
 /* device buffers, asynchronous on `stream` (no host synchronisation; scratch owned by the handle); dL / dgrad / dhvals may be NULL */
 int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad, double* dhvals, void* stream);
+
+/* ---- rollout sweeps: final states and fidelities over perturbed systems ------------------------------------------------ */
+/* One trajectory of controls, S systems that differ by a few parameters, one call: the loop of the reference's robustness check
+ * (unitary_sampling_problem.jl:204-244: `unitary_rollout(traj.a, timesteps, systems(zeta))[:, end]` and `iso_vec_unitary_fidelity`
+ * for every zeta of a grid; `UnitarySamplingProblem(system::Function, distribution, num_samples, ...)`, :186-200, draws its systems
+ * the same way).  Sample s is the base system plus n_pert additive perturbation generators, with a factor per drive:
+ *     G_s(a) = G_drift + sum_{j < n_pert} theta[s, j] P_j + sum_{k < m} c[s, k] a_k G_k
+ *     x_{t+1} = exp(dt_t G_s(a_t)) x_t,   t = 0 .. T-2,   x_0 = init (2N x cols, column-major)
+ * theta: S x n_pert, sample-major; c (`scale`): S x m, sample-major, or NULL = all ones.  The reference's systems(zeta) is
+ * G_drift = 0, P_0 = iso(-i Z), theta[s, 0] = zeta_s; a relative amplitude error eps on drive k is c[s, k] = 1 + eps.  The matrices
+ * are whatever the caller passes, as in qc_desc: iso generators of Hamiltonians, or Lindblad generators with N = levels^2
+ * (`open_rollout`).  The propagator is the matrix exponential, as in qc_rollout.  Only the controls and timesteps are read from Z.
+ * Kernels: 2N <= 16 with up to 8 drives runs on the f64 matrix cores, one wavefront per (sample, chunk of intervals)
+ * ("mfma16-sweep"); larger systems run the rollout kernels once per sample ("rollout-per-sample": correctness, not speed).
+ * Results do not depend on scheduling: repeated calls return the same bits.  Non-finite inputs are evaluated, not rejected.
+ * Out of scope: per-knot outputs, gradients, the free-phase fidelity, several devices. */
+#define QC_MAX_PERT 8
+#define QC_SWEEP_FID_NONE (-1)   /* qc_sweep_desc.fid_kind: final states only */
+typedef struct qc_sweep_desc {
+    int64_t T;
+    int32_t zdim;
+    int32_t off_a;               /* offset of the controls (m entries) inside a knot */
+    int32_t off_dt;              /* offset of the timestep inside a knot, -1: fixed */
+    int32_t N;                   /* iso dimension n = 2N */
+    double dt_fixed;
+    int64_t global_dim;
+    int32_t m;                   /* drives */
+    int32_t state_cols;          /* as qc_desc.state_cols: 0 or N = a unitary (2N x N); K >= 1 = K kets (2N x K) */
+    int32_t n_pert;              /* 0 .. QC_MAX_PERT */
+    int32_t fid_kind;            /* QC_SWEEP_FID_NONE | QC_FID_UNITARY | QC_FID_KET (state_cols = 1) | QC_FID_DENSITY (state_cols = 1, N = levels^2) */
+    const double* G_drift;       /* n x n, column-major */
+    const double* G_drives;      /* m matrices of n x n */
+    const double* G_pert;        /* n_pert matrices of n x n (NULL when n_pert = 0) */
+    int32_t fid_form;            /* QC_FID_FORM_* (unitary only) */
+    int32_t n_sub;
+    const double* goal_iso;      /* as qc_fidelity_desc.goal_iso */
+    const int32_t* subspace;     /* unitary only: 0-based levels, or NULL = all */
+    int32_t device;
+    int32_t reserved0;
+    int64_t reserved1[2];
+} qc_sweep_desc;
+typedef struct qc_sweep qc_sweep;
+int64_t qc_sizeof_sweep_desc(void);
+/* device-free: QC_ERR_INVALID with a message (qc_sweep_last_error(NULL)); QC_ERR_UNSUPPORTED for 2N > 64 */
+int qc_sweep_desc_validate(const qc_sweep_desc* d);
+/* device-free: the launch a handle of this descriptor takes for S samples -- mfma: 1 = "mfma16-sweep", 0 = "rollout-per-sample";
+ * chunk / n_chunks: intervals per wavefront and chunks per sample of the MFMA form (n_chunks = 1 once S alone fills the device,
+ * more for few samples; n_chunks = 0 for the per-sample form).  Outputs may be NULL. */
+int qc_sweep_desc_launch(const qc_sweep_desc* d, int64_t S, int32_t* mfma, int64_t* chunk, int64_t* n_chunks);
+int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out);
+void qc_sweep_destroy(qc_sweep* h);
+const char* qc_sweep_last_error(const qc_sweep* h);
+/* "mfma16-sweep" or "rollout-per-sample" (static strings; "none" for a NULL handle) */
+const char* qc_sweep_kernel_name(const qc_sweep* h);
+/* host buffers.  Z: the full trajectory vector (zdim T + global_dim); init: 2N x cols; theta: S x n_pert (NULL when n_pert = 0);
+ * scale: S x m or NULL; finals: S x (2N cols), sample-major; fids: S values.  Either output may be NULL, not both. */
+int qc_sweep_eval(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale, double* finals,
+                  double* fids);
+/* device buffers, asynchronous on `stream`, no host synchronisation -- except that scratch is owned by the handle and grown at the
+ * first call that needs it: a call with a larger S than any before frees and allocates device memory, which synchronises the device
+ * and cannot be captured in a graph (call once with the largest S first).  One evaluation in flight per handle.  The per-sample
+ * form issues its launches (about six per sample) from a host loop inside the call. */
+int qc_sweep_eval_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
+                      double* dfinals, double* dfids, void* stream);
 
 /* Diagnostic only: when the environment variable QC_STAMPS=1 is set at qc_create, the MFMA kernel
  * records 16 s_memrealtime (100 MHz) checkpoints per interval; this copies them out (synchronises the

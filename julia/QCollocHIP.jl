@@ -68,13 +68,23 @@ struct QCRobustDesc
     global_dim::Int64; n_knots::Int64; hessian::Int32; device::Int32; reserved1::NTuple{2,Int64}
 end
 
+# mirror of `qc_sweep_desc`
+struct QCSweepDesc
+    T::Int64; zdim::Int32; off_a::Int32; off_dt::Int32; N::Int32; dt_fixed::Float64; global_dim::Int64
+    m::Int32; state_cols::Int32; n_pert::Int32; fid_kind::Int32
+    G_drift::Ptr{Float64}; G_drives::Ptr{Float64}; G_pert::Ptr{Float64}
+    fid_form::Int32; n_sub::Int32; goal_iso::Ptr{Float64}; subspace::Ptr{Int32}
+    device::Int32; reserved0::Int32; reserved1::NTuple{2,Int64}
+end
+
 function __init__()
     # constants were renumbered between ABI 0.1 / 0.2 / 0.3 and retired in 0.4 (QC_REG_*): the struct sizes do not show that, the version does
     abi = ccall(dlsym(dlopen(LIB[]), :qc_abi_version), Int32, ())
     abi == QC_ABI_VERSION || error("QCollocHIP: $(LIB[]) has ABI version $abi, this binding mirrors $QC_ABI_VERSION")
     # a stale mirror would corrupt memory silently: compare with the structs the library was compiled with
     for (sym, T) in ((:qc_sizeof_desc, QCDesc), (:qc_sizeof_dims, QCDims), (:qc_sizeof_terms_desc, QCTermsDesc),
-                     (:qc_sizeof_robust_desc, QCRobustDesc), (:qc_sizeof_terms_ext, QCTermsExt))
+                     (:qc_sizeof_robust_desc, QCRobustDesc), (:qc_sizeof_terms_ext, QCTermsExt),
+                     (:qc_sizeof_sweep_desc, QCSweepDesc))
         lib = ccall(dlsym(dlopen(LIB[]), sym), Int64, ())
         lib == sizeof(T) || error("QCollocHIP: $(T) has $(sizeof(T)) bytes, $(LIB[]) expects $lib (header / binding version mismatch)")
     end
@@ -649,6 +659,50 @@ function unitary_rollout(dyn::HIPDynamics, Z⃗::AbstractVector{Float64}, init::
     GC.@preserve Z⃗ init out check(ccall((:qc_rollout, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
                                         dyn.handle, Z⃗, init, out), dyn.handle)
     return out
+end
+
+"""
+    rollout_sweep(init, controls, Δt, G_drift, G_drives, G_pert, θ; scale=nothing, cols, goal=nothing, fid_kind=-1,
+                  subspace=nothing, squared=false, device=0)  ->  (finals, fids)
+
+Final states and fidelities of ONE trajectory of controls under S perturbed systems, in one call (`qc_sweep_eval`): the loop of the
+reference's robustness check, `unitary_rollout(traj.a, timesteps, systems(ζ))[:, end]` and `iso_vec_unitary_fidelity` for every ζ
+(unitary_sampling_problem.jl:233-243).  Sample s evolves under G_drift + Σ_j θ[s, j] G_pert[j] + Σ_k scale[s, k] a_k G_drives[k]
+(2N×2N generators: `system.G_drift`, `system.G_drives`, and e.g. `G(Z)` for a detuning).  `controls` is m×T, `Δt` a vector of T
+timesteps, `θ` S×p, `scale` S×m or nothing; `fid_kind` -1 (none), 0 (unitary; `subspace` 1-based, `squared`), 1 (ket), 2 (density
+operator).  `finals` is (2N·cols)×S.  UNTESTED here, like the rest of this file.
+"""
+function rollout_sweep(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift, G_drives, G_pert,
+                       θ::AbstractMatrix{Float64}; scale=nothing, cols::Int, goal=nothing, fid_kind::Int=-1, subspace=nothing,
+                       squared::Bool=false, device::Int=0)
+    n = size(G_drift, 1); N = n ÷ 2
+    m, T = size(controls); p = length(G_pert); S = size(θ, 1)
+    G0 = Float64.(vec(G_drift))
+    Gd = m == 0 ? Float64[] : reduce(vcat, [Float64.(vec(G)) for G in G_drives])
+    Gp = p == 0 ? Float64[] : reduce(vcat, [Float64.(vec(G)) for G in G_pert])
+    sub = isnothing(subspace) ? Int32[] : Int32.(collect(subspace) .- 1)
+    g = isnothing(goal) ? Float64[] : Float64.(collect(goal))
+    Z⃗ = vec(vcat(controls, reshape(Δt, 1, T)))                      # knot layout [a; Δt]
+    θt = Matrix{Float64}(transpose(θ))                               # sample-major
+    ct = isnothing(scale) ? Float64[] : vec(Matrix{Float64}(transpose(scale)))
+    finals = Matrix{Float64}(undef, n * cols, S)
+    fids = fid_kind >= 0 ? Vector{Float64}(undef, S) : Float64[]
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve G0 Gd Gp sub g begin
+        desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
+                               pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
+                               squared ? 1 : 0, length(sub), isempty(g) ? C_NULL : pointer(g), isempty(sub) ? C_NULL : pointer(sub),
+                               device, 0, (0, 0)))
+        rc = ccall((:qc_sweep_create, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Ptr{Cvoid}}), desc, h)
+        rc == 0 || error("qc_sweep_create: " * unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
+    end
+    rc = GC.@preserve Z⃗ init θt ct finals fids ccall((:qc_sweep_eval, LIB[]), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        h[], Z⃗, init, S, p == 0 ? C_NULL : pointer(θt), isempty(ct) ? C_NULL : pointer(ct), finals, fid_kind >= 0 ? pointer(fids) : C_NULL)
+    msg = rc == 0 ? "" : unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), h[]))
+    ccall((:qc_sweep_destroy, LIB[]), Cvoid, (Ptr{Cvoid},), h[])
+    rc == 0 || error("qc_sweep_eval: " * msg)
+    return finals, fids
 end
 
 """

@@ -46,6 +46,8 @@ QC_REG_PLAIN = 3
 QC_ABI_VERSION = 6          # QC_VERSION_MAJOR * 1000 + QC_VERSION_MINOR of the include/qcolloc.h this file mirrors
 QC_FID_FORM_ABS, QC_FID_FORM_ABS2 = 0, 1
 QC_ROBUST_HESS_NONE, QC_ROBUST_HESS_EXACT = 0, 1
+QC_MAX_PERT = 8
+QC_SWEEP_FID_NONE = -1      # qc_sweep_desc.fid_kind: final states only
 QC_ROWS_STACKED = 0
 QC_ROWS_BY_COMPONENT = 1
 
@@ -181,6 +183,32 @@ class qc_robust_desc(C.Structure):
     ]
 
 
+class qc_sweep_desc(C.Structure):
+    _fields_ = [
+        ("T", C.c_int64),
+        ("zdim", C.c_int32),
+        ("off_a", C.c_int32),
+        ("off_dt", C.c_int32),
+        ("N", C.c_int32),
+        ("dt_fixed", C.c_double),
+        ("global_dim", C.c_int64),
+        ("m", C.c_int32),
+        ("state_cols", C.c_int32),
+        ("n_pert", C.c_int32),
+        ("fid_kind", C.c_int32),
+        ("G_drift", _c_double_p),
+        ("G_drives", _c_double_p),
+        ("G_pert", _c_double_p),
+        ("fid_form", C.c_int32),
+        ("n_sub", C.c_int32),
+        ("goal_iso", _c_double_p),
+        ("subspace", C.POINTER(C.c_int32)),
+        ("device", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("reserved1", C.c_int64 * 2),
+    ]
+
+
 # Every symbol include/qcolloc.h declares: (name, restype, argtypes).  tests/test_abi.py checks this
 # table against the header and against the built library.
 _DESC_P = C.POINTER(qc_desc)
@@ -189,6 +217,7 @@ _H = C.c_void_p
 _TDESC_P = C.POINTER(qc_terms_desc)
 _RDESC_P = C.POINTER(qc_robust_desc)
 _TEXT_P = C.POINTER(qc_terms_ext)
+_SDESC_P = C.POINTER(qc_sweep_desc)
 SYMBOLS = {
     "qc_operator_to_iso_vec": (C.c_int, [C.c_int32, _c_double_p, _c_double_p, _c_double_p]),
     "qc_iso_vec_to_operator": (C.c_int, [C.c_int32, _c_double_p, _c_double_p, _c_double_p]),
@@ -271,6 +300,15 @@ SYMBOLS = {
     "qc_robust_hess_structure": (C.c_int, [_H, _c_int64_p, _c_int64_p, C.c_int]),
     "qc_robust_eval": (C.c_int, [_H, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "qc_robust_eval_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qc_sizeof_sweep_desc": (C.c_int64, []),
+    "qc_sweep_desc_validate": (C.c_int, [_SDESC_P]),
+    "qc_sweep_desc_launch": (C.c_int, [_SDESC_P, C.c_int64, C.POINTER(C.c_int32), _c_int64_p, _c_int64_p]),
+    "qc_sweep_create": (C.c_int, [_SDESC_P, C.POINTER(_H)]),
+    "qc_sweep_destroy": (None, [_H]),
+    "qc_sweep_last_error": (C.c_char_p, [_H]),
+    "qc_sweep_kernel_name": (C.c_char_p, [_H]),
+    "qc_sweep_eval": (C.c_int, [_H, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "qc_sweep_eval_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qc_debug_read_stamps": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_int64]),
     "qc_debug_host_expand_rate": (C.c_int, [_H, C.c_int32, _c_double_p]),
     "qc_version": (C.c_char_p, []),
@@ -301,7 +339,8 @@ def _load() -> C.CDLL:
                           "(constants were renumbered between minor versions; stale build? run __graft_entry__.build())")
     # the struct mirrors above must be the structs this build of the library was compiled with
     for name, mirror in (("qc_sizeof_desc", qc_desc), ("qc_sizeof_dims", qc_dims_t), ("qc_sizeof_terms_desc", qc_terms_desc),
-                         ("qc_sizeof_robust_desc", qc_robust_desc), ("qc_sizeof_terms_ext", qc_terms_ext)):
+                         ("qc_sizeof_robust_desc", qc_robust_desc), ("qc_sizeof_terms_ext", qc_terms_ext),
+                         ("qc_sizeof_sweep_desc", qc_sweep_desc)):
         if getattr(lib, name)() != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: {name}() = {getattr(lib, name)()} but the Python mirror has {C.sizeof(mirror)} bytes "
                               "(stale build? run __graft_entry__.build())")

@@ -1,0 +1,608 @@
+// Rollout sweeps: ONE trajectory of controls, S systems that differ by a few parameters, S final states and S fidelities
+// (the reference's robustness check, unitary_sampling_problem.jl:204-244: `unitary_rollout(traj.a, timesteps, systems(zeta))[:, end]`
+// and `iso_vec_unitary_fidelity` for every zeta of a grid).  Sample s is
+//     G_s(a) = G_drift + sum_{j<p} theta[s,j] P_j + sum_{k<m} c[s,k] a_k G_k,      x_{t+1} = exp(dt_t G_s(a_t)) x_t,  x_0 = init.
+// The work is S (T-1) independent 2N x 2N exponentials and S ordered products.
+//
+// 2N <= 16, up to 8 drives ("mfma16-sweep"): one wavefront per (sample, chunk of consecutive intervals) on v_mfma_f64_16x16x4_f64, every
+// matrix one 16 x 16 tile in registers (lane maps: qc_mfma_kernels.hip header; sizes below 16 zero-padded -- the exponential of the
+// padded generator is the exponential of the true one plus an identity block).  Once per wave: the sample's base tile
+// G_drift + sum theta P_j and the m drive tiles, all in A layout; the sample's factors c[s,k] are folded into the control values.  Per
+// interval: Y = dt G_s(a_t) / 2^sq with ||Y||_1 <= 1/8 (wave-uniform sq), the degree-8 Taylor polynomial in Horner form
+// R_k = Y R_k+1 + I/(k-1)! (threshold, degree and truncation 4e-14 of qc_mfma_exp.hip, without its Frechet chains), sq squarings, and
+// W <- E_t W onto the running chunk product.  Squarings and the product need E as the LEFT factor; a D-layout tile read as the A
+// operand acts as its transpose (qc_mfma_exp.hip header), so E^T is made by an LDS transpose and used as the A operand -- an identity
+// for every matrix, antisymmetric generator or not (Lindblad generators are not).  MFMAs per interval: 8 x 4 + 4 sq + 4.
+// Nothing leaves registers / LDS until the chunk's total is done; the totals go to handle scratch, S x n_chunks tiles.
+// A second launch, one workgroup per sample, chains the totals onto init in ascending order, stores the final state and evaluates
+// the fidelity (definitions of qc_fidelity.hip).  No atomics, no order that depends on scheduling: repeated calls give the same bits.
+//
+// 16 < 2N <= 64, or more than 8 drives ("rollout-per-sample"): a small kernel writes the sample's generator set (perturbed drift,
+// scaled drives), the rollout kernels of qc_rollout.hip run on it, and the same final-state / fidelity launch follows.  Correctness,
+// not speed.
+#include <math.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "qc_mfma_common.h"
+
+namespace {
+
+using namespace qc_mfma;
+
+constexpr int kSDeg = 8;            // as qc_mfma_exp.hip: ||Y||_1 <= 1/8, degree 8, truncation (1/8)^9 / 9! = 4e-14
+constexpr double kSTh = 0.125;
+constexpr int kSMmax = 8;           // drive tiles a wave keeps in registers
+constexpr int kSWaves = 4;          // (sample, chunk) items per workgroup: one wave each, the waves never synchronise
+constexpr int kFinT = 256;          // threads of the final-state / fidelity workgroup
+constexpr long long kSweepFill = 2048;   // waves that give every SIMD a couple: 256 CUs x 4 SIMDs x 2
+
+// 1 / k!, k = 0 .. 8
+__constant__ const double kSInvFact[kSDeg + 1] = {1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0, 1.0 / 40320.0};
+
+struct SweepParams {
+    int n, nc, m, p, zdim, off_a, off_dt, n_int, chunk, n_chunks;
+    long long items;             // S * n_chunks
+    double dt_fixed;
+    const double* img;           // A-layout images [matrix][kk][lane]: drift, m drives, p perturbations
+};
+
+struct FinParams {
+    int n, ns, ld, n_chunks, fid_kind, fid_form, fid_n;
+    long long src_stride;        // 0: every sample starts from the same state (init); ns: per-sample states (per-sample form)
+};
+
+template <int CTRL>
+__device__ inline double sdpp(double x) {
+    int lo = __double2loint(x), hi = __double2hiint(x);
+    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+__device__ inline v4d simg(const double* __restrict__ img, int mat, int lane) {
+    const double* p = img + (size_t)mat * 256 + lane;
+    return v4d{p[0], p[64], p[128], p[192]};
+}
+
+// D = A B + C with one accumulator: the four MFMAs of a Horner step or a squaring
+__device__ __forceinline__ v4d mma16(const v4d& a, const v4d& b, v4d acc) {
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], b[kk], acc, 0, 0, 0);
+    return acc;
+}
+
+template <int M>
+__global__ __launch_bounds__(64 * kSWaves, 2) void qc_sweep_mfma16_kernel(const SweepParams P, const double* __restrict__ Z,
+                                                                           const double* __restrict__ theta, const double* __restrict__ scale,
+                                                                           double* __restrict__ tot) {
+    __shared__ double scr_all[kSWaves * 16 * 17];
+    const int lane = threadIdx.x & 63;
+    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double* __restrict__ scr = scr_all + wq * (16 * 17);
+    const long long item = (long long)blockIdx.x * kSWaves + wq;
+    if (item >= P.items) return;
+    const long long s = item / P.n_chunks;
+    const int c = (int)(item - s * P.n_chunks);
+    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
+    const int g = lane >> 4, j = lane & 15;
+    const int m = P.m;
+    const bool ft = P.off_dt >= 0;
+    const v4d IdB = identity_B(g, j);
+    const v4d zero = {0.0, 0.0, 0.0, 0.0};
+
+    // ---- once per wave: the sample's base tile and the drive tiles ---------------------------------------------------------
+    v4d base = simg(P.img, 0, lane);
+    for (int q = 0; q < P.p; ++q) {
+        const double th = theta[s * P.p + q];
+        const v4d Pq = simg(P.img, 1 + m + q, lane);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) base[r] = fma(th, Pq[r], base[r]);
+    }
+    v4d Gj[M];
+#pragma unroll
+    for (int u = 0; u < M; ++u) Gj[u] = u < m ? simg(P.img, 1 + u, lane) : zero;
+    // lane l holds the sample's factor of drive min(l, m-1); folded into the control values
+    const int kl = lane < m ? lane : (m > 0 ? m - 1 : 0);
+    const double cl = (scale && m > 0) ? scale[s * m + kl] : 1.0;
+
+    const double* __restrict__ z = Z + (long long)t0 * P.zdim;
+    double av = m > 0 ? z[P.off_a + kl] : 0.0;
+    const double hfix = opaque_scalar(P.dt_fixed);      // keeps the two arms apart: no flat load (qc_mfma_common.h)
+    double h = ft ? z[P.off_dt] : hfix;
+    v4d W = IdB;
+#pragma unroll 1
+    for (int t = t0; t < t1; ++t) {
+        // the next interval's controls and timestep are requested before this interval's products
+        const double* __restrict__ zn = Z + (long long)(t + 1 < t1 ? t + 1 : t) * P.zdim;
+        const double av_n = m > 0 ? zn[P.off_a + kl] : 0.0;
+        const double h_n = ft ? zn[P.off_dt] : hfix;
+        const double al = av * cl;
+        v4d Ga = base;
+#pragma unroll
+        for (int u = 0; u < M; ++u) {
+            const double a = u < m ? bcast_lane(al, u) : 0.0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Ga[r] = fma(a, Gj[u][r], Ga[r]);
+        }
+        // ||h G||_1 = largest column sum: lane (g, i) reg kk holds G[i][4kk+g]; rows of 16 lanes share a column
+        int sq = 0;
+        {
+            double best = 0.0;
+            bool bad = false;
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                double cs = fabs(h * Ga[kk]);
+                cs += sdpp<0x128>(cs);
+                cs += sdpp<0x124>(cs);
+                cs += sdpp<0x122>(cs);
+                cs += sdpp<0x121>(cs);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double v = bcast_lane(cs, 16 * r);
+                    if (!(v == v) || v > 1e300) bad = true;
+                    best = fmax(best, v);
+                }
+            }
+            if (!bad && best > kSTh) {
+                int e;
+                (void)frexp(best / kSTh, &e);
+                sq = e;
+                if (ldexp(kSTh, e - 1) >= best) sq = e - 1;
+                sq = sq < 0 ? 0 : (sq > 60 ? 60 : sq);
+            }
+            sq = __builtin_amdgcn_readfirstlane(sq);
+        }
+        const double sc = ldexp(1.0, -sq);
+        const v4d Y = (h * sc) * Ga;
+        // Horner: R_deg+1 = I/deg!,  R_k = Y R_k+1 + I/(k-1)!
+        // (the coefficients 1 / (k-1)! from a table of correctly rounded constants: the last one is exactly 1, so a zero generator gives
+        //  exactly the identity; computed in the loop they cost two f64 divisions a step)
+        v4d R = kSInvFact[kSDeg] * IdB;
+#pragma unroll 1
+        for (int k = kSDeg; k >= 1; --k)        // (unrolled, the eight scaled identities are hoisted out of the interval loop: 64 VGPRs)
+            R = mma16(Y, R, kSInvFact[k - 1] * IdB);
+        for (int q = 0; q < sq; ++q) {
+            const v4d Et = lds_transpose16(scr, R, g, j);
+            R = mma16(Et, R, zero);
+        }
+        const v4d Et = lds_transpose16(scr, R, g, j);     // E^T in D layout = E in A layout
+        W = mma16(Et, W, zero);
+        av = av_n;
+        h = h_n;
+    }
+    double* __restrict__ o = tot + item * 256;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) o[j * 16 + 4 * r + g] = W[r];
+}
+
+// The generator set of one sample for the rollout kernels: [G_drift + sum theta_j P_j | c_k G_k], column-major n x n each
+__global__ __launch_bounds__(256) void qc_sweep_gen_kernel(int n2, int m, int p, const double* __restrict__ G, const double* __restrict__ theta_s,
+                                                           const double* __restrict__ scale_s, double* __restrict__ out) {
+    const int total = (1 + m) * n2;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int mat = idx / n2, e = idx - mat * n2;
+        double v = G[idx];
+        if (mat == 0) {
+            for (int q = 0; q < p; ++q) v = fma(theta_s[q], G[(size_t)(1 + m + q) * n2 + e], v);
+        } else if (scale_s) {
+            v *= scale_s[mat - 1];
+        }
+        out[idx] = v;
+    }
+}
+
+// One workgroup per sample: x = Q_last ... Q_0 src (ascending order), final state, fidelity.
+// Fidelity from t = (g_r . x) + i (g_i . x):  unitary |t| / n or |t|^2 / n^2,  ket |t|^2,  density operator Re t  (qc_fidelity.hip).
+__global__ __launch_bounds__(kFinT) void qc_sweep_finish_kernel(const FinParams F, const double* __restrict__ tot, const double* __restrict__ src,
+                                                                const double* __restrict__ gr, const double* __restrict__ gi,
+                                                                double* __restrict__ finals, double* __restrict__ fids) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    __shared__ double red[2][kFinT / 64];
+    const int tid = threadIdx.x, n = F.n, ns = F.ns, ld = F.ld, l2 = ld * ld;
+    const long long s = blockIdx.x;
+    double* cur = sm;
+    double* nxt = sm + ns;
+    double* Q = sm + 2 * ns;
+    const double* __restrict__ x0 = src + s * F.src_stride;
+    for (int idx = tid; idx < ns; idx += kFinT) cur[idx] = x0[idx];
+    const double* __restrict__ Qs = tot + s * F.n_chunks * (long long)l2;
+    for (int c = 0; c < F.n_chunks; ++c) {
+        __syncthreads();
+        for (int idx = tid; idx < l2; idx += kFinT) Q[idx] = Qs[(long long)c * l2 + idx];
+        __syncthreads();
+        for (int idx = tid; idx < ns; idx += kFinT) {
+            const int r = idx % n, col = idx / n;
+            double acc = 0.0;
+            for (int q = 0; q < n; ++q) acc = fma(Q[r + ld * q], cur[q + n * col], acc);
+            nxt[idx] = acc;
+        }
+        double* tmp = cur; cur = nxt; nxt = tmp;
+    }
+    __syncthreads();
+    if (finals)
+        for (int idx = tid; idx < ns; idx += kFinT) finals[s * ns + idx] = cur[idx];
+    if (!fids) return;
+    double ar = 0.0, ai = 0.0;
+    for (int i = tid; i < ns; i += kFinT) {
+        const double xi = cur[i];
+        ar = fma(gr[i], xi, ar);
+        ai = fma(gi[i], xi, ai);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        ar += __shfl_xor(ar, off, 64);
+        ai += __shfl_xor(ai, off, 64);
+    }
+    if ((tid & 63) == 0) { red[0][tid >> 6] = ar; red[1][tid >> 6] = ai; }
+    __syncthreads();
+    if (tid == 0) {
+        const double tr = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        const double ti = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        const double nn = (double)F.fid_n;
+        double Fv;
+        if (F.fid_kind == QC_FID_UNITARY) Fv = F.fid_form == QC_FID_FORM_ABS2 ? (tr * tr + ti * ti) / (nn * nn) : sqrt(tr * tr + ti * ti) / nn;
+        else if (F.fid_kind == QC_FID_KET) Fv = tr * tr + ti * ti;
+        else Fv = tr;
+        fids[s] = Fv;
+    }
+}
+
+thread_local std::string g_swerr;
+
+}  // namespace
+
+struct qc_sweep {
+    qc_sweep_desc d;             // caller-owned arrays are not retained (pointers nulled)
+    int device = 0;
+    bool mfma = false;
+    int n = 0, nc = 0, ns = 0, fid_n = 0;
+    int64_t Zlen = 0;
+    double* dG = nullptr;        // (1 + m + p) matrices, column-major (per-sample form)
+    double* dImg = nullptr;      // their A-layout images (MFMA form)
+    double *dgr = nullptr, *dgi = nullptr;
+    // scratch of the "_dev" entry point, grown at the first call that needs it
+    double* dTot = nullptr;  size_t capTot = 0;
+    double* dFin = nullptr;  size_t capFin = 0;
+    double *dGs = nullptr, *dRE = nullptr, *dRQ = nullptr, *dRS = nullptr, *dRout = nullptr;
+    // staging of the host-buffer entry point
+    double *sZ = nullptr, *sInit = nullptr;
+    double* sTheta = nullptr;  size_t capTheta = 0;
+    double* sScale = nullptr;  size_t capScale = 0;
+    double* sFinals = nullptr; size_t capFinals = 0;
+    double* sFids = nullptr;   size_t capFids = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+};
+
+namespace {
+
+int sfail(qc_sweep* h, int code, const std::string& msg) {
+    if (h) h->err = msg;
+    g_swerr = msg;
+    return code;
+}
+
+int isqrt_exact(int v) {
+    int r = 0;
+    while ((r + 1) * (r + 1) <= v) ++r;
+    return r * r == v ? r : -1;
+}
+
+// The launch rule, in one place.  n_chunks = 1 once the samples alone give every SIMD a couple of waves; fewer samples split the
+// trajectory, up to ceil(sqrt(T-1)) chunks (beyond that the ordered chain of the second launch outweighs what the first gains).
+void sweep_chunks(int64_t S, int64_t T, int64_t* chunk, int64_t* n_chunks) {
+    const int64_t n_int = T - 1;
+    const int64_t want = S >= kSweepFill ? 1 : (kSweepFill + S - 1) / S;
+    int64_t r = 1;
+    while (r * r < n_int) ++r;
+    const int64_t nch = want < r ? want : r;
+    *chunk = (n_int + nch - 1) / nch;
+    *n_chunks = (n_int + *chunk - 1) / *chunk;
+}
+
+int sweep_validate(const qc_sweep_desc* d) {
+    if (!d) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: NULL descriptor");
+    if (d->N < 1) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: N must be >= 1");
+    if (d->m < 0) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: m must be >= 0");
+    if (d->T < 2) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: T must be >= 2");
+    if (d->T > (1ll << 30)) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: T too large");
+    if (d->zdim < 1 || d->global_dim < 0) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: bad zdim / global_dim");
+    if (d->off_a < 0 || (int64_t)d->off_a + d->m > d->zdim) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: off_a outside the knot (m entries from off_a must fit inside zdim)");
+    if (d->off_dt < -1 || d->off_dt >= d->zdim) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: off_dt outside the knot");
+    if (d->n_pert < 0 || d->n_pert > QC_MAX_PERT) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: n_pert must be in 0 .. QC_MAX_PERT (8)");
+    if (d->n_pert > 0 && !d->G_pert) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: n_pert > 0 but G_pert is NULL");
+    if (!d->G_drift) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: G_drift is NULL");
+    if (d->m > 0 && !d->G_drives) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: m > 0 but G_drives is NULL");
+    if (d->state_cols < 0) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: state_cols must be >= 0");
+    const int nc = d->state_cols == 0 ? d->N : d->state_cols;
+    if (d->fid_kind != QC_SWEEP_FID_NONE) {
+        if (d->fid_kind != QC_FID_UNITARY && d->fid_kind != QC_FID_KET && d->fid_kind != QC_FID_DENSITY)
+            return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: unknown fid_kind");
+        if (d->fid_form != QC_FID_FORM_ABS && d->fid_form != QC_FID_FORM_ABS2) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: unknown fid_form");
+        if (!d->goal_iso) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: a fidelity needs goal_iso");
+        if (d->fid_kind == QC_FID_UNITARY) {
+            if (nc != d->N) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: the unitary fidelity needs state_cols = 0 or N");
+            if (d->subspace) {
+                if (d->n_sub < 1 || d->n_sub > d->N) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: n_sub must be in 1 .. N");
+                for (int a = 0; a < d->n_sub; ++a) {
+                    if (d->subspace[a] < 0 || d->subspace[a] >= d->N) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: subspace index outside 0 .. N-1");
+                    for (int b = 0; b < a; ++b)
+                        if (d->subspace[b] == d->subspace[a]) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: subspace levels must be distinct");
+                }
+            }
+        } else {
+            if (d->subspace || d->fid_form != QC_FID_FORM_ABS)
+                return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: subspace and fid_form apply to QC_FID_UNITARY only");
+            if (nc != 1) return sfail(nullptr, QC_ERR_INVALID, d->fid_kind == QC_FID_KET ? "qc_sweep: the ket fidelity needs state_cols = 1"
+                                                                                             : "qc_sweep: the density-operator fidelity needs state_cols = 1");
+            if (d->fid_kind == QC_FID_DENSITY && isqrt_exact(d->N) < 0)
+                return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: the density-operator fidelity needs N = levels^2");
+        }
+    }
+    if (2 * (int64_t)d->N > 64) return sfail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: 2N = " + std::to_string(2 * (int64_t)d->N) + " exceeds the supported 2N <= 64");
+    if (2 * (int64_t)d->N * nc > 4096) return sfail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: states of more than 4096 entries (2N x state_cols) are not supported");
+    if (d->m > 64) return sfail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: more than 64 drives are not supported");
+    return QC_OK;
+}
+
+bool sweep_is_mfma(const qc_sweep_desc* d) { return 2 * d->N <= 16 && d->m <= kSMmax; }
+
+template <class T>
+hipError_t grow(T** p, size_t* cap, size_t need) {
+    if (need <= *cap) return hipSuccess;
+    if (*p) {
+        hipError_t e = hipFree(*p);
+        *p = nullptr;
+        *cap = 0;
+        if (e != hipSuccess) return e;
+    }
+    hipError_t e = hipMalloc((void**)p, need * sizeof(T));
+    if (e == hipSuccess) *cap = need;
+    return e;
+}
+
+}  // namespace
+
+#define QCS_HIP(h, call)                                                                              \
+    do {                                                                                              \
+        hipError_t e_ = (call);                                                                       \
+        if (e_ != hipSuccess) return sfail(h, QC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+extern "C" const char* qc_sweep_last_error(const qc_sweep* h) { return h ? h->err.c_str() : g_swerr.c_str(); }
+
+extern "C" int64_t qc_sizeof_sweep_desc(void) { return (int64_t)sizeof(qc_sweep_desc); }
+
+extern "C" int qc_sweep_desc_validate(const qc_sweep_desc* d) { return sweep_validate(d); }
+
+extern "C" int qc_sweep_desc_launch(const qc_sweep_desc* d, int64_t S, int32_t* mfma, int64_t* chunk, int64_t* n_chunks) {
+    int rc = sweep_validate(d);
+    if (rc) return rc;
+    if (S < 1) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep_desc_launch: S must be >= 1");
+    const bool mf = sweep_is_mfma(d);
+    int64_t ch = d->T - 1, nch = 0;      // per-sample form: the rollout kernels' own scan, no totals
+    if (mf) sweep_chunks(S, d->T, &ch, &nch);
+    if (mfma) *mfma = mf ? 1 : 0;
+    if (chunk) *chunk = ch;
+    if (n_chunks) *n_chunks = nch;
+    return QC_OK;
+}
+
+extern "C" const char* qc_sweep_kernel_name(const qc_sweep* h) {
+    if (!h) return "none";
+    return h->mfma ? "mfma16-sweep" : "rollout-per-sample";
+}
+
+extern "C" void qc_sweep_destroy(qc_sweep* h) {
+    if (!h) return;
+    qc_device_guard guard(h->device);
+    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
+    for (double* p : {h->dG, h->dImg, h->dgr, h->dgi, h->dTot, h->dFin, h->dGs, h->dRE, h->dRQ, h->dRS, h->dRout, h->sZ, h->sInit, h->sTheta, h->sScale,
+                      h->sFinals, h->sFids})
+        if (p) (void)hipFree(p);
+    delete h;
+}
+
+extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
+    if (!out) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep_create: out is NULL");
+    *out = nullptr;
+    int rc = sweep_validate(d);
+    if (rc) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sfail(nullptr, QC_ERR_NO_DEVICE, "qc_sweep_create: no HIP device visible");
+    if (d->device < 0 || d->device >= ndev) return sfail(nullptr, QC_ERR_NO_DEVICE, "qc_sweep_create: device ordinal out of range");
+    qc_sweep* h = new qc_sweep();
+    h->d = *d;
+    h->device = d->device;
+    h->mfma = sweep_is_mfma(d);
+    const int N = d->N, n = 2 * N, n2 = n * n, m = d->m, p = d->n_pert;
+    h->n = n;
+    h->nc = d->state_cols == 0 ? N : d->state_cols;
+    h->ns = n * h->nc;
+    h->Zlen = d->T * (int64_t)d->zdim + d->global_dim;
+    // generators: drift, drives, perturbations
+    const int nm = 1 + m + p;
+    std::vector<double> G((size_t)nm * n2);
+    memcpy(G.data(), d->G_drift, (size_t)n2 * 8);
+    if (m) memcpy(G.data() + n2, d->G_drives, (size_t)m * n2 * 8);
+    if (p) memcpy(G.data() + (size_t)(1 + m) * n2, d->G_pert, (size_t)p * n2 * 8);
+    std::vector<double> img;
+    if (h->mfma) {   // A layout: lane (g, i) reg kk holds G[i][4 kk + g], zero outside n x n
+        img.assign((size_t)nm * 256, 0.0);
+        for (int mat = 0; mat < nm; ++mat)
+            for (int kk = 0; kk < 4; ++kk)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int g = lane >> 4, i = lane & 15, col = 4 * kk + g;
+                    if (i < n && col < n) img[(size_t)mat * 256 + kk * 64 + lane] = G[(size_t)mat * n2 + (size_t)col * n + i];
+                }
+    }
+    // fidelity: the constant vectors g_r, g_i of qc_fidelity.hip
+    std::vector<double> gr, gi;
+    if (d->fid_kind != QC_SWEEP_FID_NONE) {
+        gr.assign(h->ns, 0.0);
+        gi.assign(h->ns, 0.0);
+        if (d->fid_kind == QC_FID_UNITARY) {
+            std::vector<int> sub;
+            if (d->subspace) sub.assign(d->subspace, d->subspace + d->n_sub);
+            else for (int k = 0; k < N; ++k) sub.push_back(k);
+            h->fid_n = (int)sub.size();
+            for (int jc : sub)
+                for (int i : sub) {
+                    const int re = jc * 2 * N + i, im = re + N;
+                    const double Gre = d->goal_iso[re], Gim = d->goal_iso[im];
+                    gr[re] = Gre;  gr[im] = Gim;
+                    gi[re] = -Gim; gi[im] = Gre;
+                }
+        } else if (d->fid_kind == QC_FID_KET) {
+            h->fid_n = 1;
+            for (int i = 0; i < N; ++i) {
+                gr[i] = d->goal_iso[i];      gr[N + i] = d->goal_iso[N + i];
+                gi[i] = -d->goal_iso[N + i]; gi[N + i] = d->goal_iso[i];
+            }
+        } else {
+            h->fid_n = 1;
+            const int L = isqrt_exact(N);
+            const double* gre = d->goal_iso;
+            const double* gim = d->goal_iso + L;
+            for (int jc = 0; jc < L; ++jc)
+                for (int i = 0; i < L; ++i) {
+                    gr[jc * L + i] = gre[i] * gre[jc] + gim[i] * gim[jc];
+                    gr[L * L + jc * L + i] = gim[i] * gre[jc] - gre[i] * gim[jc];
+                }
+        }
+    }
+    h->d.G_drift = h->d.G_drives = h->d.G_pert = h->d.goal_iso = nullptr;
+    h->d.subspace = nullptr;
+    auto bail = [&](hipError_t e, const char* what) {
+        std::string msg = std::string(what) + ": " + hipGetErrorString(e);
+        qc_sweep_destroy(h);
+        return sfail(nullptr, QC_ERR_HIP, msg);
+    };
+    qc_device_guard guard(d->device);
+    if (guard.err != hipSuccess) return bail(guard.err, "hipSetDevice");
+    auto up = [&](double** dst, const double* src, size_t count) {
+        hipError_t x = hipMalloc((void**)dst, count * 8);
+        if (x == hipSuccess && src) x = hipMemcpy(*dst, src, count * 8, hipMemcpyHostToDevice);
+        return x;
+    };
+    hipError_t e;
+    if (h->mfma) {
+        if ((e = up(&h->dImg, img.data(), img.size())) != hipSuccess) return bail(e, "hipMalloc / hipMemcpy");
+    } else {
+        const size_t T = (size_t)d->T;
+        QcParams P{};
+        P.n = n; P.nc = h->nc;
+        size_t nE, nQ, nS;
+        int ch, nch;
+        qc_rollout_scratch(P, (long long)T, &nE, &nQ, &nS, &ch, &nch);
+        if ((e = up(&h->dG, G.data(), G.size())) != hipSuccess) return bail(e, "hipMalloc / hipMemcpy");
+        if ((e = up(&h->dGs, nullptr, (size_t)(1 + m) * n2)) != hipSuccess) return bail(e, "hipMalloc");
+        if ((e = up(&h->dRE, nullptr, nE)) != hipSuccess) return bail(e, "hipMalloc");
+        if ((e = up(&h->dRQ, nullptr, nQ)) != hipSuccess) return bail(e, "hipMalloc");
+        if ((e = up(&h->dRS, nullptr, nS)) != hipSuccess) return bail(e, "hipMalloc");
+        if ((e = up(&h->dRout, nullptr, (size_t)h->ns * T)) != hipSuccess) return bail(e, "hipMalloc");
+    }
+    if (!gr.empty()) {
+        if ((e = up(&h->dgr, gr.data(), gr.size())) != hipSuccess) return bail(e, "hipMalloc / hipMemcpy");
+        if ((e = up(&h->dgi, gi.data(), gi.size())) != hipSuccess) return bail(e, "hipMalloc / hipMemcpy");
+    }
+    if ((e = up(&h->sZ, nullptr, (size_t)h->Zlen)) != hipSuccess) return bail(e, "hipMalloc");
+    if ((e = up(&h->sInit, nullptr, (size_t)h->ns)) != hipSuccess) return bail(e, "hipMalloc");
+    if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
+    *out = h;
+    return QC_OK;
+}
+
+extern "C" int qc_sweep_eval_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
+                                 double* dfinals, double* dfids, void* stream) {
+    if (!h) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep_eval_dev: NULL handle");
+    if (!dZ || !dinit) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval_dev: NULL input");
+    if (S < 1 || S > (1ll << 24)) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval_dev: S must be in 1 .. 2^24");
+    if (h->d.n_pert > 0 && !dtheta) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval_dev: theta is NULL but the handle has perturbations");
+    if (!dfinals && !dfids) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval_dev: finals and fids are both NULL");
+    if (dfids && h->d.fid_kind == QC_SWEEP_FID_NONE) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval_dev: fidelities requested from a handle created without one");
+    qc_device_guard guard(h->device);
+    if (guard.err != hipSuccess) return sfail(h, QC_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(guard.err));
+    hipStream_t st = (hipStream_t)stream;
+    const int n = h->n, m = h->d.m, p = h->d.n_pert;
+    FinParams F;
+    F.n = n; F.ns = h->ns;
+    F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;
+    const double* src;
+    if (h->mfma) {
+        int64_t chunk, n_chunks;
+        sweep_chunks(S, h->d.T, &chunk, &n_chunks);
+        QCS_HIP(h, grow(&h->dTot, &h->capTot, (size_t)S * n_chunks * 256));
+        SweepParams P;
+        P.n = n; P.nc = h->nc; P.m = m; P.p = p; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
+        P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks;
+        P.items = S * n_chunks;
+        P.dt_fixed = h->d.dt_fixed;
+        P.img = h->dImg;
+        const unsigned grid = (unsigned)((P.items + kSWaves - 1) / kSWaves);
+#define QC_SWEEP_LAUNCH(M_) hipLaunchKernelGGL(qc_sweep_mfma16_kernel<M_>, dim3(grid), dim3(64 * kSWaves), 0, st, P, dZ, dtheta, dscale, h->dTot)
+        if (m <= 1) QC_SWEEP_LAUNCH(1);
+        else if (m <= 2) QC_SWEEP_LAUNCH(2);
+        else if (m <= 4) QC_SWEEP_LAUNCH(4);
+        else if (m <= 6) QC_SWEEP_LAUNCH(6);
+        else QC_SWEEP_LAUNCH(8);
+#undef QC_SWEEP_LAUNCH
+        F.ld = 16; F.n_chunks = (int)n_chunks; F.src_stride = 0;
+        src = dinit;
+    } else {
+        QCS_HIP(h, grow(&h->dFin, &h->capFin, (size_t)S * h->ns));
+        QcParams P{};
+        P.N = h->d.N; P.n = n; P.nc = h->nc; P.s = h->ns; P.m = m; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
+        P.dt_fixed = h->d.dt_fixed; P.G = h->dGs;
+        const int n2 = n * n, gen_grid = ((1 + m) * n2 + 255) / 256;
+        const size_t last = (size_t)(h->d.T - 1) * h->ns;
+        for (int64_t s = 0; s < S; ++s) {
+            hipLaunchKernelGGL(qc_sweep_gen_kernel, dim3(gen_grid), dim3(256), 0, st, n2, m, p, (const double*)h->dG, p ? dtheta + s * p : nullptr,
+                               (dscale && m) ? dscale + s * m : nullptr, h->dGs);
+            QCS_HIP(h, qc_launch_rollout(P, h->d.T, dZ, dinit, h->dRout, h->dRE, h->dRQ, h->dRS, st));
+            QCS_HIP(h, hipMemcpyAsync(h->dFin + (size_t)s * h->ns, h->dRout + last, (size_t)h->ns * 8, hipMemcpyDeviceToDevice, st));
+        }
+        F.ld = n; F.n_chunks = 0; F.src_stride = h->ns;
+        src = h->dFin;
+    }
+    const size_t lds = ((size_t)2 * h->ns + (size_t)F.ld * F.ld) * 8;
+    if (lds > 64 * 1024)
+        QCS_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(qc_sweep_finish_kernel, dim3((unsigned)S), dim3(kFinT), lds, st, F, (const double*)h->dTot, src, (const double*)h->dgr,
+                       (const double*)h->dgi, dfinals, dfids);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return sfail(h, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return QC_OK;
+}
+
+extern "C" int qc_sweep_eval(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale, double* finals,
+                             double* fids) {
+    if (!h) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep_eval: NULL handle");
+    if (!Z || !init) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval: NULL input");
+    if (S < 1 || S > (1ll << 24)) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval: S must be in 1 .. 2^24");
+    const int m = h->d.m, p = h->d.n_pert;
+    if (p > 0 && !theta) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval: theta is NULL but the handle has perturbations");
+    if (!finals && !fids) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval: finals and fids are both NULL");
+    if (fids && h->d.fid_kind == QC_SWEEP_FID_NONE) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval: fidelities requested from a handle created without one");
+    qc_device_guard guard(h->device);
+    if (guard.err != hipSuccess) return sfail(h, QC_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(guard.err));
+    const bool use_scale = scale && m > 0;
+    if (p) QCS_HIP(h, grow(&h->sTheta, &h->capTheta, (size_t)S * p));
+    if (use_scale) QCS_HIP(h, grow(&h->sScale, &h->capScale, (size_t)S * m));
+    if (finals) QCS_HIP(h, grow(&h->sFinals, &h->capFinals, (size_t)S * h->ns));
+    if (fids) QCS_HIP(h, grow(&h->sFids, &h->capFids, (size_t)S));
+    QCS_HIP(h, hipMemcpyAsync(h->sZ, Z, (size_t)h->Zlen * 8, hipMemcpyHostToDevice, h->stream));
+    QCS_HIP(h, hipMemcpyAsync(h->sInit, init, (size_t)h->ns * 8, hipMemcpyHostToDevice, h->stream));
+    if (p) QCS_HIP(h, hipMemcpyAsync(h->sTheta, theta, (size_t)S * p * 8, hipMemcpyHostToDevice, h->stream));
+    if (use_scale) QCS_HIP(h, hipMemcpyAsync(h->sScale, scale, (size_t)S * m * 8, hipMemcpyHostToDevice, h->stream));
+    int rc = qc_sweep_eval_dev(h, h->sZ, h->sInit, S, p ? h->sTheta : nullptr, use_scale ? h->sScale : nullptr, finals ? h->sFinals : nullptr,
+                               fids ? h->sFids : nullptr, h->stream);
+    if (rc) return rc;
+    if (finals) QCS_HIP(h, hipMemcpyAsync(finals, h->sFinals, (size_t)S * h->ns * 8, hipMemcpyDeviceToHost, h->stream));
+    if (fids) QCS_HIP(h, hipMemcpyAsync(fids, h->sFids, (size_t)S * 8, hipMemcpyDeviceToHost, h->stream));
+    QCS_HIP(h, hipStreamSynchronize(h->stream));
+    return QC_OK;
+}

@@ -7,6 +7,15 @@
 
 x_{t+1} = exp(Δt_t G(a_t)) x_t; the result has one column per knot.  The functions taking raw controls build a
 minimal trajectory layout [state, a, Δt] for the descriptor; `QuantumDynamics.rollout` reuses an existing handle.
+
+Sweeps through `qc_sweep_*`: one trajectory of controls, S perturbed systems, S final states and fidelities in one call --
+the loop of the reference's robustness check, `unitary_rollout(traj.a, timesteps, systems(ζ))[:, end]` and
+`iso_vec_unitary_fidelity` for every ζ of a grid (unitary_sampling_problem.jl:204-244):
+
+    rollout_sweep(init, controls, Δt, system, perturbations, θ, scale)     (finals, fids)
+    unitary_rollout_fidelity_sweep(traj, system, perturbations, θ)         S fidelities of the rolled-out unitary
+    rollout_fidelity_sweep(traj, system, perturbations, θ; state_name)     ... of a ket
+    RolloutSweep                                                            the handle, for callers that sweep repeatedly
 """
 from __future__ import annotations
 
@@ -14,6 +23,7 @@ import ctypes as C
 from typing import Optional, Sequence
 
 import numpy as np
+import torch
 
 from . import _lib
 from .isomorphisms import operator_to_iso_vec
@@ -96,3 +106,227 @@ def rollout_fidelity(traj: NamedTrajectory, system, state_name: str = "ψ̃", co
     dts = traj[traj.timestep].ravel() if isinstance(traj.timestep, str) else float(traj.timestep)
     psi = rollout(np.ascontiguousarray(init, dtype=np.float64), traj[control_name], dts, system, device)
     return iso_fidelity(psi[:, -1], np.asarray(traj.goal[state_name], dtype=np.float64), device)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+#  Rollout sweeps over perturbed systems through `qc_sweep_*`
+# ---------------------------------------------------------------------------------------------------------------
+_FID_KINDS = {None: _lib.QC_SWEEP_FID_NONE, "none": _lib.QC_SWEEP_FID_NONE, "unitary": _lib.QC_FID_UNITARY, "ket": _lib.QC_FID_KET,
+              "density": _lib.QC_FID_DENSITY}
+
+
+def _sweep_generators(system, perturbations) -> list:
+    """Perturbation generators (2N x 2N): Hermitian operators of a `QuantumSystem` go through `iso_generator`, as its
+    Hamiltonians do; an `OpenQuantumSystem` takes generator matrices as they are."""
+    from .isomorphisms import iso_generator
+    from .quantum_systems import OpenQuantumSystem
+    n = 2 * system.state_levels
+    out = []
+    for P in perturbations:
+        P = np.asarray(P)
+        G = np.asarray(P, dtype=np.float64) if isinstance(system, OpenQuantumSystem) else iso_generator(np.asarray(P, dtype=complex))
+        if G.shape != (n, n):
+            raise ValueError(f"perturbation has generator shape {G.shape}, expected ({n}, {n})")
+        out.append(G)
+    return out
+
+
+class RolloutSweep:
+    """S rollouts of one trajectory of controls under S perturbed systems, final states and fidelities only:
+
+        G_s(a) = G_drift + sum_j theta[s, j] P_j + sum_k scale[s, k] a_k G_k,     x_{t+1} = exp(dt_t G_s(a_t)) x_t
+
+    system         `QuantumSystem` or `OpenQuantumSystem`
+    perturbations  Hermitian operators (QuantumSystem) or generator matrices (OpenQuantumSystem), at most 8
+    T              knots
+    cols           columns of the state: system.levels for a unitary, K for K kets, 1 for a density operator (default: unitary)
+    goal, fid_kind fidelity of every final state: "unitary" (goal = iso-vec of U_goal; `subspace`, `fid_form`), "ket" or
+                   "density" (goal = [Re psi; Im psi]); None: final states only
+    The trajectory vector is knot-major with the controls at `off_a` and the timestep at `off_dt` of every knot of `zdim`
+    entries (default: the minimal layout [a, dt], built by `pack`; dt_fixed: no timestep in the knot)."""
+
+    def __init__(self, system, perturbations, T: int, cols: Optional[int] = None, goal=None, fid_kind=None, subspace=None,
+                 fid_form: int = _lib.QC_FID_FORM_ABS, zdim: Optional[int] = None, off_a: int = 0, off_dt: Optional[int] = None,
+                 dt_fixed: Optional[float] = None, global_dim: int = 0, device: int = 0):
+        self._h = None
+        m = system.n_drives
+        N = system.state_levels
+        n = 2 * N
+        gens = _sweep_generators(system, perturbations)
+        if zdim is None:
+            zdim, off_a, off_dt = (max(m, 1), 0, -1) if dt_fixed is not None else (m + 1, 0, m)
+        elif off_dt is None:
+            off_dt = -1
+        self.N, self.n, self.m, self.T, self.p = N, n, m, int(T), len(gens)
+        self.cols = system.levels if cols is None else int(cols)
+        self.ns = n * self.cols
+        self.zdim, self.off_a, self.off_dt, self.global_dim = int(zdim), int(off_a), int(off_dt), int(global_dim)
+        self.Z_len = self.T * self.zdim + self.global_dim
+        self.fid_kind = _FID_KINDS[fid_kind] if (fid_kind is None or isinstance(fid_kind, str)) else int(fid_kind)
+        flat = lambda Gs: np.ascontiguousarray(np.stack([np.asarray(G, dtype=np.float64).reshape(-1, order="F") for G in Gs]))
+        self._G0 = np.ascontiguousarray(np.asarray(system.G_drift, dtype=np.float64).reshape(-1, order="F"))
+        self._Gd = flat(system.G_drives) if m else None
+        self._Gp = flat(gens) if gens else None
+        self._goal = None if goal is None else np.ascontiguousarray(goal, dtype=np.float64).ravel()
+        self._sub = None if subspace is None else np.ascontiguousarray(subspace, dtype=np.int32)
+        d = _lib.qc_sweep_desc()
+        d.T, d.zdim, d.off_a, d.off_dt, d.N = self.T, self.zdim, self.off_a, self.off_dt, N
+        d.dt_fixed = 0.0 if dt_fixed is None else float(dt_fixed)
+        d.global_dim, d.m, d.n_pert = self.global_dim, m, self.p
+        d.state_cols = 0 if self.cols == N else self.cols
+        d.fid_kind, d.fid_form = self.fid_kind, int(fid_form)
+        d.G_drift = _lib.dptr(self._G0)
+        d.G_drives = _lib.dptr(self._Gd) if m else None
+        d.G_pert = _lib.dptr(self._Gp) if gens else None
+        d.goal_iso = _lib.dptr(self._goal) if self._goal is not None else None
+        d.subspace = self._sub.ctypes.data_as(C.POINTER(C.c_int32)) if self._sub is not None else None
+        d.n_sub = 0 if self._sub is None else int(self._sub.size)
+        d.device = device
+        self._desc = d
+        h = C.c_void_p()
+        rc = _lib.lib.qc_sweep_create(C.byref(d), C.byref(h))
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(None).decode())
+        self._h = h
+
+    @property
+    def kernel_name(self) -> str:
+        """"mfma16-sweep" (2N <= 16, up to 8 drives) or "rollout-per-sample"."""
+        return _lib.lib.qc_sweep_kernel_name(self._h).decode()
+
+    def launch(self, S: int):
+        """(mfma, chunk, n_chunks) of a call with S samples: `qc_sweep_desc_launch`."""
+        mf, ch, nch = C.c_int32(), C.c_int64(), C.c_int64()
+        rc = _lib.lib.qc_sweep_desc_launch(C.byref(self._desc), int(S), C.byref(mf), C.byref(ch), C.byref(nch))
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(None).decode())
+        return bool(mf.value), ch.value, nch.value
+
+    def pack(self, controls, dts=None) -> np.ndarray:
+        """The trajectory vector of this handle's layout from controls (m x T) and timesteps (scalar or one per knot)."""
+        controls = np.asarray(controls, dtype=np.float64).reshape(self.m, -1)
+        if controls.shape[1] != self.T:
+            raise ValueError(f"controls must be {self.m} x {self.T}")
+        Z = np.zeros(self.Z_len)
+        K = Z[:self.T * self.zdim].reshape(self.T, self.zdim)
+        K[:, self.off_a:self.off_a + self.m] = controls.T
+        if self.off_dt >= 0:
+            if dts is None:
+                raise ValueError("this handle reads its timesteps from the trajectory vector")
+            K[:, self.off_dt] = np.full(self.T, float(dts)) if np.ndim(dts) == 0 else np.asarray(dts, dtype=np.float64).ravel()
+        return Z
+
+    def _samples(self, theta, scale):
+        theta = None if theta is None else np.asarray(theta, dtype=np.float64)
+        if theta is not None and theta.ndim == 1:
+            theta = theta.reshape(-1, 1) if self.p == 1 else theta.reshape(-1, self.p)
+        scale = None if scale is None else np.asarray(scale, dtype=np.float64)
+        if scale is not None and scale.ndim == 1:
+            scale = scale.reshape(-1, 1) if self.m == 1 else scale.reshape(-1, self.m)
+        if theta is None and scale is None:
+            raise ValueError("theta (S x n_pert) or scale (S x m) must give the number of samples")
+        S = theta.shape[0] if theta is not None else scale.shape[0]
+        if theta is not None and theta.shape != (S, self.p):
+            raise ValueError(f"theta must be S x {self.p}")
+        if self.p and theta is None:
+            raise ValueError("theta is required: the handle has perturbations")
+        if scale is not None and scale.shape != (S, self.m):
+            raise ValueError(f"scale must be {S} x {self.m}")
+        if S < 1:
+            raise ValueError("at least one sample")
+        return S, (np.ascontiguousarray(theta) if self.p else None), (np.ascontiguousarray(scale) if scale is not None and self.m else None)
+
+    def eval(self, Z, init, theta, scale=None, finals: bool = True, fids: Optional[bool] = None):
+        """(finals, fids): finals (2N cols) x S or None; fids S values or None (default: when the handle has a fidelity)."""
+        Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
+        if Z.size != self.Z_len:
+            raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
+        init = np.ascontiguousarray(init, dtype=np.float64).ravel()
+        if init.size != self.ns:
+            raise ValueError(f"initial state has length {init.size}, expected {self.ns}")
+        S, theta, scale = self._samples(theta, scale)
+        if fids is None:
+            fids = self.fid_kind != _lib.QC_SWEEP_FID_NONE
+        out = np.empty((S, self.ns)) if finals else None
+        f = np.empty(S) if fids else None
+        rc = _lib.lib.qc_sweep_eval(self._h, _lib.dptr(Z), _lib.dptr(init), S, _lib.dptr(theta) if theta is not None else None,
+                                    _lib.dptr(scale) if scale is not None else None, _lib.dptr(out) if finals else None,
+                                    _lib.dptr(f) if fids else None)
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        return (np.ascontiguousarray(out.T) if finals else None), f
+
+    def eval_device(self, dZ, dinit, dtheta, dscale, dfinals, dfids, stream=None):
+        """Device-resident evaluation on torch CUDA tensors (float64), asynchronous on `stream`: dtheta S x n_pert (None
+        without perturbations: dfinals / dfids give S), dscale S x m or None, dfinals S x (2N cols) or None, dfids S or None."""
+        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        if dfids is not None:
+            S = dfids.numel()
+        elif dfinals is not None:
+            S = dfinals.numel() // self.ns
+        else:
+            raise ValueError("dfinals and dfids are both None")
+        for t, cnt, what in ((dtheta, S * self.p, "dtheta"), (dscale, S * self.m, "dscale"), (dfinals, S * self.ns, "dfinals"), (dZ, self.Z_len, "dZ"),
+                             (dinit, self.ns, "dinit")):
+            if t is not None and (t.numel() != cnt or t.dtype != torch.float64 or not t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous float64 tensor of {cnt} entries")
+        rc = _lib.lib.qc_sweep_eval_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, dtheta.data_ptr() if (dtheta is not None and self.p) else None,
+                                        dscale.data_ptr() if (dscale is not None and self.m) else None,
+                                        dfinals.data_ptr() if dfinals is not None else None, dfids.data_ptr() if dfids is not None else None, s)
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib.qc_sweep_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None, cols: Optional[int] = None, goal=None, fid_kind=None,
+                  subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS):
+    """(finals, fids) of S rollouts under the perturbed systems: finals is (2N cols) x S, fids S values (None without `fid_kind`).
+    theta is S x len(perturbations) (S x 0 without perturbations), scale S x n_drives or None (all ones)."""
+    controls = np.asarray(controls, dtype=np.float64)
+    if controls.ndim != 2 or controls.shape[0] != system.n_drives:
+        raise ValueError("controls must be n_drives x T")
+    T = controls.shape[1]
+    init = np.ascontiguousarray(init, dtype=np.float64).ravel()
+    n = 2 * system.state_levels
+    if cols is None:
+        cols = init.size // n
+    sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device)
+    try:
+        return sw.eval(sw.pack(controls, dts), init, theta, scale)
+    finally:
+        sw.close()
+
+
+def _traj_dts(traj):
+    return traj[traj.timestep].ravel() if isinstance(traj.timestep, str) else float(traj.timestep)
+
+
+def unitary_rollout_fidelity_sweep(traj: NamedTrajectory, system, perturbations, theta, scale=None, state_name: str = "Ũ⃗",
+                                   control_name: str = "a", subspace: Optional[Sequence[int]] = None, device: int = 0) -> np.ndarray:
+    """`unitary_rollout_fidelity` under S perturbed systems: initial state, goal and timesteps as that function takes them."""
+    init = traj.initial.get(state_name) if getattr(traj, "initial", None) else None
+    if init is None:
+        init = operator_to_iso_vec(np.eye(system.levels, dtype=complex))
+    return rollout_sweep(np.asarray(init, dtype=np.float64), traj[control_name], _traj_dts(traj), system, perturbations, theta, scale,
+                         cols=system.levels, goal=np.asarray(traj.goal[state_name], dtype=np.float64), fid_kind="unitary", subspace=subspace,
+                         device=device)[1]
+
+
+def rollout_fidelity_sweep(traj: NamedTrajectory, system, perturbations, theta, scale=None, state_name: str = "ψ̃", control_name: str = "a",
+                           device: int = 0) -> np.ndarray:
+    """`rollout_fidelity` of a ket component under S perturbed systems."""
+    init = traj.initial.get(state_name) if getattr(traj, "initial", None) else None
+    if init is None:
+        init = traj[state_name][:, 0]
+    return rollout_sweep(np.ascontiguousarray(init, dtype=np.float64), traj[control_name], _traj_dts(traj), system, perturbations, theta, scale,
+                         cols=1, goal=np.asarray(traj.goal[state_name], dtype=np.float64), fid_kind="ket", device=device)[1]
