@@ -9,20 +9,19 @@
 #include <math.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
-#include "qc_internal.h"
+#include "qc_side.h"
 
-struct qc_fidelity {
-    int N = 0, s = 0, n_sub = 0, device = 0, kind = QC_FID_UNITARY;
+struct qc_fidelity : qc_side {
+    int N = 0, s = 0, n_sub = 0, kind = QC_FID_UNITARY;
     int form = QC_FID_FORM_ABS;      // |tr| / n  or  |tr|^2 / n^2
     int K = 0;                       // free phases (global variables behind the state in the input vector)
     double *dgr = nullptr, *dgi = nullptr, *dU = nullptr, *dOut = nullptr;   // dOut: [value(2: F, l) | gradF (P) | hessF (P(P+1)/2)], P = s + K
     // free phases: m_r(u) = sum_p (CR + i CI)[r][p] u_p,  tr = sum_r exp(i theta_r) m_r,  theta_r = sum_k phi_k lam[k][r]
     double *dCR = nullptr, *dCI = nullptr, *dLam = nullptr, *dWork = nullptr;
-    hipStream_t stream = nullptr;
-    std::string err;
 };
 
 namespace {
@@ -162,6 +161,7 @@ __global__ __launch_bounds__(256) void qc_fidelity_kernel(const double* __restri
     const double tr = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
     const double ti = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
     // unitary: F = |t| / n (or |t|^2 / n^2);   ket: F = |t|^2 (iso_fidelity);   density operator against a pure goal: F = Re t = psi' rho psi
+    // (written out again in qc_sweep_finish_kernel, qc_sweep.hip: a shared inline function changed this kernel's generated code)
     const bool sq = kind == QC_FID_UNITARY && form == QC_FID_FORM_ABS2;
     const double Fv = kind == QC_FID_UNITARY ? (sq ? (tr * tr + ti * ti) / (n * n) : sqrt(tr * tr + ti * ti) / n)
                                              : (kind == QC_FID_KET ? tr * tr + ti * ti : tr);
@@ -210,19 +210,9 @@ __global__ __launch_bounds__(256) void qc_fidelity_kernel(const double* __restri
 }
 
 thread_local std::string g_ferr;
-int ffail(qc_fidelity* h, int code, const std::string& msg) {
-    if (h) h->err = msg;
-    g_ferr = msg;
-    return code;
-}
+int ffail(qc_side* h, int code, const std::string& msg) { return qc_side_fail(h, &g_ferr, code, msg); }
 
 }  // namespace
-
-#define QCF_HIP(h, call)                                                                              \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) return ffail(h, QC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 extern "C" const char* qc_fidelity_last_error(const qc_fidelity* h) { return h ? h->err.c_str() : g_ferr.c_str(); }
 
@@ -283,6 +273,76 @@ extern "C" int qc_hermitian_eig(int32_t d, const double* A_re, const double* A_i
     memcpy(w, ww.data(), (size_t)d * 8);
     memcpy(V_re, vr.data(), (size_t)d * d * 8);
     memcpy(V_im, vi.data(), (size_t)d * d * 8);
+    return QC_OK;
+}
+
+// g_r, g_i and n of qc_side.h: the one definition of the fidelity's constants (this handle and qc_sweep's).
+int qc_fidelity_goal(int kind, int N, const double* goal_iso, const int32_t* subspace, int n_sub, double* gr, double* gi) {
+    const int len = kind == QC_FID_UNITARY ? 2 * N * N : 2 * N;
+    std::fill(gr, gr + len, 0.0);
+    std::fill(gi, gi + len, 0.0);
+    if (kind == QC_FID_UNITARY) {
+        const int n = subspace ? n_sub : N;
+        for (int b = 0; b < n; ++b)
+            for (int a = 0; a < n; ++a) {
+                const int re = (subspace ? subspace[b] : b) * 2 * N + (subspace ? subspace[a] : a), im = re + N;
+                const double Gre = goal_iso[re], Gim = goal_iso[im];
+                gr[re] = Gre;  gr[im] = Gim;
+                gi[re] = -Gim; gi[im] = Gre;
+            }
+        return n;
+    }
+    const int L = kind == QC_FID_KET ? N : qc_isqrt_exact(N);
+    const double* gre = goal_iso;            // [Re psi_goal; Im psi_goal]
+    const double* gim = goal_iso + L;
+    if (kind == QC_FID_KET) {
+        // <g|psi> = (g_re . p_re + g_im . p_im) + i (g_re . p_im - g_im . p_re)
+        for (int i = 0; i < L; ++i) {
+            gr[i] = gre[i];  gr[L + i] = gim[i];
+            gi[i] = -gim[i]; gi[L + i] = gre[i];
+        }
+    } else {
+        // psi' rho psi = sum_ij conj(psi_i) rho_ij psi_j = <P, rho>_F with P = psi psi'; real for Hermitian rho:
+        // Re <P, rho> = sum Re P_ij Re rho_ij + Im P_ij Im rho_ij on the iso-vec [vec(Re rho); vec(Im rho)] (column-major)
+        for (int j = 0; j < L; ++j)
+            for (int i = 0; i < L; ++i) {
+                gr[j * L + i] = gre[i] * gre[j] + gim[i] * gim[j];             // Re (psi_i conj(psi_j))
+                gr[L * L + j * L + i] = gim[i] * gre[j] - gre[i] * gim[j];     // Im (psi_i conj(psi_j))
+            }
+    }
+    return 1;
+}
+
+// The device half of both creates (arguments checked by the caller; N = levels for every kind): the constant vectors, the free
+// phases' tables (K > 0: CR, CI, lam), the staging of the host-buffer entry point.
+static int fid_build(const char* who, int device, int kind, int N, int form, const double* goal_iso, const int32_t* subspace, int n_sub, int K,
+                     const std::vector<double>& CR, const std::vector<double>& CI, const std::vector<double>& lam, qc_fidelity** out) {
+    int rc = qc_side_check_device(device, who, &g_ferr);
+    if (rc) return rc;
+    qc_side_new<qc_fidelity> h(new qc_fidelity());
+    h->device = device;
+    h->N = N;
+    h->kind = kind;
+    h->form = form;
+    h->K = K;
+    h->s = kind == QC_FID_KET ? 2 * N : 2 * N * N;
+    std::vector<double> gr(h->s), gi(h->s);
+    h->n_sub = qc_fidelity_goal(kind, kind == QC_FID_DENSITY ? N * N : N, goal_iso, subspace, n_sub, gr.data(), gi.data());
+    qc_device_guard guard(device);
+    QC_SIDE_HIP(nullptr, g_ferr, guard.err);
+    const size_t P = (size_t)h->s + K;
+    QC_SIDE_HIP(nullptr, g_ferr, h->alloc(&h->dgr, gr.size(), gr.data()));
+    QC_SIDE_HIP(nullptr, g_ferr, h->alloc(&h->dgi, gi.size(), gi.data()));
+    QC_SIDE_HIP(nullptr, g_ferr, h->alloc(&h->dU, P));
+    QC_SIDE_HIP(nullptr, g_ferr, h->alloc(&h->dOut, 2 + P + P * (P + 1) / 2));
+    if (K > 0) {
+        QC_SIDE_HIP(nullptr, g_ferr, h->alloc(&h->dCR, CR.size(), CR.data()));
+        QC_SIDE_HIP(nullptr, g_ferr, h->alloc(&h->dCI, CI.size(), CI.data()));
+        QC_SIDE_HIP(nullptr, g_ferr, h->alloc(&h->dLam, lam.size(), lam.data()));
+        QC_SIDE_HIP(nullptr, g_ferr, h->alloc(&h->dWork, 2 + 2 * P + 2 * (size_t)K * h->s + 2 * (size_t)K * K + 4 * (size_t)h->n_sub));
+    }
+    QC_SIDE_HIP(nullptr, g_ferr, h->open_stream());
+    *out = h.release();
     return QC_OK;
 }
 
@@ -362,25 +422,8 @@ extern "C" int qc_fidelity_create_desc(const qc_fidelity_desc* d, qc_fidelity** 
             }
         }
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ffail(nullptr, QC_ERR_NO_DEVICE, "qc_fidelity_create: no HIP device visible");
-    if (d->device < 0 || d->device >= ndev) return ffail(nullptr, QC_ERR_NO_DEVICE, "qc_fidelity_create: device ordinal out of range");
-    qc_fidelity* h = new qc_fidelity();
-    h->N = N;
-    h->s = 2 * N * N;
-    h->n_sub = n;
-    h->device = d->device;
-    h->form = d->form;
-    h->K = K;
+    const int s = 2 * N * N;
     const double* goal_iso = d->goal_iso;
-    std::vector<double> gr(h->s, 0.0), gi(h->s, 0.0);
-    for (int j : sub)
-        for (int i : sub) {
-            const int re = j * 2 * N + i, im = j * 2 * N + N + i;
-            const double Gre = goal_iso[re], Gim = goal_iso[im];
-            gr[re] = Gre;  gr[im] = Gim;
-            gi[re] = -Gim; gi[im] = Gre;
-        }
     std::vector<double> CR, CI;
     if (K > 0) {
         // m_r = sum_{a,b} conj(V_ar) U_ab W_br,  W = G' V  (all on the subspace);  d m_r / d Re U_ab = c, d m_r / d Im U_ab = i c
@@ -396,8 +439,8 @@ extern "C" int qc_fidelity_create_desc(const qc_fidelity_desc* d, qc_fidelity** 
                 }
                 Wr[(size_t)r * n + b] = sr; Wi[(size_t)r * n + b] = si;
             }
-        CR.assign((size_t)n * h->s, 0.0);
-        CI.assign((size_t)n * h->s, 0.0);
+        CR.assign((size_t)n * s, 0.0);
+        CI.assign((size_t)n * s, 0.0);
         for (int r = 0; r < n; ++r)
             for (int b = 0; b < n; ++b)
                 for (int a = 0; a < n; ++a) {
@@ -405,35 +448,11 @@ extern "C" int qc_fidelity_create_desc(const qc_fidelity_desc* d, qc_fidelity** 
                     const double cr = var * Wr[(size_t)r * n + b] - vai * Wi[(size_t)r * n + b];
                     const double ci = var * Wi[(size_t)r * n + b] + vai * Wr[(size_t)r * n + b];
                     const int re = sub[b] * 2 * N + sub[a], im = re + N;
-                    CR[(size_t)r * h->s + re] = cr;  CI[(size_t)r * h->s + re] = ci;       // d/d Re U_ab = c
-                    CR[(size_t)r * h->s + im] = -ci; CI[(size_t)r * h->s + im] = cr;       // d/d Im U_ab = i c
+                    CR[(size_t)r * s + re] = cr;  CI[(size_t)r * s + re] = ci;       // d/d Re U_ab = c
+                    CR[(size_t)r * s + im] = -ci; CI[(size_t)r * s + im] = cr;       // d/d Im U_ab = i c
                 }
     }
-    auto bail = [&](hipError_t e, const char* what) { std::string m = std::string(what) + ": " + hipGetErrorString(e); qc_fidelity_destroy(h); return ffail(nullptr, QC_ERR_HIP, m); };
-    hipError_t e;
-    qc_device_guard guard(d->device);
-    if (guard.err != hipSuccess) return bail(guard.err, "hipSetDevice");
-    const size_t P = (size_t)h->s + K;
-    const size_t nout = 2 + P + P * (P + 1) / 2;
-    if ((e = hipMalloc((void**)&h->dgr, h->s * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc((void**)&h->dgi, h->s * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc((void**)&h->dU, P * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc((void**)&h->dOut, nout * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMemcpy(h->dgr, gr.data(), h->s * 8, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-    if ((e = hipMemcpy(h->dgi, gi.data(), h->s * 8, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-    if (K > 0) {
-        const size_t nw = 2 + 2 * P + 2 * (size_t)K * h->s + 2 * (size_t)K * K + 4 * (size_t)n;
-        if ((e = hipMalloc((void**)&h->dCR, CR.size() * 8)) != hipSuccess) return bail(e, "hipMalloc");
-        if ((e = hipMalloc((void**)&h->dCI, CI.size() * 8)) != hipSuccess) return bail(e, "hipMalloc");
-        if ((e = hipMalloc((void**)&h->dLam, lam.size() * 8)) != hipSuccess) return bail(e, "hipMalloc");
-        if ((e = hipMalloc((void**)&h->dWork, nw * 8)) != hipSuccess) return bail(e, "hipMalloc");
-        if ((e = hipMemcpy(h->dCR, CR.data(), CR.size() * 8, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-        if ((e = hipMemcpy(h->dCI, CI.data(), CI.size() * 8, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-        if ((e = hipMemcpy(h->dLam, lam.data(), lam.size() * 8, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-    }
-    if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
-    *out = h;
-    return QC_OK;
+    return fid_build("qc_fidelity_create", d->device, QC_FID_UNITARY, N, d->form, d->goal_iso, d->subspace, d->n_sub, K, CR, CI, lam, out);
 }
 
 extern "C" int qc_fidelity_create(int32_t N, const double* goal_iso, const int32_t* subspace, int32_t n_sub, int32_t device,
@@ -457,56 +476,12 @@ extern "C" int qc_fidelity_create_kind(int32_t kind, int32_t N, const double* go
     *out = nullptr;
     if (kind != QC_FID_KET && kind != QC_FID_DENSITY) return ffail(nullptr, QC_ERR_INVALID, "qc_fidelity_create_kind: kind must be QC_FID_KET or QC_FID_DENSITY");
     if (N < 1 || N > 64 || !goal_ket_iso) return ffail(nullptr, QC_ERR_INVALID, "qc_fidelity_create_kind: bad N or goal");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ffail(nullptr, QC_ERR_NO_DEVICE, "qc_fidelity_create_kind: no HIP device visible");
-    if (device < 0 || device >= ndev) return ffail(nullptr, QC_ERR_NO_DEVICE, "qc_fidelity_create_kind: device ordinal out of range");
-    qc_fidelity* h = new qc_fidelity();
-    h->N = N;
-    h->kind = kind;
-    h->n_sub = 1;
-    h->device = device;
-    h->s = kind == QC_FID_KET ? 2 * N : 2 * N * N;
-    std::vector<double> gr(h->s, 0.0), gi(h->s, 0.0);
-    const double* gre = goal_ket_iso;        // [Re psi_goal; Im psi_goal]
-    const double* gim = goal_ket_iso + N;
-    if (kind == QC_FID_KET) {
-        // <g|psi> = (g_re . p_re + g_im . p_im) + i (g_re . p_im - g_im . p_re)
-        for (int i = 0; i < N; ++i) {
-            gr[i] = gre[i];  gr[N + i] = gim[i];
-            gi[i] = -gim[i]; gi[N + i] = gre[i];
-        }
-    } else {
-        // psi' rho psi = sum_ij conj(psi_i) rho_ij psi_j = <P, rho>_F with P = psi psi'; real for Hermitian rho:
-        // Re <P, rho> = sum Re P_ij Re rho_ij + Im P_ij Im rho_ij on the iso-vec [vec(Re rho); vec(Im rho)] (column-major)
-        for (int j = 0; j < N; ++j)
-            for (int i = 0; i < N; ++i) {
-                const double pre = gre[i] * gre[j] + gim[i] * gim[j];       // Re (psi_i conj(psi_j))
-                const double pim = gim[i] * gre[j] - gre[i] * gim[j];       // Im (psi_i conj(psi_j))
-                gr[j * N + i] = pre;
-                gr[N * N + j * N + i] = pim;
-            }
-    }
-    auto bail = [&](hipError_t e, const char* what) { std::string m = std::string(what) + ": " + hipGetErrorString(e); qc_fidelity_destroy(h); return ffail(nullptr, QC_ERR_HIP, m); };
-    hipError_t e;
-    qc_device_guard guard(device);
-    if (guard.err != hipSuccess) return bail(guard.err, "hipSetDevice");
-    const size_t nout = 2 + (size_t)h->s + (size_t)h->s * (h->s + 1) / 2;
-    if ((e = hipMalloc((void**)&h->dgr, h->s * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc((void**)&h->dgi, h->s * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc((void**)&h->dU, h->s * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc((void**)&h->dOut, nout * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMemcpy(h->dgr, gr.data(), h->s * 8, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-    if ((e = hipMemcpy(h->dgi, gi.data(), h->s * 8, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-    if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
-    *out = h;
-    return QC_OK;
+    return fid_build("qc_fidelity_create_kind", device, kind, N, QC_FID_FORM_ABS, goal_ket_iso, nullptr, 0, 0, {}, {}, {}, out);
 }
 
 extern "C" void qc_fidelity_destroy(qc_fidelity* h) {
     if (!h) return;
-    qc_device_guard guard(h->device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    for (double* p : {h->dgr, h->dgi, h->dU, h->dOut, h->dCR, h->dCI, h->dLam, h->dWork}) if (p) (void)hipFree(p);
+    h->release_device();
     delete h;
 }
 
@@ -514,7 +489,7 @@ extern "C" int qc_fidelity_eval_dev(qc_fidelity* h, const double* dU, double* dv
     if (!h) return ffail(nullptr, QC_ERR_INVALID, "qc_fidelity_eval_dev: NULL handle");
     if (!dU || !dval2) return ffail(h, QC_ERR_INVALID, "qc_fidelity_eval_dev: NULL buffer");
     qc_device_guard guard(h->device);
-    if (guard.err != hipSuccess) return ffail(h, QC_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(guard.err));
+    QC_SIDE_HIP(h, g_ferr, guard.err);
     hipLaunchKernelGGL(qc_fidelity_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, dU, h->dgr, h->dgi, h->s, h->n_sub, h->kind, h->form, h->K,
                        h->dCR, h->dCI, h->dLam, h->dWork, dval2, dgrad, dhess);
     hipError_t e = hipGetLastError();
@@ -526,19 +501,19 @@ extern "C" int qc_fidelity_eval(qc_fidelity* h, const double* U_iso, double* fid
     if (!h) return ffail(nullptr, QC_ERR_INVALID, "qc_fidelity_eval: NULL handle");
     if (!U_iso) return ffail(h, QC_ERR_INVALID, "qc_fidelity_eval: NULL input");
     qc_device_guard guard(h->device);
-    QCF_HIP(h, guard.err);
+    QC_SIDE_HIP(h, g_ferr, guard.err);
     const size_t P = (size_t)h->s + h->K;    // input = [state ; free phases]
-    QCF_HIP(h, hipMemcpyAsync(h->dU, U_iso, P * 8, hipMemcpyHostToDevice, h->stream));
+    QC_SIDE_HIP(h, g_ferr, hipMemcpyAsync(h->dU, U_iso, P * 8, hipMemcpyHostToDevice, h->stream));
     double* dval = h->dOut;
     double* dgrad = h->dOut + 2;
     double* dhess = h->dOut + 2 + P;
     int rc = qc_fidelity_eval_dev(h, h->dU, dval, grad ? dgrad : nullptr, hess ? dhess : nullptr, h->stream);
     if (rc) return rc;
     double v[2];
-    QCF_HIP(h, hipMemcpyAsync(v, dval, 16, hipMemcpyDeviceToHost, h->stream));
-    if (grad) QCF_HIP(h, hipMemcpyAsync(grad, dgrad, P * 8, hipMemcpyDeviceToHost, h->stream));
-    if (hess) QCF_HIP(h, hipMemcpyAsync(hess, dhess, P * (P + 1) / 2 * 8, hipMemcpyDeviceToHost, h->stream));
-    QCF_HIP(h, hipStreamSynchronize(h->stream));
+    QC_SIDE_HIP(h, g_ferr, hipMemcpyAsync(v, dval, 16, hipMemcpyDeviceToHost, h->stream));
+    if (grad) QC_SIDE_HIP(h, g_ferr, hipMemcpyAsync(grad, dgrad, P * 8, hipMemcpyDeviceToHost, h->stream));
+    if (hess) QC_SIDE_HIP(h, g_ferr, hipMemcpyAsync(hess, dhess, P * (P + 1) / 2 * 8, hipMemcpyDeviceToHost, h->stream));
+    QC_SIDE_HIP(h, g_ferr, hipStreamSynchronize(h->stream));
     if (fidelity) *fidelity = v[0];
     if (infidelity) *infidelity = v[1];
     return QC_OK;

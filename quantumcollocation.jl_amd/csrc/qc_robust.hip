@@ -38,7 +38,7 @@
 #include <string>
 #include <vector>
 
-#include "qc_internal.h"
+#include "qc_side.h"
 
 namespace {
 
@@ -364,30 +364,22 @@ __global__ __launch_bounds__(kRobThreads) void qc_robust_syrk_kernel(SyrkParams 
 }
 
 thread_local std::string g_rerr;
-int rfail(qc_robust* h, int code, const std::string& msg);
+int rfail(qc_side* h, int code, const std::string& msg) { return qc_side_fail(h, &g_rerr, code, msg); }
 
 }  // namespace
 
-struct qc_robust {
+struct qc_robust : qc_side {
     qc_robust_desc d{};
-    int n = 0, P = 0, kp = 0, m2p = 0, nparts = 0, device = 0;
+    int n = 0, P = 0, kp = 0, m2p = 0, nparts = 0;
     int64_t V = 0, Vp = 0, nh = 0, ngroups = 0, Zlen = 0;
     size_t lds_partial = 0, lds_grad = 0;
     std::vector<int64_t> local;   // P sorted offsets inside a knot
     int *dsub = nullptr, *dslot = nullptr, *dvar = nullptr;
     double *dH = nullptr, *dpart = nullptr, *dglob = nullptr, *dr = nullptr, *dcvec = nullptr, *ddtn = nullptr;
-    double *dZ = nullptr, *dL = nullptr, *dgrad = nullptr, *dhess = nullptr;   // staging of the host-pointer entry
-    hipStream_t stream = nullptr;
-    std::string err;
+    double *dZ = nullptr, *dL = nullptr, *dgrad = nullptr, *dhess = nullptr;   // staging of the host-pointer entry (dhess: at the first call that asks for it)
 };
 
 namespace {
-
-int rfail(qc_robust* h, int code, const std::string& msg) {
-    if (h) h->err = msg;
-    g_rerr = msg;
-    return code;
-}
 
 struct RobLayout {
     int n = 0, P = 0;
@@ -461,12 +453,6 @@ int robust_layout(const qc_robust_desc* d, RobLayout* out) {
 
 }  // namespace
 
-#define QCR_HIP(h, call)                                                                              \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) return rfail(h, QC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 extern "C" const char* qc_robust_last_error(const qc_robust* h) { return h ? h->err.c_str() : g_rerr.c_str(); }
 
 extern "C" int64_t qc_sizeof_robust_desc(void) { return (int64_t)sizeof(qc_robust_desc); }
@@ -523,10 +509,8 @@ extern "C" int qc_robust_create(const qc_robust_desc* d, qc_robust** out) {
     RobLayout L;
     int rc = robust_layout(d, &L);
     if (rc) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return rfail(nullptr, QC_ERR_NO_DEVICE, "qc_robust_create: no HIP device visible");
-    if (d->device < 0 || d->device >= ndev) return rfail(nullptr, QC_ERR_NO_DEVICE, "qc_robust_create: device ordinal out of range");
-    qc_robust* h = new qc_robust();
+    if ((rc = qc_side_check_device(d->device, "qc_robust_create", &g_rerr))) return rc;
+    qc_side_new<qc_robust> h(new qc_robust());
     h->d = *d;
     h->d.subspace = nullptr;    // caller-owned arrays are not retained
     h->d.H_re = h->d.H_im = nullptr;
@@ -550,51 +534,36 @@ extern "C" int qc_robust_create(const qc_robust_desc* d, qc_robust** out) {
         Hp[e] = d->H_re[e];
         Hp[nn + e] = d->H_im ? d->H_im[e] : 0.0;
     }
-    auto bail = [&](hipError_t e, const char* what) {
-        std::string m = std::string(what) + ": " + hipGetErrorString(e);
-        qc_robust_destroy(h);
-        return rfail(nullptr, QC_ERR_HIP, m);
-    };
-    hipError_t e;
-    if ((e = hipSetDevice(d->device)) != hipSuccess) return bail(e, "hipSetDevice");
-    auto up = [&](void** dst, const void* src, size_t bytes) {
-        hipError_t x = hipMalloc(dst, bytes);
-        if (x == hipSuccess && src) x = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-        return x;
-    };
-    if ((e = up((void**)&h->dsub, L.sub.data(), L.sub.size() * 4)) != hipSuccess) return bail(e, "hipMalloc / hipMemcpy");
-    if ((e = up((void**)&h->dslot, L.slot.data(), L.slot.size() * 4)) != hipSuccess) return bail(e, "hipMalloc / hipMemcpy");
-    if ((e = up((void**)&h->dvar, L.var.data(), L.var.size() * 4)) != hipSuccess) return bail(e, "hipMalloc / hipMemcpy");
-    if ((e = up((void**)&h->dH, Hp.data(), Hp.size() * 8)) != hipSuccess) return bail(e, "hipMalloc / hipMemcpy");
-    if ((e = up((void**)&h->dpart, nullptr, (size_t)h->nparts * (m2 + 1) * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = up((void**)&h->dglob, nullptr, (size_t)(m2 + 2) * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = up((void**)&h->dZ, nullptr, (size_t)h->Zlen * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = up((void**)&h->dL, nullptr, 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = up((void**)&h->dgrad, nullptr, (size_t)h->Zlen * 8)) != hipSuccess) return bail(e, "hipMalloc");
+    qc_device_guard guard(d->device);
+    QC_SIDE_HIP(nullptr, g_rerr, guard.err);
+    QC_SIDE_HIP(nullptr, g_rerr, h->alloc(&h->dsub, L.sub.size(), L.sub.data()));
+    QC_SIDE_HIP(nullptr, g_rerr, h->alloc(&h->dslot, L.slot.size(), L.slot.data()));
+    QC_SIDE_HIP(nullptr, g_rerr, h->alloc(&h->dvar, L.var.size(), L.var.data()));
+    QC_SIDE_HIP(nullptr, g_rerr, h->alloc(&h->dH, Hp.size(), Hp.data()));
+    QC_SIDE_HIP(nullptr, g_rerr, h->alloc(&h->dpart, (size_t)h->nparts * (m2 + 1)));
+    QC_SIDE_HIP(nullptr, g_rerr, h->alloc(&h->dglob, (size_t)(m2 + 2)));
+    QC_SIDE_HIP(nullptr, g_rerr, h->alloc(&h->dZ, (size_t)h->Zlen));
+    QC_SIDE_HIP(nullptr, g_rerr, h->alloc(&h->dL, 1));
+    QC_SIDE_HIP(nullptr, g_rerr, h->alloc(&h->dgrad, (size_t)h->Zlen));
     if (h->nh) {
         // rows past V stay zero: the SYRK reads whole 16-row tiles
-        if ((e = up((void**)&h->dr, nullptr, (size_t)h->Vp * h->m2p * 8)) != hipSuccess) return bail(e, "hipMalloc");
-        if ((e = hipMemset(h->dr, 0, (size_t)h->Vp * h->m2p * 8)) != hipSuccess) return bail(e, "hipMemset");
-        if ((e = up((void**)&h->dcvec, nullptr, (size_t)h->V * 8)) != hipSuccess) return bail(e, "hipMalloc");
-        if ((e = up((void**)&h->ddtn, nullptr, (size_t)d->n_knots * 8)) != hipSuccess) return bail(e, "hipMalloc");
+        QC_SIDE_HIP(nullptr, g_rerr, h->alloc(&h->dr, (size_t)h->Vp * h->m2p));
+        QC_SIDE_HIP(nullptr, g_rerr, hipMemset(h->dr, 0, (size_t)h->Vp * h->m2p * 8));
+        QC_SIDE_HIP(nullptr, g_rerr, h->alloc(&h->dcvec, (size_t)h->V));
+        QC_SIDE_HIP(nullptr, g_rerr, h->alloc(&h->ddtn, (size_t)d->n_knots));
     }
-    if (h->lds_partial > 65536 &&
-        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(qc_robust_partial_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_partial)) != hipSuccess)
-        return bail(e, "hipFuncSetAttribute");
-    if (h->lds_grad > 65536 &&
-        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(qc_robust_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_grad)) != hipSuccess)
-        return bail(e, "hipFuncSetAttribute");
-    if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
-    *out = h;
+    if (h->lds_partial > 65536)
+        QC_SIDE_HIP(nullptr, g_rerr, hipFuncSetAttribute(reinterpret_cast<const void*>(qc_robust_partial_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_partial));
+    if (h->lds_grad > 65536)
+        QC_SIDE_HIP(nullptr, g_rerr, hipFuncSetAttribute(reinterpret_cast<const void*>(qc_robust_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_grad));
+    QC_SIDE_HIP(nullptr, g_rerr, h->open_stream());
+    *out = h.release();
     return QC_OK;
 }
 
 extern "C" void qc_robust_destroy(qc_robust* h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    for (int* p : {h->dsub, h->dslot, h->dvar}) if (p) (void)hipFree(p);
-    for (double* p : {h->dH, h->dpart, h->dglob, h->dr, h->dcvec, h->ddtn, h->dZ, h->dL, h->dgrad, h->dhess}) if (p) (void)hipFree(p);
+    h->release_device();
     delete h;
 }
 
@@ -637,6 +606,8 @@ extern "C" int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, do
     if (!h) return rfail(nullptr, QC_ERR_INVALID, "qc_robust_eval_dev: NULL handle");
     if (!dZ) return rfail(h, QC_ERR_INVALID, "qc_robust_eval_dev: NULL input");
     if (dhvals && !h->nh) return rfail(h, QC_ERR_INVALID, "qc_robust_eval_dev: Hessian values requested from a handle created without a Hessian");
+    qc_device_guard guard(h->device);
+    QC_SIDE_HIP(h, g_rerr, guard.err);
     RobParams P;
     P.T = h->d.T;
     P.K = h->d.n_knots;
@@ -689,16 +660,17 @@ extern "C" int qc_robust_eval(qc_robust* h, const double* Z, double* L, double* 
     if (!h) return rfail(nullptr, QC_ERR_INVALID, "qc_robust_eval: NULL handle");
     if (!Z) return rfail(h, QC_ERR_INVALID, "qc_robust_eval: NULL input");
     if (hvals && !h->nh) return rfail(h, QC_ERR_INVALID, "qc_robust_eval: Hessian values requested from a handle created without a Hessian");
-    QCR_HIP(h, hipSetDevice(h->device));
-    if (hvals && !h->dhess) QCR_HIP(h, hipMalloc((void**)&h->dhess, (size_t)h->nh * 8));
-    QCR_HIP(h, hipMemcpyAsync(h->dZ, Z, (size_t)h->Zlen * 8, hipMemcpyHostToDevice, h->stream));
+    qc_device_guard guard(h->device);
+    QC_SIDE_HIP(h, g_rerr, guard.err);
+    if (hvals && !h->dhess) QC_SIDE_HIP(h, g_rerr, h->alloc(&h->dhess, (size_t)h->nh));
+    QC_SIDE_HIP(h, g_rerr, hipMemcpyAsync(h->dZ, Z, (size_t)h->Zlen * 8, hipMemcpyHostToDevice, h->stream));
     int rc = qc_robust_eval_dev(h, h->dZ, h->dL, grad ? h->dgrad : nullptr, hvals ? h->dhess : nullptr, h->stream);
     if (rc) return rc;
     double l = 0.0;
-    QCR_HIP(h, hipMemcpyAsync(&l, h->dL, 8, hipMemcpyDeviceToHost, h->stream));
-    if (grad) QCR_HIP(h, hipMemcpyAsync(grad, h->dgrad, (size_t)h->Zlen * 8, hipMemcpyDeviceToHost, h->stream));
-    if (hvals) QCR_HIP(h, hipMemcpyAsync(hvals, h->dhess, (size_t)h->nh * 8, hipMemcpyDeviceToHost, h->stream));
-    QCR_HIP(h, hipStreamSynchronize(h->stream));
+    QC_SIDE_HIP(h, g_rerr, hipMemcpyAsync(&l, h->dL, 8, hipMemcpyDeviceToHost, h->stream));
+    if (grad) QC_SIDE_HIP(h, g_rerr, hipMemcpyAsync(grad, h->dgrad, (size_t)h->Zlen * 8, hipMemcpyDeviceToHost, h->stream));
+    if (hvals) QC_SIDE_HIP(h, g_rerr, hipMemcpyAsync(hvals, h->dhess, (size_t)h->nh * 8, hipMemcpyDeviceToHost, h->stream));
+    QC_SIDE_HIP(h, g_rerr, hipStreamSynchronize(h->stream));
     if (L) *L = l;
     return QC_OK;
 }

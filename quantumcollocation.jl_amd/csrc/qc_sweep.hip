@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "qc_mfma_common.h"
+#include "qc_side.h"
 
 namespace {
 
@@ -242,7 +243,7 @@ __global__ __launch_bounds__(kFinT) void qc_sweep_finish_kernel(const FinParams 
         const double tr = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
         const double ti = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
         const double nn = (double)F.fid_n;
-        double Fv;
+        double Fv;      // the mapping of qc_fidelity_kernel (qc_fidelity.hip), written out again: sharing it changed that kernel's generated code
         if (F.fid_kind == QC_FID_UNITARY) Fv = F.fid_form == QC_FID_FORM_ABS2 ? (tr * tr + ti * ti) / (nn * nn) : sqrt(tr * tr + ti * ti) / nn;
         else if (F.fid_kind == QC_FID_KET) Fv = tr * tr + ti * ti;
         else Fv = tr;
@@ -251,12 +252,12 @@ __global__ __launch_bounds__(kFinT) void qc_sweep_finish_kernel(const FinParams 
 }
 
 thread_local std::string g_swerr;
+int sfail(qc_side* h, int code, const std::string& msg) { return qc_side_fail(h, &g_swerr, code, msg); }
 
 }  // namespace
 
-struct qc_sweep {
+struct qc_sweep : qc_side {
     qc_sweep_desc d;             // caller-owned arrays are not retained (pointers nulled)
-    int device = 0;
     bool mfma = false;
     int n = 0, nc = 0, ns = 0, fid_n = 0;
     int64_t Zlen = 0;
@@ -273,23 +274,9 @@ struct qc_sweep {
     double* sScale = nullptr;  size_t capScale = 0;
     double* sFinals = nullptr; size_t capFinals = 0;
     double* sFids = nullptr;   size_t capFids = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
 };
 
 namespace {
-
-int sfail(qc_sweep* h, int code, const std::string& msg) {
-    if (h) h->err = msg;
-    g_swerr = msg;
-    return code;
-}
-
-int isqrt_exact(int v) {
-    int r = 0;
-    while ((r + 1) * (r + 1) <= v) ++r;
-    return r * r == v ? r : -1;
-}
 
 // The launch rule, in one place.  n_chunks = 1 once the samples alone give every SIMD a couple of waves; fewer samples split the
 // trajectory, up to ceil(sqrt(T-1)) chunks (beyond that the ordered chain of the second launch outweighs what the first gains).
@@ -338,7 +325,7 @@ int sweep_validate(const qc_sweep_desc* d) {
                 return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: subspace and fid_form apply to QC_FID_UNITARY only");
             if (nc != 1) return sfail(nullptr, QC_ERR_INVALID, d->fid_kind == QC_FID_KET ? "qc_sweep: the ket fidelity needs state_cols = 1"
                                                                                              : "qc_sweep: the density-operator fidelity needs state_cols = 1");
-            if (d->fid_kind == QC_FID_DENSITY && isqrt_exact(d->N) < 0)
+            if (d->fid_kind == QC_FID_DENSITY && qc_isqrt_exact(d->N) < 0)
                 return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: the density-operator fidelity needs N = levels^2");
         }
     }
@@ -350,27 +337,7 @@ int sweep_validate(const qc_sweep_desc* d) {
 
 bool sweep_is_mfma(const qc_sweep_desc* d) { return 2 * d->N <= 16 && d->m <= kSMmax; }
 
-template <class T>
-hipError_t grow(T** p, size_t* cap, size_t need) {
-    if (need <= *cap) return hipSuccess;
-    if (*p) {
-        hipError_t e = hipFree(*p);
-        *p = nullptr;
-        *cap = 0;
-        if (e != hipSuccess) return e;
-    }
-    hipError_t e = hipMalloc((void**)p, need * sizeof(T));
-    if (e == hipSuccess) *cap = need;
-    return e;
-}
-
 }  // namespace
-
-#define QCS_HIP(h, call)                                                                              \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) return sfail(h, QC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 extern "C" const char* qc_sweep_last_error(const qc_sweep* h) { return h ? h->err.c_str() : g_swerr.c_str(); }
 
@@ -398,11 +365,7 @@ extern "C" const char* qc_sweep_kernel_name(const qc_sweep* h) {
 
 extern "C" void qc_sweep_destroy(qc_sweep* h) {
     if (!h) return;
-    qc_device_guard guard(h->device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    for (double* p : {h->dG, h->dImg, h->dgr, h->dgi, h->dTot, h->dFin, h->dGs, h->dRE, h->dRQ, h->dRS, h->dRout, h->sZ, h->sInit, h->sTheta, h->sScale,
-                      h->sFinals, h->sFids})
-        if (p) (void)hipFree(p);
+    h->release_device();
     delete h;
 }
 
@@ -411,10 +374,8 @@ extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
     *out = nullptr;
     int rc = sweep_validate(d);
     if (rc) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sfail(nullptr, QC_ERR_NO_DEVICE, "qc_sweep_create: no HIP device visible");
-    if (d->device < 0 || d->device >= ndev) return sfail(nullptr, QC_ERR_NO_DEVICE, "qc_sweep_create: device ordinal out of range");
-    qc_sweep* h = new qc_sweep();
+    if ((rc = qc_side_check_device(d->device, "qc_sweep_create", &g_swerr))) return rc;
+    qc_side_new<qc_sweep> h(new qc_sweep());
     h->d = *d;
     h->device = d->device;
     h->mfma = sweep_is_mfma(d);
@@ -439,58 +400,18 @@ extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
                     if (i < n && col < n) img[(size_t)mat * 256 + kk * 64 + lane] = G[(size_t)mat * n2 + (size_t)col * n + i];
                 }
     }
-    // fidelity: the constant vectors g_r, g_i of qc_fidelity.hip
-    std::vector<double> gr, gi;
+    std::vector<double> gr, gi;      // the fidelity's constant vectors
     if (d->fid_kind != QC_SWEEP_FID_NONE) {
-        gr.assign(h->ns, 0.0);
-        gi.assign(h->ns, 0.0);
-        if (d->fid_kind == QC_FID_UNITARY) {
-            std::vector<int> sub;
-            if (d->subspace) sub.assign(d->subspace, d->subspace + d->n_sub);
-            else for (int k = 0; k < N; ++k) sub.push_back(k);
-            h->fid_n = (int)sub.size();
-            for (int jc : sub)
-                for (int i : sub) {
-                    const int re = jc * 2 * N + i, im = re + N;
-                    const double Gre = d->goal_iso[re], Gim = d->goal_iso[im];
-                    gr[re] = Gre;  gr[im] = Gim;
-                    gi[re] = -Gim; gi[im] = Gre;
-                }
-        } else if (d->fid_kind == QC_FID_KET) {
-            h->fid_n = 1;
-            for (int i = 0; i < N; ++i) {
-                gr[i] = d->goal_iso[i];      gr[N + i] = d->goal_iso[N + i];
-                gi[i] = -d->goal_iso[N + i]; gi[N + i] = d->goal_iso[i];
-            }
-        } else {
-            h->fid_n = 1;
-            const int L = isqrt_exact(N);
-            const double* gre = d->goal_iso;
-            const double* gim = d->goal_iso + L;
-            for (int jc = 0; jc < L; ++jc)
-                for (int i = 0; i < L; ++i) {
-                    gr[jc * L + i] = gre[i] * gre[jc] + gim[i] * gim[jc];
-                    gr[L * L + jc * L + i] = gim[i] * gre[jc] - gre[i] * gim[jc];
-                }
-        }
+        gr.resize(h->ns);
+        gi.resize(h->ns);
+        h->fid_n = qc_fidelity_goal(d->fid_kind, N, d->goal_iso, d->subspace, d->n_sub, gr.data(), gi.data());
     }
     h->d.G_drift = h->d.G_drives = h->d.G_pert = h->d.goal_iso = nullptr;
     h->d.subspace = nullptr;
-    auto bail = [&](hipError_t e, const char* what) {
-        std::string msg = std::string(what) + ": " + hipGetErrorString(e);
-        qc_sweep_destroy(h);
-        return sfail(nullptr, QC_ERR_HIP, msg);
-    };
     qc_device_guard guard(d->device);
-    if (guard.err != hipSuccess) return bail(guard.err, "hipSetDevice");
-    auto up = [&](double** dst, const double* src, size_t count) {
-        hipError_t x = hipMalloc((void**)dst, count * 8);
-        if (x == hipSuccess && src) x = hipMemcpy(*dst, src, count * 8, hipMemcpyHostToDevice);
-        return x;
-    };
-    hipError_t e;
+    QC_SIDE_HIP(nullptr, g_swerr, guard.err);
     if (h->mfma) {
-        if ((e = up(&h->dImg, img.data(), img.size())) != hipSuccess) return bail(e, "hipMalloc / hipMemcpy");
+        QC_SIDE_HIP(nullptr, g_swerr, h->alloc(&h->dImg, img.size(), img.data()));
     } else {
         const size_t T = (size_t)d->T;
         QcParams P{};
@@ -498,21 +419,21 @@ extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
         size_t nE, nQ, nS;
         int ch, nch;
         qc_rollout_scratch(P, (long long)T, &nE, &nQ, &nS, &ch, &nch);
-        if ((e = up(&h->dG, G.data(), G.size())) != hipSuccess) return bail(e, "hipMalloc / hipMemcpy");
-        if ((e = up(&h->dGs, nullptr, (size_t)(1 + m) * n2)) != hipSuccess) return bail(e, "hipMalloc");
-        if ((e = up(&h->dRE, nullptr, nE)) != hipSuccess) return bail(e, "hipMalloc");
-        if ((e = up(&h->dRQ, nullptr, nQ)) != hipSuccess) return bail(e, "hipMalloc");
-        if ((e = up(&h->dRS, nullptr, nS)) != hipSuccess) return bail(e, "hipMalloc");
-        if ((e = up(&h->dRout, nullptr, (size_t)h->ns * T)) != hipSuccess) return bail(e, "hipMalloc");
+        QC_SIDE_HIP(nullptr, g_swerr, h->alloc(&h->dG, G.size(), G.data()));
+        QC_SIDE_HIP(nullptr, g_swerr, h->alloc(&h->dGs, (size_t)(1 + m) * n2));
+        QC_SIDE_HIP(nullptr, g_swerr, h->alloc(&h->dRE, nE));
+        QC_SIDE_HIP(nullptr, g_swerr, h->alloc(&h->dRQ, nQ));
+        QC_SIDE_HIP(nullptr, g_swerr, h->alloc(&h->dRS, nS));
+        QC_SIDE_HIP(nullptr, g_swerr, h->alloc(&h->dRout, (size_t)h->ns * T));
     }
     if (!gr.empty()) {
-        if ((e = up(&h->dgr, gr.data(), gr.size())) != hipSuccess) return bail(e, "hipMalloc / hipMemcpy");
-        if ((e = up(&h->dgi, gi.data(), gi.size())) != hipSuccess) return bail(e, "hipMalloc / hipMemcpy");
+        QC_SIDE_HIP(nullptr, g_swerr, h->alloc(&h->dgr, gr.size(), gr.data()));
+        QC_SIDE_HIP(nullptr, g_swerr, h->alloc(&h->dgi, gi.size(), gi.data()));
     }
-    if ((e = up(&h->sZ, nullptr, (size_t)h->Zlen)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = up(&h->sInit, nullptr, (size_t)h->ns)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
-    *out = h;
+    QC_SIDE_HIP(nullptr, g_swerr, h->alloc(&h->sZ, (size_t)h->Zlen));
+    QC_SIDE_HIP(nullptr, g_swerr, h->alloc(&h->sInit, (size_t)h->ns));
+    QC_SIDE_HIP(nullptr, g_swerr, h->open_stream());
+    *out = h.release();
     return QC_OK;
 }
 
@@ -525,7 +446,7 @@ extern "C" int qc_sweep_eval_dev(qc_sweep* h, const double* dZ, const double* di
     if (!dfinals && !dfids) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval_dev: finals and fids are both NULL");
     if (dfids && h->d.fid_kind == QC_SWEEP_FID_NONE) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval_dev: fidelities requested from a handle created without one");
     qc_device_guard guard(h->device);
-    if (guard.err != hipSuccess) return sfail(h, QC_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(guard.err));
+    QC_SIDE_HIP(h, g_swerr, guard.err);
     hipStream_t st = (hipStream_t)stream;
     const int n = h->n, m = h->d.m, p = h->d.n_pert;
     FinParams F;
@@ -535,7 +456,7 @@ extern "C" int qc_sweep_eval_dev(qc_sweep* h, const double* dZ, const double* di
     if (h->mfma) {
         int64_t chunk, n_chunks;
         sweep_chunks(S, h->d.T, &chunk, &n_chunks);
-        QCS_HIP(h, grow(&h->dTot, &h->capTot, (size_t)S * n_chunks * 256));
+        QC_SIDE_HIP(h, g_swerr, h->grow(&h->dTot, &h->capTot, (size_t)S * n_chunks * 256));
         SweepParams P;
         P.n = n; P.nc = h->nc; P.m = m; P.p = p; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
         P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks;
@@ -553,7 +474,7 @@ extern "C" int qc_sweep_eval_dev(qc_sweep* h, const double* dZ, const double* di
         F.ld = 16; F.n_chunks = (int)n_chunks; F.src_stride = 0;
         src = dinit;
     } else {
-        QCS_HIP(h, grow(&h->dFin, &h->capFin, (size_t)S * h->ns));
+        QC_SIDE_HIP(h, g_swerr, h->grow(&h->dFin, &h->capFin, (size_t)S * h->ns));
         QcParams P{};
         P.N = h->d.N; P.n = n; P.nc = h->nc; P.s = h->ns; P.m = m; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
         P.dt_fixed = h->d.dt_fixed; P.G = h->dGs;
@@ -562,15 +483,15 @@ extern "C" int qc_sweep_eval_dev(qc_sweep* h, const double* dZ, const double* di
         for (int64_t s = 0; s < S; ++s) {
             hipLaunchKernelGGL(qc_sweep_gen_kernel, dim3(gen_grid), dim3(256), 0, st, n2, m, p, (const double*)h->dG, p ? dtheta + s * p : nullptr,
                                (dscale && m) ? dscale + s * m : nullptr, h->dGs);
-            QCS_HIP(h, qc_launch_rollout(P, h->d.T, dZ, dinit, h->dRout, h->dRE, h->dRQ, h->dRS, st));
-            QCS_HIP(h, hipMemcpyAsync(h->dFin + (size_t)s * h->ns, h->dRout + last, (size_t)h->ns * 8, hipMemcpyDeviceToDevice, st));
+            QC_SIDE_HIP(h, g_swerr, qc_launch_rollout(P, h->d.T, dZ, dinit, h->dRout, h->dRE, h->dRQ, h->dRS, st));
+            QC_SIDE_HIP(h, g_swerr, hipMemcpyAsync(h->dFin + (size_t)s * h->ns, h->dRout + last, (size_t)h->ns * 8, hipMemcpyDeviceToDevice, st));
         }
         F.ld = n; F.n_chunks = 0; F.src_stride = h->ns;
         src = h->dFin;
     }
     const size_t lds = ((size_t)2 * h->ns + (size_t)F.ld * F.ld) * 8;
     if (lds > 64 * 1024)
-        QCS_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        QC_SIDE_HIP(h, g_swerr, hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(qc_sweep_finish_kernel, dim3((unsigned)S), dim3(kFinT), lds, st, F, (const double*)h->dTot, src, (const double*)h->dgr,
                        (const double*)h->dgi, dfinals, dfids);
     hipError_t e = hipGetLastError();
@@ -588,21 +509,21 @@ extern "C" int qc_sweep_eval(qc_sweep* h, const double* Z, const double* init, i
     if (!finals && !fids) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval: finals and fids are both NULL");
     if (fids && h->d.fid_kind == QC_SWEEP_FID_NONE) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval: fidelities requested from a handle created without one");
     qc_device_guard guard(h->device);
-    if (guard.err != hipSuccess) return sfail(h, QC_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(guard.err));
+    QC_SIDE_HIP(h, g_swerr, guard.err);
     const bool use_scale = scale && m > 0;
-    if (p) QCS_HIP(h, grow(&h->sTheta, &h->capTheta, (size_t)S * p));
-    if (use_scale) QCS_HIP(h, grow(&h->sScale, &h->capScale, (size_t)S * m));
-    if (finals) QCS_HIP(h, grow(&h->sFinals, &h->capFinals, (size_t)S * h->ns));
-    if (fids) QCS_HIP(h, grow(&h->sFids, &h->capFids, (size_t)S));
-    QCS_HIP(h, hipMemcpyAsync(h->sZ, Z, (size_t)h->Zlen * 8, hipMemcpyHostToDevice, h->stream));
-    QCS_HIP(h, hipMemcpyAsync(h->sInit, init, (size_t)h->ns * 8, hipMemcpyHostToDevice, h->stream));
-    if (p) QCS_HIP(h, hipMemcpyAsync(h->sTheta, theta, (size_t)S * p * 8, hipMemcpyHostToDevice, h->stream));
-    if (use_scale) QCS_HIP(h, hipMemcpyAsync(h->sScale, scale, (size_t)S * m * 8, hipMemcpyHostToDevice, h->stream));
+    if (p) QC_SIDE_HIP(h, g_swerr, h->grow(&h->sTheta, &h->capTheta, (size_t)S * p));
+    if (use_scale) QC_SIDE_HIP(h, g_swerr, h->grow(&h->sScale, &h->capScale, (size_t)S * m));
+    if (finals) QC_SIDE_HIP(h, g_swerr, h->grow(&h->sFinals, &h->capFinals, (size_t)S * h->ns));
+    if (fids) QC_SIDE_HIP(h, g_swerr, h->grow(&h->sFids, &h->capFids, (size_t)S));
+    QC_SIDE_HIP(h, g_swerr, hipMemcpyAsync(h->sZ, Z, (size_t)h->Zlen * 8, hipMemcpyHostToDevice, h->stream));
+    QC_SIDE_HIP(h, g_swerr, hipMemcpyAsync(h->sInit, init, (size_t)h->ns * 8, hipMemcpyHostToDevice, h->stream));
+    if (p) QC_SIDE_HIP(h, g_swerr, hipMemcpyAsync(h->sTheta, theta, (size_t)S * p * 8, hipMemcpyHostToDevice, h->stream));
+    if (use_scale) QC_SIDE_HIP(h, g_swerr, hipMemcpyAsync(h->sScale, scale, (size_t)S * m * 8, hipMemcpyHostToDevice, h->stream));
     int rc = qc_sweep_eval_dev(h, h->sZ, h->sInit, S, p ? h->sTheta : nullptr, use_scale ? h->sScale : nullptr, finals ? h->sFinals : nullptr,
                                fids ? h->sFids : nullptr, h->stream);
     if (rc) return rc;
-    if (finals) QCS_HIP(h, hipMemcpyAsync(finals, h->sFinals, (size_t)S * h->ns * 8, hipMemcpyDeviceToHost, h->stream));
-    if (fids) QCS_HIP(h, hipMemcpyAsync(fids, h->sFids, (size_t)S * 8, hipMemcpyDeviceToHost, h->stream));
-    QCS_HIP(h, hipStreamSynchronize(h->stream));
+    if (finals) QC_SIDE_HIP(h, g_swerr, hipMemcpyAsync(finals, h->sFinals, (size_t)S * h->ns * 8, hipMemcpyDeviceToHost, h->stream));
+    if (fids) QC_SIDE_HIP(h, g_swerr, hipMemcpyAsync(fids, h->sFids, (size_t)S * 8, hipMemcpyDeviceToHost, h->stream));
+    QC_SIDE_HIP(h, g_swerr, hipStreamSynchronize(h->stream));
     return QC_OK;
 }

@@ -21,11 +21,11 @@
 #include <string>
 #include <vector>
 
-#include "qc_internal.h"
+#include "qc_side.h"
 
-struct qc_terms {
+struct qc_terms : qc_side {
     qc_terms_desc d{};
-    int n_reg = 0, device = 0, cross = 0;
+    int n_reg = 0, cross = 0;
     int64_t hess_per_knot = 0;
     int* dslot = nullptr;          // zdim: index into the regulariser list or -1
     double* dR = nullptr;          // n_reg
@@ -39,8 +39,6 @@ struct qc_terms {
     std::vector<int> s_index, p_a, p_b, l_index;
     int* dxi = nullptr;            // [sslot zdim | lslot zdim | adj_ptr zdim+1 | adj_idx 2 n_pair | pair_a | pair_b]
     double* dxd = nullptr;         // [smooth_R | lin_w | adj_Q 2 n_pair | pair_Q]
-    hipStream_t stream = nullptr;
-    std::string err;
 };
 
 namespace {
@@ -190,19 +188,9 @@ __global__ __launch_bounds__(256) void qc_terms_sum_kernel(const double* __restr
 }
 
 thread_local std::string g_terr;
-int tfail(qc_terms* h, int code, const std::string& msg) {
-    if (h) h->err = msg;
-    g_terr = msg;
-    return code;
-}
+int tfail(qc_side* h, int code, const std::string& msg) { return qc_side_fail(h, &g_terr, code, msg); }
 
 }  // namespace
-
-#define QCT_HIP(h, call)                                                                              \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) return tfail(h, QC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 extern "C" const char* qc_terms_last_error(const qc_terms* h) { return h ? h->err.c_str() : g_terr.c_str(); }
 
@@ -353,10 +341,8 @@ extern "C" int qc_terms_create_ext(const qc_terms_desc* d, const qc_terms_ext* x
     int rc = ext_validate(d, x, &cross, &cross_p);
     if (rc) return rc;
     if (ext_empty(x)) x = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tfail(nullptr, QC_ERR_NO_DEVICE, "qc_terms_create: no HIP device visible");
-    if (d->device < 0 || d->device >= ndev) return tfail(nullptr, QC_ERR_NO_DEVICE, "qc_terms_create: device ordinal out of range");
-    qc_terms* h = new qc_terms();
+    if ((rc = qc_side_check_device(d->device, "qc_terms_create", &g_terr))) return rc;
+    qc_side_new<qc_terms> h(new qc_terms());
     h->d = *d;
     h->n_reg = d->n_reg;
     h->device = d->device;
@@ -412,51 +398,29 @@ extern "C" int qc_terms_create_ext(const qc_terms_desc* d, const qc_terms_ext* x
     h->d.reg_baseline = nullptr;
     std::vector<int> slot(d->zdim, -1);
     for (int k = 0; k < d->n_reg; ++k) slot[d->reg_index[k]] = k;
-    auto bail = [&](hipError_t e, const char* what) {
-        std::string m = std::string(what) + ": " + hipGetErrorString(e);
-        qc_terms_destroy(h);
-        return tfail(nullptr, QC_ERR_HIP, m);
-    };
-    hipError_t e;
     const size_t Zlen = (size_t)d->T * d->zdim + (size_t)d->global_dim;
-    const size_t nh = (size_t)h->hess_nnz;
-    if ((e = hipSetDevice(d->device)) != hipSuccess) return bail(e, "hipSetDevice");
-    if (!xi.empty()) {
-        if ((e = hipMalloc((void**)&h->dxi, xi.size() * 4)) != hipSuccess) return bail(e, "hipMalloc");
-        if ((e = hipMemcpy(h->dxi, xi.data(), xi.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-    }
-    if (!xd.empty()) {
-        if ((e = hipMalloc((void**)&h->dxd, xd.size() * 8)) != hipSuccess) return bail(e, "hipMalloc");
-        if ((e = hipMemcpy(h->dxd, xd.data(), xd.size() * 8, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-    }
-    if ((e = hipMalloc((void**)&h->dslot, slot.size() * 4)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMemcpy(h->dslot, slot.data(), slot.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
+    qc_device_guard guard(d->device);
+    QC_SIDE_HIP(nullptr, g_terr, guard.err);
+    if (!xi.empty()) QC_SIDE_HIP(nullptr, g_terr, h->alloc(&h->dxi, xi.size(), xi.data()));
+    if (!xd.empty()) QC_SIDE_HIP(nullptr, g_terr, h->alloc(&h->dxd, xd.size(), xd.data()));
+    QC_SIDE_HIP(nullptr, g_terr, h->alloc(&h->dslot, slot.size(), slot.data()));
     if (d->n_reg > 0) {
-        if ((e = hipMalloc((void**)&h->dR, (size_t)d->n_reg * 8)) != hipSuccess) return bail(e, "hipMalloc");
-        if ((e = hipMemcpy(h->dR, d->reg_R, (size_t)d->n_reg * 8, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-        if (d->reg_baseline) {
-            const size_t nb = (size_t)d->n_reg * d->T * 8;
-            if ((e = hipMalloc((void**)&h->dbase, nb)) != hipSuccess) return bail(e, "hipMalloc");
-            if ((e = hipMemcpy(h->dbase, d->reg_baseline, nb, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy");
-        }
+        QC_SIDE_HIP(nullptr, g_terr, h->alloc(&h->dR, (size_t)d->n_reg, d->reg_R));
+        if (d->reg_baseline) QC_SIDE_HIP(nullptr, g_terr, h->alloc(&h->dbase, (size_t)d->n_reg * d->T, d->reg_baseline));
     }
-    if ((e = hipMalloc((void**)&h->dpart, (size_t)d->T * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc((void**)&h->dZ, Zlen * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc((void**)&h->dJ, 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc((void**)&h->dgrad, Zlen * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if (nh && (e = hipMalloc((void**)&h->dhess, nh * 8)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
-    *out = h;
+    QC_SIDE_HIP(nullptr, g_terr, h->alloc(&h->dpart, (size_t)d->T));
+    QC_SIDE_HIP(nullptr, g_terr, h->alloc(&h->dZ, Zlen));
+    QC_SIDE_HIP(nullptr, g_terr, h->alloc(&h->dJ, 1));
+    QC_SIDE_HIP(nullptr, g_terr, h->alloc(&h->dgrad, Zlen));
+    if (h->hess_nnz) QC_SIDE_HIP(nullptr, g_terr, h->alloc(&h->dhess, (size_t)h->hess_nnz));
+    QC_SIDE_HIP(nullptr, g_terr, h->open_stream());
+    *out = h.release();
     return QC_OK;
 }
 
 extern "C" void qc_terms_destroy(qc_terms* h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    if (h->dslot) (void)hipFree(h->dslot);
-    if (h->dxi) (void)hipFree(h->dxi);
-    for (double* p : {h->dxd, h->dR, h->dbase, h->dpart, h->dZ, h->dJ, h->dgrad, h->dhess}) if (p) (void)hipFree(p);
+    h->release_device();
     delete h;
 }
 
@@ -488,6 +452,8 @@ extern "C" int qc_terms_hess_structure(const qc_terms* h, int64_t* rows, int64_t
 extern "C" int qc_terms_eval_dev(qc_terms* h, const double* dZ, double* dJ, double* dgrad, double* dhvals, void* stream) {
     if (!h) return tfail(nullptr, QC_ERR_INVALID, "qc_terms_eval_dev: NULL handle");
     if (!dZ || !dJ) return tfail(h, QC_ERR_INVALID, "qc_terms_eval_dev: NULL buffer");
+    qc_device_guard guard(h->device);
+    QC_SIDE_HIP(h, g_terr, guard.err);
     TermsParams P;
     P.T = h->d.T;
     P.zdim = h->d.zdim;
@@ -540,15 +506,16 @@ extern "C" int qc_terms_eval(qc_terms* h, const double* Z, double* J, double* gr
     if (!Z) return tfail(h, QC_ERR_INVALID, "qc_terms_eval: NULL input");
     const size_t Zlen = (size_t)h->d.T * h->d.zdim + (size_t)h->d.global_dim;
     const size_t nh = (size_t)h->hess_nnz;
-    QCT_HIP(h, hipSetDevice(h->device));
-    QCT_HIP(h, hipMemcpyAsync(h->dZ, Z, Zlen * 8, hipMemcpyHostToDevice, h->stream));
+    qc_device_guard guard(h->device);
+    QC_SIDE_HIP(h, g_terr, guard.err);
+    QC_SIDE_HIP(h, g_terr, hipMemcpyAsync(h->dZ, Z, Zlen * 8, hipMemcpyHostToDevice, h->stream));
     int rc = qc_terms_eval_dev(h, h->dZ, h->dJ, grad ? h->dgrad : nullptr, hvals ? h->dhess : nullptr, h->stream);
     if (rc) return rc;
     double j = 0.0;
-    QCT_HIP(h, hipMemcpyAsync(&j, h->dJ, 8, hipMemcpyDeviceToHost, h->stream));
-    if (grad) QCT_HIP(h, hipMemcpyAsync(grad, h->dgrad, Zlen * 8, hipMemcpyDeviceToHost, h->stream));
-    if (hvals && nh) QCT_HIP(h, hipMemcpyAsync(hvals, h->dhess, nh * 8, hipMemcpyDeviceToHost, h->stream));
-    QCT_HIP(h, hipStreamSynchronize(h->stream));
+    QC_SIDE_HIP(h, g_terr, hipMemcpyAsync(&j, h->dJ, 8, hipMemcpyDeviceToHost, h->stream));
+    if (grad) QC_SIDE_HIP(h, g_terr, hipMemcpyAsync(grad, h->dgrad, Zlen * 8, hipMemcpyDeviceToHost, h->stream));
+    if (hvals && nh) QC_SIDE_HIP(h, g_terr, hipMemcpyAsync(hvals, h->dhess, nh * 8, hipMemcpyDeviceToHost, h->stream));
+    QC_SIDE_HIP(h, g_terr, hipStreamSynchronize(h->stream));
     if (J) *J = j;
     return QC_OK;
 }

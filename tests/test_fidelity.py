@@ -430,3 +430,98 @@ def test_fidelity_kernel_at_64_levels(qc, oracle):
         blk = (np.outer(gr[:j1], gr[j0:j1]) + np.outer(gi[:j1], gi[j0:j1])) / (n * n * Fr) - np.outer(grad[:j1], grad[j0:j1]) / Fr
         for j in range(j0, j1):
             np.testing.assert_allclose(H[j * (j + 1) // 2:j * (j + 1) // 2 + j + 1], blk[:j + 1, j - j0], rtol=1e-10, atol=1e-12)
+
+
+# ---- the constants g_r, g_i, n behind every fidelity handle (qc_fidelity_goal, csrc/qc_side.h), on the CPU ----
+GOAL_CASES = [("unitary", 0, 3, ()), ("unitary-sub", 0, 3, (2, 0)), ("ket", 1, 3, ()), ("density", 2, 4, ())]     # (id, kind, N, subspace)
+
+
+@pytest.fixture(scope="module")
+def goal_driver(qc, tmp_path_factory):
+    import os
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "quantumcollocation.jl_amd", "csrc")
+    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("needs hipcc")
+    exe = str(tmp_path_factory.mktemp("fid_goal") / "fid_goal_test")
+    cmd = [hipcc, "-O1", "-std=c++17", "--offload-arch=gfx950", "-x", "hip", "-I" + csrc, "-I" + os.path.join(root, "include"),
+           os.path.join(root, "tests", "fid_goal_test.cpp"), "-o", exe, "-L" + csrc, "-lqcolloc_hip", "-Wl,-rpath," + csrc]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+    def run(kind, N, goal, sub):
+        path = os.path.join(os.path.dirname(exe), "goal.txt")
+        np.savetxt(path, goal, fmt="%.17g")
+        r = subprocess.run([exe, str(kind), str(N), path] + [str(a) for a in sub], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0, r.stderr
+        rows = r.stdout.split("\n", 1)
+        g = np.loadtxt(rows[1].splitlines()).reshape(-1, 2)
+        return int(rows[0]), g[:, 0], g[:, 1]
+    return run
+
+
+@pytest.mark.parametrize("name,kind,N,sub", GOAL_CASES, ids=[c[0] for c in GOAL_CASES])
+def test_fidelity_goal_vectors_give_the_overlap(goal_driver, name, kind, N, sub):
+    """g_r.x + i g_i.x is the complex overlap of the definition (header of qc_fidelity.hip), formed here in numpy complex arithmetic from
+    the iso-vec: tr(G_sub' U_sub), <g|psi>, psi' rho psi over the Hermitian part of rho.  Bound: the rounding of a dot product of at most
+    18 terms, 1e-14 ||g|| ||x||."""
+    rng = np.random.default_rng(1234)
+    L = {0: N, 1: N, 2: 2}[kind]                                  # levels (the density operator's N is levels^2)
+    shape = (L, L) if kind == 0 else (L,)
+    G = rng.standard_normal(shape) + 1j * rng.standard_normal(shape)
+
+    def iso(M):                                                   # columns [Re; Im] one after the other (a ket: one column)
+        M = M.reshape(L, -1)
+        return np.concatenate([np.concatenate([M[:, j].real, M[:, j].imag]) for j in range(M.shape[1])])
+
+    n, gr, gi = goal_driver(kind, N, iso(G), sub)
+    slen = 2 * N * N if kind == 0 else 2 * N
+    assert gr.size == slen and gi.size == slen
+    assert n == ((len(sub) or N) if kind == 0 else 1)
+    lev = list(sub) if sub else list(range(L))
+    for _ in range(5):
+        x = rng.standard_normal(slen)
+        if kind == 0:
+            X = x.reshape(N, 2 * N)
+            U = (X[:, :N] + 1j * X[:, N:]).T                      # U[:, j] = column j
+            t = np.trace(G[np.ix_(lev, lev)].conj().T @ U[np.ix_(lev, lev)])
+        elif kind == 1:
+            t = np.vdot(G, x[:N] + 1j * x[N:])
+        else:
+            rho = x[:N].reshape(L, L, order="F") + 1j * x[N:].reshape(L, L, order="F")
+            t = np.vdot(G, 0.5 * (rho + rho.conj().T) @ G)
+        got = gr @ x + 1j * (gi @ x)
+        assert abs(got - t) <= 1e-14 * np.sqrt(gr @ gr + gi @ gi) * np.linalg.norm(x), (name, got, t)
+
+
+@pytest.mark.gpu
+def test_fidelity_one_handle_alternating_outputs_and_many_handles(qc, oracle):
+    """One handle serves calls with and without gradient / Hessian in turn, with the bits of the first call and of a fresh handle; the
+    last of 20 handles created and destroyed in a row still evaluates (each owns and releases its own device memory)."""
+    from qcolloc_amd.objectives import _Fidelity
+    same = lambda a, b: all((x is None and y is None) or np.array_equal(np.asarray(x), np.asarray(y)) for x, y in zip(a, b))
+    N = 2
+    rng = np.random.default_rng(77)
+    goal = oracle.operator_to_iso_vec(rand_unitary(N, rng))
+    u = oracle.operator_to_iso_vec(rand_unitary(N, rng)) + 0.05 * rng.standard_normal(2 * N * N)
+    f = _Fidelity(goal)
+    full = f.eval(u)
+    bare = f.eval(u, grad=False, hess=False)
+    assert bare[:2] == full[:2] and bare[2] is None and bare[3] is None
+    assert same(f.eval(u), full)
+    fresh = _Fidelity(goal)
+    assert same(fresh.eval(u, grad=False, hess=False), bare) and same(fresh.eval(u), full)
+    fresh.close()
+    f.close()
+    for k in range(20):
+        f = _Fidelity(goal)
+        if k < 19:
+            f.close()
+    assert same(f.eval(u), full)
+    Fr, gr, Hr = oracle.fidelity_value_grad_hess(u, goal, None)
+    assert abs(full[0] - Fr) < 1e-13
+    np.testing.assert_allclose(full[2], gr, rtol=1e-11, atol=1e-13)
+    f.close()

@@ -545,3 +545,29 @@ def test_gpu_hessian_above_the_dense_check(qc, N, sub, T, K, free, state_first, 
         obj.close()
         Hv = None
         gc.collect()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("T", [1, 2])
+def test_hessian_staging_arrives_with_the_first_call_that_asks(qc, T):
+    """A handle with the exact Hessian, host-buffer calls without Hessian values, then with, then without: the staging of the values is
+    allocated by the second call.  Every result carries the bits of fresh handles' (one whose first call asks for the values, one that
+    never does)."""
+    rng = np.random.default_rng(31 + T)
+    s, Z = _spec_and_Z(rng, T, 2, None, True)
+    traj = _traj(qc, s, Z)
+    make = lambda: qc.UnitaryRobustnessObjective(traj, H_error=s.H, eval_hessian=True)
+    obj, with_h, without_h = make(), make(), make()
+    try:
+        L0, g0, _ = without_h._eval(Z, True, False)
+        L1, g1, H1 = with_h._eval(Z, True, True)
+        assert L0 == L1 and np.array_equal(g0, g1)
+        for want_h in (False, True, False):
+            L, g, H = obj._eval(Z, True, want_h)
+            assert L == L0 and np.array_equal(g, g0)
+            assert (H is None) if not want_h else np.array_equal(H, H1)
+        assert abs(L0 - rr.loss(Z, s)) <= 1e-12 * abs(rr.loss(Z, s))
+        assert np.abs(H1 - rr.packed_upper(rr.hessian(Z, s))).max() <= 1e-10 * np.abs(H1).max()
+    finally:
+        for o in (obj, with_h, without_h):
+            o.close()

@@ -559,3 +559,36 @@ def test_sweep_non_finite_input(qc, N):
     np.testing.assert_array_equal(again[0], good[0])
     np.testing.assert_array_equal(again[1], good[1])
     sw.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N,m,T,sizes", [(2, 2, 5, (1, 7, 3)), (9, 1, 3, (1, 3))], ids=["mfma16-sweep", "rollout-per-sample"])
+def test_sweep_scratch_grows_and_is_reused(qc, N, m, T, sizes):
+    """One handle serves S = 1, then a larger S, then (MFMA form) a smaller one, through the host-buffer and the device entry point: the
+    scratch behind them (the chunk totals or the per-sample finals, and the staging of theta, scale, finals, fidelities) is freed and
+    taken afresh when S grows, and reused when it shrinks.  Every result carries the bits a fresh handle returns at that S."""
+    rng = np.random.default_rng(100 + N)
+    sys_ = qc.QuantumSystem(_herm(rng, N), [_herm(rng, N, 0.3) for _ in range(m)])
+    perts = [_herm(rng, N)]
+    goal = ref.operator_to_iso_vec(_unitary(rng, N))
+    make = lambda: qc.RolloutSweep(sys_, perts, T, goal=goal, fid_kind="unitary")
+    sw = make()
+    assert sw.kernel_name == ("mfma16-sweep" if 2 * N <= 16 else "rollout-per-sample")
+    Z = sw.pack(rng.uniform(-1, 1, (m, T)), rng.uniform(0.1, 0.3, T))
+    init = ref.operator_to_iso_vec(_unitary(rng, N))
+    dev = torch.device("cuda:0")
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    for S in sizes:
+        theta, scale = rng.uniform(-0.3, 0.3, (S, 1)), rng.uniform(0.9, 1.1, (S, m))
+        fresh = make()
+        want = fresh.eval(Z, init, theta, scale)
+        fresh.close()
+        got = sw.eval(Z, init, theta, scale)
+        np.testing.assert_array_equal(got[0], want[0])
+        np.testing.assert_array_equal(got[1], want[1])
+        dfin, dfid = torch.full((S, sw.ns), -7.0, dtype=torch.float64, device=dev), torch.full((S,), -7.0, dtype=torch.float64, device=dev)
+        sw.eval_device(t(Z), t(init), t(theta), t(scale), dfin, dfid)
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(dfin.cpu().numpy().T, want[0])
+        np.testing.assert_array_equal(dfid.cpu().numpy(), want[1])
+    sw.close()

@@ -163,3 +163,30 @@ def test_terms_device_entry_and_minimum_time_only(qc, oracle):
     Z[3] = np.nan
     assert np.isfinite(obj.grad_L(Z)).all()
     obj.close()
+
+
+def _same(a, b):
+    return all((x is None and y is None) or np.array_equal(np.asarray(x), np.asarray(y)) for x, y in zip(a, b))
+
+
+@pytest.mark.gpu
+def test_terms_one_handle_alternating_outputs_and_many_handles(qc, oracle):
+    """One handle serves calls with and without gradient / Hessian in turn, with the bits of the first call and of a fresh handle; the
+    last of 20 handles created and destroyed in a row still evaluates (each owns and releases its own device memory)."""
+    traj, spec, tm, Z = make_terms(oracle, qc, T=5, baseline=True, D=1.0)
+    obj = qc.TrajectoryObjective(spec, traj)
+    full = obj._eval(Z, True, True)
+    bare = obj._eval(Z, False, False)
+    assert bare[0] == full[0] and bare[1] is None and bare[2] is None
+    assert _same(obj._eval(Z, True, True), full)
+    fresh = qc.TrajectoryObjective(spec, traj)
+    assert _same(fresh._eval(Z, False, False), bare) and _same(fresh._eval(Z, True, True), full)
+    fresh.close()
+    obj.close()
+    for k in range(20):
+        obj = qc.TrajectoryObjective(spec, traj)
+        if k < 19:
+            obj.close()
+    assert _same(obj._eval(Z, True, True), full)
+    assert abs(full[0] - oracle.terms_value(tm, Z)) <= 1e-12 * max(1.0, abs(oracle.terms_value(tm, Z)))
+    obj.close()

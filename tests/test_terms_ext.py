@@ -315,3 +315,32 @@ def test_regulariser_only_objective_is_unchanged(qc):
     np.testing.assert_allclose(g, ref.grad(only, Z), rtol=1e-13, atol=1e-15)
     np.testing.assert_allclose(H, ref.hess_values(only, Z), rtol=1e-13, atol=1e-15)
     obj.close()
+
+
+@pytest.mark.gpu
+def test_one_handle_alternating_outputs_and_many_handles(qc):
+    """The extension handle (two more device tables) through the same use as the plain one: calls with and without gradient / Hessian
+    in turn return the bits of the first call and of a fresh handle; the last of 20 handles created and destroyed in a row (the
+    smallest shape, T = 1) still evaluates."""
+    same = lambda a, b: all((x is None and y is None) or np.array_equal(np.asarray(x), np.asarray(y)) for x, y in zip(a, b))
+    traj, spec, tm, Z = make_case(qc, T=2, global_dim=2, baseline=True, seed=9)
+    obj = qc.TrajectoryObjective(spec, traj)
+    assert obj.has_ext
+    full = obj._eval(Z, True, True)
+    bare = obj._eval(Z, False, False)
+    assert bare[0] == full[0] and bare[1] is None and bare[2] is None
+    assert same(obj._eval(Z, True, True), full)
+    fresh = qc.TrajectoryObjective(spec, traj)
+    assert same(fresh._eval(Z, False, False), bare) and same(fresh._eval(Z, True, True), full)
+    fresh.close()
+    obj.close()
+    traj, spec, tm, Z = make_case(qc, T=1, seed=8)
+    for k in range(20):
+        obj = qc.TrajectoryObjective(spec, traj)
+        if k < 19:
+            obj.close()
+    J, g, H = obj._eval(Z, True, True)
+    assert abs(J - ref.value(tm, Z)) <= 1e-12 * max(1.0, abs(ref.value(tm, Z)))
+    np.testing.assert_allclose(g, ref.grad(tm, Z), rtol=1e-12, atol=1e-13)
+    np.testing.assert_allclose(H, ref.hess_values(tm, Z), rtol=1e-12, atol=1e-13)
+    obj.close()
