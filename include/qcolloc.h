@@ -25,6 +25,7 @@
  *   dynamics.F(Z.datavec)               (:45)            qc_eval_F        / qc_eval_F_dev
  *   dynamics.dF(Z.datavec)              (:46)            qc_eval_jac      / qc_eval_F_jac(_dev)
  *   dynamics.dF_structure               (:46)            qc_jac_structure
+ *   dynamics.dF(Z) * v, dynamics.dF(Z)' * lam            qc_eval_jvp / qc_eval_vjp (_dev, _dev_multi): matrix-free
  *   dynamics.mu_d2F(Z.datavec, mu)      (:52)            qc_eval_hess     / qc_eval_hess_dev
  *   dynamics.mu_d2F_structure           (:52)            qc_hess_structure
  *   shapes (Z.dims.states*(Z.T-1), Z.dim*Z.T+Z.global_dim)  (:44,48)   qc_dims
@@ -256,7 +257,10 @@ int qc_dims(const qc_handle* h, qc_dims_t* out);
  * "lds-gws-hess"; exponential integrator: "mfma16-exp-hess", "mfma16-exp-hess-gather"
  * (drive generators with one entry per row: Pauli strings), "mfma32-exp-hess" / "mfma32-exp-hess-gather", "lds-exp-hess", "lds-gws-exp-hess");
  * which = 2: qc_eval_F_jac_hess_dev ("mfma16-pade4-fused-gather" / "mfma16-pade4-fused", "mfma32-pade4-fused-ell", or
- * "two-launches"). */
+ * "two-launches");
+ * which = 3: dF v ("mfma16-pade4-jvp": the fused matrix-free kernel of the order-4 Pade integrator at 2N <= 16, up to 8 state columns
+ * and 8 drives; else "generic-jvp"), which = 4: dF' lam ("generic-vjp" on every handle) -- generic: the handle's own dF launch into a
+ * scratch of the handle, then a product kernel. */
 const char* qc_kernel_name(const qc_handle* h, int32_t which);
 int qc_jac_structure(const qc_handle* h, int64_t* rows, int64_t* cols, int one_based);
 int qc_hess_structure(const qc_handle* h, int64_t* rows, int64_t* cols, int one_based);
@@ -306,6 +310,26 @@ int qc_eval_hess_dev(qc_handle* h, const double* dZ, const double* dmu, double* 
  * "mfma16-pade4-fused" -- order-4 Pade, a unitary on 8 levels, Hermitian Hamiltonians, up to 6 drives: BASELINE configs 3 / 4), else
  * the two launches of qc_eval_F_jac_dev and qc_eval_hess_dev on `stream`; the values are bit-identical either way.  dF may be NULL. */
 int qc_eval_F_jac_hess_dev(qc_handle* h, const double* dZ, const double* dmu, double* dF, double* dvals, double* dhvals, void* stream);
+
+/* Matrix-free Jacobian products at Z: what a consumer that never needs the VALUES of dF asks for (augmented-Lagrangian and first-order
+ * methods: grad(lam'F + rho/2 |F|^2) = dF'(lam + rho F); Krylov solves of the KKT system; adjoint checks; MOI's
+ * eval_constraint_jacobian_product / _transpose_product).  Two vectors of Z_len and F_len doubles move instead of jac_nnz values.
+ * Repeated calls return the same bits: no floating-point atomics, every output entry has one writer and a fixed summation order.
+ * The first call on a handle that takes the generic path (qc_kernel_name(h, 3 / 4)) allocates its scratch and tables (it synchronises
+ * the device and cannot be captured in a graph; call once first); one evaluation in flight per handle, as everywhere.
+ * qc_desc.jac_block_order cannot change a product.  Handles from qc_create_multi: QC_ERR_UNSUPPORTED (use the shard handles). */
+/* y = dF(Z) v.   v: Z_len, y: F_len (the handle's rows; rows no integrator owns -- QC_ROWS_BY_COMPONENT -- are not written, as by F) */
+int qc_eval_jvp_dev(qc_handle* h, const double* dZ, const double* dv, double* dy, void* stream);
+/* w = dF(Z)' lam. lam: F_len, w: Z_len, EVERY entry written: variables the handle's intervals do not touch (the last knot's
+ * controls and timestep, components no integrator reads, the global_dim tail, knots outside a shard's range) are exactly 0.0 */
+int qc_eval_vjp_dev(qc_handle* h, const double* dZ, const double* dlam, double* dw, void* stream);
+/* host buffers; honour qc_set_new_x like their siblings (rows of y that no integrator owns are delivered as 0) */
+int qc_eval_jvp(qc_handle* h, const double* Z, const double* v, double* y);
+int qc_eval_vjp(qc_handle* h, const double* Z, const double* lam, double* w);
+/* integrator lists on one device (sampling, direct sum: members with qc_desc placement over one merged trajectory):
+ * y rows member by member; w = the SUM over members, in member order (the first member overwrites, the others add) */
+int qc_eval_jvp_dev_multi(qc_handle* const* hs, int32_t count, const double* dZ, const double* dv, double* dy, void* stream);
+int qc_eval_vjp_dev_multi(qc_handle* const* hs, int32_t count, const double* dZ, const double* dlam, double* dw, void* stream);
 
 /* Several handles over the same trajectory in ONE launch: the K unitary integrators of a `UnitarySamplingProblem`
  * (reference unitary_sampling_problem.jl:134-155), each created with its slot of the shared per-interval blocks

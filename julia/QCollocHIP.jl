@@ -544,6 +544,27 @@ handle in between moves it -- and goes back to `set_new_x!(dyn, true)` right aft
 """
 knot_generation(dyn::HIPDynamics) = ccall((:qc_knot_generation, LIB[]), Int64, (Ptr{Cvoid},), dyn.handle)
 
+"""
+Matrix-free Jacobian products (`qc_eval_jvp` / `qc_eval_vjp`): `dF_mul!(y, dyn, Z⃗, v)` writes `y = ∂F(Z⃗) v` (length `dyn.dims.F_len`),
+`dFt_mul!(w, dyn, Z⃗, λ)` writes `w = ∂F(Z⃗)ᵀ λ` (length `dyn.dims.Z_len`, every entry written) -- the counterparts of MOI's
+`eval_constraint_jacobian_product` / `eval_constraint_jacobian_transpose_product` for the dynamics rows, without the values of `∂F`.
+Both honour `set_new_x!`.  One handle on one device (a `dynamics_list` goes through the library's `_dev_multi` entries instead).
+"""
+function dF_mul!(y::Vector{Float64}, dyn::HIPDynamics, Z⃗::Vector{Float64}, v::Vector{Float64})
+    length(dyn.handles) == 1 || error("dF_mul!: one handle on one device only")
+    length(y) == dyn.dims.F_len || error("dF_mul!: y has length $(length(y)), expected $(dyn.dims.F_len)")
+    length(v) == dyn.dims.Z_len && length(Z⃗) == dyn.dims.Z_len || error("dF_mul!: Z⃗ and v must have length $(dyn.dims.Z_len)")
+    GC.@preserve Z⃗ v y check(ccall((:qc_eval_jvp, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), dyn.handle, Z⃗, v, y), dyn.handle)
+    return y
+end
+function dFt_mul!(w::Vector{Float64}, dyn::HIPDynamics, Z⃗::Vector{Float64}, λ::Vector{Float64})
+    length(dyn.handles) == 1 || error("dFt_mul!: one handle on one device only")
+    length(w) == dyn.dims.Z_len && length(Z⃗) == dyn.dims.Z_len || error("dFt_mul!: Z⃗ and w must have length $(dyn.dims.Z_len)")
+    length(λ) == dyn.dims.F_len || error("dFt_mul!: λ has length $(length(λ)), expected $(dyn.dims.F_len)")
+    GC.@preserve Z⃗ λ w check(ccall((:qc_eval_vjp, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), dyn.handle, Z⃗, λ, w), dyn.handle)
+    return w
+end
+
 # ---------------------------------------------------------------------------------------------------------------
 #  Objective terms and rollouts (SURVEY.md 8f): the same `ccall` pattern over qc_terms_* / qc_fidelity_* / qc_rollout
 # ---------------------------------------------------------------------------------------------------------------

@@ -417,6 +417,7 @@ int qc_blueprint_build(const qc_desc* d, qc_blueprint* B, std::string* err) {
         }
         P.antisym = anti && !sw.no_antisym ? 1 : 0;      // (QC_NO_ANTISYM=1, diagnostic: force the general path)
     }
+    B->cls.product_mfma = !sw.no_product_mfma;      // (QC_NO_PRODUCT_MFMA=1: the Jacobian products' generic path, for A/B runs and the tests)
     P.head = sw.no_head ? 0 : 1;      // (QC_NO_HEAD=1, diagnostic: the run-time form of the 2N = 16 F + dF kernel)
     // Outputs are written once and never re-read by the kernel: non-temporal stores measured fastest on
     // MI355X (profiles/README.md: plain 14.4, sc1 12.8, nt 11.9 us per config-3 evaluation).
@@ -559,7 +560,8 @@ extern "C" void qc_destroy(qc_handle* h) {
     // both streams idle before any pinned or device block is freed (a failed call may have left chunk kernels in flight on either)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->stream2) (void)hipStreamSynchronize(h->stream2);
-    double* bufs[] = {h->dG, h->dGx, h->dZ, h->dF, h->dJ, h->dMu, h->dH, (double*)h->dStamps, h->dRE, h->dRQ, h->dRS, h->dRinit, h->dRout, h->dRZ, h->dWs, h->dHs};
+    double* bufs[] = {h->dG, h->dGx, h->dZ, h->dF, h->dJ, h->dMu, h->dH, (double*)h->dStamps, h->dRE, h->dRQ, h->dRS, h->dRinit, h->dRout, h->dRZ, h->dWs, h->dHs,
+                      h->dPvals, (double*)h->dPtab, h->dPx, h->dPy, h->dPl};
     if (h->hJc) (void)hipHostFree(h->hJc);
     if (h->hFc) (void)hipHostFree(h->hFc);
     if (h->hZ) (void)hipHostFree(h->hZ);
@@ -597,6 +599,8 @@ extern "C" const char* qc_kernel_name(const qc_handle* h, int32_t which) {
     if (!h) return "none";
     if (!h->shards.empty()) return qc_kernel_name(h->shards[0], which);
     const QcPlan& p = h->plan;
+    if (which == 3) return qc_jvp_kernel_name(p.jvp);
+    if (which == 4) return qc_vjp_kernel_name(p.vjp);
     return which == 0 ? qc_jac_kernel_name(p.jac) : (which == 2 ? qc_fused_kernel_name(p.fused) : qc_hess_kernel_name(p.hess));
 }
 

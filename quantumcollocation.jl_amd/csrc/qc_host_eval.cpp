@@ -1422,6 +1422,50 @@ extern "C" int qc_eval_hess(qc_handle* h, const double* Z, const double* mu, dou
     return multi_run(h, [&](int i) { return hess_host(h->shards[i], Z, mu, hvals + h->shard_H_off[i], n); });
 }
 
+// Jacobian products with host buffers: the knots as in every host-buffer call (qc_set_new_x is honoured), the vector up, the
+// device-resident product on the handle's stream, the result down.  Rows of y that no integrator owns (QC_ROWS_BY_COMPONENT) are
+// delivered as 0: the staging vector is zeroed when it is made and no kernel writes them.
+extern "C" int qc_eval_jvp(qc_handle* h, const double* Z, const double* v, double* y) {
+    if (!h) return fail(nullptr, QC_ERR_INVALID, "qc_eval_jvp: NULL handle");
+    if (is_multi(h)) return fail(&h->err, QC_ERR_UNSUPPORTED, "qc_eval_jvp: the Jacobian products do not serve multi-device handles (qc_create_multi)");
+    if (!Z || !v || !y) return fail(&h->err, QC_ERR_INVALID, "qc_eval_jvp: NULL buffer");
+    const QcParams& P = h->prm;
+    if (P.n_int == 0) return QC_OK;
+    qc_device_guard guard(h->device);
+    QC_HIP(h, guard.err);
+    int rc;
+    if ((rc = drain_if_needed(h)) || (rc = drain_leader_if_needed(h))) return rc;
+    if ((rc = ensure(h, &h->dPx, (size_t)h->dims.Z_len)) || (rc = ensure_zeroed(h, &h->dPy, (size_t)h->dims.F_len))) return rc;
+    if ((rc = upload_knots(h, Z))) return rc;
+    const size_t o = (size_t)P.t_begin * P.zdim, n = (size_t)(P.n_int + 1) * P.zdim;      // the knots this handle's intervals read
+    QC_HIP(h, hipMemcpyAsync(h->dPx + o, v + o, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if ((rc = qc_product_jvp_dev(h, "qc_eval_jvp", h->dZ, h->dPx, h->dPy, h->stream))) return rc;
+    QC_HIP(h, hipMemcpyAsync(y, h->dPy, (size_t)h->dims.F_len * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QC_HIP(h, hipEventRecord(h->ev_done, h->stream));
+    return wait_done(h, 1);
+}
+
+extern "C" int qc_eval_vjp(qc_handle* h, const double* Z, const double* lam, double* w) {
+    if (!h) return fail(nullptr, QC_ERR_INVALID, "qc_eval_vjp: NULL handle");
+    if (is_multi(h)) return fail(&h->err, QC_ERR_UNSUPPORTED, "qc_eval_vjp: the Jacobian products do not serve multi-device handles (qc_create_multi)");
+    if (!Z || !lam || !w) return fail(&h->err, QC_ERR_INVALID, "qc_eval_vjp: NULL buffer");
+    const QcParams& P = h->prm;
+    qc_device_guard guard(h->device);
+    QC_HIP(h, guard.err);
+    int rc;
+    if ((rc = drain_if_needed(h)) || (rc = drain_leader_if_needed(h))) return rc;
+    if ((rc = ensure(h, &h->dPx, (size_t)h->dims.Z_len)) || (rc = ensure(h, &h->dPl, (size_t)std::max<int64_t>(1, h->dims.F_len)))) return rc;
+    if ((rc = ensure(h, &h->dZ, (size_t)h->dims.Z_len))) return rc;
+    if (P.n_int > 0) {
+        if ((rc = upload_knots(h, Z))) return rc;
+        QC_HIP(h, hipMemcpyAsync(h->dPl, lam, (size_t)h->dims.F_len * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    if ((rc = qc_product_vjp_dev(h, "qc_eval_vjp", h->dZ, h->dPl, h->dPx, false, h->stream))) return rc;
+    QC_HIP(h, hipMemcpyAsync(w, h->dPx, (size_t)h->dims.Z_len * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QC_HIP(h, hipEventRecord(h->ev_done, h->stream));
+    return wait_done(h, 1);
+}
+
 // ------------------------------------------------------------------------------------------------
 //  Integrator lists with several state integrators, host buffers (UnitarySamplingProblem, UnitaryDirectSumProblem,
 //  QuantumStateSamplingProblem): one composed handle per state integrator, ONE upload of the knots, the batched launch where

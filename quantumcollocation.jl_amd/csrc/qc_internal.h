@@ -74,6 +74,7 @@ struct QcClass {
     int kernel = QC_KERNEL_LDS;   // QC_KERNEL_MFMA: Gx exists / QC_KERNEL_LDS
     bool ell16 = false;           // QcParams.ell16 exists (2N = 16 Pade order 4, or the exponential integrator: one entry per drive row)
     bool stamped = false;         // QcParams.stamps exists (QC_STAMPS=1 diagnostics)
+    bool product_mfma = true;     // dF v may take its fused MFMA kernel (false: QC_NO_PRODUCT_MFMA=1 at create time)
 };                                // (QcParams.ell exists  <=>  QcParams.ell_R > 0)
 
 // Which kernel serves a handle: the answer of qc_plan (qc_plan.h).  One enumerator per kernel family a launch can reach.  F + dF:
@@ -94,6 +95,9 @@ enum QcHessKernel {
 // dF + mu_d2F at one point:
 enum QcFusedKernel { QC_FUSED_TWO_LAUNCHES, QC_FUSED_PADE4_16, QC_FUSED_PADE4_16_GATHER, QC_FUSED_PADE4_32_ELL, QC_FUSED_KERNELS };
 
+// dF v and dF' lam (qc_products.hip; qc_mfma_products.hip):
+enum QcProductKernel { QC_PROD_GENERIC, QC_PROD_PADE4_16, QC_PROD_KERNELS };
+
 struct QcPlan {
     QcJacKernel jac;
     QcHessKernel hess;
@@ -102,6 +106,7 @@ struct QcPlan {
     bool batch_jac, batch_hess;    // may join a batched F + dF / mu_d2F launch (shapes equal to the others': the caller's check)
     bool hess_chunks;              // the mu_d2F launch may be split into chunks of intervals
     size_t hess_scratch_doubles;   // scratch the mu_d2F kernel needs in QcParams.hs (0: none), allocated at the first call
+    QcProductKernel jvp, vjp;      // dF v and dF' lam: the generic two-launch path, or a fused matrix-free kernel (dF v only)
 };
 
 struct qc_fanout;
@@ -188,6 +193,10 @@ struct qc_handle {
     double* dWs = nullptr;     // global workspace of the LDS kernels for systems beyond the LDS budget
     double* dHs = nullptr;     // scratch of the 4 x 4-tile Hessian kernel (first Hessian call)
     double *dRE = nullptr, *dRQ = nullptr, *dRS = nullptr, *dRinit = nullptr, *dRout = nullptr, *dRZ = nullptr;   // rollout scratch / staging
+    // Jacobian products, generic path (qc_products.hip): created at the first product call, released by qc_destroy
+    double* dPvals = nullptr;  // scratch Jacobian values of this handle's intervals (n_int * J_stride doubles)
+    int32_t* dPtab = nullptr;  // the per-interval pattern sorted by row and by column (QcProductTables)
+    double *dPx = nullptr, *dPy = nullptr, *dPl = nullptr;   // staging of the host-buffer forms: v / w (Z_len), y and lam (F_len)
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;   // odd chunks of the direct-to-host path (kernel boundaries of one stream overlap the other's stores)
     hipEvent_t ev_staged = nullptr;  // the knots are on the device (recorded on `stream`, waited for by `stream2`)
@@ -280,6 +289,12 @@ hipError_t qc_launch_mfma16_fused(const QcParams& P, bool gather, const double* 
 bool qc_mfma16_hess_supported(const QcParams& P);     // the order-4 mu_d2F kernels at 2N <= 16
 bool qc_mfma16_hess_gather_supported(const QcParams& P, const QcClass& cls);   // ... the one-wave kernel's row-gather form
 hipError_t qc_launch_mfma16_hess(const QcParams& P, bool gather, const double* dZ, const double* dMu, double* dH, hipStream_t st);   // the one-wave kernel
+
+// Jacobian products (qc_products.hip): the generic path's tables and kernels; the entry points' shared front end
+bool qc_mfma16_products_supported(const QcParams& P, const QcClass& cls);   // the fused matrix-free forward kernel (qc_mfma_products.hip)
+hipError_t qc_launch_mfma16_jvp(const QcParams& P, const double* dZ, const double* dv, double* dy, hipStream_t st);
+int qc_product_jvp_dev(qc_handle* h, const char* who, const double* dZ, const double* dv, double* dy, hipStream_t st);
+int qc_product_vjp_dev(qc_handle* h, const char* who, const double* dZ, const double* dlam, double* dw, bool accumulate, hipStream_t st);
 
 hipError_t qc_launch_pack_jac(const double* dJ, double* dJc, int n_int, int jac_nnz, int comp_len, int n2, int jo_F, int jo_B, int head2,
                               int tail_src, hipStream_t st);

@@ -44,6 +44,9 @@ const Name kFusedNames[QC_FUSED_KERNELS] = {
     {"PADE4_32_ELL", "mfma32-pade4-fused-ell"},
 };
 
+const Name kJvpNames[QC_PROD_KERNELS] = {{"GENERIC", "generic-jvp"}, {"PADE4_16", "mfma16-pade4-jvp"}};
+const Name kVjpNames[QC_PROD_KERNELS] = {{"GENERIC", "generic-vjp"}, {"PADE4_16", "generic-vjp"}};      // (there is no fused transposed kernel)
+
 // The two-wave mu_d2F kernel (qc_mfma_hess2.hip) serves launches of up to one round of the device (four workgroups per CU): measured
 // against the one-wave kernel (profiles/r03_hess2_ab.txt) 6.1 - 6.8 / 7.0 / 8.6 us against 7.1 / 7.5 / 8.7 at T = 250 / 500 / 1000; beyond
 // one round the one-wave kernel's persistent grid is faster (T = 2000: 15.1 against 17.3 us; T = 8000: 47.7 against 52.9).
@@ -122,6 +125,12 @@ QcFusedKernel qc_plan_fused(const QcParams& P, const QcClass& cls, const QcSwitc
     return QC_FUSED_TWO_LAUNCHES;
 }
 
+// dF v: the fused matrix-free kernel where it serves the handle (order-4 Pade, 2N <= 16, up to 8 state columns and 8 drives:
+// qc_mfma_products.hip), else the generic path -- the handle's own dF launch into a scratch, then a product kernel (qc_products.hip).
+// dF' lam: always the generic path.  A fused transposed kernel (one wave per knot) was built and measured at config 3 ABOVE the
+// F + dF launch that a fused product has to beat (profiles/products_summary.txt), so it is not part of the library.
+QcProductKernel qc_plan_product(const QcParams& P, const QcClass& cls) { return qc_mfma16_products_supported(P, cls) ? QC_PROD_PADE4_16 : QC_PROD_GENERIC; }
+
 const QcSwitches& qc_switches() {
     static QcSwitches s = read_switches();
 #ifdef QC_FUSED_ELL_DYNAMIC      /* experiment builds: this switch is read at every launch (A/B inside one process, on the same buffers) */
@@ -130,7 +139,8 @@ const QcSwitches& qc_switches() {
     return s;
 }
 
-QcCreateSwitches qc_create_switches() { return QcCreateSwitches{env_int("QC_NO_ELL", 0) != 0, env_int("QC_NO_ANTISYM", 0) != 0, env_int("QC_NO_HEAD", 0) != 0}; }
+QcCreateSwitches qc_create_switches() { return QcCreateSwitches{env_int("QC_NO_ELL", 0) != 0, env_int("QC_NO_ANTISYM", 0) != 0, env_int("QC_NO_HEAD", 0) != 0,
+                                                                      env_int("QC_NO_PRODUCT_MFMA", 0) != 0}; }
 
 bool qc_plan_mfma_serves(const QcParams& P) { return mfma_jac(P) >= 0; }
 
@@ -144,12 +154,16 @@ QcPlan qc_plan(const QcParams& P, const QcClass& cls, const QcSwitches& sw) {
     p.batch_hess = p.batch_jac && P.m <= 8 && P.hess_nnz > 0 && p.hess >= QC_HESS_EXP16;
     p.hess_chunks = p.hess >= QC_HESS_PADE4_32_ELL;      // the order-4 kernels up to 2N = 32
     p.hess_scratch_doubles = p.hess == QC_HESS_PADE4_64 ? qc_mfma64_hess_scratch_doubles(P) : 0;      // (128 MiB)
+    p.jvp = qc_plan_product(P, cls);
+    p.vjp = QC_PROD_GENERIC;
     return p;
 }
 
 const char* qc_jac_kernel_name(QcJacKernel k) { return kJacNames[k].name; }
 const char* qc_hess_kernel_name(QcHessKernel k) { return kHessNames[k].name; }
 const char* qc_fused_kernel_name(QcFusedKernel k) { return kFusedNames[k].name; }
+const char* qc_jvp_kernel_name(QcProductKernel k) { return kJvpNames[k].name; }
+const char* qc_vjp_kernel_name(QcProductKernel k) { return kVjpNames[k].name; }
 const char* qc_jac_kernel_id(QcJacKernel k) { return kJacNames[k].id; }
 const char* qc_hess_kernel_id(QcHessKernel k) { return kHessNames[k].id; }
 const char* qc_fused_kernel_id(QcFusedKernel k) { return kFusedNames[k].id; }

@@ -21,6 +21,7 @@ struct QcCreateSwitches {
     bool no_ell;           // QC_NO_ELL=1: no row-gather tables are built at all
     bool no_antisym;       // QC_NO_ANTISYM=1: the generators are treated as not antisymmetric
     bool no_head;          // QC_NO_HEAD=1: the 2N = 16 F + dF launch never takes its HEAD instantiation (A/B runs, tests)
+    bool no_product_mfma;  // QC_NO_PRODUCT_MFMA=1: dF v takes the generic path although the fused kernel serves the handle (A/B runs, tests)
 };
 QcCreateSwitches qc_create_switches();
 
@@ -30,11 +31,14 @@ QcPlan qc_plan(const QcParams& P, const QcClass& cls, const QcSwitches& sw = qc_
 QcJacKernel qc_plan_jac(const QcParams& P, const QcClass& cls, const QcSwitches& sw = qc_switches());
 QcHessKernel qc_plan_hess(const QcParams& P, const QcClass& cls, const QcSwitches& sw = qc_switches());
 QcFusedKernel qc_plan_fused(const QcParams& P, const QcClass& cls, const QcSwitches& sw = qc_switches());
+QcProductKernel qc_plan_product(const QcParams& P, const QcClass& cls);      // dF v (dF' lam always takes the generic path)
 bool qc_plan_mfma_serves(const QcParams& P);      // some MFMA kernel writes F + dF of this descriptor (qc_create: MFMA or LDS)
 
 const char* qc_jac_kernel_name(QcJacKernel k);     // what qc_kernel_name returns
 const char* qc_hess_kernel_name(QcHessKernel k);
 const char* qc_fused_kernel_name(QcFusedKernel k);
+const char* qc_jvp_kernel_name(QcProductKernel k);   // qc_kernel_name(h, 3)
+const char* qc_vjp_kernel_name(QcProductKernel k);   // qc_kernel_name(h, 4)
 const char* qc_jac_kernel_id(QcJacKernel k);       // the enumerator without its prefix (tests/kernel_plan_test.cpp)
 const char* qc_hess_kernel_id(QcHessKernel k);
 const char* qc_fused_kernel_id(QcFusedKernel k);

@@ -622,6 +622,46 @@ class QuantumDynamics:
             self._h, self._dev_ptr(Z, self.dims.Z_len, "Z"), self._dev_ptr(mu, self.dims.n_rows, "mu"),
             self._dev_ptr(H, self.dims.hess_nnz, "H"), C.c_void_p(st.cuda_stream)), self._h)
 
+    # -- matrix-free Jacobian products: dF(Z) v and dF(Z)' lam without the values of dF (qc_eval_jvp / qc_eval_vjp) -----------------
+    @property
+    def product_kernel_names(self) -> Tuple[str, str]:
+        """Kernels of dF v and dF' lam (qc_kernel_name(h, 3 / 4)): "mfma16-pade4-jvp" (fused) or "generic-jvp", and "generic-vjp"."""
+        return _lib.lib.qc_kernel_name(self._h, 3).decode(), _lib.lib.qc_kernel_name(self._h, 4).decode()
+
+    def _vec(self, x, n: int, name: str) -> np.ndarray:
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.size != n:
+            raise ValueError(f"{name} has length {x.size}, expected {n}")
+        return x
+
+    def dF_times(self, Z, v, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """y = dF(Z) v, length F_len (host buffers; `set_new_x(False)` reuses the knots on the device)."""
+        Z, v = self._Z(Z), self._vec(v, int(self.dims.Z_len), "v")
+        y = self._out("y", int(self.dims.F_len), out, True)
+        self._check(_lib.lib.qc_eval_jvp(self._h, _lib.dptr(Z), _lib.dptr(v), _lib.dptr(y)))
+        return y
+
+    def dFT_times(self, Z, lam, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """w = dF(Z)' lam, length Z_len, every entry written (host buffers)."""
+        Z, lam = self._Z(Z), self._vec(lam, int(self.dims.F_len), "lam")
+        w = self._out("w", int(self.dims.Z_len), out, True)
+        self._check(_lib.lib.qc_eval_vjp(self._h, _lib.dptr(Z), _lib.dptr(lam), _lib.dptr(w)))
+        return w
+
+    def dF_times_device(self, Z: torch.Tensor, v: torch.Tensor, y: torch.Tensor, stream=None) -> None:
+        """y = dF(Z) v on device tensors, asynchronous on `stream` (default: torch's current stream on the handle's device)."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(_lib.lib.qc_eval_jvp_dev(
+            self._h, self._dev_ptr(Z, self.dims.Z_len, "Z"), self._dev_ptr(v, self.dims.Z_len, "v"),
+            self._dev_ptr(y, self.dims.F_len, "y"), C.c_void_p(st.cuda_stream)), self._h)
+
+    def dFT_times_device(self, Z: torch.Tensor, lam: torch.Tensor, w: torch.Tensor, stream=None) -> None:
+        """w = dF(Z)' lam on device tensors, asynchronous on `stream`; every entry of w is written."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(_lib.lib.qc_eval_vjp_dev(
+            self._h, self._dev_ptr(Z, self.dims.Z_len, "Z"), self._dev_ptr(lam, self.dims.F_len, "lam"),
+            self._dev_ptr(w, self.dims.Z_len, "w"), C.c_void_p(st.cuda_stream)), self._h)
+
 
 class ComposedQuantumDynamics(QuantumDynamics):
     """`QuantumDynamics` over an integrator list with SEVERAL unitary integrators (UnitarySamplingProblem: K systems
@@ -794,6 +834,46 @@ class ComposedQuantumDynamics(QuantumDynamics):
         H = self._out("H", int(self.dims.hess_nnz), out, fresh)
         self._check(_lib.lib.qc_eval_hess_list(self._handles, len(self._parts), _lib.dptr(Z), _lib.dptr(mu), _lib.dptr(H)), self._parts[0][2])
         return H
+
+    # -- matrix-free Jacobian products over the list: the "_dev_multi" entries (members in member order on the stream) --------------
+    @property
+    def product_kernel_names(self) -> Tuple[str, str]:
+        h = self._parts[0][2]
+        return _lib.lib.qc_kernel_name(h, 3).decode(), _lib.lib.qc_kernel_name(h, 4).decode()
+
+    def _no_products_over_devices(self):
+        if self.devices is not None:
+            raise _lib.QCollocError(_lib.QC_ERR_UNSUPPORTED, "the Jacobian products do not serve integrator lists over several devices")
+
+    def dF_times_device(self, Z: torch.Tensor, v: torch.Tensor, y: torch.Tensor, stream=None) -> None:
+        self._no_products_over_devices()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(_lib.lib.qc_eval_jvp_dev_multi(
+            self._handles, len(self._parts), self._dev_ptr(Z, self.dims.Z_len, "Z"), self._dev_ptr(v, self.dims.Z_len, "v"),
+            self._dev_ptr(y, self.dims.F_len, "y"), C.c_void_p(st.cuda_stream)), self._parts[0][2])
+
+    def dFT_times_device(self, Z: torch.Tensor, lam: torch.Tensor, w: torch.Tensor, stream=None) -> None:
+        self._no_products_over_devices()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(_lib.lib.qc_eval_vjp_dev_multi(
+            self._handles, len(self._parts), self._dev_ptr(Z, self.dims.Z_len, "Z"), self._dev_ptr(lam, self.dims.F_len, "lam"),
+            self._dev_ptr(w, self.dims.Z_len, "w"), C.c_void_p(st.cuda_stream)), self._parts[0][2])
+
+    def _through_device(self, fn, Z, x, n_in: int, n_out: int, name: str, out: Optional[np.ndarray]) -> np.ndarray:
+        self._no_products_over_devices()
+        Z, x = self._Z(Z), self._vec(x, n_in, name)
+        res = self._out(name, n_out, out, True)
+        dZ, dx = torch.from_numpy(Z).to(self._dev), torch.from_numpy(x).to(self._dev)
+        dres = torch.zeros(n_out, dtype=torch.float64, device=self._dev)      # (rows no member owns are delivered as 0)
+        fn(dZ, dx, dres)
+        res[:] = dres.cpu().numpy()
+        return res
+
+    def dF_times(self, Z, v, out: Optional[np.ndarray] = None) -> np.ndarray:
+        return self._through_device(self.dF_times_device, Z, v, int(self.dims.Z_len), int(self.dims.F_len), "v", out)
+
+    def dFT_times(self, Z, lam, out: Optional[np.ndarray] = None) -> np.ndarray:
+        return self._through_device(self.dFT_times_device, Z, lam, int(self.dims.F_len), int(self.dims.Z_len), "lam", out)
 
     def knot_generation(self) -> int:
         return int(_lib.lib.qc_knot_generation(self._parts[0][2]))

@@ -213,6 +213,33 @@ class QuantumControlEvaluator:
                 H[slot[0]:slot[0] + slot[1]] = cobj.mu_d2g(x, mu[r0:r0 + cobj.dim])
             r0 += cobj.dim
 
+    # -- Jacobian products (MOI's eval_constraint_jacobian_product / eval_constraint_jacobian_transpose_product) ---------
+    # The dynamics rows go through the library's matrix-free products (no Jacobian value is formed); any other rows through
+    # their existing dense pieces.
+    def constraint_jacobian_times(self, x, v) -> np.ndarray:
+        """y = J(x) v over all constraint rows (dynamics rows first)."""
+        x, v = self._x(x), self._x(v)
+        y = np.zeros(self.n_constraints)
+        if self._can_elide:
+            self.dynamics.set_new_x(True)
+        y[:self.n_dynamics_rows] = self.dynamics.dF_times(x, v)
+        for cobj, (off, cnt) in zip(self.constraints, self._con_jac):
+            np.add.at(y, self._jac_rows[off:off + cnt], np.asarray(cobj.dg(x)).ravel() * v[self._jac_cols[off:off + cnt]])
+        return y
+
+    def constraint_jacobian_transpose_times(self, x, lam) -> np.ndarray:
+        """w = J(x)' lam over all variables."""
+        x = self._x(x)
+        lam = np.ascontiguousarray(lam, dtype=np.float64)
+        if lam.size != self.n_constraints:
+            raise ValueError(f"lam has length {lam.size}, expected {self.n_constraints}")
+        if self._can_elide:
+            self.dynamics.set_new_x(True)
+        w = np.array(self.dynamics.dFT_times(x, lam[:self.n_dynamics_rows]))
+        for cobj, (off, cnt) in zip(self.constraints, self._con_jac):
+            np.add.at(w, self._jac_cols[off:off + cnt], np.asarray(cobj.dg(x)).ravel() * lam[self._jac_rows[off:off + cnt]])
+        return w
+
     # -- conveniences for solvers that want matrices -------------------------------------------------------------------
     def jacobian_matrix(self, x):
         import scipy.sparse as sp
