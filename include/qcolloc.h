@@ -664,6 +664,14 @@ int qc_debug_read_stamps(qc_handle* h, uint64_t* out, int64_t count);
  * bench.py reports next to the PCIe bound.  QC_ERR_UNSUPPORTED when the handle's Jacobian has no replicated blocks. */
 int qc_debug_host_expand_rate(qc_handle* h, int32_t reps, double* GBps);
 
+/* Diagnostic only: would the entry points evaluate this list with ONE launch (gridDim.y = count) rather than one per member?
+ * what = 0: F + dF of qc_eval_F_jac_dev_multi; 1: mu_d2F of qc_eval_hess_dev_multi; 2: the Jacobian values of the host-buffer list
+ * calls (qc_eval_jac_list, qc_eval_F_jac_list), whose members write one block per interval for a single copy to the host.  Returns 1
+ * or 0 from the functions those entry points decide with -- nothing is launched or allocated -- or a QC_ERR_* code: a NULL handle,
+ * handles bound to different devices, a multi-device handle, for what = 2 handles that do not describe one problem.  The results do
+ * not depend on the answer. */
+int qc_debug_list_shares_launch(qc_handle* const* hs, int32_t count, int32_t what);
+
 /* Library/build identification: "qcolloc-hip <major>.<minor> (gfx950, ...)" */
 const char* qc_version(void);
 /* QC_VERSION_MAJOR * 1000 + QC_VERSION_MINOR of the build.  A binding compares it with the header version it mirrors when

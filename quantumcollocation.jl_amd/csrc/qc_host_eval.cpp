@@ -192,22 +192,29 @@ extern "C" int qc_eval_F_jac_dev(qc_handle* h, const double* dZ, double* dF, dou
 // ------------------------------------------------------------------------------------------------
 //  Several handles in one launch (the systems of a sampling problem)
 // ------------------------------------------------------------------------------------------------
-// Returns 1 when the handles can share a launch (and hs[0]->dBatch holds their parameter blocks), 0 when not, < 0 on error.
-static int prepare_batch(qc_handle* const* hs, int32_t count, bool hessian) {
+// Can the handles share one launch?  qc_plan_list (qc_plan.cpp) holds the condition; this only collects what it reads.
+static bool list_shares_launch(qc_handle* const* hs, int32_t count, QcListLaunch what) {
+    if (count < 2) return false;
+    std::vector<const QcParams*> prm((size_t)count);
+    std::vector<const QcPlan*> plans((size_t)count);
+    for (int i = 0; i < count; ++i) { prm[(size_t)i] = &hs[i]->prm; plans[(size_t)i] = &hs[i]->plan; }
+    return qc_plan_list(prm.data(), plans.data(), count, what);
+}
+static int batch_check(qc_handle* const* hs, int32_t count) {
     qc_handle* h0 = hs[0];
     for (int i = 0; i < count; ++i) {
         if (is_multi(hs[i])) return fail(&h0->err, QC_ERR_INVALID, "batched launch: multi-device handles are not accepted");
         if (hs[i]->device != h0->device) return fail(&h0->err, QC_ERR_INVALID, "batched launch: the handles are bound to different devices");
     }
-    if (count < 2 || count > 65535) return 0;
-    for (int i = 0; i < count; ++i) {
-        const qc_handle* h = hs[i];
-        if (!(hessian ? h->plan.batch_hess : h->plan.batch_jac)) return 0;
-        if (hessian && h->prm.antisym != h0->prm.antisym) return 0;   // (the antisymmetric generators' Hessian kernel is a different one)
-        if (h->prm.n_int != h0->prm.n_int || h->prm.t_begin != h0->prm.t_begin || h->prm.zdim != h0->prm.zdim || h->prm.m != h0->prm.m ||
-            h->prm.n != h0->prm.n || h->prm.nc != h0->prm.nc)
-            return 0;
-    }
+    return QC_OK;
+}
+
+// Returns 1 when the handles can share a launch (and hs[0]->dBatch holds their parameter blocks), 0 when not, < 0 on error.
+static int prepare_batch(qc_handle* const* hs, int32_t count, bool hessian) {
+    qc_handle* h0 = hs[0];
+    int rc;
+    if ((rc = batch_check(hs, count))) return rc;
+    if (!list_shares_launch(hs, count, hessian ? QC_LIST_HESS : QC_LIST_F_JAC)) return 0;
     bool same = h0->dBatch != nullptr && (int)h0->batch_members.size() == count;
     for (int i = 0; same && i < count; ++i) same = h0->batch_members[i] == hs[i]->serial;
     if (same) return 1;
@@ -1511,27 +1518,38 @@ static int land_batch_params(qc_handle* const* hs, int32_t count, const std::vec
     return QC_OK;
 }
 
+// A member writes the compact form of its values itself (one copy of the N replicated blocks): its segment is `direct`
+static bool landing_direct(const qc_handle* h) { return compact_plan(h->prm).useful && h->plan.compact; }
+// The landing path serves the list: the leader's switches, and some member has something to gain from the compact form
+static bool landing_serves(qc_handle* const* hs, int32_t count) {
+    if (hs[0]->host_landing != 1 || hs[0]->host_compact != 1) return false;
+    for (int i = 0; i < count; ++i) if (landing_direct(hs[i])) return true;
+    return false;
+}
+// ... and its members go out as one launch: every segment direct, QC_LIST_BATCH not 0 (A/B diagnostics), and qc_plan_list
+static bool landing_shares_launch(qc_handle* const* hs, int32_t count) {
+    if (!landing_serves(hs, count) || !qc_switches().list_batch) return false;
+    for (int i = 0; i < count; ++i) if (!landing_direct(hs[i])) return false;
+    return list_shares_launch(hs, count, QC_LIST_LANDING);
+}
+
 static int list_eval_landing(qc_handle* const* hs, int32_t count, double* F, double* vals, int shards) {
     qc_handle* h = hs[0];
     const QcParams& P0 = h->prm;
-    if (!vals || h->host_landing != 1 || h->host_compact != 1) return 0;
-    struct Seg { CompactPlan cp; bool direct, batchable; size_t len, off; };
+    if (!vals || !landing_serves(hs, count)) return 0;
+    struct Seg { CompactPlan cp; bool direct; size_t len, off; };
     std::vector<Seg> seg((size_t)count);
     const size_t f_len = (size_t)P0.F_stride;       // always in the block: its layout must not depend on what a call asks for
     size_t blk = f_len;
-    bool any = false;
     for (int i = 0; i < count; ++i) {
         const QcParams& P = hs[i]->prm;
         Seg& S = seg[(size_t)i];
         S.cp = compact_plan(P);
-        S.direct = S.cp.useful && hs[i]->plan.compact;
-        S.batchable = S.direct && hs[i]->plan.batch_jac;
+        S.direct = landing_direct(hs[i]);
         S.len = S.direct ? (size_t)S.cp.comp_len : (size_t)P.jac_nnz;
         S.off = blk;
         blk += S.len;
-        any = any || S.direct;
     }
-    if (!any) return 0;
     const double t_begin = now_us();
     const size_t n_int = (size_t)P0.n_int, cap = n_int * blk;
     int rc;
@@ -1549,8 +1567,7 @@ static int list_eval_landing(qc_handle* const* hs, int32_t count, double* F, dou
     std::vector<QcParams> Cs((size_t)count);
     // one launch for every member where the batched kernel serves them all (2N <= 16, order 4, equal shapes: the K systems of a
     // sampling problem, the members of a direct sum of equal systems), as the "_dev_multi" entry points do; else one launch each
-    bool batch = count >= 2 && count <= 65535;
-    const bool no_batch = !qc_switches().list_batch;     // A/B diagnostics
+    const bool batch = landing_shares_launch(hs, count);
     for (int i = 0; i < count; ++i) {
         const Seg& S = seg[(size_t)i];
         QcParams& C = Cs[(size_t)i];
@@ -1558,8 +1575,6 @@ static int list_eval_landing(qc_handle* const* hs, int32_t count, double* F, dou
         C.J_stride = (long long)blk;
         C.J_off = (long long)S.off;
         C.F_stride = (long long)blk;                          // (F_off = the handle's first row inside the problem's rows: unchanged)
-        const QcParams& Pi = hs[i]->prm;
-        batch = batch && !no_batch && S.batchable && Pi.m == P0.m && Pi.n == P0.n && Pi.nc == P0.nc;
     }
     if (batch) {
         if ((rc = land_batch_params(hs, count, Cs, blk))) return rc;
@@ -1725,6 +1740,20 @@ extern "C" int qc_eval_F_jac_list(qc_handle* const* hs, int32_t count, const dou
 extern "C" int qc_eval_hess_list(qc_handle* const* hs, int32_t count, const double* Z, const double* mu, double* hvals) {
     if (hs && count >= 1 && hs[0] && !hvals) return fail(&hs[0]->err, QC_ERR_INVALID, "qc_eval_hess_list: NULL buffer");
     return list_eval(hs, count, Z, mu, nullptr, nullptr, hvals, "qc_eval_hess_list");
+}
+
+// Diagnostic: would the entry points evaluate this list with ONE launch?  The same functions they call, nothing launched or allocated.
+extern "C" int qc_debug_list_shares_launch(qc_handle* const* hs, int32_t count, int32_t what) {
+    if (!hs || count < 1) return fail(nullptr, QC_ERR_INVALID, "qc_debug_list_shares_launch: no handles");
+    for (int i = 0; i < count; ++i) if (!hs[i]) return fail(nullptr, QC_ERR_INVALID, "qc_debug_list_shares_launch: NULL handle");
+    if (what < 0 || what >= QC_LIST_LAUNCHES) return fail(&hs[0]->err, QC_ERR_INVALID, "qc_debug_list_shares_launch: `what` is 0 (F + dF), 1 (mu_d2F) or 2 (host-buffer Jacobian)");
+    int rc;
+    if (what == QC_LIST_LANDING) {
+        if ((rc = list_check(hs, count, "qc_debug_list_shares_launch"))) return rc;
+        return hs[0]->prm.n_int > 0 && landing_shares_launch(hs, count) ? 1 : 0;
+    }
+    if ((rc = batch_check(hs, count))) return rc;
+    return hs[0]->prm.n_int > 0 && list_shares_launch(hs, count, (QcListLaunch)what) ? 1 : 0;
 }
 
 // ------------------------------------------------------------------------------------------------

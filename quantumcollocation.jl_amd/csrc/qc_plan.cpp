@@ -159,6 +159,24 @@ QcPlan qc_plan(const QcParams& P, const QcClass& cls, const QcSwitches& sw) {
     return p;
 }
 
+// One launch for a list: every member may join the batched launch of its kind (QcPlan.batch_jac / batch_hess; the landing layout is
+// written by the kernels that honour QcParams.copies), and everything the launch takes from the leader alone is the same for all of
+// them -- the grid (n_int), the instantiation (drive-count class from m, masked or unmasked tile from n and nc; mu_d2F: the kernel for
+// antisymmetric generators or the general one) -- as is the trajectory they read (zdim, t_begin).  gridDim.y is a 16-bit quantity.
+bool qc_plan_list(const QcParams* const* members, const QcPlan* const* plans, int count, QcListLaunch what) {
+    if (count < 2 || count > 65535) return false;
+    const QcParams& P0 = *members[0];
+    for (int i = 0; i < count; ++i) {
+        const QcParams& P = *members[i];
+        const QcPlan& p = *plans[i];
+        if (!(what == QC_LIST_HESS ? p.batch_hess : p.batch_jac)) return false;
+        if (what == QC_LIST_LANDING && !p.compact) return false;
+        if (what == QC_LIST_HESS && P.antisym != P0.antisym) return false;
+        if (P.n_int != P0.n_int || P.t_begin != P0.t_begin || P.zdim != P0.zdim || P.m != P0.m || P.n != P0.n || P.nc != P0.nc) return false;
+    }
+    return true;
+}
+
 const char* qc_jac_kernel_name(QcJacKernel k) { return kJacNames[k].name; }
 const char* qc_hess_kernel_name(QcHessKernel k) { return kHessNames[k].name; }
 const char* qc_fused_kernel_name(QcFusedKernel k) { return kFusedNames[k].name; }

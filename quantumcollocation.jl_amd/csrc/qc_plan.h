@@ -34,6 +34,13 @@ QcFusedKernel qc_plan_fused(const QcParams& P, const QcClass& cls, const QcSwitc
 QcProductKernel qc_plan_product(const QcParams& P, const QcClass& cls);      // dF v (dF' lam always takes the generic path)
 bool qc_plan_mfma_serves(const QcParams& P);      // some MFMA kernel writes F + dF of this descriptor (qc_create: MFMA or LDS)
 
+// Can the members of a list share ONE launch (gridDim.y = count, each workgroup reading its member's parameter block from device
+// memory)?  The whole condition, for the three places such a launch starts from: the device-resident F + dF and mu_d2F entry points
+// ("_dev_multi") and the host-buffer Jacobian path, which launches the members' landing layouts.  Pure; `plans[i]` is qc_plan of
+// `members[i]` (a landing layout changes the placement and the copies of a member, none of the fields read here).
+enum QcListLaunch { QC_LIST_F_JAC = 0, QC_LIST_HESS = 1, QC_LIST_LANDING = 2, QC_LIST_LAUNCHES };
+bool qc_plan_list(const QcParams* const* members, const QcPlan* const* plans, int count, QcListLaunch what);
+
 const char* qc_jac_kernel_name(QcJacKernel k);     // what qc_kernel_name returns
 const char* qc_hess_kernel_name(QcHessKernel k);
 const char* qc_fused_kernel_name(QcFusedKernel k);

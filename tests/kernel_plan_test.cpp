@@ -3,7 +3,9 @@
 // (qc_blueprint_build) and the plan function (qc_plan, qc_plan.cpp).  No GPU: tests/test_kernel_plan.py builds this file against
 // libqcolloc_hip.so, runs it and compares the output byte for byte with tests/golden/kernel_selection.txt, which was recorded
 // from the predicate chains the library had before it had a plan function.  After the cases: every name qc_kernel_name gave for a kernel.
-// usage: kernel_plan_test full | switches | enumerators
+// `lists`: pairs and triples of descriptors, one line per list with the three answers of qc_plan_list (can the members share one
+// launch: F + dF, mu_d2F, the host-buffer Jacobian path) behind the members as qc_create would see them.
+// usage: kernel_plan_test full | switches | lists | enumerators
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -80,11 +82,13 @@ const char* class_of(const Setup& S) { return S.h.cls.kernel == QC_KERNEL_MFMA ?
 
 std::set<std::string> g_names;
 
-void run_case(const Case& c) {
+int columns_of(const Case& c) { return c.skind == S_UNITARY ? c.N : (c.skind == S_KETS ? std::max(1, c.N / 2) : 1); }
+
+// the descriptor of a case; `G` keeps the generators it points at
+qc_desc desc_of(const Case& c, const std::vector<double>& G) {
     const int N = c.N, n = 2 * N, m = c.m;
-    const int nc = c.skind == S_UNITARY ? N : (c.skind == S_KETS ? std::max(1, N / 2) : 1);
+    const int nc = columns_of(c);
     const int s = n * nc;
-    const std::vector<double> G = generators(n, m, c.gkind);
     qc_desc d;
     memset(&d, 0, sizeof(d));
     d.N = N;
@@ -101,6 +105,13 @@ void run_case(const Case& c) {
     d.G_drives = G.data() + (size_t)n * n;
     d.kernel = c.kernel;
     d.state_cols = c.skind == S_UNITARY ? 0 : nc;
+    return d;
+}
+
+void run_case(const Case& c) {
+    const int N = c.N, m = c.m;
+    const std::vector<double> G = generators(2 * N, m, c.gkind);
+    qc_desc d = desc_of(c, G);
     char what[96];
     snprintf(what, sizeof(what), "%s%d N=%d %s %s m=%d %s n=%d %s c=%d", c.order ? "pade" : "exp", c.order, N, kSName[c.skind], c.free_dt ? "free" : "fixed", m,
              kGName[c.gkind], c.n_int, kernel_class_name(c.kernel), c.chunk);
@@ -174,17 +185,105 @@ void sweep_full() {
             for (int sk = 0; sk < 2; ++sk) run_case(Case{4, N, 6, g, sk, true, 1000, QC_KERNEL_AUTO, 63});
 }
 
+// ---- lists: members over ONE trajectory (the knot is as wide as the widest member needs; a member may cover a range of intervals) ----
+struct Member { Case c; int t_begin, t_end; };      // t_end = 0: every interval
+
+Member whole(int order, int N, int m, int gkind = G_DENSE, int skind = S_UNITARY, bool free_dt = true, int kernel = QC_KERNEL_AUTO) {
+    return Member{Case{order, N, m, gkind, skind, free_dt, 40, kernel, 0}, 0, 0};
+}
+Member shard(Member mb, int t_begin, int t_end) { mb.t_begin = t_begin; mb.t_end = t_end; return mb; }
+Member of_length(Member mb, int n_int) { mb.c.n_int = n_int; return mb; }
+
+void run_list(const std::vector<Member>& members, int own_zdim = -1) {
+    const int count = (int)members.size();
+    int zdim = 0;
+    for (const Member& mb : members) zdim = std::max(zdim, 2 * mb.c.N * columns_of(mb.c) + mb.c.m + (mb.c.free_dt ? 1 : 0));
+    std::vector<Setup> S((size_t)count);
+    std::vector<const QcParams*> prm;
+    std::vector<const QcPlan*> plans;
+    std::string what;
+    for (int i = 0; i < count; ++i) {
+        const Case& c = members[(size_t)i].c;
+        const std::vector<double> G = generators(2 * c.N, c.m, c.gkind);
+        qc_desc d = desc_of(c, G);
+        d.zdim = i == own_zdim ? d.zdim + 1 : zdim;      // (`own_zdim`: that member reads knots of another width -- not one trajectory)
+        d.t_begin = members[(size_t)i].t_begin;
+        d.t_end = members[(size_t)i].t_end;
+        const int rc = setup(&d, G, &S[(size_t)i]);
+        char text[128];
+        snprintf(text, sizeof(text), "%s%s%d N=%d %s %s m=%d %s t=%d+%d z=%d %s", i ? " ; " : "", c.order ? "pade" : "exp", c.order, c.N, kSName[c.skind],
+                 c.free_dt ? "free" : "fixed", c.m, kGName[c.gkind], rc ? -1 : (int)S[(size_t)i].h.prm.t_begin, rc ? -1 : S[(size_t)i].h.prm.n_int, d.zdim,
+                 kernel_class_name(c.kernel));
+        what += text;
+        if (rc) { printf("list %d: %s | refused %d\n", count, what.c_str(), rc); return; }
+        S[(size_t)i].h.plan = qc_plan(S[(size_t)i].h.prm, S[(size_t)i].h.cls);
+        prm.push_back(&S[(size_t)i].h.prm);
+        plans.push_back(&S[(size_t)i].h.plan);
+    }
+    // the members | one launch for F + dF, for mu_d2F, for the host-buffer Jacobian path
+    printf("list %d: %s | %d %d %d\n", count, what.c_str(), (int)qc_plan_list(prm.data(), plans.data(), count, QC_LIST_F_JAC),
+           (int)qc_plan_list(prm.data(), plans.data(), count, QC_LIST_HESS), (int)qc_plan_list(prm.data(), plans.data(), count, QC_LIST_LANDING));
+}
+
+void sweep_lists() {
+    // equal members: every drive-count class of the batched launches, the drive counts beyond the registers of mu_d2F, full and padded tiles
+    for (int N : {2, 5, 8})
+        for (int m : {0, 2, 6, 8, 9, 32})
+            for (int count : {2, 3}) run_list(std::vector<Member>((size_t)count, whole(4, N, m)));
+    for (int N : {2, 8}) run_list({whole(4, N, 0, G_DENSE, S_UNITARY, false), whole(4, N, 0, G_DENSE, S_UNITARY, false)});      // linear: no Hessian
+    run_list({whole(4, 8, 6, G_DENSE, S_KETS), whole(4, 8, 6, G_DENSE, S_KETS), whole(4, 8, 6, G_DENSE, S_KETS)});
+    run_list({whole(4, 8, 3, G_PERM), whole(4, 8, 3, G_PERM)});
+    run_list({whole(4, 8, 7, G_NONANTI), whole(4, 8, 7, G_NONANTI)});
+    // one field apart: drives, levels, state columns, antisymmetry, timestep kind alone does not count
+    run_list({whole(4, 8, 6), whole(4, 8, 4)});
+    run_list({whole(4, 8, 6), whole(4, 8, 5)});      // (the same drive-count class: still two launches)
+    run_list({whole(4, 8, 4), whole(4, 8, 4), whole(4, 8, 6)});
+    run_list({whole(4, 8, 6), whole(4, 8, 4), whole(4, 8, 4)});
+    run_list({whole(4, 8, 2), whole(4, 5, 2)});
+    run_list({whole(4, 4, 2), whole(4, 5, 2), whole(4, 4, 2)});
+    run_list({whole(4, 8, 2), whole(4, 8, 2, G_DENSE, S_KETS)});
+    run_list({whole(4, 8, 2, G_DENSE, S_KETS), whole(4, 8, 2, G_DENSE, S_DENSITY)});
+    run_list({whole(4, 8, 6), whole(4, 8, 6, G_NONANTI)});
+    run_list({whole(4, 8, 6, G_NONANTI), whole(4, 8, 6), whole(4, 8, 6)});
+    run_list({whole(4, 8, 6), whole(4, 8, 6, G_PERM)});
+    run_list({whole(4, 8, 9), whole(4, 8, 9, G_NONANTI)});
+    // a member of the LDS class, of the exponential integrator, of another order, of the 2N = 32 kernels
+    run_list({whole(4, 8, 6), whole(4, 8, 6, G_DENSE, S_UNITARY, true, QC_KERNEL_LDS)});
+    run_list({whole(4, 8, 6, G_DENSE, S_UNITARY, true, QC_KERNEL_LDS), whole(4, 8, 6), whole(4, 8, 6)});
+    run_list({whole(4, 8, 6, G_DENSE, S_UNITARY, true, QC_KERNEL_LDS), whole(4, 8, 6, G_DENSE, S_UNITARY, true, QC_KERNEL_LDS)});
+    run_list({whole(4, 8, 6), whole(0, 8, 6)});
+    run_list({whole(0, 8, 6), whole(0, 8, 6)});
+    run_list({whole(0, 2, 2), whole(0, 2, 2), whole(0, 2, 2)});
+    run_list({whole(6, 8, 2), whole(6, 8, 2)});
+    run_list({whole(4, 8, 2), whole(6, 8, 2)});
+    run_list({whole(4, 16, 2), whole(4, 16, 2)});
+    run_list({whole(4, 9, 2), whole(4, 9, 2)});
+    // one member alone
+    run_list({whole(4, 8, 6)});
+    run_list({whole(4, 2, 2)});
+    // ranges of intervals: equal shards share, another first interval or another length does not; knots of another width
+    run_list({shard(whole(4, 8, 6), 3, 9), shard(whole(4, 8, 6), 3, 9)});
+    run_list({shard(whole(4, 8, 6), 3, 9), shard(whole(4, 8, 6), 4, 10)});
+    run_list({shard(whole(4, 8, 6), 3, 9), shard(whole(4, 8, 6), 3, 10), shard(whole(4, 8, 6), 3, 9)});
+    run_list({whole(4, 8, 6), shard(whole(4, 8, 6), 0, 39)});
+    run_list({whole(4, 2, 2), of_length(whole(4, 2, 2), 41)});
+    run_list({whole(4, 8, 6), whole(4, 8, 6)}, 1);
+    // lengths past the persistent grids of the batched launches (1024 and 4096 workgroups)
+    for (int len : {1025, 4097}) run_list({of_length(whole(4, 8, 6), len), of_length(whole(4, 8, 6), len)});
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     const std::string mode = argc > 1 ? argv[1] : "full";
     if (mode == "full") sweep_full();
     else if (mode == "switches") sweep_switches();
+    else if (mode == "lists") sweep_lists();
     else if (mode == "enumerators") {
         for (int k = 0; k < QC_JAC_KERNELS; ++k) printf("jac %s\n", qc_jac_kernel_id((QcJacKernel)k));
         for (int k = 0; k < QC_HESS_KERNELS; ++k) printf("hess %s\n", qc_hess_kernel_id((QcHessKernel)k));
         for (int k = 0; k < QC_FUSED_KERNELS; ++k) printf("fused %s\n", qc_fused_kernel_id((QcFusedKernel)k));
-    } else { fprintf(stderr, "usage: %s full | switches | enumerators\n", argv[0]); return 2; }
+    } else { fprintf(stderr, "usage: %s full | switches | lists | enumerators\n", argv[0]); return 2; }
     for (const std::string& n : g_names) printf("name %s\n", n.c_str());
     return 0;
 }

@@ -165,6 +165,48 @@ def composed_oracle(inp, hess_align=1):
     return SimpleNamespace(F=F, dF=dF, structure=structure, mu_d2F=mu_d2F, hess_structure=hess_structure, rows=rows, probs=probs)
 
 
+def composed_c_oracle(inp):
+    """composed_oracle's values from the C restatement (oracle/qc_oracle.c: milliseconds where the numpy oracle takes minutes): one
+    COracle per group, outputs interleaved per interval in integrator order.  `t_begin`, `t_end`: the intervals wanted (a shard); mu is
+    always the full-length vector."""
+    import __graft_entry__ as g
+    import oracle.qc_oracle_c as oc
+    from types import SimpleNamespace
+    qc = g.load_package()
+    groups = qc.split_groups(inp.integrators)
+    probs = [problem_from_inputs(SimpleNamespace(integrators=grp, traj=inp.traj)) for grp in groups]
+    for p in probs:
+        p.hess_align = 1
+    cos = [oc.COracle(p) for p in probs]
+    T = inp.traj.T
+    rows = sum(c.ddim for c in cos)
+
+    def interleave(parts):
+        return np.concatenate(parts, axis=1).reshape(-1)
+
+    def span(t_begin, t_end):
+        t_end = T - 1 if t_end is None else t_end
+        return t_begin, t_end, t_end - t_begin
+
+    def F_dF(Z, t_begin=0, t_end=None, want_F=True, want_J=True):
+        t_begin, t_end, k = span(t_begin, t_end)
+        outs = [c.F_dF(Z, t_begin, t_end, want_F, want_J) for c in cos]
+        return (interleave([F.reshape(k, c.ddim) for c, (F, _) in zip(cos, outs)]) if want_F else None,
+                interleave([J.reshape(k, c.jac_nnz) for c, (_, J) in zip(cos, outs)]) if want_J else None)
+
+    def mu_d2F(Z, mu, t_begin=0, t_end=None):
+        t_begin, t_end, k = span(t_begin, t_end)
+        mus = np.asarray(mu).reshape(T - 1, rows)
+        out, ro = [], 0
+        for c in cos:
+            out.append(c.mu_d2F(Z, np.ascontiguousarray(mus[:, ro:ro + c.ddim]).reshape(-1), t_begin, t_end).reshape(k, c.hess_nnz))
+            ro += c.ddim
+        return interleave(out)
+
+    return SimpleNamespace(F_dF=F_dF, F=lambda Z, *a: F_dF(Z, *a, want_J=False)[0], dF=lambda Z, *a: F_dF(Z, *a, want_F=False)[1],
+                           mu_d2F=mu_d2F, rows=rows, probs=probs)
+
+
 def aa_columns(dyn):
     """Columns of the per-interval Hessian value block that hold (a_i, a_j) entries (for every member of a composed handle).
     Round 6: mu_d2F ALONE takes these from the Gram matrix M D^T where the handle's drives have one entry per row

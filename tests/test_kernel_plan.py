@@ -2,7 +2,11 @@
 half of qc_create and the plan function over a sweep of descriptors and prints one line per case -- the kernel class, the three
 kernels (enumerators) and the properties the host paths read -- and then every name qc_kernel_name gave for an enumerator.  The table must equal tests/golden/kernel_selection.txt byte for
 byte: that file was recorded from the predicate chains of the launchers, of qc_kernel_name and of the host paths as they were before
-one function took their place."""
+one function took their place.
+
+The fourth section is about lists of handles (sampling problems, direct sums): can the members share ONE launch (qc_plan_list)?  Its
+lines were checked one by one against the rule that test_list_answers_follow_the_rule_in_words restates from the members' printed
+descriptions alone, so the recorded answers do not rest on the function that printed them."""
 import os
 import shutil
 import subprocess
@@ -19,6 +23,7 @@ SECTIONS = [
     ("# section: default", "full", {}),
     ("# section: QC_NO_ELL=1", "switches", {"QC_NO_ELL": "1"}),
     ("# section: QC_HESS_TWO_WAVES=0 QC_HESS_G2=0", "switches", {"QC_HESS_TWO_WAVES": "0", "QC_HESS_G2": "0"}),
+    ("# section: lists", "lists", {}),
 ]
 # Families that no descriptor reaches without a switch (or QC_STAMPS): the one-wave mu_d2F kernel's row-gather form stands behind
 # qc_mfma_hess_g2.hip, which serves every handle it serves.
@@ -88,3 +93,29 @@ def test_every_kernel_family_occurs_in_the_table(driver):
     assert every - default == SWITCH_GATED          # reached by descriptors alone: everything else
     assert SWITCH_GATED <= kernels_in("".join(golden.values()))      # ... and the rest under the switches of the other sections
     assert kernels_in("".join(golden.values())) <= every
+
+
+def test_list_answers_follow_the_rule_in_words(driver):
+    """One launch serves a list of two or more members when every member is an order-4 Pade integrator of the MFMA class with 2N <= 16
+    (the batched kernel: up to 32 drives for F + dF and the host-buffer Jacobian path, up to 8 and a Hessian at all -- drives or a free
+    timestep -- for mu_d2F), and the members agree in levels, state columns, drives, first interval, length and knot width; mu_d2F
+    also wants them to agree on whether their generators are antisymmetric.  Restated here from the printed descriptions."""
+    cols = {"unitary": lambda N: N, "kets": lambda N: max(1, N // 2), "density": lambda N: 1}
+    lines = run(driver, "lists", {}).splitlines()
+    assert len(lines) >= 70
+    seen = set()
+    for line in lines:
+        head, answers = line.split(" | ")
+        count, members = head.split(": ")
+        ms = []
+        for text in members.split(" ; "):
+            integ, N, state, dt, m, gen, t, z, cls = text.split()
+            N, m = int(N[2:]), int(m[2:])
+            ms.append(dict(batchable=integ == "pade4" and cls == "auto" and 2 * N <= 16 and m <= 32, hess=m <= 8 and (m > 0 or dt == "free"),
+                           shape=(N, cols[state](N), m, t, z), anti=gen != "nonanti"))
+        assert int(count.split()[1]) == len(ms)
+        share = len(ms) >= 2 and all(x["batchable"] for x in ms) and len({x["shape"] for x in ms}) == 1
+        hess = share and all(x["hess"] for x in ms) and len({x["anti"] for x in ms}) == 1
+        assert answers.split() == [str(int(share)), str(int(hess)), str(int(share))], line
+        seen.add((len(ms), share, hess))
+    assert {(2, True, True), (3, True, True), (2, True, False), (3, True, False), (2, False, False), (3, False, False), (1, False, False)} <= seen
