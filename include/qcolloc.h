@@ -603,7 +603,9 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * Kernels: 2N <= 16 with up to 8 drives runs on the f64 matrix cores, one wavefront per (sample, chunk of intervals)
  * ("mfma16-sweep"); larger systems run the rollout kernels once per sample ("rollout-per-sample": correctness, not speed).
  * Results do not depend on scheduling: repeated calls return the same bits.  Non-finite inputs are evaluated, not rejected.
- * Out of scope: per-knot outputs, gradients, the free-phase fidelity, several devices. */
+ * Gradients (qc_sweep_grad*, below) are served for closed systems in the MFMA form.
+ * Out of scope: per-knot outputs, open-system gradients (they need stored forward states), derivatives with respect to theta and
+ * `scale`, second derivatives, the free-phase fidelity, several devices. */
 #define QC_MAX_PERT 8
 #define QC_SWEEP_FID_NONE (-1)   /* qc_sweep_desc.fid_kind: final states only */
 typedef struct qc_sweep_desc {
@@ -652,6 +654,30 @@ int qc_sweep_eval(qc_sweep* h, const double* Z, const double* init, int64_t S, c
  * form issues its launches (about six per sample) from a host loop inside the call. */
 int qc_sweep_eval_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
                       double* dfinals, double* dfids, void* stream);
+
+/* ---- sweep gradients: the adjoint of the sweep -------------------------------------------------------------------------- */
+/* dF_s/da_{t,k} and dF_s/ddt_t of every sample's fidelity, and J = sum_s w_s F_s with its dense gradient over Z.  One backward walk
+ * with one Frechet-derivative chain per interval: the cost is a small constant times the forward sweep, whatever the number of drives.
+ * Served where ALL of these hold; everything else returns QC_ERR_UNSUPPORTED with a message that names the reason:
+ *   - the handle takes the "mfma16-sweep" form (2N <= 16, m <= 8);
+ *   - fid_kind is QC_FID_UNITARY (either form, with or without subspace) or QC_FID_KET;
+ *   - at most 16 state columns;
+ *   - G_drift, every drive and every perturbation are antisymmetric, max |G + G^T| <= 64 eps max |G| (closed systems: iso generators
+ *     of Hermitian operators; Lindblad generators are not).
+ * The last knot's controls and timestep enter no interval: their derivatives are exactly +0.0, as is every entry of `grad` that is
+ * neither a control nor a timestep.  The |tr| / n form is not special-cased at tr = 0 (NaN there, as qc_fidelity_eval).
+ * `fids` carry the bits of qc_sweep_eval; repeated calls return the same bits (no atomics, sums in a fixed order). */
+/* device-free: *supported = 1 / 0; when 0, qc_sweep_last_error(NULL) says why.  An invalid descriptor returns its own error. */
+int qc_sweep_desc_grad_supported(const qc_sweep_desc* d, int32_t* supported);
+/* device buffers, asynchronous on `stream`.  weights: S values or NULL (= 1/S each); fids: S values or NULL; J: one double or NULL;
+ * grad: zdim T + global_dim values or NULL; grad_samples: S x (T-1) x (m + (off_dt >= 0)), sample-major, per interval the drives then
+ * the timestep, or NULL.  At least one output must be non-NULL.  Scratch and the one-in-flight rule as qc_sweep_eval_dev (without
+ * grad_samples the handle keeps a buffer of that size itself).  Non-finite inputs are evaluated, not rejected. */
+int qc_sweep_grad_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
+                      const double* dweights, double* dfids, double* dJ, double* dgrad, double* dgrad_samples, void* stream);
+/* the same on host buffers (synchronous) */
+int qc_sweep_grad(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
+                  const double* weights, double* fids, double* J, double* grad, double* grad_samples);
 
 /* Diagnostic only: when the environment variable QC_STAMPS=1 is set at qc_create, the MFMA kernel
  * records 16 s_memrealtime (100 MHz) checkpoints per interval; this copies them out (synchronises the

@@ -727,6 +727,58 @@ function rollout_sweep(init::AbstractVector{Float64}, controls::AbstractMatrix{F
 end
 
 """
+    rollout_sweep_gradient(init, controls, Δt, G_drift, G_drives, G_pert, θ; scale=nothing, weights=nothing, cols, goal, fid_kind=0,
+                           subspace=nothing, squared=false, per_sample=false, device=0)  ->  (J, fids, ∇a, ∇Δt[, grad_samples])
+
+The adjoint of `rollout_sweep` (`qc_sweep_grad`): J = Σ_s w_s F_s (`weights`: S values, default 1/S each), the S fidelities, and the
+gradient of J with respect to the controls (`∇a`, m×T) and the timesteps (`∇Δt`, T); the last knot's columns are zero.  With
+`per_sample`, `grad_samples` is (m+1)×(T-1)×S: ∂F_s/∂a_{t,k}, then ∂F_s/∂Δt_t.  Served for closed systems (antisymmetric generators)
+with 2N ≤ 16, m ≤ 8 and `fid_kind` 0 (unitary) or 1 (ket); everything else errors with the library's reason.  Arguments as
+`rollout_sweep`.  UNTESTED here, like the rest of this file.
+"""
+function rollout_sweep_gradient(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift, G_drives,
+                                G_pert, θ::AbstractMatrix{Float64}; scale=nothing, weights=nothing, cols::Int, goal, fid_kind::Int=0,
+                                subspace=nothing, squared::Bool=false, per_sample::Bool=false, device::Int=0)
+    n = size(G_drift, 1); N = n ÷ 2
+    m, T = size(controls); p = length(G_pert); S = size(θ, 1)
+    G0 = Float64.(vec(G_drift))
+    Gd = m == 0 ? Float64[] : reduce(vcat, [Float64.(vec(G)) for G in G_drives])
+    Gp = p == 0 ? Float64[] : reduce(vcat, [Float64.(vec(G)) for G in G_pert])
+    sub = isnothing(subspace) ? Int32[] : Int32.(collect(subspace) .- 1)
+    g = Float64.(collect(goal))
+    Z⃗ = vec(vcat(controls, reshape(Δt, 1, T)))                      # knot layout [a; Δt]
+    θt = Matrix{Float64}(transpose(θ))                               # sample-major
+    ct = isnothing(scale) ? Float64[] : vec(Matrix{Float64}(transpose(scale)))
+    w = isnothing(weights) ? Float64[] : Float64.(collect(weights))
+    fids = Vector{Float64}(undef, S)
+    J = Ref(0.0)
+    grad = Vector{Float64}(undef, (m + 1) * T)
+    gs = per_sample ? Array{Float64}(undef, m + 1, T - 1, S) : Array{Float64}(undef, 0, 0, 0)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve G0 Gd Gp sub g begin
+        desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
+                               pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
+                               squared ? 1 : 0, length(sub), pointer(g), isempty(sub) ? C_NULL : pointer(sub),
+                               device, 0, (0, 0)))
+        ok = Ref{Int32}(0)
+        rc = ccall((:qc_sweep_desc_grad_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
+        (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
+        rc = ccall((:qc_sweep_create, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Ptr{Cvoid}}), desc, h)
+        rc == 0 || error("qc_sweep_create: " * unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
+    end
+    rc = GC.@preserve Z⃗ init θt ct w fids grad gs ccall((:qc_sweep_grad, LIB[]), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ptr{Float64},
+         Ptr{Float64}),
+        h[], Z⃗, init, S, p == 0 ? C_NULL : pointer(θt), isempty(ct) ? C_NULL : pointer(ct), isempty(w) ? C_NULL : pointer(w), fids, J, grad,
+        per_sample ? pointer(gs) : C_NULL)
+    msg = rc == 0 ? "" : unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), h[]))
+    ccall((:qc_sweep_destroy, LIB[]), Cvoid, (Ptr{Cvoid},), h[])
+    rc == 0 || error("qc_sweep_grad: " * msg)
+    G = reshape(grad, m + 1, T)
+    return per_sample ? (J[], fids, G[1:m, :], G[m + 1, :], gs) : (J[], fids, G[1:m, :], G[m + 1, :])
+end
+
+"""
     iso_vec_unitary_fidelity(Ũ⃗, Ũ⃗_goal; subspace=nothing, device=0, squared=false)          (unitary_minimum_time_problem.jl:77)
     iso_vec_unitary_free_phase_fidelity(Ũ⃗, Ũ⃗_goal, phases, phase_operators; subspace=nothing)  (unitary_minimum_time_problem.jl:86-90)
 

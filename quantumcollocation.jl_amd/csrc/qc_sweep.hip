@@ -28,6 +28,7 @@
 
 #include "qc_mfma_common.h"
 #include "qc_side.h"
+#include "qc_sweep_internal.h"
 
 namespace {
 
@@ -256,26 +257,6 @@ int sfail(qc_side* h, int code, const std::string& msg) { return qc_side_fail(h,
 
 }  // namespace
 
-struct qc_sweep : qc_side {
-    qc_sweep_desc d;             // caller-owned arrays are not retained (pointers nulled)
-    bool mfma = false;
-    int n = 0, nc = 0, ns = 0, fid_n = 0;
-    int64_t Zlen = 0;
-    double* dG = nullptr;        // (1 + m + p) matrices, column-major (per-sample form)
-    double* dImg = nullptr;      // their A-layout images (MFMA form)
-    double *dgr = nullptr, *dgi = nullptr;
-    // scratch of the "_dev" entry point, grown at the first call that needs it
-    double* dTot = nullptr;  size_t capTot = 0;
-    double* dFin = nullptr;  size_t capFin = 0;
-    double *dGs = nullptr, *dRE = nullptr, *dRQ = nullptr, *dRS = nullptr, *dRout = nullptr;
-    // staging of the host-buffer entry point
-    double *sZ = nullptr, *sInit = nullptr;
-    double* sTheta = nullptr;  size_t capTheta = 0;
-    double* sScale = nullptr;  size_t capScale = 0;
-    double* sFinals = nullptr; size_t capFinals = 0;
-    double* sFids = nullptr;   size_t capFids = 0;
-};
-
 namespace {
 
 // The launch rule, in one place.  n_chunks = 1 once the samples alone give every SIMD a couple of waves; fewer samples split the
@@ -339,6 +320,37 @@ bool sweep_is_mfma(const qc_sweep_desc* d) { return 2 * d->N <= 16 && d->m <= kS
 
 }  // namespace
 
+// the pieces qc_sweep_grad.hip shares (qc_sweep_internal.h)
+int qc_sweep_fail(qc_side* h, int code, const std::string& msg) { return sfail(h, code, msg); }
+std::string* qc_sweep_err_slot() { return &g_swerr; }
+int qc_sweep_validate_desc(const qc_sweep_desc* d) { return sweep_validate(d); }
+bool qc_sweep_desc_is_mfma(const qc_sweep_desc* d) { return sweep_is_mfma(d); }
+
+int qc_sweep_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, hipStream_t st, int64_t* chunk_out,
+                           int64_t* n_chunks_out) {
+    const int m = h->d.m;
+    int64_t chunk, n_chunks;
+    sweep_chunks(S, h->d.T, &chunk, &n_chunks);
+    QC_SIDE_HIP(h, g_swerr, h->grow(&h->dTot, &h->capTot, (size_t)S * n_chunks * 256));
+    SweepParams P;
+    P.n = h->n; P.nc = h->nc; P.m = m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
+    P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks;
+    P.items = S * n_chunks;
+    P.dt_fixed = h->d.dt_fixed;
+    P.img = h->dImg;
+    const unsigned grid = (unsigned)((P.items + kSWaves - 1) / kSWaves);
+#define QC_SWEEP_LAUNCH(M_) hipLaunchKernelGGL(qc_sweep_mfma16_kernel<M_>, dim3(grid), dim3(64 * kSWaves), 0, st, P, dZ, dtheta, dscale, h->dTot)
+    if (m <= 1) QC_SWEEP_LAUNCH(1);
+    else if (m <= 2) QC_SWEEP_LAUNCH(2);
+    else if (m <= 4) QC_SWEEP_LAUNCH(4);
+    else if (m <= 6) QC_SWEEP_LAUNCH(6);
+    else QC_SWEEP_LAUNCH(8);
+#undef QC_SWEEP_LAUNCH
+    *chunk_out = chunk;
+    *n_chunks_out = n_chunks;
+    return QC_OK;
+}
+
 extern "C" const char* qc_sweep_last_error(const qc_sweep* h) { return h ? h->err.c_str() : g_swerr.c_str(); }
 
 extern "C" int64_t qc_sizeof_sweep_desc(void) { return (int64_t)sizeof(qc_sweep_desc); }
@@ -379,6 +391,7 @@ extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
     h->d = *d;
     h->device = d->device;
     h->mfma = sweep_is_mfma(d);
+    h->grad_ok = qc_sweep_grad_scope(d, &h->grad_why);      // from the caller's matrices, which the handle does not keep
     const int N = d->N, n = 2 * N, n2 = n * n, m = d->m, p = d->n_pert;
     h->n = n;
     h->nc = d->state_cols == 0 ? N : d->state_cols;
@@ -455,22 +468,8 @@ extern "C" int qc_sweep_eval_dev(qc_sweep* h, const double* dZ, const double* di
     const double* src;
     if (h->mfma) {
         int64_t chunk, n_chunks;
-        sweep_chunks(S, h->d.T, &chunk, &n_chunks);
-        QC_SIDE_HIP(h, g_swerr, h->grow(&h->dTot, &h->capTot, (size_t)S * n_chunks * 256));
-        SweepParams P;
-        P.n = n; P.nc = h->nc; P.m = m; P.p = p; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
-        P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks;
-        P.items = S * n_chunks;
-        P.dt_fixed = h->d.dt_fixed;
-        P.img = h->dImg;
-        const unsigned grid = (unsigned)((P.items + kSWaves - 1) / kSWaves);
-#define QC_SWEEP_LAUNCH(M_) hipLaunchKernelGGL(qc_sweep_mfma16_kernel<M_>, dim3(grid), dim3(64 * kSWaves), 0, st, P, dZ, dtheta, dscale, h->dTot)
-        if (m <= 1) QC_SWEEP_LAUNCH(1);
-        else if (m <= 2) QC_SWEEP_LAUNCH(2);
-        else if (m <= 4) QC_SWEEP_LAUNCH(4);
-        else if (m <= 6) QC_SWEEP_LAUNCH(6);
-        else QC_SWEEP_LAUNCH(8);
-#undef QC_SWEEP_LAUNCH
+        int rc = qc_sweep_launch_totals(h, dZ, S, dtheta, dscale, st, &chunk, &n_chunks);
+        if (rc) return rc;
         F.ld = 16; F.n_chunks = (int)n_chunks; F.src_stride = 0;
         src = dinit;
     } else {

@@ -1,0 +1,542 @@
+// Sweep gradients: the adjoint of the rollout sweep of qc_sweep.hip.  For every sample s of
+//     G_s(a) = G_drift + sum_j theta[s,j] P_j + sum_k c[s,k] a_k G_k,   x_{t+1} = E_t x_t,  E_t = exp(h_t G_s(a_t)),   F_s = phi(x_{T-1})
+// the derivatives dF_s/da_{t,k} and dF_s/dh_t of every interval, and their weighted sum over the samples as a dense gradient over Z.
+// With lambda_{T-1} = dphi/dx, lambda_t = E_t^T lambda_{t+1} and L(X; D) the Frechet derivative of exp at X in direction D,
+//     dF_s/da_{t,k} = c[s,k] h <lambda_{t+1} x_t^T, L(hG; G_k)> = c[s,k] h <L(hG^T; lambda_{t+1} x_t^T), G_k>        (L(X; .)* = L(X^T; .)),
+//     dF_s/dh_t     = <lambda_{t+1}, G x_{t+1}>:
+// ONE Frechet chain per interval gives all m drive derivatives as inner products with the drive tiles.
+//
+// Scope: the "mfma16-sweep" form (2N <= 16, m <= 8), a unitary or ket fidelity, at most 16 state columns, and ANTISYMMETRIC drift,
+// drives and perturbations (closed systems: every QuantumSystem).  Antisymmetry makes E orthogonal, which is used three times:
+//   * x_t = E^T x_{t+1} reverses the forward step exactly, so no forward state is stored inside a chunk;
+//   * E^T commutes with exp(s hG), so L(hG; E^T K) = E^T L(hG; K): with K = x_{t+1} lambda_{t+1}^T, known BEFORE the interval's
+//     exponential, the chain in direction K runs beside the Horner chain of E itself and one product with E^T follows.  The order
+//     problem (M_t needs x_t, which needs E) is gone: neither are the Horner / squaring intermediates kept, nor is the R chain computed twice;
+//   * <lambda, G x> = -sum (lambda x^T)_ab G_ba, so the timestep derivative is an inner product of tiles already in registers.
+// Everything else returns QC_ERR_UNSUPPORTED (Lindblad generators need stored forward states).
+//
+// Launches of one call:
+//   1. the forward chunk totals: qc_sweep_mfma16_kernel of qc_sweep.hip, unchanged, same chunk rule;
+//   2. qc_sweep_seed_kernel, one workgroup per sample: chains the totals in ascending order exactly as qc_sweep_finish_kernel does (the
+//      fidelities carry the bits of qc_sweep_eval), stores x at every chunk end, F_s, lambda_{T-1} = dphi/dx by the definitions of
+//      qc_fidelity.hip (|t| / n: (t_r g_r + t_i g_i) / (n^2 F), not special-cased at t = 0, as there; |t|^2 forms: 2 (t_r g_r + t_i g_i) / n^2),
+//      then chains the transposed totals back down and stores lambda at every chunk end;
+//   3. qc_sweep_grad_kernel, one wavefront per (sample, chunk), walking the chunk BACKWARDS; every matrix one 16 x 16 tile in registers
+//      (lane maps: qc_mfma_kernels.hip header; A layout: lane (g, i) reg kk = A[i][4kk+g]; B / D layout: lane (g, j) reg r = X[4r+g][j];
+//      a D-layout tile read as the A operand acts as its transpose).  Per interval, with x, lambda the D-layout tiles of knot t+1:
+//        x_A, lambda_A             one LDS round trip (two tiles transposed)
+//        KT = lambda x^T           mma(lambda_A, x_A): D layout of K^T; read as an A operand it acts as K
+//        dF/dh = -sum KT . Ga      elementwise with the generator's A-layout tile
+//        Y = h G / 2^sq, ||Y||_1 <= 1/8, dY = (h / 2^sq) K          (threshold, degree 8 and 1/k! table of the forward kernel)
+//        R_k = Y R_k+1 + I/(k-1)!,   dR_k = dY R_k+1 + Y dR_k+1      k = 8 .. 1     (12 MFMAs a step)
+//        sq squarings  dE <- E dE + dE E,  E <- E E                  (12 MFMAs and one LDS round trip each: E^T, dE^T as A operands)
+//        ZT = E^T dE                h L(hG; x_t lambda_{t+1}^T): read against an A-layout tile it is its own transpose
+//        dF/da_k = c_k sum ZT . G_k   m wave reductions in a fixed order (DPP row sums, then four row values)
+//        x <- E^T x,  lambda <- E^T lambda                            (E in D layout IS the A operand E^T: no transpose)
+//      and the m + 1 values of the interval leave through one vector store (lane k: drive k, lane m: timestep).
+//      MFMAs per interval: 4 + 8 x 12 + 12 sq + 4 + 4 + 4 = 112 + 12 sq, against the forward kernel's 40 + 4 sq (2.8x - 3x).
+//   4. qc_sweep_grad_reduce_kernel / qc_sweep_J_kernel: grad = sum_s w_s dF_s in ascending s, one thread per entry of Z (every entry that is
+//      not a control or timestep of knots 0 .. T-2 is written as +0.0); J = sum_s w_s F_s by a fixed tree.  No atomics anywhere: repeated
+//      calls give the same bits.
+//
+// Truncation of the once-differentiated series: the degree-8 polynomial's derivative misses sum_{k>=9} k ||Y||^(k-1) / k! ||dY||
+// <= 1.15 (1/8)^8 / 8! ||dY|| = 1.7e-12 ||dY||; over the 2^sq factors of the squarings the directions add up to h ||c_k G_k||, so the
+// relative error of a drive derivative is 1.7e-12, three orders inside the tests' 1e-9.  The degree stays 8.
+//
+// gfx950 cross-compile: see the table in DESIGN.md ("Sweep gradients"); no private segment, no spills in any instantiation.
+#include <math.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "qc_mfma_common.h"
+#include "qc_sweep_internal.h"
+
+namespace {
+
+using namespace qc_mfma;
+
+constexpr int kGDeg = 8;            // as the forward kernel (kSDeg, kSTh of qc_sweep.hip)
+constexpr double kGTh = 0.125;
+constexpr int kGWaves = 4;          // (sample, chunk) items per workgroup: one wave each, the waves never synchronise
+constexpr int kSeedT = 256;         // threads of the seed workgroup: the thread count of qc_sweep_finish_kernel (same sums, same bits)
+constexpr int kRedT = 256;
+
+// 1 / k!, k = 0 .. 8: the values of kSInvFact (qc_sweep.hip; a __constant__ table is private to its translation unit)
+__constant__ const double kGInvFact[kGDeg + 1] = {1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0, 1.0 / 40320.0};
+
+struct GradParams {
+    int n, nc, m, p, zdim, off_a, off_dt, n_int, chunk, n_chunks, nd;   // nd = m + (off_dt >= 0): derivatives per interval
+    long long items;             // S * n_chunks
+    double dt_fixed;
+    const double* img;           // A-layout images [matrix][kk][lane]: drift, m drives, p perturbations
+};
+
+struct SeedParams {
+    int n, ns, n_chunks, fid_kind, fid_form, fid_n;
+};
+
+struct ReduceParams {
+    int zdim, off_a, off_dt, m, nd;
+    long long T, Zlen, S;
+};
+
+template <int CTRL>
+__device__ inline double gdpp(double x) {
+    int lo = __double2loint(x), hi = __double2hiint(x);
+    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+__device__ inline v4d gimg(const double* __restrict__ img, int mat, int lane) {
+    const double* p = img + (size_t)mat * 256 + lane;
+    return v4d{p[0], p[64], p[128], p[192]};
+}
+
+__device__ __forceinline__ v4d gmma(const v4d& a, const v4d& b, v4d acc) {
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], b[kk], acc, 0, 0, 0);
+    return acc;
+}
+
+// (R, dR) <- (A R + C,  dA R + A dR): a Horner step (A = Y, dA = dY, C = I / (k-1)!) or a squaring (A = E, dA = dE, C = 0).
+// Three independent accumulator chains, interleaved.
+__device__ __forceinline__ void gstep(const v4d& A, const v4d& dA, v4d& R, v4d& dR, const v4d& C) {
+    const v4d z = {0.0, 0.0, 0.0, 0.0};
+    v4d a0 = z, a1 = z, a2 = C;
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+        a0 = __builtin_amdgcn_mfma_f64_16x16x4f64(dA[kk], R[kk], a0, 0, 0, 0);
+        a1 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[kk], dR[kk], a1, 0, 0, 0);
+        a2 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[kk], R[kk], a2, 0, 0, 0);
+    }
+    dR = a0 + a1;
+    R = a2;
+}
+
+// the sum over the 64 lanes in a fixed order, wave-uniform: row sums by DPP rotations, then (row 0 + row 1) + (row 2 + row 3)
+__device__ inline double wave_sum(double v) {
+    v += gdpp<0x128>(v);
+    v += gdpp<0x124>(v);
+    v += gdpp<0x122>(v);
+    v += gdpp<0x121>(v);
+    return (bcast_lane(v, 0) + bcast_lane(v, 16)) + (bcast_lane(v, 32) + bcast_lane(v, 48));
+}
+
+template <int M>
+__global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_grad_kernel(const GradParams P, const double* __restrict__ Z, const double* __restrict__ theta,
+                                                                         const double* __restrict__ scale, const double* __restrict__ xs,
+                                                                         const double* __restrict__ ls, double* __restrict__ gs) {
+    __shared__ double scr_all[kGWaves * 2 * 272];
+    const int lane = threadIdx.x & 63;
+    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double* __restrict__ scr = scr_all + wq * (2 * 272);
+    const long long item = (long long)blockIdx.x * kGWaves + wq;
+    if (item >= P.items) return;
+    const long long s = item / P.n_chunks;
+    const int c = (int)(item - s * P.n_chunks);
+    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
+    const int g = lane >> 4, j = lane & 15;
+    const int m = P.m;
+    const bool ft = P.off_dt >= 0;
+    const v4d IdB = identity_B(g, j);
+    const v4d zero = {0.0, 0.0, 0.0, 0.0};
+
+    // ---- once per wave: the sample's base tile, the drive tiles, the state and the adjoint at the chunk's end --------------------
+    v4d base = gimg(P.img, 0, lane);
+    for (int q = 0; q < P.p; ++q) {
+        const double th = theta[s * P.p + q];
+        const v4d Pq = gimg(P.img, 1 + m + q, lane);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) base[r] = fma(th, Pq[r], base[r]);
+    }
+    v4d Gj[M];
+#pragma unroll
+    for (int u = 0; u < M; ++u) Gj[u] = u < m ? gimg(P.img, 1 + u, lane) : zero;
+    const int kl = lane < m ? lane : (m > 0 ? m - 1 : 0);
+    const double cl = (scale && m > 0) ? scale[s * m + kl] : 1.0;
+
+    v4d x, lam;
+    {
+        const int ns = P.n * P.nc;
+        const double* __restrict__ xe = xs + item * ns;
+        const double* __restrict__ le = ls + item * ns;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 4 * r + g;
+            const bool in = row < P.n && j < P.nc;
+            x[r] = in ? xe[row + P.n * j] : 0.0;
+            lam[r] = in ? le[row + P.n * j] : 0.0;
+        }
+    }
+
+    const double hfix = opaque_scalar(P.dt_fixed);
+    const double* __restrict__ z = Z + (long long)(t1 - 1) * P.zdim;
+    double av = m > 0 ? z[P.off_a + kl] : 0.0;
+    double h = ft ? z[P.off_dt] : hfix;
+#pragma unroll 1
+    for (int t = t1 - 1; t >= t0; --t) {
+        // the previous interval's controls and timestep are requested before this interval's products
+        const double* __restrict__ zn = Z + (long long)(t > t0 ? t - 1 : t) * P.zdim;
+        const double av_n = m > 0 ? zn[P.off_a + kl] : 0.0;
+        const double h_n = ft ? zn[P.off_dt] : hfix;
+        const double al = av * cl;
+        v4d Ga = base;
+#pragma unroll
+        for (int u = 0; u < M; ++u) {
+            const double a = u < m ? bcast_lane(al, u) : 0.0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Ga[r] = fma(a, Gj[u][r], Ga[r]);
+        }
+        // the number of squarings: the rule of the forward kernel
+        int sq = 0;
+        {
+            double best = 0.0;
+            bool bad = false;
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                double cs = fabs(h * Ga[kk]);
+                cs += gdpp<0x128>(cs);
+                cs += gdpp<0x124>(cs);
+                cs += gdpp<0x122>(cs);
+                cs += gdpp<0x121>(cs);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double v = bcast_lane(cs, 16 * r);
+                    if (!(v == v) || v > 1e300) bad = true;
+                    best = fmax(best, v);
+                }
+            }
+            if (!bad && best > kGTh) {
+                int e;
+                (void)frexp(best / kGTh, &e);
+                sq = e;
+                if (ldexp(kGTh, e - 1) >= best) sq = e - 1;
+                sq = sq < 0 ? 0 : (sq > 60 ? 60 : sq);
+            }
+            sq = __builtin_amdgcn_readfirstlane(sq);
+        }
+        const double hs = h * ldexp(1.0, -sq);
+        // K^T = lambda x^T of knot t+1 (D layout) from the A-layout forms of both
+        v4d KT;
+        {
+            const v4d in[2] = {x, lam};
+            v4d tr[2];
+            lds_transpose16_multi<2>(scr, in, tr, g, j);
+            KT = gmma(tr[1], tr[0], zero);
+        }
+        // M = 8: kept loop-invariant, the eight lane compares below live in 16 scalar registers and the kernel spills one; an opaque
+        // copy of the lane index has them made per interval instead (8 v_cmp)
+        int ln = lane;
+        if constexpr (M >= 8) asm volatile("" : "+v"(ln));
+        double out = 0.0;
+        if (ft) {
+            double ph = 0.0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ph = fma(KT[r], Ga[r], ph);
+            const double dh = -wave_sum(ph);
+            out = ln == m ? dh : out;
+        }
+        const v4d Y = hs * Ga;
+        const v4d dY = hs * KT;
+        v4d R = kGInvFact[kGDeg] * IdB;
+        v4d dR = zero;
+#pragma unroll 1
+        for (int k = kGDeg; k >= 1; --k) gstep(Y, dY, R, dR, kGInvFact[k - 1] * IdB);
+        for (int q = 0; q < sq; ++q) {
+            const v4d in[2] = {R, dR};
+            v4d tr[2];
+            lds_transpose16_multi<2>(scr, in, tr, g, j);      // E^T, dE^T in D layout = E, dE in A layout
+            gstep(tr[0], tr[1], R, dR, zero);
+        }
+        const v4d ZT = gmma(R, dR, zero);                       // E^T dE
+#pragma unroll
+        for (int u = 0; u < M; ++u) {
+            if (u < m) {
+                double pu = 0.0;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) pu = fma(ZT[r], Gj[u][r], pu);
+                const double du = wave_sum(pu);
+                out = ln == u ? du * cl : out;
+            }
+        }
+        if (lane < P.nd) gs[(s * P.n_int + t) * P.nd + lane] = out;
+        x = gmma(R, x, zero);
+        lam = gmma(R, lam, zero);
+        av = av_n;
+        h = h_n;
+    }
+}
+
+// One workgroup per sample.  Up: x = Q_c ... Q_0 init with the loops of qc_sweep_finish_kernel, x stored at every chunk end; F_s and
+// lambda = dphi/dx at the final state.  Down: lambda <- Q_c^T lambda, stored at every chunk end.
+__global__ __launch_bounds__(kSeedT) void qc_sweep_seed_kernel(const SeedParams F, const double* __restrict__ tot, const double* __restrict__ src,
+                                                               const double* __restrict__ gr, const double* __restrict__ gi,
+                                                               double* __restrict__ xs, double* __restrict__ ls, double* __restrict__ fids) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    __shared__ double red[2][kSeedT / 64];
+    __shared__ double coef[3];
+    const int tid = threadIdx.x, n = F.n, ns = F.ns, ld = 16, l2 = 256;
+    const long long s = blockIdx.x;
+    double* cur = sm;
+    double* nxt = sm + ns;
+    double* Q = sm + 2 * ns;
+    for (int idx = tid; idx < ns; idx += kSeedT) cur[idx] = src[idx];
+    const double* __restrict__ Qs = tot + s * F.n_chunks * (long long)l2;
+    double* __restrict__ xo = xs + s * F.n_chunks * (long long)ns;
+    double* __restrict__ lo = ls + s * F.n_chunks * (long long)ns;
+    for (int c = 0; c < F.n_chunks; ++c) {
+        __syncthreads();
+        for (int idx = tid; idx < l2; idx += kSeedT) Q[idx] = Qs[(long long)c * l2 + idx];
+        __syncthreads();
+        for (int idx = tid; idx < ns; idx += kSeedT) {
+            const int r = idx % n, col = idx / n;
+            double acc = 0.0;
+            for (int q = 0; q < n; ++q) acc = fma(Q[r + ld * q], cur[q + n * col], acc);
+            nxt[idx] = acc;
+            xo[(long long)c * ns + idx] = acc;
+        }
+        double* tmp = cur; cur = nxt; nxt = tmp;
+    }
+    __syncthreads();
+    double ar = 0.0, ai = 0.0;
+    for (int i = tid; i < ns; i += kSeedT) {
+        const double xi = cur[i];
+        ar = fma(gr[i], xi, ar);
+        ai = fma(gi[i], xi, ai);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        ar += __shfl_xor(ar, off, 64);
+        ai += __shfl_xor(ai, off, 64);
+    }
+    if ((tid & 63) == 0) { red[0][tid >> 6] = ar; red[1][tid >> 6] = ai; }
+    __syncthreads();
+    if (tid == 0) {
+        const double tr = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        const double ti = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        const double nn = (double)F.fid_n;
+        double Fv, fac;      // the mapping and the gradient factor of qc_fidelity_kernel (qc_fidelity.hip)
+        if (F.fid_kind == QC_FID_UNITARY) {
+            if (F.fid_form == QC_FID_FORM_ABS2) { Fv = (tr * tr + ti * ti) / (nn * nn); fac = 2.0 / (nn * nn); }
+            else { Fv = sqrt(tr * tr + ti * ti) / nn; fac = 1.0 / (nn * nn * Fv); }
+        } else { Fv = tr * tr + ti * ti; fac = 2.0; }
+        fids[s] = Fv;
+        coef[0] = tr; coef[1] = ti; coef[2] = fac;
+    }
+    __syncthreads();
+    const double tr = coef[0], ti = coef[1], fac = coef[2];
+    for (int idx = tid; idx < ns; idx += kSeedT) {
+        const double v = (tr * gr[idx] + ti * gi[idx]) * fac;
+        cur[idx] = v;
+        lo[(long long)(F.n_chunks - 1) * ns + idx] = v;
+    }
+    for (int c = F.n_chunks - 1; c >= 1; --c) {
+        __syncthreads();
+        for (int idx = tid; idx < l2; idx += kSeedT) Q[idx] = Qs[(long long)c * l2 + idx];
+        __syncthreads();
+        for (int idx = tid; idx < ns; idx += kSeedT) {
+            const int r = idx % n, col = idx / n;
+            double acc = 0.0;
+            for (int q = 0; q < n; ++q) acc = fma(Q[q + ld * r], cur[q + n * col], acc);
+            nxt[idx] = acc;
+            lo[(long long)(c - 1) * ns + idx] = acc;
+        }
+        double* tmp = cur; cur = nxt; nxt = tmp;
+    }
+}
+
+// grad[i] = sum_s w_s dF_s/dZ_i in ascending s for the controls and timesteps of knots 0 .. T-2, +0.0 everywhere else
+__global__ __launch_bounds__(kRedT) void qc_sweep_grad_reduce_kernel(const ReduceParams R, const double* __restrict__ gs, const double* __restrict__ w,
+                                                                     double* __restrict__ grad) {
+    const long long i = (long long)blockIdx.x * kRedT + threadIdx.x;
+    if (i >= R.Zlen) return;
+    const long long t = i / R.zdim;
+    const int o = (int)(i - t * R.zdim);
+    int k = -1;
+    if (t < R.T - 1) {
+        if (o >= R.off_a && o < R.off_a + R.m) k = o - R.off_a;
+        else if (o == R.off_dt) k = R.m;       // off_dt = -1: never
+    }
+    double acc = 0.0;
+    if (k >= 0) {
+        const long long stride = (R.T - 1) * R.nd;
+        const double* __restrict__ p = gs + t * R.nd + k;
+        const double w1 = 1.0 / (double)R.S;
+        for (long long s = 0; s < R.S; ++s) acc = fma(w ? w[s] : w1, p[s * stride], acc);
+    }
+    grad[i] = acc;
+}
+
+// J = sum_s w_s F_s: thread i sums s = i, i + 256, ... in ascending order, then a fixed tree over the 256 partial sums
+__global__ __launch_bounds__(kRedT) void qc_sweep_J_kernel(long long S, const double* __restrict__ fids, const double* __restrict__ w, double* __restrict__ J) {
+    __shared__ double part[kRedT];
+    const int tid = threadIdx.x;
+    const double w1 = 1.0 / (double)S;
+    double acc = 0.0;
+    for (long long s = tid; s < S; s += kRedT) acc = fma(w ? w[s] : w1, fids[s], acc);
+    part[tid] = acc;
+    __syncthreads();
+    for (int off = kRedT / 2; off > 0; off >>= 1) {
+        if (tid < off) part[tid] += part[tid + off];
+        __syncthreads();
+    }
+    if (tid == 0) *J = part[0];
+}
+
+int gfail(qc_side* h, int code, const std::string& msg) { return qc_sweep_fail(h, code, msg); }
+
+}  // namespace
+
+// The tolerance of the antisymmetry test: max |G + G^T| <= 64 eps max |G| per matrix.  iso generators of exactly Hermitian operators are
+// exactly antisymmetric; 64 eps admits operators that were symmetrised or scaled in floating point, and stays ten orders below any
+// dissipator worth the name.
+bool qc_sweep_grad_scope(const qc_sweep_desc* d, std::string* why) {
+    const int n = 2 * d->N;
+    if (!qc_sweep_desc_is_mfma(d)) {
+        *why = n > 16 ? "the handle takes the rollout-per-sample form (2N = " + std::to_string(n) + " > 16)"
+                      : "the handle takes the rollout-per-sample form (" + std::to_string(d->m) + " drives > 8)";
+        return false;
+    }
+    const double* sets[3] = {d->G_drift, d->G_drives, d->G_pert};
+    const int counts[3] = {1, d->m, d->n_pert};
+    const char* names[3] = {"G_drift", "drive generator", "perturbation generator"};
+    for (int q = 0; q < 3; ++q)
+        for (int k = 0; k < counts[q]; ++k) {
+            const double* G = sets[q] + (size_t)k * n * n;
+            double big = 0.0, asym = 0.0;
+            for (int c = 0; c < n; ++c)
+                for (int r = 0; r < n; ++r) {
+                    big = fmax(big, fabs(G[(size_t)c * n + r]));
+                    asym = fmax(asym, fabs(G[(size_t)c * n + r] + G[(size_t)r * n + c]));
+                }
+            if (!(asym <= 64.0 * 2.220446049250313e-16 * big)) {
+                *why = std::string(names[q]) + (q ? " " + std::to_string(k) : std::string()) +
+                       " is not antisymmetric (open-system generators are not served: their gradients need stored forward states)";
+                return false;
+            }
+        }
+    const int nc = d->state_cols == 0 ? d->N : d->state_cols;
+    if (nc > 16) { *why = "states of more than 16 columns are not served (state_cols = " + std::to_string(nc) + ")"; return false; }
+    if (d->fid_kind == QC_SWEEP_FID_NONE) { *why = "the handle has no fidelity (QC_SWEEP_FID_NONE)"; return false; }
+    if (d->fid_kind == QC_FID_DENSITY) { *why = "the density-operator fidelity is not served"; return false; }
+    return true;
+}
+
+extern "C" int qc_sweep_desc_grad_supported(const qc_sweep_desc* d, int32_t* supported) {
+    int rc = qc_sweep_validate_desc(d);
+    if (rc) return rc;
+    if (!supported) return gfail(nullptr, QC_ERR_INVALID, "qc_sweep_desc_grad_supported: supported is NULL");
+    std::string why;
+    const bool ok = qc_sweep_grad_scope(d, &why);
+    *supported = ok ? 1 : 0;
+    if (!ok) (void)gfail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep gradients: " + why);
+    return QC_OK;
+}
+
+extern "C" int qc_sweep_grad_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
+                                 const double* dweights, double* dfids, double* dJ, double* dgrad, double* dgrad_samples, void* stream) {
+    if (!h) return gfail(nullptr, QC_ERR_INVALID, "qc_sweep_grad_dev: NULL handle");
+    if (!h->grad_ok) return gfail(h, QC_ERR_UNSUPPORTED, "qc_sweep gradients: " + h->grad_why);
+    if (!dZ || !dinit) return gfail(h, QC_ERR_INVALID, "qc_sweep_grad_dev: NULL input");
+    if (S < 1 || S > (1ll << 24)) return gfail(h, QC_ERR_INVALID, "qc_sweep_grad_dev: S must be in 1 .. 2^24");
+    if (h->d.n_pert > 0 && !dtheta) return gfail(h, QC_ERR_INVALID, "qc_sweep_grad_dev: theta is NULL but the handle has perturbations");
+    if (!dfids && !dJ && !dgrad && !dgrad_samples) return gfail(h, QC_ERR_INVALID, "qc_sweep_grad_dev: every output is NULL");
+    std::string& slot = *qc_sweep_err_slot();
+    qc_device_guard guard(h->device);
+    QC_SIDE_HIP(h, slot, guard.err);
+    hipStream_t st = (hipStream_t)stream;
+    const int m = h->d.m;
+    const int nd = m + (h->d.off_dt >= 0 ? 1 : 0);
+    const int64_t n_int = h->d.T - 1;
+    int64_t chunk, n_chunks;
+    int rc = qc_sweep_launch_totals(h, dZ, S, dtheta, dscale, st, &chunk, &n_chunks);
+    if (rc) return rc;
+    const size_t n_state = (size_t)S * n_chunks * h->ns;
+    QC_SIDE_HIP(h, slot, h->grow(&h->dXs, &h->capXs, n_state));
+    QC_SIDE_HIP(h, slot, h->grow(&h->dLs, &h->capLs, n_state));
+    if (!dfids) {
+        QC_SIDE_HIP(h, slot, h->grow(&h->dGfid, &h->capGfid, (size_t)S));
+        dfids = h->dGfid;
+    }
+    const bool want_grad = dgrad || dgrad_samples;
+    double* gsamp = dgrad_samples;
+    if (want_grad && !gsamp && nd > 0) {
+        QC_SIDE_HIP(h, slot, h->grow(&h->dGsamp, &h->capGsamp, (size_t)S * n_int * nd));
+        gsamp = h->dGsamp;
+    }
+    SeedParams F;
+    F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
+    F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;
+    const size_t lds = ((size_t)2 * h->ns + 256) * 8;
+    hipLaunchKernelGGL(qc_sweep_seed_kernel, dim3((unsigned)S), dim3(kSeedT), lds, st, F, (const double*)h->dTot, dinit, (const double*)h->dgr,
+                       (const double*)h->dgi, h->dXs, h->dLs, dfids);
+    if (want_grad && nd > 0) {
+        GradParams P;
+        P.n = h->n; P.nc = h->nc; P.m = m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
+        P.n_int = (int)n_int; P.chunk = (int)chunk; P.n_chunks = (int)n_chunks; P.nd = nd;
+        P.items = S * n_chunks;
+        P.dt_fixed = h->d.dt_fixed;
+        P.img = h->dImg;
+        const unsigned grid = (unsigned)((P.items + kGWaves - 1) / kGWaves);
+#define QC_GRAD_LAUNCH(M_) hipLaunchKernelGGL(qc_sweep_grad_kernel<M_>, dim3(grid), dim3(64 * kGWaves), 0, st, P, dZ, dtheta, dscale, \
+                                              (const double*)h->dXs, (const double*)h->dLs, gsamp)
+        if (m <= 1) QC_GRAD_LAUNCH(1);
+        else if (m <= 2) QC_GRAD_LAUNCH(2);
+        else if (m <= 4) QC_GRAD_LAUNCH(4);
+        else if (m <= 6) QC_GRAD_LAUNCH(6);
+        else QC_GRAD_LAUNCH(8);
+#undef QC_GRAD_LAUNCH
+    }
+    if (dgrad) {
+        ReduceParams R;
+        R.zdim = h->d.zdim; R.off_a = h->d.off_a; R.off_dt = h->d.off_dt; R.m = m; R.nd = nd;
+        R.T = h->d.T; R.Zlen = h->Zlen; R.S = S;
+        hipLaunchKernelGGL(qc_sweep_grad_reduce_kernel, dim3((unsigned)((h->Zlen + kRedT - 1) / kRedT)), dim3(kRedT), 0, st, R, (const double*)gsamp,
+                           dweights, dgrad);
+    }
+    if (dJ) hipLaunchKernelGGL(qc_sweep_J_kernel, dim3(1), dim3(kRedT), 0, st, (long long)S, (const double*)dfids, dweights, dJ);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return gfail(h, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return QC_OK;
+}
+
+extern "C" int qc_sweep_grad(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
+                             const double* weights, double* fids, double* J, double* grad, double* grad_samples) {
+    if (!h) return gfail(nullptr, QC_ERR_INVALID, "qc_sweep_grad: NULL handle");
+    if (!h->grad_ok) return gfail(h, QC_ERR_UNSUPPORTED, "qc_sweep gradients: " + h->grad_why);
+    if (!Z || !init) return gfail(h, QC_ERR_INVALID, "qc_sweep_grad: NULL input");
+    if (S < 1 || S > (1ll << 24)) return gfail(h, QC_ERR_INVALID, "qc_sweep_grad: S must be in 1 .. 2^24");
+    const int m = h->d.m, p = h->d.n_pert;
+    if (p > 0 && !theta) return gfail(h, QC_ERR_INVALID, "qc_sweep_grad: theta is NULL but the handle has perturbations");
+    if (!fids && !J && !grad && !grad_samples) return gfail(h, QC_ERR_INVALID, "qc_sweep_grad: every output is NULL");
+    std::string& slot = *qc_sweep_err_slot();
+    qc_device_guard guard(h->device);
+    QC_SIDE_HIP(h, slot, guard.err);
+    const bool use_scale = scale && m > 0;
+    const size_t n_samp = (size_t)S * (size_t)(h->d.T - 1) * (size_t)(m + (h->d.off_dt >= 0 ? 1 : 0));
+    if (p) QC_SIDE_HIP(h, slot, h->grow(&h->sTheta, &h->capTheta, (size_t)S * p));
+    if (use_scale) QC_SIDE_HIP(h, slot, h->grow(&h->sScale, &h->capScale, (size_t)S * m));
+    if (weights) QC_SIDE_HIP(h, slot, h->grow(&h->sW, &h->capW, (size_t)S));
+    if (fids) QC_SIDE_HIP(h, slot, h->grow(&h->sFids, &h->capFids, (size_t)S));
+    if (grad_samples && n_samp) QC_SIDE_HIP(h, slot, h->grow(&h->sGradS, &h->capGradS, n_samp));
+    if (grad && !h->sGrad) QC_SIDE_HIP(h, slot, h->alloc(&h->sGrad, (size_t)h->Zlen));
+    if (J && !h->sJ) QC_SIDE_HIP(h, slot, h->alloc(&h->sJ, (size_t)1));
+    QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sZ, Z, (size_t)h->Zlen * 8, hipMemcpyHostToDevice, h->stream));
+    QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sInit, init, (size_t)h->ns * 8, hipMemcpyHostToDevice, h->stream));
+    if (p) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sTheta, theta, (size_t)S * p * 8, hipMemcpyHostToDevice, h->stream));
+    if (use_scale) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sScale, scale, (size_t)S * m * 8, hipMemcpyHostToDevice, h->stream));
+    if (weights) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sW, weights, (size_t)S * 8, hipMemcpyHostToDevice, h->stream));
+    const bool samp = grad_samples && n_samp;
+    int rc = qc_sweep_grad_dev(h, h->sZ, h->sInit, S, p ? h->sTheta : nullptr, use_scale ? h->sScale : nullptr, weights ? h->sW : nullptr,
+                               fids ? h->sFids : nullptr, J ? h->sJ : nullptr, grad ? h->sGrad : nullptr, samp ? h->sGradS : nullptr, h->stream);
+    if (rc) return rc;
+    if (fids) QC_SIDE_HIP(h, slot, hipMemcpyAsync(fids, h->sFids, (size_t)S * 8, hipMemcpyDeviceToHost, h->stream));
+    if (J) QC_SIDE_HIP(h, slot, hipMemcpyAsync(J, h->sJ, 8, hipMemcpyDeviceToHost, h->stream));
+    if (grad) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad, h->sGrad, (size_t)h->Zlen * 8, hipMemcpyDeviceToHost, h->stream));
+    if (samp) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad_samples, h->sGradS, n_samp * 8, hipMemcpyDeviceToHost, h->stream));
+    QC_SIDE_HIP(h, slot, hipStreamSynchronize(h->stream));
+    return QC_OK;
+}

@@ -1,0 +1,48 @@
+// What qc_sweep.hip (forward sweep) and qc_sweep_grad.hip (its adjoint) share: the handle, the descriptor checks and the launch of the
+// forward chunk totals (with it the chunk rule).  Not part of the ABI.
+#pragma once
+
+#include <string>
+
+#include "qc_side.h"
+
+struct qc_sweep : qc_side {
+    qc_sweep_desc d;             // caller-owned arrays are not retained (pointers nulled)
+    bool mfma = false;
+    bool grad_ok = false;        // the gradient's scope (qc_sweep_grad.hip), decided at create from the caller's matrices
+    std::string grad_why;        // when not: the reason
+    int n = 0, nc = 0, ns = 0, fid_n = 0;
+    int64_t Zlen = 0;
+    double* dG = nullptr;        // (1 + m + p) matrices, column-major (per-sample form)
+    double* dImg = nullptr;      // their A-layout images (MFMA form)
+    double *dgr = nullptr, *dgi = nullptr;
+    // scratch of the "_dev" entry point, grown at the first call that needs it
+    double* dTot = nullptr;  size_t capTot = 0;
+    double* dFin = nullptr;  size_t capFin = 0;
+    double *dGs = nullptr, *dRE = nullptr, *dRQ = nullptr, *dRS = nullptr, *dRout = nullptr;
+    // staging of the host-buffer entry point
+    double *sZ = nullptr, *sInit = nullptr;
+    double* sTheta = nullptr;  size_t capTheta = 0;
+    double* sScale = nullptr;  size_t capScale = 0;
+    double* sFinals = nullptr; size_t capFinals = 0;
+    double* sFids = nullptr;   size_t capFids = 0;
+    // gradient: states and adjoints at the chunk ends, per-sample derivatives, fidelities; staging of its host-buffer entry point
+    double* dXs = nullptr;   size_t capXs = 0;
+    double* dLs = nullptr;   size_t capLs = 0;
+    double* dGsamp = nullptr; size_t capGsamp = 0;
+    double* dGfid = nullptr; size_t capGfid = 0;
+    double* sW = nullptr;    size_t capW = 0;
+    double* sGradS = nullptr; size_t capGradS = 0;
+    double *sGrad = nullptr, *sJ = nullptr;
+};
+
+// records the message in the handle (when there is one) and in the slot qc_sweep_last_error(NULL) returns
+int qc_sweep_fail(qc_side* h, int code, const std::string& msg);
+std::string* qc_sweep_err_slot();
+int qc_sweep_validate_desc(const qc_sweep_desc* d);
+bool qc_sweep_desc_is_mfma(const qc_sweep_desc* d);
+// "mfma16-sweep" handles: grows h->dTot and launches qc_sweep_mfma16_kernel on `st` (S x n_chunks tiles of 256 doubles)
+int qc_sweep_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, hipStream_t st, int64_t* chunk,
+                           int64_t* n_chunks);
+// device-free: is this (valid) descriptor inside the gradient's scope?  `why` receives the reason when it is not.
+bool qc_sweep_grad_scope(const qc_sweep_desc* d, std::string* why);

@@ -729,3 +729,103 @@ class UnitaryRobustnessObjective:
             self.close()
         except Exception:
             pass
+
+
+class SweepInfidelityObjective:
+    """L(Z) = 1 - sum_s w_s F_s: the mean (weighted) infidelity of the trajectory's pulse over S perturbed systems
+
+        G_s(a) = G_drift + sum_j theta[s, j] P_j + sum_k scale[s, k] a_k G_k,
+
+    each F_s the fidelity of the rollout from the trajectory's initial state to its goal (`RolloutSweep.grad`: one adjoint sweep per
+    gradient, whatever the number of drives).  `L(Z)`, `grad_L(Z)` (dense, length `len(Z)`; only the controls and timesteps carry
+    entries).  First order only: `hess_structure` is empty and `hess_L` raises, so the term belongs in a
+    `QuantumControlEvaluator(eval_hessian=False)`.  The layout comes from the trajectory: `traj.dim`, the offsets of `control_name`
+    and of the timestep, `traj.global_dim`.
+
+    state_name  a unitary component (2 N^2 entries: unitary fidelity, `subspace`, `form`) or a ket component (2 N entries)
+    theta       S x len(perturbations);  scale  S x n_drives or None;  weights  S values or None (1/S each)"""
+    _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
+
+    def __init__(self, traj: NamedTrajectory, system, perturbations, theta, scale=None, weights=None, state_name: str = "Ũ⃗",
+                 control_name: str = "a", subspace=None, form: str = "abs", device: int = 0):
+        from .rollouts import RolloutSweep
+        self._sweep = None
+        if state_name not in traj.components:
+            raise ValueError(f"the trajectory has no component {state_name}")
+        if control_name not in traj.components:
+            raise ValueError(f"the trajectory has no component {control_name}")
+        if form not in ("abs", "abs2"):
+            raise ValueError("form must be 'abs' or 'abs2'")
+        N, m = system.state_levels, system.n_drives
+        if len(traj.components[control_name]) != m:
+            raise ValueError(f"component {control_name} has {len(traj.components[control_name])} rows, the system has {m} drives")
+        s = len(traj.components[state_name])
+        if s == 2 * N * N and N > 1:
+            kind, cols = "unitary", N
+        elif s == 2 * N:
+            kind, cols = "ket", 1
+        else:
+            raise ValueError(f"component {state_name} has length {s}: neither a unitary (2 N^2) nor a ket (2 N) of N = {N} levels")
+        if kind == "ket" and (subspace is not None or form != "abs"):
+            raise ValueError("subspace and form apply to a unitary component only")
+        if state_name not in traj.goal:
+            raise ValueError(f"the trajectory has no goal for {state_name}")
+        init = traj.initial.get(state_name)
+        if init is None:
+            init = traj[state_name][:, 0]
+        from .rollouts import _sweep_samples
+        self.S, self._theta, self._scale = _sweep_samples(len(perturbations), m, theta, scale)
+        self._weights = None
+        if weights is not None:
+            self._weights = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+            if self._weights.size != self.S:
+                raise ValueError(f"weights must have {self.S} entries")
+        free = isinstance(traj.timestep, str)
+        self.traj = traj
+        self.Z_len = traj.T * traj.dim + traj.global_dim
+        self._init = np.ascontiguousarray(init, dtype=np.float64).ravel()
+        sw = RolloutSweep(system, perturbations, traj.T, cols=cols, goal=np.asarray(traj.goal[state_name], dtype=np.float64), fid_kind=kind,
+                          subspace=subspace, fid_form=_lib.QC_FID_FORM_ABS2 if form == "abs2" else _lib.QC_FID_FORM_ABS, zdim=traj.dim,
+                          off_a=traj.offset(control_name), off_dt=traj.offset(traj.timestep) if free else -1,
+                          dt_fixed=None if free else float(traj.timestep), global_dim=traj.global_dim, device=device)
+        self._sweep = sw
+        if not sw.grad_supported:
+            why = sw.grad_unsupported_reason
+            sw.close()
+            raise _lib.QCollocError(_lib.QC_ERR_UNSUPPORTED, why)
+        self.hess_structure = (np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64))
+
+    def J_fids_grad(self, Z):
+        """(J, fids, dJ/dZ) of one adjoint sweep."""
+        return self._sweep.grad(Z, self._init, self._theta, self._scale, self._weights)
+
+    def fidelities(self, Z) -> np.ndarray:
+        return self._sweep.eval(Z, self._init, self._theta, self._scale, finals=False)[1]
+
+    def L(self, Z) -> float:
+        f = self.fidelities(Z)
+        w = np.full(self.S, 1.0 / self.S) if self._weights is None else self._weights
+        return 1.0 - float(np.dot(w, f))
+
+    def grad_L(self, Z) -> np.ndarray:
+        return -self.J_fids_grad(Z)[2]
+
+    def hess_L(self, Z):
+        raise RuntimeError("SweepInfidelityObjective is first order: build the evaluator with eval_hessian=False")
+
+    def __getattr__(self, name):
+        al = type(self)._ALIASES
+        if name in al:
+            return getattr(self, al[name])
+        raise AttributeError(name)
+
+    def close(self):
+        if getattr(self, "_sweep", None) is not None:
+            self._sweep.close()
+            self._sweep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -131,6 +131,28 @@ def _sweep_generators(system, perturbations) -> list:
     return out
 
 
+def _sweep_samples(p: int, m: int, theta, scale):
+    """(S, theta S x p or None, scale S x m or None) from what the caller passed."""
+    theta = None if theta is None else np.asarray(theta, dtype=np.float64)
+    if theta is not None and theta.ndim == 1:
+        theta = theta.reshape(-1, 1) if p == 1 else theta.reshape(-1, p)
+    scale = None if scale is None else np.asarray(scale, dtype=np.float64)
+    if scale is not None and scale.ndim == 1:
+        scale = scale.reshape(-1, 1) if m == 1 else scale.reshape(-1, m)
+    if theta is None and scale is None:
+        raise ValueError("theta (S x n_pert) or scale (S x m) must give the number of samples")
+    S = theta.shape[0] if theta is not None else scale.shape[0]
+    if theta is not None and theta.shape != (S, p):
+        raise ValueError(f"theta must be S x {p}")
+    if p and theta is None:
+        raise ValueError("theta is required: the handle has perturbations")
+    if scale is not None and scale.shape != (S, m):
+        raise ValueError(f"scale must be {S} x {m}")
+    if S < 1:
+        raise ValueError("at least one sample")
+    return S, (np.ascontiguousarray(theta) if p else None), (np.ascontiguousarray(scale) if scale is not None and m else None)
+
+
 class RolloutSweep:
     """S rollouts of one trajectory of controls under S perturbed systems, final states and fidelities only:
 
@@ -217,24 +239,7 @@ class RolloutSweep:
         return Z
 
     def _samples(self, theta, scale):
-        theta = None if theta is None else np.asarray(theta, dtype=np.float64)
-        if theta is not None and theta.ndim == 1:
-            theta = theta.reshape(-1, 1) if self.p == 1 else theta.reshape(-1, self.p)
-        scale = None if scale is None else np.asarray(scale, dtype=np.float64)
-        if scale is not None and scale.ndim == 1:
-            scale = scale.reshape(-1, 1) if self.m == 1 else scale.reshape(-1, self.m)
-        if theta is None and scale is None:
-            raise ValueError("theta (S x n_pert) or scale (S x m) must give the number of samples")
-        S = theta.shape[0] if theta is not None else scale.shape[0]
-        if theta is not None and theta.shape != (S, self.p):
-            raise ValueError(f"theta must be S x {self.p}")
-        if self.p and theta is None:
-            raise ValueError("theta is required: the handle has perturbations")
-        if scale is not None and scale.shape != (S, self.m):
-            raise ValueError(f"scale must be {S} x {self.m}")
-        if S < 1:
-            raise ValueError("at least one sample")
-        return S, (np.ascontiguousarray(theta) if self.p else None), (np.ascontiguousarray(scale) if scale is not None and self.m else None)
+        return _sweep_samples(self.p, self.m, theta, scale)
 
     def eval(self, Z, init, theta, scale=None, finals: bool = True, fids: Optional[bool] = None):
         """(finals, fids): finals (2N cols) x S or None; fids S values or None (default: when the handle has a fidelity)."""
@@ -273,6 +278,74 @@ class RolloutSweep:
         rc = _lib.lib.qc_sweep_eval_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, dtheta.data_ptr() if (dtheta is not None and self.p) else None,
                                         dscale.data_ptr() if (dscale is not None and self.m) else None,
                                         dfinals.data_ptr() if dfinals is not None else None, dfids.data_ptr() if dfids is not None else None, s)
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+
+    # -- gradients: the adjoint of the sweep -------------------------------------------------------------------------------------
+    @property
+    def n_deriv(self) -> int:
+        """Derivatives per interval and sample: the m drives, then the timestep when the trajectory vector carries it."""
+        return self.m + (1 if self.off_dt >= 0 else 0)
+
+    @property
+    def grad_supported(self) -> bool:
+        """Does `grad` serve this handle?  (`qc_sweep_desc_grad_supported`: the MFMA form, a unitary or ket fidelity, at most 16
+        state columns, antisymmetric generators.)  `grad_unsupported_reason` says why not."""
+        return self._grad_scope()[0]
+
+    @property
+    def grad_unsupported_reason(self) -> Optional[str]:
+        return self._grad_scope()[1]
+
+    def _grad_scope(self):
+        ok = C.c_int32()
+        rc = _lib.lib.qc_sweep_desc_grad_supported(C.byref(self._desc), C.byref(ok))
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(None).decode())
+        return bool(ok.value), (None if ok.value else _lib.lib.qc_sweep_last_error(None).decode())
+
+    def grad(self, Z, init, theta, scale=None, weights=None, per_sample: bool = False):
+        """(J, fids, grad[, grad_samples]): J = sum_s w_s F_s (weights: S values, default 1/S each), the S fidelities, the dense
+        gradient of J over the trajectory vector (zero outside the controls and timesteps of knots 0 .. T-2) and, with
+        `per_sample`, dF_s/d(a_t, dt_t) as an S x (T-1) x n_deriv array (drives, then the timestep)."""
+        Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
+        if Z.size != self.Z_len:
+            raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
+        init = np.ascontiguousarray(init, dtype=np.float64).ravel()
+        if init.size != self.ns:
+            raise ValueError(f"initial state has length {init.size}, expected {self.ns}")
+        S, theta, scale = self._samples(theta, scale)
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+            if weights.size != S:
+                raise ValueError(f"weights must have {S} entries")
+        f, J, g = np.empty(S), C.c_double(), np.empty(self.Z_len)
+        gs = np.empty((S, self.T - 1, self.n_deriv)) if per_sample else None
+        opt = lambda a: _lib.dptr(a) if a is not None else None
+        rc = _lib.lib.qc_sweep_grad(self._h, _lib.dptr(Z), _lib.dptr(init), S, opt(theta), opt(scale), opt(weights), _lib.dptr(f), C.byref(J),
+                                    _lib.dptr(g), opt(gs) if (per_sample and gs.size) else None)
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        return (J.value, f, g, gs) if per_sample else (J.value, f, g)
+
+    def grad_device(self, dZ, dinit, S: int, dtheta=None, dscale=None, dweights=None, dfids=None, dJ=None, dgrad=None, dgrad_samples=None,
+                    stream=None):
+        """Device-resident gradient on torch CUDA tensors (float64), asynchronous on `stream`: `qc_sweep_grad_dev`.  Outputs are
+        optional one at a time: dfids S, dJ one value, dgrad Z_len, dgrad_samples S x (T-1) x n_deriv."""
+        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        S = int(S)
+        if dfids is None and dJ is None and dgrad is None and dgrad_samples is None:
+            raise ValueError("every output is None")
+        for t, cnt, what in ((dZ, self.Z_len, "dZ"), (dinit, self.ns, "dinit"), (dtheta, S * self.p, "dtheta"), (dscale, S * self.m, "dscale"),
+                             (dweights, S, "dweights"), (dfids, S, "dfids"), (dJ, 1, "dJ"), (dgrad, self.Z_len, "dgrad"),
+                             (dgrad_samples, S * (self.T - 1) * self.n_deriv, "dgrad_samples")):
+            if t is not None and (t.numel() != cnt or t.dtype != torch.float64 or not t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous float64 tensor of {cnt} entries")
+        if self.p and dtheta is None:
+            raise ValueError("dtheta is required: the handle has perturbations")
+        ptr = lambda t, use=True: t.data_ptr() if (t is not None and use and t.numel()) else None
+        rc = _lib.lib.qc_sweep_grad_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dweights),
+                                        ptr(dfids), ptr(dJ), ptr(dgrad), ptr(dgrad_samples), s)
         if rc != _lib.QC_OK:
             raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
 
