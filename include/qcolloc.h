@@ -26,6 +26,7 @@
  *   dynamics.dF(Z.datavec)              (:46)            qc_eval_jac      / qc_eval_F_jac(_dev)
  *   dynamics.dF_structure               (:46)            qc_jac_structure
  *   dynamics.dF(Z) * v, dynamics.dF(Z)' * lam            qc_eval_jvp / qc_eval_vjp (_dev, _dev_multi): matrix-free
+ *   (dynamics.mu_d2F(Z, mu), symmetric) * v               qc_eval_hvp (_dev, _dev_multi): matrix-free
  *   dynamics.mu_d2F(Z.datavec, mu)      (:52)            qc_eval_hess     / qc_eval_hess_dev
  *   dynamics.mu_d2F_structure           (:52)            qc_hess_structure
  *   shapes (Z.dims.states*(Z.T-1), Z.dim*Z.T+Z.global_dim)  (:44,48)   qc_dims
@@ -260,7 +261,9 @@ int qc_dims(const qc_handle* h, qc_dims_t* out);
  * "two-launches");
  * which = 3: dF v ("mfma16-pade4-jvp": the fused matrix-free kernel of the order-4 Pade integrator at 2N <= 16, up to 8 state columns
  * and 8 drives; else "generic-jvp"), which = 4: dF' lam ("generic-vjp" on every handle) -- generic: the handle's own dF launch into a
- * scratch of the handle, then a product kernel. */
+ * scratch of the handle, then a product kernel;
+ * which = 5: (mu d2F) v ("generic-hvp" on every handle: the handle's own mu_d2F launch into a scratch of the handle, then a product
+ * kernel; there is no fused matrix-free kernel for it). */
 const char* qc_kernel_name(const qc_handle* h, int32_t which);
 int qc_jac_structure(const qc_handle* h, int64_t* rows, int64_t* cols, int one_based);
 int qc_hess_structure(const qc_handle* h, int64_t* rows, int64_t* cols, int one_based);
@@ -330,6 +333,25 @@ int qc_eval_vjp(qc_handle* h, const double* Z, const double* lam, double* w);
  * y rows member by member; w = the SUM over members, in member order (the first member overwrites, the others add) */
 int qc_eval_jvp_dev_multi(qc_handle* const* hs, int32_t count, const double* dZ, const double* dv, double* dy, void* stream);
 int qc_eval_vjp_dev_multi(qc_handle* const* hs, int32_t count, const double* dZ, const double* dlam, double* dw, void* stream);
+
+/* Matrix-free product with the Hessian of the Lagrangian of the dynamics: w = H(Z, mu) v, where H is the full symmetric Z_len x Z_len
+ * matrix whose upper triangle qc_hess_structure and qc_eval_hess[_dev] of the same handle describe -- entries with equal coordinates
+ * summed, a diagonal entry counted once, an off-diagonal entry (i, j) giving H_ij v_j to w_i and H_ij v_i to w_j.  What a truncated
+ * Newton or Krylov method asks for beside the Jacobian products (hess(L_rho) v = hess(J) v + ((lam + rho F) d2F) v + rho dF'(dF v)),
+ * and MOI's eval_hessian_lagrangian_product: two vectors of Z_len doubles move instead of hess_nnz values.
+ * mu / dmu: exactly what qc_eval_hess / qc_eval_hess_dev take (the FULL multiplier vector, n_rows).  v, w: Z_len.  EVERY entry of w is
+ * written; entries that no structural Hessian entry of the handle's intervals touches (state components no integrator reads, the last
+ * knot's controls and timestep, the global_dim tail, knots outside a shard's range) are exactly +0.0.
+ * qc_desc.hess_align, hess_tail_zeros and hess_block_order cannot change a product (the padding takes no part, the sums run in the
+ * order of the coordinates).  No floating-point atomics: every entry of w has one writer and a fixed summation order, repeated calls
+ * return the same bits.  The first call on a handle allocates a scratch of n_intervals x (values per interval) doubles and a table (it
+ * synchronises the device and cannot be captured in a graph; call once first); both are released by qc_destroy.
+ * QC_ERR_UNSUPPORTED: handles without an analytic Hessian (hess_nnz == 0), handles from qc_create_multi (use the shard handles). */
+int qc_eval_hvp_dev(qc_handle* h, const double* dZ, const double* dmu, const double* dv, double* dw, void* stream);
+/* host buffers; honours qc_set_new_x like its siblings */
+int qc_eval_hvp(qc_handle* h, const double* Z, const double* mu, const double* v, double* w);
+/* integrator lists on one device: w = the SUM over members, in member order (the first member overwrites, the others add) */
+int qc_eval_hvp_dev_multi(qc_handle* const* hs, int32_t count, const double* dZ, const double* dmu, const double* dv, double* dw, void* stream);
 
 /* Several handles over the same trajectory in ONE launch: the K unitary integrators of a `UnitarySamplingProblem`
  * (reference unitary_sampling_problem.jl:134-155), each created with its slot of the shared per-interval blocks

@@ -565,6 +565,21 @@ function dFt_mul!(w::Vector{Float64}, dyn::HIPDynamics, Zâƒ—::Vector{Float64}, Î
     return w
 end
 
+"""
+Matrix-free product with the Hessian of the Lagrangian of the dynamics (`qc_eval_hvp`): `mu_d2F_mul!(w, dyn, Zâƒ—, Î¼, v)` writes
+`w = H v` (length `dyn.dims.Z_len`, every entry written), `H` the full symmetric matrix whose upper triangle `mu_d2F` and
+`mu_d2F_structure` describe (duplicates summed, a diagonal entry counted once) -- the dynamics' part of MOI's
+`eval_hessian_lagrangian_product`, without the values of `Î¼âˆ‚Â²F`.  `Î¼` is what `mu_d2F` takes.  Honours `set_new_x!`.  One handle on one
+device.
+"""
+function mu_d2F_mul!(w::Vector{Float64}, dyn::HIPDynamics, Zâƒ—::Vector{Float64}, Î¼::Vector{Float64}, v::Vector{Float64})
+    length(dyn.handles) == 1 || error("mu_d2F_mul!: one handle on one device only")
+    length(w) == dyn.dims.Z_len && length(v) == dyn.dims.Z_len && length(Zâƒ—) == dyn.dims.Z_len || error("mu_d2F_mul!: Zâƒ—, v and w must have length $(dyn.dims.Z_len)")
+    length(Î¼) == dyn.dims.n_rows || error("mu_d2F_mul!: Î¼ has length $(length(Î¼)), expected $(dyn.dims.n_rows)")
+    GC.@preserve Zâƒ— Î¼ v w check(ccall((:qc_eval_hvp, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), dyn.handle, Zâƒ—, Î¼, v, w), dyn.handle)
+    return w
+end
+
 # ---------------------------------------------------------------------------------------------------------------
 #  Objective terms and rollouts (SURVEY.md 8f): the same `ccall` pattern over qc_terms_* / qc_fidelity_* / qc_rollout
 # ---------------------------------------------------------------------------------------------------------------

@@ -252,6 +252,9 @@ SYMBOLS = {
     "qc_eval_vjp": (C.c_int, [_H, _c_double_p, _c_double_p, _c_double_p]),
     "qc_eval_jvp_dev_multi": (C.c_int, [C.POINTER(_H), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qc_eval_vjp_dev_multi": (C.c_int, [C.POINTER(_H), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qc_eval_hvp_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qc_eval_hvp": (C.c_int, [_H, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "qc_eval_hvp_dev_multi": (C.c_int, [C.POINTER(_H), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qc_eval_F_list": (C.c_int, [C.POINTER(_H), C.c_int32, _c_double_p, _c_double_p]),
     "qc_eval_jac_list": (C.c_int, [C.POINTER(_H), C.c_int32, _c_double_p, _c_double_p]),
     "qc_eval_F_jac_list": (C.c_int, [C.POINTER(_H), C.c_int32, _c_double_p, _c_double_p, _c_double_p]),

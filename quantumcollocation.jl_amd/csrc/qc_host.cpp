@@ -561,7 +561,7 @@ extern "C" void qc_destroy(qc_handle* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->stream2) (void)hipStreamSynchronize(h->stream2);
     double* bufs[] = {h->dG, h->dGx, h->dZ, h->dF, h->dJ, h->dMu, h->dH, (double*)h->dStamps, h->dRE, h->dRQ, h->dRS, h->dRinit, h->dRout, h->dRZ, h->dWs, h->dHs,
-                      h->dPvals, (double*)h->dPtab, h->dPx, h->dPy, h->dPl};
+                      h->dPvals, (double*)h->dPtab, h->dPx, h->dPy, h->dPl, h->dHPvals, (double*)h->dHPtab, h->dHPw, h->dHPmu};
     if (h->hJc) (void)hipHostFree(h->hJc);
     if (h->hFc) (void)hipHostFree(h->hFc);
     if (h->hZ) (void)hipHostFree(h->hZ);
@@ -601,6 +601,7 @@ extern "C" const char* qc_kernel_name(const qc_handle* h, int32_t which) {
     const QcPlan& p = h->plan;
     if (which == 3) return qc_jvp_kernel_name(p.jvp);
     if (which == 4) return qc_vjp_kernel_name(p.vjp);
+    if (which == 5) return qc_hvp_kernel_name(p.hvp);
     return which == 0 ? qc_jac_kernel_name(p.jac) : (which == 2 ? qc_fused_kernel_name(p.fused) : qc_hess_kernel_name(p.hess));
 }
 

@@ -1473,6 +1473,34 @@ extern "C" int qc_eval_vjp(qc_handle* h, const double* Z, const double* lam, dou
     return wait_done(h, 1);
 }
 
+// The Hessian product with host buffers: the knots as in every host-buffer call, the multipliers of the handle's intervals and v up, the
+// device-resident product on the handle's stream, w down.
+extern "C" int qc_eval_hvp(qc_handle* h, const double* Z, const double* mu, const double* v, double* w) {
+    if (!h) return fail(nullptr, QC_ERR_INVALID, "qc_eval_hvp: NULL handle");
+    if (is_multi(h)) return fail(&h->err, QC_ERR_UNSUPPORTED, "qc_eval_hvp: the Hessian product does not serve multi-device handles (qc_create_multi)");
+    if (h->prm.hess_nnz == 0) return fail(&h->err, QC_ERR_UNSUPPORTED, "qc_eval_hvp: this handle has no analytic Hessian (hess_nnz = 0)");
+    if (!Z || !mu || !v || !w) return fail(&h->err, QC_ERR_INVALID, "qc_eval_hvp: NULL buffer");
+    const QcParams& P = h->prm;
+    qc_device_guard guard(h->device);
+    QC_HIP(h, guard.err);
+    int rc;
+    if ((rc = drain_if_needed(h)) || (rc = drain_leader_if_needed(h))) return rc;
+    if ((rc = ensure(h, &h->dPx, (size_t)h->dims.Z_len)) || (rc = ensure(h, &h->dHPw, (size_t)h->dims.Z_len)) ||
+        (rc = ensure(h, &h->dHPmu, (size_t)std::max<int64_t>(1, h->dims.n_rows))) || (rc = ensure(h, &h->dZ, (size_t)h->dims.Z_len)))
+        return rc;
+    if (P.n_int > 0) {
+        if ((rc = upload_knots(h, Z))) return rc;
+        const size_t m0 = (size_t)P.t_begin * P.F_stride, mn = (size_t)P.n_int * P.F_stride;      // the rows of this handle's intervals
+        QC_HIP(h, hipMemcpyAsync(h->dHPmu + m0, mu + m0, mn * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        const size_t o = (size_t)P.t_begin * P.zdim, n = (size_t)(P.n_int + 1) * P.zdim;           // ... and the knots they read
+        QC_HIP(h, hipMemcpyAsync(h->dPx + o, v + o, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    if ((rc = qc_product_hvp_dev(h, "qc_eval_hvp", h->dZ, h->dHPmu, h->dPx, h->dHPw, false, h->stream))) return rc;
+    QC_HIP(h, hipMemcpyAsync(w, h->dHPw, (size_t)h->dims.Z_len * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    QC_HIP(h, hipEventRecord(h->ev_done, h->stream));
+    return wait_done(h, 1);
+}
+
 // ------------------------------------------------------------------------------------------------
 //  Integrator lists with several state integrators, host buffers (UnitarySamplingProblem, UnitaryDirectSumProblem,
 //  QuantumStateSamplingProblem): one composed handle per state integrator, ONE upload of the knots, the batched launch where

@@ -107,6 +107,7 @@ struct QcPlan {
     bool hess_chunks;              // the mu_d2F launch may be split into chunks of intervals
     size_t hess_scratch_doubles;   // scratch the mu_d2F kernel needs in QcParams.hs (0: none), allocated at the first call
     QcProductKernel jvp, vjp;      // dF v and dF' lam: the generic two-launch path, or a fused matrix-free kernel (dF v only)
+    QcProductKernel hvp;           // (mu d2F) v: the generic two-launch path (there is no fused kernel)
 };
 
 struct qc_fanout;
@@ -197,6 +198,10 @@ struct qc_handle {
     double* dPvals = nullptr;  // scratch Jacobian values of this handle's intervals (n_int * J_stride doubles)
     int32_t* dPtab = nullptr;  // the per-interval pattern sorted by row and by column (QcProductTables)
     double *dPx = nullptr, *dPy = nullptr, *dPl = nullptr;   // staging of the host-buffer forms: v / w (Z_len), y and lam (F_len)
+    // Hessian product, generic path (qc_products.hip): created at the first call, released by qc_destroy
+    double* dHPvals = nullptr;  // scratch mu_d2F values of this handle's intervals (n_int * H_stride doubles)
+    int32_t* dHPtab = nullptr;  // the per-interval pattern sorted by target variable, either side of a knot (QcHessProductTables)
+    double *dHPw = nullptr, *dHPmu = nullptr;   // staging of qc_eval_hvp: w (Z_len; v goes through dPx) and mu (n_rows)
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;   // odd chunks of the direct-to-host path (kernel boundaries of one stream overlap the other's stores)
     hipEvent_t ev_staged = nullptr;  // the knots are on the device (recorded on `stream`, waited for by `stream2`)
@@ -295,6 +300,8 @@ bool qc_mfma16_products_supported(const QcParams& P, const QcClass& cls);   // t
 hipError_t qc_launch_mfma16_jvp(const QcParams& P, const double* dZ, const double* dv, double* dy, hipStream_t st);
 int qc_product_jvp_dev(qc_handle* h, const char* who, const double* dZ, const double* dv, double* dy, hipStream_t st);
 int qc_product_vjp_dev(qc_handle* h, const char* who, const double* dZ, const double* dlam, double* dw, bool accumulate, hipStream_t st);
+int qc_product_hvp_dev(qc_handle* h, const char* who, const double* dZ, const double* dmu, const double* dv, double* dw, bool accumulate,
+                       hipStream_t st);
 
 hipError_t qc_launch_pack_jac(const double* dJ, double* dJc, int n_int, int jac_nnz, int comp_len, int n2, int jo_F, int jo_B, int head2,
                               int tail_src, hipStream_t st);

@@ -46,6 +46,7 @@ const Name kFusedNames[QC_FUSED_KERNELS] = {
 
 const Name kJvpNames[QC_PROD_KERNELS] = {{"GENERIC", "generic-jvp"}, {"PADE4_16", "mfma16-pade4-jvp"}};
 const Name kVjpNames[QC_PROD_KERNELS] = {{"GENERIC", "generic-vjp"}, {"PADE4_16", "generic-vjp"}};      // (there is no fused transposed kernel)
+const Name kHvpNames[QC_PROD_KERNELS] = {{"GENERIC", "generic-hvp"}, {"PADE4_16", "generic-hvp"}};      // (... and no fused Hessian-product kernel)
 
 // The two-wave mu_d2F kernel (qc_mfma_hess2.hip) serves launches of up to one round of the device (four workgroups per CU): measured
 // against the one-wave kernel (profiles/r03_hess2_ab.txt) 6.1 - 6.8 / 7.0 / 8.6 us against 7.1 / 7.5 / 8.7 at T = 250 / 500 / 1000; beyond
@@ -156,6 +157,7 @@ QcPlan qc_plan(const QcParams& P, const QcClass& cls, const QcSwitches& sw) {
     p.hess_scratch_doubles = p.hess == QC_HESS_PADE4_64 ? qc_mfma64_hess_scratch_doubles(P) : 0;      // (128 MiB)
     p.jvp = qc_plan_product(P, cls);
     p.vjp = QC_PROD_GENERIC;
+    p.hvp = QC_PROD_GENERIC;      // (mu d2F) v: the handle's own mu_d2F launch into a scratch, then the product kernel of qc_products.hip
     return p;
 }
 
@@ -182,6 +184,7 @@ const char* qc_hess_kernel_name(QcHessKernel k) { return kHessNames[k].name; }
 const char* qc_fused_kernel_name(QcFusedKernel k) { return kFusedNames[k].name; }
 const char* qc_jvp_kernel_name(QcProductKernel k) { return kJvpNames[k].name; }
 const char* qc_vjp_kernel_name(QcProductKernel k) { return kVjpNames[k].name; }
+const char* qc_hvp_kernel_name(QcProductKernel k) { return kHvpNames[k].name; }
 const char* qc_jac_kernel_id(QcJacKernel k) { return kJacNames[k].id; }
 const char* qc_hess_kernel_id(QcHessKernel k) { return kHessNames[k].id; }
 const char* qc_fused_kernel_id(QcFusedKernel k) { return kFusedNames[k].id; }

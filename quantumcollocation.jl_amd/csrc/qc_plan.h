@@ -46,6 +46,7 @@ const char* qc_hess_kernel_name(QcHessKernel k);
 const char* qc_fused_kernel_name(QcFusedKernel k);
 const char* qc_jvp_kernel_name(QcProductKernel k);   // qc_kernel_name(h, 3)
 const char* qc_vjp_kernel_name(QcProductKernel k);   // qc_kernel_name(h, 4)
+const char* qc_hvp_kernel_name(QcProductKernel k);   // qc_kernel_name(h, 5)
 const char* qc_jac_kernel_id(QcJacKernel k);       // the enumerator without its prefix (tests/kernel_plan_test.cpp)
 const char* qc_hess_kernel_id(QcHessKernel k);
 const char* qc_fused_kernel_id(QcFusedKernel k);

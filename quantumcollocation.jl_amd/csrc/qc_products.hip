@@ -14,6 +14,15 @@
 // Every output entry has one writer and a fixed summation order: no atomics, nothing depends on scheduling, repeated calls give
 // the same bits.  The transposed kernel writes EVERY entry of w (knots the handle's intervals do not touch and the global_dim tail
 // get 0.0) unless it accumulates (the later members of an integrator list).
+//
+// The Hessian product w = H(Z, mu) v (qc_eval_hvp_dev and its host-buffer and list forms' device half), H the full symmetric matrix whose
+// upper triangle qc_hess_structure describes, follows the transposed Jacobian product: the handle's own mu_d2F launch into a scratch of
+// n_int x H_stride doubles, then a product kernel, one workgroup per knot and one thread per knot entry, driven by a table built from
+// qc_local_hess_structure: every structural entry (i, j) of the upper triangle is listed under target i with source j and, unless
+// i == j, under target j with source i; the lists are sorted by (target, source) -- by coordinates, never by where a value lies in the
+// interval's block -- and the targets at knot t of an interval (its right-hand neighbour) are kept apart from those at knot t+1 (its
+// left-hand neighbour).  An entry of w sums over the block of interval t-1, then over that of interval t.  The alignment padding of a
+// block (explicit zeros recorded as duplicates of the block's first entry) is not in the table at all.
 #include <string.h>
 
 #include <algorithm>
@@ -93,6 +102,45 @@ __global__ __launch_bounds__(kThreads) void qc_vjp_generic_kernel(const int32_t*
     }
 }
 
+// Hessian product tables (int32), one allocation: the header, then for side 0 (targets at knot t of an interval) and side 1 (targets at
+// knot t+1):  ptr[zdim + 1] | ent[...] value index in the interval's block | src[...] local source variable (>= zdim: knot t+1)
+struct QcHessProductTables {
+    int ptr[2], ent[2], src[2];        // offsets (ints) from the start of the allocation
+};
+
+// grid: one workgroup per knot, then the workgroups of the global_dim tail
+__global__ __launch_bounds__(kThreads) void qc_hvp_generic_kernel(const int32_t* __restrict__ tab, int n_int, long long t_begin, long long T,
+                                                                 long long global_dim, int zdim, long long H_stride, long long H_off,
+                                                                 const double* __restrict__ vals, const double* __restrict__ v,
+                                                                 double* __restrict__ w, int accumulate) {
+    const long long t = blockIdx.x;
+    if (t >= T) {      // variables after the knots: no Hessian entry touches them
+        const long long i = (t - T) * kThreads + threadIdx.x;
+        if (i < global_dim && !accumulate) w[T * zdim + i] = 0.0;
+        return;
+    }
+    const QcHessProductTables& H = *reinterpret_cast<const QcHessProductTables*>(tab);
+    const long long bl = t - 1 - t_begin, br = t - t_begin;      // the interval to the left (this knot is its t+1) and to the right
+    const bool left = bl >= 0 && bl < n_int, right = br >= 0 && br < n_int;
+    double* wt = w + t * zdim;
+    for (int c = threadIdx.x; c < zdim; c += kThreads) {
+        double acc = 0.0;
+        if (left) {
+            const int32_t *ptr = tab + H.ptr[1], *ent = tab + H.ent[1], *src = tab + H.src[1];
+            const double* Hb = vals + (size_t)bl * H_stride + H_off;
+            const double* vb = v + (t - 1) * zdim;      // local source j >= zdim is entry j - zdim of knot t: contiguous
+            for (int i = ptr[c]; i < ptr[c + 1]; ++i) acc += Hb[ent[i]] * vb[src[i]];
+        }
+        if (right) {
+            const int32_t *ptr = tab + H.ptr[0], *ent = tab + H.ent[0], *src = tab + H.src[0];
+            const double* Hb = vals + (size_t)br * H_stride + H_off;
+            const double* vb = v + t * zdim;
+            for (int i = ptr[c]; i < ptr[c + 1]; ++i) acc += Hb[ent[i]] * vb[src[i]];
+        }
+        wt[c] = accumulate ? wt[c] + acc : acc;
+    }
+}
+
 // The tables of a handle, on the host: the pattern sorted by (row, column), and by (column, row) on either side -- never by where a
 // value lies in the interval's block, so qc_desc.jac_block_order cannot change a sum's order (entries are unique).
 std::vector<int32_t> build_tables(const QcParams& P) {
@@ -154,6 +202,55 @@ int prepare_generic(qc_handle* h) {
     return QC_OK;
 }
 
+// The Hessian product's table, on the host.  Only the hess_nnz structural entries take part: the h_pad padding entries behind them are
+// zero duplicates of the first entry, which would otherwise count a diagonal first entry once per padding word.
+std::vector<int32_t> build_hess_tables(const QcParams& P) {
+    std::vector<int32_t> lr, lc;
+    qc_local_hess_structure(P, &lr, &lc);
+    const int zd = P.zdim;
+    struct Term { int32_t target, src, ent; };
+    std::vector<Term> terms;
+    for (int e = 0; e < P.hess_nnz; ++e) {
+        terms.push_back({lr[e], lc[e], e});
+        if (lr[e] != lc[e]) terms.push_back({lc[e], lr[e], e});
+    }
+    std::sort(terms.begin(), terms.end(), [](const Term& a, const Term& b) {
+        return a.target != b.target ? a.target < b.target : (a.src != b.src ? a.src < b.src : a.ent < b.ent);
+    });
+    std::vector<int32_t> ptr[2], ent[2], src[2];
+    for (int side = 0; side < 2; ++side) {
+        ptr[side].assign(zd + 1, 0);
+        for (const Term& x : terms)
+            if ((x.target >= zd) == (side == 1)) {
+                ++ptr[side][x.target - side * zd + 1];
+                ent[side].push_back(x.ent);      // (terms are in target order: the lists come out grouped by target)
+                src[side].push_back(x.src);
+            }
+        for (int c = 0; c < zd; ++c) ptr[side][c + 1] += ptr[side][c];
+    }
+    static_assert(sizeof(QcHessProductTables) % sizeof(int32_t) == 0, "the header is a whole number of ints");
+    QcHessProductTables H;
+    std::vector<int32_t> blob(sizeof(QcHessProductTables) / sizeof(int32_t));
+    auto append = [&](const std::vector<int32_t>& a) { const int at = (int)blob.size(); blob.insert(blob.end(), a.begin(), a.end()); return at; };
+    for (int side = 0; side < 2; ++side) { H.ptr[side] = append(ptr[side]); H.ent[side] = append(ent[side]); H.src[side] = append(src[side]); }
+    memcpy(blob.data(), &H, sizeof(H));
+    return blob;
+}
+
+// first Hessian product call of a handle: the table and the scratch values
+int prepare_hess_generic(qc_handle* h) {
+    if (h->dHPtab) return QC_OK;
+    const std::vector<int32_t> blob = build_hess_tables(h->prm);
+    const size_t nvals = (size_t)h->prm.n_int * (size_t)h->prm.H_stride;
+    if (nvals && !h->dHPvals) QC_HIP(h, hipMalloc((void**)&h->dHPvals, nvals * sizeof(double)));
+    int32_t* tab = nullptr;
+    QC_HIP(h, hipMalloc((void**)&tab, blob.size() * sizeof(int32_t)));
+    const hipError_t e = hipMemcpy(tab, blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(tab); QC_HIP(h, e); }
+    h->dHPtab = tab;
+    return QC_OK;
+}
+
 int check_args(qc_handle* h, const char* who, const void* a, const void* b, const void* c) {
     if (!h->shards.empty())
         return fail(&h->err, QC_ERR_UNSUPPORTED, std::string(who) + ": the Jacobian products do not serve multi-device handles (qc_create_multi); "
@@ -203,6 +300,31 @@ int qc_product_vjp_dev(qc_handle* h, const char* who, const double* dZ, const do
     return QC_OK;
 }
 
+int qc_product_hvp_dev(qc_handle* h, const char* who, const double* dZ, const double* dmu, const double* dv, double* dw, bool accumulate,
+                       hipStream_t st) {
+    if (!h->shards.empty())
+        return fail(&h->err, QC_ERR_UNSUPPORTED, std::string(who) + ": the Hessian product does not serve multi-device handles (qc_create_multi); "
+                                                 "use the shard handles (qc_multi_shard) on their own devices");
+    if (h->prm.hess_nnz == 0)
+        return fail(&h->err, QC_ERR_UNSUPPORTED, std::string(who) + ": this handle has no analytic Hessian (hess_nnz = 0)");
+    if (!dZ || !dmu || !dv || !dw) return fail(&h->err, QC_ERR_INVALID, std::string(who) + ": NULL buffer");
+    if (((uintptr_t)dZ | (uintptr_t)dmu | (uintptr_t)dv | (uintptr_t)dw) % 8) return fail(&h->err, QC_ERR_INVALID, std::string(who) + ": a buffer is not 8-byte aligned");
+    const QcParams& P = h->prm;
+    const long long T = h->desc.T, gd = h->desc.global_dim;
+    qc_device_guard guard(h->device);
+    QC_HIP(h, guard.err);
+    int rc;
+    if ((rc = prepare_hess_generic(h))) return rc;
+    // the handle's slice of a value vector starts at its first interval: the scratch is the slice itself
+    if (P.n_int > 0 && (rc = qc_eval_hess_dev(h, dZ, dmu, h->dHPvals, (void*)st))) return rc;
+    const long long grid = T + (gd + kThreads - 1) / kThreads;
+    if (grid > 0x7fffffffLL) return fail(&h->err, QC_ERR_UNSUPPORTED, std::string(who) + ": too many knots for one launch");
+    hipLaunchKernelGGL(qc_hvp_generic_kernel, dim3((unsigned)grid), dim3(kThreads), 0, st, h->dHPtab, P.n_int, P.t_begin, T, gd, P.zdim, P.H_stride, P.H_off,
+                       h->dHPvals, dv, dw, accumulate ? 1 : 0);
+    QC_HIP(h, hipGetLastError());
+    return QC_OK;
+}
+
 extern "C" int qc_eval_jvp_dev(qc_handle* h, const double* dZ, const double* dv, double* dy, void* stream) {
     if (!h) return fail(nullptr, QC_ERR_INVALID, "qc_eval_jvp_dev: NULL handle");
     return qc_product_jvp_dev(h, "qc_eval_jvp_dev", dZ, dv, dy, (hipStream_t)stream);
@@ -213,14 +335,19 @@ extern "C" int qc_eval_vjp_dev(qc_handle* h, const double* dZ, const double* dla
     return qc_product_vjp_dev(h, "qc_eval_vjp_dev", dZ, dlam, dw, false, (hipStream_t)stream);
 }
 
+extern "C" int qc_eval_hvp_dev(qc_handle* h, const double* dZ, const double* dmu, const double* dv, double* dw, void* stream) {
+    if (!h) return fail(nullptr, QC_ERR_INVALID, "qc_eval_hvp_dev: NULL handle");
+    return qc_product_hvp_dev(h, "qc_eval_hvp_dev", dZ, dmu, dv, dw, false, (hipStream_t)stream);
+}
+
 // Integrator lists on one device: the members run in member order on the stream.  y: every member writes its own rows of the
 // problem's row vector.  w: the first member overwrites (every entry), the others add -- a fixed order, so the sum is reproducible.
-static int list_front(qc_handle* const* hs, int32_t count, const char* who) {
+static int list_front(qc_handle* const* hs, int32_t count, const char* who, const char* what = "the Jacobian products do") {
     if (!hs || count < 1) return fail(nullptr, QC_ERR_INVALID, std::string(who) + ": no handles");
     for (int i = 0; i < count; ++i) if (!hs[i]) return fail(nullptr, QC_ERR_INVALID, std::string(who) + ": NULL handle");
     for (int i = 0; i < count; ++i) {
         if (!hs[i]->shards.empty())
-            return fail(&hs[0]->err, QC_ERR_UNSUPPORTED, std::string(who) + ": the Jacobian products do not serve multi-device handles (qc_create_multi)");
+            return fail(&hs[0]->err, QC_ERR_UNSUPPORTED, std::string(who) + ": " + what + " not serve multi-device handles (qc_create_multi)");
         if (hs[i]->device != hs[0]->device) return fail(&hs[0]->err, QC_ERR_INVALID, std::string(who) + ": the handles are bound to different devices");
         if (hs[i]->dims.Z_len != hs[0]->dims.Z_len) return fail(&hs[0]->err, QC_ERR_INVALID, std::string(who) + ": the handles are not over one trajectory");
     }
@@ -243,6 +370,20 @@ extern "C" int qc_eval_vjp_dev_multi(qc_handle* const* hs, int32_t count, const 
     if ((rc = list_front(hs, count, "qc_eval_vjp_dev_multi"))) return rc;
     for (int i = 0; i < count; ++i)
         if ((rc = qc_product_vjp_dev(hs[i], "qc_eval_vjp_dev_multi", dZ, dlam, dw, i > 0, (hipStream_t)stream))) {
+            if (i) hs[0]->err = hs[i]->err;
+            return rc;
+        }
+    return QC_OK;
+}
+
+extern "C" int qc_eval_hvp_dev_multi(qc_handle* const* hs, int32_t count, const double* dZ, const double* dmu, const double* dv, double* dw,
+                                     void* stream) {
+    int rc;
+    if ((rc = list_front(hs, count, "qc_eval_hvp_dev_multi", "the Hessian product does"))) return rc;
+    for (int i = 0; i < count; ++i)      // refused before any member has written: a list with a member without a Hessian leaves w alone
+        if (hs[i]->prm.hess_nnz == 0) return fail(&hs[0]->err, QC_ERR_UNSUPPORTED, "qc_eval_hvp_dev_multi: a member has no analytic Hessian (hess_nnz = 0)");
+    for (int i = 0; i < count; ++i)
+        if ((rc = qc_product_hvp_dev(hs[i], "qc_eval_hvp_dev_multi", dZ, dmu, dv, dw, i > 0, (hipStream_t)stream))) {
             if (i) hs[0]->err = hs[i]->err;
             return rc;
         }

@@ -662,6 +662,34 @@ class QuantumDynamics:
             self._h, self._dev_ptr(Z, self.dims.Z_len, "Z"), self._dev_ptr(lam, self.dims.F_len, "lam"),
             self._dev_ptr(w, self.dims.Z_len, "w"), C.c_void_p(st.cuda_stream)), self._h)
 
+    # -- matrix-free Hessian product: w = H(Z, mu) v, H the full symmetric matrix of mu_d2F's upper triangle (qc_eval_hvp) ----------
+    @property
+    def hess_product_kernel_name(self) -> str:
+        """Kernel of (mu d2F) v (qc_kernel_name(h, 5)): "generic-hvp".  (`kernel_names` stays the pair of F + dF and mu_d2F, and
+        `product_kernel_names` the pair of the Jacobian products.)"""
+        return _lib.lib.qc_kernel_name(self._h, 5).decode()
+
+    def _no_hessian(self) -> None:
+        if not self.eval_hessian:
+            raise _lib.QCollocError(_lib.QC_ERR_UNSUPPORTED, "the dynamics were built with eval_hessian=False: no Hessian product")
+
+    def mu_d2F_times(self, Z, mu, v, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """w = (mu d2F)(Z) v, length Z_len, every entry written (host buffers; `set_new_x(False)` reuses the knots on the device).
+        mu is what `mu_d2F` takes; the matrix is the full symmetric one, duplicates summed, a diagonal entry counted once."""
+        self._no_hessian()
+        Z, mu, v = self._Z(Z), self._vec(mu, int(self.dims.n_rows), "mu"), self._vec(v, int(self.dims.Z_len), "v")
+        w = self._out("w", int(self.dims.Z_len), out, True)
+        self._check(_lib.lib.qc_eval_hvp(self._h, _lib.dptr(Z), _lib.dptr(mu), _lib.dptr(v), _lib.dptr(w)))
+        return w
+
+    def mu_d2F_times_device(self, Z: torch.Tensor, mu: torch.Tensor, v: torch.Tensor, w: torch.Tensor, stream=None) -> None:
+        """w = (mu d2F)(Z) v on device tensors, asynchronous on `stream`; every entry of w is written."""
+        self._no_hessian()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(_lib.lib.qc_eval_hvp_dev(
+            self._h, self._dev_ptr(Z, self.dims.Z_len, "Z"), self._dev_ptr(mu, self.dims.n_rows, "mu"),
+            self._dev_ptr(v, self.dims.Z_len, "v"), self._dev_ptr(w, self.dims.Z_len, "w"), C.c_void_p(st.cuda_stream)), self._h)
+
 
 class ComposedQuantumDynamics(QuantumDynamics):
     """`QuantumDynamics` over an integrator list with SEVERAL unitary integrators (UnitarySamplingProblem: K systems
@@ -874,6 +902,35 @@ class ComposedQuantumDynamics(QuantumDynamics):
 
     def dFT_times(self, Z, lam, out: Optional[np.ndarray] = None) -> np.ndarray:
         return self._through_device(self.dFT_times_device, Z, lam, int(self.dims.F_len), int(self.dims.Z_len), "lam", out)
+
+    # -- ... and the Hessian product over the list: w = the sum over members, in member order -------------------------------------------
+    @property
+    def hess_product_kernel_name(self) -> str:
+        return _lib.lib.qc_kernel_name(self._parts[0][2], 5).decode()
+
+    def _no_hessian(self) -> None:
+        if not self.eval_hessian or not self.dims.hess_nnz:
+            raise _lib.QCollocError(_lib.QC_ERR_UNSUPPORTED, "no analytic Hessian for this integrator list: no Hessian product")
+
+    def mu_d2F_times_device(self, Z: torch.Tensor, mu: torch.Tensor, v: torch.Tensor, w: torch.Tensor, stream=None) -> None:
+        self._no_products_over_devices()
+        self._no_hessian()
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _lib.check(_lib.lib.qc_eval_hvp_dev_multi(
+            self._handles, len(self._parts), self._dev_ptr(Z, self.dims.Z_len, "Z"), self._dev_ptr(mu, self.dims.n_rows, "mu"),
+            self._dev_ptr(v, self.dims.Z_len, "v"), self._dev_ptr(w, self.dims.Z_len, "w"), C.c_void_p(st.cuda_stream)), self._parts[0][2])
+
+    def mu_d2F_times(self, Z, mu, v, out: Optional[np.ndarray] = None) -> np.ndarray:
+        self._no_products_over_devices()
+        self._no_hessian()
+        n = int(self.dims.Z_len)
+        Z, mu, v = self._Z(Z), self._vec(mu, int(self.dims.n_rows), "mu"), self._vec(v, n, "v")
+        res = self._out("w", n, out, True)
+        dZ, dmu, dv = (torch.from_numpy(x).to(self._dev) for x in (Z, mu, v))
+        dw = torch.empty(n, dtype=torch.float64, device=self._dev)      # (the first member writes every entry)
+        self.mu_d2F_times_device(dZ, dmu, dv, dw)
+        res[:] = dw.cpu().numpy()
+        return res
 
     def knot_generation(self) -> int:
         return int(_lib.lib.qc_knot_generation(self._parts[0][2]))

@@ -240,6 +240,40 @@ class QuantumControlEvaluator:
             np.add.at(w, self._jac_cols[off:off + cnt], np.asarray(cobj.dg(x)).ravel() * lam[self._jac_rows[off:off + cnt]])
         return w
 
+    # -- Hessian-of-the-Lagrangian product (MOI's eval_hessian_lagrangian_product) -----------------------------------------------------
+    @staticmethod
+    def _sym_coo_times(w: np.ndarray, vals, rows: np.ndarray, cols: np.ndarray, v: np.ndarray, scale: float = 1.0) -> None:
+        """w += scale * (full symmetric matrix of the COO piece) v: duplicates summed, a diagonal entry counted once."""
+        vals = scale * np.asarray(vals, dtype=np.float64).ravel()
+        np.add.at(w, rows, vals * v[cols])
+        off = rows != cols
+        np.add.at(w, cols[off], vals[off] * v[rows[off]])
+
+    def hessian_lagrangian_times(self, x, sigma: float, mu, v) -> np.ndarray:
+        """w = (sigma hess(J)(x) + sum_i mu_i hess(c_i)(x)) v: the objectives' pieces from their COO values, the dynamics through the
+        library's matrix-free product (no Hessian value of the dynamics is formed), the other constraints' `mu_d2g` pieces."""
+        if not self.eval_hessian:
+            raise RuntimeError("the evaluator was built with eval_hessian=False (quasi-Newton solve)")
+        x, v = self._x(x), self._x(v)
+        mu = np.ascontiguousarray(mu, dtype=np.float64)
+        if mu.size != self.n_constraints:
+            raise ValueError(f"mu has length {mu.size}, expected {self.n_constraints}")
+        w = np.zeros(self.n_variables)
+        if self._hess_dyn[1]:
+            if self._can_elide:
+                self.dynamics.set_new_x(True)
+            w += self.dynamics.mu_d2F_times(x, mu[:self.n_dynamics_rows], v)
+            self._x_F = None      # x's knots are on the device now, the cached residuals may be another x's
+        for o, (off, cnt) in zip(self.objectives, self._obj_hess):
+            self._sym_coo_times(w, o.hess_L(x), self._hess_rows[off:off + cnt], self._hess_cols[off:off + cnt], v, sigma)
+        r0 = self.n_dynamics_rows
+        for cobj, slot in zip(self.constraints, self._con_hess):
+            if slot is not None:
+                off, cnt = slot
+                self._sym_coo_times(w, cobj.mu_d2g(x, mu[r0:r0 + cobj.dim]), self._hess_rows[off:off + cnt], self._hess_cols[off:off + cnt], v)
+            r0 += cobj.dim
+        return w
+
     # -- conveniences for solvers that want matrices -------------------------------------------------------------------
     def jacobian_matrix(self, x):
         import scipy.sparse as sp
