@@ -625,9 +625,10 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * Kernels: 2N <= 16 with up to 8 drives runs on the f64 matrix cores, one wavefront per (sample, chunk of intervals)
  * ("mfma16-sweep"); larger systems run the rollout kernels once per sample ("rollout-per-sample": correctness, not speed).
  * Results do not depend on scheduling: repeated calls return the same bits.  Non-finite inputs are evaluated, not rejected.
- * Gradients (qc_sweep_grad*, below) are served for closed systems in the MFMA form.
- * Out of scope: per-knot outputs, open-system gradients (they need stored forward states), derivatives with respect to theta and
- * `scale`, second derivatives, the free-phase fidelity, several devices. */
+ * Gradients with respect to the controls and timesteps (qc_sweep_grad*) and to the samples' own parameters theta and `scale`
+ * (qc_sweep_grad_params*), both below, are served for closed systems in the MFMA form.
+ * Out of scope: per-knot outputs, open-system gradients (they need stored forward states), second derivatives, derivatives of the
+ * final states, the free-phase fidelity, several devices. */
 #define QC_MAX_PERT 8
 #define QC_SWEEP_FID_NONE (-1)   /* qc_sweep_desc.fid_kind: final states only */
 typedef struct qc_sweep_desc {
@@ -700,6 +701,25 @@ int qc_sweep_grad_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_
 /* the same on host buffers (synchronous) */
 int qc_sweep_grad(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
                   const double* weights, double* fids, double* J, double* grad, double* grad_samples);
+
+/* The derivatives with respect to the SYSTEMS: grad_theta[s, j] = dF_s/dtheta[s, j] (S x n_pert) and grad_scale[s, k] = dF_s/dc[s, k]
+ * (S x m), sample-major as theta / scale, raw per-sample values (no weights):
+ *     dF_s/dtheta[s, j] = sum_t dt_t <lambda_{t+1} x_t^T, L(dt_t G; P_j)>,   dF_s/dc[s, k] = sum_t a_{t,k} dt_t <lambda_{t+1} x_t^T, L(dt_t G; G_k)>
+ * over the intervals t = 0 .. T-2, from the same backward walk (one per call, whatever is requested): the per-interval tile of the
+ * walk is summed over a chunk and contracted with the perturbation tiles once, the drive contractions are weighted with the controls
+ * before the factor c[s, k] is applied (no division by c: defined at c = 0; scale = NULL: the derivative at c = 1).  The chunk
+ * shares are added in ascending chunk order: no atomics, repeated calls return the same bits, and grad_theta / grad_scale do not
+ * depend on which other outputs were requested.  Every other argument, the scope (qc_sweep_desc_grad_supported), the scratch and the
+ * one-in-flight rule are those of qc_sweep_grad_dev, and fids / J / grad / grad_samples carry its bits; without grad and
+ * grad_samples the S x (T-1) x (m + (off_dt >= 0)) per-interval buffer is neither allocated nor written.  Every output is optional,
+ * at least one must be non-NULL; grad_theta on a handle with n_pert = 0, or grad_scale with m = 0, is QC_ERR_INVALID. */
+int qc_sweep_grad_params_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
+                             const double* dweights, double* dfids, double* dJ, double* dgrad, double* dgrad_samples,
+                             double* dgrad_theta, double* dgrad_scale, void* stream);
+/* the same on host buffers (synchronous) */
+int qc_sweep_grad_params(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
+                         const double* weights, double* fids, double* J, double* grad, double* grad_samples,
+                         double* grad_theta, double* grad_scale);
 
 /* Diagnostic only: when the environment variable QC_STAMPS=1 is set at qc_create, the MFMA kernel
  * records 16 s_memrealtime (100 MHz) checkpoints per interval; this copies them out (synchronises the

@@ -794,6 +794,53 @@ function rollout_sweep_gradient(init::AbstractVector{Float64}, controls::Abstrac
 end
 
 """
+    rollout_sweep_parameter_gradient(init, controls, Δt, G_drift, G_drives, G_pert, θ; scale=nothing, cols, goal, fid_kind=0,
+                                     subspace=nothing, squared=false, device=0)  ->  (fids, ∇θ, ∇c)
+
+The derivatives of the S fidelities of `rollout_sweep` with respect to the SYSTEMS (`qc_sweep_grad_params`): `∇θ[s, j]` = ∂F_s/∂θ[s, j]
+(S×p) and `∇c[s, k]` = ∂F_s/∂scale[s, k] (S×m; `scale = nothing`: taken at all ones), raw per-sample values from one backward walk.
+Scope and arguments as `rollout_sweep_gradient`.  UNTESTED here, like the rest of this file.
+"""
+function rollout_sweep_parameter_gradient(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift,
+                                          G_drives, G_pert, θ::AbstractMatrix{Float64}; scale=nothing, cols::Int, goal, fid_kind::Int=0,
+                                          subspace=nothing, squared::Bool=false, device::Int=0)
+    n = size(G_drift, 1); N = n ÷ 2
+    m, T = size(controls); p = length(G_pert); S = size(θ, 1)
+    G0 = Float64.(vec(G_drift))
+    Gd = m == 0 ? Float64[] : reduce(vcat, [Float64.(vec(G)) for G in G_drives])
+    Gp = p == 0 ? Float64[] : reduce(vcat, [Float64.(vec(G)) for G in G_pert])
+    sub = isnothing(subspace) ? Int32[] : Int32.(collect(subspace) .- 1)
+    g = Float64.(collect(goal))
+    Z⃗ = vec(vcat(controls, reshape(Δt, 1, T)))                      # knot layout [a; Δt]
+    θt = Matrix{Float64}(transpose(θ))                               # sample-major
+    ct = isnothing(scale) ? Float64[] : vec(Matrix{Float64}(transpose(scale)))
+    fids = Vector{Float64}(undef, S)
+    gθ = Matrix{Float64}(undef, p, S)                                # sample-major: column s holds sample s
+    gc = Matrix{Float64}(undef, m, S)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve G0 Gd Gp sub g begin
+        desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
+                               pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
+                               squared ? 1 : 0, length(sub), pointer(g), isempty(sub) ? C_NULL : pointer(sub),
+                               device, 0, (0, 0)))
+        ok = Ref{Int32}(0)
+        rc = ccall((:qc_sweep_desc_grad_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
+        (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
+        rc = ccall((:qc_sweep_create, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Ptr{Cvoid}}), desc, h)
+        rc == 0 || error("qc_sweep_create: " * unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
+    end
+    rc = GC.@preserve Z⃗ init θt ct fids gθ gc ccall((:qc_sweep_grad_params, LIB[]), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        h[], Z⃗, init, S, p == 0 ? C_NULL : pointer(θt), isempty(ct) ? C_NULL : pointer(ct), C_NULL, fids, C_NULL, C_NULL, C_NULL,
+        p == 0 ? C_NULL : pointer(gθ), m == 0 ? C_NULL : pointer(gc))
+    msg = rc == 0 ? "" : unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), h[]))
+    ccall((:qc_sweep_destroy, LIB[]), Cvoid, (Ptr{Cvoid},), h[])
+    rc == 0 || error("qc_sweep_grad_params: " * msg)
+    return fids, Matrix{Float64}(transpose(gθ)), Matrix{Float64}(transpose(gc))
+end
+
+"""
     iso_vec_unitary_fidelity(Ũ⃗, Ũ⃗_goal; subspace=nothing, device=0, squared=false)          (unitary_minimum_time_problem.jl:77)
     iso_vec_unitary_free_phase_fidelity(Ũ⃗, Ũ⃗_goal, phases, phase_operators; subspace=nothing)  (unitary_minimum_time_problem.jl:86-90)
 

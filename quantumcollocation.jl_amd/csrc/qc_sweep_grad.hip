@@ -39,6 +39,13 @@
 //      not a control or timestep of knots 0 .. T-2 is written as +0.0); J = sum_s w_s F_s by a fixed tree.  No atomics anywhere: repeated
 //      calls give the same bits.
 //
+// Parameter gradients (qc_sweep_grad_params*): the derivatives with respect to the sample's own parameters,
+//     dF_s/dtheta[s,j] = sum_t sum(ZT_t . P_j),     dF_s/dc[s,k] = sum_t a_{t,k} sum(ZT_t . G_k)      (du_{t,k} before the factor c_k),
+// from the flavour <M, true> of the walk: Acc = sum_t ZT_t over the chunk (contracted with the perturbation tiles once, at the chunk's
+// end) and lane k's sum_t a_{t,k} du_{t,k}, both kept in the wave's LDS slice; the chunk's shares go to scratch S x n_chunks x (p + m)
+// and qc_sweep_par_reduce_kernel adds them in ascending chunk order.  The flavour <M, false> is the walk qc_sweep_grad_dev launches,
+// instruction for instruction what it was before the second flavour existed.
+//
 // Truncation of the once-differentiated series: the degree-8 polynomial's derivative misses sum_{k>=9} k ||Y||^(k-1) / k! ||dY||
 // <= 1.15 (1/8)^8 / 8! ||dY|| = 1.7e-12 ||dY||; over the 2^sq factors of the squarings the directions add up to h ||c_k G_k||, so the
 // relative error of a drive derivative is 1.7e-12, three orders inside the tests' 1e-9.  The degree stays 8.
@@ -125,14 +132,24 @@ __device__ inline double wave_sum(double v) {
     return (bcast_lane(v, 0) + bcast_lane(v, 16)) + (bcast_lane(v, 32) + bcast_lane(v, 48));
 }
 
-template <int M>
+// LDS of one wave: two transposition tiles, and in the parameter flavour behind them the accumulator tile sum_t ZT_t (256), the
+// interval's unscaled controls (64) and the scale accumulator (64)
+template <bool PAR>
+constexpr int kGSlice = 2 * 272 + (PAR ? 256 + 128 : 0);
+
+// One wavefront per (sample, chunk), walking the chunk backwards.  PAR = false: the per-interval derivatives only (`part` unused).
+// PAR = true, the parameter flavour, also accumulates the chunk's shares of dF_s/dtheta_j = sum_t sum(ZT_t . P_j) and
+// dF_s/dc_k = sum_t a_{t,k} sum(ZT_t . G_k) and stores them at the chunk's end as part[item][p + m]; `gs` may then be NULL (no
+// per-interval store, no timestep derivative).
+template <int M, bool PAR = false>
 __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_grad_kernel(const GradParams P, const double* __restrict__ Z, const double* __restrict__ theta,
                                                                          const double* __restrict__ scale, const double* __restrict__ xs,
-                                                                         const double* __restrict__ ls, double* __restrict__ gs) {
-    __shared__ double scr_all[kGWaves * 2 * 272];
+                                                                         const double* __restrict__ ls, double* __restrict__ gs,
+                                                                         double* __restrict__ part) {
+    __shared__ double scr_all[kGWaves * kGSlice<PAR>];
     const int lane = threadIdx.x & 63;
     const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * (2 * 272);
+    double* __restrict__ scr = scr_all + wq * kGSlice<PAR>;
     const long long item = (long long)blockIdx.x * kGWaves + wq;
     if (item >= P.items) return;
     const long long s = item / P.n_chunks;
@@ -176,6 +193,16 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_grad_kernel(const Gr
     const double* __restrict__ z = Z + (long long)(t1 - 1) * P.zdim;
     double av = m > 0 ? z[P.off_a + kl] : 0.0;
     double h = ft ? z[P.off_dt] : hfix;
+    // PAR: Acc = sum_t ZT_t (lane l, register r at accl[64 r + l]) and lane k's sum_t a_{t,k} du_{t,k} (accl[320 + l]; du BEFORE the
+    // factor c_k: no division by c) live in the wave's LDS slice, and the interval's unscaled controls wait there (accl[256 + l]) for
+    // the interval's end: every lane reads back what it wrote itself (no barrier), one read / write pair per interval off the MFMA
+    // chain.  Held in registers they do not fit beside M = 6 at three waves per SIMD.
+    double* accl = scr + 2 * 272;
+    if constexpr (PAR) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) accl[64 * r + lane] = 0.0;
+        accl[320 + lane] = 0.0;
+    }
 #pragma unroll 1
     for (int t = t1 - 1; t >= t0; --t) {
         // the previous interval's controls and timestep are requested before this interval's products
@@ -183,6 +210,7 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_grad_kernel(const Gr
         const double av_n = m > 0 ? zn[P.off_a + kl] : 0.0;
         const double h_n = ft ? zn[P.off_dt] : hfix;
         const double al = av * cl;
+        if constexpr (PAR) accl[256 + lane] = av;
         v4d Ga = base;
 #pragma unroll
         for (int u = 0; u < M; ++u) {
@@ -230,9 +258,9 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_grad_kernel(const Gr
         // M = 8: kept loop-invariant, the eight lane compares below live in 16 scalar registers and the kernel spills one; an opaque
         // copy of the lane index has them made per interval instead (8 v_cmp)
         int ln = lane;
-        if constexpr (M >= 8) asm volatile("" : "+v"(ln));
-        double out = 0.0;
-        if (ft) {
+        if constexpr (M >= 8 || (PAR && M >= 6)) asm volatile("" : "+v"(ln));
+        double out = 0.0, duv = 0.0;      // duv (PAR): lane k holds du_k = sum ZT . G_k
+        if (ft && (!PAR || gs)) {
             double ph = 0.0;
 #pragma unroll
             for (int r = 0; r < 4; ++r) ph = fma(KT[r], Ga[r], ph);
@@ -259,15 +287,57 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_grad_kernel(const Gr
 #pragma unroll
                 for (int r = 0; r < 4; ++r) pu = fma(ZT[r], Gj[u][r], pu);
                 const double du = wave_sum(pu);
-                out = ln == u ? du * cl : out;
+                if constexpr (PAR) duv = ln == u ? du : duv;
+                else out = ln == u ? du * cl : out;
             }
         }
-        if (lane < P.nd) gs[(s * P.n_int + t) * P.nd + lane] = out;
+        if constexpr (PAR) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) accl[64 * r + lane] += ZT[r];
+            accl[320 + lane] = fma(accl[256 + lane], duv, accl[320 + lane]);       // lanes >= m: duv = 0
+            out = ln < m ? duv * cl : out;
+            if (gs && lane < P.nd) gs[(s * P.n_int + t) * P.nd + lane] = out;
+        } else {
+            if (lane < P.nd) gs[(s * P.n_int + t) * P.nd + lane] = out;
+        }
         x = gmma(R, x, zero);
         lam = gmma(R, lam, zero);
         av = av_n;
         h = h_n;
     }
+    if constexpr (PAR) {
+        // the chunk's shares: one contraction of Acc per perturbation, the tiles read once here
+        v4d Acc;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Acc[r] = accl[64 * r + lane];
+        double acc_t = 0.0;
+        for (int q = 0; q < P.p; ++q) {
+            const v4d Pq = gimg(P.img, 1 + m + q, lane);
+            double pq = 0.0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) pq = fma(Acc[r], Pq[r], pq);
+            const double dq = wave_sum(pq);
+            acc_t = lane == q ? dq : acc_t;
+        }
+        double* __restrict__ po = part + item * (P.p + m);
+        if (lane < P.p) po[lane] = acc_t;
+        if (lane < m) po[P.p + lane] = accl[320 + lane];
+    }
+}
+
+// grad_theta[s][j] / grad_scale[s][k] = the chunk shares of sample s added in ascending chunk order; one thread per (s, parameter)
+__global__ __launch_bounds__(kRedT) void qc_sweep_par_reduce_kernel(long long S, int n_chunks, int p, int m, const double* __restrict__ part,
+                                                                    double* __restrict__ gth, double* __restrict__ gsc) {
+    const int np = p + m;
+    const long long i = (long long)blockIdx.x * kRedT + threadIdx.x;
+    if (i >= S * np) return;
+    const long long s = i / np;
+    const int q = (int)(i - s * np);
+    const double* __restrict__ src = part + s * n_chunks * np + q;
+    double acc = 0.0;
+    for (int c = 0; c < n_chunks; ++c) acc += src[(long long)c * np];
+    if (q < p) { if (gth) gth[s * p + q] = acc; }
+    else if (gsc) gsc[s * m + (q - p)] = acc;
 }
 
 // One workgroup per sample.  Up: x = Q_c ... Q_0 init with the loops of qc_sweep_finish_kernel, x stored at every chunk end; F_s and
@@ -436,19 +506,25 @@ extern "C" int qc_sweep_desc_grad_supported(const qc_sweep_desc* d, int32_t* sup
     return QC_OK;
 }
 
-extern "C" int qc_sweep_grad_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
-                                 const double* dweights, double* dfids, double* dJ, double* dgrad, double* dgrad_samples, void* stream) {
-    if (!h) return gfail(nullptr, QC_ERR_INVALID, "qc_sweep_grad_dev: NULL handle");
+// Both device entry points.  Without dgrad_theta / dgrad_scale this is qc_sweep_grad_dev as it always was: the same launches of the same
+// kernels.  With either, the walk is the parameter flavour, which also serves the per-interval outputs when they are asked for.
+static int qc_sweep_grad_launch(qc_sweep* h, const char* who, const double* dZ, const double* dinit, int64_t S, const double* dtheta,
+                                const double* dscale, const double* dweights, double* dfids, double* dJ, double* dgrad, double* dgrad_samples,
+                                double* dgrad_theta, double* dgrad_scale, void* stream) {
+    const std::string pre = std::string(who) + ": ";
+    if (!h) return gfail(nullptr, QC_ERR_INVALID, pre + "NULL handle");
     if (!h->grad_ok) return gfail(h, QC_ERR_UNSUPPORTED, "qc_sweep gradients: " + h->grad_why);
-    if (!dZ || !dinit) return gfail(h, QC_ERR_INVALID, "qc_sweep_grad_dev: NULL input");
-    if (S < 1 || S > (1ll << 24)) return gfail(h, QC_ERR_INVALID, "qc_sweep_grad_dev: S must be in 1 .. 2^24");
-    if (h->d.n_pert > 0 && !dtheta) return gfail(h, QC_ERR_INVALID, "qc_sweep_grad_dev: theta is NULL but the handle has perturbations");
-    if (!dfids && !dJ && !dgrad && !dgrad_samples) return gfail(h, QC_ERR_INVALID, "qc_sweep_grad_dev: every output is NULL");
+    if (!dZ || !dinit) return gfail(h, QC_ERR_INVALID, pre + "NULL input");
+    if (S < 1 || S > (1ll << 24)) return gfail(h, QC_ERR_INVALID, pre + "S must be in 1 .. 2^24");
+    if (h->d.n_pert > 0 && !dtheta) return gfail(h, QC_ERR_INVALID, pre + "theta is NULL but the handle has perturbations");
+    if (!dfids && !dJ && !dgrad && !dgrad_samples && !dgrad_theta && !dgrad_scale) return gfail(h, QC_ERR_INVALID, pre + "every output is NULL");
+    if (dgrad_theta && h->d.n_pert == 0) return gfail(h, QC_ERR_INVALID, pre + "grad_theta is given but the handle has no perturbations (n_pert = 0)");
+    if (dgrad_scale && h->d.m == 0) return gfail(h, QC_ERR_INVALID, pre + "grad_scale is given but the handle has no drives (m = 0)");
     std::string& slot = *qc_sweep_err_slot();
     qc_device_guard guard(h->device);
     QC_SIDE_HIP(h, slot, guard.err);
     hipStream_t st = (hipStream_t)stream;
-    const int m = h->d.m;
+    const int m = h->d.m, p = h->d.n_pert;
     const int nd = m + (h->d.off_dt >= 0 ? 1 : 0);
     const int64_t n_int = h->d.T - 1;
     int64_t chunk, n_chunks;
@@ -461,34 +537,47 @@ extern "C" int qc_sweep_grad_dev(qc_sweep* h, const double* dZ, const double* di
         QC_SIDE_HIP(h, slot, h->grow(&h->dGfid, &h->capGfid, (size_t)S));
         dfids = h->dGfid;
     }
-    const bool want_grad = dgrad || dgrad_samples;
+    const bool want_par = dgrad_theta || dgrad_scale;
+    const bool want_grad = (dgrad || dgrad_samples) && nd > 0;
     double* gsamp = dgrad_samples;
-    if (want_grad && !gsamp && nd > 0) {
+    if (want_grad && !gsamp) {
         QC_SIDE_HIP(h, slot, h->grow(&h->dGsamp, &h->capGsamp, (size_t)S * n_int * nd));
         gsamp = h->dGsamp;
     }
+    if (want_par) QC_SIDE_HIP(h, slot, h->grow(&h->dPart, &h->capPart, (size_t)S * n_chunks * (p + m)));
     SeedParams F;
     F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
     F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;
     const size_t lds = ((size_t)2 * h->ns + 256) * 8;
     hipLaunchKernelGGL(qc_sweep_seed_kernel, dim3((unsigned)S), dim3(kSeedT), lds, st, F, (const double*)h->dTot, dinit, (const double*)h->dgr,
                        (const double*)h->dgi, h->dXs, h->dLs, dfids);
-    if (want_grad && nd > 0) {
+    if (want_grad || want_par) {
         GradParams P;
-        P.n = h->n; P.nc = h->nc; P.m = m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
+        P.n = h->n; P.nc = h->nc; P.m = m; P.p = p; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
         P.n_int = (int)n_int; P.chunk = (int)chunk; P.n_chunks = (int)n_chunks; P.nd = nd;
         P.items = S * n_chunks;
         P.dt_fixed = h->d.dt_fixed;
         P.img = h->dImg;
         const unsigned grid = (unsigned)((P.items + kGWaves - 1) / kGWaves);
-#define QC_GRAD_LAUNCH(M_) hipLaunchKernelGGL(qc_sweep_grad_kernel<M_>, dim3(grid), dim3(64 * kGWaves), 0, st, P, dZ, dtheta, dscale, \
-                                              (const double*)h->dXs, (const double*)h->dLs, gsamp)
+        double* gs = want_grad ? gsamp : nullptr;
+#define QC_GRAD_LAUNCH(M_)                                                                                                                      \
+    do {                                                                                                                                        \
+        if (want_par)                                                                                                                           \
+            hipLaunchKernelGGL((qc_sweep_grad_kernel<M_, true>), dim3(grid), dim3(64 * kGWaves), 0, st, P, dZ, dtheta, dscale,                    \
+                               (const double*)h->dXs, (const double*)h->dLs, gs, h->dPart);                                                     \
+        else                                                                                                                                    \
+            hipLaunchKernelGGL((qc_sweep_grad_kernel<M_, false>), dim3(grid), dim3(64 * kGWaves), 0, st, P, dZ, dtheta, dscale,                   \
+                               (const double*)h->dXs, (const double*)h->dLs, gs, (double*)nullptr);                                             \
+    } while (0)
         if (m <= 1) QC_GRAD_LAUNCH(1);
         else if (m <= 2) QC_GRAD_LAUNCH(2);
         else if (m <= 4) QC_GRAD_LAUNCH(4);
         else if (m <= 6) QC_GRAD_LAUNCH(6);
         else QC_GRAD_LAUNCH(8);
 #undef QC_GRAD_LAUNCH
+        if (want_par)
+            hipLaunchKernelGGL(qc_sweep_par_reduce_kernel, dim3((unsigned)((S * (p + m) + kRedT - 1) / kRedT)), dim3(kRedT), 0, st, (long long)S,
+                               (int)n_chunks, p, m, (const double*)h->dPart, dgrad_theta, dgrad_scale);
     }
     if (dgrad) {
         ReduceParams R;
@@ -503,15 +592,33 @@ extern "C" int qc_sweep_grad_dev(qc_sweep* h, const double* dZ, const double* di
     return QC_OK;
 }
 
-extern "C" int qc_sweep_grad(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
-                             const double* weights, double* fids, double* J, double* grad, double* grad_samples) {
-    if (!h) return gfail(nullptr, QC_ERR_INVALID, "qc_sweep_grad: NULL handle");
+extern "C" int qc_sweep_grad_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
+                                 const double* dweights, double* dfids, double* dJ, double* dgrad, double* dgrad_samples, void* stream) {
+    return qc_sweep_grad_launch(h, "qc_sweep_grad_dev", dZ, dinit, S, dtheta, dscale, dweights, dfids, dJ, dgrad, dgrad_samples, nullptr, nullptr,
+                                stream);
+}
+
+extern "C" int qc_sweep_grad_params_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
+                                        const double* dweights, double* dfids, double* dJ, double* dgrad, double* dgrad_samples,
+                                        double* dgrad_theta, double* dgrad_scale, void* stream) {
+    return qc_sweep_grad_launch(h, "qc_sweep_grad_params_dev", dZ, dinit, S, dtheta, dscale, dweights, dfids, dJ, dgrad, dgrad_samples, dgrad_theta,
+                                dgrad_scale, stream);
+}
+
+// Both host-buffer entry points: stage, call the device entry point on the handle's stream, copy back, synchronise.
+static int qc_sweep_grad_host(qc_sweep* h, const char* who, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
+                              const double* weights, double* fids, double* J, double* grad, double* grad_samples, double* grad_theta,
+                              double* grad_scale) {
+    const std::string pre = std::string(who) + ": ";
+    if (!h) return gfail(nullptr, QC_ERR_INVALID, pre + "NULL handle");
     if (!h->grad_ok) return gfail(h, QC_ERR_UNSUPPORTED, "qc_sweep gradients: " + h->grad_why);
-    if (!Z || !init) return gfail(h, QC_ERR_INVALID, "qc_sweep_grad: NULL input");
-    if (S < 1 || S > (1ll << 24)) return gfail(h, QC_ERR_INVALID, "qc_sweep_grad: S must be in 1 .. 2^24");
+    if (!Z || !init) return gfail(h, QC_ERR_INVALID, pre + "NULL input");
+    if (S < 1 || S > (1ll << 24)) return gfail(h, QC_ERR_INVALID, pre + "S must be in 1 .. 2^24");
     const int m = h->d.m, p = h->d.n_pert;
-    if (p > 0 && !theta) return gfail(h, QC_ERR_INVALID, "qc_sweep_grad: theta is NULL but the handle has perturbations");
-    if (!fids && !J && !grad && !grad_samples) return gfail(h, QC_ERR_INVALID, "qc_sweep_grad: every output is NULL");
+    if (p > 0 && !theta) return gfail(h, QC_ERR_INVALID, pre + "theta is NULL but the handle has perturbations");
+    if (!fids && !J && !grad && !grad_samples && !grad_theta && !grad_scale) return gfail(h, QC_ERR_INVALID, pre + "every output is NULL");
+    if (grad_theta && p == 0) return gfail(h, QC_ERR_INVALID, pre + "grad_theta is given but the handle has no perturbations (n_pert = 0)");
+    if (grad_scale && m == 0) return gfail(h, QC_ERR_INVALID, pre + "grad_scale is given but the handle has no drives (m = 0)");
     std::string& slot = *qc_sweep_err_slot();
     qc_device_guard guard(h->device);
     QC_SIDE_HIP(h, slot, guard.err);
@@ -522,6 +629,8 @@ extern "C" int qc_sweep_grad(qc_sweep* h, const double* Z, const double* init, i
     if (weights) QC_SIDE_HIP(h, slot, h->grow(&h->sW, &h->capW, (size_t)S));
     if (fids) QC_SIDE_HIP(h, slot, h->grow(&h->sFids, &h->capFids, (size_t)S));
     if (grad_samples && n_samp) QC_SIDE_HIP(h, slot, h->grow(&h->sGradS, &h->capGradS, n_samp));
+    if (grad_theta) QC_SIDE_HIP(h, slot, h->grow(&h->sGth, &h->capGth, (size_t)S * p));
+    if (grad_scale) QC_SIDE_HIP(h, slot, h->grow(&h->sGsc, &h->capGsc, (size_t)S * m));
     if (grad && !h->sGrad) QC_SIDE_HIP(h, slot, h->alloc(&h->sGrad, (size_t)h->Zlen));
     if (J && !h->sJ) QC_SIDE_HIP(h, slot, h->alloc(&h->sJ, (size_t)1));
     QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sZ, Z, (size_t)h->Zlen * 8, hipMemcpyHostToDevice, h->stream));
@@ -530,13 +639,27 @@ extern "C" int qc_sweep_grad(qc_sweep* h, const double* Z, const double* init, i
     if (use_scale) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sScale, scale, (size_t)S * m * 8, hipMemcpyHostToDevice, h->stream));
     if (weights) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sW, weights, (size_t)S * 8, hipMemcpyHostToDevice, h->stream));
     const bool samp = grad_samples && n_samp;
-    int rc = qc_sweep_grad_dev(h, h->sZ, h->sInit, S, p ? h->sTheta : nullptr, use_scale ? h->sScale : nullptr, weights ? h->sW : nullptr,
-                               fids ? h->sFids : nullptr, J ? h->sJ : nullptr, grad ? h->sGrad : nullptr, samp ? h->sGradS : nullptr, h->stream);
+    int rc = qc_sweep_grad_launch(h, who, h->sZ, h->sInit, S, p ? h->sTheta : nullptr, use_scale ? h->sScale : nullptr, weights ? h->sW : nullptr,
+                                  fids ? h->sFids : nullptr, J ? h->sJ : nullptr, grad ? h->sGrad : nullptr, samp ? h->sGradS : nullptr,
+                                  grad_theta ? h->sGth : nullptr, grad_scale ? h->sGsc : nullptr, h->stream);
     if (rc) return rc;
     if (fids) QC_SIDE_HIP(h, slot, hipMemcpyAsync(fids, h->sFids, (size_t)S * 8, hipMemcpyDeviceToHost, h->stream));
     if (J) QC_SIDE_HIP(h, slot, hipMemcpyAsync(J, h->sJ, 8, hipMemcpyDeviceToHost, h->stream));
     if (grad) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad, h->sGrad, (size_t)h->Zlen * 8, hipMemcpyDeviceToHost, h->stream));
     if (samp) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad_samples, h->sGradS, n_samp * 8, hipMemcpyDeviceToHost, h->stream));
+    if (grad_theta) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad_theta, h->sGth, (size_t)S * p * 8, hipMemcpyDeviceToHost, h->stream));
+    if (grad_scale) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad_scale, h->sGsc, (size_t)S * m * 8, hipMemcpyDeviceToHost, h->stream));
     QC_SIDE_HIP(h, slot, hipStreamSynchronize(h->stream));
     return QC_OK;
+}
+
+extern "C" int qc_sweep_grad(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
+                             const double* weights, double* fids, double* J, double* grad, double* grad_samples) {
+    return qc_sweep_grad_host(h, "qc_sweep_grad", Z, init, S, theta, scale, weights, fids, J, grad, grad_samples, nullptr, nullptr);
+}
+
+extern "C" int qc_sweep_grad_params(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
+                                    const double* weights, double* fids, double* J, double* grad, double* grad_samples, double* grad_theta,
+                                    double* grad_scale) {
+    return qc_sweep_grad_host(h, "qc_sweep_grad_params", Z, init, S, theta, scale, weights, fids, J, grad, grad_samples, grad_theta, grad_scale);
 }

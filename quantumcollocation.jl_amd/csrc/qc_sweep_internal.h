@@ -34,6 +34,10 @@ struct qc_sweep : qc_side {
     double* sW = nullptr;    size_t capW = 0;
     double* sGradS = nullptr; size_t capGradS = 0;
     double *sGrad = nullptr, *sJ = nullptr;
+    // parameter gradients: the chunk shares S x n_chunks x (n_pert + m); staging of the host-buffer entry point
+    double* dPart = nullptr; size_t capPart = 0;
+    double* sGth = nullptr;  size_t capGth = 0;
+    double* sGsc = nullptr;  size_t capGsc = 0;
 };
 
 // records the message in the handle (when there is one) and in the slot qc_sweep_last_error(NULL) returns

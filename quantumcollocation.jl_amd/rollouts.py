@@ -15,6 +15,7 @@ the loop of the reference's robustness check, `unitary_rollout(traj.a, timesteps
     rollout_sweep(init, controls, Δt, system, perturbations, θ, scale)     (finals, fids)
     unitary_rollout_fidelity_sweep(traj, system, perturbations, θ)         S fidelities of the rolled-out unitary
     rollout_fidelity_sweep(traj, system, perturbations, θ; state_name)     ... of a ket
+    rollout_sweep_parameter_gradient(init, controls, Δt, system, perturbations, θ, scale)   (fids, dF/dθ, dF/dscale)
     RolloutSweep                                                            the handle, for callers that sweep repeatedly
 """
 from __future__ import annotations
@@ -226,7 +227,7 @@ class RolloutSweep:
 
     def pack(self, controls, dts=None) -> np.ndarray:
         """The trajectory vector of this handle's layout from controls (m x T) and timesteps (scalar or one per knot)."""
-        controls = np.asarray(controls, dtype=np.float64).reshape(self.m, -1)
+        controls = np.asarray(controls, dtype=np.float64).reshape(self.m, -1) if self.m else np.zeros((0, self.T))
         if controls.shape[1] != self.T:
             raise ValueError(f"controls must be {self.m} x {self.T}")
         Z = np.zeros(self.Z_len)
@@ -349,6 +350,57 @@ class RolloutSweep:
         if rc != _lib.QC_OK:
             raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
 
+    # -- gradients with respect to the systems: dF_s/dtheta and dF_s/dscale ---------------------------------------------------
+    def param_grad(self, Z, init, theta, scale=None, weights=None, with_controls: bool = False):
+        """(fids, grad_theta, grad_scale): the S fidelities, dF_s/dtheta[s, j] (S x n_pert) and dF_s/dscale[s, k] (S x m; `scale`
+        None: taken at all ones), raw per-sample values from one backward walk (`qc_sweep_grad_params`).  With `with_controls`:
+        (J, fids, grad, grad_theta, grad_scale), J and the dense gradient over the trajectory vector as `grad` returns them."""
+        Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
+        if Z.size != self.Z_len:
+            raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
+        init = np.ascontiguousarray(init, dtype=np.float64).ravel()
+        if init.size != self.ns:
+            raise ValueError(f"initial state has length {init.size}, expected {self.ns}")
+        S, theta, scale = self._samples(theta, scale)
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+            if weights.size != S:
+                raise ValueError(f"weights must have {S} entries")
+        f, gth, gsc = np.empty(S), np.empty((S, self.p)), np.empty((S, self.m))
+        J, g = C.c_double(), (np.empty(self.Z_len) if with_controls else None)
+        opt = lambda a: _lib.dptr(a) if (a is not None and a.size) else None
+        rc = _lib.lib.qc_sweep_grad_params(self._h, _lib.dptr(Z), _lib.dptr(init), S, opt(theta), opt(scale), opt(weights), _lib.dptr(f),
+                                           C.byref(J) if with_controls else None, opt(g), None, opt(gth), opt(gsc))
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        return (J.value, f, g, gth, gsc) if with_controls else (f, gth, gsc)
+
+    def param_grad_device(self, dZ, dinit, S: int, dtheta=None, dscale=None, dweights=None, dfids=None, dJ=None, dgrad=None, dgrad_samples=None,
+                          dgrad_theta=None, dgrad_scale=None, stream=None):
+        """`grad_device` plus dgrad_theta (S x n_pert) and dgrad_scale (S x m): `qc_sweep_grad_params_dev`.  Every output is
+        optional; without dgrad and dgrad_samples no per-interval buffer is written."""
+        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        S = int(S)
+        if all(t is None for t in (dfids, dJ, dgrad, dgrad_samples, dgrad_theta, dgrad_scale)):
+            raise ValueError("every output is None")
+        if dgrad_theta is not None and not self.p:
+            raise ValueError("dgrad_theta is given but the handle has no perturbations")
+        if dgrad_scale is not None and not self.m:
+            raise ValueError("dgrad_scale is given but the handle has no drives")
+        for t, cnt, what in ((dZ, self.Z_len, "dZ"), (dinit, self.ns, "dinit"), (dtheta, S * self.p, "dtheta"), (dscale, S * self.m, "dscale"),
+                             (dweights, S, "dweights"), (dfids, S, "dfids"), (dJ, 1, "dJ"), (dgrad, self.Z_len, "dgrad"),
+                             (dgrad_samples, S * (self.T - 1) * self.n_deriv, "dgrad_samples"), (dgrad_theta, S * self.p, "dgrad_theta"),
+                             (dgrad_scale, S * self.m, "dgrad_scale")):
+            if t is not None and (t.numel() != cnt or t.dtype != torch.float64 or not t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous float64 tensor of {cnt} entries")
+        if self.p and dtheta is None:
+            raise ValueError("dtheta is required: the handle has perturbations")
+        ptr = lambda t, use=True: t.data_ptr() if (t is not None and use and t.numel()) else None
+        rc = _lib.lib.qc_sweep_grad_params_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dweights),
+                                               ptr(dfids), ptr(dJ), ptr(dgrad), ptr(dgrad_samples), ptr(dgrad_theta), ptr(dgrad_scale), s)
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+
     def close(self):
         if getattr(self, "_h", None):
             _lib.lib.qc_sweep_destroy(self._h)
@@ -376,6 +428,25 @@ def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None,
     sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device)
     try:
         return sw.eval(sw.pack(controls, dts), init, theta, scale)
+    finally:
+        sw.close()
+
+
+def rollout_sweep_parameter_gradient(init, controls, dts, system, perturbations, theta, scale=None, cols: Optional[int] = None, goal=None,
+                                     fid_kind="unitary", subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS):
+    """(fids, grad_theta, grad_scale) of S rollouts under the perturbed systems: the fidelities of `rollout_sweep` and their derivatives
+    with respect to theta (S x len(perturbations)) and scale (S x n_drives; None: taken at all ones).  Arguments as `rollout_sweep`."""
+    controls = np.asarray(controls, dtype=np.float64)
+    if controls.ndim != 2 or controls.shape[0] != system.n_drives:
+        raise ValueError("controls must be n_drives x T")
+    T = controls.shape[1]
+    init = np.ascontiguousarray(init, dtype=np.float64).ravel()
+    n = 2 * system.state_levels
+    if cols is None:
+        cols = init.size // n
+    sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device)
+    try:
+        return sw.param_grad(sw.pack(controls, dts), init, theta, scale)
     finally:
         sw.close()
 
