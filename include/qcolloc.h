@@ -624,13 +624,17 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * (`open_rollout`).  The propagator is the matrix exponential, as in qc_rollout.  Only the controls and timesteps are read from Z.
  * Kernels: 2N <= 16 with up to 8 drives runs on the f64 matrix cores, one wavefront per (sample, chunk of intervals)
  * ("mfma16-sweep"); larger systems run the rollout kernels once per sample ("rollout-per-sample": correctness, not speed).
+ * With wide = QC_SWEEP_WIDE the matrix cores serve 16 < 2N <= 32 (up to 8 drives) as well ("mfma32-sweep": 2 x 2 tiles a matrix, the same
+ * work item and chunk rule); 2N <= 16 is "mfma16-sweep" as before, everything else the per-sample form.  wide = 0 is the routing of the
+ * two sentences above, unchanged; any other value is QC_ERR_INVALID.
  * Results do not depend on scheduling: repeated calls return the same bits.  Non-finite inputs are evaluated, not rejected.
  * Gradients with respect to the controls and timesteps (qc_sweep_grad*) and to the samples' own parameters theta and `scale`
- * (qc_sweep_grad_params*), both below, are served for closed systems in the MFMA form.
+ * (qc_sweep_grad_params*), both below, are served for closed systems in the MFMA forms (parameter gradients: "mfma16-sweep" only).
  * Out of scope: per-knot outputs, open-system gradients (they need stored forward states), second derivatives, derivatives of the
  * final states, the free-phase fidelity, several devices. */
 #define QC_MAX_PERT 8
 #define QC_SWEEP_FID_NONE (-1)   /* qc_sweep_desc.fid_kind: final states only */
+#define QC_SWEEP_WIDE 1          /* qc_sweep_desc.wide */
 typedef struct qc_sweep_desc {
     int64_t T;
     int32_t zdim;
@@ -651,21 +655,21 @@ typedef struct qc_sweep_desc {
     const double* goal_iso;      /* as qc_fidelity_desc.goal_iso */
     const int32_t* subspace;     /* unitary only: 0-based levels, or NULL = all */
     int32_t device;
-    int32_t reserved0;
+    int32_t wide;                /* 0, or QC_SWEEP_WIDE: the matrix-core form up to 2N = 32 ("mfma32-sweep"); anything else is QC_ERR_INVALID */
     int64_t reserved1[2];
 } qc_sweep_desc;
 typedef struct qc_sweep qc_sweep;
 int64_t qc_sizeof_sweep_desc(void);
 /* device-free: QC_ERR_INVALID with a message (qc_sweep_last_error(NULL)); QC_ERR_UNSUPPORTED for 2N > 64 */
 int qc_sweep_desc_validate(const qc_sweep_desc* d);
-/* device-free: the launch a handle of this descriptor takes for S samples -- mfma: 1 = "mfma16-sweep", 0 = "rollout-per-sample";
+/* device-free: the launch a handle of this descriptor takes for S samples -- mfma: 1 = "mfma16-sweep" or "mfma32-sweep", 0 = "rollout-per-sample";
  * chunk / n_chunks: intervals per wavefront and chunks per sample of the MFMA form (n_chunks = 1 once S alone fills the device,
  * more for few samples; n_chunks = 0 for the per-sample form).  Outputs may be NULL. */
 int qc_sweep_desc_launch(const qc_sweep_desc* d, int64_t S, int32_t* mfma, int64_t* chunk, int64_t* n_chunks);
 int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out);
 void qc_sweep_destroy(qc_sweep* h);
 const char* qc_sweep_last_error(const qc_sweep* h);
-/* "mfma16-sweep" or "rollout-per-sample" (static strings; "none" for a NULL handle) */
+/* "mfma16-sweep", "mfma32-sweep" (wide descriptors, 16 < 2N <= 32) or "rollout-per-sample" (static strings; "none" for a NULL handle) */
 const char* qc_sweep_kernel_name(const qc_sweep* h);
 /* host buffers.  Z: the full trajectory vector (zdim T + global_dim); init: 2N x cols; theta: S x n_pert (NULL when n_pert = 0);
  * scale: S x m or NULL; finals: S x (2N cols), sample-major; fids: S values.  Either output may be NULL, not both. */
@@ -682,7 +686,7 @@ int qc_sweep_eval_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_
 /* dF_s/da_{t,k} and dF_s/ddt_t of every sample's fidelity, and J = sum_s w_s F_s with its dense gradient over Z.  One backward walk
  * with one Frechet-derivative chain per interval: the cost is a small constant times the forward sweep, whatever the number of drives.
  * Served where ALL of these hold; everything else returns QC_ERR_UNSUPPORTED with a message that names the reason:
- *   - the handle takes the "mfma16-sweep" form (2N <= 16, m <= 8);
+ *   - the handle takes the "mfma16-sweep" form (2N <= 16, m <= 8) or, with wide = QC_SWEEP_WIDE, the "mfma32-sweep" form (2N <= 32, m <= 8);
  *   - fid_kind is QC_FID_UNITARY (either form, with or without subspace) or QC_FID_KET;
  *   - at most 16 state columns;
  *   - G_drift, every drive and every perturbation are antisymmetric, max |G + G^T| <= 64 eps max |G| (closed systems: iso generators
@@ -712,7 +716,8 @@ int qc_sweep_grad(qc_sweep* h, const double* Z, const double* init, int64_t S, c
  * depend on which other outputs were requested.  Every other argument, the scope (qc_sweep_desc_grad_supported), the scratch and the
  * one-in-flight rule are those of qc_sweep_grad_dev, and fids / J / grad / grad_samples carry its bits; without grad and
  * grad_samples the S x (T-1) x (m + (off_dt >= 0)) per-interval buffer is neither allocated nor written.  Every output is optional,
- * at least one must be non-NULL; grad_theta on a handle with n_pert = 0, or grad_scale with m = 0, is QC_ERR_INVALID. */
+ * at least one must be non-NULL; grad_theta on a handle with n_pert = 0, or grad_scale with m = 0, is QC_ERR_INVALID.
+ * On an "mfma32-sweep" handle both entry points return QC_ERR_UNSUPPORTED ("parameter gradients are not served in the mfma32-sweep form"). */
 int qc_sweep_grad_params_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
                              const double* dweights, double* dfids, double* dJ, double* dgrad, double* dgrad_samples,
                              double* dgrad_theta, double* dgrad_scale, void* stream);

@@ -74,7 +74,7 @@ struct QCSweepDesc
     m::Int32; state_cols::Int32; n_pert::Int32; fid_kind::Int32
     G_drift::Ptr{Float64}; G_drives::Ptr{Float64}; G_pert::Ptr{Float64}
     fid_form::Int32; n_sub::Int32; goal_iso::Ptr{Float64}; subspace::Ptr{Int32}
-    device::Int32; reserved0::Int32; reserved1::NTuple{2,Int64}
+    device::Int32; wide::Int32; reserved1::NTuple{2,Int64}
 end
 
 function __init__()
@@ -699,18 +699,19 @@ end
 
 """
     rollout_sweep(init, controls, Δt, G_drift, G_drives, G_pert, θ; scale=nothing, cols, goal=nothing, fid_kind=-1,
-                  subspace=nothing, squared=false, device=0)  ->  (finals, fids)
+                  subspace=nothing, squared=false, device=0, wide=false)  ->  (finals, fids)
 
 Final states and fidelities of ONE trajectory of controls under S perturbed systems, in one call (`qc_sweep_eval`): the loop of the
 reference's robustness check, `unitary_rollout(traj.a, timesteps, systems(ζ))[:, end]` and `iso_vec_unitary_fidelity` for every ζ
 (unitary_sampling_problem.jl:233-243).  Sample s evolves under G_drift + Σ_j θ[s, j] G_pert[j] + Σ_k scale[s, k] a_k G_drives[k]
 (2N×2N generators: `system.G_drift`, `system.G_drives`, and e.g. `G(Z)` for a detuning).  `controls` is m×T, `Δt` a vector of T
 timesteps, `θ` S×p, `scale` S×m or nothing; `fid_kind` -1 (none), 0 (unitary; `subspace` 1-based, `squared`), 1 (ket), 2 (density
-operator).  `finals` is (2N·cols)×S.  UNTESTED here, like the rest of this file.
+operator).  `wide = true` sets `qc_sweep_desc.wide = QC_SWEEP_WIDE`: the matrix-core form up to 2N = 32 ("mfma32-sweep") instead of one
+rollout per sample from 2N = 18 up.  `finals` is (2N·cols)×S.  UNTESTED here, like the rest of this file.
 """
 function rollout_sweep(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift, G_drives, G_pert,
                        θ::AbstractMatrix{Float64}; scale=nothing, cols::Int, goal=nothing, fid_kind::Int=-1, subspace=nothing,
-                       squared::Bool=false, device::Int=0)
+                       squared::Bool=false, device::Int=0, wide::Bool=false)
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(θ, 1)
     G0 = Float64.(vec(G_drift))
@@ -728,7 +729,7 @@ function rollout_sweep(init::AbstractVector{Float64}, controls::AbstractMatrix{F
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
                                squared ? 1 : 0, length(sub), isempty(g) ? C_NULL : pointer(g), isempty(sub) ? C_NULL : pointer(sub),
-                               device, 0, (0, 0)))
+                               device, wide ? 1 : 0, (0, 0)))
         rc = ccall((:qc_sweep_create, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Ptr{Cvoid}}), desc, h)
         rc == 0 || error("qc_sweep_create: " * unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
     end
@@ -743,17 +744,17 @@ end
 
 """
     rollout_sweep_gradient(init, controls, Δt, G_drift, G_drives, G_pert, θ; scale=nothing, weights=nothing, cols, goal, fid_kind=0,
-                           subspace=nothing, squared=false, per_sample=false, device=0)  ->  (J, fids, ∇a, ∇Δt[, grad_samples])
+                           subspace=nothing, squared=false, per_sample=false, device=0, wide=false)  ->  (J, fids, ∇a, ∇Δt[, grad_samples])
 
 The adjoint of `rollout_sweep` (`qc_sweep_grad`): J = Σ_s w_s F_s (`weights`: S values, default 1/S each), the S fidelities, and the
 gradient of J with respect to the controls (`∇a`, m×T) and the timesteps (`∇Δt`, T); the last knot's columns are zero.  With
 `per_sample`, `grad_samples` is (m+1)×(T-1)×S: ∂F_s/∂a_{t,k}, then ∂F_s/∂Δt_t.  Served for closed systems (antisymmetric generators)
-with 2N ≤ 16, m ≤ 8 and `fid_kind` 0 (unitary) or 1 (ket); everything else errors with the library's reason.  Arguments as
+with 2N ≤ 16 (`wide = true`: 2N ≤ 32), m ≤ 8 and `fid_kind` 0 (unitary) or 1 (ket); everything else errors with the library's reason.  Arguments as
 `rollout_sweep`.  UNTESTED here, like the rest of this file.
 """
 function rollout_sweep_gradient(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift, G_drives,
                                 G_pert, θ::AbstractMatrix{Float64}; scale=nothing, weights=nothing, cols::Int, goal, fid_kind::Int=0,
-                                subspace=nothing, squared::Bool=false, per_sample::Bool=false, device::Int=0)
+                                subspace=nothing, squared::Bool=false, per_sample::Bool=false, device::Int=0, wide::Bool=false)
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(θ, 1)
     G0 = Float64.(vec(G_drift))
@@ -774,7 +775,7 @@ function rollout_sweep_gradient(init::AbstractVector{Float64}, controls::Abstrac
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
                                squared ? 1 : 0, length(sub), pointer(g), isempty(sub) ? C_NULL : pointer(sub),
-                               device, 0, (0, 0)))
+                               device, wide ? 1 : 0, (0, 0)))
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_grad_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
         (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))

@@ -48,6 +48,7 @@ QC_FID_FORM_ABS, QC_FID_FORM_ABS2 = 0, 1
 QC_ROBUST_HESS_NONE, QC_ROBUST_HESS_EXACT = 0, 1
 QC_MAX_PERT = 8
 QC_SWEEP_FID_NONE = -1      # qc_sweep_desc.fid_kind: final states only
+QC_SWEEP_WIDE = 1           # qc_sweep_desc.wide: the matrix-core form up to 2N = 32
 QC_ROWS_STACKED = 0
 QC_ROWS_BY_COMPONENT = 1
 
@@ -204,7 +205,7 @@ class qc_sweep_desc(C.Structure):
         ("goal_iso", _c_double_p),
         ("subspace", C.POINTER(C.c_int32)),
         ("device", C.c_int32),
-        ("reserved0", C.c_int32),
+        ("wide", C.c_int32),
         ("reserved1", C.c_int64 * 2),
     ]
 

@@ -20,6 +20,9 @@
 // 16 < 2N <= 64, or more than 8 drives ("rollout-per-sample"): a small kernel writes the sample's generator set (perturbed drift,
 // scaled drives), the rollout kernels of qc_rollout.hip run on it, and the same final-state / fidelity launch follows.  Correctness,
 // not speed.
+//
+// A descriptor with wide = QC_SWEEP_WIDE takes the matrix cores up to 2N = 32: 16 < 2N <= 32 with up to 8 drives is "mfma32-sweep"
+// (qc_sweep32.hip, 2 x 2 tiles a matrix); the second launch below is shared, with ld = 32.  wide = 0 is the routing above, unchanged.
 #include <math.h>
 #include <string.h>
 
@@ -313,10 +316,16 @@ int sweep_validate(const qc_sweep_desc* d) {
     if (2 * (int64_t)d->N > 64) return sfail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: 2N = " + std::to_string(2 * (int64_t)d->N) + " exceeds the supported 2N <= 64");
     if (2 * (int64_t)d->N * nc > 4096) return sfail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: states of more than 4096 entries (2N x state_cols) are not supported");
     if (d->m > 64) return sfail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: more than 64 drives are not supported");
+    if (d->wide != 0 && d->wide != QC_SWEEP_WIDE) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: wide must be 0 or QC_SWEEP_WIDE (1)");
     return QC_OK;
 }
 
-bool sweep_is_mfma(const qc_sweep_desc* d) { return 2 * d->N <= 16 && d->m <= kSMmax; }
+int sweep_form(const qc_sweep_desc* d) {
+    if (d->m > kSMmax) return 0;
+    if (2 * d->N <= 16) return 1;
+    return (d->wide == QC_SWEEP_WIDE && 2 * d->N <= 32) ? 2 : 0;
+}
+bool sweep_is_mfma(const qc_sweep_desc* d) { return sweep_form(d) != 0; }
 
 }  // namespace
 
@@ -325,9 +334,12 @@ int qc_sweep_fail(qc_side* h, int code, const std::string& msg) { return sfail(h
 std::string* qc_sweep_err_slot() { return &g_swerr; }
 int qc_sweep_validate_desc(const qc_sweep_desc* d) { return sweep_validate(d); }
 bool qc_sweep_desc_is_mfma(const qc_sweep_desc* d) { return sweep_is_mfma(d); }
+int qc_sweep_desc_form(const qc_sweep_desc* d) { return sweep_form(d); }
+void qc_sweep_chunks(int64_t S, int64_t T, int64_t* chunk, int64_t* n_chunks) { sweep_chunks(S, T, chunk, n_chunks); }
 
 int qc_sweep_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, hipStream_t st, int64_t* chunk_out,
                            int64_t* n_chunks_out) {
+    if (h->mfma32) return qc_sweep32_launch_totals(h, dZ, S, dtheta, dscale, st, chunk_out, n_chunks_out);
     const int m = h->d.m;
     int64_t chunk, n_chunks;
     sweep_chunks(S, h->d.T, &chunk, &n_chunks);
@@ -372,7 +384,7 @@ extern "C" int qc_sweep_desc_launch(const qc_sweep_desc* d, int64_t S, int32_t* 
 
 extern "C" const char* qc_sweep_kernel_name(const qc_sweep* h) {
     if (!h) return "none";
-    return h->mfma ? "mfma16-sweep" : "rollout-per-sample";
+    return h->mfma32 ? "mfma32-sweep" : h->mfma ? "mfma16-sweep" : "rollout-per-sample";
 }
 
 extern "C" void qc_sweep_destroy(qc_sweep* h) {
@@ -391,6 +403,7 @@ extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
     h->d = *d;
     h->device = d->device;
     h->mfma = sweep_is_mfma(d);
+    h->mfma32 = sweep_form(d) == 2;
     h->grad_ok = qc_sweep_grad_scope(d, &h->grad_why);      // from the caller's matrices, which the handle does not keep
     const int N = d->N, n = 2 * N, n2 = n * n, m = d->m, p = d->n_pert;
     h->n = n;
@@ -404,7 +417,10 @@ extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
     if (m) memcpy(G.data() + n2, d->G_drives, (size_t)m * n2 * 8);
     if (p) memcpy(G.data() + (size_t)(1 + m) * n2, d->G_pert, (size_t)p * n2 * 8);
     std::vector<double> img;
-    if (h->mfma) {   // A layout: lane (g, i) reg kk holds G[i][4 kk + g], zero outside n x n
+    if (h->mfma32) {
+        img.resize((size_t)nm * 1024);
+        for (int mat = 0; mat < nm; ++mat) qc_sweep32_image(G.data() + (size_t)mat * n2, n, img.data() + (size_t)mat * 1024);
+    } else if (h->mfma) {   // A layout: lane (g, i) reg kk holds G[i][4 kk + g], zero outside n x n
         img.assign((size_t)nm * 256, 0.0);
         for (int mat = 0; mat < nm; ++mat)
             for (int kk = 0; kk < 4; ++kk)
@@ -470,7 +486,7 @@ extern "C" int qc_sweep_eval_dev(qc_sweep* h, const double* dZ, const double* di
         int64_t chunk, n_chunks;
         int rc = qc_sweep_launch_totals(h, dZ, S, dtheta, dscale, st, &chunk, &n_chunks);
         if (rc) return rc;
-        F.ld = 16; F.n_chunks = (int)n_chunks; F.src_stride = 0;
+        F.ld = h->mfma32 ? 32 : 16; F.n_chunks = (int)n_chunks; F.src_stride = 0;
         src = dinit;
     } else {
         QC_SIDE_HIP(h, g_swerr, h->grow(&h->dFin, &h->capFin, (size_t)S * h->ns));

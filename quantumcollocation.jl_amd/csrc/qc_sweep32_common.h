@@ -1,0 +1,106 @@
+// What the forward kernel (qc_sweep32.hip) and the backward walk (qc_sweep32_grad.hip) of the "mfma32-sweep" form share, in one place so
+// that it cannot drift: the walk reverses the forward step only if both form the same generator and choose the same number of
+// squarings.  Constants, the sample's base matrix, the interval's generator, the squaring rule, the four-tile transpose.
+#pragma once
+#include <math.h>
+
+#include "qc_mfma_common.h"
+
+namespace qc_sweep32 {
+
+using namespace qc_mfma;
+
+constexpr int kDeg = 8;             // as qc_sweep.hip: ||Y||_1 <= 1/8, degree 8, truncation (1/8)^9 / 9! = 4e-14
+constexpr double kTh = 0.125;
+constexpr int kWaves = 4;           // (sample, chunk) items per workgroup: one wave each, the waves never synchronise
+constexpr int kScr = 4 * 272;       // doubles of LDS per wave: four transposition tiles
+
+// 1 / k!, k = 0 .. 8: the values of kSInvFact (qc_sweep.hip; a __constant__ table is private to its translation unit)
+static __constant__ const double kInvFact[kDeg + 1] = {1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0, 1.0 / 40320.0};
+
+template <int CTRL>
+static __device__ __forceinline__ double dpp(double x) {
+    int lo = __double2loint(x), hi = __double2hiint(x);
+    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+// sample s's base matrix G_drift + sum_q theta[s, q] P_q in A layout (images: 1024 doubles a matrix -- drift, m drives, p perturbations)
+__device__ __forceinline__ void base_matrix(const double* __restrict__ img, int m, int p, const double* __restrict__ theta, long long s, int lane,
+                                            v4d (&base)[2][2]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) base[q >> 1][q & 1] = load_image_tile(img + q * 256, lane);
+    for (int q = 0; q < p; ++q) {
+        const double th = theta[s * p + q];
+        const double* __restrict__ Pq = img + (size_t)(1 + m + q) * 1024;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const v4d t = load_image_tile(Pq + u * 256, lane);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) base[u >> 1][u & 1][r] = fma(th, t[r], base[u >> 1][u & 1][r]);
+        }
+    }
+}
+
+// G = base + sum_u al_u G_u in A layout; lane u of `al` holds the (scaled) amplitude of drive u.  The drive images are read from the
+// image buffer every interval (8 16-byte loads per drive and lane): eight resident drives would be 256 VGPRs.
+__device__ __forceinline__ void generator(const double* __restrict__ img, int m, double al, const v4d (&base)[2][2], int lane, v4d (&G)[2][2]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) G[q >> 1][q & 1] = base[q >> 1][q & 1];
+#pragma unroll 1
+    for (int u = 0; u < m; ++u) {
+        const double a = bcast_lane(al, u);
+        const double* __restrict__ Gu = img + (size_t)(1 + u) * 1024;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const v4d t4 = load_image_tile(Gu + q * 256, lane);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) G[q >> 1][q & 1][r] = fma(a, t4[r], G[q >> 1][q & 1][r]);
+        }
+    }
+}
+
+// The number of squarings, wave-uniform: the smallest sq with ||h G||_1 / 2^sq <= 1/8 (0 for a non-finite norm).  ||h G||_1 is the
+// largest column sum: tile (I, K), lane (g, i), reg kk holds G[16 I + i][16 K + 4 kk + g]; the two tile rows and the 16 lanes of a row
+// share a column.
+__device__ __forceinline__ int squarings(const v4d (&G)[2][2], double h) {
+    int sq = 0;
+    double best = 0.0;
+    bool bad = false;
+#pragma unroll
+    for (int K = 0; K < 2; ++K) {
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            double cs = fabs(h * G[0][K][kk]) + fabs(h * G[1][K][kk]);
+            cs += dpp<0x128>(cs);
+            cs += dpp<0x124>(cs);
+            cs += dpp<0x122>(cs);
+            cs += dpp<0x121>(cs);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double v = bcast_lane(cs, 16 * r);
+                if (!(v == v) || v > 1e300) bad = true;
+                best = fmax(best, v);
+            }
+        }
+    }
+    if (!bad && best > kTh) {
+        int e;
+        (void)frexp(best / kTh, &e);
+        sq = e;
+        if (ldexp(kTh, e - 1) >= best) sq = e - 1;
+        sq = sq < 0 ? 0 : (sq > 60 ? 60 : sq);
+    }
+    return __builtin_amdgcn_readfirstlane(sq);
+}
+
+// the four tiles of a D-layout matrix, each transposed: the matrix in A layout (one LDS round trip)
+__device__ __forceinline__ void transpose4(double* __restrict__ scr, const v4d (&X)[2][2], v4d (&Xt)[2][2], int g, int j) {
+    const v4d in[4] = {X[0][0], X[0][1], X[1][0], X[1][1]};
+    v4d out[4];
+    lds_transpose16_multi<4>(scr, in, out, g, j);
+    Xt[0][0] = out[0]; Xt[0][1] = out[1]; Xt[1][0] = out[2]; Xt[1][1] = out[3];
+}
+
+}  // namespace qc_sweep32

@@ -1,0 +1,345 @@
+// Sweep gradients for "mfma32-sweep" handles (16 < 2N <= 32, wide descriptors): the adjoint walk of qc_sweep_grad.hip with every matrix
+// 2 x 2 tiles of 16 x 16.  The mathematics is that file's, line for line (read its header first): antisymmetric generators make E
+// orthogonal, so x_t = E^T x_{t+1} (no state stored inside a chunk), L(hG; E^T K) = E^T L(hG; K) with K = x_{t+1} lambda_{t+1}^T (the
+// Frechet chain runs beside the Horner chain), one chain per interval serves all m drives, dF/da_k = c_k sum ZT . G_k,
+// dF/dh = -sum KT . G.  Degree 8, threshold 1/8, the 1/k! table, the generator and the squaring rule are the forward kernel's: both files
+// take them from qc_sweep32_common.h.
+//
+// Launches of one call on such a handle (qc_sweep_grad_launch of qc_sweep_grad.hip routes here):
+//   1. qc_sweep_mfma32_kernel: the forward chunk totals, column-major 32 x 32;
+//   2. qc_sweep32_seed_kernel, one workgroup per sample: the loops and the reduction of qc_sweep_finish_kernel at ld = 32 (the
+//      fidelities carry the bits of qc_sweep_eval on the same handle), x at every chunk end, lambda_{T-1} = dphi/dx by the formulas of
+//      qc_fidelity.hip, then lambda chained down through the transposed totals and stored at every chunk end;
+//   3. qc_sweep32_grad_kernel, one wavefront per (sample, chunk), walking the chunk backwards.  X[I][J] is the tile of rows 16 I .. and
+//      columns 16 J ..; the state and the adjoint are 32 x <= 16: two tiles each.  "A D-layout tile read as the A operand is its
+//      transpose" holds per tile, so for a D-layout matrix M the A operand (I, K) of M^T is the tile M[K][I] as it stands (an index
+//      swap), and the A operand (I, K) of M is the tile M[I][K] transposed through LDS.  Per interval:
+//        KT[I][J] = lambda_I x_J^T                    four tiles transposed in one LDS round trip, 4 tile products
+//        dF/dh = -sum_IJ KT[I][J] . Ga[J][I]          elementwise against the generator's A-layout tiles
+//        Y = h G / 2^sq,  dY(I, K) = (h / 2^sq) KT[K][I]
+//        R_k = Y R_k+1 + I/(k-1)!,  dR_k = dY R_k+1 + Y dR_k+1,  k = 8 .. 1     one tile column at a time, in place: column J of the
+//                                                     results needs column J of R and dR only; six accumulator tiles, six chains
+//        sq squarings: dE <- E dE + dE E, E <- E E    E, dE as A operands: eight tiles transposed in two LDS round trips of four
+//        ZT[I][J] = sum_K R[K][I]^T dR[K][J]          E^T dE
+//        dF/da_k = c_k sum_IJ ZT[I][J] . G_k[J][I]    the drive images read again from the image buffer (qc_sweep32.hip), m wave sums
+//        x_I <- sum_K R[K][I]^T x_K,  lambda likewise
+//      and the m + 1 values of the interval leave through one vector store (lane k: drive k, lane m: timestep).
+//      MFMAs per interval: 16 + 8 x 96 + 96 sq + 32 + 32 = 848 + 96 sq, against the forward kernel's 288 + 32 sq (2.9x - 3x).
+//   4. qc_sweep_grad_reduce_kernel / qc_sweep_J_kernel of qc_sweep_grad.hip, unchanged (they do not depend on the size).
+// No atomics, sums in a fixed order: repeated calls give the same bits.  Parameter gradients are not served in this form.
+#include <math.h>
+
+#include <string>
+
+#include "qc_mfma_common.h"
+#include "qc_sweep32_common.h"
+#include "qc_sweep_internal.h"
+
+namespace {
+
+using namespace qc_sweep32;
+
+constexpr int kVSeedT = 256;        // threads of the seed workgroup: the thread count of qc_sweep_finish_kernel (same sums, same bits)
+
+struct Grad32Params {
+    int n, nc, m, p, zdim, off_a, off_dt, n_int, chunk, n_chunks, nd;   // nd = m + (off_dt >= 0): derivatives per interval
+    long long items;             // S * n_chunks
+    double dt_fixed;
+    const double* img;           // A-layout images, 1024 doubles a matrix: drift, m drives, p perturbations
+};
+
+struct Seed32Params {
+    int n, ns, n_chunks, fid_kind, fid_form, fid_n;
+};
+
+// the sum over the 64 lanes in a fixed order, wave-uniform (as qc_sweep_grad.hip)
+__device__ inline double vwave_sum(double v) {
+    v += dpp<0x128>(v);
+    v += dpp<0x124>(v);
+    v += dpp<0x122>(v);
+    v += dpp<0x121>(v);
+    return (bcast_lane(v, 0) + bcast_lane(v, 16)) + (bcast_lane(v, 32) + bcast_lane(v, 48));
+}
+
+// column J of (R, dR) <- (A R + C, dA R + A dR) in place; C given by its tiles of that column.  Six accumulator chains, interleaved.
+__device__ __forceinline__ void vcol(const v4d (&A)[2][2], const v4d (&dA)[2][2], v4d (&R)[2][2], v4d (&dR)[2][2], int J, const v4d& c0,
+                                     const v4d& c1) {
+    const v4d z = {0.0, 0.0, 0.0, 0.0};
+    v4d p0 = z, p1 = z, q0 = z, q1 = z, r0 = c0, r1 = c1;
+#pragma unroll
+    for (int K = 0; K < 2; ++K) {
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            p0 = __builtin_amdgcn_mfma_f64_16x16x4f64(dA[0][K][kk], R[K][J][kk], p0, 0, 0, 0);
+            p1 = __builtin_amdgcn_mfma_f64_16x16x4f64(dA[1][K][kk], R[K][J][kk], p1, 0, 0, 0);
+            q0 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[0][K][kk], dR[K][J][kk], q0, 0, 0, 0);
+            q1 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[1][K][kk], dR[K][J][kk], q1, 0, 0, 0);
+            r0 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[0][K][kk], R[K][J][kk], r0, 0, 0, 0);
+            r1 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[1][K][kk], R[K][J][kk], r1, 0, 0, 0);
+        }
+    }
+    dR[0][J] = p0 + q0;
+    dR[1][J] = p1 + q1;
+    R[0][J] = r0;
+    R[1][J] = r1;
+}
+
+__device__ __forceinline__ void vstep(const v4d (&A)[2][2], const v4d (&dA)[2][2], v4d (&R)[2][2], v4d (&dR)[2][2], const v4d& cI) {
+    const v4d z = {0.0, 0.0, 0.0, 0.0};
+    vcol(A, dA, R, dR, 0, cI, z);
+    vcol(A, dA, R, dR, 1, z, cI);
+}
+
+// y_I = sum_K M[K][I]^T v_K: M^T v for a D-layout M and a two-tile column block v
+__device__ __forceinline__ void vapplyT(const v4d (&M)[2][2], v4d (&v)[2]) {
+    const v4d z = {0.0, 0.0, 0.0, 0.0};
+    v4d y0 = z, y1 = z;
+#pragma unroll
+    for (int K = 0; K < 2; ++K) {
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            y0 = __builtin_amdgcn_mfma_f64_16x16x4f64(M[K][0][kk], v[K][kk], y0, 0, 0, 0);
+            y1 = __builtin_amdgcn_mfma_f64_16x16x4f64(M[K][1][kk], v[K][kk], y1, 0, 0, 0);
+        }
+    }
+    v[0] = y0;
+    v[1] = y1;
+}
+
+__global__ __launch_bounds__(64 * kWaves) void qc_sweep32_grad_kernel(const Grad32Params P, const double* __restrict__ Z, const double* __restrict__ theta,
+                                                                       const double* __restrict__ scale, const double* __restrict__ xs,
+                                                                       const double* __restrict__ ls, double* __restrict__ gs) {
+    __shared__ double scr_all[kWaves * kScr];
+    const int lane = threadIdx.x & 63;
+    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double* __restrict__ scr = scr_all + wq * kScr;
+    const long long item = (long long)blockIdx.x * kWaves + wq;
+    if (item >= P.items) return;
+    const long long s = item / P.n_chunks;
+    const int c = (int)(item - s * P.n_chunks);
+    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
+    const int g = lane >> 4, j = lane & 15;
+    const int m = P.m;
+    const bool ft = P.off_dt >= 0;
+    const v4d IdB = identity_B(g, j);
+    const v4d zero = {0.0, 0.0, 0.0, 0.0};
+
+    // ---- once per wave: the sample's base matrix, the state and the adjoint at the chunk's end --------------------------------------
+    v4d base[2][2];
+    base_matrix(P.img, m, P.p, theta, s, lane, base);
+    const int kl = lane < m ? lane : (m > 0 ? m - 1 : 0);
+    const double cl = (scale && m > 0) ? scale[s * m + kl] : 1.0;
+
+    v4d x[2], lam[2];
+    {
+        const int ns = P.n * P.nc;
+        const double* __restrict__ xe = xs + item * ns;
+        const double* __restrict__ le = ls + item * ns;
+#pragma unroll
+        for (int I = 0; I < 2; ++I)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * I + 4 * r + g;
+                const bool in = row < P.n && j < P.nc;
+                x[I][r] = in ? xe[row + P.n * j] : 0.0;
+                lam[I][r] = in ? le[row + P.n * j] : 0.0;
+            }
+    }
+
+    const double hfix = opaque_scalar(P.dt_fixed);
+    const double* __restrict__ z = Z + (long long)(t1 - 1) * P.zdim;
+    double av = m > 0 ? z[P.off_a + kl] : 0.0;
+    double h = ft ? z[P.off_dt] : hfix;
+#pragma unroll 1
+    for (int t = t1 - 1; t >= t0; --t) {
+        // the previous interval's controls and timestep are requested before this interval's products
+        const double* __restrict__ zn = Z + (long long)(t > t0 ? t - 1 : t) * P.zdim;
+        const double av_n = m > 0 ? zn[P.off_a + kl] : 0.0;
+        const double h_n = ft ? zn[P.off_dt] : hfix;
+        const double al = av * cl;
+        v4d Y[2][2], dY[2][2];
+        generator(P.img, m, al, base, lane, Y);
+        const int sq = squarings(Y, h);      // the rule of the forward kernel: one function
+        const double hs = h * ldexp(1.0, -sq);
+        // KT = lambda x^T of knot t+1 (D layout), from the transposed tiles of both; dY in A layout is KT with the block index swapped
+        {
+            const v4d in[4] = {x[0], x[1], lam[0], lam[1]};
+            v4d tr[4];
+            lds_transpose16_multi<4>(scr, in, tr, g, j);
+            v4d k00 = zero, k01 = zero, k10 = zero, k11 = zero;
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                k00 = __builtin_amdgcn_mfma_f64_16x16x4f64(tr[2][kk], tr[0][kk], k00, 0, 0, 0);
+                k01 = __builtin_amdgcn_mfma_f64_16x16x4f64(tr[2][kk], tr[1][kk], k01, 0, 0, 0);
+                k10 = __builtin_amdgcn_mfma_f64_16x16x4f64(tr[3][kk], tr[0][kk], k10, 0, 0, 0);
+                k11 = __builtin_amdgcn_mfma_f64_16x16x4f64(tr[3][kk], tr[1][kk], k11, 0, 0, 0);
+            }
+            dY[0][0] = k00; dY[1][0] = k01; dY[0][1] = k10; dY[1][1] = k11;      // dY(I, K) = KT[K][I]
+        }
+        // an opaque copy of the lane index: the lane compares below are made per interval instead of living in scalar registers across
+        // the loop (as in qc_sweep_grad_kernel at M = 8)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        double out = 0.0;
+        if (ft) {
+            // sum_IJ KT[I][J] . Ga[J][I] = sum_IK dY(I, K) . Ga(I, K)
+            double ph = 0.0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) ph = fma(dY[q >> 1][q & 1][r], Y[q >> 1][q & 1][r], ph);
+            const double dh = -vwave_sum(ph);
+            out = ln == m ? dh : out;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            Y[q >> 1][q & 1] = hs * Y[q >> 1][q & 1];
+            dY[q >> 1][q & 1] = hs * dY[q >> 1][q & 1];
+        }
+        v4d R[2][2] = {{kInvFact[kDeg] * IdB, zero}, {zero, kInvFact[kDeg] * IdB}};
+        v4d dR[2][2] = {{zero, zero}, {zero, zero}};
+#pragma unroll 1
+        for (int k = kDeg; k >= 1; --k) vstep(Y, dY, R, dR, kInvFact[k - 1] * IdB);
+        for (int q = 0; q < sq; ++q) {
+            transpose4(scr, R, Y, g, j);           // E, dE in A layout; Y, dY are free from here on
+            transpose4(scr, dR, dY, g, j);
+            vstep(Y, dY, R, dR, zero);
+        }
+        // ZT = E^T dE, into Y
+#pragma unroll
+        for (int J = 0; J < 2; ++J) {
+            v4d z0 = zero, z1 = zero;
+#pragma unroll
+            for (int K = 0; K < 2; ++K) {
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) {
+                    z0 = __builtin_amdgcn_mfma_f64_16x16x4f64(R[K][0][kk], dR[K][J][kk], z0, 0, 0, 0);
+                    z1 = __builtin_amdgcn_mfma_f64_16x16x4f64(R[K][1][kk], dR[K][J][kk], z1, 0, 0, 0);
+                }
+            }
+            Y[0][J] = z0;
+            Y[1][J] = z1;
+        }
+#pragma unroll 1
+        for (int u = 0; u < m; ++u) {
+            const double* __restrict__ Gu = P.img + (size_t)(1 + u) * 1024;
+            double pu = 0.0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const v4d t4 = load_image_tile(Gu + q * 256, lane);       // tile (J, I) = q against ZT[I][J]
+#pragma unroll
+                for (int r = 0; r < 4; ++r) pu = fma(Y[q & 1][q >> 1][r], t4[r], pu);
+            }
+            const double du = vwave_sum(pu);
+            out = ln == u ? du * cl : out;
+        }
+        if (ln < P.nd) gs[(s * P.n_int + t) * P.nd + lane] = out;
+        vapplyT(R, x);
+        vapplyT(R, lam);
+        av = av_n;
+        h = h_n;
+    }
+}
+
+// One workgroup per sample.  Up: x = Q_c ... Q_0 init with the loops of qc_sweep_finish_kernel (ld = 32), x stored at every chunk end;
+// F_s and lambda = dphi/dx at the final state.  Down: lambda <- Q_c^T lambda, stored at every chunk end.  (qc_sweep_seed_kernel of
+// qc_sweep_grad.hip with the leading dimension of the totals 32 instead of 16; that kernel is left as it is.)
+__global__ __launch_bounds__(kVSeedT) void qc_sweep32_seed_kernel(const Seed32Params F, const double* __restrict__ tot, const double* __restrict__ src,
+                                                                  const double* __restrict__ gr, const double* __restrict__ gi,
+                                                                  double* __restrict__ xs, double* __restrict__ ls, double* __restrict__ fids) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    __shared__ double red[2][kVSeedT / 64];
+    __shared__ double coef[3];
+    const int tid = threadIdx.x, n = F.n, ns = F.ns, ld = 32, l2 = 1024;
+    const long long s = blockIdx.x;
+    double* cur = sm;
+    double* nxt = sm + ns;
+    double* Q = sm + 2 * ns;
+    for (int idx = tid; idx < ns; idx += kVSeedT) cur[idx] = src[idx];
+    const double* __restrict__ Qs = tot + s * F.n_chunks * (long long)l2;
+    double* __restrict__ xo = xs + s * F.n_chunks * (long long)ns;
+    double* __restrict__ lo = ls + s * F.n_chunks * (long long)ns;
+    for (int c = 0; c < F.n_chunks; ++c) {
+        __syncthreads();
+        for (int idx = tid; idx < l2; idx += kVSeedT) Q[idx] = Qs[(long long)c * l2 + idx];
+        __syncthreads();
+        for (int idx = tid; idx < ns; idx += kVSeedT) {
+            const int r = idx % n, col = idx / n;
+            double acc = 0.0;
+            for (int q = 0; q < n; ++q) acc = fma(Q[r + ld * q], cur[q + n * col], acc);
+            nxt[idx] = acc;
+            xo[(long long)c * ns + idx] = acc;
+        }
+        double* tmp = cur; cur = nxt; nxt = tmp;
+    }
+    __syncthreads();
+    double ar = 0.0, ai = 0.0;
+    for (int i = tid; i < ns; i += kVSeedT) {
+        const double xi = cur[i];
+        ar = fma(gr[i], xi, ar);
+        ai = fma(gi[i], xi, ai);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        ar += __shfl_xor(ar, off, 64);
+        ai += __shfl_xor(ai, off, 64);
+    }
+    if ((tid & 63) == 0) { red[0][tid >> 6] = ar; red[1][tid >> 6] = ai; }
+    __syncthreads();
+    if (tid == 0) {
+        const double tr = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        const double ti = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        const double nn = (double)F.fid_n;
+        double Fv, fac;      // the mapping and the gradient factor of qc_fidelity_kernel (qc_fidelity.hip)
+        if (F.fid_kind == QC_FID_UNITARY) {
+            if (F.fid_form == QC_FID_FORM_ABS2) { Fv = (tr * tr + ti * ti) / (nn * nn); fac = 2.0 / (nn * nn); }
+            else { Fv = sqrt(tr * tr + ti * ti) / nn; fac = 1.0 / (nn * nn * Fv); }
+        } else { Fv = tr * tr + ti * ti; fac = 2.0; }
+        fids[s] = Fv;
+        coef[0] = tr; coef[1] = ti; coef[2] = fac;
+    }
+    __syncthreads();
+    const double tr = coef[0], ti = coef[1], fac = coef[2];
+    for (int idx = tid; idx < ns; idx += kVSeedT) {
+        const double v = (tr * gr[idx] + ti * gi[idx]) * fac;
+        cur[idx] = v;
+        lo[(long long)(F.n_chunks - 1) * ns + idx] = v;
+    }
+    for (int c = F.n_chunks - 1; c >= 1; --c) {
+        __syncthreads();
+        for (int idx = tid; idx < l2; idx += kVSeedT) Q[idx] = Qs[(long long)c * l2 + idx];
+        __syncthreads();
+        for (int idx = tid; idx < ns; idx += kVSeedT) {
+            const int r = idx % n, col = idx / n;
+            double acc = 0.0;
+            for (int q = 0; q < n; ++q) acc = fma(Q[q + ld * r], cur[q + n * col], acc);
+            nxt[idx] = acc;
+            lo[(long long)(c - 1) * ns + idx] = acc;
+        }
+        double* tmp = cur; cur = nxt; nxt = tmp;
+    }
+}
+
+}  // namespace
+
+void qc_sweep32_launch_seed(qc_sweep* h, int64_t S, int64_t n_chunks, const double* dinit, double* dfids, hipStream_t st) {
+    Seed32Params F;
+    F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
+    F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;
+    const size_t lds = ((size_t)2 * h->ns + 1024) * 8;       // at most 16 state columns: 16 KiB
+    hipLaunchKernelGGL(qc_sweep32_seed_kernel, dim3((unsigned)S), dim3(kVSeedT), lds, st, F, (const double*)h->dTot, dinit, (const double*)h->dgr,
+                       (const double*)h->dgi, h->dXs, h->dLs, dfids);
+}
+
+void qc_sweep32_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,
+                            double* gs, hipStream_t st) {
+    Grad32Params P;
+    P.n = h->n; P.nc = h->nc; P.m = h->d.m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
+    P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks; P.nd = P.m + (P.off_dt >= 0 ? 1 : 0);
+    P.items = S * n_chunks;
+    P.dt_fixed = h->d.dt_fixed;
+    P.img = h->dImg;
+    const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
+    hipLaunchKernelGGL(qc_sweep32_grad_kernel, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, (const double*)h->dXs,
+                       (const double*)h->dLs, gs);
+}

@@ -14,6 +14,8 @@
 //     problem (M_t needs x_t, which needs E) is gone: neither are the Horner / squaring intermediates kept, nor is the R chain computed twice;
 //   * <lambda, G x> = -sum (lambda x^T)_ab G_ba, so the timestep derivative is an inner product of tiles already in registers.
 // Everything else returns QC_ERR_UNSUPPORTED (Lindblad generators need stored forward states).
+// Wide descriptors (wide = QC_SWEEP_WIDE) extend the scope to the "mfma32-sweep" form, 2N <= 32: this file routes such handles to the
+// seed and walk kernels of qc_sweep32_grad.hip and shares its reductions (launch 4) with them; no parameter gradients there.
 //
 // Launches of one call:
 //   1. the forward chunk totals: qc_sweep_mfma16_kernel of qc_sweep.hip, unchanged, same chunk rule;
@@ -466,7 +468,8 @@ int gfail(qc_side* h, int code, const std::string& msg) { return qc_sweep_fail(h
 bool qc_sweep_grad_scope(const qc_sweep_desc* d, std::string* why) {
     const int n = 2 * d->N;
     if (!qc_sweep_desc_is_mfma(d)) {
-        *why = n > 16 ? "the handle takes the rollout-per-sample form (2N = " + std::to_string(n) + " > 16)"
+        const int top = d->wide == QC_SWEEP_WIDE ? 32 : 16;      // wide descriptors: "mfma32-sweep" up to 2N = 32 (qc_sweep32_grad.hip)
+        *why = n > top ? "the handle takes the rollout-per-sample form (2N = " + std::to_string(n) + " > " + std::to_string(top) + ")"
                       : "the handle takes the rollout-per-sample form (" + std::to_string(d->m) + " drives > 8)";
         return false;
     }
@@ -545,13 +548,18 @@ static int qc_sweep_grad_launch(qc_sweep* h, const char* who, const double* dZ, 
         gsamp = h->dGsamp;
     }
     if (want_par) QC_SIDE_HIP(h, slot, h->grow(&h->dPart, &h->capPart, (size_t)S * n_chunks * (p + m)));
-    SeedParams F;
-    F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
-    F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;
-    const size_t lds = ((size_t)2 * h->ns + 256) * 8;
-    hipLaunchKernelGGL(qc_sweep_seed_kernel, dim3((unsigned)S), dim3(kSeedT), lds, st, F, (const double*)h->dTot, dinit, (const double*)h->dgr,
-                       (const double*)h->dgi, h->dXs, h->dLs, dfids);
-    if (want_grad || want_par) {
+    if (h->mfma32) {      // the 2 x 2-tile form: its own seed and walk (qc_sweep32_grad.hip), then the reductions below
+        qc_sweep32_launch_seed(h, S, n_chunks, dinit, dfids, st);
+        if (want_grad) qc_sweep32_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, gsamp, st);
+    } else {
+        SeedParams F;
+        F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
+        F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;
+        const size_t lds = ((size_t)2 * h->ns + 256) * 8;
+        hipLaunchKernelGGL(qc_sweep_seed_kernel, dim3((unsigned)S), dim3(kSeedT), lds, st, F, (const double*)h->dTot, dinit, (const double*)h->dgr,
+                           (const double*)h->dgi, h->dXs, h->dLs, dfids);
+    }
+    if (!h->mfma32 && (want_grad || want_par)) {
         GradParams P;
         P.n = h->n; P.nc = h->nc; P.m = m; P.p = p; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
         P.n_int = (int)n_int; P.chunk = (int)chunk; P.n_chunks = (int)n_chunks; P.nd = nd;
@@ -601,6 +609,7 @@ extern "C" int qc_sweep_grad_dev(qc_sweep* h, const double* dZ, const double* di
 extern "C" int qc_sweep_grad_params_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
                                         const double* dweights, double* dfids, double* dJ, double* dgrad, double* dgrad_samples,
                                         double* dgrad_theta, double* dgrad_scale, void* stream) {
+    if (h && h->mfma32) return gfail(h, QC_ERR_UNSUPPORTED, "qc_sweep gradients: parameter gradients are not served in the mfma32-sweep form");
     return qc_sweep_grad_launch(h, "qc_sweep_grad_params_dev", dZ, dinit, S, dtheta, dscale, dweights, dfids, dJ, dgrad, dgrad_samples, dgrad_theta,
                                 dgrad_scale, stream);
 }
@@ -661,5 +670,6 @@ extern "C" int qc_sweep_grad(qc_sweep* h, const double* Z, const double* init, i
 extern "C" int qc_sweep_grad_params(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
                                     const double* weights, double* fids, double* J, double* grad, double* grad_samples, double* grad_theta,
                                     double* grad_scale) {
+    if (h && h->mfma32) return gfail(h, QC_ERR_UNSUPPORTED, "qc_sweep gradients: parameter gradients are not served in the mfma32-sweep form");
     return qc_sweep_grad_host(h, "qc_sweep_grad_params", Z, init, S, theta, scale, weights, fids, J, grad, grad_samples, grad_theta, grad_scale);
 }

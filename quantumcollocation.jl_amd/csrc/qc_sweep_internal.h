@@ -9,6 +9,7 @@
 struct qc_sweep : qc_side {
     qc_sweep_desc d;             // caller-owned arrays are not retained (pointers nulled)
     bool mfma = false;
+    bool mfma32 = false;         // the 2 x 2-tile form of a wide descriptor ("mfma32-sweep", qc_sweep32.hip); mfma is set as well
     bool grad_ok = false;        // the gradient's scope (qc_sweep_grad.hip), decided at create from the caller's matrices
     std::string grad_why;        // when not: the reason
     int n = 0, nc = 0, ns = 0, fid_n = 0;
@@ -45,8 +46,22 @@ int qc_sweep_fail(qc_side* h, int code, const std::string& msg);
 std::string* qc_sweep_err_slot();
 int qc_sweep_validate_desc(const qc_sweep_desc* d);
 bool qc_sweep_desc_is_mfma(const qc_sweep_desc* d);
+// 0: "rollout-per-sample", 1: "mfma16-sweep", 2: "mfma32-sweep" (wide descriptors with 16 < 2N <= 32)
+int qc_sweep_desc_form(const qc_sweep_desc* d);
+// the chunk rule of the MFMA forms
+void qc_sweep_chunks(int64_t S, int64_t T, int64_t* chunk, int64_t* n_chunks);
 // "mfma16-sweep" handles: grows h->dTot and launches qc_sweep_mfma16_kernel on `st` (S x n_chunks tiles of 256 doubles)
 int qc_sweep_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, hipStream_t st, int64_t* chunk,
                            int64_t* n_chunks);
+// "mfma32-sweep" handles (qc_sweep32.hip): the A-layout image of one n x n matrix (1024 doubles), and the launch of qc_sweep_mfma32_kernel
+// (S x n_chunks column-major 32 x 32 totals of 1024 doubles in h->dTot)
+void qc_sweep32_image(const double* G, int n, double* img);
+int qc_sweep32_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, hipStream_t st, int64_t* chunk,
+                             int64_t* n_chunks);
+// "mfma32-sweep" gradients (qc_sweep32_grad.hip): qc_sweep32_seed_kernel (x and lambda at every chunk end, fidelities) and the backward walk
+// qc_sweep32_grad_kernel (gs: S x (T-1) x nd); scratch is the caller's
+void qc_sweep32_launch_seed(qc_sweep* h, int64_t S, int64_t n_chunks, const double* dinit, double* dfids, hipStream_t st);
+void qc_sweep32_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,
+                            double* gs, hipStream_t st);
 // device-free: is this (valid) descriptor inside the gradient's scope?  `why` receives the reason when it is not.
 bool qc_sweep_grad_scope(const qc_sweep_desc* d, std::string* why);

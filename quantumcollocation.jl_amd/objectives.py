@@ -743,11 +743,12 @@ class SweepInfidelityObjective:
     and of the timestep, `traj.global_dim`.
 
     state_name  a unitary component (2 N^2 entries: unitary fidelity, `subspace`, `form`) or a ket component (2 N entries)
-    theta       S x len(perturbations);  scale  S x n_drives or None;  weights  S values or None (1/S each)"""
+    theta       S x len(perturbations);  scale  S x n_drives or None;  weights  S values or None (1/S each)
+    wide        as `RolloutSweep`: True serves systems of 16 < 2N <= 32 (9 .. 16 levels) in the "mfma32-sweep" form"""
     _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
 
     def __init__(self, traj: NamedTrajectory, system, perturbations, theta, scale=None, weights=None, state_name: str = "Ũ⃗",
-                 control_name: str = "a", subspace=None, form: str = "abs", device: int = 0):
+                 control_name: str = "a", subspace=None, form: str = "abs", device: int = 0, wide: bool = False):
         from .rollouts import RolloutSweep
         self._sweep = None
         if state_name not in traj.components:
@@ -787,7 +788,7 @@ class SweepInfidelityObjective:
         sw = RolloutSweep(system, perturbations, traj.T, cols=cols, goal=np.asarray(traj.goal[state_name], dtype=np.float64), fid_kind=kind,
                           subspace=subspace, fid_form=_lib.QC_FID_FORM_ABS2 if form == "abs2" else _lib.QC_FID_FORM_ABS, zdim=traj.dim,
                           off_a=traj.offset(control_name), off_dt=traj.offset(traj.timestep) if free else -1,
-                          dt_fixed=None if free else float(traj.timestep), global_dim=traj.global_dim, device=device)
+                          dt_fixed=None if free else float(traj.timestep), global_dim=traj.global_dim, device=device, wide=wide)
         self._sweep = sw
         if not sw.grad_supported:
             why = sw.grad_unsupported_reason

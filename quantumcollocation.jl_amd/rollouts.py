@@ -166,11 +166,14 @@ class RolloutSweep:
     goal, fid_kind fidelity of every final state: "unitary" (goal = iso-vec of U_goal; `subspace`, `fid_form`), "ket" or
                    "density" (goal = [Re psi; Im psi]); None: final states only
     The trajectory vector is knot-major with the controls at `off_a` and the timestep at `off_dt` of every knot of `zdim`
-    entries (default: the minimal layout [a, dt], built by `pack`; dt_fixed: no timestep in the knot)."""
+    entries (default: the minimal layout [a, dt], built by `pack`; dt_fixed: no timestep in the knot).
+    wide           True: systems of 16 < 2N <= 32 with up to 8 drives run on the matrix cores too ("mfma32-sweep", with gradients over the
+                   controls and timesteps; no parameter gradients there yet) instead of one rollout per sample.  Nothing changes at
+                   2N <= 16."""
 
     def __init__(self, system, perturbations, T: int, cols: Optional[int] = None, goal=None, fid_kind=None, subspace=None,
                  fid_form: int = _lib.QC_FID_FORM_ABS, zdim: Optional[int] = None, off_a: int = 0, off_dt: Optional[int] = None,
-                 dt_fixed: Optional[float] = None, global_dim: int = 0, device: int = 0):
+                 dt_fixed: Optional[float] = None, global_dim: int = 0, device: int = 0, wide: bool = False):
         self._h = None
         m = system.n_drives
         N = system.state_levels
@@ -205,6 +208,8 @@ class RolloutSweep:
         d.subspace = self._sub.ctypes.data_as(C.POINTER(C.c_int32)) if self._sub is not None else None
         d.n_sub = 0 if self._sub is None else int(self._sub.size)
         d.device = device
+        d.wide = _lib.QC_SWEEP_WIDE if wide else 0
+        self.wide = bool(wide)
         self._desc = d
         h = C.c_void_p()
         rc = _lib.lib.qc_sweep_create(C.byref(d), C.byref(h))
@@ -214,7 +219,7 @@ class RolloutSweep:
 
     @property
     def kernel_name(self) -> str:
-        """"mfma16-sweep" (2N <= 16, up to 8 drives) or "rollout-per-sample"."""
+        """"mfma16-sweep" (2N <= 16, up to 8 drives), "mfma32-sweep" (`wide`, 16 < 2N <= 32, up to 8 drives) or "rollout-per-sample"."""
         return _lib.lib.qc_sweep_kernel_name(self._h).decode()
 
     def launch(self, S: int):
@@ -414,9 +419,9 @@ class RolloutSweep:
 
 
 def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None, cols: Optional[int] = None, goal=None, fid_kind=None,
-                  subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS):
+                  subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS, wide: bool = False):
     """(finals, fids) of S rollouts under the perturbed systems: finals is (2N cols) x S, fids S values (None without `fid_kind`).
-    theta is S x len(perturbations) (S x 0 without perturbations), scale S x n_drives or None (all ones)."""
+    theta is S x len(perturbations) (S x 0 without perturbations), scale S x n_drives or None (all ones); `wide` as `RolloutSweep`."""
     controls = np.asarray(controls, dtype=np.float64)
     if controls.ndim != 2 or controls.shape[0] != system.n_drives:
         raise ValueError("controls must be n_drives x T")
@@ -425,7 +430,7 @@ def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None,
     n = 2 * system.state_levels
     if cols is None:
         cols = init.size // n
-    sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device)
+    sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device, wide=wide)
     try:
         return sw.eval(sw.pack(controls, dts), init, theta, scale)
     finally:
