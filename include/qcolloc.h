@@ -630,8 +630,9 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * Results do not depend on scheduling: repeated calls return the same bits.  Non-finite inputs are evaluated, not rejected.
  * Gradients with respect to the controls and timesteps (qc_sweep_grad*) and to the samples' own parameters theta and `scale`
  * (qc_sweep_grad_params*), both below, are served for closed systems in the MFMA forms (parameter gradients: "mfma16-sweep" only).
- * Out of scope: per-knot outputs, open-system gradients (they need stored forward states), second derivatives, derivatives of the
- * final states, the free-phase fidelity, several devices. */
+ * Derivatives of the final states themselves, contracted with cotangents the caller chooses (qc_sweep_vjp*, below), carry any function
+ * of the final states: leakage, the free-phase fidelity, several kets at once, a loss written elsewhere.
+ * Out of scope: per-knot outputs, open-system gradients (they need stored forward states), second derivatives, several devices. */
 #define QC_MAX_PERT 8
 #define QC_SWEEP_FID_NONE (-1)   /* qc_sweep_desc.fid_kind: final states only */
 #define QC_SWEEP_WIDE 1          /* qc_sweep_desc.wide */
@@ -725,6 +726,34 @@ int qc_sweep_grad_params_dev(qc_sweep* h, const double* dZ, const double* dinit,
 int qc_sweep_grad_params(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
                          const double* weights, double* fids, double* J, double* grad, double* grad_samples,
                          double* grad_theta, double* grad_scale);
+
+/* ---- sweep pullbacks: gradients of any function of the final states ------------------------------------------------------ */
+/* The pullback of (Z, init, theta, c) -> x_final[s]: the caller hands in one cotangent C_s per sample (the derivative of their loss
+ * with respect to that sample's final state) and receives the derivatives of phi_s = <C_s, x_final[s]>.  It is the adjoint walk of
+ * qc_sweep_grad with lambda_{T-1} = C_s in place of the fidelity's own seed, so a call costs what a gradient call costs; the final
+ * state being linear in the initial one, dphi_s/dinit = lambda_0 comes from one more transposed product of the seed. */
+/* device-free: may the pullback serve this descriptor?  Scope = the gradient's scope WITHOUT its two fidelity conditions: an MFMA form
+ * ("mfma16-sweep", or "mfma32-sweep" with wide = QC_SWEEP_WIDE), antisymmetric drift / drives / perturbations (the same 64-eps test),
+ * at most 16 state columns.  fid_kind may be anything, QC_SWEEP_FID_NONE and QC_FID_DENSITY included.  When 0,
+ * qc_sweep_last_error(NULL) says why, prefixed "qc_sweep pullback: ".  An invalid descriptor returns its own error. */
+int qc_sweep_desc_vjp_supported(const qc_sweep_desc* d, int32_t* supported);
+/* phi_s = <cot[s], x_final[s]>.  cot: S x (2N cols), the layout of `finals`.  Outputs, each optional, at least one non-NULL:
+ *   finals        S x (2N cols)      the bits of qc_sweep_eval
+ *   grad          Z_len              sum_s dphi_s/dZ (plain sum, ascending s), +0.0 outside controls / timesteps of knots 0..T-2
+ *   grad_samples  S x (T-1) x nd     dphi_s/d(a_t, dt_t), the layout of qc_sweep_grad
+ *   grad_init     S x (2N cols)      dphi_s/dinit = (E_{T-2} ... E_0)^T cot[s]
+ *   grad_theta    S x n_pert, grad_scale  S x m   ("mfma16-sweep" only; on an "mfma32-sweep" handle QC_ERR_UNSUPPORTED,
+ *                                    "parameter cotangents are not served in the mfma32-sweep form")
+ * cot must not overlap any output.  Scratch and the one-in-flight rule as qc_sweep_grad_dev.  Repeated calls return the same bits, and
+ * no output's bits depend on which other outputs were requested.  Non-finite cotangents are evaluated, not rejected: they reach
+ * their own sample's outputs and `grad`, nothing else. */
+int qc_sweep_vjp_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
+                     const double* dcot, double* dfinals, double* dgrad, double* dgrad_samples, double* dgrad_init,
+                     double* dgrad_theta, double* dgrad_scale, void* stream);
+/* the same on host buffers (synchronous) */
+int qc_sweep_vjp(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
+                 const double* cot, double* finals, double* grad, double* grad_samples, double* grad_init,
+                 double* grad_theta, double* grad_scale);
 
 /* Diagnostic only: when the environment variable QC_STAMPS=1 is set at qc_create, the MFMA kernel
  * records 16 s_memrealtime (100 MHz) checkpoints per interval; this copies them out (synchronises the

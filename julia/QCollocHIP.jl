@@ -842,6 +842,59 @@ function rollout_sweep_parameter_gradient(init::AbstractVector{Float64}, control
 end
 
 """
+    rollout_sweep_pullback(init, controls, Δt, G_drift, G_drives, G_pert, θ, C̄; scale=nothing, cols, params=false, device=0,
+                           wide=false)  ->  (finals, ∇a, ∇Δt, ∇init[, ∇θ, ∇c])
+
+The pullback of `rollout_sweep` (`qc_sweep_vjp`): `C̄` is (2N·cols)×S, column s the cotangent of sample s's final state (the derivative
+of the caller's loss with respect to it, e.g. what `Zygote.pullback` hands to an `rrule`), and with φ_s = ⟨C̄[:, s], finals[:, s]⟩ the
+results are the final states themselves, Σ_s ∂φ_s/∂a (m×T) and Σ_s ∂φ_s/∂Δt (T; the last knot's columns are zero), `∇init`
+(2N·cols)×S with column s = ∂φ_s/∂init (sum the columns for a shared initial state) and, with `params`, `∇θ` (S×p) and `∇c` (S×m).
+Served for closed systems (antisymmetric generators) with 2N ≤ 16 (`wide = true`: 2N ≤ 32, without `params`), m ≤ 8 and at most 16
+state columns; no fidelity is involved.  Arguments as `rollout_sweep`.  UNTESTED here, like the rest of this file.
+"""
+function rollout_sweep_pullback(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift, G_drives,
+                                G_pert, θ::AbstractMatrix{Float64}, C̄::AbstractMatrix{Float64}; scale=nothing, cols::Int, params::Bool=false,
+                                device::Int=0, wide::Bool=false)
+    n = size(G_drift, 1); N = n ÷ 2
+    m, T = size(controls); p = length(G_pert); S = size(θ, 1)
+    size(C̄) == (n * cols, S) || error("rollout_sweep_pullback: C̄ must be $(n * cols)×$S")
+    G0 = Float64.(vec(G_drift))
+    Gd = m == 0 ? Float64[] : reduce(vcat, [Float64.(vec(G)) for G in G_drives])
+    Gp = p == 0 ? Float64[] : reduce(vcat, [Float64.(vec(G)) for G in G_pert])
+    Z⃗ = vec(vcat(controls, reshape(Δt, 1, T)))                      # knot layout [a; Δt]
+    θt = Matrix{Float64}(transpose(θ))                               # sample-major
+    ct = isnothing(scale) ? Float64[] : vec(Matrix{Float64}(transpose(scale)))
+    cot = Matrix{Float64}(C̄)                                         # column s holds sample s: sample-major as it stands
+    finals = Matrix{Float64}(undef, n * cols, S)
+    grad = Vector{Float64}(undef, (m + 1) * T)
+    ginit = Matrix{Float64}(undef, n * cols, S)
+    gθ = Matrix{Float64}(undef, p, S)                                # sample-major: column s holds sample s
+    gc = Matrix{Float64}(undef, m, S)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve G0 Gd Gp begin
+        desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, -1,
+                               pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
+                               0, 0, C_NULL, C_NULL, device, wide ? 1 : 0, (0, 0)))
+        ok = Ref{Int32}(0)
+        rc = ccall((:qc_sweep_desc_vjp_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
+        (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
+        rc = ccall((:qc_sweep_create, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Ptr{Cvoid}}), desc, h)
+        rc == 0 || error("qc_sweep_create: " * unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
+    end
+    rc = GC.@preserve Z⃗ init θt ct cot finals grad ginit gθ gc ccall((:qc_sweep_vjp, LIB[]), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        h[], Z⃗, init, S, p == 0 ? C_NULL : pointer(θt), isempty(ct) ? C_NULL : pointer(ct), cot, finals, grad, C_NULL, ginit,
+        (params && p > 0) ? pointer(gθ) : C_NULL, (params && m > 0) ? pointer(gc) : C_NULL)
+    msg = rc == 0 ? "" : unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), h[]))
+    ccall((:qc_sweep_destroy, LIB[]), Cvoid, (Ptr{Cvoid},), h[])
+    rc == 0 || error("qc_sweep_vjp: " * msg)
+    G = reshape(grad, m + 1, T)
+    return params ? (finals, G[1:m, :], G[m + 1, :], ginit, Matrix{Float64}(transpose(gθ)), Matrix{Float64}(transpose(gc))) :
+                    (finals, G[1:m, :], G[m + 1, :], ginit)
+end
+
+"""
     iso_vec_unitary_fidelity(Ũ⃗, Ũ⃗_goal; subspace=nothing, device=0, squared=false)          (unitary_minimum_time_problem.jl:77)
     iso_vec_unitary_free_phase_fidelity(Ũ⃗, Ũ⃗_goal, phases, phase_operators; subspace=nothing)  (unitary_minimum_time_problem.jl:86-90)
 

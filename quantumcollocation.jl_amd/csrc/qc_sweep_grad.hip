@@ -52,6 +52,9 @@
 // <= 1.15 (1/8)^8 / 8! ||dY|| = 1.7e-12 ||dY||; over the 2^sq factors of the squarings the directions add up to h ||c_k G_k||, so the
 // relative error of a drive derivative is 1.7e-12, three orders inside the tests' 1e-9.  The degree stays 8.
 //
+// Pullbacks (qc_sweep_vjp.hip): the same walks behind a seed that takes lambda_{T-1} from the caller; qc_sweep16_launch_walk below is the
+// launch of this file's walk for both, qc_sweep_closed_scope what the two scopes share.
+//
 // gfx950 cross-compile: see the table in DESIGN.md ("Sweep gradients"); no private segment, no spills in any instantiation.
 #include <math.h>
 #include <string.h>
@@ -465,7 +468,8 @@ int gfail(qc_side* h, int code, const std::string& msg) { return qc_sweep_fail(h
 // The tolerance of the antisymmetry test: max |G + G^T| <= 64 eps max |G| per matrix.  iso generators of exactly Hermitian operators are
 // exactly antisymmetric; 64 eps admits operators that were symmetrised or scaled in floating point, and stays ten orders below any
 // dissipator worth the name.
-bool qc_sweep_grad_scope(const qc_sweep_desc* d, std::string* why) {
+// What the gradient and the pullback (qc_sweep_vjp.hip) ask of a descriptor alike: an MFMA form, antisymmetric matrices, at most 16 state columns.
+bool qc_sweep_closed_scope(const qc_sweep_desc* d, std::string* why) {
     const int n = 2 * d->N;
     if (!qc_sweep_desc_is_mfma(d)) {
         const int top = d->wide == QC_SWEEP_WIDE ? 32 : 16;      // wide descriptors: "mfma32-sweep" up to 2N = 32 (qc_sweep32_grad.hip)
@@ -493,6 +497,11 @@ bool qc_sweep_grad_scope(const qc_sweep_desc* d, std::string* why) {
         }
     const int nc = d->state_cols == 0 ? d->N : d->state_cols;
     if (nc > 16) { *why = "states of more than 16 columns are not served (state_cols = " + std::to_string(nc) + ")"; return false; }
+    return true;
+}
+
+bool qc_sweep_grad_scope(const qc_sweep_desc* d, std::string* why) {
+    if (!qc_sweep_closed_scope(d, why)) return false;
     if (d->fid_kind == QC_SWEEP_FID_NONE) { *why = "the handle has no fidelity (QC_SWEEP_FID_NONE)"; return false; }
     if (d->fid_kind == QC_FID_DENSITY) { *why = "the density-operator fidelity is not served"; return false; }
     return true;
@@ -507,6 +516,41 @@ extern "C" int qc_sweep_desc_grad_supported(const qc_sweep_desc* d, int32_t* sup
     *supported = ok ? 1 : 0;
     if (!ok) (void)gfail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep gradients: " + why);
     return QC_OK;
+}
+
+// The backward walk of "mfma16-sweep" handles, for the gradient above and the pullback of qc_sweep_vjp.hip: qc_sweep_grad_kernel<M, false>, or
+// with `par` the flavour <M, true> (gs may then be NULL) followed by qc_sweep_par_reduce_kernel out of h->dPart.  x and lambda at the chunk
+// ends are read from h->dXs / h->dLs; scratch is the caller's.
+void qc_sweep16_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,
+                            double* gs, bool want_par, double* dgrad_theta, double* dgrad_scale, hipStream_t st) {
+    const int m = h->d.m, p = h->d.n_pert;
+    const int nd = m + (h->d.off_dt >= 0 ? 1 : 0);
+    const int64_t n_int = h->d.T - 1;
+    GradParams P;
+    P.n = h->n; P.nc = h->nc; P.m = m; P.p = p; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
+    P.n_int = (int)n_int; P.chunk = (int)chunk; P.n_chunks = (int)n_chunks; P.nd = nd;
+    P.items = S * n_chunks;
+    P.dt_fixed = h->d.dt_fixed;
+    P.img = h->dImg;
+    const unsigned grid = (unsigned)((P.items + kGWaves - 1) / kGWaves);
+#define QC_GRAD_LAUNCH(M_)                                                                                                                      \
+    do {                                                                                                                                        \
+        if (want_par)                                                                                                                           \
+            hipLaunchKernelGGL((qc_sweep_grad_kernel<M_, true>), dim3(grid), dim3(64 * kGWaves), 0, st, P, dZ, dtheta, dscale,                    \
+                               (const double*)h->dXs, (const double*)h->dLs, gs, h->dPart);                                                     \
+        else                                                                                                                                    \
+            hipLaunchKernelGGL((qc_sweep_grad_kernel<M_, false>), dim3(grid), dim3(64 * kGWaves), 0, st, P, dZ, dtheta, dscale,                   \
+                               (const double*)h->dXs, (const double*)h->dLs, gs, (double*)nullptr);                                             \
+    } while (0)
+    if (m <= 1) QC_GRAD_LAUNCH(1);
+    else if (m <= 2) QC_GRAD_LAUNCH(2);
+    else if (m <= 4) QC_GRAD_LAUNCH(4);
+    else if (m <= 6) QC_GRAD_LAUNCH(6);
+    else QC_GRAD_LAUNCH(8);
+#undef QC_GRAD_LAUNCH
+    if (want_par)
+        hipLaunchKernelGGL(qc_sweep_par_reduce_kernel, dim3((unsigned)((S * (p + m) + kRedT - 1) / kRedT)), dim3(kRedT), 0, st, (long long)S,
+                           (int)n_chunks, p, m, (const double*)h->dPart, dgrad_theta, dgrad_scale);
 }
 
 // Both device entry points.  Without dgrad_theta / dgrad_scale this is qc_sweep_grad_dev as it always was: the same launches of the same
@@ -559,34 +603,8 @@ static int qc_sweep_grad_launch(qc_sweep* h, const char* who, const double* dZ, 
         hipLaunchKernelGGL(qc_sweep_seed_kernel, dim3((unsigned)S), dim3(kSeedT), lds, st, F, (const double*)h->dTot, dinit, (const double*)h->dgr,
                            (const double*)h->dgi, h->dXs, h->dLs, dfids);
     }
-    if (!h->mfma32 && (want_grad || want_par)) {
-        GradParams P;
-        P.n = h->n; P.nc = h->nc; P.m = m; P.p = p; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
-        P.n_int = (int)n_int; P.chunk = (int)chunk; P.n_chunks = (int)n_chunks; P.nd = nd;
-        P.items = S * n_chunks;
-        P.dt_fixed = h->d.dt_fixed;
-        P.img = h->dImg;
-        const unsigned grid = (unsigned)((P.items + kGWaves - 1) / kGWaves);
-        double* gs = want_grad ? gsamp : nullptr;
-#define QC_GRAD_LAUNCH(M_)                                                                                                                      \
-    do {                                                                                                                                        \
-        if (want_par)                                                                                                                           \
-            hipLaunchKernelGGL((qc_sweep_grad_kernel<M_, true>), dim3(grid), dim3(64 * kGWaves), 0, st, P, dZ, dtheta, dscale,                    \
-                               (const double*)h->dXs, (const double*)h->dLs, gs, h->dPart);                                                     \
-        else                                                                                                                                    \
-            hipLaunchKernelGGL((qc_sweep_grad_kernel<M_, false>), dim3(grid), dim3(64 * kGWaves), 0, st, P, dZ, dtheta, dscale,                   \
-                               (const double*)h->dXs, (const double*)h->dLs, gs, (double*)nullptr);                                             \
-    } while (0)
-        if (m <= 1) QC_GRAD_LAUNCH(1);
-        else if (m <= 2) QC_GRAD_LAUNCH(2);
-        else if (m <= 4) QC_GRAD_LAUNCH(4);
-        else if (m <= 6) QC_GRAD_LAUNCH(6);
-        else QC_GRAD_LAUNCH(8);
-#undef QC_GRAD_LAUNCH
-        if (want_par)
-            hipLaunchKernelGGL(qc_sweep_par_reduce_kernel, dim3((unsigned)((S * (p + m) + kRedT - 1) / kRedT)), dim3(kRedT), 0, st, (long long)S,
-                               (int)n_chunks, p, m, (const double*)h->dPart, dgrad_theta, dgrad_scale);
-    }
+    if (!h->mfma32 && (want_grad || want_par))
+        qc_sweep16_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);
     if (dgrad) {
         ReduceParams R;
         R.zdim = h->d.zdim; R.off_a = h->d.off_a; R.off_dt = h->d.off_dt; R.m = m; R.nd = nd;

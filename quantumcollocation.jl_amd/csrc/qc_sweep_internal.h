@@ -1,4 +1,4 @@
-// What qc_sweep.hip (forward sweep) and qc_sweep_grad.hip (its adjoint) share: the handle, the descriptor checks and the launch of the
+// What qc_sweep.hip (forward sweep), qc_sweep_grad.hip (its adjoint) and qc_sweep_vjp.hip (the pullback of the final states) share: the handle, the descriptor checks and the launch of the
 // forward chunk totals (with it the chunk rule).  Not part of the ABI.
 #pragma once
 
@@ -12,6 +12,8 @@ struct qc_sweep : qc_side {
     bool mfma32 = false;         // the 2 x 2-tile form of a wide descriptor ("mfma32-sweep", qc_sweep32.hip); mfma is set as well
     bool grad_ok = false;        // the gradient's scope (qc_sweep_grad.hip), decided at create from the caller's matrices
     std::string grad_why;        // when not: the reason
+    bool vjp_ok = false;         // the pullback's scope (qc_sweep_vjp.hip): the gradient's without its fidelity conditions
+    std::string vjp_why;
     int n = 0, nc = 0, ns = 0, fid_n = 0;
     int64_t Zlen = 0;
     double* dG = nullptr;        // (1 + m + p) matrices, column-major (per-sample form)
@@ -39,6 +41,9 @@ struct qc_sweep : qc_side {
     double* dPart = nullptr; size_t capPart = 0;
     double* sGth = nullptr;  size_t capGth = 0;
     double* sGsc = nullptr;  size_t capGsc = 0;
+    // pullback (qc_sweep_vjp.hip): staging of the cotangents and of grad_init in its host-buffer entry point (finals: sFinals above)
+    double* sCot = nullptr;   size_t capCot = 0;
+    double* sGinit = nullptr; size_t capGinit = 0;
 };
 
 // records the message in the handle (when there is one) and in the slot qc_sweep_last_error(NULL) returns
@@ -63,5 +68,12 @@ int qc_sweep32_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const dou
 void qc_sweep32_launch_seed(qc_sweep* h, int64_t S, int64_t n_chunks, const double* dinit, double* dfids, hipStream_t st);
 void qc_sweep32_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,
                             double* gs, hipStream_t st);
+// "mfma16-sweep" handles (qc_sweep_grad.hip): the backward walk qc_sweep_grad_kernel<M, false> (gs: S x (T-1) x nd), or with `par` the
+// parameter flavour <M, true> (gs may be NULL) and qc_sweep_par_reduce_kernel out of h->dPart; scratch is the caller's
+void qc_sweep16_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,
+                            double* gs, bool par, double* dgrad_theta, double* dgrad_scale, hipStream_t st);
 // device-free: is this (valid) descriptor inside the gradient's scope?  `why` receives the reason when it is not.
 bool qc_sweep_grad_scope(const qc_sweep_desc* d, std::string* why);
+// what the gradient and the pullback ask alike (an MFMA form, antisymmetric matrices, at most 16 state columns), and the pullback's scope
+bool qc_sweep_closed_scope(const qc_sweep_desc* d, std::string* why);
+bool qc_sweep_vjp_scope(const qc_sweep_desc* d, std::string* why);

@@ -1,0 +1,268 @@
+// Sweep pullbacks: the adjoint of the map (Z, init, theta, c) -> x_final[s] of the rollout sweep, for cotangents the CALLER chooses.
+// With phi_s = <C_s, x_final[s]> and lambda_{T-1} = C_s in place of the fidelity's dphi/dx, every formula of qc_sweep_grad.hip (read
+// its header first) holds unchanged:
+//     dphi_s/da_{t,k} = c_k h <L(hG^T; lambda_{t+1} x_t^T), G_k>,   dphi_s/dh_t = <lambda_{t+1}, G x_{t+1}>,   lambda_t = E_t^T lambda_{t+1},
+// and, the final state being linear in the initial one, dphi_s/dinit = lambda_0.  The backward walks (qc_sweep_grad_kernel<M, PAR>,
+// qc_sweep32_grad_kernel) read lambda from a buffer and do not know where it came from: they are launched as they are, through
+// qc_sweep16_launch_walk / qc_sweep32_launch_walk.  What is new here is the seed and the plain sum.
+//
+// Launches of one call:
+//   1. the forward chunk totals (qc_sweep_launch_totals: the kernel and the chunk rule of qc_sweep_eval);
+//   2. qc_sweep_cot_seed_kernel ("mfma16-sweep": totals 16 x 16, ld = 16) or qc_sweep32_cot_seed_kernel ("mfma32-sweep": 32 x 32,
+//      ld = 32), one workgroup per sample.  Up: the loops of qc_sweep_finish_kernel (x at every chunk end into dXs; the last x into
+//      `finals` when asked for: the bits of qc_sweep_eval).  Down: lambda at the last chunk end = C_s as read, no arithmetic; then
+//      lambda <- Q_c^T lambda for c = n_chunks-1 .. 1, stored at every chunk end into dLs.  With `grad_init` one more step than the
+//      fidelity seeds take: lambda_0 = Q_0^T lambda_{end of chunk 0}.  (n_chunks = 1: that step is the only transposed product.)
+//   3. the walk, when a derivative over the intervals or the parameters is asked for: flavour <M, false> without grad_theta /
+//      grad_scale, <M, true> and qc_sweep_par_reduce_kernel with either (as qc_sweep_grad_launch chooses); the wide walk has one flavour.
+//      With m = 0 and a fixed timestep there is nothing per interval: only <1, true> runs, and only for grad_theta.
+//   4. qc_sweep_vjp_reduce_kernel: grad = sum_s dphi_s/dZ, the PLAIN sum in ascending s (qc_sweep_grad_reduce_kernel reads a missing
+//      weight vector as 1/S each); +0.0 at every entry that is not a control or timestep of knots 0 .. T-2.
+// No atomics, sums in a fixed order: repeated calls return the same bits, and no output's bits depend on which others were asked for.
+//
+// Scope: the gradient's without its two fidelity conditions (qc_sweep_vjp_scope below shares qc_sweep_closed_scope with it).
+#include <math.h>
+
+#include <string>
+
+#include "qc_sweep_internal.h"
+
+namespace {
+
+constexpr int kCotT = 256;        // threads of the seed workgroup: the thread count of qc_sweep_finish_kernel (same sums, same bits)
+constexpr int kSumT = 256;
+
+struct CotParams {
+    int n, ns, n_chunks;
+};
+
+struct SumParams {
+    int zdim, off_a, off_dt, m, nd;
+    long long T, Zlen, S;
+};
+
+// The body of both seed kernels; LD is the leading dimension of the totals.  LDS: cur, nxt (ns each) and one total (LD x LD).
+template <int LD>
+__device__ __forceinline__ void cot_seed(const CotParams F, const double* __restrict__ tot, const double* __restrict__ src,
+                                         const double* __restrict__ cot, double* __restrict__ xs, double* __restrict__ ls,
+                                         double* __restrict__ finals, double* __restrict__ ginit, double* sm) {
+    constexpr int ld = LD, l2 = LD * LD;
+    const int tid = threadIdx.x, n = F.n, ns = F.ns;
+    const long long s = blockIdx.x;
+    double* cur = sm;
+    double* nxt = sm + ns;
+    double* Q = sm + 2 * ns;
+    for (int idx = tid; idx < ns; idx += kCotT) cur[idx] = src[idx];
+    const double* __restrict__ Qs = tot + s * F.n_chunks * (long long)l2;
+    double* __restrict__ xo = xs + s * F.n_chunks * (long long)ns;
+    double* __restrict__ lo = ls + s * F.n_chunks * (long long)ns;
+    for (int c = 0; c < F.n_chunks; ++c) {
+        __syncthreads();
+        for (int idx = tid; idx < l2; idx += kCotT) Q[idx] = Qs[(long long)c * l2 + idx];
+        __syncthreads();
+        for (int idx = tid; idx < ns; idx += kCotT) {
+            const int r = idx % n, col = idx / n;
+            double acc = 0.0;
+            for (int q = 0; q < n; ++q) acc = fma(Q[r + ld * q], cur[q + n * col], acc);
+            nxt[idx] = acc;
+            xo[(long long)c * ns + idx] = acc;
+        }
+        double* tmp = cur; cur = nxt; nxt = tmp;
+    }
+    __syncthreads();
+    if (finals)
+        for (int idx = tid; idx < ns; idx += kCotT) finals[s * ns + idx] = cur[idx];
+    // lambda at the final knot: the caller's cotangent
+    for (int idx = tid; idx < ns; idx += kCotT) {
+        const double v = cot[s * ns + idx];
+        cur[idx] = v;
+        lo[(long long)(F.n_chunks - 1) * ns + idx] = v;
+    }
+    for (int c = F.n_chunks - 1; c >= (ginit ? 0 : 1); --c) {
+        __syncthreads();
+        for (int idx = tid; idx < l2; idx += kCotT) Q[idx] = Qs[(long long)c * l2 + idx];
+        __syncthreads();
+        for (int idx = tid; idx < ns; idx += kCotT) {
+            const int r = idx % n, col = idx / n;
+            double acc = 0.0;
+            for (int q = 0; q < n; ++q) acc = fma(Q[q + ld * r], cur[q + n * col], acc);
+            nxt[idx] = acc;
+            if (c > 0) lo[(long long)(c - 1) * ns + idx] = acc;
+            else ginit[s * ns + idx] = acc;          // lambda_0 = Q_0^T lambda_{end of chunk 0}
+        }
+        double* tmp = cur; cur = nxt; nxt = tmp;
+    }
+}
+
+__global__ __launch_bounds__(kCotT) void qc_sweep_cot_seed_kernel(const CotParams F, const double* __restrict__ tot, const double* __restrict__ src,
+                                                                  const double* __restrict__ cot, double* __restrict__ xs, double* __restrict__ ls,
+                                                                  double* __restrict__ finals, double* __restrict__ ginit) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    cot_seed<16>(F, tot, src, cot, xs, ls, finals, ginit, sm);
+}
+
+__global__ __launch_bounds__(kCotT) void qc_sweep32_cot_seed_kernel(const CotParams F, const double* __restrict__ tot, const double* __restrict__ src,
+                                                                    const double* __restrict__ cot, double* __restrict__ xs, double* __restrict__ ls,
+                                                                    double* __restrict__ finals, double* __restrict__ ginit) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    cot_seed<32>(F, tot, src, cot, xs, ls, finals, ginit, sm);
+}
+
+// grad[i] = sum_s dphi_s/dZ_i, the plain sum in ascending s, for the controls and timesteps of knots 0 .. T-2; +0.0 everywhere else
+__global__ __launch_bounds__(kSumT) void qc_sweep_vjp_reduce_kernel(const SumParams R, const double* __restrict__ gs, double* __restrict__ grad) {
+    const long long i = (long long)blockIdx.x * kSumT + threadIdx.x;
+    if (i >= R.Zlen) return;
+    const long long t = i / R.zdim;
+    const int o = (int)(i - t * R.zdim);
+    int k = -1;
+    if (t < R.T - 1) {
+        if (o >= R.off_a && o < R.off_a + R.m) k = o - R.off_a;
+        else if (o == R.off_dt) k = R.m;       // off_dt = -1: never
+    }
+    double acc = 0.0;
+    if (k >= 0) {
+        const long long stride = (R.T - 1) * R.nd;
+        const double* __restrict__ p = gs + t * R.nd + k;
+        for (long long s = 0; s < R.S; ++s) acc += p[s * stride];
+    }
+    grad[i] = acc;
+}
+
+int vfail(qc_side* h, int code, const std::string& msg) { return qc_sweep_fail(h, code, msg); }
+
+const char* const kNoWidePar = "qc_sweep pullback: parameter cotangents are not served in the mfma32-sweep form";
+
+// the argument checks both entry points share, in the order of the header's table
+int vjp_check(qc_sweep* h, const char* who, const void* Z, const void* init, int64_t S, const void* theta, const void* cot, bool any_out,
+              bool g_theta, bool g_scale) {
+    const std::string pre = std::string(who) + ": ";
+    if (!h) return vfail(nullptr, QC_ERR_INVALID, pre + "NULL handle");
+    if (!h->vjp_ok) return vfail(h, QC_ERR_UNSUPPORTED, "qc_sweep pullback: " + h->vjp_why);
+    if (!Z || !init) return vfail(h, QC_ERR_INVALID, pre + "NULL input");
+    if (!cot) return vfail(h, QC_ERR_INVALID, pre + "cot is NULL");
+    if (S < 1 || S > (1ll << 24)) return vfail(h, QC_ERR_INVALID, pre + "S must be in 1 .. 2^24");
+    if (h->d.n_pert > 0 && !theta) return vfail(h, QC_ERR_INVALID, pre + "theta is NULL but the handle has perturbations");
+    if (!any_out) return vfail(h, QC_ERR_INVALID, pre + "every output is NULL");
+    if (g_theta && h->d.n_pert == 0) return vfail(h, QC_ERR_INVALID, pre + "grad_theta is given but the handle has no perturbations (n_pert = 0)");
+    if (g_scale && h->d.m == 0) return vfail(h, QC_ERR_INVALID, pre + "grad_scale is given but the handle has no drives (m = 0)");
+    if ((g_theta || g_scale) && h->mfma32) return vfail(h, QC_ERR_UNSUPPORTED, kNoWidePar);
+    return QC_OK;
+}
+
+}  // namespace
+
+bool qc_sweep_vjp_scope(const qc_sweep_desc* d, std::string* why) { return qc_sweep_closed_scope(d, why); }
+
+extern "C" int qc_sweep_desc_vjp_supported(const qc_sweep_desc* d, int32_t* supported) {
+    int rc = qc_sweep_validate_desc(d);
+    if (rc) return rc;
+    if (!supported) return vfail(nullptr, QC_ERR_INVALID, "qc_sweep_desc_vjp_supported: supported is NULL");
+    std::string why;
+    const bool ok = qc_sweep_vjp_scope(d, &why);
+    *supported = ok ? 1 : 0;
+    if (!ok) (void)vfail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep pullback: " + why);
+    return QC_OK;
+}
+
+static int qc_sweep_vjp_launch(qc_sweep* h, const char* who, const double* dZ, const double* dinit, int64_t S, const double* dtheta,
+                               const double* dscale, const double* dcot, double* dfinals, double* dgrad, double* dgrad_samples, double* dgrad_init,
+                               double* dgrad_theta, double* dgrad_scale, void* stream) {
+    const bool any_out = dfinals || dgrad || dgrad_samples || dgrad_init || dgrad_theta || dgrad_scale;
+    int rc = vjp_check(h, who, dZ, dinit, S, dtheta, dcot, any_out, dgrad_theta != nullptr, dgrad_scale != nullptr);
+    if (rc) return rc;
+    std::string& slot = *qc_sweep_err_slot();
+    qc_device_guard guard(h->device);
+    QC_SIDE_HIP(h, slot, guard.err);
+    hipStream_t st = (hipStream_t)stream;
+    const int m = h->d.m, p = h->d.n_pert;
+    const int nd = m + (h->d.off_dt >= 0 ? 1 : 0);
+    const int64_t n_int = h->d.T - 1;
+    int64_t chunk, n_chunks;
+    rc = qc_sweep_launch_totals(h, dZ, S, dtheta, dscale, st, &chunk, &n_chunks);
+    if (rc) return rc;
+    const size_t n_state = (size_t)S * n_chunks * h->ns;
+    QC_SIDE_HIP(h, slot, h->grow(&h->dXs, &h->capXs, n_state));
+    QC_SIDE_HIP(h, slot, h->grow(&h->dLs, &h->capLs, n_state));
+    const bool want_par = dgrad_theta || dgrad_scale;
+    const bool want_grad = (dgrad || dgrad_samples) && nd > 0;
+    double* gsamp = dgrad_samples;
+    if (want_grad && !gsamp) {
+        QC_SIDE_HIP(h, slot, h->grow(&h->dGsamp, &h->capGsamp, (size_t)S * n_int * nd));
+        gsamp = h->dGsamp;
+    }
+    if (want_par) QC_SIDE_HIP(h, slot, h->grow(&h->dPart, &h->capPart, (size_t)S * n_chunks * (p + m)));
+    CotParams F;
+    F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
+    if (h->mfma32) {
+        const size_t lds = ((size_t)2 * h->ns + 1024) * 8;       // at most 16 state columns: 16 KiB
+        hipLaunchKernelGGL(qc_sweep32_cot_seed_kernel, dim3((unsigned)S), dim3(kCotT), lds, st, F, (const double*)h->dTot, dinit, dcot, h->dXs, h->dLs,
+                           dfinals, dgrad_init);
+        if (want_grad) qc_sweep32_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, gsamp, st);
+    } else {
+        const size_t lds = ((size_t)2 * h->ns + 256) * 8;
+        hipLaunchKernelGGL(qc_sweep_cot_seed_kernel, dim3((unsigned)S), dim3(kCotT), lds, st, F, (const double*)h->dTot, dinit, dcot, h->dXs, h->dLs,
+                           dfinals, dgrad_init);
+        if (want_grad || want_par)
+            qc_sweep16_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);
+    }
+    if (dgrad) {
+        SumParams R;
+        R.zdim = h->d.zdim; R.off_a = h->d.off_a; R.off_dt = h->d.off_dt; R.m = m; R.nd = nd;
+        R.T = h->d.T; R.Zlen = h->Zlen; R.S = S;
+        hipLaunchKernelGGL(qc_sweep_vjp_reduce_kernel, dim3((unsigned)((h->Zlen + kSumT - 1) / kSumT)), dim3(kSumT), 0, st, R, (const double*)gsamp, dgrad);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return vfail(h, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return QC_OK;
+}
+
+extern "C" int qc_sweep_vjp_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
+                                const double* dcot, double* dfinals, double* dgrad, double* dgrad_samples, double* dgrad_init,
+                                double* dgrad_theta, double* dgrad_scale, void* stream) {
+    return qc_sweep_vjp_launch(h, "qc_sweep_vjp_dev", dZ, dinit, S, dtheta, dscale, dcot, dfinals, dgrad, dgrad_samples, dgrad_init, dgrad_theta,
+                               dgrad_scale, stream);
+}
+
+// The host-buffer entry point: stage, call the device entry point on the handle's stream, copy back, synchronise.
+extern "C" int qc_sweep_vjp(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
+                            const double* cot, double* finals, double* grad, double* grad_samples, double* grad_init, double* grad_theta,
+                            double* grad_scale) {
+    const char* who = "qc_sweep_vjp";
+    const bool any_out = finals || grad || grad_samples || grad_init || grad_theta || grad_scale;
+    int rc = vjp_check(h, who, Z, init, S, theta, cot, any_out, grad_theta != nullptr, grad_scale != nullptr);
+    if (rc) return rc;
+    std::string& slot = *qc_sweep_err_slot();
+    qc_device_guard guard(h->device);
+    QC_SIDE_HIP(h, slot, guard.err);
+    const int m = h->d.m, p = h->d.n_pert;
+    const bool use_scale = scale && m > 0;
+    const size_t n_fin = (size_t)S * h->ns;
+    const size_t n_samp = (size_t)S * (size_t)(h->d.T - 1) * (size_t)(m + (h->d.off_dt >= 0 ? 1 : 0));
+    if (p) QC_SIDE_HIP(h, slot, h->grow(&h->sTheta, &h->capTheta, (size_t)S * p));
+    if (use_scale) QC_SIDE_HIP(h, slot, h->grow(&h->sScale, &h->capScale, (size_t)S * m));
+    QC_SIDE_HIP(h, slot, h->grow(&h->sCot, &h->capCot, n_fin));
+    if (finals) QC_SIDE_HIP(h, slot, h->grow(&h->sFinals, &h->capFinals, n_fin));
+    if (grad_init) QC_SIDE_HIP(h, slot, h->grow(&h->sGinit, &h->capGinit, n_fin));
+    if (grad_samples && n_samp) QC_SIDE_HIP(h, slot, h->grow(&h->sGradS, &h->capGradS, n_samp));
+    if (grad_theta) QC_SIDE_HIP(h, slot, h->grow(&h->sGth, &h->capGth, (size_t)S * p));
+    if (grad_scale) QC_SIDE_HIP(h, slot, h->grow(&h->sGsc, &h->capGsc, (size_t)S * m));
+    if (grad && !h->sGrad) QC_SIDE_HIP(h, slot, h->alloc(&h->sGrad, (size_t)h->Zlen));
+    QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sZ, Z, (size_t)h->Zlen * 8, hipMemcpyHostToDevice, h->stream));
+    QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sInit, init, (size_t)h->ns * 8, hipMemcpyHostToDevice, h->stream));
+    if (p) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sTheta, theta, (size_t)S * p * 8, hipMemcpyHostToDevice, h->stream));
+    if (use_scale) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sScale, scale, (size_t)S * m * 8, hipMemcpyHostToDevice, h->stream));
+    QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sCot, cot, n_fin * 8, hipMemcpyHostToDevice, h->stream));
+    const bool samp = grad_samples && n_samp;
+    rc = qc_sweep_vjp_launch(h, who, h->sZ, h->sInit, S, p ? h->sTheta : nullptr, use_scale ? h->sScale : nullptr, h->sCot,
+                             finals ? h->sFinals : nullptr, grad ? h->sGrad : nullptr, samp ? h->sGradS : nullptr, grad_init ? h->sGinit : nullptr,
+                             grad_theta ? h->sGth : nullptr, grad_scale ? h->sGsc : nullptr, h->stream);
+    if (rc) return rc;
+    if (finals) QC_SIDE_HIP(h, slot, hipMemcpyAsync(finals, h->sFinals, n_fin * 8, hipMemcpyDeviceToHost, h->stream));
+    if (grad) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad, h->sGrad, (size_t)h->Zlen * 8, hipMemcpyDeviceToHost, h->stream));
+    if (samp) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad_samples, h->sGradS, n_samp * 8, hipMemcpyDeviceToHost, h->stream));
+    if (grad_init) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad_init, h->sGinit, n_fin * 8, hipMemcpyDeviceToHost, h->stream));
+    if (grad_theta) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad_theta, h->sGth, (size_t)S * p * 8, hipMemcpyDeviceToHost, h->stream));
+    if (grad_scale) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad_scale, h->sGsc, (size_t)S * m * 8, hipMemcpyDeviceToHost, h->stream));
+    QC_SIDE_HIP(h, slot, hipStreamSynchronize(h->stream));
+    return QC_OK;
+}

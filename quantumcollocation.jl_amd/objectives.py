@@ -830,3 +830,106 @@ class SweepInfidelityObjective:
             self.close()
         except Exception:
             pass
+
+
+class SweepFinalStateObjective:
+    """L(Z) = loss(X): any function, written in torch, of the final states of the trajectory's pulse over S perturbed systems (the
+    systems of `SweepInfidelityObjective`).  X is the S x (2N cols) float64 device tensor of `RolloutSweep.finals_autograd`, row s the
+    final state of sample s, column-major 2N x cols ([Re; Im] per column); `loss` maps it to a 0-dim tensor.  `L(Z)` evaluates it,
+    `grad_L(Z)` (dense, length `len(Z)`) runs torch's backward through the sweep's pullback: one adjoint sweep per gradient.  First
+    order only, as `SweepInfidelityObjective`: `hess_structure` is empty and `hess_L` raises.
+
+    state_name  a unitary component (2 N^2 entries), a component of K kets (2 N K entries, the kets side by side) or a list of ket
+                component names (stacked as columns in that order).  No goal is read: the loss carries whatever it compares with.
+    theta       S x len(perturbations);  scale  S x n_drives or None
+    wide        as `RolloutSweep`"""
+    _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
+
+    def __init__(self, traj: NamedTrajectory, system, perturbations, theta, loss, scale=None, state_name="Ũ⃗", control_name: str = "a",
+                 device: int = 0, wide: bool = False):
+        from .rollouts import RolloutSweep, _sweep_samples
+        self._sweep = None
+        if not callable(loss):
+            raise ValueError("loss must be a callable from the S x (2N cols) tensor of final states to a 0-dim tensor")
+        names = [state_name] if isinstance(state_name, str) else list(state_name)
+        for name in names + [control_name]:
+            if name not in traj.components:
+                raise ValueError(f"the trajectory has no component {name}")
+        N, m = system.state_levels, system.n_drives
+        if len(traj.components[control_name]) != m:
+            raise ValueError(f"component {control_name} has {len(traj.components[control_name])} rows, the system has {m} drives")
+        cols, init = 0, []
+        for name in names:
+            s = len(traj.components[name])
+            if s % (2 * N) or (len(names) > 1 and s != 2 * N):
+                raise ValueError(f"component {name} has length {s}: " + ("not a ket (2 N)" if len(names) > 1 else "no multiple of 2 N") + f" of N = {N} levels")
+            cols += s // (2 * N)
+            x0 = traj.initial.get(name)
+            init.append(np.asarray(traj[name][:, 0] if x0 is None else x0, dtype=np.float64).ravel())
+        self.S, theta, scale = _sweep_samples(len(perturbations), m, theta, scale)
+        free = isinstance(traj.timestep, str)
+        self.traj, self.loss = traj, loss
+        self.Z_len = traj.T * traj.dim + traj.global_dim
+        sw = RolloutSweep(system, perturbations, traj.T, cols=cols, zdim=traj.dim, off_a=traj.offset(control_name),
+                          off_dt=traj.offset(traj.timestep) if free else -1, dt_fixed=None if free else float(traj.timestep),
+                          global_dim=traj.global_dim, device=device, wide=wide)
+        self._sweep = sw
+        if not sw.vjp_supported:
+            why = sw.vjp_unsupported_reason
+            sw.close()
+            self._sweep = None
+            raise _lib.QCollocError(_lib.QC_ERR_UNSUPPORTED, why)
+        dev = torch.device("cuda", device)
+        put = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        self._dev = dev
+        self._dinit, self._dtheta, self._dscale = put(np.concatenate(init)), put(theta), put(scale)
+        if self._dtheta is None and self._dscale is None:      # samples without any parameter: S identical systems
+            self._dtheta = torch.zeros((self.S, 0), dtype=torch.float64, device=dev)
+        self.hess_structure = (np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64))
+
+    def _loss(self, Z, grad: bool):
+        Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
+        if Z.size != self.Z_len:
+            raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
+        with torch.cuda.device(self._dev):
+            dZ = torch.from_numpy(Z).to(self._dev).requires_grad_(grad)
+            with torch.set_grad_enabled(grad):
+                L = self.loss(self._sweep.finals_autograd(dZ, self._dinit, self._dtheta, self._dscale))
+            if L.dim() != 0:
+                raise ValueError("loss must return a 0-dim tensor")
+            if not grad:
+                return float(L), None
+            L.backward()
+            g = dZ.grad
+            return float(L.detach()), (np.zeros(self.Z_len) if g is None else g.cpu().numpy())
+
+    def finals(self, Z) -> np.ndarray:
+        """The S x (2N cols) final states the loss sees."""
+        return self._sweep.eval(Z, self._dinit.cpu().numpy(), None if self._dtheta is None else self._dtheta.cpu().numpy(),
+                                None if self._dscale is None else self._dscale.cpu().numpy(), fids=False)[0].T
+
+    def L(self, Z) -> float:
+        return self._loss(Z, False)[0]
+
+    def grad_L(self, Z) -> np.ndarray:
+        return self._loss(Z, True)[1]
+
+    def hess_L(self, Z):
+        raise RuntimeError("SweepFinalStateObjective is first order: build the evaluator with eval_hessian=False")
+
+    def __getattr__(self, name):
+        al = type(self)._ALIASES
+        if name in al:
+            return getattr(self, al[name])
+        raise AttributeError(name)
+
+    def close(self):
+        if getattr(self, "_sweep", None) is not None:
+            self._sweep.close()
+            self._sweep = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

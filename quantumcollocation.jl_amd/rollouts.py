@@ -17,6 +17,8 @@ the loop of the reference's robustness check, `unitary_rollout(traj.a, timesteps
     rollout_fidelity_sweep(traj, system, perturbations, θ; state_name)     ... of a ket
     rollout_sweep_parameter_gradient(init, controls, Δt, system, perturbations, θ, scale)   (fids, dF/dθ, dF/dscale)
     RolloutSweep                                                            the handle, for callers that sweep repeatedly
+    RolloutSweep.vjp / .vjp_device / .finals_autograd                       the pullback of the final states (`qc_sweep_vjp*`): any loss of
+                                                                            them, in torch, differentiated by one adjoint sweep
 """
 from __future__ import annotations
 
@@ -406,6 +408,91 @@ class RolloutSweep:
         if rc != _lib.QC_OK:
             raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
 
+    # -- pullbacks: the derivatives of any function of the final states -------------------------------------------------------------
+    @property
+    def vjp_supported(self) -> bool:
+        """Does `vjp` serve this handle?  (`qc_sweep_desc_vjp_supported`: the MFMA forms, at most 16 state columns, antisymmetric
+        generators; any fidelity or none.)  `vjp_unsupported_reason` says why not."""
+        return self._vjp_scope()[0]
+
+    @property
+    def vjp_unsupported_reason(self) -> Optional[str]:
+        return self._vjp_scope()[1]
+
+    def _vjp_scope(self):
+        ok = C.c_int32()
+        rc = _lib.lib.qc_sweep_desc_vjp_supported(C.byref(self._desc), C.byref(ok))
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(None).decode())
+        return bool(ok.value), (None if ok.value else _lib.lib.qc_sweep_last_error(None).decode())
+
+    def vjp(self, Z, init, cot, theta, scale=None, per_sample: bool = False, init_grad: bool = False, params: bool = False):
+        """The pullback of the final states: with phi_s = <cot[s], x_final[s]> (cot: S x (2N cols), one cotangent per sample), returns
+        `grad`, the plain sum over the samples of dphi_s/dZ as a dense vector over the trajectory vector, followed -- in this order --
+        by what was asked for:
+            per_sample   grad_samples, S x (T-1) x n_deriv: dphi_s/d(a_t, dt_t)
+            init_grad    grad_init, S x (2N cols): dphi_s/dinit
+            params       grad_theta (S x n_pert) and grad_scale (S x m), two entries ("mfma16-sweep" handles only)."""
+        Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
+        if Z.size != self.Z_len:
+            raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
+        init = np.ascontiguousarray(init, dtype=np.float64).ravel()
+        if init.size != self.ns:
+            raise ValueError(f"initial state has length {init.size}, expected {self.ns}")
+        S, theta, scale = self._samples(theta, scale)
+        cot = np.ascontiguousarray(cot, dtype=np.float64)
+        if cot.shape != (S, self.ns):
+            raise ValueError(f"cot must be {S} x {self.ns}")
+        g = np.empty(self.Z_len)
+        gs = np.empty((S, self.T - 1, self.n_deriv)) if per_sample else None
+        gi = np.empty((S, self.ns)) if init_grad else None
+        gth, gsc = (np.empty((S, self.p)), np.empty((S, self.m))) if params else (None, None)
+        opt = lambda a: _lib.dptr(a) if (a is not None and a.size) else None
+        rc = _lib.lib.qc_sweep_vjp(self._h, _lib.dptr(Z), _lib.dptr(init), S, opt(theta), opt(scale), _lib.dptr(cot), None, _lib.dptr(g), opt(gs),
+                                   opt(gi), opt(gth), opt(gsc))
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        return (g,) + ((gs,) if per_sample else ()) + ((gi,) if init_grad else ()) + ((gth, gsc) if params else ())
+
+    def vjp_device(self, dZ, dinit, S: int, dcot, dtheta=None, dscale=None, dfinals=None, dgrad=None, dgrad_samples=None, dgrad_init=None,
+                   dgrad_theta=None, dgrad_scale=None, stream=None):
+        """Device-resident pullback on torch CUDA tensors (float64), asynchronous on `stream`: `qc_sweep_vjp_dev`.  dcot S x (2N cols);
+        outputs optional one at a time: dfinals S x (2N cols) (the bits of `eval_device`), dgrad Z_len, dgrad_samples
+        S x (T-1) x n_deriv, dgrad_init S x (2N cols), dgrad_theta S x n_pert, dgrad_scale S x m."""
+        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        S = int(S)
+        if all(t is None for t in (dfinals, dgrad, dgrad_samples, dgrad_init, dgrad_theta, dgrad_scale)):
+            raise ValueError("every output is None")
+        if dcot is None:
+            raise ValueError("dcot is required")
+        if dgrad_theta is not None and not self.p:
+            raise ValueError("dgrad_theta is given but the handle has no perturbations")
+        if dgrad_scale is not None and not self.m:
+            raise ValueError("dgrad_scale is given but the handle has no drives")
+        for t, cnt, what in ((dZ, self.Z_len, "dZ"), (dinit, self.ns, "dinit"), (dcot, S * self.ns, "dcot"), (dtheta, S * self.p, "dtheta"),
+                             (dscale, S * self.m, "dscale"), (dfinals, S * self.ns, "dfinals"), (dgrad, self.Z_len, "dgrad"),
+                             (dgrad_samples, S * (self.T - 1) * self.n_deriv, "dgrad_samples"), (dgrad_init, S * self.ns, "dgrad_init"),
+                             (dgrad_theta, S * self.p, "dgrad_theta"), (dgrad_scale, S * self.m, "dgrad_scale")):
+            if t is not None and (t.numel() != cnt or t.dtype != torch.float64 or not t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous float64 tensor of {cnt} entries")
+        if self.p and dtheta is None:
+            raise ValueError("dtheta is required: the handle has perturbations")
+        ptr = lambda t, use=True: t.data_ptr() if (t is not None and use and t.numel()) else None
+        rc = _lib.lib.qc_sweep_vjp_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dcot), ptr(dfinals),
+                                       ptr(dgrad), ptr(dgrad_samples), ptr(dgrad_init), ptr(dgrad_theta), ptr(dgrad_scale), s)
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+
+    def finals_autograd(self, dZ, dinit, dtheta=None, dscale=None):
+        """The S x (2N cols) final states as a differentiable torch tensor: forward is `eval_device` on the current stream, backward one
+        `vjp_device` call.  dZ (Z_len), dinit (2N cols), dtheta (S x n_pert), dscale (S x m or None) are float64 CUDA tensors; whichever
+        requires grad receives one: Z the plain sum over the samples, init the sum of the per-sample derivatives, theta and scale
+        their per-sample values ("mfma16-sweep" handles only: on a wide handle a theta or scale that requires grad raises in backward)."""
+        if dtheta is None and dscale is None:
+            raise ValueError("dtheta (S x n_pert) or dscale (S x m) must give the number of samples")
+        S = (dtheta if dtheta is not None else dscale).shape[0]
+        return _SweepFinals.apply(self, int(S), dZ, dinit, dtheta, dscale)
+
     def close(self):
         if getattr(self, "_h", None):
             _lib.lib.qc_sweep_destroy(self._h)
@@ -416,6 +503,44 @@ class RolloutSweep:
             self.close()
         except Exception:
             pass
+
+
+class _SweepFinals(torch.autograd.Function):
+    """`RolloutSweep.finals_autograd`: final states forward, one pullback call backward, only the outputs whose inputs need them."""
+
+    @staticmethod
+    def forward(ctx, sw, S, dZ, dinit, dtheta, dscale):
+        ctx.init_shape = dinit.shape
+        dZ, dinit = dZ.detach().contiguous(), dinit.detach().contiguous().reshape(-1)
+        dtheta = None if dtheta is None else dtheta.detach().contiguous()
+        dscale = None if dscale is None else dscale.detach().contiguous()
+        out = torch.empty((S, sw.ns), dtype=torch.float64, device=dZ.device)
+        sw.eval_device(dZ, dinit, dtheta, dscale, out, None)
+        ctx.sw, ctx.S = sw, S
+        ctx.save_for_backward(dZ, dinit, dtheta, dscale)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        sw, S = ctx.sw, ctx.S
+        dZ, dinit, dtheta, dscale = ctx.saved_tensors
+        need_Z, need_init, need_theta, need_scale = ctx.needs_input_grad[2:6]
+        if not (need_Z or need_init or need_theta or need_scale):
+            return (None,) * 6
+        if sw.kernel_name == "mfma32-sweep" and (need_theta or need_scale):
+            raise _lib.QCollocError(_lib.QC_ERR_UNSUPPORTED, "qc_sweep pullback: parameter cotangents are not served in the mfma32-sweep form")
+        mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dZ.device)
+        gZ = mk(sw.Z_len) if need_Z else None
+        gI = mk(S, sw.ns) if need_init else None
+        gT = mk(S, sw.p) if (need_theta and sw.p) else None
+        gC = mk(S, sw.m) if (need_scale and sw.m) else None
+        if any(t is not None for t in (gZ, gI, gT, gC)):
+            sw.vjp_device(dZ, dinit, S, grad_output.contiguous(), dtheta, dscale, dgrad=gZ, dgrad_init=gI, dgrad_theta=gT, dgrad_scale=gC)
+        if need_theta and gT is None:
+            gT = torch.zeros_like(dtheta)
+        if need_scale and gC is None:
+            gC = torch.zeros_like(dscale)
+        return None, None, gZ, (gI.sum(0).reshape(ctx.init_shape) if need_init else None), gT, gC
 
 
 def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None, cols: Optional[int] = None, goal=None, fid_kind=None,
