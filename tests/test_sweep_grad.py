@@ -6,7 +6,8 @@ properties, the refused handles, non-finite input, the objective inside an evalu
 
 Tolerance (GPU against the reference), per sample: |got - want| <= 1e-9 max(1, max |grad F_s|).  The argument is test_sweep.py's for the
 fidelities: the states agree to 1e-10, and a gradient entry is a bounded bilinear form in the state x and the adjoint lambda.
-Measured worst errors: profiles/sweep_grad_summary.txt."""
+Measured worst errors: profiles/sweep_grad_summary.txt.
+Every sample of mid-size and filled launches (S = 97 .. 2049) against the reference: tests/test_sweep_every_sample.py."""
 import ctypes as C
 import os
 import sys

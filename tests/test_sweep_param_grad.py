@@ -8,7 +8,8 @@ arguments, the example.
 Tolerance (GPU against the reference), per sample s: |got - want| <= 1e-9 max(1, A_s), A_s = max over the parameters of
 sum_t |term_{s,t}| from the forward-mode reference: the per-interval bound of tests/test_sweep_grad.py (states to 1e-10, truncation
 1.7e-12 relative per term) carried through a sum, so it scales with the sum of magnitudes, not with T.  The identities between
-outputs of one call hold to 1e-12 max(1, A_s).  Measured worst ratios: profiles/sweep_param_grad_summary.txt."""
+outputs of one call hold to 1e-12 max(1, A_s).  Measured worst ratios: profiles/sweep_param_grad_summary.txt.
+Every sample of mid-size and filled launches (S = 97 .. 2049) against the reference: tests/test_sweep_every_sample.py."""
 import ctypes as C
 import os
 import sys

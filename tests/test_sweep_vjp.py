@@ -7,7 +7,8 @@ with the fidelity gradient, isolation of a non-finite cotangent, refusals, autog
 Tolerance (GPU against the reference).  The cotangents have Frobenius norm 1, so lambda has norm 1 along the whole walk (the
 propagators are orthogonal), as the fidelity seeds have; test_sweep_grad.py's argument carries over: per sample
 |got - want| <= 1e-9 max(1, max |want_s|) for grad_samples, grad_theta and grad_scale.  grad_init = W^T C_s is an orthogonal image of a
-unit vector: the state tolerance of test_sweep.py (rtol 1e-10, atol 1e-11).  Measured worst errors: profiles/sweep_vjp_summary.txt."""
+unit vector: the state tolerance of test_sweep.py (rtol 1e-10, atol 1e-11).  Measured worst errors: profiles/sweep_vjp_summary.txt.
+Every sample of mid-size and filled launches (S = 97 .. 2049) against the reference: tests/test_sweep_every_sample.py."""
 import ctypes as C
 import os
 import sys

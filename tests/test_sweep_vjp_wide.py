@@ -1,6 +1,7 @@
 """Sweep pullbacks on wide handles ("mfma32-sweep": qc_sweep32_cot_seed_kernel and the wide walk, 16 < 2N <= 32): every requested output
 against the forward-mode reference of tests/sweep_vjp_reference.py, with the checks and the tolerances of test_sweep_vjp.py (read its
-header); no parameter cotangents in this form.  Measured worst errors: profiles/sweep_vjp_summary.txt."""
+header); no parameter cotangents in this form.  Measured worst errors: profiles/sweep_vjp_summary.txt.
+Every sample of mid-size and filled launches (S = 301 .. 2049) against the reference: tests/test_sweep_every_sample.py."""
 import numpy as np
 import pytest
 import torch

@@ -4,7 +4,8 @@ value of `grad_samples` against the forward-mode reference of tests/sweep_grad_r
 squarings, bits, refusals, non-finite input, the objective inside an evaluator and the example.
 
 Tolerance: test_sweep_grad.py's, per sample |got - want| <= 1e-9 max(1, max |grad F_s|); a gradient entry is a bounded bilinear form in
-the state and the adjoint, whatever the size.  Measured worst errors: profiles/sweep_wide_summary.txt."""
+the state and the adjoint, whatever the size.  Measured worst errors: profiles/sweep_wide_summary.txt.
+Every sample of mid-size and filled launches (S = 301 .. 2049) against the reference: tests/test_sweep_every_sample.py."""
 import os
 import sys
 
