@@ -632,7 +632,11 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * (qc_sweep_grad_params*), both below, are served for closed systems in the MFMA forms (parameter gradients: "mfma16-sweep" only).
  * Derivatives of the final states themselves, contracted with cotangents the caller chooses (qc_sweep_vjp*, below), carry any function
  * of the final states: leakage, the free-phase fidelity, several kets at once, a loss written elsewhere.
- * Out of scope: per-knot outputs, open-system gradients (they need stored forward states), second derivatives, several devices. */
+ * The forward-mode counterpart, the tangent of the final states and fidelities along one direction (qc_sweep_jvp*, below), is served
+ * for "mfma16-sweep" handles with any generators, Lindblad ones included; with the pullback it gives Gauss-Newton products of any loss.
+ * Out of scope: per-knot outputs, open-system gradients (reverse mode needs stored forward states; their directional derivatives are
+ * qc_sweep_jvp's), pushforwards on "mfma32-sweep" and "rollout-per-sample" handles, several directions per call, exact second
+ * derivatives, several devices. */
 #define QC_MAX_PERT 8
 #define QC_SWEEP_FID_NONE (-1)   /* qc_sweep_desc.fid_kind: final states only */
 #define QC_SWEEP_WIDE 1          /* qc_sweep_desc.wide */
@@ -754,6 +758,38 @@ int qc_sweep_vjp_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t
 int qc_sweep_vjp(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
                  const double* cot, double* finals, double* grad, double* grad_samples, double* grad_init,
                  double* grad_theta, double* grad_scale);
+
+/* ---- sweep pushforwards: tangents of the final states and fidelities along one direction --------------------------------- */
+/* The pushforward of (Z, init, theta, c) -> x_final[s] along the direction (vZ, vinit, vtheta, vscale):
+ *     d(hG)_t = vh_t G_s(a_t) + h_t ( sum_j vtheta[s,j] P_j + sum_k ( vscale[s,k] a_{t,k} + c[s,k] va_{t,k} ) G_k )
+ *     xdot_0 = vinit,   xdot_{t+1} = E_t xdot_t + L(h_t G; d(hG)_t) x_t   (L: the Frechet derivative of exp),   t = 0 .. T-2
+ *     tfinals[s] = xdot_{T-1},   tfids[s] = <dF/dx(x_final[s]), xdot_{T-1}>   (the |tr| / n form is not special-cased at tr = 0).
+ * One forward walk that differentiates every product beside itself: 108 + 12 sq matrix-core instructions per interval against the
+ * sweep's 36 + 4 sq.  Nothing is reversed, so antisymmetry is not asked for: Lindblad generators (QC_FID_DENSITY handles) are served.
+ * With one pullback call it gives the Gauss-Newton product J^T (d2 loss) J v of any loss of the final states. */
+/* device-free: may the pushforward serve this descriptor?  Scope: the "mfma16-sweep" form (2N <= 16, m <= 8), any generators, any
+ * state_cols and fid_kind the sweep serves there.  When 0, qc_sweep_last_error(NULL) says why, prefixed "qc_sweep pushforward: "
+ * ("... not served in the mfma32-sweep form", or the rollout-per-sample form with its cause).  An invalid descriptor returns its own error. */
+int qc_sweep_desc_jvp_supported(const qc_sweep_desc* d, int32_t* supported);
+/* Directions, each optional (NULL = zero: the same bits as an explicit zero array), at least one non-NULL:
+ *   vZ       Z_len, the layout of Z, shared by the samples.  ONLY the controls and timesteps of knots 0 .. T-2 are read: whatever
+ *            stands anywhere else (a NaN included) has no effect
+ *   vinit    2N x cols, shared by the samples
+ *   vtheta   S x n_pert (QC_ERR_INVALID when n_pert = 0)
+ *   vscale   S x m (QC_ERR_INVALID when m = 0); valid with scale = NULL, which means c = 1
+ * Outputs, each optional, at least one non-NULL:
+ *   finals   S x (2N cols), fids  S     the bits of qc_sweep_eval on the same handle
+ *   tfinals  S x (2N cols), tfids S     the tangents (fids / tfids on a handle without a fidelity: QC_ERR_INVALID)
+ * Directions must not overlap outputs.  S in 1 .. 2^24.  Scratch and the one-in-flight rule as qc_sweep_eval_dev.  Repeated calls
+ * return the same bits, and no output's bits depend on which other outputs were requested.  Non-finite inputs are evaluated, not
+ * rejected: a non-finite entry of vtheta[s] or vscale[s] stays inside sample s (the number of squarings never depends on the direction). */
+int qc_sweep_jvp_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
+                     const double* dvZ, const double* dvinit, const double* dvtheta, const double* dvscale,
+                     double* dfinals, double* dfids, double* dtfinals, double* dtfids, void* stream);
+/* the same on host buffers (synchronous) */
+int qc_sweep_jvp(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
+                 const double* vZ, const double* vinit, const double* vtheta, const double* vscale,
+                 double* finals, double* fids, double* tfinals, double* tfids);
 
 /* Diagnostic only: when the environment variable QC_STAMPS=1 is set at qc_create, the MFMA kernel
  * records 16 s_memrealtime (100 MHz) checkpoints per interval; this copies them out (synchronises the

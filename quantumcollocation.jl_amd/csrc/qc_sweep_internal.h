@@ -1,5 +1,6 @@
-// What qc_sweep.hip (forward sweep), qc_sweep_grad.hip (its adjoint) and qc_sweep_vjp.hip (the pullback of the final states) share: the handle, the descriptor checks and the launch of the
-// forward chunk totals (with it the chunk rule).  Not part of the ABI.
+// What qc_sweep.hip (forward sweep), qc_sweep_grad.hip (its adjoint), qc_sweep_vjp.hip (the pullback of the final states) and
+// qc_sweep_jvp.hip (their pushforward) share: the handle, the descriptor checks and the launch of the forward chunk totals (with it
+// the chunk rule).  Not part of the ABI.
 #pragma once
 
 #include <string>
@@ -14,6 +15,8 @@ struct qc_sweep : qc_side {
     std::string grad_why;        // when not: the reason
     bool vjp_ok = false;         // the pullback's scope (qc_sweep_vjp.hip): the gradient's without its fidelity conditions
     std::string vjp_why;
+    bool jvp_ok = false;         // the pushforward's scope (qc_sweep_jvp.hip): "mfma16-sweep" handles, any generators
+    std::string jvp_why;
     int n = 0, nc = 0, ns = 0, fid_n = 0;
     int64_t Zlen = 0;
     double* dG = nullptr;        // (1 + m + p) matrices, column-major (per-sample form)
@@ -44,6 +47,14 @@ struct qc_sweep : qc_side {
     // pullback (qc_sweep_vjp.hip): staging of the cotangents and of grad_init in its host-buffer entry point (finals: sFinals above)
     double* sCot = nullptr;   size_t capCot = 0;
     double* sGinit = nullptr; size_t capGinit = 0;
+    // pushforward (qc_sweep_jvp.hip): the chunk totals and their tangents, S x n_chunks x 2 tiles; staging of the directions and of the
+    // tangent outputs in its host-buffer entry point (finals, fids: sFinals, sFids above)
+    double* dTotJ = nullptr;  size_t capTotJ = 0;
+    double *sVZ = nullptr, *sVinit = nullptr;
+    double* sVth = nullptr;   size_t capVth = 0;
+    double* sVsc = nullptr;   size_t capVsc = 0;
+    double* sTfin = nullptr;  size_t capTfin = 0;
+    double* sTfid = nullptr;  size_t capTfid = 0;
 };
 
 // records the message in the handle (when there is one) and in the slot qc_sweep_last_error(NULL) returns
@@ -77,3 +88,5 @@ bool qc_sweep_grad_scope(const qc_sweep_desc* d, std::string* why);
 // what the gradient and the pullback ask alike (an MFMA form, antisymmetric matrices, at most 16 state columns), and the pullback's scope
 bool qc_sweep_closed_scope(const qc_sweep_desc* d, std::string* why);
 bool qc_sweep_vjp_scope(const qc_sweep_desc* d, std::string* why);
+// the pushforward's scope (qc_sweep_jvp.hip): the "mfma16-sweep" form, whatever the generators
+bool qc_sweep_jvp_scope(const qc_sweep_desc* d, std::string* why);

@@ -1,0 +1,455 @@
+// Sweep pushforwards: the tangent of the map (Z, init, theta, c) -> x_final[s] of the rollout sweep along ONE direction
+// (vZ, vinit, vtheta, vc) -- the forward-mode counterpart of qc_sweep_vjp.hip.  With G_s(a) = G_drift + sum_j theta[s,j] P_j +
+// sum_k c[s,k] a_k G_k and x_{t+1} = E_t x_t, E_t = exp(h_t G_s(a_t)), x_0 = init:
+//     d(hG)_t = vh_t G_s(a_t) + h_t ( sum_j vtheta[s,j] P_j + sum_k ( vc[s,k] a_{t,k} + c[s,k] va_{t,k} ) G_k )
+//     xdot_0 = vinit,    xdot_{t+1} = E_t xdot_t + L(h_t G; d(hG)_t) x_t          (L: the Frechet derivative of exp)
+//     tfinals[s] = xdot_{T-1},    tfids[s] = <dF/dx(x_final[s]), xdot_{T-1}>.
+// Nothing is reversed, so no antisymmetry is asked for: Lindblad generators are served like any others (the adjoint walks of
+// qc_sweep_grad.hip are not: they reverse the state with E^T).
+//
+// "mfma16-sweep" handles only (2N <= 16, up to 8 drives).  qc_sweep_jvp_kernel<M> has the work item, workgroup shape and chunk rule of
+// qc_sweep_mfma16_kernel (qc_sweep.hip; read its header first): one wavefront per (sample, chunk), kSWaves of them per workgroup,
+// never synchronised.  Every product of the forward kernel is differentiated next to itself, with the tangent tile in the lane map
+// of the tile it belongs to:
+//   once per wave   Bdot = sum_j vtheta[s,j] P_j (A layout), the lane's vc[s,k] beside c[s,k]
+//   coefficients    al = a c,  aldot = va c + a vc
+//   generators      Ga = base + sum al_u G_u,  Gadot = Bdot + sum aldot_u G_u
+//   squarings       sq from ||h Ga||_1 by the forward kernel's rule; the tangent never influences it (a non-finite direction cannot
+//                   change what the other outputs see)
+//   scaled tiles    Y = (h 2^-sq) Ga,  Ydot = (vh 2^-sq) Ga + (h 2^-sq) Gadot
+//   Horner          Rdot <- Ydot R + Y Rdot (from the old R), R <- Y R + I/(k-1)!           8 x 12 MFMAs on three independent chains
+//   per squaring    Rdot <- E Rdot + Edot E, R <- E E         (E, Edot as left factors: two LDS transposes in one round trip)  12 MFMAs
+//   totals          Wdot <- E Wdot + Edot W, W <- E W                                                                             12 MFMAs
+// 108 + 12 sq MFMAs per interval against the forward 36 + 4 sq.  The R / W chain is the forward kernel's operation for operation
+// (same expressions for Ga, sq, Y, the same table, the same product order; an MFMA is an exact ascending-k fma chain), so W carries
+// the forward kernel's bits.  The once-differentiated degree-8 series at ||Y||_1 <= 1/8 truncates at 1.7e-12 relative.
+// The wave stores W and Wdot: S x n_chunks x 2 tiles of handle scratch.
+//
+// qc_sweep_jvp_finish_kernel, one workgroup per sample, has the loops and the reduction order of qc_sweep_finish_kernel:
+// x <- init, xdot <- vinit; for ascending chunks xdot <- Q_c xdot + Qdot_c x, then x <- Q_c x; finals / fids carry the bits of
+// qc_sweep_eval on the same handle.  A NULL direction is read as zeros through the same arithmetic: NULL and an explicit zero array
+// give the same bits.  No atomics, sums in a fixed order: repeated calls return the same bits, and no output's bits depend on which
+// others were asked for.
+//
+// gfx950 cross-compile: see the table in DESIGN.md ("Sweep pushforwards"); no private segment, no spills in any instantiation.
+#include <math.h>
+
+#include <string>
+
+#include "qc_mfma_common.h"
+#include "qc_sweep_internal.h"
+
+namespace {
+
+using namespace qc_mfma;
+
+// the constants of qc_sweep.hip, restated (that file's are internal to it)
+constexpr int kSDeg = 8;
+constexpr double kSTh = 0.125;
+constexpr int kSWaves = 4;
+constexpr int kFinT = 256;
+
+__constant__ const double kSInvFact[kSDeg + 1] = {1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0, 1.0 / 40320.0};
+
+struct JvpParams {
+    int n, nc, m, p, zdim, off_a, off_dt, n_int, chunk, n_chunks;
+    long long items;             // S * n_chunks
+    double dt_fixed;
+    const double* img;           // A-layout images [matrix][kk][lane]: drift, m drives, p perturbations
+};
+
+struct JvpFinParams {
+    int n, ns, n_chunks, fid_kind, fid_form, fid_n;
+};
+
+template <int CTRL>
+__device__ inline double sdpp(double x) {
+    int lo = __double2loint(x), hi = __double2hiint(x);
+    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+__device__ inline v4d simg(const double* __restrict__ img, int mat, int lane) {
+    const double* p = img + (size_t)mat * 256 + lane;
+    return v4d{p[0], p[64], p[128], p[192]};
+}
+
+// A product and its derivative: P = A B + C (the chain of qc_sweep.hip's mma16, operation for operation) and
+// Pdot = Adot B + A Bdot, the twelve MFMAs issued round-robin on three independent accumulators.
+__device__ __forceinline__ void mma16_d(const v4d& a, const v4d& ad, v4d& b, v4d& bd, const v4d& c) {
+    const v4d zero = {0.0, 0.0, 0.0, 0.0};
+    v4d t0 = zero, t1 = zero, r = c;
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+        t0 = __builtin_amdgcn_mfma_f64_16x16x4f64(ad[kk], b[kk], t0, 0, 0, 0);
+        t1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], bd[kk], t1, 0, 0, 0);
+        r = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], b[kk], r, 0, 0, 0);
+    }
+    bd = t0 + t1;
+    b = r;
+}
+
+template <int M>
+__global__ __launch_bounds__(64 * kSWaves, 2) void qc_sweep_jvp_kernel(const JvpParams P, const double* __restrict__ Z,
+                                                                        const double* __restrict__ theta, const double* __restrict__ scale,
+                                                                        const double* __restrict__ vZ, const double* __restrict__ vtheta,
+                                                                        const double* __restrict__ vscale, double* __restrict__ tot) {
+    __shared__ double scr_all[kSWaves * 2 * 16 * 17];
+    const int lane = threadIdx.x & 63;
+    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double* __restrict__ scr = scr_all + wq * (2 * 16 * 17);
+    const long long item = (long long)blockIdx.x * kSWaves + wq;
+    if (item >= P.items) return;
+    const long long s = item / P.n_chunks;
+    const int c = (int)(item - s * P.n_chunks);
+    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
+    const int g = lane >> 4, j = lane & 15;
+    const int m = P.m;
+    const bool ft = P.off_dt >= 0;
+    const bool hasv = vZ != nullptr;
+    const v4d IdB = identity_B(g, j);
+    const v4d zero = {0.0, 0.0, 0.0, 0.0};
+
+    // ---- once per wave: the sample's base tile, its tangent, and the drive tiles -------------------------------------------
+    v4d base = simg(P.img, 0, lane);
+    v4d based = zero;
+    for (int q = 0; q < P.p; ++q) {
+        const double th = theta[s * P.p + q];
+        const double vth = vtheta ? vtheta[s * P.p + q] : 0.0;
+        const v4d Pq = simg(P.img, 1 + m + q, lane);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            base[r] = fma(th, Pq[r], base[r]);
+            based[r] = fma(vth, Pq[r], based[r]);
+        }
+    }
+    v4d Gj[M];
+#pragma unroll
+    for (int u = 0; u < M; ++u) Gj[u] = u < m ? simg(P.img, 1 + u, lane) : zero;
+    // lane l holds the sample's factor of drive min(l, m-1) and its tangent
+    const int kl = lane < m ? lane : (m > 0 ? m - 1 : 0);
+    const double cl = (scale && m > 0) ? scale[s * m + kl] : 1.0;
+    const double vcl = (vscale && m > 0) ? vscale[s * m + kl] : 0.0;
+
+    const double* __restrict__ z = Z + (long long)t0 * P.zdim;
+    double av = m > 0 ? z[P.off_a + kl] : 0.0;
+    const double hfix = opaque_scalar(P.dt_fixed);
+    double h = ft ? z[P.off_dt] : hfix;
+    double vav = 0.0, vh = 0.0;
+    if (hasv) {
+        const double* __restrict__ vz = vZ + (long long)t0 * P.zdim;
+        if (m > 0) vav = vz[P.off_a + kl];
+        if (ft) vh = vz[P.off_dt];
+    }
+    v4d W = IdB, Wd = zero;
+#pragma unroll 1
+    for (int t = t0; t < t1; ++t) {
+        // the next interval's controls, timestep and their tangents are requested before this interval's products
+        const long long tn = t + 1 < t1 ? t + 1 : t;
+        const double* __restrict__ zn = Z + tn * P.zdim;
+        const double av_n = m > 0 ? zn[P.off_a + kl] : 0.0;
+        const double h_n = ft ? zn[P.off_dt] : hfix;
+        double vav_n = 0.0, vh_n = 0.0;
+        if (hasv) {
+            const double* __restrict__ vzn = vZ + tn * P.zdim;
+            if (m > 0) vav_n = vzn[P.off_a + kl];
+            if (ft) vh_n = vzn[P.off_dt];
+        }
+        const double al = av * cl;
+        const double ald = fma(vav, cl, av * vcl);
+        v4d Ga = base, Gad = based;
+#pragma unroll
+        for (int u = 0; u < M; ++u) {
+            const double a = u < m ? bcast_lane(al, u) : 0.0;
+            const double ad = u < m ? bcast_lane(ald, u) : 0.0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                Ga[r] = fma(a, Gj[u][r], Ga[r]);
+                Gad[r] = fma(ad, Gj[u][r], Gad[r]);
+            }
+        }
+        // ||h G||_1 = largest column sum, as qc_sweep_mfma16_kernel: the tangent has no say in sq
+        int sq = 0;
+        {
+            double best = 0.0;
+            bool bad = false;
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                double cs = fabs(h * Ga[kk]);
+                cs += sdpp<0x128>(cs);
+                cs += sdpp<0x124>(cs);
+                cs += sdpp<0x122>(cs);
+                cs += sdpp<0x121>(cs);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double v = bcast_lane(cs, 16 * r);
+                    if (!(v == v) || v > 1e300) bad = true;
+                    best = fmax(best, v);
+                }
+            }
+            if (!bad && best > kSTh) {
+                int e;
+                (void)frexp(best / kSTh, &e);
+                sq = e;
+                if (ldexp(kSTh, e - 1) >= best) sq = e - 1;
+                sq = sq < 0 ? 0 : (sq > 60 ? 60 : sq);
+            }
+            sq = __builtin_amdgcn_readfirstlane(sq);
+        }
+        const double sc = ldexp(1.0, -sq);
+        const v4d Y = (h * sc) * Ga;
+        v4d Yd;
+        {
+            const double hs = h * sc, vhs = vh * sc;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Yd[r] = fma(vhs, Ga[r], hs * Gad[r]);
+        }
+        // Horner on the pair: Rdot_k = Ydot R_k+1 + Y Rdot_k+1,  R_k = Y R_k+1 + I/(k-1)!
+        v4d R = kSInvFact[kSDeg] * IdB, Rd = zero;
+#pragma unroll 1
+        for (int k = kSDeg; k >= 1; --k) mma16_d(Y, Yd, R, Rd, kSInvFact[k - 1] * IdB);
+        for (int q = 0; q < sq; ++q) {
+            const v4d in[2] = {R, Rd};
+            v4d tr[2];
+            lds_transpose16_multi<2>(scr, in, tr, g, j);      // E^T, Edot^T in D layout = E, Edot in A layout
+            mma16_d(tr[0], tr[1], R, Rd, zero);
+        }
+        const v4d in[2] = {R, Rd};
+        v4d tr[2];
+        lds_transpose16_multi<2>(scr, in, tr, g, j);
+        mma16_d(tr[0], tr[1], W, Wd, zero);
+        av = av_n;
+        h = h_n;
+        vav = vav_n;
+        vh = vh_n;
+    }
+    double* __restrict__ o = tot + item * 512;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        o[j * 16 + 4 * r + g] = W[r];
+        o[256 + j * 16 + 4 * r + g] = Wd[r];
+    }
+}
+
+// One workgroup per sample: x = Q_last ... Q_0 init and its tangent in ascending order, final state, fidelity and their tangents.
+// The x loop, the fidelity sums and their mapping are qc_sweep_finish_kernel's (ld = 16), so finals / fids carry its bits.
+// With t = (g_r . x) + i (g_i . x) and tdot likewise from xdot:  dF = (t_r tdot_r + t_i tdot_i) / (n^2 F) for |t| / n (not special-cased
+// at t = 0), 2 (t_r tdot_r + t_i tdot_i) / n^2 for |t|^2 / n^2, 2 (...) for a ket, tdot_r for a density operator (qc_fidelity.hip).
+__global__ __launch_bounds__(kFinT) void qc_sweep_jvp_finish_kernel(const JvpFinParams F, const double* __restrict__ tot, const double* __restrict__ src,
+                                                                    const double* __restrict__ vsrc, const double* __restrict__ gr,
+                                                                    const double* __restrict__ gi, double* __restrict__ finals,
+                                                                    double* __restrict__ fids, double* __restrict__ tfinals,
+                                                                    double* __restrict__ tfids) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    __shared__ double red[4][kFinT / 64];
+    constexpr int ld = 16, l2 = 256;
+    const int tid = threadIdx.x, n = F.n, ns = F.ns;
+    const long long s = blockIdx.x;
+    double* cur = sm;
+    double* nxt = sm + ns;
+    double* dcur = sm + 2 * ns;
+    double* dnxt = sm + 3 * ns;
+    double* Q = sm + 4 * ns;
+    double* Qd = Q + l2;
+    for (int idx = tid; idx < ns; idx += kFinT) {
+        cur[idx] = src[idx];
+        dcur[idx] = vsrc ? vsrc[idx] : 0.0;
+    }
+    const double* __restrict__ Qs = tot + s * F.n_chunks * (long long)(2 * l2);
+    for (int c = 0; c < F.n_chunks; ++c) {
+        __syncthreads();
+        for (int idx = tid; idx < 2 * l2; idx += kFinT) Q[idx] = Qs[(long long)c * (2 * l2) + idx];
+        __syncthreads();
+        for (int idx = tid; idx < ns; idx += kFinT) {
+            const int r = idx % n, col = idx / n;
+            double acc = 0.0, dacc = 0.0;
+            for (int q = 0; q < n; ++q) acc = fma(Q[r + ld * q], cur[q + n * col], acc);
+            for (int q = 0; q < n; ++q) dacc = fma(Q[r + ld * q], dcur[q + n * col], dacc);
+            for (int q = 0; q < n; ++q) dacc = fma(Qd[r + ld * q], cur[q + n * col], dacc);
+            nxt[idx] = acc;
+            dnxt[idx] = dacc;
+        }
+        double* tmp = cur; cur = nxt; nxt = tmp;
+        tmp = dcur; dcur = dnxt; dnxt = tmp;
+    }
+    __syncthreads();
+    if (finals)
+        for (int idx = tid; idx < ns; idx += kFinT) finals[s * ns + idx] = cur[idx];
+    if (tfinals)
+        for (int idx = tid; idx < ns; idx += kFinT) tfinals[s * ns + idx] = dcur[idx];
+    if (!fids && !tfids) return;
+    double ar = 0.0, ai = 0.0, br = 0.0, bi = 0.0;
+    for (int i = tid; i < ns; i += kFinT) {
+        const double xi = cur[i], di = dcur[i];
+        ar = fma(gr[i], xi, ar);
+        ai = fma(gi[i], xi, ai);
+        br = fma(gr[i], di, br);
+        bi = fma(gi[i], di, bi);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        ar += __shfl_xor(ar, off, 64);
+        ai += __shfl_xor(ai, off, 64);
+        br += __shfl_xor(br, off, 64);
+        bi += __shfl_xor(bi, off, 64);
+    }
+    if ((tid & 63) == 0) { red[0][tid >> 6] = ar; red[1][tid >> 6] = ai; red[2][tid >> 6] = br; red[3][tid >> 6] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+        const double tr = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        const double ti = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        const double dr = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
+        const double di = (red[3][0] + red[3][1]) + (red[3][2] + red[3][3]);
+        const double nn = (double)F.fid_n;
+        double Fv;      // the mapping of qc_sweep_finish_kernel, written out again
+        if (F.fid_kind == QC_FID_UNITARY) Fv = F.fid_form == QC_FID_FORM_ABS2 ? (tr * tr + ti * ti) / (nn * nn) : sqrt(tr * tr + ti * ti) / nn;
+        else if (F.fid_kind == QC_FID_KET) Fv = tr * tr + ti * ti;
+        else Fv = tr;
+        if (fids) fids[s] = Fv;
+        if (tfids) {
+            const double dot = tr * dr + ti * di;
+            double dF;
+            if (F.fid_kind == QC_FID_UNITARY) dF = F.fid_form == QC_FID_FORM_ABS2 ? 2.0 * dot / (nn * nn) : dot / (nn * nn * Fv);
+            else if (F.fid_kind == QC_FID_KET) dF = 2.0 * dot;
+            else dF = dr;
+            tfids[s] = dF;
+        }
+    }
+}
+
+int jfail(qc_side* h, int code, const std::string& msg) { return qc_sweep_fail(h, code, msg); }
+
+// the argument checks both entry points share, in the order of the header's table
+int jvp_check(qc_sweep* h, const char* who, const void* Z, const void* init, int64_t S, const void* theta, bool any_dir, bool any_out, bool v_theta,
+              bool v_scale, bool any_fid) {
+    const std::string pre = std::string(who) + ": ";
+    if (!h) return jfail(nullptr, QC_ERR_INVALID, pre + "NULL handle");
+    if (!h->jvp_ok) return jfail(h, QC_ERR_UNSUPPORTED, "qc_sweep pushforward: " + h->jvp_why);
+    if (!Z || !init) return jfail(h, QC_ERR_INVALID, pre + "NULL input");
+    if (S < 1 || S > (1ll << 24)) return jfail(h, QC_ERR_INVALID, pre + "S must be in 1 .. 2^24");
+    if (h->d.n_pert > 0 && !theta) return jfail(h, QC_ERR_INVALID, pre + "theta is NULL but the handle has perturbations");
+    if (!any_dir) return jfail(h, QC_ERR_INVALID, pre + "every direction is NULL");
+    if (!any_out) return jfail(h, QC_ERR_INVALID, pre + "every output is NULL");
+    if (v_theta && h->d.n_pert == 0) return jfail(h, QC_ERR_INVALID, pre + "vtheta is given but the handle has no perturbations (n_pert = 0)");
+    if (v_scale && h->d.m == 0) return jfail(h, QC_ERR_INVALID, pre + "vscale is given but the handle has no drives (m = 0)");
+    if (any_fid && h->d.fid_kind == QC_SWEEP_FID_NONE)
+        return jfail(h, QC_ERR_INVALID, pre + "fidelities or their tangents requested from a handle created without one");
+    return QC_OK;
+}
+
+}  // namespace
+
+bool qc_sweep_jvp_scope(const qc_sweep_desc* d, std::string* why) {
+    const int form = qc_sweep_desc_form(d);
+    if (form == 1) return true;
+    if (form == 2) { *why = "pushforwards are not served in the mfma32-sweep form"; return false; }
+    const int n = 2 * d->N, top = d->wide == QC_SWEEP_WIDE ? 32 : 16;
+    *why = n > top ? "the handle takes the rollout-per-sample form (2N = " + std::to_string(n) + " > " + std::to_string(top) + ")"
+                   : "the handle takes the rollout-per-sample form (" + std::to_string(d->m) + " drives > 8)";
+    return false;
+}
+
+extern "C" int qc_sweep_desc_jvp_supported(const qc_sweep_desc* d, int32_t* supported) {
+    int rc = qc_sweep_validate_desc(d);
+    if (rc) return rc;
+    if (!supported) return jfail(nullptr, QC_ERR_INVALID, "qc_sweep_desc_jvp_supported: supported is NULL");
+    std::string why;
+    const bool ok = qc_sweep_jvp_scope(d, &why);
+    *supported = ok ? 1 : 0;
+    if (!ok) (void)jfail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep pushforward: " + why);
+    return QC_OK;
+}
+
+static int qc_sweep_jvp_launch(qc_sweep* h, const char* who, const double* dZ, const double* dinit, int64_t S, const double* dtheta,
+                               const double* dscale, const double* dvZ, const double* dvinit, const double* dvtheta, const double* dvscale,
+                               double* dfinals, double* dfids, double* dtfinals, double* dtfids, void* stream) {
+    int rc = jvp_check(h, who, dZ, dinit, S, dtheta, dvZ || dvinit || dvtheta || dvscale, dfinals || dfids || dtfinals || dtfids, dvtheta != nullptr,
+                       dvscale != nullptr, dfids || dtfids);
+    if (rc) return rc;
+    std::string& slot = *qc_sweep_err_slot();
+    qc_device_guard guard(h->device);
+    QC_SIDE_HIP(h, slot, guard.err);
+    hipStream_t st = (hipStream_t)stream;
+    const int m = h->d.m;
+    int64_t chunk, n_chunks;
+    qc_sweep_chunks(S, h->d.T, &chunk, &n_chunks);
+    QC_SIDE_HIP(h, slot, h->grow(&h->dTotJ, &h->capTotJ, (size_t)S * n_chunks * 512));
+    JvpParams P;
+    P.n = h->n; P.nc = h->nc; P.m = m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
+    P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks;
+    P.items = S * n_chunks;
+    P.dt_fixed = h->d.dt_fixed;
+    P.img = h->dImg;
+    const unsigned grid = (unsigned)((P.items + kSWaves - 1) / kSWaves);
+#define QC_JVP_LAUNCH(M_) \
+    hipLaunchKernelGGL(qc_sweep_jvp_kernel<M_>, dim3(grid), dim3(64 * kSWaves), 0, st, P, dZ, dtheta, dscale, dvZ, dvtheta, dvscale, h->dTotJ)
+    if (m <= 1) QC_JVP_LAUNCH(1);
+    else if (m <= 2) QC_JVP_LAUNCH(2);
+    else if (m <= 4) QC_JVP_LAUNCH(4);
+    else if (m <= 6) QC_JVP_LAUNCH(6);
+    else QC_JVP_LAUNCH(8);
+#undef QC_JVP_LAUNCH
+    JvpFinParams F;
+    F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
+    F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;
+    const size_t lds = ((size_t)4 * h->ns + 512) * 8;      // at most 4096 state entries: 132 KiB of the 160
+    if (lds > 64 * 1024)
+        QC_SIDE_HIP(h, slot, hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep_jvp_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(qc_sweep_jvp_finish_kernel, dim3((unsigned)S), dim3(kFinT), lds, st, F, (const double*)h->dTotJ, dinit, dvinit,
+                       (const double*)h->dgr, (const double*)h->dgi, dfinals, dfids, dtfinals, dtfids);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return jfail(h, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return QC_OK;
+}
+
+extern "C" int qc_sweep_jvp_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
+                                const double* dvZ, const double* dvinit, const double* dvtheta, const double* dvscale, double* dfinals,
+                                double* dfids, double* dtfinals, double* dtfids, void* stream) {
+    return qc_sweep_jvp_launch(h, "qc_sweep_jvp_dev", dZ, dinit, S, dtheta, dscale, dvZ, dvinit, dvtheta, dvscale, dfinals, dfids, dtfinals, dtfids,
+                               stream);
+}
+
+// The host-buffer entry point: stage, call the device entry point on the handle's stream, copy back, synchronise.
+extern "C" int qc_sweep_jvp(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale, const double* vZ,
+                            const double* vinit, const double* vtheta, const double* vscale, double* finals, double* fids, double* tfinals,
+                            double* tfids) {
+    const char* who = "qc_sweep_jvp";
+    int rc = jvp_check(h, who, Z, init, S, theta, vZ || vinit || vtheta || vscale, finals || fids || tfinals || tfids, vtheta != nullptr,
+                       vscale != nullptr, fids || tfids);
+    if (rc) return rc;
+    std::string& slot = *qc_sweep_err_slot();
+    qc_device_guard guard(h->device);
+    QC_SIDE_HIP(h, slot, guard.err);
+    const int m = h->d.m, p = h->d.n_pert;
+    const bool use_scale = scale && m > 0;
+    const size_t n_fin = (size_t)S * h->ns;
+    if (p) QC_SIDE_HIP(h, slot, h->grow(&h->sTheta, &h->capTheta, (size_t)S * p));
+    if (use_scale) QC_SIDE_HIP(h, slot, h->grow(&h->sScale, &h->capScale, (size_t)S * m));
+    if (vZ && !h->sVZ) QC_SIDE_HIP(h, slot, h->alloc(&h->sVZ, (size_t)h->Zlen));
+    if (vinit && !h->sVinit) QC_SIDE_HIP(h, slot, h->alloc(&h->sVinit, (size_t)h->ns));
+    if (vtheta) QC_SIDE_HIP(h, slot, h->grow(&h->sVth, &h->capVth, (size_t)S * p));
+    if (vscale) QC_SIDE_HIP(h, slot, h->grow(&h->sVsc, &h->capVsc, (size_t)S * m));
+    if (finals) QC_SIDE_HIP(h, slot, h->grow(&h->sFinals, &h->capFinals, n_fin));
+    if (fids) QC_SIDE_HIP(h, slot, h->grow(&h->sFids, &h->capFids, (size_t)S));
+    if (tfinals) QC_SIDE_HIP(h, slot, h->grow(&h->sTfin, &h->capTfin, n_fin));
+    if (tfids) QC_SIDE_HIP(h, slot, h->grow(&h->sTfid, &h->capTfid, (size_t)S));
+    QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sZ, Z, (size_t)h->Zlen * 8, hipMemcpyHostToDevice, h->stream));
+    QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sInit, init, (size_t)h->ns * 8, hipMemcpyHostToDevice, h->stream));
+    if (p) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sTheta, theta, (size_t)S * p * 8, hipMemcpyHostToDevice, h->stream));
+    if (use_scale) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sScale, scale, (size_t)S * m * 8, hipMemcpyHostToDevice, h->stream));
+    if (vZ) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sVZ, vZ, (size_t)h->Zlen * 8, hipMemcpyHostToDevice, h->stream));
+    if (vinit) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sVinit, vinit, (size_t)h->ns * 8, hipMemcpyHostToDevice, h->stream));
+    if (vtheta) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sVth, vtheta, (size_t)S * p * 8, hipMemcpyHostToDevice, h->stream));
+    if (vscale) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sVsc, vscale, (size_t)S * m * 8, hipMemcpyHostToDevice, h->stream));
+    rc = qc_sweep_jvp_launch(h, who, h->sZ, h->sInit, S, p ? h->sTheta : nullptr, use_scale ? h->sScale : nullptr, vZ ? h->sVZ : nullptr,
+                             vinit ? h->sVinit : nullptr, vtheta ? h->sVth : nullptr, vscale ? h->sVsc : nullptr, finals ? h->sFinals : nullptr,
+                             fids ? h->sFids : nullptr, tfinals ? h->sTfin : nullptr, tfids ? h->sTfid : nullptr, h->stream);
+    if (rc) return rc;
+    if (finals) QC_SIDE_HIP(h, slot, hipMemcpyAsync(finals, h->sFinals, n_fin * 8, hipMemcpyDeviceToHost, h->stream));
+    if (fids) QC_SIDE_HIP(h, slot, hipMemcpyAsync(fids, h->sFids, (size_t)S * 8, hipMemcpyDeviceToHost, h->stream));
+    if (tfinals) QC_SIDE_HIP(h, slot, hipMemcpyAsync(tfinals, h->sTfin, n_fin * 8, hipMemcpyDeviceToHost, h->stream));
+    if (tfids) QC_SIDE_HIP(h, slot, hipMemcpyAsync(tfids, h->sTfid, (size_t)S * 8, hipMemcpyDeviceToHost, h->stream));
+    QC_SIDE_HIP(h, slot, hipStreamSynchronize(h->stream));
+    return QC_OK;
+}

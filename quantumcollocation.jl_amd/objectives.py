@@ -837,7 +837,11 @@ class SweepFinalStateObjective:
     systems of `SweepInfidelityObjective`).  X is the S x (2N cols) float64 device tensor of `RolloutSweep.finals_autograd`, row s the
     final state of sample s, column-major 2N x cols ([Re; Im] per column); `loss` maps it to a 0-dim tensor.  `L(Z)` evaluates it,
     `grad_L(Z)` (dense, length `len(Z)`) runs torch's backward through the sweep's pullback: one adjoint sweep per gradient.  First
-    order only, as `SweepInfidelityObjective`: `hess_structure` is empty and `hess_L` raises.
+    order only, as `SweepInfidelityObjective`: `hess_structure` is empty and `hess_L` raises.  Curvature is matrix-free:
+    `gauss_newton_times(Z, v)` is the generalized Gauss-Newton product of the loss, one pushforward and one pullback of the sweep.
+    `L`, `grad_L` and `gauss_newton_times` also take Z (and v) as float64 tensors on the handle's device; `grad_L` and
+    `gauss_newton_times` then return device tensors, so an optimiser can keep the trajectory vector there.  numpy in, numpy out is
+    unchanged.
 
     state_name  a unitary component (2 N^2 entries), a component of K kets (2 N K entries, the kets side by side) or a list of ket
                 component names (stacked as columns in that order).  No goal is read: the loss carries whatever it compares with.
@@ -888,11 +892,13 @@ class SweepFinalStateObjective:
         self.hess_structure = (np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64))
 
     def _loss(self, Z, grad: bool):
-        Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
-        if Z.size != self.Z_len:
-            raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
+        on_device = torch.is_tensor(Z)      # a float64 tensor on the handle's device: the gradient stays there
+        if not on_device:
+            Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
+        if (Z.numel() if on_device else Z.size) != self.Z_len:
+            raise ValueError(f"Z has length {Z.numel() if on_device else Z.size}, expected {self.Z_len}")
         with torch.cuda.device(self._dev):
-            dZ = torch.from_numpy(Z).to(self._dev).requires_grad_(grad)
+            dZ = (Z.detach().to(self._dev).reshape(-1).clone() if on_device else torch.from_numpy(Z).to(self._dev)).requires_grad_(grad)
             with torch.set_grad_enabled(grad):
                 L = self.loss(self._sweep.finals_autograd(dZ, self._dinit, self._dtheta, self._dscale))
             if L.dim() != 0:
@@ -901,6 +907,8 @@ class SweepFinalStateObjective:
                 return float(L), None
             L.backward()
             g = dZ.grad
+            if on_device:
+                return float(L.detach()), (torch.zeros_like(dZ.detach()) if g is None else g)
             return float(L.detach()), (np.zeros(self.Z_len) if g is None else g.cpu().numpy())
 
     def finals(self, Z) -> np.ndarray:
@@ -909,13 +917,48 @@ class SweepFinalStateObjective:
                                 None if self._dscale is None else self._dscale.cpu().numpy(), fids=False)[0].T
 
     def L(self, Z) -> float:
+        """loss(X(Z)); Z a numpy vector or a float64 tensor on the handle's device."""
         return self._loss(Z, False)[0]
 
-    def grad_L(self, Z) -> np.ndarray:
+    def grad_L(self, Z):
+        """The dense gradient, length `len(Z)`: a numpy array for a numpy Z, a tensor on the handle's device for a tensor Z (nothing
+        crosses to the host but the loss value)."""
         return self._loss(Z, True)[1]
 
     def hess_L(self, Z):
         raise RuntimeError("SweepFinalStateObjective is first order: build the evaluator with eval_hessian=False")
+
+    def gauss_newton_times(self, Z, v):
+        """The generalized Gauss-Newton product J^T (d2 loss / dX2) J v as a dense vector of length `len(Z)`, J the Jacobian of the
+        final states X with respect to Z: one pushforward (X and Xdot = J v, `jvp_device`), the loss's own Hessian product
+        u = d2 loss(X) Xdot by double backward on the loss alone (X a detached leaf), one pullback (`vjp_device`, cot = u).  A loss
+        that is linear in X gives zeros.  Z and v are numpy arrays (the result is one) or float64 tensors on the handle's device (the
+        result stays there).  Needs the pushforward's scope beside the pullback's: closed systems on an "mfma16-sweep" handle."""
+        sw = self._sweep
+        if not sw.jvp_supported:
+            raise _lib.QCollocError(_lib.QC_ERR_UNSUPPORTED, sw.jvp_unsupported_reason)
+        on_device = torch.is_tensor(Z) and torch.is_tensor(v)
+        put = lambda a: (a.detach() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))).to(self._dev).contiguous().reshape(-1)
+        dZ, dv = put(Z), put(v)
+        if dZ.numel() != self.Z_len or dv.numel() != self.Z_len:
+            raise ValueError(f"Z and v must have length {self.Z_len}")
+        with torch.cuda.device(self._dev):
+            X = torch.empty((self.S, sw.ns), dtype=torch.float64, device=self._dev)
+            Xd = torch.empty_like(X)
+            sw.jvp_device(dZ, self._dinit, self.S, self._dtheta, self._dscale, dvZ=dv, dfinals=X, dtfinals=Xd)
+            u = None
+            with torch.enable_grad():
+                X.requires_grad_(True)
+                L = self.loss(X)
+                if L.dim() != 0:
+                    raise ValueError("loss must return a 0-dim tensor")
+                g = torch.autograd.grad(L, X, create_graph=True, allow_unused=True)[0] if L.requires_grad else None
+                if g is not None and g.requires_grad:
+                    u = torch.autograd.grad(g, X, grad_outputs=Xd, allow_unused=True)[0]
+            out = torch.zeros(self.Z_len, dtype=torch.float64, device=self._dev)
+            if u is not None:      # (a loss linear in X has no second derivative: exact zeros, no pullback)
+                sw.vjp_device(dZ, self._dinit, self.S, u.detach().contiguous(), self._dtheta, self._dscale, dgrad=out)
+        return out if on_device else out.cpu().numpy()
 
     def __getattr__(self, name):
         al = type(self)._ALIASES

@@ -19,6 +19,8 @@ the loop of the reference's robustness check, `unitary_rollout(traj.a, timesteps
     RolloutSweep                                                            the handle, for callers that sweep repeatedly
     RolloutSweep.vjp / .vjp_device / .finals_autograd                       the pullback of the final states (`qc_sweep_vjp*`): any loss of
                                                                             them, in torch, differentiated by one adjoint sweep
+    RolloutSweep.jvp / .jvp_device                                          the pushforward (`qc_sweep_jvp*`): tangents of the final states and
+                                                                            fidelities along one direction, open systems included
 """
 from __future__ import annotations
 
@@ -483,11 +485,91 @@ class RolloutSweep:
         if rc != _lib.QC_OK:
             raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
 
+    # -- pushforwards: the tangent of the final states and fidelities along one direction -------------------------------------------
+    @property
+    def jvp_supported(self) -> bool:
+        """Does `jvp` serve this handle?  (`qc_sweep_desc_jvp_supported`: the "mfma16-sweep" form, any generators -- Lindblad ones
+        included -- and any fidelity or none.)  `jvp_unsupported_reason` says why not."""
+        return self._jvp_scope()[0]
+
+    @property
+    def jvp_unsupported_reason(self) -> Optional[str]:
+        return self._jvp_scope()[1]
+
+    def _jvp_scope(self):
+        ok = C.c_int32()
+        rc = _lib.lib.qc_sweep_desc_jvp_supported(C.byref(self._desc), C.byref(ok))
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(None).decode())
+        return bool(ok.value), (None if ok.value else _lib.lib.qc_sweep_last_error(None).decode())
+
+    def jvp(self, Z, init, vZ, theta, scale=None, vinit=None, vtheta=None, vscale=None, fids: bool = False):
+        """The pushforward of the final states along the direction (vZ, vinit, vtheta, vscale): `tfinals`, S x (2N cols), row s the tangent
+        of sample s's final state, and with `fids` also `tfids`, the S tangents of the fidelities.  vZ (Z_len, the layout of Z: only the
+        controls and timesteps of knots 0 .. T-2 act) and vinit (2N cols) are shared by the samples, vtheta is S x n_pert, vscale S x m
+        (valid with scale = None: taken at all ones); whichever is None is zero, at least one must be given."""
+        Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
+        if Z.size != self.Z_len:
+            raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
+        init = np.ascontiguousarray(init, dtype=np.float64).ravel()
+        if init.size != self.ns:
+            raise ValueError(f"initial state has length {init.size}, expected {self.ns}")
+        if theta is None and scale is None and (vtheta is not None or vscale is not None):
+            S = np.asarray(vtheta if vtheta is not None else vscale).reshape(-1, self.p if vtheta is not None else self.m).shape[0]
+        else:
+            S, theta, scale = self._samples(theta, scale)
+        vec = lambda a, cnt, what: None if a is None else self._sized(np.ascontiguousarray(a, dtype=np.float64).ravel(), cnt, what)
+        vZ, vinit = vec(vZ, self.Z_len, "vZ"), vec(vinit, self.ns, "vinit")
+        vtheta, vscale = vec(vtheta, S * self.p, "vtheta"), vec(vscale, S * self.m, "vscale")
+        tf = np.empty((S, self.ns))
+        tfid = np.empty(S) if fids else None
+        opt = lambda a: _lib.dptr(a) if a is not None else None
+        rc = _lib.lib.qc_sweep_jvp(self._h, _lib.dptr(Z), _lib.dptr(init), S, opt(theta), opt(scale), opt(vZ), opt(vinit), opt(vtheta), opt(vscale),
+                                   None, None, _lib.dptr(tf), opt(tfid))
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        return (tf, tfid) if fids else tf
+
+    @staticmethod
+    def _sized(a, cnt, what):
+        if a.size != cnt:
+            raise ValueError(f"{what} has {a.size} entries, expected {cnt}")
+        return a
+
+    def jvp_device(self, dZ, dinit, S: int, dtheta=None, dscale=None, dvZ=None, dvinit=None, dvtheta=None, dvscale=None, dfinals=None, dfids=None,
+                   dtfinals=None, dtfids=None, stream=None):
+        """Device-resident pushforward on torch CUDA tensors (float64), asynchronous on `stream`: `qc_sweep_jvp_dev`.  Directions, each
+        optional, at least one: dvZ Z_len, dvinit 2N cols, dvtheta S x n_pert, dvscale S x m.  Outputs, each optional, at least one:
+        dfinals S x (2N cols) and dfids S (the bits of `eval_device`), dtfinals S x (2N cols), dtfids S."""
+        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        S = int(S)
+        if all(t is None for t in (dvZ, dvinit, dvtheta, dvscale)):
+            raise ValueError("every direction is None")
+        if all(t is None for t in (dfinals, dfids, dtfinals, dtfids)):
+            raise ValueError("every output is None")
+        if dvtheta is not None and not self.p:
+            raise ValueError("dvtheta is given but the handle has no perturbations")
+        if dvscale is not None and not self.m:
+            raise ValueError("dvscale is given but the handle has no drives")
+        for t, cnt, what in ((dZ, self.Z_len, "dZ"), (dinit, self.ns, "dinit"), (dtheta, S * self.p, "dtheta"), (dscale, S * self.m, "dscale"),
+                             (dvZ, self.Z_len, "dvZ"), (dvinit, self.ns, "dvinit"), (dvtheta, S * self.p, "dvtheta"), (dvscale, S * self.m, "dvscale"),
+                             (dfinals, S * self.ns, "dfinals"), (dfids, S, "dfids"), (dtfinals, S * self.ns, "dtfinals"), (dtfids, S, "dtfids")):
+            if t is not None and (t.numel() != cnt or t.dtype != torch.float64 or not t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous float64 tensor of {cnt} entries")
+        if self.p and dtheta is None:
+            raise ValueError("dtheta is required: the handle has perturbations")
+        ptr = lambda t, use=True: t.data_ptr() if (t is not None and use and t.numel()) else None
+        rc = _lib.lib.qc_sweep_jvp_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dvZ), ptr(dvinit),
+                                       ptr(dvtheta), ptr(dvscale), ptr(dfinals), ptr(dfids), ptr(dtfinals), ptr(dtfids), s)
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+
     def finals_autograd(self, dZ, dinit, dtheta=None, dscale=None):
         """The S x (2N cols) final states as a differentiable torch tensor: forward is `eval_device` on the current stream, backward one
-        `vjp_device` call.  dZ (Z_len), dinit (2N cols), dtheta (S x n_pert), dscale (S x m or None) are float64 CUDA tensors; whichever
-        requires grad receives one: Z the plain sum over the samples, init the sum of the per-sample derivatives, theta and scale
-        their per-sample values ("mfma16-sweep" handles only: on a wide handle a theta or scale that requires grad raises in backward)."""
+        `vjp_device` call, and under `torch.autograd.forward_ad` the tangent is one `jvp_device` call ("mfma16-sweep" handles).  dZ
+        (Z_len), dinit (2N cols), dtheta (S x n_pert), dscale (S x m or None) are float64 CUDA tensors; whichever requires grad
+        receives one: Z the plain sum over the samples, init the sum of the per-sample derivatives, theta and scale their per-sample
+        values ("mfma16-sweep" handles only: on a wide handle a theta or scale that requires grad raises in backward)."""
         if dtheta is None and dscale is None:
             raise ValueError("dtheta (S x n_pert) or dscale (S x m) must give the number of samples")
         S = (dtheta if dtheta is not None else dscale).shape[0]
@@ -518,6 +600,22 @@ class _SweepFinals(torch.autograd.Function):
         sw.eval_device(dZ, dinit, dtheta, dscale, out, None)
         ctx.sw, ctx.S = sw, S
         ctx.save_for_backward(dZ, dinit, dtheta, dscale)
+        ctx.save_for_forward(dZ, dinit, dtheta, dscale)
+        return out
+
+    @staticmethod
+    def jvp(ctx, _sw, _S, tZ, tinit, ttheta, tscale):
+        """Forward mode: tangents for whichever of Z, init, theta, scale carry one, one `jvp_device` call."""
+        sw, S = ctx.sw, ctx.S
+        dZ, dinit, dtheta, dscale = ctx.saved_tensors
+        flat = lambda t: None if t is None else t.detach().contiguous().reshape(-1)
+        tZ, tinit = flat(tZ), flat(tinit)
+        ttheta = flat(ttheta) if sw.p else None
+        tscale = flat(tscale) if sw.m else None
+        out = torch.empty((S, sw.ns), dtype=torch.float64, device=dZ.device)
+        if all(t is None for t in (tZ, tinit, ttheta, tscale)):
+            return out.zero_()
+        sw.jvp_device(dZ, dinit, S, dtheta, dscale, dvZ=tZ, dvinit=tinit, dvtheta=ttheta, dvscale=tscale, dtfinals=out)
         return out
 
     @staticmethod
