@@ -29,7 +29,9 @@
 // x <- init, xdot <- vinit; for ascending chunks xdot <- Q_c xdot + Qdot_c x, then x <- Q_c x; finals / fids carry the bits of
 // qc_sweep_eval on the same handle.  A NULL direction is read as zeros through the same arithmetic: NULL and an explicit zero array
 // give the same bits.  No atomics, sums in a fixed order: repeated calls return the same bits, and no output's bits depend on which
-// others were asked for.
+// others were asked for.  Its dynamic LDS is 4 ns + 512 doubles (x, its successor, their tangents, one chunk total and its tangent);
+// ns = 2N x state_cols reaches 4096 entries (sweep_validate), which is 135168 bytes = 132 KiB of the 160 KiB of a CU.  Above 64 KiB
+// (ns > 1920) the launch opts in with hipFuncSetAttribute; an MI355X accepts it up to ns = 4096 (tests/test_sweep_many_columns.py).
 //
 // gfx950 cross-compile: see the table in DESIGN.md ("Sweep pushforwards"); no private segment, no spills in any instantiation.
 #include <math.h>

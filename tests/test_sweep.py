@@ -6,7 +6,9 @@ robustness check, bit reproducibility, device-resident calls on a side stream, n
 
 Tolerances (GPU against the reference): states rtol 1e-10 / atol 1e-11, the project's rollout tolerance (tests/test_rollout.py);
 fidelities 1e-9 absolute, which the state tolerance implies (|dF| <= sqrt(N) max|dU| for N <= 32).  The reference itself agrees with
-the independent route to better than 1e-12 (first test)."""
+the independent route to better than 1e-12 (first test).
+States of many columns, up to the 4096 entries the descriptor admits (the strided loops and the LDS opt-in of the finish kernels):
+tests/test_sweep_many_columns.py; every sample of the pushforward's launches: tests/test_sweep_jvp_every_sample.py."""
 import ctypes as C
 import os
 import subprocess

@@ -9,7 +9,9 @@ Tolerance (GPU against the reference).  The two reference routes agree to 1e-13 
 holds them to 1e-11).  The kernels hold the states to 1e-10 (test_sweep.py), and a tangent is a bounded bilinear form of states and
 direction -- the argument of GRAD_RTOL in tests/test_sweep_grad.py: per sample |got - want| <= 1e-9 max(1, max |want_s|) for tfinals
 and tfids.  finals: the state tolerance of test_sweep.py.  The adjoint identity compares two quantities that are each within 1e-9 of the
-truth: 2e-9."""
+truth: 2e-9.
+Every sample of mid-size and filled launches, the scratch `dTotJ`: tests/test_sweep_jvp_every_sample.py; states of up to 4096 entries:
+tests/test_sweep_many_columns.py."""
 import ctypes as C
 import os
 import sys

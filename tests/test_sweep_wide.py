@@ -4,7 +4,8 @@ the gradient scope, the struct mirror.  GPU: parity with the scipy reference of 
 tiling, padding, chunking and squaring can go wrong, exact cases, bits, non-finite input, the unchanged default.
 
 Tolerances are test_sweep.py's (states rtol 1e-10 / atol 1e-11, fidelities 1e-9 absolute; its argument |dF| <= sqrt(N) max|dU| holds for
-N <= 32).  Every test prints its worst error against the bound; measured values: profiles/sweep_wide_summary.txt."""
+N <= 32).  Every test prints its worst error against the bound; measured values: profiles/sweep_wide_summary.txt.
+Wide states of many columns (more than 3584 entries: the finish kernel's LDS opt-in at ld = 32): tests/test_sweep_many_columns.py."""
 import ctypes as C
 import os
 import subprocess
