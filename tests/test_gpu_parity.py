@@ -452,13 +452,17 @@ def test_antisymmetric_generator_path_matches_general_path(qc, monkeypatch, cfg,
 @pytest.mark.parametrize("cfg,T,align", [(3, 1000, 0), (3, 1000, 16), (5, 500, 0), (5, 500, 16), (3, 3000, 16), (3, 4300, 0), (5, 1100, 16)])
 def test_full_size_hessian_properties(qc, oracle, cfg, T, align):
     """Configs 3 (T=1000) and 5 (T=500) at full size, and stretched past the grids' caps (2 999 and 4 299 intervals on 1 024 persistent
-    workgroups at 2N = 16; five intervals per workgroup at 2N = 32): linearity in mu, directional second derivative against
-    the Jacobian, an oracle window in the middle of the trajectory."""
+    workgroups of F + dF at 2N = 16 -- mu_d2F there is qc_mfma_hess_g2.hip, one interval per workgroup; at 2N = 32 the row-gather kernel of
+    qc_mfma32_ell.hip, one interval per workgroup as well, 1 099 of them: the dense-image kernel's runs of intervals are
+    tests/test_pade4_launch_forms.py's): linearity in mu, directional second derivative against the Jacobian, an oracle window in the
+    middle of the trajectory."""
     inp = qc.config_inputs(cfg, T=T)
     prob = problem_from_inputs(inp)
     prob.hess_align = align or 1
     Z = inp.traj.datavec
     dyn = qc.QuantumDynamics(inp.integrators, inp.traj, hess_align=align)
+    if cfg == 5:
+        assert dyn.kernel_names == ("mfma32-pade4-ell", "mfma32-pade4-hess-ell"), dyn.kernel_names
     rng = np.random.default_rng(11)
     mu1, mu2 = rng.standard_normal(prob.n_rows), rng.standard_normal(prob.n_rows)
     H1, H2, H12 = dyn.mu_d2F(Z, mu1), dyn.mu_d2F(Z, mu2), dyn.mu_d2F(Z, 2.0 * mu1 - 3.0 * mu2)
@@ -1016,12 +1020,16 @@ def test_dense_drives_keep_the_dense_image_kernel(qc, oracle):
 
 
 def test_mfma32_hessian_large_T_matches_lds_kernel(qc):
-    """Thousands of workgroups (one per interval), XCD remap included, against the LDS kernel."""
+    """Config 5's Pauli drives at T = 2300: the row-gather kernel (qc_mfma32_ell.hip, `mfma32-pade4-hess-ell`) on 2299 workgroups, one
+    per interval, XCD remap included, against the LDS kernel.  (The dense-image kernel of qc_mfma32_hess.hip, which gives each
+    workgroup a run of intervals, is not reached from here: tests/test_pade4_launch_forms.py.)"""
     inp = qc.config_inputs(5, T=2300)
     Z = inp.traj.datavec
     out = {}
     for kernel in ("mfma", "lds"):
         dyn = qc.QuantumDynamics(inp.integrators, inp.traj, kernel=kernel)
+        if kernel == "mfma":
+            assert dyn.kernel_names == ("mfma32-pade4-ell", "mfma32-pade4-hess-ell"), dyn.kernel_names
         mu = np.random.default_rng(4).standard_normal(dyn.dims.n_rows)
         out[kernel] = dyn.mu_d2F(Z, mu)
         dyn.close()
