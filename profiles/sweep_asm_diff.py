@@ -1,0 +1,90 @@
+#!/usr/bin/env python3
+"""Device assembly of the sweep family at two commits, compared per kernel symbol: the instruction stream (labels renumbered, comments
+dropped), the .amdhsa_kernel block and the metadata (VGPRs, AGPRs, SGPRs, LDS, scratch, spills).  Needs no GPU.
+
+    for f in qc_sweep qc_sweep32 qc_sweep_grad qc_sweep32_grad qc_sweep_vjp qc_sweep_jvp; do
+        hipcc <the Makefile's CXXFLAGS> --cuda-device-only -S $f.hip -o DIR/$f.s       # once in each tree
+    done
+    python profiles/sweep_asm_diff.py PARENT_DIR NEW_DIR [--changed qc_sweep_seed_kernel,...]
+
+Kernels named by --changed (default: the four seed kernels) are reported with their metadata on both sides, wherever they live; every
+other kernel must be identical, and the exit status says whether it is."""
+import argparse
+import os
+import re
+import subprocess
+import sys
+
+FILES = ["qc_sweep", "qc_sweep32", "qc_sweep_grad", "qc_sweep32_grad", "qc_sweep_vjp", "qc_sweep_jvp"]
+SEEDS = "qc_sweep_seed_kernel,qc_sweep32_seed_kernel,qc_sweep_cot_seed_kernel,qc_sweep32_cot_seed_kernel"
+KEYS = ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "sgpr_spill_count", "vgpr_spill_count")
+
+
+def relabel(text):
+    return re.sub(r"\.LBB\d+_", ".LBB_", text)
+
+
+def kernels(path):
+    """{mangled name: (instructions, .amdhsa_kernel block, metadata)} of one .s file"""
+    txt = open(path).read()
+    notes = txt[txt.rfind("amdhsa.kernels"):]
+    out = {}
+    for m in re.finditer(r"^(_Z\w+):\s*; @\1\n(.*?)^\.Lfunc_end\d+:", txt, re.S | re.M):
+        name = m.group(1)
+        k = re.search(r"\.amdhsa_kernel %s\n(.*?)\.end_amdhsa_kernel" % name, txt, re.S)
+        if not k:
+            continue      # a device function
+        body = [re.sub(r"\s*;.*$", "", ln) for ln in relabel(m.group(2)).splitlines()]
+        body = [ln for ln in body if ln.strip()]
+        blk = [b for b in re.split(r"\n  - \.agpr_count", notes) if re.search(r"\.name:\s+%s\n" % name, b)]
+        assert len(blk) == 1, name
+        meta = {key: int(re.search(r"\.%s:\s+(\d+)" % key, ".agpr_count" + blk[0]).group(1)) for key in KEYS}
+        meta["instructions"] = sum(1 for ln in body if ln.startswith("\t") and not ln.strip().startswith("."))
+        out[name] = ("\n".join(body), relabel(k.group(1)), meta)
+    return out
+
+
+def plain(name):
+    o = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip().replace("(anonymous namespace)::", "")
+    return re.match(r"(?:void )?([\w:]+(?:<[^>]*>)?)", o).group(1)
+
+
+def show(meta):
+    return (f"VGPR {meta['vgpr_count']} AGPR {meta['agpr_count']} SGPR {meta['sgpr_count']} LDS {meta['group_segment_fixed_size']} B scratch "
+            f"{meta['private_segment_fixed_size']} B spills {meta['sgpr_spill_count']}+{meta['vgpr_spill_count']} instructions {meta['instructions']}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("parent")
+    ap.add_argument("new")
+    ap.add_argument("--changed", default=SEEDS)
+    a = ap.parse_args()
+    changed = set(a.changed.split(","))
+    sides = [{}, {}]
+    differ = same = 0
+    for f in FILES:
+        A, B = (kernels(os.path.join(d, f + ".s")) for d in (a.parent, a.new))
+        for name in sorted(set(A) | set(B)):
+            p = plain(name)
+            if p in changed:
+                for side, K in zip(sides, (A, B)):
+                    if name in K:
+                        side[p] = (f, K[name][2])
+            elif name in A and name in B and A[name] == B[name]:
+                same += 1
+                print(f"{f}.hip  {p}: identical instructions and metadata  ({show(A[name][2])})")
+            else:
+                differ += 1
+                print(f"{f}.hip  {p}: DIFFERS" if name in A and name in B else f"{f}.hip  {p}: on one side only")
+    for p in sorted(changed):
+        for label, side in zip(("parent", "new   "), sides):
+            if p in side:
+                print(f"{p}  {label} ({side[p][0]}.hip): {show(side[p][1])}")
+    print(f"{same} kernels identical in instruction stream and metadata, {differ} differ or exist on one side only "
+          f"(the {len(changed)} kernels named as changed not counted)")
+    return 1 if differ else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

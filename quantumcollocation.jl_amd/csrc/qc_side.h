@@ -1,11 +1,18 @@
 // Base of the side handles (qc_fidelity, qc_terms, qc_robust, qc_sweep: the objects beside the dynamics handle).  It owns what they
 // all have -- device, stream, last error, and every device allocation -- so a family's file holds its descriptor checks, its kernels
-// and its launches only.  Not part of the ABI: the handle structs are opaque there.
+// and its launches only; qc_stage below is the host-buffer side of an entry point (copies in, copies out, one synchronise).  Not part of
+// the ABI: the handle structs are opaque there.
 #pragma once
 
 #include <memory>
 
 #include "qc_internal.h"
+
+// Scratch of doubles that follows the largest request so far (qc_side::grow): the device pointer and its capacity in elements.
+struct qc_buf {
+    double* p = nullptr;
+    size_t cap = 0;
+};
 
 struct qc_side {
     int device = 0;
@@ -22,18 +29,16 @@ struct qc_side {
         return src ? hipMemcpy(*p, src, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
     }
     // Scratch that follows the largest request so far: freed, then allocated afresh (the contents are never carried over).
-    template <class T>
-    hipError_t grow(T** p, size_t* cap, size_t need) {
-        if (need <= *cap) return hipSuccess;
-        if (*p) {
-            for (void*& q : owned) if (q == *p) { q = owned.back(); owned.pop_back(); break; }
-            hipError_t e = hipFree(*p);
-            *p = nullptr;
-            *cap = 0;
+    hipError_t grow(qc_buf& b, size_t need) {
+        if (need <= b.cap) return hipSuccess;
+        if (b.p) {
+            for (void*& q : owned) if (q == b.p) { q = owned.back(); owned.pop_back(); break; }
+            hipError_t e = hipFree(b.p);
+            b = qc_buf();
             if (e != hipSuccess) return e;
         }
-        hipError_t e = alloc(p, need);
-        if (e == hipSuccess) *cap = need;
+        hipError_t e = alloc(&b.p, need);
+        if (e == hipSuccess) b.cap = need;
         return e;
     }
     hipError_t open_stream() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking); }
@@ -67,6 +72,50 @@ inline int qc_side_fail(qc_side* h, std::string* slot, int code, const std::stri
         hipError_t e_ = (call);                                                                                           \
         if (e_ != hipSuccess) return qc_side_fail(h, &(slot), QC_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
+
+// The host-buffer side of one call, built on the stack at the top of a host entry point (after its argument checks): it selects the
+// handle's device, stages every argument in a buffer of the handle on h->stream, and finish() queues the copies back and synchronises once.
+// The FIRST HIP error is kept and every later step is skipped, so a nullptr from in / out means "not asked for" and nothing else; the
+// caller tests status() once before it launches and returns finish().  Nothing here allocates host memory.
+struct qc_stage {
+    static constexpr int kMaxOut = 8;
+    qc_side* h;
+    std::string* slot;              // the family's thread_local string
+    qc_device_guard guard;
+    hipError_t err;
+    const char* what = "select the device";
+    struct { double* host; const double* dev; size_t count; } back[kMaxOut];
+    int n_back = 0;
+
+    qc_stage(qc_side* h_, std::string* slot_) : h(h_), slot(slot_), guard(h_->device), err(guard.err) {}
+    // `count` doubles of host memory, copied into `b`: the device pointer, or nullptr when there is nothing to copy
+    double* in(qc_buf& b, const double* host, size_t count) {
+        if (!host || !count || !room(b, count)) return nullptr;
+        note(hipMemcpyAsync(b.p, host, count * 8, hipMemcpyHostToDevice, h->stream), "copy to the device");
+        return b.p;
+    }
+    // `count` doubles of `b` that finish() copies to `host`: the device pointer, or nullptr when the output is not asked for
+    double* out(qc_buf& b, double* host, size_t count) {
+        if (!host || !count || !room(b, count)) return nullptr;
+        if (n_back == kMaxOut) { note(hipErrorInvalidValue, "more outputs than qc_stage holds"); return nullptr; }
+        back[n_back++] = {host, b.p, count};
+        return b.p;
+    }
+    int status() { return err == hipSuccess ? QC_OK : qc_side_fail(h, slot, QC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(err)); }
+    int finish() {
+        for (int i = 0; i < n_back && err == hipSuccess; ++i)
+            note(hipMemcpyAsync(back[i].host, back[i].dev, back[i].count * 8, hipMemcpyDeviceToHost, h->stream), "copy to the host");
+        if (err == hipSuccess) note(hipStreamSynchronize(h->stream), "hipStreamSynchronize");
+        return status();
+    }
+
+private:
+    void note(hipError_t e, const char* w) { if (err == hipSuccess && e != hipSuccess) { err = e; what = w; } }
+    bool room(qc_buf& b, size_t count) {
+        if (err == hipSuccess) note(h->grow(b, count), "staging buffer");
+        return err == hipSuccess;
+    }
+};
 
 inline int qc_side_check_device(int device, const char* who, std::string* slot) {
     int ndev = 0;

@@ -255,16 +255,16 @@ __global__ __launch_bounds__(kFinT) void qc_sweep_finish_kernel(const FinParams 
     }
 }
 
-thread_local std::string g_swerr;
-int sfail(qc_side* h, int code, const std::string& msg) { return qc_side_fail(h, &g_swerr, code, msg); }
-
 }  // namespace
 
-namespace {
+// the pieces the family's other files share (qc_sweep_internal.h)
+static thread_local std::string g_swerr;
+int qc_sweep_fail(qc_side* h, int code, const std::string& msg) { return qc_side_fail(h, &g_swerr, code, msg); }
+std::string* qc_sweep_err_slot() { return &g_swerr; }
 
 // The launch rule, in one place.  n_chunks = 1 once the samples alone give every SIMD a couple of waves; fewer samples split the
 // trajectory, up to ceil(sqrt(T-1)) chunks (beyond that the ordered chain of the second launch outweighs what the first gains).
-void sweep_chunks(int64_t S, int64_t T, int64_t* chunk, int64_t* n_chunks) {
+void qc_sweep_chunks(int64_t S, int64_t T, int64_t* chunk, int64_t* n_chunks) {
     const int64_t n_int = T - 1;
     const int64_t want = S >= kSweepFill ? 1 : (kSweepFill + S - 1) / S;
     int64_t r = 1;
@@ -274,76 +274,84 @@ void sweep_chunks(int64_t S, int64_t T, int64_t* chunk, int64_t* n_chunks) {
     *n_chunks = (n_int + *chunk - 1) / *chunk;
 }
 
-int sweep_validate(const qc_sweep_desc* d) {
-    if (!d) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: NULL descriptor");
-    if (d->N < 1) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: N must be >= 1");
-    if (d->m < 0) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: m must be >= 0");
-    if (d->T < 2) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: T must be >= 2");
-    if (d->T > (1ll << 30)) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: T too large");
-    if (d->zdim < 1 || d->global_dim < 0) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: bad zdim / global_dim");
-    if (d->off_a < 0 || (int64_t)d->off_a + d->m > d->zdim) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: off_a outside the knot (m entries from off_a must fit inside zdim)");
-    if (d->off_dt < -1 || d->off_dt >= d->zdim) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: off_dt outside the knot");
-    if (d->n_pert < 0 || d->n_pert > QC_MAX_PERT) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: n_pert must be in 0 .. QC_MAX_PERT (8)");
-    if (d->n_pert > 0 && !d->G_pert) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: n_pert > 0 but G_pert is NULL");
-    if (!d->G_drift) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: G_drift is NULL");
-    if (d->m > 0 && !d->G_drives) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: m > 0 but G_drives is NULL");
-    if (d->state_cols < 0) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: state_cols must be >= 0");
+int qc_sweep_validate_desc(const qc_sweep_desc* d) {
+    if (!d) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: NULL descriptor");
+    if (d->N < 1) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: N must be >= 1");
+    if (d->m < 0) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: m must be >= 0");
+    if (d->T < 2) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: T must be >= 2");
+    if (d->T > (1ll << 30)) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: T too large");
+    if (d->zdim < 1 || d->global_dim < 0) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: bad zdim / global_dim");
+    if (d->off_a < 0 || (int64_t)d->off_a + d->m > d->zdim) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: off_a outside the knot (m entries from off_a must fit inside zdim)");
+    if (d->off_dt < -1 || d->off_dt >= d->zdim) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: off_dt outside the knot");
+    if (d->n_pert < 0 || d->n_pert > QC_MAX_PERT) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: n_pert must be in 0 .. QC_MAX_PERT (8)");
+    if (d->n_pert > 0 && !d->G_pert) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: n_pert > 0 but G_pert is NULL");
+    if (!d->G_drift) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: G_drift is NULL");
+    if (d->m > 0 && !d->G_drives) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: m > 0 but G_drives is NULL");
+    if (d->state_cols < 0) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: state_cols must be >= 0");
     const int nc = d->state_cols == 0 ? d->N : d->state_cols;
     if (d->fid_kind != QC_SWEEP_FID_NONE) {
         if (d->fid_kind != QC_FID_UNITARY && d->fid_kind != QC_FID_KET && d->fid_kind != QC_FID_DENSITY)
-            return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: unknown fid_kind");
-        if (d->fid_form != QC_FID_FORM_ABS && d->fid_form != QC_FID_FORM_ABS2) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: unknown fid_form");
-        if (!d->goal_iso) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: a fidelity needs goal_iso");
+            return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: unknown fid_kind");
+        if (d->fid_form != QC_FID_FORM_ABS && d->fid_form != QC_FID_FORM_ABS2) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: unknown fid_form");
+        if (!d->goal_iso) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: a fidelity needs goal_iso");
         if (d->fid_kind == QC_FID_UNITARY) {
-            if (nc != d->N) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: the unitary fidelity needs state_cols = 0 or N");
+            if (nc != d->N) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: the unitary fidelity needs state_cols = 0 or N");
             if (d->subspace) {
-                if (d->n_sub < 1 || d->n_sub > d->N) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: n_sub must be in 1 .. N");
+                if (d->n_sub < 1 || d->n_sub > d->N) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: n_sub must be in 1 .. N");
                 for (int a = 0; a < d->n_sub; ++a) {
-                    if (d->subspace[a] < 0 || d->subspace[a] >= d->N) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: subspace index outside 0 .. N-1");
+                    if (d->subspace[a] < 0 || d->subspace[a] >= d->N) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: subspace index outside 0 .. N-1");
                     for (int b = 0; b < a; ++b)
-                        if (d->subspace[b] == d->subspace[a]) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: subspace levels must be distinct");
+                        if (d->subspace[b] == d->subspace[a]) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: subspace levels must be distinct");
                 }
             }
         } else {
             if (d->subspace || d->fid_form != QC_FID_FORM_ABS)
-                return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: subspace and fid_form apply to QC_FID_UNITARY only");
-            if (nc != 1) return sfail(nullptr, QC_ERR_INVALID, d->fid_kind == QC_FID_KET ? "qc_sweep: the ket fidelity needs state_cols = 1"
+                return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: subspace and fid_form apply to QC_FID_UNITARY only");
+            if (nc != 1) return qc_sweep_fail(nullptr, QC_ERR_INVALID, d->fid_kind == QC_FID_KET ? "qc_sweep: the ket fidelity needs state_cols = 1"
                                                                                              : "qc_sweep: the density-operator fidelity needs state_cols = 1");
             if (d->fid_kind == QC_FID_DENSITY && qc_isqrt_exact(d->N) < 0)
-                return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: the density-operator fidelity needs N = levels^2");
+                return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: the density-operator fidelity needs N = levels^2");
         }
     }
-    if (2 * (int64_t)d->N > 64) return sfail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: 2N = " + std::to_string(2 * (int64_t)d->N) + " exceeds the supported 2N <= 64");
-    if (2 * (int64_t)d->N * nc > 4096) return sfail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: states of more than 4096 entries (2N x state_cols) are not supported");
-    if (d->m > 64) return sfail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: more than 64 drives are not supported");
-    if (d->wide != 0 && d->wide != QC_SWEEP_WIDE) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep: wide must be 0 or QC_SWEEP_WIDE (1)");
+    if (2 * (int64_t)d->N > 64) return qc_sweep_fail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: 2N = " + std::to_string(2 * (int64_t)d->N) + " exceeds the supported 2N <= 64");
+    if (2 * (int64_t)d->N * nc > 4096) return qc_sweep_fail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: states of more than 4096 entries (2N x state_cols) are not supported");
+    if (d->m > 64) return qc_sweep_fail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: more than 64 drives are not supported");
+    if (d->wide != 0 && d->wide != QC_SWEEP_WIDE) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: wide must be 0 or QC_SWEEP_WIDE (1)");
     return QC_OK;
 }
 
-int sweep_form(const qc_sweep_desc* d) {
+int qc_sweep_desc_form(const qc_sweep_desc* d) {
     if (d->m > kSMmax) return 0;
     if (2 * d->N <= 16) return 1;
     return (d->wide == QC_SWEEP_WIDE && 2 * d->N <= 32) ? 2 : 0;
 }
-bool sweep_is_mfma(const qc_sweep_desc* d) { return sweep_form(d) != 0; }
+bool qc_sweep_desc_is_mfma(const qc_sweep_desc* d) { return qc_sweep_desc_form(d) != 0; }
 
-}  // namespace
+std::string qc_sweep_per_sample_why(const qc_sweep_desc* d) {
+    const int n = 2 * d->N, top = d->wide == QC_SWEEP_WIDE ? 32 : 16;      // wide descriptors: "mfma32-sweep" up to 2N = 32
+    return n > top ? "the handle takes the rollout-per-sample form (2N = " + std::to_string(n) + " > " + std::to_string(top) + ")"
+                   : "the handle takes the rollout-per-sample form (" + std::to_string(d->m) + " drives > 8)";
+}
 
-// the pieces qc_sweep_grad.hip shares (qc_sweep_internal.h)
-int qc_sweep_fail(qc_side* h, int code, const std::string& msg) { return sfail(h, code, msg); }
-std::string* qc_sweep_err_slot() { return &g_swerr; }
-int qc_sweep_validate_desc(const qc_sweep_desc* d) { return sweep_validate(d); }
-bool qc_sweep_desc_is_mfma(const qc_sweep_desc* d) { return sweep_is_mfma(d); }
-int qc_sweep_desc_form(const qc_sweep_desc* d) { return sweep_form(d); }
-void qc_sweep_chunks(int64_t S, int64_t T, int64_t* chunk, int64_t* n_chunks) { sweep_chunks(S, T, chunk, n_chunks); }
+int qc_sweep_check(qc_sweep* h, const char* who, const bool qc_sweep::*ok, const char* scope, const std::string qc_sweep::*why, const void* Z,
+                   const void* init, const char* missing, int64_t S, const void* theta) {
+    const std::string pre = std::string(who) + ": ";
+    if (!h) return qc_sweep_fail(nullptr, QC_ERR_INVALID, pre + "NULL handle");
+    if (ok && !(h->*ok)) return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, scope + h->*why);
+    if (!Z || !init) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "NULL input");
+    if (missing) return qc_sweep_fail(h, QC_ERR_INVALID, pre + missing + " is NULL");
+    if (S < 1 || S > (1ll << 24)) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "S must be in 1 .. 2^24");
+    if (h->d.n_pert > 0 && !theta) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "theta is NULL but the handle has perturbations");
+    return QC_OK;
+}
 
 int qc_sweep_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, hipStream_t st, int64_t* chunk_out,
                            int64_t* n_chunks_out) {
     if (h->mfma32) return qc_sweep32_launch_totals(h, dZ, S, dtheta, dscale, st, chunk_out, n_chunks_out);
     const int m = h->d.m;
     int64_t chunk, n_chunks;
-    sweep_chunks(S, h->d.T, &chunk, &n_chunks);
-    QC_SIDE_HIP(h, g_swerr, h->grow(&h->dTot, &h->capTot, (size_t)S * n_chunks * 256));
+    qc_sweep_chunks(S, h->d.T, &chunk, &n_chunks);
+    QC_SIDE_HIP(h, g_swerr, h->grow(h->dTot, (size_t)S * n_chunks * 256));
     SweepParams P;
     P.n = h->n; P.nc = h->nc; P.m = m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
     P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks;
@@ -351,12 +359,8 @@ int qc_sweep_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const doubl
     P.dt_fixed = h->d.dt_fixed;
     P.img = h->dImg;
     const unsigned grid = (unsigned)((P.items + kSWaves - 1) / kSWaves);
-#define QC_SWEEP_LAUNCH(M_) hipLaunchKernelGGL(qc_sweep_mfma16_kernel<M_>, dim3(grid), dim3(64 * kSWaves), 0, st, P, dZ, dtheta, dscale, h->dTot)
-    if (m <= 1) QC_SWEEP_LAUNCH(1);
-    else if (m <= 2) QC_SWEEP_LAUNCH(2);
-    else if (m <= 4) QC_SWEEP_LAUNCH(4);
-    else if (m <= 6) QC_SWEEP_LAUNCH(6);
-    else QC_SWEEP_LAUNCH(8);
+#define QC_SWEEP_LAUNCH(M_) hipLaunchKernelGGL(qc_sweep_mfma16_kernel<M_>, dim3(grid), dim3(64 * kSWaves), 0, st, P, dZ, dtheta, dscale, h->dTot.p)
+    QC_SWEEP_FOR_M(m, QC_SWEEP_LAUNCH);
 #undef QC_SWEEP_LAUNCH
     *chunk_out = chunk;
     *n_chunks_out = n_chunks;
@@ -367,15 +371,15 @@ extern "C" const char* qc_sweep_last_error(const qc_sweep* h) { return h ? h->er
 
 extern "C" int64_t qc_sizeof_sweep_desc(void) { return (int64_t)sizeof(qc_sweep_desc); }
 
-extern "C" int qc_sweep_desc_validate(const qc_sweep_desc* d) { return sweep_validate(d); }
+extern "C" int qc_sweep_desc_validate(const qc_sweep_desc* d) { return qc_sweep_validate_desc(d); }
 
 extern "C" int qc_sweep_desc_launch(const qc_sweep_desc* d, int64_t S, int32_t* mfma, int64_t* chunk, int64_t* n_chunks) {
-    int rc = sweep_validate(d);
+    int rc = qc_sweep_validate_desc(d);
     if (rc) return rc;
-    if (S < 1) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep_desc_launch: S must be >= 1");
-    const bool mf = sweep_is_mfma(d);
+    if (S < 1) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep_desc_launch: S must be >= 1");
+    const bool mf = qc_sweep_desc_is_mfma(d);
     int64_t ch = d->T - 1, nch = 0;      // per-sample form: the rollout kernels' own scan, no totals
-    if (mf) sweep_chunks(S, d->T, &ch, &nch);
+    if (mf) qc_sweep_chunks(S, d->T, &ch, &nch);
     if (mfma) *mfma = mf ? 1 : 0;
     if (chunk) *chunk = ch;
     if (n_chunks) *n_chunks = nch;
@@ -394,16 +398,16 @@ extern "C" void qc_sweep_destroy(qc_sweep* h) {
 }
 
 extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
-    if (!out) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep_create: out is NULL");
+    if (!out) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep_create: out is NULL");
     *out = nullptr;
-    int rc = sweep_validate(d);
+    int rc = qc_sweep_validate_desc(d);
     if (rc) return rc;
     if ((rc = qc_side_check_device(d->device, "qc_sweep_create", &g_swerr))) return rc;
     qc_side_new<qc_sweep> h(new qc_sweep());
     h->d = *d;
     h->device = d->device;
-    h->mfma = sweep_is_mfma(d);
-    h->mfma32 = sweep_form(d) == 2;
+    h->mfma = qc_sweep_desc_is_mfma(d);
+    h->mfma32 = qc_sweep_desc_form(d) == 2;
     h->grad_ok = qc_sweep_grad_scope(d, &h->grad_why);      // from the caller's matrices, which the handle does not keep
     h->vjp_ok = qc_sweep_vjp_scope(d, &h->vjp_why);
     h->jvp_ok = qc_sweep_jvp_scope(d, &h->jvp_why);
@@ -461,21 +465,28 @@ extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
         QC_SIDE_HIP(nullptr, g_swerr, h->alloc(&h->dgr, gr.size(), gr.data()));
         QC_SIDE_HIP(nullptr, g_swerr, h->alloc(&h->dgi, gi.size(), gi.data()));
     }
-    QC_SIDE_HIP(nullptr, g_swerr, h->alloc(&h->sZ, (size_t)h->Zlen));
-    QC_SIDE_HIP(nullptr, g_swerr, h->alloc(&h->sInit, (size_t)h->ns));
+    QC_SIDE_HIP(nullptr, g_swerr, h->grow(h->sZ, (size_t)h->Zlen));
+    QC_SIDE_HIP(nullptr, g_swerr, h->grow(h->sInit, (size_t)h->ns));
     QC_SIDE_HIP(nullptr, g_swerr, h->open_stream());
     *out = h.release();
     return QC_OK;
 }
 
-extern "C" int qc_sweep_eval_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
-                                 double* dfinals, double* dfids, void* stream) {
-    if (!h) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep_eval_dev: NULL handle");
-    if (!dZ || !dinit) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval_dev: NULL input");
-    if (S < 1 || S > (1ll << 24)) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval_dev: S must be in 1 .. 2^24");
-    if (h->d.n_pert > 0 && !dtheta) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval_dev: theta is NULL but the handle has perturbations");
-    if (!dfinals && !dfids) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval_dev: finals and fids are both NULL");
-    if (dfids && h->d.fid_kind == QC_SWEEP_FID_NONE) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval_dev: fidelities requested from a handle created without one");
+// the argument checks of both entry points, in the order of the header
+static int eval_check(qc_sweep* h, const char* who, const double* Z, const double* init, int64_t S, const double* theta, const double* finals,
+                      const double* fids) {
+    int rc = qc_sweep_check(h, who, nullptr, nullptr, nullptr, Z, init, nullptr, S, theta);
+    if (rc) return rc;
+    const std::string pre = std::string(who) + ": ";
+    if (!finals && !fids) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "finals and fids are both NULL");
+    if (fids && h->d.fid_kind == QC_SWEEP_FID_NONE) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "fidelities requested from a handle created without one");
+    return QC_OK;
+}
+
+static int qc_sweep_eval_launch(qc_sweep* h, const char* who, const double* dZ, const double* dinit, int64_t S, const double* dtheta,
+                                const double* dscale, double* dfinals, double* dfids, void* stream) {
+    int rc = eval_check(h, who, dZ, dinit, S, dtheta, dfinals, dfids);
+    if (rc) return rc;
     qc_device_guard guard(h->device);
     QC_SIDE_HIP(h, g_swerr, guard.err);
     hipStream_t st = (hipStream_t)stream;
@@ -486,12 +497,12 @@ extern "C" int qc_sweep_eval_dev(qc_sweep* h, const double* dZ, const double* di
     const double* src;
     if (h->mfma) {
         int64_t chunk, n_chunks;
-        int rc = qc_sweep_launch_totals(h, dZ, S, dtheta, dscale, st, &chunk, &n_chunks);
+        rc = qc_sweep_launch_totals(h, dZ, S, dtheta, dscale, st, &chunk, &n_chunks);
         if (rc) return rc;
         F.ld = h->mfma32 ? 32 : 16; F.n_chunks = (int)n_chunks; F.src_stride = 0;
         src = dinit;
     } else {
-        QC_SIDE_HIP(h, g_swerr, h->grow(&h->dFin, &h->capFin, (size_t)S * h->ns));
+        QC_SIDE_HIP(h, g_swerr, h->grow(h->dFin, (size_t)S * h->ns));
         QcParams P{};
         P.N = h->d.N; P.n = n; P.nc = h->nc; P.s = h->ns; P.m = m; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
         P.dt_fixed = h->d.dt_fixed; P.G = h->dGs;
@@ -501,46 +512,40 @@ extern "C" int qc_sweep_eval_dev(qc_sweep* h, const double* dZ, const double* di
             hipLaunchKernelGGL(qc_sweep_gen_kernel, dim3(gen_grid), dim3(256), 0, st, n2, m, p, (const double*)h->dG, p ? dtheta + s * p : nullptr,
                                (dscale && m) ? dscale + s * m : nullptr, h->dGs);
             QC_SIDE_HIP(h, g_swerr, qc_launch_rollout(P, h->d.T, dZ, dinit, h->dRout, h->dRE, h->dRQ, h->dRS, st));
-            QC_SIDE_HIP(h, g_swerr, hipMemcpyAsync(h->dFin + (size_t)s * h->ns, h->dRout + last, (size_t)h->ns * 8, hipMemcpyDeviceToDevice, st));
+            QC_SIDE_HIP(h, g_swerr, hipMemcpyAsync(h->dFin.p + (size_t)s * h->ns, h->dRout + last, (size_t)h->ns * 8, hipMemcpyDeviceToDevice, st));
         }
         F.ld = n; F.n_chunks = 0; F.src_stride = h->ns;
-        src = h->dFin;
+        src = h->dFin.p;
     }
     const size_t lds = ((size_t)2 * h->ns + (size_t)F.ld * F.ld) * 8;
     if (lds > 64 * 1024)
         QC_SIDE_HIP(h, g_swerr, hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(qc_sweep_finish_kernel, dim3((unsigned)S), dim3(kFinT), lds, st, F, (const double*)h->dTot, src, (const double*)h->dgr,
+    hipLaunchKernelGGL(qc_sweep_finish_kernel, dim3((unsigned)S), dim3(kFinT), lds, st, F, (const double*)h->dTot.p, src, (const double*)h->dgr,
                        (const double*)h->dgi, dfinals, dfids);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return sfail(h, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return qc_sweep_fail(h, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return QC_OK;
+}
+
+extern "C" int qc_sweep_eval_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
+                                 double* dfinals, double* dfids, void* stream) {
+    return qc_sweep_eval_launch(h, "qc_sweep_eval_dev", dZ, dinit, S, dtheta, dscale, dfinals, dfids, stream);
 }
 
 extern "C" int qc_sweep_eval(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale, double* finals,
                              double* fids) {
-    if (!h) return sfail(nullptr, QC_ERR_INVALID, "qc_sweep_eval: NULL handle");
-    if (!Z || !init) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval: NULL input");
-    if (S < 1 || S > (1ll << 24)) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval: S must be in 1 .. 2^24");
-    const int m = h->d.m, p = h->d.n_pert;
-    if (p > 0 && !theta) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval: theta is NULL but the handle has perturbations");
-    if (!finals && !fids) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval: finals and fids are both NULL");
-    if (fids && h->d.fid_kind == QC_SWEEP_FID_NONE) return sfail(h, QC_ERR_INVALID, "qc_sweep_eval: fidelities requested from a handle created without one");
-    qc_device_guard guard(h->device);
-    QC_SIDE_HIP(h, g_swerr, guard.err);
-    const bool use_scale = scale && m > 0;
-    if (p) QC_SIDE_HIP(h, g_swerr, h->grow(&h->sTheta, &h->capTheta, (size_t)S * p));
-    if (use_scale) QC_SIDE_HIP(h, g_swerr, h->grow(&h->sScale, &h->capScale, (size_t)S * m));
-    if (finals) QC_SIDE_HIP(h, g_swerr, h->grow(&h->sFinals, &h->capFinals, (size_t)S * h->ns));
-    if (fids) QC_SIDE_HIP(h, g_swerr, h->grow(&h->sFids, &h->capFids, (size_t)S));
-    QC_SIDE_HIP(h, g_swerr, hipMemcpyAsync(h->sZ, Z, (size_t)h->Zlen * 8, hipMemcpyHostToDevice, h->stream));
-    QC_SIDE_HIP(h, g_swerr, hipMemcpyAsync(h->sInit, init, (size_t)h->ns * 8, hipMemcpyHostToDevice, h->stream));
-    if (p) QC_SIDE_HIP(h, g_swerr, hipMemcpyAsync(h->sTheta, theta, (size_t)S * p * 8, hipMemcpyHostToDevice, h->stream));
-    if (use_scale) QC_SIDE_HIP(h, g_swerr, hipMemcpyAsync(h->sScale, scale, (size_t)S * m * 8, hipMemcpyHostToDevice, h->stream));
-    int rc = qc_sweep_eval_dev(h, h->sZ, h->sInit, S, p ? h->sTheta : nullptr, use_scale ? h->sScale : nullptr, finals ? h->sFinals : nullptr,
-                               fids ? h->sFids : nullptr, h->stream);
+    const char* who = "qc_sweep_eval";
+    int rc = eval_check(h, who, Z, init, S, theta, finals, fids);
     if (rc) return rc;
-    if (finals) QC_SIDE_HIP(h, g_swerr, hipMemcpyAsync(finals, h->sFinals, (size_t)S * h->ns * 8, hipMemcpyDeviceToHost, h->stream));
-    if (fids) QC_SIDE_HIP(h, g_swerr, hipMemcpyAsync(fids, h->sFids, (size_t)S * 8, hipMemcpyDeviceToHost, h->stream));
-    QC_SIDE_HIP(h, g_swerr, hipStreamSynchronize(h->stream));
-    return QC_OK;
+    const size_t nS = (size_t)S, m = (size_t)h->d.m, p = (size_t)h->d.n_pert, ns = (size_t)h->ns;
+    qc_stage stage(h, &g_swerr);
+    const double* dZ = stage.in(h->sZ, Z, (size_t)h->Zlen);
+    const double* dinit = stage.in(h->sInit, init, ns);
+    const double* dtheta = stage.in(h->sTheta, theta, nS * p);
+    const double* dscale = stage.in(h->sScale, scale, nS * m);
+    double* dfinals = stage.out(h->sFinals, finals, nS * ns);
+    double* dfids = stage.out(h->sFids, fids, nS);
+    if ((rc = stage.status())) return rc;
+    if ((rc = qc_sweep_eval_launch(h, who, dZ, dinit, S, dtheta, dscale, dfinals, dfids, h->stream))) return rc;
+    return stage.finish();
 }

@@ -144,7 +144,7 @@ int qc_sweep32_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const dou
                              int64_t* n_chunks_out) {
     int64_t chunk, n_chunks;
     qc_sweep_chunks(S, h->d.T, &chunk, &n_chunks);
-    QC_SIDE_HIP(h, *qc_sweep_err_slot(), h->grow(&h->dTot, &h->capTot, (size_t)S * n_chunks * 1024));
+    QC_SIDE_HIP(h, *qc_sweep_err_slot(), h->grow(h->dTot, (size_t)S * n_chunks * 1024));
     Sweep32Params P;
     P.n = h->n; P.m = h->d.m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
     P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks;
@@ -152,7 +152,7 @@ int qc_sweep32_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const dou
     P.dt_fixed = h->d.dt_fixed;
     P.img = h->dImg;
     const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
-    hipLaunchKernelGGL(qc_sweep_mfma32_kernel, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, h->dTot);
+    hipLaunchKernelGGL(qc_sweep_mfma32_kernel, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, h->dTot.p);
     *chunk_out = chunk;
     *n_chunks_out = n_chunks;
     return QC_OK;

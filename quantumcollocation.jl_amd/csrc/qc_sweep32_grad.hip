@@ -7,9 +7,8 @@
 //
 // Launches of one call on such a handle (qc_sweep_grad_launch of qc_sweep_grad.hip routes here):
 //   1. qc_sweep_mfma32_kernel: the forward chunk totals, column-major 32 x 32;
-//   2. qc_sweep32_seed_kernel, one workgroup per sample: the loops and the reduction of qc_sweep_finish_kernel at ld = 32 (the
-//      fidelities carry the bits of qc_sweep_eval on the same handle), x at every chunk end, lambda_{T-1} = dphi/dx by the formulas of
-//      qc_fidelity.hip, then lambda chained down through the transposed totals and stored at every chunk end;
+//   2. qc_sweep32_seed_kernel (qc_sweep_grad.hip: the seed of that file at ld = 32), one workgroup per sample: x at every chunk end, the
+//      fidelities with the bits of qc_sweep_eval on the same handle, lambda at every chunk end;
 //   3. qc_sweep32_grad_kernel, one wavefront per (sample, chunk), walking the chunk backwards.  X[I][J] is the tile of rows 16 I .. and
 //      columns 16 J ..; the state and the adjoint are 32 x <= 16: two tiles each.  "A D-layout tile read as the A operand is its
 //      transpose" holds per tile, so for a D-layout matrix M the A operand (I, K) of M^T is the tile M[K][I] as it stands (an index
@@ -39,17 +38,11 @@ namespace {
 
 using namespace qc_sweep32;
 
-constexpr int kVSeedT = 256;        // threads of the seed workgroup: the thread count of qc_sweep_finish_kernel (same sums, same bits)
-
 struct Grad32Params {
     int n, nc, m, p, zdim, off_a, off_dt, n_int, chunk, n_chunks, nd;   // nd = m + (off_dt >= 0): derivatives per interval
     long long items;             // S * n_chunks
     double dt_fixed;
     const double* img;           // A-layout images, 1024 doubles a matrix: drift, m drives, p perturbations
-};
-
-struct Seed32Params {
-    int n, ns, n_chunks, fid_kind, fid_form, fid_n;
 };
 
 // the sum over the 64 lanes in a fixed order, wave-uniform (as qc_sweep_grad.hip)
@@ -241,95 +234,7 @@ __global__ __launch_bounds__(64 * kWaves) void qc_sweep32_grad_kernel(const Grad
     }
 }
 
-// One workgroup per sample.  Up: x = Q_c ... Q_0 init with the loops of qc_sweep_finish_kernel (ld = 32), x stored at every chunk end;
-// F_s and lambda = dphi/dx at the final state.  Down: lambda <- Q_c^T lambda, stored at every chunk end.  (qc_sweep_seed_kernel of
-// qc_sweep_grad.hip with the leading dimension of the totals 32 instead of 16; that kernel is left as it is.)
-__global__ __launch_bounds__(kVSeedT) void qc_sweep32_seed_kernel(const Seed32Params F, const double* __restrict__ tot, const double* __restrict__ src,
-                                                                  const double* __restrict__ gr, const double* __restrict__ gi,
-                                                                  double* __restrict__ xs, double* __restrict__ ls, double* __restrict__ fids) {
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    __shared__ double red[2][kVSeedT / 64];
-    __shared__ double coef[3];
-    const int tid = threadIdx.x, n = F.n, ns = F.ns, ld = 32, l2 = 1024;
-    const long long s = blockIdx.x;
-    double* cur = sm;
-    double* nxt = sm + ns;
-    double* Q = sm + 2 * ns;
-    for (int idx = tid; idx < ns; idx += kVSeedT) cur[idx] = src[idx];
-    const double* __restrict__ Qs = tot + s * F.n_chunks * (long long)l2;
-    double* __restrict__ xo = xs + s * F.n_chunks * (long long)ns;
-    double* __restrict__ lo = ls + s * F.n_chunks * (long long)ns;
-    for (int c = 0; c < F.n_chunks; ++c) {
-        __syncthreads();
-        for (int idx = tid; idx < l2; idx += kVSeedT) Q[idx] = Qs[(long long)c * l2 + idx];
-        __syncthreads();
-        for (int idx = tid; idx < ns; idx += kVSeedT) {
-            const int r = idx % n, col = idx / n;
-            double acc = 0.0;
-            for (int q = 0; q < n; ++q) acc = fma(Q[r + ld * q], cur[q + n * col], acc);
-            nxt[idx] = acc;
-            xo[(long long)c * ns + idx] = acc;
-        }
-        double* tmp = cur; cur = nxt; nxt = tmp;
-    }
-    __syncthreads();
-    double ar = 0.0, ai = 0.0;
-    for (int i = tid; i < ns; i += kVSeedT) {
-        const double xi = cur[i];
-        ar = fma(gr[i], xi, ar);
-        ai = fma(gi[i], xi, ai);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        ar += __shfl_xor(ar, off, 64);
-        ai += __shfl_xor(ai, off, 64);
-    }
-    if ((tid & 63) == 0) { red[0][tid >> 6] = ar; red[1][tid >> 6] = ai; }
-    __syncthreads();
-    if (tid == 0) {
-        const double tr = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        const double ti = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-        const double nn = (double)F.fid_n;
-        double Fv, fac;      // the mapping and the gradient factor of qc_fidelity_kernel (qc_fidelity.hip)
-        if (F.fid_kind == QC_FID_UNITARY) {
-            if (F.fid_form == QC_FID_FORM_ABS2) { Fv = (tr * tr + ti * ti) / (nn * nn); fac = 2.0 / (nn * nn); }
-            else { Fv = sqrt(tr * tr + ti * ti) / nn; fac = 1.0 / (nn * nn * Fv); }
-        } else { Fv = tr * tr + ti * ti; fac = 2.0; }
-        fids[s] = Fv;
-        coef[0] = tr; coef[1] = ti; coef[2] = fac;
-    }
-    __syncthreads();
-    const double tr = coef[0], ti = coef[1], fac = coef[2];
-    for (int idx = tid; idx < ns; idx += kVSeedT) {
-        const double v = (tr * gr[idx] + ti * gi[idx]) * fac;
-        cur[idx] = v;
-        lo[(long long)(F.n_chunks - 1) * ns + idx] = v;
-    }
-    for (int c = F.n_chunks - 1; c >= 1; --c) {
-        __syncthreads();
-        for (int idx = tid; idx < l2; idx += kVSeedT) Q[idx] = Qs[(long long)c * l2 + idx];
-        __syncthreads();
-        for (int idx = tid; idx < ns; idx += kVSeedT) {
-            const int r = idx % n, col = idx / n;
-            double acc = 0.0;
-            for (int q = 0; q < n; ++q) acc = fma(Q[q + ld * r], cur[q + n * col], acc);
-            nxt[idx] = acc;
-            lo[(long long)(c - 1) * ns + idx] = acc;
-        }
-        double* tmp = cur; cur = nxt; nxt = tmp;
-    }
-}
-
 }  // namespace
-
-void qc_sweep32_launch_seed(qc_sweep* h, int64_t S, int64_t n_chunks, const double* dinit, double* dfids, hipStream_t st) {
-    Seed32Params F;
-    F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
-    F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;
-    const size_t lds = ((size_t)2 * h->ns + 1024) * 8;       // at most 16 state columns: 16 KiB
-    hipLaunchKernelGGL(qc_sweep32_seed_kernel, dim3((unsigned)S), dim3(kVSeedT), lds, st, F, (const double*)h->dTot, dinit, (const double*)h->dgr,
-                       (const double*)h->dgi, h->dXs, h->dLs, dfids);
-}
 
 void qc_sweep32_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,
                             double* gs, hipStream_t st) {
@@ -340,6 +245,6 @@ void qc_sweep32_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const doub
     P.dt_fixed = h->d.dt_fixed;
     P.img = h->dImg;
     const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
-    hipLaunchKernelGGL(qc_sweep32_grad_kernel, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, (const double*)h->dXs,
-                       (const double*)h->dLs, gs);
+    hipLaunchKernelGGL(qc_sweep32_grad_kernel, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, (const double*)h->dXs.p,
+                       (const double*)h->dLs.p, gs);
 }

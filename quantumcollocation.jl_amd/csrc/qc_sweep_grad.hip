@@ -19,7 +19,8 @@
 //
 // Launches of one call:
 //   1. the forward chunk totals: qc_sweep_mfma16_kernel of qc_sweep.hip, unchanged, same chunk rule;
-//   2. qc_sweep_seed_kernel, one workgroup per sample: chains the totals in ascending order exactly as qc_sweep_finish_kernel does (the
+//   2. qc_sweep_seed_kernel (ld = 16; qc_sweep32_seed_kernel, ld = 32, on wide handles: one body, fid_seed<LD>, on the chains of
+//      qc_sweep_seed.h), one workgroup per sample: chains the totals in ascending order exactly as qc_sweep_finish_kernel does (the
 //      fidelities carry the bits of qc_sweep_eval), stores x at every chunk end, F_s, lambda_{T-1} = dphi/dx by the definitions of
 //      qc_fidelity.hip (|t| / n: (t_r g_r + t_i g_i) / (n^2 F), not special-cased at t = 0, as there; |t|^2 forms: 2 (t_r g_r + t_i g_i) / n^2),
 //      then chains the transposed totals back down and stores lambda at every chunk end;
@@ -64,6 +65,7 @@
 
 #include "qc_mfma_common.h"
 #include "qc_sweep_internal.h"
+#include "qc_sweep_seed.h"
 
 namespace {
 
@@ -72,7 +74,7 @@ using namespace qc_mfma;
 constexpr int kGDeg = 8;            // as the forward kernel (kSDeg, kSTh of qc_sweep.hip)
 constexpr double kGTh = 0.125;
 constexpr int kGWaves = 4;          // (sample, chunk) items per workgroup: one wave each, the waves never synchronise
-constexpr int kSeedT = 256;         // threads of the seed workgroup: the thread count of qc_sweep_finish_kernel (same sums, same bits)
+using qc_sweep_seed::kSeedT;        // threads of the seed workgroup
 constexpr int kRedT = 256;
 
 // 1 / k!, k = 0 .. 8: the values of kSInvFact (qc_sweep.hip; a __constant__ table is private to its translation unit)
@@ -345,37 +347,21 @@ __global__ __launch_bounds__(kRedT) void qc_sweep_par_reduce_kernel(long long S,
     else if (gsc) gsc[s * m + (q - p)] = acc;
 }
 
-// One workgroup per sample.  Up: x = Q_c ... Q_0 init with the loops of qc_sweep_finish_kernel, x stored at every chunk end; F_s and
-// lambda = dphi/dx at the final state.  Down: lambda <- Q_c^T lambda, stored at every chunk end.
-__global__ __launch_bounds__(kSeedT) void qc_sweep_seed_kernel(const SeedParams F, const double* __restrict__ tot, const double* __restrict__ src,
-                                                               const double* __restrict__ gr, const double* __restrict__ gi,
-                                                               double* __restrict__ xs, double* __restrict__ ls, double* __restrict__ fids) {
-    extern __shared__ __attribute__((aligned(16))) double sm[];
+// The body of both seed kernels, one workgroup per sample; LD is the leading dimension of the totals.  Up (qc_sweep_seed.h): x at every
+// chunk end; F_s and lambda = dphi/dx at the final state; down: lambda at every chunk end.
+template <int LD>
+__device__ __forceinline__ void fid_seed(const SeedParams F, const double* __restrict__ tot, const double* __restrict__ src,
+                                         const double* __restrict__ gr, const double* __restrict__ gi, double* __restrict__ xs,
+                                         double* __restrict__ ls, double* __restrict__ fids, double* sm) {
     __shared__ double red[2][kSeedT / 64];
     __shared__ double coef[3];
-    const int tid = threadIdx.x, n = F.n, ns = F.ns, ld = 16, l2 = 256;
+    const int tid = threadIdx.x, ns = F.ns;
     const long long s = blockIdx.x;
-    double* cur = sm;
-    double* nxt = sm + ns;
-    double* Q = sm + 2 * ns;
-    for (int idx = tid; idx < ns; idx += kSeedT) cur[idx] = src[idx];
-    const double* __restrict__ Qs = tot + s * F.n_chunks * (long long)l2;
-    double* __restrict__ xo = xs + s * F.n_chunks * (long long)ns;
+    qc_sweep_seed::Lds L(sm, ns);
+    const double* __restrict__ Qs = tot + s * F.n_chunks * (long long)(LD * LD);
     double* __restrict__ lo = ls + s * F.n_chunks * (long long)ns;
-    for (int c = 0; c < F.n_chunks; ++c) {
-        __syncthreads();
-        for (int idx = tid; idx < l2; idx += kSeedT) Q[idx] = Qs[(long long)c * l2 + idx];
-        __syncthreads();
-        for (int idx = tid; idx < ns; idx += kSeedT) {
-            const int r = idx % n, col = idx / n;
-            double acc = 0.0;
-            for (int q = 0; q < n; ++q) acc = fma(Q[r + ld * q], cur[q + n * col], acc);
-            nxt[idx] = acc;
-            xo[(long long)c * ns + idx] = acc;
-        }
-        double* tmp = cur; cur = nxt; nxt = tmp;
-    }
-    __syncthreads();
+    qc_sweep_seed::chain_up<LD>(L, F.n, ns, F.n_chunks, Qs, src, xs + s * F.n_chunks * (long long)ns);
+    double* cur = L.cur;
     double ar = 0.0, ai = 0.0;
     for (int i = tid; i < ns; i += kSeedT) {
         const double xi = cur[i];
@@ -408,19 +394,21 @@ __global__ __launch_bounds__(kSeedT) void qc_sweep_seed_kernel(const SeedParams 
         cur[idx] = v;
         lo[(long long)(F.n_chunks - 1) * ns + idx] = v;
     }
-    for (int c = F.n_chunks - 1; c >= 1; --c) {
-        __syncthreads();
-        for (int idx = tid; idx < l2; idx += kSeedT) Q[idx] = Qs[(long long)c * l2 + idx];
-        __syncthreads();
-        for (int idx = tid; idx < ns; idx += kSeedT) {
-            const int r = idx % n, col = idx / n;
-            double acc = 0.0;
-            for (int q = 0; q < n; ++q) acc = fma(Q[q + ld * r], cur[q + n * col], acc);
-            nxt[idx] = acc;
-            lo[(long long)(c - 1) * ns + idx] = acc;
-        }
-        double* tmp = cur; cur = nxt; nxt = tmp;
-    }
+    qc_sweep_seed::chain_down<LD>(L, F.n, ns, F.n_chunks, Qs, lo, nullptr);
+}
+
+__global__ __launch_bounds__(kSeedT) void qc_sweep_seed_kernel(const SeedParams F, const double* __restrict__ tot, const double* __restrict__ src,
+                                                               const double* __restrict__ gr, const double* __restrict__ gi,
+                                                               double* __restrict__ xs, double* __restrict__ ls, double* __restrict__ fids) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    fid_seed<16>(F, tot, src, gr, gi, xs, ls, fids, sm);
+}
+
+__global__ __launch_bounds__(kSeedT) void qc_sweep32_seed_kernel(const SeedParams F, const double* __restrict__ tot, const double* __restrict__ src,
+                                                                 const double* __restrict__ gr, const double* __restrict__ gi,
+                                                                 double* __restrict__ xs, double* __restrict__ ls, double* __restrict__ fids) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    fid_seed<32>(F, tot, src, gr, gi, xs, ls, fids, sm);
 }
 
 // grad[i] = sum_s w_s dF_s/dZ_i in ascending s for the controls and timesteps of knots 0 .. T-2, +0.0 everywhere else
@@ -461,8 +449,6 @@ __global__ __launch_bounds__(kRedT) void qc_sweep_J_kernel(long long S, const do
     if (tid == 0) *J = part[0];
 }
 
-int gfail(qc_side* h, int code, const std::string& msg) { return qc_sweep_fail(h, code, msg); }
-
 }  // namespace
 
 // The tolerance of the antisymmetry test: max |G + G^T| <= 64 eps max |G| per matrix.  iso generators of exactly Hermitian operators are
@@ -471,12 +457,7 @@ int gfail(qc_side* h, int code, const std::string& msg) { return qc_sweep_fail(h
 // What the gradient and the pullback (qc_sweep_vjp.hip) ask of a descriptor alike: an MFMA form, antisymmetric matrices, at most 16 state columns.
 bool qc_sweep_closed_scope(const qc_sweep_desc* d, std::string* why) {
     const int n = 2 * d->N;
-    if (!qc_sweep_desc_is_mfma(d)) {
-        const int top = d->wide == QC_SWEEP_WIDE ? 32 : 16;      // wide descriptors: "mfma32-sweep" up to 2N = 32 (qc_sweep32_grad.hip)
-        *why = n > top ? "the handle takes the rollout-per-sample form (2N = " + std::to_string(n) + " > " + std::to_string(top) + ")"
-                      : "the handle takes the rollout-per-sample form (" + std::to_string(d->m) + " drives > 8)";
-        return false;
-    }
+    if (!qc_sweep_desc_is_mfma(d)) { *why = qc_sweep_per_sample_why(d); return false; }
     const double* sets[3] = {d->G_drift, d->G_drives, d->G_pert};
     const int counts[3] = {1, d->m, d->n_pert};
     const char* names[3] = {"G_drift", "drive generator", "perturbation generator"};
@@ -510,11 +491,11 @@ bool qc_sweep_grad_scope(const qc_sweep_desc* d, std::string* why) {
 extern "C" int qc_sweep_desc_grad_supported(const qc_sweep_desc* d, int32_t* supported) {
     int rc = qc_sweep_validate_desc(d);
     if (rc) return rc;
-    if (!supported) return gfail(nullptr, QC_ERR_INVALID, "qc_sweep_desc_grad_supported: supported is NULL");
+    if (!supported) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep_desc_grad_supported: supported is NULL");
     std::string why;
     const bool ok = qc_sweep_grad_scope(d, &why);
     *supported = ok ? 1 : 0;
-    if (!ok) (void)gfail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep gradients: " + why);
+    if (!ok) (void)qc_sweep_fail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep gradients: " + why);
     return QC_OK;
 }
 
@@ -537,20 +518,28 @@ void qc_sweep16_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const doub
     do {                                                                                                                                        \
         if (want_par)                                                                                                                           \
             hipLaunchKernelGGL((qc_sweep_grad_kernel<M_, true>), dim3(grid), dim3(64 * kGWaves), 0, st, P, dZ, dtheta, dscale,                    \
-                               (const double*)h->dXs, (const double*)h->dLs, gs, h->dPart);                                                     \
+                               (const double*)h->dXs.p, (const double*)h->dLs.p, gs, h->dPart.p);                                               \
         else                                                                                                                                    \
             hipLaunchKernelGGL((qc_sweep_grad_kernel<M_, false>), dim3(grid), dim3(64 * kGWaves), 0, st, P, dZ, dtheta, dscale,                   \
-                               (const double*)h->dXs, (const double*)h->dLs, gs, (double*)nullptr);                                             \
+                               (const double*)h->dXs.p, (const double*)h->dLs.p, gs, (double*)nullptr);                                         \
     } while (0)
-    if (m <= 1) QC_GRAD_LAUNCH(1);
-    else if (m <= 2) QC_GRAD_LAUNCH(2);
-    else if (m <= 4) QC_GRAD_LAUNCH(4);
-    else if (m <= 6) QC_GRAD_LAUNCH(6);
-    else QC_GRAD_LAUNCH(8);
+    QC_SWEEP_FOR_M(m, QC_GRAD_LAUNCH);
 #undef QC_GRAD_LAUNCH
     if (want_par)
         hipLaunchKernelGGL(qc_sweep_par_reduce_kernel, dim3((unsigned)((S * (p + m) + kRedT - 1) / kRedT)), dim3(kRedT), 0, st, (long long)S,
-                           (int)n_chunks, p, m, (const double*)h->dPart, dgrad_theta, dgrad_scale);
+                           (int)n_chunks, p, m, (const double*)h->dPart.p, dgrad_theta, dgrad_scale);
+}
+
+// the argument checks of all four entry points, in the order of the header
+static int grad_check(qc_sweep* h, const char* who, const double* Z, const double* init, int64_t S, const double* theta, bool any_out, bool g_theta,
+                      bool g_scale) {
+    int rc = qc_sweep_check(h, who, &qc_sweep::grad_ok, "qc_sweep gradients: ", &qc_sweep::grad_why, Z, init, nullptr, S, theta);
+    if (rc) return rc;
+    const std::string pre = std::string(who) + ": ";
+    if (!any_out) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "every output is NULL");
+    if (g_theta && h->d.n_pert == 0) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "grad_theta is given but the handle has no perturbations (n_pert = 0)");
+    if (g_scale && h->d.m == 0) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "grad_scale is given but the handle has no drives (m = 0)");
+    return QC_OK;
 }
 
 // Both device entry points.  Without dgrad_theta / dgrad_scale this is qc_sweep_grad_dev as it always was: the same launches of the same
@@ -558,15 +547,9 @@ void qc_sweep16_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const doub
 static int qc_sweep_grad_launch(qc_sweep* h, const char* who, const double* dZ, const double* dinit, int64_t S, const double* dtheta,
                                 const double* dscale, const double* dweights, double* dfids, double* dJ, double* dgrad, double* dgrad_samples,
                                 double* dgrad_theta, double* dgrad_scale, void* stream) {
-    const std::string pre = std::string(who) + ": ";
-    if (!h) return gfail(nullptr, QC_ERR_INVALID, pre + "NULL handle");
-    if (!h->grad_ok) return gfail(h, QC_ERR_UNSUPPORTED, "qc_sweep gradients: " + h->grad_why);
-    if (!dZ || !dinit) return gfail(h, QC_ERR_INVALID, pre + "NULL input");
-    if (S < 1 || S > (1ll << 24)) return gfail(h, QC_ERR_INVALID, pre + "S must be in 1 .. 2^24");
-    if (h->d.n_pert > 0 && !dtheta) return gfail(h, QC_ERR_INVALID, pre + "theta is NULL but the handle has perturbations");
-    if (!dfids && !dJ && !dgrad && !dgrad_samples && !dgrad_theta && !dgrad_scale) return gfail(h, QC_ERR_INVALID, pre + "every output is NULL");
-    if (dgrad_theta && h->d.n_pert == 0) return gfail(h, QC_ERR_INVALID, pre + "grad_theta is given but the handle has no perturbations (n_pert = 0)");
-    if (dgrad_scale && h->d.m == 0) return gfail(h, QC_ERR_INVALID, pre + "grad_scale is given but the handle has no drives (m = 0)");
+    int rc = grad_check(h, who, dZ, dinit, S, dtheta, dfids || dJ || dgrad || dgrad_samples || dgrad_theta || dgrad_scale, dgrad_theta != nullptr,
+                        dgrad_scale != nullptr);
+    if (rc) return rc;
     std::string& slot = *qc_sweep_err_slot();
     qc_device_guard guard(h->device);
     QC_SIDE_HIP(h, slot, guard.err);
@@ -575,35 +558,33 @@ static int qc_sweep_grad_launch(qc_sweep* h, const char* who, const double* dZ, 
     const int nd = m + (h->d.off_dt >= 0 ? 1 : 0);
     const int64_t n_int = h->d.T - 1;
     int64_t chunk, n_chunks;
-    int rc = qc_sweep_launch_totals(h, dZ, S, dtheta, dscale, st, &chunk, &n_chunks);
+    rc = qc_sweep_launch_totals(h, dZ, S, dtheta, dscale, st, &chunk, &n_chunks);
     if (rc) return rc;
     const size_t n_state = (size_t)S * n_chunks * h->ns;
-    QC_SIDE_HIP(h, slot, h->grow(&h->dXs, &h->capXs, n_state));
-    QC_SIDE_HIP(h, slot, h->grow(&h->dLs, &h->capLs, n_state));
+    QC_SIDE_HIP(h, slot, h->grow(h->dXs, n_state));
+    QC_SIDE_HIP(h, slot, h->grow(h->dLs, n_state));
     if (!dfids) {
-        QC_SIDE_HIP(h, slot, h->grow(&h->dGfid, &h->capGfid, (size_t)S));
-        dfids = h->dGfid;
+        QC_SIDE_HIP(h, slot, h->grow(h->dGfid, (size_t)S));
+        dfids = h->dGfid.p;
     }
     const bool want_par = dgrad_theta || dgrad_scale;
     const bool want_grad = (dgrad || dgrad_samples) && nd > 0;
     double* gsamp = dgrad_samples;
     if (want_grad && !gsamp) {
-        QC_SIDE_HIP(h, slot, h->grow(&h->dGsamp, &h->capGsamp, (size_t)S * n_int * nd));
-        gsamp = h->dGsamp;
+        QC_SIDE_HIP(h, slot, h->grow(h->dGsamp, (size_t)S * n_int * nd));
+        gsamp = h->dGsamp.p;
     }
-    if (want_par) QC_SIDE_HIP(h, slot, h->grow(&h->dPart, &h->capPart, (size_t)S * n_chunks * (p + m)));
-    if (h->mfma32) {      // the 2 x 2-tile form: its own seed and walk (qc_sweep32_grad.hip), then the reductions below
-        qc_sweep32_launch_seed(h, S, n_chunks, dinit, dfids, st);
+    if (want_par) QC_SIDE_HIP(h, slot, h->grow(h->dPart, (size_t)S * n_chunks * (p + m)));
+    SeedParams F;
+    F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
+    F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;
+    const size_t lds = qc_sweep_seed::lds_bytes(h->ns, h->mfma32 ? 32 : 16);      // at most 16 state columns: 16 KiB
+    const auto seed = h->mfma32 ? qc_sweep32_seed_kernel : qc_sweep_seed_kernel;
+    hipLaunchKernelGGL(seed, dim3((unsigned)S), dim3(kSeedT), lds, st, F, (const double*)h->dTot.p, dinit, (const double*)h->dgr,
+                       (const double*)h->dgi, h->dXs.p, h->dLs.p, dfids);
+    if (h->mfma32) {      // the 2 x 2-tile form: its own walk (qc_sweep32_grad.hip), then the reductions below
         if (want_grad) qc_sweep32_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, gsamp, st);
-    } else {
-        SeedParams F;
-        F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
-        F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;
-        const size_t lds = ((size_t)2 * h->ns + 256) * 8;
-        hipLaunchKernelGGL(qc_sweep_seed_kernel, dim3((unsigned)S), dim3(kSeedT), lds, st, F, (const double*)h->dTot, dinit, (const double*)h->dgr,
-                           (const double*)h->dgi, h->dXs, h->dLs, dfids);
-    }
-    if (!h->mfma32 && (want_grad || want_par))
+    } else if (want_grad || want_par)
         qc_sweep16_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);
     if (dgrad) {
         ReduceParams R;
@@ -614,7 +595,7 @@ static int qc_sweep_grad_launch(qc_sweep* h, const char* who, const double* dZ, 
     }
     if (dJ) hipLaunchKernelGGL(qc_sweep_J_kernel, dim3(1), dim3(kRedT), 0, st, (long long)S, (const double*)dfids, dweights, dJ);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return gfail(h, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return qc_sweep_fail(h, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return QC_OK;
 }
 
@@ -627,57 +608,35 @@ extern "C" int qc_sweep_grad_dev(qc_sweep* h, const double* dZ, const double* di
 extern "C" int qc_sweep_grad_params_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
                                         const double* dweights, double* dfids, double* dJ, double* dgrad, double* dgrad_samples,
                                         double* dgrad_theta, double* dgrad_scale, void* stream) {
-    if (h && h->mfma32) return gfail(h, QC_ERR_UNSUPPORTED, "qc_sweep gradients: parameter gradients are not served in the mfma32-sweep form");
+    if (h && h->mfma32) return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, "qc_sweep gradients: parameter gradients are not served in the mfma32-sweep form");
     return qc_sweep_grad_launch(h, "qc_sweep_grad_params_dev", dZ, dinit, S, dtheta, dscale, dweights, dfids, dJ, dgrad, dgrad_samples, dgrad_theta,
                                 dgrad_scale, stream);
 }
 
-// Both host-buffer entry points: stage, call the device entry point on the handle's stream, copy back, synchronise.
+// Both host-buffer entry points: stage, launch on the handle's stream, copy back, synchronise.
 static int qc_sweep_grad_host(qc_sweep* h, const char* who, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
                               const double* weights, double* fids, double* J, double* grad, double* grad_samples, double* grad_theta,
                               double* grad_scale) {
-    const std::string pre = std::string(who) + ": ";
-    if (!h) return gfail(nullptr, QC_ERR_INVALID, pre + "NULL handle");
-    if (!h->grad_ok) return gfail(h, QC_ERR_UNSUPPORTED, "qc_sweep gradients: " + h->grad_why);
-    if (!Z || !init) return gfail(h, QC_ERR_INVALID, pre + "NULL input");
-    if (S < 1 || S > (1ll << 24)) return gfail(h, QC_ERR_INVALID, pre + "S must be in 1 .. 2^24");
-    const int m = h->d.m, p = h->d.n_pert;
-    if (p > 0 && !theta) return gfail(h, QC_ERR_INVALID, pre + "theta is NULL but the handle has perturbations");
-    if (!fids && !J && !grad && !grad_samples && !grad_theta && !grad_scale) return gfail(h, QC_ERR_INVALID, pre + "every output is NULL");
-    if (grad_theta && p == 0) return gfail(h, QC_ERR_INVALID, pre + "grad_theta is given but the handle has no perturbations (n_pert = 0)");
-    if (grad_scale && m == 0) return gfail(h, QC_ERR_INVALID, pre + "grad_scale is given but the handle has no drives (m = 0)");
-    std::string& slot = *qc_sweep_err_slot();
-    qc_device_guard guard(h->device);
-    QC_SIDE_HIP(h, slot, guard.err);
-    const bool use_scale = scale && m > 0;
-    const size_t n_samp = (size_t)S * (size_t)(h->d.T - 1) * (size_t)(m + (h->d.off_dt >= 0 ? 1 : 0));
-    if (p) QC_SIDE_HIP(h, slot, h->grow(&h->sTheta, &h->capTheta, (size_t)S * p));
-    if (use_scale) QC_SIDE_HIP(h, slot, h->grow(&h->sScale, &h->capScale, (size_t)S * m));
-    if (weights) QC_SIDE_HIP(h, slot, h->grow(&h->sW, &h->capW, (size_t)S));
-    if (fids) QC_SIDE_HIP(h, slot, h->grow(&h->sFids, &h->capFids, (size_t)S));
-    if (grad_samples && n_samp) QC_SIDE_HIP(h, slot, h->grow(&h->sGradS, &h->capGradS, n_samp));
-    if (grad_theta) QC_SIDE_HIP(h, slot, h->grow(&h->sGth, &h->capGth, (size_t)S * p));
-    if (grad_scale) QC_SIDE_HIP(h, slot, h->grow(&h->sGsc, &h->capGsc, (size_t)S * m));
-    if (grad && !h->sGrad) QC_SIDE_HIP(h, slot, h->alloc(&h->sGrad, (size_t)h->Zlen));
-    if (J && !h->sJ) QC_SIDE_HIP(h, slot, h->alloc(&h->sJ, (size_t)1));
-    QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sZ, Z, (size_t)h->Zlen * 8, hipMemcpyHostToDevice, h->stream));
-    QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sInit, init, (size_t)h->ns * 8, hipMemcpyHostToDevice, h->stream));
-    if (p) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sTheta, theta, (size_t)S * p * 8, hipMemcpyHostToDevice, h->stream));
-    if (use_scale) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sScale, scale, (size_t)S * m * 8, hipMemcpyHostToDevice, h->stream));
-    if (weights) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sW, weights, (size_t)S * 8, hipMemcpyHostToDevice, h->stream));
-    const bool samp = grad_samples && n_samp;
-    int rc = qc_sweep_grad_launch(h, who, h->sZ, h->sInit, S, p ? h->sTheta : nullptr, use_scale ? h->sScale : nullptr, weights ? h->sW : nullptr,
-                                  fids ? h->sFids : nullptr, J ? h->sJ : nullptr, grad ? h->sGrad : nullptr, samp ? h->sGradS : nullptr,
-                                  grad_theta ? h->sGth : nullptr, grad_scale ? h->sGsc : nullptr, h->stream);
+    int rc = grad_check(h, who, Z, init, S, theta, fids || J || grad || grad_samples || grad_theta || grad_scale, grad_theta != nullptr,
+                        grad_scale != nullptr);
     if (rc) return rc;
-    if (fids) QC_SIDE_HIP(h, slot, hipMemcpyAsync(fids, h->sFids, (size_t)S * 8, hipMemcpyDeviceToHost, h->stream));
-    if (J) QC_SIDE_HIP(h, slot, hipMemcpyAsync(J, h->sJ, 8, hipMemcpyDeviceToHost, h->stream));
-    if (grad) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad, h->sGrad, (size_t)h->Zlen * 8, hipMemcpyDeviceToHost, h->stream));
-    if (samp) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad_samples, h->sGradS, n_samp * 8, hipMemcpyDeviceToHost, h->stream));
-    if (grad_theta) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad_theta, h->sGth, (size_t)S * p * 8, hipMemcpyDeviceToHost, h->stream));
-    if (grad_scale) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad_scale, h->sGsc, (size_t)S * m * 8, hipMemcpyDeviceToHost, h->stream));
-    QC_SIDE_HIP(h, slot, hipStreamSynchronize(h->stream));
-    return QC_OK;
+    const size_t nS = (size_t)S, m = (size_t)h->d.m, p = (size_t)h->d.n_pert, Zlen = (size_t)h->Zlen;
+    const size_t n_samp = nS * (size_t)(h->d.T - 1) * (m + (h->d.off_dt >= 0 ? 1 : 0));
+    qc_stage stage(h, qc_sweep_err_slot());
+    const double* dZ = stage.in(h->sZ, Z, Zlen);
+    const double* dinit = stage.in(h->sInit, init, (size_t)h->ns);
+    const double* dtheta = stage.in(h->sTheta, theta, nS * p);
+    const double* dscale = stage.in(h->sScale, scale, nS * m);
+    const double* dweights = stage.in(h->sW, weights, nS);
+    double* dfids = stage.out(h->sFids, fids, nS);
+    double* dJ = stage.out(h->sJ, J, 1);
+    double* dgrad = stage.out(h->sGrad, grad, Zlen);
+    double* dsamp = stage.out(h->sGradS, grad_samples, n_samp);
+    double* dgth = stage.out(h->sGth, grad_theta, nS * p);
+    double* dgsc = stage.out(h->sGsc, grad_scale, nS * m);
+    if ((rc = stage.status())) return rc;
+    if ((rc = qc_sweep_grad_launch(h, who, dZ, dinit, S, dtheta, dscale, dweights, dfids, dJ, dgrad, dsamp, dgth, dgsc, h->stream))) return rc;
+    return stage.finish();
 }
 
 extern "C" int qc_sweep_grad(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
@@ -688,6 +647,6 @@ extern "C" int qc_sweep_grad(qc_sweep* h, const double* Z, const double* init, i
 extern "C" int qc_sweep_grad_params(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
                                     const double* weights, double* fids, double* J, double* grad, double* grad_samples, double* grad_theta,
                                     double* grad_scale) {
-    if (h && h->mfma32) return gfail(h, QC_ERR_UNSUPPORTED, "qc_sweep gradients: parameter gradients are not served in the mfma32-sweep form");
+    if (h && h->mfma32) return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, "qc_sweep gradients: parameter gradients are not served in the mfma32-sweep form");
     return qc_sweep_grad_host(h, "qc_sweep_grad_params", Z, init, S, theta, scale, weights, fids, J, grad, grad_samples, grad_theta, grad_scale);
 }

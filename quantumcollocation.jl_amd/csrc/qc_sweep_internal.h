@@ -1,6 +1,6 @@
 // What qc_sweep.hip (forward sweep), qc_sweep_grad.hip (its adjoint), qc_sweep_vjp.hip (the pullback of the final states) and
-// qc_sweep_jvp.hip (their pushforward) share: the handle, the descriptor checks and the launch of the forward chunk totals (with it
-// the chunk rule).  Not part of the ABI.
+// qc_sweep_jvp.hip (their pushforward) share: the handle with its scratch and staging buffers, the descriptor and argument checks and
+// the launch of the forward chunk totals (with it the chunk rule).  Not part of the ABI.
 #pragma once
 
 #include <string>
@@ -22,48 +22,57 @@ struct qc_sweep : qc_side {
     double* dG = nullptr;        // (1 + m + p) matrices, column-major (per-sample form)
     double* dImg = nullptr;      // their A-layout images (MFMA form)
     double *dgr = nullptr, *dgi = nullptr;
-    // scratch of the "_dev" entry point, grown at the first call that needs it
-    double* dTot = nullptr;  size_t capTot = 0;
-    double* dFin = nullptr;  size_t capFin = 0;
-    double *dGs = nullptr, *dRE = nullptr, *dRQ = nullptr, *dRS = nullptr, *dRout = nullptr;
-    // staging of the host-buffer entry point
-    double *sZ = nullptr, *sInit = nullptr;
-    double* sTheta = nullptr;  size_t capTheta = 0;
-    double* sScale = nullptr;  size_t capScale = 0;
-    double* sFinals = nullptr; size_t capFinals = 0;
-    double* sFids = nullptr;   size_t capFids = 0;
-    // gradient: states and adjoints at the chunk ends, per-sample derivatives, fidelities; staging of its host-buffer entry point
-    double* dXs = nullptr;   size_t capXs = 0;
-    double* dLs = nullptr;   size_t capLs = 0;
-    double* dGsamp = nullptr; size_t capGsamp = 0;
-    double* dGfid = nullptr; size_t capGfid = 0;
-    double* sW = nullptr;    size_t capW = 0;
-    double* sGradS = nullptr; size_t capGradS = 0;
-    double *sGrad = nullptr, *sJ = nullptr;
-    // parameter gradients: the chunk shares S x n_chunks x (n_pert + m); staging of the host-buffer entry point
-    double* dPart = nullptr; size_t capPart = 0;
-    double* sGth = nullptr;  size_t capGth = 0;
-    double* sGsc = nullptr;  size_t capGsc = 0;
-    // pullback (qc_sweep_vjp.hip): staging of the cotangents and of grad_init in its host-buffer entry point (finals: sFinals above)
-    double* sCot = nullptr;   size_t capCot = 0;
-    double* sGinit = nullptr; size_t capGinit = 0;
-    // pushforward (qc_sweep_jvp.hip): the chunk totals and their tangents, S x n_chunks x 2 tiles; staging of the directions and of the
-    // tangent outputs in its host-buffer entry point (finals, fids: sFinals, sFids above)
-    double* dTotJ = nullptr;  size_t capTotJ = 0;
-    double *sVZ = nullptr, *sVinit = nullptr;
-    double* sVth = nullptr;   size_t capVth = 0;
-    double* sVsc = nullptr;   size_t capVsc = 0;
-    double* sTfin = nullptr;  size_t capTfin = 0;
-    double* sTfid = nullptr;  size_t capTfid = 0;
+    // Scratch of the "_dev" entry points, grown at the first call that needs it.  Largest request of a call, and who makes it:
+    qc_buf dTot;         // chunk totals, S x n_chunks x 256 (mfma32: 1024)                  eval, grad, vjp
+    qc_buf dFin;         // per-sample form: final states, S x ns                             eval
+    double *dGs = nullptr, *dRE = nullptr, *dRQ = nullptr, *dRS = nullptr, *dRout = nullptr;      // per-sample form, sized at create
+    qc_buf dXs, dLs;     // x and lambda at the chunk ends, S x n_chunks x ns each            grad, vjp
+    qc_buf dGsamp;       // per-interval derivatives when the caller keeps none, S x (T-1) x nd   grad, vjp
+    qc_buf dGfid;        // fidelities when the caller keeps none, S                         grad
+    qc_buf dPart;        // chunk shares of the parameter gradients, S x n_chunks x (p + m)  grad_params, vjp
+    qc_buf dTotJ;        // chunk totals and their tangents, S x n_chunks x 512              jvp
+    // Staging of the host-buffer entry points (qc_stage): one buffer per argument, shared by every entry point that has the argument.
+    qc_buf sZ, sInit;    // Zlen, ns: allocated at create                                     every entry
+    qc_buf sTheta;       // S x p                                                             every entry
+    qc_buf sScale;       // S x m                                                             every entry
+    qc_buf sFinals;      // S x ns                                                            eval, vjp, jvp
+    qc_buf sFids;        // S                                                                 eval, grad, jvp
+    qc_buf sW;           // weights, S                                                        grad
+    qc_buf sJ;           // 1                                                                 grad
+    qc_buf sGrad;        // the dense gradient, Zlen                                          grad, vjp
+    qc_buf sGradS;       // per-sample gradients, S x (T-1) x nd                              grad, vjp
+    qc_buf sGth;         // grad_theta, S x p                                                 grad_params, vjp
+    qc_buf sGsc;         // grad_scale, S x m                                                 grad_params, vjp
+    qc_buf sCot;         // cotangents, S x ns                                                vjp
+    qc_buf sGinit;       // grad_init, S x ns                                                 vjp
+    qc_buf sVZ, sVinit;  // directions, Zlen and ns                                           jvp
+    qc_buf sVth, sVsc;   // directions, S x p and S x m                                       jvp
+    qc_buf sTfin, sTfid; // tangents, S x ns and S                                            jvp
 };
 
 // records the message in the handle (when there is one) and in the slot qc_sweep_last_error(NULL) returns
 int qc_sweep_fail(qc_side* h, int code, const std::string& msg);
 std::string* qc_sweep_err_slot();
+// The argument checks every entry point shares, in the order of the tables of qcolloc.h: the NULL handle; the entry's scope
+// (`ok`: the handle's flag, NULL for qc_sweep_eval; refused as `scope` + the handle's reason `why`); NULL Z / init; `missing`, the name
+// of a further input that is NULL (the pullback's "cot"), else NULL; the range of S; theta against n_pert.  The entry's own lines follow.
+int qc_sweep_check(qc_sweep* h, const char* who, const bool qc_sweep::*ok, const char* scope, const std::string qc_sweep::*why, const void* Z,
+                   const void* init, const char* missing, int64_t S, const void* theta);
+// the M of the kernels templated on the drive tiles a wave keeps in registers: LAUNCH(M) for the smallest of 1, 2, 4, 6, 8 that holds m
+#define QC_SWEEP_FOR_M(m, LAUNCH)      \
+    do {                               \
+        if ((m) <= 1) LAUNCH(1);       \
+        else if ((m) <= 2) LAUNCH(2);  \
+        else if ((m) <= 4) LAUNCH(4);  \
+        else if ((m) <= 6) LAUNCH(6);  \
+        else LAUNCH(8);                \
+    } while (0)
 int qc_sweep_validate_desc(const qc_sweep_desc* d);
 bool qc_sweep_desc_is_mfma(const qc_sweep_desc* d);
 // 0: "rollout-per-sample", 1: "mfma16-sweep", 2: "mfma32-sweep" (wide descriptors with 16 < 2N <= 32)
 int qc_sweep_desc_form(const qc_sweep_desc* d);
+// form 0: "the handle takes the rollout-per-sample form (...)" with its cause, the reason of every scope that needs an MFMA form
+std::string qc_sweep_per_sample_why(const qc_sweep_desc* d);
 // the chunk rule of the MFMA forms
 void qc_sweep_chunks(int64_t S, int64_t T, int64_t* chunk, int64_t* n_chunks);
 // "mfma16-sweep" handles: grows h->dTot and launches qc_sweep_mfma16_kernel on `st` (S x n_chunks tiles of 256 doubles)
@@ -74,9 +83,7 @@ int qc_sweep_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const doubl
 void qc_sweep32_image(const double* G, int n, double* img);
 int qc_sweep32_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, hipStream_t st, int64_t* chunk,
                              int64_t* n_chunks);
-// "mfma32-sweep" gradients (qc_sweep32_grad.hip): qc_sweep32_seed_kernel (x and lambda at every chunk end, fidelities) and the backward walk
-// qc_sweep32_grad_kernel (gs: S x (T-1) x nd); scratch is the caller's
-void qc_sweep32_launch_seed(qc_sweep* h, int64_t S, int64_t n_chunks, const double* dinit, double* dfids, hipStream_t st);
+// "mfma32-sweep" gradients (qc_sweep32_grad.hip): the backward walk qc_sweep32_grad_kernel (gs: S x (T-1) x nd); scratch is the caller's
 void qc_sweep32_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,
                             double* gs, hipStream_t st);
 // "mfma16-sweep" handles (qc_sweep_grad.hip): the backward walk qc_sweep_grad_kernel<M, false> (gs: S x (T-1) x nd), or with `par` the

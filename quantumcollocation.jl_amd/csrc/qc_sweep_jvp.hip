@@ -30,7 +30,7 @@
 // qc_sweep_eval on the same handle.  A NULL direction is read as zeros through the same arithmetic: NULL and an explicit zero array
 // give the same bits.  No atomics, sums in a fixed order: repeated calls return the same bits, and no output's bits depend on which
 // others were asked for.  Its dynamic LDS is 4 ns + 512 doubles (x, its successor, their tangents, one chunk total and its tangent);
-// ns = 2N x state_cols reaches 4096 entries (sweep_validate), which is 135168 bytes = 132 KiB of the 160 KiB of a CU.  Above 64 KiB
+// ns = 2N x state_cols reaches 4096 entries (qc_sweep_validate_desc), which is 135168 bytes = 132 KiB of the 160 KiB of a CU.  Above 64 KiB
 // (ns > 1920) the launch opts in with hipFuncSetAttribute; an MI355X accepts it up to ns = 4096 (tests/test_sweep_many_columns.py).
 //
 // gfx950 cross-compile: see the table in DESIGN.md ("Sweep pushforwards"); no private segment, no spills in any instantiation.
@@ -320,23 +320,18 @@ __global__ __launch_bounds__(kFinT) void qc_sweep_jvp_finish_kernel(const JvpFin
     }
 }
 
-int jfail(qc_side* h, int code, const std::string& msg) { return qc_sweep_fail(h, code, msg); }
-
 // the argument checks both entry points share, in the order of the header's table
 int jvp_check(qc_sweep* h, const char* who, const void* Z, const void* init, int64_t S, const void* theta, bool any_dir, bool any_out, bool v_theta,
               bool v_scale, bool any_fid) {
+    int rc = qc_sweep_check(h, who, &qc_sweep::jvp_ok, "qc_sweep pushforward: ", &qc_sweep::jvp_why, Z, init, nullptr, S, theta);
+    if (rc) return rc;
     const std::string pre = std::string(who) + ": ";
-    if (!h) return jfail(nullptr, QC_ERR_INVALID, pre + "NULL handle");
-    if (!h->jvp_ok) return jfail(h, QC_ERR_UNSUPPORTED, "qc_sweep pushforward: " + h->jvp_why);
-    if (!Z || !init) return jfail(h, QC_ERR_INVALID, pre + "NULL input");
-    if (S < 1 || S > (1ll << 24)) return jfail(h, QC_ERR_INVALID, pre + "S must be in 1 .. 2^24");
-    if (h->d.n_pert > 0 && !theta) return jfail(h, QC_ERR_INVALID, pre + "theta is NULL but the handle has perturbations");
-    if (!any_dir) return jfail(h, QC_ERR_INVALID, pre + "every direction is NULL");
-    if (!any_out) return jfail(h, QC_ERR_INVALID, pre + "every output is NULL");
-    if (v_theta && h->d.n_pert == 0) return jfail(h, QC_ERR_INVALID, pre + "vtheta is given but the handle has no perturbations (n_pert = 0)");
-    if (v_scale && h->d.m == 0) return jfail(h, QC_ERR_INVALID, pre + "vscale is given but the handle has no drives (m = 0)");
+    if (!any_dir) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "every direction is NULL");
+    if (!any_out) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "every output is NULL");
+    if (v_theta && h->d.n_pert == 0) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "vtheta is given but the handle has no perturbations (n_pert = 0)");
+    if (v_scale && h->d.m == 0) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "vscale is given but the handle has no drives (m = 0)");
     if (any_fid && h->d.fid_kind == QC_SWEEP_FID_NONE)
-        return jfail(h, QC_ERR_INVALID, pre + "fidelities or their tangents requested from a handle created without one");
+        return qc_sweep_fail(h, QC_ERR_INVALID, pre + "fidelities or their tangents requested from a handle created without one");
     return QC_OK;
 }
 
@@ -346,20 +341,18 @@ bool qc_sweep_jvp_scope(const qc_sweep_desc* d, std::string* why) {
     const int form = qc_sweep_desc_form(d);
     if (form == 1) return true;
     if (form == 2) { *why = "pushforwards are not served in the mfma32-sweep form"; return false; }
-    const int n = 2 * d->N, top = d->wide == QC_SWEEP_WIDE ? 32 : 16;
-    *why = n > top ? "the handle takes the rollout-per-sample form (2N = " + std::to_string(n) + " > " + std::to_string(top) + ")"
-                   : "the handle takes the rollout-per-sample form (" + std::to_string(d->m) + " drives > 8)";
+    *why = qc_sweep_per_sample_why(d);
     return false;
 }
 
 extern "C" int qc_sweep_desc_jvp_supported(const qc_sweep_desc* d, int32_t* supported) {
     int rc = qc_sweep_validate_desc(d);
     if (rc) return rc;
-    if (!supported) return jfail(nullptr, QC_ERR_INVALID, "qc_sweep_desc_jvp_supported: supported is NULL");
+    if (!supported) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep_desc_jvp_supported: supported is NULL");
     std::string why;
     const bool ok = qc_sweep_jvp_scope(d, &why);
     *supported = ok ? 1 : 0;
-    if (!ok) (void)jfail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep pushforward: " + why);
+    if (!ok) (void)qc_sweep_fail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep pushforward: " + why);
     return QC_OK;
 }
 
@@ -376,7 +369,7 @@ static int qc_sweep_jvp_launch(qc_sweep* h, const char* who, const double* dZ, c
     const int m = h->d.m;
     int64_t chunk, n_chunks;
     qc_sweep_chunks(S, h->d.T, &chunk, &n_chunks);
-    QC_SIDE_HIP(h, slot, h->grow(&h->dTotJ, &h->capTotJ, (size_t)S * n_chunks * 512));
+    QC_SIDE_HIP(h, slot, h->grow(h->dTotJ, (size_t)S * n_chunks * 512));
     JvpParams P;
     P.n = h->n; P.nc = h->nc; P.m = m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
     P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks;
@@ -385,12 +378,8 @@ static int qc_sweep_jvp_launch(qc_sweep* h, const char* who, const double* dZ, c
     P.img = h->dImg;
     const unsigned grid = (unsigned)((P.items + kSWaves - 1) / kSWaves);
 #define QC_JVP_LAUNCH(M_) \
-    hipLaunchKernelGGL(qc_sweep_jvp_kernel<M_>, dim3(grid), dim3(64 * kSWaves), 0, st, P, dZ, dtheta, dscale, dvZ, dvtheta, dvscale, h->dTotJ)
-    if (m <= 1) QC_JVP_LAUNCH(1);
-    else if (m <= 2) QC_JVP_LAUNCH(2);
-    else if (m <= 4) QC_JVP_LAUNCH(4);
-    else if (m <= 6) QC_JVP_LAUNCH(6);
-    else QC_JVP_LAUNCH(8);
+    hipLaunchKernelGGL(qc_sweep_jvp_kernel<M_>, dim3(grid), dim3(64 * kSWaves), 0, st, P, dZ, dtheta, dscale, dvZ, dvtheta, dvscale, h->dTotJ.p)
+    QC_SWEEP_FOR_M(m, QC_JVP_LAUNCH);
 #undef QC_JVP_LAUNCH
     JvpFinParams F;
     F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
@@ -398,10 +387,10 @@ static int qc_sweep_jvp_launch(qc_sweep* h, const char* who, const double* dZ, c
     const size_t lds = ((size_t)4 * h->ns + 512) * 8;      // at most 4096 state entries: 132 KiB of the 160
     if (lds > 64 * 1024)
         QC_SIDE_HIP(h, slot, hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep_jvp_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(qc_sweep_jvp_finish_kernel, dim3((unsigned)S), dim3(kFinT), lds, st, F, (const double*)h->dTotJ, dinit, dvinit,
+    hipLaunchKernelGGL(qc_sweep_jvp_finish_kernel, dim3((unsigned)S), dim3(kFinT), lds, st, F, (const double*)h->dTotJ.p, dinit, dvinit,
                        (const double*)h->dgr, (const double*)h->dgi, dfinals, dfids, dtfinals, dtfids);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return jfail(h, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return qc_sweep_fail(h, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return QC_OK;
 }
 
@@ -412,7 +401,7 @@ extern "C" int qc_sweep_jvp_dev(qc_sweep* h, const double* dZ, const double* din
                                stream);
 }
 
-// The host-buffer entry point: stage, call the device entry point on the handle's stream, copy back, synchronise.
+// The host-buffer entry point: stage, launch on the handle's stream, copy back, synchronise.
 extern "C" int qc_sweep_jvp(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale, const double* vZ,
                             const double* vinit, const double* vtheta, const double* vscale, double* finals, double* fids, double* tfinals,
                             double* tfids) {
@@ -420,38 +409,22 @@ extern "C" int qc_sweep_jvp(qc_sweep* h, const double* Z, const double* init, in
     int rc = jvp_check(h, who, Z, init, S, theta, vZ || vinit || vtheta || vscale, finals || fids || tfinals || tfids, vtheta != nullptr,
                        vscale != nullptr, fids || tfids);
     if (rc) return rc;
-    std::string& slot = *qc_sweep_err_slot();
-    qc_device_guard guard(h->device);
-    QC_SIDE_HIP(h, slot, guard.err);
-    const int m = h->d.m, p = h->d.n_pert;
-    const bool use_scale = scale && m > 0;
-    const size_t n_fin = (size_t)S * h->ns;
-    if (p) QC_SIDE_HIP(h, slot, h->grow(&h->sTheta, &h->capTheta, (size_t)S * p));
-    if (use_scale) QC_SIDE_HIP(h, slot, h->grow(&h->sScale, &h->capScale, (size_t)S * m));
-    if (vZ && !h->sVZ) QC_SIDE_HIP(h, slot, h->alloc(&h->sVZ, (size_t)h->Zlen));
-    if (vinit && !h->sVinit) QC_SIDE_HIP(h, slot, h->alloc(&h->sVinit, (size_t)h->ns));
-    if (vtheta) QC_SIDE_HIP(h, slot, h->grow(&h->sVth, &h->capVth, (size_t)S * p));
-    if (vscale) QC_SIDE_HIP(h, slot, h->grow(&h->sVsc, &h->capVsc, (size_t)S * m));
-    if (finals) QC_SIDE_HIP(h, slot, h->grow(&h->sFinals, &h->capFinals, n_fin));
-    if (fids) QC_SIDE_HIP(h, slot, h->grow(&h->sFids, &h->capFids, (size_t)S));
-    if (tfinals) QC_SIDE_HIP(h, slot, h->grow(&h->sTfin, &h->capTfin, n_fin));
-    if (tfids) QC_SIDE_HIP(h, slot, h->grow(&h->sTfid, &h->capTfid, (size_t)S));
-    QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sZ, Z, (size_t)h->Zlen * 8, hipMemcpyHostToDevice, h->stream));
-    QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sInit, init, (size_t)h->ns * 8, hipMemcpyHostToDevice, h->stream));
-    if (p) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sTheta, theta, (size_t)S * p * 8, hipMemcpyHostToDevice, h->stream));
-    if (use_scale) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sScale, scale, (size_t)S * m * 8, hipMemcpyHostToDevice, h->stream));
-    if (vZ) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sVZ, vZ, (size_t)h->Zlen * 8, hipMemcpyHostToDevice, h->stream));
-    if (vinit) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sVinit, vinit, (size_t)h->ns * 8, hipMemcpyHostToDevice, h->stream));
-    if (vtheta) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sVth, vtheta, (size_t)S * p * 8, hipMemcpyHostToDevice, h->stream));
-    if (vscale) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sVsc, vscale, (size_t)S * m * 8, hipMemcpyHostToDevice, h->stream));
-    rc = qc_sweep_jvp_launch(h, who, h->sZ, h->sInit, S, p ? h->sTheta : nullptr, use_scale ? h->sScale : nullptr, vZ ? h->sVZ : nullptr,
-                             vinit ? h->sVinit : nullptr, vtheta ? h->sVth : nullptr, vscale ? h->sVsc : nullptr, finals ? h->sFinals : nullptr,
-                             fids ? h->sFids : nullptr, tfinals ? h->sTfin : nullptr, tfids ? h->sTfid : nullptr, h->stream);
-    if (rc) return rc;
-    if (finals) QC_SIDE_HIP(h, slot, hipMemcpyAsync(finals, h->sFinals, n_fin * 8, hipMemcpyDeviceToHost, h->stream));
-    if (fids) QC_SIDE_HIP(h, slot, hipMemcpyAsync(fids, h->sFids, (size_t)S * 8, hipMemcpyDeviceToHost, h->stream));
-    if (tfinals) QC_SIDE_HIP(h, slot, hipMemcpyAsync(tfinals, h->sTfin, n_fin * 8, hipMemcpyDeviceToHost, h->stream));
-    if (tfids) QC_SIDE_HIP(h, slot, hipMemcpyAsync(tfids, h->sTfid, (size_t)S * 8, hipMemcpyDeviceToHost, h->stream));
-    QC_SIDE_HIP(h, slot, hipStreamSynchronize(h->stream));
-    return QC_OK;
+    const size_t nS = (size_t)S, m = (size_t)h->d.m, p = (size_t)h->d.n_pert, ns = (size_t)h->ns, Zlen = (size_t)h->Zlen;
+    qc_stage stage(h, qc_sweep_err_slot());
+    const double* dZ = stage.in(h->sZ, Z, Zlen);
+    const double* dinit = stage.in(h->sInit, init, ns);
+    const double* dtheta = stage.in(h->sTheta, theta, nS * p);
+    const double* dscale = stage.in(h->sScale, scale, nS * m);
+    const double* dvZ = stage.in(h->sVZ, vZ, Zlen);
+    const double* dvinit = stage.in(h->sVinit, vinit, ns);
+    const double* dvtheta = stage.in(h->sVth, vtheta, nS * p);
+    const double* dvscale = stage.in(h->sVsc, vscale, nS * m);
+    double* dfinals = stage.out(h->sFinals, finals, nS * ns);
+    double* dfids = stage.out(h->sFids, fids, nS);
+    double* dtfinals = stage.out(h->sTfin, tfinals, nS * ns);
+    double* dtfids = stage.out(h->sTfid, tfids, nS);
+    if ((rc = stage.status())) return rc;
+    if ((rc = qc_sweep_jvp_launch(h, who, dZ, dinit, S, dtheta, dscale, dvZ, dvinit, dvtheta, dvscale, dfinals, dfids, dtfinals, dtfids, h->stream)))
+        return rc;
+    return stage.finish();
 }

@@ -26,10 +26,11 @@
 #include <string>
 
 #include "qc_sweep_internal.h"
+#include "qc_sweep_seed.h"
 
 namespace {
 
-constexpr int kCotT = 256;        // threads of the seed workgroup: the thread count of qc_sweep_finish_kernel (same sums, same bits)
+constexpr int kCotT = qc_sweep_seed::kSeedT;      // threads of the seed workgroup
 constexpr int kSumT = 256;
 
 struct CotParams {
@@ -41,57 +42,26 @@ struct SumParams {
     long long T, Zlen, S;
 };
 
-// The body of both seed kernels; LD is the leading dimension of the totals.  LDS: cur, nxt (ns each) and one total (LD x LD).
+// The body of both seed kernels, on the chains of qc_sweep_seed.h; LD is the leading dimension of the totals.
 template <int LD>
 __device__ __forceinline__ void cot_seed(const CotParams F, const double* __restrict__ tot, const double* __restrict__ src,
                                          const double* __restrict__ cot, double* __restrict__ xs, double* __restrict__ ls,
                                          double* __restrict__ finals, double* __restrict__ ginit, double* sm) {
-    constexpr int ld = LD, l2 = LD * LD;
-    const int tid = threadIdx.x, n = F.n, ns = F.ns;
+    const int tid = threadIdx.x, ns = F.ns;
     const long long s = blockIdx.x;
-    double* cur = sm;
-    double* nxt = sm + ns;
-    double* Q = sm + 2 * ns;
-    for (int idx = tid; idx < ns; idx += kCotT) cur[idx] = src[idx];
-    const double* __restrict__ Qs = tot + s * F.n_chunks * (long long)l2;
-    double* __restrict__ xo = xs + s * F.n_chunks * (long long)ns;
+    qc_sweep_seed::Lds L(sm, ns);
+    const double* __restrict__ Qs = tot + s * F.n_chunks * (long long)(LD * LD);
     double* __restrict__ lo = ls + s * F.n_chunks * (long long)ns;
-    for (int c = 0; c < F.n_chunks; ++c) {
-        __syncthreads();
-        for (int idx = tid; idx < l2; idx += kCotT) Q[idx] = Qs[(long long)c * l2 + idx];
-        __syncthreads();
-        for (int idx = tid; idx < ns; idx += kCotT) {
-            const int r = idx % n, col = idx / n;
-            double acc = 0.0;
-            for (int q = 0; q < n; ++q) acc = fma(Q[r + ld * q], cur[q + n * col], acc);
-            nxt[idx] = acc;
-            xo[(long long)c * ns + idx] = acc;
-        }
-        double* tmp = cur; cur = nxt; nxt = tmp;
-    }
-    __syncthreads();
+    qc_sweep_seed::chain_up<LD>(L, F.n, ns, F.n_chunks, Qs, src, xs + s * F.n_chunks * (long long)ns);
     if (finals)
-        for (int idx = tid; idx < ns; idx += kCotT) finals[s * ns + idx] = cur[idx];
+        for (int idx = tid; idx < ns; idx += kCotT) finals[s * ns + idx] = L.cur[idx];
     // lambda at the final knot: the caller's cotangent
     for (int idx = tid; idx < ns; idx += kCotT) {
         const double v = cot[s * ns + idx];
-        cur[idx] = v;
+        L.cur[idx] = v;
         lo[(long long)(F.n_chunks - 1) * ns + idx] = v;
     }
-    for (int c = F.n_chunks - 1; c >= (ginit ? 0 : 1); --c) {
-        __syncthreads();
-        for (int idx = tid; idx < l2; idx += kCotT) Q[idx] = Qs[(long long)c * l2 + idx];
-        __syncthreads();
-        for (int idx = tid; idx < ns; idx += kCotT) {
-            const int r = idx % n, col = idx / n;
-            double acc = 0.0;
-            for (int q = 0; q < n; ++q) acc = fma(Q[q + ld * r], cur[q + n * col], acc);
-            nxt[idx] = acc;
-            if (c > 0) lo[(long long)(c - 1) * ns + idx] = acc;
-            else ginit[s * ns + idx] = acc;          // lambda_0 = Q_0^T lambda_{end of chunk 0}
-        }
-        double* tmp = cur; cur = nxt; nxt = tmp;
-    }
+    qc_sweep_seed::chain_down<LD>(L, F.n, ns, F.n_chunks, Qs, lo, ginit ? ginit + s * ns : nullptr);
 }
 
 __global__ __launch_bounds__(kCotT) void qc_sweep_cot_seed_kernel(const CotParams F, const double* __restrict__ tot, const double* __restrict__ src,
@@ -128,24 +98,18 @@ __global__ __launch_bounds__(kSumT) void qc_sweep_vjp_reduce_kernel(const SumPar
     grad[i] = acc;
 }
 
-int vfail(qc_side* h, int code, const std::string& msg) { return qc_sweep_fail(h, code, msg); }
-
 const char* const kNoWidePar = "qc_sweep pullback: parameter cotangents are not served in the mfma32-sweep form";
 
 // the argument checks both entry points share, in the order of the header's table
 int vjp_check(qc_sweep* h, const char* who, const void* Z, const void* init, int64_t S, const void* theta, const void* cot, bool any_out,
               bool g_theta, bool g_scale) {
+    int rc = qc_sweep_check(h, who, &qc_sweep::vjp_ok, "qc_sweep pullback: ", &qc_sweep::vjp_why, Z, init, cot ? nullptr : "cot", S, theta);
+    if (rc) return rc;
     const std::string pre = std::string(who) + ": ";
-    if (!h) return vfail(nullptr, QC_ERR_INVALID, pre + "NULL handle");
-    if (!h->vjp_ok) return vfail(h, QC_ERR_UNSUPPORTED, "qc_sweep pullback: " + h->vjp_why);
-    if (!Z || !init) return vfail(h, QC_ERR_INVALID, pre + "NULL input");
-    if (!cot) return vfail(h, QC_ERR_INVALID, pre + "cot is NULL");
-    if (S < 1 || S > (1ll << 24)) return vfail(h, QC_ERR_INVALID, pre + "S must be in 1 .. 2^24");
-    if (h->d.n_pert > 0 && !theta) return vfail(h, QC_ERR_INVALID, pre + "theta is NULL but the handle has perturbations");
-    if (!any_out) return vfail(h, QC_ERR_INVALID, pre + "every output is NULL");
-    if (g_theta && h->d.n_pert == 0) return vfail(h, QC_ERR_INVALID, pre + "grad_theta is given but the handle has no perturbations (n_pert = 0)");
-    if (g_scale && h->d.m == 0) return vfail(h, QC_ERR_INVALID, pre + "grad_scale is given but the handle has no drives (m = 0)");
-    if ((g_theta || g_scale) && h->mfma32) return vfail(h, QC_ERR_UNSUPPORTED, kNoWidePar);
+    if (!any_out) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "every output is NULL");
+    if (g_theta && h->d.n_pert == 0) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "grad_theta is given but the handle has no perturbations (n_pert = 0)");
+    if (g_scale && h->d.m == 0) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "grad_scale is given but the handle has no drives (m = 0)");
+    if ((g_theta || g_scale) && h->mfma32) return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, kNoWidePar);
     return QC_OK;
 }
 
@@ -156,11 +120,11 @@ bool qc_sweep_vjp_scope(const qc_sweep_desc* d, std::string* why) { return qc_sw
 extern "C" int qc_sweep_desc_vjp_supported(const qc_sweep_desc* d, int32_t* supported) {
     int rc = qc_sweep_validate_desc(d);
     if (rc) return rc;
-    if (!supported) return vfail(nullptr, QC_ERR_INVALID, "qc_sweep_desc_vjp_supported: supported is NULL");
+    if (!supported) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep_desc_vjp_supported: supported is NULL");
     std::string why;
     const bool ok = qc_sweep_vjp_scope(d, &why);
     *supported = ok ? 1 : 0;
-    if (!ok) (void)vfail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep pullback: " + why);
+    if (!ok) (void)qc_sweep_fail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep pullback: " + why);
     return QC_OK;
 }
 
@@ -181,30 +145,26 @@ static int qc_sweep_vjp_launch(qc_sweep* h, const char* who, const double* dZ, c
     rc = qc_sweep_launch_totals(h, dZ, S, dtheta, dscale, st, &chunk, &n_chunks);
     if (rc) return rc;
     const size_t n_state = (size_t)S * n_chunks * h->ns;
-    QC_SIDE_HIP(h, slot, h->grow(&h->dXs, &h->capXs, n_state));
-    QC_SIDE_HIP(h, slot, h->grow(&h->dLs, &h->capLs, n_state));
+    QC_SIDE_HIP(h, slot, h->grow(h->dXs, n_state));
+    QC_SIDE_HIP(h, slot, h->grow(h->dLs, n_state));
     const bool want_par = dgrad_theta || dgrad_scale;
     const bool want_grad = (dgrad || dgrad_samples) && nd > 0;
     double* gsamp = dgrad_samples;
     if (want_grad && !gsamp) {
-        QC_SIDE_HIP(h, slot, h->grow(&h->dGsamp, &h->capGsamp, (size_t)S * n_int * nd));
-        gsamp = h->dGsamp;
+        QC_SIDE_HIP(h, slot, h->grow(h->dGsamp, (size_t)S * n_int * nd));
+        gsamp = h->dGsamp.p;
     }
-    if (want_par) QC_SIDE_HIP(h, slot, h->grow(&h->dPart, &h->capPart, (size_t)S * n_chunks * (p + m)));
+    if (want_par) QC_SIDE_HIP(h, slot, h->grow(h->dPart, (size_t)S * n_chunks * (p + m)));
     CotParams F;
     F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
+    const size_t lds = qc_sweep_seed::lds_bytes(h->ns, h->mfma32 ? 32 : 16);      // at most 16 state columns: 16 KiB
+    const auto seed = h->mfma32 ? qc_sweep32_cot_seed_kernel : qc_sweep_cot_seed_kernel;
+    hipLaunchKernelGGL(seed, dim3((unsigned)S), dim3(kCotT), lds, st, F, (const double*)h->dTot.p, dinit, dcot, h->dXs.p, h->dLs.p, dfinals,
+                       dgrad_init);
     if (h->mfma32) {
-        const size_t lds = ((size_t)2 * h->ns + 1024) * 8;       // at most 16 state columns: 16 KiB
-        hipLaunchKernelGGL(qc_sweep32_cot_seed_kernel, dim3((unsigned)S), dim3(kCotT), lds, st, F, (const double*)h->dTot, dinit, dcot, h->dXs, h->dLs,
-                           dfinals, dgrad_init);
         if (want_grad) qc_sweep32_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, gsamp, st);
-    } else {
-        const size_t lds = ((size_t)2 * h->ns + 256) * 8;
-        hipLaunchKernelGGL(qc_sweep_cot_seed_kernel, dim3((unsigned)S), dim3(kCotT), lds, st, F, (const double*)h->dTot, dinit, dcot, h->dXs, h->dLs,
-                           dfinals, dgrad_init);
-        if (want_grad || want_par)
-            qc_sweep16_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);
-    }
+    } else if (want_grad || want_par)
+        qc_sweep16_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);
     if (dgrad) {
         SumParams R;
         R.zdim = h->d.zdim; R.off_a = h->d.off_a; R.off_dt = h->d.off_dt; R.m = m; R.nd = nd;
@@ -212,7 +172,7 @@ static int qc_sweep_vjp_launch(qc_sweep* h, const char* who, const double* dZ, c
         hipLaunchKernelGGL(qc_sweep_vjp_reduce_kernel, dim3((unsigned)((h->Zlen + kSumT - 1) / kSumT)), dim3(kSumT), 0, st, R, (const double*)gsamp, dgrad);
     }
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return vfail(h, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return qc_sweep_fail(h, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return QC_OK;
 }
 
@@ -223,7 +183,7 @@ extern "C" int qc_sweep_vjp_dev(qc_sweep* h, const double* dZ, const double* din
                                dgrad_scale, stream);
 }
 
-// The host-buffer entry point: stage, call the device entry point on the handle's stream, copy back, synchronise.
+// The host-buffer entry point: stage, launch on the handle's stream, copy back, synchronise.
 extern "C" int qc_sweep_vjp(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
                             const double* cot, double* finals, double* grad, double* grad_samples, double* grad_init, double* grad_theta,
                             double* grad_scale) {
@@ -231,38 +191,21 @@ extern "C" int qc_sweep_vjp(qc_sweep* h, const double* Z, const double* init, in
     const bool any_out = finals || grad || grad_samples || grad_init || grad_theta || grad_scale;
     int rc = vjp_check(h, who, Z, init, S, theta, cot, any_out, grad_theta != nullptr, grad_scale != nullptr);
     if (rc) return rc;
-    std::string& slot = *qc_sweep_err_slot();
-    qc_device_guard guard(h->device);
-    QC_SIDE_HIP(h, slot, guard.err);
-    const int m = h->d.m, p = h->d.n_pert;
-    const bool use_scale = scale && m > 0;
-    const size_t n_fin = (size_t)S * h->ns;
-    const size_t n_samp = (size_t)S * (size_t)(h->d.T - 1) * (size_t)(m + (h->d.off_dt >= 0 ? 1 : 0));
-    if (p) QC_SIDE_HIP(h, slot, h->grow(&h->sTheta, &h->capTheta, (size_t)S * p));
-    if (use_scale) QC_SIDE_HIP(h, slot, h->grow(&h->sScale, &h->capScale, (size_t)S * m));
-    QC_SIDE_HIP(h, slot, h->grow(&h->sCot, &h->capCot, n_fin));
-    if (finals) QC_SIDE_HIP(h, slot, h->grow(&h->sFinals, &h->capFinals, n_fin));
-    if (grad_init) QC_SIDE_HIP(h, slot, h->grow(&h->sGinit, &h->capGinit, n_fin));
-    if (grad_samples && n_samp) QC_SIDE_HIP(h, slot, h->grow(&h->sGradS, &h->capGradS, n_samp));
-    if (grad_theta) QC_SIDE_HIP(h, slot, h->grow(&h->sGth, &h->capGth, (size_t)S * p));
-    if (grad_scale) QC_SIDE_HIP(h, slot, h->grow(&h->sGsc, &h->capGsc, (size_t)S * m));
-    if (grad && !h->sGrad) QC_SIDE_HIP(h, slot, h->alloc(&h->sGrad, (size_t)h->Zlen));
-    QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sZ, Z, (size_t)h->Zlen * 8, hipMemcpyHostToDevice, h->stream));
-    QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sInit, init, (size_t)h->ns * 8, hipMemcpyHostToDevice, h->stream));
-    if (p) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sTheta, theta, (size_t)S * p * 8, hipMemcpyHostToDevice, h->stream));
-    if (use_scale) QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sScale, scale, (size_t)S * m * 8, hipMemcpyHostToDevice, h->stream));
-    QC_SIDE_HIP(h, slot, hipMemcpyAsync(h->sCot, cot, n_fin * 8, hipMemcpyHostToDevice, h->stream));
-    const bool samp = grad_samples && n_samp;
-    rc = qc_sweep_vjp_launch(h, who, h->sZ, h->sInit, S, p ? h->sTheta : nullptr, use_scale ? h->sScale : nullptr, h->sCot,
-                             finals ? h->sFinals : nullptr, grad ? h->sGrad : nullptr, samp ? h->sGradS : nullptr, grad_init ? h->sGinit : nullptr,
-                             grad_theta ? h->sGth : nullptr, grad_scale ? h->sGsc : nullptr, h->stream);
-    if (rc) return rc;
-    if (finals) QC_SIDE_HIP(h, slot, hipMemcpyAsync(finals, h->sFinals, n_fin * 8, hipMemcpyDeviceToHost, h->stream));
-    if (grad) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad, h->sGrad, (size_t)h->Zlen * 8, hipMemcpyDeviceToHost, h->stream));
-    if (samp) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad_samples, h->sGradS, n_samp * 8, hipMemcpyDeviceToHost, h->stream));
-    if (grad_init) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad_init, h->sGinit, n_fin * 8, hipMemcpyDeviceToHost, h->stream));
-    if (grad_theta) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad_theta, h->sGth, (size_t)S * p * 8, hipMemcpyDeviceToHost, h->stream));
-    if (grad_scale) QC_SIDE_HIP(h, slot, hipMemcpyAsync(grad_scale, h->sGsc, (size_t)S * m * 8, hipMemcpyDeviceToHost, h->stream));
-    QC_SIDE_HIP(h, slot, hipStreamSynchronize(h->stream));
-    return QC_OK;
+    const size_t nS = (size_t)S, m = (size_t)h->d.m, p = (size_t)h->d.n_pert, n_fin = nS * (size_t)h->ns, Zlen = (size_t)h->Zlen;
+    const size_t n_samp = nS * (size_t)(h->d.T - 1) * (m + (h->d.off_dt >= 0 ? 1 : 0));
+    qc_stage stage(h, qc_sweep_err_slot());
+    const double* dZ = stage.in(h->sZ, Z, Zlen);
+    const double* dinit = stage.in(h->sInit, init, (size_t)h->ns);
+    const double* dtheta = stage.in(h->sTheta, theta, nS * p);
+    const double* dscale = stage.in(h->sScale, scale, nS * m);
+    const double* dcot = stage.in(h->sCot, cot, n_fin);
+    double* dfinals = stage.out(h->sFinals, finals, n_fin);
+    double* dgrad = stage.out(h->sGrad, grad, Zlen);
+    double* dsamp = stage.out(h->sGradS, grad_samples, n_samp);
+    double* dginit = stage.out(h->sGinit, grad_init, n_fin);
+    double* dgth = stage.out(h->sGth, grad_theta, nS * p);
+    double* dgsc = stage.out(h->sGsc, grad_scale, nS * m);
+    if ((rc = stage.status())) return rc;
+    if ((rc = qc_sweep_vjp_launch(h, who, dZ, dinit, S, dtheta, dscale, dcot, dfinals, dgrad, dsamp, dginit, dgth, dgsc, h->stream))) return rc;
+    return stage.finish();
 }

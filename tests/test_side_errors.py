@@ -3,12 +3,14 @@ needs no device: one line `family | case name | return code | message` per case,
 That file was recorded from the library as it was before the families' error recording, device check and allocation moved into
 csrc/qc_side.h, so the messages (API: bindings match on them) are the ones each family wrote by hand.
 
-Cases against the `?fail(` call sites of the sources (the one-line definitions of ffail / tfail / rfail / sfail not counted; several
-cases may reach one site through different fields or entry points):
+Cases against the `?fail(` call sites of the sources (`qc_sweep_fail(` in qc_sweep.hip; the one-line definitions of ffail / tfail / rfail /
+qc_sweep_fail not counted; several cases may reach one site through different fields or entry points):
     qc_fidelity.hip  24 sites, 20 reached by 24 cases
     qc_terms.hip     29 sites, 26 reached by 30 cases
     qc_robust.hip    31 sites, 25 reached by 27 cases
-    qc_sweep.hip     41 sites, 30 reached by 33 cases   (one site holds two texts, ket and density operator: a case each)
+    qc_sweep.hip     38 sites, 29 reached by 33 cases   (one site holds two texts, ket and density operator: a case each; the NULL
+                     handle of qc_sweep_eval and of qc_sweep_eval_dev is one site, in qc_sweep_check, which every entry point of the
+                     family calls first)
 plus one valid descriptor per family, refused with QC_ERR_NO_DEVICE where there is no GPU ("<create>: no HIP device visible"; the other
 text of that check in qc_side.h, "<create>: device ordinal out of range", needs a visible device to be out of range of).
 Sites without a case: each needs a created handle or a failing HIP call.
@@ -18,8 +20,10 @@ Sites without a case: each needs a created handle or a failing HIP call.
     qc_terms.hip     qc_terms_eval_dev "NULL buffer", "kernel launch: ..."; qc_terms_eval "NULL input"
     qc_robust.hip    qc_robust_hess_structure "NULL output"; qc_robust_eval_dev and qc_robust_eval "NULL input" and "Hessian values
                      requested from a handle created without a Hessian"; qc_robust_eval_dev "kernel launch: ..."
-    qc_sweep.hip     qc_sweep_eval_dev and qc_sweep_eval "NULL input", "S must be in 1 .. 2^24", "theta is NULL but ...", "finals and fids
-                     are both NULL", "fidelities requested from a handle created without one"; qc_sweep_eval_dev "kernel launch: ..."."""
+    qc_sweep.hip     qc_sweep_check (the lines every entry point shares) the entry's scope, "NULL input", "<input> is NULL", "S must be in
+                     1 .. 2^24", "theta is NULL but ..."; qc_sweep_eval_dev and qc_sweep_eval "finals and fids are both NULL",
+                     "fidelities requested from a handle created without one", "kernel launch: ..."; and, needing neither, the
+                     descriptor's "wide must be 0 or QC_SWEEP_WIDE (1)" (tests/test_sweep_wide.py holds the return code)."""
 import ctypes as C
 import os
 
