@@ -634,9 +634,11 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * of the final states: leakage, the free-phase fidelity, several kets at once, a loss written elsewhere.
  * The forward-mode counterpart, the tangent of the final states and fidelities along one direction (qc_sweep_jvp*, below), is served
  * for "mfma16-sweep" handles with any generators, Lindblad ones included; with the pullback it gives Gauss-Newton products of any loss.
+ * The tangent of the pullback along one direction (qc_sweep_hvp*, below) gives exact Hessian products of any loss of the final states
+ * where both of them are served (closed systems, "mfma16-sweep").
  * Out of scope: per-knot outputs, open-system gradients (reverse mode needs stored forward states; their directional derivatives are
- * qc_sweep_jvp's), pushforwards on "mfma32-sweep" and "rollout-per-sample" handles, several directions per call, exact second
- * derivatives, several devices. */
+ * qc_sweep_jvp's), pushforwards on "mfma32-sweep" and "rollout-per-sample" handles (Hessian products likewise), several directions per
+ * call, tangents of grad_theta / grad_scale, several devices. */
 #define QC_MAX_PERT 8
 #define QC_SWEEP_FID_NONE (-1)   /* qc_sweep_desc.fid_kind: final states only */
 #define QC_SWEEP_WIDE 1          /* qc_sweep_desc.wide */
@@ -790,6 +792,44 @@ int qc_sweep_jvp_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t
 int qc_sweep_jvp(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
                  const double* vZ, const double* vinit, const double* vtheta, const double* vscale,
                  double* finals, double* fids, double* tfinals, double* tfids);
+
+/* ---- sweep Hessian products: the tangent of the sweep pullback along one direction --------------------------------------- */
+/* With phi_s = <cot[s], x_final[s]>, g_s = dphi_s/d(a_t, dt_t) (qc_sweep_vjp's grad_samples[s]) and q_s = dphi_s/dinit (its grad_init[s]):
+ *     tgrad_samples[s] = d/de g_s(Z + e vZ, init + e vinit, theta + e vtheta, c + e vscale; cot + e vcot) at e = 0
+ *     tgrad_init[s]    = d/de q_s = Wdot^T cot[s] + W^T vcot[s]              (W: the sample's propagator, Wdot its tangent)
+ *     tgrad            = sum_s tgrad_samples[s] (plain sum, ascending s) in the layout of Z.
+ * With cot = d loss/dX and vcot = (d2 loss/dX2) Xdot, Xdot = qc_sweep_jvp's tfinals along vZ, tgrad is the EXACT Hessian product of
+ * loss(X(Z)) with vZ; with vcot = NULL it is the curvature of the sweep map alone, sum_s <cot[s], d2 x_s/dZ2 vZ>: what the Gauss-Newton
+ * product of qc_sweep_jvp + qc_sweep_vjp drops, and the whole Hessian of a loss that is linear in the final states.
+ * One tangent forward walk (qc_sweep_jvp's, for the chunk totals) and one backward walk that differentiates every product of the
+ * gradient walk beside itself with a degree-10 series: 408 + 36 sq matrix-core instructions per interval against the pullback's 112 + 12 sq. */
+/* device-free: may the Hessian product serve this descriptor?  Scope: what the pullback and the pushforward BOTH serve -- the
+ * "mfma16-sweep" form (2N <= 16, m <= 8), antisymmetric drift / drives / perturbations, at most 16 state columns, any fid_kind
+ * (QC_SWEEP_FID_NONE included).  When 0, qc_sweep_last_error(NULL) says why, prefixed "qc_sweep Hessian product: ": the pullback's reason
+ * (antisymmetry, more than 16 columns, the rollout-per-sample form with its cause) or "... not served in the mfma32-sweep form".  An invalid
+ * descriptor returns its own error. */
+int qc_sweep_desc_hvp_supported(const qc_sweep_desc* d, int32_t* supported);
+/* cot: S x (2N cols), required.  Directions, each optional (NULL = zero: the same bits as an explicit zero array), at least one non-NULL:
+ *   vZ       Z_len; ONLY the controls and timesteps of knots 0 .. T-2 are read (a NaN anywhere else has no effect)
+ *   vinit    2N x cols, shared by the samples
+ *   vtheta   S x n_pert (QC_ERR_INVALID when n_pert = 0)
+ *   vscale   S x m (QC_ERR_INVALID when m = 0); valid with scale = NULL, which means c = 1
+ *   vcot     S x (2N cols)
+ * Outputs, each optional, at least one non-NULL:
+ *   tgrad          Z_len            +0.0 outside the controls / timesteps of knots 0 .. T-2
+ *   tgrad_samples  S x (T-1) x nd   the layout of qc_sweep_grad's grad_samples
+ *   tgrad_init     S x (2N cols)
+ * Inputs must not overlap outputs.  S in 1 .. 2^24.  Scratch and the one-in-flight rule as qc_sweep_eval_dev.  No atomics: repeated calls
+ * return the same bits, and no output's bits depend on which other outputs were requested.  Non-finite entries of cot[s], vcot[s],
+ * vtheta[s], vscale[s] are evaluated, not rejected: they reach sample s's outputs and tgrad, nothing else (the number of squarings never
+ * depends on a direction). */
+int qc_sweep_hvp_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
+                     const double* dcot, const double* dvZ, const double* dvinit, const double* dvtheta, const double* dvscale,
+                     const double* dvcot, double* dtgrad, double* dtgrad_samples, double* dtgrad_init, void* stream);
+/* the same on host buffers (synchronous) */
+int qc_sweep_hvp(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
+                 const double* cot, const double* vZ, const double* vinit, const double* vtheta, const double* vscale,
+                 const double* vcot, double* tgrad, double* tgrad_samples, double* tgrad_init);
 
 /* Diagnostic only: when the environment variable QC_STAMPS=1 is set at qc_create, the MFMA kernel
  * records 16 s_memrealtime (100 MHz) checkpoints per interval; this copies them out (synchronises the

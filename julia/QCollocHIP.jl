@@ -950,6 +950,67 @@ function rollout_sweep_pushforward(init::AbstractVector{Float64}, controls::Abst
 end
 
 """
+    rollout_sweep_hessian_product(init, controls, Δt, G_drift, G_drives, G_pert, θ, cot; scale=nothing, cols, vZ=nothing, vinit=nothing,
+                                  vtheta=nothing, vscale=nothing, vcot=nothing, device=0)  ->  (tgrad, tgrad_samples, tgrad_init)
+
+The tangent of the pullback of `rollout_sweep` along one direction (`qc_sweep_hvp`).  `cot` is (2N·cols)×S, one cotangent per sample;
+`vZ` an (m+1)×T matrix in the knot layout [a; Δt] (only the columns of knots 1 … T−1 act), `vinit` a 2N·cols vector, `vtheta` S×p,
+`vscale` S×m, `vcot` (2N·cols)×S; whichever is `nothing` is zero, at least one must be given.  Returns `tgrad`, (m+1)×T (the plain sum
+over the samples, zero in the last column), `tgrad_samples`, (m+1)×(T−1)×S, and `tgrad_init`, (2N·cols)×S.  With `cot` the gradient of a
+loss of the final states and `vcot` its Hessian times the pushforward's tangents, `tgrad` is the exact Hessian product of the loss.
+Served for closed systems (antisymmetric generators) with 2N ≤ 16, m ≤ 8 and at most 16 columns.  UNTESTED here, like the rest of this file.
+"""
+function rollout_sweep_hessian_product(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift,
+                                       G_drives, G_pert, θ::AbstractMatrix{Float64}, cot::AbstractMatrix{Float64}; scale=nothing, cols::Int,
+                                       vZ=nothing, vinit=nothing, vtheta=nothing, vscale=nothing, vcot=nothing, device::Int=0)
+    n = size(G_drift, 1); N = n ÷ 2
+    m, T = size(controls); p = length(G_pert); S = size(θ, 1)
+    G0 = Float64.(vec(G_drift))
+    Gd = m == 0 ? Float64[] : reduce(vcat, [Float64.(vec(G)) for G in G_drives])
+    Gp = p == 0 ? Float64[] : reduce(vcat, [Float64.(vec(G)) for G in G_pert])
+    Z⃗ = vec(vcat(controls, reshape(Δt, 1, T)))                      # knot layout [a; Δt]
+    θt = Matrix{Float64}(transpose(θ))                               # sample-major
+    ct = isnothing(scale) ? Float64[] : vec(Matrix{Float64}(transpose(scale)))
+    size(cot) == (n * cols, S) || error("rollout_sweep_hessian_product: cot must be $(n * cols)×$S")
+    (isnothing(vcot) || size(vcot) == (n * cols, S)) || error("rollout_sweep_hessian_product: vcot must be $(n * cols)×$S")
+    (isnothing(vtheta) || size(vtheta) == (S, p)) || error("rollout_sweep_hessian_product: vtheta must be $S×$p")
+    (isnothing(vscale) || size(vscale) == (S, m)) || error("rollout_sweep_hessian_product: vscale must be $S×$m")
+    (isnothing(scale) || size(scale) == (S, m)) || error("rollout_sweep_hessian_product: scale must be $S×$m")
+    cv = Float64.(vec(cot))                                          # column s is sample s: sample-major as it stands
+    vcv = isnothing(vcot) ? Float64[] : Float64.(vec(vcot))
+    vz = isnothing(vZ) ? Float64[] : Float64.(vec(vZ))
+    vi = isnothing(vinit) ? Float64[] : Float64.(vec(vinit))
+    vθ = isnothing(vtheta) ? Float64[] : vec(Matrix{Float64}(transpose(vtheta)))
+    vc = isnothing(vscale) ? Float64[] : vec(Matrix{Float64}(transpose(vscale)))
+    (isempty(vz) || length(vz) == (m + 1) * T) || error("rollout_sweep_hessian_product: vZ must be $(m + 1)×$T")
+    (isempty(vi) || length(vi) == n * cols) || error("rollout_sweep_hessian_product: vinit must have $(n * cols) entries")
+    tgrad = Matrix{Float64}(undef, m + 1, T)
+    tsamp = Array{Float64}(undef, m + 1, T - 1, S)
+    tginit = Matrix{Float64}(undef, n * cols, S)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve G0 Gd Gp begin
+        desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, -1,
+                               pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
+                               0, 0, C_NULL, C_NULL, device, 0, (0, 0)))
+        ok = Ref{Int32}(0)
+        rc = ccall((:qc_sweep_desc_hvp_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
+        (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
+        rc = ccall((:qc_sweep_create, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Ptr{Cvoid}}), desc, h)
+        rc == 0 || error("qc_sweep_create: " * unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
+    end
+    rc = GC.@preserve Z⃗ init θt ct cv vz vi vθ vc vcv tgrad tsamp tginit ccall((:qc_sweep_hvp, LIB[]), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        h[], Z⃗, init, S, p == 0 ? C_NULL : pointer(θt), isempty(ct) ? C_NULL : pointer(ct), cv, isempty(vz) ? C_NULL : pointer(vz),
+        isempty(vi) ? C_NULL : pointer(vi), isempty(vθ) ? C_NULL : pointer(vθ), isempty(vc) ? C_NULL : pointer(vc),
+        isempty(vcv) ? C_NULL : pointer(vcv), tgrad, tsamp, tginit)
+    msg = rc == 0 ? "" : unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), h[]))
+    ccall((:qc_sweep_destroy, LIB[]), Cvoid, (Ptr{Cvoid},), h[])
+    rc == 0 || error("qc_sweep_hvp: " * msg)
+    return tgrad, tsamp, tginit
+end
+
+"""
     iso_vec_unitary_fidelity(Ũ⃗, Ũ⃗_goal; subspace=nothing, device=0, squared=false)          (unitary_minimum_time_problem.jl:77)
     iso_vec_unitary_free_phase_fidelity(Ũ⃗, Ũ⃗_goal, phases, phase_operators; subspace=nothing)  (unitary_minimum_time_problem.jl:86-90)
 

@@ -411,6 +411,7 @@ extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
     h->grad_ok = qc_sweep_grad_scope(d, &h->grad_why);      // from the caller's matrices, which the handle does not keep
     h->vjp_ok = qc_sweep_vjp_scope(d, &h->vjp_why);
     h->jvp_ok = qc_sweep_jvp_scope(d, &h->jvp_why);
+    h->hvp_ok = qc_sweep_hvp_scope(d, &h->hvp_why);
     const int N = d->N, n = 2 * N, n2 = n * n, m = d->m, p = d->n_pert;
     h->n = n;
     h->nc = d->state_cols == 0 ? N : d->state_cols;

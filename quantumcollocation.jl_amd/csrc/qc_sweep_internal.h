@@ -1,5 +1,5 @@
-// What qc_sweep.hip (forward sweep), qc_sweep_grad.hip (its adjoint), qc_sweep_vjp.hip (the pullback of the final states) and
-// qc_sweep_jvp.hip (their pushforward) share: the handle with its scratch and staging buffers, the descriptor and argument checks and
+// What qc_sweep.hip (forward sweep), qc_sweep_grad.hip (its adjoint), qc_sweep_vjp.hip (the pullback of the final states),
+// qc_sweep_jvp.hip (their pushforward) and qc_sweep_hvp.hip (the tangent of the pullback) share: the handle with its scratch and staging buffers, the descriptor and argument checks and
 // the launch of the forward chunk totals (with it the chunk rule).  Not part of the ABI.
 #pragma once
 
@@ -17,6 +17,8 @@ struct qc_sweep : qc_side {
     std::string vjp_why;
     bool jvp_ok = false;         // the pushforward's scope (qc_sweep_jvp.hip): "mfma16-sweep" handles, any generators
     std::string jvp_why;
+    bool hvp_ok = false;         // the Hessian product's scope (qc_sweep_hvp.hip): what the pullback and the pushforward both serve
+    std::string hvp_why;
     int n = 0, nc = 0, ns = 0, fid_n = 0;
     int64_t Zlen = 0;
     double* dG = nullptr;        // (1 + m + p) matrices, column-major (per-sample form)
@@ -30,7 +32,9 @@ struct qc_sweep : qc_side {
     qc_buf dGsamp;       // per-interval derivatives when the caller keeps none, S x (T-1) x nd   grad, vjp
     qc_buf dGfid;        // fidelities when the caller keeps none, S                         grad
     qc_buf dPart;        // chunk shares of the parameter gradients, S x n_chunks x (p + m)  grad_params, vjp
-    qc_buf dTotJ;        // chunk totals and their tangents, S x n_chunks x 512              jvp
+    qc_buf dTotJ;        // chunk totals and their tangents, S x n_chunks x 512              jvp, hvp
+    qc_buf dXsT, dLsT;   // xdot and lambdadot at the chunk ends, S x n_chunks x ns each      hvp (x and lambda: dXs, dLs)
+    qc_buf dTGsamp;      // per-interval tangents when the caller keeps none, S x (T-1) x nd  hvp
     // Staging of the host-buffer entry points (qc_stage): one buffer per argument, shared by every entry point that has the argument.
     qc_buf sZ, sInit;    // Zlen, ns: allocated at create                                     every entry
     qc_buf sTheta;       // S x p                                                             every entry
@@ -43,11 +47,15 @@ struct qc_sweep : qc_side {
     qc_buf sGradS;       // per-sample gradients, S x (T-1) x nd                              grad, vjp
     qc_buf sGth;         // grad_theta, S x p                                                 grad_params, vjp
     qc_buf sGsc;         // grad_scale, S x m                                                 grad_params, vjp
-    qc_buf sCot;         // cotangents, S x ns                                                vjp
+    qc_buf sCot;         // cotangents, S x ns                                                vjp, hvp
     qc_buf sGinit;       // grad_init, S x ns                                                 vjp
-    qc_buf sVZ, sVinit;  // directions, Zlen and ns                                           jvp
-    qc_buf sVth, sVsc;   // directions, S x p and S x m                                       jvp
+    qc_buf sVZ, sVinit;  // directions, Zlen and ns                                           jvp, hvp
+    qc_buf sVth, sVsc;   // directions, S x p and S x m                                       jvp, hvp
     qc_buf sTfin, sTfid; // tangents, S x ns and S                                            jvp
+    qc_buf sVcot;        // the direction of the cotangents, S x ns                           hvp
+    qc_buf sTgrad;       // the dense tangent of the gradient, Zlen                           hvp
+    qc_buf sTgradS;      // its per-sample form, S x (T-1) x nd                               hvp
+    qc_buf sTginit;      // the tangent of grad_init, S x ns                                  hvp
 };
 
 // records the message in the handle (when there is one) and in the slot qc_sweep_last_error(NULL) returns
@@ -97,3 +105,11 @@ bool qc_sweep_closed_scope(const qc_sweep_desc* d, std::string* why);
 bool qc_sweep_vjp_scope(const qc_sweep_desc* d, std::string* why);
 // the pushforward's scope (qc_sweep_jvp.hip): the "mfma16-sweep" form, whatever the generators
 bool qc_sweep_jvp_scope(const qc_sweep_desc* d, std::string* why);
+// "mfma16-sweep" handles (qc_sweep_jvp.hip): grows h->dTotJ and launches qc_sweep_jvp_kernel<M> on `st` (S x n_chunks x 2 tiles of 256
+// doubles: the chunk totals and their tangents along (vZ, vtheta, vscale), each NULL = zero)
+int qc_sweep_jvp_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dvZ,
+                               const double* dvtheta, const double* dvscale, hipStream_t st, int64_t* chunk, int64_t* n_chunks);
+// the plain sum over the samples of a per-interval buffer (qc_sweep_vjp.hip: qc_sweep_vjp_reduce_kernel), launched on `st`
+void qc_sweep_launch_plain_sum(qc_sweep* h, int64_t S, const double* gs, double* dgrad, hipStream_t st);
+// the Hessian product's scope (qc_sweep_hvp.hip): the pullback's, within the "mfma16-sweep" form
+bool qc_sweep_hvp_scope(const qc_sweep_desc* d, std::string* why);

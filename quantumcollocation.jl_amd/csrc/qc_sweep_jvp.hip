@@ -356,16 +356,11 @@ extern "C" int qc_sweep_desc_jvp_supported(const qc_sweep_desc* d, int32_t* supp
     return QC_OK;
 }
 
-static int qc_sweep_jvp_launch(qc_sweep* h, const char* who, const double* dZ, const double* dinit, int64_t S, const double* dtheta,
-                               const double* dscale, const double* dvZ, const double* dvinit, const double* dvtheta, const double* dvscale,
-                               double* dfinals, double* dfids, double* dtfinals, double* dtfids, void* stream) {
-    int rc = jvp_check(h, who, dZ, dinit, S, dtheta, dvZ || dvinit || dvtheta || dvscale, dfinals || dfids || dtfinals || dtfids, dvtheta != nullptr,
-                       dvscale != nullptr, dfids || dtfids);
-    if (rc) return rc;
+// The chunk totals W_c and their tangents Wdot_c of "mfma16-sweep" handles, for the pushforward below and the Hessian product of
+// qc_sweep_hvp.hip: grows h->dTotJ and launches qc_sweep_jvp_kernel<M> on `st` (S x n_chunks x 2 tiles of 256 doubles).
+int qc_sweep_jvp_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dvZ,
+                               const double* dvtheta, const double* dvscale, hipStream_t st, int64_t* chunk_out, int64_t* n_chunks_out) {
     std::string& slot = *qc_sweep_err_slot();
-    qc_device_guard guard(h->device);
-    QC_SIDE_HIP(h, slot, guard.err);
-    hipStream_t st = (hipStream_t)stream;
     const int m = h->d.m;
     int64_t chunk, n_chunks;
     qc_sweep_chunks(S, h->d.T, &chunk, &n_chunks);
@@ -381,6 +376,23 @@ static int qc_sweep_jvp_launch(qc_sweep* h, const char* who, const double* dZ, c
     hipLaunchKernelGGL(qc_sweep_jvp_kernel<M_>, dim3(grid), dim3(64 * kSWaves), 0, st, P, dZ, dtheta, dscale, dvZ, dvtheta, dvscale, h->dTotJ.p)
     QC_SWEEP_FOR_M(m, QC_JVP_LAUNCH);
 #undef QC_JVP_LAUNCH
+    *chunk_out = chunk;
+    *n_chunks_out = n_chunks;
+    return QC_OK;
+}
+
+static int qc_sweep_jvp_launch(qc_sweep* h, const char* who, const double* dZ, const double* dinit, int64_t S, const double* dtheta,
+                               const double* dscale, const double* dvZ, const double* dvinit, const double* dvtheta, const double* dvscale,
+                               double* dfinals, double* dfids, double* dtfinals, double* dtfids, void* stream) {
+    int rc = jvp_check(h, who, dZ, dinit, S, dtheta, dvZ || dvinit || dvtheta || dvscale, dfinals || dfids || dtfinals || dtfids, dvtheta != nullptr,
+                       dvscale != nullptr, dfids || dtfids);
+    if (rc) return rc;
+    std::string& slot = *qc_sweep_err_slot();
+    qc_device_guard guard(h->device);
+    QC_SIDE_HIP(h, slot, guard.err);
+    hipStream_t st = (hipStream_t)stream;
+    int64_t chunk, n_chunks;
+    if ((rc = qc_sweep_jvp_launch_totals(h, dZ, S, dtheta, dscale, dvZ, dvtheta, dvscale, st, &chunk, &n_chunks))) return rc;
     JvpFinParams F;
     F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
     F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;

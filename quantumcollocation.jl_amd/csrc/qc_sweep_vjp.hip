@@ -128,6 +128,15 @@ extern "C" int qc_sweep_desc_vjp_supported(const qc_sweep_desc* d, int32_t* supp
     return QC_OK;
 }
 
+// grad = the plain sum over the samples of the per-interval buffer gs (S x (T-1) x nd), for the pullback below and the Hessian product
+// of qc_sweep_hvp.hip
+void qc_sweep_launch_plain_sum(qc_sweep* h, int64_t S, const double* gs, double* dgrad, hipStream_t st) {
+    SumParams R;
+    R.zdim = h->d.zdim; R.off_a = h->d.off_a; R.off_dt = h->d.off_dt; R.m = h->d.m; R.nd = h->d.m + (h->d.off_dt >= 0 ? 1 : 0);
+    R.T = h->d.T; R.Zlen = h->Zlen; R.S = S;
+    hipLaunchKernelGGL(qc_sweep_vjp_reduce_kernel, dim3((unsigned)((h->Zlen + kSumT - 1) / kSumT)), dim3(kSumT), 0, st, R, gs, dgrad);
+}
+
 static int qc_sweep_vjp_launch(qc_sweep* h, const char* who, const double* dZ, const double* dinit, int64_t S, const double* dtheta,
                                const double* dscale, const double* dcot, double* dfinals, double* dgrad, double* dgrad_samples, double* dgrad_init,
                                double* dgrad_theta, double* dgrad_scale, void* stream) {
@@ -165,12 +174,7 @@ static int qc_sweep_vjp_launch(qc_sweep* h, const char* who, const double* dZ, c
         if (want_grad) qc_sweep32_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, gsamp, st);
     } else if (want_grad || want_par)
         qc_sweep16_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);
-    if (dgrad) {
-        SumParams R;
-        R.zdim = h->d.zdim; R.off_a = h->d.off_a; R.off_dt = h->d.off_dt; R.m = m; R.nd = nd;
-        R.T = h->d.T; R.Zlen = h->Zlen; R.S = S;
-        hipLaunchKernelGGL(qc_sweep_vjp_reduce_kernel, dim3((unsigned)((h->Zlen + kSumT - 1) / kSumT)), dim3(kSumT), 0, st, R, (const double*)gsamp, dgrad);
-    }
+    if (dgrad) qc_sweep_launch_plain_sum(h, S, gsamp, dgrad, st);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return qc_sweep_fail(h, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return QC_OK;

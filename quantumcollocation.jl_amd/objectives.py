@@ -838,9 +838,10 @@ class SweepFinalStateObjective:
     final state of sample s, column-major 2N x cols ([Re; Im] per column); `loss` maps it to a 0-dim tensor.  `L(Z)` evaluates it,
     `grad_L(Z)` (dense, length `len(Z)`) runs torch's backward through the sweep's pullback: one adjoint sweep per gradient.  First
     order only, as `SweepInfidelityObjective`: `hess_structure` is empty and `hess_L` raises.  Curvature is matrix-free:
-    `gauss_newton_times(Z, v)` is the generalized Gauss-Newton product of the loss, one pushforward and one pullback of the sweep.
-    `L`, `grad_L` and `gauss_newton_times` also take Z (and v) as float64 tensors on the handle's device; `grad_L` and
-    `gauss_newton_times` then return device tensors, so an optimiser can keep the trajectory vector there.  numpy in, numpy out is
+    `gauss_newton_times(Z, v)` is the generalized Gauss-Newton product of the loss, one pushforward and one pullback of the sweep;
+    `hessian_times(Z, v)` is the exact Hessian product, one pushforward and one tangent pullback (`RolloutSweep.hvp_device`).
+    `L`, `grad_L`, `gauss_newton_times` and `hessian_times` also take Z (and v) as float64 tensors on the handle's device; `grad_L` and
+    the two products then return device tensors, so an optimiser can keep the trajectory vector there.  numpy in, numpy out is
     unchanged.
 
     state_name  a unitary component (2 N^2 entries), a component of K kets (2 N K entries, the kets side by side) or a list of ket
@@ -958,6 +959,41 @@ class SweepFinalStateObjective:
             out = torch.zeros(self.Z_len, dtype=torch.float64, device=self._dev)
             if u is not None:      # (a loss linear in X has no second derivative: exact zeros, no pullback)
                 sw.vjp_device(dZ, self._dinit, self.S, u.detach().contiguous(), self._dtheta, self._dscale, dgrad=out)
+        return out if on_device else out.cpu().numpy()
+
+    def hessian_times(self, Z, v):
+        """The EXACT Hessian product d2 L / dZ2 v as a dense vector of length `len(Z)`: one pushforward (X and Xdot = J v, `jvp_device`),
+        cot = d loss/dX and vcot = (d2 loss/dX2) Xdot by torch on the loss alone (X a detached leaf), one `hvp_device` call -- the tangent
+        of the pullback along (v, vcot).  It is `gauss_newton_times` plus the curvature of the sweep map, sum_s <cot_s, d2 X_s/dZ2 v>, which
+        for a loss that is linear or nearly linear in X is the whole Hessian.  A loss linear in X gives vcot = 0, not a skipped call.  Z and
+        v are numpy arrays (the result is one) or float64 tensors on the handle's device (the result stays there).  Needs the Hessian
+        product's scope: closed systems on an "mfma16-sweep" handle."""
+        sw = self._sweep
+        if not sw.hvp_supported:
+            raise _lib.QCollocError(_lib.QC_ERR_UNSUPPORTED, sw.hvp_unsupported_reason)
+        on_device = torch.is_tensor(Z) and torch.is_tensor(v)
+        put = lambda a: (a.detach() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))).to(self._dev).contiguous().reshape(-1)
+        dZ, dv = put(Z), put(v)
+        if dZ.numel() != self.Z_len or dv.numel() != self.Z_len:
+            raise ValueError(f"Z and v must have length {self.Z_len}")
+        with torch.cuda.device(self._dev):
+            X = torch.empty((self.S, sw.ns), dtype=torch.float64, device=self._dev)
+            Xd = torch.empty_like(X)
+            sw.jvp_device(dZ, self._dinit, self.S, self._dtheta, self._dscale, dvZ=dv, dfinals=X, dtfinals=Xd)
+            g = u = None
+            with torch.enable_grad():
+                X.requires_grad_(True)
+                L = self.loss(X)
+                if L.dim() != 0:
+                    raise ValueError("loss must return a 0-dim tensor")
+                g = torch.autograd.grad(L, X, create_graph=True, allow_unused=True)[0] if L.requires_grad else None
+                if g is not None and g.requires_grad:
+                    u = torch.autograd.grad(g, X, grad_outputs=Xd, allow_unused=True)[0]
+            out = torch.zeros(self.Z_len, dtype=torch.float64, device=self._dev)
+            if g is not None:      # (a loss that does not depend on X: exact zeros)
+                cot = g.detach().contiguous()
+                vcot = torch.zeros_like(cot) if u is None else u.detach().contiguous()
+                sw.hvp_device(dZ, self._dinit, self.S, cot, self._dtheta, self._dscale, dvZ=dv, dvcot=vcot, dtgrad=out)
         return out if on_device else out.cpu().numpy()
 
     def __getattr__(self, name):

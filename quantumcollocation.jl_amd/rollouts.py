@@ -21,6 +21,8 @@ the loop of the reference's robustness check, `unitary_rollout(traj.a, timesteps
                                                                             them, in torch, differentiated by one adjoint sweep
     RolloutSweep.jvp / .jvp_device                                          the pushforward (`qc_sweep_jvp*`): tangents of the final states and
                                                                             fidelities along one direction, open systems included
+    RolloutSweep.hvp / .hvp_device                                          the tangent of the pullback (`qc_sweep_hvp*`): exact Hessian products of
+                                                                            any loss of the final states
 """
 from __future__ import annotations
 
@@ -561,6 +563,90 @@ class RolloutSweep:
         ptr = lambda t, use=True: t.data_ptr() if (t is not None and use and t.numel()) else None
         rc = _lib.lib.qc_sweep_jvp_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dvZ), ptr(dvinit),
                                        ptr(dvtheta), ptr(dvscale), ptr(dfinals), ptr(dfids), ptr(dtfinals), ptr(dtfids), s)
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+
+    # -- Hessian products: the tangent of the pullback along one direction ------------------------------------------------------------
+    @property
+    def hvp_supported(self) -> bool:
+        """Does `hvp` serve this handle?  (`qc_sweep_desc_hvp_supported`: what `vjp` and `jvp` both serve -- the "mfma16-sweep" form,
+        antisymmetric generators, at most 16 state columns, any fidelity or none.)  `hvp_unsupported_reason` says why not."""
+        return self._hvp_scope()[0]
+
+    @property
+    def hvp_unsupported_reason(self) -> Optional[str]:
+        return self._hvp_scope()[1]
+
+    def _hvp_scope(self):
+        ok = C.c_int32()
+        rc = _lib.lib.qc_sweep_desc_hvp_supported(C.byref(self._desc), C.byref(ok))
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(None).decode())
+        return bool(ok.value), (None if ok.value else _lib.lib.qc_sweep_last_error(None).decode())
+
+    def hvp(self, Z, init, cot, theta, scale=None, vZ=None, vinit=None, vtheta=None, vscale=None, vcot=None, per_sample: bool = False,
+            init_grad: bool = False):
+        """The tangent of the pullback `vjp` along the direction (vZ, vinit, vtheta, vscale, vcot), each None = zero, at least one given:
+        returns `tgrad` (Z_len), the directional derivative of `vjp`'s `grad`, followed -- in this order -- by what was asked for:
+            per_sample   tgrad_samples, S x (T-1) x n_deriv: the derivative of `grad_samples`
+            init_grad    tgrad_init, S x (2N cols): the derivative of `grad_init`
+        With cot = d loss/dX and vcot = (d2 loss/dX2) Xdot (Xdot: `jvp` along vZ) `tgrad` is the exact Hessian product of loss(X(Z)) with
+        vZ; with vcot = None it is the curvature of the sweep map alone, what a Gauss-Newton product drops."""
+        Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
+        if Z.size != self.Z_len:
+            raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
+        init = np.ascontiguousarray(init, dtype=np.float64).ravel()
+        if init.size != self.ns:
+            raise ValueError(f"initial state has length {init.size}, expected {self.ns}")
+        cot = np.ascontiguousarray(cot, dtype=np.float64)
+        if theta is None and scale is None:
+            S = cot.reshape(-1, self.ns).shape[0]
+        else:
+            S, theta, scale = self._samples(theta, scale)
+        if cot.size != S * self.ns:
+            raise ValueError(f"cot must be {S} x {self.ns}")
+        vec = lambda a, cnt, what: None if a is None else self._sized(np.ascontiguousarray(a, dtype=np.float64).ravel(), cnt, what)
+        vZ, vinit, vcot = vec(vZ, self.Z_len, "vZ"), vec(vinit, self.ns, "vinit"), vec(vcot, S * self.ns, "vcot")
+        vtheta, vscale = vec(vtheta, S * self.p, "vtheta"), vec(vscale, S * self.m, "vscale")
+        tg = np.empty(self.Z_len)
+        tgs = np.empty((S, self.T - 1, self.n_deriv)) if per_sample else None
+        tgi = np.empty((S, self.ns)) if init_grad else None
+        opt = lambda a: _lib.dptr(a) if (a is not None and a.size) else None
+        dirs = lambda a: _lib.dptr(a) if a is not None else None
+        rc = _lib.lib.qc_sweep_hvp(self._h, _lib.dptr(Z), _lib.dptr(init), S, opt(theta), opt(scale), _lib.dptr(cot), dirs(vZ), dirs(vinit),
+                                   dirs(vtheta), dirs(vscale), dirs(vcot), _lib.dptr(tg), opt(tgs), opt(tgi))
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        return (tg,) + ((tgs,) if per_sample else ()) + ((tgi,) if init_grad else ())
+
+    def hvp_device(self, dZ, dinit, S: int, dcot, dtheta=None, dscale=None, dvZ=None, dvinit=None, dvtheta=None, dvscale=None, dvcot=None,
+                   dtgrad=None, dtgrad_samples=None, dtgrad_init=None, stream=None):
+        """Device-resident Hessian product on torch CUDA tensors (float64), asynchronous on `stream`: `qc_sweep_hvp_dev`.  dcot
+        S x (2N cols); directions, each optional, at least one: dvZ Z_len, dvinit 2N cols, dvtheta S x n_pert, dvscale S x m, dvcot
+        S x (2N cols).  Outputs, each optional, at least one: dtgrad Z_len, dtgrad_samples S x (T-1) x n_deriv, dtgrad_init S x (2N cols)."""
+        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        S = int(S)
+        if dcot is None:
+            raise ValueError("dcot is required")
+        if all(t is None for t in (dvZ, dvinit, dvtheta, dvscale, dvcot)):
+            raise ValueError("every direction is None")
+        if all(t is None for t in (dtgrad, dtgrad_samples, dtgrad_init)):
+            raise ValueError("every output is None")
+        if dvtheta is not None and not self.p:
+            raise ValueError("dvtheta is given but the handle has no perturbations")
+        if dvscale is not None and not self.m:
+            raise ValueError("dvscale is given but the handle has no drives")
+        for t, cnt, what in ((dZ, self.Z_len, "dZ"), (dinit, self.ns, "dinit"), (dcot, S * self.ns, "dcot"), (dtheta, S * self.p, "dtheta"),
+                             (dscale, S * self.m, "dscale"), (dvZ, self.Z_len, "dvZ"), (dvinit, self.ns, "dvinit"), (dvtheta, S * self.p, "dvtheta"),
+                             (dvscale, S * self.m, "dvscale"), (dvcot, S * self.ns, "dvcot"), (dtgrad, self.Z_len, "dtgrad"),
+                             (dtgrad_samples, S * (self.T - 1) * self.n_deriv, "dtgrad_samples"), (dtgrad_init, S * self.ns, "dtgrad_init")):
+            if t is not None and (t.numel() != cnt or t.dtype != torch.float64 or not t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous float64 tensor of {cnt} entries")
+        if self.p and dtheta is None:
+            raise ValueError("dtheta is required: the handle has perturbations")
+        ptr = lambda t, use=True: t.data_ptr() if (t is not None and use and t.numel()) else None
+        rc = _lib.lib.qc_sweep_hvp_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dcot), ptr(dvZ),
+                                       ptr(dvinit), ptr(dvtheta), ptr(dvscale), ptr(dvcot), ptr(dtgrad), ptr(dtgrad_samples), ptr(dtgrad_init), s)
         if rc != _lib.QC_OK:
             raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
 
