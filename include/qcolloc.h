@@ -831,6 +831,47 @@ int qc_sweep_hvp(qc_sweep* h, const double* Z, const double* init, int64_t S, co
                  const double* cot, const double* vZ, const double* vinit, const double* vtheta, const double* vscale,
                  const double* vcot, double* tgrad, double* tgrad_samples, double* tgrad_init);
 
+/* ---- noise-trajectory sweeps: perturbations that change from interval to interval, and their gradients ------------------- */
+/* The sweep above holds theta[s, j] constant for the whole pulse.  Here every sample also carries a trajectory of perturbation
+ * amplitudes: in interval t = 0 .. T-2, for sample s,
+ *     G_{s,t} = G_drift + sum_j (theta[s, j] + noise[s, t, j]) P_j + sum_k c[s, k] a_{t,k} G_k,     x_{t+1} = exp(dt_t G_{s,t}) x_t.
+ * noise: S x (T-1) x n_pert doubles, sample-major, then interval, then perturbation: noise[(s (T-1) + t) n_pert + j].  A detuning that
+ * drifts during the pulse (Ornstein-Uhlenbeck, 1/f), additive noise on a drive line (P_j = G_k), S realisations of a stochastic
+ * average: one call in place of S single-sample calls that each carry the noise in a Z of their own.  The handle is an ordinary
+ * qc_sweep handle; the perturbation tiles sit in registers beside the drive tiles, their coefficients read per sample and interval.
+ * At noise = +0.0 the outputs equal those of qc_sweep_eval / qc_sweep_grad on the same handle value for value (a -0.0 may come out
+ * as +0.0, nothing else).
+ * Out of scope: "mfma32-sweep" and "rollout-per-sample" handles; pullbacks, pushforwards and Hessian products with noise (and with
+ * them the autograd function of the Python layer); several devices. */
+/* device-free: may the noise sweep serve this descriptor?  Scope of the evaluation: the "mfma16-sweep" form, n_pert >= 1,
+ * m + n_pert <= 8, any generators (Lindblad ones included), any state_cols and fid_kind the sweep serves there.  When 0,
+ * qc_sweep_last_error(NULL) says why, prefixed "qc_sweep noise: ": "... not served in the mfma32-sweep form", the rollout-per-sample
+ * form with its cause, n_pert = 0, or m + n_pert > 8 with the two numbers.  An invalid descriptor returns its own error. */
+int qc_sweep_desc_noise_supported(const qc_sweep_desc* d, int32_t* supported);
+/* The arguments and rules of qc_sweep_eval / qc_sweep_eval_dev, plus `noise` (required; it must not overlap an output:
+ * QC_ERR_INVALID).  finals: S x (2N cols); fids: S; either may be NULL, not both.  Scratch, the one-in-flight rule and S in 1 .. 2^24
+ * as qc_sweep_eval_dev.  Two launches: the chunk totals with m + n_pert tiles, and the sweep's own final-state / fidelity launch.
+ * Non-finite entries of noise[s] are evaluated, not rejected: they reach sample s's outputs, nothing else. */
+int qc_sweep_noise_eval(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
+                        const double* noise, double* finals, double* fids);
+int qc_sweep_noise_eval_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
+                            const double* dnoise, double* dfinals, double* dfids, void* stream);
+/* The arguments, layouts, weights rule and outputs of qc_sweep_grad / qc_sweep_grad_dev (every output optional, at least one
+ * non-NULL), plus `noise` as above and one more output:
+ *   grad_noise   S x (T-1) x n_pert, the layout of noise: dF_s/dnoise[s, t, j] = dt_t <lambda_{t+1} x_t^T, L(dt_t G_{s,t}; P_j)>, raw
+ *                per-sample values (no weights) -- the time-resolved noise sensitivity of every sample, from the per-interval tile the
+ *                backward walk forms anyway (qc_sweep_grad_params sums it over t: at noise = 0, sum_t grad_noise[s, t, j] = grad_theta[s, j]).
+ * Scope: the noise scope and the gradient's together (closed systems, a unitary or ket fidelity, at most 16 state columns); a refusal
+ * is prefixed "qc_sweep noise: " and carries the noise scope's reason, else the gradient's own.  Without grad_samples the handle
+ * keeps the per-interval buffer itself when `grad` needs it.  No atomics: repeated calls return the same bits, and no output's bits
+ * depend on which other outputs were requested.  Non-finite entries of noise[s] reach sample s's outputs and `grad` / `J`, nothing else. */
+int qc_sweep_noise_grad(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
+                        const double* noise, const double* weights, double* fids, double* J, double* grad, double* grad_samples,
+                        double* grad_noise);
+int qc_sweep_noise_grad_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
+                            const double* dnoise, const double* dweights, double* dfids, double* dJ, double* dgrad,
+                            double* dgrad_samples, double* dgrad_noise, void* stream);
+
 /* Diagnostic only: when the environment variable QC_STAMPS=1 is set at qc_create, the MFMA kernel
  * records 16 s_memrealtime (100 MHz) checkpoints per interval; this copies them out (synchronises the
  * device).  Not part of the evaluated path; a handle created without QC_STAMPS returns

@@ -795,6 +795,102 @@ function rollout_sweep_gradient(init::AbstractVector{Float64}, controls::Abstrac
 end
 
 """
+    rollout_noise_sweep(init, controls, Δt, G_drift, G_drives, G_pert, ξ; θ=nothing, scale=nothing, cols, goal=nothing, fid_kind=-1,
+                        subspace=nothing, squared=false, device=0)  ->  (finals, fids)
+
+`rollout_sweep` with perturbation amplitudes that change from interval to interval (`qc_sweep_noise_eval`): in interval t sample s
+evolves under G_drift + Σ_j (θ[s, j] + ξ[j, t, s]) G_pert[j] + Σ_k scale[s, k] a_{t,k} G_drives[k].  `ξ` is p×(T-1)×S (the library's
+sample-major layout as a column-major array), `θ` S×p or nothing (zeros).  Served for 2N ≤ 16 with p ≥ 1 and m + p ≤ 8; everything else
+errors with the library's reason.  Other arguments as `rollout_sweep`.  UNTESTED here, like the rest of this file.
+"""
+function rollout_noise_sweep(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift, G_drives,
+                             G_pert, ξ::AbstractArray{Float64,3}; θ=nothing, scale=nothing, cols::Int, goal=nothing, fid_kind::Int=-1,
+                             subspace=nothing, squared::Bool=false, device::Int=0)
+    n = size(G_drift, 1); N = n ÷ 2
+    m, T = size(controls); p = length(G_pert); S = size(ξ, 3)
+    size(ξ) == (p, T - 1, S) || error("rollout_noise_sweep: ξ must be $p×$(T - 1)×S")
+    G0 = Float64.(vec(G_drift))
+    Gd = m == 0 ? Float64[] : reduce(vcat, [Float64.(vec(G)) for G in G_drives])
+    Gp = p == 0 ? Float64[] : reduce(vcat, [Float64.(vec(G)) for G in G_pert])
+    sub = isnothing(subspace) ? Int32[] : Int32.(collect(subspace) .- 1)
+    g = isnothing(goal) ? Float64[] : Float64.(collect(goal))
+    Z⃗ = vec(vcat(controls, reshape(Δt, 1, T)))                      # knot layout [a; Δt]
+    θt = isnothing(θ) ? zeros(p, S) : Matrix{Float64}(transpose(θ))  # sample-major
+    ct = isnothing(scale) ? Float64[] : vec(Matrix{Float64}(transpose(scale)))
+    ξv = Array{Float64}(ξ)
+    finals = Matrix{Float64}(undef, n * cols, S)
+    fids = fid_kind >= 0 ? Vector{Float64}(undef, S) : Float64[]
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve G0 Gd Gp sub g begin
+        desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
+                               pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
+                               squared ? 1 : 0, length(sub), isempty(g) ? C_NULL : pointer(g), isempty(sub) ? C_NULL : pointer(sub),
+                               device, 0, (0, 0)))
+        ok = Ref{Int32}(0)
+        rc = ccall((:qc_sweep_desc_noise_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
+        (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
+        rc = ccall((:qc_sweep_create, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Ptr{Cvoid}}), desc, h)
+        rc == 0 || error("qc_sweep_create: " * unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
+    end
+    rc = GC.@preserve Z⃗ init θt ct ξv finals fids ccall((:qc_sweep_noise_eval, LIB[]), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        h[], Z⃗, init, S, θt, isempty(ct) ? C_NULL : pointer(ct), ξv, finals, fid_kind >= 0 ? pointer(fids) : C_NULL)
+    msg = rc == 0 ? "" : unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), h[]))
+    ccall((:qc_sweep_destroy, LIB[]), Cvoid, (Ptr{Cvoid},), h[])
+    rc == 0 || error("qc_sweep_noise_eval: " * msg)
+    return finals, fids
+end
+
+"""
+    rollout_noise_sweep_gradient(init, controls, Δt, G_drift, G_drives, G_pert, ξ; θ=nothing, scale=nothing, weights=nothing, cols, goal,
+                                 fid_kind=0, subspace=nothing, squared=false, device=0)  ->  (J, fids, ∇a, ∇Δt, ∇ξ)
+
+The adjoint of `rollout_noise_sweep` (`qc_sweep_noise_grad`): J, the S fidelities and the gradient of J over the controls and timesteps
+as `rollout_sweep_gradient` returns them, and `∇ξ[j, t, s]` = ∂F_s/∂ξ[j, t, s] (p×(T-1)×S, raw per-sample values): the time-resolved noise
+sensitivity of every sample.  Closed systems, `fid_kind` 0 (unitary) or 1 (ket), 2N ≤ 16, p ≥ 1, m + p ≤ 8.  UNTESTED here, like the
+rest of this file.
+"""
+function rollout_noise_sweep_gradient(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift,
+                                      G_drives, G_pert, ξ::AbstractArray{Float64,3}; θ=nothing, scale=nothing, weights=nothing, cols::Int,
+                                      goal, fid_kind::Int=0, subspace=nothing, squared::Bool=false, device::Int=0)
+    n = size(G_drift, 1); N = n ÷ 2
+    m, T = size(controls); p = length(G_pert); S = size(ξ, 3)
+    size(ξ) == (p, T - 1, S) || error("rollout_noise_sweep_gradient: ξ must be $p×$(T - 1)×S")
+    G0 = Float64.(vec(G_drift))
+    Gd = m == 0 ? Float64[] : reduce(vcat, [Float64.(vec(G)) for G in G_drives])
+    Gp = p == 0 ? Float64[] : reduce(vcat, [Float64.(vec(G)) for G in G_pert])
+    sub = isnothing(subspace) ? Int32[] : Int32.(collect(subspace) .- 1)
+    g = Float64.(collect(goal))
+    Z⃗ = vec(vcat(controls, reshape(Δt, 1, T)))                      # knot layout [a; Δt]
+    θt = isnothing(θ) ? zeros(p, S) : Matrix{Float64}(transpose(θ))  # sample-major
+    ct = isnothing(scale) ? Float64[] : vec(Matrix{Float64}(transpose(scale)))
+    w = isnothing(weights) ? Float64[] : Float64.(collect(weights))
+    ξv = Array{Float64}(ξ)
+    fids = Vector{Float64}(undef, S)
+    J = Ref(0.0)
+    grad = Vector{Float64}(undef, (m + 1) * T)
+    ∇ξ = Array{Float64}(undef, p, T - 1, S)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve G0 Gd Gp sub g begin
+        desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
+                               pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
+                               squared ? 1 : 0, length(sub), pointer(g), isempty(sub) ? C_NULL : pointer(sub),
+                               device, 0, (0, 0)))
+        rc = ccall((:qc_sweep_create, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Ptr{Cvoid}}), desc, h)
+        rc == 0 || error("qc_sweep_create: " * unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
+    end
+    rc = GC.@preserve Z⃗ init θt ct ξv w fids grad ∇ξ ccall((:qc_sweep_noise_grad, LIB[]), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        h[], Z⃗, init, S, θt, isempty(ct) ? C_NULL : pointer(ct), ξv, isempty(w) ? C_NULL : pointer(w), fids, J, grad, C_NULL, ∇ξ)
+    msg = rc == 0 ? "" : unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), h[]))      # out of scope: the library's reason
+    ccall((:qc_sweep_destroy, LIB[]), Cvoid, (Ptr{Cvoid},), h[])
+    rc == 0 || error("qc_sweep_noise_grad: " * msg)
+    G = reshape(grad, m + 1, T)
+    return J[], fids, G[1:m, :], G[m + 1, :], ∇ξ
+end
+
+"""
     rollout_sweep_parameter_gradient(init, controls, Δt, G_drift, G_drives, G_pert, θ; scale=nothing, cols, goal, fid_kind=0,
                                      subspace=nothing, squared=false, device=0)  ->  (fids, ∇θ, ∇c)
 

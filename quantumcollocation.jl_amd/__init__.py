@@ -18,12 +18,12 @@ from .objectives import (DensityOperatorPureStateInfidelityObjective, FinalQuant
                          QuantumStateObjective, iso_fidelity, MinimumTimeObjective, QuadraticRegularizer, TimeStepsAllEqualConstraint,
                          TrajectoryObjective, UnitaryInfidelityObjective, iso_vec_unitary_fidelity, iso_vec_unitary_free_phase_fidelity,
                          UnitaryFreePhaseInfidelityObjective, FinalUnitaryFreePhaseFidelityConstraint, UnitaryRobustnessObjective,
-                         QuadraticSmoothnessRegularizer, PairwiseQuadraticRegularizer, L1Regularizer, L1SlackConstraint, slack_names, SweepInfidelityObjective, SweepFinalStateObjective)
+                         QuadraticSmoothnessRegularizer, PairwiseQuadraticRegularizer, L1Regularizer, L1SlackConstraint, slack_names, SweepInfidelityObjective, SweepNoiseInfidelityObjective, SweepFinalStateObjective)
 from .problems import (CONFIGS, config_inputs, density_operator_smooth_pulse_inputs, multi_qubit_system, quantum_state_sampling_inputs, quantum_state_smooth_pulse_inputs,
                        unitary_bang_bang_inputs, unitary_direct_sum_inputs, unitary_robustness_problem, unitary_sampling_inputs, unitary_smooth_pulse_inputs,
                        ControlProblemInputs, unitary_smooth_pulse_problem, unitary_direct_sum_problem, direct_sum_graph, add_l1_slacks)
 from .quantum_systems import OpenQuantumSystem, QuantumSystem
-from .rollouts import (RolloutSweep, open_rollout, rollout, rollout_fidelity, rollout_fidelity_sweep, rollout_sweep, rollout_sweep_parameter_gradient, unitary_rollout,
+from .rollouts import (RolloutSweep, open_rollout, rollout, rollout_fidelity, rollout_fidelity_sweep, rollout_noise_sweep, rollout_sweep, rollout_sweep_parameter_gradient, unitary_rollout,
                        unitary_rollout_fidelity, unitary_rollout_fidelity_sweep)
 from .trajectory_initialization import initialize_trajectory, unitary_geodesic
 
@@ -38,7 +38,7 @@ __all__ = [
     "FinalUnitaryFreePhaseFidelityConstraint", "UnitaryInfidelityObjective", "FinalUnitaryFidelityConstraint", "QuantumStateObjective", "FinalQuantumStateFidelityConstraint", "DensityOperatorPureStateInfidelityObjective", "iso_fidelity",
     "QuadraticRegularizer", "MinimumTimeObjective", "TrajectoryObjective", "TimeStepsAllEqualConstraint",
     "OpenQuantumSystem", "DensityOperatorExponentialIntegrator", "density_operator_smooth_pulse_inputs",
-    "density_to_iso_vec", "iso_vec_to_density", "iso_operator", "unitary_rollout", "rollout", "open_rollout", "unitary_rollout_fidelity", "rollout_fidelity", "RolloutSweep", "SweepInfidelityObjective", "SweepFinalStateObjective", "rollout_sweep", "rollout_sweep_parameter_gradient", "unitary_rollout_fidelity_sweep", "rollout_fidelity_sweep", "make_desc", "desc_dims", "desc_structures", "state_row_offset", "QCollocError",
+    "density_to_iso_vec", "iso_vec_to_density", "iso_operator", "unitary_rollout", "rollout", "open_rollout", "unitary_rollout_fidelity", "rollout_fidelity", "RolloutSweep", "SweepInfidelityObjective", "SweepNoiseInfidelityObjective", "SweepFinalStateObjective", "rollout_sweep", "rollout_noise_sweep", "rollout_sweep_parameter_gradient", "unitary_rollout_fidelity_sweep", "rollout_fidelity_sweep", "make_desc", "desc_dims", "desc_structures", "state_row_offset", "QCollocError",
     "EmbeddedOperator", "UnitaryRobustnessObjective", "unitary_robustness_problem", "ControlProblemInputs",
     "QuadraticSmoothnessRegularizer", "PairwiseQuadraticRegularizer", "L1Regularizer", "L1SlackConstraint", "slack_names",
     "unitary_smooth_pulse_problem", "unitary_direct_sum_problem", "direct_sum_graph", "add_l1_slacks",

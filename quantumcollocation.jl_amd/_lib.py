@@ -343,6 +343,14 @@ SYMBOLS = {
                                _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "qc_sweep_hvp_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qc_sweep_desc_noise_supported": (C.c_int, [_SDESC_P, C.POINTER(C.c_int32)]),
+    "qc_sweep_noise_eval": (C.c_int, [_H, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "qc_sweep_noise_eval_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "qc_sweep_noise_grad": (C.c_int, [_H, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                      _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "qc_sweep_noise_grad_dev": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qc_debug_read_stamps": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_int64]),
     "qc_debug_host_expand_rate": (C.c_int, [_H, C.c_int32, _c_double_p]),
     "qc_debug_list_shares_launch": (C.c_int, [C.POINTER(_H), C.c_int32, C.c_int32]),

@@ -412,6 +412,9 @@ extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
     h->vjp_ok = qc_sweep_vjp_scope(d, &h->vjp_why);
     h->jvp_ok = qc_sweep_jvp_scope(d, &h->jvp_why);
     h->hvp_ok = qc_sweep_hvp_scope(d, &h->hvp_why);
+    h->noise_ok = qc_sweep_noise_scope(d, &h->noise_why);
+    h->noise_grad_ok = h->noise_ok && h->grad_ok;
+    h->noise_grad_why = h->noise_ok ? h->grad_why : h->noise_why;
     const int N = d->N, n = 2 * N, n2 = n * n, m = d->m, p = d->n_pert;
     h->n = n;
     h->nc = d->state_cols == 0 ? N : d->state_cols;
@@ -484,6 +487,27 @@ static int eval_check(qc_sweep* h, const char* who, const double* Z, const doubl
     return QC_OK;
 }
 
+// the second launch: qc_sweep_finish_kernel, one workgroup per sample
+static int finish_launch(qc_sweep* h, const FinParams& F, int64_t S, const double* src, double* dfinals, double* dfids, hipStream_t st) {
+    const size_t lds = ((size_t)2 * h->ns + (size_t)F.ld * F.ld) * 8;
+    if (lds > 64 * 1024)
+        QC_SIDE_HIP(h, g_swerr, hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(qc_sweep_finish_kernel, dim3((unsigned)S), dim3(kFinT), lds, st, F, (const double*)h->dTot.p, src, (const double*)h->dgr,
+                       (const double*)h->dgi, dfinals, dfids);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return qc_sweep_fail(h, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return QC_OK;
+}
+
+// MFMA forms: the same launch on the chunk totals in h->dTot, for the noise sweep of qc_sweep_noise.hip
+int qc_sweep_launch_finish(qc_sweep* h, int64_t S, int64_t n_chunks, const double* dinit, double* dfinals, double* dfids, hipStream_t st) {
+    FinParams F;
+    F.n = h->n; F.ns = h->ns;
+    F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;
+    F.ld = h->mfma32 ? 32 : 16; F.n_chunks = (int)n_chunks; F.src_stride = 0;
+    return finish_launch(h, F, S, dinit, dfinals, dfids, st);
+}
+
 static int qc_sweep_eval_launch(qc_sweep* h, const char* who, const double* dZ, const double* dinit, int64_t S, const double* dtheta,
                                 const double* dscale, double* dfinals, double* dfids, void* stream) {
     int rc = eval_check(h, who, dZ, dinit, S, dtheta, dfinals, dfids);
@@ -518,14 +542,7 @@ static int qc_sweep_eval_launch(qc_sweep* h, const char* who, const double* dZ, 
         F.ld = n; F.n_chunks = 0; F.src_stride = h->ns;
         src = h->dFin.p;
     }
-    const size_t lds = ((size_t)2 * h->ns + (size_t)F.ld * F.ld) * 8;
-    if (lds > 64 * 1024)
-        QC_SIDE_HIP(h, g_swerr, hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(qc_sweep_finish_kernel, dim3((unsigned)S), dim3(kFinT), lds, st, F, (const double*)h->dTot.p, src, (const double*)h->dgr,
-                       (const double*)h->dgi, dfinals, dfids);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return qc_sweep_fail(h, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return QC_OK;
+    return finish_launch(h, F, S, src, dfinals, dfids, st);
 }
 
 extern "C" int qc_sweep_eval_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,

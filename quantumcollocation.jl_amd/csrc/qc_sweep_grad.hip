@@ -530,6 +530,30 @@ void qc_sweep16_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const doub
                            (int)n_chunks, p, m, (const double*)h->dPart.p, dgrad_theta, dgrad_scale);
 }
 
+// Launch 2 (the fidelity's seed) and launch 4 (the weighted reductions) of a gradient call, for the entry points below and the noise sweep
+// of qc_sweep_noise.hip.  The seed reads the chunk totals of h->dTot and writes h->dXs / h->dLs (grown by the caller) and the S fidelities.
+void qc_sweep_launch_fid_seed(qc_sweep* h, int64_t S, int64_t n_chunks, const double* dinit, double* dfids, hipStream_t st) {
+    SeedParams F;
+    F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
+    F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;
+    const size_t lds = qc_sweep_seed::lds_bytes(h->ns, h->mfma32 ? 32 : 16);      // at most 16 state columns: 16 KiB
+    const auto seed = h->mfma32 ? qc_sweep32_seed_kernel : qc_sweep_seed_kernel;
+    hipLaunchKernelGGL(seed, dim3((unsigned)S), dim3(kSeedT), lds, st, F, (const double*)h->dTot.p, dinit, (const double*)h->dgr,
+                       (const double*)h->dgi, h->dXs.p, h->dLs.p, dfids);
+}
+
+// dgrad = sum_s w_s gsamp[s] over Z (qc_sweep_grad_reduce_kernel) and dJ = sum_s w_s dfids[s] (qc_sweep_J_kernel); either may be NULL
+void qc_sweep_launch_weighted(qc_sweep* h, int64_t S, const double* gsamp, const double* dweights, const double* dfids, double* dgrad, double* dJ,
+                              hipStream_t st) {
+    if (dgrad) {
+        ReduceParams R;
+        R.zdim = h->d.zdim; R.off_a = h->d.off_a; R.off_dt = h->d.off_dt; R.m = h->d.m; R.nd = h->d.m + (h->d.off_dt >= 0 ? 1 : 0);
+        R.T = h->d.T; R.Zlen = h->Zlen; R.S = S;
+        hipLaunchKernelGGL(qc_sweep_grad_reduce_kernel, dim3((unsigned)((h->Zlen + kRedT - 1) / kRedT)), dim3(kRedT), 0, st, R, gsamp, dweights, dgrad);
+    }
+    if (dJ) hipLaunchKernelGGL(qc_sweep_J_kernel, dim3(1), dim3(kRedT), 0, st, (long long)S, dfids, dweights, dJ);
+}
+
 // the argument checks of all four entry points, in the order of the header
 static int grad_check(qc_sweep* h, const char* who, const double* Z, const double* init, int64_t S, const double* theta, bool any_out, bool g_theta,
                       bool g_scale) {
@@ -575,25 +599,12 @@ static int qc_sweep_grad_launch(qc_sweep* h, const char* who, const double* dZ, 
         gsamp = h->dGsamp.p;
     }
     if (want_par) QC_SIDE_HIP(h, slot, h->grow(h->dPart, (size_t)S * n_chunks * (p + m)));
-    SeedParams F;
-    F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
-    F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;
-    const size_t lds = qc_sweep_seed::lds_bytes(h->ns, h->mfma32 ? 32 : 16);      // at most 16 state columns: 16 KiB
-    const auto seed = h->mfma32 ? qc_sweep32_seed_kernel : qc_sweep_seed_kernel;
-    hipLaunchKernelGGL(seed, dim3((unsigned)S), dim3(kSeedT), lds, st, F, (const double*)h->dTot.p, dinit, (const double*)h->dgr,
-                       (const double*)h->dgi, h->dXs.p, h->dLs.p, dfids);
+    qc_sweep_launch_fid_seed(h, S, n_chunks, dinit, dfids, st);
     if (h->mfma32) {      // the 2 x 2-tile form: its own walk (qc_sweep32_grad.hip), then the reductions below
         if (want_grad) qc_sweep32_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, gsamp, st);
     } else if (want_grad || want_par)
         qc_sweep16_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);
-    if (dgrad) {
-        ReduceParams R;
-        R.zdim = h->d.zdim; R.off_a = h->d.off_a; R.off_dt = h->d.off_dt; R.m = m; R.nd = nd;
-        R.T = h->d.T; R.Zlen = h->Zlen; R.S = S;
-        hipLaunchKernelGGL(qc_sweep_grad_reduce_kernel, dim3((unsigned)((h->Zlen + kRedT - 1) / kRedT)), dim3(kRedT), 0, st, R, (const double*)gsamp,
-                           dweights, dgrad);
-    }
-    if (dJ) hipLaunchKernelGGL(qc_sweep_J_kernel, dim3(1), dim3(kRedT), 0, st, (long long)S, (const double*)dfids, dweights, dJ);
+    qc_sweep_launch_weighted(h, S, gsamp, dweights, dfids, dgrad, dJ, st);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return qc_sweep_fail(h, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return QC_OK;

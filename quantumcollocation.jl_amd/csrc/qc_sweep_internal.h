@@ -1,5 +1,5 @@
 // What qc_sweep.hip (forward sweep), qc_sweep_grad.hip (its adjoint), qc_sweep_vjp.hip (the pullback of the final states),
-// qc_sweep_jvp.hip (their pushforward) and qc_sweep_hvp.hip (the tangent of the pullback) share: the handle with its scratch and staging buffers, the descriptor and argument checks and
+// qc_sweep_jvp.hip (their pushforward), qc_sweep_hvp.hip (the tangent of the pullback) and qc_sweep_noise.hip (noise trajectories) share: the handle with its scratch and staging buffers, the descriptor and argument checks and
 // the launch of the forward chunk totals (with it the chunk rule).  Not part of the ABI.
 #pragma once
 
@@ -19,18 +19,22 @@ struct qc_sweep : qc_side {
     std::string jvp_why;
     bool hvp_ok = false;         // the Hessian product's scope (qc_sweep_hvp.hip): what the pullback and the pushforward both serve
     std::string hvp_why;
+    bool noise_ok = false;       // the noise sweep's scope (qc_sweep_noise.hip): "mfma16-sweep", n_pert >= 1, m + n_pert <= 8 tiles
+    std::string noise_why;
+    bool noise_grad_ok = false;  // its gradient's scope: the noise scope and the gradient's together
+    std::string noise_grad_why;  // the noise scope's reason, else the gradient's own
     int n = 0, nc = 0, ns = 0, fid_n = 0;
     int64_t Zlen = 0;
     double* dG = nullptr;        // (1 + m + p) matrices, column-major (per-sample form)
     double* dImg = nullptr;      // their A-layout images (MFMA form)
     double *dgr = nullptr, *dgi = nullptr;
     // Scratch of the "_dev" entry points, grown at the first call that needs it.  Largest request of a call, and who makes it:
-    qc_buf dTot;         // chunk totals, S x n_chunks x 256 (mfma32: 1024)                  eval, grad, vjp
+    qc_buf dTot;         // chunk totals, S x n_chunks x 256 (mfma32: 1024)                  eval, grad, vjp, noise
     qc_buf dFin;         // per-sample form: final states, S x ns                             eval
     double *dGs = nullptr, *dRE = nullptr, *dRQ = nullptr, *dRS = nullptr, *dRout = nullptr;      // per-sample form, sized at create
-    qc_buf dXs, dLs;     // x and lambda at the chunk ends, S x n_chunks x ns each            grad, vjp
-    qc_buf dGsamp;       // per-interval derivatives when the caller keeps none, S x (T-1) x nd   grad, vjp
-    qc_buf dGfid;        // fidelities when the caller keeps none, S                         grad
+    qc_buf dXs, dLs;     // x and lambda at the chunk ends, S x n_chunks x ns each            grad, vjp, noise_grad
+    qc_buf dGsamp;       // per-interval derivatives when the caller keeps none, S x (T-1) x nd   grad, vjp, noise_grad
+    qc_buf dGfid;        // fidelities when the caller keeps none, S                         grad, noise_grad
     qc_buf dPart;        // chunk shares of the parameter gradients, S x n_chunks x (p + m)  grad_params, vjp
     qc_buf dTotJ;        // chunk totals and their tangents, S x n_chunks x 512              jvp, hvp
     qc_buf dXsT, dLsT;   // xdot and lambdadot at the chunk ends, S x n_chunks x ns each      hvp (x and lambda: dXs, dLs)
@@ -56,6 +60,8 @@ struct qc_sweep : qc_side {
     qc_buf sTgrad;       // the dense tangent of the gradient, Zlen                           hvp
     qc_buf sTgradS;      // its per-sample form, S x (T-1) x nd                               hvp
     qc_buf sTginit;      // the tangent of grad_init, S x ns                                  hvp
+    qc_buf sNoise;       // noise, S x (T-1) x p                                              noise_eval, noise_grad
+    qc_buf sGnoise;      // grad_noise, S x (T-1) x p                                         noise_grad
 };
 
 // records the message in the handle (when there is one) and in the slot qc_sweep_last_error(NULL) returns
@@ -113,3 +119,12 @@ int qc_sweep_jvp_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const d
 void qc_sweep_launch_plain_sum(qc_sweep* h, int64_t S, const double* gs, double* dgrad, hipStream_t st);
 // the Hessian product's scope (qc_sweep_hvp.hip): the pullback's, within the "mfma16-sweep" form
 bool qc_sweep_hvp_scope(const qc_sweep_desc* d, std::string* why);
+// the second launch of an evaluation on an MFMA form (qc_sweep.hip): qc_sweep_finish_kernel on the chunk totals in h->dTot
+int qc_sweep_launch_finish(qc_sweep* h, int64_t S, int64_t n_chunks, const double* dinit, double* dfinals, double* dfids, hipStream_t st);
+// launches 2 and 4 of a gradient call (qc_sweep_grad.hip): the fidelity's seed (reads h->dTot; writes h->dXs / h->dLs, grown by the caller,
+// and the S fidelities), and grad = sum_s w_s gsamp[s] / J = sum_s w_s fids[s] (either may be NULL)
+void qc_sweep_launch_fid_seed(qc_sweep* h, int64_t S, int64_t n_chunks, const double* dinit, double* dfids, hipStream_t st);
+void qc_sweep_launch_weighted(qc_sweep* h, int64_t S, const double* gsamp, const double* dweights, const double* dfids, double* dgrad, double* dJ,
+                              hipStream_t st);
+// the noise sweep's scope (qc_sweep_noise.hip): the "mfma16-sweep" form, n_pert >= 1, m + n_pert <= 8
+bool qc_sweep_noise_scope(const qc_sweep_desc* d, std::string* why);

@@ -832,6 +832,56 @@ class SweepInfidelityObjective:
             pass
 
 
+class SweepNoiseInfidelityObjective(SweepInfidelityObjective):
+    """L(Z) = 1 - sum_s w_s F_s over S noise realisations: `SweepInfidelityObjective` with perturbation amplitudes that change from
+    interval to interval,
+
+        G_{s,t} = G_drift + sum_j (theta[s, j] + noise[s, t, j]) P_j + sum_k scale[s, k] a_{t,k} G_k
+
+    (`RolloutSweep.noise_eval` / `noise_grad`: one sweep per value, one adjoint sweep per gradient).  The realisations are fixed at
+    construction (common random numbers: the same S noise trajectories at every iterate), so L is a smooth deterministic function of
+    the pulse.  Interface and first-order rule of `SweepInfidelityObjective`.
+
+    noise       S x (T-1) x len(perturbations), or S x (T-1) with one perturbation: it gives S
+    theta       S x len(perturbations) or None (zeros);  scale  S x n_drives or None;  weights  S values or None (1/S each)
+    `noise_sensitivity(Z)` returns dF_s/dnoise[s, t, j], S x (T-1) x len(perturbations): the time-domain filter function of the pulse."""
+
+    def __init__(self, traj: NamedTrajectory, system, perturbations, noise, theta=None, scale=None, weights=None, state_name: str = "Ũ⃗",
+                 control_name: str = "a", subspace=None, form: str = "abs", device: int = 0):
+        p = len(perturbations)
+        if noise is None:
+            raise ValueError("noise is required: S x (T-1) x len(perturbations)")
+        noise = np.asarray(noise, dtype=np.float64)
+        if noise.ndim == 2 and p == 1:
+            noise = noise[:, :, None]
+        if noise.ndim != 3 or noise.shape[0] < 1 or noise.shape[1:] != (traj.T - 1, p):
+            raise ValueError(f"noise must be S x {traj.T - 1} x {p}")
+        if theta is None:
+            theta = np.zeros((noise.shape[0], p))
+        super().__init__(traj, system, perturbations, theta, scale=scale, weights=weights, state_name=state_name, control_name=control_name,
+                         subspace=subspace, form=form, device=device)
+        sw = self._sweep
+        if self.S != noise.shape[0]:
+            sw.close()
+            raise ValueError(f"theta / scale give {self.S} samples, noise gives {noise.shape[0]}")
+        if not sw.noise_supported:
+            why = sw.noise_unsupported_reason
+            sw.close()
+            raise _lib.QCollocError(_lib.QC_ERR_UNSUPPORTED, why)
+        self._noise = np.ascontiguousarray(noise)
+
+    def J_fids_grad(self, Z):
+        """(J, fids, dJ/dZ) of one adjoint sweep."""
+        return self._sweep.noise_grad(Z, self._init, self._noise, self._theta, self._scale, self._weights)[:3]
+
+    def fidelities(self, Z) -> np.ndarray:
+        return self._sweep.noise_eval(Z, self._init, self._noise, self._theta, self._scale, finals=False)[1]
+
+    def noise_sensitivity(self, Z) -> np.ndarray:
+        """dF_s/dnoise[s, t, j], S x (T-1) x len(perturbations), raw per-sample values."""
+        return self._sweep.noise_grad(Z, self._init, self._noise, self._theta, self._scale, self._weights)[3]
+
+
 class SweepFinalStateObjective:
     """L(Z) = loss(X): any function, written in torch, of the final states of the trajectory's pulse over S perturbed systems (the
     systems of `SweepInfidelityObjective`).  X is the S x (2N cols) float64 device tensor of `RolloutSweep.finals_autograd`, row s the

@@ -23,6 +23,9 @@ the loop of the reference's robustness check, `unitary_rollout(traj.a, timesteps
                                                                             fidelities along one direction, open systems included
     RolloutSweep.hvp / .hvp_device                                          the tangent of the pullback (`qc_sweep_hvp*`): exact Hessian products of
                                                                             any loss of the final states
+    rollout_noise_sweep(init, controls, Δt, system, perturbations, ξ, θ)   (finals, fids) under per-interval perturbations ξ[s, t, j]
+    RolloutSweep.noise_eval / .noise_grad (+ _device)                       noise trajectories (`qc_sweep_noise_*`): the sweep and its gradient with
+                                                                            θ[s, j] + ξ[s, t, j] in interval t, and dF_s/dξ[s, t, j] of every sample
 """
 from __future__ import annotations
 
@@ -650,6 +653,145 @@ class RolloutSweep:
         if rc != _lib.QC_OK:
             raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
 
+    # -- noise trajectories: perturbation amplitudes that change from interval to interval ---------------------------------------------
+    @property
+    def noise_supported(self) -> bool:
+        """Do `noise_eval` / `noise_eval_device` serve this handle?  (`qc_sweep_desc_noise_supported`: the "mfma16-sweep" form, at least
+        one perturbation, drives and perturbations together at most 8.)  `noise_unsupported_reason` says why not.  `noise_grad` also
+        needs `grad_supported`."""
+        return self._noise_scope()[0]
+
+    @property
+    def noise_unsupported_reason(self) -> Optional[str]:
+        return self._noise_scope()[1]
+
+    def _noise_scope(self):
+        ok = C.c_int32()
+        rc = _lib.lib.qc_sweep_desc_noise_supported(C.byref(self._desc), C.byref(ok))
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(None).decode())
+        return bool(ok.value), (None if ok.value else _lib.lib.qc_sweep_last_error(None).decode())
+
+    def _noise_samples(self, noise, theta, scale):
+        """(S, noise S x (T-1) x p, theta S x p, scale S x m or None): the noise gives S; theta None means zeros."""
+        if noise is None:
+            raise ValueError("noise is required: S x (T-1) x n_pert")
+        noise = np.asarray(noise, dtype=np.float64)
+        if noise.ndim == 2 and self.p == 1:
+            noise = noise[:, :, None]
+        if noise.ndim != 3 or noise.shape[0] < 1 or noise.shape[1:] != (self.T - 1, self.p):
+            raise ValueError(f"noise must be S x {self.T - 1} x {self.p}" + (f" (or S x {self.T - 1})" if self.p == 1 else ""))
+        S = noise.shape[0]
+        if theta is None:
+            theta = np.zeros((S, self.p))
+        S2, theta, scale = _sweep_samples(self.p, self.m, theta, scale)
+        if S2 != S:
+            raise ValueError(f"theta / scale give {S2} samples, noise gives {S}")
+        return S, np.ascontiguousarray(noise), theta, scale
+
+    def _host_Z_init(self, Z, init):
+        Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
+        if Z.size != self.Z_len:
+            raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
+        init = np.ascontiguousarray(init, dtype=np.float64).ravel()
+        if init.size != self.ns:
+            raise ValueError(f"initial state has length {init.size}, expected {self.ns}")
+        return Z, init
+
+    def noise_eval(self, Z, init, noise, theta=None, scale=None, finals: bool = True, fids: Optional[bool] = None):
+        """`eval` with a noise trajectory per sample: in interval t sample s sees theta[s, j] + noise[s, t, j] on perturbation j
+        (`qc_sweep_noise_eval`).  noise: S x (T-1) x n_pert (S x (T-1) when n_pert = 1); theta: S x n_pert or None = zeros.
+        Returns (finals, fids) as `eval`."""
+        Z, init = self._host_Z_init(Z, init)
+        S, noise, theta, scale = self._noise_samples(noise, theta, scale)
+        if fids is None:
+            fids = self.fid_kind != _lib.QC_SWEEP_FID_NONE
+        out = np.empty((S, self.ns)) if finals else None
+        f = np.empty(S) if fids else None
+        opt = lambda a: _lib.dptr(a) if (a is not None and a.size) else None
+        rc = _lib.lib.qc_sweep_noise_eval(self._h, _lib.dptr(Z), _lib.dptr(init), S, opt(theta), opt(scale), opt(noise), opt(out), opt(f))
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        return (np.ascontiguousarray(out.T) if finals else None), f
+
+    def _device_theta(self, dtheta, S, like):
+        """theta=None means zeros: one zero tensor per S, kept by the handle."""
+        if dtheta is not None or not self.p:
+            return dtheta
+        z = getattr(self, "_zero_theta", None)
+        if z is None or z.numel() != S * self.p or z.device != like.device:
+            z = self._zero_theta = torch.zeros(S * self.p, dtype=torch.float64, device=like.device)
+        return z
+
+    def noise_eval_device(self, dZ, dinit, dnoise, dtheta=None, dscale=None, dfinals=None, dfids=None, stream=None):
+        """Device-resident `noise_eval` on torch CUDA tensors (float64), asynchronous on `stream`: `qc_sweep_noise_eval_dev`.  dnoise
+        S x (T-1) x n_pert gives S; dtheta S x n_pert or None = zeros; dscale S x m or None; dfinals S x (2N cols) or None; dfids S
+        or None."""
+        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        if dnoise is None:
+            raise ValueError("dnoise is required")
+        per = (self.T - 1) * self.p
+        if not per or dnoise.numel() % per or not dnoise.numel():
+            raise ValueError(f"dnoise must hold S x {self.T - 1} x {self.p} entries")
+        S = dnoise.numel() // per
+        if dfinals is None and dfids is None:
+            raise ValueError("dfinals and dfids are both None")
+        dtheta = self._device_theta(dtheta, S, dnoise)
+        for t, cnt, what in ((dZ, self.Z_len, "dZ"), (dinit, self.ns, "dinit"), (dnoise, S * per, "dnoise"), (dtheta, S * self.p, "dtheta"),
+                             (dscale, S * self.m, "dscale"), (dfinals, S * self.ns, "dfinals"), (dfids, S, "dfids")):
+            if t is not None and (t.numel() != cnt or t.dtype != torch.float64 or not t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous float64 tensor of {cnt} entries")
+        ptr = lambda t, use=True: t.data_ptr() if (t is not None and use and t.numel()) else None
+        rc = _lib.lib.qc_sweep_noise_eval_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dnoise),
+                                              ptr(dfinals), ptr(dfids), s)
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+
+    def noise_grad(self, Z, init, noise, theta=None, scale=None, weights=None, per_sample: bool = False):
+        """(J, fids, grad, grad_noise[, grad_samples]) under the noise trajectories of `noise_eval` (`qc_sweep_noise_grad`): J, fids and
+        the dense gradient as `grad` returns them, and grad_noise[s, t, j] = dF_s/dnoise[s, t, j], S x (T-1) x n_pert, raw per-sample
+        values -- the time-resolved noise sensitivity of every sample.  With `per_sample` also dF_s/d(a_t, dt_t) as in `grad`."""
+        Z, init = self._host_Z_init(Z, init)
+        S, noise, theta, scale = self._noise_samples(noise, theta, scale)
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+            if weights.size != S:
+                raise ValueError(f"weights must have {S} entries")
+        f, J, g, gn = np.empty(S), C.c_double(), np.empty(self.Z_len), np.empty((S, self.T - 1, self.p))
+        gs = np.empty((S, self.T - 1, self.n_deriv)) if per_sample else None
+        opt = lambda a: _lib.dptr(a) if (a is not None and a.size) else None
+        rc = _lib.lib.qc_sweep_noise_grad(self._h, _lib.dptr(Z), _lib.dptr(init), S, opt(theta), opt(scale), opt(noise), opt(weights), _lib.dptr(f),
+                                          C.byref(J), _lib.dptr(g), opt(gs), opt(gn))
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        return (J.value, f, g, gn, gs) if per_sample else (J.value, f, g, gn)
+
+    def noise_grad_device(self, dZ, dinit, dnoise, dtheta=None, dscale=None, dweights=None, dfids=None, dJ=None, dgrad=None, dgrad_samples=None,
+                          dgrad_noise=None, stream=None):
+        """Device-resident `noise_grad`: `qc_sweep_noise_grad_dev`.  dnoise S x (T-1) x n_pert gives S.  Outputs are optional one at
+        a time: dfids S, dJ one value, dgrad Z_len, dgrad_samples S x (T-1) x n_deriv, dgrad_noise S x (T-1) x n_pert."""
+        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        if dnoise is None:
+            raise ValueError("dnoise is required")
+        per = (self.T - 1) * self.p
+        if not per or dnoise.numel() % per or not dnoise.numel():
+            raise ValueError(f"dnoise must hold S x {self.T - 1} x {self.p} entries")
+        S = dnoise.numel() // per
+        if all(t is None for t in (dfids, dJ, dgrad, dgrad_samples, dgrad_noise)):
+            raise ValueError("every output is None")
+        dtheta = self._device_theta(dtheta, S, dnoise)
+        for t, cnt, what in ((dZ, self.Z_len, "dZ"), (dinit, self.ns, "dinit"), (dnoise, S * per, "dnoise"), (dtheta, S * self.p, "dtheta"),
+                             (dscale, S * self.m, "dscale"), (dweights, S, "dweights"), (dfids, S, "dfids"), (dJ, 1, "dJ"),
+                             (dgrad, self.Z_len, "dgrad"), (dgrad_samples, S * (self.T - 1) * self.n_deriv, "dgrad_samples"),
+                             (dgrad_noise, S * per, "dgrad_noise")):
+            if t is not None and (t.numel() != cnt or t.dtype != torch.float64 or not t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous float64 tensor of {cnt} entries")
+        ptr = lambda t, use=True: t.data_ptr() if (t is not None and use and t.numel()) else None
+        rc = _lib.lib.qc_sweep_noise_grad_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dnoise),
+                                              ptr(dweights), ptr(dfids), ptr(dJ), ptr(dgrad), ptr(dgrad_samples), ptr(dgrad_noise), s)
+        if rc != _lib.QC_OK:
+            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+
     def finals_autograd(self, dZ, dinit, dtheta=None, dscale=None):
         """The S x (2N cols) final states as a differentiable torch tensor: forward is `eval_device` on the current stream, backward one
         `vjp_device` call, and under `torch.autograd.forward_ad` the tangent is one `jvp_device` call ("mfma16-sweep" handles).  dZ
@@ -742,6 +884,26 @@ def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None,
     sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device, wide=wide)
     try:
         return sw.eval(sw.pack(controls, dts), init, theta, scale)
+    finally:
+        sw.close()
+
+
+def rollout_noise_sweep(init, controls, dts, system, perturbations, noise, theta=None, scale=None, cols: Optional[int] = None, goal=None,
+                        fid_kind=None, subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS):
+    """(finals, fids) of S rollouts whose perturbation amplitudes change from interval to interval: in interval t sample s sees
+    theta[s, j] + noise[s, t, j] on perturbation j.  noise is S x (T-1) x len(perturbations) (S x (T-1) for one perturbation), theta
+    S x len(perturbations) or None (zeros); everything else as `rollout_sweep`."""
+    controls = np.asarray(controls, dtype=np.float64)
+    if controls.ndim != 2 or controls.shape[0] != system.n_drives:
+        raise ValueError("controls must be n_drives x T")
+    T = controls.shape[1]
+    init = np.ascontiguousarray(init, dtype=np.float64).ravel()
+    n = 2 * system.state_levels
+    if cols is None:
+        cols = init.size // n
+    sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device)
+    try:
+        return sw.noise_eval(sw.pack(controls, dts), init, noise, theta, scale)
     finally:
         sw.close()
 
