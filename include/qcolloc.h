@@ -627,21 +627,31 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * With wide = QC_SWEEP_WIDE the matrix cores serve 16 < 2N <= 32 (up to 8 drives) as well ("mfma32-sweep": 2 x 2 tiles a matrix, the same
  * work item and chunk rule); 2N <= 16 is "mfma16-sweep" as before, everything else the per-sample form.  wide = 0 is the routing of the
  * two sentences above, unchanged; any other value is QC_ERR_INVALID.
+ * reserved1[0] = QC_SWEEP_STORED_STATES chooses reverse mode by the STORED-STATE walk: qc_sweep_grad*, qc_sweep_grad_params* and
+ * qc_sweep_vjp* then keep the forward states x_0 .. x_{T-2} of every sample in handle scratch (S x (T-1) x 2N x cols doubles) and read
+ * them on the way back instead of reversing the step, which serves ANY generators in the "mfma16-sweep" form: Lindblad generators
+ * (N = levels^2) with QC_FID_DENSITY, non-Hermitian effective Hamiltonians.  A handle with the flag takes that walk whatever its
+ * generators, antisymmetric ones included.  reserved1[0] = 0 is everything as it was, bit for bit; any other value is QC_ERR_INVALID;
+ * reserved1[1] is ignored.  qc_sweep_eval*, qc_sweep_jvp*, qc_sweep_noise_eval* do not look at the flag, and qc_sweep_hvp* /
+ * qc_sweep_noise_grad* keep their scope (antisymmetric generators) and their kernels with it.
  * Results do not depend on scheduling: repeated calls return the same bits.  Non-finite inputs are evaluated, not rejected.
  * Gradients with respect to the controls and timesteps (qc_sweep_grad*) and to the samples' own parameters theta and `scale`
- * (qc_sweep_grad_params*), both below, are served for closed systems in the MFMA forms (parameter gradients: "mfma16-sweep" only).
+ * (qc_sweep_grad_params*), both below, are served for closed systems in the MFMA forms (parameter gradients: "mfma16-sweep" only), and
+ * with reserved1[0] = QC_SWEEP_STORED_STATES for open systems in the "mfma16-sweep" form.
  * Derivatives of the final states themselves, contracted with cotangents the caller chooses (qc_sweep_vjp*, below), carry any function
  * of the final states: leakage, the free-phase fidelity, several kets at once, a loss written elsewhere.
  * The forward-mode counterpart, the tangent of the final states and fidelities along one direction (qc_sweep_jvp*, below), is served
  * for "mfma16-sweep" handles with any generators, Lindblad ones included; with the pullback it gives Gauss-Newton products of any loss.
  * The tangent of the pullback along one direction (qc_sweep_hvp*, below) gives exact Hessian products of any loss of the final states
  * where both of them are served (closed systems, "mfma16-sweep").
- * Out of scope: per-knot outputs, open-system gradients (reverse mode needs stored forward states; their directional derivatives are
- * qc_sweep_jvp's), pushforwards on "mfma32-sweep" and "rollout-per-sample" handles (Hessian products likewise), several directions per
+ * Out of scope: per-knot outputs, open-system gradients in the "mfma32-sweep" form (2N > 16: the stored-state walk is built for
+ * "mfma16-sweep" only; their directional derivatives are not served there either), Hessian products and noise gradients of open
+ * systems, pushforwards on "mfma32-sweep" and "rollout-per-sample" handles (Hessian products likewise), several directions per
  * call, tangents of grad_theta / grad_scale, several devices. */
 #define QC_MAX_PERT 8
 #define QC_SWEEP_FID_NONE (-1)   /* qc_sweep_desc.fid_kind: final states only */
 #define QC_SWEEP_WIDE 1          /* qc_sweep_desc.wide */
+#define QC_SWEEP_STORED_STATES 1 /* qc_sweep_desc.reserved1[0]: reverse mode by the stored-state walk */
 typedef struct qc_sweep_desc {
     int64_t T;
     int32_t zdim;
@@ -663,7 +673,7 @@ typedef struct qc_sweep_desc {
     const int32_t* subspace;     /* unitary only: 0-based levels, or NULL = all */
     int32_t device;
     int32_t wide;                /* 0, or QC_SWEEP_WIDE: the matrix-core form up to 2N = 32 ("mfma32-sweep"); anything else is QC_ERR_INVALID */
-    int64_t reserved1[2];
+    int64_t reserved1[2];        /* [0]: 0, or QC_SWEEP_STORED_STATES: reverse mode reads stored forward states (any generators, "mfma16-sweep"); anything else is QC_ERR_INVALID.  [1]: ignored */
 } qc_sweep_desc;
 typedef struct qc_sweep qc_sweep;
 int64_t qc_sizeof_sweep_desc(void);
@@ -698,6 +708,9 @@ int qc_sweep_eval_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_
  *   - at most 16 state columns;
  *   - G_drift, every drive and every perturbation are antisymmetric, max |G + G^T| <= 64 eps max |G| (closed systems: iso generators
  *     of Hermitian operators; Lindblad generators are not).
+ * With reserved1[0] = QC_SWEEP_STORED_STATES the scope is instead: the "mfma16-sweep" form (2N <= 16, m <= 8), at most 16 state columns,
+ * a fidelity on the handle -- QC_FID_DENSITY included (F = Re t is linear: lambda_{T-1} = g_r) -- and ANY generators.  A wide handle
+ * in the "mfma32-sweep" form with the flag is refused ("stored-state gradients are not served in the mfma32-sweep form").
  * The last knot's controls and timestep enter no interval: their derivatives are exactly +0.0, as is every entry of `grad` that is
  * neither a control nor a timestep.  The |tr| / n form is not special-cased at tr = 0 (NaN there, as qc_fidelity_eval).
  * `fids` carry the bits of qc_sweep_eval; repeated calls return the same bits (no atomics, sums in a fixed order). */
@@ -740,7 +753,8 @@ int qc_sweep_grad_params(qc_sweep* h, const double* Z, const double* init, int64
  * state being linear in the initial one, dphi_s/dinit = lambda_0 comes from one more transposed product of the seed. */
 /* device-free: may the pullback serve this descriptor?  Scope = the gradient's scope WITHOUT its two fidelity conditions: an MFMA form
  * ("mfma16-sweep", or "mfma32-sweep" with wide = QC_SWEEP_WIDE), antisymmetric drift / drives / perturbations (the same 64-eps test),
- * at most 16 state columns.  fid_kind may be anything, QC_SWEEP_FID_NONE and QC_FID_DENSITY included.  When 0,
+ * at most 16 state columns; with reserved1[0] = QC_SWEEP_STORED_STATES the "mfma16-sweep" form, at most 16 state columns, any
+ * generators.  fid_kind may be anything, QC_SWEEP_FID_NONE and QC_FID_DENSITY included.  When 0,
  * qc_sweep_last_error(NULL) says why, prefixed "qc_sweep pullback: ".  An invalid descriptor returns its own error. */
 int qc_sweep_desc_vjp_supported(const qc_sweep_desc* d, int32_t* supported);
 /* phi_s = <cot[s], x_final[s]>.  cot: S x (2N cols), the layout of `finals`.  Outputs, each optional, at least one non-NULL:

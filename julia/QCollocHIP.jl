@@ -699,7 +699,7 @@ end
 
 """
     rollout_sweep(init, controls, Δt, G_drift, G_drives, G_pert, θ; scale=nothing, cols, goal=nothing, fid_kind=-1,
-                  subspace=nothing, squared=false, device=0, wide=false)  ->  (finals, fids)
+                  subspace=nothing, squared=false, device=0, wide=false, stored_states=false)  ->  (finals, fids)
 
 Final states and fidelities of ONE trajectory of controls under S perturbed systems, in one call (`qc_sweep_eval`): the loop of the
 reference's robustness check, `unitary_rollout(traj.a, timesteps, systems(ζ))[:, end]` and `iso_vec_unitary_fidelity` for every ζ
@@ -707,11 +707,14 @@ reference's robustness check, `unitary_rollout(traj.a, timesteps, systems(ζ))[:
 (2N×2N generators: `system.G_drift`, `system.G_drives`, and e.g. `G(Z)` for a detuning).  `controls` is m×T, `Δt` a vector of T
 timesteps, `θ` S×p, `scale` S×m or nothing; `fid_kind` -1 (none), 0 (unitary; `subspace` 1-based, `squared`), 1 (ket), 2 (density
 operator).  `wide = true` sets `qc_sweep_desc.wide = QC_SWEEP_WIDE`: the matrix-core form up to 2N = 32 ("mfma32-sweep") instead of one
-rollout per sample from 2N = 18 up.  `finals` is (2N·cols)×S.  UNTESTED here, like the rest of this file.
+rollout per sample from 2N = 18 up.  `stored_states = true` sets `qc_sweep_desc.reserved1[1] = QC_SWEEP_STORED_STATES` (C index 0): reverse
+mode (`rollout_sweep_gradient`, `rollout_sweep_parameter_gradient`, `rollout_sweep_pullback`) then reads stored forward states and serves
+open systems with 2N ≤ 16 -- Lindblad generators with `fid_kind = 2`, non-Hermitian effective Hamiltonians; the forward sweep itself does
+not look at it.  `finals` is (2N·cols)×S.  UNTESTED here, like the rest of this file.
 """
 function rollout_sweep(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift, G_drives, G_pert,
                        θ::AbstractMatrix{Float64}; scale=nothing, cols::Int, goal=nothing, fid_kind::Int=-1, subspace=nothing,
-                       squared::Bool=false, device::Int=0, wide::Bool=false)
+                       squared::Bool=false, device::Int=0, wide::Bool=false, stored_states::Bool=false)
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(θ, 1)
     G0 = Float64.(vec(G_drift))
@@ -729,7 +732,7 @@ function rollout_sweep(init::AbstractVector{Float64}, controls::AbstractMatrix{F
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
                                squared ? 1 : 0, length(sub), isempty(g) ? C_NULL : pointer(g), isempty(sub) ? C_NULL : pointer(sub),
-                               device, wide ? 1 : 0, (0, 0)))
+                               device, wide ? 1 : 0, (stored_states ? 1 : 0, 0)))
         rc = ccall((:qc_sweep_create, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Ptr{Cvoid}}), desc, h)
         rc == 0 || error("qc_sweep_create: " * unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
     end
@@ -744,17 +747,18 @@ end
 
 """
     rollout_sweep_gradient(init, controls, Δt, G_drift, G_drives, G_pert, θ; scale=nothing, weights=nothing, cols, goal, fid_kind=0,
-                           subspace=nothing, squared=false, per_sample=false, device=0, wide=false)  ->  (J, fids, ∇a, ∇Δt[, grad_samples])
+                           subspace=nothing, squared=false, per_sample=false, device=0, wide=false, stored_states=false)  ->  (J, fids, ∇a, ∇Δt[, grad_samples])
 
 The adjoint of `rollout_sweep` (`qc_sweep_grad`): J = Σ_s w_s F_s (`weights`: S values, default 1/S each), the S fidelities, and the
 gradient of J with respect to the controls (`∇a`, m×T) and the timesteps (`∇Δt`, T); the last knot's columns are zero.  With
 `per_sample`, `grad_samples` is (m+1)×(T-1)×S: ∂F_s/∂a_{t,k}, then ∂F_s/∂Δt_t.  Served for closed systems (antisymmetric generators)
-with 2N ≤ 16 (`wide = true`: 2N ≤ 32), m ≤ 8 and `fid_kind` 0 (unitary) or 1 (ket); everything else errors with the library's reason.  Arguments as
+with 2N ≤ 16 (`wide = true`: 2N ≤ 32), m ≤ 8 and `fid_kind` 0 (unitary) or 1 (ket); with `stored_states = true` for ANY generators with 2N ≤ 16,
+m ≤ 8 and `fid_kind` 0, 1 or 2 (density operator); everything else errors with the library's reason.  Arguments as
 `rollout_sweep`.  UNTESTED here, like the rest of this file.
 """
 function rollout_sweep_gradient(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift, G_drives,
                                 G_pert, θ::AbstractMatrix{Float64}; scale=nothing, weights=nothing, cols::Int, goal, fid_kind::Int=0,
-                                subspace=nothing, squared::Bool=false, per_sample::Bool=false, device::Int=0, wide::Bool=false)
+                                subspace=nothing, squared::Bool=false, per_sample::Bool=false, device::Int=0, wide::Bool=false, stored_states::Bool=false)
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(θ, 1)
     G0 = Float64.(vec(G_drift))
@@ -775,7 +779,7 @@ function rollout_sweep_gradient(init::AbstractVector{Float64}, controls::Abstrac
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
                                squared ? 1 : 0, length(sub), pointer(g), isempty(sub) ? C_NULL : pointer(sub),
-                               device, wide ? 1 : 0, (0, 0)))
+                               device, wide ? 1 : 0, (stored_states ? 1 : 0, 0)))
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_grad_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
         (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
@@ -892,15 +896,15 @@ end
 
 """
     rollout_sweep_parameter_gradient(init, controls, Δt, G_drift, G_drives, G_pert, θ; scale=nothing, cols, goal, fid_kind=0,
-                                     subspace=nothing, squared=false, device=0)  ->  (fids, ∇θ, ∇c)
+                                     subspace=nothing, squared=false, device=0, stored_states=false)  ->  (fids, ∇θ, ∇c)
 
 The derivatives of the S fidelities of `rollout_sweep` with respect to the SYSTEMS (`qc_sweep_grad_params`): `∇θ[s, j]` = ∂F_s/∂θ[s, j]
 (S×p) and `∇c[s, k]` = ∂F_s/∂scale[s, k] (S×m; `scale = nothing`: taken at all ones), raw per-sample values from one backward walk.
-Scope and arguments as `rollout_sweep_gradient`.  UNTESTED here, like the rest of this file.
+Scope and arguments as `rollout_sweep_gradient` (`stored_states = true`: open systems, as there).  UNTESTED here, like the rest of this file.
 """
 function rollout_sweep_parameter_gradient(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift,
                                           G_drives, G_pert, θ::AbstractMatrix{Float64}; scale=nothing, cols::Int, goal, fid_kind::Int=0,
-                                          subspace=nothing, squared::Bool=false, device::Int=0)
+                                          subspace=nothing, squared::Bool=false, device::Int=0, stored_states::Bool=false)
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(θ, 1)
     G0 = Float64.(vec(G_drift))
@@ -919,7 +923,7 @@ function rollout_sweep_parameter_gradient(init::AbstractVector{Float64}, control
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
                                squared ? 1 : 0, length(sub), pointer(g), isempty(sub) ? C_NULL : pointer(sub),
-                               device, 0, (0, 0)))
+                               device, 0, (stored_states ? 1 : 0, 0)))
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_grad_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
         (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
@@ -939,18 +943,18 @@ end
 
 """
     rollout_sweep_pullback(init, controls, Δt, G_drift, G_drives, G_pert, θ, C̄; scale=nothing, cols, params=false, device=0,
-                           wide=false)  ->  (finals, ∇a, ∇Δt, ∇init[, ∇θ, ∇c])
+                           wide=false, stored_states=false)  ->  (finals, ∇a, ∇Δt, ∇init[, ∇θ, ∇c])
 
 The pullback of `rollout_sweep` (`qc_sweep_vjp`): `C̄` is (2N·cols)×S, column s the cotangent of sample s's final state (the derivative
 of the caller's loss with respect to it, e.g. what `Zygote.pullback` hands to an `rrule`), and with φ_s = ⟨C̄[:, s], finals[:, s]⟩ the
 results are the final states themselves, Σ_s ∂φ_s/∂a (m×T) and Σ_s ∂φ_s/∂Δt (T; the last knot's columns are zero), `∇init`
 (2N·cols)×S with column s = ∂φ_s/∂init (sum the columns for a shared initial state) and, with `params`, `∇θ` (S×p) and `∇c` (S×m).
 Served for closed systems (antisymmetric generators) with 2N ≤ 16 (`wide = true`: 2N ≤ 32, without `params`), m ≤ 8 and at most 16
-state columns; no fidelity is involved.  Arguments as `rollout_sweep`.  UNTESTED here, like the rest of this file.
+state columns, with `stored_states = true` for any generators with 2N ≤ 16; no fidelity is involved.  Arguments as `rollout_sweep`.  UNTESTED here, like the rest of this file.
 """
 function rollout_sweep_pullback(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift, G_drives,
                                 G_pert, θ::AbstractMatrix{Float64}, C̄::AbstractMatrix{Float64}; scale=nothing, cols::Int, params::Bool=false,
-                                device::Int=0, wide::Bool=false)
+                                device::Int=0, wide::Bool=false, stored_states::Bool=false)
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(θ, 1)
     size(C̄) == (n * cols, S) || error("rollout_sweep_pullback: C̄ must be $(n * cols)×$S")
@@ -970,7 +974,7 @@ function rollout_sweep_pullback(init::AbstractVector{Float64}, controls::Abstrac
     GC.@preserve G0 Gd Gp begin
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, -1,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
-                               0, 0, C_NULL, C_NULL, device, wide ? 1 : 0, (0, 0)))
+                               0, 0, C_NULL, C_NULL, device, wide ? 1 : 0, (stored_states ? 1 : 0, 0)))
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_vjp_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
         (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))

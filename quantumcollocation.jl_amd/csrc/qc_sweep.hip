@@ -317,6 +317,8 @@ int qc_sweep_validate_desc(const qc_sweep_desc* d) {
     if (2 * (int64_t)d->N * nc > 4096) return qc_sweep_fail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: states of more than 4096 entries (2N x state_cols) are not supported");
     if (d->m > 64) return qc_sweep_fail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: more than 64 drives are not supported");
     if (d->wide != 0 && d->wide != QC_SWEEP_WIDE) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: wide must be 0 or QC_SWEEP_WIDE (1)");
+    if (d->reserved1[0] != 0 && d->reserved1[0] != QC_SWEEP_STORED_STATES)
+        return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: reserved1[0] must be 0 or QC_SWEEP_STORED_STATES (1)");
     return QC_OK;
 }
 
@@ -413,8 +415,13 @@ extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
     h->jvp_ok = qc_sweep_jvp_scope(d, &h->jvp_why);
     h->hvp_ok = qc_sweep_hvp_scope(d, &h->hvp_why);
     h->noise_ok = qc_sweep_noise_scope(d, &h->noise_why);
-    h->noise_grad_ok = h->noise_ok && h->grad_ok;
-    h->noise_grad_why = h->noise_ok ? h->grad_why : h->noise_why;
+    {      // the noise gradient keeps the closed walk and its scope, whatever reserved1[0] says
+        std::string closed_why;
+        const bool closed_ok = qc_sweep_closed_grad_scope(d, &closed_why);
+        h->noise_grad_ok = h->noise_ok && closed_ok;
+        h->noise_grad_why = h->noise_ok ? closed_why : h->noise_why;
+    }
+    h->stored = d->reserved1[0] == QC_SWEEP_STORED_STATES;
     const int N = d->N, n = 2 * N, n2 = n * n, m = d->m, p = d->n_pert;
     h->n = n;
     h->nc = d->state_cols == 0 ? N : d->state_cols;

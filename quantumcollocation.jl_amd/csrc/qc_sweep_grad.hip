@@ -13,7 +13,9 @@
 //     exponential, the chain in direction K runs beside the Horner chain of E itself and one product with E^T follows.  The order
 //     problem (M_t needs x_t, which needs E) is gone: neither are the Horner / squaring intermediates kept, nor is the R chain computed twice;
 //   * <lambda, G x> = -sum (lambda x^T)_ab G_ba, so the timestep derivative is an inner product of tiles already in registers.
-// Everything else returns QC_ERR_UNSUPPORTED (Lindblad generators need stored forward states).
+// Everything else returns QC_ERR_UNSUPPORTED (Lindblad generators need stored forward states) -- unless the descriptor opts in with
+// reserved1[0] = QC_SWEEP_STORED_STATES: such handles are routed to the stored-state walk of qc_sweep_open_grad.hip, whatever their
+// generators, behind the same totals, seed (with lambda = g_r for the density fidelity) and reductions; qc_sweep_reverse_scope decides.
 // Wide descriptors (wide = QC_SWEEP_WIDE) extend the scope to the "mfma32-sweep" form, 2N <= 32: this file routes such handles to the
 // seed and walk kernels of qc_sweep32_grad.hip and shares its reductions (launch 4) with them; no parameter gradients there.
 //
@@ -66,26 +68,14 @@
 #include "qc_mfma_common.h"
 #include "qc_sweep_internal.h"
 #include "qc_sweep_seed.h"
+#include "qc_sweep_walk.h"
 
 namespace {
 
 using namespace qc_mfma;
-
-constexpr int kGDeg = 8;            // as the forward kernel (kSDeg, kSTh of qc_sweep.hip)
-constexpr double kGTh = 0.125;
-constexpr int kGWaves = 4;          // (sample, chunk) items per workgroup: one wave each, the waves never synchronise
+using namespace qc_sweep_walk;   // the series, the squaring rule, the step and the wave sum both walks share
 using qc_sweep_seed::kSeedT;        // threads of the seed workgroup
 constexpr int kRedT = 256;
-
-// 1 / k!, k = 0 .. 8: the values of kSInvFact (qc_sweep.hip; a __constant__ table is private to its translation unit)
-__constant__ const double kGInvFact[kGDeg + 1] = {1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0, 1.0 / 40320.0};
-
-struct GradParams {
-    int n, nc, m, p, zdim, off_a, off_dt, n_int, chunk, n_chunks, nd;   // nd = m + (off_dt >= 0): derivatives per interval
-    long long items;             // S * n_chunks
-    double dt_fixed;
-    const double* img;           // A-layout images [matrix][kk][lane]: drift, m drives, p perturbations
-};
 
 struct SeedParams {
     int n, ns, n_chunks, fid_kind, fid_form, fid_n;
@@ -95,54 +85,6 @@ struct ReduceParams {
     int zdim, off_a, off_dt, m, nd;
     long long T, Zlen, S;
 };
-
-template <int CTRL>
-__device__ inline double gdpp(double x) {
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ inline v4d gimg(const double* __restrict__ img, int mat, int lane) {
-    const double* p = img + (size_t)mat * 256 + lane;
-    return v4d{p[0], p[64], p[128], p[192]};
-}
-
-__device__ __forceinline__ v4d gmma(const v4d& a, const v4d& b, v4d acc) {
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], b[kk], acc, 0, 0, 0);
-    return acc;
-}
-
-// (R, dR) <- (A R + C,  dA R + A dR): a Horner step (A = Y, dA = dY, C = I / (k-1)!) or a squaring (A = E, dA = dE, C = 0).
-// Three independent accumulator chains, interleaved.
-__device__ __forceinline__ void gstep(const v4d& A, const v4d& dA, v4d& R, v4d& dR, const v4d& C) {
-    const v4d z = {0.0, 0.0, 0.0, 0.0};
-    v4d a0 = z, a1 = z, a2 = C;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-        a0 = __builtin_amdgcn_mfma_f64_16x16x4f64(dA[kk], R[kk], a0, 0, 0, 0);
-        a1 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[kk], dR[kk], a1, 0, 0, 0);
-        a2 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[kk], R[kk], a2, 0, 0, 0);
-    }
-    dR = a0 + a1;
-    R = a2;
-}
-
-// the sum over the 64 lanes in a fixed order, wave-uniform: row sums by DPP rotations, then (row 0 + row 1) + (row 2 + row 3)
-__device__ inline double wave_sum(double v) {
-    v += gdpp<0x128>(v);
-    v += gdpp<0x124>(v);
-    v += gdpp<0x122>(v);
-    v += gdpp<0x121>(v);
-    return (bcast_lane(v, 0) + bcast_lane(v, 16)) + (bcast_lane(v, 32) + bcast_lane(v, 48));
-}
-
-// LDS of one wave: two transposition tiles, and in the parameter flavour behind them the accumulator tile sum_t ZT_t (256), the
-// interval's unscaled controls (64) and the scale accumulator (64)
-template <bool PAR>
-constexpr int kGSlice = 2 * 272 + (PAR ? 256 + 128 : 0);
 
 // One wavefront per (sample, chunk), walking the chunk backwards.  PAR = false: the per-interval derivatives only (`part` unused).
 // PAR = true, the parameter flavour, also accumulates the chunk's shares of dF_s/dtheta_j = sum_t sum(ZT_t . P_j) and
@@ -225,7 +167,8 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_grad_kernel(const Gr
 #pragma unroll
             for (int r = 0; r < 4; ++r) Ga[r] = fma(a, Gj[u][r], Ga[r]);
         }
-        // the number of squarings: the rule of the forward kernel
+        // the number of squarings: the rule of the forward kernel (qc_sweep_walk::squarings, written out: the call changed this kernel's
+        // scalar register count)
         int sq = 0;
         {
             double best = 0.0;
@@ -384,8 +327,10 @@ __device__ __forceinline__ void fid_seed(const SeedParams F, const double* __res
             if (F.fid_form == QC_FID_FORM_ABS2) { Fv = (tr * tr + ti * ti) / (nn * nn); fac = 2.0 / (nn * nn); }
             else { Fv = sqrt(tr * tr + ti * ti) / nn; fac = 1.0 / (nn * nn * Fv); }
         } else { Fv = tr * tr + ti * ti; fac = 2.0; }
+        double cr = tr, ci = ti;
+        if (F.fid_kind == QC_FID_DENSITY) { Fv = tr; cr = 1.0; ci = 0.0; fac = 1.0; }      // F = Re t is linear: lambda = g_r as stored
         fids[s] = Fv;
-        coef[0] = tr; coef[1] = ti; coef[2] = fac;
+        coef[0] = cr; coef[1] = ci; coef[2] = fac;
     }
     __syncthreads();
     const double tr = coef[0], ti = coef[1], fac = coef[2];
@@ -481,11 +426,31 @@ bool qc_sweep_closed_scope(const qc_sweep_desc* d, std::string* why) {
     return true;
 }
 
-bool qc_sweep_grad_scope(const qc_sweep_desc* d, std::string* why) {
+// Reverse mode of a descriptor: reserved1[0] chooses the walk.  0: the closed walk and its scope above.  QC_SWEEP_STORED_STATES: the
+// stored-state walk of qc_sweep_open_grad.hip, which asks nothing of the generators: the "mfma16-sweep" form, at most 16 state columns.
+bool qc_sweep_reverse_scope(const qc_sweep_desc* d, std::string* why) {
+    if (d->reserved1[0] != QC_SWEEP_STORED_STATES) return qc_sweep_closed_scope(d, why);
+    const int form = qc_sweep_desc_form(d);
+    if (form == 0) { *why = qc_sweep_per_sample_why(d); return false; }
+    if (form == 2) { *why = "stored-state gradients are not served in the mfma32-sweep form"; return false; }
+    const int nc = d->state_cols == 0 ? d->N : d->state_cols;
+    if (nc > 16) { *why = "states of more than 16 columns are not served (state_cols = " + std::to_string(nc) + ")"; return false; }
+    return true;
+}
+
+// the gradient's scope whatever reserved1[0] says: what the noise gradient (qc_sweep_noise.hip) keeps asking
+bool qc_sweep_closed_grad_scope(const qc_sweep_desc* d, std::string* why) {
     if (!qc_sweep_closed_scope(d, why)) return false;
     if (d->fid_kind == QC_SWEEP_FID_NONE) { *why = "the handle has no fidelity (QC_SWEEP_FID_NONE)"; return false; }
     if (d->fid_kind == QC_FID_DENSITY) { *why = "the density-operator fidelity is not served"; return false; }
     return true;
+}
+
+bool qc_sweep_grad_scope(const qc_sweep_desc* d, std::string* why) {
+    if (d->reserved1[0] != QC_SWEEP_STORED_STATES) return qc_sweep_closed_grad_scope(d, why);
+    if (!qc_sweep_reverse_scope(d, why)) return false;
+    if (d->fid_kind == QC_SWEEP_FID_NONE) { *why = "the handle has no fidelity (QC_SWEEP_FID_NONE)"; return false; }
+    return true;      // QC_FID_DENSITY included: its seed is lambda = g_r
 }
 
 extern "C" int qc_sweep_desc_grad_supported(const qc_sweep_desc* d, int32_t* supported) {
@@ -525,9 +490,14 @@ void qc_sweep16_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const doub
     } while (0)
     QC_SWEEP_FOR_M(m, QC_GRAD_LAUNCH);
 #undef QC_GRAD_LAUNCH
-    if (want_par)
-        hipLaunchKernelGGL(qc_sweep_par_reduce_kernel, dim3((unsigned)((S * (p + m) + kRedT - 1) / kRedT)), dim3(kRedT), 0, st, (long long)S,
-                           (int)n_chunks, p, m, (const double*)h->dPart.p, dgrad_theta, dgrad_scale);
+    if (want_par) qc_sweep_launch_par_reduce(h, S, n_chunks, dgrad_theta, dgrad_scale, st);
+}
+
+// grad_theta / grad_scale out of the chunk shares in h->dPart (qc_sweep_par_reduce_kernel), for the walk above and the stored-state walk
+void qc_sweep_launch_par_reduce(qc_sweep* h, int64_t S, int64_t n_chunks, double* dgrad_theta, double* dgrad_scale, hipStream_t st) {
+    const int m = h->d.m, p = h->d.n_pert;
+    hipLaunchKernelGGL(qc_sweep_par_reduce_kernel, dim3((unsigned)((S * (p + m) + kRedT - 1) / kRedT)), dim3(kRedT), 0, st, (long long)S,
+                       (int)n_chunks, p, m, (const double*)h->dPart.p, dgrad_theta, dgrad_scale);
 }
 
 // Launch 2 (the fidelity's seed) and launch 4 (the weighted reductions) of a gradient call, for the entry points below and the noise sweep
@@ -599,8 +569,13 @@ static int qc_sweep_grad_launch(qc_sweep* h, const char* who, const double* dZ, 
         gsamp = h->dGsamp.p;
     }
     if (want_par) QC_SIDE_HIP(h, slot, h->grow(h->dPart, (size_t)S * n_chunks * (p + m)));
+    if (h->stored && (want_grad || want_par)) QC_SIDE_HIP(h, slot, h->grow(h->dXall, (size_t)S * (size_t)n_int * h->ns));
     qc_sweep_launch_fid_seed(h, S, n_chunks, dinit, dfids, st);
-    if (h->mfma32) {      // the 2 x 2-tile form: its own walk (qc_sweep32_grad.hip), then the reductions below
+    if (h->stored) {      // reserved1[0] = QC_SWEEP_STORED_STATES: the walk of qc_sweep_open_grad.hip, whatever the generators
+        if (want_grad || want_par)
+            qc_sweep_open_launch_walk(h, dZ, dinit, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta,
+                                      dgrad_scale, st);
+    } else if (h->mfma32) {      // the 2 x 2-tile form: its own walk (qc_sweep32_grad.hip), then the reductions below
         if (want_grad) qc_sweep32_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, gsamp, st);
     } else if (want_grad || want_par)
         qc_sweep16_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);

@@ -1,4 +1,4 @@
-// What qc_sweep.hip (forward sweep), qc_sweep_grad.hip (its adjoint), qc_sweep_vjp.hip (the pullback of the final states),
+// What qc_sweep.hip (forward sweep), qc_sweep_grad.hip (its adjoint), qc_sweep_open_grad.hip (the adjoint on stored states), qc_sweep_vjp.hip (the pullback of the final states),
 // qc_sweep_jvp.hip (their pushforward), qc_sweep_hvp.hip (the tangent of the pullback) and qc_sweep_noise.hip (noise trajectories) share: the handle with its scratch and staging buffers, the descriptor and argument checks and
 // the launch of the forward chunk totals (with it the chunk rule).  Not part of the ABI.
 #pragma once
@@ -11,6 +11,7 @@ struct qc_sweep : qc_side {
     qc_sweep_desc d;             // caller-owned arrays are not retained (pointers nulled)
     bool mfma = false;
     bool mfma32 = false;         // the 2 x 2-tile form of a wide descriptor ("mfma32-sweep", qc_sweep32.hip); mfma is set as well
+    bool stored = false;         // reserved1[0] = QC_SWEEP_STORED_STATES: reverse mode by the stored-state walk (qc_sweep_open_grad.hip)
     bool grad_ok = false;        // the gradient's scope (qc_sweep_grad.hip), decided at create from the caller's matrices
     std::string grad_why;        // when not: the reason
     bool vjp_ok = false;         // the pullback's scope (qc_sweep_vjp.hip): the gradient's without its fidelity conditions
@@ -35,6 +36,7 @@ struct qc_sweep : qc_side {
     qc_buf dXs, dLs;     // x and lambda at the chunk ends, S x n_chunks x ns each            grad, vjp, noise_grad
     qc_buf dGsamp;       // per-interval derivatives when the caller keeps none, S x (T-1) x nd   grad, vjp, noise_grad
     qc_buf dGfid;        // fidelities when the caller keeps none, S                         grad, noise_grad
+    qc_buf dXall;        // stored-state walk: x_t of knots 0 .. T-2, S x (T-1) x ns                  grad, vjp (stored handles)
     qc_buf dPart;        // chunk shares of the parameter gradients, S x n_chunks x (p + m)  grad_params, vjp
     qc_buf dTotJ;        // chunk totals and their tangents, S x n_chunks x 512              jvp, hvp
     qc_buf dXsT, dLsT;   // xdot and lambdadot at the chunk ends, S x n_chunks x ns each      hvp (x and lambda: dXs, dLs)
@@ -104,6 +106,17 @@ void qc_sweep32_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const doub
 // parameter flavour <M, true> (gs may be NULL) and qc_sweep_par_reduce_kernel out of h->dPart; scratch is the caller's
 void qc_sweep16_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,
                             double* gs, bool par, double* dgrad_theta, double* dgrad_scale, hipStream_t st);
+// grad_theta / grad_scale out of the chunk shares in h->dPart (qc_sweep_grad.hip: qc_sweep_par_reduce_kernel)
+void qc_sweep_launch_par_reduce(qc_sweep* h, int64_t S, int64_t n_chunks, double* dgrad_theta, double* dgrad_scale, hipStream_t st);
+// Stored-state handles (qc_sweep_open_grad.hip): qc_sweep_open_store_kernel<M> writes x_t of every knot 0 .. T-2 into h->dXall (grown by
+// the caller) from `dinit` and the chunk ends of h->dXs, then qc_sweep_open_grad_kernel<M, par> walks every chunk backwards from h->dLs;
+// arguments and outputs as qc_sweep16_launch_walk
+void qc_sweep_open_launch_walk(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
+                               int64_t chunk, int64_t n_chunks, double* gs, bool par, double* dgrad_theta, double* dgrad_scale, hipStream_t st);
+// what reverse mode asks of a descriptor: reserved1[0] = 0, the closed scope; QC_SWEEP_STORED_STATES, the "mfma16-sweep" form and at most
+// 16 state columns, any generators.  qc_sweep_closed_grad_scope: the gradient's scope of reserved1[0] = 0, for the noise gradient.
+bool qc_sweep_reverse_scope(const qc_sweep_desc* d, std::string* why);
+bool qc_sweep_closed_grad_scope(const qc_sweep_desc* d, std::string* why);
 // device-free: is this (valid) descriptor inside the gradient's scope?  `why` receives the reason when it is not.
 bool qc_sweep_grad_scope(const qc_sweep_desc* d, std::string* why);
 // what the gradient and the pullback ask alike (an MFMA form, antisymmetric matrices, at most 16 state columns), and the pullback's scope

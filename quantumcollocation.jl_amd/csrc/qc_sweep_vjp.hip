@@ -20,7 +20,8 @@
 //      weight vector as 1/S each); +0.0 at every entry that is not a control or timestep of knots 0 .. T-2.
 // No atomics, sums in a fixed order: repeated calls return the same bits, and no output's bits depend on which others were asked for.
 //
-// Scope: the gradient's without its two fidelity conditions (qc_sweep_vjp_scope below shares qc_sweep_closed_scope with it).
+// Scope: the gradient's without its two fidelity conditions (qc_sweep_vjp_scope below is qc_sweep_reverse_scope: the closed scope, or with
+// reserved1[0] = QC_SWEEP_STORED_STATES the stored-state walk's, and then launch 3 is qc_sweep_open_launch_walk of qc_sweep_open_grad.hip).
 #include <math.h>
 
 #include <string>
@@ -115,7 +116,7 @@ int vjp_check(qc_sweep* h, const char* who, const void* Z, const void* init, int
 
 }  // namespace
 
-bool qc_sweep_vjp_scope(const qc_sweep_desc* d, std::string* why) { return qc_sweep_closed_scope(d, why); }
+bool qc_sweep_vjp_scope(const qc_sweep_desc* d, std::string* why) { return qc_sweep_reverse_scope(d, why); }
 
 extern "C" int qc_sweep_desc_vjp_supported(const qc_sweep_desc* d, int32_t* supported) {
     int rc = qc_sweep_validate_desc(d);
@@ -164,13 +165,18 @@ static int qc_sweep_vjp_launch(qc_sweep* h, const char* who, const double* dZ, c
         gsamp = h->dGsamp.p;
     }
     if (want_par) QC_SIDE_HIP(h, slot, h->grow(h->dPart, (size_t)S * n_chunks * (p + m)));
+    if (h->stored && (want_grad || want_par)) QC_SIDE_HIP(h, slot, h->grow(h->dXall, (size_t)S * (size_t)n_int * h->ns));
     CotParams F;
     F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
     const size_t lds = qc_sweep_seed::lds_bytes(h->ns, h->mfma32 ? 32 : 16);      // at most 16 state columns: 16 KiB
     const auto seed = h->mfma32 ? qc_sweep32_cot_seed_kernel : qc_sweep_cot_seed_kernel;
     hipLaunchKernelGGL(seed, dim3((unsigned)S), dim3(kCotT), lds, st, F, (const double*)h->dTot.p, dinit, dcot, h->dXs.p, h->dLs.p, dfinals,
                        dgrad_init);
-    if (h->mfma32) {
+    if (h->stored) {      // reserved1[0] = QC_SWEEP_STORED_STATES: the walk of qc_sweep_open_grad.hip behind the same seed
+        if (want_grad || want_par)
+            qc_sweep_open_launch_walk(h, dZ, dinit, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta,
+                                      dgrad_scale, st);
+    } else if (h->mfma32) {
         if (want_grad) qc_sweep32_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, gsamp, st);
     } else if (want_grad || want_par)
         qc_sweep16_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);

@@ -742,13 +742,17 @@ class SweepInfidelityObjective:
     `QuantumControlEvaluator(eval_hessian=False)`.  The layout comes from the trajectory: `traj.dim`, the offsets of `control_name`
     and of the timestep, `traj.global_dim`.
 
-    state_name  a unitary component (2 N^2 entries: unitary fidelity, `subspace`, `form`) or a ket component (2 N entries)
+    state_name  a unitary component (2 N^2 entries: unitary fidelity, `subspace`, `form`) or a ket component (2 N entries); with an
+                `OpenQuantumSystem` the iso-vec of a density operator (2 levels^2 entries: the density fidelity <psi|rho|psi>)
     theta       S x len(perturbations);  scale  S x n_drives or None;  weights  S values or None (1/S each)
-    wide        as `RolloutSweep`: True serves systems of 16 < 2N <= 32 (9 .. 16 levels) in the "mfma32-sweep" form"""
+    wide        as `RolloutSweep`: True serves systems of 16 < 2N <= 32 (9 .. 16 levels) in the "mfma32-sweep" form
+    stored_states  as `RolloutSweep`: True takes the gradient by the stored-state walk, which serves open systems
+    goal_ket    density component only: [Re psi; Im psi] (2 levels entries) of the pure state the fidelity compares with"""
     _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
 
     def __init__(self, traj: NamedTrajectory, system, perturbations, theta, scale=None, weights=None, state_name: str = "Ũ⃗",
-                 control_name: str = "a", subspace=None, form: str = "abs", device: int = 0, wide: bool = False):
+                 control_name: str = "a", subspace=None, form: str = "abs", device: int = 0, wide: bool = False,
+                 stored_states: bool = False, goal_ket=None):
         from .rollouts import RolloutSweep
         self._sweep = None
         if state_name not in traj.components:
@@ -761,16 +765,27 @@ class SweepInfidelityObjective:
         if len(traj.components[control_name]) != m:
             raise ValueError(f"component {control_name} has {len(traj.components[control_name])} rows, the system has {m} drives")
         s = len(traj.components[state_name])
-        if s == 2 * N * N and N > 1:
+        is_open = system.state_levels != system.levels
+        if is_open and s == 2 * N:
+            kind, cols = "density", 1
+        elif s == 2 * N * N and N > 1:
             kind, cols = "unitary", N
         elif s == 2 * N:
             kind, cols = "ket", 1
         else:
             raise ValueError(f"component {state_name} has length {s}: neither a unitary (2 N^2) nor a ket (2 N) of N = {N} levels")
-        if kind == "ket" and (subspace is not None or form != "abs"):
+        if kind != "unitary" and (subspace is not None or form != "abs"):
             raise ValueError("subspace and form apply to a unitary component only")
-        if state_name not in traj.goal:
+        if (goal_ket is not None) != (kind == "density"):
+            raise ValueError("goal_ket ([Re psi; Im psi]) is given exactly when the component is a density operator of an OpenQuantumSystem")
+        if kind == "density":
+            goal = np.asarray(goal_ket, dtype=np.float64).ravel()
+            if goal.size != 2 * system.levels:
+                raise ValueError(f"goal_ket must have {2 * system.levels} entries")
+        elif state_name not in traj.goal:
             raise ValueError(f"the trajectory has no goal for {state_name}")
+        else:
+            goal = np.asarray(traj.goal[state_name], dtype=np.float64)
         init = traj.initial.get(state_name)
         if init is None:
             init = traj[state_name][:, 0]
@@ -785,11 +800,13 @@ class SweepInfidelityObjective:
         self.traj = traj
         self.Z_len = traj.T * traj.dim + traj.global_dim
         self._init = np.ascontiguousarray(init, dtype=np.float64).ravel()
-        sw = RolloutSweep(system, perturbations, traj.T, cols=cols, goal=np.asarray(traj.goal[state_name], dtype=np.float64), fid_kind=kind,
+        sw = RolloutSweep(system, perturbations, traj.T, cols=cols, goal=goal, fid_kind=kind,
                           subspace=subspace, fid_form=_lib.QC_FID_FORM_ABS2 if form == "abs2" else _lib.QC_FID_FORM_ABS, zdim=traj.dim,
                           off_a=traj.offset(control_name), off_dt=traj.offset(traj.timestep) if free else -1,
-                          dt_fixed=None if free else float(traj.timestep), global_dim=traj.global_dim, device=device, wide=wide)
+                          dt_fixed=None if free else float(traj.timestep), global_dim=traj.global_dim, device=device, wide=wide,
+                          stored_states=stored_states)
         self._sweep = sw
+        self.stored_states = sw.stored_states
         if not sw.grad_supported:
             why = sw.grad_unsupported_reason
             sw.close()
@@ -897,11 +914,13 @@ class SweepFinalStateObjective:
     state_name  a unitary component (2 N^2 entries), a component of K kets (2 N K entries, the kets side by side) or a list of ket
                 component names (stacked as columns in that order).  No goal is read: the loss carries whatever it compares with.
     theta       S x len(perturbations);  scale  S x n_drives or None
-    wide        as `RolloutSweep`"""
+    wide        as `RolloutSweep`
+    stored_states  as `RolloutSweep`: True takes the pullback by the stored-state walk, which serves open systems (gradients and
+                `gauss_newton_times`; `hessian_times` keeps the scope of `RolloutSweep.hvp`)"""
     _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
 
     def __init__(self, traj: NamedTrajectory, system, perturbations, theta, loss, scale=None, state_name="Ũ⃗", control_name: str = "a",
-                 device: int = 0, wide: bool = False):
+                 device: int = 0, wide: bool = False, stored_states: bool = False):
         from .rollouts import RolloutSweep, _sweep_samples
         self._sweep = None
         if not callable(loss):
@@ -927,8 +946,9 @@ class SweepFinalStateObjective:
         self.Z_len = traj.T * traj.dim + traj.global_dim
         sw = RolloutSweep(system, perturbations, traj.T, cols=cols, zdim=traj.dim, off_a=traj.offset(control_name),
                           off_dt=traj.offset(traj.timestep) if free else -1, dt_fixed=None if free else float(traj.timestep),
-                          global_dim=traj.global_dim, device=device, wide=wide)
+                          global_dim=traj.global_dim, device=device, wide=wide, stored_states=stored_states)
         self._sweep = sw
+        self.stored_states = sw.stored_states
         if not sw.vjp_supported:
             why = sw.vjp_unsupported_reason
             sw.close()

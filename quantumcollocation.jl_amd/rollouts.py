@@ -178,11 +178,16 @@ class RolloutSweep:
     entries (default: the minimal layout [a, dt], built by `pack`; dt_fixed: no timestep in the knot).
     wide           True: systems of 16 < 2N <= 32 with up to 8 drives run on the matrix cores too ("mfma32-sweep", with gradients over the
                    controls and timesteps; no parameter gradients there yet) instead of one rollout per sample.  Nothing changes at
-                   2N <= 16."""
+                   2N <= 16.
+    stored_states  True: `grad`, `grad_params` and `vjp` keep the forward states of every sample on the device (S x (T-1) x 2N x cols
+                   doubles) and read them on the way back instead of reversing the step.  That serves ANY generators in the
+                   "mfma16-sweep" form: an `OpenQuantumSystem` with the "density" fidelity, a non-Hermitian effective Hamiltonian.
+                   Closed systems give the same derivatives either way (to rounding); `hvp` and `noise_grad` keep their scope."""
 
     def __init__(self, system, perturbations, T: int, cols: Optional[int] = None, goal=None, fid_kind=None, subspace=None,
                  fid_form: int = _lib.QC_FID_FORM_ABS, zdim: Optional[int] = None, off_a: int = 0, off_dt: Optional[int] = None,
-                 dt_fixed: Optional[float] = None, global_dim: int = 0, device: int = 0, wide: bool = False):
+                 dt_fixed: Optional[float] = None, global_dim: int = 0, device: int = 0, wide: bool = False,
+                 stored_states: bool = False):
         self._h = None
         m = system.n_drives
         N = system.state_levels
@@ -219,6 +224,8 @@ class RolloutSweep:
         d.device = device
         d.wide = _lib.QC_SWEEP_WIDE if wide else 0
         self.wide = bool(wide)
+        d.reserved1[0] = _lib.QC_SWEEP_STORED_STATES if stored_states else 0
+        self.stored_states = bool(stored_states)
         self._desc = d
         h = C.c_void_p()
         rc = _lib.lib.qc_sweep_create(C.byref(d), C.byref(h))
@@ -305,7 +312,8 @@ class RolloutSweep:
     @property
     def grad_supported(self) -> bool:
         """Does `grad` serve this handle?  (`qc_sweep_desc_grad_supported`: the MFMA form, a unitary or ket fidelity, at most 16
-        state columns, antisymmetric generators.)  `grad_unsupported_reason` says why not."""
+        state columns, antisymmetric generators; with `stored_states` the "mfma16-sweep" form, any fidelity, any generators.)
+        `grad_unsupported_reason` says why not."""
         return self._grad_scope()[0]
 
     @property
@@ -419,7 +427,8 @@ class RolloutSweep:
     @property
     def vjp_supported(self) -> bool:
         """Does `vjp` serve this handle?  (`qc_sweep_desc_vjp_supported`: the MFMA forms, at most 16 state columns, antisymmetric
-        generators; any fidelity or none.)  `vjp_unsupported_reason` says why not."""
+        generators; with `stored_states` the "mfma16-sweep" form and any generators; any fidelity or none.)
+        `vjp_unsupported_reason` says why not."""
         return self._vjp_scope()[0]
 
     @property
@@ -870,9 +879,10 @@ class _SweepFinals(torch.autograd.Function):
 
 
 def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None, cols: Optional[int] = None, goal=None, fid_kind=None,
-                  subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS, wide: bool = False):
+                  subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS, wide: bool = False, stored_states: bool = False):
     """(finals, fids) of S rollouts under the perturbed systems: finals is (2N cols) x S, fids S values (None without `fid_kind`).
-    theta is S x len(perturbations) (S x 0 without perturbations), scale S x n_drives or None (all ones); `wide` as `RolloutSweep`."""
+    theta is S x len(perturbations) (S x 0 without perturbations), scale S x n_drives or None (all ones); `wide` and `stored_states` as
+    `RolloutSweep` (the forward sweep itself does not look at `stored_states`)."""
     controls = np.asarray(controls, dtype=np.float64)
     if controls.ndim != 2 or controls.shape[0] != system.n_drives:
         raise ValueError("controls must be n_drives x T")
@@ -881,7 +891,8 @@ def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None,
     n = 2 * system.state_levels
     if cols is None:
         cols = init.size // n
-    sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device, wide=wide)
+    sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device, wide=wide,
+                      stored_states=stored_states)
     try:
         return sw.eval(sw.pack(controls, dts), init, theta, scale)
     finally:
@@ -909,9 +920,11 @@ def rollout_noise_sweep(init, controls, dts, system, perturbations, noise, theta
 
 
 def rollout_sweep_parameter_gradient(init, controls, dts, system, perturbations, theta, scale=None, cols: Optional[int] = None, goal=None,
-                                     fid_kind="unitary", subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS):
+                                     fid_kind="unitary", subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS,
+                                     stored_states: bool = False):
     """(fids, grad_theta, grad_scale) of S rollouts under the perturbed systems: the fidelities of `rollout_sweep` and their derivatives
-    with respect to theta (S x len(perturbations)) and scale (S x n_drives; None: taken at all ones).  Arguments as `rollout_sweep`."""
+    with respect to theta (S x len(perturbations)) and scale (S x n_drives; None: taken at all ones).  Arguments as `rollout_sweep`;
+    `stored_states=True` serves open systems (`RolloutSweep`)."""
     controls = np.asarray(controls, dtype=np.float64)
     if controls.ndim != 2 or controls.shape[0] != system.n_drives:
         raise ValueError("controls must be n_drives x T")
@@ -920,7 +933,8 @@ def rollout_sweep_parameter_gradient(init, controls, dts, system, perturbations,
     n = 2 * system.state_levels
     if cols is None:
         cols = init.size // n
-    sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device)
+    sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device,
+                      stored_states=stored_states)
     try:
         return sw.param_grad(sw.pack(controls, dts), init, theta, scale)
     finally:
