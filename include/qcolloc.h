@@ -626,7 +626,9 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * ("mfma16-sweep"); larger systems run the rollout kernels once per sample ("rollout-per-sample": correctness, not speed).
  * With wide = QC_SWEEP_WIDE the matrix cores serve 16 < 2N <= 32 (up to 8 drives) as well ("mfma32-sweep": 2 x 2 tiles a matrix, the same
  * work item and chunk rule); 2N <= 16 is "mfma16-sweep" as before, everything else the per-sample form.  wide = 0 is the routing of the
- * two sentences above, unchanged; any other value is QC_ERR_INVALID.
+ * two sentences above, unchanged.  wide = QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS (3) is wide = QC_SWEEP_WIDE in every respect but one:
+ * an "mfma32-sweep" handle then serves the parameter gradients (qc_sweep_grad_params*) and the parameter cotangents of the pullback
+ * (qc_sweep_vjp*: grad_theta, grad_scale).  Any other value (bit 1 without bit 0 among them) is QC_ERR_INVALID.
  * reserved1[0] = QC_SWEEP_STORED_STATES chooses reverse mode by the STORED-STATE walk: qc_sweep_grad*, qc_sweep_grad_params* and
  * qc_sweep_vjp* then keep the forward states x_0 .. x_{T-2} of every sample in handle scratch (S x (T-1) x 2N x cols doubles) and read
  * them on the way back instead of reversing the step, which serves ANY generators in the "mfma16-sweep" form: Lindblad generators
@@ -650,7 +652,8 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * call, tangents of grad_theta / grad_scale, several devices. */
 #define QC_MAX_PERT 8
 #define QC_SWEEP_FID_NONE (-1)   /* qc_sweep_desc.fid_kind: final states only */
-#define QC_SWEEP_WIDE 1          /* qc_sweep_desc.wide */
+#define QC_SWEEP_WIDE 1          /* qc_sweep_desc.wide, bit 0 */
+#define QC_SWEEP_WIDE_PARAMS 2   /* qc_sweep_desc.wide, bit 1: the mfma32-sweep form serves parameter gradients and parameter cotangents; only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_STORED_STATES 1 /* qc_sweep_desc.reserved1[0]: reverse mode by the stored-state walk */
 typedef struct qc_sweep_desc {
     int64_t T;
@@ -672,7 +675,7 @@ typedef struct qc_sweep_desc {
     const double* goal_iso;      /* as qc_fidelity_desc.goal_iso */
     const int32_t* subspace;     /* unitary only: 0-based levels, or NULL = all */
     int32_t device;
-    int32_t wide;                /* 0, or QC_SWEEP_WIDE: the matrix-core form up to 2N = 32 ("mfma32-sweep"); anything else is QC_ERR_INVALID */
+    int32_t wide;                /* bit field; valid: 0, QC_SWEEP_WIDE (1): the matrix-core form up to 2N = 32 ("mfma32-sweep"), or QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS (3): that form, and qc_sweep_grad_params* / the grad_theta, grad_scale of qc_sweep_vjp* are served in it (form, launch, kernel name and every *_supported answer as with 1; harmless where the handle takes another form); anything else is QC_ERR_INVALID */
     int64_t reserved1[2];        /* [0]: 0, or QC_SWEEP_STORED_STATES: reverse mode reads stored forward states (any generators, "mfma16-sweep"); anything else is QC_ERR_INVALID.  [1]: ignored */
 } qc_sweep_desc;
 typedef struct qc_sweep qc_sweep;
@@ -737,7 +740,10 @@ int qc_sweep_grad(qc_sweep* h, const double* Z, const double* init, int64_t S, c
  * one-in-flight rule are those of qc_sweep_grad_dev, and fids / J / grad / grad_samples carry its bits; without grad and
  * grad_samples the S x (T-1) x (m + (off_dt >= 0)) per-interval buffer is neither allocated nor written.  Every output is optional,
  * at least one must be non-NULL; grad_theta on a handle with n_pert = 0, or grad_scale with m = 0, is QC_ERR_INVALID.
- * On an "mfma32-sweep" handle both entry points return QC_ERR_UNSUPPORTED ("parameter gradients are not served in the mfma32-sweep form"). */
+ * On an "mfma32-sweep" handle made with wide = QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS both entry points behave exactly as on an
+ * "mfma16-sweep" handle (the parameter flavour of the 2 x 2-tile walk; scope, checks and outputs as above, fids / J / grad / grad_samples
+ * with the bits of qc_sweep_grad on the same handle).  On one made with wide = QC_SWEEP_WIDE alone both return QC_ERR_UNSUPPORTED
+ * ("parameter gradients are not served in the mfma32-sweep form"). */
 int qc_sweep_grad_params_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
                              const double* dweights, double* dfids, double* dJ, double* dgrad, double* dgrad_samples,
                              double* dgrad_theta, double* dgrad_scale, void* stream);
@@ -762,7 +768,8 @@ int qc_sweep_desc_vjp_supported(const qc_sweep_desc* d, int32_t* supported);
  *   grad          Z_len              sum_s dphi_s/dZ (plain sum, ascending s), +0.0 outside controls / timesteps of knots 0..T-2
  *   grad_samples  S x (T-1) x nd     dphi_s/d(a_t, dt_t), the layout of qc_sweep_grad
  *   grad_init     S x (2N cols)      dphi_s/dinit = (E_{T-2} ... E_0)^T cot[s]
- *   grad_theta    S x n_pert, grad_scale  S x m   ("mfma16-sweep" only; on an "mfma32-sweep" handle QC_ERR_UNSUPPORTED,
+ *   grad_theta    S x n_pert, grad_scale  S x m   ("mfma16-sweep", and "mfma32-sweep" handles made with wide = QC_SWEEP_WIDE |
+ *                                    QC_SWEEP_WIDE_PARAMS; on an "mfma32-sweep" handle without that bit QC_ERR_UNSUPPORTED,
  *                                    "parameter cotangents are not served in the mfma32-sweep form")
  * cot must not overlap any output.  Scratch and the one-in-flight rule as qc_sweep_grad_dev.  Repeated calls return the same bits, and
  * no output's bits depend on which other outputs were requested.  Non-finite cotangents are evaluated, not rejected: they reach

@@ -896,15 +896,17 @@ end
 
 """
     rollout_sweep_parameter_gradient(init, controls, Δt, G_drift, G_drives, G_pert, θ; scale=nothing, cols, goal, fid_kind=0,
-                                     subspace=nothing, squared=false, device=0, stored_states=false)  ->  (fids, ∇θ, ∇c)
+                                     subspace=nothing, squared=false, device=0, stored_states=false, wide=false)  ->  (fids, ∇θ, ∇c)
 
 The derivatives of the S fidelities of `rollout_sweep` with respect to the SYSTEMS (`qc_sweep_grad_params`): `∇θ[s, j]` = ∂F_s/∂θ[s, j]
 (S×p) and `∇c[s, k]` = ∂F_s/∂scale[s, k] (S×m; `scale = nothing`: taken at all ones), raw per-sample values from one backward walk.
-Scope and arguments as `rollout_sweep_gradient` (`stored_states = true`: open systems, as there).  UNTESTED here, like the rest of this file.
+Scope and arguments as `rollout_sweep_gradient` (`stored_states = true`: open systems, as there).  `wide = true` sets
+`qc_sweep_desc.wide = QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS` (3): 2N ≤ 32 on the matrix cores, parameter gradients included.
+UNTESTED here, like the rest of this file.
 """
 function rollout_sweep_parameter_gradient(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift,
                                           G_drives, G_pert, θ::AbstractMatrix{Float64}; scale=nothing, cols::Int, goal, fid_kind::Int=0,
-                                          subspace=nothing, squared::Bool=false, device::Int=0, stored_states::Bool=false)
+                                          subspace=nothing, squared::Bool=false, device::Int=0, stored_states::Bool=false, wide::Bool=false)
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(θ, 1)
     G0 = Float64.(vec(G_drift))
@@ -923,7 +925,7 @@ function rollout_sweep_parameter_gradient(init::AbstractVector{Float64}, control
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
                                squared ? 1 : 0, length(sub), pointer(g), isempty(sub) ? C_NULL : pointer(sub),
-                               device, 0, (stored_states ? 1 : 0, 0)))
+                               device, wide ? 3 : 0, (stored_states ? 1 : 0, 0)))      # 3 = QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_grad_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
         (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
@@ -943,18 +945,20 @@ end
 
 """
     rollout_sweep_pullback(init, controls, Δt, G_drift, G_drives, G_pert, θ, C̄; scale=nothing, cols, params=false, device=0,
-                           wide=false, stored_states=false)  ->  (finals, ∇a, ∇Δt, ∇init[, ∇θ, ∇c])
+                           wide=false, stored_states=false, wide_params=false)  ->  (finals, ∇a, ∇Δt, ∇init[, ∇θ, ∇c])
 
 The pullback of `rollout_sweep` (`qc_sweep_vjp`): `C̄` is (2N·cols)×S, column s the cotangent of sample s's final state (the derivative
 of the caller's loss with respect to it, e.g. what `Zygote.pullback` hands to an `rrule`), and with φ_s = ⟨C̄[:, s], finals[:, s]⟩ the
 results are the final states themselves, Σ_s ∂φ_s/∂a (m×T) and Σ_s ∂φ_s/∂Δt (T; the last knot's columns are zero), `∇init`
 (2N·cols)×S with column s = ∂φ_s/∂init (sum the columns for a shared initial state) and, with `params`, `∇θ` (S×p) and `∇c` (S×m).
-Served for closed systems (antisymmetric generators) with 2N ≤ 16 (`wide = true`: 2N ≤ 32, without `params`), m ≤ 8 and at most 16
+Served for closed systems (antisymmetric generators) with 2N ≤ 16 (`wide = true`: 2N ≤ 32, there with `params` only if also `wide_params = true`, which sets bit 1 of
+`qc_sweep_desc.wide`, QC_SWEEP_WIDE_PARAMS), m ≤ 8 and at most 16
 state columns, with `stored_states = true` for any generators with 2N ≤ 16; no fidelity is involved.  Arguments as `rollout_sweep`.  UNTESTED here, like the rest of this file.
 """
 function rollout_sweep_pullback(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift, G_drives,
                                 G_pert, θ::AbstractMatrix{Float64}, C̄::AbstractMatrix{Float64}; scale=nothing, cols::Int, params::Bool=false,
-                                device::Int=0, wide::Bool=false, stored_states::Bool=false)
+                                device::Int=0, wide::Bool=false, stored_states::Bool=false, wide_params::Bool=false)
+    (wide_params && !wide) && error("rollout_sweep_pullback: wide_params = true needs wide = true")
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(θ, 1)
     size(C̄) == (n * cols, S) || error("rollout_sweep_pullback: C̄ must be $(n * cols)×$S")
@@ -974,7 +978,7 @@ function rollout_sweep_pullback(init::AbstractVector{Float64}, controls::Abstrac
     GC.@preserve G0 Gd Gp begin
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, -1,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
-                               0, 0, C_NULL, C_NULL, device, wide ? 1 : 0, (stored_states ? 1 : 0, 0)))
+                               0, 0, C_NULL, C_NULL, device, (wide ? 1 : 0) | (wide_params ? 2 : 0), (stored_states ? 1 : 0, 0)))
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_vjp_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
         (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))

@@ -48,7 +48,8 @@ QC_FID_FORM_ABS, QC_FID_FORM_ABS2 = 0, 1
 QC_ROBUST_HESS_NONE, QC_ROBUST_HESS_EXACT = 0, 1
 QC_MAX_PERT = 8
 QC_SWEEP_FID_NONE = -1      # qc_sweep_desc.fid_kind: final states only
-QC_SWEEP_WIDE = 1           # qc_sweep_desc.wide: the matrix-core form up to 2N = 32
+QC_SWEEP_WIDE = 1           # qc_sweep_desc.wide, bit 0: the matrix-core form up to 2N = 32
+QC_SWEEP_WIDE_PARAMS = 2    # qc_sweep_desc.wide, bit 1 (only with bit 0): parameter gradients and cotangents in that form
 QC_SWEEP_STORED_STATES = 1  # qc_sweep_desc.reserved1[0]: reverse mode by the stored-state walk (open systems)
 QC_ROWS_STACKED = 0
 QC_ROWS_BY_COMPONENT = 1

@@ -23,6 +23,8 @@
 //
 // A descriptor with wide = QC_SWEEP_WIDE takes the matrix cores up to 2N = 32: 16 < 2N <= 32 with up to 8 drives is "mfma32-sweep"
 // (qc_sweep32.hip, 2 x 2 tiles a matrix); the second launch below is shared, with ld = 32.  wide = 0 is the routing above, unchanged.
+// `wide` is a bit field: bit 1 (QC_SWEEP_WIDE_PARAMS, only together with bit 0) changes nothing here -- the form, the launch and the
+// forward sweep are those of wide = 1; it lets qc_sweep_grad_params* and qc_sweep_vjp* serve the parameter outputs in that form.
 #include <math.h>
 #include <string.h>
 
@@ -316,7 +318,8 @@ int qc_sweep_validate_desc(const qc_sweep_desc* d) {
     if (2 * (int64_t)d->N > 64) return qc_sweep_fail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: 2N = " + std::to_string(2 * (int64_t)d->N) + " exceeds the supported 2N <= 64");
     if (2 * (int64_t)d->N * nc > 4096) return qc_sweep_fail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: states of more than 4096 entries (2N x state_cols) are not supported");
     if (d->m > 64) return qc_sweep_fail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: more than 64 drives are not supported");
-    if (d->wide != 0 && d->wide != QC_SWEEP_WIDE) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: wide must be 0 or QC_SWEEP_WIDE (1)");
+    if (d->wide != 0 && d->wide != QC_SWEEP_WIDE && d->wide != (QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS))
+        return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: wide must be 0, QC_SWEEP_WIDE (1) or QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS (3)");
     if (d->reserved1[0] != 0 && d->reserved1[0] != QC_SWEEP_STORED_STATES)
         return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: reserved1[0] must be 0 or QC_SWEEP_STORED_STATES (1)");
     return QC_OK;
@@ -325,12 +328,12 @@ int qc_sweep_validate_desc(const qc_sweep_desc* d) {
 int qc_sweep_desc_form(const qc_sweep_desc* d) {
     if (d->m > kSMmax) return 0;
     if (2 * d->N <= 16) return 1;
-    return (d->wide == QC_SWEEP_WIDE && 2 * d->N <= 32) ? 2 : 0;
+    return ((d->wide & QC_SWEEP_WIDE) && 2 * d->N <= 32) ? 2 : 0;
 }
 bool qc_sweep_desc_is_mfma(const qc_sweep_desc* d) { return qc_sweep_desc_form(d) != 0; }
 
 std::string qc_sweep_per_sample_why(const qc_sweep_desc* d) {
-    const int n = 2 * d->N, top = d->wide == QC_SWEEP_WIDE ? 32 : 16;      // wide descriptors: "mfma32-sweep" up to 2N = 32
+    const int n = 2 * d->N, top = (d->wide & QC_SWEEP_WIDE) ? 32 : 16;      // wide descriptors: "mfma32-sweep" up to 2N = 32
     return n > top ? "the handle takes the rollout-per-sample form (2N = " + std::to_string(n) + " > " + std::to_string(top) + ")"
                    : "the handle takes the rollout-per-sample form (" + std::to_string(d->m) + " drives > 8)";
 }
@@ -410,6 +413,7 @@ extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
     h->device = d->device;
     h->mfma = qc_sweep_desc_is_mfma(d);
     h->mfma32 = qc_sweep_desc_form(d) == 2;
+    h->wide_par = h->mfma32 && (d->wide & QC_SWEEP_WIDE_PARAMS);
     h->grad_ok = qc_sweep_grad_scope(d, &h->grad_why);      // from the caller's matrices, which the handle does not keep
     h->vjp_ok = qc_sweep_vjp_scope(d, &h->vjp_why);
     h->jvp_ok = qc_sweep_jvp_scope(d, &h->jvp_why);

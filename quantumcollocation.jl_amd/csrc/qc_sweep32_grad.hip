@@ -9,7 +9,7 @@
 //   1. qc_sweep_mfma32_kernel: the forward chunk totals, column-major 32 x 32;
 //   2. qc_sweep32_seed_kernel (qc_sweep_grad.hip: the seed of that file at ld = 32), one workgroup per sample: x at every chunk end, the
 //      fidelities with the bits of qc_sweep_eval on the same handle, lambda at every chunk end;
-//   3. qc_sweep32_grad_kernel, one wavefront per (sample, chunk), walking the chunk backwards.  X[I][J] is the tile of rows 16 I .. and
+//   3. qc_sweep32_grad_kernel<false>, one wavefront per (sample, chunk), walking the chunk backwards.  X[I][J] is the tile of rows 16 I .. and
 //      columns 16 J ..; the state and the adjoint are 32 x <= 16: two tiles each.  "A D-layout tile read as the A operand is its
 //      transpose" holds per tile, so for a D-layout matrix M the A operand (I, K) of M^T is the tile M[K][I] as it stands (an index
 //      swap), and the A operand (I, K) of M is the tile M[I][K] transposed through LDS.  Per interval:
@@ -25,7 +25,21 @@
 //      and the m + 1 values of the interval leave through one vector store (lane k: drive k, lane m: timestep).
 //      MFMAs per interval: 16 + 8 x 96 + 96 sq + 32 + 32 = 848 + 96 sq, against the forward kernel's 288 + 32 sq (2.9x - 3x).
 //   4. qc_sweep_grad_reduce_kernel / qc_sweep_J_kernel of qc_sweep_grad.hip, unchanged (they do not depend on the size).
-// No atomics, sums in a fixed order: repeated calls give the same bits.  Parameter gradients are not served in this form.
+// No atomics, sums in a fixed order: repeated calls give the same bits.
+//
+// Parameter gradients and cotangents (descriptors with wide = QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS): the flavour <true> of the walk, the
+// flavour <M, true> of qc_sweep_grad.hip restated on 2 x 2 tiles.  Besides everything above it keeps, per (sample, chunk) wave,
+//     Acc[I][J] = sum_t ZT_t[I][J]   (four tiles; ZT carries the factor h_t)   and, in lane k,   sum_t a_{t,k} du_{t,k},
+// du_{t,k} = sum_IJ ZT[I][J] . G_k[J][I] BEFORE the factor c_k (no division by c: defined at c = 0), a_{t,k} the unscaled control.  At the
+// chunk's end Acc is contracted once with every perturbation's image, dF_s/dtheta_q = sum_t sum(ZT_t . P_q), and the p + m shares go
+// to part[item][p + m]; qc_sweep_par_reduce_kernel (qc_sweep_grad.hip) adds them in ascending chunk order.  16 double adds and one fma a
+// lane and interval, p contractions a chunk, no MFMA more.  With gs = NULL the per-interval store and the timestep's wave sum are skipped.
+// Acc lives in LDS behind the wave's transposition tiles: held in registers (32 a lane) the flavour spilled four vector and sixteen scalar
+// registers; in LDS, with the addresses the chunk's end needs parked in vector registers, it spills nothing.  Two waves a workgroup
+// (2 x 16.9 KB of LDS) instead of four: one wave per SIMD either way, and no static allocation beyond 64 KB.  The flavour <false> is
+// instruction for instruction the walk as it was before the second flavour existed.
+// gfx950 cross-compile: <false> 256 VGPRs + 96 AGPRs, 106 SGPRs, 34816 B LDS (four waves); <true> 248 VGPRs + 96 AGPRs, 106 SGPRs,
+// 33792 B LDS (two waves); no private segment, no spills in either.
 #include <math.h>
 
 #include <string>
@@ -99,14 +113,27 @@ __device__ __forceinline__ void vapplyT(const v4d (&M)[2][2], v4d (&v)[2]) {
     v[1] = y1;
 }
 
-__global__ __launch_bounds__(64 * kWaves) void qc_sweep32_grad_kernel(const Grad32Params P, const double* __restrict__ Z, const double* __restrict__ theta,
+// One wavefront per (sample, chunk), walking the chunk backwards.  PAR = false: the per-interval derivatives
+// only (`part` unused).  PAR = true, the parameter flavour (qc_sweep_grad_kernel<M, true> on 2 x 2 tiles), also keeps Acc = sum_t ZT_t
+// (four tiles) and, in lane k, sum_t a_{t,k} du_{t,k} with du_{t,k} = sum ZT . G_k BEFORE the factor c_k (no division by c: defined at
+// c = 0), contracts Acc with every perturbation's image once at the chunk's end and stores the chunk's shares as part[item][p + m];
+// `gs` may then be NULL (no per-interval store, no timestep derivative).  The per-interval values of the two flavours are the same
+// operations on the same operands: the same bits.
+template <bool PAR>
+constexpr int kGW = PAR ? 2 : kWaves;                      // waves a workgroup: one wave per SIMD either way (512 registers a wave)
+template <bool PAR>
+constexpr int kGSl = PAR ? kScr + 16 * 64 : kScr;          // doubles of LDS a wave: the transposition tiles, PAR: and Acc behind them
+
+template <bool PAR>
+__global__ __launch_bounds__(64 * kGW<PAR>) void qc_sweep32_grad_kernel(const Grad32Params P, const double* __restrict__ Z, const double* __restrict__ theta,
                                                                        const double* __restrict__ scale, const double* __restrict__ xs,
-                                                                       const double* __restrict__ ls, double* __restrict__ gs) {
-    __shared__ double scr_all[kWaves * kScr];
+                                                                       const double* __restrict__ ls, double* __restrict__ gs,
+                                                                       double* __restrict__ part) {
+    __shared__ double scr_all[kGW<PAR> * kGSl<PAR>];
     const int lane = threadIdx.x & 63;
     const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kScr;
-    const long long item = (long long)blockIdx.x * kWaves + wq;
+    double* __restrict__ scr = scr_all + wq * kGSl<PAR>;
+    const long long item = (long long)blockIdx.x * kGW<PAR> + wq;
     if (item >= P.items) return;
     const long long s = item / P.n_chunks;
     const int c = (int)(item - s * P.n_chunks);
@@ -143,6 +170,28 @@ __global__ __launch_bounds__(64 * kWaves) void qc_sweep32_grad_kernel(const Grad
     const double* __restrict__ z = Z + (long long)(t1 - 1) * P.zdim;
     double av = m > 0 ? z[P.off_a + kl] : 0.0;
     double h = ft ? z[P.off_dt] : hfix;
+    // PAR: Acc = sum_t ZT_t lives in the wave's LDS slice (tile q of lane l, register r at accl[64 (4 q + r) + l]: every lane reads back
+    // what it wrote itself, no barrier, one read / write pair per interval off the MFMA chain); lane k's sum_t a_{t,k} du_{t,k} in a register
+    double* accl = scr + kScr;
+    double accv = 0.0;
+    if constexpr (PAR) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) accl[64 * i + lane] = 0.0;
+    }
+    // what the chunk's end needs waits in vector registers (the share's address per lane, p), and the lane's address in gs walks down
+    // in one: the loop has no scalar register to spare
+    double* po = nullptr;
+    double* gp = nullptr;
+    int pv = 0;
+    int nde = P.nd;                  // PAR without gs: 0, no lane stores
+    if constexpr (PAR) {
+        po = part + item * (P.p + m) + lane;
+        pv = P.p;
+        asm volatile("" : "+v"(po), "+v"(pv));
+        nde = gs ? P.nd : 0;
+        gp = gs ? gs + (s * P.n_int + (t1 - 1)) * nde + lane : nullptr;
+        asm volatile("" : "+v"(gp));
+    }
 #pragma unroll 1
     for (int t = t1 - 1; t >= t0; --t) {
         // the previous interval's controls and timestep are requested before this interval's products
@@ -151,7 +200,10 @@ __global__ __launch_bounds__(64 * kWaves) void qc_sweep32_grad_kernel(const Grad
         const double h_n = ft ? zn[P.off_dt] : hfix;
         const double al = av * cl;
         v4d Y[2][2], dY[2][2];
-        generator(P.img, m, al, base, lane, Y);
+        // PAR: the image buffer's address is taken anew where it is used, so that no derived address is kept across the interval
+        const double* __restrict__ img = P.img;
+        if constexpr (PAR) asm volatile("" : "+s"(img));
+        generator(img, m, al, base, lane, Y);
         const int sq = squarings(Y, h);      // the rule of the forward kernel: one function
         const double hs = h * ldexp(1.0, -sq);
         // KT = lambda x^T of knot t+1 (D layout), from the transposed tiles of both; dY in A layout is KT with the block index swapped
@@ -173,8 +225,8 @@ __global__ __launch_bounds__(64 * kWaves) void qc_sweep32_grad_kernel(const Grad
         // the loop (as in qc_sweep_grad_kernel at M = 8)
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        double out = 0.0;
-        if (ft) {
+        double out = 0.0, duv = 0.0;      // duv (PAR): lane k holds du_k = sum ZT . G_k; lanes >= m keep 0
+        if (PAR ? nde > m : ft) {       // PAR: only with gs (nde = nd = m + 1)
             // sum_IJ KT[I][J] . Ga[J][I] = sum_IK dY(I, K) . Ga(I, K)
             double ph = 0.0;
 #pragma unroll
@@ -213,9 +265,11 @@ __global__ __launch_bounds__(64 * kWaves) void qc_sweep32_grad_kernel(const Grad
             Y[0][J] = z0;
             Y[1][J] = z1;
         }
+        const double* __restrict__ imgc = P.img;
+        if constexpr (PAR) asm volatile("" : "+s"(imgc));
 #pragma unroll 1
         for (int u = 0; u < m; ++u) {
-            const double* __restrict__ Gu = P.img + (size_t)(1 + u) * 1024;
+            const double* __restrict__ Gu = imgc + (size_t)(1 + u) * 1024;
             double pu = 0.0;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -224,20 +278,54 @@ __global__ __launch_bounds__(64 * kWaves) void qc_sweep32_grad_kernel(const Grad
                 for (int r = 0; r < 4; ++r) pu = fma(Y[q & 1][q >> 1][r], t4[r], pu);
             }
             const double du = vwave_sum(pu);
-            out = ln == u ? du * cl : out;
+            if constexpr (PAR) duv = ln == u ? du : duv;
+            else out = ln == u ? du * cl : out;
         }
-        if (ln < P.nd) gs[(s * P.n_int + t) * P.nd + lane] = out;
+        if constexpr (PAR) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) accl[64 * (4 * q + r) + lane] += Y[q >> 1][q & 1][r];
+            accv = fma(av, duv, accv);
+            out = ln < m ? duv * cl : out;
+            if (ln < nde) *gp = out;
+            gp -= nde;
+        } else {
+            if (ln < P.nd) gs[(s * P.n_int + t) * P.nd + lane] = out;
+        }
         vapplyT(R, x);
         vapplyT(R, lam);
         av = av_n;
         h = h_n;
+    }
+    if constexpr (PAR) {
+        // the chunk's shares: one contraction of Acc per perturbation, the image tiles read once here; tile (J, I) = u against Acc[I][J]
+        const int p = __builtin_amdgcn_readfirstlane(pv);
+        int le = lane;
+        asm volatile("" : "+v"(le));      // the lane compares are made here, not kept across the loop
+        double acc_t = 0.0;
+#pragma unroll 1
+        for (int q = 0; q < p; ++q) {
+            const double* __restrict__ Pq = P.img + (size_t)(1 + m + q) * 1024;
+            double pq = 0.0;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const v4d t4 = load_image_tile(Pq + u * 256, lane);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) pq = fma(accl[64 * (4 * (2 * (u & 1) + (u >> 1)) + r) + lane], t4[r], pq);
+            }
+            const double dq = vwave_sum(pq);
+            acc_t = le == q ? dq : acc_t;
+        }
+        if (le < p) po[0] = acc_t;
+        if (le < m) po[p] = accv;
     }
 }
 
 }  // namespace
 
 void qc_sweep32_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,
-                            double* gs, hipStream_t st) {
+                            double* gs, bool par, double* dgrad_theta, double* dgrad_scale, hipStream_t st) {
     Grad32Params P;
     P.n = h->n; P.nc = h->nc; P.m = h->d.m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
     P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks; P.nd = P.m + (P.off_dt >= 0 ? 1 : 0);
@@ -245,6 +333,11 @@ void qc_sweep32_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const doub
     P.dt_fixed = h->d.dt_fixed;
     P.img = h->dImg;
     const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
-    hipLaunchKernelGGL(qc_sweep32_grad_kernel, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, (const double*)h->dXs.p,
-                       (const double*)h->dLs.p, gs);
+    if (par) {
+        hipLaunchKernelGGL(qc_sweep32_grad_kernel<true>, dim3((unsigned)((P.items + kGW<true> - 1) / kGW<true>)), dim3(64 * kGW<true>), 0, st, P, dZ, dtheta, dscale, (const double*)h->dXs.p,
+                           (const double*)h->dLs.p, gs, h->dPart.p);
+        qc_sweep_launch_par_reduce(h, S, n_chunks, dgrad_theta, dgrad_scale, st);
+    } else
+        hipLaunchKernelGGL(qc_sweep32_grad_kernel<false>, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, (const double*)h->dXs.p,
+                           (const double*)h->dLs.p, gs, (double*)nullptr);
 }

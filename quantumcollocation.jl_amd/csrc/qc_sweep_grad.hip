@@ -17,7 +17,8 @@
 // reserved1[0] = QC_SWEEP_STORED_STATES: such handles are routed to the stored-state walk of qc_sweep_open_grad.hip, whatever their
 // generators, behind the same totals, seed (with lambda = g_r for the density fidelity) and reductions; qc_sweep_reverse_scope decides.
 // Wide descriptors (wide = QC_SWEEP_WIDE) extend the scope to the "mfma32-sweep" form, 2N <= 32: this file routes such handles to the
-// seed and walk kernels of qc_sweep32_grad.hip and shares its reductions (launch 4) with them; no parameter gradients there.
+// seed and walk kernels of qc_sweep32_grad.hip and shares its reductions (launch 4) with them; parameter gradients there only for
+// descriptors that also set QC_SWEEP_WIDE_PARAMS (the flavour <true> of that file's walk, then qc_sweep_par_reduce_kernel of this one).
 //
 // Launches of one call:
 //   1. the forward chunk totals: qc_sweep_mfma16_kernel of qc_sweep.hip, unchanged, same chunk rule;
@@ -524,6 +525,9 @@ void qc_sweep_launch_weighted(qc_sweep* h, int64_t S, const double* gsamp, const
     if (dJ) hipLaunchKernelGGL(qc_sweep_J_kernel, dim3(1), dim3(kRedT), 0, st, (long long)S, dfids, dweights, dJ);
 }
 
+// "mfma32-sweep" handles made without QC_SWEEP_WIDE_PARAMS, in scope or not: the refusal of both parameter entry points
+static const char* const kNoWideParGrad = "qc_sweep gradients: parameter gradients are not served in the mfma32-sweep form";
+
 // the argument checks of all four entry points, in the order of the header
 static int grad_check(qc_sweep* h, const char* who, const double* Z, const double* init, int64_t S, const double* theta, bool any_out, bool g_theta,
                       bool g_scale) {
@@ -576,7 +580,8 @@ static int qc_sweep_grad_launch(qc_sweep* h, const char* who, const double* dZ, 
             qc_sweep_open_launch_walk(h, dZ, dinit, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta,
                                       dgrad_scale, st);
     } else if (h->mfma32) {      // the 2 x 2-tile form: its own walk (qc_sweep32_grad.hip), then the reductions below
-        if (want_grad) qc_sweep32_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, gsamp, st);
+        if (want_grad || want_par)      // want_par: only on handles with QC_SWEEP_WIDE_PARAMS (the entry points refuse the others)
+            qc_sweep32_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);
     } else if (want_grad || want_par)
         qc_sweep16_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);
     qc_sweep_launch_weighted(h, S, gsamp, dweights, dfids, dgrad, dJ, st);
@@ -594,7 +599,7 @@ extern "C" int qc_sweep_grad_dev(qc_sweep* h, const double* dZ, const double* di
 extern "C" int qc_sweep_grad_params_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
                                         const double* dweights, double* dfids, double* dJ, double* dgrad, double* dgrad_samples,
                                         double* dgrad_theta, double* dgrad_scale, void* stream) {
-    if (h && h->mfma32) return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, "qc_sweep gradients: parameter gradients are not served in the mfma32-sweep form");
+    if (h && h->mfma32 && !h->wide_par) return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, kNoWideParGrad);
     return qc_sweep_grad_launch(h, "qc_sweep_grad_params_dev", dZ, dinit, S, dtheta, dscale, dweights, dfids, dJ, dgrad, dgrad_samples, dgrad_theta,
                                 dgrad_scale, stream);
 }
@@ -633,6 +638,6 @@ extern "C" int qc_sweep_grad(qc_sweep* h, const double* Z, const double* init, i
 extern "C" int qc_sweep_grad_params(qc_sweep* h, const double* Z, const double* init, int64_t S, const double* theta, const double* scale,
                                     const double* weights, double* fids, double* J, double* grad, double* grad_samples, double* grad_theta,
                                     double* grad_scale) {
-    if (h && h->mfma32) return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, "qc_sweep gradients: parameter gradients are not served in the mfma32-sweep form");
+    if (h && h->mfma32 && !h->wide_par) return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, kNoWideParGrad);
     return qc_sweep_grad_host(h, "qc_sweep_grad_params", Z, init, S, theta, scale, weights, fids, J, grad, grad_samples, grad_theta, grad_scale);
 }

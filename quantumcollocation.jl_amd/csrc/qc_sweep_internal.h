@@ -11,6 +11,7 @@ struct qc_sweep : qc_side {
     qc_sweep_desc d;             // caller-owned arrays are not retained (pointers nulled)
     bool mfma = false;
     bool mfma32 = false;         // the 2 x 2-tile form of a wide descriptor ("mfma32-sweep", qc_sweep32.hip); mfma is set as well
+    bool wide_par = false;       // mfma32 and wide has QC_SWEEP_WIDE_PARAMS: parameter gradients and cotangents are served (qc_sweep32_grad.hip)
     bool stored = false;         // reserved1[0] = QC_SWEEP_STORED_STATES: reverse mode by the stored-state walk (qc_sweep_open_grad.hip)
     bool grad_ok = false;        // the gradient's scope (qc_sweep_grad.hip), decided at create from the caller's matrices
     std::string grad_why;        // when not: the reason
@@ -99,9 +100,10 @@ int qc_sweep_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const doubl
 void qc_sweep32_image(const double* G, int n, double* img);
 int qc_sweep32_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, hipStream_t st, int64_t* chunk,
                              int64_t* n_chunks);
-// "mfma32-sweep" gradients (qc_sweep32_grad.hip): the backward walk qc_sweep32_grad_kernel (gs: S x (T-1) x nd); scratch is the caller's
+// "mfma32-sweep" gradients (qc_sweep32_grad.hip): the backward walk qc_sweep32_grad_kernel<false> (gs: S x (T-1) x nd), or with `par` the
+// parameter flavour <true> (gs may be NULL) and qc_sweep_par_reduce_kernel out of h->dPart; scratch is the caller's
 void qc_sweep32_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,
-                            double* gs, hipStream_t st);
+                            double* gs, bool par, double* dgrad_theta, double* dgrad_scale, hipStream_t st);
 // "mfma16-sweep" handles (qc_sweep_grad.hip): the backward walk qc_sweep_grad_kernel<M, false> (gs: S x (T-1) x nd), or with `par` the
 // parameter flavour <M, true> (gs may be NULL) and qc_sweep_par_reduce_kernel out of h->dPart; scratch is the caller's
 void qc_sweep16_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,

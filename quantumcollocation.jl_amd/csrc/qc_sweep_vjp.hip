@@ -3,7 +3,7 @@
 // its header first) holds unchanged:
 //     dphi_s/da_{t,k} = c_k h <L(hG^T; lambda_{t+1} x_t^T), G_k>,   dphi_s/dh_t = <lambda_{t+1}, G x_{t+1}>,   lambda_t = E_t^T lambda_{t+1},
 // and, the final state being linear in the initial one, dphi_s/dinit = lambda_0.  The backward walks (qc_sweep_grad_kernel<M, PAR>,
-// qc_sweep32_grad_kernel) read lambda from a buffer and do not know where it came from: they are launched as they are, through
+// qc_sweep32_grad_kernel<PAR>) read lambda from a buffer and do not know where it came from: they are launched as they are, through
 // qc_sweep16_launch_walk / qc_sweep32_launch_walk.  What is new here is the seed and the plain sum.
 //
 // Launches of one call:
@@ -14,7 +14,8 @@
 //      lambda <- Q_c^T lambda for c = n_chunks-1 .. 1, stored at every chunk end into dLs.  With `grad_init` one more step than the
 //      fidelity seeds take: lambda_0 = Q_0^T lambda_{end of chunk 0}.  (n_chunks = 1: that step is the only transposed product.)
 //   3. the walk, when a derivative over the intervals or the parameters is asked for: flavour <M, false> without grad_theta /
-//      grad_scale, <M, true> and qc_sweep_par_reduce_kernel with either (as qc_sweep_grad_launch chooses); the wide walk has one flavour.
+//      grad_scale, <M, true> and qc_sweep_par_reduce_kernel with either (as qc_sweep_grad_launch chooses); the wide walk likewise
+//      (qc_sweep32_grad_kernel<false> / <true>), its parameter flavour only on handles made with QC_SWEEP_WIDE_PARAMS.
 //      With m = 0 and a fixed timestep there is nothing per interval: only <1, true> runs, and only for grad_theta.
 //   4. qc_sweep_vjp_reduce_kernel: grad = sum_s dphi_s/dZ, the PLAIN sum in ascending s (qc_sweep_grad_reduce_kernel reads a missing
 //      weight vector as 1/S each); +0.0 at every entry that is not a control or timestep of knots 0 .. T-2.
@@ -110,7 +111,7 @@ int vjp_check(qc_sweep* h, const char* who, const void* Z, const void* init, int
     if (!any_out) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "every output is NULL");
     if (g_theta && h->d.n_pert == 0) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "grad_theta is given but the handle has no perturbations (n_pert = 0)");
     if (g_scale && h->d.m == 0) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "grad_scale is given but the handle has no drives (m = 0)");
-    if ((g_theta || g_scale) && h->mfma32) return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, kNoWidePar);
+    if ((g_theta || g_scale) && h->mfma32 && !h->wide_par) return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, kNoWidePar);
     return QC_OK;
 }
 
@@ -177,7 +178,8 @@ static int qc_sweep_vjp_launch(qc_sweep* h, const char* who, const double* dZ, c
             qc_sweep_open_launch_walk(h, dZ, dinit, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta,
                                       dgrad_scale, st);
     } else if (h->mfma32) {
-        if (want_grad) qc_sweep32_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, gsamp, st);
+        if (want_grad || want_par)
+            qc_sweep32_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);
     } else if (want_grad || want_par)
         qc_sweep16_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);
     if (dgrad) qc_sweep_launch_plain_sum(h, S, gsamp, dgrad, st);

@@ -177,8 +177,9 @@ class RolloutSweep:
     The trajectory vector is knot-major with the controls at `off_a` and the timestep at `off_dt` of every knot of `zdim`
     entries (default: the minimal layout [a, dt], built by `pack`; dt_fixed: no timestep in the knot).
     wide           True: systems of 16 < 2N <= 32 with up to 8 drives run on the matrix cores too ("mfma32-sweep", with gradients over the
-                   controls and timesteps; no parameter gradients there yet) instead of one rollout per sample.  Nothing changes at
-                   2N <= 16.
+                   controls and timesteps) instead of one rollout per sample.  Nothing changes at 2N <= 16.
+    wide_params    True (only with `wide`): an "mfma32-sweep" handle also serves `param_grad`, the `params` of `vjp` and the theta /
+                   scale gradients of `finals_autograd`.  Without it those refuse there, as they always did; nothing else changes.
     stored_states  True: `grad`, `grad_params` and `vjp` keep the forward states of every sample on the device (S x (T-1) x 2N x cols
                    doubles) and read them on the way back instead of reversing the step.  That serves ANY generators in the
                    "mfma16-sweep" form: an `OpenQuantumSystem` with the "density" fidelity, a non-Hermitian effective Hamiltonian.
@@ -187,8 +188,10 @@ class RolloutSweep:
     def __init__(self, system, perturbations, T: int, cols: Optional[int] = None, goal=None, fid_kind=None, subspace=None,
                  fid_form: int = _lib.QC_FID_FORM_ABS, zdim: Optional[int] = None, off_a: int = 0, off_dt: Optional[int] = None,
                  dt_fixed: Optional[float] = None, global_dim: int = 0, device: int = 0, wide: bool = False,
-                 stored_states: bool = False):
+                 stored_states: bool = False, wide_params: bool = False):
         self._h = None
+        if wide_params and not wide:
+            raise ValueError("wide_params=True needs wide=True")
         m = system.n_drives
         N = system.state_levels
         n = 2 * N
@@ -222,8 +225,9 @@ class RolloutSweep:
         d.subspace = self._sub.ctypes.data_as(C.POINTER(C.c_int32)) if self._sub is not None else None
         d.n_sub = 0 if self._sub is None else int(self._sub.size)
         d.device = device
-        d.wide = _lib.QC_SWEEP_WIDE if wide else 0
+        d.wide = (_lib.QC_SWEEP_WIDE if wide else 0) | (_lib.QC_SWEEP_WIDE_PARAMS if wide_params else 0)
         self.wide = bool(wide)
+        self.wide_params = bool(wide_params)
         d.reserved1[0] = _lib.QC_SWEEP_STORED_STATES if stored_states else 0
         self.stored_states = bool(stored_states)
         self._desc = d
@@ -375,7 +379,8 @@ class RolloutSweep:
     # -- gradients with respect to the systems: dF_s/dtheta and dF_s/dscale ---------------------------------------------------
     def param_grad(self, Z, init, theta, scale=None, weights=None, with_controls: bool = False):
         """(fids, grad_theta, grad_scale): the S fidelities, dF_s/dtheta[s, j] (S x n_pert) and dF_s/dscale[s, k] (S x m; `scale`
-        None: taken at all ones), raw per-sample values from one backward walk (`qc_sweep_grad_params`).  With `with_controls`:
+        None: taken at all ones), raw per-sample values from one backward walk (`qc_sweep_grad_params`; "mfma16-sweep" handles, and
+        "mfma32-sweep" handles made with `wide_params`).  With `with_controls`:
         (J, fids, grad, grad_theta, grad_scale), J and the dense gradient over the trajectory vector as `grad` returns them."""
         Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
         if Z.size != self.Z_len:
@@ -448,7 +453,8 @@ class RolloutSweep:
         by what was asked for:
             per_sample   grad_samples, S x (T-1) x n_deriv: dphi_s/d(a_t, dt_t)
             init_grad    grad_init, S x (2N cols): dphi_s/dinit
-            params       grad_theta (S x n_pert) and grad_scale (S x m), two entries ("mfma16-sweep" handles only)."""
+            params       grad_theta (S x n_pert) and grad_scale (S x m), two entries ("mfma16-sweep" handles, and "mfma32-sweep" handles made
+                         with `wide_params`)."""
         Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
         if Z.size != self.Z_len:
             raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
@@ -806,7 +812,8 @@ class RolloutSweep:
         `vjp_device` call, and under `torch.autograd.forward_ad` the tangent is one `jvp_device` call ("mfma16-sweep" handles).  dZ
         (Z_len), dinit (2N cols), dtheta (S x n_pert), dscale (S x m or None) are float64 CUDA tensors; whichever requires grad
         receives one: Z the plain sum over the samples, init the sum of the per-sample derivatives, theta and scale their per-sample
-        values ("mfma16-sweep" handles only: on a wide handle a theta or scale that requires grad raises in backward)."""
+        values ("mfma16-sweep" handles, and "mfma32-sweep" handles made with `wide_params`: on a wide handle made without it a theta or
+        scale that requires grad raises in backward)."""
         if dtheta is None and dscale is None:
             raise ValueError("dtheta (S x n_pert) or dscale (S x m) must give the number of samples")
         S = (dtheta if dtheta is not None else dscale).shape[0]
@@ -862,7 +869,7 @@ class _SweepFinals(torch.autograd.Function):
         need_Z, need_init, need_theta, need_scale = ctx.needs_input_grad[2:6]
         if not (need_Z or need_init or need_theta or need_scale):
             return (None,) * 6
-        if sw.kernel_name == "mfma32-sweep" and (need_theta or need_scale):
+        if sw.kernel_name == "mfma32-sweep" and not sw.wide_params and (need_theta or need_scale):
             raise _lib.QCollocError(_lib.QC_ERR_UNSUPPORTED, "qc_sweep pullback: parameter cotangents are not served in the mfma32-sweep form")
         mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dZ.device)
         gZ = mk(sw.Z_len) if need_Z else None
@@ -921,10 +928,11 @@ def rollout_noise_sweep(init, controls, dts, system, perturbations, noise, theta
 
 def rollout_sweep_parameter_gradient(init, controls, dts, system, perturbations, theta, scale=None, cols: Optional[int] = None, goal=None,
                                      fid_kind="unitary", subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS,
-                                     stored_states: bool = False):
+                                     stored_states: bool = False, wide: bool = False):
     """(fids, grad_theta, grad_scale) of S rollouts under the perturbed systems: the fidelities of `rollout_sweep` and their derivatives
     with respect to theta (S x len(perturbations)) and scale (S x n_drives; None: taken at all ones).  Arguments as `rollout_sweep`;
-    `stored_states=True` serves open systems (`RolloutSweep`)."""
+    `stored_states=True` serves open systems (`RolloutSweep`); `wide=True` serves 16 < 2N <= 32 on the matrix cores (the handle is made
+    with `wide` and `wide_params`)."""
     controls = np.asarray(controls, dtype=np.float64)
     if controls.ndim != 2 or controls.shape[0] != system.n_drives:
         raise ValueError("controls must be n_drives x T")
@@ -934,7 +942,7 @@ def rollout_sweep_parameter_gradient(init, controls, dts, system, perturbations,
     if cols is None:
         cols = init.size // n
     sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device,
-                      stored_states=stored_states)
+                      stored_states=stored_states, wide=wide, wide_params=wide)
     try:
         return sw.param_grad(sw.pack(controls, dts), init, theta, scale)
     finally:
