@@ -628,32 +628,39 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * work item and chunk rule); 2N <= 16 is "mfma16-sweep" as before, everything else the per-sample form.  wide = 0 is the routing of the
  * two sentences above, unchanged.  wide = QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS (3) is wide = QC_SWEEP_WIDE in every respect but one:
  * an "mfma32-sweep" handle then serves the parameter gradients (qc_sweep_grad_params*) and the parameter cotangents of the pullback
- * (qc_sweep_vjp*: grad_theta, grad_scale).  Any other value (bit 1 without bit 0 among them) is QC_ERR_INVALID.
+ * (qc_sweep_vjp*: grad_theta, grad_scale).  Bit 3, QC_SWEEP_WIDE_STORED (wide = 9, or 11 with the parameter bit), likewise changes one
+ * thing only: an "mfma32-sweep" handle whose descriptor also sets reserved1[0] = QC_SWEEP_STORED_STATES then serves reverse mode by the
+ * stored-state walk on 2 x 2 tiles (below); without reserved1[0], or where the handle takes another form, the bit does nothing.  The
+ * valid values are 0, 1, 3, 9 and 11; any other value (bit 1 or 3 without bit 0, bit 2, 5 and 7 among them) is QC_ERR_INVALID.
  * reserved1[0] = QC_SWEEP_STORED_STATES chooses reverse mode by the STORED-STATE walk: qc_sweep_grad*, qc_sweep_grad_params* and
  * qc_sweep_vjp* then keep the forward states x_0 .. x_{T-2} of every sample in handle scratch (S x (T-1) x 2N x cols doubles) and read
  * them on the way back instead of reversing the step, which serves ANY generators in the "mfma16-sweep" form: Lindblad generators
- * (N = levels^2) with QC_FID_DENSITY, non-Hermitian effective Hamiltonians.  A handle with the flag takes that walk whatever its
+ * (N = levels^2) with QC_FID_DENSITY, non-Hermitian effective Hamiltonians.  The "mfma32-sweep" form (two qubits with T1 / T2: levels^2 = 16,
+ * 2N = 32; a three-level transmon: 2N = 18) serves it for descriptors that also set QC_SWEEP_WIDE_STORED in `wide`.  The buffer is
+ * S x (T-1) x 2N x cols doubles: 32 doubles a knot for a two-qubit Lindblad state (250 MiB at S = 1024, T = 1000), 512 doubles a knot
+ * for a 16-level unitary (4 GiB at S = 1024, T = 1000); an allocation that fails is QC_ERR_HIP, and the handle stays usable.  A handle with the flag takes that walk whatever its
  * generators, antisymmetric ones included.  reserved1[0] = 0 is everything as it was, bit for bit; any other value is QC_ERR_INVALID;
  * reserved1[1] is ignored.  qc_sweep_eval*, qc_sweep_jvp*, qc_sweep_noise_eval* do not look at the flag, and qc_sweep_hvp* /
  * qc_sweep_noise_grad* keep their scope (antisymmetric generators) and their kernels with it.
  * Results do not depend on scheduling: repeated calls return the same bits.  Non-finite inputs are evaluated, not rejected.
  * Gradients with respect to the controls and timesteps (qc_sweep_grad*) and to the samples' own parameters theta and `scale`
  * (qc_sweep_grad_params*), both below, are served for closed systems in the MFMA forms (parameter gradients: "mfma16-sweep" only), and
- * with reserved1[0] = QC_SWEEP_STORED_STATES for open systems in the "mfma16-sweep" form.
+ * with reserved1[0] = QC_SWEEP_STORED_STATES for open systems in the "mfma16-sweep" form and, with QC_SWEEP_WIDE_STORED, the "mfma32-sweep" form.
  * Derivatives of the final states themselves, contracted with cotangents the caller chooses (qc_sweep_vjp*, below), carry any function
  * of the final states: leakage, the free-phase fidelity, several kets at once, a loss written elsewhere.
  * The forward-mode counterpart, the tangent of the final states and fidelities along one direction (qc_sweep_jvp*, below), is served
  * for "mfma16-sweep" handles with any generators, Lindblad ones included; with the pullback it gives Gauss-Newton products of any loss.
  * The tangent of the pullback along one direction (qc_sweep_hvp*, below) gives exact Hessian products of any loss of the final states
  * where both of them are served (closed systems, "mfma16-sweep").
- * Out of scope: per-knot outputs, open-system gradients in the "mfma32-sweep" form (2N > 16: the stored-state walk is built for
- * "mfma16-sweep" only; their directional derivatives are not served there either), Hessian products and noise gradients of open
+ * Out of scope: per-knot outputs, open-system gradients in the "mfma32-sweep" form without QC_SWEEP_WIDE_STORED (their directional
+ * derivatives are not served there at all), checkpointing inside a chunk, Hessian products and noise gradients of open
  * systems, pushforwards on "mfma32-sweep" and "rollout-per-sample" handles (Hessian products likewise), several directions per
  * call, tangents of grad_theta / grad_scale, several devices. */
 #define QC_MAX_PERT 8
 #define QC_SWEEP_FID_NONE (-1)   /* qc_sweep_desc.fid_kind: final states only */
 #define QC_SWEEP_WIDE 1          /* qc_sweep_desc.wide, bit 0 */
 #define QC_SWEEP_WIDE_PARAMS 2   /* qc_sweep_desc.wide, bit 1: the mfma32-sweep form serves parameter gradients and parameter cotangents; only together with QC_SWEEP_WIDE */
+#define QC_SWEEP_WIDE_STORED 8   /* qc_sweep_desc.wide, bit 3: the mfma32-sweep form serves the stored-state walk; only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_STORED_STATES 1 /* qc_sweep_desc.reserved1[0]: reverse mode by the stored-state walk */
 typedef struct qc_sweep_desc {
     int64_t T;
@@ -675,8 +682,8 @@ typedef struct qc_sweep_desc {
     const double* goal_iso;      /* as qc_fidelity_desc.goal_iso */
     const int32_t* subspace;     /* unitary only: 0-based levels, or NULL = all */
     int32_t device;
-    int32_t wide;                /* bit field; valid: 0, QC_SWEEP_WIDE (1): the matrix-core form up to 2N = 32 ("mfma32-sweep"), or QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS (3): that form, and qc_sweep_grad_params* / the grad_theta, grad_scale of qc_sweep_vjp* are served in it (form, launch, kernel name and every *_supported answer as with 1; harmless where the handle takes another form); anything else is QC_ERR_INVALID */
-    int64_t reserved1[2];        /* [0]: 0, or QC_SWEEP_STORED_STATES: reverse mode reads stored forward states (any generators, "mfma16-sweep"); anything else is QC_ERR_INVALID.  [1]: ignored */
+    int32_t wide;                /* bit field; valid: 0, QC_SWEEP_WIDE (1): the matrix-core form up to 2N = 32 ("mfma32-sweep"), or QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS (3): that form, and qc_sweep_grad_params* / the grad_theta, grad_scale of qc_sweep_vjp* are served in it (form, launch, kernel name and every *_supported answer as with 1; harmless where the handle takes another form); either of them | QC_SWEEP_WIDE_STORED (9, 11): that form also serves reverse mode by the stored-state walk when reserved1[0] = QC_SWEEP_STORED_STATES (nothing else changes); anything else is QC_ERR_INVALID */
+    int64_t reserved1[2];        /* [0]: 0, or QC_SWEEP_STORED_STATES: reverse mode reads stored forward states (any generators; "mfma16-sweep", and "mfma32-sweep" with QC_SWEEP_WIDE_STORED in `wide`); anything else is QC_ERR_INVALID.  [1]: ignored */
 } qc_sweep_desc;
 typedef struct qc_sweep qc_sweep;
 int64_t qc_sizeof_sweep_desc(void);
@@ -713,7 +720,9 @@ int qc_sweep_eval_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_
  *     of Hermitian operators; Lindblad generators are not).
  * With reserved1[0] = QC_SWEEP_STORED_STATES the scope is instead: the "mfma16-sweep" form (2N <= 16, m <= 8), at most 16 state columns,
  * a fidelity on the handle -- QC_FID_DENSITY included (F = Re t is linear: lambda_{T-1} = g_r) -- and ANY generators.  A wide handle
- * in the "mfma32-sweep" form with the flag is refused ("stored-state gradients are not served in the mfma32-sweep form").
+ * in the "mfma32-sweep" form with the flag is refused ("stored-state gradients are not served in the mfma32-sweep form") unless its
+ * `wide` has QC_SWEEP_WIDE_STORED (9 or 11): then the same scope holds with 2N <= 32 (the 2 x 2-tile stored-state walk, whatever the
+ * generators, antisymmetric ones included).
  * The last knot's controls and timestep enter no interval: their derivatives are exactly +0.0, as is every entry of `grad` that is
  * neither a control nor a timestep.  The |tr| / n form is not special-cased at tr = 0 (NaN there, as qc_fidelity_eval).
  * `fids` carry the bits of qc_sweep_eval; repeated calls return the same bits (no atomics, sums in a fixed order). */
@@ -743,7 +752,8 @@ int qc_sweep_grad(qc_sweep* h, const double* Z, const double* init, int64_t S, c
  * On an "mfma32-sweep" handle made with wide = QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS both entry points behave exactly as on an
  * "mfma16-sweep" handle (the parameter flavour of the 2 x 2-tile walk; scope, checks and outputs as above, fids / J / grad / grad_samples
  * with the bits of qc_sweep_grad on the same handle).  On one made with wide = QC_SWEEP_WIDE alone both return QC_ERR_UNSUPPORTED
- * ("parameter gradients are not served in the mfma32-sweep form"). */
+ * ("parameter gradients are not served in the mfma32-sweep form"), with or without QC_SWEEP_WIDE_STORED: the stored-state walk's
+ * parameter flavour on 2 x 2 tiles needs wide = 11. */
 int qc_sweep_grad_params_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
                              const double* dweights, double* dfids, double* dJ, double* dgrad, double* dgrad_samples,
                              double* dgrad_theta, double* dgrad_scale, void* stream);
@@ -759,8 +769,8 @@ int qc_sweep_grad_params(qc_sweep* h, const double* Z, const double* init, int64
  * state being linear in the initial one, dphi_s/dinit = lambda_0 comes from one more transposed product of the seed. */
 /* device-free: may the pullback serve this descriptor?  Scope = the gradient's scope WITHOUT its two fidelity conditions: an MFMA form
  * ("mfma16-sweep", or "mfma32-sweep" with wide = QC_SWEEP_WIDE), antisymmetric drift / drives / perturbations (the same 64-eps test),
- * at most 16 state columns; with reserved1[0] = QC_SWEEP_STORED_STATES the "mfma16-sweep" form, at most 16 state columns, any
- * generators.  fid_kind may be anything, QC_SWEEP_FID_NONE and QC_FID_DENSITY included.  When 0,
+ * at most 16 state columns; with reserved1[0] = QC_SWEEP_STORED_STATES the "mfma16-sweep" form (or "mfma32-sweep" with
+ * QC_SWEEP_WIDE_STORED in `wide`), at most 16 state columns, any generators.  fid_kind may be anything, QC_SWEEP_FID_NONE and QC_FID_DENSITY included.  When 0,
  * qc_sweep_last_error(NULL) says why, prefixed "qc_sweep pullback: ".  An invalid descriptor returns its own error. */
 int qc_sweep_desc_vjp_supported(const qc_sweep_desc* d, int32_t* supported);
 /* phi_s = <cot[s], x_final[s]>.  cot: S x (2N cols), the layout of `finals`.  Outputs, each optional, at least one non-NULL:

@@ -707,14 +707,16 @@ reference's robustness check, `unitary_rollout(traj.a, timesteps, systems(ζ))[:
 (2N×2N generators: `system.G_drift`, `system.G_drives`, and e.g. `G(Z)` for a detuning).  `controls` is m×T, `Δt` a vector of T
 timesteps, `θ` S×p, `scale` S×m or nothing; `fid_kind` -1 (none), 0 (unitary; `subspace` 1-based, `squared`), 1 (ket), 2 (density
 operator).  `wide = true` sets `qc_sweep_desc.wide = QC_SWEEP_WIDE`: the matrix-core form up to 2N = 32 ("mfma32-sweep") instead of one
-rollout per sample from 2N = 18 up.  `stored_states = true` sets `qc_sweep_desc.reserved1[1] = QC_SWEEP_STORED_STATES` (C index 0): reverse
+rollout per sample from 2N = 18 up.  `wide_stored = true` (only with `wide` and `stored_states`) adds `QC_SWEEP_WIDE_STORED` (8) to
+`qc_sweep_desc.wide`: the stored-state walk then serves 16 < 2N ≤ 32 too (two qubits with T1 / T2), in `rollout_sweep_gradient`,
+`rollout_sweep_parameter_gradient` and `rollout_sweep_pullback`.  `stored_states = true` sets `qc_sweep_desc.reserved1[1] = QC_SWEEP_STORED_STATES` (C index 0): reverse
 mode (`rollout_sweep_gradient`, `rollout_sweep_parameter_gradient`, `rollout_sweep_pullback`) then reads stored forward states and serves
 open systems with 2N ≤ 16 -- Lindblad generators with `fid_kind = 2`, non-Hermitian effective Hamiltonians; the forward sweep itself does
 not look at it.  `finals` is (2N·cols)×S.  UNTESTED here, like the rest of this file.
 """
 function rollout_sweep(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift, G_drives, G_pert,
                        θ::AbstractMatrix{Float64}; scale=nothing, cols::Int, goal=nothing, fid_kind::Int=-1, subspace=nothing,
-                       squared::Bool=false, device::Int=0, wide::Bool=false, stored_states::Bool=false)
+                       squared::Bool=false, device::Int=0, wide::Bool=false, stored_states::Bool=false, wide_stored::Bool=false)
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(θ, 1)
     G0 = Float64.(vec(G_drift))
@@ -732,7 +734,7 @@ function rollout_sweep(init::AbstractVector{Float64}, controls::AbstractMatrix{F
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
                                squared ? 1 : 0, length(sub), isempty(g) ? C_NULL : pointer(g), isempty(sub) ? C_NULL : pointer(sub),
-                               device, wide ? 1 : 0, (stored_states ? 1 : 0, 0)))
+                               device, (wide ? 1 : 0) | (wide_stored ? 8 : 0), (stored_states ? 1 : 0, 0)))      # 8 = QC_SWEEP_WIDE_STORED
         rc = ccall((:qc_sweep_create, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Ptr{Cvoid}}), desc, h)
         rc == 0 || error("qc_sweep_create: " * unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
     end
@@ -758,7 +760,7 @@ m ≤ 8 and `fid_kind` 0, 1 or 2 (density operator); everything else errors with
 """
 function rollout_sweep_gradient(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift, G_drives,
                                 G_pert, θ::AbstractMatrix{Float64}; scale=nothing, weights=nothing, cols::Int, goal, fid_kind::Int=0,
-                                subspace=nothing, squared::Bool=false, per_sample::Bool=false, device::Int=0, wide::Bool=false, stored_states::Bool=false)
+                                subspace=nothing, squared::Bool=false, per_sample::Bool=false, device::Int=0, wide::Bool=false, stored_states::Bool=false, wide_stored::Bool=false)
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(θ, 1)
     G0 = Float64.(vec(G_drift))
@@ -779,7 +781,7 @@ function rollout_sweep_gradient(init::AbstractVector{Float64}, controls::Abstrac
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
                                squared ? 1 : 0, length(sub), pointer(g), isempty(sub) ? C_NULL : pointer(sub),
-                               device, wide ? 1 : 0, (stored_states ? 1 : 0, 0)))
+                               device, (wide ? 1 : 0) | (wide_stored ? 8 : 0), (stored_states ? 1 : 0, 0)))      # 8 = QC_SWEEP_WIDE_STORED
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_grad_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
         (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
@@ -906,7 +908,7 @@ UNTESTED here, like the rest of this file.
 """
 function rollout_sweep_parameter_gradient(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift,
                                           G_drives, G_pert, θ::AbstractMatrix{Float64}; scale=nothing, cols::Int, goal, fid_kind::Int=0,
-                                          subspace=nothing, squared::Bool=false, device::Int=0, stored_states::Bool=false, wide::Bool=false)
+                                          subspace=nothing, squared::Bool=false, device::Int=0, stored_states::Bool=false, wide_stored::Bool=false, wide::Bool=false)
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(θ, 1)
     G0 = Float64.(vec(G_drift))
@@ -925,7 +927,7 @@ function rollout_sweep_parameter_gradient(init::AbstractVector{Float64}, control
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
                                squared ? 1 : 0, length(sub), pointer(g), isempty(sub) ? C_NULL : pointer(sub),
-                               device, wide ? 3 : 0, (stored_states ? 1 : 0, 0)))      # 3 = QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS
+                               device, (wide ? 3 : 0) | (wide_stored ? 8 : 0), (stored_states ? 1 : 0, 0)))      # 3 = QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS, 8 = QC_SWEEP_WIDE_STORED
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_grad_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
         (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
@@ -957,7 +959,7 @@ state columns, with `stored_states = true` for any generators with 2N ≤ 16; no
 """
 function rollout_sweep_pullback(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift, G_drives,
                                 G_pert, θ::AbstractMatrix{Float64}, C̄::AbstractMatrix{Float64}; scale=nothing, cols::Int, params::Bool=false,
-                                device::Int=0, wide::Bool=false, stored_states::Bool=false, wide_params::Bool=false)
+                                device::Int=0, wide::Bool=false, stored_states::Bool=false, wide_stored::Bool=false, wide_params::Bool=false)
     (wide_params && !wide) && error("rollout_sweep_pullback: wide_params = true needs wide = true")
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(θ, 1)
@@ -978,7 +980,7 @@ function rollout_sweep_pullback(init::AbstractVector{Float64}, controls::Abstrac
     GC.@preserve G0 Gd Gp begin
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, -1,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
-                               0, 0, C_NULL, C_NULL, device, (wide ? 1 : 0) | (wide_params ? 2 : 0), (stored_states ? 1 : 0, 0)))
+                               0, 0, C_NULL, C_NULL, device, (wide ? 1 : 0) | (wide_params ? 2 : 0) | (wide_stored ? 8 : 0), (stored_states ? 1 : 0, 0)))
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_vjp_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
         (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))

@@ -38,28 +38,6 @@ struct Sweep32Params {
     const double* img;           // A-layout images, 1024 doubles a matrix: drift, m drives, p perturbations
 };
 
-// column J of  X <- A X + c I  in place (A in A layout, X in B / D layout): two independent chains of 8 MFMAs
-__device__ __forceinline__ void wcol(const v4d (&A)[2][2], v4d (&X)[2][2], int J, const v4d& c0, const v4d& c1) {
-    v4d n0 = c0, n1 = c1;
-#pragma unroll
-    for (int K = 0; K < 2; ++K) {
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            n0 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[0][K][kk], X[K][J][kk], n0, 0, 0, 0);
-            n1 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[1][K][kk], X[K][J][kk], n1, 0, 0, 0);
-        }
-    }
-    X[0][J] = n0;
-    X[1][J] = n1;
-}
-
-// X <- A X + c I, c I given as its diagonal tile
-__device__ __forceinline__ void wmul(const v4d (&A)[2][2], v4d (&X)[2][2], const v4d& cI) {
-    const v4d zero = {0.0, 0.0, 0.0, 0.0};
-    wcol(A, X, 0, cI, zero);
-    wcol(A, X, 1, zero, cI);
-}
-
 __global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_mfma32_kernel(const Sweep32Params P, const double* __restrict__ Z,
                                                                            const double* __restrict__ theta, const double* __restrict__ scale,
                                                                            double* __restrict__ tot) {

@@ -1,6 +1,7 @@
-// What the forward kernel (qc_sweep32.hip) and the backward walk (qc_sweep32_grad.hip) of the "mfma32-sweep" form share, in one place so
-// that it cannot drift: the walk reverses the forward step only if both form the same generator and choose the same number of
-// squarings.  Constants, the sample's base matrix, the interval's generator, the squaring rule, the four-tile transpose.
+// What the forward kernel (qc_sweep32.hip) and the backward walks (qc_sweep32_grad.hip, qc_sweep32_open_grad.hip) of the "mfma32-sweep" form
+// share, in one place so that it cannot drift: the closed walk reverses the forward step, and the stored states match the stored-state
+// walk, only if all form the same generator and choose the same number of squarings.  Constants, the sample's base matrix, the
+// interval's generator, the squaring rule, the four-tile transpose, the in-place product X <- A X + c I.
 #pragma once
 #include <math.h>
 
@@ -101,6 +102,28 @@ __device__ __forceinline__ void transpose4(double* __restrict__ scr, const v4d (
     v4d out[4];
     lds_transpose16_multi<4>(scr, in, out, g, j);
     Xt[0][0] = out[0]; Xt[0][1] = out[1]; Xt[1][0] = out[2]; Xt[1][1] = out[3];
+}
+
+// column J of  X <- A X + c I  in place (A in A layout, X in B / D layout): two independent chains of 8 MFMAs
+__device__ __forceinline__ void wcol(const v4d (&A)[2][2], v4d (&X)[2][2], int J, const v4d& c0, const v4d& c1) {
+    v4d n0 = c0, n1 = c1;
+#pragma unroll
+    for (int K = 0; K < 2; ++K) {
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            n0 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[0][K][kk], X[K][J][kk], n0, 0, 0, 0);
+            n1 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[1][K][kk], X[K][J][kk], n1, 0, 0, 0);
+        }
+    }
+    X[0][J] = n0;
+    X[1][J] = n1;
+}
+
+// X <- A X + c I, c I given as its diagonal tile
+__device__ __forceinline__ void wmul(const v4d (&A)[2][2], v4d (&X)[2][2], const v4d& cI) {
+    const v4d zero = {0.0, 0.0, 0.0, 0.0};
+    wcol(A, X, 0, cI, zero);
+    wcol(A, X, 1, zero, cI);
 }
 
 }  // namespace qc_sweep32

@@ -3,7 +3,8 @@
 // orthogonal, so x_t = E^T x_{t+1} (no state stored inside a chunk), L(hG; E^T K) = E^T L(hG; K) with K = x_{t+1} lambda_{t+1}^T (the
 // Frechet chain runs beside the Horner chain), one chain per interval serves all m drives, dF/da_k = c_k sum ZT . G_k,
 // dF/dh = -sum KT . G.  Degree 8, threshold 1/8, the 1/k! table, the generator and the squaring rule are the forward kernel's: both files
-// take them from qc_sweep32_common.h.
+// take them from qc_sweep32_common.h; the paired column step, the product with E^T and the wave sum are those of qc_sweep32_walk.h, shared
+// with the stored-state walk of qc_sweep32_open_grad.hip.
 //
 // Launches of one call on such a handle (qc_sweep_grad_launch of qc_sweep_grad.hip routes here):
 //   1. qc_sweep_mfma32_kernel: the forward chunk totals, column-major 32 x 32;
@@ -46,6 +47,7 @@
 
 #include "qc_mfma_common.h"
 #include "qc_sweep32_common.h"
+#include "qc_sweep32_walk.h"
 #include "qc_sweep_internal.h"
 
 namespace {
@@ -58,60 +60,6 @@ struct Grad32Params {
     double dt_fixed;
     const double* img;           // A-layout images, 1024 doubles a matrix: drift, m drives, p perturbations
 };
-
-// the sum over the 64 lanes in a fixed order, wave-uniform (as qc_sweep_grad.hip)
-__device__ inline double vwave_sum(double v) {
-    v += dpp<0x128>(v);
-    v += dpp<0x124>(v);
-    v += dpp<0x122>(v);
-    v += dpp<0x121>(v);
-    return (bcast_lane(v, 0) + bcast_lane(v, 16)) + (bcast_lane(v, 32) + bcast_lane(v, 48));
-}
-
-// column J of (R, dR) <- (A R + C, dA R + A dR) in place; C given by its tiles of that column.  Six accumulator chains, interleaved.
-__device__ __forceinline__ void vcol(const v4d (&A)[2][2], const v4d (&dA)[2][2], v4d (&R)[2][2], v4d (&dR)[2][2], int J, const v4d& c0,
-                                     const v4d& c1) {
-    const v4d z = {0.0, 0.0, 0.0, 0.0};
-    v4d p0 = z, p1 = z, q0 = z, q1 = z, r0 = c0, r1 = c1;
-#pragma unroll
-    for (int K = 0; K < 2; ++K) {
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            p0 = __builtin_amdgcn_mfma_f64_16x16x4f64(dA[0][K][kk], R[K][J][kk], p0, 0, 0, 0);
-            p1 = __builtin_amdgcn_mfma_f64_16x16x4f64(dA[1][K][kk], R[K][J][kk], p1, 0, 0, 0);
-            q0 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[0][K][kk], dR[K][J][kk], q0, 0, 0, 0);
-            q1 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[1][K][kk], dR[K][J][kk], q1, 0, 0, 0);
-            r0 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[0][K][kk], R[K][J][kk], r0, 0, 0, 0);
-            r1 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[1][K][kk], R[K][J][kk], r1, 0, 0, 0);
-        }
-    }
-    dR[0][J] = p0 + q0;
-    dR[1][J] = p1 + q1;
-    R[0][J] = r0;
-    R[1][J] = r1;
-}
-
-__device__ __forceinline__ void vstep(const v4d (&A)[2][2], const v4d (&dA)[2][2], v4d (&R)[2][2], v4d (&dR)[2][2], const v4d& cI) {
-    const v4d z = {0.0, 0.0, 0.0, 0.0};
-    vcol(A, dA, R, dR, 0, cI, z);
-    vcol(A, dA, R, dR, 1, z, cI);
-}
-
-// y_I = sum_K M[K][I]^T v_K: M^T v for a D-layout M and a two-tile column block v
-__device__ __forceinline__ void vapplyT(const v4d (&M)[2][2], v4d (&v)[2]) {
-    const v4d z = {0.0, 0.0, 0.0, 0.0};
-    v4d y0 = z, y1 = z;
-#pragma unroll
-    for (int K = 0; K < 2; ++K) {
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            y0 = __builtin_amdgcn_mfma_f64_16x16x4f64(M[K][0][kk], v[K][kk], y0, 0, 0, 0);
-            y1 = __builtin_amdgcn_mfma_f64_16x16x4f64(M[K][1][kk], v[K][kk], y1, 0, 0, 0);
-        }
-    }
-    v[0] = y0;
-    v[1] = y1;
-}
 
 // One wavefront per (sample, chunk), walking the chunk backwards.  PAR = false: the per-interval derivatives
 // only (`part` unused).  PAR = true, the parameter flavour (qc_sweep_grad_kernel<M, true> on 2 x 2 tiles), also keeps Acc = sum_t ZT_t

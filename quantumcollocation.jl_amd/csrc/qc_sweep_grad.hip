@@ -14,8 +14,8 @@
 //     problem (M_t needs x_t, which needs E) is gone: neither are the Horner / squaring intermediates kept, nor is the R chain computed twice;
 //   * <lambda, G x> = -sum (lambda x^T)_ab G_ba, so the timestep derivative is an inner product of tiles already in registers.
 // Everything else returns QC_ERR_UNSUPPORTED (Lindblad generators need stored forward states) -- unless the descriptor opts in with
-// reserved1[0] = QC_SWEEP_STORED_STATES: such handles are routed to the stored-state walk of qc_sweep_open_grad.hip, whatever their
-// generators, behind the same totals, seed (with lambda = g_r for the density fidelity) and reductions; qc_sweep_reverse_scope decides.
+// reserved1[0] = QC_SWEEP_STORED_STATES: such handles are routed to the stored-state walk of qc_sweep_open_grad.hip (wide handles that also
+// set QC_SWEEP_WIDE_STORED: of qc_sweep32_open_grad.hip), whatever their generators, behind the same totals, seed (with lambda = g_r for the density fidelity) and reductions; qc_sweep_reverse_scope decides.
 // Wide descriptors (wide = QC_SWEEP_WIDE) extend the scope to the "mfma32-sweep" form, 2N <= 32: this file routes such handles to the
 // seed and walk kernels of qc_sweep32_grad.hip and shares its reductions (launch 4) with them; parameter gradients there only for
 // descriptors that also set QC_SWEEP_WIDE_PARAMS (the flavour <true> of that file's walk, then qc_sweep_par_reduce_kernel of this one).
@@ -428,12 +428,13 @@ bool qc_sweep_closed_scope(const qc_sweep_desc* d, std::string* why) {
 }
 
 // Reverse mode of a descriptor: reserved1[0] chooses the walk.  0: the closed walk and its scope above.  QC_SWEEP_STORED_STATES: the
-// stored-state walk of qc_sweep_open_grad.hip, which asks nothing of the generators: the "mfma16-sweep" form, at most 16 state columns.
+// stored-state walk of qc_sweep_open_grad.hip, which asks nothing of the generators: the "mfma16-sweep" form, at most 16 state columns;
+// the "mfma32-sweep" form only for descriptors that opt in with QC_SWEEP_WIDE_STORED (the 2 x 2-tile walk of qc_sweep32_open_grad.hip).
 bool qc_sweep_reverse_scope(const qc_sweep_desc* d, std::string* why) {
     if (d->reserved1[0] != QC_SWEEP_STORED_STATES) return qc_sweep_closed_scope(d, why);
     const int form = qc_sweep_desc_form(d);
     if (form == 0) { *why = qc_sweep_per_sample_why(d); return false; }
-    if (form == 2) { *why = "stored-state gradients are not served in the mfma32-sweep form"; return false; }
+    if (form == 2 && !(d->wide & QC_SWEEP_WIDE_STORED)) { *why = "stored-state gradients are not served in the mfma32-sweep form"; return false; }
     const int nc = d->state_cols == 0 ? d->N : d->state_cols;
     if (nc > 16) { *why = "states of more than 16 columns are not served (state_cols = " + std::to_string(nc) + ")"; return false; }
     return true;
@@ -576,9 +577,9 @@ static int qc_sweep_grad_launch(qc_sweep* h, const char* who, const double* dZ, 
     if (h->stored && (want_grad || want_par)) QC_SIDE_HIP(h, slot, h->grow(h->dXall, (size_t)S * (size_t)n_int * h->ns));
     qc_sweep_launch_fid_seed(h, S, n_chunks, dinit, dfids, st);
     if (h->stored) {      // reserved1[0] = QC_SWEEP_STORED_STATES: the walk of qc_sweep_open_grad.hip, whatever the generators
-        if (want_grad || want_par)
-            qc_sweep_open_launch_walk(h, dZ, dinit, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta,
-                                      dgrad_scale, st);
+        if (want_grad || want_par)      // (an "mfma32-sweep" handle is in scope only with QC_SWEEP_WIDE_STORED: the 2 x 2-tile walk)
+            (h->mfma32 ? qc_sweep32_open_launch_walk : qc_sweep_open_launch_walk)(h, dZ, dinit, S, dtheta, dscale, chunk, n_chunks,
+                                                                                 want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);
     } else if (h->mfma32) {      // the 2 x 2-tile form: its own walk (qc_sweep32_grad.hip), then the reductions below
         if (want_grad || want_par)      // want_par: only on handles with QC_SWEEP_WIDE_PARAMS (the entry points refuse the others)
             qc_sweep32_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);

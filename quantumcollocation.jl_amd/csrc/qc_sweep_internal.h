@@ -1,4 +1,4 @@
-// What qc_sweep.hip (forward sweep), qc_sweep_grad.hip (its adjoint), qc_sweep_open_grad.hip (the adjoint on stored states), qc_sweep_vjp.hip (the pullback of the final states),
+// What qc_sweep.hip (forward sweep), qc_sweep_grad.hip (its adjoint), qc_sweep_open_grad.hip and qc_sweep32_open_grad.hip (the adjoint on stored states), qc_sweep_vjp.hip (the pullback of the final states),
 // qc_sweep_jvp.hip (their pushforward), qc_sweep_hvp.hip (the tangent of the pullback) and qc_sweep_noise.hip (noise trajectories) share: the handle with its scratch and staging buffers, the descriptor and argument checks and
 // the launch of the forward chunk totals (with it the chunk rule).  Not part of the ABI.
 #pragma once
@@ -12,6 +12,7 @@ struct qc_sweep : qc_side {
     bool mfma = false;
     bool mfma32 = false;         // the 2 x 2-tile form of a wide descriptor ("mfma32-sweep", qc_sweep32.hip); mfma is set as well
     bool wide_par = false;       // mfma32 and wide has QC_SWEEP_WIDE_PARAMS: parameter gradients and cotangents are served (qc_sweep32_grad.hip)
+    bool wide_stored = false;    // mfma32 and wide has QC_SWEEP_WIDE_STORED: with `stored`, reverse mode by the 2 x 2-tile stored-state walk (qc_sweep32_open_grad.hip)
     bool stored = false;         // reserved1[0] = QC_SWEEP_STORED_STATES: reverse mode by the stored-state walk (qc_sweep_open_grad.hip)
     bool grad_ok = false;        // the gradient's scope (qc_sweep_grad.hip), decided at create from the caller's matrices
     std::string grad_why;        // when not: the reason
@@ -115,8 +116,12 @@ void qc_sweep_launch_par_reduce(qc_sweep* h, int64_t S, int64_t n_chunks, double
 // arguments and outputs as qc_sweep16_launch_walk
 void qc_sweep_open_launch_walk(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
                                int64_t chunk, int64_t n_chunks, double* gs, bool par, double* dgrad_theta, double* dgrad_scale, hipStream_t st);
-// what reverse mode asks of a descriptor: reserved1[0] = 0, the closed scope; QC_SWEEP_STORED_STATES, the "mfma16-sweep" form and at most
-// 16 state columns, any generators.  qc_sweep_closed_grad_scope: the gradient's scope of reserved1[0] = 0, for the noise gradient.
+// "mfma32-sweep" handles with `stored` and `wide_stored` (qc_sweep32_open_grad.hip): the same two steps on 2 x 2 tiles,
+// qc_sweep32_open_store_kernel and qc_sweep32_open_grad_kernel<par>; arguments and outputs as qc_sweep_open_launch_walk
+void qc_sweep32_open_launch_walk(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
+                                 int64_t chunk, int64_t n_chunks, double* gs, bool par, double* dgrad_theta, double* dgrad_scale, hipStream_t st);
+// what reverse mode asks of a descriptor: reserved1[0] = 0, the closed scope; QC_SWEEP_STORED_STATES, the "mfma16-sweep" form (or the
+// "mfma32-sweep" form of a descriptor whose wide has QC_SWEEP_WIDE_STORED) and at most 16 state columns, any generators.  qc_sweep_closed_grad_scope: the gradient's scope of reserved1[0] = 0, for the noise gradient.
 bool qc_sweep_reverse_scope(const qc_sweep_desc* d, std::string* why);
 bool qc_sweep_closed_grad_scope(const qc_sweep_desc* d, std::string* why);
 // device-free: is this (valid) descriptor inside the gradient's scope?  `why` receives the reason when it is not.

@@ -22,7 +22,8 @@
 // No atomics, sums in a fixed order: repeated calls return the same bits, and no output's bits depend on which others were asked for.
 //
 // Scope: the gradient's without its two fidelity conditions (qc_sweep_vjp_scope below is qc_sweep_reverse_scope: the closed scope, or with
-// reserved1[0] = QC_SWEEP_STORED_STATES the stored-state walk's, and then launch 3 is qc_sweep_open_launch_walk of qc_sweep_open_grad.hip).
+// reserved1[0] = QC_SWEEP_STORED_STATES the stored-state walk's, and then launch 3 is qc_sweep_open_launch_walk of qc_sweep_open_grad.hip or,
+// on an "mfma32-sweep" handle made with QC_SWEEP_WIDE_STORED, qc_sweep32_open_launch_walk of qc_sweep32_open_grad.hip).
 #include <math.h>
 
 #include <string>
@@ -174,9 +175,9 @@ static int qc_sweep_vjp_launch(qc_sweep* h, const char* who, const double* dZ, c
     hipLaunchKernelGGL(seed, dim3((unsigned)S), dim3(kCotT), lds, st, F, (const double*)h->dTot.p, dinit, dcot, h->dXs.p, h->dLs.p, dfinals,
                        dgrad_init);
     if (h->stored) {      // reserved1[0] = QC_SWEEP_STORED_STATES: the walk of qc_sweep_open_grad.hip behind the same seed
-        if (want_grad || want_par)
-            qc_sweep_open_launch_walk(h, dZ, dinit, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta,
-                                      dgrad_scale, st);
+        if (want_grad || want_par)      // (an "mfma32-sweep" handle is in scope only with QC_SWEEP_WIDE_STORED: qc_sweep32_open_grad.hip)
+            (h->mfma32 ? qc_sweep32_open_launch_walk : qc_sweep_open_launch_walk)(h, dZ, dinit, S, dtheta, dscale, chunk, n_chunks,
+                                                                                 want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);
     } else if (h->mfma32) {
         if (want_grad || want_par)
             qc_sweep32_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);

@@ -747,12 +747,13 @@ class SweepInfidelityObjective:
     theta       S x len(perturbations);  scale  S x n_drives or None;  weights  S values or None (1/S each)
     wide        as `RolloutSweep`: True serves systems of 16 < 2N <= 32 (9 .. 16 levels) in the "mfma32-sweep" form
     stored_states  as `RolloutSweep`: True takes the gradient by the stored-state walk, which serves open systems
+    wide_stored as `RolloutSweep` (only with `wide` and `stored_states`): that walk in the "mfma32-sweep" form, e.g. two qubits with T1 / T2
     goal_ket    density component only: [Re psi; Im psi] (2 levels entries) of the pure state the fidelity compares with"""
     _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
 
     def __init__(self, traj: NamedTrajectory, system, perturbations, theta, scale=None, weights=None, state_name: str = "Ũ⃗",
                  control_name: str = "a", subspace=None, form: str = "abs", device: int = 0, wide: bool = False,
-                 stored_states: bool = False, goal_ket=None):
+                 stored_states: bool = False, goal_ket=None, wide_stored: bool = False):
         from .rollouts import RolloutSweep
         self._sweep = None
         if state_name not in traj.components:
@@ -804,9 +805,10 @@ class SweepInfidelityObjective:
                           subspace=subspace, fid_form=_lib.QC_FID_FORM_ABS2 if form == "abs2" else _lib.QC_FID_FORM_ABS, zdim=traj.dim,
                           off_a=traj.offset(control_name), off_dt=traj.offset(traj.timestep) if free else -1,
                           dt_fixed=None if free else float(traj.timestep), global_dim=traj.global_dim, device=device, wide=wide,
-                          stored_states=stored_states)
+                          stored_states=stored_states, wide_stored=wide_stored)
         self._sweep = sw
         self.stored_states = sw.stored_states
+        self.wide_stored = sw.wide_stored
         if not sw.grad_supported:
             why = sw.grad_unsupported_reason
             sw.close()
@@ -916,11 +918,13 @@ class SweepFinalStateObjective:
     theta       S x len(perturbations);  scale  S x n_drives or None
     wide        as `RolloutSweep`
     stored_states  as `RolloutSweep`: True takes the pullback by the stored-state walk, which serves open systems (gradients and
-                `gauss_newton_times`; `hessian_times` keeps the scope of `RolloutSweep.hvp`)"""
+                `gauss_newton_times`; `hessian_times` keeps the scope of `RolloutSweep.hvp`)
+    wide_stored as `RolloutSweep` (only with `wide` and `stored_states`): that walk in the "mfma32-sweep" form (gradients only: the
+                pushforward behind `gauss_newton_times` is not served there)"""
     _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
 
     def __init__(self, traj: NamedTrajectory, system, perturbations, theta, loss, scale=None, state_name="Ũ⃗", control_name: str = "a",
-                 device: int = 0, wide: bool = False, stored_states: bool = False):
+                 device: int = 0, wide: bool = False, stored_states: bool = False, wide_stored: bool = False):
         from .rollouts import RolloutSweep, _sweep_samples
         self._sweep = None
         if not callable(loss):
@@ -946,9 +950,10 @@ class SweepFinalStateObjective:
         self.Z_len = traj.T * traj.dim + traj.global_dim
         sw = RolloutSweep(system, perturbations, traj.T, cols=cols, zdim=traj.dim, off_a=traj.offset(control_name),
                           off_dt=traj.offset(traj.timestep) if free else -1, dt_fixed=None if free else float(traj.timestep),
-                          global_dim=traj.global_dim, device=device, wide=wide, stored_states=stored_states)
+                          global_dim=traj.global_dim, device=device, wide=wide, stored_states=stored_states, wide_stored=wide_stored)
         self._sweep = sw
         self.stored_states = sw.stored_states
+        self.wide_stored = sw.wide_stored
         if not sw.vjp_supported:
             why = sw.vjp_unsupported_reason
             sw.close()

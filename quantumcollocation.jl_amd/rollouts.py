@@ -183,15 +183,22 @@ class RolloutSweep:
     stored_states  True: `grad`, `grad_params` and `vjp` keep the forward states of every sample on the device (S x (T-1) x 2N x cols
                    doubles) and read them on the way back instead of reversing the step.  That serves ANY generators in the
                    "mfma16-sweep" form: an `OpenQuantumSystem` with the "density" fidelity, a non-Hermitian effective Hamiltonian.
-                   Closed systems give the same derivatives either way (to rounding); `hvp` and `noise_grad` keep their scope."""
+                   Closed systems give the same derivatives either way (to rounding); `hvp` and `noise_grad` keep their scope.
+    wide_stored    True (only with `wide` and `stored_states`): an "mfma32-sweep" handle serves the stored-state walk too -- two qubits
+                   with T1 / T2 (levels^2 = 16), a three-level transmon with relaxation, 9 .. 16 levels with a non-Hermitian
+                   Hamiltonian.  The device buffer is S x (T-1) x 2N x cols doubles: 32 a knot for a two-qubit density operator
+                   (250 MiB at S = 1024, T = 1000), 512 a knot for a 16-level unitary (4 GiB).  Parameter outputs there also need
+                   `wide_params`.  Without it such handles refuse reverse mode, as they always did; nothing else changes."""
 
     def __init__(self, system, perturbations, T: int, cols: Optional[int] = None, goal=None, fid_kind=None, subspace=None,
                  fid_form: int = _lib.QC_FID_FORM_ABS, zdim: Optional[int] = None, off_a: int = 0, off_dt: Optional[int] = None,
                  dt_fixed: Optional[float] = None, global_dim: int = 0, device: int = 0, wide: bool = False,
-                 stored_states: bool = False, wide_params: bool = False):
+                 stored_states: bool = False, wide_params: bool = False, wide_stored: bool = False):
         self._h = None
         if wide_params and not wide:
             raise ValueError("wide_params=True needs wide=True")
+        if wide_stored and not (wide and stored_states):
+            raise ValueError("wide_stored=True needs wide=True and stored_states=True")
         m = system.n_drives
         N = system.state_levels
         n = 2 * N
@@ -225,9 +232,11 @@ class RolloutSweep:
         d.subspace = self._sub.ctypes.data_as(C.POINTER(C.c_int32)) if self._sub is not None else None
         d.n_sub = 0 if self._sub is None else int(self._sub.size)
         d.device = device
-        d.wide = (_lib.QC_SWEEP_WIDE if wide else 0) | (_lib.QC_SWEEP_WIDE_PARAMS if wide_params else 0)
+        d.wide = ((_lib.QC_SWEEP_WIDE if wide else 0) | (_lib.QC_SWEEP_WIDE_PARAMS if wide_params else 0)
+                  | (_lib.QC_SWEEP_WIDE_STORED if wide_stored else 0))
         self.wide = bool(wide)
         self.wide_params = bool(wide_params)
+        self.wide_stored = bool(wide_stored)
         d.reserved1[0] = _lib.QC_SWEEP_STORED_STATES if stored_states else 0
         self.stored_states = bool(stored_states)
         self._desc = d
@@ -316,7 +325,8 @@ class RolloutSweep:
     @property
     def grad_supported(self) -> bool:
         """Does `grad` serve this handle?  (`qc_sweep_desc_grad_supported`: the MFMA form, a unitary or ket fidelity, at most 16
-        state columns, antisymmetric generators; with `stored_states` the "mfma16-sweep" form, any fidelity, any generators.)
+        state columns, antisymmetric generators; with `stored_states` the "mfma16-sweep" form -- with `wide_stored` the "mfma32-sweep"
+        form as well --, any fidelity, any generators.)
         `grad_unsupported_reason` says why not."""
         return self._grad_scope()[0]
 
@@ -432,7 +442,8 @@ class RolloutSweep:
     @property
     def vjp_supported(self) -> bool:
         """Does `vjp` serve this handle?  (`qc_sweep_desc_vjp_supported`: the MFMA forms, at most 16 state columns, antisymmetric
-        generators; with `stored_states` the "mfma16-sweep" form and any generators; any fidelity or none.)
+        generators; with `stored_states` the "mfma16-sweep" form (with `wide_stored`: or "mfma32-sweep") and any generators; any
+        fidelity or none.)
         `vjp_unsupported_reason` says why not."""
         return self._vjp_scope()[0]
 
@@ -886,10 +897,11 @@ class _SweepFinals(torch.autograd.Function):
 
 
 def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None, cols: Optional[int] = None, goal=None, fid_kind=None,
-                  subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS, wide: bool = False, stored_states: bool = False):
+                  subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS, wide: bool = False, stored_states: bool = False,
+                  wide_stored: bool = False):
     """(finals, fids) of S rollouts under the perturbed systems: finals is (2N cols) x S, fids S values (None without `fid_kind`).
-    theta is S x len(perturbations) (S x 0 without perturbations), scale S x n_drives or None (all ones); `wide` and `stored_states` as
-    `RolloutSweep` (the forward sweep itself does not look at `stored_states`)."""
+    theta is S x len(perturbations) (S x 0 without perturbations), scale S x n_drives or None (all ones); `wide`, `stored_states` and
+    `wide_stored` as `RolloutSweep` (the forward sweep itself looks at neither of the last two)."""
     controls = np.asarray(controls, dtype=np.float64)
     if controls.ndim != 2 or controls.shape[0] != system.n_drives:
         raise ValueError("controls must be n_drives x T")
@@ -899,7 +911,7 @@ def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None,
     if cols is None:
         cols = init.size // n
     sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device, wide=wide,
-                      stored_states=stored_states)
+                      stored_states=stored_states, wide_stored=wide_stored)
     try:
         return sw.eval(sw.pack(controls, dts), init, theta, scale)
     finally:
@@ -928,11 +940,11 @@ def rollout_noise_sweep(init, controls, dts, system, perturbations, noise, theta
 
 def rollout_sweep_parameter_gradient(init, controls, dts, system, perturbations, theta, scale=None, cols: Optional[int] = None, goal=None,
                                      fid_kind="unitary", subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS,
-                                     stored_states: bool = False, wide: bool = False):
+                                     stored_states: bool = False, wide: bool = False, wide_stored: bool = False):
     """(fids, grad_theta, grad_scale) of S rollouts under the perturbed systems: the fidelities of `rollout_sweep` and their derivatives
     with respect to theta (S x len(perturbations)) and scale (S x n_drives; None: taken at all ones).  Arguments as `rollout_sweep`;
     `stored_states=True` serves open systems (`RolloutSweep`); `wide=True` serves 16 < 2N <= 32 on the matrix cores (the handle is made
-    with `wide` and `wide_params`)."""
+    with `wide` and `wide_params`); all three of `wide`, `stored_states` and `wide_stored` serve open systems there (wide = 11)."""
     controls = np.asarray(controls, dtype=np.float64)
     if controls.ndim != 2 or controls.shape[0] != system.n_drives:
         raise ValueError("controls must be n_drives x T")
@@ -942,7 +954,7 @@ def rollout_sweep_parameter_gradient(init, controls, dts, system, perturbations,
     if cols is None:
         cols = init.size // n
     sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device,
-                      stored_states=stored_states, wide=wide, wide_params=wide)
+                      stored_states=stored_states, wide=wide, wide_params=wide, wide_stored=wide_stored)
     try:
         return sw.param_grad(sw.pack(controls, dts), init, theta, scale)
     finally:
