@@ -630,8 +630,11 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * an "mfma32-sweep" handle then serves the parameter gradients (qc_sweep_grad_params*) and the parameter cotangents of the pullback
  * (qc_sweep_vjp*: grad_theta, grad_scale).  Bit 3, QC_SWEEP_WIDE_STORED (wide = 9, or 11 with the parameter bit), likewise changes one
  * thing only: an "mfma32-sweep" handle whose descriptor also sets reserved1[0] = QC_SWEEP_STORED_STATES then serves reverse mode by the
- * stored-state walk on 2 x 2 tiles (below); without reserved1[0], or where the handle takes another form, the bit does nothing.  The
- * valid values are 0, 1, 3, 9 and 11; any other value (bit 1 or 3 without bit 0, bit 2, 5 and 7 among them) is QC_ERR_INVALID.
+ * stored-state walk on 2 x 2 tiles (below); without reserved1[0], or where the handle takes another form, the bit does nothing.  Bit 4,
+ * QC_SWEEP_WIDE_TANGENT (wide = 17, 19, 25 or 27), likewise changes one thing only: an "mfma32-sweep" handle then serves the pushforward
+ * (qc_sweep_jvp*, below) with any generators; the forward sweep, gradients, pullbacks, the launch and the kernel name are untouched, and
+ * where the handle takes another form the bit does nothing.  The valid values are 0, 1, 3, 9, 11, 17, 19, 25 and 27; any other value
+ * (bit 1, 3 or 4 without bit 0, bit 2, 5 and 7 among them) is QC_ERR_INVALID.
  * reserved1[0] = QC_SWEEP_STORED_STATES chooses reverse mode by the STORED-STATE walk: qc_sweep_grad*, qc_sweep_grad_params* and
  * qc_sweep_vjp* then keep the forward states x_0 .. x_{T-2} of every sample in handle scratch (S x (T-1) x 2N x cols doubles) and read
  * them on the way back instead of reversing the step, which serves ANY generators in the "mfma16-sweep" form: Lindblad generators
@@ -649,18 +652,21 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * Derivatives of the final states themselves, contracted with cotangents the caller chooses (qc_sweep_vjp*, below), carry any function
  * of the final states: leakage, the free-phase fidelity, several kets at once, a loss written elsewhere.
  * The forward-mode counterpart, the tangent of the final states and fidelities along one direction (qc_sweep_jvp*, below), is served
- * for "mfma16-sweep" handles with any generators, Lindblad ones included; with the pullback it gives Gauss-Newton products of any loss.
+ * for "mfma16-sweep" handles, and for "mfma32-sweep" handles whose `wide` has QC_SWEEP_WIDE_TANGENT, with any generators, Lindblad ones
+ * included (no flag, no state buffer: nothing is reversed); with the pullback it gives Gauss-Newton products of any loss.
  * The tangent of the pullback along one direction (qc_sweep_hvp*, below) gives exact Hessian products of any loss of the final states
  * where both of them are served (closed systems, "mfma16-sweep").
  * Out of scope: per-knot outputs, open-system gradients in the "mfma32-sweep" form without QC_SWEEP_WIDE_STORED (their directional
  * derivatives are not served there at all), checkpointing inside a chunk, Hessian products and noise gradients of open
- * systems, pushforwards on "mfma32-sweep" and "rollout-per-sample" handles (Hessian products likewise), several directions per
+ * systems, pushforwards on "mfma32-sweep" and "rollout-per-sample" handles (the former unless `wide` has QC_SWEEP_WIDE_TANGENT; Hessian
+ * products on both, with or without that bit), several directions per
  * call, tangents of grad_theta / grad_scale, several devices. */
 #define QC_MAX_PERT 8
 #define QC_SWEEP_FID_NONE (-1)   /* qc_sweep_desc.fid_kind: final states only */
 #define QC_SWEEP_WIDE 1          /* qc_sweep_desc.wide, bit 0 */
 #define QC_SWEEP_WIDE_PARAMS 2   /* qc_sweep_desc.wide, bit 1: the mfma32-sweep form serves parameter gradients and parameter cotangents; only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_WIDE_STORED 8   /* qc_sweep_desc.wide, bit 3: the mfma32-sweep form serves the stored-state walk; only together with QC_SWEEP_WIDE */
+#define QC_SWEEP_WIDE_TANGENT 16 /* qc_sweep_desc.wide, bit 4: the mfma32-sweep form serves pushforwards (qc_sweep_jvp*); only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_STORED_STATES 1 /* qc_sweep_desc.reserved1[0]: reverse mode by the stored-state walk */
 typedef struct qc_sweep_desc {
     int64_t T;
@@ -798,10 +804,12 @@ int qc_sweep_vjp(qc_sweep* h, const double* Z, const double* init, int64_t S, co
  *     xdot_0 = vinit,   xdot_{t+1} = E_t xdot_t + L(h_t G; d(hG)_t) x_t   (L: the Frechet derivative of exp),   t = 0 .. T-2
  *     tfinals[s] = xdot_{T-1},   tfids[s] = <dF/dx(x_final[s]), xdot_{T-1}>   (the |tr| / n form is not special-cased at tr = 0).
  * One forward walk that differentiates every product beside itself: 108 + 12 sq matrix-core instructions per interval against the
- * sweep's 36 + 4 sq.  Nothing is reversed, so antisymmetry is not asked for: Lindblad generators (QC_FID_DENSITY handles) are served.
+ * sweep's 36 + 4 sq ("mfma32-sweep": 864 + 96 sq against 288 + 32 sq).  Nothing is reversed, so antisymmetry is not asked for: Lindblad
+ * generators (QC_FID_DENSITY handles) are served.
  * With one pullback call it gives the Gauss-Newton product J^T (d2 loss) J v of any loss of the final states. */
-/* device-free: may the pushforward serve this descriptor?  Scope: the "mfma16-sweep" form (2N <= 16, m <= 8), any generators, any
- * state_cols and fid_kind the sweep serves there.  When 0, qc_sweep_last_error(NULL) says why, prefixed "qc_sweep pushforward: "
+/* device-free: may the pushforward serve this descriptor?  Scope: the "mfma16-sweep" form (2N <= 16, m <= 8), or the "mfma32-sweep" form
+ * (16 < 2N <= 32, m <= 8) of a descriptor whose `wide` has QC_SWEEP_WIDE_TANGENT; any generators, any state_cols and fid_kind the sweep
+ * serves there.  When 0, qc_sweep_last_error(NULL) says why, prefixed "qc_sweep pushforward: "
  * ("... not served in the mfma32-sweep form", or the rollout-per-sample form with its cause).  An invalid descriptor returns its own error. */
 int qc_sweep_desc_jvp_supported(const qc_sweep_desc* d, int32_t* supported);
 /* Directions, each optional (NULL = zero: the same bits as an explicit zero array), at least one non-NULL:

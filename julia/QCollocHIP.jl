@@ -14,6 +14,8 @@ using Libdl
 
 const LIB = Ref{String}(get(ENV, "QCOLLOC_HIP_LIB", "libqcolloc_hip.so"))
 const QC_MAX_DERIV = 8
+const QC_SWEEP_WIDE = 1            # qc_sweep_desc.wide, bit 0: the matrix-core form up to 2N = 32 ("mfma32-sweep")
+const QC_SWEEP_WIDE_TANGENT = 16   # qc_sweep_desc.wide, bit 4 (only with bit 0): pushforwards in that form
 const QC_ABI_VERSION = 6      # QC_VERSION_MAJOR * 1000 + QC_VERSION_MINOR of the include/qcolloc.h these mirrors were written against
 
 # mirror of `qc_desc` (include/qcolloc.h); field order and types must match the header -- `__init__` checks the sizes against
@@ -1002,17 +1004,19 @@ end
 
 """
     rollout_sweep_pushforward(init, controls, Δt, G_drift, G_drives, G_pert, θ; scale=nothing, cols, vZ=nothing, vinit=nothing,
-                              vtheta=nothing, vscale=nothing, device=0)  ->  (finals, tfinals)
+                              vtheta=nothing, vscale=nothing, device=0, wide=false)  ->  (finals, tfinals)
 
 The pushforward of `rollout_sweep` (`qc_sweep_jvp`): the final states, (2N·cols)×S, and their tangents along one direction, the same
 shape.  `vZ` is an (m+1)×T matrix in the knot layout [a; Δt] (only the columns of knots 1 … T−1 act), `vinit` a 2N·cols vector, `vtheta`
 S×p and `vscale` S×m (valid with `scale = nothing`: taken at all ones); whichever is `nothing` is zero, at least one must be given.
-Served with 2N ≤ 16 and m ≤ 8 for ANY generators, Lindblad ones included (nothing is reversed); no fidelity is involved.  Arguments as
-`rollout_sweep`.  UNTESTED here, like the rest of this file.
+Served with 2N ≤ 16 and m ≤ 8 for ANY generators, Lindblad ones included (nothing is reversed); no fidelity is involved.  `wide = true`
+sets `qc_sweep_desc.wide = QC_SWEEP_WIDE | QC_SWEEP_WIDE_TANGENT` (17): the matrix-core form up to 2N = 32 ("mfma32-sweep") with its
+pushforward, e.g. two coupled three-level transmons or two qubits with T1 / T2.  Arguments as `rollout_sweep`.  UNTESTED here, like the
+rest of this file.
 """
 function rollout_sweep_pushforward(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift,
                                    G_drives, G_pert, θ::AbstractMatrix{Float64}; scale=nothing, cols::Int, vZ=nothing, vinit=nothing,
-                                   vtheta=nothing, vscale=nothing, device::Int=0)
+                                   vtheta=nothing, vscale=nothing, device::Int=0, wide::Bool=false)
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(θ, 1)
     G0 = Float64.(vec(G_drift))
@@ -1036,7 +1040,7 @@ function rollout_sweep_pushforward(init::AbstractVector{Float64}, controls::Abst
     GC.@preserve G0 Gd Gp begin
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, -1,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
-                               0, 0, C_NULL, C_NULL, device, 0, (0, 0)))
+                               0, 0, C_NULL, C_NULL, device, wide ? (QC_SWEEP_WIDE | QC_SWEEP_WIDE_TANGENT) : 0, (0, 0)))
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_jvp_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
         (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))

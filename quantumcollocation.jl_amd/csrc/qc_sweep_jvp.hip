@@ -7,7 +7,8 @@
 // Nothing is reversed, so no antisymmetry is asked for: Lindblad generators are served like any others (the adjoint walks of
 // qc_sweep_grad.hip are not: they reverse the state with E^T).
 //
-// "mfma16-sweep" handles only (2N <= 16, up to 8 drives).  qc_sweep_jvp_kernel<M> has the work item, workgroup shape and chunk rule of
+// "mfma16-sweep" handles (2N <= 16, up to 8 drives); "mfma32-sweep" handles made with QC_SWEEP_WIDE_TANGENT take qc_sweep32_jvp.hip for the
+// chunk totals and share the finish kernel and the entry points below.  qc_sweep_jvp_kernel<M> has the work item, workgroup shape and chunk rule of
 // qc_sweep_mfma16_kernel (qc_sweep.hip; read its header first): one wavefront per (sample, chunk), kSWaves of them per workgroup,
 // never synchronised.  Every product of the forward kernel is differentiated next to itself, with the tangent tile in the lane map
 // of the tile it belongs to:
@@ -29,9 +30,13 @@
 // x <- init, xdot <- vinit; for ascending chunks xdot <- Q_c xdot + Qdot_c x, then x <- Q_c x; finals / fids carry the bits of
 // qc_sweep_eval on the same handle.  A NULL direction is read as zeros through the same arithmetic: NULL and an explicit zero array
 // give the same bits.  No atomics, sums in a fixed order: repeated calls return the same bits, and no output's bits depend on which
-// others were asked for.  Its dynamic LDS is 4 ns + 512 doubles (x, its successor, their tangents, one chunk total and its tangent);
-// ns = 2N x state_cols reaches 4096 entries (qc_sweep_validate_desc), which is 135168 bytes = 132 KiB of the 160 KiB of a CU.  Above 64 KiB
-// (ns > 1920) the launch opts in with hipFuncSetAttribute; an MI355X accepts it up to ns = 4096 (tests/test_sweep_many_columns.py).
+// others were asked for.  The totals are ld x ld, ld = 16 ("mfma32-sweep": 32, as qc_sweep_finish_kernel), the loops the same.  Its
+// dynamic LDS is 4 ns + 2 ld^2 doubles (x, its successor, their tangents, one chunk total and its tangent);
+// ns = 2N x state_cols reaches 4096 entries (qc_sweep_validate_desc), which is 135168 bytes = 132 KiB of the 160 KiB of a CU (ld = 32:
+// 144 KiB).  Above 64 KiB the launch opts in with hipFuncSetAttribute; an MI355X accepts it up to ns = 4096
+// (tests/test_sweep_many_columns.py, tests/test_sweep_wide_jvp.py).  Should the runtime refuse the attribute on a wide handle, Q and Qdot
+// pass through one ld^2 slot one after the other (136 KiB): the sums keep their order and so their bits; a refusal of that is an error
+// return.
 //
 // gfx950 cross-compile: see the table in DESIGN.md ("Sweep pushforwards"); no private segment, no spills in any instantiation.
 #include <math.h>
@@ -62,6 +67,7 @@ struct JvpParams {
 
 struct JvpFinParams {
     int n, ns, n_chunks, fid_kind, fid_form, fid_n;
+    int one_slot;                // ld = 32 only: Q and Qdot pass through one slot of ld x ld doubles, one after the other (the same sums, the same bits)
 };
 
 template <int CTRL>
@@ -238,14 +244,14 @@ __global__ __launch_bounds__(64 * kSWaves, 2) void qc_sweep_jvp_kernel(const Jvp
 // The x loop, the fidelity sums and their mapping are qc_sweep_finish_kernel's (ld = 16), so finals / fids carry its bits.
 // With t = (g_r . x) + i (g_i . x) and tdot likewise from xdot:  dF = (t_r tdot_r + t_i tdot_i) / (n^2 F) for |t| / n (not special-cased
 // at t = 0), 2 (t_r tdot_r + t_i tdot_i) / n^2 for |t|^2 / n^2, 2 (...) for a ket, tdot_r for a density operator (qc_fidelity.hip).
-__global__ __launch_bounds__(kFinT) void qc_sweep_jvp_finish_kernel(const JvpFinParams F, const double* __restrict__ tot, const double* __restrict__ src,
-                                                                    const double* __restrict__ vsrc, const double* __restrict__ gr,
-                                                                    const double* __restrict__ gi, double* __restrict__ finals,
-                                                                    double* __restrict__ fids, double* __restrict__ tfinals,
-                                                                    double* __restrict__ tfids) {
+// The totals are ld x ld, l2 = ld^2 doubles each: 16 for "mfma16-sweep" handles, 32 for "mfma32-sweep" ones (the two kernels below).
+template <int ld, int l2>
+__device__ __forceinline__ void jvp_finish(const JvpFinParams& F, const double* __restrict__ tot, const double* __restrict__ src,
+                                           const double* __restrict__ vsrc, const double* __restrict__ gr, const double* __restrict__ gi,
+                                           double* __restrict__ finals, double* __restrict__ fids, double* __restrict__ tfinals,
+                                           double* __restrict__ tfids) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     __shared__ double red[4][kFinT / 64];
-    constexpr int ld = 16, l2 = 256;
     const int tid = threadIdx.x, n = F.n, ns = F.ns;
     const long long s = blockIdx.x;
     double* cur = sm;
@@ -260,6 +266,32 @@ __global__ __launch_bounds__(kFinT) void qc_sweep_jvp_finish_kernel(const JvpFin
     }
     const double* __restrict__ Qs = tot + s * F.n_chunks * (long long)(2 * l2);
     for (int c = 0; c < F.n_chunks; ++c) {
+        if (ld == 32 && F.one_slot) {
+            // Q, then Qdot in its place: dnxt keeps the tangent's sum between the two passes, every chain in the order of the loop below
+            __syncthreads();
+            for (int idx = tid; idx < l2; idx += kFinT) Q[idx] = Qs[(long long)c * (2 * l2) + idx];
+            __syncthreads();
+            for (int idx = tid; idx < ns; idx += kFinT) {
+                const int r = idx % n, col = idx / n;
+                double acc = 0.0, dacc = 0.0;
+                for (int q = 0; q < n; ++q) acc = fma(Q[r + ld * q], cur[q + n * col], acc);
+                for (int q = 0; q < n; ++q) dacc = fma(Q[r + ld * q], dcur[q + n * col], dacc);
+                nxt[idx] = acc;
+                dnxt[idx] = dacc;
+            }
+            __syncthreads();
+            for (int idx = tid; idx < l2; idx += kFinT) Q[idx] = Qs[(long long)c * (2 * l2) + l2 + idx];
+            __syncthreads();
+            for (int idx = tid; idx < ns; idx += kFinT) {
+                const int r = idx % n, col = idx / n;
+                double dacc = dnxt[idx];
+                for (int q = 0; q < n; ++q) dacc = fma(Q[r + ld * q], cur[q + n * col], dacc);
+                dnxt[idx] = dacc;
+            }
+            double* tmp = cur; cur = nxt; nxt = tmp;
+            tmp = dcur; dcur = dnxt; dnxt = tmp;
+            continue;
+        }
         __syncthreads();
         for (int idx = tid; idx < 2 * l2; idx += kFinT) Q[idx] = Qs[(long long)c * (2 * l2) + idx];
         __syncthreads();
@@ -320,6 +352,25 @@ __global__ __launch_bounds__(kFinT) void qc_sweep_jvp_finish_kernel(const JvpFin
     }
 }
 
+__global__ __launch_bounds__(kFinT) void qc_sweep_jvp_finish_kernel(const JvpFinParams F, const double* __restrict__ tot, const double* __restrict__ src,
+                                                                    const double* __restrict__ vsrc, const double* __restrict__ gr,
+                                                                    const double* __restrict__ gi, double* __restrict__ finals,
+                                                                    double* __restrict__ fids, double* __restrict__ tfinals,
+                                                                    double* __restrict__ tfids) {
+    constexpr int ld = 16, l2 = 256;
+    jvp_finish<ld, l2>(F, tot, src, vsrc, gr, gi, finals, fids, tfinals, tfids);
+}
+
+// the same on the 32 x 32 totals of "mfma32-sweep" handles (qc_sweep32_jvp.hip), as qc_sweep_finish_kernel takes ld = 32 for them
+__global__ __launch_bounds__(kFinT) void qc_sweep32_jvp_finish_kernel(const JvpFinParams F, const double* __restrict__ tot, const double* __restrict__ src,
+                                                                      const double* __restrict__ vsrc, const double* __restrict__ gr,
+                                                                      const double* __restrict__ gi, double* __restrict__ finals,
+                                                                      double* __restrict__ fids, double* __restrict__ tfinals,
+                                                                      double* __restrict__ tfids) {
+    constexpr int ld = 32, l2 = 1024;
+    jvp_finish<ld, l2>(F, tot, src, vsrc, gr, gi, finals, fids, tfinals, tfids);
+}
+
 // the argument checks both entry points share, in the order of the header's table
 int jvp_check(qc_sweep* h, const char* who, const void* Z, const void* init, int64_t S, const void* theta, bool any_dir, bool any_out, bool v_theta,
               bool v_scale, bool any_fid) {
@@ -340,7 +391,11 @@ int jvp_check(qc_sweep* h, const char* who, const void* Z, const void* init, int
 bool qc_sweep_jvp_scope(const qc_sweep_desc* d, std::string* why) {
     const int form = qc_sweep_desc_form(d);
     if (form == 1) return true;
-    if (form == 2) { *why = "pushforwards are not served in the mfma32-sweep form"; return false; }
+    if (form == 2) {
+        if (d->wide & QC_SWEEP_WIDE_TANGENT) return true;      // qc_sweep32_jvp.hip
+        *why = "pushforwards are not served in the mfma32-sweep form";
+        return false;
+    }
     *why = qc_sweep_per_sample_why(d);
     return false;
 }
@@ -356,10 +411,12 @@ extern "C" int qc_sweep_desc_jvp_supported(const qc_sweep_desc* d, int32_t* supp
     return QC_OK;
 }
 
-// The chunk totals W_c and their tangents Wdot_c of "mfma16-sweep" handles, for the pushforward below and the Hessian product of
-// qc_sweep_hvp.hip: grows h->dTotJ and launches qc_sweep_jvp_kernel<M> on `st` (S x n_chunks x 2 tiles of 256 doubles).
+// The chunk totals W_c and their tangents Wdot_c, for the pushforward below and the Hessian product of qc_sweep_hvp.hip: grows h->dTotJ
+// and launches qc_sweep_jvp_kernel<M> on `st` (S x n_chunks x 2 tiles of 256 doubles); "mfma32-sweep" handles go to
+// qc_sweep32_jvp.hip (S x n_chunks x 2 matrices of 1024 doubles).
 int qc_sweep_jvp_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dvZ,
                                const double* dvtheta, const double* dvscale, hipStream_t st, int64_t* chunk_out, int64_t* n_chunks_out) {
+    if (h->mfma32) return qc_sweep32_jvp_launch_totals(h, dZ, S, dtheta, dscale, dvZ, dvtheta, dvscale, st, chunk_out, n_chunks_out);
     std::string& slot = *qc_sweep_err_slot();
     const int m = h->d.m;
     int64_t chunk, n_chunks;
@@ -396,11 +453,31 @@ static int qc_sweep_jvp_launch(qc_sweep* h, const char* who, const double* dZ, c
     JvpFinParams F;
     F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
     F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;
-    const size_t lds = ((size_t)4 * h->ns + 512) * 8;      // at most 4096 state entries: 132 KiB of the 160
-    if (lds > 64 * 1024)
-        QC_SIDE_HIP(h, slot, hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep_jvp_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(qc_sweep_jvp_finish_kernel, dim3((unsigned)S), dim3(kFinT), lds, st, F, (const double*)h->dTotJ.p, dinit, dvinit,
-                       (const double*)h->dgr, (const double*)h->dgi, dfinals, dfids, dtfinals, dtfids);
+    F.one_slot = 0;
+    if (h->mfma32) {
+        // 4 ns + 2 x 1024 doubles: 144 KiB of the 160 at ns = 4096
+        size_t lds32 = ((size_t)4 * h->ns + 2048) * 8;
+        if (lds32 > 64 * 1024) {
+            const void* fn = reinterpret_cast<const void*>(&qc_sweep32_jvp_finish_kernel);
+            hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds32);
+            if (ea != hipSuccess) {
+                // the runtime refuses the two-slot size: Q and Qdot through one slot (136 KiB at ns = 4096)
+                (void)hipGetLastError();
+                F.one_slot = 1;
+                lds32 = ((size_t)4 * h->ns + 1024) * 8;
+                ea = lds32 > 64 * 1024 ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds32) : hipSuccess;
+            }
+            QC_SIDE_HIP(h, slot, ea);
+        }
+        hipLaunchKernelGGL(qc_sweep32_jvp_finish_kernel, dim3((unsigned)S), dim3(kFinT), lds32, st, F, (const double*)h->dTotJ.p, dinit, dvinit,
+                           (const double*)h->dgr, (const double*)h->dgi, dfinals, dfids, dtfinals, dtfids);
+    } else {
+        const size_t lds = ((size_t)4 * h->ns + 512) * 8;      // at most 4096 state entries: 132 KiB of the 160
+        if (lds > 64 * 1024)
+            QC_SIDE_HIP(h, slot, hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep_jvp_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(qc_sweep_jvp_finish_kernel, dim3((unsigned)S), dim3(kFinT), lds, st, F, (const double*)h->dTotJ.p, dinit, dvinit,
+                           (const double*)h->dgr, (const double*)h->dgi, dfinals, dfids, dtfinals, dtfids);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return qc_sweep_fail(h, QC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return QC_OK;

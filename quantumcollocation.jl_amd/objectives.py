@@ -919,12 +919,14 @@ class SweepFinalStateObjective:
     wide        as `RolloutSweep`
     stored_states  as `RolloutSweep`: True takes the pullback by the stored-state walk, which serves open systems (gradients and
                 `gauss_newton_times`; `hessian_times` keeps the scope of `RolloutSweep.hvp`)
-    wide_stored as `RolloutSweep` (only with `wide` and `stored_states`): that walk in the "mfma32-sweep" form (gradients only: the
-                pushforward behind `gauss_newton_times` is not served there)"""
+    wide_stored as `RolloutSweep` (only with `wide` and `stored_states`): that walk in the "mfma32-sweep" form (gradients only, unless
+                `wide_tangent` is set as well)
+    wide_tangent  as `RolloutSweep` (only with `wide`): the pushforward in the "mfma32-sweep" form, so that `gauss_newton_times` is
+                served there (closed systems, and open ones with `stored_states` and `wide_stored`); `hessian_times` keeps refusing"""
     _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
 
     def __init__(self, traj: NamedTrajectory, system, perturbations, theta, loss, scale=None, state_name="Ũ⃗", control_name: str = "a",
-                 device: int = 0, wide: bool = False, stored_states: bool = False, wide_stored: bool = False):
+                 device: int = 0, wide: bool = False, stored_states: bool = False, wide_stored: bool = False, wide_tangent: bool = False):
         from .rollouts import RolloutSweep, _sweep_samples
         self._sweep = None
         if not callable(loss):
@@ -950,10 +952,12 @@ class SweepFinalStateObjective:
         self.Z_len = traj.T * traj.dim + traj.global_dim
         sw = RolloutSweep(system, perturbations, traj.T, cols=cols, zdim=traj.dim, off_a=traj.offset(control_name),
                           off_dt=traj.offset(traj.timestep) if free else -1, dt_fixed=None if free else float(traj.timestep),
-                          global_dim=traj.global_dim, device=device, wide=wide, stored_states=stored_states, wide_stored=wide_stored)
+                          global_dim=traj.global_dim, device=device, wide=wide, stored_states=stored_states, wide_stored=wide_stored,
+                          wide_tangent=wide_tangent)
         self._sweep = sw
         self.stored_states = sw.stored_states
         self.wide_stored = sw.wide_stored
+        self.wide_tangent = sw.wide_tangent
         if not sw.vjp_supported:
             why = sw.vjp_unsupported_reason
             sw.close()
@@ -1009,7 +1013,8 @@ class SweepFinalStateObjective:
         final states X with respect to Z: one pushforward (X and Xdot = J v, `jvp_device`), the loss's own Hessian product
         u = d2 loss(X) Xdot by double backward on the loss alone (X a detached leaf), one pullback (`vjp_device`, cot = u).  A loss
         that is linear in X gives zeros.  Z and v are numpy arrays (the result is one) or float64 tensors on the handle's device (the
-        result stays there).  Needs the pushforward's scope beside the pullback's: closed systems on an "mfma16-sweep" handle."""
+        result stays there).  Needs the pushforward's scope beside the pullback's: an "mfma16-sweep" handle, or an "mfma32-sweep" handle
+        made with `wide_tangent`."""
         sw = self._sweep
         if not sw.jvp_supported:
             raise _lib.QCollocError(_lib.QC_ERR_UNSUPPORTED, sw.jvp_unsupported_reason)

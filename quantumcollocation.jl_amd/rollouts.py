@@ -188,15 +188,21 @@ class RolloutSweep:
                    with T1 / T2 (levels^2 = 16), a three-level transmon with relaxation, 9 .. 16 levels with a non-Hermitian
                    Hamiltonian.  The device buffer is S x (T-1) x 2N x cols doubles: 32 a knot for a two-qubit density operator
                    (250 MiB at S = 1024, T = 1000), 512 a knot for a 16-level unitary (4 GiB).  Parameter outputs there also need
-                   `wide_params`.  Without it such handles refuse reverse mode, as they always did; nothing else changes."""
+                   `wide_params`.  Without it such handles refuse reverse mode, as they always did; nothing else changes.
+    wide_tangent   True (only with `wide`): an "mfma32-sweep" handle serves `jvp`, `jvp_device` and the forward-mode rule of
+                   `finals_autograd` -- any generators, open systems included, with no state buffer (nothing is reversed): about three
+                   forward sweeps by the instruction count.  Without it those refuse there, as they always did; nothing else changes
+                   (`hvp` keeps refusing in that form)."""
 
     def __init__(self, system, perturbations, T: int, cols: Optional[int] = None, goal=None, fid_kind=None, subspace=None,
                  fid_form: int = _lib.QC_FID_FORM_ABS, zdim: Optional[int] = None, off_a: int = 0, off_dt: Optional[int] = None,
                  dt_fixed: Optional[float] = None, global_dim: int = 0, device: int = 0, wide: bool = False,
-                 stored_states: bool = False, wide_params: bool = False, wide_stored: bool = False):
+                 stored_states: bool = False, wide_params: bool = False, wide_stored: bool = False, wide_tangent: bool = False):
         self._h = None
         if wide_params and not wide:
             raise ValueError("wide_params=True needs wide=True")
+        if wide_tangent and not wide:
+            raise ValueError("wide_tangent=True needs wide=True")
         if wide_stored and not (wide and stored_states):
             raise ValueError("wide_stored=True needs wide=True and stored_states=True")
         m = system.n_drives
@@ -233,7 +239,8 @@ class RolloutSweep:
         d.n_sub = 0 if self._sub is None else int(self._sub.size)
         d.device = device
         d.wide = ((_lib.QC_SWEEP_WIDE if wide else 0) | (_lib.QC_SWEEP_WIDE_PARAMS if wide_params else 0)
-                  | (_lib.QC_SWEEP_WIDE_STORED if wide_stored else 0))
+                  | (_lib.QC_SWEEP_WIDE_STORED if wide_stored else 0) | (_lib.QC_SWEEP_WIDE_TANGENT if wide_tangent else 0))
+        self.wide_tangent = bool(wide_tangent)
         self.wide = bool(wide)
         self.wide_params = bool(wide_params)
         self.wide_stored = bool(wide_stored)
@@ -519,7 +526,7 @@ class RolloutSweep:
     # -- pushforwards: the tangent of the final states and fidelities along one direction -------------------------------------------
     @property
     def jvp_supported(self) -> bool:
-        """Does `jvp` serve this handle?  (`qc_sweep_desc_jvp_supported`: the "mfma16-sweep" form, any generators -- Lindblad ones
+        """Does `jvp` serve this handle?  (`qc_sweep_desc_jvp_supported`: the "mfma16-sweep" form, or "mfma32-sweep" with `wide_tangent`; any generators -- Lindblad ones
         included -- and any fidelity or none.)  `jvp_unsupported_reason` says why not."""
         return self._jvp_scope()[0]
 
@@ -820,7 +827,7 @@ class RolloutSweep:
 
     def finals_autograd(self, dZ, dinit, dtheta=None, dscale=None):
         """The S x (2N cols) final states as a differentiable torch tensor: forward is `eval_device` on the current stream, backward one
-        `vjp_device` call, and under `torch.autograd.forward_ad` the tangent is one `jvp_device` call ("mfma16-sweep" handles).  dZ
+        `vjp_device` call, and under `torch.autograd.forward_ad` the tangent is one `jvp_device` call ("mfma16-sweep" handles, and "mfma32-sweep" handles made with `wide_tangent`).  dZ
         (Z_len), dinit (2N cols), dtheta (S x n_pert), dscale (S x m or None) are float64 CUDA tensors; whichever requires grad
         receives one: Z the plain sum over the samples, init the sum of the per-sample derivatives, theta and scale their per-sample
         values ("mfma16-sweep" handles, and "mfma32-sweep" handles made with `wide_params`: on a wide handle made without it a theta or
@@ -898,10 +905,10 @@ class _SweepFinals(torch.autograd.Function):
 
 def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None, cols: Optional[int] = None, goal=None, fid_kind=None,
                   subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS, wide: bool = False, stored_states: bool = False,
-                  wide_stored: bool = False):
+                  wide_stored: bool = False, wide_tangent: bool = False):
     """(finals, fids) of S rollouts under the perturbed systems: finals is (2N cols) x S, fids S values (None without `fid_kind`).
-    theta is S x len(perturbations) (S x 0 without perturbations), scale S x n_drives or None (all ones); `wide`, `stored_states` and
-    `wide_stored` as `RolloutSweep` (the forward sweep itself looks at neither of the last two)."""
+    theta is S x len(perturbations) (S x 0 without perturbations), scale S x n_drives or None (all ones); `wide`, `stored_states`,
+    `wide_stored` and `wide_tangent` as `RolloutSweep` (the forward sweep itself looks at none of the last three)."""
     controls = np.asarray(controls, dtype=np.float64)
     if controls.ndim != 2 or controls.shape[0] != system.n_drives:
         raise ValueError("controls must be n_drives x T")
@@ -911,7 +918,7 @@ def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None,
     if cols is None:
         cols = init.size // n
     sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device, wide=wide,
-                      stored_states=stored_states, wide_stored=wide_stored)
+                      stored_states=stored_states, wide_stored=wide_stored, wide_tangent=wide_tangent)
     try:
         return sw.eval(sw.pack(controls, dts), init, theta, scale)
     finally:
