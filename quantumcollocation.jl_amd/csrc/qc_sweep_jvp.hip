@@ -40,6 +40,8 @@
 //
 // gfx950 cross-compile: see the table in DESIGN.md ("Sweep pushforwards"); no private segment, no spills in any instantiation.
 #include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
 
 #include <string>
 
@@ -457,8 +459,16 @@ static int qc_sweep_jvp_launch(qc_sweep* h, const char* who, const double* dZ, c
     if (h->mfma32) {
         // 4 ns + 2 x 1024 doubles: 144 KiB of the 160 at ns = 4096
         size_t lds32 = ((size_t)4 * h->ns + 2048) * 8;
-        if (lds32 > 64 * 1024) {
-            const void* fn = reinterpret_cast<const void*>(&qc_sweep32_jvp_finish_kernel);
+        const void* fn = reinterpret_cast<const void*>(&qc_sweep32_jvp_finish_kernel);
+        // QC_SWEEP_JVP_ONE_SLOT=<non-zero integer> (diagnostic override; garbage and 0: not set): every launch, at any ns, as though the
+        // two-slot request below had been refused.  The bits are the same by design, so each such launch says so on stderr.
+        static const bool force_one_slot = getenv("QC_SWEEP_JVP_ONE_SLOT") && atoi(getenv("QC_SWEEP_JVP_ONE_SLOT")) != 0;
+        if (force_one_slot) {
+            F.one_slot = 1;
+            lds32 = ((size_t)4 * h->ns + 1024) * 8;
+            if (lds32 > 64 * 1024) QC_SIDE_HIP(h, slot, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds32));
+            fprintf(stderr, "qcolloc: QC_SWEEP_JVP_ONE_SLOT is active: pushforward finish kernel through one slot\n");
+        } else if (lds32 > 64 * 1024) {
             hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds32);
             if (ea != hipSuccess) {
                 // the runtime refuses the two-slot size: Q and Qdot through one slot (136 KiB at ns = 4096)

@@ -271,7 +271,8 @@ KNOBS = ["QC_HOST_COMPACT", "QC_FUSED_VARIANT", "QC_STORE_MODE", "QC_NO_FUSED", 
          "QC_HOST_TAPER", "QC_HOST_TAIL_SPLIT", "QC_HOST_STREAMS", "QC_HOST_REARM_JOBS", "QC_HOST_REARM", "QC_HOST_PIECE_KB", "QC_HOST_PIECES",
          "QC_HOST_NT", "QC_HOST_NOWATCH", "QC_HOST_NBUF", "QC_HOST_MULTI_FULL", "QC_HOST_LANDING", "QC_HOST_HESS_CHUNKS", "QC_HOST_F_DIRECT",
          "QC_HOST_F_CHUNKS", "QC_HOST_FILL_NT", "QC_HOST_CHUNKS", "QC_HOST_AFFINITY", "QC_HESS_TWO_WAVES", "QC_HESS_GRID", "QC_ELL_JAC",
-         "QC_DEBUG_SKIP", "QC_HOST_TIMEOUT_MS", "QC_HOST_TRACE", "QC_EXP_ELL", "QC_HESS_G2", "QC_HESS_ELL", "QC_FUSED_ELL", "QC_LIST_BATCH"]
+         "QC_DEBUG_SKIP", "QC_HOST_TIMEOUT_MS", "QC_HOST_TRACE", "QC_EXP_ELL", "QC_HESS_G2", "QC_HESS_ELL", "QC_FUSED_ELL", "QC_LIST_BATCH",
+         "QC_SWEEP_JVP_ONE_SLOT"]
 _KNOB_SCRIPT = r"""
 import sys, json
 sys.path[:0] = [%(root)r, %(tests)r]

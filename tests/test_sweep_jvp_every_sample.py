@@ -37,10 +37,10 @@ CLOSED = [k for k in TABLE if k not in LINDBLAD]
 _REF = {}          # case name -> the Frechet reference of the R rows: computed once, shared, never written to
 
 
-def build_rows(qc, name):
+def build_rows(qc, name, table=TABLE):
     """The R rows of test_sweep_every_sample.build_rows (the same systems, theta, scale and cotangents) plus a direction with every part
     non-zero: vcontrols, vdts (free timesteps) and vinit shared by the samples, vtheta and vscale one row per class."""
-    rows = te.build_rows(qc, name, TABLE)
+    rows = te.build_rows(qc, name, table)
     rng = np.random.default_rng(11 + sum(map(ord, name)))
     T, m, p, ns = rows["T"], rows["m"], rows["p"], rows["init"].size
     rows["vcontrols"] = rng.standard_normal((m, T))
@@ -75,10 +75,10 @@ def reference(rows):
 # ---------------------------------------------------------------------------------------------------------------------------------
 #  CPU
 # ---------------------------------------------------------------------------------------------------------------------------------
-def test_pushforward_reference_reuse_is_sound(qc):
+def assert_reference_reuse_is_sound(qc, shapes):
     """Two samples with equal rows have equal Frechet references, bit for bit, and distinct rows differ: the route treats a sample by
-    its own row (theta, scale, vtheta, vscale) alone."""
-    for name, spec in (("closed", ("unitary", 2, 2, 1, True, True, R, 5, te.U01A2)), ("open", ("density", 2, 2, 1, False, True, R, 5, ("density", None, "abs")))):
+    its own row (theta, scale, vtheta, vscale) alone.  `shapes`: (name, case tuple with S = R and T = 5) pairs."""
+    for name, spec in shapes:
         table = {"reuse-" + name: (spec, False, None, None)}
         rows = te.build_rows(qc, "reuse-" + name, table)
         rng = np.random.default_rng(3)
@@ -103,6 +103,11 @@ def test_pushforward_reference_reuse_is_sound(qc):
         moved = frechet(other, [0])
         np.testing.assert_array_equal(moved["finals"], own["finals"][:1])
         assert np.abs(moved["tfinals"] - own["tfinals"][:1]).max() > 1e-3
+
+
+def test_pushforward_reference_reuse_is_sound(qc):
+    assert_reference_reuse_is_sound(qc, (("closed", ("unitary", 2, 2, 1, True, True, R, 5, te.U01A2)),
+                                         ("open", ("density", 2, 2, 1, False, True, R, 5, ("density", None, "abs")))))
 
 
 def test_lindblad_launch_edge(qc):

@@ -9,7 +9,9 @@ launch of the finish kernel), forward-mode autograd, the Gauss-Newton product, r
 Tolerance (GPU against the reference): that of tests/test_sweep_jvp.py, JVP_RTOL = 1e-9 -- per sample
 |got - want| <= 1e-9 max(1, max |want_s|) for tfinals and tfids (the kernels hold states to 1e-10, a tangent is a bounded bilinear
 form of states and direction); finals: the state tolerance of test_sweep.py.  The adjoint identity: 1e-9 relative, both sides above
-1e-3.  The helpers are those of the existing files, imported, not copied."""
+1e-3.  The helpers are those of the existing files, imported, not copied.
+Every sample of mid-size and filled launches, the scratch `dTotJ`, the one-slot branch of the finish kernel:
+tests/test_sweep_wide_jvp_every_sample.py."""
 import ctypes as C
 import inspect
 import os
@@ -47,13 +49,17 @@ SPECS = {
     "n12-ket": ("ket", 12, 2, 1, True, True, 11, 5, ("ket", None, "abs"), None),
     "squarings": ("unitary", 9, 2, 1, False, True, 3, 8, U_ABS, None),                                 # timesteps log-uniform in [1e-3, 40]
     "one-chunk": ("unitary", 9, 2, 1, True, True, 2048, 3, U_ABS, (0, 1000, 2047)),
+    "one-interval": ("unitary", 9, 2, 1, False, True, 3, 2, U_ABS, None),                              # T = 2: the prefetch reads tn = t
+    "n16-no-perturbations": ("unitary", 16, 2, 0, True, True, 3, 6, U_ABS, None),                      # p = 0: theta empty, no vtheta, Bdot stays zero
+    "long": ("unitary", 9, 2, 1, False, True, 2, 1000, U_ABS, None),                                   # 32 chunks of 32, the last 7: the finish kernel chains 32 totals
 }
 LINDBLAD = {
     "two-qubit-lindblad": lambda qc: two.two_qubit_case(qc, "wide-jvp/two-qubit-lindblad", S=5, T=9),  # N = 16 = 4^2, density fidelity
     "qutrit-lindblad": lambda qc: two.qutrit_case(qc, "wide-jvp/qutrit-lindblad", S=3, T=6, free=False),
 }
 CASES = list(SPECS) + list(LINDBLAD)
-ITEMS = {"n9-S5-T11": (3, 4, 1, 20), "n9-S3-T11": (3, 4, 1, 12), "n10-S3-T10": (3, 3, 3, 9), "one-chunk": (2, 1, 2, 2048)}
+ITEMS = {"n9-S5-T11": (3, 4, 1, 20), "n9-S3-T11": (3, 4, 1, 12), "n10-S3-T10": (3, 3, 3, 9), "one-chunk": (2, 1, 2, 2048),
+         "one-interval": (1, 1, 1, 3), "n16-no-perturbations": (2, 3, 1, 9), "long": (32, 32, 7, 64)}
 
 
 def build(qc, name):
@@ -200,10 +206,12 @@ def test_python_keywords(qc):
             qc.RolloutSweep(sys9, [], 5, wide_tangent=True, **kw)
 
 
-@pytest.mark.parametrize("name", [k for k in CASES if k != "one-chunk"] + ["one-chunk", "many-columns"])
+# `long` (T = 1000) is left out, as tests/test_sweep_jvp.py leaves its own out: the 1e-11 bound between the two routes was not written
+# for a thousand steps
+@pytest.mark.parametrize("name", [k for k in CASES if k not in ("one-chunk", "long")] + ["one-chunk", "many-columns"])
 def test_reference_routes_agree(qc, name):
-    """expm_frechet along the recurrence against the complex step through expm on every case the GPU tests use (two samples of each):
-    1e-11 max(1, max |want|), and tangents that a zero could not pass for."""
+    """expm_frechet along the recurrence against the complex step through expm on every case the GPU tests use but `long` (two samples
+    of each): 1e-11 max(1, max |want|), and tangents that a zero could not pass for."""
     c = many_columns(qc) if name == "many-columns" else build(qc, name)
     samples = sorted({0, c["S"] - 1})
     args = (c["G0"], c["Gd"], c["Gp"], c["controls"], c["dts"], c["init"], c["theta"], c["scale"], samples)
