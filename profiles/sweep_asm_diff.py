@@ -1,23 +1,27 @@
 #!/usr/bin/env python3
 """Device assembly of the sweep family at two commits, compared per kernel symbol: the instruction stream (labels renumbered, comments
-dropped), the .amdhsa_kernel block and the metadata (VGPRs, AGPRs, SGPRs, LDS, scratch, spills).  Needs no GPU.
+dropped), the .amdhsa_kernel block and the metadata (VGPRs, AGPRs, SGPRs, LDS, scratch, spills, MFMA count).  Needs no GPU.
 
-    for f in qc_sweep qc_sweep32 qc_sweep_grad qc_sweep32_grad qc_sweep_vjp qc_sweep_jvp; do
+    for f in <FILES below>; do
         hipcc <the Makefile's CXXFLAGS> --cuda-device-only -S $f.hip -o DIR/$f.s       # once in each tree
     done
-    python profiles/sweep_asm_diff.py PARENT_DIR NEW_DIR [--changed qc_sweep_seed_kernel,...]
+    python profiles/sweep_asm_diff.py PARENT_DIR NEW_DIR [--changed qc_sweep_seed_kernel,qc_sweep_grad_kernel,...]
 
-Kernels named by --changed (default: the four seed kernels) are reported with their metadata on both sides, wherever they live; every
-other kernel must be identical, and the exit status says whether it is."""
+Kernels named by --changed (default: the four seed kernels; a template's name without its arguments names every instantiation) are
+reported with their metadata on both sides, wherever they live, and must agree in everything that decides occupancy (VGPRs, AGPRs, LDS,
+scratch, spills: none) and in their MFMA count; SGPRs and the instruction count may move.  Every other kernel must be identical.  The
+exit status says whether all of that holds."""
 import argparse
 import os
 import re
 import subprocess
 import sys
 
-FILES = ["qc_sweep", "qc_sweep32", "qc_sweep_grad", "qc_sweep32_grad", "qc_sweep_vjp", "qc_sweep_jvp"]
+FILES = ["qc_sweep", "qc_sweep32", "qc_sweep_grad", "qc_sweep32_grad", "qc_sweep_vjp", "qc_sweep_jvp", "qc_sweep32_jvp", "qc_sweep_hvp",
+         "qc_sweep_noise", "qc_sweep_open_grad", "qc_sweep32_open_grad"]
 SEEDS = "qc_sweep_seed_kernel,qc_sweep32_seed_kernel,qc_sweep_cot_seed_kernel,qc_sweep32_cot_seed_kernel"
 KEYS = ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "sgpr_spill_count", "vgpr_spill_count")
+FIXED = ("vgpr_count", "agpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "sgpr_spill_count", "vgpr_spill_count", "mfma")
 
 
 def relabel(text):
@@ -40,6 +44,7 @@ def kernels(path):
         assert len(blk) == 1, name
         meta = {key: int(re.search(r"\.%s:\s+(\d+)" % key, ".agpr_count" + blk[0]).group(1)) for key in KEYS}
         meta["instructions"] = sum(1 for ln in body if ln.startswith("\t") and not ln.strip().startswith("."))
+        meta["mfma"] = sum(1 for ln in body if ln.strip().startswith("v_mfma"))
         out[name] = ("\n".join(body), relabel(k.group(1)), meta)
     return out
 
@@ -51,7 +56,8 @@ def plain(name):
 
 def show(meta):
     return (f"VGPR {meta['vgpr_count']} AGPR {meta['agpr_count']} SGPR {meta['sgpr_count']} LDS {meta['group_segment_fixed_size']} B scratch "
-            f"{meta['private_segment_fixed_size']} B spills {meta['sgpr_spill_count']}+{meta['vgpr_spill_count']} instructions {meta['instructions']}")
+            f"{meta['private_segment_fixed_size']} B spills {meta['sgpr_spill_count']}+{meta['vgpr_spill_count']} MFMA {meta['mfma']} "
+            f"instructions {meta['instructions']}")
 
 
 def main():
@@ -62,12 +68,12 @@ def main():
     a = ap.parse_args()
     changed = set(a.changed.split(","))
     sides = [{}, {}]
-    differ = same = 0
+    differ = same = moved = 0
     for f in FILES:
         A, B = (kernels(os.path.join(d, f + ".s")) for d in (a.parent, a.new))
         for name in sorted(set(A) | set(B)):
             p = plain(name)
-            if p in changed:
+            if p in changed or p.split("<")[0] in changed:
                 for side, K in zip(sides, (A, B)):
                     if name in K:
                         side[p] = (f, K[name][2])
@@ -77,13 +83,23 @@ def main():
             else:
                 differ += 1
                 print(f"{f}.hip  {p}: DIFFERS" if name in A and name in B else f"{f}.hip  {p}: on one side only")
-    for p in sorted(changed):
+    for p in sorted(set(sides[0]) | set(sides[1])):
         for label, side in zip(("parent", "new   "), sides):
             if p in side:
                 print(f"{p}  {label} ({side[p][0]}.hip): {show(side[p][1])}")
-    print(f"{same} kernels identical in instruction stream and metadata, {differ} differ or exist on one side only "
-          f"(the {len(changed)} kernels named as changed not counted)")
-    return 1 if differ else 0
+        if p in sides[0] and p in sides[1]:
+            A, B = sides[0][p][1], sides[1][p][1]
+            off = [k for k in FIXED if A[k] != B[k]] + [k for k in ("sgpr_spill_count", "vgpr_spill_count") if B[k]]
+            if off:
+                moved += 1
+            print(f"{p}  " + (f"RESOURCES MOVED: {', '.join(off)}" if off else "resources and MFMA count equal, no spills") +
+                  f"; SGPR {B['sgpr_count'] - A['sgpr_count']:+d}, instructions {B['instructions'] - A['instructions']:+d}")
+        else:
+            moved += 1
+            print(f"{p}  on one side only")
+    print(f"{same} kernels identical in instruction stream and metadata, {differ} differ or exist on one side only; of the "
+          f"{len(set(sides[0]) | set(sides[1]))} kernels named as changed, {moved} moved in VGPRs, AGPRs, LDS, scratch, spills or MFMA count")
+    return 1 if differ or moved else 0
 
 
 if __name__ == "__main__":

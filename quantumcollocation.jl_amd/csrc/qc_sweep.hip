@@ -33,63 +33,31 @@
 
 #include "qc_mfma_common.h"
 #include "qc_side.h"
+#include "qc_sweep16_common.h"
 #include "qc_sweep_internal.h"
 
 namespace {
 
-using namespace qc_mfma;
+using namespace qc_sweep16;         // constants, table, tile load, generator, squaring rule and product of the 16 x 16 form
 
-constexpr int kSDeg = 8;            // as qc_mfma_exp.hip: ||Y||_1 <= 1/8, degree 8, truncation (1/8)^9 / 9! = 4e-14
-constexpr double kSTh = 0.125;
 constexpr int kSMmax = 8;           // drive tiles a wave keeps in registers
-constexpr int kSWaves = 4;          // (sample, chunk) items per workgroup: one wave each, the waves never synchronise
 constexpr int kFinT = 256;          // threads of the final-state / fidelity workgroup
 constexpr long long kSweepFill = 2048;   // waves that give every SIMD a couple: 256 CUs x 4 SIMDs x 2
-
-// 1 / k!, k = 0 .. 8
-__constant__ const double kSInvFact[kSDeg + 1] = {1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0, 1.0 / 40320.0};
-
-struct SweepParams {
-    int n, nc, m, p, zdim, off_a, off_dt, n_int, chunk, n_chunks;
-    long long items;             // S * n_chunks
-    double dt_fixed;
-    const double* img;           // A-layout images [matrix][kk][lane]: drift, m drives, p perturbations
-};
 
 struct FinParams {
     int n, ns, ld, n_chunks, fid_kind, fid_form, fid_n;
     long long src_stride;        // 0: every sample starts from the same state (init); ns: per-sample states (per-sample form)
 };
 
-template <int CTRL>
-__device__ inline double sdpp(double x) {
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ inline v4d simg(const double* __restrict__ img, int mat, int lane) {
-    const double* p = img + (size_t)mat * 256 + lane;
-    return v4d{p[0], p[64], p[128], p[192]};
-}
-
-// D = A B + C with one accumulator: the four MFMAs of a Horner step or a squaring
-__device__ __forceinline__ v4d mma16(const v4d& a, const v4d& b, v4d acc) {
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], b[kk], acc, 0, 0, 0);
-    return acc;
-}
-
 template <int M>
-__global__ __launch_bounds__(64 * kSWaves, 2) void qc_sweep_mfma16_kernel(const SweepParams P, const double* __restrict__ Z,
+__global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_mfma16_kernel(const SweepParams P, const double* __restrict__ Z,
                                                                            const double* __restrict__ theta, const double* __restrict__ scale,
                                                                            double* __restrict__ tot) {
-    __shared__ double scr_all[kSWaves * 16 * 17];
+    __shared__ double scr_all[kWaves * kTile];
     const int lane = threadIdx.x & 63;
     const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * (16 * 17);
-    const long long item = (long long)blockIdx.x * kSWaves + wq;
+    double* __restrict__ scr = scr_all + wq * kTile;
+    const long long item = (long long)blockIdx.x * kWaves + wq;
     if (item >= P.items) return;
     const long long s = item / P.n_chunks;
     const int c = (int)(item - s * P.n_chunks);
@@ -101,16 +69,9 @@ __global__ __launch_bounds__(64 * kSWaves, 2) void qc_sweep_mfma16_kernel(const 
     const v4d zero = {0.0, 0.0, 0.0, 0.0};
 
     // ---- once per wave: the sample's base tile and the drive tiles ---------------------------------------------------------
-    v4d base = simg(P.img, 0, lane);
-    for (int q = 0; q < P.p; ++q) {
-        const double th = theta[s * P.p + q];
-        const v4d Pq = simg(P.img, 1 + m + q, lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) base[r] = fma(th, Pq[r], base[r]);
-    }
+    const v4d base = base_tile(P.img, m, P.p, theta, s, lane);
     v4d Gj[M];
-#pragma unroll
-    for (int u = 0; u < M; ++u) Gj[u] = u < m ? simg(P.img, 1 + u, lane) : zero;
+    resident_tiles(P.img, m, lane, Gj);
     // lane l holds the sample's factor of drive min(l, m-1); folded into the control values
     const int kl = lane < m ? lane : (m > 0 ? m - 1 : 0);
     const double cl = (scale && m > 0) ? scale[s * m + kl] : 1.0;
@@ -127,50 +88,17 @@ __global__ __launch_bounds__(64 * kSWaves, 2) void qc_sweep_mfma16_kernel(const 
         const double av_n = m > 0 ? zn[P.off_a + kl] : 0.0;
         const double h_n = ft ? zn[P.off_dt] : hfix;
         const double al = av * cl;
-        v4d Ga = base;
-#pragma unroll
-        for (int u = 0; u < M; ++u) {
-            const double a = u < m ? bcast_lane(al, u) : 0.0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Ga[r] = fma(a, Gj[u][r], Ga[r]);
-        }
-        // ||h G||_1 = largest column sum: lane (g, i) reg kk holds G[i][4kk+g]; rows of 16 lanes share a column
-        int sq = 0;
-        {
-            double best = 0.0;
-            bool bad = false;
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                double cs = fabs(h * Ga[kk]);
-                cs += sdpp<0x128>(cs);
-                cs += sdpp<0x124>(cs);
-                cs += sdpp<0x122>(cs);
-                cs += sdpp<0x121>(cs);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const double v = bcast_lane(cs, 16 * r);
-                    if (!(v == v) || v > 1e300) bad = true;
-                    best = fmax(best, v);
-                }
-            }
-            if (!bad && best > kSTh) {
-                int e;
-                (void)frexp(best / kSTh, &e);
-                sq = e;
-                if (ldexp(kSTh, e - 1) >= best) sq = e - 1;
-                sq = sq < 0 ? 0 : (sq > 60 ? 60 : sq);
-            }
-            sq = __builtin_amdgcn_readfirstlane(sq);
-        }
+        const v4d Ga = generator(base, Gj, m, al);
+        const int sq = squarings(h, Ga);
         const double sc = ldexp(1.0, -sq);
         const v4d Y = (h * sc) * Ga;
         // Horner: R_deg+1 = I/deg!,  R_k = Y R_k+1 + I/(k-1)!
         // (the coefficients 1 / (k-1)! from a table of correctly rounded constants: the last one is exactly 1, so a zero generator gives
         //  exactly the identity; computed in the loop they cost two f64 divisions a step)
-        v4d R = kSInvFact[kSDeg] * IdB;
+        v4d R = kInvFact[kDeg] * IdB;
 #pragma unroll 1
-        for (int k = kSDeg; k >= 1; --k)        // (unrolled, the eight scaled identities are hoisted out of the interval loop: 64 VGPRs)
-            R = mma16(Y, R, kSInvFact[k - 1] * IdB);
+        for (int k = kDeg; k >= 1; --k)        // (unrolled, the eight scaled identities are hoisted out of the interval loop: 64 VGPRs)
+            R = mma16(Y, R, kInvFact[k - 1] * IdB);
         for (int q = 0; q < sq; ++q) {
             const v4d Et = lds_transpose16(scr, R, g, j);
             R = mma16(Et, R, zero);
@@ -355,19 +283,13 @@ int qc_sweep_check(qc_sweep* h, const char* who, const bool qc_sweep::*ok, const
 int qc_sweep_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, hipStream_t st, int64_t* chunk_out,
                            int64_t* n_chunks_out) {
     if (h->mfma32) return qc_sweep32_launch_totals(h, dZ, S, dtheta, dscale, st, chunk_out, n_chunks_out);
-    const int m = h->d.m;
     int64_t chunk, n_chunks;
     qc_sweep_chunks(S, h->d.T, &chunk, &n_chunks);
     QC_SIDE_HIP(h, g_swerr, h->grow(h->dTot, (size_t)S * n_chunks * 256));
-    SweepParams P;
-    P.n = h->n; P.nc = h->nc; P.m = m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
-    P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks;
-    P.items = S * n_chunks;
-    P.dt_fixed = h->d.dt_fixed;
-    P.img = h->dImg;
-    const unsigned grid = (unsigned)((P.items + kSWaves - 1) / kSWaves);
-#define QC_SWEEP_LAUNCH(M_) hipLaunchKernelGGL(qc_sweep_mfma16_kernel<M_>, dim3(grid), dim3(64 * kSWaves), 0, st, P, dZ, dtheta, dscale, h->dTot.p)
-    QC_SWEEP_FOR_M(m, QC_SWEEP_LAUNCH);
+    const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
+    const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
+#define QC_SWEEP_LAUNCH(M_) hipLaunchKernelGGL(qc_sweep_mfma16_kernel<M_>, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, h->dTot.p)
+    QC_SWEEP_FOR_M(P.m, QC_SWEEP_LAUNCH);
 #undef QC_SWEEP_LAUNCH
     *chunk_out = chunk;
     *n_chunks_out = n_chunks;

@@ -31,14 +31,7 @@ namespace {
 
 using namespace qc_sweep32;
 
-struct Sweep32Params {
-    int n, m, p, zdim, off_a, off_dt, n_int, chunk, n_chunks;
-    long long items;             // S * n_chunks
-    double dt_fixed;
-    const double* img;           // A-layout images, 1024 doubles a matrix: drift, m drives, p perturbations
-};
-
-__global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_mfma32_kernel(const Sweep32Params P, const double* __restrict__ Z,
+__global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_mfma32_kernel(const SweepParams P, const double* __restrict__ Z,
                                                                            const double* __restrict__ theta, const double* __restrict__ scale,
                                                                            double* __restrict__ tot) {
     __shared__ double scr_all[kWaves * kScr];
@@ -123,12 +116,7 @@ int qc_sweep32_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const dou
     int64_t chunk, n_chunks;
     qc_sweep_chunks(S, h->d.T, &chunk, &n_chunks);
     QC_SIDE_HIP(h, *qc_sweep_err_slot(), h->grow(h->dTot, (size_t)S * n_chunks * 1024));
-    Sweep32Params P;
-    P.n = h->n; P.m = h->d.m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
-    P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks;
-    P.items = S * n_chunks;
-    P.dt_fixed = h->d.dt_fixed;
-    P.img = h->dImg;
+    const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
     const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
     hipLaunchKernelGGL(qc_sweep_mfma32_kernel, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, h->dTot.p);
     *chunk_out = chunk;

@@ -1,31 +1,17 @@
-// What the forward kernel (qc_sweep32.hip) and the backward walks (qc_sweep32_grad.hip, qc_sweep32_open_grad.hip) of the "mfma32-sweep" form
-// share, in one place so that it cannot drift: the closed walk reverses the forward step, and the stored states match the stored-state
-// walk, only if all form the same generator and choose the same number of squarings.  Constants, the sample's base matrix, the
-// interval's generator, the squaring rule, the four-tile transpose, the in-place product X <- A X + c I.
+// What the forward kernel (qc_sweep32.hip), the backward walks (qc_sweep32_grad.hip, qc_sweep32_open_grad.hip) and the pushforward
+// (qc_sweep32_jvp.hip) of the "mfma32-sweep" form share, in one place so that it cannot drift: the closed walk reverses the forward step,
+// and the stored states match the stored-state walk, only if all form the same generator and choose the same number of squarings.  The
+// sample's base matrix, the interval's generator, the squaring rule, the four-tile transpose, the in-place product X <- A X + c I;
+// constants, table, DPP move, wave sum and the rule's tail are those of qc_sweep_common.h.  The counterpart of qc_sweep16_common.h.
 #pragma once
-#include <math.h>
 
-#include "qc_mfma_common.h"
+#include "qc_sweep_common.h"
 
 namespace qc_sweep32 {
 
-using namespace qc_mfma;
+using namespace qc_sweep_common;
 
-constexpr int kDeg = 8;             // as qc_sweep.hip: ||Y||_1 <= 1/8, degree 8, truncation (1/8)^9 / 9! = 4e-14
-constexpr double kTh = 0.125;
-constexpr int kWaves = 4;           // (sample, chunk) items per workgroup: one wave each, the waves never synchronise
 constexpr int kScr = 4 * 272;       // doubles of LDS per wave: four transposition tiles
-
-// 1 / k!, k = 0 .. 8: the values of kSInvFact (qc_sweep.hip; a __constant__ table is private to its translation unit)
-static __constant__ const double kInvFact[kDeg + 1] = {1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0, 1.0 / 40320.0};
-
-template <int CTRL>
-static __device__ __forceinline__ double dpp(double x) {
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
 
 // sample s's base matrix G_drift + sum_q theta[s, q] P_q in A layout (images: 1024 doubles a matrix -- drift, m drives, p perturbations)
 __device__ __forceinline__ void base_matrix(const double* __restrict__ img, int m, int p, const double* __restrict__ theta, long long s, int lane,
@@ -66,18 +52,13 @@ __device__ __forceinline__ void generator(const double* __restrict__ img, int m,
 // largest column sum: tile (I, K), lane (g, i), reg kk holds G[16 I + i][16 K + 4 kk + g]; the two tile rows and the 16 lanes of a row
 // share a column.
 __device__ __forceinline__ int squarings(const v4d (&G)[2][2], double h) {
-    int sq = 0;
     double best = 0.0;
     bool bad = false;
 #pragma unroll
     for (int K = 0; K < 2; ++K) {
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            double cs = fabs(h * G[0][K][kk]) + fabs(h * G[1][K][kk]);
-            cs += dpp<0x128>(cs);
-            cs += dpp<0x124>(cs);
-            cs += dpp<0x122>(cs);
-            cs += dpp<0x121>(cs);
+            const double cs = row_sum(fabs(h * G[0][K][kk]) + fabs(h * G[1][K][kk]));
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const double v = bcast_lane(cs, 16 * r);
@@ -86,14 +67,7 @@ __device__ __forceinline__ int squarings(const v4d (&G)[2][2], double h) {
             }
         }
     }
-    if (!bad && best > kTh) {
-        int e;
-        (void)frexp(best / kTh, &e);
-        sq = e;
-        if (ldexp(kTh, e - 1) >= best) sq = e - 1;
-        sq = sq < 0 ? 0 : (sq > 60 ? 60 : sq);
-    }
-    return __builtin_amdgcn_readfirstlane(sq);
+    return squarings_of_norm(best, bad);
 }
 
 // the four tiles of a D-layout matrix, each transposed: the matrix in A layout (one LDS round trip)

@@ -3,8 +3,8 @@
 // orthogonal, so x_t = E^T x_{t+1} (no state stored inside a chunk), L(hG; E^T K) = E^T L(hG; K) with K = x_{t+1} lambda_{t+1}^T (the
 // Frechet chain runs beside the Horner chain), one chain per interval serves all m drives, dF/da_k = c_k sum ZT . G_k,
 // dF/dh = -sum KT . G.  Degree 8, threshold 1/8, the 1/k! table, the generator and the squaring rule are the forward kernel's: both files
-// take them from qc_sweep32_common.h; the paired column step, the product with E^T and the wave sum are those of qc_sweep32_walk.h, shared
-// with the stored-state walk of qc_sweep32_open_grad.hip.
+// take them from qc_sweep32_common.h; the paired column step and the product with E^T are those of qc_sweep32_walk.h, shared with the
+// stored-state walk of qc_sweep32_open_grad.hip; the wave sum is the family's (qc_sweep_common.h).
 //
 // Launches of one call on such a handle (qc_sweep_grad_launch of qc_sweep_grad.hip routes here):
 //   1. qc_sweep_mfma32_kernel: the forward chunk totals, column-major 32 x 32;
@@ -54,13 +54,6 @@ namespace {
 
 using namespace qc_sweep32;
 
-struct Grad32Params {
-    int n, nc, m, p, zdim, off_a, off_dt, n_int, chunk, n_chunks, nd;   // nd = m + (off_dt >= 0): derivatives per interval
-    long long items;             // S * n_chunks
-    double dt_fixed;
-    const double* img;           // A-layout images, 1024 doubles a matrix: drift, m drives, p perturbations
-};
-
 // One wavefront per (sample, chunk), walking the chunk backwards.  PAR = false: the per-interval derivatives
 // only (`part` unused).  PAR = true, the parameter flavour (qc_sweep_grad_kernel<M, true> on 2 x 2 tiles), also keeps Acc = sum_t ZT_t
 // (four tiles) and, in lane k, sum_t a_{t,k} du_{t,k} with du_{t,k} = sum ZT . G_k BEFORE the factor c_k (no division by c: defined at
@@ -73,7 +66,7 @@ template <bool PAR>
 constexpr int kGSl = PAR ? kScr + 16 * 64 : kScr;          // doubles of LDS a wave: the transposition tiles, PAR: and Acc behind them
 
 template <bool PAR>
-__global__ __launch_bounds__(64 * kGW<PAR>) void qc_sweep32_grad_kernel(const Grad32Params P, const double* __restrict__ Z, const double* __restrict__ theta,
+__global__ __launch_bounds__(64 * kGW<PAR>) void qc_sweep32_grad_kernel(const SweepParams P, const double* __restrict__ Z, const double* __restrict__ theta,
                                                                        const double* __restrict__ scale, const double* __restrict__ xs,
                                                                        const double* __restrict__ ls, double* __restrict__ gs,
                                                                        double* __restrict__ part) {
@@ -181,7 +174,7 @@ __global__ __launch_bounds__(64 * kGW<PAR>) void qc_sweep32_grad_kernel(const Gr
             for (int q = 0; q < 4; ++q)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) ph = fma(dY[q >> 1][q & 1][r], Y[q >> 1][q & 1][r], ph);
-            const double dh = -vwave_sum(ph);
+            const double dh = -wave_sum(ph);
             out = ln == m ? dh : out;
         }
 #pragma unroll
@@ -225,7 +218,7 @@ __global__ __launch_bounds__(64 * kGW<PAR>) void qc_sweep32_grad_kernel(const Gr
 #pragma unroll
                 for (int r = 0; r < 4; ++r) pu = fma(Y[q & 1][q >> 1][r], t4[r], pu);
             }
-            const double du = vwave_sum(pu);
+            const double du = wave_sum(pu);
             if constexpr (PAR) duv = ln == u ? du : duv;
             else out = ln == u ? du * cl : out;
         }
@@ -262,7 +255,7 @@ __global__ __launch_bounds__(64 * kGW<PAR>) void qc_sweep32_grad_kernel(const Gr
 #pragma unroll
                 for (int r = 0; r < 4; ++r) pq = fma(accl[64 * (4 * (2 * (u & 1) + (u >> 1)) + r) + lane], t4[r], pq);
             }
-            const double dq = vwave_sum(pq);
+            const double dq = wave_sum(pq);
             acc_t = le == q ? dq : acc_t;
         }
         if (le < p) po[0] = acc_t;
@@ -274,12 +267,7 @@ __global__ __launch_bounds__(64 * kGW<PAR>) void qc_sweep32_grad_kernel(const Gr
 
 void qc_sweep32_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,
                             double* gs, bool par, double* dgrad_theta, double* dgrad_scale, hipStream_t st) {
-    Grad32Params P;
-    P.n = h->n; P.nc = h->nc; P.m = h->d.m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
-    P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks; P.nd = P.m + (P.off_dt >= 0 ? 1 : 0);
-    P.items = S * n_chunks;
-    P.dt_fixed = h->d.dt_fixed;
-    P.img = h->dImg;
+    const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
     const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
     if (par) {
         hipLaunchKernelGGL(qc_sweep32_grad_kernel<true>, dim3((unsigned)((P.items + kGW<true> - 1) / kGW<true>)), dim3(64 * kGW<true>), 0, st, P, dZ, dtheta, dscale, (const double*)h->dXs.p,

@@ -40,13 +40,6 @@ namespace {
 
 using namespace qc_sweep32;
 
-struct Jvp32Params {
-    int n, m, p, zdim, off_a, off_dt, n_int, chunk, n_chunks;
-    long long items;             // S * n_chunks
-    double dt_fixed;
-    const double* img;           // A-layout images, 1024 doubles a matrix: drift, m drives, p perturbations
-};
-
 // G = base + sum_u al_u G_u and Gd = based + sum_u ald_u G_u in A layout from one pass over the drive images.  The G chain is
 // qc_sweep32::generator's: the same fma on the same operands in the same order, so G carries its bits.
 __device__ __forceinline__ void generator_pair(const double* __restrict__ img, int m, double al, double ald, const v4d (&base)[2][2],
@@ -77,7 +70,7 @@ __device__ __forceinline__ void generator_pair(const double* __restrict__ img, i
 constexpr int kJW = 2;                       // waves a workgroup: one wave per SIMD either way (512 registers a wave)
 constexpr int kJSl = kScr + 19 * 64;         // doubles of LDS a wave: the transposition tiles; behind them Bdot and three values a lane
 
-__global__ __launch_bounds__(64 * kJW) void qc_sweep32_jvp_kernel(const Jvp32Params P, const double* __restrict__ Z,
+__global__ __launch_bounds__(64 * kJW) void qc_sweep32_jvp_kernel(const SweepParams P, const double* __restrict__ Z,
                                                                       const double* __restrict__ theta, const double* __restrict__ scale,
                                                                       const double* __restrict__ vZ, const double* __restrict__ vtheta,
                                                                       const double* __restrict__ vscale, double* __restrict__ tot) {
@@ -209,12 +202,7 @@ int qc_sweep32_jvp_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const
     int64_t chunk, n_chunks;
     qc_sweep_chunks(S, h->d.T, &chunk, &n_chunks);
     QC_SIDE_HIP(h, *qc_sweep_err_slot(), h->grow(h->dTotJ, (size_t)S * n_chunks * 2048));
-    Jvp32Params P;
-    P.n = h->n; P.m = h->d.m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
-    P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks;
-    P.items = S * n_chunks;
-    P.dt_fixed = h->d.dt_fixed;
-    P.img = h->dImg;
+    const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
     const unsigned grid = (unsigned)((P.items + kJW - 1) / kJW);
     hipLaunchKernelGGL(qc_sweep32_jvp_kernel, dim3(grid), dim3(64 * kJW), 0, st, P, dZ, dtheta, dscale, dvZ, dvtheta, dvscale, h->dTotJ.p);
     *chunk_out = chunk;

@@ -41,13 +41,6 @@ namespace {
 
 using namespace qc_sweep32;
 
-struct Open32Params {
-    int n, nc, m, p, zdim, off_a, off_dt, n_int, chunk, n_chunks, nd;   // nd = m + (off_dt >= 0): derivatives per interval
-    long long items;             // S * n_chunks
-    double dt_fixed;
-    const double* img;           // A-layout images, 1024 doubles a matrix: drift, m drives, p perturbations
-};
-
 // v <- A v for an A-layout matrix and a two-tile column block (B / D layout)
 __device__ __forceinline__ void xapply(const v4d (&A)[2][2], v4d (&v)[2]) {
     const v4d z = {0.0, 0.0, 0.0, 0.0};
@@ -65,7 +58,7 @@ __device__ __forceinline__ void xapply(const v4d (&A)[2][2], v4d (&v)[2]) {
 }
 
 // x_t of every knot of the chunk, t = t0 .. t1-1, from the chunk-start state
-__global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep32_open_store_kernel(const Open32Params P, const double* __restrict__ Z,
+__global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep32_open_store_kernel(const SweepParams P, const double* __restrict__ Z,
                                                                                  const double* __restrict__ theta, const double* __restrict__ scale,
                                                                                  const double* __restrict__ init, const double* __restrict__ xs,
                                                                                  double* __restrict__ xall) {
@@ -171,7 +164,7 @@ constexpr int kOSl = PAR ? kScr + 16 * 64 : kScr;          // doubles of LDS a w
 // One wavefront per (sample, chunk), walking the chunk backwards on the stored states.  The flavours, `part` and `gs` as
 // qc_sweep32_grad_kernel (qc_sweep32_grad.hip).
 template <bool PAR>
-__global__ __launch_bounds__(64 * kOW<PAR>) void qc_sweep32_open_grad_kernel(const Open32Params P, const double* __restrict__ Z,
+__global__ __launch_bounds__(64 * kOW<PAR>) void qc_sweep32_open_grad_kernel(const SweepParams P, const double* __restrict__ Z,
                                                                             const double* __restrict__ theta, const double* __restrict__ scale,
                                                                             const double* __restrict__ xall, const double* __restrict__ ls,
                                                                             double* __restrict__ gs, double* __restrict__ part) {
@@ -317,7 +310,7 @@ __global__ __launch_bounds__(64 * kOW<PAR>) void qc_sweep32_open_grad_kernel(con
                     Y[q >> 1][q & 1][r] = fma(a, t4[r], Y[q >> 1][q & 1][r]);
                 }
             }
-            const double du = vwave_sum(pu);
+            const double du = wave_sum(pu);
             if constexpr (PAR) duv = ln == u ? du : duv;
             else out = ln == u ? du * cl : out;
         }
@@ -328,7 +321,7 @@ __global__ __launch_bounds__(64 * kOW<PAR>) void qc_sweep32_open_grad_kernel(con
             for (int q = 0; q < 4; ++q)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) ph = fma(dR[q & 1][q >> 1][r], Y[q >> 1][q & 1][r], ph);
-            const double dh = vwave_sum(ph);
+            const double dh = wave_sum(ph);
             out = ln == m ? dh : out;
         }
         if constexpr (PAR) {
@@ -364,7 +357,7 @@ __global__ __launch_bounds__(64 * kOW<PAR>) void qc_sweep32_open_grad_kernel(con
 #pragma unroll
                 for (int r = 0; r < 4; ++r) pq = fma(accl[64 * (4 * (2 * (u & 1) + (u >> 1)) + r) + lane], t4[r], pq);
             }
-            const double dq = vwave_sum(pq);
+            const double dq = wave_sum(pq);
             acc_t = le == q ? dq : acc_t;
         }
         if (le < p) po[0] = acc_t;
@@ -376,12 +369,7 @@ __global__ __launch_bounds__(64 * kOW<PAR>) void qc_sweep32_open_grad_kernel(con
 
 void qc_sweep32_open_launch_walk(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
                                  int64_t chunk, int64_t n_chunks, double* gs, bool par, double* dgrad_theta, double* dgrad_scale, hipStream_t st) {
-    Open32Params P;
-    P.n = h->n; P.nc = h->nc; P.m = h->d.m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
-    P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks; P.nd = P.m + (P.off_dt >= 0 ? 1 : 0);
-    P.items = S * n_chunks;
-    P.dt_fixed = h->d.dt_fixed;
-    P.img = h->dImg;
+    const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
     hipLaunchKernelGGL(qc_sweep32_open_store_kernel, dim3((unsigned)((P.items + kWaves - 1) / kWaves)), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale,
                        dinit, (const double*)h->dXs.p, h->dXall.p);
     if (par) {

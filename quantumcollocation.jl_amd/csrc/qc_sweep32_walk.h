@@ -1,20 +1,11 @@
 // What the two backward walks of the "mfma32-sweep" form share: the closed walk of qc_sweep32_grad.hip (qc_sweep32_grad_kernel, which reverses
 // the forward step) and the stored-state walk of qc_sweep32_open_grad.hip (qc_sweep32_open_grad_kernel, which reads the forward states).
-// The paired column step of the Horner / squaring chains on 2 x 2 tiles, the product with E^T and the wave sum in a fixed order; constants,
-// generator and squaring rule are those of qc_sweep32_common.h.
+// The paired column step of the Horner / squaring chains on 2 x 2 tiles and the product with E^T; constants, generator and squaring rule
+// are those of qc_sweep32_common.h, the wave sum that of qc_sweep_common.h.
 #pragma once
 #include "qc_sweep32_common.h"
 
 namespace qc_sweep32 {
-
-// the sum over the 64 lanes in a fixed order, wave-uniform (as qc_sweep_grad.hip)
-static __device__ inline double vwave_sum(double v) {
-    v += dpp<0x128>(v);
-    v += dpp<0x124>(v);
-    v += dpp<0x122>(v);
-    v += dpp<0x121>(v);
-    return (bcast_lane(v, 0) + bcast_lane(v, 16)) + (bcast_lane(v, 32) + bcast_lane(v, 48));
-}
 
 // column J of (R, dR) <- (A R + C, dA R + A dR) in place; C given by its tiles of that column.  Six accumulator chains, interleaved.
 __device__ __forceinline__ void vcol(const v4d (&A)[2][2], const v4d (&dA)[2][2], v4d (&R)[2][2], v4d (&dR)[2][2], int J, const v4d& c0,

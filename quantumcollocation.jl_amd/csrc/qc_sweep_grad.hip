@@ -67,14 +67,13 @@
 #include <vector>
 
 #include "qc_mfma_common.h"
+#include "qc_sweep16_common.h"
 #include "qc_sweep_internal.h"
 #include "qc_sweep_seed.h"
-#include "qc_sweep_walk.h"
 
 namespace {
 
-using namespace qc_mfma;
-using namespace qc_sweep_walk;   // the series, the squaring rule, the step and the wave sum both walks share
+using namespace qc_sweep16;         // the series, the generator, the squaring rule, the step and the wave sum
 using qc_sweep_seed::kSeedT;        // threads of the seed workgroup
 constexpr int kRedT = 256;
 
@@ -92,15 +91,15 @@ struct ReduceParams {
 // dF_s/dc_k = sum_t a_{t,k} sum(ZT_t . G_k) and stores them at the chunk's end as part[item][p + m]; `gs` may then be NULL (no
 // per-interval store, no timestep derivative).
 template <int M, bool PAR = false>
-__global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_grad_kernel(const GradParams P, const double* __restrict__ Z, const double* __restrict__ theta,
+__global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_grad_kernel(const SweepParams P, const double* __restrict__ Z, const double* __restrict__ theta,
                                                                          const double* __restrict__ scale, const double* __restrict__ xs,
                                                                          const double* __restrict__ ls, double* __restrict__ gs,
                                                                          double* __restrict__ part) {
-    __shared__ double scr_all[kGWaves * kGSlice<PAR>];
+    __shared__ double scr_all[kWaves * kWalkSlice<PAR>];
     const int lane = threadIdx.x & 63;
     const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kGSlice<PAR>;
-    const long long item = (long long)blockIdx.x * kGWaves + wq;
+    double* __restrict__ scr = scr_all + wq * kWalkSlice<PAR>;
+    const long long item = (long long)blockIdx.x * kWaves + wq;
     if (item >= P.items) return;
     const long long s = item / P.n_chunks;
     const int c = (int)(item - s * P.n_chunks);
@@ -112,16 +111,9 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_grad_kernel(const Gr
     const v4d zero = {0.0, 0.0, 0.0, 0.0};
 
     // ---- once per wave: the sample's base tile, the drive tiles, the state and the adjoint at the chunk's end --------------------
-    v4d base = gimg(P.img, 0, lane);
-    for (int q = 0; q < P.p; ++q) {
-        const double th = theta[s * P.p + q];
-        const v4d Pq = gimg(P.img, 1 + m + q, lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) base[r] = fma(th, Pq[r], base[r]);
-    }
+    const v4d base = base_tile(P.img, m, P.p, theta, s, lane);
     v4d Gj[M];
-#pragma unroll
-    for (int u = 0; u < M; ++u) Gj[u] = u < m ? gimg(P.img, 1 + u, lane) : zero;
+    resident_tiles(P.img, m, lane, Gj);
     const int kl = lane < m ? lane : (m > 0 ? m - 1 : 0);
     const double cl = (scale && m > 0) ? scale[s * m + kl] : 1.0;
 
@@ -147,7 +139,7 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_grad_kernel(const Gr
     // factor c_k: no division by c) live in the wave's LDS slice, and the interval's unscaled controls wait there (accl[256 + l]) for
     // the interval's end: every lane reads back what it wrote itself (no barrier), one read / write pair per interval off the MFMA
     // chain.  Held in registers they do not fit beside M = 6 at three waves per SIMD.
-    double* accl = scr + 2 * 272;
+    double* accl = scr + 2 * kTile;
     if constexpr (PAR) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) accl[64 * r + lane] = 0.0;
@@ -161,42 +153,8 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_grad_kernel(const Gr
         const double h_n = ft ? zn[P.off_dt] : hfix;
         const double al = av * cl;
         if constexpr (PAR) accl[256 + lane] = av;
-        v4d Ga = base;
-#pragma unroll
-        for (int u = 0; u < M; ++u) {
-            const double a = u < m ? bcast_lane(al, u) : 0.0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Ga[r] = fma(a, Gj[u][r], Ga[r]);
-        }
-        // the number of squarings: the rule of the forward kernel (qc_sweep_walk::squarings, written out: the call changed this kernel's
-        // scalar register count)
-        int sq = 0;
-        {
-            double best = 0.0;
-            bool bad = false;
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                double cs = fabs(h * Ga[kk]);
-                cs += gdpp<0x128>(cs);
-                cs += gdpp<0x124>(cs);
-                cs += gdpp<0x122>(cs);
-                cs += gdpp<0x121>(cs);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const double v = bcast_lane(cs, 16 * r);
-                    if (!(v == v) || v > 1e300) bad = true;
-                    best = fmax(best, v);
-                }
-            }
-            if (!bad && best > kGTh) {
-                int e;
-                (void)frexp(best / kGTh, &e);
-                sq = e;
-                if (ldexp(kGTh, e - 1) >= best) sq = e - 1;
-                sq = sq < 0 ? 0 : (sq > 60 ? 60 : sq);
-            }
-            sq = __builtin_amdgcn_readfirstlane(sq);
-        }
+        const v4d Ga = generator(base, Gj, m, al);
+        const int sq = squarings(h, Ga);      // the rule of the forward kernel
         const double hs = h * ldexp(1.0, -sq);
         // K^T = lambda x^T of knot t+1 (D layout) from the A-layout forms of both
         v4d KT;
@@ -204,7 +162,7 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_grad_kernel(const Gr
             const v4d in[2] = {x, lam};
             v4d tr[2];
             lds_transpose16_multi<2>(scr, in, tr, g, j);
-            KT = gmma(tr[1], tr[0], zero);
+            KT = mma16(tr[1], tr[0], zero);
         }
         // M = 8: kept loop-invariant, the eight lane compares below live in 16 scalar registers and the kernel spills one; an opaque
         // copy of the lane index has them made per interval instead (8 v_cmp)
@@ -220,17 +178,17 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_grad_kernel(const Gr
         }
         const v4d Y = hs * Ga;
         const v4d dY = hs * KT;
-        v4d R = kGInvFact[kGDeg] * IdB;
+        v4d R = kInvFact[kDeg] * IdB;
         v4d dR = zero;
 #pragma unroll 1
-        for (int k = kGDeg; k >= 1; --k) gstep(Y, dY, R, dR, kGInvFact[k - 1] * IdB);
+        for (int k = kDeg; k >= 1; --k) step16(Y, dY, R, dR, kInvFact[k - 1] * IdB);
         for (int q = 0; q < sq; ++q) {
             const v4d in[2] = {R, dR};
             v4d tr[2];
             lds_transpose16_multi<2>(scr, in, tr, g, j);      // E^T, dE^T in D layout = E, dE in A layout
-            gstep(tr[0], tr[1], R, dR, zero);
+            step16(tr[0], tr[1], R, dR, zero);
         }
-        const v4d ZT = gmma(R, dR, zero);                       // E^T dE
+        const v4d ZT = mma16(R, dR, zero);                       // E^T dE
 #pragma unroll
         for (int u = 0; u < M; ++u) {
             if (u < m) {
@@ -251,8 +209,8 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_grad_kernel(const Gr
         } else {
             if (lane < P.nd) gs[(s * P.n_int + t) * P.nd + lane] = out;
         }
-        x = gmma(R, x, zero);
-        lam = gmma(R, lam, zero);
+        x = mma16(R, x, zero);
+        lam = mma16(R, lam, zero);
         av = av_n;
         h = h_n;
     }
@@ -263,7 +221,7 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_grad_kernel(const Gr
         for (int r = 0; r < 4; ++r) Acc[r] = accl[64 * r + lane];
         double acc_t = 0.0;
         for (int q = 0; q < P.p; ++q) {
-            const v4d Pq = gimg(P.img, 1 + m + q, lane);
+            const v4d Pq = image_tile(P.img, 1 + m + q, lane);
             double pq = 0.0;
 #pragma unroll
             for (int r = 0; r < 4; ++r) pq = fma(Acc[r], Pq[r], pq);
@@ -471,26 +429,18 @@ extern "C" int qc_sweep_desc_grad_supported(const qc_sweep_desc* d, int32_t* sup
 // ends are read from h->dXs / h->dLs; scratch is the caller's.
 void qc_sweep16_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,
                             double* gs, bool want_par, double* dgrad_theta, double* dgrad_scale, hipStream_t st) {
-    const int m = h->d.m, p = h->d.n_pert;
-    const int nd = m + (h->d.off_dt >= 0 ? 1 : 0);
-    const int64_t n_int = h->d.T - 1;
-    GradParams P;
-    P.n = h->n; P.nc = h->nc; P.m = m; P.p = p; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
-    P.n_int = (int)n_int; P.chunk = (int)chunk; P.n_chunks = (int)n_chunks; P.nd = nd;
-    P.items = S * n_chunks;
-    P.dt_fixed = h->d.dt_fixed;
-    P.img = h->dImg;
-    const unsigned grid = (unsigned)((P.items + kGWaves - 1) / kGWaves);
+    const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
+    const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
 #define QC_GRAD_LAUNCH(M_)                                                                                                                      \
     do {                                                                                                                                        \
         if (want_par)                                                                                                                           \
-            hipLaunchKernelGGL((qc_sweep_grad_kernel<M_, true>), dim3(grid), dim3(64 * kGWaves), 0, st, P, dZ, dtheta, dscale,                    \
+            hipLaunchKernelGGL((qc_sweep_grad_kernel<M_, true>), dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale,                    \
                                (const double*)h->dXs.p, (const double*)h->dLs.p, gs, h->dPart.p);                                               \
         else                                                                                                                                    \
-            hipLaunchKernelGGL((qc_sweep_grad_kernel<M_, false>), dim3(grid), dim3(64 * kGWaves), 0, st, P, dZ, dtheta, dscale,                   \
+            hipLaunchKernelGGL((qc_sweep_grad_kernel<M_, false>), dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale,                   \
                                (const double*)h->dXs.p, (const double*)h->dLs.p, gs, (double*)nullptr);                                         \
     } while (0)
-    QC_SWEEP_FOR_M(m, QC_GRAD_LAUNCH);
+    QC_SWEEP_FOR_M(P.m, QC_GRAD_LAUNCH);
 #undef QC_GRAD_LAUNCH
     if (want_par) qc_sweep_launch_par_reduce(h, S, n_chunks, dgrad_theta, dgrad_scale, st);
 }

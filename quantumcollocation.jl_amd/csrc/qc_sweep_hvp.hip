@@ -58,60 +58,24 @@
 #include <string>
 
 #include "qc_mfma_common.h"
+#include "qc_sweep16_common.h"
 #include "qc_sweep_internal.h"
 
 namespace {
 
-using namespace qc_mfma;
+using namespace qc_sweep16;         // threshold and squaring rule, tile load, generator, product and wave sum of the 16 x 16 form
 
-constexpr int kHDeg = 10;           // see "Series degree" above
-constexpr double kHTh = 0.125;      // the forward kernel's threshold (kSTh of qc_sweep.hip)
-constexpr int kHWaves = 4;          // (sample, chunk) items per workgroup: one wave each, the waves never synchronise
+constexpr int kHDeg = 10;           // see "Series degree" above: this file's own degree and table
 constexpr int kHSeedT = 256;
-constexpr int kHSlice = 4 * 272;    // LDS of one wave: four transposition tiles
+constexpr int kHSlice = 4 * kTile;  // LDS of one wave: four transposition tiles
 
 // 1 / k!, k = 0 .. 10
 __constant__ const double kHInvFact[kHDeg + 1] = {1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0,
                                                   1.0 / 40320.0, 1.0 / 362880.0, 1.0 / 3628800.0};
 
-struct HvpParams {
-    int n, nc, m, p, zdim, off_a, off_dt, n_int, chunk, n_chunks, nd;   // nd = m + (off_dt >= 0): derivatives per interval
-    long long items;             // S * n_chunks
-    double dt_fixed;
-    const double* img;           // A-layout images [matrix][kk][lane]: drift, m drives, p perturbations
-};
-
 struct HvpSeedParams {
     int n, ns, n_chunks;
 };
-
-template <int CTRL>
-__device__ inline double hdpp(double x) {
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ inline v4d himg(const double* __restrict__ img, int mat, int lane) {
-    const double* p = img + (size_t)mat * 256 + lane;
-    return v4d{p[0], p[64], p[128], p[192]};
-}
-
-__device__ __forceinline__ v4d hmma(const v4d& a, const v4d& b, v4d acc) {
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], b[kk], acc, 0, 0, 0);
-    return acc;
-}
-
-// the sum over the 64 lanes in a fixed order, wave-uniform: row sums by DPP rotations, then (row 0 + row 1) + (row 2 + row 3)
-__device__ inline double hwave_sum(double v) {
-    v += hdpp<0x128>(v);
-    v += hdpp<0x124>(v);
-    v += hdpp<0x122>(v);
-    v += hdpp<0x121>(v);
-    return (bcast_lane(v, 0) + bcast_lane(v, 16)) + (bcast_lane(v, 32) + bcast_lane(v, 48));
-}
 
 // The nine products of a step on the quadruple (R, Rdot, dR, dRdot) with the left factors (A, Adot, dA, dAdot):
 //     R <- A R + C,  Rdot <- Adot R + A Rdot,  dR <- dA R + A dR,  dRdot <- dAdot R + dA Rdot + Adot dR + A dRdot
@@ -144,17 +108,17 @@ __device__ __forceinline__ void hstep(const v4d& A, const v4d& Ad, const v4d& dA
 // One wavefront per (sample, chunk), walking the chunk backwards: the gradient walk with every product differentiated beside itself.
 // xs / ls: x and lambda at the chunk ends, xts / lts: their tangents; tgs: S x (T-1) x nd.
 template <int M>
-__global__ __launch_bounds__(64 * kHWaves, 1) void qc_sweep_hvp_kernel(const HvpParams P, const double* __restrict__ Z, const double* __restrict__ theta,
+__global__ __launch_bounds__(64 * kWaves, 1) void qc_sweep_hvp_kernel(const SweepParams P, const double* __restrict__ Z, const double* __restrict__ theta,
                                                                         const double* __restrict__ scale, const double* __restrict__ vZ,
                                                                         const double* __restrict__ vtheta, const double* __restrict__ vscale,
                                                                         const double* __restrict__ xs, const double* __restrict__ ls,
                                                                         const double* __restrict__ xts, const double* __restrict__ lts,
                                                                         double* __restrict__ tgs) {
-    __shared__ double scr_all[kHWaves * kHSlice];
+    __shared__ double scr_all[kWaves * kHSlice];
     const int lane = threadIdx.x & 63;
     const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     double* __restrict__ scr = scr_all + wq * kHSlice;
-    const long long item = (long long)blockIdx.x * kHWaves + wq;
+    const long long item = (long long)blockIdx.x * kWaves + wq;
     if (item >= P.items) return;
     const long long s = item / P.n_chunks;
     const int c = (int)(item - s * P.n_chunks);
@@ -167,21 +131,10 @@ __global__ __launch_bounds__(64 * kHWaves, 1) void qc_sweep_hvp_kernel(const Hvp
     const v4d zero = {0.0, 0.0, 0.0, 0.0};
 
     // ---- once per wave: the sample's base tile and its tangent, the drive tiles, the four states at the chunk's end -----------------
-    v4d base = himg(P.img, 0, lane);
-    v4d based = zero;
-    for (int q = 0; q < P.p; ++q) {
-        const double th = theta[s * P.p + q];
-        const double vth = vtheta ? vtheta[s * P.p + q] : 0.0;
-        const v4d Pq = himg(P.img, 1 + m + q, lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            base[r] = fma(th, Pq[r], base[r]);
-            based[r] = fma(vth, Pq[r], based[r]);
-        }
-    }
+    v4d base, based;
+    base_tile(P.img, m, P.p, theta, vtheta, s, lane, base, based);
     v4d Gj[M];
-#pragma unroll
-    for (int u = 0; u < M; ++u) Gj[u] = u < m ? himg(P.img, 1 + u, lane) : zero;
+    resident_tiles(P.img, m, lane, Gj);
     // lane l holds the sample's factor of drive min(l, m-1) and its tangent
     const int kl = lane < m ? lane : (m > 0 ? m - 1 : 0);
     const double cl = (scale && m > 0) ? scale[s * m + kl] : 1.0;
@@ -236,45 +189,9 @@ __global__ __launch_bounds__(64 * kHWaves, 1) void qc_sweep_hvp_kernel(const Hvp
         // made per interval instead
         int mu = m;
         asm volatile("" : "+s"(mu));
-        v4d Ga = base, Gad = based;
-#pragma unroll
-        for (int u = 0; u < M; ++u) {
-            const double a = u < mu ? bcast_lane(al, u) : 0.0;
-            const double ad = u < mu ? bcast_lane(ald, u) : 0.0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                Ga[r] = fma(a, Gj[u][r], Ga[r]);
-                Gad[r] = fma(ad, Gj[u][r], Gad[r]);
-            }
-        }
-        // the number of squarings: the rule of the forward kernel, from ||h Ga||_1 alone
-        int sq = 0;
-        {
-            double best = 0.0;
-            bool bad = false;
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                double cs = fabs(h * Ga[kk]);
-                cs += hdpp<0x128>(cs);
-                cs += hdpp<0x124>(cs);
-                cs += hdpp<0x122>(cs);
-                cs += hdpp<0x121>(cs);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const double v = bcast_lane(cs, 16 * r);
-                    if (!(v == v) || v > 1e300) bad = true;
-                    best = fmax(best, v);
-                }
-            }
-            if (!bad && best > kHTh) {
-                int e;
-                (void)frexp(best / kHTh, &e);
-                sq = e;
-                if (ldexp(kHTh, e - 1) >= best) sq = e - 1;
-                sq = sq < 0 ? 0 : (sq > 60 ? 60 : sq);
-            }
-            sq = __builtin_amdgcn_readfirstlane(sq);
-        }
+        v4d Ga, Gad;
+        generator(base, based, Gj, mu, al, ald, Ga, Gad);
+        const int sq = squarings(h, Ga);      // the rule of the forward kernel, from ||h Ga||_1 alone
         const double sc = ldexp(1.0, -sq);
         const double hs = h * sc, vhs = vh * sc;
         // K^T = lambda x^T of knot t+1 (D layout) and its tangent, from the A-layout forms of the four states
@@ -283,9 +200,9 @@ __global__ __launch_bounds__(64 * kHWaves, 1) void qc_sweep_hvp_kernel(const Hvp
             const v4d in[4] = {x, lam, xd, lamd};
             v4d tr[4];
             lds_transpose16_multi<4>(scr, in, tr, g, j);
-            KT = hmma(tr[1], tr[0], zero);
-            KTd = hmma(tr[3], tr[0], zero);
-            KTd = hmma(tr[1], tr[2], KTd);
+            KT = mma16(tr[1], tr[0], zero);
+            KTd = mma16(tr[3], tr[0], zero);
+            KTd = mma16(tr[1], tr[2], KTd);
         }
         // kept loop-invariant, the lane compares below live in two scalar registers each and the larger instantiations spill them; an opaque
         // copy of the lane index has them made per interval instead (as qc_sweep_grad_kernel<8>)
@@ -298,7 +215,7 @@ __global__ __launch_bounds__(64 * kHWaves, 1) void qc_sweep_hvp_kernel(const Hvp
             for (int r = 0; r < 4; ++r) ph = fma(KTd[r], Ga[r], ph);
 #pragma unroll
             for (int r = 0; r < 4; ++r) ph = fma(KT[r], Gad[r], ph);
-            const double dhd = -hwave_sum(ph);
+            const double dhd = -wave_sum(ph);
             out = ln == mu ? dhd : out;
         }
         const v4d Y = hs * Ga;
@@ -318,9 +235,9 @@ __global__ __launch_bounds__(64 * kHWaves, 1) void qc_sweep_hvp_kernel(const Hvp
             lds_transpose16_multi<4>(scr, in, tr, g, j);      // the transposes in D layout = E, Edot, dE, dEdot in A layout
             hstep(tr[0], tr[1], tr[2], tr[3], R, Rd, dR, dRd, zero);
         }
-        const v4d ZT = hmma(R, dR, zero);                       // E^T dE
-        v4d ZTd = hmma(Rd, dR, zero);                           // Edot^T dE + E^T dEdot
-        ZTd = hmma(R, dRd, ZTd);
+        const v4d ZT = mma16(R, dR, zero);                       // E^T dE
+        v4d ZTd = mma16(Rd, dR, zero);                           // Edot^T dE + E^T dEdot
+        ZTd = mma16(R, dRd, ZTd);
 #pragma unroll
         for (int u = 0; u < M; ++u) {
             if (u < mu) {
@@ -330,19 +247,19 @@ __global__ __launch_bounds__(64 * kHWaves, 1) void qc_sweep_hvp_kernel(const Hvp
                     pu = fma(ZT[r], Gj[u][r], pu);
                     pud = fma(ZTd[r], Gj[u][r], pud);
                 }
-                const double du = hwave_sum(pu);
-                const double dud = hwave_sum(pud);
+                const double du = wave_sum(pu);
+                const double dud = wave_sum(pud);
                 out = ln == u ? fma(dud, cl, du * vcl) : out;
             }
         }
         if (ln < P.nd) tgs[(s * P.n_int + t) * P.nd + ln] = out;
         {
-            v4d nxd = hmma(Rd, x, zero);
-            nxd = hmma(R, xd, nxd);
-            v4d nld = hmma(Rd, lam, zero);
-            nld = hmma(R, lamd, nld);
-            x = hmma(R, x, zero);
-            lam = hmma(R, lam, zero);
+            v4d nxd = mma16(Rd, x, zero);
+            nxd = mma16(R, xd, nxd);
+            v4d nld = mma16(Rd, lam, zero);
+            nld = mma16(R, lamd, nld);
+            x = mma16(R, x, zero);
+            lam = mma16(R, lam, zero);
             xd = nxd;
             lamd = nld;
         }
@@ -499,15 +416,10 @@ static int qc_sweep_hvp_launch(qc_sweep* h, const char* who, const double* dZ, c
     hipLaunchKernelGGL(qc_sweep_hvp_seed_kernel, dim3((unsigned)S), dim3(kHSeedT), lds, st, F, (const double*)h->dTotJ.p, dinit, dvinit, dcot, dvcot,
                        h->dXs.p, h->dXsT.p, h->dLs.p, h->dLsT.p, dtgrad_init);
     if (want_walk) {
-        HvpParams P;
-        P.n = h->n; P.nc = h->nc; P.m = m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
-        P.n_int = (int)n_int; P.chunk = (int)chunk; P.n_chunks = (int)n_chunks; P.nd = nd;
-        P.items = S * n_chunks;
-        P.dt_fixed = h->d.dt_fixed;
-        P.img = h->dImg;
-        const unsigned grid = (unsigned)((P.items + kHWaves - 1) / kHWaves);
+        const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
+        const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
 #define QC_HVP_LAUNCH(M_)                                                                                                                 \
-    hipLaunchKernelGGL(qc_sweep_hvp_kernel<M_>, dim3(grid), dim3(64 * kHWaves), 0, st, P, dZ, dtheta, dscale, dvZ, dvtheta, dvscale,       \
+    hipLaunchKernelGGL(qc_sweep_hvp_kernel<M_>, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, dvZ, dvtheta, dvscale,       \
                        (const double*)h->dXs.p, (const double*)h->dLs.p, (const double*)h->dXsT.p, (const double*)h->dLsT.p, tgs)
         QC_SWEEP_FOR_M(m, QC_HVP_LAUNCH);
 #undef QC_HVP_LAUNCH

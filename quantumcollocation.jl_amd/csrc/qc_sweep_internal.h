@@ -1,6 +1,6 @@
 // What qc_sweep.hip (forward sweep), qc_sweep_grad.hip (its adjoint), qc_sweep_open_grad.hip and qc_sweep32_open_grad.hip (the adjoint on stored states), qc_sweep_vjp.hip (the pullback of the final states),
-// qc_sweep_jvp.hip (their pushforward), qc_sweep_hvp.hip (the tangent of the pullback) and qc_sweep_noise.hip (noise trajectories) share: the handle with its scratch and staging buffers, the descriptor and argument checks and
-// the launch of the forward chunk totals (with it the chunk rule).  Not part of the ABI.
+// qc_sweep_jvp.hip (their pushforward), qc_sweep_hvp.hip (the tangent of the pullback) and qc_sweep_noise.hip (noise trajectories) share: the handle with its scratch and staging buffers, the descriptor and argument checks, the launch
+// parameters of the (sample, chunk) kernels (SweepParams, qc_sweep_params) and the launch of the forward chunk totals (with it the chunk rule).  Not part of the ABI.
 #pragma once
 
 #include <string>
@@ -68,6 +68,24 @@ struct qc_sweep : qc_side {
     qc_buf sNoise;       // noise, S x (T-1) x p                                              noise_eval, noise_grad
     qc_buf sGnoise;      // grad_noise, S x (T-1) x p                                         noise_grad
 };
+
+// The launch parameters of every kernel of the MFMA forms that runs one wavefront per (sample, chunk of consecutive intervals)
+struct SweepParams {
+    int n, nc, m, p, zdim, off_a, off_dt, n_int, chunk, n_chunks, nd;   // nd = m + (off_dt >= 0): derivatives per interval
+    long long items;             // S * n_chunks
+    double dt_fixed;
+    const double* img;           // A-layout images, 256 doubles a matrix ("mfma32-sweep": 1024): drift, m drives, p perturbations
+};
+
+inline SweepParams qc_sweep_params(const qc_sweep* h, int64_t S, int64_t chunk, int64_t n_chunks) {
+    SweepParams P;
+    P.n = h->n; P.nc = h->nc; P.m = h->d.m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
+    P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks; P.nd = h->d.m + (h->d.off_dt >= 0 ? 1 : 0);
+    P.items = S * n_chunks;
+    P.dt_fixed = h->d.dt_fixed;
+    P.img = h->dImg;
+    return P;
+}
 
 // records the message in the handle (when there is one) and in the slot qc_sweep_last_error(NULL) returns
 int qc_sweep_fail(qc_side* h, int code, const std::string& msg);

@@ -9,7 +9,7 @@
 //
 // "mfma16-sweep" handles (2N <= 16, up to 8 drives); "mfma32-sweep" handles made with QC_SWEEP_WIDE_TANGENT take qc_sweep32_jvp.hip for the
 // chunk totals and share the finish kernel and the entry points below.  qc_sweep_jvp_kernel<M> has the work item, workgroup shape and chunk rule of
-// qc_sweep_mfma16_kernel (qc_sweep.hip; read its header first): one wavefront per (sample, chunk), kSWaves of them per workgroup,
+// qc_sweep_mfma16_kernel (qc_sweep.hip; read its header first): one wavefront per (sample, chunk), kWaves of them per workgroup,
 // never synchronised.  Every product of the forward kernel is differentiated next to itself, with the tangent tile in the lane map
 // of the tile it belongs to:
 //   once per wave   Bdot = sum_j vtheta[s,j] P_j (A layout), the lane's vc[s,k] beside c[s,k]
@@ -46,70 +46,30 @@
 #include <string>
 
 #include "qc_mfma_common.h"
+#include "qc_sweep16_common.h"
 #include "qc_sweep_internal.h"
 
 namespace {
 
-using namespace qc_mfma;
+using namespace qc_sweep16;
 
-// the constants of qc_sweep.hip, restated (that file's are internal to it)
-constexpr int kSDeg = 8;
-constexpr double kSTh = 0.125;
-constexpr int kSWaves = 4;
-constexpr int kFinT = 256;
-
-__constant__ const double kSInvFact[kSDeg + 1] = {1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0, 1.0 / 40320.0};
-
-struct JvpParams {
-    int n, nc, m, p, zdim, off_a, off_dt, n_int, chunk, n_chunks;
-    long long items;             // S * n_chunks
-    double dt_fixed;
-    const double* img;           // A-layout images [matrix][kk][lane]: drift, m drives, p perturbations
-};
+constexpr int kFinT = 256;          // threads of the finish workgroup, as qc_sweep_finish_kernel's
 
 struct JvpFinParams {
     int n, ns, n_chunks, fid_kind, fid_form, fid_n;
     int one_slot;                // ld = 32 only: Q and Qdot pass through one slot of ld x ld doubles, one after the other (the same sums, the same bits)
 };
 
-template <int CTRL>
-__device__ inline double sdpp(double x) {
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ inline v4d simg(const double* __restrict__ img, int mat, int lane) {
-    const double* p = img + (size_t)mat * 256 + lane;
-    return v4d{p[0], p[64], p[128], p[192]};
-}
-
-// A product and its derivative: P = A B + C (the chain of qc_sweep.hip's mma16, operation for operation) and
-// Pdot = Adot B + A Bdot, the twelve MFMAs issued round-robin on three independent accumulators.
-__device__ __forceinline__ void mma16_d(const v4d& a, const v4d& ad, v4d& b, v4d& bd, const v4d& c) {
-    const v4d zero = {0.0, 0.0, 0.0, 0.0};
-    v4d t0 = zero, t1 = zero, r = c;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-        t0 = __builtin_amdgcn_mfma_f64_16x16x4f64(ad[kk], b[kk], t0, 0, 0, 0);
-        t1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], bd[kk], t1, 0, 0, 0);
-        r = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], b[kk], r, 0, 0, 0);
-    }
-    bd = t0 + t1;
-    b = r;
-}
-
 template <int M>
-__global__ __launch_bounds__(64 * kSWaves, 2) void qc_sweep_jvp_kernel(const JvpParams P, const double* __restrict__ Z,
+__global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_jvp_kernel(const SweepParams P, const double* __restrict__ Z,
                                                                         const double* __restrict__ theta, const double* __restrict__ scale,
                                                                         const double* __restrict__ vZ, const double* __restrict__ vtheta,
                                                                         const double* __restrict__ vscale, double* __restrict__ tot) {
-    __shared__ double scr_all[kSWaves * 2 * 16 * 17];
+    __shared__ double scr_all[kWaves * 2 * kTile];
     const int lane = threadIdx.x & 63;
     const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * (2 * 16 * 17);
-    const long long item = (long long)blockIdx.x * kSWaves + wq;
+    double* __restrict__ scr = scr_all + wq * (2 * kTile);
+    const long long item = (long long)blockIdx.x * kWaves + wq;
     if (item >= P.items) return;
     const long long s = item / P.n_chunks;
     const int c = (int)(item - s * P.n_chunks);
@@ -122,21 +82,10 @@ __global__ __launch_bounds__(64 * kSWaves, 2) void qc_sweep_jvp_kernel(const Jvp
     const v4d zero = {0.0, 0.0, 0.0, 0.0};
 
     // ---- once per wave: the sample's base tile, its tangent, and the drive tiles -------------------------------------------
-    v4d base = simg(P.img, 0, lane);
-    v4d based = zero;
-    for (int q = 0; q < P.p; ++q) {
-        const double th = theta[s * P.p + q];
-        const double vth = vtheta ? vtheta[s * P.p + q] : 0.0;
-        const v4d Pq = simg(P.img, 1 + m + q, lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            base[r] = fma(th, Pq[r], base[r]);
-            based[r] = fma(vth, Pq[r], based[r]);
-        }
-    }
+    v4d base, based;
+    base_tile(P.img, m, P.p, theta, vtheta, s, lane, base, based);
     v4d Gj[M];
-#pragma unroll
-    for (int u = 0; u < M; ++u) Gj[u] = u < m ? simg(P.img, 1 + u, lane) : zero;
+    resident_tiles(P.img, m, lane, Gj);
     // lane l holds the sample's factor of drive min(l, m-1) and its tangent
     const int kl = lane < m ? lane : (m > 0 ? m - 1 : 0);
     const double cl = (scale && m > 0) ? scale[s * m + kl] : 1.0;
@@ -168,45 +117,9 @@ __global__ __launch_bounds__(64 * kSWaves, 2) void qc_sweep_jvp_kernel(const Jvp
         }
         const double al = av * cl;
         const double ald = fma(vav, cl, av * vcl);
-        v4d Ga = base, Gad = based;
-#pragma unroll
-        for (int u = 0; u < M; ++u) {
-            const double a = u < m ? bcast_lane(al, u) : 0.0;
-            const double ad = u < m ? bcast_lane(ald, u) : 0.0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                Ga[r] = fma(a, Gj[u][r], Ga[r]);
-                Gad[r] = fma(ad, Gj[u][r], Gad[r]);
-            }
-        }
-        // ||h G||_1 = largest column sum, as qc_sweep_mfma16_kernel: the tangent has no say in sq
-        int sq = 0;
-        {
-            double best = 0.0;
-            bool bad = false;
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                double cs = fabs(h * Ga[kk]);
-                cs += sdpp<0x128>(cs);
-                cs += sdpp<0x124>(cs);
-                cs += sdpp<0x122>(cs);
-                cs += sdpp<0x121>(cs);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const double v = bcast_lane(cs, 16 * r);
-                    if (!(v == v) || v > 1e300) bad = true;
-                    best = fmax(best, v);
-                }
-            }
-            if (!bad && best > kSTh) {
-                int e;
-                (void)frexp(best / kSTh, &e);
-                sq = e;
-                if (ldexp(kSTh, e - 1) >= best) sq = e - 1;
-                sq = sq < 0 ? 0 : (sq > 60 ? 60 : sq);
-            }
-            sq = __builtin_amdgcn_readfirstlane(sq);
-        }
+        v4d Ga, Gad;
+        generator(base, based, Gj, m, al, ald, Ga, Gad);
+        const int sq = squarings(h, Ga);      // the forward kernel's rule: the tangent has no say in sq
         const double sc = ldexp(1.0, -sq);
         const v4d Y = (h * sc) * Ga;
         v4d Yd;
@@ -216,19 +129,19 @@ __global__ __launch_bounds__(64 * kSWaves, 2) void qc_sweep_jvp_kernel(const Jvp
             for (int r = 0; r < 4; ++r) Yd[r] = fma(vhs, Ga[r], hs * Gad[r]);
         }
         // Horner on the pair: Rdot_k = Ydot R_k+1 + Y Rdot_k+1,  R_k = Y R_k+1 + I/(k-1)!
-        v4d R = kSInvFact[kSDeg] * IdB, Rd = zero;
+        v4d R = kInvFact[kDeg] * IdB, Rd = zero;
 #pragma unroll 1
-        for (int k = kSDeg; k >= 1; --k) mma16_d(Y, Yd, R, Rd, kSInvFact[k - 1] * IdB);
+        for (int k = kDeg; k >= 1; --k) step16(Y, Yd, R, Rd, kInvFact[k - 1] * IdB);
         for (int q = 0; q < sq; ++q) {
             const v4d in[2] = {R, Rd};
             v4d tr[2];
             lds_transpose16_multi<2>(scr, in, tr, g, j);      // E^T, Edot^T in D layout = E, Edot in A layout
-            mma16_d(tr[0], tr[1], R, Rd, zero);
+            step16(tr[0], tr[1], R, Rd, zero);
         }
         const v4d in[2] = {R, Rd};
         v4d tr[2];
         lds_transpose16_multi<2>(scr, in, tr, g, j);
-        mma16_d(tr[0], tr[1], W, Wd, zero);
+        step16(tr[0], tr[1], W, Wd, zero);
         av = av_n;
         h = h_n;
         vav = vav_n;
@@ -420,20 +333,14 @@ int qc_sweep_jvp_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const d
                                const double* dvtheta, const double* dvscale, hipStream_t st, int64_t* chunk_out, int64_t* n_chunks_out) {
     if (h->mfma32) return qc_sweep32_jvp_launch_totals(h, dZ, S, dtheta, dscale, dvZ, dvtheta, dvscale, st, chunk_out, n_chunks_out);
     std::string& slot = *qc_sweep_err_slot();
-    const int m = h->d.m;
     int64_t chunk, n_chunks;
     qc_sweep_chunks(S, h->d.T, &chunk, &n_chunks);
     QC_SIDE_HIP(h, slot, h->grow(h->dTotJ, (size_t)S * n_chunks * 512));
-    JvpParams P;
-    P.n = h->n; P.nc = h->nc; P.m = m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
-    P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks;
-    P.items = S * n_chunks;
-    P.dt_fixed = h->d.dt_fixed;
-    P.img = h->dImg;
-    const unsigned grid = (unsigned)((P.items + kSWaves - 1) / kSWaves);
+    const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
+    const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
 #define QC_JVP_LAUNCH(M_) \
-    hipLaunchKernelGGL(qc_sweep_jvp_kernel<M_>, dim3(grid), dim3(64 * kSWaves), 0, st, P, dZ, dtheta, dscale, dvZ, dvtheta, dvscale, h->dTotJ.p)
-    QC_SWEEP_FOR_M(m, QC_JVP_LAUNCH);
+    hipLaunchKernelGGL(qc_sweep_jvp_kernel<M_>, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, dvZ, dvtheta, dvscale, h->dTotJ.p)
+    QC_SWEEP_FOR_M(P.m, QC_JVP_LAUNCH);
 #undef QC_JVP_LAUNCH
     *chunk_out = chunk;
     *n_chunks_out = n_chunks;

@@ -34,98 +34,14 @@
 #include <string>
 
 #include "qc_mfma_common.h"
+#include "qc_sweep16_common.h"
 #include "qc_sweep_internal.h"
 
 namespace {
 
-using namespace qc_mfma;
+using namespace qc_sweep16;         // the forward kernel's and the closed walk's pieces: both kernels here are theirs with m + p tiles
 
-// the constants of qc_sweep.hip / qc_sweep_grad.hip, restated (those files' are internal to them)
-constexpr int kNDeg = 8;
-constexpr double kNTh = 0.125;
 constexpr int kNTiles = 8;          // tiles a wave keeps in registers: drives and perturbations together
-constexpr int kNWaves = 4;          // (sample, chunk) items per workgroup: one wave each, the waves never synchronise
-constexpr int kNGSlice = 2 * 272;   // LDS doubles of one wave of the backward walk: two transposition tiles
-
-__constant__ const double kNInvFact[kNDeg + 1] = {1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0, 1.0 / 40320.0};
-
-struct NoiseParams {
-    int n, nc, m, p, zdim, off_a, off_dt, n_int, chunk, n_chunks, nd;   // nd = m + (off_dt >= 0): derivatives per interval in grad_samples
-    long long items;             // S * n_chunks
-    double dt_fixed;
-    const double* img;           // A-layout images [matrix][kk][lane]: drift, m drives, p perturbations
-};
-
-template <int CTRL>
-__device__ inline double ndpp(double x) {
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ inline v4d nimg(const double* __restrict__ img, int mat, int lane) {
-    const double* p = img + (size_t)mat * 256 + lane;
-    return v4d{p[0], p[64], p[128], p[192]};
-}
-
-__device__ __forceinline__ v4d nmma(const v4d& a, const v4d& b, v4d acc) {
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], b[kk], acc, 0, 0, 0);
-    return acc;
-}
-
-// (R, dR) <- (A R + C,  dA R + A dR): gstep of qc_sweep_grad.hip
-__device__ __forceinline__ void nstep(const v4d& A, const v4d& dA, v4d& R, v4d& dR, const v4d& C) {
-    const v4d z = {0.0, 0.0, 0.0, 0.0};
-    v4d a0 = z, a1 = z, a2 = C;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-        a0 = __builtin_amdgcn_mfma_f64_16x16x4f64(dA[kk], R[kk], a0, 0, 0, 0);
-        a1 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[kk], dR[kk], a1, 0, 0, 0);
-        a2 = __builtin_amdgcn_mfma_f64_16x16x4f64(A[kk], R[kk], a2, 0, 0, 0);
-    }
-    dR = a0 + a1;
-    R = a2;
-}
-
-// the sum over the 64 lanes in a fixed order, wave-uniform: wave_sum of qc_sweep_grad.hip
-__device__ inline double nwave_sum(double v) {
-    v += ndpp<0x128>(v);
-    v += ndpp<0x124>(v);
-    v += ndpp<0x122>(v);
-    v += ndpp<0x121>(v);
-    return (bcast_lane(v, 0) + bcast_lane(v, 16)) + (bcast_lane(v, 32) + bcast_lane(v, 48));
-}
-
-// the number of squarings of the interval: the rule of qc_sweep_mfma16_kernel, expression for expression
-__device__ __forceinline__ int nsquarings(double h, const v4d& Ga) {
-    int sq = 0;
-    double best = 0.0;
-    bool bad = false;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-        double cs = fabs(h * Ga[kk]);
-        cs += ndpp<0x128>(cs);
-        cs += ndpp<0x124>(cs);
-        cs += ndpp<0x122>(cs);
-        cs += ndpp<0x121>(cs);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const double v = bcast_lane(cs, 16 * r);
-            if (!(v == v) || v > 1e300) bad = true;
-            best = fmax(best, v);
-        }
-    }
-    if (!bad && best > kNTh) {
-        int e;
-        (void)frexp(best / kNTh, &e);
-        sq = e;
-        if (ldexp(kNTh, e - 1) >= best) sq = e - 1;
-        sq = sq < 0 ? 0 : (sq > 60 ? 60 : sq);
-    }
-    return __builtin_amdgcn_readfirstlane(sq);
-}
 
 // Where lane l finds the coefficient of tile min(l, m + p - 1).  Drive lanes read the shared controls of knot t of Z, perturbation
 // lanes the sample's own noise of interval t; lanes past the last tile repeat the last one (p >= 1: there always is one).
@@ -135,7 +51,7 @@ struct LaneCoef {
     double cl;           // c[s,k] for a drive lane, 1 for a perturbation lane
 };
 
-__device__ __forceinline__ LaneCoef lane_coef(const NoiseParams& P, int lane, long long s, const double* __restrict__ scale) {
+__device__ __forceinline__ LaneCoef lane_coef(const SweepParams& P, int lane, long long s, const double* __restrict__ scale) {
     const int m = P.m, mt = m + P.p;
     const int kl = lane < mt ? lane : mt - 1;
     LaneCoef c;
@@ -152,14 +68,14 @@ __device__ __forceinline__ double lane_load(const LaneCoef& c, const double* __r
 
 // Launch 1: the chunk totals.  qc_sweep_mfma16_kernel with m + p tiles and the per-lane coefficient source.
 template <int M>
-__global__ __launch_bounds__(64 * kNWaves, 2) void qc_sweep_noise_kernel(const NoiseParams P, const double* __restrict__ Z,
+__global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_noise_kernel(const SweepParams P, const double* __restrict__ Z,
                                                                           const double* __restrict__ theta, const double* __restrict__ scale,
                                                                           const double* __restrict__ noise, double* __restrict__ tot) {
-    __shared__ double scr_all[kNWaves * 16 * 17];
+    __shared__ double scr_all[kWaves * kTile];
     const int lane = threadIdx.x & 63;
     const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * (16 * 17);
-    const long long item = (long long)blockIdx.x * kNWaves + wq;
+    double* __restrict__ scr = scr_all + wq * kTile;
+    const long long item = (long long)blockIdx.x * kWaves + wq;
     if (item >= P.items) return;
     const long long s = item / P.n_chunks;
     const int c = (int)(item - s * P.n_chunks);
@@ -171,16 +87,9 @@ __global__ __launch_bounds__(64 * kNWaves, 2) void qc_sweep_noise_kernel(const N
     const v4d zero = {0.0, 0.0, 0.0, 0.0};
 
     // ---- once per wave: the sample's base tile, the drive and perturbation tiles --------------------------------------------
-    v4d base = nimg(P.img, 0, lane);
-    for (int q = 0; q < P.p; ++q) {
-        const double th = theta[s * P.p + q];
-        const v4d Pq = nimg(P.img, 1 + m + q, lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) base[r] = fma(th, Pq[r], base[r]);
-    }
+    const v4d base = base_tile(P.img, m, P.p, theta, s, lane);
     v4d Gj[M];      // the images follow one another: tile u is matrix 1 + u, drives then perturbations
-#pragma unroll
-    for (int u = 0; u < M; ++u) Gj[u] = u < mt ? nimg(P.img, 1 + u, lane) : zero;
+    resident_tiles(P.img, mt, lane, Gj);
     const LaneCoef lc = lane_coef(P, lane, s, scale);
     const double* __restrict__ ns = noise + s * P.n_int * (long long)P.p;      // the sample's noise
 
@@ -197,25 +106,19 @@ __global__ __launch_bounds__(64 * kNWaves, 2) void qc_sweep_noise_kernel(const N
         const double av_n = lane_load(lc, zn, ns + (long long)tn * P.p);
         const double h_n = ft ? zn[P.off_dt] : hfix;
         const double al = av * lc.cl;
-        v4d Ga = base;
-#pragma unroll
-        for (int u = 0; u < M; ++u) {
-            const double a = u < mt ? bcast_lane(al, u) : 0.0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Ga[r] = fma(a, Gj[u][r], Ga[r]);
-        }
-        const int sq = nsquarings(h, Ga);
+        const v4d Ga = generator(base, Gj, mt, al);
+        const int sq = squarings(h, Ga);
         const double sc = ldexp(1.0, -sq);
         const v4d Y = (h * sc) * Ga;
-        v4d R = kNInvFact[kNDeg] * IdB;
+        v4d R = kInvFact[kDeg] * IdB;
 #pragma unroll 1
-        for (int k = kNDeg; k >= 1; --k) R = nmma(Y, R, kNInvFact[k - 1] * IdB);
+        for (int k = kDeg; k >= 1; --k) R = mma16(Y, R, kInvFact[k - 1] * IdB);
         for (int q = 0; q < sq; ++q) {
             const v4d Et = lds_transpose16(scr, R, g, j);
-            R = nmma(Et, R, zero);
+            R = mma16(Et, R, zero);
         }
         const v4d Et = lds_transpose16(scr, R, g, j);     // E^T in D layout = E in A layout
-        W = nmma(Et, W, zero);
+        W = mma16(Et, W, zero);
         av = av_n;
         h = h_n;
     }
@@ -227,16 +130,16 @@ __global__ __launch_bounds__(64 * kNWaves, 2) void qc_sweep_noise_kernel(const N
 // Launch 3: the backward walk.  qc_sweep_grad_kernel<M, false> with m + p tiles; gs (S x (T-1) x nd) and gn (S x (T-1) x p) may each be
 // NULL, not both.
 template <int M>
-__global__ __launch_bounds__(64 * kNWaves, 2) void qc_sweep_noise_grad_kernel(const NoiseParams P, const double* __restrict__ Z,
+__global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_noise_grad_kernel(const SweepParams P, const double* __restrict__ Z,
                                                                                const double* __restrict__ theta, const double* __restrict__ scale,
                                                                                const double* __restrict__ noise, const double* __restrict__ xs,
                                                                                const double* __restrict__ ls, double* __restrict__ gs,
                                                                                double* __restrict__ gn) {
-    __shared__ double scr_all[kNWaves * kNGSlice];
+    __shared__ double scr_all[kWaves * kWalkSlice<false>];
     const int lane = threadIdx.x & 63;
     const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kNGSlice;
-    const long long item = (long long)blockIdx.x * kNWaves + wq;
+    double* __restrict__ scr = scr_all + wq * kWalkSlice<false>;
+    const long long item = (long long)blockIdx.x * kWaves + wq;
     if (item >= P.items) return;
     const long long s = item / P.n_chunks;
     const int c = (int)(item - s * P.n_chunks);
@@ -247,16 +150,9 @@ __global__ __launch_bounds__(64 * kNWaves, 2) void qc_sweep_noise_grad_kernel(co
     const v4d IdB = identity_B(g, j);
     const v4d zero = {0.0, 0.0, 0.0, 0.0};
 
-    v4d base = nimg(P.img, 0, lane);
-    for (int q = 0; q < P.p; ++q) {
-        const double th = theta[s * P.p + q];
-        const v4d Pq = nimg(P.img, 1 + m + q, lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) base[r] = fma(th, Pq[r], base[r]);
-    }
+    const v4d base = base_tile(P.img, m, P.p, theta, s, lane);
     v4d Gj[M];
-#pragma unroll
-    for (int u = 0; u < M; ++u) Gj[u] = u < mt ? nimg(P.img, 1 + u, lane) : zero;
+    resident_tiles(P.img, mt, lane, Gj);
     const LaneCoef lc = lane_coef(P, lane, s, scale);
     const double* __restrict__ ns = noise + s * P.n_int * (long long)P.p;      // the sample's noise
 
@@ -286,14 +182,14 @@ __global__ __launch_bounds__(64 * kNWaves, 2) void qc_sweep_noise_grad_kernel(co
         const double av_n = lane_load(lc, zn, ns + (long long)tn * P.p);
         const double h_n = ft ? zn[P.off_dt] : hfix;
         const double al = av * lc.cl;
-        v4d Ga = base;
+        v4d Ga = base;      // qc_sweep16::generator written out: through the call <6> spills two scalar registers
 #pragma unroll
         for (int u = 0; u < M; ++u) {
             const double a = u < mt ? bcast_lane(al, u) : 0.0;
 #pragma unroll
             for (int r = 0; r < 4; ++r) Ga[r] = fma(a, Gj[u][r], Ga[r]);
         }
-        const int sq = nsquarings(h, Ga);
+        const int sq = squarings(h, Ga);
         const double hs = h * ldexp(1.0, -sq);
         // K^T = lambda x^T of knot t+1 (D layout) from the A-layout forms of both
         v4d KT;
@@ -301,7 +197,7 @@ __global__ __launch_bounds__(64 * kNWaves, 2) void qc_sweep_noise_grad_kernel(co
             const v4d in[2] = {x, lam};
             v4d tr[2];
             lds_transpose16_multi<2>(scr, in, tr, g, j);
-            KT = nmma(tr[1], tr[0], zero);
+            KT = mma16(tr[1], tr[0], zero);
         }
         // M = 8: the lane compares are made per interval from an opaque copy of the lane index (qc_sweep_grad_kernel: kept loop-invariant
         // they live in scalar registers and the kernel spills)
@@ -312,50 +208,40 @@ __global__ __launch_bounds__(64 * kNWaves, 2) void qc_sweep_noise_grad_kernel(co
             double ph = 0.0;
 #pragma unroll
             for (int r = 0; r < 4; ++r) ph = fma(KT[r], Ga[r], ph);
-            const double dh = -nwave_sum(ph);
+            const double dh = -wave_sum(ph);
             out = ln == mt ? dh : out;
         }
         const v4d Y = hs * Ga;
         const v4d dY = hs * KT;
-        v4d R = kNInvFact[kNDeg] * IdB;
+        v4d R = kInvFact[kDeg] * IdB;
         v4d dR = zero;
 #pragma unroll 1
-        for (int k = kNDeg; k >= 1; --k) nstep(Y, dY, R, dR, kNInvFact[k - 1] * IdB);
+        for (int k = kDeg; k >= 1; --k) step16(Y, dY, R, dR, kInvFact[k - 1] * IdB);
         for (int q = 0; q < sq; ++q) {
             const v4d in[2] = {R, dR};
             v4d tr[2];
             lds_transpose16_multi<2>(scr, in, tr, g, j);      // E^T, dE^T in D layout = E, dE in A layout
-            nstep(tr[0], tr[1], R, dR, zero);
+            step16(tr[0], tr[1], R, dR, zero);
         }
-        const v4d ZT = nmma(R, dR, zero);                       // E^T dE
+        const v4d ZT = mma16(R, dR, zero);                       // E^T dE
 #pragma unroll
         for (int u = 0; u < M; ++u) {
             if (u < mt) {
                 double pu = 0.0;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) pu = fma(ZT[r], Gj[u][r], pu);
-                const double du = nwave_sum(pu);
+                const double du = wave_sum(pu);
                 out = ln == u ? du * lc.cl : out;      // a perturbation lane's factor is 1
             }
         }
         const long long it = s * P.n_int + t;
         if (gs && (ln < m || (ft && ln == mt))) gs[it * P.nd + (ln < m ? ln : m)] = out;
         if (gn && ln >= m && ln < mt) gn[it * P.p + (ln - m)] = out;
-        x = nmma(R, x, zero);
-        lam = nmma(R, lam, zero);
+        x = mma16(R, x, zero);
+        lam = mma16(R, lam, zero);
         av = av_n;
         h = h_n;
     }
-}
-
-NoiseParams noise_params(const qc_sweep* h, int64_t S, int64_t chunk, int64_t n_chunks) {
-    NoiseParams P;
-    P.n = h->n; P.nc = h->nc; P.m = h->d.m; P.p = h->d.n_pert; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
-    P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks; P.nd = h->d.m + (h->d.off_dt >= 0 ? 1 : 0);
-    P.items = S * n_chunks;
-    P.dt_fixed = h->d.dt_fixed;
-    P.img = h->dImg;
-    return P;
 }
 
 // launch 1: grows h->dTot and launches qc_sweep_noise_kernel<M> (S x n_chunks tiles of 256 doubles, the layout of qc_sweep_launch_totals)
@@ -365,9 +251,9 @@ int noise_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* 
     int64_t chunk, n_chunks;
     qc_sweep_chunks(S, h->d.T, &chunk, &n_chunks);
     QC_SIDE_HIP(h, slot, h->grow(h->dTot, (size_t)S * n_chunks * 256));
-    const NoiseParams P = noise_params(h, S, chunk, n_chunks);
-    const unsigned grid = (unsigned)((P.items + kNWaves - 1) / kNWaves);
-#define QC_NOISE_LAUNCH(M_) hipLaunchKernelGGL(qc_sweep_noise_kernel<M_>, dim3(grid), dim3(64 * kNWaves), 0, st, P, dZ, dtheta, dscale, dnoise, h->dTot.p)
+    const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
+    const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
+#define QC_NOISE_LAUNCH(M_) hipLaunchKernelGGL(qc_sweep_noise_kernel<M_>, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, dnoise, h->dTot.p)
     QC_SWEEP_FOR_M(P.m + P.p, QC_NOISE_LAUNCH);
 #undef QC_NOISE_LAUNCH
     *chunk_out = chunk;
@@ -436,7 +322,7 @@ int noise_grad_launch(qc_sweep* h, const char* who, const double* dZ, const doub
     hipStream_t st = (hipStream_t)stream;
     int64_t chunk, n_chunks;
     if ((rc = noise_launch_totals(h, dZ, S, dtheta, dscale, dnoise, st, &chunk, &n_chunks))) return rc;
-    const NoiseParams P = noise_params(h, S, chunk, n_chunks);
+    const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
     const size_t n_state = (size_t)S * n_chunks * h->ns;
     QC_SIDE_HIP(h, slot, h->grow(h->dXs, n_state));
     QC_SIDE_HIP(h, slot, h->grow(h->dLs, n_state));
@@ -452,10 +338,10 @@ int noise_grad_launch(qc_sweep* h, const char* who, const double* dZ, const doub
     }
     qc_sweep_launch_fid_seed(h, S, n_chunks, dinit, dfids, st);
     if (want_grad || dgrad_noise) {
-        const unsigned grid = (unsigned)((P.items + kNWaves - 1) / kNWaves);
+        const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
         double* gs = want_grad ? gsamp : nullptr;
 #define QC_NOISE_GRAD_LAUNCH(M_)                                                                                                         \
-    hipLaunchKernelGGL(qc_sweep_noise_grad_kernel<M_>, dim3(grid), dim3(64 * kNWaves), 0, st, P, dZ, dtheta, dscale, dnoise,               \
+    hipLaunchKernelGGL(qc_sweep_noise_grad_kernel<M_>, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, dnoise,               \
                        (const double*)h->dXs.p, (const double*)h->dLs.p, gs, dgrad_noise)
         QC_SWEEP_FOR_M(P.m + P.p, QC_NOISE_GRAD_LAUNCH);
 #undef QC_NOISE_GRAD_LAUNCH

@@ -44,25 +44,24 @@
 #include <string>
 
 #include "qc_mfma_common.h"
+#include "qc_sweep16_common.h"
 #include "qc_sweep_internal.h"
-#include "qc_sweep_walk.h"
 
 namespace {
 
-using namespace qc_mfma;
-using namespace qc_sweep_walk;
+using namespace qc_sweep16;
 
 // x_t of every knot of the chunk, t = t0 .. t1-1, from the chunk-start state
 template <int M>
-__global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_open_store_kernel(const GradParams P, const double* __restrict__ Z,
+__global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_open_store_kernel(const SweepParams P, const double* __restrict__ Z,
                                                                                const double* __restrict__ theta, const double* __restrict__ scale,
                                                                                const double* __restrict__ init, const double* __restrict__ xs,
                                                                                double* __restrict__ xall) {
-    __shared__ double scr_all[kGWaves * 16 * 17];
+    __shared__ double scr_all[kWaves * kTile];
     const int lane = threadIdx.x & 63;
     const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * (16 * 17);
-    const long long item = (long long)blockIdx.x * kGWaves + wq;
+    double* __restrict__ scr = scr_all + wq * kTile;
+    const long long item = (long long)blockIdx.x * kWaves + wq;
     if (item >= P.items) return;
     const long long s = item / P.n_chunks;
     const int c = (int)(item - s * P.n_chunks);
@@ -74,16 +73,9 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_open_store_kernel(co
     const v4d zero = {0.0, 0.0, 0.0, 0.0};
     const int ns = P.n * P.nc;
 
-    v4d base = gimg(P.img, 0, lane);
-    for (int q = 0; q < P.p; ++q) {
-        const double th = theta[s * P.p + q];
-        const v4d Pq = gimg(P.img, 1 + m + q, lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) base[r] = fma(th, Pq[r], base[r]);
-    }
+    const v4d base = base_tile(P.img, m, P.p, theta, s, lane);
     v4d Gj[M];
-#pragma unroll
-    for (int u = 0; u < M; ++u) Gj[u] = u < m ? gimg(P.img, 1 + u, lane) : zero;
+    resident_tiles(P.img, m, lane, Gj);
     const int kl = lane < m ? lane : (m > 0 ? m - 1 : 0);
     const double cl = (scale && m > 0) ? scale[s * m + kl] : 1.0;
 
@@ -113,24 +105,18 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_open_store_kernel(co
         const double av_n = m > 0 ? zn[P.off_a + kl] : 0.0;
         const double h_n = ft ? zn[P.off_dt] : hfix;
         const double al = av * cl;
-        v4d Ga = base;
-#pragma unroll
-        for (int u = 0; u < M; ++u) {
-            const double a = u < m ? bcast_lane(al, u) : 0.0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Ga[r] = fma(a, Gj[u][r], Ga[r]);
-        }
+        const v4d Ga = generator(base, Gj, m, al);
         const int sq = squarings(h, Ga);
         const v4d Y = (h * ldexp(1.0, -sq)) * Ga;
-        v4d R = kGInvFact[kGDeg] * IdB;
+        v4d R = kInvFact[kDeg] * IdB;
 #pragma unroll 1
-        for (int k = kGDeg; k >= 1; --k) R = gmma(Y, R, kGInvFact[k - 1] * IdB);
+        for (int k = kDeg; k >= 1; --k) R = mma16(Y, R, kInvFact[k - 1] * IdB);
         for (int q = 0; q < sq; ++q) {
             const v4d Et = lds_transpose16(scr, R, g, j);
-            R = gmma(Et, R, zero);
+            R = mma16(Et, R, zero);
         }
         const v4d Et = lds_transpose16(scr, R, g, j);     // E^T in D layout = E in A layout
-        x = gmma(Et, x, zero);
+        x = mma16(Et, x, zero);
         av = av_n;
         h = h_n;
     }
@@ -148,16 +134,16 @@ __device__ __forceinline__ v4d load_xT(const double* __restrict__ xp, int n4, in
 // One wavefront per (sample, chunk), walking the chunk backwards on the stored states.  The flavours and `part` / `gs` as
 // qc_sweep_grad_kernel (qc_sweep_grad.hip).
 template <int M, bool PAR = false>
-__global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_open_grad_kernel(const GradParams P, const double* __restrict__ Z,
+__global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_open_grad_kernel(const SweepParams P, const double* __restrict__ Z,
                                                                               const double* __restrict__ theta, const double* __restrict__ scale,
                                                                               const double* __restrict__ xall, const double* __restrict__ ls,
                                                                               double* __restrict__ gs, double* __restrict__ part) {
     constexpr bool kTight = M >= 6 || PAR;      // the flavours whose loop-invariant lane masks do not fit the scalar registers
-    __shared__ double scr_all[kGWaves * kGSlice<PAR>];
+    __shared__ double scr_all[kWaves * kWalkSlice<PAR>];
     const int lane = threadIdx.x & 63;
     const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kGSlice<PAR>;
-    const long long item = (long long)blockIdx.x * kGWaves + wq;
+    double* __restrict__ scr = scr_all + wq * kWalkSlice<PAR>;
+    const long long item = (long long)blockIdx.x * kWaves + wq;
     if (item >= P.items) return;
     const long long s = item / P.n_chunks;
     const int c = (int)(item - s * P.n_chunks);
@@ -170,16 +156,9 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_open_grad_kernel(con
     const int ns = P.n * P.nc;
 
     // ---- once per wave: the sample's base tile, the drive tiles, the adjoint at the chunk's end ------------------------------------
-    v4d base = gimg(P.img, 0, lane);
-    for (int q = 0; q < P.p; ++q) {
-        const double th = theta[s * P.p + q];
-        const v4d Pq = gimg(P.img, 1 + m + q, lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) base[r] = fma(th, Pq[r], base[r]);
-    }
+    const v4d base = base_tile(P.img, m, P.p, theta, s, lane);
     v4d Gj[M];
-#pragma unroll
-    for (int u = 0; u < M; ++u) Gj[u] = u < m ? gimg(P.img, 1 + u, lane) : zero;
+    resident_tiles(P.img, m, lane, Gj);
     const int kl = lane < m ? lane : (m > 0 ? m - 1 : 0);
     const double cl = (scale && m > 0) ? scale[s * m + kl] : 1.0;
 
@@ -210,7 +189,7 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_open_grad_kernel(con
     double* gp = gs + (s * P.n_int + (t1 - 1)) * P.nd + lane;
     const int stl = (gs && lane < P.nd) ? 1 : 0;
     // PAR: the accumulators of qc_sweep_grad_kernel, at the same places of the wave's LDS slice
-    double* accl = scr + 2 * 272;
+    double* accl = scr + 2 * kTile;
     if constexpr (PAR) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) accl[64 * r + lane] = 0.0;
@@ -223,18 +202,12 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_open_grad_kernel(con
         const double h_n = ft ? ap[dto] : hfix;
         const double al = av * cl;
         if constexpr (PAR) accl[256 + lane] = av;
-        v4d Ga = base;
-#pragma unroll
-        for (int u = 0; u < M; ++u) {
-            const double a = u < m ? bcast_lane(al, u) : 0.0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Ga[r] = fma(a, Gj[u][r], Ga[r]);
-        }
+        const v4d Ga = generator(base, Gj, m, al);
         const int sq = squarings(h, Ga);
         const double sc = ldexp(1.0, -sq);
         // KT = lambda_{t+1} x_t^T (D layout): as an A operand it acts as K^T = x_t lambda^T, the direction of the chain on hG
         const v4d lamA = lds_transpose16(scr, lam, g, j);
-        const v4d KT = gmma(lamA, xT, zero);
+        const v4d KT = mma16(lamA, xT, zero);
         // the state of the interval below is requested before this interval's chain
         {
             int ok = okx;      // likewise the four masks of the state's padding
@@ -244,15 +217,15 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_open_grad_kernel(con
         }
         const v4d Y = (h * sc) * Ga;
         const v4d dY = sc * KT;
-        v4d R = kGInvFact[kGDeg] * IdB;
+        v4d R = kInvFact[kDeg] * IdB;
         v4d dR = zero;
 #pragma unroll 1
-        for (int k = kGDeg; k >= 1; --k) gstep(Y, dY, R, dR, kGInvFact[k - 1] * IdB);
+        for (int k = kDeg; k >= 1; --k) step16(Y, dY, R, dR, kInvFact[k - 1] * IdB);
         for (int q = 0; q < sq; ++q) {
             const v4d in[2] = {R, dR};
             v4d tr[2];
             lds_transpose16_multi<2>(scr, in, tr, g, j);      // E^T, dE^T in D layout = E, dE in A layout
-            gstep(tr[0], tr[1], R, dR, zero);
+            step16(tr[0], tr[1], R, dR, zero);
         }
         // dR = L(hG; K^T) = L(hG^T; K)^T: against an A-layout tile it is its own transpose
         int ln = lane;      // as in qc_sweep_grad_kernel: the lane compares are made per interval, not kept in scalar registers
@@ -291,7 +264,7 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_open_grad_kernel(con
             if (st) *gp = out;
             gp -= P.nd;
         }
-        lam = gmma(R, lam, zero);
+        lam = mma16(R, lam, zero);
         av = av_n;
         h = h_n;
     }
@@ -301,7 +274,7 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_open_grad_kernel(con
         for (int r = 0; r < 4; ++r) Acc[r] = accl[64 * r + lane];
         double acc_t = 0.0;
         for (int q = 0; q < P.p; ++q) {
-            const v4d Pq = gimg(P.img, 1 + m + q, lane);
+            const v4d Pq = image_tile(P.img, 1 + m + q, lane);
             double pq = 0.0;
 #pragma unroll
             for (int r = 0; r < 4; ++r) pq = fma(Acc[r], Pq[r], pq);
@@ -318,27 +291,20 @@ __global__ __launch_bounds__(64 * kGWaves, 2) void qc_sweep_open_grad_kernel(con
 
 void qc_sweep_open_launch_walk(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
                                int64_t chunk, int64_t n_chunks, double* gs, bool want_par, double* dgrad_theta, double* dgrad_scale, hipStream_t st) {
-    const int m = h->d.m, p = h->d.n_pert;
-    const int nd = m + (h->d.off_dt >= 0 ? 1 : 0);
-    GradParams P;
-    P.n = h->n; P.nc = h->nc; P.m = m; P.p = p; P.zdim = h->d.zdim; P.off_a = h->d.off_a; P.off_dt = h->d.off_dt;
-    P.n_int = (int)(h->d.T - 1); P.chunk = (int)chunk; P.n_chunks = (int)n_chunks; P.nd = nd;
-    P.items = S * n_chunks;
-    P.dt_fixed = h->d.dt_fixed;
-    P.img = h->dImg;
-    const unsigned grid = (unsigned)((P.items + kGWaves - 1) / kGWaves);
+    const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
+    const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
 #define QC_OPEN_LAUNCH(M_)                                                                                                                      \
     do {                                                                                                                                        \
-        hipLaunchKernelGGL(qc_sweep_open_store_kernel<M_>, dim3(grid), dim3(64 * kGWaves), 0, st, P, dZ, dtheta, dscale, dinit,                  \
+        hipLaunchKernelGGL(qc_sweep_open_store_kernel<M_>, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, dinit,                  \
                            (const double*)h->dXs.p, h->dXall.p);                                                                                \
         if (want_par)                                                                                                                           \
-            hipLaunchKernelGGL((qc_sweep_open_grad_kernel<M_, true>), dim3(grid), dim3(64 * kGWaves), 0, st, P, dZ, dtheta, dscale,               \
+            hipLaunchKernelGGL((qc_sweep_open_grad_kernel<M_, true>), dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale,               \
                                (const double*)h->dXall.p, (const double*)h->dLs.p, gs, h->dPart.p);                                             \
         else                                                                                                                                    \
-            hipLaunchKernelGGL((qc_sweep_open_grad_kernel<M_, false>), dim3(grid), dim3(64 * kGWaves), 0, st, P, dZ, dtheta, dscale,              \
+            hipLaunchKernelGGL((qc_sweep_open_grad_kernel<M_, false>), dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale,              \
                                (const double*)h->dXall.p, (const double*)h->dLs.p, gs, (double*)nullptr);                                       \
     } while (0)
-    QC_SWEEP_FOR_M(m, QC_OPEN_LAUNCH);
+    QC_SWEEP_FOR_M(P.m, QC_OPEN_LAUNCH);
 #undef QC_OPEN_LAUNCH
     if (want_par) qc_sweep_launch_par_reduce(h, S, n_chunks, dgrad_theta, dgrad_scale, st);
 }

@@ -204,8 +204,8 @@ def test_spread_rows_make_waves_diverge(qc, name):
     spans = [(t0, min(T - 1, t0 + chunk)) for t0 in range(0, T - 1, chunk)]
     assert len(spans) == n_chunks
     assert max(len(set(sq[r, a:b].tolist())) for r in range(R) for a, b in spans) >= 3
-    # the walk's workgroups: the counts of their waves, step by step from the chunk's end.  4 restates kGWaves (qc_sweep_walk.h) and kWaves
-    # (qc_sweep32_common.h); 2 restates kOW<true> of qc_sweep32_open_grad.hip, the parameter flavour of the wide walk (wide = 11)
+    # the walk's workgroups: the counts of their waves, step by step from the chunk's end.  4 restates kWaves (qc_sweep_common.h, both
+    # forms); 2 restates kOW<true> of qc_sweep32_open_grad.hip, the parameter flavour of the wide walk (wide = 11)
     cls = tes.classes(S)
     for waves in ((2, 4) if 11 in CASES[name][6] else (4,)):
         seq = [tuple(sq[cls[item // n_chunks], spans[item % n_chunks][0]:spans[item % n_chunks][1]][::-1]) for item in range(S * n_chunks)]
