@@ -633,8 +633,12 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * stored-state walk on 2 x 2 tiles (below); without reserved1[0], or where the handle takes another form, the bit does nothing.  Bit 4,
  * QC_SWEEP_WIDE_TANGENT (wide = 17, 19, 25 or 27), likewise changes one thing only: an "mfma32-sweep" handle then serves the pushforward
  * (qc_sweep_jvp*, below) with any generators; the forward sweep, gradients, pullbacks, the launch and the kernel name are untouched, and
- * where the handle takes another form the bit does nothing.  The valid values are 0, 1, 3, 9, 11, 17, 19, 25 and 27; any other value
- * (bit 1, 3 or 4 without bit 0, bit 2, 5 and 7 among them) is QC_ERR_INVALID.
+ * where the handle takes another form the bit does nothing.  Bit 6, QC_SWEEP_WIDE_NOISE (any of the odd values | 64), likewise changes
+ * one thing only: an "mfma32-sweep" handle then serves the noise-trajectory sweeps and their gradients (qc_sweep_noise_*, below); form,
+ * launch, kernel name, every other *_supported answer and every other entry point's output are bit-identical to the same descriptor
+ * without the bit, and where the handle takes another form (2N <= 16 with its own noise kernels and tile rule, rollout-per-sample) the bit
+ * does nothing.  The valid values are 0, 1, 3, 9, 11, 17, 19, 25 and 27, and each of the eight odd ones | 64 (65 .. 91);
+ * any other value (bit 1, 3, 4 or 6 without bit 0, bit 2, 5 and 7 among them) is QC_ERR_INVALID.
  * reserved1[0] = QC_SWEEP_STORED_STATES chooses reverse mode by the STORED-STATE walk: qc_sweep_grad*, qc_sweep_grad_params* and
  * qc_sweep_vjp* then keep the forward states x_0 .. x_{T-2} of every sample in handle scratch (S x (T-1) x 2N x cols doubles) and read
  * them on the way back instead of reversing the step, which serves ANY generators in the "mfma16-sweep" form: Lindblad generators
@@ -656,6 +660,8 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * included (no flag, no state buffer: nothing is reversed); with the pullback it gives Gauss-Newton products of any loss.
  * The tangent of the pullback along one direction (qc_sweep_hvp*, below) gives exact Hessian products of any loss of the final states
  * where both of them are served (closed systems, "mfma16-sweep").
+ * Noise-trajectory sweeps (qc_sweep_noise_*, below) are served for "mfma16-sweep" handles, and for "mfma32-sweep" handles whose `wide` has
+ * QC_SWEEP_WIDE_NOISE.
  * Out of scope: per-knot outputs, open-system gradients in the "mfma32-sweep" form without QC_SWEEP_WIDE_STORED (their directional
  * derivatives are not served there at all), checkpointing inside a chunk, Hessian products and noise gradients of open
  * systems, pushforwards on "mfma32-sweep" and "rollout-per-sample" handles (the former unless `wide` has QC_SWEEP_WIDE_TANGENT; Hessian
@@ -667,6 +673,7 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
 #define QC_SWEEP_WIDE_PARAMS 2   /* qc_sweep_desc.wide, bit 1: the mfma32-sweep form serves parameter gradients and parameter cotangents; only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_WIDE_STORED 8   /* qc_sweep_desc.wide, bit 3: the mfma32-sweep form serves the stored-state walk; only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_WIDE_TANGENT 16 /* qc_sweep_desc.wide, bit 4: the mfma32-sweep form serves pushforwards (qc_sweep_jvp*); only together with QC_SWEEP_WIDE */
+#define QC_SWEEP_WIDE_NOISE 64   /* qc_sweep_desc.wide, bit 6: the mfma32-sweep form serves noise-trajectory sweeps and their gradients (qc_sweep_noise_*); only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_STORED_STATES 1 /* qc_sweep_desc.reserved1[0]: reverse mode by the stored-state walk */
 typedef struct qc_sweep_desc {
     int64_t T;
@@ -688,7 +695,7 @@ typedef struct qc_sweep_desc {
     const double* goal_iso;      /* as qc_fidelity_desc.goal_iso */
     const int32_t* subspace;     /* unitary only: 0-based levels, or NULL = all */
     int32_t device;
-    int32_t wide;                /* bit field; valid: 0, QC_SWEEP_WIDE (1): the matrix-core form up to 2N = 32 ("mfma32-sweep"), or QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS (3): that form, and qc_sweep_grad_params* / the grad_theta, grad_scale of qc_sweep_vjp* are served in it (form, launch, kernel name and every *_supported answer as with 1; harmless where the handle takes another form); either of them | QC_SWEEP_WIDE_STORED (9, 11): that form also serves reverse mode by the stored-state walk when reserved1[0] = QC_SWEEP_STORED_STATES (nothing else changes); anything else is QC_ERR_INVALID */
+    int32_t wide;                /* bit field; valid: 0, QC_SWEEP_WIDE (1): the matrix-core form up to 2N = 32 ("mfma32-sweep"), or QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS (3): that form, and qc_sweep_grad_params* / the grad_theta, grad_scale of qc_sweep_vjp* are served in it (form, launch, kernel name and every *_supported answer as with 1; harmless where the handle takes another form); either of them | QC_SWEEP_WIDE_STORED (9, 11): that form also serves reverse mode by the stored-state walk when reserved1[0] = QC_SWEEP_STORED_STATES (nothing else changes); any of those | QC_SWEEP_WIDE_TANGENT (17, 19, 25, 27): that form also serves qc_sweep_jvp*; any of the eight | QC_SWEEP_WIDE_NOISE (64): that form also serves qc_sweep_noise_*; anything else is QC_ERR_INVALID */
     int64_t reserved1[2];        /* [0]: 0, or QC_SWEEP_STORED_STATES: reverse mode reads stored forward states (any generators; "mfma16-sweep", and "mfma32-sweep" with QC_SWEEP_WIDE_STORED in `wide`); anything else is QC_ERR_INVALID.  [1]: ignored */
 } qc_sweep_desc;
 typedef struct qc_sweep qc_sweep;
@@ -877,15 +884,22 @@ int qc_sweep_hvp(qc_sweep* h, const double* Z, const double* init, int64_t S, co
  * noise: S x (T-1) x n_pert doubles, sample-major, then interval, then perturbation: noise[(s (T-1) + t) n_pert + j].  A detuning that
  * drifts during the pulse (Ornstein-Uhlenbeck, 1/f), additive noise on a drive line (P_j = G_k), S realisations of a stochastic
  * average: one call in place of S single-sample calls that each carry the noise in a Z of their own.  The handle is an ordinary
- * qc_sweep handle; the perturbation tiles sit in registers beside the drive tiles, their coefficients read per sample and interval.
+ * qc_sweep handle; in the "mfma16-sweep" form the perturbation tiles sit in registers beside the drive tiles, their coefficients read
+ * per sample and interval.  An "mfma32-sweep" handle (16 < 2N <= 32: two coupled three-level transmons with drifting detunings, a 4-qubit
+ * register, two qubits with T1 / T2 whose decay rate fluctuates) serves both entry-point families when its descriptor sets
+ * QC_SWEEP_WIDE_NOISE in `wide`: that form keeps no generator resident (every image is read again per interval), so the only limits
+ * there are m <= 8 and n_pert <= QC_MAX_PERT, up to 16 generators.  Every contract below holds in both forms.
  * At noise = +0.0 the outputs equal those of qc_sweep_eval / qc_sweep_grad on the same handle value for value (a -0.0 may come out
  * as +0.0, nothing else).
- * Out of scope: "mfma32-sweep" and "rollout-per-sample" handles; pullbacks, pushforwards and Hessian products with noise (and with
- * them the autograd function of the Python layer); several devices. */
-/* device-free: may the noise sweep serve this descriptor?  Scope of the evaluation: the "mfma16-sweep" form, n_pert >= 1,
- * m + n_pert <= 8, any generators (Lindblad ones included), any state_cols and fid_kind the sweep serves there.  When 0,
- * qc_sweep_last_error(NULL) says why, prefixed "qc_sweep noise: ": "... not served in the mfma32-sweep form", the rollout-per-sample
- * form with its cause, n_pert = 0, or m + n_pert > 8 with the two numbers.  An invalid descriptor returns its own error. */
+ * Out of scope: "mfma32-sweep" handles without QC_SWEEP_WIDE_NOISE and "rollout-per-sample" handles;
+ * pullbacks, pushforwards and Hessian products with noise (and with them the autograd function of the Python layer); noise gradients of
+ * open systems; several devices. */
+/* device-free: may the noise sweep serve this descriptor?  Scope of the evaluation: the "mfma16-sweep" form with n_pert >= 1 and
+ * m + n_pert <= 8, or the "mfma32-sweep" form of a descriptor whose `wide` has QC_SWEEP_WIDE_NOISE with n_pert >= 1 (no condition on
+ * m + n_pert); any generators (Lindblad ones included), any state_cols and fid_kind the sweep serves there.  When 0,
+ * qc_sweep_last_error(NULL) says why, prefixed "qc_sweep noise: ": "... not served in the mfma32-sweep form" (that form without the
+ * bit), the rollout-per-sample form with its cause, n_pert = 0, or ("mfma16-sweep") m + n_pert > 8 with the two numbers.  An invalid
+ * descriptor returns its own error. */
 int qc_sweep_desc_noise_supported(const qc_sweep_desc* d, int32_t* supported);
 /* The arguments and rules of qc_sweep_eval / qc_sweep_eval_dev, plus `noise` (required; it must not overlap an output:
  * QC_ERR_INVALID).  finals: S x (2N cols); fids: S; either may be NULL, not both.  Scratch, the one-in-flight rule and S in 1 .. 2^24

@@ -16,6 +16,7 @@ const LIB = Ref{String}(get(ENV, "QCOLLOC_HIP_LIB", "libqcolloc_hip.so"))
 const QC_MAX_DERIV = 8
 const QC_SWEEP_WIDE = 1            # qc_sweep_desc.wide, bit 0: the matrix-core form up to 2N = 32 ("mfma32-sweep")
 const QC_SWEEP_WIDE_TANGENT = 16   # qc_sweep_desc.wide, bit 4 (only with bit 0): pushforwards in that form
+const QC_SWEEP_WIDE_NOISE = 64     # qc_sweep_desc.wide, bit 6 (only with bit 0): noise-trajectory sweeps and their gradients in that form
 const QC_ABI_VERSION = 6      # QC_VERSION_MAJOR * 1000 + QC_VERSION_MINOR of the include/qcolloc.h these mirrors were written against
 
 # mirror of `qc_desc` (include/qcolloc.h); field order and types must match the header -- `__init__` checks the sizes against
@@ -804,16 +805,17 @@ end
 
 """
     rollout_noise_sweep(init, controls, Δt, G_drift, G_drives, G_pert, ξ; θ=nothing, scale=nothing, cols, goal=nothing, fid_kind=-1,
-                        subspace=nothing, squared=false, device=0)  ->  (finals, fids)
+                        subspace=nothing, squared=false, device=0, wide=false)  ->  (finals, fids)
 
 `rollout_sweep` with perturbation amplitudes that change from interval to interval (`qc_sweep_noise_eval`): in interval t sample s
 evolves under G_drift + Σ_j (θ[s, j] + ξ[j, t, s]) G_pert[j] + Σ_k scale[s, k] a_{t,k} G_drives[k].  `ξ` is p×(T-1)×S (the library's
-sample-major layout as a column-major array), `θ` S×p or nothing (zeros).  Served for 2N ≤ 16 with p ≥ 1 and m + p ≤ 8; everything else
-errors with the library's reason.  Other arguments as `rollout_sweep`.  UNTESTED here, like the rest of this file.
+sample-major layout as a column-major array), `θ` S×p or nothing (zeros).  Served for 2N ≤ 16 with p ≥ 1 and m + p ≤ 8; `wide = true` sets
+`qc_sweep_desc.wide = QC_SWEEP_WIDE | QC_SWEEP_WIDE_NOISE` (65): 16 < 2N ≤ 32 on the matrix cores with p ≥ 1, m ≤ 8 and no limit on
+m + p.  Everything else errors with the library's reason.  Other arguments as `rollout_sweep`.  UNTESTED here, like the rest of this file.
 """
 function rollout_noise_sweep(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift, G_drives,
                              G_pert, ξ::AbstractArray{Float64,3}; θ=nothing, scale=nothing, cols::Int, goal=nothing, fid_kind::Int=-1,
-                             subspace=nothing, squared::Bool=false, device::Int=0)
+                             subspace=nothing, squared::Bool=false, device::Int=0, wide::Bool=false)
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(ξ, 3)
     size(ξ) == (p, T - 1, S) || error("rollout_noise_sweep: ξ must be $p×$(T - 1)×S")
@@ -833,7 +835,7 @@ function rollout_noise_sweep(init::AbstractVector{Float64}, controls::AbstractMa
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
                                squared ? 1 : 0, length(sub), isempty(g) ? C_NULL : pointer(g), isempty(sub) ? C_NULL : pointer(sub),
-                               device, 0, (0, 0)))
+                               device, wide ? (QC_SWEEP_WIDE | QC_SWEEP_WIDE_NOISE) : 0, (0, 0)))
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_noise_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
         (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
@@ -851,16 +853,17 @@ end
 
 """
     rollout_noise_sweep_gradient(init, controls, Δt, G_drift, G_drives, G_pert, ξ; θ=nothing, scale=nothing, weights=nothing, cols, goal,
-                                 fid_kind=0, subspace=nothing, squared=false, device=0)  ->  (J, fids, ∇a, ∇Δt, ∇ξ)
+                                 fid_kind=0, subspace=nothing, squared=false, device=0, wide=false)  ->  (J, fids, ∇a, ∇Δt, ∇ξ)
 
 The adjoint of `rollout_noise_sweep` (`qc_sweep_noise_grad`): J, the S fidelities and the gradient of J over the controls and timesteps
 as `rollout_sweep_gradient` returns them, and `∇ξ[j, t, s]` = ∂F_s/∂ξ[j, t, s] (p×(T-1)×S, raw per-sample values): the time-resolved noise
-sensitivity of every sample.  Closed systems, `fid_kind` 0 (unitary) or 1 (ket), 2N ≤ 16, p ≥ 1, m + p ≤ 8.  UNTESTED here, like the
-rest of this file.
+sensitivity of every sample.  Closed systems, `fid_kind` 0 (unitary) or 1 (ket), 2N ≤ 16, p ≥ 1, m + p ≤ 8; `wide = true` sets
+`qc_sweep_desc.wide = QC_SWEEP_WIDE | QC_SWEEP_WIDE_NOISE` (65): 16 < 2N ≤ 32 with p ≥ 1, m ≤ 8, no limit on m + p.  UNTESTED here, like
+the rest of this file.
 """
 function rollout_noise_sweep_gradient(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift,
                                       G_drives, G_pert, ξ::AbstractArray{Float64,3}; θ=nothing, scale=nothing, weights=nothing, cols::Int,
-                                      goal, fid_kind::Int=0, subspace=nothing, squared::Bool=false, device::Int=0)
+                                      goal, fid_kind::Int=0, subspace=nothing, squared::Bool=false, device::Int=0, wide::Bool=false)
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(ξ, 3)
     size(ξ) == (p, T - 1, S) || error("rollout_noise_sweep_gradient: ξ must be $p×$(T - 1)×S")
@@ -883,7 +886,7 @@ function rollout_noise_sweep_gradient(init::AbstractVector{Float64}, controls::A
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
                                squared ? 1 : 0, length(sub), pointer(g), isempty(sub) ? C_NULL : pointer(sub),
-                               device, 0, (0, 0)))
+                               device, wide ? (QC_SWEEP_WIDE | QC_SWEEP_WIDE_NOISE) : 0, (0, 0)))
         rc = ccall((:qc_sweep_create, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Ptr{Cvoid}}), desc, h)
         rc == 0 || error("qc_sweep_create: " * unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
     end

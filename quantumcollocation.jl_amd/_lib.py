@@ -52,6 +52,7 @@ QC_SWEEP_WIDE = 1           # qc_sweep_desc.wide, bit 0: the matrix-core form up
 QC_SWEEP_WIDE_PARAMS = 2    # qc_sweep_desc.wide, bit 1 (only with bit 0): parameter gradients and cotangents in that form
 QC_SWEEP_WIDE_STORED = 8    # qc_sweep_desc.wide, bit 3 (only with bit 0): the stored-state walk in that form
 QC_SWEEP_WIDE_TANGENT = 16  # qc_sweep_desc.wide, bit 4 (only with bit 0): pushforwards in that form
+QC_SWEEP_WIDE_NOISE = 64  # qc_sweep_desc.wide, bit 6 (only with bit 0): noise-trajectory sweeps and their gradients in that form
 QC_SWEEP_STORED_STATES = 1  # qc_sweep_desc.reserved1[0]: reverse mode by the stored-state walk (open systems)
 QC_ROWS_STACKED = 0
 QC_ROWS_BY_COMPONENT = 1

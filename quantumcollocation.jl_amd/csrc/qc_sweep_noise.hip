@@ -25,7 +25,10 @@
 // Cost against the sweep at the same M: n_pert more fmas per tile register (4 n_pert) and the same single load per interval; the
 // gradient adds n_pert wave reductions per interval.
 //
-// Out of scope: "mfma32-sweep" and "rollout-per-sample" handles, pullbacks / pushforwards / Hessian products with noise, several devices.
+// "mfma32-sweep" handles whose descriptor sets QC_SWEEP_WIDE_NOISE are routed to the two kernels of qc_sweep32_noise.hip (the same lane
+// map on 2 x 2 tiles; nothing is resident there, so no tile limit); the checks, the staging and the entry points below are shared.
+//
+// Out of scope: "mfma32-sweep" handles without that bit and "rollout-per-sample" handles, pullbacks / pushforwards / Hessian products with noise, several devices.
 //
 // gfx950 cross-compile: see the table in DESIGN.md ("Noise-trajectory sweeps"); no private segment, no spills in any instantiation.
 #include <math.h>
@@ -247,6 +250,7 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_noise_grad_kernel(con
 // launch 1: grows h->dTot and launches qc_sweep_noise_kernel<M> (S x n_chunks tiles of 256 doubles, the layout of qc_sweep_launch_totals)
 int noise_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dnoise, hipStream_t st,
                         int64_t* chunk_out, int64_t* n_chunks_out) {
+    if (h->wide_noise) return qc_sweep32_noise_launch_totals(h, dZ, S, dtheta, dscale, dnoise, st, chunk_out, n_chunks_out);      // the only mfma32 handles in scope
     std::string& slot = *qc_sweep_err_slot();
     int64_t chunk, n_chunks;
     qc_sweep_chunks(S, h->d.T, &chunk, &n_chunks);
@@ -337,7 +341,9 @@ int noise_grad_launch(qc_sweep* h, const char* who, const double* dZ, const doub
         gsamp = h->dGsamp.p;
     }
     qc_sweep_launch_fid_seed(h, S, n_chunks, dinit, dfids, st);
-    if (want_grad || dgrad_noise) {
+    if ((want_grad || dgrad_noise) && h->wide_noise) {
+        qc_sweep32_noise_launch_walk(h, dZ, S, dtheta, dscale, dnoise, chunk, n_chunks, want_grad ? gsamp : nullptr, dgrad_noise, st);
+    } else if (want_grad || dgrad_noise) {
         const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
         double* gs = want_grad ? gsamp : nullptr;
 #define QC_NOISE_GRAD_LAUNCH(M_)                                                                                                         \
@@ -356,10 +362,10 @@ int noise_grad_launch(qc_sweep* h, const char* who, const double* dZ, const doub
 
 bool qc_sweep_noise_scope(const qc_sweep_desc* d, std::string* why) {
     const int form = qc_sweep_desc_form(d);
-    if (form == 2) { *why = "noise trajectories are not served in the mfma32-sweep form"; return false; }
+    if (form == 2 && !(d->wide & QC_SWEEP_WIDE_NOISE)) { *why = "noise trajectories are not served in the mfma32-sweep form"; return false; }
     if (form == 0) { *why = qc_sweep_per_sample_why(d); return false; }
     if (d->n_pert == 0) { *why = "the handle has no perturbations (n_pert = 0): noise enters through the perturbation generators"; return false; }
-    if (d->m + d->n_pert > kNTiles) {
+    if (form == 1 && d->m + d->n_pert > kNTiles) {      // the wide form keeps no tile resident: m <= 8 and n_pert <= QC_MAX_PERT, up to 16 generators
         *why = "m + n_pert = " + std::to_string(d->m) + " + " + std::to_string(d->n_pert) + " exceeds the 8 tiles a wavefront keeps in registers";
         return false;
     }

@@ -748,12 +748,13 @@ class SweepInfidelityObjective:
     wide        as `RolloutSweep`: True serves systems of 16 < 2N <= 32 (9 .. 16 levels) in the "mfma32-sweep" form
     stored_states  as `RolloutSweep`: True takes the gradient by the stored-state walk, which serves open systems
     wide_stored as `RolloutSweep` (only with `wide` and `stored_states`): that walk in the "mfma32-sweep" form, e.g. two qubits with T1 / T2
+    wide_noise  as `RolloutSweep` (only with `wide`): what `SweepNoiseInfidelityObjective` needs in the "mfma32-sweep" form; nothing here reads it
     goal_ket    density component only: [Re psi; Im psi] (2 levels entries) of the pure state the fidelity compares with"""
     _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
 
     def __init__(self, traj: NamedTrajectory, system, perturbations, theta, scale=None, weights=None, state_name: str = "Ũ⃗",
                  control_name: str = "a", subspace=None, form: str = "abs", device: int = 0, wide: bool = False,
-                 stored_states: bool = False, goal_ket=None, wide_stored: bool = False):
+                 stored_states: bool = False, goal_ket=None, wide_stored: bool = False, wide_noise: bool = False):
         from .rollouts import RolloutSweep
         self._sweep = None
         if state_name not in traj.components:
@@ -805,7 +806,7 @@ class SweepInfidelityObjective:
                           subspace=subspace, fid_form=_lib.QC_FID_FORM_ABS2 if form == "abs2" else _lib.QC_FID_FORM_ABS, zdim=traj.dim,
                           off_a=traj.offset(control_name), off_dt=traj.offset(traj.timestep) if free else -1,
                           dt_fixed=None if free else float(traj.timestep), global_dim=traj.global_dim, device=device, wide=wide,
-                          stored_states=stored_states, wide_stored=wide_stored)
+                          stored_states=stored_states, wide_stored=wide_stored, wide_noise=wide_noise)
         self._sweep = sw
         self.stored_states = sw.stored_states
         self.wide_stored = sw.wide_stored
@@ -863,10 +864,12 @@ class SweepNoiseInfidelityObjective(SweepInfidelityObjective):
 
     noise       S x (T-1) x len(perturbations), or S x (T-1) with one perturbation: it gives S
     theta       S x len(perturbations) or None (zeros);  scale  S x n_drives or None;  weights  S values or None (1/S each)
+    wide, wide_noise  as `RolloutSweep`: both True serve systems of 16 < 2N <= 32 (two three-level transmons, a 4-qubit register) in the
+                "mfma32-sweep" form, with up to 8 drives and 8 perturbations
     `noise_sensitivity(Z)` returns dF_s/dnoise[s, t, j], S x (T-1) x len(perturbations): the time-domain filter function of the pulse."""
 
     def __init__(self, traj: NamedTrajectory, system, perturbations, noise, theta=None, scale=None, weights=None, state_name: str = "Ũ⃗",
-                 control_name: str = "a", subspace=None, form: str = "abs", device: int = 0):
+                 control_name: str = "a", subspace=None, form: str = "abs", device: int = 0, wide: bool = False, wide_noise: bool = False):
         p = len(perturbations)
         if noise is None:
             raise ValueError("noise is required: S x (T-1) x len(perturbations)")
@@ -878,7 +881,7 @@ class SweepNoiseInfidelityObjective(SweepInfidelityObjective):
         if theta is None:
             theta = np.zeros((noise.shape[0], p))
         super().__init__(traj, system, perturbations, theta, scale=scale, weights=weights, state_name=state_name, control_name=control_name,
-                         subspace=subspace, form=form, device=device)
+                         subspace=subspace, form=form, device=device, wide=wide, wide_noise=wide_noise)
         sw = self._sweep
         if self.S != noise.shape[0]:
             sw.close()

@@ -192,13 +192,19 @@ class RolloutSweep:
     wide_tangent   True (only with `wide`): an "mfma32-sweep" handle serves `jvp`, `jvp_device` and the forward-mode rule of
                    `finals_autograd` -- any generators, open systems included, with no state buffer (nothing is reversed): about three
                    forward sweeps by the instruction count.  Without it those refuse there, as they always did; nothing else changes
-                   (`hvp` keeps refusing in that form)."""
+                   (`hvp` keeps refusing in that form).
+    wide_noise     True (only with `wide`): an "mfma32-sweep" handle serves `noise_eval`, `noise_grad` and their device forms with at
+                   least one perturbation -- up to 8 drives and 8 perturbations, no tile limit (that form keeps no generator resident).
+                   Without it those refuse there, as they always did; nothing else changes, and nothing changes at 2N <= 16."""
 
     def __init__(self, system, perturbations, T: int, cols: Optional[int] = None, goal=None, fid_kind=None, subspace=None,
                  fid_form: int = _lib.QC_FID_FORM_ABS, zdim: Optional[int] = None, off_a: int = 0, off_dt: Optional[int] = None,
                  dt_fixed: Optional[float] = None, global_dim: int = 0, device: int = 0, wide: bool = False,
-                 stored_states: bool = False, wide_params: bool = False, wide_stored: bool = False, wide_tangent: bool = False):
+                 stored_states: bool = False, wide_params: bool = False, wide_stored: bool = False, wide_tangent: bool = False,
+                 wide_noise: bool = False):
         self._h = None
+        if wide_noise and not wide:
+            raise ValueError("wide_noise=True needs wide=True")
         if wide_params and not wide:
             raise ValueError("wide_params=True needs wide=True")
         if wide_tangent and not wide:
@@ -239,8 +245,10 @@ class RolloutSweep:
         d.n_sub = 0 if self._sub is None else int(self._sub.size)
         d.device = device
         d.wide = ((_lib.QC_SWEEP_WIDE if wide else 0) | (_lib.QC_SWEEP_WIDE_PARAMS if wide_params else 0)
-                  | (_lib.QC_SWEEP_WIDE_STORED if wide_stored else 0) | (_lib.QC_SWEEP_WIDE_TANGENT if wide_tangent else 0))
+                  | (_lib.QC_SWEEP_WIDE_STORED if wide_stored else 0) | (_lib.QC_SWEEP_WIDE_TANGENT if wide_tangent else 0)
+                  | (_lib.QC_SWEEP_WIDE_NOISE if wide_noise else 0))
         self.wide_tangent = bool(wide_tangent)
+        self.wide_noise = bool(wide_noise)
         self.wide = bool(wide)
         self.wide_params = bool(wide_params)
         self.wide_stored = bool(wide_stored)
@@ -690,7 +698,8 @@ class RolloutSweep:
     @property
     def noise_supported(self) -> bool:
         """Do `noise_eval` / `noise_eval_device` serve this handle?  (`qc_sweep_desc_noise_supported`: the "mfma16-sweep" form, at least
-        one perturbation, drives and perturbations together at most 8.)  `noise_unsupported_reason` says why not.  `noise_grad` also
+        one perturbation, drives and perturbations together at most 8; or the "mfma32-sweep" form of a handle made with `wide_noise`, at
+        least one perturbation, no limit on drives and perturbations together.)  `noise_unsupported_reason` says why not.  `noise_grad` also
         needs `grad_supported`."""
         return self._noise_scope()[0]
 
@@ -926,10 +935,11 @@ def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None,
 
 
 def rollout_noise_sweep(init, controls, dts, system, perturbations, noise, theta=None, scale=None, cols: Optional[int] = None, goal=None,
-                        fid_kind=None, subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS):
+                        fid_kind=None, subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS, wide: bool = False):
     """(finals, fids) of S rollouts whose perturbation amplitudes change from interval to interval: in interval t sample s sees
     theta[s, j] + noise[s, t, j] on perturbation j.  noise is S x (T-1) x len(perturbations) (S x (T-1) for one perturbation), theta
-    S x len(perturbations) or None (zeros); everything else as `rollout_sweep`."""
+    S x len(perturbations) or None (zeros); everything else as `rollout_sweep`.  `wide=True` serves 16 < 2N <= 32 on the matrix cores
+    (the handle is made with `wide` and `wide_noise`)."""
     controls = np.asarray(controls, dtype=np.float64)
     if controls.ndim != 2 or controls.shape[0] != system.n_drives:
         raise ValueError("controls must be n_drives x T")
@@ -938,7 +948,8 @@ def rollout_noise_sweep(init, controls, dts, system, perturbations, noise, theta
     n = 2 * system.state_levels
     if cols is None:
         cols = init.size // n
-    sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device)
+    sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device,
+                      wide=wide, wide_noise=wide)
     try:
         return sw.noise_eval(sw.pack(controls, dts), init, noise, theta, scale)
     finally:
