@@ -57,26 +57,10 @@ def newton_cg(times, b, max_iter: int, rtol: float = 1e-4):
     return x, k, False
 
 
-def main(T: int = 50, grid: int = 11, steps: int = 10, verbose: bool = True, max_iter: int = 60, width: float = 0.05, cg_iter: int = 25,
-         halvings: int = 5):
-    qc = g.load_package()
-    f0, f1, viol, z, traj, system = solve(max_iter, T=T, verbose=False, return_solution=True)
-    zetas = np.linspace(-width, width, grid)
-    dev = torch.device("cuda", 0)
-    target = {}
-    loss = lambda X: ((X - target["g"]) ** 2).sum() / (2 * X.shape[0])
-    obj = qc.SweepFinalStateObjective(traj, system, [qc.GATES["Z"]], zetas[:, None], loss)
-    # g: the goal in the global phase the solved pulse reaches it with (robust_gauss_newton.py says why)
-    N = system.levels
-    G = qc.GATES["H"]
-    V = obj.finals(z).reshape(grid, N, 2 * N)                                # [s, column, row]: Re rows, then Im rows
-    U = (V[:, :, :N] + 1j * V[:, :, N:]).transpose(0, 2, 1)
-    phase = np.exp(1j * np.angle((G.conj()[None] * U).sum()))
-    target["g"] = torch.from_numpy(np.ascontiguousarray(qc.operator_to_iso_vec(phase * G), dtype=np.float64)).to(dev)
-    zdim, a = traj.dim, traj.components["a"]
-    idx_host = np.concatenate([t * zdim + np.arange(a.start, a.stop) for t in range(1, T - 1)])      # the first and last controls stay pinned
-    idx = torch.from_numpy(idx_host).to(dev)
-    Z = torch.from_numpy(np.array(z, dtype=np.float64)).to(dev)
+def truncated_newton(obj, Z, idx, steps: int, cg_iter: int = 25, halvings: int = 5, lam: float = 1e-3, verbose: bool = True):
+    """The truncated-Newton loop described above on a `SweepFinalStateObjective`: Z the trajectory vector on the device, idx the entries the
+    steps may move.  Shared with examples/transmon_newton_cg.py.  Returns the final Z, the loss after every accepted step (the start
+    value first), the counts and the `summary` line."""
 
     def lift(v):
         full = torch.zeros_like(Z)
@@ -84,7 +68,7 @@ def main(T: int = 50, grid: int = 11, steps: int = 10, verbose: bool = True, max
         return full
 
     history = [obj.L(Z)]
-    lam, accepted, exact, gn, cg_total, fallbacks, trials = 1e-3, 0, 0, 0, 0, 0, 0
+    accepted, exact, gn, cg_total, fallbacks, trials = 0, 0, 0, 0, 0, 0
     for it in range(steps):
         grad = obj.grad_L(Z)[idx]
         if float(grad.abs().max()) == 0.0:
@@ -128,11 +112,36 @@ def main(T: int = 50, grid: int = 11, steps: int = 10, verbose: bool = True, max
                   f"lambda -> {lam:.1e}")
     summary = (f"truncated Newton: {accepted} accepted steps of {steps}, {exact} exact Hessian products (one pushforward + one tangent pullback each), "
                f"{gn} Gauss-Newton products in {fallbacks} fall-back steps: loss {history[0]:.6e} -> {history[-1]:.6e}")
-    out = dict(loss_history=history, accepted=accepted, exact_products=exact, gn_products=gn, fallbacks=fallbacks, cg_iterations=cg_total,
-               loss_evaluations=trials, kernel=obj._sweep.kernel_name, T=T, S=grid, controls=Z.cpu().numpy(), summary=summary)
+    return dict(Z=Z, loss_history=history, accepted=accepted, exact_products=exact, gn_products=gn, fallbacks=fallbacks, cg_iterations=cg_total,
+                loss_evaluations=trials, summary=summary)
+
+
+def main(T: int = 50, grid: int = 11, steps: int = 10, verbose: bool = True, max_iter: int = 60, width: float = 0.05, cg_iter: int = 25,
+         halvings: int = 5):
+    qc = g.load_package()
+    f0, f1, viol, z, traj, system = solve(max_iter, T=T, verbose=False, return_solution=True)
+    zetas = np.linspace(-width, width, grid)
+    dev = torch.device("cuda", 0)
+    target = {}
+    loss = lambda X: ((X - target["g"]) ** 2).sum() / (2 * X.shape[0])
+    obj = qc.SweepFinalStateObjective(traj, system, [qc.GATES["Z"]], zetas[:, None], loss)
+    # g: the goal in the global phase the solved pulse reaches it with (robust_gauss_newton.py says why)
+    N = system.levels
+    G = qc.GATES["H"]
+    V = obj.finals(z).reshape(grid, N, 2 * N)                                # [s, column, row]: Re rows, then Im rows
+    U = (V[:, :, :N] + 1j * V[:, :, N:]).transpose(0, 2, 1)
+    phase = np.exp(1j * np.angle((G.conj()[None] * U).sum()))
+    target["g"] = torch.from_numpy(np.ascontiguousarray(qc.operator_to_iso_vec(phase * G), dtype=np.float64)).to(dev)
+    zdim, a = traj.dim, traj.components["a"]
+    idx_host = np.concatenate([t * zdim + np.arange(a.start, a.stop) for t in range(1, T - 1)])      # the first and last controls stay pinned
+    idx = torch.from_numpy(idx_host).to(dev)
+    Z = torch.from_numpy(np.array(z, dtype=np.float64)).to(dev)
+    res = truncated_newton(obj, Z, idx, steps, cg_iter=cg_iter, halvings=halvings, verbose=verbose)
+    out = dict(res, kernel=obj._sweep.kernel_name, T=T, S=grid, controls=res["Z"].cpu().numpy())
+    del out["Z"]
     if verbose:
         print(f"rollout fidelity of the solved pulse: {f1:.6f}; {grid} detunings in [-{width}, {width}], T = {T}")
-        print(summary)
+        print(out["summary"])
     obj.close()
     return out
 

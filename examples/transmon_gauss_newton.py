@@ -29,10 +29,10 @@ from robust_gauss_newton import conjugate_gradients
 from transmon_robustness import LEVELS, SUBSPACE, goal_gate, two_transmons
 
 
-def main(T: int = 40, grid: int = 9, steps: int = 8, weight: float = 1.0, width: float = 2 * np.pi * 0.002, duration: float = 40.0,
-         cg_iter: int = 20, damping: float = 1.0, verbose: bool = True):
-    """Returns the loss after every accepted step (`loss_history`, the start value first), the counts, the mean leakage before and
-    after, and the kernel that served the sweeps."""
+def problem(T: int, grid: int, weight: float, width: float, duration: float, **objective):
+    """The two-transmon problem described above as a `SweepFinalStateObjective(..., wide=True, **objective)`; shared with
+    examples/transmon_newton_cg.py.  Returns (obj, Z, idx, leakage, dt): the objective, the start trajectory vector on the device, the
+    entries the steps may move (the controls of knots 1 .. T-2) and the mean leakage of a trajectory vector."""
     qc = g.load_package()
     H0, drives, n1 = two_transmons()
     system = qc.QuantumSystem(H0, drives)
@@ -62,7 +62,7 @@ def main(T: int = 40, grid: int = 9, steps: int = 8, weight: float = 1.0, width:
         dist, leak = terms(X)
         return (dist + weight * leak) / (2 * X.shape[0])
 
-    obj = qc.SweepFinalStateObjective(traj, system, [n1], zetas[:, None], loss, wide=True, wide_tangent=True)
+    obj = qc.SweepFinalStateObjective(traj, system, [n1], zetas[:, None], loss, wide=True, **objective)
     z = np.array(traj.datavec, dtype=np.float64)
     # g: the goal's computational block in the global phase the start pulse reaches it with (robust_gauss_newton.py says why)
     G = goal_gate()[np.ix_(SUBSPACE, SUBSPACE)]
@@ -74,15 +74,24 @@ def main(T: int = 40, grid: int = 9, steps: int = 8, weight: float = 1.0, width:
     idx = torch.from_numpy(np.concatenate([t * traj.dim + np.arange(rows.start, rows.stop) for t in range(1, T - 1)])).to(dev)
     Z = torch.from_numpy(z).to(dev)
 
-    def lift(v):
-        full = torch.zeros_like(Z)
-        full[idx] = v
-        return full
-
     def leakage(Zv):
         with torch.no_grad():
             X = torch.from_numpy(np.ascontiguousarray(obj.finals(Zv.cpu().numpy()))).to(dev)
             return float(terms(X)[1]) / (grid * len(SUBSPACE))
+
+    return obj, Z, idx, leakage, dt
+
+
+def main(T: int = 40, grid: int = 9, steps: int = 8, weight: float = 1.0, width: float = 2 * np.pi * 0.002, duration: float = 40.0,
+         cg_iter: int = 20, damping: float = 1.0, verbose: bool = True):
+    """Returns the loss after every accepted step (`loss_history`, the start value first), the counts, the mean leakage before and
+    after, and the kernel that served the sweeps."""
+    obj, Z, idx, leakage, dt = problem(T, grid, weight, width, duration, wide_tangent=True)
+
+    def lift(v):
+        full = torch.zeros_like(Z)
+        full[idx] = v
+        return full
 
     leak_before = leakage(Z)
     history = [obj.L(Z)]

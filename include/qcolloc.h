@@ -637,8 +637,13 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * one thing only: an "mfma32-sweep" handle then serves the noise-trajectory sweeps and their gradients (qc_sweep_noise_*, below); form,
  * launch, kernel name, every other *_supported answer and every other entry point's output are bit-identical to the same descriptor
  * without the bit, and where the handle takes another form (2N <= 16 with its own noise kernels and tile rule, rollout-per-sample) the bit
- * does nothing.  The valid values are 0, 1, 3, 9, 11, 17, 19, 25 and 27, and each of the eight odd ones | 64 (65 .. 91);
- * any other value (bit 1, 3, 4 or 6 without bit 0, bit 2, 5 and 7 among them) is QC_ERR_INVALID.
+ * does nothing.  Bit 8, QC_SWEEP_WIDE_HESSIAN (any of the sixteen odd values | 256), likewise changes one thing only: an "mfma32-sweep"
+ * handle whose descriptor passes the closed scope (antisymmetric drift / drives / perturbations, at most 16 state columns) then serves the
+ * Hessian product (qc_sweep_hvp*, below; qc_sweep32_hvp.hip).  It does not need QC_SWEEP_WIDE_TANGENT: the call launches the tangent
+ * totals itself.  Form, launch, kernel name, every other *_supported answer and every other entry point's output are bit-identical to the
+ * same descriptor without the bit, and at 2N <= 16 (whose Hessian product needs no bit) and in the rollout-per-sample form it does nothing.
+ * The valid values are 0, 1, 3, 9, 11, 17, 19, 25 and 27, each of the eight odd ones | 64 (65 .. 91), and each of those sixteen odd
+ * values | 256; any other value (bit 1, 3, 4, 6 or 8 without bit 0, bit 2, 5 and 7 among them) is QC_ERR_INVALID.
  * reserved1[0] = QC_SWEEP_STORED_STATES chooses reverse mode by the STORED-STATE walk: qc_sweep_grad*, qc_sweep_grad_params* and
  * qc_sweep_vjp* then keep the forward states x_0 .. x_{T-2} of every sample in handle scratch (S x (T-1) x 2N x cols doubles) and read
  * them on the way back instead of reversing the step, which serves ANY generators in the "mfma16-sweep" form: Lindblad generators
@@ -659,13 +664,13 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * for "mfma16-sweep" handles, and for "mfma32-sweep" handles whose `wide` has QC_SWEEP_WIDE_TANGENT, with any generators, Lindblad ones
  * included (no flag, no state buffer: nothing is reversed); with the pullback it gives Gauss-Newton products of any loss.
  * The tangent of the pullback along one direction (qc_sweep_hvp*, below) gives exact Hessian products of any loss of the final states
- * where both of them are served (closed systems, "mfma16-sweep").
+ * where both of them are served (closed systems; "mfma16-sweep", and "mfma32-sweep" handles whose `wide` has QC_SWEEP_WIDE_HESSIAN).
  * Noise-trajectory sweeps (qc_sweep_noise_*, below) are served for "mfma16-sweep" handles, and for "mfma32-sweep" handles whose `wide` has
  * QC_SWEEP_WIDE_NOISE.
  * Out of scope: per-knot outputs, open-system gradients in the "mfma32-sweep" form without QC_SWEEP_WIDE_STORED (their directional
  * derivatives are not served there at all), checkpointing inside a chunk, Hessian products and noise gradients of open
- * systems, pushforwards on "mfma32-sweep" and "rollout-per-sample" handles (the former unless `wide` has QC_SWEEP_WIDE_TANGENT; Hessian
- * products on both, with or without that bit), several directions per
+ * systems, pushforwards on "mfma32-sweep" and "rollout-per-sample" handles (the former unless `wide` has QC_SWEEP_WIDE_TANGENT), Hessian
+ * products on "rollout-per-sample" handles and on "mfma32-sweep" handles without QC_SWEEP_WIDE_HESSIAN, several directions per
  * call, tangents of grad_theta / grad_scale, several devices. */
 #define QC_MAX_PERT 8
 #define QC_SWEEP_FID_NONE (-1)   /* qc_sweep_desc.fid_kind: final states only */
@@ -674,6 +679,7 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
 #define QC_SWEEP_WIDE_STORED 8   /* qc_sweep_desc.wide, bit 3: the mfma32-sweep form serves the stored-state walk; only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_WIDE_TANGENT 16 /* qc_sweep_desc.wide, bit 4: the mfma32-sweep form serves pushforwards (qc_sweep_jvp*); only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_WIDE_NOISE 64   /* qc_sweep_desc.wide, bit 6: the mfma32-sweep form serves noise-trajectory sweeps and their gradients (qc_sweep_noise_*); only together with QC_SWEEP_WIDE */
+#define QC_SWEEP_WIDE_HESSIAN 256 /* qc_sweep_desc.wide, bit 8: the mfma32-sweep form serves Hessian products of closed systems (qc_sweep_hvp*); only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_STORED_STATES 1 /* qc_sweep_desc.reserved1[0]: reverse mode by the stored-state walk */
 typedef struct qc_sweep_desc {
     int64_t T;
@@ -695,7 +701,7 @@ typedef struct qc_sweep_desc {
     const double* goal_iso;      /* as qc_fidelity_desc.goal_iso */
     const int32_t* subspace;     /* unitary only: 0-based levels, or NULL = all */
     int32_t device;
-    int32_t wide;                /* bit field; valid: 0, QC_SWEEP_WIDE (1): the matrix-core form up to 2N = 32 ("mfma32-sweep"), or QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS (3): that form, and qc_sweep_grad_params* / the grad_theta, grad_scale of qc_sweep_vjp* are served in it (form, launch, kernel name and every *_supported answer as with 1; harmless where the handle takes another form); either of them | QC_SWEEP_WIDE_STORED (9, 11): that form also serves reverse mode by the stored-state walk when reserved1[0] = QC_SWEEP_STORED_STATES (nothing else changes); any of those | QC_SWEEP_WIDE_TANGENT (17, 19, 25, 27): that form also serves qc_sweep_jvp*; any of the eight | QC_SWEEP_WIDE_NOISE (64): that form also serves qc_sweep_noise_*; anything else is QC_ERR_INVALID */
+    int32_t wide;                /* bit field; valid: 0, QC_SWEEP_WIDE (1): the matrix-core form up to 2N = 32 ("mfma32-sweep"), or QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS (3): that form, and qc_sweep_grad_params* / the grad_theta, grad_scale of qc_sweep_vjp* are served in it (form, launch, kernel name and every *_supported answer as with 1; harmless where the handle takes another form); either of them | QC_SWEEP_WIDE_STORED (9, 11): that form also serves reverse mode by the stored-state walk when reserved1[0] = QC_SWEEP_STORED_STATES (nothing else changes); any of those | QC_SWEEP_WIDE_TANGENT (17, 19, 25, 27): that form also serves qc_sweep_jvp*; any of the eight | QC_SWEEP_WIDE_NOISE (64): that form also serves qc_sweep_noise_*; any of the sixteen | QC_SWEEP_WIDE_HESSIAN (256): that form also serves qc_sweep_hvp* for closed systems; anything else is QC_ERR_INVALID */
     int64_t reserved1[2];        /* [0]: 0, or QC_SWEEP_STORED_STATES: reverse mode reads stored forward states (any generators; "mfma16-sweep", and "mfma32-sweep" with QC_SWEEP_WIDE_STORED in `wide`); anything else is QC_ERR_INVALID.  [1]: ignored */
 } qc_sweep_desc;
 typedef struct qc_sweep qc_sweep;
@@ -848,12 +854,14 @@ int qc_sweep_jvp(qc_sweep* h, const double* Z, const double* init, int64_t S, co
  * loss(X(Z)) with vZ; with vcot = NULL it is the curvature of the sweep map alone, sum_s <cot[s], d2 x_s/dZ2 vZ>: what the Gauss-Newton
  * product of qc_sweep_jvp + qc_sweep_vjp drops, and the whole Hessian of a loss that is linear in the final states.
  * One tangent forward walk (qc_sweep_jvp's, for the chunk totals) and one backward walk that differentiates every product of the
- * gradient walk beside itself with a degree-10 series: 408 + 36 sq matrix-core instructions per interval against the pullback's 112 + 12 sq. */
-/* device-free: may the Hessian product serve this descriptor?  Scope: what the pullback and the pushforward BOTH serve -- the
- * "mfma16-sweep" form (2N <= 16, m <= 8), antisymmetric drift / drives / perturbations, at most 16 state columns, any fid_kind
- * (QC_SWEEP_FID_NONE included).  When 0, qc_sweep_last_error(NULL) says why, prefixed "qc_sweep Hessian product: ": the pullback's reason
- * (antisymmetry, more than 16 columns, the rollout-per-sample form with its cause) or "... not served in the mfma32-sweep form".  An invalid
- * descriptor returns its own error. */
+ * gradient walk beside itself with a degree-10 series: 408 + 36 sq matrix-core instructions per interval against the pullback's 112 + 12 sq
+ * ("mfma32-sweep" handles with QC_SWEEP_WIDE_HESSIAN: the same two walks on 2 x 2 tiles, 3120 + 288 sq against 848 + 96 sq). */
+/* device-free: may the Hessian product serve this descriptor?  Scope: the closed scope of the pullback -- antisymmetric drift / drives /
+ * perturbations, at most 16 state columns, any fid_kind (QC_SWEEP_FID_NONE included) -- in the "mfma16-sweep" form (2N <= 16, m <= 8),
+ * or in the "mfma32-sweep" form (16 < 2N <= 32, m <= 8) of a descriptor whose `wide` has QC_SWEEP_WIDE_HESSIAN (QC_SWEEP_WIDE_TANGENT is
+ * not needed).  When 0, qc_sweep_last_error(NULL) says why, prefixed "qc_sweep Hessian product: ": the pullback's reason first
+ * (antisymmetry, more than 16 columns, the rollout-per-sample form with its cause), then "... not served in the mfma32-sweep form" (that
+ * form without the bit).  An invalid descriptor returns its own error. */
 int qc_sweep_desc_hvp_supported(const qc_sweep_desc* d, int32_t* supported);
 /* cot: S x (2N cols), required.  Directions, each optional (NULL = zero: the same bits as an explicit zero array), at least one non-NULL:
  *   vZ       Z_len; ONLY the controls and timesteps of knots 0 .. T-2 are read (a NaN anywhere else has no effect)

@@ -17,6 +17,7 @@ const QC_MAX_DERIV = 8
 const QC_SWEEP_WIDE = 1            # qc_sweep_desc.wide, bit 0: the matrix-core form up to 2N = 32 ("mfma32-sweep")
 const QC_SWEEP_WIDE_TANGENT = 16   # qc_sweep_desc.wide, bit 4 (only with bit 0): pushforwards in that form
 const QC_SWEEP_WIDE_NOISE = 64     # qc_sweep_desc.wide, bit 6 (only with bit 0): noise-trajectory sweeps and their gradients in that form
+const QC_SWEEP_WIDE_HESSIAN = 256  # qc_sweep_desc.wide, bit 8 (only with bit 0): Hessian products of closed systems in that form
 const QC_ABI_VERSION = 6      # QC_VERSION_MAJOR * 1000 + QC_VERSION_MINOR of the include/qcolloc.h these mirrors were written against
 
 # mirror of `qc_desc` (include/qcolloc.h); field order and types must match the header -- `__init__` checks the sizes against
@@ -1064,18 +1065,21 @@ end
 
 """
     rollout_sweep_hessian_product(init, controls, Δt, G_drift, G_drives, G_pert, θ, cot; scale=nothing, cols, vZ=nothing, vinit=nothing,
-                                  vtheta=nothing, vscale=nothing, vcot=nothing, device=0)  ->  (tgrad, tgrad_samples, tgrad_init)
+                                  vtheta=nothing, vscale=nothing, vcot=nothing, device=0, wide=false)  ->  (tgrad, tgrad_samples, tgrad_init)
 
 The tangent of the pullback of `rollout_sweep` along one direction (`qc_sweep_hvp`).  `cot` is (2N·cols)×S, one cotangent per sample;
 `vZ` an (m+1)×T matrix in the knot layout [a; Δt] (only the columns of knots 1 … T−1 act), `vinit` a 2N·cols vector, `vtheta` S×p,
 `vscale` S×m, `vcot` (2N·cols)×S; whichever is `nothing` is zero, at least one must be given.  Returns `tgrad`, (m+1)×T (the plain sum
 over the samples, zero in the last column), `tgrad_samples`, (m+1)×(T−1)×S, and `tgrad_init`, (2N·cols)×S.  With `cot` the gradient of a
 loss of the final states and `vcot` its Hessian times the pushforward's tangents, `tgrad` is the exact Hessian product of the loss.
-Served for closed systems (antisymmetric generators) with 2N ≤ 16, m ≤ 8 and at most 16 columns.  UNTESTED here, like the rest of this file.
+Served for closed systems (antisymmetric generators) with 2N ≤ 16, m ≤ 8 and at most 16 columns.  `wide = true` sets
+`qc_sweep_desc.wide = QC_SWEEP_WIDE | QC_SWEEP_WIDE_HESSIAN` (257): the matrix-core form up to 2N = 32 ("mfma32-sweep") with its Hessian
+product, the same scope otherwise; nothing changes at 2N ≤ 16.  UNTESTED here, like the rest of this file.
 """
 function rollout_sweep_hessian_product(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift,
                                        G_drives, G_pert, θ::AbstractMatrix{Float64}, cot::AbstractMatrix{Float64}; scale=nothing, cols::Int,
-                                       vZ=nothing, vinit=nothing, vtheta=nothing, vscale=nothing, vcot=nothing, device::Int=0)
+                                       vZ=nothing, vinit=nothing, vtheta=nothing, vscale=nothing, vcot=nothing, device::Int=0,
+                                       wide::Bool=false)
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(θ, 1)
     G0 = Float64.(vec(G_drift))
@@ -1104,7 +1108,7 @@ function rollout_sweep_hessian_product(init::AbstractVector{Float64}, controls::
     GC.@preserve G0 Gd Gp begin
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, -1,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
-                               0, 0, C_NULL, C_NULL, device, 0, (0, 0)))
+                               0, 0, C_NULL, C_NULL, device, wide ? (QC_SWEEP_WIDE | QC_SWEEP_WIDE_HESSIAN) : 0, (0, 0)))
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_hvp_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
         (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))

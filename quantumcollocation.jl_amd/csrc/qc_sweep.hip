@@ -25,7 +25,7 @@
 // (qc_sweep32.hip, 2 x 2 tiles a matrix); the second launch below is shared, with ld = 32.  wide = 0 is the routing above, unchanged.
 // `wide` is a bit field: bit 1 (QC_SWEEP_WIDE_PARAMS, only together with bit 0) changes nothing here -- the form, the launch and the
 // forward sweep are those of wide = 1; it lets qc_sweep_grad_params* and qc_sweep_vjp* serve the parameter outputs in that form.
-// Bits 3, 4 and 6 (QC_SWEEP_WIDE_STORED, _TANGENT, _NOISE) likewise: each lets one more family of entry points serve that form.
+// Bits 3, 4, 6 and 8 (QC_SWEEP_WIDE_STORED, _TANGENT, _NOISE, _HESSIAN) likewise: each lets one more family of entry points serve that form.
 #include <math.h>
 #include <string.h>
 
@@ -247,11 +247,12 @@ int qc_sweep_validate_desc(const qc_sweep_desc* d) {
     if (2 * (int64_t)d->N > 64) return qc_sweep_fail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: 2N = " + std::to_string(2 * (int64_t)d->N) + " exceeds the supported 2N <= 64");
     if (2 * (int64_t)d->N * nc > 4096) return qc_sweep_fail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: states of more than 4096 entries (2N x state_cols) are not supported");
     if (d->m > 64) return qc_sweep_fail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: more than 64 drives are not supported");
-    // bits 1 (QC_SWEEP_WIDE_PARAMS), 3 (QC_SWEEP_WIDE_STORED), 4 (QC_SWEEP_WIDE_TANGENT) and 6 (QC_SWEEP_WIDE_NOISE) only together with
-    // bit 0; bits 2 and 5 are not assigned: 0, 1, 3, 9, 11, 17, 19, 25, 27, and each of the eight odd values | 64
-    if ((d->wide & ~(QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS | QC_SWEEP_WIDE_STORED | QC_SWEEP_WIDE_TANGENT | QC_SWEEP_WIDE_NOISE)) != 0 ||
+    // bits 1 (QC_SWEEP_WIDE_PARAMS), 3 (QC_SWEEP_WIDE_STORED), 4 (QC_SWEEP_WIDE_TANGENT), 6 (QC_SWEEP_WIDE_NOISE) and 8
+    // (QC_SWEEP_WIDE_HESSIAN) only together with bit 0; bits 2, 5 and 7 are not assigned: 0, 1, 3, 9, 11, 17, 19, 25, 27, each of the
+    // eight odd values | 64, and each of those sixteen odd values | 256
+    if ((d->wide & ~(QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS | QC_SWEEP_WIDE_STORED | QC_SWEEP_WIDE_TANGENT | QC_SWEEP_WIDE_NOISE | QC_SWEEP_WIDE_HESSIAN)) != 0 ||
         (d->wide != 0 && !(d->wide & QC_SWEEP_WIDE)))
-        return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: wide must be 0 or QC_SWEEP_WIDE (1), alone or with QC_SWEEP_WIDE_PARAMS (2), QC_SWEEP_WIDE_STORED (8), QC_SWEEP_WIDE_TANGENT (16) and / or QC_SWEEP_WIDE_NOISE (64): 0, 1, 3, 9, 11, 17, 19, 25 or 27, or one of those eight | 64");
+        return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: wide must be 0 or QC_SWEEP_WIDE (1), alone or with QC_SWEEP_WIDE_PARAMS (2), QC_SWEEP_WIDE_STORED (8), QC_SWEEP_WIDE_TANGENT (16), QC_SWEEP_WIDE_NOISE (64) and / or QC_SWEEP_WIDE_HESSIAN (256): 0, 1, 3, 9, 11, 17, 19, 25 or 27, or one of those eight | 64, or one of the sixteen odd values | 256");
     if (d->reserved1[0] != 0 && d->reserved1[0] != QC_SWEEP_STORED_STATES)
         return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: reserved1[0] must be 0 or QC_SWEEP_STORED_STATES (1)");
     return QC_OK;
@@ -343,6 +344,7 @@ extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
     h->wide_stored = h->mfma32 && (d->wide & QC_SWEEP_WIDE_STORED);
     h->wide_tangent = h->mfma32 && (d->wide & QC_SWEEP_WIDE_TANGENT);
     h->wide_noise = h->mfma32 && (d->wide & QC_SWEEP_WIDE_NOISE);
+    h->wide_hessian = h->mfma32 && (d->wide & QC_SWEEP_WIDE_HESSIAN);
     h->grad_ok = qc_sweep_grad_scope(d, &h->grad_why);      // from the caller's matrices, which the handle does not keep
     h->vjp_ok = qc_sweep_vjp_scope(d, &h->vjp_why);
     h->jvp_ok = qc_sweep_jvp_scope(d, &h->jvp_why);

@@ -15,8 +15,10 @@
 // antisymmetry identities of that walk, x_t = E^T x_{t+1} and L(hG; E^T K) = E^T L(hG; K), hold for every e along the direction, so
 // they may be differentiated as they stand.
 //
-// Scope: what the pullback and the pushforward both serve -- the "mfma16-sweep" form (2N <= 16, m <= 8), antisymmetric drift, drives and
-// perturbations, at most 16 state columns, any fid_kind.  Everything else: QC_ERR_UNSUPPORTED, "qc_sweep Hessian product: " + the reason.
+// Scope: the pullback's closed scope -- antisymmetric drift, drives and perturbations, at most 16 state columns, any fid_kind -- in the
+// "mfma16-sweep" form (2N <= 16, m <= 8: this file), and in the "mfma32-sweep" form of a descriptor whose wide has QC_SWEEP_WIDE_HESSIAN
+// (qc_sweep32_hvp.hip: the walk on 2 x 2 tiles; this file's launch function routes to it and its seed kernel is this file's at ld = 32).
+// Everything else: QC_ERR_UNSUPPORTED, "qc_sweep Hessian product: " + the reason.
 //
 // Launches of one call:
 //   1. qc_sweep_jvp_kernel<M> (qc_sweep_jvp.hip, unchanged, through qc_sweep_jvp_launch_totals): the chunk totals W_c and their tangents
@@ -270,18 +272,18 @@ __global__ __launch_bounds__(64 * kWaves, 1) void qc_sweep_hvp_kernel(const Swee
     }
 }
 
-// One workgroup per sample.  tot: the sample's n_chunks pairs (W_c, Wdot_c) of 16 x 16 column-major tiles.  Up, ascending chunks:
+// One workgroup per sample.  tot: the sample's n_chunks pairs (W_c, Wdot_c) of ld x ld column-major matrices, l2 = ld^2 doubles each:
+// ld = 16 for "mfma16-sweep" handles, 32 for "mfma32-sweep" ones (the two kernels below, as qc_sweep_jvp_finish_kernel).  Up, ascending chunks:
 // xdot <- Q_c xdot + Qdot_c x, x <- Q_c x (the loops of qc_sweep_jvp_finish_kernel), both stored at every chunk end.  Down:
 // lambda = cot, lambdadot = vcot (NULL: zeros) at the last chunk end; lambdadot <- Q_c^T lambdadot + Qdot_c^T lambda,
 // lambda <- Q_c^T lambda for c = n_chunks-1 .. 1, stored at the end of chunk c-1; with tginit the step c = 0 as well, whose lambdadot is
 // the sample's tgrad_init.
-__global__ __launch_bounds__(kHSeedT) void qc_sweep_hvp_seed_kernel(const HvpSeedParams F, const double* __restrict__ tot, const double* __restrict__ src,
-                                                                    const double* __restrict__ vsrc, const double* __restrict__ cot,
-                                                                    const double* __restrict__ vcot, double* __restrict__ xs,
-                                                                    double* __restrict__ xts, double* __restrict__ ls, double* __restrict__ lts,
-                                                                    double* __restrict__ tginit) {
+template <int ld, int l2>
+__device__ __forceinline__ void hvp_seed(const HvpSeedParams& F, const double* __restrict__ tot, const double* __restrict__ src,
+                                         const double* __restrict__ vsrc, const double* __restrict__ cot, const double* __restrict__ vcot,
+                                         double* __restrict__ xs, double* __restrict__ xts, double* __restrict__ ls, double* __restrict__ lts,
+                                         double* __restrict__ tginit) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    constexpr int ld = 16, l2 = 256;
     const int tid = threadIdx.x, n = F.n, ns = F.ns;
     const long long s = blockIdx.x;
     double* cur = sm;
@@ -348,6 +350,25 @@ __global__ __launch_bounds__(kHSeedT) void qc_sweep_hvp_seed_kernel(const HvpSee
     }
 }
 
+__global__ __launch_bounds__(kHSeedT) void qc_sweep_hvp_seed_kernel(const HvpSeedParams F, const double* __restrict__ tot, const double* __restrict__ src,
+                                                                    const double* __restrict__ vsrc, const double* __restrict__ cot,
+                                                                    const double* __restrict__ vcot, double* __restrict__ xs,
+                                                                    double* __restrict__ xts, double* __restrict__ ls, double* __restrict__ lts,
+                                                                    double* __restrict__ tginit) {
+    constexpr int ld = 16, l2 = 256;
+    hvp_seed<ld, l2>(F, tot, src, vsrc, cot, vcot, xs, xts, ls, lts, tginit);
+}
+
+// the same on the 32 x 32 totals of "mfma32-sweep" handles (qc_sweep32_jvp.hip): 2048 doubles a pair, 4 ns + 2048 doubles of LDS (ns <= 512: 32 KiB)
+__global__ __launch_bounds__(kHSeedT) void qc_sweep32_hvp_seed_kernel(const HvpSeedParams F, const double* __restrict__ tot, const double* __restrict__ src,
+                                                                      const double* __restrict__ vsrc, const double* __restrict__ cot,
+                                                                      const double* __restrict__ vcot, double* __restrict__ xs,
+                                                                      double* __restrict__ xts, double* __restrict__ ls, double* __restrict__ lts,
+                                                                      double* __restrict__ tginit) {
+    constexpr int ld = 32, l2 = 1024;
+    hvp_seed<ld, l2>(F, tot, src, vsrc, cot, vcot, xs, xts, ls, lts, tginit);
+}
+
 const char* const kHvpScope = "qc_sweep Hessian product: ";
 
 // the argument checks both entry points share, in the order of the header's table
@@ -365,11 +386,11 @@ int hvp_check(qc_sweep* h, const char* who, const void* Z, const void* init, int
 
 }  // namespace
 
-// What the pullback and the pushforward both serve: the pullback's scope (its reasons first: the per-sample form, antisymmetry, more than 16
-// columns) within the "mfma16-sweep" form.
+// The pullback's closed scope (its reasons first: the per-sample form, antisymmetry, more than 16 columns) within the "mfma16-sweep" form,
+// or within the "mfma32-sweep" form of a descriptor whose wide has QC_SWEEP_WIDE_HESSIAN (qc_sweep32_hvp.hip).
 bool qc_sweep_hvp_scope(const qc_sweep_desc* d, std::string* why) {
     if (!qc_sweep_closed_scope(d, why)) return false;
-    if (qc_sweep_desc_form(d) == 2) { *why = "Hessian products are not served in the mfma32-sweep form"; return false; }
+    if (qc_sweep_desc_form(d) == 2 && !(d->wide & QC_SWEEP_WIDE_HESSIAN)) { *why = "Hessian products are not served in the mfma32-sweep form"; return false; }
     return true;
 }
 
@@ -412,17 +433,24 @@ static int qc_sweep_hvp_launch(qc_sweep* h, const char* who, const double* dZ, c
     }
     HvpSeedParams F;
     F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
-    const size_t lds = ((size_t)4 * h->ns + 512) * 8;      // at most 16 state columns: 12 KiB
-    hipLaunchKernelGGL(qc_sweep_hvp_seed_kernel, dim3((unsigned)S), dim3(kHSeedT), lds, st, F, (const double*)h->dTotJ.p, dinit, dvinit, dcot, dvcot,
-                       h->dXs.p, h->dXsT.p, h->dLs.p, h->dLsT.p, dtgrad_init);
-    if (want_walk) {
-        const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
-        const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
+    if (h->mfma32) {      // "mfma32-sweep" handles with wide_hessian: the seed at ld = 32, the walk of qc_sweep32_hvp.hip
+        const size_t lds32 = ((size_t)4 * h->ns + 2048) * 8;      // at most 16 state columns of 32 rows: 32 KiB
+        hipLaunchKernelGGL(qc_sweep32_hvp_seed_kernel, dim3((unsigned)S), dim3(kHSeedT), lds32, st, F, (const double*)h->dTotJ.p, dinit, dvinit, dcot,
+                           dvcot, h->dXs.p, h->dXsT.p, h->dLs.p, h->dLsT.p, dtgrad_init);
+        if (want_walk) qc_sweep32_hvp_launch_walk(h, dZ, S, dtheta, dscale, dvZ, dvtheta, dvscale, chunk, n_chunks, tgs, st);
+    } else {
+        const size_t lds = ((size_t)4 * h->ns + 512) * 8;      // at most 16 state columns: 12 KiB
+        hipLaunchKernelGGL(qc_sweep_hvp_seed_kernel, dim3((unsigned)S), dim3(kHSeedT), lds, st, F, (const double*)h->dTotJ.p, dinit, dvinit, dcot, dvcot,
+                           h->dXs.p, h->dXsT.p, h->dLs.p, h->dLsT.p, dtgrad_init);
+        if (want_walk) {
+            const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
+            const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
 #define QC_HVP_LAUNCH(M_)                                                                                                                 \
     hipLaunchKernelGGL(qc_sweep_hvp_kernel<M_>, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, dvZ, dvtheta, dvscale,       \
                        (const double*)h->dXs.p, (const double*)h->dLs.p, (const double*)h->dXsT.p, (const double*)h->dLsT.p, tgs)
-        QC_SWEEP_FOR_M(m, QC_HVP_LAUNCH);
+            QC_SWEEP_FOR_M(m, QC_HVP_LAUNCH);
 #undef QC_HVP_LAUNCH
+        }
     }
     if (dtgrad) qc_sweep_launch_plain_sum(h, S, tgs, dtgrad, st);
     hipError_t e = hipGetLastError();

@@ -1,5 +1,5 @@
 // What qc_sweep.hip (forward sweep), qc_sweep_grad.hip (its adjoint), qc_sweep_open_grad.hip and qc_sweep32_open_grad.hip (the adjoint on stored states), qc_sweep_vjp.hip (the pullback of the final states),
-// qc_sweep_jvp.hip (their pushforward), qc_sweep_hvp.hip (the tangent of the pullback) and qc_sweep_noise.hip (noise trajectories) share: the handle with its scratch and staging buffers, the descriptor and argument checks, the launch
+// qc_sweep_jvp.hip (their pushforward), qc_sweep_hvp.hip and qc_sweep32_hvp.hip (the tangent of the pullback) and qc_sweep_noise.hip (noise trajectories) share: the handle with its scratch and staging buffers, the descriptor and argument checks, the launch
 // parameters of the (sample, chunk) kernels (SweepParams, qc_sweep_params) and the launch of the forward chunk totals (with it the chunk rule).  Not part of the ABI.
 #pragma once
 
@@ -15,6 +15,7 @@ struct qc_sweep : qc_side {
     bool wide_stored = false;    // mfma32 and wide has QC_SWEEP_WIDE_STORED: with `stored`, reverse mode by the 2 x 2-tile stored-state walk (qc_sweep32_open_grad.hip)
     bool wide_tangent = false;   // mfma32 and wide has QC_SWEEP_WIDE_TANGENT: pushforwards are served (qc_sweep32_jvp.hip)
     bool wide_noise = false;     // mfma32 and wide has QC_SWEEP_WIDE_NOISE: noise trajectories are served (qc_sweep32_noise.hip)
+    bool wide_hessian = false;   // mfma32 and wide has QC_SWEEP_WIDE_HESSIAN: Hessian products of closed systems are served (qc_sweep32_hvp.hip)
     bool stored = false;         // reserved1[0] = QC_SWEEP_STORED_STATES: reverse mode by the stored-state walk (qc_sweep_open_grad.hip)
     bool grad_ok = false;        // the gradient's scope (qc_sweep_grad.hip), decided at create from the caller's matrices
     std::string grad_why;        // when not: the reason
@@ -22,7 +23,7 @@ struct qc_sweep : qc_side {
     std::string vjp_why;
     bool jvp_ok = false;         // the pushforward's scope (qc_sweep_jvp.hip): "mfma16-sweep" handles, and "mfma32-sweep" ones with wide_tangent; any generators
     std::string jvp_why;
-    bool hvp_ok = false;         // the Hessian product's scope (qc_sweep_hvp.hip): what the pullback and the pushforward both serve
+    bool hvp_ok = false;         // the Hessian product's scope (qc_sweep_hvp.hip): the closed scope in the "mfma16-sweep" form, and in the "mfma32-sweep" form with wide_hessian
     std::string hvp_why;
     bool noise_ok = false;       // the noise sweep's scope (qc_sweep_noise.hip): "mfma16-sweep", n_pert >= 1, m + n_pert <= 8 tiles; "mfma32-sweep" with wide_noise, n_pert >= 1
     std::string noise_why;
@@ -162,8 +163,13 @@ int qc_sweep_jvp_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const d
                                const double* dvtheta, const double* dvscale, hipStream_t st, int64_t* chunk, int64_t* n_chunks);
 // the plain sum over the samples of a per-interval buffer (qc_sweep_vjp.hip: qc_sweep_vjp_reduce_kernel), launched on `st`
 void qc_sweep_launch_plain_sum(qc_sweep* h, int64_t S, const double* gs, double* dgrad, hipStream_t st);
-// the Hessian product's scope (qc_sweep_hvp.hip): the pullback's, within the "mfma16-sweep" form
+// the Hessian product's scope (qc_sweep_hvp.hip): the pullback's closed scope, within the "mfma16-sweep" form or the "mfma32-sweep" form
+// of a descriptor whose wide has QC_SWEEP_WIDE_HESSIAN
 bool qc_sweep_hvp_scope(const qc_sweep_desc* d, std::string* why);
+// "mfma32-sweep" handles with `wide_hessian` (qc_sweep32_hvp.hip): qc_sweep32_hvp_kernel walks every chunk backwards from the four states
+// at the chunk ends (h->dXs, h->dLs, h->dXsT, h->dLsT, written by the seed of qc_sweep_hvp.hip at ld = 32); tgs: S x (T-1) x nd
+void qc_sweep32_hvp_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dvZ,
+                                const double* dvtheta, const double* dvscale, int64_t chunk, int64_t n_chunks, double* tgs, hipStream_t st);
 // the second launch of an evaluation on an MFMA form (qc_sweep.hip): qc_sweep_finish_kernel on the chunk totals in h->dTot
 int qc_sweep_launch_finish(qc_sweep* h, int64_t S, int64_t n_chunks, const double* dinit, double* dfinals, double* dfids, hipStream_t st);
 // launches 2 and 4 of a gradient call (qc_sweep_grad.hip): the fidelity's seed (reads h->dTot; writes h->dXs / h->dLs, grown by the caller,

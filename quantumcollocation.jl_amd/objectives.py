@@ -925,11 +925,14 @@ class SweepFinalStateObjective:
     wide_stored as `RolloutSweep` (only with `wide` and `stored_states`): that walk in the "mfma32-sweep" form (gradients only, unless
                 `wide_tangent` is set as well)
     wide_tangent  as `RolloutSweep` (only with `wide`): the pushforward in the "mfma32-sweep" form, so that `gauss_newton_times` is
-                served there (closed systems, and open ones with `stored_states` and `wide_stored`); `hessian_times` keeps refusing"""
+                served there (closed systems, and open ones with `stored_states` and `wide_stored`)
+    wide_hessian  as `RolloutSweep` (only with `wide`): the Hessian product in the "mfma32-sweep" form.  `hessian_times` there needs
+                `wide_tangent` as well (one `jvp_device`, one `hvp_device`); with one of the two it raises the handle's reason"""
     _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
 
     def __init__(self, traj: NamedTrajectory, system, perturbations, theta, loss, scale=None, state_name="Ũ⃗", control_name: str = "a",
-                 device: int = 0, wide: bool = False, stored_states: bool = False, wide_stored: bool = False, wide_tangent: bool = False):
+                 device: int = 0, wide: bool = False, stored_states: bool = False, wide_stored: bool = False, wide_tangent: bool = False,
+                 wide_hessian: bool = False):
         from .rollouts import RolloutSweep, _sweep_samples
         self._sweep = None
         if not callable(loss):
@@ -956,8 +959,9 @@ class SweepFinalStateObjective:
         sw = RolloutSweep(system, perturbations, traj.T, cols=cols, zdim=traj.dim, off_a=traj.offset(control_name),
                           off_dt=traj.offset(traj.timestep) if free else -1, dt_fixed=None if free else float(traj.timestep),
                           global_dim=traj.global_dim, device=device, wide=wide, stored_states=stored_states, wide_stored=wide_stored,
-                          wide_tangent=wide_tangent)
+                          wide_tangent=wide_tangent, wide_hessian=wide_hessian)
         self._sweep = sw
+        self.wide_hessian = sw.wide_hessian
         self.stored_states = sw.stored_states
         self.wide_stored = sw.wide_stored
         self.wide_tangent = sw.wide_tangent
@@ -1050,10 +1054,14 @@ class SweepFinalStateObjective:
         of the pullback along (v, vcot).  It is `gauss_newton_times` plus the curvature of the sweep map, sum_s <cot_s, d2 X_s/dZ2 v>, which
         for a loss that is linear or nearly linear in X is the whole Hessian.  A loss linear in X gives vcot = 0, not a skipped call.  Z and
         v are numpy arrays (the result is one) or float64 tensors on the handle's device (the result stays there).  Needs the Hessian
-        product's scope: closed systems on an "mfma16-sweep" handle."""
+        product's scope and the pushforward's: closed systems on an "mfma16-sweep" handle, or on an "mfma32-sweep" handle made with both
+        `wide_tangent` (the `jvp_device` call) and `wide_hessian` (the `hvp_device` call); with one of the two it raises
+        QC_ERR_UNSUPPORTED with the handle's reason."""
         sw = self._sweep
         if not sw.hvp_supported:
             raise _lib.QCollocError(_lib.QC_ERR_UNSUPPORTED, sw.hvp_unsupported_reason)
+        if not sw.jvp_supported:
+            raise _lib.QCollocError(_lib.QC_ERR_UNSUPPORTED, sw.jvp_unsupported_reason)
         on_device = torch.is_tensor(Z) and torch.is_tensor(v)
         put = lambda a: (a.detach() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))).to(self._dev).contiguous().reshape(-1)
         dZ, dv = put(Z), put(v)

@@ -192,17 +192,23 @@ class RolloutSweep:
     wide_tangent   True (only with `wide`): an "mfma32-sweep" handle serves `jvp`, `jvp_device` and the forward-mode rule of
                    `finals_autograd` -- any generators, open systems included, with no state buffer (nothing is reversed): about three
                    forward sweeps by the instruction count.  Without it those refuse there, as they always did; nothing else changes
-                   (`hvp` keeps refusing in that form).
+                   (`hvp` in that form is `wide_hessian`'s to serve).
     wide_noise     True (only with `wide`): an "mfma32-sweep" handle serves `noise_eval`, `noise_grad` and their device forms with at
                    least one perturbation -- up to 8 drives and 8 perturbations, no tile limit (that form keeps no generator resident).
-                   Without it those refuse there, as they always did; nothing else changes, and nothing changes at 2N <= 16."""
+                   Without it those refuse there, as they always did; nothing else changes, and nothing changes at 2N <= 16.
+    wide_hessian   True (only with `wide`): an "mfma32-sweep" handle of a closed system (antisymmetric generators, at most 16 state
+                   columns) serves `hvp` and `hvp_device`: one tangent forward walk and one backward walk on 2 x 2 tiles, about 3.4
+                   pullbacks by the instruction count.  It does not need `wide_tangent`.  Without it those refuse there, as they
+                   always did; nothing else changes, and nothing changes at 2N <= 16, where `hvp` needs no flag."""
 
     def __init__(self, system, perturbations, T: int, cols: Optional[int] = None, goal=None, fid_kind=None, subspace=None,
                  fid_form: int = _lib.QC_FID_FORM_ABS, zdim: Optional[int] = None, off_a: int = 0, off_dt: Optional[int] = None,
                  dt_fixed: Optional[float] = None, global_dim: int = 0, device: int = 0, wide: bool = False,
                  stored_states: bool = False, wide_params: bool = False, wide_stored: bool = False, wide_tangent: bool = False,
-                 wide_noise: bool = False):
+                 wide_noise: bool = False, wide_hessian: bool = False):
         self._h = None
+        if wide_hessian and not wide:
+            raise ValueError("wide_hessian=True needs wide=True")
         if wide_noise and not wide:
             raise ValueError("wide_noise=True needs wide=True")
         if wide_params and not wide:
@@ -246,7 +252,8 @@ class RolloutSweep:
         d.device = device
         d.wide = ((_lib.QC_SWEEP_WIDE if wide else 0) | (_lib.QC_SWEEP_WIDE_PARAMS if wide_params else 0)
                   | (_lib.QC_SWEEP_WIDE_STORED if wide_stored else 0) | (_lib.QC_SWEEP_WIDE_TANGENT if wide_tangent else 0)
-                  | (_lib.QC_SWEEP_WIDE_NOISE if wide_noise else 0))
+                  | (_lib.QC_SWEEP_WIDE_NOISE if wide_noise else 0) | (_lib.QC_SWEEP_WIDE_HESSIAN if wide_hessian else 0))
+        self.wide_hessian = bool(wide_hessian)
         self.wide_tangent = bool(wide_tangent)
         self.wide_noise = bool(wide_noise)
         self.wide = bool(wide)
@@ -613,12 +620,16 @@ class RolloutSweep:
     # -- Hessian products: the tangent of the pullback along one direction ------------------------------------------------------------
     @property
     def hvp_supported(self) -> bool:
-        """Does `hvp` serve this handle?  (`qc_sweep_desc_hvp_supported`: what `vjp` and `jvp` both serve -- the "mfma16-sweep" form,
-        antisymmetric generators, at most 16 state columns, any fidelity or none.)  `hvp_unsupported_reason` says why not."""
+        """Does `hvp` serve this handle?  (`qc_sweep_desc_hvp_supported`: the closed scope of `vjp` -- antisymmetric generators, at most
+        16 state columns, any fidelity or none -- in the "mfma16-sweep" form, or in the "mfma32-sweep" form of a handle made with
+        `wide_hessian`.)  `hvp_unsupported_reason` says why not."""
         return self._hvp_scope()[0]
 
     @property
     def hvp_unsupported_reason(self) -> Optional[str]:
+        """None when `hvp` is served, else the library's reason: the pullback's first (the rollout-per-sample form with its cause,
+        "... is not antisymmetric", more than 16 columns), then "Hessian products are not served in the mfma32-sweep form" for a wide
+        handle made without `wide_hessian`."""
         return self._hvp_scope()[1]
 
     def _hvp_scope(self):
