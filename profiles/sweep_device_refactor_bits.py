@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Same bits before and after the device-side refactor of the sweep kernels (one-off check; profiles/sweep_device_refactor_summary.txt).
+"""Same bits before and after a device-side refactor of the sweep kernels (one-off check; profiles/sweep_device_refactor_summary.txt and
+profiles/sweep32_device_refactor_summary.txt).
 
     QCOLLOC_HIP_VARIANT=parent python profiles/sweep_device_refactor_bits.py run DIR/parent.npz     # one fresh process per library
     python profiles/sweep_device_refactor_bits.py run DIR/new.npz
@@ -11,8 +12,13 @@ and saves every output array.  `compare` asserts with assert_array_equal that bo
     narrow ("mfma16-sweep")  N = 2, m = 2, p = 1, T = 6, free time, S in {3, 40}                       every entry point; stored-state grad, grad_params, vjp
                              the same with m = 8 (M = 8; the noise sweeps need m + p <= 8: not served)  every other entry point; stored-state walks
                              T = 8, S = 3, timesteps log-uniform: 0 .. 6 squarings in one call          every entry point; stored-state walks
-    wide ("mfma32-sweep")    N = 9, m = 1, p = 1, T = 4, S in {2, 20}                                   eval, grad, grad_params, vjp, jvp (wide = 1 + 2 + 16);
+    wide ("mfma32-sweep")    N = 9 (2N = 18: padded tiles), m = 1, p = 1, T = 4, S in {2, 20}           every entry point (wide = 1 + 2 + 16 + 64 + 256);
                                                                                                        stored-state grad, grad_params, vjp (wide = 1 + 2 + 8)
+                             the same with m = 2                                                        the same
+                             m = 1 with a fixed timestep (no timestep in the knot, nd = m)              the same
+                             T = 8, S = 3, timesteps log-uniform: 0 .. 6 squarings in one call          the same
+S = 2 and S = 3 give several chunks per sample, S = 20 and S = 40 a partly filled last workgroup.  Asking for every output alone makes the
+calls of the parameter flavours without `gs` as well.
 """
 import os
 import sys
@@ -25,11 +31,16 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 NARROW = ("eval", "grad", "grad_params", "vjp", "jvp", "hvp", "noise_eval", "noise_grad")
 REVERSE = ("grad", "grad_params", "vjp")
+WIDE = dict(wide=True, wide_params=True, wide_tangent=True, wide_noise=True, wide_hessian=True)
+WIDE_STORED = dict(wide=True, wide_params=True, stored_states=True, wide_stored=True)
 CASES = [dict(name="narrow", N=2, m=2, T=6, S=(3, 40), entries=NARROW, kw={}, stored=dict(stored_states=True), sq=None),
          dict(name="narrow-m8", N=2, m=8, T=6, S=(3,), entries=NARROW[:6], kw={}, stored=dict(stored_states=True), sq=None),
          dict(name="narrow-squarings", N=2, m=2, T=8, S=(3,), entries=NARROW, kw={}, stored=dict(stored_states=True), sq=7),
-         dict(name="wide", N=9, m=1, T=4, S=(2, 20), entries=NARROW[:5], kw=dict(wide=True, wide_params=True, wide_tangent=True),
-              stored=dict(wide=True, wide_params=True, stored_states=True, wide_stored=True), sq=None)]
+         dict(name="wide", N=9, m=1, T=4, S=(2, 20), entries=NARROW, kw=WIDE, stored=WIDE_STORED, sq=None),
+         dict(name="wide-m2", N=9, m=2, T=4, S=(2, 20), entries=NARROW, kw=WIDE, stored=WIDE_STORED, sq=None),
+         dict(name="wide-fixed-dt", N=9, m=1, T=4, S=(2, 20), entries=NARROW, kw=dict(WIDE, dt_fixed=0.2), stored=dict(WIDE_STORED, dt_fixed=0.2),
+              sq=None),
+         dict(name="wide-squarings", N=9, m=1, T=8, S=(3,), entries=NARROW, kw=WIDE, stored=WIDE_STORED, sq=7)]
 
 
 def run(path):

@@ -55,15 +55,12 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_mfma16_kernel(const S
                                                                            const double* __restrict__ theta, const double* __restrict__ scale,
                                                                            double* __restrict__ tot) {
     __shared__ double scr_all[kWaves * kTile];
-    const int lane = threadIdx.x & 63;
-    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kTile;
-    const long long item = (long long)blockIdx.x * kWaves + wq;
-    if (item >= P.items) return;
-    const long long s = item / P.n_chunks;
-    const int c = (int)(item - s * P.n_chunks);
-    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
-    const int g = lane >> 4, j = lane & 15;
+    const WaveItem w = wave_item(kWaves);
+    double* __restrict__ scr = scr_all + w.wq * kTile;
+    if (w.item >= P.items) return;
+    const ChunkRange ch = chunk_range(w.item, P.n_chunks, P.chunk, P.n_int);
+    const int lane = w.lane, t0 = ch.t0, t1 = ch.t1, g = lane >> 4, j = lane & 15;
+    const long long item = w.item, s = ch.s;
     const int m = P.m;
     const bool ft = P.off_dt >= 0;
     const v4d IdB = identity_B(g, j);
@@ -205,6 +202,16 @@ void qc_sweep_chunks(int64_t S, int64_t T, int64_t* chunk, int64_t* n_chunks) {
     *n_chunks = (n_int + *chunk - 1) / *chunk;
 }
 
+int qc_sweep_plan_totals(qc_sweep* h, int64_t S, qc_buf& buf, size_t doubles_per_item, SweepParams* P, int64_t* chunk, int64_t* n_chunks) {
+    int64_t ch, nch;
+    qc_sweep_chunks(S, h->d.T, &ch, &nch);
+    QC_SIDE_HIP(h, g_swerr, h->grow(buf, (size_t)S * nch * doubles_per_item));
+    *P = qc_sweep_params(h, S, ch, nch);
+    *chunk = ch;      // as before: untouched when the allocation fails
+    *n_chunks = nch;
+    return QC_OK;
+}
+
 int qc_sweep_validate_desc(const qc_sweep_desc* d) {
     if (!d) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: NULL descriptor");
     if (d->N < 1) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: N must be >= 1");
@@ -286,16 +293,12 @@ int qc_sweep_check(qc_sweep* h, const char* who, const bool qc_sweep::*ok, const
 int qc_sweep_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, hipStream_t st, int64_t* chunk_out,
                            int64_t* n_chunks_out) {
     if (h->mfma32) return qc_sweep32_launch_totals(h, dZ, S, dtheta, dscale, st, chunk_out, n_chunks_out);
-    int64_t chunk, n_chunks;
-    qc_sweep_chunks(S, h->d.T, &chunk, &n_chunks);
-    QC_SIDE_HIP(h, g_swerr, h->grow(h->dTot, (size_t)S * n_chunks * 256));
-    const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
-    const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
-#define QC_SWEEP_LAUNCH(M_) hipLaunchKernelGGL(qc_sweep_mfma16_kernel<M_>, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, h->dTot.p)
+    SweepParams P;
+    if (int rc = qc_sweep_plan_totals(h, S, h->dTot, 256, &P, chunk_out, n_chunks_out)) return rc;
+#define QC_SWEEP_LAUNCH(M_) \
+    hipLaunchKernelGGL(qc_sweep_mfma16_kernel<M_>, dim3(qc_sweep_grid(P, kWaves)), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, h->dTot.p)
     QC_SWEEP_FOR_M(P.m, QC_SWEEP_LAUNCH);
 #undef QC_SWEEP_LAUNCH
-    *chunk_out = chunk;
-    *n_chunks_out = n_chunks;
     return QC_OK;
 }
 

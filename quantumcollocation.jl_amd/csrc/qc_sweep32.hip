@@ -1,9 +1,11 @@
 // Rollout sweeps for 16 < 2N <= 32 with up to 8 drives ("mfma32-sweep"): the forward kernel of qc_sweep.hip with every matrix 2 x 2
 // tiles of 16 x 16 on v_mfma_f64_16x16x4_f64.  Taken only by descriptors with wide = QC_SWEEP_WIDE; the mathematics (Y = dt G_s(a_t) / 2^sq
 // with ||Y||_1 <= 1/8 and a wave-uniform sq, the degree-8 Horner chain with the correctly rounded 1/k! table, sq squarings, W <- E_t W),
-// the work item (one wavefront per (sample, chunk of consecutive intervals), four per workgroup, never synchronised) and the chunk rule
-// are those of qc_sweep_mfma16_kernel.  Sizes 18 .. 30 are zero-padded to 32: the exponential of the padded generator is the
-// exponential of the true one plus an identity block.
+// the work item (one wavefront per (sample, chunk of consecutive intervals), four per workgroup, never synchronised: wave_item and
+// chunk_range of qc_sweep_common.h, as in every kernel of both forms) and the chunk rule are those of qc_sweep_mfma16_kernel.  The interval
+// body below restates drive_lane, exp_plain (qc_sweep32_common.h; qc_sweep32_open_store_kernel calls them) and the total's store, as
+// qc_sweep32_noise_kernel does: the calls move this kernel's VGPRs or its time ("Shared and restated in the wide kernels").  Sizes 18 .. 30 are zero-padded to 32: the exponential of the padded generator is the exponential of
+// the true one plus an identity block.
 //
 // Tiles.  X[I][J] is the tile of rows 16 I .. and columns 16 J ..; lane maps per tile as everywhere (qc_mfma_kernels.hip header):
 // A layout lane (g, i) reg kk = A[i][4kk+g], B / D layout lane (g, j) reg r = X[4r+g][j].  A product is D[I][J] = sum_K A[I][K] B[K][J]:
@@ -35,15 +37,12 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_mfma32_kernel(const S
                                                                            const double* __restrict__ theta, const double* __restrict__ scale,
                                                                            double* __restrict__ tot) {
     __shared__ double scr_all[kWaves * kScr];
-    const int lane = threadIdx.x & 63;
-    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kScr;
-    const long long item = (long long)blockIdx.x * kWaves + wq;
-    if (item >= P.items) return;
-    const long long s = item / P.n_chunks;
-    const int c = (int)(item - s * P.n_chunks);
-    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
-    const int g = lane >> 4, j = lane & 15;
+    const WaveItem w = wave_item(kWaves);
+    double* __restrict__ scr = scr_all + w.wq * kScr;
+    if (w.item >= P.items) return;
+    const ChunkRange ch = chunk_range(w.item, P.n_chunks, P.chunk, P.n_int);
+    const int lane = w.lane, t0 = ch.t0, t1 = ch.t1, g = lane >> 4, j = lane & 15;
+    const long long item = w.item, s = ch.s;
     const int m = P.m;
     const bool ft = P.off_dt >= 0;
     const v4d IdB = identity_B(g, j);
@@ -113,13 +112,8 @@ void qc_sweep32_image(const double* G, int n, double* img) {
 
 int qc_sweep32_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, hipStream_t st, int64_t* chunk_out,
                              int64_t* n_chunks_out) {
-    int64_t chunk, n_chunks;
-    qc_sweep_chunks(S, h->d.T, &chunk, &n_chunks);
-    QC_SIDE_HIP(h, *qc_sweep_err_slot(), h->grow(h->dTot, (size_t)S * n_chunks * 1024));
-    const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
-    const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
-    hipLaunchKernelGGL(qc_sweep_mfma32_kernel, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, h->dTot.p);
-    *chunk_out = chunk;
-    *n_chunks_out = n_chunks;
+    SweepParams P;
+    if (int rc = qc_sweep_plan_totals(h, S, h->dTot, 1024, &P, chunk_out, n_chunks_out)) return rc;
+    hipLaunchKernelGGL(qc_sweep_mfma32_kernel, dim3(qc_sweep_grid(P, kWaves)), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, h->dTot.p);
     return QC_OK;
 }

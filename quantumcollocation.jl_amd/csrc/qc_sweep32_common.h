@@ -1,8 +1,9 @@
 // What the forward kernel (qc_sweep32.hip), the backward walks (qc_sweep32_grad.hip, qc_sweep32_open_grad.hip) and the pushforward
 // (qc_sweep32_jvp.hip) of the "mfma32-sweep" form share, in one place so that it cannot drift: the closed walk reverses the forward step,
 // and the stored states match the stored-state walk, only if all form the same generator and choose the same number of squarings.  The
-// sample's base matrix, the interval's generator, the squaring rule, the four-tile transpose, the in-place product X <- A X + c I;
-// constants, table, DPP move, wave sum and the rule's tail are those of qc_sweep_common.h.  The counterpart of qc_sweep16_common.h.
+// sample's base matrix, the interval's generator, the lane's drive and factor, a state in two tiles, the squaring rule, the four-tile
+// transpose, the in-place product X <- A X + c I, the plain exponential (called only where that leaves a kernel's registers and time alone);
+// constants, table, DPP move, wave sum, rule's tail and work item are those of qc_sweep_common.h.  The counterpart of qc_sweep16_common.h.
 #pragma once
 
 #include "qc_sweep_common.h"
@@ -46,6 +47,30 @@ __device__ __forceinline__ void generator(const double* __restrict__ img, int m,
             for (int r = 0; r < 4; ++r) G[q >> 1][q & 1][r] = fma(a, t4[r], G[q >> 1][q & 1][r]);
         }
     }
+}
+
+// lane l holds the sample's factor of drive kl = min(l, m-1), folded into the control values: cl = scale[s, kl], 1 without `scale`
+struct DriveLane {
+    int kl;
+    double cl;
+};
+
+__device__ __forceinline__ DriveLane drive_lane(const double* scale, int m, long long s, int lane) {
+    DriveLane d;
+    d.kl = lane < m ? lane : (m > 0 ? m - 1 : 0);
+    d.cl = (scale && m > 0) ? scale[s * m + d.kl] : 1.0;
+    return d;
+}
+
+// an n x nc column-major state at `p` into two D-layout tiles (rows 16 I + 4 r + g, column j), zero outside n x nc
+__device__ __forceinline__ void load_state(const double* p, int n, int nc, int g, int j, v4d (&x)[2]) {
+#pragma unroll
+    for (int I = 0; I < 2; ++I)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 16 * I + 4 * r + g;
+            x[I][r] = (row < n && j < nc) ? p[row + n * j] : 0.0;
+        }
 }
 
 // The number of squarings, wave-uniform: the smallest sq with ||h G||_1 / 2^sq <= 1/8 (0 for a non-finite norm).  ||h G||_1 is the
@@ -98,6 +123,29 @@ __device__ __forceinline__ void wmul(const v4d (&A)[2][2], v4d (&X)[2][2], const
     const v4d zero = {0.0, 0.0, 0.0, 0.0};
     wcol(A, X, 0, cI, zero);
     wcol(A, X, 1, zero, cI);
+}
+
+// where every Horner chain of the form starts: R = I / deg!   (IdB: the identity's diagonal tile, identity_B(g, j))
+__device__ __forceinline__ void horner_top(const v4d& IdB, v4d (&R)[2][2]) {
+    const v4d zero = {0.0, 0.0, 0.0, 0.0};
+    R[0][0] = kInvFact[kDeg] * IdB; R[0][1] = zero; R[1][0] = zero; R[1][1] = kInvFact[kDeg] * IdB;
+}
+
+// R = exp(hs 2^sq Y) in D layout from the generator Y in A layout (destroyed: it holds the transposed E of the last squaring).
+// Y <- hs Y;  Horner: R_deg+1 = I/deg!,  R_k = Y R_k+1 + I/(k-1)!  (the last coefficient is exactly 1: a zero generator gives the
+// identity bits);  sq squarings, E as the left factor through one LDS round trip each.
+__device__ __forceinline__ void exp_plain(double* scr, v4d (&Y)[2][2], double hs, int sq, const v4d& IdB, int g, int j,
+                                          v4d (&R)[2][2]) {
+    const v4d zero = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) Y[q >> 1][q & 1] = hs * Y[q >> 1][q & 1];
+    horner_top(IdB, R);
+#pragma unroll 1
+    for (int k = kDeg; k >= 1; --k) wmul(Y, R, kInvFact[k - 1] * IdB);
+    for (int q = 0; q < sq; ++q) {
+        transpose4(scr, R, Y, g, j);          // E in A layout; Y is free from here on
+        wmul(Y, R, zero);
+    }
 }
 
 }  // namespace qc_sweep32

@@ -4,7 +4,9 @@
 // Frechet chain runs beside the Horner chain), one chain per interval serves all m drives, dF/da_k = c_k sum ZT . G_k,
 // dF/dh = -sum KT . G.  Degree 8, threshold 1/8, the 1/k! table, the generator and the squaring rule are the forward kernel's: both files
 // take them from qc_sweep32_common.h; the paired column step and the product with E^T are those of qc_sweep32_walk.h, shared with the
-// stored-state walk of qc_sweep32_open_grad.hip; the wave sum is the family's (qc_sweep_common.h).
+// stored-state walk of qc_sweep32_open_grad.hip; the wave sum and the work item are the family's (qc_sweep_common.h).  The walk
+// restates drive_lane, load_state (qc_sweep32_common.h), exp_pair, outer_kt and contract_image (qc_sweep32_walk.h), which
+// qc_sweep32_noise_grad_kernel and qc_sweep32_jvp_kernel call: here the calls move the registers or the time of <false> ("Shared and restated in the wide kernels").
 //
 // Launches of one call on such a handle (qc_sweep_grad_launch of qc_sweep_grad.hip routes here):
 //   1. qc_sweep_mfma32_kernel: the forward chunk totals, column-major 32 x 32;
@@ -71,15 +73,12 @@ __global__ __launch_bounds__(64 * kGW<PAR>) void qc_sweep32_grad_kernel(const Sw
                                                                        const double* __restrict__ ls, double* __restrict__ gs,
                                                                        double* __restrict__ part) {
     __shared__ double scr_all[kGW<PAR> * kGSl<PAR>];
-    const int lane = threadIdx.x & 63;
-    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kGSl<PAR>;
-    const long long item = (long long)blockIdx.x * kGW<PAR> + wq;
-    if (item >= P.items) return;
-    const long long s = item / P.n_chunks;
-    const int c = (int)(item - s * P.n_chunks);
-    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
-    const int g = lane >> 4, j = lane & 15;
+    const WaveItem w = wave_item(kGW<PAR>);
+    double* __restrict__ scr = scr_all + w.wq * kGSl<PAR>;
+    if (w.item >= P.items) return;
+    const ChunkRange ch = chunk_range(w.item, P.n_chunks, P.chunk, P.n_int);
+    const int lane = w.lane, t0 = ch.t0, t1 = ch.t1, g = lane >> 4, j = lane & 15;
+    const long long item = w.item, s = ch.s;
     const int m = P.m;
     const bool ft = P.off_dt >= 0;
     const v4d IdB = identity_B(g, j);
@@ -168,13 +167,7 @@ __global__ __launch_bounds__(64 * kGW<PAR>) void qc_sweep32_grad_kernel(const Sw
         asm volatile("" : "+v"(ln));
         double out = 0.0, duv = 0.0;      // duv (PAR): lane k holds du_k = sum ZT . G_k; lanes >= m keep 0
         if (PAR ? nde > m : ft) {       // PAR: only with gs (nde = nd = m + 1)
-            // sum_IJ KT[I][J] . Ga[J][I] = sum_IK dY(I, K) . Ga(I, K)
-            double ph = 0.0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ph = fma(dY[q >> 1][q & 1][r], Y[q >> 1][q & 1][r], ph);
-            const double dh = -wave_sum(ph);
+            const double dh = -wave_sum(dot_tiles(dY, Y, 0.0));      // sum_IJ KT[I][J] . Ga[J][I] = sum_IK dY(I, K) . Ga(I, K)
             out = ln == m ? dh : out;
         }
 #pragma unroll
@@ -268,9 +261,9 @@ __global__ __launch_bounds__(64 * kGW<PAR>) void qc_sweep32_grad_kernel(const Sw
 void qc_sweep32_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,
                             double* gs, bool par, double* dgrad_theta, double* dgrad_scale, hipStream_t st) {
     const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
-    const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
+    const unsigned grid = qc_sweep_grid(P, kWaves);
     if (par) {
-        hipLaunchKernelGGL(qc_sweep32_grad_kernel<true>, dim3((unsigned)((P.items + kGW<true> - 1) / kGW<true>)), dim3(64 * kGW<true>), 0, st, P, dZ, dtheta, dscale, (const double*)h->dXs.p,
+        hipLaunchKernelGGL(qc_sweep32_grad_kernel<true>, dim3(qc_sweep_grid(P, kGW<true>)), dim3(64 * kGW<true>), 0, st, P, dZ, dtheta, dscale, (const double*)h->dXs.p,
                            (const double*)h->dLs.p, gs, h->dPart.p);
         qc_sweep_launch_par_reduce(h, S, n_chunks, dgrad_theta, dgrad_scale, st);
     } else

@@ -1,6 +1,7 @@
 // Sweep Hessian products for "mfma32-sweep" handles (16 < 2N <= 32) made with QC_SWEEP_WIDE_HESSIAN in `wide`: the backward walk of
 // qc_sweep_hvp.hip (read its header first: the recurrences, the differentiated antisymmetry identities, the series degree) with every
-// matrix 2 x 2 tiles of 16 x 16, as qc_sweep32_grad.hip is qc_sweep_grad.hip on such tiles.  The mathematics is that file's, line for line.
+// matrix 2 x 2 tiles of 16 x 16, as qc_sweep32_grad.hip is qc_sweep_grad.hip on such tiles.  The chunk-end states come from
+// load_state and the timestep's product from dot_tiles; KT, ZT, the chains and the contraction carry their tangents beside them: written out.
 //
 // Launches of one call on such a handle (qc_sweep_hvp_launch of qc_sweep_hvp.hip routes here):
 //   1. qc_sweep32_jvp_kernel (qc_sweep32_jvp.hip, unchanged, through qc_sweep32_jvp_launch_totals): W_c and Wdot_c as two column-major
@@ -206,15 +207,12 @@ __global__ __launch_bounds__(64 * kWaves) void qc_sweep32_hvp_kernel(const Sweep
                                                                       const double* __restrict__ xts, const double* __restrict__ lts,
                                                                       double* __restrict__ tgs) {
     __shared__ double scr_all[kWaves * kHSl];
-    const int lane = threadIdx.x & 63;
-    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kHSl;
-    const long long item = (long long)blockIdx.x * kWaves + wq;
-    if (item >= P.items) return;
-    const long long s = item / P.n_chunks;
-    const int c = (int)(item - s * P.n_chunks);
-    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
-    const int g = lane >> 4, j = lane & 15;
+    const WaveItem w = wave_item(kWaves);
+    double* __restrict__ scr = scr_all + w.wq * kHSl;
+    if (w.item >= P.items) return;
+    const ChunkRange ch = chunk_range(w.item, P.n_chunks, P.chunk, P.n_int);
+    const int lane = w.lane, t0 = ch.t0, t1 = ch.t1, g = lane >> 4, j = lane & 15;
+    const long long item = w.item, s = ch.s;
     const int m = P.m;
     const bool ft = P.off_dt >= 0;
     const v4d IdB = identity_B(g, j);
@@ -238,21 +236,10 @@ __global__ __launch_bounds__(64 * kWaves) void qc_sweep32_hvp_kernel(const Sweep
     v4d x[2], xd[2], lam[2], lamd[2];
     {
         const int ns = P.n * P.nc;
-        const double* __restrict__ xe = xs + item * ns;
-        const double* __restrict__ le = ls + item * ns;
-        const double* __restrict__ xte = xts + item * ns;
-        const double* __restrict__ lte = lts + item * ns;
-#pragma unroll
-        for (int I = 0; I < 2; ++I)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = 16 * I + 4 * r + g;
-                const bool in = row < P.n && j < P.nc;
-                x[I][r] = in ? xe[row + P.n * j] : 0.0;
-                lam[I][r] = in ? le[row + P.n * j] : 0.0;
-                xd[I][r] = in ? xte[row + P.n * j] : 0.0;
-                lamd[I][r] = in ? lte[row + P.n * j] : 0.0;
-            }
+        load_state(xs + item * ns, P.n, P.nc, g, j, x);
+        load_state(ls + item * ns, P.n, P.nc, g, j, lam);
+        load_state(xts + item * ns, P.n, P.nc, g, j, xd);
+        load_state(lts + item * ns, P.n, P.nc, g, j, lamd);
     }
     // What the loop reads and writes per lane walks down in vector registers (as cp and op in qc_sweep32_noise_grad_kernel): the lane's
     // control and the timestep in Z, the same two in vZ (null without one), the lane's address in tgs, and their strides.  The loop keeps
@@ -339,16 +326,7 @@ __global__ __launch_bounds__(64 * kWaves) void qc_sweep32_hvp_kernel(const Sweep
         double out = 0.0;
         if (ftv >= 0) {
             // sum_IJ (KTd[I][J] . Ga[J][I] + KT[I][J] . Gad[J][I]) = sum_IK (dYd(I, K) . Ga(I, K) + dY(I, K) . Gad(I, K))
-            double ph = 0.0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ph = fma(dYd[q >> 1][q & 1][r], Y[q >> 1][q & 1][r], ph);
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ph = fma(dY[q >> 1][q & 1][r], Yd[q >> 1][q & 1][r], ph);
-            const double dhd = -wave_sum(ph);
+            const double dhd = -wave_sum(dot_tiles(dY, Yd, dot_tiles(dYd, Y, 0.0)));
             out = ln == mu ? dhd : out;
         }
 #pragma unroll
@@ -434,7 +412,7 @@ __global__ __launch_bounds__(64 * kWaves) void qc_sweep32_hvp_kernel(const Sweep
 void qc_sweep32_hvp_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dvZ,
                                 const double* dvtheta, const double* dvscale, int64_t chunk, int64_t n_chunks, double* tgs, hipStream_t st) {
     const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
-    const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
+    const unsigned grid = qc_sweep_grid(P, kWaves);
     hipLaunchKernelGGL(qc_sweep32_hvp_kernel, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, dvZ, dvtheta, dvscale,
                        (const double*)h->dXs.p, (const double*)h->dLs.p, (const double*)h->dXsT.p, (const double*)h->dLsT.p, tgs);
 }

@@ -5,8 +5,9 @@
 //     Wdot <- E_t Wdot + L(h_t G; d(hG)_t) W,  W <- E_t W        over the intervals of the chunk
 // Nothing is reversed: Lindblad generators are served like any others, no flag and no state buffer (two qubits with T1 / T2: 2N = 32).
 //
-// Work item and chunk rule are qc_sweep_mfma32_kernel's: one wavefront per (sample, chunk), the waves of a workgroup (two, see
-// "Registers") never synchronised.  base_matrix, squarings, transpose4 and the 1/k! table come from qc_sweep32_common.h, the paired column
+// Work item and chunk rule are qc_sweep_mfma32_kernel's (wave_item / chunk_range of qc_sweep_common.h): one wavefront per (sample, chunk),
+// the waves of a workgroup (two, see "Registers") never synchronised.  The paired chain is exp_pair of qc_sweep32_walk.h; c[s,k] waits in
+// LDS, so drive_lane is restated.  base_matrix, squarings, transpose4 and the 1/k! table come from qc_sweep32_common.h, the paired column
 // step from qc_sweep32_walk.h (vcol: its R chain is wcol's, operation for operation).  Per interval:
 //   once per wave   Bdot = sum_j vtheta[s,j] P_j (A layout), the lane's vc[s,k] beside c[s,k]
 //   coefficients    al = a c,  aldot = va c + a vc
@@ -75,15 +76,12 @@ __global__ __launch_bounds__(64 * kJW) void qc_sweep32_jvp_kernel(const SweepPar
                                                                       const double* __restrict__ vZ, const double* __restrict__ vtheta,
                                                                       const double* __restrict__ vscale, double* __restrict__ tot) {
     __shared__ double scr_all[kJW * kJSl];
-    const int lane = threadIdx.x & 63;
-    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kJSl;
-    const long long item = (long long)blockIdx.x * kJW + wq;
-    if (item >= P.items) return;
-    const long long s = item / P.n_chunks;
-    const int c = (int)(item - s * P.n_chunks);
-    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
-    const int g = lane >> 4, j = lane & 15;
+    const WaveItem w = wave_item(kJW);
+    double* __restrict__ scr = scr_all + w.wq * kJSl;
+    if (w.item >= P.items) return;
+    const ChunkRange ch = chunk_range(w.item, P.n_chunks, P.chunk, P.n_int);
+    const int lane = w.lane, t0 = ch.t0, t1 = ch.t1, g = lane >> 4, j = lane & 15;
+    const long long item = w.item, s = ch.s;
     const int m = P.m;
     const bool ft = P.off_dt >= 0;
     const bool hasv = vZ != nullptr;
@@ -164,15 +162,8 @@ __global__ __launch_bounds__(64 * kJW) void qc_sweep32_jvp_kernel(const SweepPar
             Y[q >> 1][q & 1] = hs * Y[q >> 1][q & 1];
         }
         // Horner on the pair: Rdot_k = Ydot R_k+1 + Y Rdot_k+1,  R_k = Y R_k+1 + I/(k-1)!
-        v4d R[2][2] = {{kInvFact[kDeg] * IdB, zero}, {zero, kInvFact[kDeg] * IdB}};
-        v4d Rd[2][2] = {{zero, zero}, {zero, zero}};
-#pragma unroll 1
-        for (int k = kDeg; k >= 1; --k) vstep(Y, Yd, R, Rd, kInvFact[k - 1] * IdB);
-        for (int q = 0; q < sq; ++q) {
-            transpose4(scr, R, Y, g, j);          // E, Edot in A layout; Y, Ydot are free from here on
-            transpose4(scr, Rd, Yd, g, j);
-            vstep(Y, Yd, R, Rd, zero);
-        }
+        v4d R[2][2], Rd[2][2];
+        exp_pair(scr, Y, Yd, sq, IdB, g, j, R, Rd);
         transpose4(scr, R, Y, g, j);
         transpose4(scr, Rd, Yd, g, j);
         vstep(Y, Yd, W, Wd, zero);
@@ -199,13 +190,8 @@ __global__ __launch_bounds__(64 * kJW) void qc_sweep32_jvp_kernel(const SweepPar
 
 int qc_sweep32_jvp_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dvZ,
                                  const double* dvtheta, const double* dvscale, hipStream_t st, int64_t* chunk_out, int64_t* n_chunks_out) {
-    int64_t chunk, n_chunks;
-    qc_sweep_chunks(S, h->d.T, &chunk, &n_chunks);
-    QC_SIDE_HIP(h, *qc_sweep_err_slot(), h->grow(h->dTotJ, (size_t)S * n_chunks * 2048));
-    const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
-    const unsigned grid = (unsigned)((P.items + kJW - 1) / kJW);
-    hipLaunchKernelGGL(qc_sweep32_jvp_kernel, dim3(grid), dim3(64 * kJW), 0, st, P, dZ, dtheta, dscale, dvZ, dvtheta, dvscale, h->dTotJ.p);
-    *chunk_out = chunk;
-    *n_chunks_out = n_chunks;
+    SweepParams P;
+    if (int rc = qc_sweep_plan_totals(h, S, h->dTotJ, 2048, &P, chunk_out, n_chunks_out)) return rc;
+    hipLaunchKernelGGL(qc_sweep32_jvp_kernel, dim3(qc_sweep_grid(P, kJW)), dim3(64 * kJW), 0, st, P, dZ, dtheta, dscale, dvZ, dvtheta, dvscale, h->dTotJ.p);
     return QC_OK;
 }

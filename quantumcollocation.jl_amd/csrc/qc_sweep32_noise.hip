@@ -53,20 +53,17 @@ __device__ __forceinline__ LaneCoef lane_coef(const SweepParams& P, int lane, lo
     return c;
 }
 
-// Launch 1: the chunk totals.  qc_sweep_mfma32_kernel with mt generators and the per-lane coefficient source.
+// Launch 1: the chunk totals.  Restates qc_sweep_mfma32_kernel (qc_sweep32.hip; to be changed with it, exp_plain included) with mt generators.
 __global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep32_noise_kernel(const SweepParams P, const double* __restrict__ Z,
                                                                             const double* __restrict__ theta, const double* __restrict__ scale,
                                                                             const double* __restrict__ noise, double* __restrict__ tot) {
     __shared__ double scr_all[kWaves * kScr];
-    const int lane = threadIdx.x & 63;
-    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kScr;
-    const long long item = (long long)blockIdx.x * kWaves + wq;
-    if (item >= P.items) return;
-    const long long s = item / P.n_chunks;
-    const int c = (int)(item - s * P.n_chunks);
-    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
-    const int g = lane >> 4, j = lane & 15;
+    const WaveItem w = wave_item(kWaves);
+    double* __restrict__ scr = scr_all + w.wq * kScr;
+    if (w.item >= P.items) return;
+    const ChunkRange ch = chunk_range(w.item, P.n_chunks, P.chunk, P.n_int);
+    const int lane = w.lane, t0 = ch.t0, t1 = ch.t1, g = lane >> 4, j = lane & 15;
+    const long long item = w.item, s = ch.s;
     const int m = P.m, mt = m + P.p;
     const bool ft = P.off_dt >= 0;
     const v4d IdB = identity_B(g, j);
@@ -119,23 +116,21 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep32_noise_kernel(const 
             for (int r = 0; r < 4; ++r) o[(16 * J + j) * 32 + 16 * I + 4 * r + g] = W[I][J][r];
 }
 
-// Launch 3: the backward walk.  qc_sweep32_grad_kernel<false> with mt generators; gs (S x (T-1) x nd) and gn (S x (T-1) x p) may each be
-// NULL, not both.
+// Launch 3: the backward walk: qc_sweep32_grad_kernel<false> with mt generators, on load_state, outer_kt, dot_tiles and contract_image.  The
+// paired chain and ZT restate exp_pair and qc_sweep32_grad_kernel: the calls move this kernel's registers ("Shared and restated in the wide kernels").
+// gs (S x (T-1) x nd) and gn (S x (T-1) x p) may each be NULL, not both.
 __global__ __launch_bounds__(64 * kWaves) void qc_sweep32_noise_grad_kernel(const SweepParams P, const double* __restrict__ Z,
                                                                              const double* __restrict__ theta, const double* __restrict__ scale,
                                                                              const double* __restrict__ noise, const double* __restrict__ xs,
                                                                              const double* __restrict__ ls, double* __restrict__ gs,
                                                                              double* __restrict__ gn) {
     __shared__ double scr_all[kWaves * kScr];
-    const int lane = threadIdx.x & 63;
-    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kScr;
-    const long long item = (long long)blockIdx.x * kWaves + wq;
-    if (item >= P.items) return;
-    const long long s = item / P.n_chunks;
-    const int c = (int)(item - s * P.n_chunks);
-    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
-    const int g = lane >> 4, j = lane & 15;
+    const WaveItem w = wave_item(kWaves);
+    double* __restrict__ scr = scr_all + w.wq * kScr;
+    if (w.item >= P.items) return;
+    const ChunkRange ch = chunk_range(w.item, P.n_chunks, P.chunk, P.n_int);
+    const int lane = w.lane, t0 = ch.t0, t1 = ch.t1, g = lane >> 4, j = lane & 15;
+    const long long item = w.item, s = ch.s;
     const int m = P.m, mt = m + P.p;
     const bool ft = P.off_dt >= 0;
     const v4d IdB = identity_B(g, j);
@@ -166,20 +161,8 @@ __global__ __launch_bounds__(64 * kWaves) void qc_sweep32_noise_grad_kernel(cons
     asm volatile("" : "+v"(cp), "+v"(cstr), "+v"(op), "+v"(ostr));
 
     v4d x[2], lam[2];
-    {
-        const int ns = P.n * P.nc;
-        const double* __restrict__ xe = xs + item * ns;
-        const double* __restrict__ le = ls + item * ns;
-#pragma unroll
-        for (int I = 0; I < 2; ++I)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = 16 * I + 4 * r + g;
-                const bool in = row < P.n && j < P.nc;
-                x[I][r] = in ? xe[row + P.n * j] : 0.0;
-                lam[I][r] = in ? le[row + P.n * j] : 0.0;
-            }
-    }
+    load_state(xs + item * (P.n * P.nc), P.n, P.nc, g, j, x);
+    load_state(ls + item * (P.n * P.nc), P.n, P.nc, g, j, lam);
 
     const double hfix = opaque_scalar(P.dt_fixed);
     const double* __restrict__ z = Z + (long long)(t1 - 1) * P.zdim;
@@ -197,34 +180,14 @@ __global__ __launch_bounds__(64 * kWaves) void qc_sweep32_noise_grad_kernel(cons
         generator(P.img, mt, al, base, lane, Y);
         const int sq = squarings(Y, h);      // the rule of the forward kernel: one function
         const double hs = h * ldexp(1.0, -sq);
-        // KT = lambda x^T of knot t+1 (D layout), from the transposed tiles of both; dY in A layout is KT with the block index swapped
-        {
-            const v4d in[4] = {x[0], x[1], lam[0], lam[1]};
-            v4d tr[4];
-            lds_transpose16_multi<4>(scr, in, tr, g, j);
-            v4d k00 = zero, k01 = zero, k10 = zero, k11 = zero;
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                k00 = __builtin_amdgcn_mfma_f64_16x16x4f64(tr[2][kk], tr[0][kk], k00, 0, 0, 0);
-                k01 = __builtin_amdgcn_mfma_f64_16x16x4f64(tr[2][kk], tr[1][kk], k01, 0, 0, 0);
-                k10 = __builtin_amdgcn_mfma_f64_16x16x4f64(tr[3][kk], tr[0][kk], k10, 0, 0, 0);
-                k11 = __builtin_amdgcn_mfma_f64_16x16x4f64(tr[3][kk], tr[1][kk], k11, 0, 0, 0);
-            }
-            dY[0][0] = k00; dY[1][0] = k01; dY[0][1] = k10; dY[1][1] = k11;      // dY(I, K) = KT[K][I]
-        }
+        outer_kt(scr, x, lam, g, j, dY);      // KT = lambda x^T of knot t+1
         // an opaque copy of the lane index: the lane compares below are made per interval instead of living in scalar registers across
         // the loop (as in qc_sweep32_grad_kernel)
         int ln = lane;
         asm volatile("" : "+v"(ln));
         double out = 0.0;      // lane u < mt: generator u (the drives, then the noise values); lane mt: the timestep (free timesteps)
         if (ft) {
-            // sum_IJ KT[I][J] . Ga[J][I] = sum_IK dY(I, K) . Ga(I, K)
-            double ph = 0.0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ph = fma(dY[q >> 1][q & 1][r], Y[q >> 1][q & 1][r], ph);
-            const double dh = -wave_sum(ph);
+            const double dh = -wave_sum(dot_tiles(dY, Y, 0.0));      // sum_IJ KT[I][J] . Ga[J][I] = sum_IK dY(I, K) . Ga(I, K)
             out = ln == mt ? dh : out;
         }
 #pragma unroll
@@ -258,15 +221,7 @@ __global__ __launch_bounds__(64 * kWaves) void qc_sweep32_noise_grad_kernel(cons
         }
 #pragma unroll 1
         for (int u = 0; u < mt; ++u) {
-            const double* __restrict__ Gu = P.img + (size_t)(1 + u) * 1024;
-            double pu = 0.0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const v4d t4 = load_image_tile(Gu + q * 256, lane);       // tile (J, I) = q against ZT[I][J]
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pu = fma(Y[q & 1][q >> 1][r], t4[r], pu);
-            }
-            const double du = wave_sum(pu);
+            const double du = contract_image(Y, P.img + (size_t)(1 + u) * 1024, lane);
             out = ln == u ? du * cl : out;      // a perturbation lane's factor is 1
         }
         if (op) *op = out;
@@ -282,21 +237,16 @@ __global__ __launch_bounds__(64 * kWaves) void qc_sweep32_noise_grad_kernel(cons
 
 int qc_sweep32_noise_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dnoise,
                                    hipStream_t st, int64_t* chunk_out, int64_t* n_chunks_out) {
-    int64_t chunk, n_chunks;
-    qc_sweep_chunks(S, h->d.T, &chunk, &n_chunks);
-    QC_SIDE_HIP(h, *qc_sweep_err_slot(), h->grow(h->dTot, (size_t)S * n_chunks * 1024));
-    const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
-    const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
-    hipLaunchKernelGGL(qc_sweep32_noise_kernel, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, dnoise, h->dTot.p);
-    *chunk_out = chunk;
-    *n_chunks_out = n_chunks;
+    SweepParams P;
+    if (int rc = qc_sweep_plan_totals(h, S, h->dTot, 1024, &P, chunk_out, n_chunks_out)) return rc;
+    hipLaunchKernelGGL(qc_sweep32_noise_kernel, dim3(qc_sweep_grid(P, kWaves)), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, dnoise, h->dTot.p);
     return QC_OK;
 }
 
 void qc_sweep32_noise_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dnoise,
                                   int64_t chunk, int64_t n_chunks, double* gs, double* gn, hipStream_t st) {
     const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
-    const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
+    const unsigned grid = qc_sweep_grid(P, kWaves);
     hipLaunchKernelGGL(qc_sweep32_noise_grad_kernel, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, dnoise,
                        (const double*)h->dXs.p, (const double*)h->dLs.p, gs, gn);
 }

@@ -28,6 +28,9 @@
 //      shares to part[item][p + m], reduced by qc_sweep_par_reduce_kernel; gs may be NULL.  The per-interval values of both flavours are the
 //      same operations on the same operands: the same bits.
 // No atomics; every sum in a fixed order; no output's bits depend on which others were asked for.  Resources: DESIGN.md 5.8.7.
+// The store kernel is built on drive_lane, load_state and exp_plain (qc_sweep32_common.h).  The walk restates drive_lane, load_state,
+// exp_pair and, in <true>, the chunk end of qc_sweep32_grad_kernel<true>: the calls move the registers of <false>, and no bench times
+// <true> ("Shared and restated in the wide kernels").  The work item is wave_item / chunk_range of qc_sweep_common.h.
 #include <math.h>
 
 #include <string>
@@ -63,36 +66,27 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep32_open_store_kernel(c
                                                                                  const double* __restrict__ init, const double* __restrict__ xs,
                                                                                  double* __restrict__ xall) {
     __shared__ double scr_all[kWaves * kScr];
-    const int lane = threadIdx.x & 63;
-    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kScr;
-    const long long item = (long long)blockIdx.x * kWaves + wq;
-    if (item >= P.items) return;
-    const long long s = item / P.n_chunks;
-    const int c = (int)(item - s * P.n_chunks);
-    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
-    const int g = lane >> 4, j = lane & 15;
+    const WaveItem w = wave_item(kWaves);
+    double* __restrict__ scr = scr_all + w.wq * kScr;
+    if (w.item >= P.items) return;
+    const ChunkRange ch = chunk_range(w.item, P.n_chunks, P.chunk, P.n_int);
+    const int lane = w.lane, c = ch.c, t0 = ch.t0, t1 = ch.t1, g = lane >> 4, j = lane & 15;
+    const long long item = w.item, s = ch.s;
     const int m = P.m;
     const bool ft = P.off_dt >= 0;
     const v4d IdB = identity_B(g, j);
-    const v4d zero = {0.0, 0.0, 0.0, 0.0};
     const int ns = P.n * P.nc;
 
     v4d base[2][2];
     base_matrix(P.img, m, P.p, theta, s, lane, base);
-    const int kl = lane < m ? lane : (m > 0 ? m - 1 : 0);
-    const double cl = (scale && m > 0) ? scale[s * m + kl] : 1.0;
+    const DriveLane dl = drive_lane(scale, m, s, lane);
+    const int kl = dl.kl;
+    const double cl = dl.cl;
 
     v4d x[2];
     {
         const double* __restrict__ x0 = c == 0 ? init : xs + (item - 1) * ns;      // the previous chunk's end: same sample, c >= 1
-#pragma unroll
-        for (int I = 0; I < 2; ++I)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = 16 * I + 4 * r + g;
-                x[I][r] = (row < P.n && j < P.nc) ? x0[row + P.n * j] : 0.0;
-            }
+        load_state(x0, P.n, P.nc, g, j, x);
     }
     // the lane's control of the interval (lane l: drive min(l, m-1)) and, `dto` entries further, the timestep: one pointer walking up
     const double* ap = Z + (long long)t0 * P.zdim + P.off_a + kl;
@@ -129,16 +123,8 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep32_open_store_kernel(c
         v4d Y[2][2];
         generator(P.img, m, al, base, lane, Y);
         const int sq = squarings(Y, h);
-        const double hs = h * ldexp(1.0, -sq);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) Y[q >> 1][q & 1] = hs * Y[q >> 1][q & 1];
-        v4d R[2][2] = {{kInvFact[kDeg] * IdB, zero}, {zero, kInvFact[kDeg] * IdB}};
-#pragma unroll 1
-        for (int k = kDeg; k >= 1; --k) wmul(Y, R, kInvFact[k - 1] * IdB);
-        for (int q = 0; q < sq; ++q) {
-            transpose4(scr, R, Y, g, j);          // E in A layout; Y is free from here on
-            wmul(Y, R, zero);
-        }
+        v4d R[2][2];
+        exp_plain(scr, Y, h * ldexp(1.0, -sq), sq, IdB, g, j, R);
         transpose4(scr, R, Y, g, j);
         xapply(Y, x);
         av = av_n;
@@ -169,15 +155,12 @@ __global__ __launch_bounds__(64 * kOW<PAR>) void qc_sweep32_open_grad_kernel(con
                                                                             const double* __restrict__ xall, const double* __restrict__ ls,
                                                                             double* __restrict__ gs, double* __restrict__ part) {
     __shared__ double scr_all[kOW<PAR> * kOSl<PAR>];
-    const int lane = threadIdx.x & 63;
-    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kOSl<PAR>;
-    const long long item = (long long)blockIdx.x * kOW<PAR> + wq;
-    if (item >= P.items) return;
-    const long long s = item / P.n_chunks;
-    const int c = (int)(item - s * P.n_chunks);
-    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
-    const int g = lane >> 4, j = lane & 15;
+    const WaveItem w = wave_item(kOW<PAR>);
+    double* __restrict__ scr = scr_all + w.wq * kOSl<PAR>;
+    if (w.item >= P.items) return;
+    const ChunkRange ch = chunk_range(w.item, P.n_chunks, P.chunk, P.n_int);
+    const int lane = w.lane, t0 = ch.t0, t1 = ch.t1, g = lane >> 4, j = lane & 15;
+    const long long item = w.item, s = ch.s;
     const int m = P.m;
     const bool ft = P.off_dt >= 0;
     const v4d IdB = identity_B(g, j);
@@ -187,7 +170,7 @@ __global__ __launch_bounds__(64 * kOW<PAR>) void qc_sweep32_open_grad_kernel(con
     // ---- once per wave: the sample's base matrix, the adjoint at the chunk's end, the lane's view of the stored states ----------------
     v4d base[2][2];
     base_matrix(P.img, m, P.p, theta, s, lane, base);
-    const int kl = lane < m ? lane : (m > 0 ? m - 1 : 0);
+    const int kl = lane < m ? lane : (m > 0 ? m - 1 : 0);      // restates drive_lane: the shared form moves the flavour <true>, which no bench times
     const double cl = (scale && m > 0) ? scale[s * m + kl] : 1.0;
 
     v4d lam[2];
@@ -370,13 +353,13 @@ __global__ __launch_bounds__(64 * kOW<PAR>) void qc_sweep32_open_grad_kernel(con
 void qc_sweep32_open_launch_walk(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
                                  int64_t chunk, int64_t n_chunks, double* gs, bool par, double* dgrad_theta, double* dgrad_scale, hipStream_t st) {
     const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
-    hipLaunchKernelGGL(qc_sweep32_open_store_kernel, dim3((unsigned)((P.items + kWaves - 1) / kWaves)), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale,
+    hipLaunchKernelGGL(qc_sweep32_open_store_kernel, dim3(qc_sweep_grid(P, kWaves)), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale,
                        dinit, (const double*)h->dXs.p, h->dXall.p);
     if (par) {
-        hipLaunchKernelGGL(qc_sweep32_open_grad_kernel<true>, dim3((unsigned)((P.items + kOW<true> - 1) / kOW<true>)), dim3(64 * kOW<true>), 0, st, P, dZ,
+        hipLaunchKernelGGL(qc_sweep32_open_grad_kernel<true>, dim3(qc_sweep_grid(P, kOW<true>)), dim3(64 * kOW<true>), 0, st, P, dZ,
                            dtheta, dscale, (const double*)h->dXall.p, (const double*)h->dLs.p, gs, h->dPart.p);
         qc_sweep_launch_par_reduce(h, S, n_chunks, dgrad_theta, dgrad_scale, st);
     } else
-        hipLaunchKernelGGL(qc_sweep32_open_grad_kernel<false>, dim3((unsigned)((P.items + kOW<false> - 1) / kOW<false>)), dim3(64 * kOW<false>), 0, st, P, dZ,
+        hipLaunchKernelGGL(qc_sweep32_open_grad_kernel<false>, dim3(qc_sweep_grid(P, kOW<false>)), dim3(64 * kOW<false>), 0, st, P, dZ,
                            dtheta, dscale, (const double*)h->dXall.p, (const double*)h->dLs.p, gs, (double*)nullptr);
 }

@@ -1,7 +1,8 @@
 // Device code that every sweep kernel shares, whatever its tile form ("mfma16-sweep": qc_sweep16_common.h, "mfma32-sweep":
 // qc_sweep32_common.h): the series' degree and threshold, the 1 / k! table, the DPP move, the fixed-order wave sum and the scalar tail of
-// the squaring rule.  The closed walks reverse the forward step, and the stored states match the stored-state walks, only if every kernel
-// of the family chooses the same number of squarings from the same norm: the rule is here once.
+// the squaring rule, and the work item of the (sample, chunk) kernels (wave_item, chunk_range).  The closed walks reverse the forward step,
+// and the stored states match the stored-state walks, only if every kernel of the family chooses the same number of squarings from the same
+// norm: the rule is here once.
 #pragma once
 #include <math.h>
 
@@ -54,6 +55,30 @@ __device__ __forceinline__ int squarings_of_norm(double best, bool bad) {
         sq = sq < 0 ? 0 : (sq > 60 ? 60 : sq);
     }
     return __builtin_amdgcn_readfirstlane(sq);
+}
+
+// The work item of every kernel that runs one wavefront per (sample, chunk of consecutive intervals): wave wq of a workgroup of `waves`
+// takes item blockIdx.x * waves + wq = s * n_chunks + c and walks the intervals t0 .. t1-1 of sample s.  Two steps, by value: a wave whose
+// item is not below P.items returns between them, so the launch parameters of the second are still read behind that branch.  The wave's
+// LDS slice, scr_all + wq * (doubles a wave), is formed in the kernel: handed through a function the array loses its address space too late.
+struct WaveItem { int lane, wq; long long item; };
+struct ChunkRange { long long s; int c, t0, t1; };
+
+__device__ __forceinline__ WaveItem wave_item(int waves) {
+    WaveItem w;
+    w.lane = threadIdx.x & 63;
+    w.wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    w.item = (long long)blockIdx.x * waves + w.wq;
+    return w;
+}
+
+__device__ __forceinline__ ChunkRange chunk_range(long long item, int n_chunks, int chunk, int n_int) {
+    ChunkRange r;
+    r.s = item / n_chunks;
+    r.c = (int)(item - r.s * n_chunks);
+    r.t0 = r.c * chunk;
+    r.t1 = min(n_int, r.t0 + chunk);
+    return r;
 }
 
 }  // namespace qc_sweep_common

@@ -117,15 +117,12 @@ __global__ __launch_bounds__(64 * kWaves, 1) void qc_sweep_hvp_kernel(const Swee
                                                                         const double* __restrict__ xts, const double* __restrict__ lts,
                                                                         double* __restrict__ tgs) {
     __shared__ double scr_all[kWaves * kHSlice];
-    const int lane = threadIdx.x & 63;
-    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kHSlice;
-    const long long item = (long long)blockIdx.x * kWaves + wq;
-    if (item >= P.items) return;
-    const long long s = item / P.n_chunks;
-    const int c = (int)(item - s * P.n_chunks);
-    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
-    const int g = lane >> 4, j = lane & 15;
+    const WaveItem w = wave_item(kWaves);
+    double* __restrict__ scr = scr_all + w.wq * kHSlice;
+    if (w.item >= P.items) return;
+    const ChunkRange ch = chunk_range(w.item, P.n_chunks, P.chunk, P.n_int);
+    const int lane = w.lane, t0 = ch.t0, t1 = ch.t1, g = lane >> 4, j = lane & 15;
+    const long long item = w.item, s = ch.s;
     const int m = P.m;
     const bool ft = P.off_dt >= 0;
     const bool hasv = vZ != nullptr;
@@ -444,7 +441,7 @@ static int qc_sweep_hvp_launch(qc_sweep* h, const char* who, const double* dZ, c
                            h->dXs.p, h->dXsT.p, h->dLs.p, h->dLsT.p, dtgrad_init);
         if (want_walk) {
             const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
-            const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
+            const unsigned grid = qc_sweep_grid(P, kWaves);
 #define QC_HVP_LAUNCH(M_)                                                                                                                 \
     hipLaunchKernelGGL(qc_sweep_hvp_kernel<M_>, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, dvZ, dvtheta, dvscale,       \
                        (const double*)h->dXs.p, (const double*)h->dLs.p, (const double*)h->dXsT.p, (const double*)h->dLsT.p, tgs)

@@ -1,6 +1,6 @@
 // What qc_sweep.hip (forward sweep), qc_sweep_grad.hip (its adjoint), qc_sweep_open_grad.hip and qc_sweep32_open_grad.hip (the adjoint on stored states), qc_sweep_vjp.hip (the pullback of the final states),
 // qc_sweep_jvp.hip (their pushforward), qc_sweep_hvp.hip and qc_sweep32_hvp.hip (the tangent of the pullback) and qc_sweep_noise.hip (noise trajectories) share: the handle with its scratch and staging buffers, the descriptor and argument checks, the launch
-// parameters of the (sample, chunk) kernels (SweepParams, qc_sweep_params) and the launch of the forward chunk totals (with it the chunk rule).  Not part of the ABI.
+// parameters of the (sample, chunk) kernels (SweepParams, qc_sweep_params), the preamble of every launch of chunk totals (qc_sweep_plan_totals: chunk rule, scratch, parameters) and those launches.  Not part of the ABI.
 #pragma once
 
 #include <string>
@@ -114,6 +114,10 @@ int qc_sweep_desc_form(const qc_sweep_desc* d);
 std::string qc_sweep_per_sample_why(const qc_sweep_desc* d);
 // the chunk rule of the MFMA forms
 void qc_sweep_chunks(int64_t S, int64_t T, int64_t* chunk, int64_t* n_chunks);
+// What every launch of chunk totals starts with: the chunk rule for S samples, `buf` grown to S x n_chunks x doubles_per_item, the launch
+// parameters in *P, the rule's result in *chunk, *n_chunks; QC_OK or the failed allocation's code.  qc_sweep_grid: workgroups of `waves` waves.
+int qc_sweep_plan_totals(qc_sweep* h, int64_t S, qc_buf& buf, size_t doubles_per_item, SweepParams* P, int64_t* chunk, int64_t* n_chunks);
+inline unsigned qc_sweep_grid(const SweepParams& P, int waves) { return (unsigned)((P.items + waves - 1) / waves); }
 // "mfma16-sweep" handles: grows h->dTot and launches qc_sweep_mfma16_kernel on `st` (S x n_chunks tiles of 256 doubles)
 int qc_sweep_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, hipStream_t st, int64_t* chunk,
                            int64_t* n_chunks);

@@ -66,15 +66,12 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_jvp_kernel(const Swee
                                                                         const double* __restrict__ vZ, const double* __restrict__ vtheta,
                                                                         const double* __restrict__ vscale, double* __restrict__ tot) {
     __shared__ double scr_all[kWaves * 2 * kTile];
-    const int lane = threadIdx.x & 63;
-    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * (2 * kTile);
-    const long long item = (long long)blockIdx.x * kWaves + wq;
-    if (item >= P.items) return;
-    const long long s = item / P.n_chunks;
-    const int c = (int)(item - s * P.n_chunks);
-    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
-    const int g = lane >> 4, j = lane & 15;
+    const WaveItem w = wave_item(kWaves);
+    double* __restrict__ scr = scr_all + w.wq * (2 * kTile);
+    if (w.item >= P.items) return;
+    const ChunkRange ch = chunk_range(w.item, P.n_chunks, P.chunk, P.n_int);
+    const int lane = w.lane, t0 = ch.t0, t1 = ch.t1, g = lane >> 4, j = lane & 15;
+    const long long item = w.item, s = ch.s;
     const int m = P.m;
     const bool ft = P.off_dt >= 0;
     const bool hasv = vZ != nullptr;
@@ -332,18 +329,13 @@ extern "C" int qc_sweep_desc_jvp_supported(const qc_sweep_desc* d, int32_t* supp
 int qc_sweep_jvp_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dvZ,
                                const double* dvtheta, const double* dvscale, hipStream_t st, int64_t* chunk_out, int64_t* n_chunks_out) {
     if (h->mfma32) return qc_sweep32_jvp_launch_totals(h, dZ, S, dtheta, dscale, dvZ, dvtheta, dvscale, st, chunk_out, n_chunks_out);
-    std::string& slot = *qc_sweep_err_slot();
-    int64_t chunk, n_chunks;
-    qc_sweep_chunks(S, h->d.T, &chunk, &n_chunks);
-    QC_SIDE_HIP(h, slot, h->grow(h->dTotJ, (size_t)S * n_chunks * 512));
-    const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
-    const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
-#define QC_JVP_LAUNCH(M_) \
-    hipLaunchKernelGGL(qc_sweep_jvp_kernel<M_>, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, dvZ, dvtheta, dvscale, h->dTotJ.p)
+    SweepParams P;
+    if (int rc = qc_sweep_plan_totals(h, S, h->dTotJ, 512, &P, chunk_out, n_chunks_out)) return rc;
+#define QC_JVP_LAUNCH(M_)                                                                                                                    \
+    hipLaunchKernelGGL(qc_sweep_jvp_kernel<M_>, dim3(qc_sweep_grid(P, kWaves)), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, dvZ, dvtheta, \
+                       dvscale, h->dTotJ.p)
     QC_SWEEP_FOR_M(P.m, QC_JVP_LAUNCH);
 #undef QC_JVP_LAUNCH
-    *chunk_out = chunk;
-    *n_chunks_out = n_chunks;
     return QC_OK;
 }
 

@@ -75,15 +75,12 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_noise_kernel(const Sw
                                                                           const double* __restrict__ theta, const double* __restrict__ scale,
                                                                           const double* __restrict__ noise, double* __restrict__ tot) {
     __shared__ double scr_all[kWaves * kTile];
-    const int lane = threadIdx.x & 63;
-    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kTile;
-    const long long item = (long long)blockIdx.x * kWaves + wq;
-    if (item >= P.items) return;
-    const long long s = item / P.n_chunks;
-    const int c = (int)(item - s * P.n_chunks);
-    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
-    const int g = lane >> 4, j = lane & 15;
+    const WaveItem w = wave_item(kWaves);
+    double* __restrict__ scr = scr_all + w.wq * kTile;
+    if (w.item >= P.items) return;
+    const ChunkRange ch = chunk_range(w.item, P.n_chunks, P.chunk, P.n_int);
+    const int lane = w.lane, t0 = ch.t0, t1 = ch.t1, g = lane >> 4, j = lane & 15;
+    const long long item = w.item, s = ch.s;
     const int m = P.m, mt = m + P.p;
     const bool ft = P.off_dt >= 0;
     const v4d IdB = identity_B(g, j);
@@ -139,15 +136,12 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_noise_grad_kernel(con
                                                                                const double* __restrict__ ls, double* __restrict__ gs,
                                                                                double* __restrict__ gn) {
     __shared__ double scr_all[kWaves * kWalkSlice<false>];
-    const int lane = threadIdx.x & 63;
-    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kWalkSlice<false>;
-    const long long item = (long long)blockIdx.x * kWaves + wq;
-    if (item >= P.items) return;
-    const long long s = item / P.n_chunks;
-    const int c = (int)(item - s * P.n_chunks);
-    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
-    const int g = lane >> 4, j = lane & 15;
+    const WaveItem w = wave_item(kWaves);
+    double* __restrict__ scr = scr_all + w.wq * kWalkSlice<false>;
+    if (w.item >= P.items) return;
+    const ChunkRange ch = chunk_range(w.item, P.n_chunks, P.chunk, P.n_int);
+    const int lane = w.lane, t0 = ch.t0, t1 = ch.t1, g = lane >> 4, j = lane & 15;
+    const long long item = w.item, s = ch.s;
     const int m = P.m, mt = m + P.p;
     const bool ft = P.off_dt >= 0;
     const v4d IdB = identity_B(g, j);
@@ -251,17 +245,12 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_noise_grad_kernel(con
 int noise_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dnoise, hipStream_t st,
                         int64_t* chunk_out, int64_t* n_chunks_out) {
     if (h->wide_noise) return qc_sweep32_noise_launch_totals(h, dZ, S, dtheta, dscale, dnoise, st, chunk_out, n_chunks_out);      // the only mfma32 handles in scope
-    std::string& slot = *qc_sweep_err_slot();
-    int64_t chunk, n_chunks;
-    qc_sweep_chunks(S, h->d.T, &chunk, &n_chunks);
-    QC_SIDE_HIP(h, slot, h->grow(h->dTot, (size_t)S * n_chunks * 256));
-    const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
-    const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
-#define QC_NOISE_LAUNCH(M_) hipLaunchKernelGGL(qc_sweep_noise_kernel<M_>, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, dnoise, h->dTot.p)
+    SweepParams P;
+    if (int rc = qc_sweep_plan_totals(h, S, h->dTot, 256, &P, chunk_out, n_chunks_out)) return rc;
+#define QC_NOISE_LAUNCH(M_) \
+    hipLaunchKernelGGL(qc_sweep_noise_kernel<M_>, dim3(qc_sweep_grid(P, kWaves)), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, dnoise, h->dTot.p)
     QC_SWEEP_FOR_M(P.m + P.p, QC_NOISE_LAUNCH);
 #undef QC_NOISE_LAUNCH
-    *chunk_out = chunk;
-    *n_chunks_out = n_chunks;
     return QC_OK;
 }
 
@@ -344,7 +333,7 @@ int noise_grad_launch(qc_sweep* h, const char* who, const double* dZ, const doub
     if ((want_grad || dgrad_noise) && h->wide_noise) {
         qc_sweep32_noise_launch_walk(h, dZ, S, dtheta, dscale, dnoise, chunk, n_chunks, want_grad ? gsamp : nullptr, dgrad_noise, st);
     } else if (want_grad || dgrad_noise) {
-        const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
+        const unsigned grid = qc_sweep_grid(P, kWaves);
         double* gs = want_grad ? gsamp : nullptr;
 #define QC_NOISE_GRAD_LAUNCH(M_)                                                                                                         \
     hipLaunchKernelGGL(qc_sweep_noise_grad_kernel<M_>, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, dnoise,               \

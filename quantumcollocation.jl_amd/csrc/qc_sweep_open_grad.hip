@@ -58,15 +58,12 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_open_store_kernel(con
                                                                                const double* __restrict__ init, const double* __restrict__ xs,
                                                                                double* __restrict__ xall) {
     __shared__ double scr_all[kWaves * kTile];
-    const int lane = threadIdx.x & 63;
-    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kTile;
-    const long long item = (long long)blockIdx.x * kWaves + wq;
-    if (item >= P.items) return;
-    const long long s = item / P.n_chunks;
-    const int c = (int)(item - s * P.n_chunks);
-    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
-    const int g = lane >> 4, j = lane & 15;
+    const WaveItem w = wave_item(kWaves);
+    double* __restrict__ scr = scr_all + w.wq * kTile;
+    if (w.item >= P.items) return;
+    const ChunkRange ch = chunk_range(w.item, P.n_chunks, P.chunk, P.n_int);
+    const int lane = w.lane, c = ch.c, t0 = ch.t0, t1 = ch.t1, g = lane >> 4, j = lane & 15;
+    const long long item = w.item, s = ch.s;
     const int m = P.m;
     const bool ft = P.off_dt >= 0;
     const v4d IdB = identity_B(g, j);
@@ -140,15 +137,12 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_open_grad_kernel(cons
                                                                               double* __restrict__ gs, double* __restrict__ part) {
     constexpr bool kTight = M >= 6 || PAR;      // the flavours whose loop-invariant lane masks do not fit the scalar registers
     __shared__ double scr_all[kWaves * kWalkSlice<PAR>];
-    const int lane = threadIdx.x & 63;
-    const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* __restrict__ scr = scr_all + wq * kWalkSlice<PAR>;
-    const long long item = (long long)blockIdx.x * kWaves + wq;
-    if (item >= P.items) return;
-    const long long s = item / P.n_chunks;
-    const int c = (int)(item - s * P.n_chunks);
-    const int t0 = c * P.chunk, t1 = min(P.n_int, t0 + P.chunk);
-    const int g = lane >> 4, j = lane & 15;
+    const WaveItem w = wave_item(kWaves);
+    double* __restrict__ scr = scr_all + w.wq * kWalkSlice<PAR>;
+    if (w.item >= P.items) return;
+    const ChunkRange ch = chunk_range(w.item, P.n_chunks, P.chunk, P.n_int);
+    const int lane = w.lane, t0 = ch.t0, t1 = ch.t1, g = lane >> 4, j = lane & 15;
+    const long long item = w.item, s = ch.s;
     const int m = P.m;
     const bool ft = P.off_dt >= 0;
     const v4d IdB = identity_B(g, j);
@@ -292,7 +286,7 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_open_grad_kernel(cons
 void qc_sweep_open_launch_walk(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
                                int64_t chunk, int64_t n_chunks, double* gs, bool want_par, double* dgrad_theta, double* dgrad_scale, hipStream_t st) {
     const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
-    const unsigned grid = (unsigned)((P.items + kWaves - 1) / kWaves);
+    const unsigned grid = qc_sweep_grid(P, kWaves);
 #define QC_OPEN_LAUNCH(M_)                                                                                                                      \
     do {                                                                                                                                        \
         hipLaunchKernelGGL(qc_sweep_open_store_kernel<M_>, dim3(grid), dim3(64 * kWaves), 0, st, P, dZ, dtheta, dscale, dinit,                  \
