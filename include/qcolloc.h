@@ -644,6 +644,18 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * same descriptor without the bit, and at 2N <= 16 (whose Hessian product needs no bit) and in the rollout-per-sample form it does nothing.
  * The valid values are 0, 1, 3, 9, 11, 17, 19, 25 and 27, each of the eight odd ones | 64 (65 .. 91), and each of those sixteen odd
  * values | 256; any other value (bit 1, 3, 4, 6 or 8 without bit 0, bit 2, 5 and 7 among them) is QC_ERR_INVALID.
+ * Bit 10, QC_SWEEP_WIDE_64 (any of those thirty-two odd values | 1024; 1024 alone and bit 9 are QC_ERR_INVALID), takes the matrix cores
+ * up to 2N = 64: a descriptor with 32 < 2N <= 64 and up to 16 drives (5 qubits: N = 32 with 10 drives; three coupled three-level
+ * transmons: 2N = 54; a Lindblad model of a five-level system: N = 25) then takes a third matrix-core form, "mfma64-sweep"
+ * (qc_sweep64.hip): 4 x 4 tiles a matrix, the matrices in LDS, one WORKGROUP of 16 wavefronts per (sample, chunk of intervals), and the
+ * chunk rule with that item's fill constant (n_chunks = 1 once S >= 256, one workgroup per compute unit; else ceil(256 / S) chunks, at
+ * most ceil(sqrt(T-1))).  The mathematics is the family's.  That form serves the FORWARD sweep only, qc_sweep_eval*: final states
+ * and fidelities.  qc_sweep_grad*, qc_sweep_grad_params*, qc_sweep_vjp*, qc_sweep_jvp*, qc_sweep_hvp* and qc_sweep_noise_* return
+ * QC_ERR_UNSUPPORTED on such a handle, whatever the other bits say, and the qc_sweep_desc_*_supported queries answer 0 with a reason
+ * that names the form and the size ("... the mfma64-sweep form (2N = 54) ...").  Descriptors with 2N <= 32 ignore the bit completely:
+ * form, launch, kernel name, every *_supported answer and every output bit are those of the same descriptor without it.  Without the
+ * bit nothing changes anywhere.  Not in that form: more than 16 drives (rollout-per-sample), a state-action form that skips the
+ * propagator for kets, 2N > 64 (QC_ERR_UNSUPPORTED as before).
  * reserved1[0] = QC_SWEEP_STORED_STATES chooses reverse mode by the STORED-STATE walk: qc_sweep_grad*, qc_sweep_grad_params* and
  * qc_sweep_vjp* then keep the forward states x_0 .. x_{T-2} of every sample in handle scratch (S x (T-1) x 2N x cols doubles) and read
  * them on the way back instead of reversing the step, which serves ANY generators in the "mfma16-sweep" form: Lindblad generators
@@ -671,7 +683,7 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * derivatives are not served there at all), checkpointing inside a chunk, Hessian products and noise gradients of open
  * systems, pushforwards on "mfma32-sweep" and "rollout-per-sample" handles (the former unless `wide` has QC_SWEEP_WIDE_TANGENT), Hessian
  * products on "rollout-per-sample" handles and on "mfma32-sweep" handles without QC_SWEEP_WIDE_HESSIAN, several directions per
- * call, tangents of grad_theta / grad_scale, several devices. */
+ * call, tangents of grad_theta / grad_scale, several devices; in the "mfma64-sweep" form everything but the forward sweep. */
 #define QC_MAX_PERT 8
 #define QC_SWEEP_FID_NONE (-1)   /* qc_sweep_desc.fid_kind: final states only */
 #define QC_SWEEP_WIDE 1          /* qc_sweep_desc.wide, bit 0 */
@@ -680,6 +692,7 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
 #define QC_SWEEP_WIDE_TANGENT 16 /* qc_sweep_desc.wide, bit 4: the mfma32-sweep form serves pushforwards (qc_sweep_jvp*); only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_WIDE_NOISE 64   /* qc_sweep_desc.wide, bit 6: the mfma32-sweep form serves noise-trajectory sweeps and their gradients (qc_sweep_noise_*); only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_WIDE_HESSIAN 256 /* qc_sweep_desc.wide, bit 8: the mfma32-sweep form serves Hessian products of closed systems (qc_sweep_hvp*); only together with QC_SWEEP_WIDE */
+#define QC_SWEEP_WIDE_64 1024    /* qc_sweep_desc.wide, bit 10: 32 < 2N <= 64 with up to 16 drives takes the matrix cores ("mfma64-sweep", qc_sweep_eval* only); ignored at 2N <= 32; only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_STORED_STATES 1 /* qc_sweep_desc.reserved1[0]: reverse mode by the stored-state walk */
 typedef struct qc_sweep_desc {
     int64_t T;
@@ -701,21 +714,22 @@ typedef struct qc_sweep_desc {
     const double* goal_iso;      /* as qc_fidelity_desc.goal_iso */
     const int32_t* subspace;     /* unitary only: 0-based levels, or NULL = all */
     int32_t device;
-    int32_t wide;                /* bit field; valid: 0, QC_SWEEP_WIDE (1): the matrix-core form up to 2N = 32 ("mfma32-sweep"), or QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS (3): that form, and qc_sweep_grad_params* / the grad_theta, grad_scale of qc_sweep_vjp* are served in it (form, launch, kernel name and every *_supported answer as with 1; harmless where the handle takes another form); either of them | QC_SWEEP_WIDE_STORED (9, 11): that form also serves reverse mode by the stored-state walk when reserved1[0] = QC_SWEEP_STORED_STATES (nothing else changes); any of those | QC_SWEEP_WIDE_TANGENT (17, 19, 25, 27): that form also serves qc_sweep_jvp*; any of the eight | QC_SWEEP_WIDE_NOISE (64): that form also serves qc_sweep_noise_*; any of the sixteen | QC_SWEEP_WIDE_HESSIAN (256): that form also serves qc_sweep_hvp* for closed systems; anything else is QC_ERR_INVALID */
+    int32_t wide;                /* bit field; valid: 0, QC_SWEEP_WIDE (1): the matrix-core form up to 2N = 32 ("mfma32-sweep"), or QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS (3): that form, and qc_sweep_grad_params* / the grad_theta, grad_scale of qc_sweep_vjp* are served in it (form, launch, kernel name and every *_supported answer as with 1; harmless where the handle takes another form); either of them | QC_SWEEP_WIDE_STORED (9, 11): that form also serves reverse mode by the stored-state walk when reserved1[0] = QC_SWEEP_STORED_STATES (nothing else changes); any of those | QC_SWEEP_WIDE_TANGENT (17, 19, 25, 27): that form also serves qc_sweep_jvp*; any of the eight | QC_SWEEP_WIDE_NOISE (64): that form also serves qc_sweep_noise_*; any of the sixteen | QC_SWEEP_WIDE_HESSIAN (256): that form also serves qc_sweep_hvp* for closed systems; any of the thirty-two | QC_SWEEP_WIDE_64 (1024): 32 < 2N <= 64 with m <= 16 takes the matrix-core form "mfma64-sweep" (forward sweep only), nothing changes at 2N <= 32; anything else is QC_ERR_INVALID */
     int64_t reserved1[2];        /* [0]: 0, or QC_SWEEP_STORED_STATES: reverse mode reads stored forward states (any generators; "mfma16-sweep", and "mfma32-sweep" with QC_SWEEP_WIDE_STORED in `wide`); anything else is QC_ERR_INVALID.  [1]: ignored */
 } qc_sweep_desc;
 typedef struct qc_sweep qc_sweep;
 int64_t qc_sizeof_sweep_desc(void);
 /* device-free: QC_ERR_INVALID with a message (qc_sweep_last_error(NULL)); QC_ERR_UNSUPPORTED for 2N > 64 */
 int qc_sweep_desc_validate(const qc_sweep_desc* d);
-/* device-free: the launch a handle of this descriptor takes for S samples -- mfma: 1 = "mfma16-sweep" or "mfma32-sweep", 0 = "rollout-per-sample";
- * chunk / n_chunks: intervals per wavefront and chunks per sample of the MFMA form (n_chunks = 1 once S alone fills the device,
- * more for few samples; n_chunks = 0 for the per-sample form).  Outputs may be NULL. */
+/* device-free: the launch a handle of this descriptor takes for S samples -- mfma: 1 = "mfma16-sweep", "mfma32-sweep" or "mfma64-sweep", 0 = "rollout-per-sample";
+ * chunk / n_chunks: intervals per wavefront ("mfma64-sweep": per workgroup) and chunks per sample of the MFMA form (n_chunks = 1 once S
+ * alone fills the device, more for few samples; n_chunks = 0 for the per-sample form).  Outputs may be NULL. */
 int qc_sweep_desc_launch(const qc_sweep_desc* d, int64_t S, int32_t* mfma, int64_t* chunk, int64_t* n_chunks);
 int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out);
 void qc_sweep_destroy(qc_sweep* h);
 const char* qc_sweep_last_error(const qc_sweep* h);
-/* "mfma16-sweep", "mfma32-sweep" (wide descriptors, 16 < 2N <= 32) or "rollout-per-sample" (static strings; "none" for a NULL handle) */
+/* "mfma16-sweep", "mfma32-sweep" (wide descriptors, 16 < 2N <= 32), "mfma64-sweep" (descriptors with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64,
+ * 32 < 2N <= 64, m <= 16) or "rollout-per-sample" (static strings; "none" for a NULL handle) */
 const char* qc_sweep_kernel_name(const qc_sweep* h);
 /* host buffers.  Z: the full trajectory vector (zdim T + global_dim); init: 2N x cols; theta: S x n_pert (NULL when n_pert = 0);
  * scale: S x m or NULL; finals: S x (2N cols), sample-major; fids: S values.  Either output may be NULL, not both. */

@@ -18,6 +18,7 @@ const QC_SWEEP_WIDE = 1            # qc_sweep_desc.wide, bit 0: the matrix-core 
 const QC_SWEEP_WIDE_TANGENT = 16   # qc_sweep_desc.wide, bit 4 (only with bit 0): pushforwards in that form
 const QC_SWEEP_WIDE_NOISE = 64     # qc_sweep_desc.wide, bit 6 (only with bit 0): noise-trajectory sweeps and their gradients in that form
 const QC_SWEEP_WIDE_HESSIAN = 256  # qc_sweep_desc.wide, bit 8 (only with bit 0): Hessian products of closed systems in that form
+const QC_SWEEP_WIDE_64 = 1024      # qc_sweep_desc.wide, bit 10 (only with bit 0): 32 < 2N ≤ 64 with up to 16 drives on the matrix cores ("mfma64-sweep", forward sweep only)
 const QC_ABI_VERSION = 6      # QC_VERSION_MAJOR * 1000 + QC_VERSION_MINOR of the include/qcolloc.h these mirrors were written against
 
 # mirror of `qc_desc` (include/qcolloc.h); field order and types must match the header -- `__init__` checks the sizes against
@@ -703,7 +704,7 @@ end
 
 """
     rollout_sweep(init, controls, Δt, G_drift, G_drives, G_pert, θ; scale=nothing, cols, goal=nothing, fid_kind=-1,
-                  subspace=nothing, squared=false, device=0, wide=false, stored_states=false)  ->  (finals, fids)
+                  subspace=nothing, squared=false, device=0, wide=false, stored_states=false, wide64=false)  ->  (finals, fids)
 
 Final states and fidelities of ONE trajectory of controls under S perturbed systems, in one call (`qc_sweep_eval`): the loop of the
 reference's robustness check, `unitary_rollout(traj.a, timesteps, systems(ζ))[:, end]` and `iso_vec_unitary_fidelity` for every ζ
@@ -711,7 +712,9 @@ reference's robustness check, `unitary_rollout(traj.a, timesteps, systems(ζ))[:
 (2N×2N generators: `system.G_drift`, `system.G_drives`, and e.g. `G(Z)` for a detuning).  `controls` is m×T, `Δt` a vector of T
 timesteps, `θ` S×p, `scale` S×m or nothing; `fid_kind` -1 (none), 0 (unitary; `subspace` 1-based, `squared`), 1 (ket), 2 (density
 operator).  `wide = true` sets `qc_sweep_desc.wide = QC_SWEEP_WIDE`: the matrix-core form up to 2N = 32 ("mfma32-sweep") instead of one
-rollout per sample from 2N = 18 up.  `wide_stored = true` (only with `wide` and `stored_states`) adds `QC_SWEEP_WIDE_STORED` (8) to
+rollout per sample from 2N = 18 up.  `wide64 = true` (only with `wide`) adds `QC_SWEEP_WIDE_64` (1024): 32 < 2N ≤ 64 with up to 16 drives
+(5 qubits, three coupled three-level transmons) then runs on the matrix cores too ("mfma64-sweep"; the forward sweep only, so none of the
+gradient functions below takes the keyword), and nothing changes at 2N ≤ 32.  `wide_stored = true` (only with `wide` and `stored_states`) adds `QC_SWEEP_WIDE_STORED` (8) to
 `qc_sweep_desc.wide`: the stored-state walk then serves 16 < 2N ≤ 32 too (two qubits with T1 / T2), in `rollout_sweep_gradient`,
 `rollout_sweep_parameter_gradient` and `rollout_sweep_pullback`.  `stored_states = true` sets `qc_sweep_desc.reserved1[1] = QC_SWEEP_STORED_STATES` (C index 0): reverse
 mode (`rollout_sweep_gradient`, `rollout_sweep_parameter_gradient`, `rollout_sweep_pullback`) then reads stored forward states and serves
@@ -720,7 +723,9 @@ not look at it.  `finals` is (2N·cols)×S.  UNTESTED here, like the rest of thi
 """
 function rollout_sweep(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift, G_drives, G_pert,
                        θ::AbstractMatrix{Float64}; scale=nothing, cols::Int, goal=nothing, fid_kind::Int=-1, subspace=nothing,
-                       squared::Bool=false, device::Int=0, wide::Bool=false, stored_states::Bool=false, wide_stored::Bool=false)
+                       squared::Bool=false, device::Int=0, wide::Bool=false, stored_states::Bool=false, wide_stored::Bool=false,
+                       wide64::Bool=false)
+    (wide64 && !wide) && error("rollout_sweep: wide64 = true needs wide = true")
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(θ, 1)
     G0 = Float64.(vec(G_drift))
@@ -738,7 +743,7 @@ function rollout_sweep(init::AbstractVector{Float64}, controls::AbstractMatrix{F
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
                                squared ? 1 : 0, length(sub), isempty(g) ? C_NULL : pointer(g), isempty(sub) ? C_NULL : pointer(sub),
-                               device, (wide ? 1 : 0) | (wide_stored ? 8 : 0), (stored_states ? 1 : 0, 0)))      # 8 = QC_SWEEP_WIDE_STORED
+                               device, (wide ? 1 : 0) | (wide_stored ? 8 : 0) | (wide64 ? QC_SWEEP_WIDE_64 : 0), (stored_states ? 1 : 0, 0)))      # 8 = QC_SWEEP_WIDE_STORED
         rc = ccall((:qc_sweep_create, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Ptr{Cvoid}}), desc, h)
         rc == 0 || error("qc_sweep_create: " * unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
     end

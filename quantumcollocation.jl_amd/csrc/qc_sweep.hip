@@ -26,6 +26,10 @@
 // `wide` is a bit field: bit 1 (QC_SWEEP_WIDE_PARAMS, only together with bit 0) changes nothing here -- the form, the launch and the
 // forward sweep are those of wide = 1; it lets qc_sweep_grad_params* and qc_sweep_vjp* serve the parameter outputs in that form.
 // Bits 3, 4, 6 and 8 (QC_SWEEP_WIDE_STORED, _TANGENT, _NOISE, _HESSIAN) likewise: each lets one more family of entry points serve that form.
+// Bit 10 (QC_SWEEP_WIDE_64, only together with bit 0) takes the matrix cores up to 2N = 64: 32 < 2N <= 64 with up to 16 drives is
+// "mfma64-sweep" (qc_sweep64.hip: 4 x 4 tiles a matrix in LDS, one workgroup per (sample, chunk), its own fill constant in the chunk
+// rule); the second launch below is shared, with ld = 64.  That form serves the forward sweep only -- gradients, pullbacks, pushforwards,
+// Hessian products and noise sweeps answer QC_ERR_UNSUPPORTED there -- and descriptors with 2N <= 32 ignore the bit completely.
 #include <math.h>
 #include <string.h>
 
@@ -44,6 +48,8 @@ using namespace qc_sweep16;         // constants, table, tile load, generator, s
 constexpr int kSMmax = 8;           // drive tiles a wave keeps in registers
 constexpr int kFinT = 256;          // threads of the final-state / fidelity workgroup
 constexpr long long kSweepFill = 2048;   // waves that give every SIMD a couple: 256 CUs x 4 SIMDs x 2
+constexpr long long kSweepFill64 = 256;  // "mfma64-sweep": an item is a workgroup of 16 waves whose 135 168 B of LDS leave room for one per CU: 256 CUs x 1
+constexpr int kSMmax64 = 16;             // drives of the "mfma64-sweep" form: nothing is resident per drive, lane u of a wave carries drive u's amplitude
 
 struct FinParams {
     int n, ns, ld, n_chunks, fid_kind, fid_form, fid_n;
@@ -192,9 +198,10 @@ std::string* qc_sweep_err_slot() { return &g_swerr; }
 
 // The launch rule, in one place.  n_chunks = 1 once the samples alone give every SIMD a couple of waves; fewer samples split the
 // trajectory, up to ceil(sqrt(T-1)) chunks (beyond that the ordered chain of the second launch outweighs what the first gains).
-void qc_sweep_chunks(int64_t S, int64_t T, int64_t* chunk, int64_t* n_chunks) {
-    const int64_t n_int = T - 1;
-    const int64_t want = S >= kSweepFill ? 1 : (kSweepFill + S - 1) / S;
+// "mfma64-sweep": the same rule with items that are whole workgroups, one per CU -- n_chunks = 1 once S >= 256.
+void qc_sweep_chunks(qc_sweep_form form, int64_t S, int64_t T, int64_t* chunk, int64_t* n_chunks) {
+    const int64_t n_int = T - 1, fill = form == QC_SWEEP_FORM_64 ? kSweepFill64 : kSweepFill;
+    const int64_t want = S >= fill ? 1 : (fill + S - 1) / S;
     int64_t r = 1;
     while (r * r < n_int) ++r;
     const int64_t nch = want < r ? want : r;
@@ -204,7 +211,7 @@ void qc_sweep_chunks(int64_t S, int64_t T, int64_t* chunk, int64_t* n_chunks) {
 
 int qc_sweep_plan_totals(qc_sweep* h, int64_t S, qc_buf& buf, size_t doubles_per_item, SweepParams* P, int64_t* chunk, int64_t* n_chunks) {
     int64_t ch, nch;
-    qc_sweep_chunks(S, h->d.T, &ch, &nch);
+    qc_sweep_chunks(h->mfma64 ? QC_SWEEP_FORM_64 : QC_SWEEP_FORM_16, S, h->d.T, &ch, &nch);
     QC_SIDE_HIP(h, g_swerr, h->grow(buf, (size_t)S * nch * doubles_per_item));
     *P = qc_sweep_params(h, S, ch, nch);
     *chunk = ch;      // as before: untouched when the allocation fails
@@ -256,26 +263,35 @@ int qc_sweep_validate_desc(const qc_sweep_desc* d) {
     if (d->m > 64) return qc_sweep_fail(nullptr, QC_ERR_UNSUPPORTED, "qc_sweep: more than 64 drives are not supported");
     // bits 1 (QC_SWEEP_WIDE_PARAMS), 3 (QC_SWEEP_WIDE_STORED), 4 (QC_SWEEP_WIDE_TANGENT), 6 (QC_SWEEP_WIDE_NOISE) and 8
     // (QC_SWEEP_WIDE_HESSIAN) only together with bit 0; bits 2, 5 and 7 are not assigned: 0, 1, 3, 9, 11, 17, 19, 25, 27, each of the
-    // eight odd values | 64, and each of those sixteen odd values | 256
-    if ((d->wide & ~(QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS | QC_SWEEP_WIDE_STORED | QC_SWEEP_WIDE_TANGENT | QC_SWEEP_WIDE_NOISE | QC_SWEEP_WIDE_HESSIAN)) != 0 ||
+    // eight odd values | 64, and each of those sixteen odd values | 256; bit 10 (QC_SWEEP_WIDE_64) likewise only together with bit 0:
+    // each of those thirty-two odd values | 1024; bit 9 is not assigned
+    if ((d->wide & ~(QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS | QC_SWEEP_WIDE_STORED | QC_SWEEP_WIDE_TANGENT | QC_SWEEP_WIDE_NOISE | QC_SWEEP_WIDE_HESSIAN | QC_SWEEP_WIDE_64)) != 0 ||
         (d->wide != 0 && !(d->wide & QC_SWEEP_WIDE)))
-        return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: wide must be 0 or QC_SWEEP_WIDE (1), alone or with QC_SWEEP_WIDE_PARAMS (2), QC_SWEEP_WIDE_STORED (8), QC_SWEEP_WIDE_TANGENT (16), QC_SWEEP_WIDE_NOISE (64) and / or QC_SWEEP_WIDE_HESSIAN (256): 0, 1, 3, 9, 11, 17, 19, 25 or 27, or one of those eight | 64, or one of the sixteen odd values | 256");
+        return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: wide must be 0 or QC_SWEEP_WIDE (1), alone or with QC_SWEEP_WIDE_PARAMS (2), QC_SWEEP_WIDE_STORED (8), QC_SWEEP_WIDE_TANGENT (16), QC_SWEEP_WIDE_NOISE (64) and / or QC_SWEEP_WIDE_HESSIAN (256): 0, 1, 3, 9, 11, 17, 19, 25 or 27, or one of those eight | 64, or one of the sixteen odd values | 256; or one of the thirty-two odd values | QC_SWEEP_WIDE_64 (1024)");
     if (d->reserved1[0] != 0 && d->reserved1[0] != QC_SWEEP_STORED_STATES)
         return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: reserved1[0] must be 0 or QC_SWEEP_STORED_STATES (1)");
     return QC_OK;
 }
 
-int qc_sweep_desc_form(const qc_sweep_desc* d) {
-    if (d->m > kSMmax) return 0;
-    if (2 * d->N <= 16) return 1;
-    return ((d->wide & QC_SWEEP_WIDE) && 2 * d->N <= 32) ? 2 : 0;
+qc_sweep_form qc_sweep_desc_form(const qc_sweep_desc* d) {
+    if (2 * d->N > 32)      // only with both bits; below, the bit is not looked at
+        return ((d->wide & QC_SWEEP_WIDE) && (d->wide & QC_SWEEP_WIDE_64) && 2 * d->N <= 64 && d->m <= kSMmax64) ? QC_SWEEP_FORM_64 : QC_SWEEP_FORM_PER_SAMPLE;
+    if (d->m > kSMmax) return QC_SWEEP_FORM_PER_SAMPLE;
+    if (2 * d->N <= 16) return QC_SWEEP_FORM_16;
+    return ((d->wide & QC_SWEEP_WIDE) && 2 * d->N <= 32) ? QC_SWEEP_FORM_32 : QC_SWEEP_FORM_PER_SAMPLE;
 }
-bool qc_sweep_desc_is_mfma(const qc_sweep_desc* d) { return qc_sweep_desc_form(d) != 0; }
+bool qc_sweep_desc_is_mfma(const qc_sweep_desc* d) { return qc_sweep_desc_form(d) != QC_SWEEP_FORM_PER_SAMPLE; }
 
 std::string qc_sweep_per_sample_why(const qc_sweep_desc* d) {
     const int n = 2 * d->N, top = (d->wide & QC_SWEEP_WIDE) ? 32 : 16;      // wide descriptors: "mfma32-sweep" up to 2N = 32
+    if (n > 32 && (d->wide & QC_SWEEP_WIDE) && (d->wide & QC_SWEEP_WIDE_64))      // "mfma64-sweep" but for its drive limit
+        return "the handle takes the rollout-per-sample form (" + std::to_string(d->m) + " drives > 16)";
     return n > top ? "the handle takes the rollout-per-sample form (2N = " + std::to_string(n) + " > " + std::to_string(top) + ")"
                    : "the handle takes the rollout-per-sample form (" + std::to_string(d->m) + " drives > 8)";
+}
+
+std::string qc_sweep_form64_why(const qc_sweep_desc* d) {
+    return "the handle takes the mfma64-sweep form (2N = " + std::to_string(2 * d->N) + "), which serves the forward sweep only";
 }
 
 int qc_sweep_check(qc_sweep* h, const char* who, const bool qc_sweep::*ok, const char* scope, const std::string qc_sweep::*why, const void* Z,
@@ -292,6 +308,7 @@ int qc_sweep_check(qc_sweep* h, const char* who, const bool qc_sweep::*ok, const
 
 int qc_sweep_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, hipStream_t st, int64_t* chunk_out,
                            int64_t* n_chunks_out) {
+    if (h->mfma64) return qc_sweep64_launch_totals(h, dZ, S, dtheta, dscale, st, chunk_out, n_chunks_out);
     if (h->mfma32) return qc_sweep32_launch_totals(h, dZ, S, dtheta, dscale, st, chunk_out, n_chunks_out);
     SweepParams P;
     if (int rc = qc_sweep_plan_totals(h, S, h->dTot, 256, &P, chunk_out, n_chunks_out)) return rc;
@@ -312,9 +329,10 @@ extern "C" int qc_sweep_desc_launch(const qc_sweep_desc* d, int64_t S, int32_t* 
     int rc = qc_sweep_validate_desc(d);
     if (rc) return rc;
     if (S < 1) return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep_desc_launch: S must be >= 1");
-    const bool mf = qc_sweep_desc_is_mfma(d);
+    const qc_sweep_form form = qc_sweep_desc_form(d);
+    const bool mf = form != QC_SWEEP_FORM_PER_SAMPLE;
     int64_t ch = d->T - 1, nch = 0;      // per-sample form: the rollout kernels' own scan, no totals
-    if (mf) qc_sweep_chunks(S, d->T, &ch, &nch);
+    if (mf) qc_sweep_chunks(form, S, d->T, &ch, &nch);
     if (mfma) *mfma = mf ? 1 : 0;
     if (chunk) *chunk = ch;
     if (n_chunks) *n_chunks = nch;
@@ -323,7 +341,7 @@ extern "C" int qc_sweep_desc_launch(const qc_sweep_desc* d, int64_t S, int32_t* 
 
 extern "C" const char* qc_sweep_kernel_name(const qc_sweep* h) {
     if (!h) return "none";
-    return h->mfma32 ? "mfma32-sweep" : h->mfma ? "mfma16-sweep" : "rollout-per-sample";
+    return h->mfma64 ? "mfma64-sweep" : h->mfma32 ? "mfma32-sweep" : h->mfma ? "mfma16-sweep" : "rollout-per-sample";
 }
 
 extern "C" void qc_sweep_destroy(qc_sweep* h) {
@@ -342,7 +360,8 @@ extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
     h->d = *d;
     h->device = d->device;
     h->mfma = qc_sweep_desc_is_mfma(d);
-    h->mfma32 = qc_sweep_desc_form(d) == 2;
+    h->mfma32 = qc_sweep_desc_form(d) == QC_SWEEP_FORM_32;
+    h->mfma64 = qc_sweep_desc_form(d) == QC_SWEEP_FORM_64;
     h->wide_par = h->mfma32 && (d->wide & QC_SWEEP_WIDE_PARAMS);
     h->wide_stored = h->mfma32 && (d->wide & QC_SWEEP_WIDE_STORED);
     h->wide_tangent = h->mfma32 && (d->wide & QC_SWEEP_WIDE_TANGENT);
@@ -372,7 +391,10 @@ extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
     if (m) memcpy(G.data() + n2, d->G_drives, (size_t)m * n2 * 8);
     if (p) memcpy(G.data() + (size_t)(1 + m) * n2, d->G_pert, (size_t)p * n2 * 8);
     std::vector<double> img;
-    if (h->mfma32) {
+    if (h->mfma64) {
+        img.resize((size_t)nm * 4096);
+        for (int mat = 0; mat < nm; ++mat) qc_sweep64_image(G.data() + (size_t)mat * n2, n, img.data() + (size_t)mat * 4096);
+    } else if (h->mfma32) {
         img.resize((size_t)nm * 1024);
         for (int mat = 0; mat < nm; ++mat) qc_sweep32_image(G.data() + (size_t)mat * n2, n, img.data() + (size_t)mat * 1024);
     } else if (h->mfma) {   // A layout: lane (g, i) reg kk holds G[i][4 kk + g], zero outside n x n
@@ -449,7 +471,7 @@ int qc_sweep_launch_finish(qc_sweep* h, int64_t S, int64_t n_chunks, const doubl
     FinParams F;
     F.n = h->n; F.ns = h->ns;
     F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;
-    F.ld = h->mfma32 ? 32 : 16; F.n_chunks = (int)n_chunks; F.src_stride = 0;
+    F.ld = h->mfma64 ? 64 : h->mfma32 ? 32 : 16; F.n_chunks = (int)n_chunks; F.src_stride = 0;
     return finish_launch(h, F, S, dinit, dfinals, dfids, st);
 }
 
@@ -469,7 +491,7 @@ static int qc_sweep_eval_launch(qc_sweep* h, const char* who, const double* dZ, 
         int64_t chunk, n_chunks;
         rc = qc_sweep_launch_totals(h, dZ, S, dtheta, dscale, st, &chunk, &n_chunks);
         if (rc) return rc;
-        F.ld = h->mfma32 ? 32 : 16; F.n_chunks = (int)n_chunks; F.src_stride = 0;
+        F.ld = h->mfma64 ? 64 : h->mfma32 ? 32 : 16; F.n_chunks = (int)n_chunks; F.src_stride = 0;
         src = dinit;
     } else {
         QC_SIDE_HIP(h, g_swerr, h->grow(h->dFin, (size_t)S * h->ns));

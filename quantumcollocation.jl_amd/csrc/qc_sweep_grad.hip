@@ -359,6 +359,7 @@ __global__ __launch_bounds__(kRedT) void qc_sweep_J_kernel(long long S, const do
 bool qc_sweep_closed_scope(const qc_sweep_desc* d, std::string* why) {
     const int n = 2 * d->N;
     if (!qc_sweep_desc_is_mfma(d)) { *why = qc_sweep_per_sample_why(d); return false; }
+    if (qc_sweep_desc_form(d) == QC_SWEEP_FORM_64) { *why = qc_sweep_form64_why(d); return false; }
     const double* sets[3] = {d->G_drift, d->G_drives, d->G_pert};
     const int counts[3] = {1, d->m, d->n_pert};
     const char* names[3] = {"G_drift", "drive generator", "perturbation generator"};
@@ -387,9 +388,10 @@ bool qc_sweep_closed_scope(const qc_sweep_desc* d, std::string* why) {
 // the "mfma32-sweep" form only for descriptors that opt in with QC_SWEEP_WIDE_STORED (the 2 x 2-tile walk of qc_sweep32_open_grad.hip).
 bool qc_sweep_reverse_scope(const qc_sweep_desc* d, std::string* why) {
     if (d->reserved1[0] != QC_SWEEP_STORED_STATES) return qc_sweep_closed_scope(d, why);
-    const int form = qc_sweep_desc_form(d);
-    if (form == 0) { *why = qc_sweep_per_sample_why(d); return false; }
-    if (form == 2 && !(d->wide & QC_SWEEP_WIDE_STORED)) { *why = "stored-state gradients are not served in the mfma32-sweep form"; return false; }
+    const qc_sweep_form form = qc_sweep_desc_form(d);
+    if (form == QC_SWEEP_FORM_PER_SAMPLE) { *why = qc_sweep_per_sample_why(d); return false; }
+    if (form == QC_SWEEP_FORM_64) { *why = qc_sweep_form64_why(d); return false; }
+    if (form == QC_SWEEP_FORM_32 && !(d->wide & QC_SWEEP_WIDE_STORED)) { *why = "stored-state gradients are not served in the mfma32-sweep form"; return false; }
     const int nc = d->state_cols == 0 ? d->N : d->state_cols;
     if (nc > 16) { *why = "states of more than 16 columns are not served (state_cols = " + std::to_string(nc) + ")"; return false; }
     return true;

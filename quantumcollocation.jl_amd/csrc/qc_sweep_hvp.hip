@@ -387,7 +387,7 @@ int hvp_check(qc_sweep* h, const char* who, const void* Z, const void* init, int
 // or within the "mfma32-sweep" form of a descriptor whose wide has QC_SWEEP_WIDE_HESSIAN (qc_sweep32_hvp.hip).
 bool qc_sweep_hvp_scope(const qc_sweep_desc* d, std::string* why) {
     if (!qc_sweep_closed_scope(d, why)) return false;
-    if (qc_sweep_desc_form(d) == 2 && !(d->wide & QC_SWEEP_WIDE_HESSIAN)) { *why = "Hessian products are not served in the mfma32-sweep form"; return false; }
+    if (qc_sweep_desc_form(d) == QC_SWEEP_FORM_32 && !(d->wide & QC_SWEEP_WIDE_HESSIAN)) { *why = "Hessian products are not served in the mfma32-sweep form"; return false; }
     return true;
 }
 

@@ -1,4 +1,4 @@
-// What qc_sweep.hip (forward sweep), qc_sweep_grad.hip (its adjoint), qc_sweep_open_grad.hip and qc_sweep32_open_grad.hip (the adjoint on stored states), qc_sweep_vjp.hip (the pullback of the final states),
+// What qc_sweep.hip (forward sweep; its 4 x 4-tile form: qc_sweep64.hip), qc_sweep_grad.hip (its adjoint), qc_sweep_open_grad.hip and qc_sweep32_open_grad.hip (the adjoint on stored states), qc_sweep_vjp.hip (the pullback of the final states),
 // qc_sweep_jvp.hip (their pushforward), qc_sweep_hvp.hip and qc_sweep32_hvp.hip (the tangent of the pullback) and qc_sweep_noise.hip (noise trajectories) share: the handle with its scratch and staging buffers, the descriptor and argument checks, the launch
 // parameters of the (sample, chunk) kernels (SweepParams, qc_sweep_params), the preamble of every launch of chunk totals (qc_sweep_plan_totals: chunk rule, scratch, parameters) and those launches.  Not part of the ABI.
 #pragma once
@@ -11,6 +11,7 @@ struct qc_sweep : qc_side {
     qc_sweep_desc d;             // caller-owned arrays are not retained (pointers nulled)
     bool mfma = false;
     bool mfma32 = false;         // the 2 x 2-tile form of a wide descriptor ("mfma32-sweep", qc_sweep32.hip); mfma is set as well
+    bool mfma64 = false;         // the 4 x 4-tile form of a descriptor with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 ("mfma64-sweep", qc_sweep64.hip): the forward sweep only; mfma is set as well
     bool wide_par = false;       // mfma32 and wide has QC_SWEEP_WIDE_PARAMS: parameter gradients and cotangents are served (qc_sweep32_grad.hip)
     bool wide_stored = false;    // mfma32 and wide has QC_SWEEP_WIDE_STORED: with `stored`, reverse mode by the 2 x 2-tile stored-state walk (qc_sweep32_open_grad.hip)
     bool wide_tangent = false;   // mfma32 and wide has QC_SWEEP_WIDE_TANGENT: pushforwards are served (qc_sweep32_jvp.hip)
@@ -35,7 +36,7 @@ struct qc_sweep : qc_side {
     double* dImg = nullptr;      // their A-layout images (MFMA form)
     double *dgr = nullptr, *dgi = nullptr;
     // Scratch of the "_dev" entry points, grown at the first call that needs it.  Largest request of a call, and who makes it:
-    qc_buf dTot;         // chunk totals, S x n_chunks x 256 (mfma32: 1024)                  eval, grad, vjp, noise
+    qc_buf dTot;         // chunk totals, S x n_chunks x 256 (mfma32: 1024, mfma64: 4096)             eval, grad, vjp, noise
     qc_buf dFin;         // per-sample form: final states, S x ns                             eval
     double *dGs = nullptr, *dRE = nullptr, *dRQ = nullptr, *dRS = nullptr, *dRout = nullptr;      // per-sample form, sized at create
     qc_buf dXs, dLs;     // x and lambda at the chunk ends, S x n_chunks x ns each            grad, vjp, noise_grad
@@ -76,7 +77,7 @@ struct SweepParams {
     int n, nc, m, p, zdim, off_a, off_dt, n_int, chunk, n_chunks, nd;   // nd = m + (off_dt >= 0): derivatives per interval
     long long items;             // S * n_chunks
     double dt_fixed;
-    const double* img;           // A-layout images, 256 doubles a matrix ("mfma32-sweep": 1024): drift, m drives, p perturbations
+    const double* img;           // A-layout images, 256 doubles a matrix ("mfma32-sweep": 1024; "mfma64-sweep": column-major, 4096): drift, m drives, p perturbations
 };
 
 inline SweepParams qc_sweep_params(const qc_sweep* h, int64_t S, int64_t chunk, int64_t n_chunks) {
@@ -108,12 +109,16 @@ int qc_sweep_check(qc_sweep* h, const char* who, const bool qc_sweep::*ok, const
     } while (0)
 int qc_sweep_validate_desc(const qc_sweep_desc* d);
 bool qc_sweep_desc_is_mfma(const qc_sweep_desc* d);
-// 0: "rollout-per-sample", 1: "mfma16-sweep", 2: "mfma32-sweep" (wide descriptors with 16 < 2N <= 32)
-int qc_sweep_desc_form(const qc_sweep_desc* d);
-// form 0: "the handle takes the rollout-per-sample form (...)" with its cause, the reason of every scope that needs an MFMA form
+// The form a descriptor takes: "rollout-per-sample", "mfma16-sweep", "mfma32-sweep" (wide descriptors with 16 < 2N <= 32) or "mfma64-sweep"
+// (descriptors with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64, 32 < 2N <= 64, m <= 16: the forward sweep only)
+enum qc_sweep_form { QC_SWEEP_FORM_PER_SAMPLE = 0, QC_SWEEP_FORM_16 = 1, QC_SWEEP_FORM_32 = 2, QC_SWEEP_FORM_64 = 3 };
+qc_sweep_form qc_sweep_desc_form(const qc_sweep_desc* d);
+// QC_SWEEP_FORM_64: "the handle takes the mfma64-sweep form (2N = ...), which serves the forward sweep only", the reason of every other scope there
+std::string qc_sweep_form64_why(const qc_sweep_desc* d);
+// QC_SWEEP_FORM_PER_SAMPLE: "the handle takes the rollout-per-sample form (...)" with its cause, the reason of every scope that needs an MFMA form
 std::string qc_sweep_per_sample_why(const qc_sweep_desc* d);
-// the chunk rule of the MFMA forms
-void qc_sweep_chunks(int64_t S, int64_t T, int64_t* chunk, int64_t* n_chunks);
+// the chunk rule of the MFMA forms: `form` chooses the fill constant (QC_SWEEP_FORM_64: one workgroup per compute unit; _16 and _32: a couple of waves per SIMD)
+void qc_sweep_chunks(qc_sweep_form form, int64_t S, int64_t T, int64_t* chunk, int64_t* n_chunks);
 // What every launch of chunk totals starts with: the chunk rule for S samples, `buf` grown to S x n_chunks x doubles_per_item, the launch
 // parameters in *P, the rule's result in *chunk, *n_chunks; QC_OK or the failed allocation's code.  qc_sweep_grid: workgroups of `waves` waves.
 int qc_sweep_plan_totals(qc_sweep* h, int64_t S, qc_buf& buf, size_t doubles_per_item, SweepParams* P, int64_t* chunk, int64_t* n_chunks);
@@ -125,6 +130,12 @@ int qc_sweep_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const doubl
 // (S x n_chunks column-major 32 x 32 totals of 1024 doubles in h->dTot)
 void qc_sweep32_image(const double* G, int n, double* img);
 int qc_sweep32_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, hipStream_t st, int64_t* chunk,
+                             int64_t* n_chunks);
+// "mfma64-sweep" handles (qc_sweep64.hip): the zero-padded column-major 64 x 64 image of one n x n matrix (4096 doubles), and the launch of
+// qc_sweep_mfma64_kernel, one workgroup per (sample, chunk) (S x n_chunks column-major 64 x 64 totals of 4096 doubles in h->dTot)
+// (hidden: the library exports no symbol of this form)
+__attribute__((visibility("hidden"))) void qc_sweep64_image(const double* G, int n, double* img);
+__attribute__((visibility("hidden"))) int qc_sweep64_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, hipStream_t st, int64_t* chunk,
                              int64_t* n_chunks);
 // "mfma32-sweep" gradients (qc_sweep32_grad.hip): the backward walk qc_sweep32_grad_kernel<false> (gs: S x (T-1) x nd), or with `par` the
 // parameter flavour <true> (gs may be NULL) and qc_sweep_par_reduce_kernel out of h->dPart; scratch is the caller's

@@ -301,14 +301,14 @@ int jvp_check(qc_sweep* h, const char* who, const void* Z, const void* init, int
 }  // namespace
 
 bool qc_sweep_jvp_scope(const qc_sweep_desc* d, std::string* why) {
-    const int form = qc_sweep_desc_form(d);
-    if (form == 1) return true;
-    if (form == 2) {
+    const qc_sweep_form form = qc_sweep_desc_form(d);
+    if (form == QC_SWEEP_FORM_16) return true;
+    if (form == QC_SWEEP_FORM_32) {
         if (d->wide & QC_SWEEP_WIDE_TANGENT) return true;      // qc_sweep32_jvp.hip
         *why = "pushforwards are not served in the mfma32-sweep form";
         return false;
     }
-    *why = qc_sweep_per_sample_why(d);
+    *why = form == QC_SWEEP_FORM_64 ? qc_sweep_form64_why(d) : qc_sweep_per_sample_why(d);
     return false;
 }
 

@@ -199,14 +199,21 @@ class RolloutSweep:
     wide_hessian   True (only with `wide`): an "mfma32-sweep" handle of a closed system (antisymmetric generators, at most 16 state
                    columns) serves `hvp` and `hvp_device`: one tangent forward walk and one backward walk on 2 x 2 tiles, about 3.4
                    pullbacks by the instruction count.  It does not need `wide_tangent`.  Without it those refuse there, as they
-                   always did; nothing else changes, and nothing changes at 2N <= 16, where `hvp` needs no flag."""
+                   always did; nothing else changes, and nothing changes at 2N <= 16, where `hvp` needs no flag.
+    wide64         True (only with `wide`): systems of 32 < 2N <= 64 with up to 16 drives -- 5 qubits, three coupled three-level
+                   transmons, a five-level Lindblad model -- run on the matrix cores as well ("mfma64-sweep": one workgroup per
+                   (sample, chunk of intervals), the matrices in LDS) instead of one rollout per sample.  That form serves `eval` and
+                   `eval_device` only: `grad`, `param_grad`, `vjp`, `jvp`, `hvp` and the noise sweeps refuse there, naming the form.
+                   Nothing changes at 2N <= 32, and nothing changes without it."""
 
     def __init__(self, system, perturbations, T: int, cols: Optional[int] = None, goal=None, fid_kind=None, subspace=None,
                  fid_form: int = _lib.QC_FID_FORM_ABS, zdim: Optional[int] = None, off_a: int = 0, off_dt: Optional[int] = None,
                  dt_fixed: Optional[float] = None, global_dim: int = 0, device: int = 0, wide: bool = False,
                  stored_states: bool = False, wide_params: bool = False, wide_stored: bool = False, wide_tangent: bool = False,
-                 wide_noise: bool = False, wide_hessian: bool = False):
+                 wide_noise: bool = False, wide_hessian: bool = False, wide64: bool = False):
         self._h = None
+        if wide64 and not wide:
+            raise ValueError("wide64=True needs wide=True")
         if wide_hessian and not wide:
             raise ValueError("wide_hessian=True needs wide=True")
         if wide_noise and not wide:
@@ -252,7 +259,9 @@ class RolloutSweep:
         d.device = device
         d.wide = ((_lib.QC_SWEEP_WIDE if wide else 0) | (_lib.QC_SWEEP_WIDE_PARAMS if wide_params else 0)
                   | (_lib.QC_SWEEP_WIDE_STORED if wide_stored else 0) | (_lib.QC_SWEEP_WIDE_TANGENT if wide_tangent else 0)
-                  | (_lib.QC_SWEEP_WIDE_NOISE if wide_noise else 0) | (_lib.QC_SWEEP_WIDE_HESSIAN if wide_hessian else 0))
+                  | (_lib.QC_SWEEP_WIDE_NOISE if wide_noise else 0) | (_lib.QC_SWEEP_WIDE_HESSIAN if wide_hessian else 0)
+                  | (_lib.QC_SWEEP_WIDE_64 if wide64 else 0))
+        self.wide64 = bool(wide64)
         self.wide_hessian = bool(wide_hessian)
         self.wide_tangent = bool(wide_tangent)
         self.wide_noise = bool(wide_noise)
@@ -270,7 +279,8 @@ class RolloutSweep:
 
     @property
     def kernel_name(self) -> str:
-        """"mfma16-sweep" (2N <= 16, up to 8 drives), "mfma32-sweep" (`wide`, 16 < 2N <= 32, up to 8 drives) or "rollout-per-sample"."""
+        """"mfma16-sweep" (2N <= 16, up to 8 drives), "mfma32-sweep" (`wide`, 16 < 2N <= 32, up to 8 drives), "mfma64-sweep" (`wide` and
+        `wide64`, 32 < 2N <= 64, up to 16 drives) or "rollout-per-sample"."""
         return _lib.lib.qc_sweep_kernel_name(self._h).decode()
 
     def launch(self, S: int):
@@ -925,10 +935,11 @@ class _SweepFinals(torch.autograd.Function):
 
 def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None, cols: Optional[int] = None, goal=None, fid_kind=None,
                   subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS, wide: bool = False, stored_states: bool = False,
-                  wide_stored: bool = False, wide_tangent: bool = False):
+                  wide_stored: bool = False, wide_tangent: bool = False, wide64: bool = False):
     """(finals, fids) of S rollouts under the perturbed systems: finals is (2N cols) x S, fids S values (None without `fid_kind`).
     theta is S x len(perturbations) (S x 0 without perturbations), scale S x n_drives or None (all ones); `wide`, `stored_states`,
-    `wide_stored` and `wide_tangent` as `RolloutSweep` (the forward sweep itself looks at none of the last three)."""
+    `wide_stored` and `wide_tangent` as `RolloutSweep` (the forward sweep itself looks at none of the last three); `wide64` (only with
+    `wide`) as `RolloutSweep`: 32 < 2N <= 64 with up to 16 drives on the matrix cores ("mfma64-sweep")."""
     controls = np.asarray(controls, dtype=np.float64)
     if controls.ndim != 2 or controls.shape[0] != system.n_drives:
         raise ValueError("controls must be n_drives x T")
@@ -938,7 +949,7 @@ def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None,
     if cols is None:
         cols = init.size // n
     sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device, wide=wide,
-                      stored_states=stored_states, wide_stored=wide_stored, wide_tangent=wide_tangent)
+                      stored_states=stored_states, wide_stored=wide_stored, wide_tangent=wide_tangent, wide64=wide64)
     try:
         return sw.eval(sw.pack(controls, dts), init, theta, scale)
     finally:
@@ -995,21 +1006,23 @@ def _traj_dts(traj):
 
 
 def unitary_rollout_fidelity_sweep(traj: NamedTrajectory, system, perturbations, theta, scale=None, state_name: str = "Ũ⃗",
-                                   control_name: str = "a", subspace: Optional[Sequence[int]] = None, device: int = 0) -> np.ndarray:
-    """`unitary_rollout_fidelity` under S perturbed systems: initial state, goal and timesteps as that function takes them."""
+                                   control_name: str = "a", subspace: Optional[Sequence[int]] = None, device: int = 0, wide: bool = False,
+                                   wide64: bool = False) -> np.ndarray:
+    """`unitary_rollout_fidelity` under S perturbed systems: initial state, goal and timesteps as that function takes them; `wide` and
+    `wide64` as `rollout_sweep` (both True: up to 32 levels on the matrix cores)."""
     init = traj.initial.get(state_name) if getattr(traj, "initial", None) else None
     if init is None:
         init = operator_to_iso_vec(np.eye(system.levels, dtype=complex))
     return rollout_sweep(np.asarray(init, dtype=np.float64), traj[control_name], _traj_dts(traj), system, perturbations, theta, scale,
                          cols=system.levels, goal=np.asarray(traj.goal[state_name], dtype=np.float64), fid_kind="unitary", subspace=subspace,
-                         device=device)[1]
+                         device=device, wide=wide, wide64=wide64)[1]
 
 
 def rollout_fidelity_sweep(traj: NamedTrajectory, system, perturbations, theta, scale=None, state_name: str = "ψ̃", control_name: str = "a",
-                           device: int = 0) -> np.ndarray:
-    """`rollout_fidelity` of a ket component under S perturbed systems."""
+                           device: int = 0, wide: bool = False, wide64: bool = False) -> np.ndarray:
+    """`rollout_fidelity` of a ket component under S perturbed systems; `wide` and `wide64` as `rollout_sweep`."""
     init = traj.initial.get(state_name) if getattr(traj, "initial", None) else None
     if init is None:
         init = traj[state_name][:, 0]
     return rollout_sweep(np.ascontiguousarray(init, dtype=np.float64), traj[control_name], _traj_dts(traj), system, perturbations, theta, scale,
-                         cols=1, goal=np.asarray(traj.goal[state_name], dtype=np.float64), fid_kind="ket", device=device)[1]
+                         cols=1, goal=np.asarray(traj.goal[state_name], dtype=np.float64), fid_kind="ket", device=device, wide=wide, wide64=wide64)[1]
