@@ -161,12 +161,13 @@ def assert_fidelities(fids, J, rows, c, what):
         assert abs(J - np.dot(w, rfid)) <= bound, what
 
 
-def assert_launch(sw, name, S=None, table=CASES):
-    """The handle's launch form at S against the table and the restated rule: a change of the chunk rule fails here."""
+def assert_launch(sw, name, S=None, table=CASES, rule=None, kernel=None):
+    """The handle's launch form at S against the table and the restated rule: a change of the chunk rule fails here.  `rule(spec, S)`
+    and `kernel`: the restated rule and the kernel name of a form that is neither of the two this file runs."""
     spec, wide, (chunk, n_chunks, last), by_sqrt = table[name]
     S = spec[6] if S is None else S
-    want = tw.wide_launch(2 * spec[1], spec[2], S, spec[7], wide)
-    assert sw.kernel_name == ("mfma32-sweep" if wide else "mfma16-sweep")
+    want = tw.wide_launch(2 * spec[1], spec[2], S, spec[7], wide) if rule is None else rule(spec, S)
+    assert sw.kernel_name == (("mfma32-sweep" if wide else "mfma16-sweep") if kernel is None else kernel)
     assert sw.launch(S) == (True, want["chunk"], want["n_chunks"])
     if S == spec[6]:
         assert (want["chunk"], want["n_chunks"], want["last"], want["by_sqrt"]) == (chunk, n_chunks, last, by_sqrt)
@@ -177,7 +178,11 @@ def assert_launch(sw, name, S=None, table=CASES):
 #  CPU
 # ---------------------------------------------------------------------------------------------------------------------------------
 def test_classes_reach_both_ends():
-    for S in sorted({CASES[k][0][6] for k in CASES} | set(GROWTH)):
+    assert_classes_reach_both_ends({CASES[k][0][6] for k in CASES} | set(GROWTH))
+
+
+def assert_classes_reach_both_ends(sizes):
+    for S in sorted(sizes):
         cls = classes(S)
         assert cls.shape == (S,) and cls.min() == 0 and cls.max() == R - 1
         assert cls[:R].tolist() == list(range(R)) and cls[-R:].tolist() == list(range(R))[::-1]

@@ -42,10 +42,10 @@ LINEAR = ["sqrt-301", "one-2049-kets3"]
 _REF = {}          # case name -> the recurrence reference of the R rows: computed once, shared, never written to
 
 
-def build_rows(qc, name):
+def build_rows(qc, name, table=tje.TABLE):
     """The R rows of test_sweep_jvp_every_sample.build_rows (systems, theta, scale, cot, and a direction with every part non-zero) plus
     the direction of the cotangent, one row per class."""
-    rows = tje.build_rows(qc, name)
+    rows = tje.build_rows(qc, name, table)
     ns = rows["init"].size
     rows["vcot"] = np.random.default_rng(1).standard_normal((R, ns)) / np.sqrt(ns)
     return rows
@@ -101,10 +101,14 @@ def test_hvp_launch_table(qc):
 
 
 def test_hvp_reference_reuse_is_sound(qc):
+    assert_reference_reuse_is_sound(qc)
+
+
+def assert_reference_reuse_is_sound(qc, name="hvp-reuse", spec=("unitary", 2, 2, 1, True, True, R, 5, te.U01A2)):
     """Two samples with equal rows have equal recurrence references, bit for bit, and distinct rows differ: the route treats a sample by
-    its own row (theta, scale, cot, vtheta, vscale, vcot) alone."""
-    table = {"hvp-reuse": (("unitary", 2, 2, 1, True, True, R, 5, te.U01A2), False, None, None)}
-    rows = te.build_rows(qc, "hvp-reuse", table)
+    its own row (theta, scale, cot, vtheta, vscale, vcot) alone.  `spec`: a case tuple with S = R and T = 5."""
+    table = {name: (spec, False, None, None)}
+    rows = te.build_rows(qc, name, table)
     rng = np.random.default_rng(3)
     T, m, p, ns = rows["T"], rows["m"], rows["p"], rows["init"].size
     rows.update(vcontrols=rng.standard_normal((m, T)), vdts=0.1 * rng.standard_normal(T), vinit=rng.standard_normal(ns) / np.sqrt(ns),
@@ -128,9 +132,13 @@ def test_hvp_reference_reuse_is_sound(qc):
 
 @pytest.mark.parametrize("name", list(TABLE))
 def test_hvp_rows_are_not_vacuous(qc, name):
+    assert_rows_are_not_vacuous(qc, name)
+
+
+def assert_rows_are_not_vacuous(qc, name, table=TABLE):
     """No class passes on zeros and no class passes for another: every class has max |tgrad_samples| >= 1e-2 and max |tgrad_init| >= 1e-1,
     and any two classes differ by >= 1e-3 in max-norm in both outputs -- 10^6 times the bound a sample is held to."""
-    rows = build_rows(qc, name)
+    rows = build_rows(qc, name, table)
     for k in ("vcontrols", "vinit", "vtheta", "vscale", "vcot", "cot"):
         assert np.all(rows[k] != 0), k
     assert rows["vdts"] is None or np.all(rows["vdts"] != 0)
@@ -199,17 +207,16 @@ def test_hvp_every_sample(qc, name):
         sw.close()
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("name", LINEAR)
-def test_hvp_linear_part_every_sample(qc, name):
+def linear_part(qc, name, table=TABLE, **handle):
     """5: with only vcot given the product is linear in it: tgrad_samples[s] and tgrad_init[s] are the pullback's grad_samples[s] and
-    grad_init[s] with cot = vcot, every sample.  Both sides are within 1e-9 of the truth: 2e-9 max(1, max |.|_s)."""
-    rows = build_rows(qc, name)
-    c = launch_of(rows, TABLE[name][0][6])
+    grad_init[s] with cot = vcot, every sample.  Both sides are within 1e-9 of the truth: 2e-9 max(1, max |.|_s).  `handle`: the
+    keywords of the handle beside the case's own."""
+    rows = build_rows(qc, name, table)
+    c = launch_of(rows, table[name][0][6])
     cls = c["cls"]
-    sw = ts.make_sweep(qc, rows)
+    sw = ts.make_sweep(qc, rows, **handle)
     try:
-        assert_launch(sw, name, table=TABLE)
+        assert_launch(sw, name, table=table)
         Z, _, out = hvp_call(sw, c, dict(vcot=c["vcot"]))
         pull = sw.vjp(Z, c["init"], c["vcot"], c["theta"], c["scale"], per_sample=True, init_grad=True)
         for key, other in (("tgrad_samples", pull[1]), ("tgrad_init", pull[2])):
@@ -230,29 +237,34 @@ def test_hvp_linear_part_every_sample(qc, name):
 
 
 @pytest.mark.gpu
-def test_hvp_scratch_growth_every_sample(qc):
+@pytest.mark.parametrize("name", LINEAR)
+def test_hvp_linear_part_every_sample(qc, name):
+    linear_part(qc, name)
+
+
+def scratch_growth(qc, name, table=TABLE, **handle):
     """One handle at S = 301, then 2049, then 97 with the same T: 5 chunks, 1, 5 again, so dTot / dXs / dLs (shared with `grad` and `vjp`)
     and dXsT / dLsT / dTGsamp grow and are then reused at a smaller stride.  At every S, in this order: `grad_device`, `hvp_device`,
-    `vjp_device`.  The Hessian product passes checks 1 to 3 and carries the bits of a fresh handle's, and so does the pullback after it."""
-    name = "sqrt-301"
-    rows = build_rows(qc, name)
-    sw = ts.make_sweep(qc, rows)
+    `vjp_device`.  The Hessian product passes checks 1 to 3 and carries the bits of a fresh handle's, and so does the pullback after it.
+    `handle`: the keywords of the handle beside the case's own."""
+    rows = build_rows(qc, name, table)
+    sw = ts.make_sweep(qc, rows, **handle)
     try:
         seen = []
         for S in GROWTH:
             c = launch_of(rows, S)
-            seen.append(assert_launch(sw, name, S, table=TABLE)["n_chunks"])
+            seen.append(assert_launch(sw, name, S, table=table)["n_chunks"])
             what = f"every/{name} grown to S = {S}"
             Z = sw.pack(c["controls"], c["dts"])
             J, fids, grad, gs = te.grad_call(sw, Z, c)
             _, dirs, out = hvp_call(sw, c)
             pull = tv.device_call(sw, Z, c, list(tv.OUTPUTS))
-            fresh = ts.make_sweep(qc, rows)
+            fresh = ts.make_sweep(qc, rows, **handle)
             try:
                 _, _, out2 = hvp_call(fresh, c, dirs)
             finally:
                 fresh.close()
-            fresh = ts.make_sweep(qc, rows)
+            fresh = ts.make_sweep(qc, rows, **handle)
             try:
                 pull2 = tv.device_call(fresh, Z, c, list(tv.OUTPUTS))
                 J2, fids2, grad2, gs2 = te.grad_call(fresh, Z, c)
@@ -269,3 +281,8 @@ def test_hvp_scratch_growth_every_sample(qc):
         assert seen == [5, 1, 5]
     finally:
         sw.close()
+
+
+@pytest.mark.gpu
+def test_hvp_scratch_growth_every_sample(qc):
+    scratch_growth(qc, "sqrt-301")

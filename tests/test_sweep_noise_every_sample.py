@@ -70,12 +70,12 @@ def template_m(count):
     return next(M for M in (1, 2, 4, 6, 8) if count <= M)
 
 
-def n_rows(name):
-    return CASES[name][0][6] if name in ONE_ROW_PER_SAMPLE else te.R
+def n_rows(name, table=CASES, one_row=ONE_ROW_PER_SAMPLE):
+    return table[name][0][6] if name in one_row else te.R
 
 
-def class_map(name, S):
-    return np.arange(S) if name in ONE_ROW_PER_SAMPLE else classes(S)
+def class_map(name, S, one_row=ONE_ROW_PER_SAMPLE):
+    return np.arange(S) if name in one_row else classes(S)
 
 
 def build_rows(qc, name, table=CASES, rows=None):
@@ -166,10 +166,14 @@ def test_every_noise_template_is_reached():
 
 
 def test_noise_reference_reuse_is_sound(qc):
+    assert_reference_reuse_is_sound(qc)
+
+
+def assert_reference_reuse_is_sound(qc, name="reuse", spec=("unitary", 2, 2, 2, True, True, te.R, 5, U01A2)):
     """Two samples with equal rows have equal references, bit for bit, and distinct rows differ: `noise_finals` and `noise_grads_forward`
-    treat a sample by its own row (theta, scale, noise) alone."""
-    table = {"reuse": (("unitary", 2, 2, 2, True, True, te.R, 5, U01A2), False, None, None)}
-    rows = build_rows(qc, "reuse", table, rows=te.R)
+    treat a sample by its own row (theta, scale, noise) alone.  `spec`: a case tuple with S = R and T = 5."""
+    table = {name: (spec, False, None, None)}
+    rows = build_rows(qc, name, table, rows=te.R)
     S = 2 * te.R + 3
     c = launch_of(rows, S, classes(S))
     cls = c["cls"]
@@ -192,10 +196,14 @@ def test_noise_reference_reuse_is_sound(qc):
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_noise_rows_are_not_vacuous(qc, name):
+    assert_rows_are_not_vacuous(qc, name)
+
+
+def assert_rows_are_not_vacuous(qc, name, table=CASES, one_row=ONE_ROW_PER_SAMPLE):
     """No class passes on zeros and no class passes for another: every class has max |grad_noise| >= 1e-2, and any two classes differ by
     >= 1e-3 in max-norm in finals, in grad_samples (where it has columns) and in grad_noise -- 10^6 times the gradient bound."""
-    rows = build_rows(qc, name)
-    Rn = n_rows(name)
+    Rn = n_rows(name, table, one_row)
+    rows = build_rows(qc, name, table, rows=Rn)
     finals, fids, gs, gn = reference(rows)
     assert finals.shape == (Rn, rows["init"].size) and gn.shape == (Rn, rows["T"] - 1, rows["p"]) and np.isfinite(fids).all()
     assert gs.shape == (Rn, rows["T"] - 1, rows["m"] + (1 if np.ndim(rows["dts"]) else 0))
@@ -308,23 +316,21 @@ def test_noise_every_sample(qc, name):
         sw.close()
 
 
-@pytest.mark.gpu
-def test_noise_scratch_growth_every_sample(qc):
+def scratch_growth(qc, name, table=CASES, **handle):
     """One handle at S = 301 (host buffers), then 2049 (device tensors), then 97 (host buffers) with the same T: 5 chunks, 1, 5 again, so
     dTot / dXs / dLs grow and are then reused at a smaller stride, and so do the staging buffers `sNoise` and `sGnoise`.  At every S both
-    noise entries carry the bits of a fresh handle's and pass checks 1 to 3."""
-    name = "sqrt-301"
-    rows = build_rows(qc, name)
-    sw = ts.make_sweep(qc, rows)
+    noise entries carry the bits of a fresh handle's and pass checks 1 to 3.  `handle`: the keywords of the handle beside the case's own."""
+    rows = build_rows(qc, name, table, rows=te.R)
+    sw = ts.make_sweep(qc, rows, **handle)
     try:
         seen = []
         for S, calls in zip(GROWTH, (host_calls, device_calls, host_calls)):
             c = launch_of(rows, S, classes(S))
-            seen.append(assert_launch(sw, name, S, table=CASES)["n_chunks"])
+            seen.append(assert_launch(sw, name, S, table=table)["n_chunks"])
             what = f"every/{name} grown to S = {S}"
             Z = sw.pack(c["controls"], c["dts"])
             out = calls(sw, Z, c)
-            fresh = ts.make_sweep(qc, rows)
+            fresh = ts.make_sweep(qc, rows, **handle)
             try:
                 out2 = calls(fresh, Z, c)
             finally:
@@ -334,3 +340,8 @@ def test_noise_scratch_growth_every_sample(qc):
         assert seen == [5, 1, 5]
     finally:
         sw.close()
+
+
+@pytest.mark.gpu
+def test_noise_scratch_growth_every_sample(qc):
+    scratch_growth(qc, "sqrt-301")

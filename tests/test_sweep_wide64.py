@@ -6,7 +6,7 @@ generator norms, exact cases, bits, non-finite input, the unchanged default.
 
 Tolerances are test_sweep.py's (states rtol 1e-10 / atol 1e-11, fidelities 1e-9 absolute; its argument |dF| <= sqrt(N) max|dU| is
 stated for N <= 32, which is exactly this range).  Every GPU test prints its worst error against the bound; measured values:
-profiles/sweep_wide64_summary.txt."""
+profiles/sweep_wide64_summary.txt.  Every sample of launches of 200 .. 510 workgroups: tests/test_sweep_wide64_every_sample.py."""
 import ctypes as C
 import inspect
 import os

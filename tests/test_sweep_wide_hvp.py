@@ -11,7 +11,8 @@ Tolerance (GPU against the reference): that of tests/test_sweep_hvp.py, HVP_RTOL
 narrow one on 2 x 2 tiles with the same degree-10 series (twice-differentiated truncation 2e-14 at ||Y||_1 <= 1/8); its inner products
 have 32 terms where the narrow ones have 16, which moves rounding by a factor of two at 1e-16, far below the bound.  Two quantities that
 are each within 1e-9 of the truth are compared at 2e-9.  The helpers are those of the existing files, imported, not copied; the direction,
-the cotangent and their draws follow test_sweep_hvp.build."""
+the cotangent and their draws follow test_sweep_hvp.build.  Every sample of mid-size and filled launches:
+tests/test_sweep_wide_hvp_every_sample.py."""
 import ctypes as C
 import inspect
 import os

@@ -6,7 +6,8 @@ the squarings, exact equalities at zero noise, the resolution identity, additive
 handle at 2N = 32, a filled launch, bit-level properties, a NaN, the refusals, the objective and the example.
 
 Tolerances are those at the top of tests/test_sweep_noise.py, always against the reference: states rtol 1e-10 / atol 1e-11, fidelities
-1e-9, every gradient output (grad_noise included) per sample |got - want| <= 1e-9 max(1, max |.|)."""
+1e-9, every gradient output (grad_noise included) per sample |got - want| <= 1e-9 max(1, max |.|).
+Every sample of mid-size and filled launches, long chunks, 15 and 16 generators: tests/test_sweep_wide_noise_every_sample.py."""
 import ctypes as C
 import os
 import sys
