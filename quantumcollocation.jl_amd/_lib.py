@@ -406,6 +406,13 @@ def check(rc: int, handle=None) -> None:
         raise QCollocError(rc, msg.decode() if msg else "unknown error")
 
 
+def check_rc(rc: int, last_error: str, handle=None) -> None:
+    """`check` for the side handles (fidelity, terms, robustness, sweep): `last_error` names their own `qc_*_last_error`; handle None
+    asks for the message of a failed create or descriptor query."""
+    if rc != QC_OK:
+        raise QCollocError(rc, getattr(lib, last_error)(handle).decode())
+
+
 def dptr(a: np.ndarray):
     """double* of a C- or F-contiguous float64 numpy array (no copy)."""
     assert a.dtype == np.float64 and (a.flags.c_contiguous or a.flags.f_contiguous)

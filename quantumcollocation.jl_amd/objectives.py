@@ -65,8 +65,7 @@ class _Fidelity:
             self.s = 2 * self.N if kind == "ket" else 2 * self.N * self.N
             rc = _lib.lib.qc_fidelity_create_kind(_lib.QC_FID_KET if kind == "ket" else _lib.QC_FID_DENSITY, self.N, _lib.dptr(goal_iso),
                                                   device, C.byref(self._h))
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_fidelity_last_error(None).decode())
+        _lib.check_rc(rc, "qc_fidelity_last_error")
         self.P = self.s + self.K          # input length: [state ; free phases]
 
     def eval(self, u: np.ndarray, grad: bool = True, hess: bool = True):
@@ -78,8 +77,7 @@ class _Fidelity:
         H = np.empty(self.P * (self.P + 1) // 2) if hess else None
         rc = _lib.lib.qc_fidelity_eval(self._h, _lib.dptr(u), C.byref(F), C.byref(L), _lib.dptr(g) if grad else None,
                                        _lib.dptr(H) if hess else None)
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_fidelity_last_error(self._h).decode())
+        _lib.check_rc(rc, "qc_fidelity_last_error", self._h)
         return F.value, L.value, g, H
 
     def close(self):
@@ -507,8 +505,7 @@ class TrajectoryObjective:
             rc = _lib.lib.qc_terms_create_ext(C.byref(d), C.byref(self._ext), C.byref(self._h))
         else:
             rc = _lib.lib.qc_terms_create(C.byref(d), C.byref(self._h))
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_terms_last_error(None).decode())
+        _lib.check_rc(rc, "qc_terms_last_error")
         nnz = C.c_int64()
         _lib.lib.qc_terms_hess_nnz(self._h, C.byref(nnz))
         self.hess_nnz = nnz.value
@@ -525,8 +522,7 @@ class TrajectoryObjective:
         g = np.empty(self.Z_len) if grad else None
         H = np.empty(self.hess_nnz) if hess else None
         rc = _lib.lib.qc_terms_eval(self._h, _lib.dptr(Z), C.byref(J), _lib.dptr(g) if grad else None, _lib.dptr(H) if hess else None)
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_terms_last_error(self._h).decode())
+        _lib.check_rc(rc, "qc_terms_last_error", self._h)
         return J.value, g, H
 
     def L(self, Z) -> float:
@@ -546,8 +542,7 @@ class TrajectoryObjective:
         s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
         rc = _lib.lib.qc_terms_eval_dev(self._h, dZ.data_ptr(), dJ.data_ptr(), dgrad.data_ptr() if dgrad is not None else None,
                                         dhess.data_ptr() if dhess is not None else None, s)
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_terms_last_error(self._h).decode())
+        _lib.check_rc(rc, "qc_terms_last_error", self._h)
 
     def __getattr__(self, name):
         al = type(self)._ALIASES
@@ -654,8 +649,7 @@ class UnitaryRobustnessObjective:
         self.Z_len = traj.T * traj.dim + traj.global_dim
         self._h = C.c_void_p()
         rc = _lib.lib.qc_robust_create(C.byref(d), C.byref(self._h))
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_robust_last_error(None).decode())
+        _lib.check_rc(rc, "qc_robust_last_error")
         v = C.c_int64()
         _lib.lib.qc_robust_n_vars(self._h, C.byref(v))
         self.n_vars = v.value
@@ -673,8 +667,7 @@ class UnitaryRobustnessObjective:
             r = np.empty(self.hess_nnz, dtype=np.int64)
             c = np.empty(self.hess_nnz, dtype=np.int64)
             rc = _lib.lib.qc_robust_hess_structure(self._h, _lib.iptr(r), _lib.iptr(c), 0)
-            if rc != _lib.QC_OK:
-                raise _lib.QCollocError(rc, _lib.lib.qc_robust_last_error(self._h).decode())
+            _lib.check_rc(rc, "qc_robust_last_error", self._h)
             self._structure = (r, c)
         return self._structure
 
@@ -689,8 +682,7 @@ class UnitaryRobustnessObjective:
         H = np.empty(self.hess_nnz) if hess else None
         rc = _lib.lib.qc_robust_eval(self._h, _lib.dptr(Z), C.byref(L), _lib.dptr(g) if grad else None,
                                      _lib.dptr(H) if hess and self.hess_nnz else None)
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_robust_last_error(self._h).decode())
+        _lib.check_rc(rc, "qc_robust_last_error", self._h)
         return L.value, g, H
 
     def L(self, Z) -> float:
@@ -710,8 +702,7 @@ class UnitaryRobustnessObjective:
         s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
         rc = _lib.lib.qc_robust_eval_dev(self._h, dZ.data_ptr(), dL.data_ptr() if dL is not None else None,
                                          dgrad.data_ptr() if dgrad is not None else None, dhess.data_ptr() if dhess is not None else None, s)
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_robust_last_error(self._h).decode())
+        _lib.check_rc(rc, "qc_robust_last_error", self._h)
 
     def __getattr__(self, name):
         al = type(self)._ALIASES

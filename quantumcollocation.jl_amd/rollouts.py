@@ -121,6 +121,7 @@ def rollout_fidelity(traj: NamedTrajectory, system, state_name: str = "ψ̃", co
 # ---------------------------------------------------------------------------------------------------------------
 #  Rollout sweeps over perturbed systems through `qc_sweep_*`
 # ---------------------------------------------------------------------------------------------------------------
+_ERR = "qc_sweep_last_error"      # what `_lib.check_rc` asks for the message of a failed `qc_sweep_*` call
 _FID_KINDS = {None: _lib.QC_SWEEP_FID_NONE, "none": _lib.QC_SWEEP_FID_NONE, "unitary": _lib.QC_FID_UNITARY, "ket": _lib.QC_FID_KET,
               "density": _lib.QC_FID_DENSITY}
 
@@ -161,6 +162,41 @@ def _sweep_samples(p: int, m: int, theta, scale):
     if S < 1:
         raise ValueError("at least one sample")
     return S, (np.ascontiguousarray(theta) if p else None), (np.ascontiguousarray(scale) if scale is not None and m else None)
+
+
+def _host_ptr(a, given: bool = False):
+    """double* of an optional host array: null when it is None or empty -- or, with `given` (the directions vZ, vinit, vtheta, vscale,
+    vcot, which the library counts as given even when empty), only when it is None."""
+    return _lib.dptr(a) if (a is not None and (given or a.size)) else None
+
+
+def _dev_ptr(t, use=True):
+    """Device pointer of an optional tensor: null when it is None or has no elements, or when the handle has no `use` for it."""
+    return t.data_ptr() if (t is not None and use and t.numel()) else None
+
+
+def _stream_of(stream):
+    return stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+
+
+def _refuse_all_none(what: str, *tensors):
+    for t in tensors:
+        if t is not None:
+            return
+    raise ValueError(f"every {what} is None")
+
+
+def _device_counts(sw) -> dict:
+    """Entries of every named tensor of the device entries as (per sample, shared by the samples): a call with S samples expects
+    per sample * S + shared of them."""
+    shared = lambda cnt: (0, cnt)
+    Z, state, states, one = shared(sw.Z_len), shared(sw.ns), (sw.ns, 0), (1, 0)
+    theta, scale, derivs, noise = (sw.p, 0), (sw.m, 0), ((sw.T - 1) * sw.n_deriv, 0), ((sw.T - 1) * sw.p, 0)
+    return {"dZ": Z, "dinit": state, "dtheta": theta, "dscale": scale, "dweights": one, "dcot": states,
+            "dvZ": Z, "dvinit": state, "dvtheta": theta, "dvscale": scale, "dvcot": states, "dnoise": noise,
+            "dfinals": states, "dfids": one, "dJ": shared(1), "dgrad": Z, "dgrad_samples": derivs, "dgrad_init": states,
+            "dgrad_theta": theta, "dgrad_scale": scale, "dgrad_noise": noise,
+            "dtfinals": states, "dtfids": one, "dtgrad": Z, "dtgrad_samples": derivs, "dtgrad_init": states}
 
 
 class RolloutSweep:
@@ -212,18 +248,21 @@ class RolloutSweep:
                  stored_states: bool = False, wide_params: bool = False, wide_stored: bool = False, wide_tangent: bool = False,
                  wide_noise: bool = False, wide_hessian: bool = False, wide64: bool = False):
         self._h = None
-        if wide64 and not wide:
-            raise ValueError("wide64=True needs wide=True")
-        if wide_hessian and not wide:
-            raise ValueError("wide_hessian=True needs wide=True")
-        if wide_noise and not wide:
-            raise ValueError("wide_noise=True needs wide=True")
-        if wide_params and not wide:
-            raise ValueError("wide_params=True needs wide=True")
-        if wide_tangent and not wide:
-            raise ValueError("wide_tangent=True needs wide=True")
-        if wide_stored and not (wide and stored_states):
-            raise ValueError("wide_stored=True needs wide=True and stored_states=True")
+        flags = (   # (keyword, given, its bit of qc_sweep_desc.wide, what it needs, the refusal without that)
+            ("wide64", wide64, _lib.QC_SWEEP_WIDE_64, wide, "wide64=True needs wide=True"),
+            ("wide_hessian", wide_hessian, _lib.QC_SWEEP_WIDE_HESSIAN, wide, "wide_hessian=True needs wide=True"),
+            ("wide_noise", wide_noise, _lib.QC_SWEEP_WIDE_NOISE, wide, "wide_noise=True needs wide=True"),
+            ("wide_params", wide_params, _lib.QC_SWEEP_WIDE_PARAMS, wide, "wide_params=True needs wide=True"),
+            ("wide_tangent", wide_tangent, _lib.QC_SWEEP_WIDE_TANGENT, wide, "wide_tangent=True needs wide=True"),
+            ("wide_stored", wide_stored, _lib.QC_SWEEP_WIDE_STORED, wide and stored_states,
+             "wide_stored=True needs wide=True and stored_states=True"),
+            ("wide", wide, _lib.QC_SWEEP_WIDE, True, None))
+        wide_bits = 0
+        for keyword, given, bit, needs, refusal in flags:
+            if given and not needs:
+                raise ValueError(refusal)
+            setattr(self, keyword, bool(given))
+            wide_bits |= bit if given else 0
         m = system.n_drives
         N = system.state_levels
         n = 2 * N
@@ -257,25 +296,20 @@ class RolloutSweep:
         d.subspace = self._sub.ctypes.data_as(C.POINTER(C.c_int32)) if self._sub is not None else None
         d.n_sub = 0 if self._sub is None else int(self._sub.size)
         d.device = device
-        d.wide = ((_lib.QC_SWEEP_WIDE if wide else 0) | (_lib.QC_SWEEP_WIDE_PARAMS if wide_params else 0)
-                  | (_lib.QC_SWEEP_WIDE_STORED if wide_stored else 0) | (_lib.QC_SWEEP_WIDE_TANGENT if wide_tangent else 0)
-                  | (_lib.QC_SWEEP_WIDE_NOISE if wide_noise else 0) | (_lib.QC_SWEEP_WIDE_HESSIAN if wide_hessian else 0)
-                  | (_lib.QC_SWEEP_WIDE_64 if wide64 else 0))
-        self.wide64 = bool(wide64)
-        self.wide_hessian = bool(wide_hessian)
-        self.wide_tangent = bool(wide_tangent)
-        self.wide_noise = bool(wide_noise)
-        self.wide = bool(wide)
-        self.wide_params = bool(wide_params)
-        self.wide_stored = bool(wide_stored)
+        d.wide = wide_bits
         d.reserved1[0] = _lib.QC_SWEEP_STORED_STATES if stored_states else 0
         self.stored_states = bool(stored_states)
         self._desc = d
+        self._counts = _device_counts(self)
         h = C.c_void_p()
-        rc = _lib.lib.qc_sweep_create(C.byref(d), C.byref(h))
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(None).decode())
+        _lib.check_rc(_lib.lib.qc_sweep_create(C.byref(d), C.byref(h)), _ERR)
         self._h = h
+
+    def _scope(self, supported):
+        """(served?, the library's reason why not or None) from a `qc_sweep_desc_*_supported` function."""
+        ok = C.c_int32()
+        _lib.check_rc(supported(C.byref(self._desc), C.byref(ok)), _ERR)
+        return bool(ok.value), (None if ok.value else _lib.lib.qc_sweep_last_error(None).decode())
 
     @property
     def kernel_name(self) -> str:
@@ -286,9 +320,7 @@ class RolloutSweep:
     def launch(self, S: int):
         """(mfma, chunk, n_chunks) of a call with S samples: `qc_sweep_desc_launch`."""
         mf, ch, nch = C.c_int32(), C.c_int64(), C.c_int64()
-        rc = _lib.lib.qc_sweep_desc_launch(C.byref(self._desc), int(S), C.byref(mf), C.byref(ch), C.byref(nch))
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(None).decode())
+        _lib.check_rc(_lib.lib.qc_sweep_desc_launch(C.byref(self._desc), int(S), C.byref(mf), C.byref(ch), C.byref(nch)), _ERR)
         return bool(mf.value), ch.value, nch.value
 
     def pack(self, controls, dts=None) -> np.ndarray:
@@ -308,45 +340,88 @@ class RolloutSweep:
     def _samples(self, theta, scale):
         return _sweep_samples(self.p, self.m, theta, scale)
 
-    def eval(self, Z, init, theta, scale=None, finals: bool = True, fids: Optional[bool] = None):
-        """(finals, fids): finals (2N cols) x S or None; fids S values or None (default: when the handle has a fidelity)."""
+    # -- the argument checks of the host entries ... --------------------------------------------------------------------------------
+    def _host_Z_init(self, Z, init):
         Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
         if Z.size != self.Z_len:
             raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
         init = np.ascontiguousarray(init, dtype=np.float64).ravel()
         if init.size != self.ns:
             raise ValueError(f"initial state has length {init.size}, expected {self.ns}")
+        return Z, init
+
+    @staticmethod
+    def _host_weights(weights, S):
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+            if weights.size != S:
+                raise ValueError(f"weights must have {S} entries")
+        return weights
+
+    @staticmethod
+    def _host_direction(a, cnt, what):
+        """A direction as a flat array of `cnt` entries; None stays None."""
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.size != cnt:
+            raise ValueError(f"{what} has {a.size} entries, expected {cnt}")
+        return a
+
+    # -- ... and of the device entries ------------------------------------------------------------------------------------------------
+    def _check_device(self, S, **tensors):
+        """Every tensor that is given is contiguous float64 with the count `_device_counts` states for its name."""
+        for what, t in tensors.items():
+            if t is not None:
+                per_sample, shared = self._counts[what]
+                cnt = per_sample * S + shared
+                if t.numel() != cnt or t.dtype != torch.float64 or not t.is_contiguous():
+                    raise ValueError(f"{what} must be a contiguous float64 tensor of {cnt} entries")
+
+    def _require_dtheta(self, dtheta):
+        if self.p and dtheta is None:
+            raise ValueError("dtheta is required: the handle has perturbations")
+
+    def _refuse_unbacked(self, what_theta, like_theta, what_scale, like_scale):
+        """A tensor shaped like theta on a handle without perturbations, one shaped like scale on a handle without drives."""
+        if like_theta is not None and not self.p:
+            raise ValueError(f"{what_theta} is given but the handle has no perturbations")
+        if like_scale is not None and not self.m:
+            raise ValueError(f"{what_scale} is given but the handle has no drives")
+
+    def _noise_S(self, dnoise):
+        if dnoise is None:
+            raise ValueError("dnoise is required")
+        per = (self.T - 1) * self.p
+        if not per or dnoise.numel() % per or not dnoise.numel():
+            raise ValueError(f"dnoise must hold S x {self.T - 1} x {self.p} entries")
+        return dnoise.numel() // per
+
+    def eval(self, Z, init, theta, scale=None, finals: bool = True, fids: Optional[bool] = None):
+        """(finals, fids): finals (2N cols) x S or None; fids S values or None (default: when the handle has a fidelity)."""
+        Z, init = self._host_Z_init(Z, init)
         S, theta, scale = self._samples(theta, scale)
         if fids is None:
             fids = self.fid_kind != _lib.QC_SWEEP_FID_NONE
         out = np.empty((S, self.ns)) if finals else None
         f = np.empty(S) if fids else None
-        rc = _lib.lib.qc_sweep_eval(self._h, _lib.dptr(Z), _lib.dptr(init), S, _lib.dptr(theta) if theta is not None else None,
-                                    _lib.dptr(scale) if scale is not None else None, _lib.dptr(out) if finals else None,
-                                    _lib.dptr(f) if fids else None)
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        _lib.check_rc(_lib.lib.qc_sweep_eval(self._h, _lib.dptr(Z), _lib.dptr(init), S, _host_ptr(theta), _host_ptr(scale), _host_ptr(out),
+                                             _host_ptr(f)), _ERR, self._h)
         return (np.ascontiguousarray(out.T) if finals else None), f
 
     def eval_device(self, dZ, dinit, dtheta, dscale, dfinals, dfids, stream=None):
         """Device-resident evaluation on torch CUDA tensors (float64), asynchronous on `stream`: dtheta S x n_pert (None
         without perturbations: dfinals / dfids give S), dscale S x m or None, dfinals S x (2N cols) or None, dfids S or None."""
-        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        s = _stream_of(stream)
         if dfids is not None:
-            S = dfids.numel()
+            S = dfids.numel()       # (dfids gives S and is not checked further, as ever)
         elif dfinals is not None:
             S = dfinals.numel() // self.ns
         else:
             raise ValueError("dfinals and dfids are both None")
-        for t, cnt, what in ((dtheta, S * self.p, "dtheta"), (dscale, S * self.m, "dscale"), (dfinals, S * self.ns, "dfinals"), (dZ, self.Z_len, "dZ"),
-                             (dinit, self.ns, "dinit")):
-            if t is not None and (t.numel() != cnt or t.dtype != torch.float64 or not t.is_contiguous()):
-                raise ValueError(f"{what} must be a contiguous float64 tensor of {cnt} entries")
-        rc = _lib.lib.qc_sweep_eval_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, dtheta.data_ptr() if (dtheta is not None and self.p) else None,
-                                        dscale.data_ptr() if (dscale is not None and self.m) else None,
-                                        dfinals.data_ptr() if dfinals is not None else None, dfids.data_ptr() if dfids is not None else None, s)
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        self._check_device(S, dtheta=dtheta, dscale=dscale, dfinals=dfinals, dZ=dZ, dinit=dinit)
+        _lib.check_rc(_lib.lib.qc_sweep_eval_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, _dev_ptr(dtheta, self.p), _dev_ptr(dscale, self.m),
+                                                 _dev_ptr(dfinals), _dev_ptr(dfids), s), _ERR, self._h)
 
     # -- gradients: the adjoint of the sweep -------------------------------------------------------------------------------------
     @property
@@ -360,63 +435,38 @@ class RolloutSweep:
         state columns, antisymmetric generators; with `stored_states` the "mfma16-sweep" form -- with `wide_stored` the "mfma32-sweep"
         form as well --, any fidelity, any generators.)
         `grad_unsupported_reason` says why not."""
-        return self._grad_scope()[0]
+        return self._scope(_lib.lib.qc_sweep_desc_grad_supported)[0]
 
     @property
     def grad_unsupported_reason(self) -> Optional[str]:
-        return self._grad_scope()[1]
-
-    def _grad_scope(self):
-        ok = C.c_int32()
-        rc = _lib.lib.qc_sweep_desc_grad_supported(C.byref(self._desc), C.byref(ok))
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(None).decode())
-        return bool(ok.value), (None if ok.value else _lib.lib.qc_sweep_last_error(None).decode())
+        return self._scope(_lib.lib.qc_sweep_desc_grad_supported)[1]
 
     def grad(self, Z, init, theta, scale=None, weights=None, per_sample: bool = False):
         """(J, fids, grad[, grad_samples]): J = sum_s w_s F_s (weights: S values, default 1/S each), the S fidelities, the dense
         gradient of J over the trajectory vector (zero outside the controls and timesteps of knots 0 .. T-2) and, with
         `per_sample`, dF_s/d(a_t, dt_t) as an S x (T-1) x n_deriv array (drives, then the timestep)."""
-        Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
-        if Z.size != self.Z_len:
-            raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
-        init = np.ascontiguousarray(init, dtype=np.float64).ravel()
-        if init.size != self.ns:
-            raise ValueError(f"initial state has length {init.size}, expected {self.ns}")
+        Z, init = self._host_Z_init(Z, init)
         S, theta, scale = self._samples(theta, scale)
-        if weights is not None:
-            weights = np.ascontiguousarray(weights, dtype=np.float64).ravel()
-            if weights.size != S:
-                raise ValueError(f"weights must have {S} entries")
+        weights = self._host_weights(weights, S)
         f, J, g = np.empty(S), C.c_double(), np.empty(self.Z_len)
         gs = np.empty((S, self.T - 1, self.n_deriv)) if per_sample else None
-        opt = lambda a: _lib.dptr(a) if a is not None else None
-        rc = _lib.lib.qc_sweep_grad(self._h, _lib.dptr(Z), _lib.dptr(init), S, opt(theta), opt(scale), opt(weights), _lib.dptr(f), C.byref(J),
-                                    _lib.dptr(g), opt(gs) if (per_sample and gs.size) else None)
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        _lib.check_rc(_lib.lib.qc_sweep_grad(self._h, _lib.dptr(Z), _lib.dptr(init), S, _host_ptr(theta), _host_ptr(scale), _host_ptr(weights),
+                                             _lib.dptr(f), C.byref(J), _lib.dptr(g), _host_ptr(gs)), _ERR, self._h)
         return (J.value, f, g, gs) if per_sample else (J.value, f, g)
 
     def grad_device(self, dZ, dinit, S: int, dtheta=None, dscale=None, dweights=None, dfids=None, dJ=None, dgrad=None, dgrad_samples=None,
                     stream=None):
         """Device-resident gradient on torch CUDA tensors (float64), asynchronous on `stream`: `qc_sweep_grad_dev`.  Outputs are
         optional one at a time: dfids S, dJ one value, dgrad Z_len, dgrad_samples S x (T-1) x n_deriv."""
-        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        s = _stream_of(stream)
         S = int(S)
-        if dfids is None and dJ is None and dgrad is None and dgrad_samples is None:
-            raise ValueError("every output is None")
-        for t, cnt, what in ((dZ, self.Z_len, "dZ"), (dinit, self.ns, "dinit"), (dtheta, S * self.p, "dtheta"), (dscale, S * self.m, "dscale"),
-                             (dweights, S, "dweights"), (dfids, S, "dfids"), (dJ, 1, "dJ"), (dgrad, self.Z_len, "dgrad"),
-                             (dgrad_samples, S * (self.T - 1) * self.n_deriv, "dgrad_samples")):
-            if t is not None and (t.numel() != cnt or t.dtype != torch.float64 or not t.is_contiguous()):
-                raise ValueError(f"{what} must be a contiguous float64 tensor of {cnt} entries")
-        if self.p and dtheta is None:
-            raise ValueError("dtheta is required: the handle has perturbations")
-        ptr = lambda t, use=True: t.data_ptr() if (t is not None and use and t.numel()) else None
-        rc = _lib.lib.qc_sweep_grad_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dweights),
-                                        ptr(dfids), ptr(dJ), ptr(dgrad), ptr(dgrad_samples), s)
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        ptr = _dev_ptr
+        _refuse_all_none("output", dfids, dJ, dgrad, dgrad_samples)
+        self._check_device(S, dZ=dZ, dinit=dinit, dtheta=dtheta, dscale=dscale, dweights=dweights, dfids=dfids, dJ=dJ, dgrad=dgrad,
+                           dgrad_samples=dgrad_samples)
+        self._require_dtheta(dtheta)
+        _lib.check_rc(_lib.lib.qc_sweep_grad_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dweights),
+                                                 ptr(dfids), ptr(dJ), ptr(dgrad), ptr(dgrad_samples), s), _ERR, self._h)
 
     # -- gradients with respect to the systems: dF_s/dtheta and dF_s/dscale ---------------------------------------------------
     def param_grad(self, Z, init, theta, scale=None, weights=None, with_controls: bool = False):
@@ -424,51 +474,31 @@ class RolloutSweep:
         None: taken at all ones), raw per-sample values from one backward walk (`qc_sweep_grad_params`; "mfma16-sweep" handles, and
         "mfma32-sweep" handles made with `wide_params`).  With `with_controls`:
         (J, fids, grad, grad_theta, grad_scale), J and the dense gradient over the trajectory vector as `grad` returns them."""
-        Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
-        if Z.size != self.Z_len:
-            raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
-        init = np.ascontiguousarray(init, dtype=np.float64).ravel()
-        if init.size != self.ns:
-            raise ValueError(f"initial state has length {init.size}, expected {self.ns}")
+        Z, init = self._host_Z_init(Z, init)
         S, theta, scale = self._samples(theta, scale)
-        if weights is not None:
-            weights = np.ascontiguousarray(weights, dtype=np.float64).ravel()
-            if weights.size != S:
-                raise ValueError(f"weights must have {S} entries")
+        weights = self._host_weights(weights, S)
         f, gth, gsc = np.empty(S), np.empty((S, self.p)), np.empty((S, self.m))
         J, g = C.c_double(), (np.empty(self.Z_len) if with_controls else None)
-        opt = lambda a: _lib.dptr(a) if (a is not None and a.size) else None
-        rc = _lib.lib.qc_sweep_grad_params(self._h, _lib.dptr(Z), _lib.dptr(init), S, opt(theta), opt(scale), opt(weights), _lib.dptr(f),
-                                           C.byref(J) if with_controls else None, opt(g), None, opt(gth), opt(gsc))
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        _lib.check_rc(_lib.lib.qc_sweep_grad_params(self._h, _lib.dptr(Z), _lib.dptr(init), S, _host_ptr(theta), _host_ptr(scale), _host_ptr(weights),
+                                                    _lib.dptr(f), C.byref(J) if with_controls else None, _host_ptr(g), None, _host_ptr(gth),
+                                                    _host_ptr(gsc)), _ERR, self._h)
         return (J.value, f, g, gth, gsc) if with_controls else (f, gth, gsc)
 
     def param_grad_device(self, dZ, dinit, S: int, dtheta=None, dscale=None, dweights=None, dfids=None, dJ=None, dgrad=None, dgrad_samples=None,
                           dgrad_theta=None, dgrad_scale=None, stream=None):
         """`grad_device` plus dgrad_theta (S x n_pert) and dgrad_scale (S x m): `qc_sweep_grad_params_dev`.  Every output is
         optional; without dgrad and dgrad_samples no per-interval buffer is written."""
-        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        s = _stream_of(stream)
         S = int(S)
-        if all(t is None for t in (dfids, dJ, dgrad, dgrad_samples, dgrad_theta, dgrad_scale)):
-            raise ValueError("every output is None")
-        if dgrad_theta is not None and not self.p:
-            raise ValueError("dgrad_theta is given but the handle has no perturbations")
-        if dgrad_scale is not None and not self.m:
-            raise ValueError("dgrad_scale is given but the handle has no drives")
-        for t, cnt, what in ((dZ, self.Z_len, "dZ"), (dinit, self.ns, "dinit"), (dtheta, S * self.p, "dtheta"), (dscale, S * self.m, "dscale"),
-                             (dweights, S, "dweights"), (dfids, S, "dfids"), (dJ, 1, "dJ"), (dgrad, self.Z_len, "dgrad"),
-                             (dgrad_samples, S * (self.T - 1) * self.n_deriv, "dgrad_samples"), (dgrad_theta, S * self.p, "dgrad_theta"),
-                             (dgrad_scale, S * self.m, "dgrad_scale")):
-            if t is not None and (t.numel() != cnt or t.dtype != torch.float64 or not t.is_contiguous()):
-                raise ValueError(f"{what} must be a contiguous float64 tensor of {cnt} entries")
-        if self.p and dtheta is None:
-            raise ValueError("dtheta is required: the handle has perturbations")
-        ptr = lambda t, use=True: t.data_ptr() if (t is not None and use and t.numel()) else None
-        rc = _lib.lib.qc_sweep_grad_params_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dweights),
-                                               ptr(dfids), ptr(dJ), ptr(dgrad), ptr(dgrad_samples), ptr(dgrad_theta), ptr(dgrad_scale), s)
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        ptr = _dev_ptr
+        _refuse_all_none("output", dfids, dJ, dgrad, dgrad_samples, dgrad_theta, dgrad_scale)
+        self._refuse_unbacked("dgrad_theta", dgrad_theta, "dgrad_scale", dgrad_scale)
+        self._check_device(S, dZ=dZ, dinit=dinit, dtheta=dtheta, dscale=dscale, dweights=dweights, dfids=dfids, dJ=dJ, dgrad=dgrad,
+                           dgrad_samples=dgrad_samples, dgrad_theta=dgrad_theta, dgrad_scale=dgrad_scale)
+        self._require_dtheta(dtheta)
+        _lib.check_rc(_lib.lib.qc_sweep_grad_params_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m),
+                                                        ptr(dweights), ptr(dfids), ptr(dJ), ptr(dgrad), ptr(dgrad_samples), ptr(dgrad_theta),
+                                                        ptr(dgrad_scale), s), _ERR, self._h)
 
     # -- pullbacks: the derivatives of any function of the final states -------------------------------------------------------------
     @property
@@ -477,18 +507,11 @@ class RolloutSweep:
         generators; with `stored_states` the "mfma16-sweep" form (with `wide_stored`: or "mfma32-sweep") and any generators; any
         fidelity or none.)
         `vjp_unsupported_reason` says why not."""
-        return self._vjp_scope()[0]
+        return self._scope(_lib.lib.qc_sweep_desc_vjp_supported)[0]
 
     @property
     def vjp_unsupported_reason(self) -> Optional[str]:
-        return self._vjp_scope()[1]
-
-    def _vjp_scope(self):
-        ok = C.c_int32()
-        rc = _lib.lib.qc_sweep_desc_vjp_supported(C.byref(self._desc), C.byref(ok))
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(None).decode())
-        return bool(ok.value), (None if ok.value else _lib.lib.qc_sweep_last_error(None).decode())
+        return self._scope(_lib.lib.qc_sweep_desc_vjp_supported)[1]
 
     def vjp(self, Z, init, cot, theta, scale=None, per_sample: bool = False, init_grad: bool = False, params: bool = False):
         """The pullback of the final states: with phi_s = <cot[s], x_final[s]> (cot: S x (2N cols), one cotangent per sample), returns
@@ -498,12 +521,7 @@ class RolloutSweep:
             init_grad    grad_init, S x (2N cols): dphi_s/dinit
             params       grad_theta (S x n_pert) and grad_scale (S x m), two entries ("mfma16-sweep" handles, and "mfma32-sweep" handles made
                          with `wide_params`)."""
-        Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
-        if Z.size != self.Z_len:
-            raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
-        init = np.ascontiguousarray(init, dtype=np.float64).ravel()
-        if init.size != self.ns:
-            raise ValueError(f"initial state has length {init.size}, expected {self.ns}")
+        Z, init = self._host_Z_init(Z, init)
         S, theta, scale = self._samples(theta, scale)
         cot = np.ascontiguousarray(cot, dtype=np.float64)
         if cot.shape != (S, self.ns):
@@ -512,11 +530,8 @@ class RolloutSweep:
         gs = np.empty((S, self.T - 1, self.n_deriv)) if per_sample else None
         gi = np.empty((S, self.ns)) if init_grad else None
         gth, gsc = (np.empty((S, self.p)), np.empty((S, self.m))) if params else (None, None)
-        opt = lambda a: _lib.dptr(a) if (a is not None and a.size) else None
-        rc = _lib.lib.qc_sweep_vjp(self._h, _lib.dptr(Z), _lib.dptr(init), S, opt(theta), opt(scale), _lib.dptr(cot), None, _lib.dptr(g), opt(gs),
-                                   opt(gi), opt(gth), opt(gsc))
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        _lib.check_rc(_lib.lib.qc_sweep_vjp(self._h, _lib.dptr(Z), _lib.dptr(init), S, _host_ptr(theta), _host_ptr(scale), _lib.dptr(cot), None,
+                                            _lib.dptr(g), _host_ptr(gs), _host_ptr(gi), _host_ptr(gth), _host_ptr(gsc)), _ERR, self._h)
         return (g,) + ((gs,) if per_sample else ()) + ((gi,) if init_grad else ()) + ((gth, gsc) if params else ())
 
     def vjp_device(self, dZ, dinit, S: int, dcot, dtheta=None, dscale=None, dfinals=None, dgrad=None, dgrad_samples=None, dgrad_init=None,
@@ -524,108 +539,67 @@ class RolloutSweep:
         """Device-resident pullback on torch CUDA tensors (float64), asynchronous on `stream`: `qc_sweep_vjp_dev`.  dcot S x (2N cols);
         outputs optional one at a time: dfinals S x (2N cols) (the bits of `eval_device`), dgrad Z_len, dgrad_samples
         S x (T-1) x n_deriv, dgrad_init S x (2N cols), dgrad_theta S x n_pert, dgrad_scale S x m."""
-        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        s = _stream_of(stream)
         S = int(S)
-        if all(t is None for t in (dfinals, dgrad, dgrad_samples, dgrad_init, dgrad_theta, dgrad_scale)):
-            raise ValueError("every output is None")
+        ptr = _dev_ptr
+        _refuse_all_none("output", dfinals, dgrad, dgrad_samples, dgrad_init, dgrad_theta, dgrad_scale)
         if dcot is None:
             raise ValueError("dcot is required")
-        if dgrad_theta is not None and not self.p:
-            raise ValueError("dgrad_theta is given but the handle has no perturbations")
-        if dgrad_scale is not None and not self.m:
-            raise ValueError("dgrad_scale is given but the handle has no drives")
-        for t, cnt, what in ((dZ, self.Z_len, "dZ"), (dinit, self.ns, "dinit"), (dcot, S * self.ns, "dcot"), (dtheta, S * self.p, "dtheta"),
-                             (dscale, S * self.m, "dscale"), (dfinals, S * self.ns, "dfinals"), (dgrad, self.Z_len, "dgrad"),
-                             (dgrad_samples, S * (self.T - 1) * self.n_deriv, "dgrad_samples"), (dgrad_init, S * self.ns, "dgrad_init"),
-                             (dgrad_theta, S * self.p, "dgrad_theta"), (dgrad_scale, S * self.m, "dgrad_scale")):
-            if t is not None and (t.numel() != cnt or t.dtype != torch.float64 or not t.is_contiguous()):
-                raise ValueError(f"{what} must be a contiguous float64 tensor of {cnt} entries")
-        if self.p and dtheta is None:
-            raise ValueError("dtheta is required: the handle has perturbations")
-        ptr = lambda t, use=True: t.data_ptr() if (t is not None and use and t.numel()) else None
-        rc = _lib.lib.qc_sweep_vjp_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dcot), ptr(dfinals),
-                                       ptr(dgrad), ptr(dgrad_samples), ptr(dgrad_init), ptr(dgrad_theta), ptr(dgrad_scale), s)
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        self._refuse_unbacked("dgrad_theta", dgrad_theta, "dgrad_scale", dgrad_scale)
+        self._check_device(S, dZ=dZ, dinit=dinit, dcot=dcot, dtheta=dtheta, dscale=dscale, dfinals=dfinals, dgrad=dgrad, dgrad_samples=dgrad_samples,
+                           dgrad_init=dgrad_init, dgrad_theta=dgrad_theta, dgrad_scale=dgrad_scale)
+        self._require_dtheta(dtheta)
+        _lib.check_rc(_lib.lib.qc_sweep_vjp_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dcot),
+                                                ptr(dfinals), ptr(dgrad), ptr(dgrad_samples), ptr(dgrad_init), ptr(dgrad_theta), ptr(dgrad_scale), s),
+                      _ERR, self._h)
 
     # -- pushforwards: the tangent of the final states and fidelities along one direction -------------------------------------------
     @property
     def jvp_supported(self) -> bool:
         """Does `jvp` serve this handle?  (`qc_sweep_desc_jvp_supported`: the "mfma16-sweep" form, or "mfma32-sweep" with `wide_tangent`; any generators -- Lindblad ones
         included -- and any fidelity or none.)  `jvp_unsupported_reason` says why not."""
-        return self._jvp_scope()[0]
+        return self._scope(_lib.lib.qc_sweep_desc_jvp_supported)[0]
 
     @property
     def jvp_unsupported_reason(self) -> Optional[str]:
-        return self._jvp_scope()[1]
-
-    def _jvp_scope(self):
-        ok = C.c_int32()
-        rc = _lib.lib.qc_sweep_desc_jvp_supported(C.byref(self._desc), C.byref(ok))
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(None).decode())
-        return bool(ok.value), (None if ok.value else _lib.lib.qc_sweep_last_error(None).decode())
+        return self._scope(_lib.lib.qc_sweep_desc_jvp_supported)[1]
 
     def jvp(self, Z, init, vZ, theta, scale=None, vinit=None, vtheta=None, vscale=None, fids: bool = False):
         """The pushforward of the final states along the direction (vZ, vinit, vtheta, vscale): `tfinals`, S x (2N cols), row s the tangent
         of sample s's final state, and with `fids` also `tfids`, the S tangents of the fidelities.  vZ (Z_len, the layout of Z: only the
         controls and timesteps of knots 0 .. T-2 act) and vinit (2N cols) are shared by the samples, vtheta is S x n_pert, vscale S x m
         (valid with scale = None: taken at all ones); whichever is None is zero, at least one must be given."""
-        Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
-        if Z.size != self.Z_len:
-            raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
-        init = np.ascontiguousarray(init, dtype=np.float64).ravel()
-        if init.size != self.ns:
-            raise ValueError(f"initial state has length {init.size}, expected {self.ns}")
+        Z, init = self._host_Z_init(Z, init)
         if theta is None and scale is None and (vtheta is not None or vscale is not None):
             S = np.asarray(vtheta if vtheta is not None else vscale).reshape(-1, self.p if vtheta is not None else self.m).shape[0]
         else:
             S, theta, scale = self._samples(theta, scale)
-        vec = lambda a, cnt, what: None if a is None else self._sized(np.ascontiguousarray(a, dtype=np.float64).ravel(), cnt, what)
+        vec, ptr = self._host_direction, _host_ptr
         vZ, vinit = vec(vZ, self.Z_len, "vZ"), vec(vinit, self.ns, "vinit")
         vtheta, vscale = vec(vtheta, S * self.p, "vtheta"), vec(vscale, S * self.m, "vscale")
         tf = np.empty((S, self.ns))
         tfid = np.empty(S) if fids else None
-        opt = lambda a: _lib.dptr(a) if a is not None else None
-        rc = _lib.lib.qc_sweep_jvp(self._h, _lib.dptr(Z), _lib.dptr(init), S, opt(theta), opt(scale), opt(vZ), opt(vinit), opt(vtheta), opt(vscale),
-                                   None, None, _lib.dptr(tf), opt(tfid))
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        _lib.check_rc(_lib.lib.qc_sweep_jvp(self._h, _lib.dptr(Z), _lib.dptr(init), S, ptr(theta), ptr(scale), ptr(vZ, True), ptr(vinit, True),
+                                            ptr(vtheta, True), ptr(vscale, True), None, None, _lib.dptr(tf), ptr(tfid)), _ERR, self._h)
         return (tf, tfid) if fids else tf
-
-    @staticmethod
-    def _sized(a, cnt, what):
-        if a.size != cnt:
-            raise ValueError(f"{what} has {a.size} entries, expected {cnt}")
-        return a
 
     def jvp_device(self, dZ, dinit, S: int, dtheta=None, dscale=None, dvZ=None, dvinit=None, dvtheta=None, dvscale=None, dfinals=None, dfids=None,
                    dtfinals=None, dtfids=None, stream=None):
         """Device-resident pushforward on torch CUDA tensors (float64), asynchronous on `stream`: `qc_sweep_jvp_dev`.  Directions, each
         optional, at least one: dvZ Z_len, dvinit 2N cols, dvtheta S x n_pert, dvscale S x m.  Outputs, each optional, at least one:
         dfinals S x (2N cols) and dfids S (the bits of `eval_device`), dtfinals S x (2N cols), dtfids S."""
-        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        s = _stream_of(stream)
         S = int(S)
-        if all(t is None for t in (dvZ, dvinit, dvtheta, dvscale)):
-            raise ValueError("every direction is None")
-        if all(t is None for t in (dfinals, dfids, dtfinals, dtfids)):
-            raise ValueError("every output is None")
-        if dvtheta is not None and not self.p:
-            raise ValueError("dvtheta is given but the handle has no perturbations")
-        if dvscale is not None and not self.m:
-            raise ValueError("dvscale is given but the handle has no drives")
-        for t, cnt, what in ((dZ, self.Z_len, "dZ"), (dinit, self.ns, "dinit"), (dtheta, S * self.p, "dtheta"), (dscale, S * self.m, "dscale"),
-                             (dvZ, self.Z_len, "dvZ"), (dvinit, self.ns, "dvinit"), (dvtheta, S * self.p, "dvtheta"), (dvscale, S * self.m, "dvscale"),
-                             (dfinals, S * self.ns, "dfinals"), (dfids, S, "dfids"), (dtfinals, S * self.ns, "dtfinals"), (dtfids, S, "dtfids")):
-            if t is not None and (t.numel() != cnt or t.dtype != torch.float64 or not t.is_contiguous()):
-                raise ValueError(f"{what} must be a contiguous float64 tensor of {cnt} entries")
-        if self.p and dtheta is None:
-            raise ValueError("dtheta is required: the handle has perturbations")
-        ptr = lambda t, use=True: t.data_ptr() if (t is not None and use and t.numel()) else None
-        rc = _lib.lib.qc_sweep_jvp_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dvZ), ptr(dvinit),
-                                       ptr(dvtheta), ptr(dvscale), ptr(dfinals), ptr(dfids), ptr(dtfinals), ptr(dtfids), s)
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        ptr = _dev_ptr
+        _refuse_all_none("direction", dvZ, dvinit, dvtheta, dvscale)
+        _refuse_all_none("output", dfinals, dfids, dtfinals, dtfids)
+        self._refuse_unbacked("dvtheta", dvtheta, "dvscale", dvscale)
+        self._check_device(S, dZ=dZ, dinit=dinit, dtheta=dtheta, dscale=dscale, dvZ=dvZ, dvinit=dvinit, dvtheta=dvtheta, dvscale=dvscale,
+                           dfinals=dfinals, dfids=dfids, dtfinals=dtfinals, dtfids=dtfids)
+        self._require_dtheta(dtheta)
+        _lib.check_rc(_lib.lib.qc_sweep_jvp_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dvZ),
+                                                ptr(dvinit), ptr(dvtheta), ptr(dvscale), ptr(dfinals), ptr(dfids), ptr(dtfinals), ptr(dtfids), s),
+                      _ERR, self._h)
 
     # -- Hessian products: the tangent of the pullback along one direction ------------------------------------------------------------
     @property
@@ -633,21 +607,14 @@ class RolloutSweep:
         """Does `hvp` serve this handle?  (`qc_sweep_desc_hvp_supported`: the closed scope of `vjp` -- antisymmetric generators, at most
         16 state columns, any fidelity or none -- in the "mfma16-sweep" form, or in the "mfma32-sweep" form of a handle made with
         `wide_hessian`.)  `hvp_unsupported_reason` says why not."""
-        return self._hvp_scope()[0]
+        return self._scope(_lib.lib.qc_sweep_desc_hvp_supported)[0]
 
     @property
     def hvp_unsupported_reason(self) -> Optional[str]:
         """None when `hvp` is served, else the library's reason: the pullback's first (the rollout-per-sample form with its cause,
         "... is not antisymmetric", more than 16 columns), then "Hessian products are not served in the mfma32-sweep form" for a wide
         handle made without `wide_hessian`."""
-        return self._hvp_scope()[1]
-
-    def _hvp_scope(self):
-        ok = C.c_int32()
-        rc = _lib.lib.qc_sweep_desc_hvp_supported(C.byref(self._desc), C.byref(ok))
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(None).decode())
-        return bool(ok.value), (None if ok.value else _lib.lib.qc_sweep_last_error(None).decode())
+        return self._scope(_lib.lib.qc_sweep_desc_hvp_supported)[1]
 
     def hvp(self, Z, init, cot, theta, scale=None, vZ=None, vinit=None, vtheta=None, vscale=None, vcot=None, per_sample: bool = False,
             init_grad: bool = False):
@@ -657,12 +624,7 @@ class RolloutSweep:
             init_grad    tgrad_init, S x (2N cols): the derivative of `grad_init`
         With cot = d loss/dX and vcot = (d2 loss/dX2) Xdot (Xdot: `jvp` along vZ) `tgrad` is the exact Hessian product of loss(X(Z)) with
         vZ; with vcot = None it is the curvature of the sweep map alone, what a Gauss-Newton product drops."""
-        Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
-        if Z.size != self.Z_len:
-            raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
-        init = np.ascontiguousarray(init, dtype=np.float64).ravel()
-        if init.size != self.ns:
-            raise ValueError(f"initial state has length {init.size}, expected {self.ns}")
+        Z, init = self._host_Z_init(Z, init)
         cot = np.ascontiguousarray(cot, dtype=np.float64)
         if theta is None and scale is None:
             S = cot.reshape(-1, self.ns).shape[0]
@@ -670,18 +632,15 @@ class RolloutSweep:
             S, theta, scale = self._samples(theta, scale)
         if cot.size != S * self.ns:
             raise ValueError(f"cot must be {S} x {self.ns}")
-        vec = lambda a, cnt, what: None if a is None else self._sized(np.ascontiguousarray(a, dtype=np.float64).ravel(), cnt, what)
+        vec, ptr = self._host_direction, _host_ptr
         vZ, vinit, vcot = vec(vZ, self.Z_len, "vZ"), vec(vinit, self.ns, "vinit"), vec(vcot, S * self.ns, "vcot")
         vtheta, vscale = vec(vtheta, S * self.p, "vtheta"), vec(vscale, S * self.m, "vscale")
         tg = np.empty(self.Z_len)
         tgs = np.empty((S, self.T - 1, self.n_deriv)) if per_sample else None
         tgi = np.empty((S, self.ns)) if init_grad else None
-        opt = lambda a: _lib.dptr(a) if (a is not None and a.size) else None
-        dirs = lambda a: _lib.dptr(a) if a is not None else None
-        rc = _lib.lib.qc_sweep_hvp(self._h, _lib.dptr(Z), _lib.dptr(init), S, opt(theta), opt(scale), _lib.dptr(cot), dirs(vZ), dirs(vinit),
-                                   dirs(vtheta), dirs(vscale), dirs(vcot), _lib.dptr(tg), opt(tgs), opt(tgi))
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        _lib.check_rc(_lib.lib.qc_sweep_hvp(self._h, _lib.dptr(Z), _lib.dptr(init), S, ptr(theta), ptr(scale), _lib.dptr(cot), ptr(vZ, True),
+                                            ptr(vinit, True), ptr(vtheta, True), ptr(vscale, True), ptr(vcot, True), _lib.dptr(tg), ptr(tgs), ptr(tgi)),
+                      _ERR, self._h)
         return (tg,) + ((tgs,) if per_sample else ()) + ((tgi,) if init_grad else ())
 
     def hvp_device(self, dZ, dinit, S: int, dcot, dtheta=None, dscale=None, dvZ=None, dvinit=None, dvtheta=None, dvscale=None, dvcot=None,
@@ -689,31 +648,20 @@ class RolloutSweep:
         """Device-resident Hessian product on torch CUDA tensors (float64), asynchronous on `stream`: `qc_sweep_hvp_dev`.  dcot
         S x (2N cols); directions, each optional, at least one: dvZ Z_len, dvinit 2N cols, dvtheta S x n_pert, dvscale S x m, dvcot
         S x (2N cols).  Outputs, each optional, at least one: dtgrad Z_len, dtgrad_samples S x (T-1) x n_deriv, dtgrad_init S x (2N cols)."""
-        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        s = _stream_of(stream)
         S = int(S)
+        ptr = _dev_ptr
         if dcot is None:
             raise ValueError("dcot is required")
-        if all(t is None for t in (dvZ, dvinit, dvtheta, dvscale, dvcot)):
-            raise ValueError("every direction is None")
-        if all(t is None for t in (dtgrad, dtgrad_samples, dtgrad_init)):
-            raise ValueError("every output is None")
-        if dvtheta is not None and not self.p:
-            raise ValueError("dvtheta is given but the handle has no perturbations")
-        if dvscale is not None and not self.m:
-            raise ValueError("dvscale is given but the handle has no drives")
-        for t, cnt, what in ((dZ, self.Z_len, "dZ"), (dinit, self.ns, "dinit"), (dcot, S * self.ns, "dcot"), (dtheta, S * self.p, "dtheta"),
-                             (dscale, S * self.m, "dscale"), (dvZ, self.Z_len, "dvZ"), (dvinit, self.ns, "dvinit"), (dvtheta, S * self.p, "dvtheta"),
-                             (dvscale, S * self.m, "dvscale"), (dvcot, S * self.ns, "dvcot"), (dtgrad, self.Z_len, "dtgrad"),
-                             (dtgrad_samples, S * (self.T - 1) * self.n_deriv, "dtgrad_samples"), (dtgrad_init, S * self.ns, "dtgrad_init")):
-            if t is not None and (t.numel() != cnt or t.dtype != torch.float64 or not t.is_contiguous()):
-                raise ValueError(f"{what} must be a contiguous float64 tensor of {cnt} entries")
-        if self.p and dtheta is None:
-            raise ValueError("dtheta is required: the handle has perturbations")
-        ptr = lambda t, use=True: t.data_ptr() if (t is not None and use and t.numel()) else None
-        rc = _lib.lib.qc_sweep_hvp_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dcot), ptr(dvZ),
-                                       ptr(dvinit), ptr(dvtheta), ptr(dvscale), ptr(dvcot), ptr(dtgrad), ptr(dtgrad_samples), ptr(dtgrad_init), s)
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        _refuse_all_none("direction", dvZ, dvinit, dvtheta, dvscale, dvcot)
+        _refuse_all_none("output", dtgrad, dtgrad_samples, dtgrad_init)
+        self._refuse_unbacked("dvtheta", dvtheta, "dvscale", dvscale)
+        self._check_device(S, dZ=dZ, dinit=dinit, dcot=dcot, dtheta=dtheta, dscale=dscale, dvZ=dvZ, dvinit=dvinit, dvtheta=dvtheta, dvscale=dvscale,
+                           dvcot=dvcot, dtgrad=dtgrad, dtgrad_samples=dtgrad_samples, dtgrad_init=dtgrad_init)
+        self._require_dtheta(dtheta)
+        _lib.check_rc(_lib.lib.qc_sweep_hvp_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dcot),
+                                                ptr(dvZ), ptr(dvinit), ptr(dvtheta), ptr(dvscale), ptr(dvcot), ptr(dtgrad), ptr(dtgrad_samples),
+                                                ptr(dtgrad_init), s), _ERR, self._h)
 
     # -- noise trajectories: perturbation amplitudes that change from interval to interval ---------------------------------------------
     @property
@@ -722,18 +670,11 @@ class RolloutSweep:
         one perturbation, drives and perturbations together at most 8; or the "mfma32-sweep" form of a handle made with `wide_noise`, at
         least one perturbation, no limit on drives and perturbations together.)  `noise_unsupported_reason` says why not.  `noise_grad` also
         needs `grad_supported`."""
-        return self._noise_scope()[0]
+        return self._scope(_lib.lib.qc_sweep_desc_noise_supported)[0]
 
     @property
     def noise_unsupported_reason(self) -> Optional[str]:
-        return self._noise_scope()[1]
-
-    def _noise_scope(self):
-        ok = C.c_int32()
-        rc = _lib.lib.qc_sweep_desc_noise_supported(C.byref(self._desc), C.byref(ok))
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(None).decode())
-        return bool(ok.value), (None if ok.value else _lib.lib.qc_sweep_last_error(None).decode())
+        return self._scope(_lib.lib.qc_sweep_desc_noise_supported)[1]
 
     def _noise_samples(self, noise, theta, scale):
         """(S, noise S x (T-1) x p, theta S x p, scale S x m or None): the noise gives S; theta None means zeros."""
@@ -752,15 +693,6 @@ class RolloutSweep:
             raise ValueError(f"theta / scale give {S2} samples, noise gives {S}")
         return S, np.ascontiguousarray(noise), theta, scale
 
-    def _host_Z_init(self, Z, init):
-        Z = np.ascontiguousarray(Z, dtype=np.float64).ravel()
-        if Z.size != self.Z_len:
-            raise ValueError(f"Z has length {Z.size}, expected {self.Z_len}")
-        init = np.ascontiguousarray(init, dtype=np.float64).ravel()
-        if init.size != self.ns:
-            raise ValueError(f"initial state has length {init.size}, expected {self.ns}")
-        return Z, init
-
     def noise_eval(self, Z, init, noise, theta=None, scale=None, finals: bool = True, fids: Optional[bool] = None):
         """`eval` with a noise trajectory per sample: in interval t sample s sees theta[s, j] + noise[s, t, j] on perturbation j
         (`qc_sweep_noise_eval`).  noise: S x (T-1) x n_pert (S x (T-1) when n_pert = 1); theta: S x n_pert or None = zeros.
@@ -771,10 +703,8 @@ class RolloutSweep:
             fids = self.fid_kind != _lib.QC_SWEEP_FID_NONE
         out = np.empty((S, self.ns)) if finals else None
         f = np.empty(S) if fids else None
-        opt = lambda a: _lib.dptr(a) if (a is not None and a.size) else None
-        rc = _lib.lib.qc_sweep_noise_eval(self._h, _lib.dptr(Z), _lib.dptr(init), S, opt(theta), opt(scale), opt(noise), opt(out), opt(f))
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        _lib.check_rc(_lib.lib.qc_sweep_noise_eval(self._h, _lib.dptr(Z), _lib.dptr(init), S, _host_ptr(theta), _host_ptr(scale), _host_ptr(noise),
+                                                   _host_ptr(out), _host_ptr(f)), _ERR, self._h)
         return (np.ascontiguousarray(out.T) if finals else None), f
 
     def _device_theta(self, dtheta, S, like):
@@ -790,25 +720,15 @@ class RolloutSweep:
         """Device-resident `noise_eval` on torch CUDA tensors (float64), asynchronous on `stream`: `qc_sweep_noise_eval_dev`.  dnoise
         S x (T-1) x n_pert gives S; dtheta S x n_pert or None = zeros; dscale S x m or None; dfinals S x (2N cols) or None; dfids S
         or None."""
-        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        if dnoise is None:
-            raise ValueError("dnoise is required")
-        per = (self.T - 1) * self.p
-        if not per or dnoise.numel() % per or not dnoise.numel():
-            raise ValueError(f"dnoise must hold S x {self.T - 1} x {self.p} entries")
-        S = dnoise.numel() // per
+        s = _stream_of(stream)
+        S = self._noise_S(dnoise)
+        ptr = _dev_ptr
         if dfinals is None and dfids is None:
             raise ValueError("dfinals and dfids are both None")
         dtheta = self._device_theta(dtheta, S, dnoise)
-        for t, cnt, what in ((dZ, self.Z_len, "dZ"), (dinit, self.ns, "dinit"), (dnoise, S * per, "dnoise"), (dtheta, S * self.p, "dtheta"),
-                             (dscale, S * self.m, "dscale"), (dfinals, S * self.ns, "dfinals"), (dfids, S, "dfids")):
-            if t is not None and (t.numel() != cnt or t.dtype != torch.float64 or not t.is_contiguous()):
-                raise ValueError(f"{what} must be a contiguous float64 tensor of {cnt} entries")
-        ptr = lambda t, use=True: t.data_ptr() if (t is not None and use and t.numel()) else None
-        rc = _lib.lib.qc_sweep_noise_eval_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dnoise),
-                                              ptr(dfinals), ptr(dfids), s)
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        self._check_device(S, dZ=dZ, dinit=dinit, dnoise=dnoise, dtheta=dtheta, dscale=dscale, dfinals=dfinals, dfids=dfids)
+        _lib.check_rc(_lib.lib.qc_sweep_noise_eval_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m),
+                                                       ptr(dnoise), ptr(dfinals), ptr(dfids), s), _ERR, self._h)
 
     def noise_grad(self, Z, init, noise, theta=None, scale=None, weights=None, per_sample: bool = False):
         """(J, fids, grad, grad_noise[, grad_samples]) under the noise trajectories of `noise_eval` (`qc_sweep_noise_grad`): J, fids and
@@ -816,44 +736,28 @@ class RolloutSweep:
         values -- the time-resolved noise sensitivity of every sample.  With `per_sample` also dF_s/d(a_t, dt_t) as in `grad`."""
         Z, init = self._host_Z_init(Z, init)
         S, noise, theta, scale = self._noise_samples(noise, theta, scale)
-        if weights is not None:
-            weights = np.ascontiguousarray(weights, dtype=np.float64).ravel()
-            if weights.size != S:
-                raise ValueError(f"weights must have {S} entries")
+        weights = self._host_weights(weights, S)
         f, J, g, gn = np.empty(S), C.c_double(), np.empty(self.Z_len), np.empty((S, self.T - 1, self.p))
         gs = np.empty((S, self.T - 1, self.n_deriv)) if per_sample else None
-        opt = lambda a: _lib.dptr(a) if (a is not None and a.size) else None
-        rc = _lib.lib.qc_sweep_noise_grad(self._h, _lib.dptr(Z), _lib.dptr(init), S, opt(theta), opt(scale), opt(noise), opt(weights), _lib.dptr(f),
-                                          C.byref(J), _lib.dptr(g), opt(gs), opt(gn))
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        _lib.check_rc(_lib.lib.qc_sweep_noise_grad(self._h, _lib.dptr(Z), _lib.dptr(init), S, _host_ptr(theta), _host_ptr(scale), _host_ptr(noise),
+                                                   _host_ptr(weights), _lib.dptr(f), C.byref(J), _lib.dptr(g), _host_ptr(gs), _host_ptr(gn)),
+                      _ERR, self._h)
         return (J.value, f, g, gn, gs) if per_sample else (J.value, f, g, gn)
 
     def noise_grad_device(self, dZ, dinit, dnoise, dtheta=None, dscale=None, dweights=None, dfids=None, dJ=None, dgrad=None, dgrad_samples=None,
                           dgrad_noise=None, stream=None):
         """Device-resident `noise_grad`: `qc_sweep_noise_grad_dev`.  dnoise S x (T-1) x n_pert gives S.  Outputs are optional one at
         a time: dfids S, dJ one value, dgrad Z_len, dgrad_samples S x (T-1) x n_deriv, dgrad_noise S x (T-1) x n_pert."""
-        s = stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        if dnoise is None:
-            raise ValueError("dnoise is required")
-        per = (self.T - 1) * self.p
-        if not per or dnoise.numel() % per or not dnoise.numel():
-            raise ValueError(f"dnoise must hold S x {self.T - 1} x {self.p} entries")
-        S = dnoise.numel() // per
-        if all(t is None for t in (dfids, dJ, dgrad, dgrad_samples, dgrad_noise)):
-            raise ValueError("every output is None")
+        s = _stream_of(stream)
+        S = self._noise_S(dnoise)
+        ptr = _dev_ptr
+        _refuse_all_none("output", dfids, dJ, dgrad, dgrad_samples, dgrad_noise)
         dtheta = self._device_theta(dtheta, S, dnoise)
-        for t, cnt, what in ((dZ, self.Z_len, "dZ"), (dinit, self.ns, "dinit"), (dnoise, S * per, "dnoise"), (dtheta, S * self.p, "dtheta"),
-                             (dscale, S * self.m, "dscale"), (dweights, S, "dweights"), (dfids, S, "dfids"), (dJ, 1, "dJ"),
-                             (dgrad, self.Z_len, "dgrad"), (dgrad_samples, S * (self.T - 1) * self.n_deriv, "dgrad_samples"),
-                             (dgrad_noise, S * per, "dgrad_noise")):
-            if t is not None and (t.numel() != cnt or t.dtype != torch.float64 or not t.is_contiguous()):
-                raise ValueError(f"{what} must be a contiguous float64 tensor of {cnt} entries")
-        ptr = lambda t, use=True: t.data_ptr() if (t is not None and use and t.numel()) else None
-        rc = _lib.lib.qc_sweep_noise_grad_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m), ptr(dnoise),
-                                              ptr(dweights), ptr(dfids), ptr(dJ), ptr(dgrad), ptr(dgrad_samples), ptr(dgrad_noise), s)
-        if rc != _lib.QC_OK:
-            raise _lib.QCollocError(rc, _lib.lib.qc_sweep_last_error(self._h).decode())
+        self._check_device(S, dZ=dZ, dinit=dinit, dnoise=dnoise, dtheta=dtheta, dscale=dscale, dweights=dweights, dfids=dfids, dJ=dJ, dgrad=dgrad,
+                           dgrad_samples=dgrad_samples, dgrad_noise=dgrad_noise)
+        _lib.check_rc(_lib.lib.qc_sweep_noise_grad_dev(self._h, dZ.data_ptr(), dinit.data_ptr(), S, ptr(dtheta, self.p), ptr(dscale, self.m),
+                                                       ptr(dnoise), ptr(dweights), ptr(dfids), ptr(dJ), ptr(dgrad), ptr(dgrad_samples),
+                                                       ptr(dgrad_noise), s), _ERR, self._h)
 
     def finals_autograd(self, dZ, dinit, dtheta=None, dscale=None):
         """The S x (2N cols) final states as a differentiable torch tensor: forward is `eval_device` on the current stream, backward one
@@ -933,13 +837,9 @@ class _SweepFinals(torch.autograd.Function):
         return None, None, gZ, (gI.sum(0).reshape(ctx.init_shape) if need_init else None), gT, gC
 
 
-def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None, cols: Optional[int] = None, goal=None, fid_kind=None,
-                  subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS, wide: bool = False, stored_states: bool = False,
-                  wide_stored: bool = False, wide_tangent: bool = False, wide64: bool = False):
-    """(finals, fids) of S rollouts under the perturbed systems: finals is (2N cols) x S, fids S values (None without `fid_kind`).
-    theta is S x len(perturbations) (S x 0 without perturbations), scale S x n_drives or None (all ones); `wide`, `stored_states`,
-    `wide_stored` and `wide_tangent` as `RolloutSweep` (the forward sweep itself looks at none of the last three); `wide64` (only with
-    `wide`) as `RolloutSweep`: 32 < 2N <= 64 with up to 16 drives on the matrix cores ("mfma64-sweep")."""
+def _one_shot(entry, init, controls, dts, system, perturbations, args, cols, **handle):
+    """`entry(sw, Z, init, *args)` on a handle made for this call: T and (by default) cols from the arguments, the trajectory vector
+    packed from controls and timesteps, `handle` as `RolloutSweep` takes it."""
     controls = np.asarray(controls, dtype=np.float64)
     if controls.ndim != 2 or controls.shape[0] != system.n_drives:
         raise ValueError("controls must be n_drives x T")
@@ -948,12 +848,23 @@ def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None,
     n = 2 * system.state_levels
     if cols is None:
         cols = init.size // n
-    sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device, wide=wide,
-                      stored_states=stored_states, wide_stored=wide_stored, wide_tangent=wide_tangent, wide64=wide64)
+    sw = RolloutSweep(system, perturbations, T, cols=cols, **handle)
     try:
-        return sw.eval(sw.pack(controls, dts), init, theta, scale)
+        return entry(sw, sw.pack(controls, dts), init, *args)
     finally:
         sw.close()
+
+
+def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None, cols: Optional[int] = None, goal=None, fid_kind=None,
+                  subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS, wide: bool = False, stored_states: bool = False,
+                  wide_stored: bool = False, wide_tangent: bool = False, wide64: bool = False):
+    """(finals, fids) of S rollouts under the perturbed systems: finals is (2N cols) x S, fids S values (None without `fid_kind`).
+    theta is S x len(perturbations) (S x 0 without perturbations), scale S x n_drives or None (all ones); `wide`, `stored_states`,
+    `wide_stored` and `wide_tangent` as `RolloutSweep` (the forward sweep itself looks at none of the last three); `wide64` (only with
+    `wide`) as `RolloutSweep`: 32 < 2N <= 64 with up to 16 drives on the matrix cores ("mfma64-sweep")."""
+    return _one_shot(RolloutSweep.eval, init, controls, dts, system, perturbations, (theta, scale), cols, goal=goal, fid_kind=fid_kind,
+                     subspace=subspace, fid_form=fid_form, device=device, wide=wide, stored_states=stored_states, wide_stored=wide_stored,
+                     wide_tangent=wide_tangent, wide64=wide64)
 
 
 def rollout_noise_sweep(init, controls, dts, system, perturbations, noise, theta=None, scale=None, cols: Optional[int] = None, goal=None,
@@ -962,20 +873,8 @@ def rollout_noise_sweep(init, controls, dts, system, perturbations, noise, theta
     theta[s, j] + noise[s, t, j] on perturbation j.  noise is S x (T-1) x len(perturbations) (S x (T-1) for one perturbation), theta
     S x len(perturbations) or None (zeros); everything else as `rollout_sweep`.  `wide=True` serves 16 < 2N <= 32 on the matrix cores
     (the handle is made with `wide` and `wide_noise`)."""
-    controls = np.asarray(controls, dtype=np.float64)
-    if controls.ndim != 2 or controls.shape[0] != system.n_drives:
-        raise ValueError("controls must be n_drives x T")
-    T = controls.shape[1]
-    init = np.ascontiguousarray(init, dtype=np.float64).ravel()
-    n = 2 * system.state_levels
-    if cols is None:
-        cols = init.size // n
-    sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device,
-                      wide=wide, wide_noise=wide)
-    try:
-        return sw.noise_eval(sw.pack(controls, dts), init, noise, theta, scale)
-    finally:
-        sw.close()
+    return _one_shot(RolloutSweep.noise_eval, init, controls, dts, system, perturbations, (noise, theta, scale), cols, goal=goal, fid_kind=fid_kind,
+                     subspace=subspace, fid_form=fid_form, device=device, wide=wide, wide_noise=wide)
 
 
 def rollout_sweep_parameter_gradient(init, controls, dts, system, perturbations, theta, scale=None, cols: Optional[int] = None, goal=None,
@@ -985,20 +884,9 @@ def rollout_sweep_parameter_gradient(init, controls, dts, system, perturbations,
     with respect to theta (S x len(perturbations)) and scale (S x n_drives; None: taken at all ones).  Arguments as `rollout_sweep`;
     `stored_states=True` serves open systems (`RolloutSweep`); `wide=True` serves 16 < 2N <= 32 on the matrix cores (the handle is made
     with `wide` and `wide_params`); all three of `wide`, `stored_states` and `wide_stored` serve open systems there (wide = 11)."""
-    controls = np.asarray(controls, dtype=np.float64)
-    if controls.ndim != 2 or controls.shape[0] != system.n_drives:
-        raise ValueError("controls must be n_drives x T")
-    T = controls.shape[1]
-    init = np.ascontiguousarray(init, dtype=np.float64).ravel()
-    n = 2 * system.state_levels
-    if cols is None:
-        cols = init.size // n
-    sw = RolloutSweep(system, perturbations, T, cols=cols, goal=goal, fid_kind=fid_kind, subspace=subspace, fid_form=fid_form, device=device,
-                      stored_states=stored_states, wide=wide, wide_params=wide, wide_stored=wide_stored)
-    try:
-        return sw.param_grad(sw.pack(controls, dts), init, theta, scale)
-    finally:
-        sw.close()
+    return _one_shot(RolloutSweep.param_grad, init, controls, dts, system, perturbations, (theta, scale), cols, goal=goal, fid_kind=fid_kind,
+                     subspace=subspace, fid_form=fid_form, device=device, stored_states=stored_states, wide=wide, wide_params=wide,
+                     wide_stored=wide_stored)
 
 
 def _traj_dts(traj):
