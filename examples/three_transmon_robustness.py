@@ -9,7 +9,8 @@
 in the frame rotating with the drives (energies in rad / ns).  The detuning landscape F(zeta) is ONE sweep over every detuning,
 `RolloutSweep(..., wide=True, wide64=True)`: kernel "mfma64-sweep", one workgroup per (sample, chunk of intervals) with the 64 x 64
 matrices in LDS.  Without `wide64` a system of this size runs one rollout per sample (the same call without the keyword: pass 0 as the
-third argument to see it).  That form serves the forward sweep; gradients at this size are not served by the sweeps.
+third argument to see it).  A handle made this way serves the forward sweep; with `wide64_grad=True` as well it serves gradients and
+pullbacks, which three_transmon_polish.py uses to polish this pulse.
 
     python examples/three_transmon_robustness.py [T] [landscape] [wide64]
 """

@@ -651,11 +651,19 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * chunk rule with that item's fill constant (n_chunks = 1 once S >= 256, one workgroup per compute unit; else ceil(256 / S) chunks, at
  * most ceil(sqrt(T-1))).  The mathematics is the family's.  That form serves the FORWARD sweep only, qc_sweep_eval*: final states
  * and fidelities.  qc_sweep_grad*, qc_sweep_grad_params*, qc_sweep_vjp*, qc_sweep_jvp*, qc_sweep_hvp* and qc_sweep_noise_* return
- * QC_ERR_UNSUPPORTED on such a handle, whatever the other bits say, and the qc_sweep_desc_*_supported queries answer 0 with a reason
+ * QC_ERR_UNSUPPORTED on such a handle, whatever bits 1 .. 8 say (bit 11, below, adds gradients and pullbacks), and the qc_sweep_desc_*_supported queries answer 0 with a reason
  * that names the form and the size ("... the mfma64-sweep form (2N = 54) ...").  Descriptors with 2N <= 32 ignore the bit completely:
  * form, launch, kernel name, every *_supported answer and every output bit are those of the same descriptor without it.  Without the
  * bit nothing changes anywhere.  Not in that form: more than 16 drives (rollout-per-sample), a state-action form that skips the
  * propagator for kets, 2N > 64 (QC_ERR_UNSUPPORTED as before).
+ * Bit 11, QC_SWEEP_WIDE_64_GRAD (any valid value that has bits 0 and 10, | 2048; without both of them QC_ERR_INVALID), changes one thing
+ * only: an "mfma64-sweep" handle then also serves qc_sweep_grad* (fids, J, grad, grad_samples) and qc_sweep_vjp* (finals, grad,
+ * grad_samples, grad_init) of CLOSED systems -- antisymmetric generators, the same 64-eps test -- with states of up to 32 columns, by the
+ * closed adjoint walk on 4 x 4 tiles (qc_sweep64_grad.hip; one workgroup per (sample, chunk), the forward form's chunk rule).  The
+ * fidelities and final states carry the bits of qc_sweep_eval on the same handle.  Still QC_ERR_UNSUPPORTED there, with a reason that
+ * names the form and 2N: parameter gradients and parameter cotangents, reserved1[0] = QC_SWEEP_STORED_STATES, qc_sweep_jvp*,
+ * qc_sweep_hvp* and qc_sweep_noise_*.  Form, launch, kernel name and every output bit of qc_sweep_eval* are those of the same descriptor
+ * without the bit; descriptors with 2N <= 32 ignore it completely, as they ignore bit 10.
  * reserved1[0] = QC_SWEEP_STORED_STATES chooses reverse mode by the STORED-STATE walk: qc_sweep_grad*, qc_sweep_grad_params* and
  * qc_sweep_vjp* then keep the forward states x_0 .. x_{T-2} of every sample in handle scratch (S x (T-1) x 2N x cols doubles) and read
  * them on the way back instead of reversing the step, which serves ANY generators in the "mfma16-sweep" form: Lindblad generators
@@ -692,6 +700,7 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
 #define QC_SWEEP_WIDE_TANGENT 16 /* qc_sweep_desc.wide, bit 4: the mfma32-sweep form serves pushforwards (qc_sweep_jvp*); only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_WIDE_NOISE 64   /* qc_sweep_desc.wide, bit 6: the mfma32-sweep form serves noise-trajectory sweeps and their gradients (qc_sweep_noise_*); only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_WIDE_HESSIAN 256 /* qc_sweep_desc.wide, bit 8: the mfma32-sweep form serves Hessian products of closed systems (qc_sweep_hvp*); only together with QC_SWEEP_WIDE */
+#define QC_SWEEP_WIDE_64_GRAD 2048 /* qc_sweep_desc.wide, bit 11: the mfma64-sweep form serves sweep gradients and pullbacks of closed systems (qc_sweep_grad*, qc_sweep_vjp*; qc_sweep64_grad.hip); ignored at 2N <= 32; only together with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 */
 #define QC_SWEEP_WIDE_64 1024    /* qc_sweep_desc.wide, bit 10: 32 < 2N <= 64 with up to 16 drives takes the matrix cores ("mfma64-sweep", qc_sweep_eval* only); ignored at 2N <= 32; only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_STORED_STATES 1 /* qc_sweep_desc.reserved1[0]: reverse mode by the stored-state walk */
 typedef struct qc_sweep_desc {

@@ -265,9 +265,10 @@ int qc_sweep_validate_desc(const qc_sweep_desc* d) {
     // (QC_SWEEP_WIDE_HESSIAN) only together with bit 0; bits 2, 5 and 7 are not assigned: 0, 1, 3, 9, 11, 17, 19, 25, 27, each of the
     // eight odd values | 64, and each of those sixteen odd values | 256; bit 10 (QC_SWEEP_WIDE_64) likewise only together with bit 0:
     // each of those thirty-two odd values | 1024; bit 9 is not assigned
-    if ((d->wide & ~(QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS | QC_SWEEP_WIDE_STORED | QC_SWEEP_WIDE_TANGENT | QC_SWEEP_WIDE_NOISE | QC_SWEEP_WIDE_HESSIAN | QC_SWEEP_WIDE_64)) != 0 ||
-        (d->wide != 0 && !(d->wide & QC_SWEEP_WIDE)))
-        return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: wide must be 0 or QC_SWEEP_WIDE (1), alone or with QC_SWEEP_WIDE_PARAMS (2), QC_SWEEP_WIDE_STORED (8), QC_SWEEP_WIDE_TANGENT (16), QC_SWEEP_WIDE_NOISE (64) and / or QC_SWEEP_WIDE_HESSIAN (256): 0, 1, 3, 9, 11, 17, 19, 25 or 27, or one of those eight | 64, or one of the sixteen odd values | 256; or one of the thirty-two odd values | QC_SWEEP_WIDE_64 (1024)");
+    // bit 11 (QC_SWEEP_WIDE_64_GRAD) only together with bits 0 and 10: each of those thirty-two values | 1024 | 2048
+    if ((d->wide & ~(QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS | QC_SWEEP_WIDE_STORED | QC_SWEEP_WIDE_TANGENT | QC_SWEEP_WIDE_NOISE | QC_SWEEP_WIDE_HESSIAN | QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD)) != 0 ||
+        (d->wide != 0 && !(d->wide & QC_SWEEP_WIDE)) || ((d->wide & QC_SWEEP_WIDE_64_GRAD) && !(d->wide & QC_SWEEP_WIDE_64)))
+        return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: wide must be 0 or QC_SWEEP_WIDE (1), alone or with QC_SWEEP_WIDE_PARAMS (2), QC_SWEEP_WIDE_STORED (8), QC_SWEEP_WIDE_TANGENT (16), QC_SWEEP_WIDE_NOISE (64) and / or QC_SWEEP_WIDE_HESSIAN (256): 0, 1, 3, 9, 11, 17, 19, 25 or 27, or one of those eight | 64, or one of the sixteen odd values | 256; or one of the thirty-two odd values | QC_SWEEP_WIDE_64 (1024); or one of those | QC_SWEEP_WIDE_64_GRAD (2048)");
     if (d->reserved1[0] != 0 && d->reserved1[0] != QC_SWEEP_STORED_STATES)
         return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: reserved1[0] must be 0 or QC_SWEEP_STORED_STATES (1)");
     return QC_OK;
@@ -292,6 +293,11 @@ std::string qc_sweep_per_sample_why(const qc_sweep_desc* d) {
 
 std::string qc_sweep_form64_why(const qc_sweep_desc* d) {
     return "the handle takes the mfma64-sweep form (2N = " + std::to_string(2 * d->N) + "), which serves the forward sweep only";
+}
+
+std::string qc_sweep_form64_unserved(const qc_sweep_desc* d, const char* what) {
+    if (!(d->wide & QC_SWEEP_WIDE_64_GRAD)) return qc_sweep_form64_why(d);
+    return "the handle takes the mfma64-sweep form (2N = " + std::to_string(2 * d->N) + "), which does not serve " + what;
 }
 
 int qc_sweep_check(qc_sweep* h, const char* who, const bool qc_sweep::*ok, const char* scope, const std::string qc_sweep::*why, const void* Z,
@@ -362,6 +368,7 @@ extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
     h->mfma = qc_sweep_desc_is_mfma(d);
     h->mfma32 = qc_sweep_desc_form(d) == QC_SWEEP_FORM_32;
     h->mfma64 = qc_sweep_desc_form(d) == QC_SWEEP_FORM_64;
+    h->wide64_grad = h->mfma64 && (d->wide & QC_SWEEP_WIDE_64_GRAD);
     h->wide_par = h->mfma32 && (d->wide & QC_SWEEP_WIDE_PARAMS);
     h->wide_stored = h->mfma32 && (d->wide & QC_SWEEP_WIDE_STORED);
     h->wide_tangent = h->mfma32 && (d->wide & QC_SWEEP_WIDE_TANGENT);

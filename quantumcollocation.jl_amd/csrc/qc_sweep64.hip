@@ -18,8 +18,9 @@
 // The chunk total leaves as a full 64 x 64 column-major matrix (S x n_chunks x 4096 doubles of handle scratch);
 // qc_sweep_finish_kernel (qc_sweep.hip) chains the totals with ld = 64.
 //
-// Out of scope in this form: gradients, pullbacks, pushforwards, Hessian products and noise sweeps (their entry points answer
-// QC_ERR_UNSUPPORTED on such a handle), a state-action form that skips the propagator for kets, more than 16 drives, 2N > 64.
+// Gradients and pullbacks of closed systems in this form: qc_sweep64_grad.hip, on handles that also set QC_SWEEP_WIDE_64_GRAD (without it
+// their entry points answer QC_ERR_UNSUPPORTED, as they did).  Out of scope in this form: parameter gradients, pushforwards, Hessian
+// products and noise sweeps (their entry points answer QC_ERR_UNSUPPORTED on such a handle), a state-action form that skips the propagator for kets, more than 16 drives, 2N > 64.
 #include <math.h>
 
 #include <string>

@@ -1,5 +1,5 @@
-// What the kernels of the "mfma64-sweep" form share (qc_sweep64.hip today; a backward walk must form the same generator and choose
-// the same number of squarings as the forward step): the workgroup's shape and its LDS matrices, the element a thread owns, the
+// What the kernels of the "mfma64-sweep" form share (qc_sweep64.hip, the forward sweep, and qc_sweep64_grad.hip, its backward walk, which
+// must form the same generator and choose the same number of squarings as the forward step): the workgroup's shape and its LDS matrices, the element a thread owns, the
 // sample's base matrix, the interval's generator, the squaring rule over the workgroup and the tile product out of LDS.  Constants,
 // table, wave sum, rule's tail and chunk range are those of qc_sweep_common.h.  The counterpart of qc_sweep32_common.h.
 //
@@ -88,6 +88,32 @@ __device__ __forceinline__ void tile_mul(const double* __restrict__ A, const dou
     v4d acc = I == J ? c * identity_B(g, j) : zero;
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[q * 4 * kLd], pb[4 * q], acc, 0, 0, 0);
+    double* __restrict__ pd = D + (16 * J + j) * kLd + 16 * I + g;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pd[4 * r] = acc[r];
+}
+
+// ---- the pieces of the backward walk (qc_sweep64_grad.hip): fragments of either operand, as it stands or transposed ----------------------
+// The thin matrices (a state, an adjoint: 64 x <= 32) keep the column stride kLd, so one pair of address forms serves every operand:
+//   row_frag(M, T): lane (g, i), step q reads M[16 T + i][4 q + g]  (stride kRowStep)  -- the A operand of M X, the B operand of X M^T
+//   col_frag(M, T): lane (g, j), step q reads M[4 q + g][16 T + j]  (stride kColStep)  -- the B operand of X M, the A operand of M^T X
+// (both conflict-free by the stride of 66: tile_mul's two reads).
+constexpr int kThin = 32 * kLd;           // one thin LDS matrix: 64 rows x 32 columns
+constexpr int kRowStep = 4 * kLd, kColStep = 4;
+
+__device__ __forceinline__ const double* row_frag(const double* M, int T, int g, int j) { return M + g * kLd + 16 * T + j; }
+__device__ __forceinline__ const double* col_frag(const double* M, int T, int g, int j) { return M + (16 * T + j) * kLd + g; }
+
+// acc += sum over NQ steps of a-fragment x b-fragment, ascending k (NQ = 16: a whole 64-long contraction, tile_mul's chain)
+template <int SA, int SB, int NQ>
+__device__ __forceinline__ v4d chain(const double* __restrict__ pa, const double* __restrict__ pb, v4d acc) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[q * SA], pb[q * SB], acc, 0, 0, 0);
+    return acc;
+}
+
+// a tile held in registers (D layout) into tile (I, J) of the LDS matrix D
+__device__ __forceinline__ void store_tile(double* __restrict__ D, int I, int J, int g, int j, const v4d& acc) {
     double* __restrict__ pd = D + (16 * J + j) * kLd + 16 * I + g;
 #pragma unroll
     for (int r = 0; r < 4; ++r) pd[4 * r] = acc[r];

@@ -1,0 +1,211 @@
+// Sweep gradients and pullbacks for "mfma64-sweep" handles (32 < 2N <= 64, descriptors with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 |
+// QC_SWEEP_WIDE_64_GRAD): the closed adjoint walk of qc_sweep_grad.hip with every matrix 4 x 4 tiles of 16 x 16 in LDS.  The mathematics is
+// that file's, line for line (read its header first, then qc_sweep32_grad.hip): antisymmetric generators make E orthogonal, so
+//     x_t = E^T x_{t+1},  lambda_t = E^T lambda_{t+1}                  (no state stored inside a chunk),
+//     one Frechet chain per interval in direction dY = (h / 2^sq) x_{t+1} lambda_{t+1}^T, run beside the Horner chain,
+//     sq squarings dE <- E dE + dE E, E <- E E,      ZT = E^T dE,
+//     dF/da_k = c_k sum ZT . G_k   (sum_ab ZT[a][b] G_k[b][a]),      dF/dh = -sum KT . G   (KT = lambda x^T).
+// Degree, threshold, the 1/k! table, generator(), squarings() and chunk_range are the forward kernel's (qc_sweep64_common.h,
+// qc_sweep_common.h): the walk chooses the forward step's sq from the same norm, and its R chain is tile_mul's chain, MFMA for MFMA.
+//
+// Work item: one WORKGROUP of 1024 threads per (sample, chunk), as in qc_sweep64.hip; wave w owns tile (I, J) = (w & 3, w >> 2) of every
+// 64 x 64 product.  The chunk rule is the forward form's (kSweepFill64), unchanged.  States of up to 32 columns: x, lambda and u are
+// 64 x 32 (4 x 2 tiles; the columns past nc are zero), wave w owns tile (w & 3, (w >> 2) & 1) of x (w < 8) or of lambda (w >= 8).
+//
+// LDS map (doubles; column stride 66 everywhere), 152 064 B dynamic + 2 304 B static of the CU's 160 KiB, one workgroup per CU:
+//     Y | R | dR | x | lambda | u         64 x 64 | 64 x 64 | 64 x 64 | 64 x 32 | 64 x 32 | 64 x 32
+// Six full matrices (Y, dY, two R and two dR buffers) would not fit.  Two things make the walk fit:
+//   (a) dY has rank <= nc: dY R = (h / 2^sq) x (lambda^T R).  dY is never formed; the term is two thin products through
+//       u = (h / 2^sq) R^T lambda (64 x nc): 4 nct tile chains of 16 for u and nct x 4 MFMAs a tile for x u^T (nct = 1 or 2 column tiles);
+//   (b) a wave's tile of a product is 4 registers a lane, so R and dR are updated IN PLACE: every wave holds its tiles of the new R, dR in
+//       registers across a barrier (all reads of the old ones are done), writes them over the old ones, and a second barrier publishes them.
+// Barriers of one interval, in order, and what each stands between:
+//     S   inside squarings(): behind it every wave has left the previous interval -- its ZT and E^T x products (the last reads of R, dR)
+//         are in front of Ba already; S stands between the writes of x, lambda (after Ba) and their reads by the timestep derivative,
+//         and between red[]'s writes and reads.  Y, R = I/8!, dR = 0 are written behind S.
+//     H0  publishes Y, R, dR.
+//     per Horner step k = 8 .. 1:   u = hs R^T lambda (waves 0 .. 4 nct - 1; reads R, lambda; writes u)
+//     U   publishes u;              R' = Y R + I/(k-1)!,  dR' = Y dR + x u^T   into registers (reads Y, R, dR, x, u)
+//     P   every read of R, dR, u of this step is done;   R <- R', dR <- dR'
+//     W   publishes R, dR (the next step's u reads R; u is overwritten only behind W)
+//     per squaring:   E' = E E, dE' = E dE + dE E into registers;  P;  write;  W      (the same two barriers)
+//     tail:  ZT = E^T dE (registers), x' / lambda' = E^T x / E^T lambda (registers), the m contractions of ZT with the drive images
+//            (global memory, L2-resident), wave sums, part[w][.]
+//     Ba  every read of E, dE, x, lambda is done and part[] is complete;   x, lambda <- x', lambda';  wave 0 adds the 16 partials of each of
+//         the m + 1 values in ascending wave order and stores them with one vector store into gs[s][t][.]
+// red[] keeps the rule of qc_sweep64.hip (at least one barrier between a call of squarings() and the next: there are 25 or more); part[]
+// is written in the tail and read behind Ba, and its next writes are a whole interval of barriers later.
+// E^T X needs no transposition: the A operand of E^T is the column fragment of E (qc_sweep64_common.h: col_frag), conflict-free by the stride.
+//
+// MFMAs per interval and workgroup, nct = ceil(nc / 16):  8 Horner steps x (16 x (32 + 4 nct) + 4 nct x 16) + sq x 16 x 48 + 16 x 16 (ZT)
+// + 8 nct x 16 (x, lambda) = (4352 + 1152 nct) + 768 sq, against the forward kernel's (9 + sq) x 256 = 2304 + 256 sq.
+// No atomics, sums in a fixed order: repeated calls give the same bits.  Parameter gradients, the stored-state walk, pushforwards, Hessian
+// products and noise sweeps are not served in this form.
+#include <math.h>
+
+#include <string>
+
+#include "qc_mfma_common.h"
+#include "qc_side.h"
+#include "qc_sweep64_common.h"
+#include "qc_sweep_internal.h"
+
+namespace {
+
+using namespace qc_sweep64;
+
+constexpr int kPartLd = 17;      // m + 1 <= 17 values a wave
+constexpr size_t kGradLdsBytes = (size_t)(3 * kMat + 3 * kThin) * sizeof(double);      // 152 064 B
+
+__global__ __launch_bounds__(kThreads, 1) void qc_sweep64_grad_kernel(const SweepParams P, const double* __restrict__ Z, const double* __restrict__ theta,
+                                                                        const double* __restrict__ scale, const double* __restrict__ xs,
+                                                                        const double* __restrict__ ls, double* __restrict__ gs) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    __shared__ double red[16];
+    __shared__ double part[16 * kPartLd];
+    const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, j = lane & 15;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6), I = w & 3, J = w >> 2;
+    const int Jc = J & 1;                   // the wave's column tile of a thin matrix
+    const bool second = J >= 2;             // waves 8 .. 15: lambda's tiles; waves 0 .. 7: x's and u's
+    const long long item = blockIdx.x;
+    const ChunkRange ch = chunk_range(item, P.n_chunks, P.chunk, P.n_int);
+    const int t0 = ch.t0, t1 = ch.t1, m = P.m, nc = P.nc;
+    const int nct = nc > 16 ? 2 : 1;
+    const long long s = ch.s;
+    const bool ft = P.off_dt >= 0;
+    const v4d IdB = identity_B(g, j);
+    const v4d zero = {0.0, 0.0, 0.0, 0.0};
+    double* const Yb = sm;
+    double* const Rb = sm + kMat;
+    double* const dRb = sm + 2 * kMat;
+    double* const Xb = sm + 3 * kMat;
+    double* const Lb = Xb + kThin;
+    double* const Ub = Lb + kThin;
+    double* const mine = second ? Lb : Xb;      // the thin matrix whose tile (I, Jc) this wave carries through E^T
+
+    // ---- once per item: the sample's base matrix, the state and the adjoint at the chunk's end (zero outside n x nc) -----------------
+    double base[4];
+    base_elems(P.img, m, P.p, theta, s, tid, base);
+    const int kl = lane < m ? lane : (m > 0 ? m - 1 : 0);
+    const double cl = (scale && m > 0) ? scale[s * m + kl] : 1.0;
+    {
+        const int ns = P.n * nc;
+        const double* __restrict__ xe = xs + item * ns;
+        const double* __restrict__ le = ls + item * ns;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int idx = tid + 1024 * e, row = idx & 63, col = idx >> 6;
+            const bool in = row < P.n && col < nc;
+            Xb[col * kLd + row] = in ? xe[row + P.n * col] : 0.0;
+            Lb[col * kLd + row] = in ? le[row + P.n * col] : 0.0;
+        }
+    }
+
+    const gptr G0 = (gptr)(unsigned long long)P.img;
+    const double* __restrict__ z = Z + (long long)(t1 - 1) * P.zdim;
+    double av = m > 0 ? z[P.off_a + kl] : 0.0;
+    const double hfix = opaque_scalar(P.dt_fixed);
+    double h = ft ? z[P.off_dt] : hfix;
+#pragma unroll 1
+    for (int t = t1 - 1; t >= t0; --t) {
+        // the previous interval's controls and timestep are requested before this interval's products
+        const double* __restrict__ zn = Z + (long long)(t > t0 ? t - 1 : t) * P.zdim;
+        const double av_n = m > 0 ? zn[P.off_a + kl] : 0.0;
+        const double h_n = ft ? zn[P.off_dt] : hfix;
+        double G[4];
+        generator(P.img, m, av * cl, base, tid, G);
+        const int sq = squarings(red, G, h, lane, w);      // barrier S; the rule of the forward kernel: one function
+        const double hs = h * ldexp(1.0, -sq);
+        // lane k < m: drive k's wave sum; lane m: the timestep's (sum KT . G, its sign at the store)
+        double out = 0.0;
+        if (ft) {
+            // sum_ab KT[a][b] G[b][a] over the thread's elements G[b = lane][a = w + 16 e], KT[a][b] = sum_c lambda[a][c] x[b][c]
+            double kt[4] = {0.0, 0.0, 0.0, 0.0};
+            for (int c = 0; c < nc; ++c) {
+                const double xv = Xb[c * kLd + lane];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) kt[e] = fma(Lb[c * kLd + w + 16 * e], xv, kt[e]);
+            }
+            double ph = 0.0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) ph = fma(kt[e], G[e], ph);
+            const double dh = wave_sum(ph);
+            out = lane == m ? dh : out;
+        }
+        // Horner: R_deg+1 = I/deg!, dR_deg+1 = 0;  R_k = Y R_k+1 + I/(k-1)!,  dR_k = dY R_k+1 + Y dR_k+1
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            Yb[lds_at(tid, e)] = hs * G[e];
+            Rb[lds_at(tid, e)] = on_diagonal(tid, e) ? kInvFact[kDeg] : 0.0;
+            dRb[lds_at(tid, e)] = 0.0;
+        }
+        __syncthreads();      // H0
+#pragma unroll 1
+        for (int k = kDeg; k >= 1; --k) {
+            if (!second && Jc < nct) {
+                const v4d u = chain<kColStep, kColStep, 16>(col_frag(Rb, I, g, j), col_frag(Lb, Jc, g, j), zero);
+                store_tile(Ub, I, Jc, g, j, hs * u);
+            }
+            __syncthreads();      // U
+            const v4d c0 = I == J ? kInvFact[k - 1] * IdB : zero;
+            const v4d nR = chain<kRowStep, kColStep, 16>(row_frag(Yb, I, g, j), col_frag(Rb, J, g, j), c0);
+            v4d nD = chain<kRowStep, kColStep, 16>(row_frag(Yb, I, g, j), col_frag(dRb, J, g, j), zero);
+            nD = chain<kRowStep, kRowStep, 4>(row_frag(Xb, I, g, j), row_frag(Ub, J, g, j), nD);
+            if (nct > 1) nD = chain<kRowStep, kRowStep, 4>(row_frag(Xb, I, g, j) + 16 * kLd, row_frag(Ub, J, g, j) + 16 * kLd, nD);
+            __syncthreads();      // P
+            store_tile(Rb, I, J, g, j, nR);
+            store_tile(dRb, I, J, g, j, nD);
+            __syncthreads();      // W
+        }
+#pragma unroll 1
+        for (int q = 0; q < sq; ++q) {
+            const v4d nE = chain<kRowStep, kColStep, 16>(row_frag(Rb, I, g, j), col_frag(Rb, J, g, j), zero);
+            v4d nD = chain<kRowStep, kColStep, 16>(row_frag(Rb, I, g, j), col_frag(dRb, J, g, j), zero);
+            nD = chain<kRowStep, kColStep, 16>(row_frag(dRb, I, g, j), col_frag(Rb, J, g, j), nD);
+            __syncthreads();      // P
+            store_tile(Rb, I, J, g, j, nE);
+            store_tile(dRb, I, J, g, j, nD);
+            __syncthreads();      // W
+        }
+        // ZT = E^T dE, the wave's tile of x or lambda through E^T, and the drive derivatives
+        const v4d ZT = chain<kColStep, kColStep, 16>(col_frag(Rb, I, g, j), col_frag(dRb, J, g, j), zero);
+        v4d nx = zero;
+        if (Jc < nct) nx = chain<kColStep, kColStep, 16>(col_frag(Rb, I, g, j), col_frag(mine, Jc, g, j), zero);
+        // the lane's elements ZT[a = 16 I + 4 r + g][b = 16 J + j] against G_u[b][a] (column-major images: a * 64 + b)
+        const gptr Ge = G0 + (16 * I + g) * 64 + 16 * J + j;
+#pragma unroll 1
+        for (int u = 0; u < m; ++u) {
+            const gptr Gu = Ge + (size_t)(1 + u) * kImg;
+            double pu = 0.0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) pu = fma(ZT[r], Gu[256 * r], pu);
+            const double du = wave_sum(pu);
+            out = lane == u ? du : out;
+        }
+        if (lane < P.nd) part[w * kPartLd + lane] = out;
+        __syncthreads();      // Ba
+        if (Jc < nct) store_tile(mine, I, Jc, g, j, nx);
+        if (w == 0 && lane < P.nd) {
+            double acc = part[lane];
+#pragma unroll
+            for (int i = 1; i < 16; ++i) acc += part[i * kPartLd + lane];
+            gs[(s * P.n_int + t) * P.nd + lane] = lane < m ? acc * cl : -acc;
+        }
+        av = av_n;
+        h = h_n;
+    }
+}
+
+}  // namespace
+
+int qc_sweep64_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,
+                           double* gs, hipStream_t st) {
+    const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
+    // per launch, as qc_sweep64_launch_totals: the attribute belongs to the (function, device) pair
+    QC_SIDE_HIP(h, *qc_sweep_err_slot(), hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep64_grad_kernel),
+                                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradLdsBytes));
+    hipLaunchKernelGGL(qc_sweep64_grad_kernel, dim3((unsigned)P.items), dim3(kThreads), kGradLdsBytes, st, P, dZ, dtheta, dscale,
+                       (const double*)h->dXs.p, (const double*)h->dLs.p, gs);
+    QC_SIDE_HIP(h, *qc_sweep_err_slot(), hipGetLastError());
+    return QC_OK;
+}

@@ -16,6 +16,8 @@
 // Everything else returns QC_ERR_UNSUPPORTED (Lindblad generators need stored forward states) -- unless the descriptor opts in with
 // reserved1[0] = QC_SWEEP_STORED_STATES: such handles are routed to the stored-state walk of qc_sweep_open_grad.hip (wide handles that also
 // set QC_SWEEP_WIDE_STORED: of qc_sweep32_open_grad.hip), whatever their generators, behind the same totals, seed (with lambda = g_r for the density fidelity) and reductions; qc_sweep_reverse_scope decides.
+// Descriptors with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD extend the closed scope to the "mfma64-sweep" form, 32 < 2N <= 64, with
+// states of up to 32 columns: the seed at ld = 64 and the walk of qc_sweep64_grad.hip, the same reductions; no parameter gradients there.
 // Wide descriptors (wide = QC_SWEEP_WIDE) extend the scope to the "mfma32-sweep" form, 2N <= 32: this file routes such handles to the
 // seed and walk kernels of qc_sweep32_grad.hip and shares its reductions (launch 4) with them; parameter gradients there only for
 // descriptors that also set QC_SWEEP_WIDE_PARAMS (the flavour <true> of that file's walk, then qc_sweep_par_reduce_kernel of this one).
@@ -305,6 +307,13 @@ __global__ __launch_bounds__(kSeedT) void qc_sweep_seed_kernel(const SeedParams 
     fid_seed<16>(F, tot, src, gr, gi, xs, ls, fids, sm);
 }
 
+__global__ __launch_bounds__(kSeedT) void qc_sweep64_seed_kernel(const SeedParams F, const double* __restrict__ tot, const double* __restrict__ src,
+                                                                 const double* __restrict__ gr, const double* __restrict__ gi,
+                                                                 double* __restrict__ xs, double* __restrict__ ls, double* __restrict__ fids) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    fid_seed<64>(F, tot, src, gr, gi, xs, ls, fids, sm);
+}
+
 __global__ __launch_bounds__(kSeedT) void qc_sweep32_seed_kernel(const SeedParams F, const double* __restrict__ tot, const double* __restrict__ src,
                                                                  const double* __restrict__ gr, const double* __restrict__ gi,
                                                                  double* __restrict__ xs, double* __restrict__ ls, double* __restrict__ fids) {
@@ -359,7 +368,8 @@ __global__ __launch_bounds__(kRedT) void qc_sweep_J_kernel(long long S, const do
 bool qc_sweep_closed_scope(const qc_sweep_desc* d, std::string* why) {
     const int n = 2 * d->N;
     if (!qc_sweep_desc_is_mfma(d)) { *why = qc_sweep_per_sample_why(d); return false; }
-    if (qc_sweep_desc_form(d) == QC_SWEEP_FORM_64) { *why = qc_sweep_form64_why(d); return false; }
+    const bool form64 = qc_sweep_desc_form(d) == QC_SWEEP_FORM_64;      // served only with QC_SWEEP_WIDE_64_GRAD (qc_sweep64_grad.hip)
+    if (form64 && !(d->wide & QC_SWEEP_WIDE_64_GRAD)) { *why = qc_sweep_form64_why(d); return false; }
     const double* sets[3] = {d->G_drift, d->G_drives, d->G_pert};
     const int counts[3] = {1, d->m, d->n_pert};
     const char* names[3] = {"G_drift", "drive generator", "perturbation generator"};
@@ -379,6 +389,10 @@ bool qc_sweep_closed_scope(const qc_sweep_desc* d, std::string* why) {
             }
         }
     const int nc = d->state_cols == 0 ? d->N : d->state_cols;
+    if (form64) {      // x and lambda are 4 x 2 tiles there: a full unitary of N <= 32 fits
+        if (nc > 32) { *why = "states of more than 32 columns are not served in the mfma64-sweep form (2N = " + std::to_string(n) + ", state_cols = " + std::to_string(nc) + ")"; return false; }
+        return true;
+    }
     if (nc > 16) { *why = "states of more than 16 columns are not served (state_cols = " + std::to_string(nc) + ")"; return false; }
     return true;
 }
@@ -390,7 +404,7 @@ bool qc_sweep_reverse_scope(const qc_sweep_desc* d, std::string* why) {
     if (d->reserved1[0] != QC_SWEEP_STORED_STATES) return qc_sweep_closed_scope(d, why);
     const qc_sweep_form form = qc_sweep_desc_form(d);
     if (form == QC_SWEEP_FORM_PER_SAMPLE) { *why = qc_sweep_per_sample_why(d); return false; }
-    if (form == QC_SWEEP_FORM_64) { *why = qc_sweep_form64_why(d); return false; }
+    if (form == QC_SWEEP_FORM_64) { *why = qc_sweep_form64_unserved(d, "stored-state gradients"); return false; }
     if (form == QC_SWEEP_FORM_32 && !(d->wide & QC_SWEEP_WIDE_STORED)) { *why = "stored-state gradients are not served in the mfma32-sweep form"; return false; }
     const int nc = d->state_cols == 0 ? d->N : d->state_cols;
     if (nc > 16) { *why = "states of more than 16 columns are not served (state_cols = " + std::to_string(nc) + ")"; return false; }
@@ -457,8 +471,11 @@ void qc_sweep_launch_fid_seed(qc_sweep* h, int64_t S, int64_t n_chunks, const do
     SeedParams F;
     F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
     F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;
-    const size_t lds = qc_sweep_seed::lds_bytes(h->ns, h->mfma32 ? 32 : 16);      // at most 16 state columns: 16 KiB
-    const auto seed = h->mfma32 ? qc_sweep32_seed_kernel : qc_sweep_seed_kernel;
+    // at most 16 state columns: 16 KiB; "mfma64-sweep": at most 32, 64 KiB and the kernel's static words, hence the opt-in
+    const size_t lds = qc_sweep_seed::lds_bytes(h->ns, h->mfma64 ? 64 : h->mfma32 ? 32 : 16);
+    const auto seed = h->mfma64 ? qc_sweep64_seed_kernel : h->mfma32 ? qc_sweep32_seed_kernel : qc_sweep_seed_kernel;
+    if (h->mfma64)      // a refusal shows as the launch's error, which the caller reads
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep64_seed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(seed, dim3((unsigned)S), dim3(kSeedT), lds, st, F, (const double*)h->dTot.p, dinit, (const double*)h->dgr,
                        (const double*)h->dgi, h->dXs.p, h->dLs.p, dfids);
 }
@@ -477,6 +494,10 @@ void qc_sweep_launch_weighted(qc_sweep* h, int64_t S, const double* gsamp, const
 
 // "mfma32-sweep" handles made without QC_SWEEP_WIDE_PARAMS, in scope or not: the refusal of both parameter entry points
 static const char* const kNoWideParGrad = "qc_sweep gradients: parameter gradients are not served in the mfma32-sweep form";
+// "mfma64-sweep" handles made with QC_SWEEP_WIDE_64_GRAD (without it the gradient's own scope refuses, as before)
+static int no_par_grad64(qc_sweep* h) {
+    return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, "qc_sweep gradients: parameter gradients are not served in the mfma64-sweep form (2N = " + std::to_string(h->n) + ")");
+}
 
 // the argument checks of all four entry points, in the order of the header
 static int grad_check(qc_sweep* h, const char* who, const double* Z, const double* init, int64_t S, const double* theta, bool any_out, bool g_theta,
@@ -525,7 +546,9 @@ static int qc_sweep_grad_launch(qc_sweep* h, const char* who, const double* dZ, 
     if (want_par) QC_SIDE_HIP(h, slot, h->grow(h->dPart, (size_t)S * n_chunks * (p + m)));
     if (h->stored && (want_grad || want_par)) QC_SIDE_HIP(h, slot, h->grow(h->dXall, (size_t)S * (size_t)n_int * h->ns));
     qc_sweep_launch_fid_seed(h, S, n_chunks, dinit, dfids, st);
-    if (h->stored) {      // reserved1[0] = QC_SWEEP_STORED_STATES: the walk of qc_sweep_open_grad.hip, whatever the generators
+    if (h->mfma64 && h->wide64_grad) {      // the 4 x 4-tile form: its own walk (qc_sweep64_grad.hip), then the reductions below
+        if (want_grad && (rc = qc_sweep64_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, gsamp, st))) return rc;
+    } else if (h->stored) {      // reserved1[0] = QC_SWEEP_STORED_STATES: the walk of qc_sweep_open_grad.hip, whatever the generators
         if (want_grad || want_par)      // (an "mfma32-sweep" handle is in scope only with QC_SWEEP_WIDE_STORED: the 2 x 2-tile walk)
             (h->mfma32 ? qc_sweep32_open_launch_walk : qc_sweep_open_launch_walk)(h, dZ, dinit, S, dtheta, dscale, chunk, n_chunks,
                                                                                  want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);
@@ -550,6 +573,7 @@ extern "C" int qc_sweep_grad_params_dev(qc_sweep* h, const double* dZ, const dou
                                         const double* dweights, double* dfids, double* dJ, double* dgrad, double* dgrad_samples,
                                         double* dgrad_theta, double* dgrad_scale, void* stream) {
     if (h && h->mfma32 && !h->wide_par) return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, kNoWideParGrad);
+    if (h && h->wide64_grad) return no_par_grad64(h);
     return qc_sweep_grad_launch(h, "qc_sweep_grad_params_dev", dZ, dinit, S, dtheta, dscale, dweights, dfids, dJ, dgrad, dgrad_samples, dgrad_theta,
                                 dgrad_scale, stream);
 }
@@ -589,5 +613,6 @@ extern "C" int qc_sweep_grad_params(qc_sweep* h, const double* Z, const double* 
                                     const double* weights, double* fids, double* J, double* grad, double* grad_samples, double* grad_theta,
                                     double* grad_scale) {
     if (h && h->mfma32 && !h->wide_par) return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, kNoWideParGrad);
+    if (h && h->wide64_grad) return no_par_grad64(h);
     return qc_sweep_grad_host(h, "qc_sweep_grad_params", Z, init, S, theta, scale, weights, fids, J, grad, grad_samples, grad_theta, grad_scale);
 }

@@ -386,6 +386,8 @@ int hvp_check(qc_sweep* h, const char* who, const void* Z, const void* init, int
 // The pullback's closed scope (its reasons first: the per-sample form, antisymmetry, more than 16 columns) within the "mfma16-sweep" form,
 // or within the "mfma32-sweep" form of a descriptor whose wide has QC_SWEEP_WIDE_HESSIAN (qc_sweep32_hvp.hip).
 bool qc_sweep_hvp_scope(const qc_sweep_desc* d, std::string* why) {
+    // the closed scope can pass in the "mfma64-sweep" form (QC_SWEEP_WIDE_64_GRAD): this scope refuses the form itself
+    if (qc_sweep_desc_form(d) == QC_SWEEP_FORM_64) { *why = qc_sweep_form64_unserved(d, "Hessian products"); return false; }
     if (!qc_sweep_closed_scope(d, why)) return false;
     if (qc_sweep_desc_form(d) == QC_SWEEP_FORM_32 && !(d->wide & QC_SWEEP_WIDE_HESSIAN)) { *why = "Hessian products are not served in the mfma32-sweep form"; return false; }
     return true;

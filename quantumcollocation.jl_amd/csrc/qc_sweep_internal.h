@@ -11,7 +11,8 @@ struct qc_sweep : qc_side {
     qc_sweep_desc d;             // caller-owned arrays are not retained (pointers nulled)
     bool mfma = false;
     bool mfma32 = false;         // the 2 x 2-tile form of a wide descriptor ("mfma32-sweep", qc_sweep32.hip); mfma is set as well
-    bool mfma64 = false;         // the 4 x 4-tile form of a descriptor with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 ("mfma64-sweep", qc_sweep64.hip): the forward sweep only; mfma is set as well
+    bool mfma64 = false;         // the 4 x 4-tile form of a descriptor with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 ("mfma64-sweep", qc_sweep64.hip): the forward sweep, and with wide64_grad its closed adjoint; mfma is set as well
+    bool wide64_grad = false;    // mfma64 and wide has QC_SWEEP_WIDE_64_GRAD: gradients and pullbacks of closed systems are served (qc_sweep64_grad.hip)
     bool wide_par = false;       // mfma32 and wide has QC_SWEEP_WIDE_PARAMS: parameter gradients and cotangents are served (qc_sweep32_grad.hip)
     bool wide_stored = false;    // mfma32 and wide has QC_SWEEP_WIDE_STORED: with `stored`, reverse mode by the 2 x 2-tile stored-state walk (qc_sweep32_open_grad.hip)
     bool wide_tangent = false;   // mfma32 and wide has QC_SWEEP_WIDE_TANGENT: pushforwards are served (qc_sweep32_jvp.hip)
@@ -115,6 +116,9 @@ enum qc_sweep_form { QC_SWEEP_FORM_PER_SAMPLE = 0, QC_SWEEP_FORM_16 = 1, QC_SWEE
 qc_sweep_form qc_sweep_desc_form(const qc_sweep_desc* d);
 // QC_SWEEP_FORM_64: "the handle takes the mfma64-sweep form (2N = ...), which serves the forward sweep only", the reason of every other scope there
 std::string qc_sweep_form64_why(const qc_sweep_desc* d);
+// QC_SWEEP_FORM_64: the reason of a scope that the form does not serve.  Without QC_SWEEP_WIDE_64_GRAD the sentence above; with it "the
+// handle takes the mfma64-sweep form (2N = ...), which does not serve <what>"
+std::string qc_sweep_form64_unserved(const qc_sweep_desc* d, const char* what);
 // QC_SWEEP_FORM_PER_SAMPLE: "the handle takes the rollout-per-sample form (...)" with its cause, the reason of every scope that needs an MFMA form
 std::string qc_sweep_per_sample_why(const qc_sweep_desc* d);
 // the chunk rule of the MFMA forms: `form` chooses the fill constant (QC_SWEEP_FORM_64: one workgroup per compute unit; _16 and _32: a couple of waves per SIMD)
@@ -137,6 +141,10 @@ int qc_sweep32_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const dou
 __attribute__((visibility("hidden"))) void qc_sweep64_image(const double* G, int n, double* img);
 __attribute__((visibility("hidden"))) int qc_sweep64_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, hipStream_t st, int64_t* chunk,
                              int64_t* n_chunks);
+// "mfma64-sweep" handles with `wide64_grad` (qc_sweep64_grad.hip): the backward walk qc_sweep64_grad_kernel, one workgroup per (sample, chunk)
+// (gs: S x (T-1) x nd; x and lambda at the chunk ends from h->dXs / h->dLs); QC_OK or the launch's code
+__attribute__((visibility("hidden"))) int qc_sweep64_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk,
+                                                                  int64_t n_chunks, double* gs, hipStream_t st);
 // "mfma32-sweep" gradients (qc_sweep32_grad.hip): the backward walk qc_sweep32_grad_kernel<false> (gs: S x (T-1) x nd), or with `par` the
 // parameter flavour <true> (gs may be NULL) and qc_sweep_par_reduce_kernel out of h->dPart; scratch is the caller's
 void qc_sweep32_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,
@@ -162,7 +170,8 @@ bool qc_sweep_reverse_scope(const qc_sweep_desc* d, std::string* why);
 bool qc_sweep_closed_grad_scope(const qc_sweep_desc* d, std::string* why);
 // device-free: is this (valid) descriptor inside the gradient's scope?  `why` receives the reason when it is not.
 bool qc_sweep_grad_scope(const qc_sweep_desc* d, std::string* why);
-// what the gradient and the pullback ask alike (an MFMA form, antisymmetric matrices, at most 16 state columns), and the pullback's scope
+// what the gradient and the pullback ask alike (an MFMA form -- "mfma64-sweep" only with QC_SWEEP_WIDE_64_GRAD --, antisymmetric matrices, at most
+// 16 state columns, in the "mfma64-sweep" form 32), and the pullback's scope
 bool qc_sweep_closed_scope(const qc_sweep_desc* d, std::string* why);
 bool qc_sweep_vjp_scope(const qc_sweep_desc* d, std::string* why);
 // the pushforward's scope (qc_sweep_jvp.hip): the "mfma16-sweep" form, and the "mfma32-sweep" form of a descriptor whose wide has

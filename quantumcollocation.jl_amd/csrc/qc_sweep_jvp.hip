@@ -308,7 +308,7 @@ bool qc_sweep_jvp_scope(const qc_sweep_desc* d, std::string* why) {
         *why = "pushforwards are not served in the mfma32-sweep form";
         return false;
     }
-    *why = form == QC_SWEEP_FORM_64 ? qc_sweep_form64_why(d) : qc_sweep_per_sample_why(d);
+    *why = form == QC_SWEEP_FORM_64 ? qc_sweep_form64_unserved(d, "pushforwards") : qc_sweep_per_sample_why(d);
     return false;
 }
 

@@ -353,7 +353,7 @@ bool qc_sweep_noise_scope(const qc_sweep_desc* d, std::string* why) {
     const qc_sweep_form form = qc_sweep_desc_form(d);
     if (form == QC_SWEEP_FORM_32 && !(d->wide & QC_SWEEP_WIDE_NOISE)) { *why = "noise trajectories are not served in the mfma32-sweep form"; return false; }
     if (form == QC_SWEEP_FORM_PER_SAMPLE) { *why = qc_sweep_per_sample_why(d); return false; }
-    if (form == QC_SWEEP_FORM_64) { *why = qc_sweep_form64_why(d); return false; }
+    if (form == QC_SWEEP_FORM_64) { *why = qc_sweep_form64_unserved(d, "noise trajectories"); return false; }
     if (d->n_pert == 0) { *why = "the handle has no perturbations (n_pert = 0): noise enters through the perturbation generators"; return false; }
     if (form == QC_SWEEP_FORM_16 && d->m + d->n_pert > kNTiles) {      // the wide form keeps no tile resident: m <= 8 and n_pert <= QC_MAX_PERT, up to 16 generators
         *why = "m + n_pert = " + std::to_string(d->m) + " + " + std::to_string(d->n_pert) + " exceeds the 8 tiles a wavefront keeps in registers";

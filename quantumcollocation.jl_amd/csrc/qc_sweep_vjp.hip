@@ -15,7 +15,8 @@
 //      fidelity seeds take: lambda_0 = Q_0^T lambda_{end of chunk 0}.  (n_chunks = 1: that step is the only transposed product.)
 //   3. the walk, when a derivative over the intervals or the parameters is asked for: flavour <M, false> without grad_theta /
 //      grad_scale, <M, true> and qc_sweep_par_reduce_kernel with either (as qc_sweep_grad_launch chooses); the wide walk likewise
-//      (qc_sweep32_grad_kernel<false> / <true>), its parameter flavour only on handles made with QC_SWEEP_WIDE_PARAMS.
+//      (qc_sweep32_grad_kernel<false> / <true>), its parameter flavour only on handles made with QC_SWEEP_WIDE_PARAMS.  "mfma64-sweep"
+//      handles made with QC_SWEEP_WIDE_64_GRAD: qc_sweep64_cot_seed_kernel (ld = 64) and qc_sweep64_grad_kernel, no parameter cotangents.
 //      With m = 0 and a fixed timestep there is nothing per interval: only <1, true> runs, and only for grad_theta.
 //   4. qc_sweep_vjp_reduce_kernel: grad = sum_s dphi_s/dZ, the PLAIN sum in ascending s (qc_sweep_grad_reduce_kernel reads a missing
 //      weight vector as 1/S each); +0.0 at every entry that is not a control or timestep of knots 0 .. T-2.
@@ -81,6 +82,13 @@ __global__ __launch_bounds__(kCotT) void qc_sweep32_cot_seed_kernel(const CotPar
     cot_seed<32>(F, tot, src, cot, xs, ls, finals, ginit, sm);
 }
 
+__global__ __launch_bounds__(kCotT) void qc_sweep64_cot_seed_kernel(const CotParams F, const double* __restrict__ tot, const double* __restrict__ src,
+                                                                    const double* __restrict__ cot, double* __restrict__ xs, double* __restrict__ ls,
+                                                                    double* __restrict__ finals, double* __restrict__ ginit) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    cot_seed<64>(F, tot, src, cot, xs, ls, finals, ginit, sm);
+}
+
 // grad[i] = sum_s dphi_s/dZ_i, the plain sum in ascending s, for the controls and timesteps of knots 0 .. T-2; +0.0 everywhere else
 __global__ __launch_bounds__(kSumT) void qc_sweep_vjp_reduce_kernel(const SumParams R, const double* __restrict__ gs, double* __restrict__ grad) {
     const long long i = (long long)blockIdx.x * kSumT + threadIdx.x;
@@ -113,6 +121,8 @@ int vjp_check(qc_sweep* h, const char* who, const void* Z, const void* init, int
     if (g_theta && h->d.n_pert == 0) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "grad_theta is given but the handle has no perturbations (n_pert = 0)");
     if (g_scale && h->d.m == 0) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "grad_scale is given but the handle has no drives (m = 0)");
     if ((g_theta || g_scale) && h->mfma32 && !h->wide_par) return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, kNoWidePar);
+    if ((g_theta || g_scale) && h->wide64_grad)
+        return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, "qc_sweep pullback: parameter cotangents are not served in the mfma64-sweep form (2N = " + std::to_string(h->n) + ")");
     return QC_OK;
 }
 
@@ -170,11 +180,16 @@ static int qc_sweep_vjp_launch(qc_sweep* h, const char* who, const double* dZ, c
     if (h->stored && (want_grad || want_par)) QC_SIDE_HIP(h, slot, h->grow(h->dXall, (size_t)S * (size_t)n_int * h->ns));
     CotParams F;
     F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
-    const size_t lds = qc_sweep_seed::lds_bytes(h->ns, h->mfma32 ? 32 : 16);      // at most 16 state columns: 16 KiB
-    const auto seed = h->mfma32 ? qc_sweep32_cot_seed_kernel : qc_sweep_cot_seed_kernel;
+    // at most 16 state columns: 16 KiB; "mfma64-sweep": at most 32, 64 KiB, hence the opt-in
+    const size_t lds = qc_sweep_seed::lds_bytes(h->ns, h->mfma64 ? 64 : h->mfma32 ? 32 : 16);
+    const auto seed = h->mfma64 ? qc_sweep64_cot_seed_kernel : h->mfma32 ? qc_sweep32_cot_seed_kernel : qc_sweep_cot_seed_kernel;
+    if (h->mfma64)
+        QC_SIDE_HIP(h, slot, hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep64_cot_seed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(seed, dim3((unsigned)S), dim3(kCotT), lds, st, F, (const double*)h->dTot.p, dinit, dcot, h->dXs.p, h->dLs.p, dfinals,
                        dgrad_init);
-    if (h->stored) {      // reserved1[0] = QC_SWEEP_STORED_STATES: the walk of qc_sweep_open_grad.hip behind the same seed
+    if (h->mfma64 && h->wide64_grad) {      // the 4 x 4-tile walk of qc_sweep64_grad.hip behind the seed at ld = 64
+        if (want_grad && (rc = qc_sweep64_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, gsamp, st))) return rc;
+    } else if (h->stored) {      // reserved1[0] = QC_SWEEP_STORED_STATES: the walk of qc_sweep_open_grad.hip behind the same seed
         if (want_grad || want_par)      // (an "mfma32-sweep" handle is in scope only with QC_SWEEP_WIDE_STORED: qc_sweep32_open_grad.hip)
             (h->mfma32 ? qc_sweep32_open_launch_walk : qc_sweep_open_launch_walk)(h, dZ, dinit, S, dtheta, dscale, chunk, n_chunks,
                                                                                  want_grad ? gsamp : nullptr, want_par, dgrad_theta, dgrad_scale, st);

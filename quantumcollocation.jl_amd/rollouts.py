@@ -240,15 +240,21 @@ class RolloutSweep:
                    transmons, a five-level Lindblad model -- run on the matrix cores as well ("mfma64-sweep": one workgroup per
                    (sample, chunk of intervals), the matrices in LDS) instead of one rollout per sample.  That form serves `eval` and
                    `eval_device` only: `grad`, `param_grad`, `vjp`, `jvp`, `hvp` and the noise sweeps refuse there, naming the form.
-                   Nothing changes at 2N <= 32, and nothing changes without it."""
+                   Nothing changes at 2N <= 32, and nothing changes without it.
+    wide64_grad    True (only with `wide64`): an "mfma64-sweep" handle of a closed system (antisymmetric generators, at most 32 state
+                   columns: a full unitary of 32 levels fits) also serves `grad`, `vjp`, their device forms and the backward rule of
+                   `finals_autograd`, by the closed adjoint walk on 4 x 4 tiles.  `param_grad`, the `params` of `vjp`, `stored_states`,
+                   `jvp`, `hvp` and the noise sweeps still refuse there, naming the form.  Nothing else changes, nothing changes at
+                   2N <= 32, and nothing changes without it."""
 
     def __init__(self, system, perturbations, T: int, cols: Optional[int] = None, goal=None, fid_kind=None, subspace=None,
                  fid_form: int = _lib.QC_FID_FORM_ABS, zdim: Optional[int] = None, off_a: int = 0, off_dt: Optional[int] = None,
                  dt_fixed: Optional[float] = None, global_dim: int = 0, device: int = 0, wide: bool = False,
                  stored_states: bool = False, wide_params: bool = False, wide_stored: bool = False, wide_tangent: bool = False,
-                 wide_noise: bool = False, wide_hessian: bool = False, wide64: bool = False):
+                 wide_noise: bool = False, wide_hessian: bool = False, wide64: bool = False, wide64_grad: bool = False):
         self._h = None
         flags = (   # (keyword, given, its bit of qc_sweep_desc.wide, what it needs, the refusal without that)
+            ("wide64_grad", wide64_grad, _lib.QC_SWEEP_WIDE_64_GRAD, wide64, "wide64_grad=True needs wide64=True"),
             ("wide64", wide64, _lib.QC_SWEEP_WIDE_64, wide, "wide64=True needs wide=True"),
             ("wide_hessian", wide_hessian, _lib.QC_SWEEP_WIDE_HESSIAN, wide, "wide_hessian=True needs wide=True"),
             ("wide_noise", wide_noise, _lib.QC_SWEEP_WIDE_NOISE, wide, "wide_noise=True needs wide=True"),
@@ -304,6 +310,15 @@ class RolloutSweep:
         h = C.c_void_p()
         _lib.check_rc(_lib.lib.qc_sweep_create(C.byref(d), C.byref(h)), _ERR)
         self._h = h
+
+    @property
+    def wide64_grad(self) -> bool:
+        """Whether the handle was made with `wide64_grad` (kept outside the instance's public flags, which are what they were)."""
+        return self._wide64_grad
+
+    @wide64_grad.setter
+    def wide64_grad(self, given):
+        self._wide64_grad = bool(given)
 
     def _scope(self, supported):
         """(served?, the library's reason why not or None) from a `qc_sweep_desc_*_supported` function."""
