@@ -57,8 +57,9 @@ def make_case(qc, T=9, free=True, dt_scaled=True, global_dim=0, baseline=False, 
     return traj, spec, tm, Z
 
 
-def ext_struct(qc, tm, keep):
-    """qc_terms_desc + qc_terms_ext of the restatement (arrays kept alive in `keep`)."""
+def ext_struct(qc, tm, keep, baseline=False):
+    """qc_terms_desc + qc_terms_ext of the restatement (arrays kept alive in `keep`).  `baseline=True` also passes
+    tm.baseline as reg_baseline; by default the descriptor carries none."""
     L = qc._lib
     arr = lambda a, dt: keep.append(np.ascontiguousarray(a, dtype=dt)) or keep[-1]
     d = L.qc_terms_desc()
@@ -68,6 +69,8 @@ def ext_struct(qc, tm, keep):
     d.weighting = L.QC_REG_DT_SCALED if tm.dt_scaled else L.QC_REG_PLAIN
     d.reg_index = ri.ctypes.data_as(C.POINTER(C.c_int32))
     d.reg_R = L.dptr(rR)
+    if baseline and tm.baseline is not None:
+        d.reg_baseline = L.dptr(arr(tm.baseline, np.float64))      # (T, n_reg), entry-fastest
     d.min_time_D, d.min_time_knots = tm.D, tm.n_mt
     x = L.qc_terms_ext()
     ip = lambda a: arr(a, np.int32).ctypes.data_as(C.POINTER(C.c_int32))
