@@ -664,6 +664,13 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * names the form and 2N: parameter gradients and parameter cotangents, reserved1[0] = QC_SWEEP_STORED_STATES, qc_sweep_jvp*,
  * qc_sweep_hvp* and qc_sweep_noise_*.  Form, launch, kernel name and every output bit of qc_sweep_eval* are those of the same descriptor
  * without the bit; descriptors with 2N <= 32 ignore it completely, as they ignore bit 10.
+ * Bit 13, QC_SWEEP_WIDE_64_PARAMS (any valid value that has bits 0, 10 and 11, | 8192; without all three of them QC_ERR_INVALID; bit 12
+ * is not assigned), changes one thing only: such a handle then also serves qc_sweep_grad_params* (grad_theta, grad_scale) and the
+ * grad_theta / grad_scale of qc_sweep_vjp*, in the scope of bit 11, by the parameter flavour of the same walk (per (sample, chunk) the
+ * p + m chunk shares in a fixed order, then the reduction of the smaller forms; no atomics).  The other outputs of a parameter call carry
+ * the bits of qc_sweep_grad / qc_sweep_vjp on the same handle, and a call without parameter outputs launches exactly what it launched
+ * without the bit.  The stored-state flag, qc_sweep_jvp*, qc_sweep_hvp* and qc_sweep_noise_* stay QC_ERR_UNSUPPORTED there; descriptors
+ * with 2N <= 32 ignore the bit completely.
  * reserved1[0] = QC_SWEEP_STORED_STATES chooses reverse mode by the STORED-STATE walk: qc_sweep_grad*, qc_sweep_grad_params* and
  * qc_sweep_vjp* then keep the forward states x_0 .. x_{T-2} of every sample in handle scratch (S x (T-1) x 2N x cols doubles) and read
  * them on the way back instead of reversing the step, which serves ANY generators in the "mfma16-sweep" form: Lindblad generators
@@ -676,7 +683,7 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * qc_sweep_noise_grad* keep their scope (antisymmetric generators) and their kernels with it.
  * Results do not depend on scheduling: repeated calls return the same bits.  Non-finite inputs are evaluated, not rejected.
  * Gradients with respect to the controls and timesteps (qc_sweep_grad*) and to the samples' own parameters theta and `scale`
- * (qc_sweep_grad_params*), both below, are served for closed systems in the MFMA forms (parameter gradients: "mfma16-sweep" only), and
+ * (qc_sweep_grad_params*), both below, are served for closed systems in the MFMA forms (parameter gradients: "mfma16-sweep", "mfma32-sweep" with QC_SWEEP_WIDE_PARAMS, "mfma64-sweep" with QC_SWEEP_WIDE_64_PARAMS), and
  * with reserved1[0] = QC_SWEEP_STORED_STATES for open systems in the "mfma16-sweep" form and, with QC_SWEEP_WIDE_STORED, the "mfma32-sweep" form.
  * Derivatives of the final states themselves, contracted with cotangents the caller chooses (qc_sweep_vjp*, below), carry any function
  * of the final states: leakage, the free-phase fidelity, several kets at once, a loss written elsewhere.
@@ -691,7 +698,8 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * derivatives are not served there at all), checkpointing inside a chunk, Hessian products and noise gradients of open
  * systems, pushforwards on "mfma32-sweep" and "rollout-per-sample" handles (the former unless `wide` has QC_SWEEP_WIDE_TANGENT), Hessian
  * products on "rollout-per-sample" handles and on "mfma32-sweep" handles without QC_SWEEP_WIDE_HESSIAN, several directions per
- * call, tangents of grad_theta / grad_scale, several devices; in the "mfma64-sweep" form everything but the forward sweep. */
+ * call, tangents of grad_theta / grad_scale, several devices; in the "mfma64-sweep" form everything but the forward sweep, with
+ * QC_SWEEP_WIDE_64_GRAD gradients and pullbacks of closed systems and with QC_SWEEP_WIDE_64_PARAMS their parameter outputs. */
 #define QC_MAX_PERT 8
 #define QC_SWEEP_FID_NONE (-1)   /* qc_sweep_desc.fid_kind: final states only */
 #define QC_SWEEP_WIDE 1          /* qc_sweep_desc.wide, bit 0 */
@@ -701,6 +709,7 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
 #define QC_SWEEP_WIDE_NOISE 64   /* qc_sweep_desc.wide, bit 6: the mfma32-sweep form serves noise-trajectory sweeps and their gradients (qc_sweep_noise_*); only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_WIDE_HESSIAN 256 /* qc_sweep_desc.wide, bit 8: the mfma32-sweep form serves Hessian products of closed systems (qc_sweep_hvp*); only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_WIDE_64_GRAD 2048 /* qc_sweep_desc.wide, bit 11: the mfma64-sweep form serves sweep gradients and pullbacks of closed systems (qc_sweep_grad*, qc_sweep_vjp*; qc_sweep64_grad.hip); ignored at 2N <= 32; only together with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 */
+#define QC_SWEEP_WIDE_64_PARAMS 8192 /* qc_sweep_desc.wide, bit 13: the mfma64-sweep form serves parameter gradients and parameter cotangents of closed systems (qc_sweep_grad_params*, grad_theta / grad_scale of qc_sweep_vjp*; the flavour <true> of qc_sweep64_grad.hip's walk); ignored at 2N <= 32; only together with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD */
 #define QC_SWEEP_WIDE_64 1024    /* qc_sweep_desc.wide, bit 10: 32 < 2N <= 64 with up to 16 drives takes the matrix cores ("mfma64-sweep", qc_sweep_eval* only); ignored at 2N <= 32; only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_STORED_STATES 1 /* qc_sweep_desc.reserved1[0]: reverse mode by the stored-state walk */
 typedef struct qc_sweep_desc {
@@ -723,7 +732,7 @@ typedef struct qc_sweep_desc {
     const double* goal_iso;      /* as qc_fidelity_desc.goal_iso */
     const int32_t* subspace;     /* unitary only: 0-based levels, or NULL = all */
     int32_t device;
-    int32_t wide;                /* bit field; valid: 0, QC_SWEEP_WIDE (1): the matrix-core form up to 2N = 32 ("mfma32-sweep"), or QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS (3): that form, and qc_sweep_grad_params* / the grad_theta, grad_scale of qc_sweep_vjp* are served in it (form, launch, kernel name and every *_supported answer as with 1; harmless where the handle takes another form); either of them | QC_SWEEP_WIDE_STORED (9, 11): that form also serves reverse mode by the stored-state walk when reserved1[0] = QC_SWEEP_STORED_STATES (nothing else changes); any of those | QC_SWEEP_WIDE_TANGENT (17, 19, 25, 27): that form also serves qc_sweep_jvp*; any of the eight | QC_SWEEP_WIDE_NOISE (64): that form also serves qc_sweep_noise_*; any of the sixteen | QC_SWEEP_WIDE_HESSIAN (256): that form also serves qc_sweep_hvp* for closed systems; any of the thirty-two | QC_SWEEP_WIDE_64 (1024): 32 < 2N <= 64 with m <= 16 takes the matrix-core form "mfma64-sweep" (forward sweep only), nothing changes at 2N <= 32; anything else is QC_ERR_INVALID */
+    int32_t wide;                /* bit field; valid: 0, QC_SWEEP_WIDE (1): the matrix-core form up to 2N = 32 ("mfma32-sweep"), or QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS (3): that form, and qc_sweep_grad_params* / the grad_theta, grad_scale of qc_sweep_vjp* are served in it (form, launch, kernel name and every *_supported answer as with 1; harmless where the handle takes another form); either of them | QC_SWEEP_WIDE_STORED (9, 11): that form also serves reverse mode by the stored-state walk when reserved1[0] = QC_SWEEP_STORED_STATES (nothing else changes); any of those | QC_SWEEP_WIDE_TANGENT (17, 19, 25, 27): that form also serves qc_sweep_jvp*; any of the eight | QC_SWEEP_WIDE_NOISE (64): that form also serves qc_sweep_noise_*; any of the sixteen | QC_SWEEP_WIDE_HESSIAN (256): that form also serves qc_sweep_hvp* for closed systems; any of the thirty-two | QC_SWEEP_WIDE_64 (1024): 32 < 2N <= 64 with m <= 16 takes the matrix-core form "mfma64-sweep" (forward sweep only), nothing changes at 2N <= 32; any of those | QC_SWEEP_WIDE_64_GRAD (2048): that form also serves qc_sweep_grad* and qc_sweep_vjp* of closed systems; any of those | QC_SWEEP_WIDE_64_PARAMS (8192): and their parameter outputs; anything else is QC_ERR_INVALID */
     int64_t reserved1[2];        /* [0]: 0, or QC_SWEEP_STORED_STATES: reverse mode reads stored forward states (any generators; "mfma16-sweep", and "mfma32-sweep" with QC_SWEEP_WIDE_STORED in `wide`); anything else is QC_ERR_INVALID.  [1]: ignored */
 } qc_sweep_desc;
 typedef struct qc_sweep qc_sweep;
@@ -795,7 +804,11 @@ int qc_sweep_grad(qc_sweep* h, const double* Z, const double* init, int64_t S, c
  * "mfma16-sweep" handle (the parameter flavour of the 2 x 2-tile walk; scope, checks and outputs as above, fids / J / grad / grad_samples
  * with the bits of qc_sweep_grad on the same handle).  On one made with wide = QC_SWEEP_WIDE alone both return QC_ERR_UNSUPPORTED
  * ("parameter gradients are not served in the mfma32-sweep form"), with or without QC_SWEEP_WIDE_STORED: the stored-state walk's
- * parameter flavour on 2 x 2 tiles needs wide = 11. */
+ * parameter flavour on 2 x 2 tiles needs wide = 11.
+ * On an "mfma64-sweep" handle made with QC_SWEEP_WIDE_64_GRAD | QC_SWEEP_WIDE_64_PARAMS both entry points serve closed systems with at
+ * most 32 state columns (the parameter flavour of the 4 x 4-tile walk: du before the factor c_k, so grad_scale is defined at c = 0;
+ * fids / J / grad / grad_samples with the bits of qc_sweep_grad on the same handle); on one made without QC_SWEEP_WIDE_64_PARAMS both
+ * return QC_ERR_UNSUPPORTED ("parameter gradients are not served in the mfma64-sweep form (2N = ...)"). */
 int qc_sweep_grad_params_dev(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
                              const double* dweights, double* dfids, double* dJ, double* dgrad, double* dgrad_samples,
                              double* dgrad_theta, double* dgrad_scale, void* stream);
@@ -822,7 +835,9 @@ int qc_sweep_desc_vjp_supported(const qc_sweep_desc* d, int32_t* supported);
  *   grad_init     S x (2N cols)      dphi_s/dinit = (E_{T-2} ... E_0)^T cot[s]
  *   grad_theta    S x n_pert, grad_scale  S x m   ("mfma16-sweep", and "mfma32-sweep" handles made with wide = QC_SWEEP_WIDE |
  *                                    QC_SWEEP_WIDE_PARAMS; on an "mfma32-sweep" handle without that bit QC_ERR_UNSUPPORTED,
- *                                    "parameter cotangents are not served in the mfma32-sweep form")
+ *                                    "parameter cotangents are not served in the mfma32-sweep form"; "mfma64-sweep" handles
+ *                                    made with QC_SWEEP_WIDE_64_GRAD | QC_SWEEP_WIDE_64_PARAMS, without the latter
+ *                                    QC_ERR_UNSUPPORTED, "... not served in the mfma64-sweep form (2N = ...)")
  * cot must not overlap any output.  Scratch and the one-in-flight rule as qc_sweep_grad_dev.  Repeated calls return the same bits, and
  * no output's bits depend on which other outputs were requested.  Non-finite cotangents are evaluated, not rejected: they reach
  * their own sample's outputs and `grad`, nothing else. */

@@ -19,6 +19,7 @@ const QC_SWEEP_WIDE_TANGENT = 16   # qc_sweep_desc.wide, bit 4 (only with bit 0)
 const QC_SWEEP_WIDE_NOISE = 64     # qc_sweep_desc.wide, bit 6 (only with bit 0): noise-trajectory sweeps and their gradients in that form
 const QC_SWEEP_WIDE_HESSIAN = 256  # qc_sweep_desc.wide, bit 8 (only with bit 0): Hessian products of closed systems in that form
 const QC_SWEEP_WIDE_64_GRAD = 2048 # qc_sweep_desc.wide, bit 11 (only with bits 0 and 10): gradients and pullbacks of closed systems in the "mfma64-sweep" form
+const QC_SWEEP_WIDE_64_PARAMS = 8192 # qc_sweep_desc.wide, bit 13 (only with bits 0, 10 and 11): parameter gradients and parameter cotangents in the "mfma64-sweep" form
 const QC_SWEEP_WIDE_64 = 1024      # qc_sweep_desc.wide, bit 10 (only with bit 0): 32 < 2N ≤ 64 with up to 16 drives on the matrix cores ("mfma64-sweep", forward sweep only)
 const QC_ABI_VERSION = 6      # QC_VERSION_MAJOR * 1000 + QC_VERSION_MINOR of the include/qcolloc.h these mirrors were written against
 
@@ -916,17 +917,21 @@ end
 
 """
     rollout_sweep_parameter_gradient(init, controls, Δt, G_drift, G_drives, G_pert, θ; scale=nothing, cols, goal, fid_kind=0,
-                                     subspace=nothing, squared=false, device=0, stored_states=false, wide=false)  ->  (fids, ∇θ, ∇c)
+                                     subspace=nothing, squared=false, device=0, stored_states=false, wide=false, wide64_params=false)  ->  (fids, ∇θ, ∇c)
 
 The derivatives of the S fidelities of `rollout_sweep` with respect to the SYSTEMS (`qc_sweep_grad_params`): `∇θ[s, j]` = ∂F_s/∂θ[s, j]
 (S×p) and `∇c[s, k]` = ∂F_s/∂scale[s, k] (S×m; `scale = nothing`: taken at all ones), raw per-sample values from one backward walk.
 Scope and arguments as `rollout_sweep_gradient` (`stored_states = true`: open systems, as there).  `wide = true` sets
 `qc_sweep_desc.wide = QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS` (3): 2N ≤ 32 on the matrix cores, parameter gradients included.
-UNTESTED here, like the rest of this file.
+`wide64_params = true` (only with `wide`) adds `QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD | QC_SWEEP_WIDE_64_PARAMS` (11267 in all): closed
+systems with 32 < 2N ≤ 64, m ≤ 16 and at most 32 state columns in the "mfma64-sweep" form, parameter gradients included.
+UNTESTED here, like the rest of this file: no Julia runs where this library is built and tested.
 """
 function rollout_sweep_parameter_gradient(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift,
                                           G_drives, G_pert, θ::AbstractMatrix{Float64}; scale=nothing, cols::Int, goal, fid_kind::Int=0,
-                                          subspace=nothing, squared::Bool=false, device::Int=0, stored_states::Bool=false, wide_stored::Bool=false, wide::Bool=false)
+                                          subspace=nothing, squared::Bool=false, device::Int=0, stored_states::Bool=false, wide_stored::Bool=false, wide::Bool=false,
+                                          wide64_params::Bool=false)
+    (wide64_params && !wide) && error("rollout_sweep_parameter_gradient: wide64_params = true needs wide = true")
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(θ, 1)
     G0 = Float64.(vec(G_drift))
@@ -945,7 +950,8 @@ function rollout_sweep_parameter_gradient(init::AbstractVector{Float64}, control
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
                                squared ? 1 : 0, length(sub), pointer(g), isempty(sub) ? C_NULL : pointer(sub),
-                               device, (wide ? 3 : 0) | (wide_stored ? 8 : 0), (stored_states ? 1 : 0, 0)))      # 3 = QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS, 8 = QC_SWEEP_WIDE_STORED
+                               device, (wide ? 3 : 0) | (wide_stored ? 8 : 0) | (wide64_params ? (QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD | QC_SWEEP_WIDE_64_PARAMS) : 0),
+                               (stored_states ? 1 : 0, 0)))      # 3 = QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS, 8 = QC_SWEEP_WIDE_STORED
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_grad_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
         (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
@@ -965,7 +971,7 @@ end
 
 """
     rollout_sweep_pullback(init, controls, Δt, G_drift, G_drives, G_pert, θ, C̄; scale=nothing, cols, params=false, device=0,
-                           wide=false, stored_states=false, wide_params=false, wide64=false, wide64_grad=false)  ->  (finals, ∇a, ∇Δt, ∇init[, ∇θ, ∇c])
+                           wide=false, stored_states=false, wide_params=false, wide64=false, wide64_grad=false, wide64_params=false)  ->  (finals, ∇a, ∇Δt, ∇init[, ∇θ, ∇c])
 
 The pullback of `rollout_sweep` (`qc_sweep_vjp`): `C̄` is (2N·cols)×S, column s the cotangent of sample s's final state (the derivative
 of the caller's loss with respect to it, e.g. what `Zygote.pullback` hands to an `rrule`), and with φ_s = ⟨C̄[:, s], finals[:, s]⟩ the
@@ -975,12 +981,14 @@ Served for closed systems (antisymmetric generators) with 2N ≤ 16 (`wide = tru
 `qc_sweep_desc.wide`, QC_SWEEP_WIDE_PARAMS), m ≤ 8 and at most 16
 state columns, with `stored_states = true` for any generators with 2N ≤ 16; no fidelity is involved.  `wide = true, wide64 = true,
 wide64_grad = true` (3073 in `qc_sweep_desc.wide`): closed systems with 32 < 2N ≤ 64, m ≤ 16 and at most 32 state columns in the
-"mfma64-sweep" form, without `params`.  Arguments as `rollout_sweep`.  UNTESTED here, like the rest of this file.
+"mfma64-sweep" form, there with `params` only if also `wide64_params = true` (bit 13, QC_SWEEP_WIDE_64_PARAMS: 11265).  Arguments as
+`rollout_sweep`.  UNTESTED here, like the rest of this file: no Julia runs where this library is built and tested.
 """
 function rollout_sweep_pullback(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift, G_drives,
                                 G_pert, θ::AbstractMatrix{Float64}, C̄::AbstractMatrix{Float64}; scale=nothing, cols::Int, params::Bool=false,
                                 device::Int=0, wide::Bool=false, stored_states::Bool=false, wide_stored::Bool=false, wide_params::Bool=false,
-                                wide64::Bool=false, wide64_grad::Bool=false)
+                                wide64::Bool=false, wide64_grad::Bool=false, wide64_params::Bool=false)
+    (wide64_params && !wide64_grad) && error("rollout_sweep_pullback: wide64_params = true needs wide64_grad = true")
     (wide_params && !wide) && error("rollout_sweep_pullback: wide_params = true needs wide = true")
     (wide64 && !wide) && error("rollout_sweep_pullback: wide64 = true needs wide = true")
     (wide64_grad && !wide64) && error("rollout_sweep_pullback: wide64_grad = true needs wide64 = true")
@@ -1003,7 +1011,7 @@ function rollout_sweep_pullback(init::AbstractVector{Float64}, controls::Abstrac
     GC.@preserve G0 Gd Gp begin
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, -1,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
-                               0, 0, C_NULL, C_NULL, device, (wide ? 1 : 0) | (wide_params ? 2 : 0) | (wide_stored ? 8 : 0) | (wide64 ? QC_SWEEP_WIDE_64 : 0) | (wide64_grad ? QC_SWEEP_WIDE_64_GRAD : 0),
+                               0, 0, C_NULL, C_NULL, device, (wide ? 1 : 0) | (wide_params ? 2 : 0) | (wide_stored ? 8 : 0) | (wide64 ? QC_SWEEP_WIDE_64 : 0) | (wide64_grad ? QC_SWEEP_WIDE_64_GRAD : 0) | (wide64_params ? QC_SWEEP_WIDE_64_PARAMS : 0),
                                (stored_states ? 1 : 0, 0)))
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_vjp_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)

@@ -39,8 +39,25 @@
 //
 // MFMAs per interval and workgroup, nct = ceil(nc / 16):  8 Horner steps x (16 x (32 + 4 nct) + 4 nct x 16) + sq x 16 x 48 + 16 x 16 (ZT)
 // + 8 nct x 16 (x, lambda) = (4352 + 1152 nct) + 768 sq, against the forward kernel's (9 + sq) x 256 = 2304 + 256 sq.
-// No atomics, sums in a fixed order: repeated calls give the same bits.  Parameter gradients, the stored-state walk, pushforwards, Hessian
-// products and noise sweeps are not served in this form.
+// No atomics, sums in a fixed order: repeated calls give the same bits.  The stored-state walk, pushforwards, Hessian products and noise
+// sweeps are not served in this form.
+//
+// The parameter flavour <true> (handles with QC_SWEEP_WIDE_64_PARAMS; qc_sweep_grad_params*, grad_theta / grad_scale of qc_sweep_vjp*) adds,
+// per (sample, chunk), the p + m chunk shares
+//     dF_s/dtheta_q: sum_{t in chunk} sum ZT_t . P_q,      dF_s/dc_k: sum_{t in chunk} a_{t,k} du_{t,k},   du_{t,k} = sum ZT_t . G_k
+// (du BEFORE the factor c_k and a the unscaled control: no division by c, so the derivative is defined at c = 0).  The scheme of the
+// smaller forms -- a running Acc = sum_t ZT_t, contracted once at the chunk's end -- does not fit: 32 KiB of LDS where 9 472 B are free,
+// or four more registers a lane where none is.  Instead the tail's image loop runs over the m + p images (the perturbation images
+// follow the drive images in P.img: the same four loads and one wave sum each), perturbation q's wave sum goes to lane nd + q, behind
+// the timestep's lane, part[][] has rows of nd + p <= 25 values (3 200 B), and wave 0, which adds the 16 partials behind Ba anyway,
+// keeps the chunk's running sums, one value a lane (lane k < m: += a_k acc; lane nd + q: += acc), and stores them after the chunk's
+// last interval with one vector store into par[item][p + m] (perturbations, then drives: what qc_sweep_par_reduce_kernel reads).  The
+// running sums live in runs[25] (200 B of LDS; static LDS 3 528 B in all), not in a register pair: held in registers the flavour needs
+// 130 a lane and spills.  Not one MFMA is added.  Barriers: the widened part[] keeps part[]'s rule -- written in the tail, Ba stands
+// between those writes and wave 0's reads, and the next writes are a whole interval of barriers later; runs[l] is written and read by
+// lane l of wave 0 and by nobody else (zeroed by it before the walk, updated behind Ba, read back for the final store), so it needs no
+// barrier at all.  With gs = NULL (only parameter outputs asked for) the timestep's KT sum
+// and the per-interval store are skipped.  The flavour <false> is the walk as it was before the second flavour existed.
 #include <math.h>
 
 #include <string>
@@ -54,15 +71,22 @@ namespace {
 
 using namespace qc_sweep64;
 
-constexpr int kPartLd = 17;      // m + 1 <= 17 values a wave
+// values a wave leaves per interval: m + 1 <= 17; the parameter flavour adds the p <= 8 perturbation sums behind them, nd + p <= 25
+template <bool PAR> constexpr int kPartLd = PAR ? 25 : 17;
 constexpr size_t kGradLdsBytes = (size_t)(3 * kMat + 3 * kThin) * sizeof(double);      // 152 064 B
 
+// PAR = false: the per-interval derivatives only (`par` unused).  PAR = true, the parameter flavour, also accumulates the chunk's shares of
+// dF_s/dtheta_q = sum_t sum(ZT_t . P_q) and dF_s/dc_k = sum_t a_{t,k} sum(ZT_t . G_k) and stores them at the chunk's end as
+// par[item][p + m] (perturbations, then drives); `gs` may then be NULL (no per-interval store, no timestep derivative).
+template <bool PAR>
 __global__ __launch_bounds__(kThreads, 1) void qc_sweep64_grad_kernel(const SweepParams P, const double* __restrict__ Z, const double* __restrict__ theta,
                                                                         const double* __restrict__ scale, const double* __restrict__ xs,
-                                                                        const double* __restrict__ ls, double* __restrict__ gs) {
+                                                                        const double* __restrict__ ls, double* __restrict__ gs,
+                                                                        double* __restrict__ par) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     __shared__ double red[16];
-    __shared__ double part[16 * kPartLd];
+    __shared__ double part[16 * kPartLd<PAR>];
+    __shared__ double runs[PAR ? kPartLd<true> : 1];      // PAR: wave 0's running chunk sums, one a lane (<false>: unused, not allocated)
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, j = lane & 15;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6), I = w & 3, J = w >> 2;
     const int Jc = J & 1;                   // the wave's column tile of a thin matrix
@@ -106,6 +130,20 @@ __global__ __launch_bounds__(kThreads, 1) void qc_sweep64_grad_kernel(const Swee
     double av = m > 0 ? z[P.off_a + kl] : 0.0;
     const double hfix = opaque_scalar(P.dt_fixed);
     double h = ft ? z[P.off_dt] : hfix;
+    // PAR: the images contracted per interval (drives, then perturbations: they follow each other in P.img), the values a wave leaves
+    // (perturbation q in lane nd + q, behind the timestep's lane)
+    // (the scalar registers are as scarce here as the vector ones: nd is spelled m + ft and the share's address is made once, per lane,
+    // so that neither P.nd, `par` nor the item's offset stays live across the walk)
+    const int nd = PAR ? m + (ft ? 1 : 0) : P.nd;
+    const int n_img = PAR ? m + P.p : m;
+    const int n_val = PAR ? n_img + (ft ? 1 : 0) : P.nd;
+    const int mine_img = !PAR || lane < m ? lane : lane >= nd ? lane - (nd - m) : -1;      // the image whose wave sum the lane keeps
+    // the lane's share: perturbations, then drives (the layout qc_sweep_par_reduce_kernel reads)
+    double* share = PAR ? par + item * (P.p + m) + (lane < m ? P.p + lane : lane - nd) : nullptr;
+    if constexpr (PAR) asm volatile("" : "+v"(share));      // made here, not at the chunk's end
+    if constexpr (PAR) {
+        if (w == 0 && lane < kPartLd<true>) runs[lane] = 0.0;      // read and written by wave 0's lane `lane` alone: no barrier
+    }
 #pragma unroll 1
     for (int t = t1 - 1; t >= t0; --t) {
         // the previous interval's controls and timestep are requested before this interval's products
@@ -118,7 +156,7 @@ __global__ __launch_bounds__(kThreads, 1) void qc_sweep64_grad_kernel(const Swee
         const double hs = h * ldexp(1.0, -sq);
         // lane k < m: drive k's wave sum; lane m: the timestep's (sum KT . G, its sign at the store)
         double out = 0.0;
-        if (ft) {
+        if (ft && (!PAR || gs)) {
             // sum_ab KT[a][b] G[b][a] over the thread's elements G[b = lane][a = w + 16 e], KT[a][b] = sum_c lambda[a][c] x[b][c]
             double kt[4] = {0.0, 0.0, 0.0, 0.0};
             for (int c = 0; c < nc; ++c) {
@@ -174,38 +212,57 @@ __global__ __launch_bounds__(kThreads, 1) void qc_sweep64_grad_kernel(const Swee
         // the lane's elements ZT[a = 16 I + 4 r + g][b = 16 J + j] against G_u[b][a] (column-major images: a * 64 + b)
         const gptr Ge = G0 + (16 * I + g) * 64 + 16 * J + j;
 #pragma unroll 1
-        for (int u = 0; u < m; ++u) {
+        for (int u = 0; u < n_img; ++u) {
             const gptr Gu = Ge + (size_t)(1 + u) * kImg;
             double pu = 0.0;
 #pragma unroll
             for (int r = 0; r < 4; ++r) pu = fma(ZT[r], Gu[256 * r], pu);
             const double du = wave_sum(pu);
-            out = lane == u ? du : out;
+            out = mine_img == u ? du : out;
         }
-        if (lane < P.nd) part[w * kPartLd + lane] = out;
+        // PAR: kept loop-invariant, the lane compares of the tail live in scalar register pairs and the kernel spills some of them; an
+        // opaque copy of the lane index has them made per interval instead
+        int ln = lane;
+        if constexpr (PAR) asm volatile("" : "+v"(ln));
+        if (ln < n_val) part[w * kPartLd<PAR> + lane] = out;
         __syncthreads();      // Ba
         if (Jc < nct) store_tile(mine, I, Jc, g, j, nx);
-        if (w == 0 && lane < P.nd) {
+        if (w == 0 && ln < n_val) {
             double acc = part[lane];
 #pragma unroll
-            for (int i = 1; i < 16; ++i) acc += part[i * kPartLd + lane];
-            gs[(s * P.n_int + t) * P.nd + lane] = lane < m ? acc * cl : -acc;
+            for (int i = 1; i < 16; ++i) acc += part[i * kPartLd<PAR> + lane];
+            if constexpr (PAR) {
+                // lane k < m: du_k BEFORE the factor c_k against the unscaled control (no division by c); the timestep's lane adds
+                // nothing that is read; lane nd + q: perturbation q's sum
+                const double run = runs[lane];
+                runs[lane] = ln < m ? fma(av, acc, run) : run + acc;
+                if (gs && ln < nd) gs[(s * P.n_int + t) * nd + lane] = ln < m ? acc * cl : -acc;
+            } else {
+                gs[(s * P.n_int + t) * P.nd + lane] = lane < m ? acc * cl : -acc;
+            }
         }
         av = av_n;
         h = h_n;
+    }
+    if constexpr (PAR) {
+        // the chunk's shares: one vector store of p + m lanes
+        int w0 = w;      // (the mask of wave 0 is not kept across the walk either)
+        asm volatile("" : "+s"(w0));
+        if (w0 == 0 && mine_img >= 0 && mine_img < n_img) *share = runs[lane];
     }
 }
 
 }  // namespace
 
 int qc_sweep64_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,
-                           double* gs, hipStream_t st) {
+                           double* gs, bool want_par, double* par, hipStream_t st) {
     const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
+    const auto walk = want_par ? qc_sweep64_grad_kernel<true> : qc_sweep64_grad_kernel<false>;
     // per launch, as qc_sweep64_launch_totals: the attribute belongs to the (function, device) pair
-    QC_SIDE_HIP(h, *qc_sweep_err_slot(), hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep64_grad_kernel),
-                                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradLdsBytes));
-    hipLaunchKernelGGL(qc_sweep64_grad_kernel, dim3((unsigned)P.items), dim3(kThreads), kGradLdsBytes, st, P, dZ, dtheta, dscale,
-                       (const double*)h->dXs.p, (const double*)h->dLs.p, gs);
+    QC_SIDE_HIP(h, *qc_sweep_err_slot(), hipFuncSetAttribute(reinterpret_cast<const void*>(walk), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                              (int)kGradLdsBytes));
+    hipLaunchKernelGGL(walk, dim3((unsigned)P.items), dim3(kThreads), kGradLdsBytes, st, P, dZ, dtheta, dscale, (const double*)h->dXs.p,
+                       (const double*)h->dLs.p, gs, want_par ? par : (double*)nullptr);
     QC_SIDE_HIP(h, *qc_sweep_err_slot(), hipGetLastError());
     return QC_OK;
 }

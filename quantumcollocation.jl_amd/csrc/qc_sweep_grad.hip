@@ -17,7 +17,8 @@
 // reserved1[0] = QC_SWEEP_STORED_STATES: such handles are routed to the stored-state walk of qc_sweep_open_grad.hip (wide handles that also
 // set QC_SWEEP_WIDE_STORED: of qc_sweep32_open_grad.hip), whatever their generators, behind the same totals, seed (with lambda = g_r for the density fidelity) and reductions; qc_sweep_reverse_scope decides.
 // Descriptors with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD extend the closed scope to the "mfma64-sweep" form, 32 < 2N <= 64, with
-// states of up to 32 columns: the seed at ld = 64 and the walk of qc_sweep64_grad.hip, the same reductions; no parameter gradients there.
+// states of up to 32 columns: the seed at ld = 64 and the walk of qc_sweep64_grad.hip, the same reductions; parameter gradients there only for descriptors that also set QC_SWEEP_WIDE_64_PARAMS (the flavour <true> of that
+// file's walk, then qc_sweep_par_reduce_kernel of this one).
 // Wide descriptors (wide = QC_SWEEP_WIDE) extend the scope to the "mfma32-sweep" form, 2N <= 32: this file routes such handles to the
 // seed and walk kernels of qc_sweep32_grad.hip and shares its reductions (launch 4) with them; parameter gradients there only for
 // descriptors that also set QC_SWEEP_WIDE_PARAMS (the flavour <true> of that file's walk, then qc_sweep_par_reduce_kernel of this one).
@@ -494,7 +495,8 @@ void qc_sweep_launch_weighted(qc_sweep* h, int64_t S, const double* gsamp, const
 
 // "mfma32-sweep" handles made without QC_SWEEP_WIDE_PARAMS, in scope or not: the refusal of both parameter entry points
 static const char* const kNoWideParGrad = "qc_sweep gradients: parameter gradients are not served in the mfma32-sweep form";
-// "mfma64-sweep" handles made with QC_SWEEP_WIDE_64_GRAD (without it the gradient's own scope refuses, as before)
+// "mfma64-sweep" handles made with QC_SWEEP_WIDE_64_GRAD but without QC_SWEEP_WIDE_64_PARAMS (without the former the gradient's own scope
+// refuses, as before)
 static int no_par_grad64(qc_sweep* h) {
     return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, "qc_sweep gradients: parameter gradients are not served in the mfma64-sweep form (2N = " + std::to_string(h->n) + ")");
 }
@@ -547,7 +549,10 @@ static int qc_sweep_grad_launch(qc_sweep* h, const char* who, const double* dZ, 
     if (h->stored && (want_grad || want_par)) QC_SIDE_HIP(h, slot, h->grow(h->dXall, (size_t)S * (size_t)n_int * h->ns));
     qc_sweep_launch_fid_seed(h, S, n_chunks, dinit, dfids, st);
     if (h->mfma64 && h->wide64_grad) {      // the 4 x 4-tile form: its own walk (qc_sweep64_grad.hip), then the reductions below
-        if (want_grad && (rc = qc_sweep64_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, gsamp, st))) return rc;
+        if ((want_grad || want_par) &&      // want_par: only on handles with QC_SWEEP_WIDE_64_PARAMS (the entry points refuse the others)
+            (rc = qc_sweep64_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, h->dPart.p, st)))
+            return rc;
+        if (want_par) qc_sweep_launch_par_reduce(h, S, n_chunks, dgrad_theta, dgrad_scale, st);
     } else if (h->stored) {      // reserved1[0] = QC_SWEEP_STORED_STATES: the walk of qc_sweep_open_grad.hip, whatever the generators
         if (want_grad || want_par)      // (an "mfma32-sweep" handle is in scope only with QC_SWEEP_WIDE_STORED: the 2 x 2-tile walk)
             (h->mfma32 ? qc_sweep32_open_launch_walk : qc_sweep_open_launch_walk)(h, dZ, dinit, S, dtheta, dscale, chunk, n_chunks,
@@ -573,7 +578,7 @@ extern "C" int qc_sweep_grad_params_dev(qc_sweep* h, const double* dZ, const dou
                                         const double* dweights, double* dfids, double* dJ, double* dgrad, double* dgrad_samples,
                                         double* dgrad_theta, double* dgrad_scale, void* stream) {
     if (h && h->mfma32 && !h->wide_par) return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, kNoWideParGrad);
-    if (h && h->wide64_grad) return no_par_grad64(h);
+    if (h && h->wide64_grad && !h->wide64_par) return no_par_grad64(h);
     return qc_sweep_grad_launch(h, "qc_sweep_grad_params_dev", dZ, dinit, S, dtheta, dscale, dweights, dfids, dJ, dgrad, dgrad_samples, dgrad_theta,
                                 dgrad_scale, stream);
 }
@@ -613,6 +618,6 @@ extern "C" int qc_sweep_grad_params(qc_sweep* h, const double* Z, const double* 
                                     const double* weights, double* fids, double* J, double* grad, double* grad_samples, double* grad_theta,
                                     double* grad_scale) {
     if (h && h->mfma32 && !h->wide_par) return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, kNoWideParGrad);
-    if (h && h->wide64_grad) return no_par_grad64(h);
+    if (h && h->wide64_grad && !h->wide64_par) return no_par_grad64(h);
     return qc_sweep_grad_host(h, "qc_sweep_grad_params", Z, init, S, theta, scale, weights, fids, J, grad, grad_samples, grad_theta, grad_scale);
 }

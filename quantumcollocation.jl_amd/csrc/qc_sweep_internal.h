@@ -13,6 +13,7 @@ struct qc_sweep : qc_side {
     bool mfma32 = false;         // the 2 x 2-tile form of a wide descriptor ("mfma32-sweep", qc_sweep32.hip); mfma is set as well
     bool mfma64 = false;         // the 4 x 4-tile form of a descriptor with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 ("mfma64-sweep", qc_sweep64.hip): the forward sweep, and with wide64_grad its closed adjoint; mfma is set as well
     bool wide64_grad = false;    // mfma64 and wide has QC_SWEEP_WIDE_64_GRAD: gradients and pullbacks of closed systems are served (qc_sweep64_grad.hip)
+    bool wide64_par = false;     // wide64_grad and wide has QC_SWEEP_WIDE_64_PARAMS: parameter gradients and cotangents are served (the flavour <true> of qc_sweep64_grad.hip's walk)
     bool wide_par = false;       // mfma32 and wide has QC_SWEEP_WIDE_PARAMS: parameter gradients and cotangents are served (qc_sweep32_grad.hip)
     bool wide_stored = false;    // mfma32 and wide has QC_SWEEP_WIDE_STORED: with `stored`, reverse mode by the 2 x 2-tile stored-state walk (qc_sweep32_open_grad.hip)
     bool wide_tangent = false;   // mfma32 and wide has QC_SWEEP_WIDE_TANGENT: pushforwards are served (qc_sweep32_jvp.hip)
@@ -141,10 +142,12 @@ int qc_sweep32_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const dou
 __attribute__((visibility("hidden"))) void qc_sweep64_image(const double* G, int n, double* img);
 __attribute__((visibility("hidden"))) int qc_sweep64_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, hipStream_t st, int64_t* chunk,
                              int64_t* n_chunks);
-// "mfma64-sweep" handles with `wide64_grad` (qc_sweep64_grad.hip): the backward walk qc_sweep64_grad_kernel, one workgroup per (sample, chunk)
-// (gs: S x (T-1) x nd; x and lambda at the chunk ends from h->dXs / h->dLs); QC_OK or the launch's code
+// "mfma64-sweep" handles with `wide64_grad` (qc_sweep64_grad.hip): the backward walk qc_sweep64_grad_kernel<false>, one workgroup per (sample, chunk)
+// (gs: S x (T-1) x nd; x and lambda at the chunk ends from h->dXs / h->dLs), or with `par` (handles with `wide64_par`) the parameter flavour
+// <true>, which also writes the chunk shares S x n_chunks x (p + m) into `part` (gs may then be NULL); the caller runs
+// qc_sweep_launch_par_reduce behind it.  QC_OK or the launch's code
 __attribute__((visibility("hidden"))) int qc_sweep64_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk,
-                                                                  int64_t n_chunks, double* gs, hipStream_t st);
+                                                                  int64_t n_chunks, double* gs, bool par, double* part, hipStream_t st);
 // "mfma32-sweep" gradients (qc_sweep32_grad.hip): the backward walk qc_sweep32_grad_kernel<false> (gs: S x (T-1) x nd), or with `par` the
 // parameter flavour <true> (gs may be NULL) and qc_sweep_par_reduce_kernel out of h->dPart; scratch is the caller's
 void qc_sweep32_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,

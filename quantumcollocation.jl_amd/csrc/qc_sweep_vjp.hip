@@ -16,7 +16,8 @@
 //   3. the walk, when a derivative over the intervals or the parameters is asked for: flavour <M, false> without grad_theta /
 //      grad_scale, <M, true> and qc_sweep_par_reduce_kernel with either (as qc_sweep_grad_launch chooses); the wide walk likewise
 //      (qc_sweep32_grad_kernel<false> / <true>), its parameter flavour only on handles made with QC_SWEEP_WIDE_PARAMS.  "mfma64-sweep"
-//      handles made with QC_SWEEP_WIDE_64_GRAD: qc_sweep64_cot_seed_kernel (ld = 64) and qc_sweep64_grad_kernel, no parameter cotangents.
+//      handles made with QC_SWEEP_WIDE_64_GRAD: qc_sweep64_cot_seed_kernel (ld = 64) and qc_sweep64_grad_kernel<false>; parameter cotangents
+//      (its flavour <true>, then qc_sweep_par_reduce_kernel) only on handles that also set QC_SWEEP_WIDE_64_PARAMS.
 //      With m = 0 and a fixed timestep there is nothing per interval: only <1, true> runs, and only for grad_theta.
 //   4. qc_sweep_vjp_reduce_kernel: grad = sum_s dphi_s/dZ, the PLAIN sum in ascending s (qc_sweep_grad_reduce_kernel reads a missing
 //      weight vector as 1/S each); +0.0 at every entry that is not a control or timestep of knots 0 .. T-2.
@@ -121,7 +122,7 @@ int vjp_check(qc_sweep* h, const char* who, const void* Z, const void* init, int
     if (g_theta && h->d.n_pert == 0) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "grad_theta is given but the handle has no perturbations (n_pert = 0)");
     if (g_scale && h->d.m == 0) return qc_sweep_fail(h, QC_ERR_INVALID, pre + "grad_scale is given but the handle has no drives (m = 0)");
     if ((g_theta || g_scale) && h->mfma32 && !h->wide_par) return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, kNoWidePar);
-    if ((g_theta || g_scale) && h->wide64_grad)
+    if ((g_theta || g_scale) && h->wide64_grad && !h->wide64_par)
         return qc_sweep_fail(h, QC_ERR_UNSUPPORTED, "qc_sweep pullback: parameter cotangents are not served in the mfma64-sweep form (2N = " + std::to_string(h->n) + ")");
     return QC_OK;
 }
@@ -188,7 +189,10 @@ static int qc_sweep_vjp_launch(qc_sweep* h, const char* who, const double* dZ, c
     hipLaunchKernelGGL(seed, dim3((unsigned)S), dim3(kCotT), lds, st, F, (const double*)h->dTot.p, dinit, dcot, h->dXs.p, h->dLs.p, dfinals,
                        dgrad_init);
     if (h->mfma64 && h->wide64_grad) {      // the 4 x 4-tile walk of qc_sweep64_grad.hip behind the seed at ld = 64
-        if (want_grad && (rc = qc_sweep64_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, gsamp, st))) return rc;
+        if ((want_grad || want_par) &&      // want_par: only on handles with QC_SWEEP_WIDE_64_PARAMS (vjp_check refuses the others)
+            (rc = qc_sweep64_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, h->dPart.p, st)))
+            return rc;
+        if (want_par) qc_sweep_launch_par_reduce(h, S, n_chunks, dgrad_theta, dgrad_scale, st);
     } else if (h->stored) {      // reserved1[0] = QC_SWEEP_STORED_STATES: the walk of qc_sweep_open_grad.hip behind the same seed
         if (want_grad || want_par)      // (an "mfma32-sweep" handle is in scope only with QC_SWEEP_WIDE_STORED: qc_sweep32_open_grad.hip)
             (h->mfma32 ? qc_sweep32_open_launch_walk : qc_sweep_open_launch_walk)(h, dZ, dinit, S, dtheta, dscale, chunk, n_chunks,

@@ -742,13 +742,14 @@ class SweepInfidelityObjective:
     wide_noise  as `RolloutSweep` (only with `wide`): what `SweepNoiseInfidelityObjective` needs in the "mfma32-sweep" form; nothing here reads it
     wide64, wide64_grad  as `RolloutSweep` (only with `wide`; `wide64_grad` only with `wide64`): all three True serve closed systems of
                 32 < 2N <= 64 (17 .. 32 levels: three coupled transmons, 5 qubits) in the "mfma64-sweep" form
+    wide64_params  as `RolloutSweep` (only with `wide64_grad`): the handle also serves `param_grad` and parameter cotangents there
     goal_ket    density component only: [Re psi; Im psi] (2 levels entries) of the pure state the fidelity compares with"""
     _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
 
     def __init__(self, traj: NamedTrajectory, system, perturbations, theta, scale=None, weights=None, state_name: str = "Ũ⃗",
                  control_name: str = "a", subspace=None, form: str = "abs", device: int = 0, wide: bool = False,
                  stored_states: bool = False, goal_ket=None, wide_stored: bool = False, wide_noise: bool = False, wide64: bool = False,
-                 wide64_grad: bool = False):
+                 wide64_grad: bool = False, wide64_params: bool = False):
         from .rollouts import RolloutSweep
         self._sweep = None
         if state_name not in traj.components:
@@ -800,7 +801,8 @@ class SweepInfidelityObjective:
                           subspace=subspace, fid_form=_lib.QC_FID_FORM_ABS2 if form == "abs2" else _lib.QC_FID_FORM_ABS, zdim=traj.dim,
                           off_a=traj.offset(control_name), off_dt=traj.offset(traj.timestep) if free else -1,
                           dt_fixed=None if free else float(traj.timestep), global_dim=traj.global_dim, device=device, wide=wide,
-                          stored_states=stored_states, wide_stored=wide_stored, wide_noise=wide_noise, wide64=wide64, wide64_grad=wide64_grad)
+                          stored_states=stored_states, wide_stored=wide_stored, wide_noise=wide_noise, wide64=wide64, wide64_grad=wide64_grad,
+                          wide64_params=wide64_params)
         self._sweep = sw
         self.stored_states = sw.stored_states
         self.wide_stored = sw.wide_stored
@@ -923,12 +925,13 @@ class SweepFinalStateObjective:
     wide_hessian  as `RolloutSweep` (only with `wide`): the Hessian product in the "mfma32-sweep" form.  `hessian_times` there needs
                 `wide_tangent` as well (one `jvp_device`, one `hvp_device`); with one of the two it raises the handle's reason
     wide64, wide64_grad  as `RolloutSweep` (only with `wide`; `wide64_grad` only with `wide64`): all three True serve closed systems of
-                32 < 2N <= 64 in the "mfma64-sweep" form, gradients only (`gauss_newton_times` and `hessian_times` raise the handle's reason)"""
+                32 < 2N <= 64 in the "mfma64-sweep" form, gradients only (`gauss_newton_times` and `hessian_times` raise the handle's reason)
+    wide64_params  as `RolloutSweep` (only with `wide64_grad`): the handle also serves `param_grad` and parameter cotangents there"""
     _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
 
     def __init__(self, traj: NamedTrajectory, system, perturbations, theta, loss, scale=None, state_name="Ũ⃗", control_name: str = "a",
                  device: int = 0, wide: bool = False, stored_states: bool = False, wide_stored: bool = False, wide_tangent: bool = False,
-                 wide_hessian: bool = False, wide64: bool = False, wide64_grad: bool = False):
+                 wide_hessian: bool = False, wide64: bool = False, wide64_grad: bool = False, wide64_params: bool = False):
         from .rollouts import RolloutSweep, _sweep_samples
         self._sweep = None
         if not callable(loss):
@@ -955,7 +958,8 @@ class SweepFinalStateObjective:
         sw = RolloutSweep(system, perturbations, traj.T, cols=cols, zdim=traj.dim, off_a=traj.offset(control_name),
                           off_dt=traj.offset(traj.timestep) if free else -1, dt_fixed=None if free else float(traj.timestep),
                           global_dim=traj.global_dim, device=device, wide=wide, stored_states=stored_states, wide_stored=wide_stored,
-                          wide_tangent=wide_tangent, wide_hessian=wide_hessian, wide64=wide64, wide64_grad=wide64_grad)
+                          wide_tangent=wide_tangent, wide_hessian=wide_hessian, wide64=wide64, wide64_grad=wide64_grad,
+                          wide64_params=wide64_params)
         self._sweep = sw
         self.wide_hessian = sw.wide_hessian
         self.stored_states = sw.stored_states

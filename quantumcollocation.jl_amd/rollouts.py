@@ -245,15 +245,22 @@ class RolloutSweep:
                    columns: a full unitary of 32 levels fits) also serves `grad`, `vjp`, their device forms and the backward rule of
                    `finals_autograd`, by the closed adjoint walk on 4 x 4 tiles.  `param_grad`, the `params` of `vjp`, `stored_states`,
                    `jvp`, `hvp` and the noise sweeps still refuse there, naming the form.  Nothing else changes, nothing changes at
-                   2N <= 32, and nothing changes without it."""
+                   2N <= 32, and nothing changes without it.
+    wide64_params  True (only with `wide64_grad`): such a handle also serves `param_grad`, `param_grad_device`, the `params` of `vjp` and
+                   the theta / scale cotangents of `finals_autograd`, by the parameter flavour of the same walk: one call gives
+                   dF_s/dtheta and dF_s/dscale of every sample (dF_s/dscale is taken before the factor scale, so it is defined at
+                   scale = 0).  `stored_states`, `jvp`, `hvp` and the noise sweeps still refuse there.  Without it `param_grad` and
+                   the `params` of `vjp` refuse there, as they did; nothing else changes, and nothing changes at 2N <= 32."""
 
     def __init__(self, system, perturbations, T: int, cols: Optional[int] = None, goal=None, fid_kind=None, subspace=None,
                  fid_form: int = _lib.QC_FID_FORM_ABS, zdim: Optional[int] = None, off_a: int = 0, off_dt: Optional[int] = None,
                  dt_fixed: Optional[float] = None, global_dim: int = 0, device: int = 0, wide: bool = False,
                  stored_states: bool = False, wide_params: bool = False, wide_stored: bool = False, wide_tangent: bool = False,
-                 wide_noise: bool = False, wide_hessian: bool = False, wide64: bool = False, wide64_grad: bool = False):
+                 wide_noise: bool = False, wide_hessian: bool = False, wide64: bool = False, wide64_grad: bool = False,
+                 wide64_params: bool = False):
         self._h = None
         flags = (   # (keyword, given, its bit of qc_sweep_desc.wide, what it needs, the refusal without that)
+            ("wide64_params", wide64_params, _lib.QC_SWEEP_WIDE_64_PARAMS, wide64_grad, "wide64_params=True needs wide64_grad=True"),
             ("wide64_grad", wide64_grad, _lib.QC_SWEEP_WIDE_64_GRAD, wide64, "wide64_grad=True needs wide64=True"),
             ("wide64", wide64, _lib.QC_SWEEP_WIDE_64, wide, "wide64=True needs wide=True"),
             ("wide_hessian", wide_hessian, _lib.QC_SWEEP_WIDE_HESSIAN, wide, "wide_hessian=True needs wide=True"),
@@ -319,6 +326,15 @@ class RolloutSweep:
     @wide64_grad.setter
     def wide64_grad(self, given):
         self._wide64_grad = bool(given)
+
+    @property
+    def wide64_params(self) -> bool:
+        """Whether the handle was made with `wide64_params` (kept outside the instance's public flags, as `wide64_grad` is)."""
+        return self._wide64_params
+
+    @wide64_params.setter
+    def wide64_params(self, given):
+        self._wide64_params = bool(given)
 
     def _scope(self, supported):
         """(served?, the library's reason why not or None) from a `qc_sweep_desc_*_supported` function."""
@@ -486,8 +502,8 @@ class RolloutSweep:
     # -- gradients with respect to the systems: dF_s/dtheta and dF_s/dscale ---------------------------------------------------
     def param_grad(self, Z, init, theta, scale=None, weights=None, with_controls: bool = False):
         """(fids, grad_theta, grad_scale): the S fidelities, dF_s/dtheta[s, j] (S x n_pert) and dF_s/dscale[s, k] (S x m; `scale`
-        None: taken at all ones), raw per-sample values from one backward walk (`qc_sweep_grad_params`; "mfma16-sweep" handles, and
-        "mfma32-sweep" handles made with `wide_params`).  With `with_controls`:
+        None: taken at all ones), raw per-sample values from one backward walk (`qc_sweep_grad_params`; "mfma16-sweep" handles,
+        "mfma32-sweep" handles made with `wide_params` and "mfma64-sweep" handles made with `wide64_params`).  With `with_controls`:
         (J, fids, grad, grad_theta, grad_scale), J and the dense gradient over the trajectory vector as `grad` returns them."""
         Z, init = self._host_Z_init(Z, init)
         S, theta, scale = self._samples(theta, scale)
@@ -534,8 +550,8 @@ class RolloutSweep:
         by what was asked for:
             per_sample   grad_samples, S x (T-1) x n_deriv: dphi_s/d(a_t, dt_t)
             init_grad    grad_init, S x (2N cols): dphi_s/dinit
-            params       grad_theta (S x n_pert) and grad_scale (S x m), two entries ("mfma16-sweep" handles, and "mfma32-sweep" handles made
-                         with `wide_params`)."""
+            params       grad_theta (S x n_pert) and grad_scale (S x m), two entries ("mfma16-sweep" handles, "mfma32-sweep" handles made
+                         with `wide_params` and "mfma64-sweep" handles made with `wide64_params`)."""
         Z, init = self._host_Z_init(Z, init)
         S, theta, scale = self._samples(theta, scale)
         cot = np.ascontiguousarray(cot, dtype=np.float64)
@@ -779,8 +795,8 @@ class RolloutSweep:
         `vjp_device` call, and under `torch.autograd.forward_ad` the tangent is one `jvp_device` call ("mfma16-sweep" handles, and "mfma32-sweep" handles made with `wide_tangent`).  dZ
         (Z_len), dinit (2N cols), dtheta (S x n_pert), dscale (S x m or None) are float64 CUDA tensors; whichever requires grad
         receives one: Z the plain sum over the samples, init the sum of the per-sample derivatives, theta and scale their per-sample
-        values ("mfma16-sweep" handles, and "mfma32-sweep" handles made with `wide_params`: on a wide handle made without it a theta or
-        scale that requires grad raises in backward)."""
+        values ("mfma16-sweep" handles, "mfma32-sweep" handles made with `wide_params` and "mfma64-sweep" handles made with
+        `wide64_params`: on a wide handle made without it a theta or scale that requires grad raises in backward)."""
         if dtheta is None and dscale is None:
             raise ValueError("dtheta (S x n_pert) or dscale (S x m) must give the number of samples")
         S = (dtheta if dtheta is not None else dscale).shape[0]
@@ -894,14 +910,16 @@ def rollout_noise_sweep(init, controls, dts, system, perturbations, noise, theta
 
 def rollout_sweep_parameter_gradient(init, controls, dts, system, perturbations, theta, scale=None, cols: Optional[int] = None, goal=None,
                                      fid_kind="unitary", subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS,
-                                     stored_states: bool = False, wide: bool = False, wide_stored: bool = False):
+                                     stored_states: bool = False, wide: bool = False, wide_stored: bool = False, wide64: bool = False,
+                                     wide64_grad: bool = False, wide64_params: bool = False):
     """(fids, grad_theta, grad_scale) of S rollouts under the perturbed systems: the fidelities of `rollout_sweep` and their derivatives
     with respect to theta (S x len(perturbations)) and scale (S x n_drives; None: taken at all ones).  Arguments as `rollout_sweep`;
     `stored_states=True` serves open systems (`RolloutSweep`); `wide=True` serves 16 < 2N <= 32 on the matrix cores (the handle is made
-    with `wide` and `wide_params`); all three of `wide`, `stored_states` and `wide_stored` serve open systems there (wide = 11)."""
+    with `wide` and `wide_params`); all three of `wide`, `stored_states` and `wide_stored` serve open systems there (wide = 11);
+    all four of `wide`, `wide64`, `wide64_grad` and `wide64_params` serve closed systems of 32 < 2N <= 64 ("mfma64-sweep")."""
     return _one_shot(RolloutSweep.param_grad, init, controls, dts, system, perturbations, (theta, scale), cols, goal=goal, fid_kind=fid_kind,
                      subspace=subspace, fid_form=fid_form, device=device, stored_states=stored_states, wide=wide, wide_params=wide,
-                     wide_stored=wide_stored)
+                     wide_stored=wide_stored, wide64=wide64, wide64_grad=wide64_grad, wide64_params=wide64_params)
 
 
 def _traj_dts(traj):
