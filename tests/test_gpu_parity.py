@@ -21,7 +21,7 @@ def assert_close(got, ref, what=""):
     np.testing.assert_allclose(got, ref, rtol=RTOL, atol=1e-12 * scale, err_msg=what)
 
 
-def dynamics_from_problem(qc, prob, kernel="auto", t_range=None):
+def dynamics_from_problem(qc, prob, kernel="auto", t_range=None, hess_align=0):
     """Build a handle straight from an oracle Problem through the raw C descriptor (no host mirror)."""
     import ctypes as C
     L = qc._lib
@@ -40,6 +40,7 @@ def dynamics_from_problem(qc, prob, kernel="auto", t_range=None):
     d.kernel = {"auto": L.QC_KERNEL_AUTO, "lds": L.QC_KERNEL_LDS, "mfma": L.QC_KERNEL_MFMA}[kernel]
     if t_range:
         d.t_begin, d.t_end = t_range
+    d.hess_align = hess_align
     h = C.c_void_p()
     L.check(L.lib.qc_create(C.byref(d), C.byref(h)))
     dims = L.qc_dims_t()

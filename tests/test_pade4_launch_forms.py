@@ -244,8 +244,18 @@ def build(qc, oracle, case):
     return prob, Z, h.h, h.dims, SimpleNamespace(_desc=desc, dims=h.dims), h.close
 
 
-def check_case(qc, oracle, coracle, case):
-    prob, Z, h, dims, like, close = build(qc, oracle, case)
+def form_text(case):
+    (jf, jg), (ff, fg), hf = case.forms()
+    return f"F + dF {jf} on {jg} workgroups; F alone {ff} on {fg}; mu_d2F {hf[0]} on {hf[-2] if len(hf) > 2 else hf[1]}"
+
+
+def check_case(qc, oracle, coracle, case, make=None, with_dF=True, F_bits=True, twice=False, one_call_bits=False, form=form_text, tag="PADE4-FORMS"):
+    """The launches of one case against the C oracle.  What tests/test_pade_other_launch_forms.py chooses (the defaults: this file):
+    `make(qc, oracle, case)` in place of build(); with_dF = False: F alone and mu_d2F only (no dF vector is allocated); F_bits = False:
+    a family whose residual-only launch does not promise the bits of F + dF's residuals (both are compared with the oracle); twice:
+    mu_d2F a second time on the same handle, the bits of the first; one_call_bits: the one call's mu_d2F equals the launch's in every
+    bit, the (a, a) block included; form(case): the form's part of the printed line."""
+    prob, Z, h, dims, like, close = (make or build)(qc, oracle, case)
     try:
         L = qc._lib
         what = case.id
@@ -255,34 +265,53 @@ def check_case(qc, oracle, coracle, case):
         want = case.names()
         assert names[:2] == want[:2] and (want[2] is None or names[2] == want[2]), (what, names, want)
         ref = coracle.COracle(prob)
-        assert (int(dims.ddim), int(dims.jac_nnz_interval), int(dims.hess_nnz_interval)) == (ref.ddim, ref.jac_nnz, ref.hess_nnz), what
+        assert (int(dims.ddim), int(dims.jac_nnz_interval), int(dims.hess_nnz_interval)) == (ref.ddim, ref.jac_nnz, ref.hess_nnz + ref.hess_pad), what
         mu = np.random.default_rng(n_int + case.m).standard_normal(prob.n_rows)
         dZ, dmu = torch.from_numpy(Z).cuda(), torch.from_numpy(mu).cuda()
         pZ, pmu = C.c_void_p(dZ.data_ptr()), C.c_void_p(dmu.data_ptr())
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         # F + dF, F alone (dvals = NULL), mu_d2F alone
-        F, J, F1, H = Guarded(dims.F_len), Guarded(dims.jac_nnz), Guarded(dims.F_len), Guarded(dims.hess_nnz)
-        L.check(L.lib.qc_eval_F_jac_dev(h, pZ, F.ptr(), J.ptr(), st), h)
+        F1, H = Guarded(dims.F_len), Guarded(dims.hess_nnz)
+        Fr = ref.F_dF(Z, 0, n_int, True, False)[0]
+        eJ, J, Jv = 0.0, None, None
+        if with_dF:
+            F, J = Guarded(dims.F_len), Guarded(dims.jac_nnz)
+            L.check(L.lib.qc_eval_F_jac_dev(h, pZ, F.ptr(), J.ptr(), st), h)
         L.check(L.lib.qc_eval_F_jac_dev(h, pZ, F1.ptr(), None, st), h)
         L.check(L.lib.qc_eval_hess_dev(h, pZ, pmu, H.ptr(), st), h)
-        Fr = ref.F_dF(Z, 0, n_int, True, False)[0]
-        eF, Fv = compare(F, n_int, lambda a, b: Fr, assert_close, what + ": F")
-        eJ, Jv = compare(J, n_int, lambda a, b: ref.F_dF(Z, a, b, False, True)[1], assert_close, what + ": dF")
-        _, F1v = compare(F1, n_int, lambda a, b: Fr, assert_close, what + ": F alone")
-        assert np.array_equal(F1v, Fv), f"{what}: F alone differs from the F of F + dF in {(F1v != Fv).sum()} values, first at {np.flatnonzero(F1v != Fv)[:5]}"
+        if with_dF:
+            eF, Fv = compare(F, n_int, lambda a, b: Fr, assert_close, what + ": F")
+            eJ, Jv = compare(J, n_int, lambda a, b: ref.F_dF(Z, a, b, False, True)[1], assert_close, what + ": dF")
+        eF1, F1v = compare(F1, n_int, lambda a, b: Fr, assert_close, what + ": F alone")
+        if not with_dF:
+            eF, Fv = eF1, F1v
+        elif F_bits:
+            assert np.array_equal(F1v, Fv), f"{what}: F alone differs from the F of F + dF in {(F1v != Fv).sum()} values, first at {np.flatnonzero(F1v != Fv)[:5]}"
         eH, Hv = compare(H, n_int, lambda a, b: ref.mu_d2F(Z, mu, a, b), assert_close_h, what + ": mu_d2F")
-        del J, H
-        (jf, jg), (ff, fg), hf = case.forms()
-        print(f"PADE4-FORMS {what}: kernels {names[0]} / {names[1]} / {names[2]}; intervals {n_int}; F + dF {jf} on {jg} workgroups; "
-              f"F alone {ff} on {fg}; mu_d2F {hf[0]} on {hf[-2] if len(hf) > 2 else hf[1]}; worst rel. error F {eF:.2e} dF {eJ:.2e} mu_d2F {eH:.2e}")
+        if twice:      # (a kernel that keeps per-workgroup scratch between its trips: the second launch starts from what the first left)
+            assert Hv is not None
+            H.t.fill_(float("nan"))
+            L.check(L.lib.qc_eval_hess_dev(h, pZ, pmu, H.ptr(), st), h)
+            Hw = H.result(what + ": mu_d2F, second launch")
+            assert np.array_equal(Hw, Hv), f"{what}: the second mu_d2F launch differs from the first in {(Hw != Hv).sum()} values, first at {np.flatnonzero(Hw != Hv)[:5]}"
+        del H
+        print(f"{tag} {what}: kernels {names[0]} / {names[1]} / {names[2]}; intervals {n_int}; {form(case)}; "
+              f"worst rel. error F {max(eF, eF1):.2e} dF {eJ:.2e} mu_d2F {eH:.2e}")
         if names[2] != "two-launches":      # the one call against the two launches (each compared with the oracle above)
-            assert Jv is not None
+            assert with_dF and Hv is not None
             F2, J2, H2 = Guarded(dims.F_len), Guarded(dims.jac_nnz), Guarded(dims.hess_nnz)
             L.check(L.lib.qc_eval_F_jac_hess_dev(h, pZ, pmu, F2.ptr(), J2.ptr(), H2.ptr(), st), h)
-            F2v, J2v, H2v = F2.result(what + ": one call, F"), J2.result(what + ": one call, dF"), H2.result(what + ": one call, mu_d2F")
+            F2v, H2v = F2.result(what + ": one call, F"), H2.result(what + ": one call, mu_d2F")
             assert_close(F2v, Fv, what + ": one call, F")
-            assert np.array_equal(J2v, Jv), f"{what}: one call, dF differs from the dF launch in {(J2v != Jv).sum()} values"
+            if Jv is not None:
+                J2v = J2.result(what + ": one call, dF")
+                assert np.array_equal(J2v, Jv), f"{what}: one call, dF differs from the dF launch in {(J2v != Jv).sum()} values"
+            else:      # both vectors stayed on the device; the launch's values were found finite above, so bitwise equality is torch.equal
+                compare(J2, n_int, lambda a, b: ref.F_dF(Z, a, b, False, True)[1], assert_close, what + ": one call, dF")
+                assert torch.equal(J2.t, J.t), f"{what}: one call, dF differs from the dF launch in {int((J2.t != J.t).sum())} values"
             assert_same_hessian_values(H2v, Hv, like, what + ": one call against two launches")
+            if one_call_bits:
+                assert np.array_equal(H2v, Hv), f"{what}: one call, mu_d2F differs from the mu_d2F launch in {(H2v != Hv).sum()} values"
             assert_close_h(H2v, ref.mu_d2F(Z, mu), what + ": one call, mu_d2F")
     finally:
         close()
