@@ -53,11 +53,13 @@ def rule64(spec, S):
     return t64.launch64(2 * spec[1], spec[2], S, spec[7], WIDE)
 
 
-def build_rows(qc, name):
-    """`te.build_rows`; the two-column rows keep the first two of the three kets and draw cotangents of that size."""
-    if name in TABLE:
-        return te.build_rows(qc, name, TABLE)
-    rows = te.build_rows(qc, name, KETS2)
+def build_rows(qc, name, table=None, kets2=None):
+    """`te.build_rows`; the two-column rows keep the first two of the three kets and draw cotangents of that size.  `table`, `kets2`:
+    another file's cases and their twins."""
+    table, kets2 = TABLE if table is None else table, KETS2 if kets2 is None else kets2
+    if name in table:
+        return te.build_rows(qc, name, table)
+    rows = te.build_rows(qc, name, kets2)
     n = rows["n"]
     rows["init"], rows["cols"] = np.ascontiguousarray(rows["init"][:2 * n]), 2
     rows["cot"] = tv.unit_cotangents(np.random.default_rng(7 + sum(map(ord, name))), R, 2 * n)

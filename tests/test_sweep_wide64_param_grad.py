@@ -13,7 +13,10 @@ returns sums, not terms, so pullback outputs are held to the rule of test_sweep_
 (max |want_s| <= A_s).  Measured worst ratios: DESIGN.md 5.8.13 and profiles/sweep_wide64_param_summary.txt.
 
 The case "chunks" (S = 3, T = 26) runs five chunks of five intervals a sample, the last one full; ragged last chunks are "chunks-ragged"
-(T = 12: 3, 3, 3, 2), the squaring cases (the same) and the bits test (T = 27: five chunks of 5 and one of 1)."""
+(T = 12: 3, 3, 3, 2), the squaring cases (the same) and the bits test (T = 27: five chunks of 5 and one of 1).  "no-drives-free-dt"
+(m = 0 with a free timestep: nd = 1, the perturbations in lanes 1 and 2) and "subspace-abs2" (a unitary fidelity on levels 0, 1, 3, 4 in
+the squared form) are lane maps and a seed no other case here reaches.  Every sample of launches of 250 .. 510 workgroups with several
+chunks of several intervals: tests/test_sweep_wide64_params_every_sample.py."""
 import ctypes as C
 import inspect
 import os
@@ -41,7 +44,8 @@ HANDLE = dict(wide=True, wide64=True, wide64_grad=True, wide64_params=True)
 HANDLE_G = dict(wide=True, wide64=True, wide64_grad=True)
 FORM = "64par"                    # the key of test_sweep_vjp.reference's cache for this file's pullback cases
 
-# name: (levels, state columns, m, p, free timestep, S, T, fidelity kind or None, scale: None | "given" | (sample, drive) of an exact zero)
+# name: (levels, state columns, m, p, free timestep, S, T, fidelity kind (full space, "abs") | (kind, subspace, form) | None,
+#        scale: None | "given" | (sample, drive) of an exact zero)
 CASES = {
     "pad": (17, 17, 2, 1, True, 3, 6, "unitary", (1, 0)),                   # zero padding to 64, second column tile with one live column
     "full": (32, 32, 3, 2, False, 2, 4, "unitary", (0, 2)),                 # no padding, nd = m
@@ -51,6 +55,8 @@ CASES = {
     "chunks": (17, 8, 2, 2, True, 3, 26, None, "given"),                    # five chunks a sample
     "chunks-ragged": (17, 8, 2, 2, True, 3, 12, None, (2, 1)),              # chunks of 3, 3, 3, 2
     "one-interval-chunks": (17, 8, 2, 1, True, 5, 3, None, "given"),        # two chunks of one interval: the chunk loop runs once
+    "no-drives-free-dt": (17, 8, 0, 2, True, 2, 4, None, None),             # nd = 1: lane 0 is the timestep's, perturbations in lanes 1, 2; lane < m never
+    "subspace-abs2": (17, 17, 2, 2, True, 3, 6, ("unitary", [0, 1, 3, 4], "abs2"), "given"),      # the fidelity's seed on a subspace, squared form
 }
 _BUILT = {}
 
@@ -60,7 +66,8 @@ def case(qc, name):
     theta = 0."""
     if name in _BUILT:
         return _BUILT[name]
-    N, nc, m, p, free, S, T, kind, sc = CASES[name]
+    N, nc, m, p, free, S, T, fid, sc = CASES[name]
+    kind, subspace, form = fid if isinstance(fid, tuple) else (fid, None, "abs")
     rng = np.random.default_rng(640 + sum(map(ord, name)))
     H0 = _herm(rng, N)
     Hd = [_herm(rng, N, (N * max(m, 1)) ** -0.5) for _ in range(m)]
@@ -83,7 +90,7 @@ def case(qc, name):
     c = dict(name=("" if kind is None else "w64par/") + name, L=N, N=N, n=2 * N, m=m, p=p, S=S, T=T,
              system=qc.QuantumSystem(H0, Hd) if qc is not None else None, perts=perts, G0=ref.iso_generator(H0),
              Gd=[ref.iso_generator(H) for H in Hd], Gp=[ref.iso_generator(P) for P in perts], init=init, cols=nc, goal=goal, kind=kind,
-             subspace=None, form="abs", controls=rng.uniform(-1, 1, (m, T)), dts=rng.uniform(0.1, 0.3, T) if free else 0.2, theta=theta,
+             subspace=subspace, form=form, controls=rng.uniform(-1, 1, (m, T)), dts=rng.uniform(0.1, 0.3, T) if free else 0.2, theta=theta,
              scale=scale, samples=list(range(S)), zero=sc if isinstance(sc, tuple) else None)
     c["cot"] = tv.unit_cotangents(rng, S, init.size)
     _BUILT[name] = c
@@ -240,9 +247,15 @@ def test_wide64_param_grad_matches_the_reference(qc, name):
             assert sw.n_deriv + sw.p == 25
         if name == "ket":
             assert sw.p == qc._lib.QC_MAX_PERT == 8
+        if name == "no-drives-free-dt":
+            assert (sw.m, sw.n_deriv, sw.p) == (0, 1, 2)
+        if name == "subspace-abs2":
+            assert (c["subspace"], c["form"]) == ([0, 1, 3, 4], "abs2")
         if c["kind"] is not None:
             assert sw.grad_supported
             Z, fids, gth, gsc = _check_fidelity_case(qc, c, sw)
+            if name == "subspace-abs2":        # |tr|^2 / 16 of a 4-level block of a random 17-level unitary is small: still 10^6 bounds
+                assert np.abs(gth).max() > 1e-3 and np.abs(gsc).max() > 1e-3
         else:
             assert not sw.grad_supported and "no fidelity" in sw.grad_unsupported_reason
             out = tv.check_case(sw, c, form=FORM, params=True)

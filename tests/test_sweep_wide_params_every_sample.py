@@ -58,12 +58,12 @@ def check_params(qc, sw, rows, c, what):
     return o
 
 
-def check_vjp_params(sw, rows, c, what):
-    """One `vjp_device` call with every output, the parameter cotangents among them."""
+def check_vjp_params(sw, rows, c, what, form="32"):
+    """One `vjp_device` call with every output, the parameter cotangents among them.  `form`: the key of `tv.reference`'s cache."""
     cls = c["cls"]
     Z = sw.pack(c["controls"], c["dts"])
     out = tv.device_call(sw, Z, c, list(tv.OUTPUTS))
-    r = tv.reference(rows, "32")
+    r = tv.reference(rows, form)
     for k in ("grad_samples", "grad_theta", "grad_scale"):
         tes.every_sample(tv.assert_samples, out[k], r[k][cls], cls, f"{what} {k}")
     tes.every_sample(tv.assert_init, out["grad_init"], r["grad_init"][cls], cls, f"{what} grad_init")
