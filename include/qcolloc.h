@@ -651,7 +651,7 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * chunk rule with that item's fill constant (n_chunks = 1 once S >= 256, one workgroup per compute unit; else ceil(256 / S) chunks, at
  * most ceil(sqrt(T-1))).  The mathematics is the family's.  That form serves the FORWARD sweep only, qc_sweep_eval*: final states
  * and fidelities.  qc_sweep_grad*, qc_sweep_grad_params*, qc_sweep_vjp*, qc_sweep_jvp*, qc_sweep_hvp* and qc_sweep_noise_* return
- * QC_ERR_UNSUPPORTED on such a handle, whatever bits 1 .. 8 say (bit 11, below, adds gradients and pullbacks), and the qc_sweep_desc_*_supported queries answer 0 with a reason
+ * QC_ERR_UNSUPPORTED on such a handle, whatever bits 1 .. 8 say (bit 11, below, adds gradients and pullbacks, bit 14 pushforwards), and the qc_sweep_desc_*_supported queries answer 0 with a reason
  * that names the form and the size ("... the mfma64-sweep form (2N = 54) ...").  Descriptors with 2N <= 32 ignore the bit completely:
  * form, launch, kernel name, every *_supported answer and every output bit are those of the same descriptor without it.  Without the
  * bit nothing changes anywhere.  Not in that form: more than 16 drives (rollout-per-sample), a state-action form that skips the
@@ -661,16 +661,26 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * grad_samples, grad_init) of CLOSED systems -- antisymmetric generators, the same 64-eps test -- with states of up to 32 columns, by the
  * closed adjoint walk on 4 x 4 tiles (qc_sweep64_grad.hip; one workgroup per (sample, chunk), the forward form's chunk rule).  The
  * fidelities and final states carry the bits of qc_sweep_eval on the same handle.  Still QC_ERR_UNSUPPORTED there, with a reason that
- * names the form and 2N: parameter gradients and parameter cotangents, reserved1[0] = QC_SWEEP_STORED_STATES, qc_sweep_jvp*,
- * qc_sweep_hvp* and qc_sweep_noise_*.  Form, launch, kernel name and every output bit of qc_sweep_eval* are those of the same descriptor
+ * names the form and 2N: parameter gradients and parameter cotangents, reserved1[0] = QC_SWEEP_STORED_STATES, qc_sweep_jvp* (served
+ * with bit 14, below), qc_sweep_hvp* and qc_sweep_noise_*.  Form, launch, kernel name and every output bit of qc_sweep_eval* are those of the same descriptor
  * without the bit; descriptors with 2N <= 32 ignore it completely, as they ignore bit 10.
  * Bit 13, QC_SWEEP_WIDE_64_PARAMS (any valid value that has bits 0, 10 and 11, | 8192; without all three of them QC_ERR_INVALID; bit 12
  * is not assigned), changes one thing only: such a handle then also serves qc_sweep_grad_params* (grad_theta, grad_scale) and the
  * grad_theta / grad_scale of qc_sweep_vjp*, in the scope of bit 11, by the parameter flavour of the same walk (per (sample, chunk) the
  * p + m chunk shares in a fixed order, then the reduction of the smaller forms; no atomics).  The other outputs of a parameter call carry
  * the bits of qc_sweep_grad / qc_sweep_vjp on the same handle, and a call without parameter outputs launches exactly what it launched
- * without the bit.  The stored-state flag, qc_sweep_jvp*, qc_sweep_hvp* and qc_sweep_noise_* stay QC_ERR_UNSUPPORTED there; descriptors
- * with 2N <= 32 ignore the bit completely.
+ * without the bit.  The stored-state flag, qc_sweep_jvp* (served with bit 14), qc_sweep_hvp* and qc_sweep_noise_* stay QC_ERR_UNSUPPORTED
+ * there; descriptors with 2N <= 32 ignore the bit completely.
+ * Bit 14, QC_SWEEP_WIDE_64_TANGENT (any valid value that has bits 0 and 10, | 16384; without both of them QC_ERR_INVALID; it needs
+ * neither bit 11 nor bit 13, because nothing is reversed), changes one thing only: an "mfma64-sweep" handle then also serves qc_sweep_jvp*
+ * (finals, fids, tfinals, tfids along vZ, vinit, vtheta, vscale) with ANY generators, Lindblad ones included (N = 25: 2N = 50), any
+ * fid_kind, for states of ns = 2N x state_cols <= 2048 entries -- every full unitary of the form (N = 32: 2048), and more columns than
+ * reverse mode's 32 below the bound (N = 17 with 33 columns) -- by the paired exponential on 4 x 4 tiles (qc_sweep64_jvp.hip; one
+ * workgroup per (sample, chunk), the forward form's chunk rule) and the finish kernel of qc_sweep_jvp.hip at ld = 64, whose LDS sets the
+ * bound; above it QC_ERR_UNSUPPORTED with a reason that names the form, 2N and ns.  finals / fids carry the bits of qc_sweep_eval on the
+ * same handle.  With bits 11 and 13 as well the pullback and the pushforward together give Gauss-Newton products.  qc_sweep_hvp*,
+ * qc_sweep_noise_* and the stored-state flag stay QC_ERR_UNSUPPORTED there.  Form, launch, kernel name, every other *_supported answer and
+ * every other entry point's output are those of the same descriptor without the bit; descriptors with 2N <= 32 ignore it completely.
  * reserved1[0] = QC_SWEEP_STORED_STATES chooses reverse mode by the STORED-STATE walk: qc_sweep_grad*, qc_sweep_grad_params* and
  * qc_sweep_vjp* then keep the forward states x_0 .. x_{T-2} of every sample in handle scratch (S x (T-1) x 2N x cols doubles) and read
  * them on the way back instead of reversing the step, which serves ANY generators in the "mfma16-sweep" form: Lindblad generators
@@ -688,7 +698,8 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * Derivatives of the final states themselves, contracted with cotangents the caller chooses (qc_sweep_vjp*, below), carry any function
  * of the final states: leakage, the free-phase fidelity, several kets at once, a loss written elsewhere.
  * The forward-mode counterpart, the tangent of the final states and fidelities along one direction (qc_sweep_jvp*, below), is served
- * for "mfma16-sweep" handles, and for "mfma32-sweep" handles whose `wide` has QC_SWEEP_WIDE_TANGENT, with any generators, Lindblad ones
+ * for "mfma16-sweep" handles, for "mfma32-sweep" handles whose `wide` has QC_SWEEP_WIDE_TANGENT, and for "mfma64-sweep" handles whose
+ * `wide` has QC_SWEEP_WIDE_64_TANGENT (states of at most 2048 entries), with any generators, Lindblad ones
  * included (no flag, no state buffer: nothing is reversed); with the pullback it gives Gauss-Newton products of any loss.
  * The tangent of the pullback along one direction (qc_sweep_hvp*, below) gives exact Hessian products of any loss of the final states
  * where both of them are served (closed systems; "mfma16-sweep", and "mfma32-sweep" handles whose `wide` has QC_SWEEP_WIDE_HESSIAN).
@@ -699,7 +710,8 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * systems, pushforwards on "mfma32-sweep" and "rollout-per-sample" handles (the former unless `wide` has QC_SWEEP_WIDE_TANGENT), Hessian
  * products on "rollout-per-sample" handles and on "mfma32-sweep" handles without QC_SWEEP_WIDE_HESSIAN, several directions per
  * call, tangents of grad_theta / grad_scale, several devices; in the "mfma64-sweep" form everything but the forward sweep, with
- * QC_SWEEP_WIDE_64_GRAD gradients and pullbacks of closed systems and with QC_SWEEP_WIDE_64_PARAMS their parameter outputs. */
+ * QC_SWEEP_WIDE_64_GRAD gradients and pullbacks of closed systems, with QC_SWEEP_WIDE_64_PARAMS their parameter outputs and with
+ * QC_SWEEP_WIDE_64_TANGENT pushforwards of states of at most 2048 entries. */
 #define QC_MAX_PERT 8
 #define QC_SWEEP_FID_NONE (-1)   /* qc_sweep_desc.fid_kind: final states only */
 #define QC_SWEEP_WIDE 1          /* qc_sweep_desc.wide, bit 0 */
@@ -710,6 +722,7 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
 #define QC_SWEEP_WIDE_HESSIAN 256 /* qc_sweep_desc.wide, bit 8: the mfma32-sweep form serves Hessian products of closed systems (qc_sweep_hvp*); only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_WIDE_64_GRAD 2048 /* qc_sweep_desc.wide, bit 11: the mfma64-sweep form serves sweep gradients and pullbacks of closed systems (qc_sweep_grad*, qc_sweep_vjp*; qc_sweep64_grad.hip); ignored at 2N <= 32; only together with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 */
 #define QC_SWEEP_WIDE_64_PARAMS 8192 /* qc_sweep_desc.wide, bit 13: the mfma64-sweep form serves parameter gradients and parameter cotangents of closed systems (qc_sweep_grad_params*, grad_theta / grad_scale of qc_sweep_vjp*; the flavour <true> of qc_sweep64_grad.hip's walk); ignored at 2N <= 32; only together with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD */
+#define QC_SWEEP_WIDE_64_TANGENT 16384 /* qc_sweep_desc.wide, bit 14: the mfma64-sweep form serves pushforwards (qc_sweep_jvp*; qc_sweep64_jvp.hip), any generators, 2N x state_cols <= 2048; ignored at 2N <= 32; only together with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 */
 #define QC_SWEEP_WIDE_64 1024    /* qc_sweep_desc.wide, bit 10: 32 < 2N <= 64 with up to 16 drives takes the matrix cores ("mfma64-sweep", qc_sweep_eval* only); ignored at 2N <= 32; only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_STORED_STATES 1 /* qc_sweep_desc.reserved1[0]: reverse mode by the stored-state walk */
 typedef struct qc_sweep_desc {
@@ -732,7 +745,7 @@ typedef struct qc_sweep_desc {
     const double* goal_iso;      /* as qc_fidelity_desc.goal_iso */
     const int32_t* subspace;     /* unitary only: 0-based levels, or NULL = all */
     int32_t device;
-    int32_t wide;                /* bit field; valid: 0, QC_SWEEP_WIDE (1): the matrix-core form up to 2N = 32 ("mfma32-sweep"), or QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS (3): that form, and qc_sweep_grad_params* / the grad_theta, grad_scale of qc_sweep_vjp* are served in it (form, launch, kernel name and every *_supported answer as with 1; harmless where the handle takes another form); either of them | QC_SWEEP_WIDE_STORED (9, 11): that form also serves reverse mode by the stored-state walk when reserved1[0] = QC_SWEEP_STORED_STATES (nothing else changes); any of those | QC_SWEEP_WIDE_TANGENT (17, 19, 25, 27): that form also serves qc_sweep_jvp*; any of the eight | QC_SWEEP_WIDE_NOISE (64): that form also serves qc_sweep_noise_*; any of the sixteen | QC_SWEEP_WIDE_HESSIAN (256): that form also serves qc_sweep_hvp* for closed systems; any of the thirty-two | QC_SWEEP_WIDE_64 (1024): 32 < 2N <= 64 with m <= 16 takes the matrix-core form "mfma64-sweep" (forward sweep only), nothing changes at 2N <= 32; any of those | QC_SWEEP_WIDE_64_GRAD (2048): that form also serves qc_sweep_grad* and qc_sweep_vjp* of closed systems; any of those | QC_SWEEP_WIDE_64_PARAMS (8192): and their parameter outputs; anything else is QC_ERR_INVALID */
+    int32_t wide;                /* bit field; valid: 0, QC_SWEEP_WIDE (1): the matrix-core form up to 2N = 32 ("mfma32-sweep"), or QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS (3): that form, and qc_sweep_grad_params* / the grad_theta, grad_scale of qc_sweep_vjp* are served in it (form, launch, kernel name and every *_supported answer as with 1; harmless where the handle takes another form); either of them | QC_SWEEP_WIDE_STORED (9, 11): that form also serves reverse mode by the stored-state walk when reserved1[0] = QC_SWEEP_STORED_STATES (nothing else changes); any of those | QC_SWEEP_WIDE_TANGENT (17, 19, 25, 27): that form also serves qc_sweep_jvp*; any of the eight | QC_SWEEP_WIDE_NOISE (64): that form also serves qc_sweep_noise_*; any of the sixteen | QC_SWEEP_WIDE_HESSIAN (256): that form also serves qc_sweep_hvp* for closed systems; any of the thirty-two | QC_SWEEP_WIDE_64 (1024): 32 < 2N <= 64 with m <= 16 takes the matrix-core form "mfma64-sweep" (forward sweep only), nothing changes at 2N <= 32; any of those | QC_SWEEP_WIDE_64_GRAD (2048): that form also serves qc_sweep_grad* and qc_sweep_vjp* of closed systems; any of those | QC_SWEEP_WIDE_64_PARAMS (8192): and their parameter outputs; any value that has QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_TANGENT (16384): that form also serves qc_sweep_jvp*, any generators; anything else is QC_ERR_INVALID */
     int64_t reserved1[2];        /* [0]: 0, or QC_SWEEP_STORED_STATES: reverse mode reads stored forward states (any generators; "mfma16-sweep", and "mfma32-sweep" with QC_SWEEP_WIDE_STORED in `wide`); anything else is QC_ERR_INVALID.  [1]: ignored */
 } qc_sweep_desc;
 typedef struct qc_sweep qc_sweep;
@@ -855,13 +868,15 @@ int qc_sweep_vjp(qc_sweep* h, const double* Z, const double* init, int64_t S, co
  *     xdot_0 = vinit,   xdot_{t+1} = E_t xdot_t + L(h_t G; d(hG)_t) x_t   (L: the Frechet derivative of exp),   t = 0 .. T-2
  *     tfinals[s] = xdot_{T-1},   tfids[s] = <dF/dx(x_final[s]), xdot_{T-1}>   (the |tr| / n form is not special-cased at tr = 0).
  * One forward walk that differentiates every product beside itself: 108 + 12 sq matrix-core instructions per interval against the
- * sweep's 36 + 4 sq ("mfma32-sweep": 864 + 96 sq against 288 + 32 sq).  Nothing is reversed, so antisymmetry is not asked for: Lindblad
+ * sweep's 36 + 4 sq ("mfma32-sweep": 864 + 96 sq against 288 + 32 sq; "mfma64-sweep": (27 + 3 sq) x 256 against (9 + sq) x 256).  Nothing is reversed, so antisymmetry is not asked for: Lindblad
  * generators (QC_FID_DENSITY handles) are served.
  * With one pullback call it gives the Gauss-Newton product J^T (d2 loss) J v of any loss of the final states. */
 /* device-free: may the pushforward serve this descriptor?  Scope: the "mfma16-sweep" form (2N <= 16, m <= 8), or the "mfma32-sweep" form
- * (16 < 2N <= 32, m <= 8) of a descriptor whose `wide` has QC_SWEEP_WIDE_TANGENT; any generators, any state_cols and fid_kind the sweep
+ * (16 < 2N <= 32, m <= 8) of a descriptor whose `wide` has QC_SWEEP_WIDE_TANGENT, or the "mfma64-sweep" form (32 < 2N <= 64, m <= 16) of
+ * one whose `wide` has QC_SWEEP_WIDE_64_TANGENT, there with 2N x state_cols <= 2048; any generators, any state_cols and fid_kind the sweep
  * serves there.  When 0, qc_sweep_last_error(NULL) says why, prefixed "qc_sweep pushforward: "
- * ("... not served in the mfma32-sweep form", or the rollout-per-sample form with its cause).  An invalid descriptor returns its own error. */
+ * ("... not served in the mfma32-sweep form", the mfma64-sweep form with 2N -- and, above the bound, ns --, or the rollout-per-sample
+ * form with its cause).  An invalid descriptor returns its own error. */
 int qc_sweep_desc_jvp_supported(const qc_sweep_desc* d, int32_t* supported);
 /* Directions, each optional (NULL = zero: the same bits as an explicit zero array), at least one non-NULL:
  *   vZ       Z_len, the layout of Z, shared by the samples.  ONLY the controls and timesteps of knots 0 .. T-2 are read: whatever

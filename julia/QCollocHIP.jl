@@ -20,6 +20,7 @@ const QC_SWEEP_WIDE_NOISE = 64     # qc_sweep_desc.wide, bit 6 (only with bit 0)
 const QC_SWEEP_WIDE_HESSIAN = 256  # qc_sweep_desc.wide, bit 8 (only with bit 0): Hessian products of closed systems in that form
 const QC_SWEEP_WIDE_64_GRAD = 2048 # qc_sweep_desc.wide, bit 11 (only with bits 0 and 10): gradients and pullbacks of closed systems in the "mfma64-sweep" form
 const QC_SWEEP_WIDE_64_PARAMS = 8192 # qc_sweep_desc.wide, bit 13 (only with bits 0, 10 and 11): parameter gradients and parameter cotangents in the "mfma64-sweep" form
+const QC_SWEEP_WIDE_64_TANGENT = 16384 # qc_sweep_desc.wide, bit 14 (only with bits 0 and 10): pushforwards in the "mfma64-sweep" form, any generators, 2N·cols ≤ 2048
 const QC_SWEEP_WIDE_64 = 1024      # qc_sweep_desc.wide, bit 10 (only with bit 0): 32 < 2N ≤ 64 with up to 16 drives on the matrix cores ("mfma64-sweep", forward sweep only)
 const QC_ABI_VERSION = 6      # QC_VERSION_MAJOR * 1000 + QC_VERSION_MINOR of the include/qcolloc.h these mirrors were written against
 
@@ -1034,19 +1035,24 @@ end
 
 """
     rollout_sweep_pushforward(init, controls, Δt, G_drift, G_drives, G_pert, θ; scale=nothing, cols, vZ=nothing, vinit=nothing,
-                              vtheta=nothing, vscale=nothing, device=0, wide=false)  ->  (finals, tfinals)
+                              vtheta=nothing, vscale=nothing, device=0, wide=false, wide64=false, wide64_tangent=false)  ->  (finals, tfinals)
 
 The pushforward of `rollout_sweep` (`qc_sweep_jvp`): the final states, (2N·cols)×S, and their tangents along one direction, the same
 shape.  `vZ` is an (m+1)×T matrix in the knot layout [a; Δt] (only the columns of knots 1 … T−1 act), `vinit` a 2N·cols vector, `vtheta`
 S×p and `vscale` S×m (valid with `scale = nothing`: taken at all ones); whichever is `nothing` is zero, at least one must be given.
 Served with 2N ≤ 16 and m ≤ 8 for ANY generators, Lindblad ones included (nothing is reversed); no fidelity is involved.  `wide = true`
 sets `qc_sweep_desc.wide = QC_SWEEP_WIDE | QC_SWEEP_WIDE_TANGENT` (17): the matrix-core form up to 2N = 32 ("mfma32-sweep") with its
-pushforward, e.g. two coupled three-level transmons or two qubits with T1 / T2.  Arguments as `rollout_sweep`.  UNTESTED here, like the
-rest of this file.
+pushforward, e.g. two coupled three-level transmons or two qubits with T1 / T2.  `wide = true, wide64 = true, wide64_tangent = true` adds
+`QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_TANGENT` (17425 in all): 32 < 2N ≤ 64 with m ≤ 16 in the "mfma64-sweep" form with its pushforward,
+any generators again (5 qubits, three coupled three-level transmons, a five-level Lindblad model), states of 2N·cols ≤ 2048 entries.
+Arguments as `rollout_sweep`.  UNTESTED here, like the rest of this file: the `wide64_tangent` path was not run.
 """
 function rollout_sweep_pushforward(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift,
                                    G_drives, G_pert, θ::AbstractMatrix{Float64}; scale=nothing, cols::Int, vZ=nothing, vinit=nothing,
-                                   vtheta=nothing, vscale=nothing, device::Int=0, wide::Bool=false)
+                                   vtheta=nothing, vscale=nothing, device::Int=0, wide::Bool=false, wide64::Bool=false,
+                                   wide64_tangent::Bool=false)
+    (wide64 && !wide) && error("rollout_sweep_pushforward: wide64 = true needs wide = true")
+    (wide64_tangent && !wide64) && error("rollout_sweep_pushforward: wide64_tangent = true needs wide64 = true")
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(θ, 1)
     G0 = Float64.(vec(G_drift))
@@ -1070,7 +1076,8 @@ function rollout_sweep_pushforward(init::AbstractVector{Float64}, controls::Abst
     GC.@preserve G0 Gd Gp begin
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, -1,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
-                               0, 0, C_NULL, C_NULL, device, wide ? (QC_SWEEP_WIDE | QC_SWEEP_WIDE_TANGENT) : 0, (0, 0)))
+                               0, 0, C_NULL, C_NULL, device, (wide ? (QC_SWEEP_WIDE | QC_SWEEP_WIDE_TANGENT) : 0) | (wide64 ? QC_SWEEP_WIDE_64 : 0) |
+                               (wide64_tangent ? QC_SWEEP_WIDE_64_TANGENT : 0), (0, 0)))
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_jvp_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
         (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))

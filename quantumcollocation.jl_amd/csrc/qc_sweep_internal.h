@@ -14,6 +14,7 @@ struct qc_sweep : qc_side {
     bool mfma64 = false;         // the 4 x 4-tile form of a descriptor with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 ("mfma64-sweep", qc_sweep64.hip): the forward sweep, and with wide64_grad its closed adjoint; mfma is set as well
     bool wide64_grad = false;    // mfma64 and wide has QC_SWEEP_WIDE_64_GRAD: gradients and pullbacks of closed systems are served (qc_sweep64_grad.hip)
     bool wide64_par = false;     // wide64_grad and wide has QC_SWEEP_WIDE_64_PARAMS: parameter gradients and cotangents are served (the flavour <true> of qc_sweep64_grad.hip's walk)
+    bool wide64_tangent = false; // mfma64 and wide has QC_SWEEP_WIDE_64_TANGENT: pushforwards are served, any generators, ns <= 2048 (qc_sweep64_jvp.hip)
     bool wide_par = false;       // mfma32 and wide has QC_SWEEP_WIDE_PARAMS: parameter gradients and cotangents are served (qc_sweep32_grad.hip)
     bool wide_stored = false;    // mfma32 and wide has QC_SWEEP_WIDE_STORED: with `stored`, reverse mode by the 2 x 2-tile stored-state walk (qc_sweep32_open_grad.hip)
     bool wide_tangent = false;   // mfma32 and wide has QC_SWEEP_WIDE_TANGENT: pushforwards are served (qc_sweep32_jvp.hip)
@@ -24,7 +25,7 @@ struct qc_sweep : qc_side {
     std::string grad_why;        // when not: the reason
     bool vjp_ok = false;         // the pullback's scope (qc_sweep_vjp.hip): the gradient's without its fidelity conditions
     std::string vjp_why;
-    bool jvp_ok = false;         // the pushforward's scope (qc_sweep_jvp.hip): "mfma16-sweep" handles, and "mfma32-sweep" ones with wide_tangent; any generators
+    bool jvp_ok = false;         // the pushforward's scope (qc_sweep_jvp.hip): "mfma16-sweep" handles, "mfma32-sweep" ones with wide_tangent, "mfma64-sweep" ones with wide64_tangent and ns <= 2048; any generators
     std::string jvp_why;
     bool hvp_ok = false;         // the Hessian product's scope (qc_sweep_hvp.hip): the closed scope in the "mfma16-sweep" form, and in the "mfma32-sweep" form with wide_hessian
     std::string hvp_why;
@@ -46,7 +47,7 @@ struct qc_sweep : qc_side {
     qc_buf dGfid;        // fidelities when the caller keeps none, S                         grad, noise_grad
     qc_buf dXall;        // stored-state walk: x_t of knots 0 .. T-2, S x (T-1) x ns                  grad, vjp (stored handles)
     qc_buf dPart;        // chunk shares of the parameter gradients, S x n_chunks x (p + m)  grad_params, vjp
-    qc_buf dTotJ;        // chunk totals and their tangents, S x n_chunks x 512 (mfma32: 2048) jvp, hvp
+    qc_buf dTotJ;        // chunk totals and their tangents, S x n_chunks x 512 (mfma32: 2048, mfma64: 8192) jvp, hvp
     qc_buf dXsT, dLsT;   // xdot and lambdadot at the chunk ends, S x n_chunks x ns each      hvp (x and lambda: dXs, dLs)
     qc_buf dTGsamp;      // per-interval tangents when the caller keeps none, S x (T-1) x nd  hvp
     // Staging of the host-buffer entry points (qc_stage): one buffer per argument, shared by every entry point that has the argument.
@@ -178,14 +179,21 @@ bool qc_sweep_grad_scope(const qc_sweep_desc* d, std::string* why);
 bool qc_sweep_closed_scope(const qc_sweep_desc* d, std::string* why);
 bool qc_sweep_vjp_scope(const qc_sweep_desc* d, std::string* why);
 // the pushforward's scope (qc_sweep_jvp.hip): the "mfma16-sweep" form, and the "mfma32-sweep" form of a descriptor whose wide has
-// QC_SWEEP_WIDE_TANGENT, whatever the generators
+// QC_SWEEP_WIDE_TANGENT, whatever the generators; the "mfma64-sweep" form of a descriptor whose wide has QC_SWEEP_WIDE_64_TANGENT with
+// ns = 2N x state_cols <= 2048 (the finish kernel's LDS at ld = 64)
 bool qc_sweep_jvp_scope(const qc_sweep_desc* d, std::string* why);
+// "mfma64-sweep" handles with `wide64_tangent` (qc_sweep64_jvp.hip): grows h->dTotJ and launches qc_sweep64_jvp_kernel on `st`, one workgroup
+// per (sample, chunk) (S x n_chunks x 2 column-major 64 x 64 matrices of 4096 doubles: the chunk totals and their tangents)
+__attribute__((visibility("hidden"))) int qc_sweep64_jvp_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale,
+                                                                        const double* dvZ, const double* dvtheta, const double* dvscale, hipStream_t st,
+                                                                        int64_t* chunk, int64_t* n_chunks);
 // "mfma32-sweep" handles with `wide_tangent` (qc_sweep32_jvp.hip): grows h->dTotJ and launches qc_sweep32_jvp_kernel on `st`
 // (S x n_chunks x 2 column-major 32 x 32 matrices of 1024 doubles: the chunk totals and their tangents)
 int qc_sweep32_jvp_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dvZ,
                                  const double* dvtheta, const double* dvscale, hipStream_t st, int64_t* chunk, int64_t* n_chunks);
 // grows h->dTotJ and launches the chunk totals and their tangents along (vZ, vtheta, vscale), each NULL = zero, on `st`: on "mfma16-sweep"
-// handles qc_sweep_jvp_kernel<M> (S x n_chunks x 2 tiles of 256 doubles), on "mfma32-sweep" handles qc_sweep32_jvp_launch_totals
+// handles qc_sweep_jvp_kernel<M> (S x n_chunks x 2 tiles of 256 doubles), on "mfma32-sweep" handles qc_sweep32_jvp_launch_totals, on
+// "mfma64-sweep" handles qc_sweep64_jvp_launch_totals
 int qc_sweep_jvp_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dvZ,
                                const double* dvtheta, const double* dvscale, hipStream_t st, int64_t* chunk, int64_t* n_chunks);
 // the plain sum over the samples of a per-interval buffer (qc_sweep_vjp.hip: qc_sweep_vjp_reduce_kernel), launched on `st`

@@ -36,7 +36,9 @@
 // 144 KiB).  Above 64 KiB the launch opts in with hipFuncSetAttribute; an MI355X accepts it up to ns = 4096
 // (tests/test_sweep_many_columns.py, tests/test_sweep_wide_jvp.py).  Should the runtime refuse the attribute on a wide handle, Q and Qdot
 // pass through one ld^2 slot one after the other (136 KiB): the sums keep their order and so their bits; a refusal of that is an error
-// return.
+// return.  "mfma64-sweep" handles made with QC_SWEEP_WIDE_64_TANGENT take qc_sweep64_jvp.hip for the chunk totals and the ld = 64
+// instantiation qc_sweep64_jvp_finish_kernel: 4 ns + 8192 doubles, which bounds their scope at ns = 2048 (128 KiB; every full unitary of
+// the form, N = 32 with 32 columns included); two slots only there, and a refused attribute is an error return.
 //
 // gfx950 cross-compile: see the table in DESIGN.md ("Sweep pushforwards"); no private segment, no spills in any instantiation.
 #include <math.h>
@@ -54,6 +56,7 @@ namespace {
 using namespace qc_sweep16;
 
 constexpr int kFinT = 256;          // threads of the finish workgroup, as qc_sweep_finish_kernel's
+constexpr int kJvpNs64 = 2048;      // "mfma64-sweep": the largest state (2N x state_cols) the finish kernel at ld = 64 holds beside two totals
 
 struct JvpFinParams {
     int n, ns, n_chunks, fid_kind, fid_form, fid_n;
@@ -283,6 +286,17 @@ __global__ __launch_bounds__(kFinT) void qc_sweep32_jvp_finish_kernel(const JvpF
     jvp_finish<ld, l2>(F, tot, src, vsrc, gr, gi, finals, fids, tfinals, tfids);
 }
 
+// the same on the 64 x 64 totals of "mfma64-sweep" handles (qc_sweep64_jvp.hip), as qc_sweep_finish_kernel takes ld = 64 for them: the
+// two-slot path only (the one-slot branch is compiled out: ld != 32), 4 ns + 8192 doubles, 128 KiB at the scope's ns = 2048
+__global__ __launch_bounds__(kFinT) void qc_sweep64_jvp_finish_kernel(const JvpFinParams F, const double* __restrict__ tot, const double* __restrict__ src,
+                                                                      const double* __restrict__ vsrc, const double* __restrict__ gr,
+                                                                      const double* __restrict__ gi, double* __restrict__ finals,
+                                                                      double* __restrict__ fids, double* __restrict__ tfinals,
+                                                                      double* __restrict__ tfids) {
+    constexpr int ld = 64, l2 = 4096;
+    jvp_finish<ld, l2>(F, tot, src, vsrc, gr, gi, finals, fids, tfinals, tfids);
+}
+
 // the argument checks both entry points share, in the order of the header's table
 int jvp_check(qc_sweep* h, const char* who, const void* Z, const void* init, int64_t S, const void* theta, bool any_dir, bool any_out, bool v_theta,
               bool v_scale, bool any_fid) {
@@ -308,6 +322,14 @@ bool qc_sweep_jvp_scope(const qc_sweep_desc* d, std::string* why) {
         *why = "pushforwards are not served in the mfma32-sweep form";
         return false;
     }
+    if (form == QC_SWEEP_FORM_64 && (d->wide & QC_SWEEP_WIDE_64_TANGENT)) {      // qc_sweep64_jvp.hip
+        // the finish kernel keeps x, its successor, their tangents and two 64 x 64 totals in LDS: (4 ns + 8192) doubles, 128 KiB at ns = 2048
+        const int64_t ns = 2 * (int64_t)d->N * (d->state_cols == 0 ? d->N : d->state_cols);
+        if (ns <= kJvpNs64) return true;
+        *why = "the handle takes the mfma64-sweep form (2N = " + std::to_string(2 * d->N) + "), which serves pushforwards of states of at most " +
+               std::to_string(kJvpNs64) + " entries (ns = 2N x state_cols = " + std::to_string(ns) + ")";
+        return false;
+    }
     *why = form == QC_SWEEP_FORM_64 ? qc_sweep_form64_unserved(d, "pushforwards") : qc_sweep_per_sample_why(d);
     return false;
 }
@@ -328,6 +350,7 @@ extern "C" int qc_sweep_desc_jvp_supported(const qc_sweep_desc* d, int32_t* supp
 // qc_sweep32_jvp.hip (S x n_chunks x 2 matrices of 1024 doubles).
 int qc_sweep_jvp_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dvZ,
                                const double* dvtheta, const double* dvscale, hipStream_t st, int64_t* chunk_out, int64_t* n_chunks_out) {
+    if (h->mfma64) return qc_sweep64_jvp_launch_totals(h, dZ, S, dtheta, dscale, dvZ, dvtheta, dvscale, st, chunk_out, n_chunks_out);
     if (h->mfma32) return qc_sweep32_jvp_launch_totals(h, dZ, S, dtheta, dscale, dvZ, dvtheta, dvscale, st, chunk_out, n_chunks_out);
     SweepParams P;
     if (int rc = qc_sweep_plan_totals(h, S, h->dTotJ, 512, &P, chunk_out, n_chunks_out)) return rc;
@@ -355,7 +378,13 @@ static int qc_sweep_jvp_launch(qc_sweep* h, const char* who, const double* dZ, c
     F.n = h->n; F.ns = h->ns; F.n_chunks = (int)n_chunks;
     F.fid_kind = h->d.fid_kind; F.fid_form = h->d.fid_form; F.fid_n = h->fid_n;
     F.one_slot = 0;
-    if (h->mfma32) {
+    if (h->mfma64) {
+        // 4 ns + 2 x 4096 doubles: 128 KiB of the 160 at ns = 2048 (the scope's bound); two slots only, a refused attribute is an error return
+        const size_t lds64 = ((size_t)4 * h->ns + 8192) * 8;
+        QC_SIDE_HIP(h, slot, hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep64_jvp_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64));
+        hipLaunchKernelGGL(qc_sweep64_jvp_finish_kernel, dim3((unsigned)S), dim3(kFinT), lds64, st, F, (const double*)h->dTotJ.p, dinit, dvinit,
+                           (const double*)h->dgr, (const double*)h->dgi, dfinals, dfids, dtfinals, dtfids);
+    } else if (h->mfma32) {
         // 4 ns + 2 x 1024 doubles: 144 KiB of the 160 at ns = 4096
         size_t lds32 = ((size_t)4 * h->ns + 2048) * 8;
         const void* fn = reinterpret_cast<const void*>(&qc_sweep32_jvp_finish_kernel);

@@ -925,13 +925,17 @@ class SweepFinalStateObjective:
     wide_hessian  as `RolloutSweep` (only with `wide`): the Hessian product in the "mfma32-sweep" form.  `hessian_times` there needs
                 `wide_tangent` as well (one `jvp_device`, one `hvp_device`); with one of the two it raises the handle's reason
     wide64, wide64_grad  as `RolloutSweep` (only with `wide`; `wide64_grad` only with `wide64`): all three True serve closed systems of
-                32 < 2N <= 64 in the "mfma64-sweep" form, gradients only (`gauss_newton_times` and `hessian_times` raise the handle's reason)
+                32 < 2N <= 64 in the "mfma64-sweep" form, gradients only (`gauss_newton_times` needs `wide64_tangent` as well;
+                `hessian_times` raises the handle's reason)
+    wide64_tangent  as `RolloutSweep` (only with `wide64`): the pushforward in the "mfma64-sweep" form, so that `gauss_newton_times` is
+                served there beside the gradients of `wide64_grad` (2N x cols <= 2048); `hessian_times` still raises
     wide64_params  as `RolloutSweep` (only with `wide64_grad`): the handle also serves `param_grad` and parameter cotangents there"""
     _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
 
     def __init__(self, traj: NamedTrajectory, system, perturbations, theta, loss, scale=None, state_name="Ũ⃗", control_name: str = "a",
                  device: int = 0, wide: bool = False, stored_states: bool = False, wide_stored: bool = False, wide_tangent: bool = False,
-                 wide_hessian: bool = False, wide64: bool = False, wide64_grad: bool = False, wide64_params: bool = False):
+                 wide_hessian: bool = False, wide64: bool = False, wide64_grad: bool = False, wide64_tangent: bool = False,
+                 wide64_params: bool = False):
         from .rollouts import RolloutSweep, _sweep_samples
         self._sweep = None
         if not callable(loss):
@@ -959,7 +963,7 @@ class SweepFinalStateObjective:
                           off_dt=traj.offset(traj.timestep) if free else -1, dt_fixed=None if free else float(traj.timestep),
                           global_dim=traj.global_dim, device=device, wide=wide, stored_states=stored_states, wide_stored=wide_stored,
                           wide_tangent=wide_tangent, wide_hessian=wide_hessian, wide64=wide64, wide64_grad=wide64_grad,
-                          wide64_params=wide64_params)
+                          wide64_tangent=wide64_tangent, wide64_params=wide64_params)
         self._sweep = sw
         self.wide_hessian = sw.wide_hessian
         self.stored_states = sw.stored_states
@@ -1020,8 +1024,8 @@ class SweepFinalStateObjective:
         final states X with respect to Z: one pushforward (X and Xdot = J v, `jvp_device`), the loss's own Hessian product
         u = d2 loss(X) Xdot by double backward on the loss alone (X a detached leaf), one pullback (`vjp_device`, cot = u).  A loss
         that is linear in X gives zeros.  Z and v are numpy arrays (the result is one) or float64 tensors on the handle's device (the
-        result stays there).  Needs the pushforward's scope beside the pullback's: an "mfma16-sweep" handle, or an "mfma32-sweep" handle
-        made with `wide_tangent`."""
+        result stays there).  Needs the pushforward's scope beside the pullback's: an "mfma16-sweep" handle, an "mfma32-sweep" handle
+        made with `wide_tangent`, or an "mfma64-sweep" handle made with `wide64_tangent`."""
         sw = self._sweep
         if not sw.jvp_supported:
             raise _lib.QCollocError(_lib.QC_ERR_UNSUPPORTED, sw.jvp_unsupported_reason)

@@ -239,29 +239,38 @@ class RolloutSweep:
     wide64         True (only with `wide`): systems of 32 < 2N <= 64 with up to 16 drives -- 5 qubits, three coupled three-level
                    transmons, a five-level Lindblad model -- run on the matrix cores as well ("mfma64-sweep": one workgroup per
                    (sample, chunk of intervals), the matrices in LDS) instead of one rollout per sample.  That form serves `eval` and
-                   `eval_device` only: `grad`, `param_grad`, `vjp`, `jvp`, `hvp` and the noise sweeps refuse there, naming the form.
+                   `eval_device` only: `grad`, `param_grad`, `vjp`, `jvp`, `hvp` and the noise sweeps refuse there, naming the form
+                   (`wide64_grad` adds `grad` and `vjp`, `wide64_params` their parameter outputs, `wide64_tangent` `jvp`).
                    Nothing changes at 2N <= 32, and nothing changes without it.
     wide64_grad    True (only with `wide64`): an "mfma64-sweep" handle of a closed system (antisymmetric generators, at most 32 state
                    columns: a full unitary of 32 levels fits) also serves `grad`, `vjp`, their device forms and the backward rule of
                    `finals_autograd`, by the closed adjoint walk on 4 x 4 tiles.  `param_grad`, the `params` of `vjp`, `stored_states`,
-                   `jvp`, `hvp` and the noise sweeps still refuse there, naming the form.  Nothing else changes, nothing changes at
-                   2N <= 32, and nothing changes without it.
+                   `hvp` and the noise sweeps still refuse there, naming the form; `jvp` is `wide64_tangent`'s to serve.  Nothing
+                   else changes, nothing changes at 2N <= 32, and nothing changes without it.
     wide64_params  True (only with `wide64_grad`): such a handle also serves `param_grad`, `param_grad_device`, the `params` of `vjp` and
                    the theta / scale cotangents of `finals_autograd`, by the parameter flavour of the same walk: one call gives
                    dF_s/dtheta and dF_s/dscale of every sample (dF_s/dscale is taken before the factor scale, so it is defined at
-                   scale = 0).  `stored_states`, `jvp`, `hvp` and the noise sweeps still refuse there.  Without it `param_grad` and
-                   the `params` of `vjp` refuse there, as they did; nothing else changes, and nothing changes at 2N <= 32."""
+                   scale = 0).  `stored_states`, `hvp` and the noise sweeps still refuse there (`jvp` is `wide64_tangent`'s to
+                   serve).  Without it `param_grad` and the `params` of `vjp` refuse there, as they did; nothing else changes, and
+                   nothing changes at 2N <= 32.
+    wide64_tangent True (only with `wide64`; it needs neither `wide64_grad` nor `wide64_params`): an "mfma64-sweep" handle also serves
+                   `jvp`, `jvp_device` and the forward-mode rule of `finals_autograd` -- any generators, open systems included (a
+                   five-level Lindblad model: 2N = 50), any fidelity, states of 2N x cols <= 2048 entries (every full unitary of the
+                   form) -- by the paired exponential on 4 x 4 tiles: three forward sweeps by the instruction count.  Above that size
+                   `jvp` refuses, naming the form, 2N and the size.  `hvp`, the noise sweeps and `stored_states` still refuse there.
+                   Without it `jvp` refuses there, as it did; nothing else changes, and nothing changes at 2N <= 32."""
 
     def __init__(self, system, perturbations, T: int, cols: Optional[int] = None, goal=None, fid_kind=None, subspace=None,
                  fid_form: int = _lib.QC_FID_FORM_ABS, zdim: Optional[int] = None, off_a: int = 0, off_dt: Optional[int] = None,
                  dt_fixed: Optional[float] = None, global_dim: int = 0, device: int = 0, wide: bool = False,
                  stored_states: bool = False, wide_params: bool = False, wide_stored: bool = False, wide_tangent: bool = False,
                  wide_noise: bool = False, wide_hessian: bool = False, wide64: bool = False, wide64_grad: bool = False,
-                 wide64_params: bool = False):
+                 wide64_tangent: bool = False, wide64_params: bool = False):
         self._h = None
         flags = (   # (keyword, given, its bit of qc_sweep_desc.wide, what it needs, the refusal without that)
             ("wide64_params", wide64_params, _lib.QC_SWEEP_WIDE_64_PARAMS, wide64_grad, "wide64_params=True needs wide64_grad=True"),
             ("wide64_grad", wide64_grad, _lib.QC_SWEEP_WIDE_64_GRAD, wide64, "wide64_grad=True needs wide64=True"),
+            ("wide64_tangent", wide64_tangent, _lib.QC_SWEEP_WIDE_64_TANGENT, wide64, "wide64_tangent=True needs wide64=True"),
             ("wide64", wide64, _lib.QC_SWEEP_WIDE_64, wide, "wide64=True needs wide=True"),
             ("wide_hessian", wide_hessian, _lib.QC_SWEEP_WIDE_HESSIAN, wide, "wide_hessian=True needs wide=True"),
             ("wide_noise", wide_noise, _lib.QC_SWEEP_WIDE_NOISE, wide, "wide_noise=True needs wide=True"),
@@ -335,6 +344,15 @@ class RolloutSweep:
     @wide64_params.setter
     def wide64_params(self, given):
         self._wide64_params = bool(given)
+
+    @property
+    def wide64_tangent(self) -> bool:
+        """Whether the handle was made with `wide64_tangent` (kept outside the instance's public flags, as `wide64_grad` is)."""
+        return self._wide64_tangent
+
+    @wide64_tangent.setter
+    def wide64_tangent(self, given):
+        self._wide64_tangent = bool(given)
 
     def _scope(self, supported):
         """(served?, the library's reason why not or None) from a `qc_sweep_desc_*_supported` function."""
@@ -587,7 +605,7 @@ class RolloutSweep:
     # -- pushforwards: the tangent of the final states and fidelities along one direction -------------------------------------------
     @property
     def jvp_supported(self) -> bool:
-        """Does `jvp` serve this handle?  (`qc_sweep_desc_jvp_supported`: the "mfma16-sweep" form, or "mfma32-sweep" with `wide_tangent`; any generators -- Lindblad ones
+        """Does `jvp` serve this handle?  (`qc_sweep_desc_jvp_supported`: the "mfma16-sweep" form, "mfma32-sweep" with `wide_tangent`, or "mfma64-sweep" with `wide64_tangent` and 2N x cols <= 2048; any generators -- Lindblad ones
         included -- and any fidelity or none.)  `jvp_unsupported_reason` says why not."""
         return self._scope(_lib.lib.qc_sweep_desc_jvp_supported)[0]
 
@@ -792,7 +810,7 @@ class RolloutSweep:
 
     def finals_autograd(self, dZ, dinit, dtheta=None, dscale=None):
         """The S x (2N cols) final states as a differentiable torch tensor: forward is `eval_device` on the current stream, backward one
-        `vjp_device` call, and under `torch.autograd.forward_ad` the tangent is one `jvp_device` call ("mfma16-sweep" handles, and "mfma32-sweep" handles made with `wide_tangent`).  dZ
+        `vjp_device` call, and under `torch.autograd.forward_ad` the tangent is one `jvp_device` call ("mfma16-sweep" handles, "mfma32-sweep" handles made with `wide_tangent` and "mfma64-sweep" handles made with `wide64_tangent`).  dZ
         (Z_len), dinit (2N cols), dtheta (S x n_pert), dscale (S x m or None) are float64 CUDA tensors; whichever requires grad
         receives one: Z the plain sum over the samples, init the sum of the per-sample derivatives, theta and scale their per-sample
         values ("mfma16-sweep" handles, "mfma32-sweep" handles made with `wide_params` and "mfma64-sweep" handles made with
