@@ -651,7 +651,7 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * chunk rule with that item's fill constant (n_chunks = 1 once S >= 256, one workgroup per compute unit; else ceil(256 / S) chunks, at
  * most ceil(sqrt(T-1))).  The mathematics is the family's.  That form serves the FORWARD sweep only, qc_sweep_eval*: final states
  * and fidelities.  qc_sweep_grad*, qc_sweep_grad_params*, qc_sweep_vjp*, qc_sweep_jvp*, qc_sweep_hvp* and qc_sweep_noise_* return
- * QC_ERR_UNSUPPORTED on such a handle, whatever bits 1 .. 8 say (bit 11, below, adds gradients and pullbacks, bit 14 pushforwards), and the qc_sweep_desc_*_supported queries answer 0 with a reason
+ * QC_ERR_UNSUPPORTED on such a handle, whatever bits 1 .. 8 say (bit 11, below, adds gradients and pullbacks, bit 14 pushforwards, bit 16 noise sweeps), and the qc_sweep_desc_*_supported queries answer 0 with a reason
  * that names the form and the size ("... the mfma64-sweep form (2N = 54) ...").  Descriptors with 2N <= 32 ignore the bit completely:
  * form, launch, kernel name, every *_supported answer and every output bit are those of the same descriptor without it.  Without the
  * bit nothing changes anywhere.  Not in that form: more than 16 drives (rollout-per-sample), a state-action form that skips the
@@ -662,14 +662,14 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * closed adjoint walk on 4 x 4 tiles (qc_sweep64_grad.hip; one workgroup per (sample, chunk), the forward form's chunk rule).  The
  * fidelities and final states carry the bits of qc_sweep_eval on the same handle.  Still QC_ERR_UNSUPPORTED there, with a reason that
  * names the form and 2N: parameter gradients and parameter cotangents, reserved1[0] = QC_SWEEP_STORED_STATES, qc_sweep_jvp* (served
- * with bit 14, below), qc_sweep_hvp* and qc_sweep_noise_*.  Form, launch, kernel name and every output bit of qc_sweep_eval* are those of the same descriptor
+ * with bit 14, below), qc_sweep_hvp* and qc_sweep_noise_* (served with bit 16, below).  Form, launch, kernel name and every output bit of qc_sweep_eval* are those of the same descriptor
  * without the bit; descriptors with 2N <= 32 ignore it completely, as they ignore bit 10.
  * Bit 13, QC_SWEEP_WIDE_64_PARAMS (any valid value that has bits 0, 10 and 11, | 8192; without all three of them QC_ERR_INVALID; bit 12
  * is not assigned), changes one thing only: such a handle then also serves qc_sweep_grad_params* (grad_theta, grad_scale) and the
  * grad_theta / grad_scale of qc_sweep_vjp*, in the scope of bit 11, by the parameter flavour of the same walk (per (sample, chunk) the
  * p + m chunk shares in a fixed order, then the reduction of the smaller forms; no atomics).  The other outputs of a parameter call carry
  * the bits of qc_sweep_grad / qc_sweep_vjp on the same handle, and a call without parameter outputs launches exactly what it launched
- * without the bit.  The stored-state flag, qc_sweep_jvp* (served with bit 14), qc_sweep_hvp* and qc_sweep_noise_* stay QC_ERR_UNSUPPORTED
+ * without the bit.  The stored-state flag, qc_sweep_jvp* (served with bit 14), qc_sweep_hvp* and qc_sweep_noise_* (served with bit 16) stay QC_ERR_UNSUPPORTED
  * there; descriptors with 2N <= 32 ignore the bit completely.
  * Bit 14, QC_SWEEP_WIDE_64_TANGENT (any valid value that has bits 0 and 10, | 16384; without both of them QC_ERR_INVALID; it needs
  * neither bit 11 nor bit 13, because nothing is reversed), changes one thing only: an "mfma64-sweep" handle then also serves qc_sweep_jvp*
@@ -679,8 +679,18 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * workgroup per (sample, chunk), the forward form's chunk rule) and the finish kernel of qc_sweep_jvp.hip at ld = 64, whose LDS sets the
  * bound; above it QC_ERR_UNSUPPORTED with a reason that names the form, 2N and ns.  finals / fids carry the bits of qc_sweep_eval on the
  * same handle.  With bits 11 and 13 as well the pullback and the pushforward together give Gauss-Newton products.  qc_sweep_hvp*,
- * qc_sweep_noise_* and the stored-state flag stay QC_ERR_UNSUPPORTED there.  Form, launch, kernel name, every other *_supported answer and
+ * qc_sweep_noise_* (served with bit 16, below) and the stored-state flag stay QC_ERR_UNSUPPORTED there.  Form, launch, kernel name, every other *_supported answer and
  * every other entry point's output are those of the same descriptor without the bit; descriptors with 2N <= 32 ignore it completely.
+ * Bit 16, QC_SWEEP_WIDE_64_NOISE (any valid value that has bits 0 and 10, | 65536; without both of them QC_ERR_INVALID; it needs none of
+ * bits 11, 13 and 14; bits 15 and 20 are not assigned), changes one thing only: an "mfma64-sweep" handle then also serves the
+ * noise-trajectory sweeps (qc_sweep_noise_*, below; qc_sweep64_noise.hip) with m <= 16 drives and 1 <= n_pert <= 8 perturbations, up to
+ * 24 generators (nothing is resident per generator there: no tile limit).  qc_sweep_noise_eval* serves ANY generators, Lindblad ones
+ * included, any fid_kind or none and any state_cols the forward sweep serves; qc_sweep_noise_grad* needs the gradient's closed scope
+ * of this form as well -- bit 11, antisymmetric generators, at most 32 state columns, a unitary or ket fidelity -- and without it answers
+ * QC_ERR_UNSUPPORTED with the gradient's own reason.  At noise = +0.0 the outputs carry the bits of qc_sweep_eval / qc_sweep_grad on the
+ * same handle.  qc_sweep_hvp* and the stored-state flag stay QC_ERR_UNSUPPORTED there.  Form, launch, kernel name, every other
+ * *_supported answer and every other entry point's output are those of the same descriptor without the bit; descriptors with 2N <= 32
+ * ignore it completely.
  * reserved1[0] = QC_SWEEP_STORED_STATES chooses reverse mode by the STORED-STATE walk: qc_sweep_grad*, qc_sweep_grad_params* and
  * qc_sweep_vjp* then keep the forward states x_0 .. x_{T-2} of every sample in handle scratch (S x (T-1) x 2N x cols doubles) and read
  * them on the way back instead of reversing the step, which serves ANY generators in the "mfma16-sweep" form: Lindblad generators
@@ -703,15 +713,16 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * included (no flag, no state buffer: nothing is reversed); with the pullback it gives Gauss-Newton products of any loss.
  * The tangent of the pullback along one direction (qc_sweep_hvp*, below) gives exact Hessian products of any loss of the final states
  * where both of them are served (closed systems; "mfma16-sweep", and "mfma32-sweep" handles whose `wide` has QC_SWEEP_WIDE_HESSIAN).
- * Noise-trajectory sweeps (qc_sweep_noise_*, below) are served for "mfma16-sweep" handles, and for "mfma32-sweep" handles whose `wide` has
- * QC_SWEEP_WIDE_NOISE.
+ * Noise-trajectory sweeps (qc_sweep_noise_*, below) are served for "mfma16-sweep" handles, for "mfma32-sweep" handles whose `wide` has
+ * QC_SWEEP_WIDE_NOISE, and for "mfma64-sweep" handles whose `wide` has QC_SWEEP_WIDE_64_NOISE.
  * Out of scope: per-knot outputs, open-system gradients in the "mfma32-sweep" form without QC_SWEEP_WIDE_STORED (their directional
  * derivatives are not served there at all), checkpointing inside a chunk, Hessian products and noise gradients of open
  * systems, pushforwards on "mfma32-sweep" and "rollout-per-sample" handles (the former unless `wide` has QC_SWEEP_WIDE_TANGENT), Hessian
  * products on "rollout-per-sample" handles and on "mfma32-sweep" handles without QC_SWEEP_WIDE_HESSIAN, several directions per
  * call, tangents of grad_theta / grad_scale, several devices; in the "mfma64-sweep" form everything but the forward sweep, with
  * QC_SWEEP_WIDE_64_GRAD gradients and pullbacks of closed systems, with QC_SWEEP_WIDE_64_PARAMS their parameter outputs and with
- * QC_SWEEP_WIDE_64_TANGENT pushforwards of states of at most 2048 entries. */
+ * QC_SWEEP_WIDE_64_TANGENT pushforwards of states of at most 2048 entries and with QC_SWEEP_WIDE_64_NOISE noise sweeps (Hessian products
+ * are not served in that form). */
 #define QC_MAX_PERT 8
 #define QC_SWEEP_FID_NONE (-1)   /* qc_sweep_desc.fid_kind: final states only */
 #define QC_SWEEP_WIDE 1          /* qc_sweep_desc.wide, bit 0 */
@@ -723,6 +734,7 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
 #define QC_SWEEP_WIDE_64_GRAD 2048 /* qc_sweep_desc.wide, bit 11: the mfma64-sweep form serves sweep gradients and pullbacks of closed systems (qc_sweep_grad*, qc_sweep_vjp*; qc_sweep64_grad.hip); ignored at 2N <= 32; only together with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 */
 #define QC_SWEEP_WIDE_64_PARAMS 8192 /* qc_sweep_desc.wide, bit 13: the mfma64-sweep form serves parameter gradients and parameter cotangents of closed systems (qc_sweep_grad_params*, grad_theta / grad_scale of qc_sweep_vjp*; the flavour <true> of qc_sweep64_grad.hip's walk); ignored at 2N <= 32; only together with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD */
 #define QC_SWEEP_WIDE_64_TANGENT 16384 /* qc_sweep_desc.wide, bit 14: the mfma64-sweep form serves pushforwards (qc_sweep_jvp*; qc_sweep64_jvp.hip), any generators, 2N x state_cols <= 2048; ignored at 2N <= 32; only together with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 */
+#define QC_SWEEP_WIDE_64_NOISE 65536 /* qc_sweep_desc.wide, bit 16: the mfma64-sweep form serves noise-trajectory sweeps and, with QC_SWEEP_WIDE_64_GRAD, their gradients (qc_sweep_noise_*; qc_sweep64_noise.hip); ignored at 2N <= 32; only together with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 */
 #define QC_SWEEP_WIDE_64 1024    /* qc_sweep_desc.wide, bit 10: 32 < 2N <= 64 with up to 16 drives takes the matrix cores ("mfma64-sweep", qc_sweep_eval* only); ignored at 2N <= 32; only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_STORED_STATES 1 /* qc_sweep_desc.reserved1[0]: reverse mode by the stored-state walk */
 typedef struct qc_sweep_desc {
@@ -949,17 +961,22 @@ int qc_sweep_hvp(qc_sweep* h, const double* Z, const double* init, int64_t S, co
  * per sample and interval.  An "mfma32-sweep" handle (16 < 2N <= 32: two coupled three-level transmons with drifting detunings, a 4-qubit
  * register, two qubits with T1 / T2 whose decay rate fluctuates) serves both entry-point families when its descriptor sets
  * QC_SWEEP_WIDE_NOISE in `wide`: that form keeps no generator resident (every image is read again per interval), so the only limits
- * there are m <= 8 and n_pert <= QC_MAX_PERT, up to 16 generators.  Every contract below holds in both forms.
+ * there are m <= 8 and n_pert <= QC_MAX_PERT, up to 16 generators.  An "mfma64-sweep" handle (32 < 2N <= 64: three coupled three-level
+ * transmons whose detunings drift, a 5-qubit register with noisy drive lines, a five-level Lindblad model) serves them when its
+ * descriptor sets QC_SWEEP_WIDE_64_NOISE (qc_sweep64_noise.hip): m <= 16 and n_pert <= QC_MAX_PERT, up to 24 generators; its gradient
+ * needs QC_SWEEP_WIDE_64_GRAD as well and serves states of up to 32 columns.  Every contract below holds in all three forms.
  * At noise = +0.0 the outputs equal those of qc_sweep_eval / qc_sweep_grad on the same handle value for value (a -0.0 may come out
  * as +0.0, nothing else).
- * Out of scope: "mfma32-sweep" handles without QC_SWEEP_WIDE_NOISE and "rollout-per-sample" handles;
+ * Out of scope: "mfma32-sweep" handles without QC_SWEEP_WIDE_NOISE, "mfma64-sweep" handles without QC_SWEEP_WIDE_64_NOISE and
+ * "rollout-per-sample" handles;
  * pullbacks, pushforwards and Hessian products with noise (and with them the autograd function of the Python layer); noise gradients of
  * open systems; several devices. */
 /* device-free: may the noise sweep serve this descriptor?  Scope of the evaluation: the "mfma16-sweep" form with n_pert >= 1 and
  * m + n_pert <= 8, or the "mfma32-sweep" form of a descriptor whose `wide` has QC_SWEEP_WIDE_NOISE with n_pert >= 1 (no condition on
- * m + n_pert); any generators (Lindblad ones included), any state_cols and fid_kind the sweep serves there.  When 0,
+ * m + n_pert), or the "mfma64-sweep" form of a descriptor whose `wide` has QC_SWEEP_WIDE_64_NOISE with n_pert >= 1 (m <= 16 by the
+ * form); any generators (Lindblad ones included), any state_cols and fid_kind the sweep serves there.  When 0,
  * qc_sweep_last_error(NULL) says why, prefixed "qc_sweep noise: ": "... not served in the mfma32-sweep form" (that form without the
- * bit), the rollout-per-sample form with its cause, n_pert = 0, or ("mfma16-sweep") m + n_pert > 8 with the two numbers.  An invalid
+ * bit), the mfma64-sweep form without its bit (the form's sentence with 2N), the rollout-per-sample form with its cause, n_pert = 0, or ("mfma16-sweep") m + n_pert > 8 with the two numbers.  An invalid
  * descriptor returns its own error. */
 int qc_sweep_desc_noise_supported(const qc_sweep_desc* d, int32_t* supported);
 /* The arguments and rules of qc_sweep_eval / qc_sweep_eval_dev, plus `noise` (required; it must not overlap an output:
@@ -975,7 +992,8 @@ int qc_sweep_noise_eval_dev(qc_sweep* h, const double* dZ, const double* dinit, 
  *   grad_noise   S x (T-1) x n_pert, the layout of noise: dF_s/dnoise[s, t, j] = dt_t <lambda_{t+1} x_t^T, L(dt_t G_{s,t}; P_j)>, raw
  *                per-sample values (no weights) -- the time-resolved noise sensitivity of every sample, from the per-interval tile the
  *                backward walk forms anyway (qc_sweep_grad_params sums it over t: at noise = 0, sum_t grad_noise[s, t, j] = grad_theta[s, j]).
- * Scope: the noise scope and the gradient's together (closed systems, a unitary or ket fidelity, at most 16 state columns); a refusal
+ * Scope: the noise scope and the gradient's together (closed systems, a unitary or ket fidelity, at most 16 state columns; in the
+ * "mfma64-sweep" form QC_SWEEP_WIDE_64_GRAD and at most 32); a refusal
  * is prefixed "qc_sweep noise: " and carries the noise scope's reason, else the gradient's own.  Without grad_samples the handle
  * keeps the per-interval buffer itself when `grad` needs it.  No atomics: repeated calls return the same bits, and no output's bits
  * depend on which other outputs were requested.  Non-finite entries of noise[s] reach sample s's outputs and `grad` / `J`, nothing else. */

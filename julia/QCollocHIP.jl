@@ -21,6 +21,7 @@ const QC_SWEEP_WIDE_HESSIAN = 256  # qc_sweep_desc.wide, bit 8 (only with bit 0)
 const QC_SWEEP_WIDE_64_GRAD = 2048 # qc_sweep_desc.wide, bit 11 (only with bits 0 and 10): gradients and pullbacks of closed systems in the "mfma64-sweep" form
 const QC_SWEEP_WIDE_64_PARAMS = 8192 # qc_sweep_desc.wide, bit 13 (only with bits 0, 10 and 11): parameter gradients and parameter cotangents in the "mfma64-sweep" form
 const QC_SWEEP_WIDE_64_TANGENT = 16384 # qc_sweep_desc.wide, bit 14 (only with bits 0 and 10): pushforwards in the "mfma64-sweep" form, any generators, 2N·cols ≤ 2048
+const QC_SWEEP_WIDE_64_NOISE = 65536 # qc_sweep_desc.wide, bit 16 (only with bits 0 and 10): noise-trajectory sweeps in the "mfma64-sweep" form (their gradients with bit 11 as well)
 const QC_SWEEP_WIDE_64 = 1024      # qc_sweep_desc.wide, bit 10 (only with bit 0): 32 < 2N ≤ 64 with up to 16 drives on the matrix cores ("mfma64-sweep", forward sweep only)
 const QC_ABI_VERSION = 6      # QC_VERSION_MAJOR * 1000 + QC_VERSION_MINOR of the include/qcolloc.h these mirrors were written against
 
@@ -820,17 +821,20 @@ end
 
 """
     rollout_noise_sweep(init, controls, Δt, G_drift, G_drives, G_pert, ξ; θ=nothing, scale=nothing, cols, goal=nothing, fid_kind=-1,
-                        subspace=nothing, squared=false, device=0, wide=false)  ->  (finals, fids)
+                        subspace=nothing, squared=false, device=0, wide=false, wide64=false)  ->  (finals, fids)
 
 `rollout_sweep` with perturbation amplitudes that change from interval to interval (`qc_sweep_noise_eval`): in interval t sample s
 evolves under G_drift + Σ_j (θ[s, j] + ξ[j, t, s]) G_pert[j] + Σ_k scale[s, k] a_{t,k} G_drives[k].  `ξ` is p×(T-1)×S (the library's
 sample-major layout as a column-major array), `θ` S×p or nothing (zeros).  Served for 2N ≤ 16 with p ≥ 1 and m + p ≤ 8; `wide = true` sets
 `qc_sweep_desc.wide = QC_SWEEP_WIDE | QC_SWEEP_WIDE_NOISE` (65): 16 < 2N ≤ 32 on the matrix cores with p ≥ 1, m ≤ 8 and no limit on
-m + p.  Everything else errors with the library's reason.  Other arguments as `rollout_sweep`.  UNTESTED here, like the rest of this file.
+m + p.  `wide64 = true` (only with `wide`) adds `QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_NOISE` (66625 in all): 32 < 2N ≤ 64 with p ≥ 1 and m ≤ 16
+in the "mfma64-sweep" form, any generators.  Everything else errors with the library's reason.  Other arguments as `rollout_sweep`.
+UNTESTED here, like the rest of this file: the `wide64` path was not run.
 """
 function rollout_noise_sweep(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift, G_drives,
                              G_pert, ξ::AbstractArray{Float64,3}; θ=nothing, scale=nothing, cols::Int, goal=nothing, fid_kind::Int=-1,
-                             subspace=nothing, squared::Bool=false, device::Int=0, wide::Bool=false)
+                             subspace=nothing, squared::Bool=false, device::Int=0, wide::Bool=false, wide64::Bool=false)
+    (!wide64 || wide) || error("rollout_noise_sweep: wide64 = true needs wide = true")
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(ξ, 3)
     size(ξ) == (p, T - 1, S) || error("rollout_noise_sweep: ξ must be $p×$(T - 1)×S")
@@ -850,7 +854,7 @@ function rollout_noise_sweep(init::AbstractVector{Float64}, controls::AbstractMa
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
                                squared ? 1 : 0, length(sub), isempty(g) ? C_NULL : pointer(g), isempty(sub) ? C_NULL : pointer(sub),
-                               device, wide ? (QC_SWEEP_WIDE | QC_SWEEP_WIDE_NOISE) : 0, (0, 0)))
+                               device, (wide ? (QC_SWEEP_WIDE | QC_SWEEP_WIDE_NOISE) : 0) | (wide64 ? (QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_NOISE) : 0), (0, 0)))
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_noise_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
         (rc == 0 && ok[] == 1) || error(unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
@@ -868,17 +872,20 @@ end
 
 """
     rollout_noise_sweep_gradient(init, controls, Δt, G_drift, G_drives, G_pert, ξ; θ=nothing, scale=nothing, weights=nothing, cols, goal,
-                                 fid_kind=0, subspace=nothing, squared=false, device=0, wide=false)  ->  (J, fids, ∇a, ∇Δt, ∇ξ)
+                                 fid_kind=0, subspace=nothing, squared=false, device=0, wide=false, wide64=false)  ->  (J, fids, ∇a, ∇Δt, ∇ξ)
 
 The adjoint of `rollout_noise_sweep` (`qc_sweep_noise_grad`): J, the S fidelities and the gradient of J over the controls and timesteps
 as `rollout_sweep_gradient` returns them, and `∇ξ[j, t, s]` = ∂F_s/∂ξ[j, t, s] (p×(T-1)×S, raw per-sample values): the time-resolved noise
 sensitivity of every sample.  Closed systems, `fid_kind` 0 (unitary) or 1 (ket), 2N ≤ 16, p ≥ 1, m + p ≤ 8; `wide = true` sets
-`qc_sweep_desc.wide = QC_SWEEP_WIDE | QC_SWEEP_WIDE_NOISE` (65): 16 < 2N ≤ 32 with p ≥ 1, m ≤ 8, no limit on m + p.  UNTESTED here, like
-the rest of this file.
+`qc_sweep_desc.wide = QC_SWEEP_WIDE | QC_SWEEP_WIDE_NOISE` (65): 16 < 2N ≤ 32 with p ≥ 1, m ≤ 8, no limit on m + p.  `wide64 = true` (only
+with `wide`) adds `QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD | QC_SWEEP_WIDE_64_NOISE` (68673 in all): closed systems with 32 < 2N ≤ 64, p ≥ 1,
+m ≤ 16 and at most 32 state columns in the "mfma64-sweep" form.  UNTESTED here, like the rest of this file: the `wide64` path was not run.
 """
 function rollout_noise_sweep_gradient(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Δt::AbstractVector{Float64}, G_drift,
                                       G_drives, G_pert, ξ::AbstractArray{Float64,3}; θ=nothing, scale=nothing, weights=nothing, cols::Int,
-                                      goal, fid_kind::Int=0, subspace=nothing, squared::Bool=false, device::Int=0, wide::Bool=false)
+                                      goal, fid_kind::Int=0, subspace=nothing, squared::Bool=false, device::Int=0, wide::Bool=false,
+                                      wide64::Bool=false)
+    (!wide64 || wide) || error("rollout_noise_sweep_gradient: wide64 = true needs wide = true")
     n = size(G_drift, 1); N = n ÷ 2
     m, T = size(controls); p = length(G_pert); S = size(ξ, 3)
     size(ξ) == (p, T - 1, S) || error("rollout_noise_sweep_gradient: ξ must be $p×$(T - 1)×S")
@@ -901,7 +908,8 @@ function rollout_noise_sweep_gradient(init::AbstractVector{Float64}, controls::A
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
                                squared ? 1 : 0, length(sub), pointer(g), isempty(sub) ? C_NULL : pointer(sub),
-                               device, wide ? (QC_SWEEP_WIDE | QC_SWEEP_WIDE_NOISE) : 0, (0, 0)))
+                               device, (wide ? (QC_SWEEP_WIDE | QC_SWEEP_WIDE_NOISE) : 0) |
+                               (wide64 ? (QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD | QC_SWEEP_WIDE_64_NOISE) : 0), (0, 0)))
         rc = ccall((:qc_sweep_create, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Ptr{Cvoid}}), desc, h)
         rc == 0 || error("qc_sweep_create: " * unsafe_string(ccall((:qc_sweep_last_error, LIB[]), Cstring, (Ptr{Cvoid},), C_NULL)))
     end

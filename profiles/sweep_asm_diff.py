@@ -18,7 +18,8 @@ import subprocess
 import sys
 
 FILES = ["qc_sweep", "qc_sweep32", "qc_sweep_grad", "qc_sweep32_grad", "qc_sweep_vjp", "qc_sweep_jvp", "qc_sweep32_jvp", "qc_sweep_hvp",
-         "qc_sweep32_hvp", "qc_sweep_noise", "qc_sweep32_noise", "qc_sweep_open_grad", "qc_sweep32_open_grad"]
+         "qc_sweep32_hvp", "qc_sweep_noise", "qc_sweep32_noise", "qc_sweep_open_grad", "qc_sweep32_open_grad", "qc_sweep64", "qc_sweep64_grad",
+         "qc_sweep64_jvp", "qc_sweep64_noise"]
 SEEDS = "qc_sweep_seed_kernel,qc_sweep32_seed_kernel,qc_sweep_cot_seed_kernel,qc_sweep32_cot_seed_kernel"
 KEYS = ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "sgpr_spill_count", "vgpr_spill_count")
 FIXED = ("vgpr_count", "agpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "sgpr_spill_count", "vgpr_spill_count", "mfma")

@@ -20,8 +20,8 @@
 //
 // Gradients and pullbacks of closed systems in this form: qc_sweep64_grad.hip, on handles that also set QC_SWEEP_WIDE_64_GRAD (without it
 // their entry points answer QC_ERR_UNSUPPORTED, as they did); their parameter outputs with QC_SWEEP_WIDE_64_PARAMS as well.  Pushforwards in
-// this form: qc_sweep64_jvp.hip, on handles that set QC_SWEEP_WIDE_64_TANGENT (any generators).  Out of scope in this form: Hessian
-// products and noise sweeps (their entry points answer QC_ERR_UNSUPPORTED on such a handle), a state-action form that skips the propagator for kets, more than 16 drives, 2N > 64.
+// this form: qc_sweep64_jvp.hip, on handles that set QC_SWEEP_WIDE_64_TANGENT (any generators); noise sweeps: qc_sweep64_noise.hip, on handles that set QC_SWEEP_WIDE_64_NOISE.  Out of scope in this form: Hessian
+// products (their entry points answer QC_ERR_UNSUPPORTED on such a handle), a state-action form that skips the propagator for kets, more than 16 drives, 2N > 64.
 #include <math.h>
 
 #include <string>

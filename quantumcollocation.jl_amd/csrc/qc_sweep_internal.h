@@ -15,6 +15,7 @@ struct qc_sweep : qc_side {
     bool wide64_grad = false;    // mfma64 and wide has QC_SWEEP_WIDE_64_GRAD: gradients and pullbacks of closed systems are served (qc_sweep64_grad.hip)
     bool wide64_par = false;     // wide64_grad and wide has QC_SWEEP_WIDE_64_PARAMS: parameter gradients and cotangents are served (the flavour <true> of qc_sweep64_grad.hip's walk)
     bool wide64_tangent = false; // mfma64 and wide has QC_SWEEP_WIDE_64_TANGENT: pushforwards are served, any generators, ns <= 2048 (qc_sweep64_jvp.hip)
+    bool wide64_noise = false;   // mfma64 and wide has QC_SWEEP_WIDE_64_NOISE: noise trajectories are served, any generators; their gradients with wide64_grad (qc_sweep64_noise.hip)
     bool wide_par = false;       // mfma32 and wide has QC_SWEEP_WIDE_PARAMS: parameter gradients and cotangents are served (qc_sweep32_grad.hip)
     bool wide_stored = false;    // mfma32 and wide has QC_SWEEP_WIDE_STORED: with `stored`, reverse mode by the 2 x 2-tile stored-state walk (qc_sweep32_open_grad.hip)
     bool wide_tangent = false;   // mfma32 and wide has QC_SWEEP_WIDE_TANGENT: pushforwards are served (qc_sweep32_jvp.hip)
@@ -29,7 +30,7 @@ struct qc_sweep : qc_side {
     std::string jvp_why;
     bool hvp_ok = false;         // the Hessian product's scope (qc_sweep_hvp.hip): the closed scope in the "mfma16-sweep" form, and in the "mfma32-sweep" form with wide_hessian
     std::string hvp_why;
-    bool noise_ok = false;       // the noise sweep's scope (qc_sweep_noise.hip): "mfma16-sweep", n_pert >= 1, m + n_pert <= 8 tiles; "mfma32-sweep" with wide_noise, n_pert >= 1
+    bool noise_ok = false;       // the noise sweep's scope (qc_sweep_noise.hip): "mfma16-sweep", n_pert >= 1, m + n_pert <= 8 tiles; "mfma32-sweep" with wide_noise, n_pert >= 1; "mfma64-sweep" with wide64_noise, n_pert >= 1
     std::string noise_why;
     bool noise_grad_ok = false;  // its gradient's scope: the noise scope and the gradient's together
     std::string noise_grad_why;  // the noise scope's reason, else the gradient's own
@@ -213,7 +214,8 @@ void qc_sweep_launch_fid_seed(qc_sweep* h, int64_t S, int64_t n_chunks, const do
 void qc_sweep_launch_weighted(qc_sweep* h, int64_t S, const double* gsamp, const double* dweights, const double* dfids, double* dgrad, double* dJ,
                               hipStream_t st);
 // the noise sweep's scope (qc_sweep_noise.hip): the "mfma16-sweep" form with n_pert >= 1 and m + n_pert <= 8, and the "mfma32-sweep" form
-// of a descriptor whose wide has QC_SWEEP_WIDE_NOISE with n_pert >= 1 (nothing is resident there: no tile limit)
+// of a descriptor whose wide has QC_SWEEP_WIDE_NOISE with n_pert >= 1 (nothing is resident there: no tile limit), and the "mfma64-sweep"
+// form of one whose wide has QC_SWEEP_WIDE_64_NOISE with n_pert >= 1 (likewise)
 bool qc_sweep_noise_scope(const qc_sweep_desc* d, std::string* why);
 // "mfma32-sweep" handles with `wide_noise` (qc_sweep32_noise.hip): grows h->dTot and launches qc_sweep32_noise_kernel on `st` (totals as
 // qc_sweep32_launch_totals), and the backward walk qc_sweep32_noise_grad_kernel (gs: S x (T-1) x nd, gn: S x (T-1) x p, either may be
@@ -222,3 +224,11 @@ int qc_sweep32_noise_launch_totals(qc_sweep* h, const double* dZ, int64_t S, con
                                    hipStream_t st, int64_t* chunk, int64_t* n_chunks);
 void qc_sweep32_noise_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dnoise,
                                   int64_t chunk, int64_t n_chunks, double* gs, double* gn, hipStream_t st);
+// "mfma64-sweep" handles with `wide64_noise` (qc_sweep64_noise.hip): grows h->dTot and launches qc_sweep64_noise_kernel on `st`, one workgroup
+// per (sample, chunk) (totals as qc_sweep64_launch_totals), and the backward walk qc_sweep64_noise_grad_kernel (gs: S x (T-1) x nd,
+// gn: S x (T-1) x p, either may be NULL; x and lambda at the chunk ends from h->dXs / h->dLs).  QC_OK or the launch's code
+__attribute__((visibility("hidden"))) int qc_sweep64_noise_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale,
+                                                                          const double* dnoise, hipStream_t st, int64_t* chunk, int64_t* n_chunks);
+__attribute__((visibility("hidden"))) int qc_sweep64_noise_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale,
+                                                                        const double* dnoise, int64_t chunk, int64_t n_chunks, double* gs, double* gn,
+                                                                        hipStream_t st);

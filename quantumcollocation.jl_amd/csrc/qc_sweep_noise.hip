@@ -27,8 +27,10 @@
 //
 // "mfma32-sweep" handles whose descriptor sets QC_SWEEP_WIDE_NOISE are routed to the two kernels of qc_sweep32_noise.hip (the same lane
 // map on 2 x 2 tiles; nothing is resident there, so no tile limit); the checks, the staging and the entry points below are shared.
+// "mfma64-sweep" handles whose descriptor sets QC_SWEEP_WIDE_64_NOISE are routed to the two kernels of qc_sweep64_noise.hip (4 x 4 tiles in
+// LDS, one workgroup per item; up to 16 + 8 generators), the gradient only with QC_SWEEP_WIDE_64_GRAD as well; the same shared parts.
 //
-// Out of scope: "mfma32-sweep" handles without that bit and "rollout-per-sample" handles, pullbacks / pushforwards / Hessian products with noise, several devices.
+// Out of scope: "mfma32-sweep" / "mfma64-sweep" handles without their bit and "rollout-per-sample" handles, pullbacks / pushforwards / Hessian products with noise, several devices.
 //
 // gfx950 cross-compile: see the table in DESIGN.md ("Noise-trajectory sweeps"); no private segment, no spills in any instantiation.
 #include <math.h>
@@ -245,6 +247,7 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qc_sweep_noise_grad_kernel(con
 int noise_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dnoise, hipStream_t st,
                         int64_t* chunk_out, int64_t* n_chunks_out) {
     if (h->wide_noise) return qc_sweep32_noise_launch_totals(h, dZ, S, dtheta, dscale, dnoise, st, chunk_out, n_chunks_out);      // the only mfma32 handles in scope
+    if (h->wide64_noise) return qc_sweep64_noise_launch_totals(h, dZ, S, dtheta, dscale, dnoise, st, chunk_out, n_chunks_out);    // the only mfma64 handles in scope
     SweepParams P;
     if (int rc = qc_sweep_plan_totals(h, S, h->dTot, 256, &P, chunk_out, n_chunks_out)) return rc;
 #define QC_NOISE_LAUNCH(M_) \
@@ -332,6 +335,8 @@ int noise_grad_launch(qc_sweep* h, const char* who, const double* dZ, const doub
     qc_sweep_launch_fid_seed(h, S, n_chunks, dinit, dfids, st);
     if ((want_grad || dgrad_noise) && h->wide_noise) {
         qc_sweep32_noise_launch_walk(h, dZ, S, dtheta, dscale, dnoise, chunk, n_chunks, want_grad ? gsamp : nullptr, dgrad_noise, st);
+    } else if ((want_grad || dgrad_noise) && h->wide64_noise) {
+        if ((rc = qc_sweep64_noise_launch_walk(h, dZ, S, dtheta, dscale, dnoise, chunk, n_chunks, want_grad ? gsamp : nullptr, dgrad_noise, st))) return rc;
     } else if (want_grad || dgrad_noise) {
         const unsigned grid = qc_sweep_grid(P, kWaves);
         double* gs = want_grad ? gsamp : nullptr;
@@ -353,9 +358,9 @@ bool qc_sweep_noise_scope(const qc_sweep_desc* d, std::string* why) {
     const qc_sweep_form form = qc_sweep_desc_form(d);
     if (form == QC_SWEEP_FORM_32 && !(d->wide & QC_SWEEP_WIDE_NOISE)) { *why = "noise trajectories are not served in the mfma32-sweep form"; return false; }
     if (form == QC_SWEEP_FORM_PER_SAMPLE) { *why = qc_sweep_per_sample_why(d); return false; }
-    if (form == QC_SWEEP_FORM_64) { *why = qc_sweep_form64_unserved(d, "noise trajectories"); return false; }
+    if (form == QC_SWEEP_FORM_64 && !(d->wide & QC_SWEEP_WIDE_64_NOISE)) { *why = qc_sweep_form64_unserved(d, "noise trajectories"); return false; }
     if (d->n_pert == 0) { *why = "the handle has no perturbations (n_pert = 0): noise enters through the perturbation generators"; return false; }
-    if (form == QC_SWEEP_FORM_16 && d->m + d->n_pert > kNTiles) {      // the wide form keeps no tile resident: m <= 8 and n_pert <= QC_MAX_PERT, up to 16 generators
+    if (form == QC_SWEEP_FORM_16 && d->m + d->n_pert > kNTiles) {      // the wide forms keep no tile resident: m <= 8 (mfma64-sweep: 16) and n_pert <= QC_MAX_PERT, up to 16 (24) generators
         *why = "m + n_pert = " + std::to_string(d->m) + " + " + std::to_string(d->n_pert) + " exceeds the 8 tiles a wavefront keeps in registers";
         return false;
     }

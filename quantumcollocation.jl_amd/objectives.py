@@ -743,13 +743,14 @@ class SweepInfidelityObjective:
     wide64, wide64_grad  as `RolloutSweep` (only with `wide`; `wide64_grad` only with `wide64`): all three True serve closed systems of
                 32 < 2N <= 64 (17 .. 32 levels: three coupled transmons, 5 qubits) in the "mfma64-sweep" form
     wide64_params  as `RolloutSweep` (only with `wide64_grad`): the handle also serves `param_grad` and parameter cotangents there
+    wide64_noise  as `RolloutSweep` (only with `wide64`): what `SweepNoiseInfidelityObjective` needs in the "mfma64-sweep" form; nothing here reads it
     goal_ket    density component only: [Re psi; Im psi] (2 levels entries) of the pure state the fidelity compares with"""
     _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
 
     def __init__(self, traj: NamedTrajectory, system, perturbations, theta, scale=None, weights=None, state_name: str = "Ũ⃗",
                  control_name: str = "a", subspace=None, form: str = "abs", device: int = 0, wide: bool = False,
-                 stored_states: bool = False, goal_ket=None, wide_stored: bool = False, wide_noise: bool = False, wide64: bool = False,
-                 wide64_grad: bool = False, wide64_params: bool = False):
+                 stored_states: bool = False, goal_ket=None, wide_stored: bool = False, wide_noise: bool = False, wide64_noise: bool = False,
+                 wide64: bool = False, wide64_grad: bool = False, wide64_params: bool = False):
         from .rollouts import RolloutSweep
         self._sweep = None
         if state_name not in traj.components:
@@ -802,7 +803,7 @@ class SweepInfidelityObjective:
                           off_a=traj.offset(control_name), off_dt=traj.offset(traj.timestep) if free else -1,
                           dt_fixed=None if free else float(traj.timestep), global_dim=traj.global_dim, device=device, wide=wide,
                           stored_states=stored_states, wide_stored=wide_stored, wide_noise=wide_noise, wide64=wide64, wide64_grad=wide64_grad,
-                          wide64_params=wide64_params)
+                          wide64_params=wide64_params, wide64_noise=wide64_noise)
         self._sweep = sw
         self.stored_states = sw.stored_states
         self.wide_stored = sw.wide_stored
@@ -862,10 +863,13 @@ class SweepNoiseInfidelityObjective(SweepInfidelityObjective):
     theta       S x len(perturbations) or None (zeros);  scale  S x n_drives or None;  weights  S values or None (1/S each)
     wide, wide_noise  as `RolloutSweep`: both True serve systems of 16 < 2N <= 32 (two three-level transmons, a 4-qubit register) in the
                 "mfma32-sweep" form, with up to 8 drives and 8 perturbations
+    wide64, wide64_grad, wide64_noise  as `RolloutSweep` (only with `wide`): all four True serve closed systems of 32 < 2N <= 64 (three coupled
+                three-level transmons, a 5-qubit register) in the "mfma64-sweep" form, with up to 16 drives and 8 perturbations
     `noise_sensitivity(Z)` returns dF_s/dnoise[s, t, j], S x (T-1) x len(perturbations): the time-domain filter function of the pulse."""
 
     def __init__(self, traj: NamedTrajectory, system, perturbations, noise, theta=None, scale=None, weights=None, state_name: str = "Ũ⃗",
-                 control_name: str = "a", subspace=None, form: str = "abs", device: int = 0, wide: bool = False, wide_noise: bool = False):
+                 control_name: str = "a", subspace=None, form: str = "abs", device: int = 0, wide: bool = False, wide_noise: bool = False,
+                 wide64: bool = False, wide64_grad: bool = False, wide64_noise: bool = False):
         p = len(perturbations)
         if noise is None:
             raise ValueError("noise is required: S x (T-1) x len(perturbations)")
@@ -877,7 +881,8 @@ class SweepNoiseInfidelityObjective(SweepInfidelityObjective):
         if theta is None:
             theta = np.zeros((noise.shape[0], p))
         super().__init__(traj, system, perturbations, theta, scale=scale, weights=weights, state_name=state_name, control_name=control_name,
-                         subspace=subspace, form=form, device=device, wide=wide, wide_noise=wide_noise)
+                         subspace=subspace, form=form, device=device, wide=wide, wide_noise=wide_noise, wide64=wide64,
+                         wide64_grad=wide64_grad, wide64_noise=wide64_noise)
         sw = self._sweep
         if self.S != noise.shape[0]:
             sw.close()

@@ -240,37 +240,48 @@ class RolloutSweep:
                    transmons, a five-level Lindblad model -- run on the matrix cores as well ("mfma64-sweep": one workgroup per
                    (sample, chunk of intervals), the matrices in LDS) instead of one rollout per sample.  That form serves `eval` and
                    `eval_device` only: `grad`, `param_grad`, `vjp`, `jvp`, `hvp` and the noise sweeps refuse there, naming the form
-                   (`wide64_grad` adds `grad` and `vjp`, `wide64_params` their parameter outputs, `wide64_tangent` `jvp`).
+                   (`wide64_grad` adds `grad` and `vjp`, `wide64_params` their parameter outputs, `wide64_tangent` `jvp`,
+                   `wide64_noise` the noise sweeps).
                    Nothing changes at 2N <= 32, and nothing changes without it.
     wide64_grad    True (only with `wide64`): an "mfma64-sweep" handle of a closed system (antisymmetric generators, at most 32 state
                    columns: a full unitary of 32 levels fits) also serves `grad`, `vjp`, their device forms and the backward rule of
                    `finals_autograd`, by the closed adjoint walk on 4 x 4 tiles.  `param_grad`, the `params` of `vjp`, `stored_states`,
-                   `hvp` and the noise sweeps still refuse there, naming the form; `jvp` is `wide64_tangent`'s to serve.  Nothing
+                   `hvp` and the noise sweeps still refuse there, naming the form; `jvp` is `wide64_tangent`'s to serve, the noise
+                   sweeps `wide64_noise`'s.  Nothing
                    else changes, nothing changes at 2N <= 32, and nothing changes without it.
     wide64_params  True (only with `wide64_grad`): such a handle also serves `param_grad`, `param_grad_device`, the `params` of `vjp` and
                    the theta / scale cotangents of `finals_autograd`, by the parameter flavour of the same walk: one call gives
                    dF_s/dtheta and dF_s/dscale of every sample (dF_s/dscale is taken before the factor scale, so it is defined at
                    scale = 0).  `stored_states`, `hvp` and the noise sweeps still refuse there (`jvp` is `wide64_tangent`'s to
-                   serve).  Without it `param_grad` and the `params` of `vjp` refuse there, as they did; nothing else changes, and
+                   serve, the noise sweeps `wide64_noise`'s).  Without it `param_grad` and the `params` of `vjp` refuse there, as they did; nothing else changes, and
                    nothing changes at 2N <= 32.
     wide64_tangent True (only with `wide64`; it needs neither `wide64_grad` nor `wide64_params`): an "mfma64-sweep" handle also serves
                    `jvp`, `jvp_device` and the forward-mode rule of `finals_autograd` -- any generators, open systems included (a
                    five-level Lindblad model: 2N = 50), any fidelity, states of 2N x cols <= 2048 entries (every full unitary of the
                    form) -- by the paired exponential on 4 x 4 tiles: three forward sweeps by the instruction count.  Above that size
-                   `jvp` refuses, naming the form, 2N and the size.  `hvp`, the noise sweeps and `stored_states` still refuse there.
-                   Without it `jvp` refuses there, as it did; nothing else changes, and nothing changes at 2N <= 32."""
+                   `jvp` refuses, naming the form, 2N and the size.  `hvp`, the noise sweeps (`wide64_noise`'s to serve) and
+                   `stored_states` still refuse there.
+                   Without it `jvp` refuses there, as it did; nothing else changes, and nothing changes at 2N <= 32.
+    wide64_noise   True (only with `wide64`; it needs none of `wide64_grad`, `wide64_params`, `wide64_tangent`): an "mfma64-sweep"
+                   handle also serves `noise_eval` and `noise_eval_device` with at least one perturbation -- up to 16 drives and 8
+                   perturbations, any generators, open systems included, any fidelity or none.  `noise_grad` and its device form
+                   also need `wide64_grad` and its scope (a closed system, at most 32 state columns, a unitary or ket fidelity);
+                   without it they refuse with the gradient's reason.  At zero noise the outputs carry the bits of `eval` / `grad`
+                   on the same handle.  `hvp` and `stored_states` still refuse there.  Without it the noise sweeps refuse there,
+                   as they did; nothing else changes, and nothing changes at 2N <= 32."""
 
     def __init__(self, system, perturbations, T: int, cols: Optional[int] = None, goal=None, fid_kind=None, subspace=None,
                  fid_form: int = _lib.QC_FID_FORM_ABS, zdim: Optional[int] = None, off_a: int = 0, off_dt: Optional[int] = None,
                  dt_fixed: Optional[float] = None, global_dim: int = 0, device: int = 0, wide: bool = False,
                  stored_states: bool = False, wide_params: bool = False, wide_stored: bool = False, wide_tangent: bool = False,
-                 wide_noise: bool = False, wide_hessian: bool = False, wide64: bool = False, wide64_grad: bool = False,
-                 wide64_tangent: bool = False, wide64_params: bool = False):
+                 wide_noise: bool = False, wide_hessian: bool = False, wide64: bool = False, wide64_noise: bool = False,
+                 wide64_grad: bool = False, wide64_tangent: bool = False, wide64_params: bool = False):
         self._h = None
         flags = (   # (keyword, given, its bit of qc_sweep_desc.wide, what it needs, the refusal without that)
             ("wide64_params", wide64_params, _lib.QC_SWEEP_WIDE_64_PARAMS, wide64_grad, "wide64_params=True needs wide64_grad=True"),
             ("wide64_grad", wide64_grad, _lib.QC_SWEEP_WIDE_64_GRAD, wide64, "wide64_grad=True needs wide64=True"),
             ("wide64_tangent", wide64_tangent, _lib.QC_SWEEP_WIDE_64_TANGENT, wide64, "wide64_tangent=True needs wide64=True"),
+            ("wide64_noise", wide64_noise, _lib.QC_SWEEP_WIDE_64_NOISE, wide64, "wide64_noise=True needs wide64=True"),
             ("wide64", wide64, _lib.QC_SWEEP_WIDE_64, wide, "wide64=True needs wide=True"),
             ("wide_hessian", wide_hessian, _lib.QC_SWEEP_WIDE_HESSIAN, wide, "wide_hessian=True needs wide=True"),
             ("wide_noise", wide_noise, _lib.QC_SWEEP_WIDE_NOISE, wide, "wide_noise=True needs wide=True"),
@@ -353,6 +364,15 @@ class RolloutSweep:
     @wide64_tangent.setter
     def wide64_tangent(self, given):
         self._wide64_tangent = bool(given)
+
+    @property
+    def wide64_noise(self) -> bool:
+        """Whether the handle was made with `wide64_noise` (kept outside the instance's public flags, as `wide64_grad` is)."""
+        return self._wide64_noise
+
+    @wide64_noise.setter
+    def wide64_noise(self, given):
+        self._wide64_noise = bool(given)
 
     def _scope(self, supported):
         """(served?, the library's reason why not or None) from a `qc_sweep_desc_*_supported` function."""
@@ -717,8 +737,9 @@ class RolloutSweep:
     def noise_supported(self) -> bool:
         """Do `noise_eval` / `noise_eval_device` serve this handle?  (`qc_sweep_desc_noise_supported`: the "mfma16-sweep" form, at least
         one perturbation, drives and perturbations together at most 8; or the "mfma32-sweep" form of a handle made with `wide_noise`, at
-        least one perturbation, no limit on drives and perturbations together.)  `noise_unsupported_reason` says why not.  `noise_grad` also
-        needs `grad_supported`."""
+        least one perturbation, no limit on drives and perturbations together; or the "mfma64-sweep" form of a handle made with
+        `wide64_noise`, likewise.)  `noise_unsupported_reason` says why not.  `noise_grad` also needs `grad_supported` (in the
+        "mfma64-sweep" form: `wide64_grad`)."""
         return self._scope(_lib.lib.qc_sweep_desc_noise_supported)[0]
 
     @property
@@ -917,13 +938,15 @@ def rollout_sweep(init, controls, dts, system, perturbations, theta, scale=None,
 
 
 def rollout_noise_sweep(init, controls, dts, system, perturbations, noise, theta=None, scale=None, cols: Optional[int] = None, goal=None,
-                        fid_kind=None, subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS, wide: bool = False):
+                        fid_kind=None, subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS, wide: bool = False,
+                        wide64: bool = False):
     """(finals, fids) of S rollouts whose perturbation amplitudes change from interval to interval: in interval t sample s sees
     theta[s, j] + noise[s, t, j] on perturbation j.  noise is S x (T-1) x len(perturbations) (S x (T-1) for one perturbation), theta
     S x len(perturbations) or None (zeros); everything else as `rollout_sweep`.  `wide=True` serves 16 < 2N <= 32 on the matrix cores
-    (the handle is made with `wide` and `wide_noise`)."""
+    (the handle is made with `wide` and `wide_noise`); `wide=True, wide64=True` serves 32 < 2N <= 64 with up to 16 drives as well (the
+    handle is made with `wide64` and `wide64_noise` too)."""
     return _one_shot(RolloutSweep.noise_eval, init, controls, dts, system, perturbations, (noise, theta, scale), cols, goal=goal, fid_kind=fid_kind,
-                     subspace=subspace, fid_form=fid_form, device=device, wide=wide, wide_noise=wide)
+                     subspace=subspace, fid_form=fid_form, device=device, wide=wide, wide_noise=wide, wide64=wide64, wide64_noise=wide64)
 
 
 def rollout_sweep_parameter_gradient(init, controls, dts, system, perturbations, theta, scale=None, cols: Optional[int] = None, goal=None,
