@@ -9,8 +9,10 @@ dropped), the .amdhsa_kernel block and the metadata (VGPRs, AGPRs, SGPRs, LDS, s
 
 Kernels named by --changed (default: the four seed kernels; a template's name without its arguments names every instantiation) are
 reported with their metadata on both sides, wherever they live, and must agree in everything that decides occupancy (VGPRs, AGPRs, LDS,
-scratch, spills: none) and in their MFMA count; SGPRs and the instruction count may move.  Every other kernel must be identical.  The
-exit status says whether all of that holds."""
+scratch, spills: none) and in their MFMA count; SGPRs and the instruction count may move.  With --vgpr-ceiling N a changed kernel's VGPR
+count may also fall, never rise, and never lie above N (the mfma64 form: 1024 threads, four waves a SIMD, N = 128).  --renamed
+PARENT=NEW,... pairs changed kernels whose name differs between the trees.  Every other kernel must be identical.  The exit status says
+whether all of that holds."""
 import argparse
 import os
 import re
@@ -69,8 +71,13 @@ def main():
     ap.add_argument("parent")
     ap.add_argument("new")
     ap.add_argument("--changed", default=SEEDS)
+    ap.add_argument("--vgpr-ceiling", type=int, default=None, metavar="N",
+                    help="a changed kernel's VGPR count may fall (never rise, never exceed N); without it any change counts as moved")
+    ap.add_argument("--renamed", default="", metavar="PARENT=NEW,...",
+                    help="changed kernels whose name differs between the trees: the parent's is compared with, and shown as, the new one")
     a = ap.parse_args()
     changed = set(a.changed.split(","))
+    renamed = dict(pair.split("=") for pair in a.renamed.split(",") if pair)
     sides = [{}, {}]
     differ = same = moved = 0
     for f in FILES:
@@ -78,9 +85,9 @@ def main():
         for name in sorted(set(A) | set(B)):
             p = plain(name)
             if p in changed or p.split("<")[0] in changed:
-                for side, K in zip(sides, (A, B)):
+                for side, K, to in zip(sides, (A, B), (renamed, {})):
                     if name in K:
-                        side[p] = (f, K[name][2])
+                        side[to.get(p, p)] = (f, K[name][2])
             elif name in A and name in B and A[name] == B[name]:
                 same += 1
                 print(f"{f}.hip  {p}: identical instructions and metadata  ({show(A[name][2])})")
@@ -93,10 +100,15 @@ def main():
                 print(f"{p}  {label} ({side[p][0]}.hip): {show(side[p][1])}")
         if p in sides[0] and p in sides[1]:
             A, B = sides[0][p][1], sides[1][p][1]
-            off = [k for k in FIXED if A[k] != B[k]] + [k for k in ("sgpr_spill_count", "vgpr_spill_count") if B[k]]
+            fell = a.vgpr_ceiling is not None and B["vgpr_count"] < A["vgpr_count"] and B["vgpr_count"] <= a.vgpr_ceiling
+            off = [k for k in FIXED if A[k] != B[k] and not (fell and k == "vgpr_count")]
+            off += [k for k in ("sgpr_spill_count", "vgpr_spill_count") if B[k]]
+            if a.vgpr_ceiling is not None and B["vgpr_count"] > a.vgpr_ceiling:
+                off.append(f"vgpr_count above the ceiling of {a.vgpr_ceiling}")
             if off:
                 moved += 1
-            print(f"{p}  " + (f"RESOURCES MOVED: {', '.join(off)}" if off else "resources and MFMA count equal, no spills") +
+            ok = f"VGPRs fell {A['vgpr_count']} -> {B['vgpr_count']}, other resources" if fell else "resources"
+            print(f"{p}  " + (f"RESOURCES MOVED: {', '.join(off)}" if off else f"{ok} and MFMA count equal, no spills") +
                   f"; SGPR {B['sgpr_count'] - A['sgpr_count']:+d}, instructions {B['instructions'] - A['instructions']:+d}")
         else:
             moved += 1

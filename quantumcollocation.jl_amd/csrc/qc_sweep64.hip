@@ -18,10 +18,22 @@
 // The chunk total leaves as a full 64 x 64 column-major matrix (S x n_chunks x 4096 doubles of handle scratch);
 // qc_sweep_finish_kernel (qc_sweep.hip) chains the totals with ld = 64.
 //
+// Noise-trajectory sweeps (handles that set QC_SWEEP_WIDE_64_NOISE; qc_sweep_noise.hip has the model and the zero-noise contract) are the
+// flavour <true> of the same kernel: in interval t of sample s
+//     G_{s,t} = G_drift + sum_j (theta[s,j] + xi[s,t,j]) P_j + sum_k c[s,k] a_{t,k} G_k.
+// Nothing is resident per generator and the perturbation images follow the drives in the image buffer, so a per-interval perturbation is a
+// longer loop bound, mt = m + p <= 24, and another coefficient source per lane (qc_sweep64_common.h: drive_lane for <false>, lane_coef for
+// <true>, behind `if constexpr`; one load per lane and interval, requested one interval ahead).  Generator u < m is drive u, coefficient
+// c[s,u] a_{t,u}, the product rounded as <false> rounds av * cl; generator m + j is perturbation j, coefficient noise[(s (T-1) + t) p + j],
+// factor 1.  base_elems folds theta; the drives are added in ascending k, THEN the perturbations in ascending j.  At xi = +0.0 the extra
+// fmas leave every value as it was (a -0 may become +0, nothing else) and everything behind the generator is the same code, so finals / fids
+// of qc_sweep_noise_eval carry the bits of qc_sweep_eval on the same handle.
+//
 // Gradients and pullbacks of closed systems in this form: qc_sweep64_grad.hip, on handles that also set QC_SWEEP_WIDE_64_GRAD (without it
 // their entry points answer QC_ERR_UNSUPPORTED, as they did); their parameter outputs with QC_SWEEP_WIDE_64_PARAMS as well.  Pushforwards in
-// this form: qc_sweep64_jvp.hip, on handles that set QC_SWEEP_WIDE_64_TANGENT (any generators); noise sweeps: qc_sweep64_noise.hip, on handles that set QC_SWEEP_WIDE_64_NOISE.  Out of scope in this form: Hessian
-// products (their entry points answer QC_ERR_UNSUPPORTED on such a handle), a state-action form that skips the propagator for kets, more than 16 drives, 2N > 64.
+// this form: qc_sweep64_jvp.hip, on handles that set QC_SWEEP_WIDE_64_TANGENT (any generators); the noise sweeps' gradient walk:
+// qc_sweep64_noise.hip.  Out of scope in this form: Hessian products (their entry points answer QC_ERR_UNSUPPORTED on such a handle), a
+// state-action form that skips the propagator for kets, more than 16 drives, 2N > 64.
 #include <math.h>
 
 #include <string>
@@ -29,56 +41,73 @@
 #include "qc_mfma_common.h"
 #include "qc_side.h"
 #include "qc_sweep64_common.h"
+#include "qc_sweep64_launch.h"
 #include "qc_sweep_internal.h"
 
 namespace {
 
 using namespace qc_sweep64;
 
+// NOISE = false: the m drives, lane l of every wave fetching drive min(l, m - 1)'s control out of the knot (drive_lane; `noise` unused).
+// NOISE = true, the noise sweeps: the mt = m + p generators, lane l fetching generator min(l, mt - 1)'s coefficient through its own pointer
+// and stride (lane_coef), stepped per interval.  Either way generator() broadcasts lane u's; everything behind it is written once.
+template <bool NOISE>
 __global__ __launch_bounds__(kThreads, 1) void qc_sweep_mfma64_kernel(const SweepParams P, const double* __restrict__ Z,
                                                                         const double* __restrict__ theta, const double* __restrict__ scale,
-                                                                        double* __restrict__ tot) {
+                                                                        const double* __restrict__ noise, double* __restrict__ tot) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     __shared__ double red[16];
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, j = lane & 15;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6), I = w & 3, J = w >> 2;
     const long long item = blockIdx.x;
     const ChunkRange ch = chunk_range(item, P.n_chunks, P.chunk, P.n_int);
-    const int t0 = ch.t0, t1 = ch.t1, m = P.m;
+    const int t0 = ch.t0, t1 = ch.t1, m = P.m, mt = NOISE ? m + P.p : m;
     const long long s = ch.s;
     const bool ft = P.off_dt >= 0;
 
-    // ---- once per item: the sample's base matrix, W = I -----------------------------------------------------------------------------
+    // ---- once per item: the sample's base matrix, the lane's coefficient source, W = I -----------------------------------------------
     double base[4];
     base_elems(P.img, m, P.p, theta, s, tid, base);
-    // lane l holds the sample's factor of drive min(l, m-1); folded into the control values
-    const int kl = lane < m ? lane : (m > 0 ? m - 1 : 0);
-    const double cl = (scale && m > 0) ? scale[s * m + kl] : 1.0;
+    int kl = 0, cstride = 0;      // <false>: the lane's drive; <true>: its pointer's step
+    const double* cp = nullptr;
+    double cl, av;
+    if constexpr (NOISE) {
+        const LaneCoef lc = lane_coef(P, lane, s, t0, Z, scale, noise);
+        cp = lc.cp, cstride = lc.stride, cl = lc.cl;
+    } else {
+        const DriveLane d = drive_lane(scale, m, s, lane);
+        kl = d.kl, cl = d.cl;
+    }
     int oY = 0, oW = 3 * kMat;      // the buffers' roles; Ra = kMat, Rb = 2 kMat
 #pragma unroll
     for (int e = 0; e < 4; ++e) sm[oW + lds_at(tid, e)] = on_diagonal(tid, e) ? 1.0 : 0.0;
 
     const double* __restrict__ z = Z + (long long)t0 * P.zdim;
-    double av = m > 0 ? z[P.off_a + kl] : 0.0;
+    if constexpr (NOISE) av = *cp;
+    else av = drive_value(z, P.off_a, m, kl);
     const double hfix = opaque_scalar(P.dt_fixed);      // keeps the two arms apart: no flat load (qc_mfma_common.h)
     double h = ft ? z[P.off_dt] : hfix;
 #pragma unroll 1
     for (int t = t0; t < t1; ++t) {
-        // the next interval's controls and timestep are requested before this interval's products
+        // the next interval's coefficients and timestep are requested before this interval's products
         const double* __restrict__ zn = Z + (long long)(t + 1 < t1 ? t + 1 : t) * P.zdim;
-        const double av_n = m > 0 ? zn[P.off_a + kl] : 0.0;
+        double av_n;
+        if constexpr (NOISE) {
+            if (t + 1 < t1) cp += cstride;
+            av_n = *cp;
+        } else {
+            av_n = drive_value(zn, P.off_a, m, kl);
+        }
         const double h_n = ft ? zn[P.off_dt] : hfix;
         double G[4];
-        generator(P.img, m, av * cl, base, tid, G);
-        const int sq = squarings(red, G, h, lane, w);      // its barrier: every wave has left the previous interval's products
+        generator(P.img, mt, av * cl, base, tid, G);      // the drives in ascending k, then (<true>) the perturbations in ascending j
+        const int sq = squarings(red, G, h, lane, w);      // barrier S: every wave has left the previous interval's products
         const double hs = h * ldexp(1.0, -sq);
         // Horner: R_deg+1 = I/deg!,  R_k = Y R_k+1 + I/(k-1)!   (the last coefficient is exactly 1: a zero generator gives the identity bits)
         int oR = kMat, oN = 2 * kMat;
-        // These writes rely on the barrier inside squarings(): it orders them behind the previous interval's last product, which read E
-        // (in Ra or Rb) and the buffer that is Y now (the only product without a barrier of its own behind it).  red[] needs both kinds of
-        // barrier: the one in squarings() stands between its writes and their reads, and the barrier below and the product barriers
-        // stand between those reads and the next interval's writes.  A kernel that reuses the header must keep at least one workgroup
-        // barrier between a call of squarings() and the next.
+        // These writes rely on S: it orders them behind the previous interval's last product, which read E (in Ra or Rb) and the buffer
+        // that is Y now (the only product without a barrier of its own behind it).  The barrier below and the product barriers are the
+        // further barriers that red[] needs between two calls of squarings() (qc_sweep64_common.h).
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             sm[oY + lds_at(tid, e)] = hs * G[e];
@@ -88,7 +117,7 @@ __global__ __launch_bounds__(kThreads, 1) void qc_sweep_mfma64_kernel(const Swee
 #pragma unroll 1
         for (int k = kDeg; k >= 1; --k) {
             tile_mul(sm + oY, sm + oR, sm + oN, I, J, g, j, kInvFact[k - 1]);
-            __syncthreads();
+            __syncthreads();      // a product reads two buffers and writes a third: one barrier per product
             const int o = oR; oR = oN; oN = o;
         }
 #pragma unroll 1
@@ -121,10 +150,14 @@ int qc_sweep64_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const dou
                              int64_t* n_chunks_out) {
     SweepParams P;
     if (int rc = qc_sweep_plan_totals(h, S, h->dTot, kImg, &P, chunk_out, n_chunks_out)) return rc;
-    // per launch: the attribute belongs to the (function, device) pair and the call is a host-side table update
-    QC_SIDE_HIP(h, *qc_sweep_err_slot(), hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep_mfma64_kernel),
-                                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-    hipLaunchKernelGGL(qc_sweep_mfma64_kernel, dim3((unsigned)P.items), dim3(kThreads), kLdsBytes, st, P, dZ, dtheta, dscale, h->dTot.p);
-    QC_SIDE_HIP(h, *qc_sweep_err_slot(), hipGetLastError());      // a launch that fails (the LDS opt-in refused) is reported here, under this kernel's name
+    QC_SWEEP64_LAUNCH(h, qc_sweep_mfma64_kernel<false>, kLdsBytes, P, st, dZ, dtheta, dscale, (const double*)nullptr, h->dTot.p);
+    return QC_OK;
+}
+
+int qc_sweep64_noise_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dnoise,
+                                   hipStream_t st, int64_t* chunk_out, int64_t* n_chunks_out) {
+    SweepParams P;
+    if (int rc = qc_sweep_plan_totals(h, S, h->dTot, kImg, &P, chunk_out, n_chunks_out)) return rc;
+    QC_SWEEP64_LAUNCH(h, qc_sweep_mfma64_kernel<true>, kLdsBytes, P, st, dZ, dtheta, dscale, dnoise, h->dTot.p);
     return QC_OK;
 }

@@ -19,28 +19,25 @@
 //       u = (h / 2^sq) R^T lambda (64 x nc): 4 nct tile chains of 16 for u and nct x 4 MFMAs a tile for x u^T (nct = 1 or 2 column tiles);
 //   (b) a wave's tile of a product is 4 registers a lane, so R and dR are updated IN PLACE: every wave holds its tiles of the new R, dR in
 //       registers across a barrier (all reads of the old ones are done), writes them over the old ones, and a second barrier publishes them.
+// The LDS map, (a), (b) and the exponential pair itself are qc_sweep64_common.h's (walk_lds, exp_pair), shared with the noise walk of
+// qc_sweep64_noise.hip; so are the state load, the timestep derivative (kt_dot) and the 16-wave sum (part_sum).
 // Barriers of one interval, in order, and what each stands between:
 //     S   inside squarings(): behind it every wave has left the previous interval -- its ZT and E^T x products (the last reads of R, dR)
 //         are in front of Ba already; S stands between the writes of x, lambda (after Ba) and their reads by the timestep derivative,
 //         and between red[]'s writes and reads.  Y, R = I/8!, dR = 0 are written behind S.
-//     H0  publishes Y, R, dR.
-//     per Horner step k = 8 .. 1:   u = hs R^T lambda (waves 0 .. 4 nct - 1; reads R, lambda; writes u)
-//     U   publishes u;              R' = Y R + I/(k-1)!,  dR' = Y dR + x u^T   into registers (reads Y, R, dR, x, u)
-//     P   every read of R, dR, u of this step is done;   R <- R', dR <- dR'
-//     W   publishes R, dR (the next step's u reads R; u is overwritten only behind W)
-//     per squaring:   E' = E E, dE' = E dE + dE E into registers;  P;  write;  W      (the same two barriers)
+//     H0, U / P / W per Horner step, P / W per squaring: inside exp_pair, argued there.
 //     tail:  ZT = E^T dE (registers), x' / lambda' = E^T x / E^T lambda (registers), the m contractions of ZT with the drive images
 //            (global memory, L2-resident), wave sums, part[w][.]
 //     Ba  every read of E, dE, x, lambda is done and part[] is complete;   x, lambda <- x', lambda';  wave 0 adds the 16 partials of each of
 //         the m + 1 values in ascending wave order and stores them with one vector store into gs[s][t][.]
-// red[] keeps the rule of qc_sweep64.hip (at least one barrier between a call of squarings() and the next: there are 25 or more); part[]
-// is written in the tail and read behind Ba, and its next writes are a whole interval of barriers later.
+// red[] keeps the rule stated at squarings() (at least one barrier between a call and the next: there are 25 or more); part[] is written
+// in the tail and read behind Ba, and its next writes are a whole interval of barriers later.
 // E^T X needs no transposition: the A operand of E^T is the column fragment of E (qc_sweep64_common.h: col_frag), conflict-free by the stride.
 //
 // MFMAs per interval and workgroup, nct = ceil(nc / 16):  8 Horner steps x (16 x (32 + 4 nct) + 4 nct x 16) + sq x 16 x 48 + 16 x 16 (ZT)
 // + 8 nct x 16 (x, lambda) = (4352 + 1152 nct) + 768 sq, against the forward kernel's (9 + sq) x 256 = 2304 + 256 sq.
 // No atomics, sums in a fixed order: repeated calls give the same bits.  The stored-state walk and Hessian products are
-// not served in this form; pushforwards are qc_sweep64_jvp.hip's (QC_SWEEP_WIDE_64_TANGENT), noise sweeps qc_sweep64_noise.hip's (QC_SWEEP_WIDE_64_NOISE), which restates this walk.
+// not served in this form; pushforwards are qc_sweep64_jvp.hip's (QC_SWEEP_WIDE_64_TANGENT), noise sweeps qc_sweep64_noise.hip's (QC_SWEEP_WIDE_64_NOISE), a second walk on the same shared pieces.
 //
 // The parameter flavour <true> (handles with QC_SWEEP_WIDE_64_PARAMS; qc_sweep_grad_params*, grad_theta / grad_scale of qc_sweep_vjp*) adds,
 // per (sample, chunk), the p + m chunk shares
@@ -65,6 +62,7 @@
 #include "qc_mfma_common.h"
 #include "qc_side.h"
 #include "qc_sweep64_common.h"
+#include "qc_sweep64_launch.h"
 #include "qc_sweep_internal.h"
 
 namespace {
@@ -73,7 +71,6 @@ using namespace qc_sweep64;
 
 // values a wave leaves per interval: m + 1 <= 17; the parameter flavour adds the p <= 8 perturbation sums behind them, nd + p <= 25
 template <bool PAR> constexpr int kPartLd = PAR ? 25 : 17;
-constexpr size_t kGradLdsBytes = (size_t)(3 * kMat + 3 * kThin) * sizeof(double);      // 152 064 B
 
 // PAR = false: the per-interval derivatives only (`par` unused).  PAR = true, the parameter flavour, also accumulates the chunk's shares of
 // dF_s/dtheta_q = sum_t sum(ZT_t . P_q) and dF_s/dc_k = sum_t a_{t,k} sum(ZT_t . G_k) and stores them at the chunk's end as
@@ -90,44 +87,28 @@ __global__ __launch_bounds__(kThreads, 1) void qc_sweep64_grad_kernel(const Swee
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, j = lane & 15;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6), I = w & 3, J = w >> 2;
     const int Jc = J & 1;                   // the wave's column tile of a thin matrix
-    const bool second = J >= 2;             // waves 8 .. 15: lambda's tiles; waves 0 .. 7: x's and u's
     const long long item = blockIdx.x;
     const ChunkRange ch = chunk_range(item, P.n_chunks, P.chunk, P.n_int);
     const int t0 = ch.t0, t1 = ch.t1, m = P.m, nc = P.nc;
     const int nct = nc > 16 ? 2 : 1;
     const long long s = ch.s;
     const bool ft = P.off_dt >= 0;
-    const v4d IdB = identity_B(g, j);
     const v4d zero = {0.0, 0.0, 0.0, 0.0};
-    double* const Yb = sm;
-    double* const Rb = sm + kMat;
-    double* const dRb = sm + 2 * kMat;
-    double* const Xb = sm + 3 * kMat;
-    double* const Lb = Xb + kThin;
-    double* const Ub = Lb + kThin;
-    double* const mine = second ? Lb : Xb;      // the thin matrix whose tile (I, Jc) this wave carries through E^T
+    const WalkLds lds = walk_lds(sm);
+    double* const mine = J >= 2 ? lds.L : lds.X;      // waves 8 .. 15 carry lambda's tile (I, Jc) through E^T, waves 0 .. 7 x's
 
     // ---- once per item: the sample's base matrix, the state and the adjoint at the chunk's end (zero outside n x nc) -----------------
     double base[4];
     base_elems(P.img, m, P.p, theta, s, tid, base);
-    const int kl = lane < m ? lane : (m > 0 ? m - 1 : 0);
-    const double cl = (scale && m > 0) ? scale[s * m + kl] : 1.0;
-    {
-        const int ns = P.n * nc;
-        const double* __restrict__ xe = xs + item * ns;
-        const double* __restrict__ le = ls + item * ns;
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int idx = tid + 1024 * e, row = idx & 63, col = idx >> 6;
-            const bool in = row < P.n && col < nc;
-            Xb[col * kLd + row] = in ? xe[row + P.n * col] : 0.0;
-            Lb[col * kLd + row] = in ? le[row + P.n * col] : 0.0;
-        }
-    }
+    const DriveLane dl = drive_lane(scale, m, s, lane);
+    const int kl = dl.kl;
+    const double cl = dl.cl;
+    load_state(xs + item * (P.n * nc), P.n, nc, tid, lds.X);
+    load_state(ls + item * (P.n * nc), P.n, nc, tid, lds.L);
 
     const gptr G0 = (gptr)(unsigned long long)P.img;
     const double* __restrict__ z = Z + (long long)(t1 - 1) * P.zdim;
-    double av = m > 0 ? z[P.off_a + kl] : 0.0;
+    double av = drive_value(z, P.off_a, m, kl);
     const double hfix = opaque_scalar(P.dt_fixed);
     double h = ft ? z[P.off_dt] : hfix;
     // PAR: the images contracted per interval (drives, then perturbations: they follow each other in P.img), the values a wave leaves
@@ -148,7 +129,7 @@ __global__ __launch_bounds__(kThreads, 1) void qc_sweep64_grad_kernel(const Swee
     for (int t = t1 - 1; t >= t0; --t) {
         // the previous interval's controls and timestep are requested before this interval's products
         const double* __restrict__ zn = Z + (long long)(t > t0 ? t - 1 : t) * P.zdim;
-        const double av_n = m > 0 ? zn[P.off_a + kl] : 0.0;
+        const double av_n = drive_value(zn, P.off_a, m, kl);
         const double h_n = ft ? zn[P.off_dt] : hfix;
         double G[4];
         generator(P.img, m, av * cl, base, tid, G);
@@ -157,58 +138,14 @@ __global__ __launch_bounds__(kThreads, 1) void qc_sweep64_grad_kernel(const Swee
         // lane k < m: drive k's wave sum; lane m: the timestep's (sum KT . G, its sign at the store)
         double out = 0.0;
         if (ft && (!PAR || gs)) {
-            // sum_ab KT[a][b] G[b][a] over the thread's elements G[b = lane][a = w + 16 e], KT[a][b] = sum_c lambda[a][c] x[b][c]
-            double kt[4] = {0.0, 0.0, 0.0, 0.0};
-            for (int c = 0; c < nc; ++c) {
-                const double xv = Xb[c * kLd + lane];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) kt[e] = fma(Lb[c * kLd + w + 16 * e], xv, kt[e]);
-            }
-            double ph = 0.0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ph = fma(kt[e], G[e], ph);
-            const double dh = wave_sum(ph);
+            const double dh = kt_dot(lds.X, lds.L, nc, G, lane, w);
             out = lane == m ? dh : out;
         }
-        // Horner: R_deg+1 = I/deg!, dR_deg+1 = 0;  R_k = Y R_k+1 + I/(k-1)!,  dR_k = dY R_k+1 + Y dR_k+1
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            Yb[lds_at(tid, e)] = hs * G[e];
-            Rb[lds_at(tid, e)] = on_diagonal(tid, e) ? kInvFact[kDeg] : 0.0;
-            dRb[lds_at(tid, e)] = 0.0;
-        }
-        __syncthreads();      // H0
-#pragma unroll 1
-        for (int k = kDeg; k >= 1; --k) {
-            if (!second && Jc < nct) {
-                const v4d u = chain<kColStep, kColStep, 16>(col_frag(Rb, I, g, j), col_frag(Lb, Jc, g, j), zero);
-                store_tile(Ub, I, Jc, g, j, hs * u);
-            }
-            __syncthreads();      // U
-            const v4d c0 = I == J ? kInvFact[k - 1] * IdB : zero;
-            const v4d nR = chain<kRowStep, kColStep, 16>(row_frag(Yb, I, g, j), col_frag(Rb, J, g, j), c0);
-            v4d nD = chain<kRowStep, kColStep, 16>(row_frag(Yb, I, g, j), col_frag(dRb, J, g, j), zero);
-            nD = chain<kRowStep, kRowStep, 4>(row_frag(Xb, I, g, j), row_frag(Ub, J, g, j), nD);
-            if (nct > 1) nD = chain<kRowStep, kRowStep, 4>(row_frag(Xb, I, g, j) + 16 * kLd, row_frag(Ub, J, g, j) + 16 * kLd, nD);
-            __syncthreads();      // P
-            store_tile(Rb, I, J, g, j, nR);
-            store_tile(dRb, I, J, g, j, nD);
-            __syncthreads();      // W
-        }
-#pragma unroll 1
-        for (int q = 0; q < sq; ++q) {
-            const v4d nE = chain<kRowStep, kColStep, 16>(row_frag(Rb, I, g, j), col_frag(Rb, J, g, j), zero);
-            v4d nD = chain<kRowStep, kColStep, 16>(row_frag(Rb, I, g, j), col_frag(dRb, J, g, j), zero);
-            nD = chain<kRowStep, kColStep, 16>(row_frag(dRb, I, g, j), col_frag(Rb, J, g, j), nD);
-            __syncthreads();      // P
-            store_tile(Rb, I, J, g, j, nE);
-            store_tile(dRb, I, J, g, j, nD);
-            __syncthreads();      // W
-        }
+        exp_pair(lds, G, hs, sq, nct, tid, I, J, g, j);      // barriers H0, U / P / W per Horner step, P / W per squaring
         // ZT = E^T dE, the wave's tile of x or lambda through E^T, and the drive derivatives
-        const v4d ZT = chain<kColStep, kColStep, 16>(col_frag(Rb, I, g, j), col_frag(dRb, J, g, j), zero);
+        const v4d ZT = chain<kColStep, kColStep, 16>(col_frag(lds.R, I, g, j), col_frag(lds.dR, J, g, j), zero);
         v4d nx = zero;
-        if (Jc < nct) nx = chain<kColStep, kColStep, 16>(col_frag(Rb, I, g, j), col_frag(mine, Jc, g, j), zero);
+        if (Jc < nct) nx = chain<kColStep, kColStep, 16>(col_frag(lds.R, I, g, j), col_frag(mine, Jc, g, j), zero);
         // the lane's elements ZT[a = 16 I + 4 r + g][b = 16 J + j] against G_u[b][a] (column-major images: a * 64 + b)
         const gptr Ge = G0 + (16 * I + g) * 64 + 16 * J + j;
 #pragma unroll 1
@@ -228,9 +165,7 @@ __global__ __launch_bounds__(kThreads, 1) void qc_sweep64_grad_kernel(const Swee
         __syncthreads();      // Ba
         if (Jc < nct) store_tile(mine, I, Jc, g, j, nx);
         if (w == 0 && ln < n_val) {
-            double acc = part[lane];
-#pragma unroll
-            for (int i = 1; i < 16; ++i) acc += part[i * kPartLd<PAR> + lane];
+            const double acc = part_sum<kPartLd<PAR>>(part, lane);
             if constexpr (PAR) {
                 // lane k < m: du_k BEFORE the factor c_k against the unscaled control (no division by c); the timestep's lane adds
                 // nothing that is read; lane nd + q: perturbation q's sum
@@ -258,11 +193,7 @@ int qc_sweep64_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const doubl
                            double* gs, bool want_par, double* par, hipStream_t st) {
     const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
     const auto walk = want_par ? qc_sweep64_grad_kernel<true> : qc_sweep64_grad_kernel<false>;
-    // per launch, as qc_sweep64_launch_totals: the attribute belongs to the (function, device) pair
-    QC_SIDE_HIP(h, *qc_sweep_err_slot(), hipFuncSetAttribute(reinterpret_cast<const void*>(walk), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                              (int)kGradLdsBytes));
-    hipLaunchKernelGGL(walk, dim3((unsigned)P.items), dim3(kThreads), kGradLdsBytes, st, P, dZ, dtheta, dscale, (const double*)h->dXs.p,
-                       (const double*)h->dLs.p, gs, want_par ? par : (double*)nullptr);
-    QC_SIDE_HIP(h, *qc_sweep_err_slot(), hipGetLastError());
+    QC_SWEEP64_LAUNCH(h, walk, kWalkLdsBytes, P, st, dZ, dtheta, dscale, (const double*)h->dXs.p, (const double*)h->dLs.p, gs,
+                      want_par ? par : (double*)nullptr);
     return QC_OK;
 }

@@ -51,6 +51,7 @@
 #include "qc_mfma_common.h"
 #include "qc_side.h"
 #include "qc_sweep64_common.h"
+#include "qc_sweep64_launch.h"
 #include "qc_sweep_internal.h"
 
 namespace {
@@ -135,12 +136,13 @@ __global__ __launch_bounds__(kThreads, 1) void qc_sweep64_jvp_kernel(const Sweep
     base_elems(P.img, m, P.p, theta, s, tid, base);
     based_elems(P.img, m, P.p, vtheta, s, tid, based);
     // lane l holds the sample's factor of drive min(l, m-1) and its tangent
-    const int kl = lane < m ? lane : (m > 0 ? m - 1 : 0);
-    const double cl = (scale && m > 0) ? scale[s * m + kl] : 1.0;
+    const DriveLane dl = drive_lane(scale, m, s, lane);
+    const int kl = dl.kl;
+    const double cl = dl.cl;
     const double vcl = (vscale && m > 0) ? vscale[s * m + kl] : 0.0;
 
     const double* __restrict__ z = Z + (long long)t0 * P.zdim;
-    double av = m > 0 ? z[P.off_a + kl] : 0.0;
+    double av = drive_value(z, P.off_a, m, kl);
     const double hfix = opaque_scalar(P.dt_fixed);
     double h = ft ? z[P.off_dt] : hfix;
     double vav = 0.0, vh = 0.0;
@@ -155,7 +157,7 @@ __global__ __launch_bounds__(kThreads, 1) void qc_sweep64_jvp_kernel(const Sweep
         // the next interval's controls, timestep and their tangents are requested before this interval's products
         const long long tn = t + 1 < t1 ? t + 1 : t;
         const double* __restrict__ zn = Z + tn * P.zdim;
-        const double av_n = m > 0 ? zn[P.off_a + kl] : 0.0;
+        const double av_n = drive_value(zn, P.off_a, m, kl);
         const double h_n = ft ? zn[P.off_dt] : hfix;
         double vav_n = 0.0, vh_n = 0.0;
         if (hasv) {
@@ -228,11 +230,6 @@ int qc_sweep64_jvp_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const
                                  const double* dvtheta, const double* dvscale, hipStream_t st, int64_t* chunk_out, int64_t* n_chunks_out) {
     SweepParams P;
     if (int rc = qc_sweep_plan_totals(h, S, h->dTotJ, 2 * kImg, &P, chunk_out, n_chunks_out)) return rc;
-    // per launch, as qc_sweep64_launch_totals: the attribute belongs to the (function, device) pair
-    QC_SIDE_HIP(h, *qc_sweep_err_slot(), hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep64_jvp_kernel),
-                                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-    hipLaunchKernelGGL(qc_sweep64_jvp_kernel, dim3((unsigned)P.items), dim3(kThreads), kLdsBytes, st, P, dZ, dtheta, dscale, dvZ, dvtheta, dvscale,
-                       h->dTotJ.p);
-    QC_SIDE_HIP(h, *qc_sweep_err_slot(), hipGetLastError());
+    QC_SWEEP64_LAUNCH(h, qc_sweep64_jvp_kernel, kLdsBytes, P, st, dZ, dtheta, dscale, dvZ, dvtheta, dvscale, h->dTotJ.p);
     return QC_OK;
 }

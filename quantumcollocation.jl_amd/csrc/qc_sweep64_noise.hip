@@ -1,28 +1,15 @@
-// Noise-trajectory sweeps for "mfma64-sweep" handles (32 < 2N <= 64) whose `wide` has QC_SWEEP_WIDE_64_NOISE: the two kernels of
-// qc_sweep_noise.hip (read its header first: the model, the zero-noise contract, grad_noise; then qc_sweep32_noise.hip, how the wide form
-// did it) with every matrix 4 x 4 tiles of 16 x 16 in LDS.  In interval t of sample s
-//     G_{s,t} = G_drift + sum_j (theta[s,j] + xi[s,t,j]) P_j + sum_k c[s,k] a_{t,k} G_k.
-// Nothing is resident per generator in this form: qc_sweep64::generator reads the images 1 .. m again every interval and the perturbation
-// images follow the drives in the image buffer, so a per-interval perturbation is a longer loop bound, mt = m + p <= 24, and a per-lane
-// coefficient source.  No tile limit: m <= 16, p <= QC_MAX_PERT.
-//   * generator u < m is drive u, coefficient c[s,u] a_{t,u} (the product rounded as qc_sweep_mfma64_kernel's av * cl); generator m + j is
-//     perturbation j, coefficient noise[(s (T-1) + t) p + j], factor 1.  Each lane that fetches a coefficient carries its own pointer and
-//     stride (zdim or p) in vector registers and steps it per interval: one load per lane and interval, requested one interval ahead;
-//   * base_elems folds theta; the drives are added in ascending k, THEN the perturbations in ascending j.  At xi = +0.0 the extra fmas leave
-//     every value as it was (a -0 may become +0, nothing else), so finals / fids / grad / grad_samples carry the bits of qc_sweep_eval and
-//     qc_sweep_grad on the same handle;
-//   * everything behind the generator is qc_sweep_mfma64_kernel's / qc_sweep64_grad_kernel's, restated here (to be changed with them:
-//     those files are not touched, so their kernels compile to what they compiled to before this file existed): squarings(), the Horner
-//     chain through tile_mul / chain<>, the squarings, W <- E W or the adjoint step.  The chunk totals go to h->dTot (S x n_chunks x 4096)
-//     and qc_sweep_finish_kernel follows at ld = 64; the gradient runs the seed, the walk below and the weighted reduction unchanged.
+// The gradient walk of the noise-trajectory sweeps for "mfma64-sweep" handles (32 < 2N <= 64) whose `wide` has QC_SWEEP_WIDE_64_NOISE
+// and QC_SWEEP_WIDE_64_GRAD: qc_sweep_noise_grad_kernel (qc_sweep_noise.hip; read its header first: the model, the zero-noise contract,
+// grad_noise; then qc_sweep32_noise.hip, how the wide form did it) with every matrix 4 x 4 tiles of 16 x 16 in LDS.  The forward launch
+// is the flavour <true> of qc_sweep_mfma64_kernel (qc_sweep64.hip: the generators of an interval, their order, the zero-noise bits); the
+// gradient runs it, the seed, the walk below and the weighted reduction.
 //
-// Forward kernel, qc_sweep64_noise_kernel: qc_sweep_mfma64_kernel with mt generators; lane l of every wave fetches generator
-// min(l, mt - 1)'s coefficient and generator() broadcasts lane u's.  LDS, barriers and MFMAs ((9 + sq) x 256 an interval) are that kernel's.
-//
-// Backward kernel, qc_sweep64_noise_grad_kernel: the closed walk of qc_sweep64_grad_kernel with mt generators and the tail's image loop over
-// all mt images.  It keeps no running sums and no chunk share: the wave sums of an interval leave in that interval.  LDS map of the
-// dynamic part, work item and the MFMA count ((4352 + 1152 nct) + 768 sq an interval) are that kernel's; static LDS is red[16],
-// part[16 x 25] and coef[2 x 32], 3 840 B, so 155 904 B of the CU's 160 KiB.
+// qc_sweep64_noise_grad_kernel is the closed walk of qc_sweep64_grad_kernel with mt = m + p generators and the tail's image loop over all
+// mt images.  The two walks are built on the same pieces of qc_sweep64_common.h -- the LDS map (walk_lds), load_state, generator_of,
+// squarings, kt_dot, exp_pair (every barrier between S and Ba, with its reason), part_sum -- and differ in where a coefficient comes from
+// and where a wave sum goes.  This one keeps no running sums and no chunk share: the wave sums of an interval leave in that interval.
+// Work item and the MFMA count ((4352 + 1152 nct) + 768 sq an interval) are that kernel's; static LDS is red[16], part[16 x 25] and
+// coef[2 x 32], 3 840 B, so 155 904 B of the CU's 160 KiB.  At xi = +0.0 fids / J / grad / grad_samples carry the bits of qc_sweep_grad.
 // The walk has no register to spare, the scalar ones least of all, so the interval's coefficients do not travel in a lane of every wave:
 //   coef[2][32]   the row of one interval, double-buffered by interval parity: entry u < mt the coefficient of generator u, scaled; entry
 //                 31 the timestep (free timesteps; a fixed one is the kernel argument).
@@ -34,18 +21,18 @@
 //     lane 31             Z[t, off_dt], stride zdim, factor 1 (free timesteps); stores nothing
 // (other lanes repeat lane mt - 1's source into entries nobody reads).  A lane whose buffer is absent keeps a null address and stride 0:
 // which buffers are present changes which lanes store, never what they hold.  Every thread's generator loop reads coef[b + u] (an LDS
-// broadcast) where qc_sweep64::generator broadcasts a lane, and the timestep from coef[b + 31].
+// broadcast: generator_of with the row as its source) where generator() broadcasts a lane, and the timestep from coef[b + 31].
 // The wave sums of the interval: lane u < mt of every wave keeps sum ZT . image u, lane mt the timestep's sum KT . G (skipped when gs is
 // absent); part[w][0 .. mt] as in the parameter flavour, and wave 0 adds the 16 partials behind Ba in ascending wave order.
-// Barriers of one interval: S, H0, U / P / W per Horner step and P / W per squaring, Ba -- those of qc_sweep64_grad.hip, with the same
-// reasons for Y, R, dR, x, lambda, u, red[] and part[].  For coef[]:
+// Barriers of one interval: S (squarings), H0, U / P / W per Horner step and P / W per squaring (exp_pair), Ba (qc_sweep64_grad.hip), with
+// the reasons given there for Y, R, dR, x, lambda, u, red[] and part[].  For coef[]:
 //     F   before the loop: publishes the first interval's half of the row (and, as S would, the states written once per item);
 //     the half b of interval t is read in front of S of interval t (generator and timestep; both are in registers behind S);
 //     wave 0 writes the other half, the next interval's, just in front of Ba of interval t: its last readers read it in front of S of
 //     the interval before, a whole interval of barriers ago, and Ba stands between this write and its first read;
 //     half b is written next in front of Ba of the next interval, behind that interval's S, hence behind every read of it.
 // No atomics, sums in a fixed order: repeated calls give the same bits.
-// gfx950 cross-compile: see the table in DESIGN.md 5.8.15; no private segment, no spills in either kernel.
+// gfx950 cross-compile: see the table in DESIGN.md 5.8.16; no private segment, no spills.
 #include <math.h>
 
 #include <string>
@@ -53,6 +40,7 @@
 #include "qc_mfma_common.h"
 #include "qc_side.h"
 #include "qc_sweep64_common.h"
+#include "qc_sweep64_launch.h"
 #include "qc_sweep_internal.h"
 
 namespace {
@@ -62,101 +50,8 @@ using namespace qc_sweep64;
 constexpr int kCoefLd = 32;       // one half of the coefficient row; entry kHEntry is the timestep
 constexpr int kHEntry = 31;
 constexpr int kPartLd = 25;       // values a wave leaves per interval: mt + 1 <= 25
-constexpr size_t kGradLdsBytes = (size_t)(3 * kMat + 3 * kThin) * sizeof(double);      // 152 064 B, as qc_sweep64_grad.hip
 
-// Where lane l finds the coefficient of generator min(l, mt - 1) in interval t, how far the next interval's lies, and the sample's factor
-// (p >= 1: there always is a generator).
-struct LaneCoef {
-    const double* cp;
-    int stride;          // doubles from one interval to the next: zdim for a drive lane, p for a perturbation lane
-    double cl;           // c[s,k] for a drive lane, 1 for a perturbation lane
-};
-
-__device__ __forceinline__ LaneCoef lane_coef(const SweepParams& P, int lane, long long s, int t, const double* __restrict__ Z,
-                                              const double* __restrict__ scale, const double* __restrict__ noise) {
-    const int m = P.m, mt = m + P.p;
-    const int kl = lane < mt ? lane : mt - 1;
-    const bool drv = kl < m;
-    LaneCoef c;
-    c.cp = drv ? Z + (long long)t * P.zdim + P.off_a + kl : noise + (s * P.n_int + t) * (long long)P.p + (kl - m);
-    c.stride = drv ? P.zdim : P.p;
-    c.cl = (scale && drv) ? scale[s * m + kl] : 1.0;
-    return c;
-}
-
-// Launch 1: the chunk totals.  Restates qc_sweep_mfma64_kernel (qc_sweep64.hip; to be changed with it) with mt generators.
-__global__ __launch_bounds__(kThreads, 1) void qc_sweep64_noise_kernel(const SweepParams P, const double* __restrict__ Z,
-                                                                         const double* __restrict__ theta, const double* __restrict__ scale,
-                                                                         const double* __restrict__ noise, double* __restrict__ tot) {
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    __shared__ double red[16];
-    const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, j = lane & 15;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6), I = w & 3, J = w >> 2;
-    const long long item = blockIdx.x;
-    const ChunkRange ch = chunk_range(item, P.n_chunks, P.chunk, P.n_int);
-    const int t0 = ch.t0, t1 = ch.t1, m = P.m, mt = m + P.p;
-    const long long s = ch.s;
-    const bool ft = P.off_dt >= 0;
-
-    // ---- once per item: the sample's base matrix, the lane's coefficient source, W = I ----------------------------------------------
-    double base[4];
-    base_elems(P.img, m, P.p, theta, s, tid, base);
-    const LaneCoef lc = lane_coef(P, lane, s, t0, Z, scale, noise);
-    const double* cp = lc.cp;
-    int oY = 0, oW = 3 * kMat;      // the buffers' roles; Ra = kMat, Rb = 2 kMat
-#pragma unroll
-    for (int e = 0; e < 4; ++e) sm[oW + lds_at(tid, e)] = on_diagonal(tid, e) ? 1.0 : 0.0;
-
-    const double* __restrict__ z = Z + (long long)t0 * P.zdim;
-    double av = *cp;
-    const double hfix = opaque_scalar(P.dt_fixed);      // keeps the two arms apart: no flat load (qc_mfma_common.h)
-    double h = ft ? z[P.off_dt] : hfix;
-#pragma unroll 1
-    for (int t = t0; t < t1; ++t) {
-        // the next interval's coefficients and timestep are requested before this interval's products
-        const double* __restrict__ zn = Z + (long long)(t + 1 < t1 ? t + 1 : t) * P.zdim;
-        if (t + 1 < t1) cp += lc.stride;
-        const double av_n = *cp;
-        const double h_n = ft ? zn[P.off_dt] : hfix;
-        double G[4];
-        generator(P.img, mt, av * lc.cl, base, tid, G);      // the drives in ascending k, then the perturbations in ascending j
-        const int sq = squarings(red, G, h, lane, w);      // its barrier: every wave has left the previous interval's products
-        const double hs = h * ldexp(1.0, -sq);
-        // Horner: R_deg+1 = I/deg!,  R_k = Y R_k+1 + I/(k-1)!; the barrier rules of qc_sweep_mfma64_kernel (these writes rely on the barrier
-        // inside squarings(); red[] has a workgroup barrier between a call of squarings() and the next)
-        int oR = kMat, oN = 2 * kMat;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            sm[oY + lds_at(tid, e)] = hs * G[e];
-            sm[oR + lds_at(tid, e)] = on_diagonal(tid, e) ? kInvFact[kDeg] : 0.0;
-        }
-        __syncthreads();
-#pragma unroll 1
-        for (int k = kDeg; k >= 1; --k) {
-            tile_mul(sm + oY, sm + oR, sm + oN, I, J, g, j, kInvFact[k - 1]);
-            __syncthreads();
-            const int o = oR; oR = oN; oN = o;
-        }
-#pragma unroll 1
-        for (int q = 0; q < sq; ++q) {
-            tile_mul(sm + oR, sm + oR, sm + oN, I, J, g, j, 0.0);
-            __syncthreads();
-            const int o = oR; oR = oN; oN = o;
-        }
-        tile_mul(sm + oR, sm + oW, sm + oY, I, J, g, j, 0.0);      // W <- E W into the buffer Y has left
-        const int o = oY; oY = oW; oW = o;
-        av = av_n;
-        h = h_n;
-    }
-    __syncthreads();
-    // column-major 64 x 64, a whole column per wave and request
-    double* __restrict__ o = tot + item * kImg + tid;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[1024 * e] = sm[oW + lds_at(tid, e)];
-}
-
-// Launch 3: the backward walk.  Restates qc_sweep64_grad_kernel (qc_sweep64_grad.hip; to be changed with it) with mt generators, the
-// coefficient row and per-lane stores.  gs (S x (T-1) x nd) and gn (S x (T-1) x p) may each be NULL, not both.
+// Launch 3: the backward walk.  gs (S x (T-1) x nd) and gn (S x (T-1) x p) may each be NULL, not both.
 __global__ __launch_bounds__(kThreads, 1) void qc_sweep64_noise_grad_kernel(const SweepParams P, const double* __restrict__ Z,
                                                                               const double* __restrict__ theta, const double* __restrict__ scale,
                                                                               const double* __restrict__ noise, const double* __restrict__ xs,
@@ -169,38 +64,21 @@ __global__ __launch_bounds__(kThreads, 1) void qc_sweep64_noise_grad_kernel(cons
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, j = lane & 15;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6), I = w & 3, J = w >> 2;
     const int Jc = J & 1;                   // the wave's column tile of a thin matrix
-    const bool second = J >= 2;             // waves 8 .. 15: lambda's tiles; waves 0 .. 7: x's and u's
     const long long item = blockIdx.x;
     const ChunkRange ch = chunk_range(item, P.n_chunks, P.chunk, P.n_int);
     const int t0 = ch.t0, t1 = ch.t1, m = P.m, nc = P.nc;
     const int nct = nc > 16 ? 2 : 1;
     const long long s = ch.s;
     const bool ft = P.off_dt >= 0;
-    const v4d IdB = identity_B(g, j);
     const v4d zero = {0.0, 0.0, 0.0, 0.0};
-    double* const Yb = sm;
-    double* const Rb = sm + kMat;
-    double* const dRb = sm + 2 * kMat;
-    double* const Xb = sm + 3 * kMat;
-    double* const Lb = Xb + kThin;
-    double* const Ub = Lb + kThin;
-    double* const mine = second ? Lb : Xb;      // the thin matrix whose tile (I, Jc) this wave carries through E^T
+    const WalkLds lds = walk_lds(sm);
+    double* const mine = J >= 2 ? lds.L : lds.X;      // waves 8 .. 15 carry lambda's tile (I, Jc) through E^T, waves 0 .. 7 x's
 
     // ---- once per item: the sample's base matrix, the state and the adjoint at the chunk's end (zero outside n x nc) -----------------
     double base[4];
     base_elems(P.img, m, P.p, theta, s, tid, base);
-    {
-        const int ns = P.n * nc;
-        const double* __restrict__ xe = xs + item * ns;
-        const double* __restrict__ le = ls + item * ns;
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int idx = tid + 1024 * e, row = idx & 63, col = idx >> 6;
-            const bool in = row < P.n && col < nc;
-            Xb[col * kLd + row] = in ? xe[row + P.n * col] : 0.0;
-            Lb[col * kLd + row] = in ? le[row + P.n * col] : 0.0;
-        }
-    }
+    load_state(xs + item * (P.n * nc), P.n, nc, tid, lds.X);
+    load_state(ls + item * (P.n * nc), P.n, nc, tid, lds.L);
     const int mt = m + P.p, n_val = mt + (ft ? 1 : 0);
     // ---- once per item: the lane's source, factor and destination (the table of the header); only wave 0's lanes < 32 use them ---------
     const double* cp;
@@ -243,75 +121,20 @@ __global__ __launch_bounds__(kThreads, 1) void qc_sweep64_noise_grad_kernel(cons
         }
         const double h = ft ? coef[b + kHEntry] : hfix;
         double G[4];
-        {      // qc_sweep64::generator with the coefficients out of the row
-            const gptr Gt = G0 + tid;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) G[e] = base[e];
-#pragma unroll 1
-            for (int u = 0; u < mt; ++u) {
-                const double a = coef[b + u];
-                const gptr Gu = Gt + (size_t)(1 + u) * kImg;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) G[e] = fma(a, Gu[1024 * e], G[e]);
-            }
-        }
+        generator_of(P.img, mt, [&](int u) { return coef[b + u]; }, base, tid, G);      // the row's entries where generator() broadcasts a lane
         const int sq = squarings(red, G, h, lane, w);      // barrier S; the rule of the forward kernel: one function
         const double hs = h * ldexp(1.0, -sq);
         // lane u < mt: generator u's wave sum; lane mt: the timestep's (sum KT . G, its sign at the store)
         double out = 0.0;
         if (want_dh) {
-            // sum_ab KT[a][b] G[b][a] over the thread's elements G[b = lane][a = w + 16 e], KT[a][b] = sum_c lambda[a][c] x[b][c]
-            double kt[4] = {0.0, 0.0, 0.0, 0.0};
-            for (int c = 0; c < nc; ++c) {
-                const double xv = Xb[c * kLd + lane];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) kt[e] = fma(Lb[c * kLd + w + 16 * e], xv, kt[e]);
-            }
-            double ph = 0.0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ph = fma(kt[e], G[e], ph);
-            const double dh = wave_sum(ph);
+            const double dh = kt_dot(lds.X, lds.L, nc, G, lane, w);
             out = lane == mt ? dh : out;
         }
-        // Horner: R_deg+1 = I/deg!, dR_deg+1 = 0;  R_k = Y R_k+1 + I/(k-1)!,  dR_k = dY R_k+1 + Y dR_k+1
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            Yb[lds_at(tid, e)] = hs * G[e];
-            Rb[lds_at(tid, e)] = on_diagonal(tid, e) ? kInvFact[kDeg] : 0.0;
-            dRb[lds_at(tid, e)] = 0.0;
-        }
-        __syncthreads();      // H0
-#pragma unroll 1
-        for (int k = kDeg; k >= 1; --k) {
-            if (!second && Jc < nct) {
-                const v4d u = chain<kColStep, kColStep, 16>(col_frag(Rb, I, g, j), col_frag(Lb, Jc, g, j), zero);
-                store_tile(Ub, I, Jc, g, j, hs * u);
-            }
-            __syncthreads();      // U
-            const v4d c0 = I == J ? kInvFact[k - 1] * IdB : zero;
-            const v4d nR = chain<kRowStep, kColStep, 16>(row_frag(Yb, I, g, j), col_frag(Rb, J, g, j), c0);
-            v4d nD = chain<kRowStep, kColStep, 16>(row_frag(Yb, I, g, j), col_frag(dRb, J, g, j), zero);
-            nD = chain<kRowStep, kRowStep, 4>(row_frag(Xb, I, g, j), row_frag(Ub, J, g, j), nD);
-            if (nct > 1) nD = chain<kRowStep, kRowStep, 4>(row_frag(Xb, I, g, j) + 16 * kLd, row_frag(Ub, J, g, j) + 16 * kLd, nD);
-            __syncthreads();      // P
-            store_tile(Rb, I, J, g, j, nR);
-            store_tile(dRb, I, J, g, j, nD);
-            __syncthreads();      // W
-        }
-#pragma unroll 1
-        for (int q = 0; q < sq; ++q) {
-            const v4d nE = chain<kRowStep, kColStep, 16>(row_frag(Rb, I, g, j), col_frag(Rb, J, g, j), zero);
-            v4d nD = chain<kRowStep, kColStep, 16>(row_frag(Rb, I, g, j), col_frag(dRb, J, g, j), zero);
-            nD = chain<kRowStep, kColStep, 16>(row_frag(dRb, I, g, j), col_frag(Rb, J, g, j), nD);
-            __syncthreads();      // P
-            store_tile(Rb, I, J, g, j, nE);
-            store_tile(dRb, I, J, g, j, nD);
-            __syncthreads();      // W
-        }
+        exp_pair(lds, G, hs, sq, nct, tid, I, J, g, j);      // barriers H0, U / P / W per Horner step, P / W per squaring
         // ZT = E^T dE, the wave's tile of x or lambda through E^T, and the derivatives of every generator
-        const v4d ZT = chain<kColStep, kColStep, 16>(col_frag(Rb, I, g, j), col_frag(dRb, J, g, j), zero);
+        const v4d ZT = chain<kColStep, kColStep, 16>(col_frag(lds.R, I, g, j), col_frag(lds.dR, J, g, j), zero);
         v4d nx = zero;
-        if (Jc < nct) nx = chain<kColStep, kColStep, 16>(col_frag(Rb, I, g, j), col_frag(mine, Jc, g, j), zero);
+        if (Jc < nct) nx = chain<kColStep, kColStep, 16>(col_frag(lds.R, I, g, j), col_frag(mine, Jc, g, j), zero);
         // the lane's elements ZT[a = 16 I + 4 r + g][b = 16 J + j] against G_u[b][a] (column-major images: a * 64 + b)
         const gptr Ge = G0 + (16 * I + g) * 64 + 16 * J + j;
 #pragma unroll 1
@@ -332,9 +155,7 @@ __global__ __launch_bounds__(kThreads, 1) void qc_sweep64_noise_grad_kernel(cons
         __syncthreads();      // Ba
         if (Jc < nct) store_tile(mine, I, Jc, g, j, nx);
         if (w == 0 && ln < n_val) {
-            double acc = part[lane];
-#pragma unroll
-            for (int i = 1; i < 16; ++i) acc += part[i * kPartLd + lane];
+            const double acc = part_sum<kPartLd>(part, lane);
             if (op) *op = acc * cl;      // drives: c[s,k]; perturbations: 1; the timestep: -1
         }
         op -= ostr;
@@ -344,25 +165,10 @@ __global__ __launch_bounds__(kThreads, 1) void qc_sweep64_noise_grad_kernel(cons
 
 }  // namespace
 
-int qc_sweep64_noise_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dnoise,
-                                   hipStream_t st, int64_t* chunk_out, int64_t* n_chunks_out) {
-    SweepParams P;
-    if (int rc = qc_sweep_plan_totals(h, S, h->dTot, kImg, &P, chunk_out, n_chunks_out)) return rc;
-    // per launch, as qc_sweep64_launch_totals: the attribute belongs to the (function, device) pair
-    QC_SIDE_HIP(h, *qc_sweep_err_slot(), hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep64_noise_kernel),
-                                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes));
-    hipLaunchKernelGGL(qc_sweep64_noise_kernel, dim3((unsigned)P.items), dim3(kThreads), kLdsBytes, st, P, dZ, dtheta, dscale, dnoise, h->dTot.p);
-    QC_SIDE_HIP(h, *qc_sweep_err_slot(), hipGetLastError());
-    return QC_OK;
-}
-
 int qc_sweep64_noise_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dnoise,
                                  int64_t chunk, int64_t n_chunks, double* gs, double* gn, hipStream_t st) {
     const SweepParams P = qc_sweep_params(h, S, chunk, n_chunks);
-    QC_SIDE_HIP(h, *qc_sweep_err_slot(), hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep64_noise_grad_kernel),
-                                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGradLdsBytes));
-    hipLaunchKernelGGL(qc_sweep64_noise_grad_kernel, dim3((unsigned)P.items), dim3(kThreads), kGradLdsBytes, st, P, dZ, dtheta, dscale, dnoise,
-                       (const double*)h->dXs.p, (const double*)h->dLs.p, gs, gn);
-    QC_SIDE_HIP(h, *qc_sweep_err_slot(), hipGetLastError());
+    QC_SWEEP64_LAUNCH(h, qc_sweep64_noise_grad_kernel, kWalkLdsBytes, P, st, dZ, dtheta, dscale, dnoise, (const double*)h->dXs.p,
+                      (const double*)h->dLs.p, gs, gn);
     return QC_OK;
 }

@@ -224,8 +224,8 @@ int qc_sweep32_noise_launch_totals(qc_sweep* h, const double* dZ, int64_t S, con
                                    hipStream_t st, int64_t* chunk, int64_t* n_chunks);
 void qc_sweep32_noise_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, const double* dnoise,
                                   int64_t chunk, int64_t n_chunks, double* gs, double* gn, hipStream_t st);
-// "mfma64-sweep" handles with `wide64_noise` (qc_sweep64_noise.hip): grows h->dTot and launches qc_sweep64_noise_kernel on `st`, one workgroup
-// per (sample, chunk) (totals as qc_sweep64_launch_totals), and the backward walk qc_sweep64_noise_grad_kernel (gs: S x (T-1) x nd,
+// "mfma64-sweep" handles with `wide64_noise`: grows h->dTot and launches qc_sweep_mfma64_kernel<true> on `st` (qc_sweep64.hip), one workgroup
+// per (sample, chunk) (totals as qc_sweep64_launch_totals), and the backward walk qc_sweep64_noise_grad_kernel (qc_sweep64_noise.hip; gs: S x (T-1) x nd,
 // gn: S x (T-1) x p, either may be NULL; x and lambda at the chunk ends from h->dXs / h->dLs).  QC_OK or the launch's code
 __attribute__((visibility("hidden"))) int qc_sweep64_noise_launch_totals(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale,
                                                                           const double* dnoise, hipStream_t st, int64_t* chunk, int64_t* n_chunks);
