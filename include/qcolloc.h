@@ -691,6 +691,18 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * same handle.  qc_sweep_hvp* and the stored-state flag stay QC_ERR_UNSUPPORTED there.  Form, launch, kernel name, every other
  * *_supported answer and every other entry point's output are those of the same descriptor without the bit; descriptors with 2N <= 32
  * ignore it completely.
+ * Bit 18, QC_SWEEP_WIDE_64_STORED (any valid value that has bits 0, 10 and 11, | 262144; without all three of them QC_ERR_INVALID, as
+ * bit 13; bit 17 and everything from bit 19 up are not assigned), matters only on an "mfma64-sweep" handle that also has reserved1[0] =
+ * QC_SWEEP_STORED_STATES: qc_sweep_grad* and qc_sweep_vjp* then serve ANY generators there -- a Lindblad model of a five-level system
+ * (N = 25, 2N = 50) with QC_FID_DENSITY, non-Hermitian effective Hamiltonians -- with states of up to 32 columns, by the stored-state walk
+ * on 4 x 4 tiles (qc_sweep64_open_grad.hip: a store launch and a walk, one workgroup per (sample, chunk) each, the forward form's chunk
+ * rule); such a handle takes that walk whatever its generators, antisymmetric ones included.  qc_sweep_grad_params* and the grad_theta /
+ * grad_scale of qc_sweep_vjp* are served when bit 13 is set as well and keep their refusal without it.  The state buffer is
+ * S x (T-1) x 2N x cols doubles: 50 doubles a knot for the five-level Lindblad state, 432 for eight columns at 27 levels.  fids / finals
+ * carry the bits of qc_sweep_eval on the same handle.  Still refused there: qc_sweep_hvp* (Hessian products are not served in this form),
+ * qc_sweep_noise_grad* of open systems (it keeps its closed scope and its kernels) and states of more than 32 columns.  Without the bit
+ * the stored-state flag stays QC_ERR_UNSUPPORTED in this form, message for message; qc_sweep_eval*, qc_sweep_jvp*, qc_sweep_noise_eval*
+ * and the launch rule do not look at the bit; descriptors with 2N <= 32 ignore it completely.
  * reserved1[0] = QC_SWEEP_STORED_STATES chooses reverse mode by the STORED-STATE walk: qc_sweep_grad*, qc_sweep_grad_params* and
  * qc_sweep_vjp* then keep the forward states x_0 .. x_{T-2} of every sample in handle scratch (S x (T-1) x 2N x cols doubles) and read
  * them on the way back instead of reversing the step, which serves ANY generators in the "mfma16-sweep" form: Lindblad generators
@@ -705,6 +717,7 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
  * Gradients with respect to the controls and timesteps (qc_sweep_grad*) and to the samples' own parameters theta and `scale`
  * (qc_sweep_grad_params*), both below, are served for closed systems in the MFMA forms (parameter gradients: "mfma16-sweep", "mfma32-sweep" with QC_SWEEP_WIDE_PARAMS, "mfma64-sweep" with QC_SWEEP_WIDE_64_PARAMS), and
  * with reserved1[0] = QC_SWEEP_STORED_STATES for open systems in the "mfma16-sweep" form and, with QC_SWEEP_WIDE_STORED, the "mfma32-sweep" form.
+ * ("mfma64-sweep": with QC_SWEEP_WIDE_64_GRAD | QC_SWEEP_WIDE_64_STORED.)
  * Derivatives of the final states themselves, contracted with cotangents the caller chooses (qc_sweep_vjp*, below), carry any function
  * of the final states: leakage, the free-phase fidelity, several kets at once, a loss written elsewhere.
  * The forward-mode counterpart, the tangent of the final states and fidelities along one direction (qc_sweep_jvp*, below), is served
@@ -735,6 +748,7 @@ int qc_robust_eval_dev(qc_robust* h, const double* dZ, double* dL, double* dgrad
 #define QC_SWEEP_WIDE_64_PARAMS 8192 /* qc_sweep_desc.wide, bit 13: the mfma64-sweep form serves parameter gradients and parameter cotangents of closed systems (qc_sweep_grad_params*, grad_theta / grad_scale of qc_sweep_vjp*; the flavour <true> of qc_sweep64_grad.hip's walk); ignored at 2N <= 32; only together with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD */
 #define QC_SWEEP_WIDE_64_TANGENT 16384 /* qc_sweep_desc.wide, bit 14: the mfma64-sweep form serves pushforwards (qc_sweep_jvp*; qc_sweep64_jvp.hip), any generators, 2N x state_cols <= 2048; ignored at 2N <= 32; only together with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 */
 #define QC_SWEEP_WIDE_64_NOISE 65536 /* qc_sweep_desc.wide, bit 16: the mfma64-sweep form serves noise-trajectory sweeps and, with QC_SWEEP_WIDE_64_GRAD, their gradients (qc_sweep_noise_*; qc_sweep64_noise.hip); ignored at 2N <= 32; only together with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 */
+#define QC_SWEEP_WIDE_64_STORED 262144 /* qc_sweep_desc.wide, bit 18: with reserved1[0] = QC_SWEEP_STORED_STATES the mfma64-sweep form serves the stored-state walk, any generators, at most 32 state columns (qc_sweep_grad*, qc_sweep_vjp*; qc_sweep64_open_grad.hip); ignored at 2N <= 32; only together with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD */
 #define QC_SWEEP_WIDE_64 1024    /* qc_sweep_desc.wide, bit 10: 32 < 2N <= 64 with up to 16 drives takes the matrix cores ("mfma64-sweep", qc_sweep_eval* only); ignored at 2N <= 32; only together with QC_SWEEP_WIDE */
 #define QC_SWEEP_STORED_STATES 1 /* qc_sweep_desc.reserved1[0]: reverse mode by the stored-state walk */
 typedef struct qc_sweep_desc {

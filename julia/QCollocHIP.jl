@@ -22,6 +22,7 @@ const QC_SWEEP_WIDE_64_GRAD = 2048 # qc_sweep_desc.wide, bit 11 (only with bits 
 const QC_SWEEP_WIDE_64_PARAMS = 8192 # qc_sweep_desc.wide, bit 13 (only with bits 0, 10 and 11): parameter gradients and parameter cotangents in the "mfma64-sweep" form
 const QC_SWEEP_WIDE_64_TANGENT = 16384 # qc_sweep_desc.wide, bit 14 (only with bits 0 and 10): pushforwards in the "mfma64-sweep" form, any generators, 2NÂ·cols â‰¤ 2048
 const QC_SWEEP_WIDE_64_NOISE = 65536 # qc_sweep_desc.wide, bit 16 (only with bits 0 and 10): noise-trajectory sweeps in the "mfma64-sweep" form (their gradients with bit 11 as well)
+const QC_SWEEP_WIDE_64_STORED = 262144 # qc_sweep_desc.wide, bit 18 (only with bits 0, 10 and 11): with stored_states, reverse mode of ANY generators in the "mfma64-sweep" form (at most 32 state columns)
 const QC_SWEEP_WIDE_64 = 1024      # qc_sweep_desc.wide, bit 10 (only with bit 0): 32 < 2N â‰¤ 64 with up to 16 drives on the matrix cores ("mfma64-sweep", forward sweep only)
 const QC_ABI_VERSION = 6      # QC_VERSION_MAJOR * 1000 + QC_VERSION_MINOR of the include/qcolloc.h these mirrors were written against
 
@@ -763,7 +764,7 @@ end
 """
     rollout_sweep_gradient(init, controls, Î”t, G_drift, G_drives, G_pert, Î¸; scale=nothing, weights=nothing, cols, goal, fid_kind=0,
                            subspace=nothing, squared=false, per_sample=false, device=0, wide=false, stored_states=false,
-                           wide64=false, wide64_grad=false)  ->  (J, fids, âˆ‡a, âˆ‡Î”t[, grad_samples])
+                           wide64=false, wide64_grad=false, wide64_stored=false)  ->  (J, fids, âˆ‡a, âˆ‡Î”t[, grad_samples])
 
 The adjoint of `rollout_sweep` (`qc_sweep_grad`): J = Î£_s w_s F_s (`weights`: S values, default 1/S each), the S fidelities, and the
 gradient of J with respect to the controls (`âˆ‡a`, mÃ—T) and the timesteps (`âˆ‡Î”t`, T); the last knot's columns are zero.  With
@@ -771,12 +772,15 @@ gradient of J with respect to the controls (`âˆ‡a`, mÃ—T) and the timesteps (`âˆ
 with 2N â‰¤ 16 (`wide = true`: 2N â‰¤ 32), m â‰¤ 8 and `fid_kind` 0 (unitary) or 1 (ket); with `stored_states = true` for ANY generators with 2N â‰¤ 16,
 m â‰¤ 8 and `fid_kind` 0, 1 or 2 (density operator); everything else errors with the library's reason.  `wide = true, wide64 = true,
 wide64_grad = true` sets `QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD` (3073): closed systems with 32 < 2N â‰¤ 64, m â‰¤ 16 and at
-most 32 state columns in the "mfma64-sweep" form.  Arguments as `rollout_sweep`.  UNTESTED here, like the rest of this file.
+most 32 state columns in the "mfma64-sweep" form.  `wide64_stored = true` (only with `wide64_grad` and `stored_states`) adds
+`QC_SWEEP_WIDE_64_STORED` (262144): ANY generators there, `fid_kind` 2 included (a five-level Lindblad model, 2N = 50), by the stored-state
+walk.  Arguments as `rollout_sweep`.  UNTESTED here, like the rest of this file.
 """
 function rollout_sweep_gradient(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Î”t::AbstractVector{Float64}, G_drift, G_drives,
                                 G_pert, Î¸::AbstractMatrix{Float64}; scale=nothing, weights=nothing, cols::Int, goal, fid_kind::Int=0,
                                 subspace=nothing, squared::Bool=false, per_sample::Bool=false, device::Int=0, wide::Bool=false, stored_states::Bool=false, wide_stored::Bool=false,
-                                wide64::Bool=false, wide64_grad::Bool=false)
+                                wide64::Bool=false, wide64_grad::Bool=false, wide64_stored::Bool=false)
+    (wide64_stored && !(wide64_grad && stored_states)) && error("rollout_sweep_gradient: wide64_stored = true needs wide64_grad = true and stored_states = true")
     (wide64 && !wide) && error("rollout_sweep_gradient: wide64 = true needs wide = true")
     (wide64_grad && !wide64) && error("rollout_sweep_gradient: wide64_grad = true needs wide64 = true")
     n = size(G_drift, 1); N = n Ã· 2
@@ -799,7 +803,8 @@ function rollout_sweep_gradient(init::AbstractVector{Float64}, controls::Abstrac
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
                                squared ? 1 : 0, length(sub), pointer(g), isempty(sub) ? C_NULL : pointer(sub),
-                               device, (wide ? 1 : 0) | (wide_stored ? 8 : 0) | (wide64 ? QC_SWEEP_WIDE_64 : 0) | (wide64_grad ? QC_SWEEP_WIDE_64_GRAD : 0),
+                               device, (wide ? 1 : 0) | (wide_stored ? 8 : 0) | (wide64 ? QC_SWEEP_WIDE_64 : 0) | (wide64_grad ? QC_SWEEP_WIDE_64_GRAD : 0) |
+                               (wide64_stored ? QC_SWEEP_WIDE_64_STORED : 0),
                                (stored_states ? 1 : 0, 0)))      # 8 = QC_SWEEP_WIDE_STORED
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_grad_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
@@ -926,20 +931,22 @@ end
 
 """
     rollout_sweep_parameter_gradient(init, controls, Î”t, G_drift, G_drives, G_pert, Î¸; scale=nothing, cols, goal, fid_kind=0,
-                                     subspace=nothing, squared=false, device=0, stored_states=false, wide=false, wide64_params=false)  ->  (fids, âˆ‡Î¸, âˆ‡c)
+                                     subspace=nothing, squared=false, device=0, stored_states=false, wide=false, wide64_stored=false, wide64_params=false)  ->  (fids, âˆ‡Î¸, âˆ‡c)
 
 The derivatives of the S fidelities of `rollout_sweep` with respect to the SYSTEMS (`qc_sweep_grad_params`): `âˆ‡Î¸[s, j]` = âˆ‚F_s/âˆ‚Î¸[s, j]
 (SÃ—p) and `âˆ‡c[s, k]` = âˆ‚F_s/âˆ‚scale[s, k] (SÃ—m; `scale = nothing`: taken at all ones), raw per-sample values from one backward walk.
 Scope and arguments as `rollout_sweep_gradient` (`stored_states = true`: open systems, as there).  `wide = true` sets
 `qc_sweep_desc.wide = QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS` (3): 2N â‰¤ 32 on the matrix cores, parameter gradients included.
 `wide64_params = true` (only with `wide`) adds `QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD | QC_SWEEP_WIDE_64_PARAMS` (11267 in all): closed
-systems with 32 < 2N â‰¤ 64, m â‰¤ 16 and at most 32 state columns in the "mfma64-sweep" form, parameter gradients included.
+systems with 32 < 2N â‰¤ 64, m â‰¤ 16 and at most 32 state columns in the "mfma64-sweep" form, parameter gradients included;
+`wide64_stored = true` (only with `wide64_params` and `stored_states`) adds `QC_SWEEP_WIDE_64_STORED` (262144): any generators there.
 UNTESTED here, like the rest of this file: no Julia runs where this library is built and tested.
 """
 function rollout_sweep_parameter_gradient(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Î”t::AbstractVector{Float64}, G_drift,
                                           G_drives, G_pert, Î¸::AbstractMatrix{Float64}; scale=nothing, cols::Int, goal, fid_kind::Int=0,
                                           subspace=nothing, squared::Bool=false, device::Int=0, stored_states::Bool=false, wide_stored::Bool=false, wide::Bool=false,
-                                          wide64_params::Bool=false)
+                                          wide64_stored::Bool=false, wide64_params::Bool=false)
+    (wide64_stored && !(wide64_params && stored_states)) && error("rollout_sweep_parameter_gradient: wide64_stored = true needs wide64_params = true and stored_states = true")
     (wide64_params && !wide) && error("rollout_sweep_parameter_gradient: wide64_params = true needs wide = true")
     n = size(G_drift, 1); N = n Ã· 2
     m, T = size(controls); p = length(G_pert); S = size(Î¸, 1)
@@ -959,7 +966,8 @@ function rollout_sweep_parameter_gradient(init::AbstractVector{Float64}, control
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, fid_kind,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
                                squared ? 1 : 0, length(sub), pointer(g), isempty(sub) ? C_NULL : pointer(sub),
-                               device, (wide ? 3 : 0) | (wide_stored ? 8 : 0) | (wide64_params ? (QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD | QC_SWEEP_WIDE_64_PARAMS) : 0),
+                               device, (wide ? 3 : 0) | (wide_stored ? 8 : 0) | (wide64_params ? (QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD | QC_SWEEP_WIDE_64_PARAMS) : 0) |
+                               (wide64_stored ? QC_SWEEP_WIDE_64_STORED : 0),
                                (stored_states ? 1 : 0, 0)))      # 3 = QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS, 8 = QC_SWEEP_WIDE_STORED
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_grad_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)
@@ -980,7 +988,7 @@ end
 
 """
     rollout_sweep_pullback(init, controls, Î”t, G_drift, G_drives, G_pert, Î¸, CÌ„; scale=nothing, cols, params=false, device=0,
-                           wide=false, stored_states=false, wide_params=false, wide64=false, wide64_grad=false, wide64_params=false)  ->  (finals, âˆ‡a, âˆ‡Î”t, âˆ‡init[, âˆ‡Î¸, âˆ‡c])
+                           wide=false, stored_states=false, wide_params=false, wide64=false, wide64_grad=false, wide64_stored=false, wide64_params=false)  ->  (finals, âˆ‡a, âˆ‡Î”t, âˆ‡init[, âˆ‡Î¸, âˆ‡c])
 
 The pullback of `rollout_sweep` (`qc_sweep_vjp`): `CÌ„` is (2NÂ·cols)Ã—S, column s the cotangent of sample s's final state (the derivative
 of the caller's loss with respect to it, e.g. what `Zygote.pullback` hands to an `rrule`), and with Ï†_s = âŸ¨CÌ„[:, s], finals[:, s]âŸ© the
@@ -990,13 +998,15 @@ Served for closed systems (antisymmetric generators) with 2N â‰¤ 16 (`wide = tru
 `qc_sweep_desc.wide`, QC_SWEEP_WIDE_PARAMS), m â‰¤ 8 and at most 16
 state columns, with `stored_states = true` for any generators with 2N â‰¤ 16; no fidelity is involved.  `wide = true, wide64 = true,
 wide64_grad = true` (3073 in `qc_sweep_desc.wide`): closed systems with 32 < 2N â‰¤ 64, m â‰¤ 16 and at most 32 state columns in the
-"mfma64-sweep" form, there with `params` only if also `wide64_params = true` (bit 13, QC_SWEEP_WIDE_64_PARAMS: 11265).  Arguments as
+"mfma64-sweep" form, there with `params` only if also `wide64_params = true` (bit 13, QC_SWEEP_WIDE_64_PARAMS: 11265); `wide64_stored = true` (only with `wide64_grad` and `stored_states`; bit 18,
+QC_SWEEP_WIDE_64_STORED) serves any generators there by the stored-state walk.  Arguments as
 `rollout_sweep`.  UNTESTED here, like the rest of this file: no Julia runs where this library is built and tested.
 """
 function rollout_sweep_pullback(init::AbstractVector{Float64}, controls::AbstractMatrix{Float64}, Î”t::AbstractVector{Float64}, G_drift, G_drives,
                                 G_pert, Î¸::AbstractMatrix{Float64}, CÌ„::AbstractMatrix{Float64}; scale=nothing, cols::Int, params::Bool=false,
                                 device::Int=0, wide::Bool=false, stored_states::Bool=false, wide_stored::Bool=false, wide_params::Bool=false,
-                                wide64::Bool=false, wide64_grad::Bool=false, wide64_params::Bool=false)
+                                wide64::Bool=false, wide64_grad::Bool=false, wide64_stored::Bool=false, wide64_params::Bool=false)
+    (wide64_stored && !(wide64_grad && stored_states)) && error("rollout_sweep_pullback: wide64_stored = true needs wide64_grad = true and stored_states = true")
     (wide64_params && !wide64_grad) && error("rollout_sweep_pullback: wide64_params = true needs wide64_grad = true")
     (wide_params && !wide) && error("rollout_sweep_pullback: wide_params = true needs wide = true")
     (wide64 && !wide) && error("rollout_sweep_pullback: wide64 = true needs wide = true")
@@ -1020,7 +1030,8 @@ function rollout_sweep_pullback(init::AbstractVector{Float64}, controls::Abstrac
     GC.@preserve G0 Gd Gp begin
         desc = Ref(QCSweepDesc(T, m + 1, 0, m, N, 0.0, 0, m, cols == N ? 0 : cols, p, -1,
                                pointer(G0), m == 0 ? C_NULL : pointer(Gd), p == 0 ? C_NULL : pointer(Gp),
-                               0, 0, C_NULL, C_NULL, device, (wide ? 1 : 0) | (wide_params ? 2 : 0) | (wide_stored ? 8 : 0) | (wide64 ? QC_SWEEP_WIDE_64 : 0) | (wide64_grad ? QC_SWEEP_WIDE_64_GRAD : 0) | (wide64_params ? QC_SWEEP_WIDE_64_PARAMS : 0),
+                               0, 0, C_NULL, C_NULL, device, (wide ? 1 : 0) | (wide_params ? 2 : 0) | (wide_stored ? 8 : 0) | (wide64 ? QC_SWEEP_WIDE_64 : 0) | (wide64_grad ? QC_SWEEP_WIDE_64_GRAD : 0) | (wide64_params ? QC_SWEEP_WIDE_64_PARAMS : 0) |
+                               (wide64_stored ? QC_SWEEP_WIDE_64_STORED : 0),
                                (stored_states ? 1 : 0, 0)))
         ok = Ref{Int32}(0)
         rc = ccall((:qc_sweep_desc_vjp_supported, LIB[]), Cint, (Ref{QCSweepDesc}, Ref{Int32}), desc, ok)

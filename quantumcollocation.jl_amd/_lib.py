@@ -58,6 +58,7 @@ QC_SWEEP_WIDE_64_GRAD = 2048  # qc_sweep_desc.wide, bit 11 (only with bits 0 and
 QC_SWEEP_WIDE_64_PARAMS = 8192  # qc_sweep_desc.wide, bit 13 (only with bits 0, 10 and 11): the "mfma64-sweep" form serves parameter gradients and parameter cotangents
 QC_SWEEP_WIDE_64_TANGENT = 16384  # qc_sweep_desc.wide, bit 14 (only with bits 0 and 10): the "mfma64-sweep" form serves pushforwards, any generators, 2N x cols <= 2048
 QC_SWEEP_WIDE_64_NOISE = 65536  # qc_sweep_desc.wide, bit 16 (only with bits 0 and 10): the "mfma64-sweep" form serves noise-trajectory sweeps (their gradients with bit 11 as well)
+QC_SWEEP_WIDE_64_STORED = 262144  # qc_sweep_desc.wide, bit 18 (only with bits 0, 10 and 11): with QC_SWEEP_STORED_STATES the "mfma64-sweep" form serves reverse mode of any generators (stored-state walk, at most 32 state columns)
 QC_SWEEP_WIDE_64 = 1024  # qc_sweep_desc.wide, bit 10 (only with bit 0): 32 < 2N <= 64 with up to 16 drives on the matrix cores ("mfma64-sweep"; the forward sweep, derivatives only with bit 11)
 QC_SWEEP_STORED_STATES = 1  # qc_sweep_desc.reserved1[0]: reverse mode by the stored-state walk (open systems)
 QC_ROWS_STACKED = 0

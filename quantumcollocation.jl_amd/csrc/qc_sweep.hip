@@ -33,7 +33,9 @@
 // Bits 11 and 13 (QC_SWEEP_WIDE_64_GRAD, only with bit 10; QC_SWEEP_WIDE_64_PARAMS, only with bit 11) change nothing here either: they let
 // qc_sweep_grad* / qc_sweep_vjp*, and then their parameter outputs, serve that form (qc_sweep64_grad.hip).  Bit 14
 // (QC_SWEEP_WIDE_64_TANGENT, only with bit 10) likewise: it lets qc_sweep_jvp* serve that form (qc_sweep64_jvp.hip), any generators.  Bit 16
-// (QC_SWEEP_WIDE_64_NOISE, only with bit 10) likewise: it lets qc_sweep_noise_* serve that form (qc_sweep64_noise.hip).
+// (QC_SWEEP_WIDE_64_NOISE, only with bit 10) likewise: it lets qc_sweep_noise_* serve that form (qc_sweep64_noise.hip).  Bit 18
+// (QC_SWEEP_WIDE_64_STORED, only with bit 11) likewise: with reserved1[0] = QC_SWEEP_STORED_STATES it lets qc_sweep_grad* / qc_sweep_vjp* serve
+// that form by the stored-state walk, any generators (qc_sweep64_open_grad.hip).
 #include <math.h>
 #include <string.h>
 
@@ -273,12 +275,14 @@ int qc_sweep_validate_desc(const qc_sweep_desc* d) {
     // bit 13 (QC_SWEEP_WIDE_64_PARAMS) only together with bits 0, 10 and 11: each of those | 8192; bit 12 is not assigned
     // bit 14 (QC_SWEEP_WIDE_64_TANGENT) only together with bits 0 and 10 (not 11 or 13: nothing is reversed): each valid value that has both | 16384
     // bit 16 (QC_SWEEP_WIDE_64_NOISE) only together with bits 0 and 10 (none of 11, 13, 14 needed): each valid value that has both | 65536; bit 15 is not assigned
-    if ((d->wide & ~(QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS | QC_SWEEP_WIDE_STORED | QC_SWEEP_WIDE_TANGENT | QC_SWEEP_WIDE_NOISE | QC_SWEEP_WIDE_HESSIAN | QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD | QC_SWEEP_WIDE_64_PARAMS | QC_SWEEP_WIDE_64_TANGENT | QC_SWEEP_WIDE_64_NOISE)) != 0 ||
+    // bit 18 (QC_SWEEP_WIDE_64_STORED) only together with bits 0, 10 and 11, as bit 13: each valid value that has all three | 262144; bit 17 and everything from bit 19 up are not assigned
+    if ((d->wide & ~(QC_SWEEP_WIDE | QC_SWEEP_WIDE_PARAMS | QC_SWEEP_WIDE_STORED | QC_SWEEP_WIDE_TANGENT | QC_SWEEP_WIDE_NOISE | QC_SWEEP_WIDE_HESSIAN | QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD | QC_SWEEP_WIDE_64_PARAMS | QC_SWEEP_WIDE_64_TANGENT | QC_SWEEP_WIDE_64_NOISE | QC_SWEEP_WIDE_64_STORED)) != 0 ||
         (d->wide != 0 && !(d->wide & QC_SWEEP_WIDE)) || ((d->wide & QC_SWEEP_WIDE_64_GRAD) && !(d->wide & QC_SWEEP_WIDE_64)) ||
         ((d->wide & QC_SWEEP_WIDE_64_PARAMS) && !(d->wide & QC_SWEEP_WIDE_64_GRAD)) ||
+        ((d->wide & QC_SWEEP_WIDE_64_STORED) && !(d->wide & QC_SWEEP_WIDE_64_GRAD)) ||
         ((d->wide & QC_SWEEP_WIDE_64_TANGENT) && !(d->wide & QC_SWEEP_WIDE_64)) ||
         ((d->wide & QC_SWEEP_WIDE_64_NOISE) && !(d->wide & QC_SWEEP_WIDE_64)))
-        return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: wide must be 0 or QC_SWEEP_WIDE (1), alone or with QC_SWEEP_WIDE_PARAMS (2), QC_SWEEP_WIDE_STORED (8), QC_SWEEP_WIDE_TANGENT (16), QC_SWEEP_WIDE_NOISE (64) and / or QC_SWEEP_WIDE_HESSIAN (256): 0, 1, 3, 9, 11, 17, 19, 25 or 27, or one of those eight | 64, or one of the sixteen odd values | 256; or one of the thirty-two odd values | QC_SWEEP_WIDE_64 (1024); or one of those | QC_SWEEP_WIDE_64_GRAD (2048); or one of those | QC_SWEEP_WIDE_64_PARAMS (8192); or any of those that has QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_TANGENT (16384); or any of those that has QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_NOISE (65536)");
+        return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: wide must be 0 or QC_SWEEP_WIDE (1), alone or with QC_SWEEP_WIDE_PARAMS (2), QC_SWEEP_WIDE_STORED (8), QC_SWEEP_WIDE_TANGENT (16), QC_SWEEP_WIDE_NOISE (64) and / or QC_SWEEP_WIDE_HESSIAN (256): 0, 1, 3, 9, 11, 17, 19, 25 or 27, or one of those eight | 64, or one of the sixteen odd values | 256; or one of the thirty-two odd values | QC_SWEEP_WIDE_64 (1024); or one of those | QC_SWEEP_WIDE_64_GRAD (2048); or one of those | QC_SWEEP_WIDE_64_PARAMS (8192); or any of those that has QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_TANGENT (16384); or any of those that has QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_NOISE (65536); or any of those that has QC_SWEEP_WIDE_64_GRAD | QC_SWEEP_WIDE_64_STORED (262144)");
     if (d->reserved1[0] != 0 && d->reserved1[0] != QC_SWEEP_STORED_STATES)
         return qc_sweep_fail(nullptr, QC_ERR_INVALID, "qc_sweep: reserved1[0] must be 0 or QC_SWEEP_STORED_STATES (1)");
     return QC_OK;
@@ -380,6 +384,7 @@ extern "C" int qc_sweep_create(const qc_sweep_desc* d, qc_sweep** out) {
     h->mfma64 = qc_sweep_desc_form(d) == QC_SWEEP_FORM_64;
     h->wide64_grad = h->mfma64 && (d->wide & QC_SWEEP_WIDE_64_GRAD);
     h->wide64_par = h->wide64_grad && (d->wide & QC_SWEEP_WIDE_64_PARAMS);
+    h->wide64_stored = h->wide64_grad && (d->wide & QC_SWEEP_WIDE_64_STORED);
     h->wide64_tangent = h->mfma64 && (d->wide & QC_SWEEP_WIDE_64_TANGENT);
     h->wide64_noise = h->mfma64 && (d->wide & QC_SWEEP_WIDE_64_NOISE);
     h->wide_par = h->mfma32 && (d->wide & QC_SWEEP_WIDE_PARAMS);

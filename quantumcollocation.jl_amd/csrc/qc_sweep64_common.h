@@ -1,6 +1,6 @@
 // What the kernels of the "mfma64-sweep" form share (qc_sweep64.hip, the forward sweep with and without noise; qc_sweep64_grad.hip and
 // qc_sweep64_noise.hip, the backward walks, which must form the same generator and choose the same number of squarings as the forward
-// step; qc_sweep64_jvp.hip, the pushforward): the workgroup's shape and its LDS matrices, the element a thread owns, the sample's base
+// step; qc_sweep64_open_grad.hip, the stored-state walk and its store kernel; qc_sweep64_jvp.hip, the pushforward): the workgroup's shape and its LDS matrices, the element a thread owns, the sample's base
 // matrix, the lane's coefficient source, the interval's generator, the squaring rule over the workgroup, the tile product out of LDS, the
 // pieces of the walk (its LDS map, the state load, the timestep derivative, the exponential pair with its barriers, the 16-wave sum).
 // The launch is qc_sweep64_launch.h's.  Constants, table, wave sum, rule's tail and chunk range are those of qc_sweep_common.h.  The

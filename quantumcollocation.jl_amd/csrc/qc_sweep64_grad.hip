@@ -36,7 +36,7 @@
 //
 // MFMAs per interval and workgroup, nct = ceil(nc / 16):  8 Horner steps x (16 x (32 + 4 nct) + 4 nct x 16) + sq x 16 x 48 + 16 x 16 (ZT)
 // + 8 nct x 16 (x, lambda) = (4352 + 1152 nct) + 768 sq, against the forward kernel's (9 + sq) x 256 = 2304 + 256 sq.
-// No atomics, sums in a fixed order: repeated calls give the same bits.  The stored-state walk and Hessian products are
+// No atomics, sums in a fixed order: repeated calls give the same bits.  The stored-state walk is qc_sweep64_open_grad.hip's (QC_SWEEP_WIDE_64_STORED), on the same shared pieces; Hessian products are
 // not served in this form; pushforwards are qc_sweep64_jvp.hip's (QC_SWEEP_WIDE_64_TANGENT), noise sweeps qc_sweep64_noise.hip's (QC_SWEEP_WIDE_64_NOISE), a second walk on the same shared pieces.
 //
 // The parameter flavour <true> (handles with QC_SWEEP_WIDE_64_PARAMS; qc_sweep_grad_params*, grad_theta / grad_scale of qc_sweep_vjp*) adds,

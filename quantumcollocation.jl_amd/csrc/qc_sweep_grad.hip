@@ -15,7 +15,7 @@
 //   * <lambda, G x> = -sum (lambda x^T)_ab G_ba, so the timestep derivative is an inner product of tiles already in registers.
 // Everything else returns QC_ERR_UNSUPPORTED (Lindblad generators need stored forward states) -- unless the descriptor opts in with
 // reserved1[0] = QC_SWEEP_STORED_STATES: such handles are routed to the stored-state walk of qc_sweep_open_grad.hip (wide handles that also
-// set QC_SWEEP_WIDE_STORED: of qc_sweep32_open_grad.hip), whatever their generators, behind the same totals, seed (with lambda = g_r for the density fidelity) and reductions; qc_sweep_reverse_scope decides.
+// set QC_SWEEP_WIDE_STORED: of qc_sweep32_open_grad.hip; "mfma64-sweep" handles that also set QC_SWEEP_WIDE_64_STORED: of qc_sweep64_open_grad.hip), whatever their generators, behind the same totals, seed (with lambda = g_r for the density fidelity) and reductions; qc_sweep_reverse_scope decides.
 // Descriptors with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 | QC_SWEEP_WIDE_64_GRAD extend the closed scope to the "mfma64-sweep" form, 32 < 2N <= 64, with
 // states of up to 32 columns: the seed at ld = 64 and the walk of qc_sweep64_grad.hip, the same reductions; parameter gradients there only for descriptors that also set QC_SWEEP_WIDE_64_PARAMS (the flavour <true> of that
 // file's walk, then qc_sweep_par_reduce_kernel of this one).
@@ -400,12 +400,19 @@ bool qc_sweep_closed_scope(const qc_sweep_desc* d, std::string* why) {
 
 // Reverse mode of a descriptor: reserved1[0] chooses the walk.  0: the closed walk and its scope above.  QC_SWEEP_STORED_STATES: the
 // stored-state walk of qc_sweep_open_grad.hip, which asks nothing of the generators: the "mfma16-sweep" form, at most 16 state columns;
-// the "mfma32-sweep" form only for descriptors that opt in with QC_SWEEP_WIDE_STORED (the 2 x 2-tile walk of qc_sweep32_open_grad.hip).
+// the "mfma32-sweep" form only for descriptors that opt in with QC_SWEEP_WIDE_STORED (the 2 x 2-tile walk of qc_sweep32_open_grad.hip);
+// the "mfma64-sweep" form only for descriptors that opt in with QC_SWEEP_WIDE_64_STORED (the 4 x 4-tile walk of qc_sweep64_open_grad.hip, at
+// most 32 state columns).
 bool qc_sweep_reverse_scope(const qc_sweep_desc* d, std::string* why) {
     if (d->reserved1[0] != QC_SWEEP_STORED_STATES) return qc_sweep_closed_scope(d, why);
     const qc_sweep_form form = qc_sweep_desc_form(d);
     if (form == QC_SWEEP_FORM_PER_SAMPLE) { *why = qc_sweep_per_sample_why(d); return false; }
-    if (form == QC_SWEEP_FORM_64) { *why = qc_sweep_form64_unserved(d, "stored-state gradients"); return false; }
+    if (form == QC_SWEEP_FORM_64) {      // only with QC_SWEEP_WIDE_64_STORED (which needs QC_SWEEP_WIDE_64_GRAD): the 4 x 4-tile walk of qc_sweep64_open_grad.hip
+        if (!(d->wide & QC_SWEEP_WIDE_64_STORED)) { *why = qc_sweep_form64_unserved(d, "stored-state gradients"); return false; }
+        const int nc64 = d->state_cols == 0 ? d->N : d->state_cols;
+        if (nc64 > 32) { *why = "states of more than 32 columns are not served in the mfma64-sweep form (2N = " + std::to_string(2 * d->N) + ", state_cols = " + std::to_string(nc64) + ")"; return false; }
+        return true;
+    }
     if (form == QC_SWEEP_FORM_32 && !(d->wide & QC_SWEEP_WIDE_STORED)) { *why = "stored-state gradients are not served in the mfma32-sweep form"; return false; }
     const int nc = d->state_cols == 0 ? d->N : d->state_cols;
     if (nc > 16) { *why = "states of more than 16 columns are not served (state_cols = " + std::to_string(nc) + ")"; return false; }
@@ -548,7 +555,12 @@ static int qc_sweep_grad_launch(qc_sweep* h, const char* who, const double* dZ, 
     if (want_par) QC_SIDE_HIP(h, slot, h->grow(h->dPart, (size_t)S * n_chunks * (p + m)));
     if (h->stored && (want_grad || want_par)) QC_SIDE_HIP(h, slot, h->grow(h->dXall, (size_t)S * (size_t)n_int * h->ns));
     qc_sweep_launch_fid_seed(h, S, n_chunks, dinit, dfids, st);
-    if (h->mfma64 && h->wide64_grad) {      // the 4 x 4-tile form: its own walk (qc_sweep64_grad.hip), then the reductions below
+    if (h->mfma64 && h->stored && h->wide64_stored) {      // the 4 x 4-tile stored-state walk (qc_sweep64_open_grad.hip), whatever the generators
+        if ((want_grad || want_par) &&      // want_par: only on handles with QC_SWEEP_WIDE_64_PARAMS (the entry points refuse the others)
+            (rc = qc_sweep64_open_launch_walk(h, dZ, dinit, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, h->dPart.p, st)))
+            return rc;
+        if (want_par) qc_sweep_launch_par_reduce(h, S, n_chunks, dgrad_theta, dgrad_scale, st);
+    } else if (h->mfma64 && h->wide64_grad) {      // the 4 x 4-tile form: its own walk (qc_sweep64_grad.hip), then the reductions below
         if ((want_grad || want_par) &&      // want_par: only on handles with QC_SWEEP_WIDE_64_PARAMS (the entry points refuse the others)
             (rc = qc_sweep64_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, h->dPart.p, st)))
             return rc;

@@ -14,6 +14,7 @@ struct qc_sweep : qc_side {
     bool mfma64 = false;         // the 4 x 4-tile form of a descriptor with QC_SWEEP_WIDE | QC_SWEEP_WIDE_64 ("mfma64-sweep", qc_sweep64.hip): the forward sweep, and with wide64_grad its closed adjoint; mfma is set as well
     bool wide64_grad = false;    // mfma64 and wide has QC_SWEEP_WIDE_64_GRAD: gradients and pullbacks of closed systems are served (qc_sweep64_grad.hip)
     bool wide64_par = false;     // wide64_grad and wide has QC_SWEEP_WIDE_64_PARAMS: parameter gradients and cotangents are served (the flavour <true> of qc_sweep64_grad.hip's walk)
+    bool wide64_stored = false;  // wide64_grad and wide has QC_SWEEP_WIDE_64_STORED: with `stored`, reverse mode by the 4 x 4-tile stored-state walk, any generators (qc_sweep64_open_grad.hip)
     bool wide64_tangent = false; // mfma64 and wide has QC_SWEEP_WIDE_64_TANGENT: pushforwards are served, any generators, ns <= 2048 (qc_sweep64_jvp.hip)
     bool wide64_noise = false;   // mfma64 and wide has QC_SWEEP_WIDE_64_NOISE: noise trajectories are served, any generators; their gradients with wide64_grad (qc_sweep64_noise.hip)
     bool wide_par = false;       // mfma32 and wide has QC_SWEEP_WIDE_PARAMS: parameter gradients and cotangents are served (qc_sweep32_grad.hip)
@@ -150,6 +151,12 @@ __attribute__((visibility("hidden"))) int qc_sweep64_launch_totals(qc_sweep* h, 
 // qc_sweep_launch_par_reduce behind it.  QC_OK or the launch's code
 __attribute__((visibility("hidden"))) int qc_sweep64_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk,
                                                                   int64_t n_chunks, double* gs, bool par, double* part, hipStream_t st);
+// "mfma64-sweep" handles with `stored` and `wide64_stored` (qc_sweep64_open_grad.hip): qc_sweep64_open_store_kernel writes x_t of every knot
+// 0 .. T-2 into h->dXall (grown by the caller) from `dinit` and the chunk ends of h->dXs, then qc_sweep64_open_grad_kernel<par> walks every chunk
+// backwards from h->dLs; arguments, outputs and what the caller runs behind it as qc_sweep64_launch_walk.  QC_OK or a launch's code
+__attribute__((visibility("hidden"))) int qc_sweep64_open_launch_walk(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta,
+                                                                       const double* dscale, int64_t chunk, int64_t n_chunks, double* gs, bool par, double* part,
+                                                                       hipStream_t st);
 // "mfma32-sweep" gradients (qc_sweep32_grad.hip): the backward walk qc_sweep32_grad_kernel<false> (gs: S x (T-1) x nd), or with `par` the
 // parameter flavour <true> (gs may be NULL) and qc_sweep_par_reduce_kernel out of h->dPart; scratch is the caller's
 void qc_sweep32_launch_walk(qc_sweep* h, const double* dZ, int64_t S, const double* dtheta, const double* dscale, int64_t chunk, int64_t n_chunks,
@@ -170,7 +177,8 @@ void qc_sweep_open_launch_walk(qc_sweep* h, const double* dZ, const double* dini
 void qc_sweep32_open_launch_walk(qc_sweep* h, const double* dZ, const double* dinit, int64_t S, const double* dtheta, const double* dscale,
                                  int64_t chunk, int64_t n_chunks, double* gs, bool par, double* dgrad_theta, double* dgrad_scale, hipStream_t st);
 // what reverse mode asks of a descriptor: reserved1[0] = 0, the closed scope; QC_SWEEP_STORED_STATES, the "mfma16-sweep" form (or the
-// "mfma32-sweep" form of a descriptor whose wide has QC_SWEEP_WIDE_STORED) and at most 16 state columns, any generators.  qc_sweep_closed_grad_scope: the gradient's scope of reserved1[0] = 0, for the noise gradient.
+// "mfma32-sweep" form of a descriptor whose wide has QC_SWEEP_WIDE_STORED) and at most 16 state columns, any generators; the "mfma64-sweep" form
+// of a descriptor whose wide has QC_SWEEP_WIDE_64_GRAD | QC_SWEEP_WIDE_64_STORED and at most 32 state columns, any generators.  qc_sweep_closed_grad_scope: the gradient's scope of reserved1[0] = 0, for the noise gradient.
 bool qc_sweep_reverse_scope(const qc_sweep_desc* d, std::string* why);
 bool qc_sweep_closed_grad_scope(const qc_sweep_desc* d, std::string* why);
 // device-free: is this (valid) descriptor inside the gradient's scope?  `why` receives the reason when it is not.

@@ -25,7 +25,8 @@
 //
 // Scope: the gradient's without its two fidelity conditions (qc_sweep_vjp_scope below is qc_sweep_reverse_scope: the closed scope, or with
 // reserved1[0] = QC_SWEEP_STORED_STATES the stored-state walk's, and then launch 3 is qc_sweep_open_launch_walk of qc_sweep_open_grad.hip or,
-// on an "mfma32-sweep" handle made with QC_SWEEP_WIDE_STORED, qc_sweep32_open_launch_walk of qc_sweep32_open_grad.hip).
+// on an "mfma32-sweep" handle made with QC_SWEEP_WIDE_STORED, qc_sweep32_open_launch_walk of qc_sweep32_open_grad.hip; on an "mfma64-sweep"
+// handle made with QC_SWEEP_WIDE_64_GRAD | QC_SWEEP_WIDE_64_STORED, qc_sweep64_open_launch_walk of qc_sweep64_open_grad.hip).
 #include <math.h>
 
 #include <string>
@@ -188,7 +189,12 @@ static int qc_sweep_vjp_launch(qc_sweep* h, const char* who, const double* dZ, c
         QC_SIDE_HIP(h, slot, hipFuncSetAttribute(reinterpret_cast<const void*>(&qc_sweep64_cot_seed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(seed, dim3((unsigned)S), dim3(kCotT), lds, st, F, (const double*)h->dTot.p, dinit, dcot, h->dXs.p, h->dLs.p, dfinals,
                        dgrad_init);
-    if (h->mfma64 && h->wide64_grad) {      // the 4 x 4-tile walk of qc_sweep64_grad.hip behind the seed at ld = 64
+    if (h->mfma64 && h->stored && h->wide64_stored) {      // the 4 x 4-tile stored-state walk of qc_sweep64_open_grad.hip behind the same seed
+        if ((want_grad || want_par) &&      // want_par: only on handles with QC_SWEEP_WIDE_64_PARAMS (vjp_check refuses the others)
+            (rc = qc_sweep64_open_launch_walk(h, dZ, dinit, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, h->dPart.p, st)))
+            return rc;
+        if (want_par) qc_sweep_launch_par_reduce(h, S, n_chunks, dgrad_theta, dgrad_scale, st);
+    } else if (h->mfma64 && h->wide64_grad) {      // the 4 x 4-tile walk of qc_sweep64_grad.hip behind the seed at ld = 64
         if ((want_grad || want_par) &&      // want_par: only on handles with QC_SWEEP_WIDE_64_PARAMS (vjp_check refuses the others)
             (rc = qc_sweep64_launch_walk(h, dZ, S, dtheta, dscale, chunk, n_chunks, want_grad ? gsamp : nullptr, want_par, h->dPart.p, st)))
             return rc;

@@ -744,13 +744,15 @@ class SweepInfidelityObjective:
                 32 < 2N <= 64 (17 .. 32 levels: three coupled transmons, 5 qubits) in the "mfma64-sweep" form
     wide64_params  as `RolloutSweep` (only with `wide64_grad`): the handle also serves `param_grad` and parameter cotangents there
     wide64_noise  as `RolloutSweep` (only with `wide64`): what `SweepNoiseInfidelityObjective` needs in the "mfma64-sweep" form; nothing here reads it
+    wide64_stored  as `RolloutSweep` (only with `wide64_grad` and `stored_states`): the stored-state walk in the "mfma64-sweep" form, e.g. a
+                five-level Lindblad model (N = 25) with `goal_ket`
     goal_ket    density component only: [Re psi; Im psi] (2 levels entries) of the pure state the fidelity compares with"""
     _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
 
     def __init__(self, traj: NamedTrajectory, system, perturbations, theta, scale=None, weights=None, state_name: str = "Ũ⃗",
                  control_name: str = "a", subspace=None, form: str = "abs", device: int = 0, wide: bool = False,
                  stored_states: bool = False, goal_ket=None, wide_stored: bool = False, wide_noise: bool = False, wide64_noise: bool = False,
-                 wide64: bool = False, wide64_grad: bool = False, wide64_params: bool = False):
+                 wide64: bool = False, wide64_stored: bool = False, wide64_grad: bool = False, wide64_params: bool = False):
         from .rollouts import RolloutSweep
         self._sweep = None
         if state_name not in traj.components:
@@ -803,7 +805,7 @@ class SweepInfidelityObjective:
                           off_a=traj.offset(control_name), off_dt=traj.offset(traj.timestep) if free else -1,
                           dt_fixed=None if free else float(traj.timestep), global_dim=traj.global_dim, device=device, wide=wide,
                           stored_states=stored_states, wide_stored=wide_stored, wide_noise=wide_noise, wide64=wide64, wide64_grad=wide64_grad,
-                          wide64_params=wide64_params, wide64_noise=wide64_noise)
+                          wide64_params=wide64_params, wide64_noise=wide64_noise, wide64_stored=wide64_stored)
         self._sweep = sw
         self.stored_states = sw.stored_states
         self.wide_stored = sw.wide_stored
@@ -934,13 +936,15 @@ class SweepFinalStateObjective:
                 `hessian_times` raises the handle's reason)
     wide64_tangent  as `RolloutSweep` (only with `wide64`): the pushforward in the "mfma64-sweep" form, so that `gauss_newton_times` is
                 served there beside the gradients of `wide64_grad` (2N x cols <= 2048); `hessian_times` still raises
-    wide64_params  as `RolloutSweep` (only with `wide64_grad`): the handle also serves `param_grad` and parameter cotangents there"""
+    wide64_params  as `RolloutSweep` (only with `wide64_grad`): the handle also serves `param_grad` and parameter cotangents there
+    wide64_stored  as `RolloutSweep` (only with `wide64_grad` and `stored_states`): the stored-state walk in the "mfma64-sweep" form, which
+                serves open systems there (gradients; `gauss_newton_times` with `wide64_tangent` as well; `hessian_times` still raises)"""
     _ALIASES = {"∇L": "grad_L", "∂²L": "hess_L", "∂²L_structure": "hess_structure"}
 
     def __init__(self, traj: NamedTrajectory, system, perturbations, theta, loss, scale=None, state_name="Ũ⃗", control_name: str = "a",
                  device: int = 0, wide: bool = False, stored_states: bool = False, wide_stored: bool = False, wide_tangent: bool = False,
-                 wide_hessian: bool = False, wide64: bool = False, wide64_grad: bool = False, wide64_tangent: bool = False,
-                 wide64_params: bool = False):
+                 wide_hessian: bool = False, wide64: bool = False, wide64_stored: bool = False, wide64_grad: bool = False,
+                 wide64_tangent: bool = False, wide64_params: bool = False):
         from .rollouts import RolloutSweep, _sweep_samples
         self._sweep = None
         if not callable(loss):
@@ -968,7 +972,7 @@ class SweepFinalStateObjective:
                           off_dt=traj.offset(traj.timestep) if free else -1, dt_fixed=None if free else float(traj.timestep),
                           global_dim=traj.global_dim, device=device, wide=wide, stored_states=stored_states, wide_stored=wide_stored,
                           wide_tangent=wide_tangent, wide_hessian=wide_hessian, wide64=wide64, wide64_grad=wide64_grad,
-                          wide64_tangent=wide64_tangent, wide64_params=wide64_params)
+                          wide64_tangent=wide64_tangent, wide64_params=wide64_params, wide64_stored=wide64_stored)
         self._sweep = sw
         self.wide_hessian = sw.wide_hessian
         self.stored_states = sw.stored_states

@@ -268,16 +268,26 @@ class RolloutSweep:
                    also need `wide64_grad` and its scope (a closed system, at most 32 state columns, a unitary or ket fidelity);
                    without it they refuse with the gradient's reason.  At zero noise the outputs carry the bits of `eval` / `grad`
                    on the same handle.  `hvp` and `stored_states` still refuse there.  Without it the noise sweeps refuse there,
-                   as they did; nothing else changes, and nothing changes at 2N <= 32."""
+                   as they did; nothing else changes, and nothing changes at 2N <= 32.
+    wide64_stored  True (only with `wide64_grad` and `stored_states`): an "mfma64-sweep" handle serves the stored-state walk too, on
+                   4 x 4 tiles -- ANY generators with at most 32 state columns: a five-level Lindblad model with the "density"
+                   fidelity (N = 25, 2N = 50), 17 .. 32 levels with a non-Hermitian Hamiltonian.  `grad`, `vjp`, their device forms
+                   and the backward rule of `finals_autograd` take that walk whatever the generators; `param_grad` and the `params`
+                   of `vjp` there also need `wide64_params`.  The device buffer is S x (T-1) x 2N x cols doubles: 50 a knot for the
+                   five-level density operator, 432 for eight columns at 27 levels.  `hvp` (not served in this form), `noise_grad`
+                   of open systems and more than 32 state columns still refuse.  Without it `stored_states` refuses there, as it
+                   did; nothing else changes, and nothing changes at 2N <= 32."""
 
     def __init__(self, system, perturbations, T: int, cols: Optional[int] = None, goal=None, fid_kind=None, subspace=None,
                  fid_form: int = _lib.QC_FID_FORM_ABS, zdim: Optional[int] = None, off_a: int = 0, off_dt: Optional[int] = None,
                  dt_fixed: Optional[float] = None, global_dim: int = 0, device: int = 0, wide: bool = False,
                  stored_states: bool = False, wide_params: bool = False, wide_stored: bool = False, wide_tangent: bool = False,
                  wide_noise: bool = False, wide_hessian: bool = False, wide64: bool = False, wide64_noise: bool = False,
-                 wide64_grad: bool = False, wide64_tangent: bool = False, wide64_params: bool = False):
+                 wide64_stored: bool = False, wide64_grad: bool = False, wide64_tangent: bool = False, wide64_params: bool = False):
         self._h = None
         flags = (   # (keyword, given, its bit of qc_sweep_desc.wide, what it needs, the refusal without that)
+            ("wide64_stored", wide64_stored, _lib.QC_SWEEP_WIDE_64_STORED, wide64_grad and stored_states,
+             "wide64_stored=True needs wide64_grad=True and stored_states=True"),
             ("wide64_params", wide64_params, _lib.QC_SWEEP_WIDE_64_PARAMS, wide64_grad, "wide64_params=True needs wide64_grad=True"),
             ("wide64_grad", wide64_grad, _lib.QC_SWEEP_WIDE_64_GRAD, wide64, "wide64_grad=True needs wide64=True"),
             ("wide64_tangent", wide64_tangent, _lib.QC_SWEEP_WIDE_64_TANGENT, wide64, "wide64_tangent=True needs wide64=True"),
@@ -346,6 +356,15 @@ class RolloutSweep:
     @wide64_grad.setter
     def wide64_grad(self, given):
         self._wide64_grad = bool(given)
+
+    @property
+    def wide64_stored(self) -> bool:
+        """Whether the handle was made with `wide64_stored` (kept outside the instance's public flags, as `wide64_grad` is)."""
+        return self._wide64_stored
+
+    @wide64_stored.setter
+    def wide64_stored(self, given):
+        self._wide64_stored = bool(given)
 
     @property
     def wide64_params(self) -> bool:
@@ -502,7 +521,7 @@ class RolloutSweep:
     def grad_supported(self) -> bool:
         """Does `grad` serve this handle?  (`qc_sweep_desc_grad_supported`: the MFMA form, a unitary or ket fidelity, at most 16
         state columns, antisymmetric generators; with `stored_states` the "mfma16-sweep" form -- with `wide_stored` the "mfma32-sweep"
-        form as well --, any fidelity, any generators.)
+        form as well, with `wide64_grad` and `wide64_stored` the "mfma64-sweep" form with at most 32 state columns --, any fidelity, any generators.)
         `grad_unsupported_reason` says why not."""
         return self._scope(_lib.lib.qc_sweep_desc_grad_supported)[0]
 
@@ -573,7 +592,7 @@ class RolloutSweep:
     @property
     def vjp_supported(self) -> bool:
         """Does `vjp` serve this handle?  (`qc_sweep_desc_vjp_supported`: the MFMA forms, at most 16 state columns, antisymmetric
-        generators; with `stored_states` the "mfma16-sweep" form (with `wide_stored`: or "mfma32-sweep") and any generators; any
+        generators; with `stored_states` the "mfma16-sweep" form (with `wide_stored`: or "mfma32-sweep"; with `wide64_grad` and `wide64_stored`: or "mfma64-sweep", at most 32 columns) and any generators; any
         fidelity or none.)
         `vjp_unsupported_reason` says why not."""
         return self._scope(_lib.lib.qc_sweep_desc_vjp_supported)[0]
@@ -952,15 +971,17 @@ def rollout_noise_sweep(init, controls, dts, system, perturbations, noise, theta
 def rollout_sweep_parameter_gradient(init, controls, dts, system, perturbations, theta, scale=None, cols: Optional[int] = None, goal=None,
                                      fid_kind="unitary", subspace=None, device: int = 0, fid_form: int = _lib.QC_FID_FORM_ABS,
                                      stored_states: bool = False, wide: bool = False, wide_stored: bool = False, wide64: bool = False,
-                                     wide64_grad: bool = False, wide64_params: bool = False):
+                                     wide64_stored: bool = False, wide64_grad: bool = False, wide64_params: bool = False):
     """(fids, grad_theta, grad_scale) of S rollouts under the perturbed systems: the fidelities of `rollout_sweep` and their derivatives
     with respect to theta (S x len(perturbations)) and scale (S x n_drives; None: taken at all ones).  Arguments as `rollout_sweep`;
     `stored_states=True` serves open systems (`RolloutSweep`); `wide=True` serves 16 < 2N <= 32 on the matrix cores (the handle is made
     with `wide` and `wide_params`); all three of `wide`, `stored_states` and `wide_stored` serve open systems there (wide = 11);
-    all four of `wide`, `wide64`, `wide64_grad` and `wide64_params` serve closed systems of 32 < 2N <= 64 ("mfma64-sweep")."""
+    all four of `wide`, `wide64`, `wide64_grad` and `wide64_params` serve closed systems of 32 < 2N <= 64 ("mfma64-sweep"), and with
+    `stored_states` and `wide64_stored` as well open systems there."""
     return _one_shot(RolloutSweep.param_grad, init, controls, dts, system, perturbations, (theta, scale), cols, goal=goal, fid_kind=fid_kind,
                      subspace=subspace, fid_form=fid_form, device=device, stored_states=stored_states, wide=wide, wide_params=wide,
-                     wide_stored=wide_stored, wide64=wide64, wide64_grad=wide64_grad, wide64_params=wide64_params)
+                     wide_stored=wide_stored, wide64=wide64, wide64_grad=wide64_grad, wide64_params=wide64_params,
+                     wide64_stored=wide64_stored)
 
 
 def _traj_dts(traj):
